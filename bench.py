@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — MCL update cycles/sec (motion + sensor + resample), N particles x 1080 beams (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full `Amcl::update` cycle (amcl_core.hpp:165-201): DifferentialDriveModel propagation,
@@ -12,9 +12,14 @@ step uploads one 1080-point scan (17 KB) and downloads the estimate, as the refe
 With --gpus N the particle set is sharded N ways (1M per rank, weak scaling) behind one logical filter; `value` is the whole
 job's rate in units of a 1M-particle cycle: N x that filter's cycle rate (`config.filter_cycles_per_s`).
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` for the dominant kernel
-(likelihood-field reweight, HIP-event timed on the library's stream) and `cpu_baseline` (the oracle, a CPU
-restatement of the reference, timed on this host on a bounded sample).
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (wall milliseconds of one
+timed step) and the configuration.  A plain run does only that: set-up, warm-up, the timed steps, the outputs, the line.
+--dump-outputs DIR writes what the last timed step returned to its caller - the estimate: DIR/pose.npy (cos, sin, x, y) and
+DIR/covariance.npy (3 x 3), float64 - for comparing two builds output for output (the inputs are seeded: same arguments, same
+inputs).  --full adds everything else behind the timed region: repeat windows, a per-stage pass, `verified` (the estimates
+against the true poses, sampled weights against the oracle), `roofline` for the dominant kernel (likelihood-field reweight,
+HIP-event timed on the library's stream, counters from rocprofv3 passes) and `roofline_by_kernel`, the other configurations
+(`configs`) and `cpu_baseline` (the oracle, a CPU restatement of the reference, timed on this host on a bounded sample).
 """
 from __future__ import annotations
 
@@ -566,16 +571,23 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--particles", type=int, default=1_000_000, help="particles per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the 10M / beam / dispersed configurations (reported beside the metric)")
-    ap.add_argument("--windows", type=int, default=5, help="repeated timing windows of --steps cycles behind the timed region")
-    ap.add_argument("--stage-steps", type=int, default=6, help="cycles of the per-stage breakdown pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the estimate of the last timed step as DIR/pose.npy and DIR/covariance.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: repeat windows, per-stage pass, verification, roofline "
+                         "(with in-run rocprofv3 counter passes), the other configurations, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="(--full) skip the 10M / beam / dispersed configurations (reported beside the metric)")
+    ap.add_argument("--windows", type=int, default=5, help="(--full) repeated timing windows of --steps cycles behind the timed region")
+    ap.add_argument("--stage-steps", type=int, default=6, help="(--full) cycles of the per-stage breakdown pass")
     ap.add_argument("--config4-particles", type=int, default=8_000_000,
-                    help="particles per GPU of the BASELINE configs[3] entry that several ranks add to the line (8M = the configuration; tests run it smaller)")
+                    help="(--full) particles per GPU of the BASELINE configs[3] entry that several ranks add to the line (8M = the configuration; tests run it smaller)")
     ap.add_argument("--sharded", action="store_true", help="use the sharded driver even with one GPU (measures its overhead)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 counter passes behind the timed region (the line then quotes the tracked profiles)")
+    ap.add_argument("--no-pmc", action="store_true", help="(--full) skip the in-run rocprofv3 counter passes behind the timed region (the line then quotes the tracked profiles)")
     ap.add_argument("--pmc-child", nargs="?", const="lf", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.pmc_child:
         pmc_child(args.pmc_child)
         return
@@ -610,14 +622,18 @@ def main():
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
 
-    import __graft_entry__ as entry
     if rank == 0:
-        entry.build()
+        if args.full:  # (the oracle as well: verified and cpu_baseline use it)
+            import __graft_entry__ as entry
+            entry.build()
+        else:
+            from beluga_amd import build as mcl_build
+            mcl_build.build()  # (nothing to do where build() has run)
     if world > 1:
         dist.barrier()
     from beluga_amd.amcl import AmclParams, DifferentialDriveModelParam, LikelihoodFieldModelParam, OccupancyGrid, se2_from_xytheta
 
-    steps_total = args.warmup + args.steps * (1 + args.windows) + args.stage_steps
+    steps_total = args.warmup + args.steps + ((args.steps * args.windows + args.stage_steps) if args.full else 0)
     cells, truth, odoms, scans, true_poses = make_workload(steps_total)
     grid = OccupancyGrid(cells, RESOLUTION, origin=se2_from_xytheta(ORIGIN[0], ORIGIN[1], 0.0))
     n_local = args.particles
@@ -682,12 +698,13 @@ def main():
     controls = [se2_from_xytheta(*o) for o in odoms]
     for c in range(args.warmup):
         assert filt.update(controls[c], scans[c]) is not None
-    # Timed region: exactly `steps` update cycles.  Only the dominant kernel carries HIP events here (two records per cycle:
-    # an event record costs ~5 us of stream time); the per-stage breakdown comes from a separate pass below.
-    filt.profile_enable(1)
-    filt.profile_read(reset=True)
+    # Timed region: exactly `steps` update cycles.  With --full the dominant kernel carries HIP events here for the roofline (two
+    # records in every 4th cycle: an event record costs ~5 us of stream time); the per-stage breakdown comes from a separate pass below.
+    if args.full:
+        filt.profile_enable(1)
+        filt.profile_read(reset=True)
     sync_all()
-    patch_before = (filt.counter("lf_patch_groups_planned"), filt.counter("lf_patch_groups_through")) if hasattr(filt, "counter") else None
+    patch_before = (filt.counter("lf_patch_groups_planned"), filt.counter("lf_patch_groups_through")) if (args.full and hasattr(filt, "counter")) else None
     library_comm = use_sharded and type(filt).__name__ == "Amcl"  # (the torch.distributed driver is beluga_amd.sharded.ShardedAmcl)
     comm_before = (filt.counter("comm_bytes_out"), filt.counter("comm_collectives"), filt.counter("comm_host_syncs")) if library_comm else None
     timed_estimates = []
@@ -702,7 +719,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    prof = filt.profile_read(reset=True)
+    if args.dump_outputs and rank == 0:  # what the last timed update() returned to its caller: the estimate (every rank gets the same one)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "pose.npy"), np.asarray(est[0], dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "covariance.npy"), np.asarray(est[1], dtype=np.float64))
     collective = None
     if comm_before is not None:
         # what the communicator moved in the timed region, from the library's own counters: the driver's check that RCCL ran over
@@ -717,119 +737,59 @@ def main():
     elif use_sharded:
         collective = {"backend": f"torch.distributed ({backend}) driver, beluga_amd/sharded.py", "ranks_seen": dist.get_world_size(),
                       "bytes_out_per_rank_per_cycle": None}
-    patch_after = (filt.counter("lf_patch_groups_planned"), filt.counter("lf_patch_groups_through")) if hasattr(filt, "counter") else None
-    # Repeated windows of the same length right behind the timed region (same filter, the trajectory continues): the spread
-    # says how much a single 20-step sample can be trusted.
-    window_rates = []
-    c = args.warmup + args.steps
-    for _ in range(args.windows):
-        sync_all()
-        w0 = time.perf_counter()
-        for _k in range(args.steps):
+    if args.full:
+        prof = filt.profile_read(reset=True)
+        patch_after = (filt.counter("lf_patch_groups_planned"), filt.counter("lf_patch_groups_through")) if hasattr(filt, "counter") else None
+        # Repeated windows of the same length right behind the timed region (same filter, the trajectory continues): the spread
+        # says how much a single 20-step sample can be trusted.
+        window_rates = []
+        c = args.warmup + args.steps
+        for _ in range(args.windows):
+            sync_all()
+            w0 = time.perf_counter()
+            for _k in range(args.steps):
+                assert filt.update(controls[c], scans[c]) is not None
+                c += 1
+            sync_all()
+            window_rates.append(args.steps / (time.perf_counter() - w0))
+        # Per-stage breakdown (events around every stage; these cycles run ~40 us slower and are not part of any rate above).
+        filt.profile_enable(2)
+        filt.profile_read(reset=True)
+        for _k in range(args.stage_steps):
             assert filt.update(controls[c], scans[c]) is not None
             c += 1
         sync_all()
-        window_rates.append(args.steps / (time.perf_counter() - w0))
-    # Per-stage breakdown (events around every stage; these cycles run ~40 us slower and are not part of any rate above).
-    filt.profile_enable(2)
-    filt.profile_read(reset=True)
-    for _k in range(args.stage_steps):
-        assert filt.update(controls[c], scans[c]) is not None
-        c += 1
-    sync_all()
-    stage_prof = filt.profile_read(reset=True)
-    filt.profile_enable(0)
-    verified = verify_run(filt, grid, timed_estimates, true_poses[args.warmup:args.warmup + args.steps], scans[min(c, len(scans) - 1)], rank) if rank == 0 else None
+        stage_prof = filt.profile_read(reset=True)
+        filt.profile_enable(0)
+        verified = verify_run(filt, grid, timed_estimates, true_poses[args.warmup:args.warmup + args.steps], scans[min(c, len(scans) - 1)], rank) if rank == 0 else None
 
-    # (read before the filter is closed below: everything rank 0 reports about it)
-    patch_whole_run = (filt.counter("lf_patch_groups_planned"), filt.counter("lf_patch_groups_through")) if hasattr(filt, "counter") else None
-    # BASELINE configs[3] with several ranks: 8M particles per GPU behind one logical filter (64M at 8 GPUs); cycles/s of
-    # that filter, beside the metric.
-    config4 = None
-    if world > 1 and not args.no_other_configs:
-        filt.close()
-        big = make_filter(args.config4_particles)
-        big.initialize(truth, np.diag([0.25, 0.25, 0.04]))
-        for c in range(2):
-            assert big.update(controls[c], scans[c]) is not None
-        sync_all_of(big)
-        t0 = time.perf_counter()
-        for c in range(2, 8):
-            assert big.update(controls[c], scans[c]) is not None
-        sync_all_of(big)
-        dt = time.perf_counter() - t0
-        t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        config4 = {"what": f"BASELINE configs[3]: {args.config4_particles * world / 1e6:g}M particles sharded over {world} GPUs "
-                           f"({args.config4_particles / 1e6:g}M each), 1080 beams, multinomial resample every cycle",
-                   "particles_per_gpu": args.config4_particles, "particles_total": args.config4_particles * world,
-                   "cycles_per_s": 6 / float(t.item()), "ms_per_cycle": float(t.item()) / 6 * 1e3}
-        big.close()
+        # (read before the filter is closed below: everything rank 0 reports about it)
+        patch_whole_run = (filt.counter("lf_patch_groups_planned"), filt.counter("lf_patch_groups_through")) if hasattr(filt, "counter") else None
+        # BASELINE configs[3] with several ranks: 8M particles per GPU behind one logical filter (64M at 8 GPUs); cycles/s of
+        # that filter, beside the metric.
+        config4 = None
+        if world > 1 and not args.no_other_configs:
+            filt.close()
+            big = make_filter(args.config4_particles)
+            big.initialize(truth, np.diag([0.25, 0.25, 0.04]))
+            for c in range(2):
+                assert big.update(controls[c], scans[c]) is not None
+            sync_all_of(big)
+            t0 = time.perf_counter()
+            for c in range(2, 8):
+                assert big.update(controls[c], scans[c]) is not None
+            sync_all_of(big)
+            dt = time.perf_counter() - t0
+            t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            config4 = {"what": f"BASELINE configs[3]: {args.config4_particles * world / 1e6:g}M particles sharded over {world} GPUs "
+                               f"({args.config4_particles / 1e6:g}M each), 1080 beams, multinomial resample every cycle",
+                       "particles_per_gpu": args.config4_particles, "particles_total": args.config4_particles * world,
+                       "cycles_per_s": 6 / float(t.item()), "ms_per_cycle": float(t.item()) / 6 * 1e3}
+            big.close()
 
     if rank == 0:
-        pmc_status = "skipped (--no-pmc)" if args.no_pmc else ("skipped (several ranks or another set size)" if (world != 1 or n_local != 1_000_000) else None)
-        if pmc_status is None:
-            filt.sync()
-            pmc_status = collect_in_run_counters()
         ms_per_step = elapsed / args.steps * 1e3
-        lf_ms, lf_count = prof["sensor_kernel"]
-        lf_avg_s = (lf_ms / max(lf_count, 1)) * 1e-3
-        bytes_lf = lf_algorithmic_bytes(n_local, BEAMS)
-        achieved_bytes = bytes_lf / lf_avg_s if lf_avg_s > 0 else 0.0
-        floor = valu_issue_floor_ms(n_local)
-        traffic_bytes, traffic_source = None, None
-        if "FETCH_SIZE" in IN_RUN_COUNTERS and "WRITE_SIZE" in IN_RUN_COUNTERS:
-            traffic_bytes = (2.0 * IN_RUN_COUNTERS["FETCH_SIZE"] + IN_RUN_COUNTERS["WRITE_SIZE"]) * 1024.0
-            traffic_source = "in-run rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this bench.py (--pmc-child), per launch of the LF kernel"
-        else:
-            for path in TRAFFIC_FILES:
-                try:
-                    with open(path) as fh:
-                        rec = json.load(fh)
-                    traffic_bytes = (2.0 * rec["fetch_size_kb"] + rec["write_size_kb"]) * 1024.0 * (n_local / rec.get("particles", 1_000_000))
-                    traffic_source = os.path.relpath(path, ROOT) + (" (collected on the LF kernels' current source)" if rec.get("kernels_hip_sha256") == lf_kernel_source_sha(KERNEL_SOURCE)
-                                                                     else " (collected on an EARLIER version of the LF kernels' source)")
-                    break
-                except (OSError, KeyError, ValueError):
-                    continue
-        patch_fraction = patch_fraction_timed = None
-        if patch_whole_run is not None:
-            planned, through = patch_whole_run
-            patch_fraction = through / planned if planned else None  # over the whole run (the repeat windows included)
-            if patch_before and patch_after and patch_after[0] > patch_before[0]:
-                patch_fraction_timed = (patch_after[1] - patch_before[1]) / (patch_after[0] - patch_before[0])
-        # SURVEY 8(d)'s whole-cycle figure: algorithmic bytes of ONE cycle at the canonical element sizes over the cycle time
-        cycle_bytes = n_local * 4 * BEAMS + n_local * 44 + n_local * (4 * math.ceil(math.log2(max(n_local, 2))) + 44) + 8 * BEAMS
-        cycle_rate = cycle_bytes / (ms_per_step * 1e-3)
-        roofline = {
-            "kernel": "k_reweight_lf_patch (likelihood-field reweight; look-ups through per-workgroup LDS patches), 70 % of the cycle",
-            # What binds this kernel is vector-instruction issue, not HBM: its table is read through LDS patches and L2 (measured
-            # HBM traffic in profiles/: ~7 % of the algorithmic bytes), so the roofline reported is the issue rate of the kernel's own
-            # instruction mix.  achieved / peak are in wave64 vector instructions per second; frac = issue floor / launch time.
-            "bound": "valu",
-            "achieved": (floor["valu_instructions_per_launch"] / lf_avg_s / 1e9) if (floor and lf_avg_s > 0) else None,
-            "peak": (floor["peak_winstr_per_s"] / 1e9) if floor else None,
-            "unit": "G wave64-instr/s",
-            "frac": (floor["issue_floor_ms"] * 1e-3 / lf_avg_s) if (floor and lf_avg_s > 0) else None,
-            # the same instructions priced at the datasheet's issue rates (2 cycles per wave64 instruction, 4 for f64) at the nominal 2.4 GHz
-            "frac_spec": (floor["issue_floor_ms_spec_rates"] * 1e-3 / lf_avg_s) if (floor and lf_avg_s > 0) else None,
-            "traffic": traffic_bytes,  # HBM bytes per launch: 2 x FETCH_SIZE + WRITE_SIZE (gfx950 tallies a read at half its size), see traffic_source
-            "traffic_source": traffic_source,
-            "in_run_counters": pmc_status,
-            "avg_launch_ms": lf_avg_s * 1e3,
-            "launches": int(lf_count),
-            "launches_sampled_every": 4,
-            "valu_issue": floor,
-            # The contract's byte figure, kept beside it (NOT the binding roofline: above 1 where the table never leaves LDS / L2)
-            "algorithmic_bytes_per_launch": bytes_lf,
-            "algorithmic_GBps": achieved_bytes / 1e9,
-            "algorithmic_over_hbm_peak": achieved_bytes / HBM_PEAK,
-            "algorithmic_over_measured_copy_rate": achieved_bytes / HBM_MEASURED,
-            "whole_cycle": {"algorithmic_bytes_per_cycle": cycle_bytes, "GBps": cycle_rate / 1e9,
-                            "over_hbm_peak_8.0TBps": cycle_rate / HBM_PEAK, "over_measured_copy_rate_6.29TBps": cycle_rate / HBM_MEASURED},
-            "groups_through_lds_patch": patch_fraction,
-            "groups_through_lds_patch_in_timed_region": patch_fraction_timed,
-        }
         out = {
             # (N = 1: BASELINE.json's metric as it stands.  Several GPUs: the contract wants the whole job's aggregate in `value` - the
             # string then says that it is an aggregate, so that nobody reads N x the rate as the rate at which estimates come out)
@@ -868,24 +828,89 @@ def main():
                 "units_of_1M_particle_cycles_per_s": world * args.steps / elapsed * (n_local / 1_000_000),
             },
             "timed_region_s": elapsed,
-            "repeat_windows": {"steps_each": args.steps, "cycles_per_s": window_rates,
-                               "min": min(window_rates) if window_rates else None,
-                               "median": float(np.median(window_rates)) if window_rates else None},
-            "stage_ms": {k: (v[0] / max(v[1], 1)) for k, v in stage_prof.items()},
-            "roofline": roofline,
-            "roofline_by_kernel": roofline_by_kernel() or None,
-            "verified": verified,
         }
-        if not args.no_other_configs and world == 1 and n_local == 1_000_000:
-            out["configs"] = other_configs(grid, cells, truth, controls, scans, filt, local_rank)
-            if not args.no_pmc and "5" in out["configs"]:
-                out["configs"]["5"]["roofline"] = collect_beam_counters()
-            if "fixed_10M" in out["configs"]:
-                out["configs"]["fixed_10M"].update(fixed_10m_roofline(out["configs"]["fixed_10M"], not args.no_pmc))
-        if config4 is not None:
-            out["configs"] = {"4": config4}
-        if not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only: the other ranks would sit in a barrier behind it)
-            out["cpu_baseline"] = cpu_baseline(cells, truth, odoms, scans, n_total)
+        if args.full:
+            pmc_status = "skipped (--no-pmc)" if args.no_pmc else ("skipped (several ranks or another set size)" if (world != 1 or n_local != 1_000_000) else None)
+            if pmc_status is None:
+                filt.sync()
+                pmc_status = collect_in_run_counters()
+            lf_ms, lf_count = prof["sensor_kernel"]
+            lf_avg_s = (lf_ms / max(lf_count, 1)) * 1e-3
+            bytes_lf = lf_algorithmic_bytes(n_local, BEAMS)
+            achieved_bytes = bytes_lf / lf_avg_s if lf_avg_s > 0 else 0.0
+            floor = valu_issue_floor_ms(n_local)
+            traffic_bytes, traffic_source = None, None
+            if "FETCH_SIZE" in IN_RUN_COUNTERS and "WRITE_SIZE" in IN_RUN_COUNTERS:
+                traffic_bytes = (2.0 * IN_RUN_COUNTERS["FETCH_SIZE"] + IN_RUN_COUNTERS["WRITE_SIZE"]) * 1024.0
+                traffic_source = "in-run rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this bench.py (--pmc-child), per launch of the LF kernel"
+            else:
+                for path in TRAFFIC_FILES:
+                    try:
+                        with open(path) as fh:
+                            rec = json.load(fh)
+                        traffic_bytes = (2.0 * rec["fetch_size_kb"] + rec["write_size_kb"]) * 1024.0 * (n_local / rec.get("particles", 1_000_000))
+                        traffic_source = os.path.relpath(path, ROOT) + (" (collected on the LF kernels' current source)" if rec.get("kernels_hip_sha256") == lf_kernel_source_sha(KERNEL_SOURCE)
+                                                                         else " (collected on an EARLIER version of the LF kernels' source)")
+                        break
+                    except (OSError, KeyError, ValueError):
+                        continue
+            patch_fraction = patch_fraction_timed = None
+            if patch_whole_run is not None:
+                planned, through = patch_whole_run
+                patch_fraction = through / planned if planned else None  # over the whole run (the repeat windows included)
+                if patch_before and patch_after and patch_after[0] > patch_before[0]:
+                    patch_fraction_timed = (patch_after[1] - patch_before[1]) / (patch_after[0] - patch_before[0])
+            # SURVEY 8(d)'s whole-cycle figure: algorithmic bytes of ONE cycle at the canonical element sizes over the cycle time
+            cycle_bytes = n_local * 4 * BEAMS + n_local * 44 + n_local * (4 * math.ceil(math.log2(max(n_local, 2))) + 44) + 8 * BEAMS
+            cycle_rate = cycle_bytes / (ms_per_step * 1e-3)
+            roofline = {
+                "kernel": "k_reweight_lf_patch (likelihood-field reweight; look-ups through per-workgroup LDS patches), 70 % of the cycle",
+                # What binds this kernel is vector-instruction issue, not HBM: its table is read through LDS patches and L2 (measured
+                # HBM traffic in profiles/: ~7 % of the algorithmic bytes), so the roofline reported is the issue rate of the kernel's own
+                # instruction mix.  achieved / peak are in wave64 vector instructions per second; frac = issue floor / launch time.
+                "bound": "valu",
+                "achieved": (floor["valu_instructions_per_launch"] / lf_avg_s / 1e9) if (floor and lf_avg_s > 0) else None,
+                "peak": (floor["peak_winstr_per_s"] / 1e9) if floor else None,
+                "unit": "G wave64-instr/s",
+                "frac": (floor["issue_floor_ms"] * 1e-3 / lf_avg_s) if (floor and lf_avg_s > 0) else None,
+                # the same instructions priced at the datasheet's issue rates (2 cycles per wave64 instruction, 4 for f64) at the nominal 2.4 GHz
+                "frac_spec": (floor["issue_floor_ms_spec_rates"] * 1e-3 / lf_avg_s) if (floor and lf_avg_s > 0) else None,
+                "traffic": traffic_bytes,  # HBM bytes per launch: 2 x FETCH_SIZE + WRITE_SIZE (gfx950 tallies a read at half its size), see traffic_source
+                "traffic_source": traffic_source,
+                "in_run_counters": pmc_status,
+                "avg_launch_ms": lf_avg_s * 1e3,
+                "launches": int(lf_count),
+                "launches_sampled_every": 4,
+                "valu_issue": floor,
+                # The contract's byte figure, kept beside it (NOT the binding roofline: above 1 where the table never leaves LDS / L2)
+                "algorithmic_bytes_per_launch": bytes_lf,
+                "algorithmic_GBps": achieved_bytes / 1e9,
+                "algorithmic_over_hbm_peak": achieved_bytes / HBM_PEAK,
+                "algorithmic_over_measured_copy_rate": achieved_bytes / HBM_MEASURED,
+                "whole_cycle": {"algorithmic_bytes_per_cycle": cycle_bytes, "GBps": cycle_rate / 1e9,
+                                "over_hbm_peak_8.0TBps": cycle_rate / HBM_PEAK, "over_measured_copy_rate_6.29TBps": cycle_rate / HBM_MEASURED},
+                "groups_through_lds_patch": patch_fraction,
+                "groups_through_lds_patch_in_timed_region": patch_fraction_timed,
+            }
+            out.update({
+                "repeat_windows": {"steps_each": args.steps, "cycles_per_s": window_rates,
+                                   "min": min(window_rates) if window_rates else None,
+                                   "median": float(np.median(window_rates)) if window_rates else None},
+                "stage_ms": {k: (v[0] / max(v[1], 1)) for k, v in stage_prof.items()},
+                "roofline": roofline,
+                "roofline_by_kernel": roofline_by_kernel() or None,
+                "verified": verified,
+            })
+            if not args.no_other_configs and world == 1 and n_local == 1_000_000:
+                out["configs"] = other_configs(grid, cells, truth, controls, scans, filt, local_rank)
+                if not args.no_pmc and "5" in out["configs"]:
+                    out["configs"]["5"]["roofline"] = collect_beam_counters()
+                if "fixed_10M" in out["configs"]:
+                    out["configs"]["fixed_10M"].update(fixed_10m_roofline(out["configs"]["fixed_10M"], not args.no_pmc))
+            if config4 is not None:
+                out["configs"] = {"4": config4}
+            if not args.no_cpu_baseline and world == 1:  # (rank 0 at N = 1 only: the other ranks would sit in a barrier behind it)
+                out["cpu_baseline"] = cpu_baseline(cells, truth, odoms, scans, n_total)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(out), flush=True)

@@ -126,3 +126,44 @@ def test_config3_10m_kld_selective_cycles_against_the_oracle():
     assert counts[0] == n_max and not fired[0], (counts, fired)  # what bench.py reports as the cycle that does not fire
     assert any(fired) and n_min <= counts[-1] < n_max, (counts, fired)
     gpu.close()
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_estimate(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: ONE line with the headline's fields and nothing
+    measured beside them, `ms_per_step` = the timed region over exactly K steps, and in DIR the estimate that the last timed update
+    returned - the one a filter in this process returns after W + K cycles on the same seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup, n = 3, 2, 1_000_000
+    out_dir = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--dump-outputs", str(out_dir)]
+    run = subprocess.run(cmd, capture_output=True, text=True, cwd=root, timeout=600)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, run.stdout
+    line = json.loads(lines[0])
+    assert line["metric"] == "MCL update cycles/sec (motion+sensor+resample), N particles x 1080 beams"
+    assert line["unit"] == "cycles/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == steps and line["warmup"] == warmup and line["config"]["particles_total"] == n
+    assert line["ms_per_step"] == pytest.approx(line["timed_region_s"] / steps * 1e3, rel=1e-9)
+    assert line["value"] == pytest.approx(steps / line["timed_region_s"], rel=1e-9)
+    for key in ("repeat_windows", "stage_ms", "roofline", "roofline_by_kernel", "verified", "configs", "cpu_baseline"):
+        assert key not in line, f"{key}: only with --full"
+    pose, cov = np.load(out_dir / "pose.npy"), np.load(out_dir / "covariance.npy")
+    assert pose.dtype == np.float64 and pose.shape == (4,) and cov.dtype == np.float64 and cov.shape == (3, 3)
+
+    cells, truth, odoms, scans, _poses = bench.make_workload(warmup + steps)
+    grid = OccupancyGrid(cells, bench.RESOLUTION, origin=se2_from_xytheta(bench.ORIGIN[0], bench.ORIGIN[1], 0.0))
+    gpu = Amcl(grid, DifferentialDriveModelParam(*bench.ALPHAS), LikelihoodFieldModelParam(**bench.LF),
+               AmclParams(min_particles=n, max_particles=n), seed=42)
+    gpu.initialize(truth, np.diag([0.25, 0.25, 0.04]))
+    for c in range(warmup + steps):
+        g = gpu.update(se2_from_xytheta(*odoms[c]), scans[c])
+        assert g is not None
+    gpu.close()
+    np.testing.assert_allclose(pose, g[0], rtol=0, atol=1e-12)
+    np.testing.assert_allclose(cov, g[1], rtol=1e-10, atol=1e-15)

@@ -198,7 +198,8 @@ def test_bench_multi_rank_flow_dry_run_on_one_gpu(tmp_path, with_config4):
     """`bench.py --gpus 2` as the driver launches it (torch.distributed.run, one process per rank), here with both ranks on the
     GPU at hand and gloo between them (BELUGA_BENCH_BACKEND=gloo: the timings mean nothing): the multi-rank flow - rendezvous,
     sharded filter, timed region with barriers, max over ranks, ONE JSON line from rank 0 - must not fall over unseen on the
-    first 8-GPU node it meets.  The line's contract fields are checked, and the filter still localises."""
+    first 8-GPU node it meets.  The line's contract fields are checked, and the filter still localises (--full: `verified`, the
+    repeat windows and config 4 are behind it)."""
     import json
     import subprocess
     import sys
@@ -206,7 +207,7 @@ def test_bench_multi_rank_flow_dry_run_on_one_gpu(tmp_path, with_config4):
     env = dict(os.environ, BELUGA_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
            "29617", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--particles", "20000", "--windows", "1",
-           "--stage-steps", "2", "--no-cpu-baseline"]
+           "--stage-steps", "2", "--no-cpu-baseline", "--full"]
     # with_config4: the branch that several ranks add to the line - BASELINE configs[3], a second sharded filter behind the first - runs
     # as well, at a reduced size (the default 8M per rank is the configuration itself; two of those on one device is the size-realistic
     # test of tests/test_cpp_facade.py)

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 python -c "import __graft_entry__ as g; g.build()" > gpurun_out/build.log 2>&1 || { tail -30 gpurun_out/build.log; exit 1; }
 timeout 1200 python -m pytest tests -m gpu -q > gpurun_out/pytest_gpu.log 2>&1; grep -E "passed|failed|error" gpurun_out/pytest_gpu.log | tail -2
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu | tail -2
-timeout 600 python bench.py --steps 30 --warmup 3 2>gpurun_out/bench.err | tee gpurun_out/bench.json
+timeout 600 python bench.py --full --steps 30 --warmup 3 2>"$TMPDIR"/bench.err | tee "$TMPDIR"/bench.json
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof/final_trace -o trace -- python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2> $GRAFT_REPO_ROOT/gpurun_out/prof/final_trace.err
 i=0

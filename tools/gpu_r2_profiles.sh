@@ -34,7 +34,7 @@ timeout 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof
 python $GRAFT_REPO_ROOT/tools/rocpd_summary.py $GRAFT_REPO_ROOT/gpurun_out/prof/c3/trace_results.db | head -30 > $O/kernel_trace_config3.txt
 rm -rf $GRAFT_REPO_ROOT/gpurun_out/prof/c3
 cd $GRAFT_REPO_ROOT
-timeout 900 python bench.py --steps 20 --warmup 5 2>/dev/null > $O/bench_1M.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>/dev/null > $O/bench_1M.json
 # beam kernel: instruction counters, then the walk statistics of the measurement build (rebuilds the library twice)
 cd /tmp
 rm -f $O/pmc_config5.txt

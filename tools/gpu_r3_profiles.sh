@@ -62,7 +62,7 @@ python tools/exp_host_time.py 2>/dev/null | tail -n 1 > $O/host_time_per_cycle.t
 python tools/exp_lf_converge.py 2>/dev/null > $O/lf_converge.txt
 [ -x build/calib_mfma_f64 ] && timeout 60 ./build/calib_mfma_f64 > $O/calib_mfma_f64.txt 2>/dev/null
 [ -x build/calib_lds_residency ] && timeout 60 ./build/calib_lds_residency > $O/calib_lds_residency.txt 2>/dev/null
-timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench.err > $O/bench_1M.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err > $O/bench_1M.json
 python tools/exp_lf_ab.py 40 2>/dev/null | grep -A2 "^all (defaults)" > $O/lf_series.txt
 python tools/exp_small.py 2>/dev/null > $O/small_filters.txt
 ls -la $O

@@ -59,7 +59,7 @@ python tools/timeline.py gpurun_out/prof/tf/trace_results.db 1 >> $O/kernel_trac
 rm -rf gpurun_out/prof/tf
 python tools/exp_host_time.py 2>/dev/null | tail -n 1 > $O/host_time_per_cycle.txt
 python tools/exp_lf_converge.py 2>/dev/null > $O/lf_converge.txt
-timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench.err > $O/bench_1M.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err > $O/bench_1M.json
 python tools/exp_pipe_ab.py 45 2>/dev/null > $O/lf_pipe_ab.txt
 python tools/exp_small.py 2>/dev/null > $O/small_filters.txt
 # the queue of blocks: A/B on the bench's set (1M and 10M), and the launch's timeline workgroup by workgroup (timing build)

@@ -58,7 +58,7 @@ python tools/timeline.py gpurun_out/prof/tf/trace_results.db 1 >> $O/kernel_trac
 rm -rf gpurun_out/prof/tf
 python tools/exp_host_time.py 2>/dev/null | tail -n 1 > $O/host_time_per_cycle.txt
 python tools/exp_lf_converge.py 2>/dev/null > $O/lf_converge.txt
-timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench.err > $O/bench_1M.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench.err > $O/bench_1M.json
 python tools/exp_small.py 2>/dev/null > $O/small_filters.txt
 python tools/exp_dispersed.py 32 2>/dev/null > $O/dispersed.txt
 python tools/exp_order_ahead.py 2>/dev/null > $O/order_ahead_counters.txt
