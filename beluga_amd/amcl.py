@@ -101,6 +101,68 @@ class OccupancyGrid:
     value_traits: Tuple[int, int, int] = (0, -1, 100)  # free, unknown, occupied
 
 
+# kDefaultNeighborKernel2d (ndt_sensor_model.hpp:113-123), in its order
+NDT_DEFAULT_KERNEL = ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 0), (0, 1), (1, -1), (1, 0), (1, 1))
+
+
+@dataclass
+class NDTModelParam2d:
+    """beluga::NDTModelParam2d (sensor/ndt_sensor_model.hpp:153-166); ndt_amcl_node's defaults are 0.01 / 1.0 / 0.6."""
+    minimum_likelihood: float = 0.0
+    d1: float = 1.0
+    d2: float = 1.0
+    neighbors_kernel: Sequence[Tuple[int, int]] = NDT_DEFAULT_KERNEL
+
+
+@dataclass
+class NDTMap2d:
+    """A SparseValueGrid2 of NDTCell2d (the layout of io::load_from_hdf5): integer keys cells[n,2], means[n,2], covariances[n,2,2]
+    and the resolution; a cell's key is floor(p / resolution) of the points it covers (no origin)."""
+    cells: np.ndarray
+    means: np.ndarray
+    covariances: np.ndarray
+    resolution: float
+
+
+def load_ndt_map_npz(path: str) -> NDTMap2d:
+    """An NDT map saved as .npz with the HDF5 file's four datasets (cells, means, covariances, resolution)."""
+    z = np.load(path)
+    return NDTMap2d(cells=np.asarray(z["cells"], dtype=np.int32).reshape(-1, 2), means=np.asarray(z["means"], dtype=np.float64).reshape(-1, 2),
+                    covariances=np.asarray(z["covariances"], dtype=np.float64).reshape(-1, 2, 2), resolution=float(z["resolution"]))
+
+
+def ndt_params_struct(p: NDTModelParam2d) -> capi.NdtParams:
+    kernel = list(p.neighbors_kernel)
+    if not 1 <= len(kernel) <= capi.MCL_NDT_MAX_OFFSETS:
+        raise ValueError(f"the neighbours kernel takes 1 .. {capi.MCL_NDT_MAX_OFFSETS} offsets")
+    out = capi.NdtParams()
+    out.minimum_likelihood, out.d1, out.d2 = p.minimum_likelihood, p.d1, p.d2
+    out.num_offsets = len(kernel)
+    for k, (dx, dy) in enumerate(kernel):
+        out.offsets[2 * k], out.offsets[2 * k + 1] = int(dx), int(dy)
+    return out
+
+
+def default_ndt_params() -> dict:
+    """mcl_default_ndt_params as a dict (minimum_likelihood, d1, d2, neighbors_kernel)."""
+    p = capi.NdtParams()
+    capi.load().mcl_default_ndt_params(C.byref(p))
+    return {"minimum_likelihood": p.minimum_likelihood, "d1": p.d1, "d2": p.d2,
+            "neighbors_kernel": tuple((p.offsets[2 * k], p.offsets[2 * k + 1]) for k in range(p.num_offsets))}
+
+
+def ndt_measurement_cells(points_xy, resolution: float):
+    """detail::to_cells (ndt_sensor_model.hpp:88-110) through the library: (means[k,2], covariances[k,2,2]) of the scan's cells."""
+    pts = np.ascontiguousarray(points_xy, dtype=np.float64).reshape(-1, 2)
+    cap = len(pts) // 5 + 1
+    means, covs = np.zeros((cap, 2)), np.zeros((cap, 2, 2))
+    k = C.c_uint64(0)
+    st = capi.load().mcl_ndt_measurement_cells(_dp(pts), len(pts), float(resolution), _dp(means), _dp(covs), C.byref(k))
+    if st != capi.MCL_OK:
+        raise capi.MclError(st, "mcl_ndt_measurement_cells")
+    return means[:k.value].copy(), covs[:k.value].copy()
+
+
 def se2_from_xytheta(x: float, y: float, theta: float) -> np.ndarray:
     return np.array([math.cos(theta), math.sin(theta), x, y], dtype=np.float64)
 
@@ -144,8 +206,15 @@ class Amcl:
             cfg.sensor_kind = capi.MCL_SENSOR_BEAM
             for k in ("z_hit", "z_short", "z_max", "z_rand", "sigma_hit", "lambda_short", "beam_max_range"):
                 setattr(cfg.beam, k, getattr(sensor, k))
+        elif isinstance(sensor, NDTModelParam2d):
+            if not isinstance(grid, NDTMap2d):
+                raise ValueError("the NDT sensor model takes an NDTMap2d")
+            cfg.sensor_kind = capi.MCL_SENSOR_NDT
+            self._ndt_params = sensor
         else:
-            raise ValueError("sensor must be LikelihoodFieldModelParam or BeamModelParam")
+            raise ValueError("sensor must be LikelihoodFieldModelParam, BeamModelParam or NDTModelParam2d")
+        if isinstance(grid, NDTMap2d) and not isinstance(sensor, NDTModelParam2d):
+            raise ValueError("an NDTMap2d needs the NDT sensor model (NDTModelParam2d)")
         cfg.shard_offset = shard_offset
         cfg.shard_capacity = shard_capacity
         cfg.hip_stream = hip_stream or None
@@ -187,8 +256,20 @@ class Amcl:
             raise capi.MclError(st, self._lib.mcl_last_error(self._ctx).decode())
 
     # -- reference surface -------------------------------------------------------------------------
-    def update_map(self, grid: OccupancyGrid):
-        """Amcl::update_map (amcl_core.hpp:150)."""
+    def update_map(self, grid):
+        """Amcl::update_map (amcl_core.hpp:150): an OccupancyGrid, or an NDTMap2d for the NDT sensor model."""
+        if isinstance(grid, NDTMap2d):
+            keys = np.ascontiguousarray(grid.cells, dtype=np.int32).reshape(-1, 2)
+            means = np.ascontiguousarray(grid.means, dtype=np.float64).reshape(-1, 2)
+            covs = np.ascontiguousarray(grid.covariances, dtype=np.float64).reshape(-1, 4)
+            if not (len(keys) == len(means) == len(covs)):
+                raise ValueError("NDTMap2d: cells, means and covariances differ in length")
+            prm = ndt_params_struct(getattr(self, "_ndt_params", None) or NDTModelParam2d())
+            self._check(self._lib.mcl_set_ndt_map(self._ctx, keys.ctypes.data_as(C.POINTER(C.c_int32)), _dp(means), _dp(covs), len(keys),
+                                                  float(grid.resolution), C.byref(prm)))
+            self._shape = None
+            self._pending_shape = None
+            return
         cells = np.ascontiguousarray(grid.cells, dtype=np.int8)
         H, W = cells.shape
         origin = np.ascontiguousarray(grid.origin, dtype=np.float64)
@@ -355,6 +436,14 @@ class Amcl:
     def reweight(self, measurement):
         pts = np.ascontiguousarray(measurement, dtype=np.float64).reshape(-1, 2)
         self._check(self._lib.mcl_reweight(self._ctx, _dp(pts), len(pts)))
+
+    def reweight_ndt_cells(self, means, covariances):
+        """NDT model: w *= 1 + sum of likelihood_at(state * cell) over caller-fitted measurement cells (base frame)."""
+        m = np.ascontiguousarray(means, dtype=np.float64).reshape(-1, 2)
+        c = np.ascontiguousarray(covariances, dtype=np.float64).reshape(-1, 4)
+        if len(m) != len(c):
+            raise ValueError("reweight_ndt_cells: means and covariances differ in length")
+        self._check(self._lib.mcl_reweight_ndt_cells(self._ctx, _dp(m), _dp(c), len(m)))
 
     def weight_sum(self) -> float:
         v = C.c_double(0)

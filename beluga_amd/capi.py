@@ -24,6 +24,8 @@ MCL_ERR_UNSUPPORTED = -7
 MCL_SENSOR_LIKELIHOOD_FIELD = 0
 MCL_SENSOR_BEAM = 1
 MCL_SENSOR_LIKELIHOOD_FIELD_PROB = 2
+MCL_SENSOR_NDT = 3
+MCL_NDT_MAX_OFFSETS = 32
 MCL_MOTION_DIFFERENTIAL, MCL_MOTION_OMNIDIRECTIONAL, MCL_MOTION_STATIONARY = 0, 1, 2
 
 STAGES = ("propagate", "reweight", "normalize", "resample", "estimate", "sensor_kernel")
@@ -62,6 +64,11 @@ class LfParams(C.Structure):
 
 class BeamParams(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("z_hit", "z_short", "z_max", "z_rand", "sigma_hit", "lambda_short", "beam_max_range")]
+
+
+class NdtParams(C.Structure):
+    _fields_ = [("minimum_likelihood", C.c_double), ("d1", C.c_double), ("d2", C.c_double), ("num_offsets", C.c_uint32),
+                ("offsets", C.c_int32 * (2 * MCL_NDT_MAX_OFFSETS))]
 
 
 class Config(C.Structure):
@@ -171,6 +178,10 @@ _SIGNATURES = {
     "mcl_debug_order": (C.c_int32, [_ctx, c_u32_p, c_u32_p]),
     "mcl_debug_set_recovery_filters": (C.c_int32, [_ctx, C.c_double, C.c_double]),
     "mcl_debug_curve_index": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "mcl_default_ndt_params": (None, [C.POINTER(NdtParams)]),
+    "mcl_set_ndt_map": (C.c_int32, [_ctx, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_uint64, C.c_double, C.POINTER(NdtParams)]),
+    "mcl_ndt_measurement_cells": (C.c_int32, [c_double_p, C.c_uint64, C.c_double, c_double_p, c_double_p, c_u64_p]),
+    "mcl_reweight_ndt_cells": (C.c_int32, [_ctx, c_double_p, c_double_p, C.c_uint64]),
     "mcl_version": (C.c_char_p, []),
     "mcl_measurement_build": (C.c_int, []),
 }

@@ -395,6 +395,23 @@ struct mcl_ctx {
     return s;
   }
   GridView grid_view() const { return GridView{d_cells.ptr, W, H, resolution, origin, origin_inverse, traits.free_value}; }
+
+  // NDT sensor model (MCL_SENSOR_NDT).  `have_map` above is the occupancy grid's (likelihood-field and beam models); an NDT context has
+  // none and keeps its own state: the map of mcl_set_ndt_map (NdtMapView: index grid + cell records), and the random-state source of
+  // the next draw (FreeCells::normal, filled from the estimate of the normalised set by do_resample).
+  bool have_ndt_map{false};
+  DeviceBuffer<int32_t> d_ndt_grid;
+  DeviceBuffer<double> d_ndt_cells;
+  NdtMapView ndt_view{};
+  uint64_t ndt_map_cells{0};
+  double ndt_resolution{0.0};
+  std::vector<double> h_ndt_meas;  // the scan's measurement cells, kNdtRecord doubles each (what stage_points uploads)
+  FreeCells ndt_random{nullptr, 0};
+  bool ndt_random_ready{false};        // ndt_random was prepared for the next draw (prepare_ndt_random)
+  DeviceBuffer<double> d_ndt_est;      // scratch of the estimate behind ndt_random (9 rows of num_chunks(n))
+  bool is_ndt() const { return cfg.sensor_kind == MCL_SENSOR_NDT; }
+  // What random_intersperse's random states are drawn from (random_free_state).
+  FreeCells random_source() const { return is_ndt() ? ndt_random : FreeCells{d_free.ptr, have_map ? n_free : 0}; }
 };
 
 namespace {
@@ -650,6 +667,47 @@ mcl_status rebuild_cube(mcl_ctx* ctx, const float* h_field) {
   return MCL_OK;
 }
 
+// detail::to_cells (ndt_sensor_model.hpp:88-110) with fit_points (:66-80): kNdtRecord doubles per cell (mean x, y, covariance xx, xy,
+// yy, 0) appended to `out`, the cells in ascending key order (the reference's order is an unordered_map's: only the rounding of the
+// weight's sum depends on it).  The group key is (p / resolution).cast<int>() - division and truncation toward zero, NOT the floor
+// of cell_near.  Points that are not finite or whose key does not fit an int are dropped (the reference's cast is undefined there).
+void ndt_fit_cells(const double* pts, uint64_t B, double resolution, std::vector<double>& out) {
+  out.clear();
+  std::vector<std::pair<std::pair<int32_t, int32_t>, uint64_t>> keyed;
+  keyed.reserve(B);
+  for (uint64_t i = 0; i < B; ++i) {
+    const double qx = pts[2 * i] / resolution, qy = pts[2 * i + 1] / resolution;
+    if (!(std::abs(qx) < 2147483647.0 && std::abs(qy) < 2147483647.0)) continue;
+    keyed.push_back({{static_cast<int32_t>(qx), static_cast<int32_t>(qy)}, i});
+  }
+  std::sort(keyed.begin(), keyed.end());
+  for (size_t a = 0; a < keyed.size();) {
+    size_t b = a;
+    while (b < keyed.size() && keyed[b].first == keyed[a].first) ++b;
+    const size_t m = b - a;
+    if (m >= 5) {  // kMinPointsPerCell
+      double sx = 0.0, sy = 0.0;
+      for (size_t t = a; t < b; ++t) {
+        sx += pts[2 * keyed[t].second];
+        sy += pts[2 * keyed[t].second + 1];
+      }
+      const double mx = sx / static_cast<double>(m), my = sy / static_cast<double>(m);
+      double cxx = 0.0, cxy = 0.0, cyy = 0.0;
+      for (size_t t = a; t < b; ++t) {
+        const double dx = pts[2 * keyed[t].second] - mx, dy = pts[2 * keyed[t].second + 1] - my;
+        cxx += dx * dx;
+        cxy += dx * dy;
+        cyy += dy * dy;
+      }
+      const double denom = static_cast<double>(m - 1);  // sample covariance
+      const double rec[kNdtRecord] = {mx, my, std::max(cxx / denom, 1e-5), cxy / denom, std::max(cyy / denom, 1e-5), 0.0};
+      out.insert(out.end(), rec, rec + kNdtRecord);
+    }
+    a = b;
+  }
+}
+void ndt_fit_scan(mcl_ctx* ctx, const double* pts, uint64_t B) { ndt_fit_cells(pts, B, ctx->ndt_resolution, ctx->h_ndt_meas); }
+
 // Stages the scan in mapped pinned memory; a kernel of the cycle pulls it into d_points (pull_scan_args / launch_pull_scan).
 mcl_status stage_points(mcl_ctx* ctx, const double* pts, uint64_t B) {
   if (B == 0) return MCL_OK;
@@ -697,7 +755,7 @@ void points_pulled(mcl_ctx* ctx, bool with_event) {
 uint32_t key_layout(const mcl_ctx* ctx) {
   const uint32_t curve = ctx->tuning.key_curve ? 0u : 2u;  // heading-major keys: Hilbert curve (default) / Morton order
   if (ctx->tuning.key_layout >= 0) return (ctx->tuning.key_layout ? 1u : 0u) | curve;
-  return (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM && ctx->tuning.lf_patch == 1 && !ctx->patch_useful && ctx->tuning.lf_far_tiles != 0 &&
+  return (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM && !ctx->is_ndt() && ctx->tuning.lf_patch == 1 && !ctx->patch_useful && ctx->tuning.lf_far_tiles != 0 &&
                   ctx->far_tiles != 0
               ? 1u
               : 0u) |
@@ -842,7 +900,7 @@ void decide_lf_mode(mcl_ctx* ctx) {
   ctx->lf_mode.decided = true;
   ctx->lf_mode.patches = false;
   ctx->lf_mode.beams = false;
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) return;
+  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM || ctx->is_ndt()) return;
   const bool palette = ctx->pal_count != 0 && ctx->tuning.lf_table == 0;
   if (ctx->tuning.lf_variant == kLfBeamLanes) {
     ctx->lf_mode.beams = palette;
@@ -856,6 +914,7 @@ void decide_lf_mode(mcl_ctx* ctx) {
 
 bool wants_ordering(const mcl_ctx* ctx) {
   if (ctx->n >= (1ull << 32)) return false;
+  if (ctx->is_ndt()) return false;  // (a lane per particle in index order: the NDT map lives in L2, locality buys nothing)
   if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) return ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles);
   if (ctx->n < static_cast<uint64_t>(ctx->tuning.sort_min_particles)) return false;
   if (ctx->lf_mode.decided && ctx->lf_mode.beams) return false;
@@ -918,6 +977,11 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
 }
 
 mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
+  if (ctx->is_ndt()) {
+    if (!ctx->have_ndt_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no NDT map set (mcl_set_ndt_map)");
+    MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
+    return MCL_OK;
+  }
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no map set");
   MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
   // (no likelihood-field kernel stages the whole scan in LDS any more: lf_variant 0 launches the lane-per-particle kernel of variant 1)
@@ -957,7 +1021,12 @@ mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_
     const bool have_frame = !keys_ready && predict_key_frame(ctx, nullptr, &frame);
     launch_order_particles(ctx->stream, ctx->cur(), ctx->n, &sort, have_frame ? &frame : nullptr, keys_ready, frame.layout);
   }
-  if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
+  if (ctx->is_ndt()) {
+    // B counts staged doubles in pairs (stage_points): the measurement cells are kNdtRecord doubles each
+    stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
+    launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, static_cast<uint32_t>(2 * B / kNdtRecord));
+    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
+  } else if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
     // Below a few thousand particles the ordering passes cost more than they save.
     // Sets below the ordering threshold (the reference's usual sizes): one or a few particles per wave, lanes over the beams
     // (launch_reweight_lf falls back to the lane-per-particle kernel where the field has no palette form).
@@ -1093,6 +1162,36 @@ mcl_status do_build_cdf(mcl_ctx* ctx, bool normalized_just_now = false, const Re
   return MCL_OK;
 }
 
+// scratch: the per-chunk partial sums (9 rows of num_chunks(n)); nullptr = d_chunk's rows from 0 on (which overlap chunk_row(1..8))
+mcl_status do_estimate_sums(mcl_ctx* ctx, const double pivot[2], double sums[12], double* scratch = nullptr);
+
+// NDT model: the random-state source of the next draw, N(estimate(particles)) of the set as it stands (ndt_amcl_node.cpp:248-254: built
+// where amcl_core.hpp:182 builds it - after the recovery estimator and the resample policy, before the estimator's reset at :184-186).
+// Only where states can be injected (p > 0): one estimate pass and its synchronisation.  The estimate's partial sums go to a buffer of
+// their own: d_chunk holds the normalisation's chunk sums (chunk_row(1)), which the CDF kernel behind it reuses.  A rejected covariance is
+// MCL_ERR_BAD_COVARIANCE (the reference throws from the generator's constructor, multivariate_normal_distribution.hpp:114-124).
+mcl_status prepare_ndt_random(mcl_ctx* ctx, double random_state_probability) {
+  ctx->ndt_random = FreeCells{nullptr, 0};
+  ctx->ndt_random_ready = true;
+  if (!(random_state_probability > 0.0)) return MCL_OK;
+  ctx->ndt_random_ready = false;
+  MCL_HIP(ctx, ctx->d_ndt_est.ensure(static_cast<size_t>(9) * std::max<uint32_t>(num_chunks(ctx->n), 1u)));
+  double sums[12];
+  if (const mcl_status s = do_estimate_sums(ctx, ctx->pivot, sums, ctx->d_ndt_est.ptr)) return s;
+  mcl_estimate est{};
+  (void)mcl_estimate_from_sums(sums, &est);
+  FreeCells src{nullptr, 1};
+  src.normal = 1;
+  src.mean[0] = est.pose[2];
+  src.mean[1] = est.pose[3];
+  src.mean[2] = std::atan2(est.pose[1], est.pose[0]);
+  if (!(std::isfinite(src.mean[0]) && std::isfinite(src.mean[1])) || !covariance_to_transform(est.covariance, src.T))
+    return fail(ctx, MCL_ERR_BAD_COVARIANCE, "Invalid covariance matrix (estimate of the particle set, NDT random states)");
+  ctx->ndt_random = src;
+  ctx->ndt_random_ready = true;
+  return MCL_OK;
+}
+
 // with_estimate (fixed-N path only): the draw kernel also leaves the estimate sums of the new set in d_scalars[8..17) and
 // their host mirror; *estimate_enqueued says whether it did.
 mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t step, uint64_t* n_out,
@@ -1101,6 +1200,14 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
                        bool finalize_norm = false, bool cdf_ready = false) {
   const mcl_amcl_params& a = ctx->cfg.amcl;
   MCL_REQUIRE(ctx, ctx->n > 0, "mcl_resample: empty particle set");
+  if (ctx->is_ndt()) {
+    // the random states of this draw (prepare_ndt_random: mcl_update prepares them before the recovery estimator's reset; the stage-level
+    // mcl_resample here); a rejected covariance fails before any particle is overwritten
+    MCL_REQUIRE(ctx, d_random_state_probability == nullptr, "NDT model: the random state probability has to be known on the host");
+    if (!ctx->ndt_random_ready)
+      if (const mcl_status s = prepare_ndt_random(ctx, random_state_probability)) return s;
+    ctx->ndt_random_ready = false;  // (used by this draw only)
+  }
   ctx->lf_wsum_count = 0;  // (the set changes: workgroup sums of an earlier reweight describe another one)
   const uint64_t max_p = std::min<uint64_t>(a.max_particles, ctx->capacity);
   stage_begin(ctx, MCL_STAGE_RESAMPLE);
@@ -1112,7 +1219,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
   ra.random_state_probability = random_state_probability;
   ra.d_random_state_probability = d_random_state_probability;
   ra.n_in = ctx->n;
-  const FreeCells fc{ctx->d_free.ptr, ctx->have_map ? ctx->n_free : 0};
+  const FreeCells fc = ctx->random_source();
   const HashParams hp{a.spatial_resolution_x, a.spatial_resolution_y, a.spatial_resolution_theta};
   const GridView gv = ctx->grid_view();
   uint64_t result = max_p;
@@ -1209,9 +1316,9 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
   return MCL_OK;
 }
 
-mcl_status do_estimate_sums(mcl_ctx* ctx, const double pivot[2], double sums[12]) {
+mcl_status do_estimate_sums(mcl_ctx* ctx, const double pivot[2], double sums[12], double* scratch) {
   stage_begin(ctx, MCL_STAGE_ESTIMATE);
-  launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, pivot[0], pivot[1], ctx->chunk_row(0), ctx->d_scalars.ptr + 8,
+  launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, pivot[0], pivot[1], scratch ? scratch : ctx->chunk_row(0), ctx->d_scalars.ptr + 8,
                        ctx->hd_scalars + 8);
   stage_end(ctx, MCL_STAGE_ESTIMATE);
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1944,7 +2051,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
     const bool padded = fires && ctx->estimate_kind == 0 && ctx->tuning.shard_pad_permille > 0 && world > 1;
     const uint64_t m = ctx->n, first_slot = ctx->cfg.shard_offset;
     auto commit = [&](uint64_t entries, bool injected_apart) -> mcl_status {
-      const FreeCells fc{ctx->d_free.ptr, ctx->have_map ? ctx->n_free : 0};
+      const FreeCells fc = ctx->random_source();
       launch_commit_routed(ctx->stream, ctx->other(), ctx->cfg.seed, ctx->step, first_slot, entries, ctx->d_replies_in.ptr, ctx->d_route_order.ptr,
                            ctx->d_targets.ptr, ctx->grid_view(), fc);
       // (the fixed-capacity exchange routes no injected slot: sharded_draw_padded / k_route_hist)
@@ -2218,7 +2325,7 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
   *out = nullptr;
   if (cfg->amcl.max_particles == 0 || cfg->amcl.resample_interval == 0)
     return fail(nullptr, MCL_ERR_INVALID_ARGUMENT, "mcl_create: max_particles and resample_interval must be > 0");
-  if (cfg->sensor_kind < MCL_SENSOR_LIKELIHOOD_FIELD || cfg->sensor_kind > MCL_SENSOR_LIKELIHOOD_FIELD_PROB)
+  if (cfg->sensor_kind < MCL_SENSOR_LIKELIHOOD_FIELD || cfg->sensor_kind > MCL_SENSOR_NDT)
     return fail(nullptr, MCL_ERR_INVALID_ARGUMENT, "mcl_create: unknown sensor_kind");
   if (cfg->motion_kind < MCL_MOTION_DIFFERENTIAL || cfg->motion_kind > MCL_MOTION_STATIONARY)
     return fail(nullptr, MCL_ERR_INVALID_ARGUMENT, "mcl_create: unknown motion_kind");
@@ -2332,6 +2439,9 @@ void mcl_destroy(mcl_ctx* ctx) {
   ctx->d_cell_exchange.release();
   ctx->d_sort_u64.release();
   ctx->d_sort_f64.release();
+  ctx->d_ndt_grid.release();
+  ctx->d_ndt_cells.release();
+  ctx->d_ndt_est.release();
   if (ctx->rccl_comm) {
     if (RcclApi* api = rccl_api(nullptr)) (void)api->CommDestroy(ctx->rccl_comm);
   }
@@ -2387,6 +2497,7 @@ extern "C" {
 mcl_status mcl_set_map(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32_t height, double resolution,
                        const double origin[4], const int8_t value_traits[3]) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_map: not on an NDT context (its map comes from mcl_set_ndt_map)");
   MCL_REQUIRE(ctx, cells && origin && value_traits && width > 0 && height > 0 && resolution > 0, "mcl_set_map: bad argument");
   MCL_REQUIRE(ctx, static_cast<uint64_t>(width) * height < 0xFFFFFFFFull, "mcl_set_map: grid too large");
   drop_pending_map(ctx);  // (a map given now replaces one that is still on its way)
@@ -2396,6 +2507,7 @@ mcl_status mcl_set_map(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32
 mcl_status mcl_set_map_async(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32_t height, double resolution,
                              const double origin[4], const int8_t value_traits[3]) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_map_async: not on an NDT context (its map comes from mcl_set_ndt_map)");
   MCL_REQUIRE(ctx, cells && origin && value_traits && width > 0 && height > 0 && resolution > 0, "mcl_set_map_async: bad argument");
   MCL_REQUIRE(ctx, static_cast<uint64_t>(width) * height < 0xFFFFFFFFull, "mcl_set_map_async: grid too large");
   if (ctx->have_comm && ctx->comm_world > 1)
@@ -2516,6 +2628,7 @@ extern "C" {
 mcl_status mcl_get_likelihood_field(mcl_ctx* ctx, float* out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, out, "null output");
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "The current sensor model does not support likelihood field");
   if (!ctx->have_map || !ctx->d_field.ptr) return fail(ctx, MCL_ERR_NOT_READY, "no likelihood field");
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2526,6 +2639,7 @@ mcl_status mcl_get_likelihood_field(mcl_ctx* ctx, float* out) {
 mcl_status mcl_set_likelihood_field(mcl_ctx* ctx, const float* field) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, field, "null field");
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_likelihood_field: not on an NDT context (its map comes from mcl_set_ndt_map)");
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "set the map first");
   if (const mcl_status s = bind_device(ctx)) return s;
   const size_t n = static_cast<size_t>(ctx->W) * ctx->H;
@@ -2621,6 +2735,11 @@ mcl_status mcl_reweight(mcl_ctx* ctx, const double* points_xy, uint64_t num_poin
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, num_points == 0 || points_xy, "null points");
   if (const mcl_status s = bind_device(ctx)) return s;
+  if (ctx->is_ndt()) {
+    if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
+    ndt_fit_scan(ctx, points_xy, num_points);
+    return do_reweight(ctx, ctx->h_ndt_meas.data(), ctx->h_ndt_meas.size() / 2);
+  }
   return do_reweight(ctx, points_xy, num_points);
 }
 
@@ -2756,6 +2875,11 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
     }
     return sharded_update(ctx, pose, points_xy, num_points, estimate, info);
   }
+  if (ctx->is_ndt()) {  // the scan's measurement cells (detail::to_cells) are what the cycle uploads: kNdtRecord doubles per cell
+    ndt_fit_scan(ctx, points_xy, num_points);
+    points_xy = ctx->h_ndt_meas.data();
+    num_points = ctx->h_ndt_meas.size() / 2;
+  }
   if (const mcl_status s = stage_points(ctx, points_xy, num_points)) {
     undo_policy();
     return s;
@@ -2777,13 +2901,14 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
   // With a fixed particle count and no selective resampling nothing in the cycle depends on a host-side decision: the
   // recovery estimator runs on the device as well and the cycle synchronises once, at the estimate.
   const mcl_amcl_params& ap = ctx->cfg.amcl;
+  // (not the NDT model: its random states need the estimate of the normalised set where the probability is > 0, a host decision)
   const bool device_policy = !ap.selective_resampling && ap.min_particles >= std::min<uint64_t>(ap.max_particles, ctx->capacity) &&
-                             ctx->tuning.device_policy != 0;
+                             ctx->tuning.device_policy != 0 && !ctx->is_ndt();
   // (the normalisation follows at once: the LF kernel leaves the sums it is built on)
   if (const mcl_status s = do_reweight(ctx, points_xy, num_points, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0)) return s;  // :176
   // Small sets (the reference's own sizes): everything behind the reweight in ONE launch of one workgroup and one synchronisation
   // (k_small_tail) - the policies are evaluated on the device, the host keeps the recovery filters' state.
-  if (ctx->tuning.small_fused != 0 && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096) {
+  if (ctx->tuning.small_fused != 0 && !ctx->is_ndt() && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096) {
     ctx->every_n_current = (ctx->every_n_current + 1) % ap.resample_interval;  // :181
     SmallTail t{};
     t.src = ctx->cur();
@@ -2803,7 +2928,7 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
     t.kld_z = ap.kld_z;
     t.hp = HashParams{ap.spatial_resolution_x, ap.spatial_resolution_y, ap.spatial_resolution_theta};
     t.g = ctx->grid_view();
-    t.fc = FreeCells{ctx->d_free.ptr, ctx->have_map ? ctx->n_free : 0};
+    t.fc = ctx->random_source();
     t.pivot_x = ctx->pivot[0];
     t.pivot_y = ctx->pivot[1];
     t.mirror = ctx->hd_scalars;
@@ -2909,6 +3034,8 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
       do_resampling = ess < static_cast<double>(ctx->n) * 0.5;
     }
     if (do_resampling) {
+      if (ctx->is_ndt())  // :182, the random state generator of ndt_amcl_node (its failure leaves the state the reference's throw leaves)
+        if (const mcl_status s = prepare_ndt_random(ctx, random_state_probability)) return s;
       if (random_state_probability > 0.0) {  // :184-186
         ctx->slow.reset();
         ctx->fast.reset();
@@ -3115,6 +3242,7 @@ mcl_status mcl_build_cdf(mcl_ctx* ctx, double* total) {
 mcl_status mcl_resample_targets(mcl_ctx* ctx, uint32_t step, double random_state_probability, double total,
                                 uint64_t first_slot, uint64_t count, double* d_targets) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_resample_targets: the sharded resampling steps are not available on an NDT context");
   MCL_REQUIRE(ctx, count == 0 || d_targets, "null targets");
   if (const mcl_status s = bind_device(ctx)) return s;
   launch_resample_targets(ctx->stream, ctx->cfg.seed, step, random_state_probability, total, first_slot, count,
@@ -3156,12 +3284,13 @@ mcl_status mcl_serve_requests(mcl_ctx* ctx, const double* d_requests, uint64_t m
 mcl_status mcl_commit_routed(mcl_ctx* ctx, uint32_t step, uint64_t first_slot, uint64_t count, const double* d_replies,
                              const uint32_t* d_order, const double* d_targets) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_commit_routed: the sharded resampling steps are not available on an NDT context");
   MCL_REQUIRE(ctx, count <= ctx->capacity, "count exceeds shard capacity");
   MCL_REQUIRE(ctx, count == 0 || (d_replies && d_order && d_targets), "null argument");
   if (const mcl_status s = bind_device(ctx)) return s;
   stage_begin(ctx, MCL_STAGE_RESAMPLE);
   launch_commit_routed(ctx->stream, ctx->other(), ctx->cfg.seed, step, first_slot, count, d_replies, d_order, d_targets,
-                       ctx->grid_view(), FreeCells{ctx->d_free.ptr, ctx->have_map ? ctx->n_free : 0});
+                       ctx->grid_view(), ctx->random_source());
   stage_end(ctx, MCL_STAGE_RESAMPLE);
   MCL_HIP(ctx, hipGetLastError());
   ctx->live ^= 1;
@@ -3173,12 +3302,13 @@ mcl_status mcl_commit_routed(mcl_ctx* ctx, uint32_t step, uint64_t first_slot, u
 mcl_status mcl_finish_candidates(mcl_ctx* ctx, uint32_t step, uint64_t first_slot, uint64_t count, const double* d_replies,
                                  const uint32_t* d_order, const double* d_targets, double* d_states, uint64_t* d_hashes) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_finish_candidates: the sharded resampling steps are not available on an NDT context");
   MCL_REQUIRE(ctx, count == 0 || (d_replies && d_order && d_targets && d_states && d_hashes), "null argument");
   if (const mcl_status s = bind_device(ctx)) return s;
   const mcl_amcl_params& a = ctx->cfg.amcl;
   stage_begin(ctx, MCL_STAGE_RESAMPLE);
   launch_finish_candidates(ctx->stream, ctx->cfg.seed, step, first_slot, count, d_replies, d_order, d_targets, ctx->grid_view(),
-                           FreeCells{ctx->d_free.ptr, ctx->have_map ? ctx->n_free : 0},
+                           ctx->random_source(),
                            HashParams{a.spatial_resolution_x, a.spatial_resolution_y, a.spatial_resolution_theta}, d_states,
                            reinterpret_cast<unsigned long long*>(d_hashes));
   stage_end(ctx, MCL_STAGE_RESAMPLE);
@@ -3270,6 +3400,7 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   ctx->lf_wsum_count = 0;  // (workgroup sums of an earlier reweight describe another set)
   ctx->order_valid = false;  // (and an order computed ahead describes the particles of another one)
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_initialize_from_map: not on an NDT context (its map comes from mcl_set_ndt_map)");
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no map set");
   MCL_REQUIRE(ctx, ctx->n_free > 0, "mcl_initialize_from_map: the map has no free cell");  // the reference asserts (:136)
   if (const mcl_status s = bind_device(ctx)) return s;
@@ -3307,14 +3438,15 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
 
 mcl_status mcl_has_likelihood_field(const mcl_ctx* ctx, int32_t* has) {
   if (!ctx || !has) return MCL_ERR_INVALID_ARGUMENT;
-  *has = ctx->cfg.sensor_kind != MCL_SENSOR_BEAM ? 1 : 0;  // beam_model.hpp has no likelihood_field() (has_likelihood_field_v)
+  // beam_model.hpp and ndt_sensor_model.hpp have no likelihood_field() (has_likelihood_field_v)
+  *has = ctx->cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD || ctx->cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB ? 1 : 0;
   return MCL_OK;
 }
 
 mcl_status mcl_get_likelihood_field_origin(mcl_ctx* ctx, double origin[4]) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, origin, "null output");
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM)
+  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM || ctx->is_ndt())
     return fail(ctx, MCL_ERR_UNSUPPORTED, "The current sensor model does not support likelihood field");
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "no likelihood field");
   // likelihood_field_model_base.hpp:105: world_to_likelihood_field_transform_.inverse(), i.e. inverse(inverse(grid.origin()))
@@ -3490,6 +3622,7 @@ mcl_status mcl_debug_set_recovery_filters(mcl_ctx* ctx, double slow, double fast
 
 mcl_status mcl_comm_attach(mcl_ctx* ctx, uint32_t rank, uint32_t world, const mcl_transport* transport) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach: the NDT model runs on one device");
   MCL_REQUIRE(ctx, world >= 1 && world <= 64 && rank < world, "mcl_comm_attach: world must be 1..64, rank < world");
   MCL_REQUIRE(ctx, world == 1 || (transport && transport->all_gather && transport->all_to_all), "mcl_comm_attach: incomplete transport");
   MCL_REQUIRE(ctx, world == 1 || ctx->cfg.shard_capacity > 0, "mcl_comm_attach: create the context with its shard_offset / shard_capacity");
@@ -3523,6 +3656,7 @@ mcl_status mcl_comm_unique_id(uint8_t id[128]) {
 
 mcl_status mcl_comm_attach_rccl(mcl_ctx* ctx, const uint8_t id[128], uint32_t rank, uint32_t world) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach_rccl: the NDT model runs on one device");
   MCL_REQUIRE(ctx, id && world >= 1 && world <= 64 && rank < world, "mcl_comm_attach_rccl: bad argument");
   std::string error;
   RcclApi* api = rccl_api(&error);
@@ -3543,6 +3677,137 @@ mcl_status mcl_comm_attach_rccl(mcl_ctx* ctx, const uint8_t id[128], uint32_t ra
   }
   const mcl_transport t{&ctx->rccl_user, rccl_all_gather, rccl_all_to_all};
   return mcl_comm_attach(ctx, rank, world, &t);
+}
+
+// ---- 2D NDT sensor model --------------------------------------------------------------------------------------------------
+void mcl_default_ndt_params(mcl_ndt_params* params) {
+  if (!params) return;
+  std::memset(params, 0, sizeof(*params));
+  params->minimum_likelihood = 0.0;  // NDTModelParam (ndt_sensor_model.hpp:153-166)
+  params->d1 = 1.0;
+  params->d2 = 1.0;
+  static const int32_t kernel[9][2] = {{-1, -1}, {-1, 0}, {-1, 1}, {0, -1}, {0, 0}, {0, 1}, {1, -1}, {1, 0}, {1, 1}};  // :113-123
+  params->num_offsets = 9;
+  for (int k = 0; k < 9; ++k) {
+    params->offsets[2 * k] = kernel[k][0];
+    params->offsets[2 * k + 1] = kernel[k][1];
+  }
+}
+
+mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* means, const double* covariances, uint64_t n,
+                           double resolution, const mcl_ndt_params* params) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  MCL_REQUIRE(ctx, ctx->is_ndt(), "mcl_set_ndt_map: the context's sensor model is not MCL_SENSOR_NDT");
+  MCL_REQUIRE(ctx, cells && means && covariances && n > 0, "mcl_set_ndt_map: null argument or no cells");
+  MCL_REQUIRE(ctx, n < (1ull << 31), "mcl_set_ndt_map: too many cells");
+  MCL_REQUIRE(ctx, std::isfinite(resolution) && resolution > 0.0, "mcl_set_ndt_map: resolution must be positive and finite");
+  mcl_ndt_params prm;
+  if (params) prm = *params;
+  else mcl_default_ndt_params(&prm);
+  MCL_REQUIRE(ctx, prm.num_offsets >= 1 && prm.num_offsets <= MCL_NDT_MAX_OFFSETS, "mcl_set_ndt_map: 1 .. 32 kernel offsets");
+  MCL_REQUIRE(ctx, std::isfinite(prm.d1) && std::isfinite(prm.d2) && std::isfinite(prm.minimum_likelihood) && prm.minimum_likelihood >= 0.0,
+              "mcl_set_ndt_map: d1, d2 must be finite and minimum_likelihood finite and >= 0");
+  int32_t reach = 1;
+  for (uint32_t k = 0; k < 2 * prm.num_offsets; ++k) {
+    MCL_REQUIRE(ctx, prm.offsets[k] >= -64 && prm.offsets[k] <= 64, "mcl_set_ndt_map: kernel offsets are limited to 64 cells");
+    reach = std::max(reach, std::abs(prm.offsets[k]));
+  }
+  int64_t x0 = INT64_MAX, y0 = INT64_MAX, x1 = INT64_MIN, y1 = INT64_MIN;
+  for (uint64_t i = 0; i < n; ++i) {
+    x0 = std::min<int64_t>(x0, cells[2 * i]);
+    x1 = std::max<int64_t>(x1, cells[2 * i]);
+    y0 = std::min<int64_t>(y0, cells[2 * i + 1]);
+    y1 = std::max<int64_t>(y1, cells[2 * i + 1]);
+    const double* m = means + 2 * i;
+    const double* c = covariances + 4 * i;
+    MCL_REQUIRE(ctx, std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) &&
+                         std::isfinite(c[3]),
+                "mcl_set_ndt_map: cell " + std::to_string(i) + " has a value that is not finite");
+    MCL_REQUIRE(ctx, std::abs(c[1] - c[2]) <= 1e-12 * std::max(std::abs(c[1]), std::abs(c[2])),
+                "mcl_set_ndt_map: the covariance of cell " + std::to_string(i) + " is not symmetric");
+  }
+  // index grid: the keys' box with a border of 2 * reach (kernels.h NdtMapView)
+  const int64_t gw = (x1 - x0 + 1) + 4 * reach, gh = (y1 - y0 + 1) + 4 * reach;
+  constexpr int64_t kMaxGridCells = int64_t{1} << 26;
+  if (gw > kMaxGridCells || gh > kMaxGridCells || gw * gh > kMaxGridCells)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_map: the bounding box of the keys exceeds 2^26 cells (" + std::to_string(gw) + " x " +
+                                              std::to_string(gh) + " with its border)");
+  std::vector<int32_t> grid(static_cast<size_t>(gw * gh), -1);
+  std::vector<double> recs(static_cast<size_t>(n) * kNdtRecord);
+  for (uint64_t i = 0; i < n; ++i) {
+    const size_t at = static_cast<size_t>((cells[2 * i + 1] - y0 + 2 * reach) * gw + (cells[2 * i] - x0 + 2 * reach));
+    MCL_REQUIRE(ctx, grid[at] < 0, "mcl_set_ndt_map: duplicate key (" + std::to_string(cells[2 * i]) + ", " + std::to_string(cells[2 * i + 1]) + ")");
+    grid[at] = static_cast<int32_t>(i);
+    const double* m = means + 2 * i;
+    const double* c = covariances + 4 * i;
+    const double r[kNdtRecord] = {m[0], m[1], c[0], c[1], c[3], 0.0};
+    std::copy(r, r + kNdtRecord, recs.begin() + static_cast<ptrdiff_t>(i * kNdtRecord));
+  }
+  if (const mcl_status s = bind_device(ctx)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a reweight in flight may still read the old map)
+  ctx->have_ndt_map = false;  // (until the new map is complete: ensure() may free the buffers the old view points at)
+  MCL_HIP(ctx, ctx->d_ndt_grid.ensure(grid.size()));
+  MCL_HIP(ctx, ctx->d_ndt_cells.ensure(recs.size()));
+  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_grid.ptr, grid.data(), grid.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_cells.ptr, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
+  NdtMapView v{};
+  v.grid = ctx->d_ndt_grid.ptr;
+  v.cells = ctx->d_ndt_cells.ptr;
+  v.gw = static_cast<uint32_t>(gw);
+  v.inv_resolution = 1. / resolution;
+  v.key_x0 = static_cast<double>(x0 - reach);
+  v.key_y0 = static_cast<double>(y0 - reach);
+  v.box_w = static_cast<double>(x1 - x0 + 1 + 2 * reach);
+  v.box_h = static_cast<double>(y1 - y0 + 1 + 2 * reach);
+  v.reach = reach;
+  v.d1 = prm.d1;
+  v.d2 = prm.d2;
+  v.minimum_likelihood = prm.minimum_likelihood;
+  v.num_offsets = prm.num_offsets;
+  for (uint32_t k = 0; k < prm.num_offsets; ++k) v.delta[k] = prm.offsets[2 * k + 1] * static_cast<int32_t>(gw) + prm.offsets[2 * k];
+  ctx->ndt_view = v;
+  ctx->ndt_map_cells = n;
+  ctx->ndt_resolution = resolution;
+  ctx->have_ndt_map = true;
+  return MCL_OK;
+}
+
+mcl_status mcl_ndt_measurement_cells(const double* points_xy, uint64_t num_points, double resolution, double* means_out, double* covs_out,
+                                     uint64_t* num_cells) {
+  if (!num_cells || (num_points && !points_xy) || !(std::isfinite(resolution) && resolution > 0.0)) return MCL_ERR_INVALID_ARGUMENT;
+  if (num_points >= 5 && (!means_out || !covs_out)) return MCL_ERR_INVALID_ARGUMENT;
+  std::vector<double> recs;
+  ndt_fit_cells(points_xy, num_points, resolution, recs);
+  const uint64_t k = recs.size() / kNdtRecord;
+  for (uint64_t j = 0; j < k; ++j) {
+    const double* r = recs.data() + j * kNdtRecord;
+    means_out[2 * j] = r[0];
+    means_out[2 * j + 1] = r[1];
+    covs_out[4 * j] = r[2];
+    covs_out[4 * j + 1] = r[3];
+    covs_out[4 * j + 2] = r[3];
+    covs_out[4 * j + 3] = r[4];
+  }
+  *num_cells = k;
+  return MCL_OK;
+}
+
+mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const double* covs, uint64_t num_cells) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  MCL_REQUIRE(ctx, ctx->is_ndt(), "mcl_reweight_ndt_cells: the context's sensor model is not MCL_SENSOR_NDT");
+  MCL_REQUIRE(ctx, num_cells == 0 || (means && covs), "null argument");
+  MCL_REQUIRE(ctx, num_cells < (1ull << 28), "too many cells");
+  if (const mcl_status s = reweight_preconditions(ctx, 0)) return s;
+  std::vector<double>& recs = ctx->h_ndt_meas;
+  recs.assign(static_cast<size_t>(num_cells) * kNdtRecord, 0.0);
+  for (uint64_t j = 0; j < num_cells; ++j) {
+    const double* c = covs + 4 * j;
+    MCL_REQUIRE(ctx, std::abs(c[1] - c[2]) <= 1e-12 * std::max(std::abs(c[1]), std::abs(c[2])), "mcl_reweight_ndt_cells: asymmetric covariance");
+    const double r[kNdtRecord] = {means[2 * j], means[2 * j + 1], c[0], c[1], c[3], 0.0};
+    std::copy(r, r + kNdtRecord, recs.begin() + static_cast<ptrdiff_t>(j * kNdtRecord));
+  }
+  if (const mcl_status s = bind_device(ctx)) return s;
+  return do_reweight(ctx, recs.data(), recs.size() / 2);
 }
 
 mcl_status mcl_sync(mcl_ctx* ctx) {

@@ -92,10 +92,39 @@ struct DiffDriveSampler {
   double first_c, first_s;
 };
 
+// Where random_intersperse's random states come from (random_free_state, kernels.hip).  Likelihood-field and beam models: uniformly
+// over the free cells of the occupancy grid (multivariate_uniform_distribution.hpp:126-161).  NDT model (normal != 0): N(mean, T T^T)
+// as mean + T z (ndt_amcl_node.cpp:248-254; multivariate_normal_distribution.hpp:109-126), count = 1 so that the Bernoulli stream
+// selects the same slots; the host fills mean / T from the estimate of the normalised set just before the draw.
 struct FreeCells {
   const uint32_t* index;  // linear indices of free cells
   uint64_t count;
+  int normal{0};
+  double mean[3]{0.0, 0.0, 0.0};  // x, y, theta
+  double T[9]{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // row-major
 };
+
+// The NDT model's map (ndt_kernels.hip): a dense int32 index grid over the bounding box of the map's keys with a border of 2 * reach
+// cells (reach = the largest |component| of a kernel offset, at least 1), -1 where no cell is present, plus the cell records.  A
+// measurement cell whose centre key lies farther than `reach` from the keys' box has no neighbour in the map (one test); any other
+// centre key's offsets stay inside the grid (no per-offset test).
+constexpr int kNdtMaxOffsets = 32;
+constexpr int kNdtRecord = 6;  // doubles per cell record: mean x, y, covariance xx, xy, yy, 0
+struct NdtMapView {
+  const int32_t* grid;  // gw x gh, row-major
+  const double* cells;  // kNdtRecord doubles per map cell
+  uint32_t gw;
+  double inv_resolution;           // 1. / resolution (regular_grid.hpp:76)
+  double key_x0, key_y0;           // key of the centre box's first cell = (smallest key) - reach
+  double box_w, box_h;             // size of the centre box (key span + 2 reach)
+  int32_t reach;                   // grid index of centre-box cell (0, 0) = reach * gw + reach
+  double d1, d2, minimum_likelihood;
+  uint32_t num_offsets;
+  int32_t delta[kNdtMaxOffsets];   // dy * gw + dx of each kernel offset, in the kernel's order
+};
+// NDTSensorModel::operator() (ndt_sensor_model.hpp:216-239): w[i] *= 1 + sum over the k measurement cells (kNdtRecord doubles each,
+// base frame) of max(sum of the present neighbours' d1 exp(-d2/2 e^T (S' + S_map)^-1 e), minimum_likelihood).  A lane per particle.
+void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k);
 
 struct HashParams {
   double res_x, res_y, res_theta;

@@ -2745,6 +2745,17 @@ __device__ __forceinline__ uint64_t cdf_tree_lower_bound_staged(const CdfTree& t
 // multivariate_uniform_distribution.hpp:145-147 over occupancy_grid.hpp:140-146,164-171: uniform heading,
 // centre of a uniformly chosen free cell in the world frame.  Addressed by the candidate's global index.
 __device__ __forceinline__ Pose2 random_free_state(uint64_t seed, uint32_t step, uint64_t j, const GridView& g, const FreeCells& fc) {
+  if (fc.normal) {  // NDT model: mean + T z (ndt_amcl_node.cpp:248-254), z from a stream of its own; the same arithmetic as k_init_normal
+    const RngWords a = rng_draw(seed, step, kRngRandomNormalA, j);
+    const RngWords b = rng_draw(seed, step, kRngRandomNormalB, j);
+    double z0, z1, z2, z3;
+    rng_box_muller(rng_uniform53(a.w[0], a.w[1]), rng_uniform53(a.w[2], a.w[3]), z0, z1);
+    rng_box_muller(rng_uniform53(b.w[0], b.w[1]), rng_uniform53(b.w[2], b.w[3]), z2, z3);
+    const double vx = fc.mean[0] + (fc.T[0] * z0 + fc.T[1] * z1 + fc.T[2] * z2);
+    const double vy = fc.mean[1] + (fc.T[3] * z0 + fc.T[4] * z1 + fc.T[5] * z2);
+    const double vt = fc.mean[2] + (fc.T[6] * z0 + fc.T[7] * z1 + fc.T[8] * z2);
+    return Pose2{rot_exp(vt), vx, vy};
+  }
   const RngWords q = rng_draw(seed, step, kRngRandomState, j);
   uint64_t cell = static_cast<uint64_t>(rng_uniform53(q.w[0], q.w[1]) * static_cast<double>(fc.count));
   if (cell >= fc.count) cell = fc.count - 1;

@@ -1,0 +1,78 @@
+// ndt_kernels.hip — the 2D NDT sensor model's reweight on gfx950: beluga::NDTSensorModel<SparseValueGrid2<...NDTCell2d...>>
+// (sensor/ndt_sensor_model.hpp:216-239; sensor/data/ndt_cell.hpp:49-68).
+//
+// A lane per particle, f64 throughout.  The measurement cells of the scan (a few hundred at most: one per 5 points) are the same for
+// every lane and are read at wave-uniform addresses (scalar loads).  Per (particle, measurement cell): the cell moved into the world
+// by the pose, its centre key, then for each offset of the neighbour kernel one int32 look-up in the index grid (kernels.h
+// NdtMapView) and, where a map cell is present, one record of 48 bytes and one f64 exponential.  The grid and the records are a
+// few hundred KB for a building-sized map at 1 m: they stay in L2.
+#include <hip/hip_runtime.h>
+
+#include "device_common.hpp"
+
+namespace mcl {
+namespace {
+
+// likelihood_at(state * measurement) (ndt_sensor_model.hpp:229-239) of measurement cell `c` for the pose (c, s, x, y).
+__device__ __forceinline__ double ndt_cell_likelihood(const NdtMapView& m, const double* __restrict__ c, const Pose2& p) {
+  const double mx = c[0], my = c[1], sa = c[2], sb = c[3], sd = c[4];
+  const double rc = p.r.c, rs = p.r.s;
+  // SE2 * NDTCell (ndt_cell.hpp:61-66): mean = so2 * mean + t (Sophus: real * x - imag * y, imag * x + real * y),
+  // covariance = R S R^T, evaluated as (R S) R^T with R = [[c, -s], [s, c]]
+  const double ux = (rc * mx - rs * my) + p.x;
+  const double uy = (rs * mx + rc * my) + p.y;
+  const double t00 = rc * sa - rs * sb, t01 = rc * sb - rs * sd;
+  const double t10 = rs * sa + rc * sb, t11 = rs * sb + rc * sd;
+  const double c00 = t00 * rc - t01 * rs, c01 = t00 * rs + t01 * rc;
+  const double c10 = t10 * rc - t11 * rs, c11 = t10 * rs + t11 * rc;
+  // cell_near (regular_grid.hpp:75-78): floor(p * (1 / resolution)), relative to the centre box; outside it no offset reaches a key
+  const double fx = floor(ux * m.inv_resolution) - m.key_x0;
+  const double fy = floor(uy * m.inv_resolution) - m.key_y0;
+  double likelihood = 0.0;
+  if (fx >= 0.0 && fx < m.box_w && fy >= 0.0 && fy < m.box_h) {
+    const int32_t centre = (static_cast<int32_t>(fy) + m.reach) * static_cast<int32_t>(m.gw) + static_cast<int32_t>(fx) + m.reach;
+    const double scale = -m.d2 / 2.0;
+    for (uint32_t o = 0; o < m.num_offsets; ++o) {
+      const int32_t idx = m.grid[centre + m.delta[o]];
+      if (idx < 0) continue;
+      const double2* rec = reinterpret_cast<const double2*>(m.cells + static_cast<size_t>(idx) * kNdtRecord);
+      const double2 mean = rec[0], ab = rec[1], d_ = rec[2];
+      // NDTCell::likelihood_at (ndt_cell.hpp:49-54): d1 exp((-d2 / 2) e^T (S' + S_map)^-1 e); Eigen's 2 x 2 inverse: adjugate / det
+      const double e0 = ux - mean.x, e1 = uy - mean.y;
+      const double s00 = c00 + ab.x, s01 = c01 + ab.y, s10 = c10 + ab.y, s11 = c11 + d_.x;
+      const double inv_det = 1.0 / (s00 * s11 - s10 * s01);
+      const double i00 = s11 * inv_det, i01 = -s01 * inv_det, i10 = -s10 * inv_det, i11 = s00 * inv_det;
+      const double v0 = scale * e0, v1 = scale * e1;
+      const double r0 = v0 * i00 + v1 * i10, r1 = v0 * i01 + v1 * i11;
+      likelihood += m.d1 * exp(r0 * e0 + r1 * e1);
+    }
+  }
+  return likelihood > m.minimum_likelihood ? likelihood : m.minimum_likelihood;  // std::max(likelihood, minimum_likelihood)
+}
+
+__global__ __launch_bounds__(kBlock) void k_reweight_ndt(Particles p, uint64_t n, NdtMapView m, const double* __restrict__ meas, uint32_t k) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const Pose2 s = load_pose(p, i);
+  // std::transform_reduce(cells, 1.0, plus, ...) (ndt_sensor_model.hpp:219-224) as libstdc++ adds it: blocks of four, the rest one by one
+  double acc = 1.0;
+  uint32_t j = 0;
+  for (; j + 4 <= k; j += 4) {
+    const double l0 = ndt_cell_likelihood(m, meas + (j + 0) * kNdtRecord, s);
+    const double l1 = ndt_cell_likelihood(m, meas + (j + 1) * kNdtRecord, s);
+    const double l2 = ndt_cell_likelihood(m, meas + (j + 2) * kNdtRecord, s);
+    const double l3 = ndt_cell_likelihood(m, meas + (j + 3) * kNdtRecord, s);
+    acc += sum4(l0, l1, l2, l3);
+  }
+  for (; j < k; ++j) acc += ndt_cell_likelihood(m, meas + j * kNdtRecord, s);
+  p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
+}
+
+}  // namespace
+
+void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_reweight_ndt, dim3(blocks_for(n)), dim3(kBlock), 0, st, p, n, m, meas, k);
+}
+
+}  // namespace mcl

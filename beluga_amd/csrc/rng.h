@@ -19,6 +19,8 @@ enum RngPurpose : uint32_t {
   kRngRandomState = 3, // words 0,1 -> free cell; words 2,3 -> heading
   kRngInitA = 4,
   kRngInitB = 5,
+  kRngRandomNormalA = 6,  // NDT model's random states N(estimate): words 0..3 -> (z0, z1)
+  kRngRandomNormalB = 7,  //                                         words 0..3 -> (z2, -)
 };
 
 struct RngWords {

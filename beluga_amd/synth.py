@@ -110,3 +110,34 @@ def normal_particles(n: int, mean_xytheta, sigmas, seed: int = 7) -> np.ndarray:
 def odometry_step(pose_xytheta, forward: float, turn: float):
     x, y, t = pose_xytheta
     return (x + forward * math.cos(t), y + forward * math.sin(t), t + turn)
+
+
+def make_ndt_map(cells: np.ndarray, resolution: float, ndt_resolution: float, origin_xy=(0.0, 0.0), seed: int = 0, min_points: int = 5):
+    """An NDT map of an occupancy grid (the project's own fit, not the reference's map builder): the centres of the occupied cells,
+    jittered by up to a tenth of a cell (seeded) so that straight walls keep a little spread, grouped by floor(p / ndt_resolution) -
+    the keys cell_near gives a look-up - and fitted like fit_points (mean, sample covariance, diagonal >= 1e-5).  Groups of fewer
+    than `min_points` points are dropped.  Returns (keys[n,2] int32, means[n,2], covariances[n,2,2])."""
+    occ = np.argwhere(np.asarray(cells) == OCCUPIED)
+    rng = np.random.Generator(np.random.PCG64(seed))
+    pts = np.stack([(occ[:, 1] + 0.5) * resolution + origin_xy[0], (occ[:, 0] + 0.5) * resolution + origin_xy[1]], 1)
+    pts = pts + rng.uniform(-0.1, 0.1, pts.shape) * resolution
+    keys = np.floor(pts / ndt_resolution).astype(np.int64)
+    order = np.lexsort((keys[:, 1], keys[:, 0]))
+    keys, pts = keys[order], pts[order]
+    bounds = np.flatnonzero(np.any(np.diff(keys, axis=0) != 0, axis=1)) + 1
+    starts = np.concatenate([[0], bounds])
+    ends = np.concatenate([bounds, [len(keys)]])
+    out_k, out_m, out_c = [], [], []
+    for a, b in zip(starts, ends):
+        if b - a < min_points:
+            continue
+        g = pts[a:b]
+        m = g.mean(axis=0)
+        d = g - m
+        cov = d.T @ d / (len(g) - 1)
+        cov[0, 0] = max(cov[0, 0], 1e-5)
+        cov[1, 1] = max(cov[1, 1], 1e-5)
+        out_k.append(keys[a])
+        out_m.append(m)
+        out_c.append(cov)
+    return (np.asarray(out_k, dtype=np.int32).reshape(-1, 2), np.asarray(out_m).reshape(-1, 2), np.asarray(out_c).reshape(-1, 2, 2))

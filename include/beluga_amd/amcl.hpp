@@ -133,7 +133,52 @@ struct BeamModelParam {
 /// beluga::LikelihoodFieldProbModelParam (sensor/likelihood_field_prob_model.hpp:34): same fields, other weighting.
 struct LikelihoodFieldProbModelParam : LikelihoodFieldModelParam {};
 
-using SensorModelParam = std::variant<LikelihoodFieldModelParam, BeamModelParam, LikelihoodFieldProbModelParam>;
+/// beluga::NDTModelParam2d (sensor/ndt_sensor_model.hpp:153-166): the reference's defaults; ndt_amcl_node's are 0.01 / 1.0 / 0.6.
+struct NDTModelParam2d {
+  double minimum_likelihood = 0.0;
+  double d1 = 1.0;
+  double d2 = 1.0;
+  std::vector<std::array<int, 2>> neighbors_kernel = {{-1, -1}, {-1, 0}, {-1, 1}, {0, -1}, {0, 0}, {0, 1}, {1, -1}, {1, 0}, {1, 1}};
+};
+
+using SensorModelParam = std::variant<LikelihoodFieldModelParam, BeamModelParam, LikelihoodFieldProbModelParam, NDTModelParam2d>;
+
+/// One NDTCell2d (sensor/data/ndt_cell.hpp): mean and 2 x 2 covariance (row-major).
+struct NDTCell2d {
+  std::array<double, 2> mean{};
+  std::array<double, 4> covariance{};
+};
+
+/// The NDT sensor model's map with the accessors of beluga::SparseValueGrid2 (sensor/data/sparse_value_grid.hpp) that code written
+/// against it reads: resolution(), size(), data_at(key) (std::nullopt where no cell is present), cell_near(point).  The cells are
+/// kept in the load_from_hdf5 layout, which is what the device map is built from.
+class NDTMap2d {
+ public:
+  using key_type = std::array<int, 2>;
+  NDTMap2d() = default;
+  NDTMap2d(std::vector<key_type> cells, std::vector<NDTCell2d> data, double resolution)
+      : cells_(std::move(cells)), data_(std::move(data)), resolution_(resolution) {
+    if (cells_.size() != data_.size()) throw std::invalid_argument("NDTMap2d: keys and cells differ in number");
+  }
+  [[nodiscard]] double resolution() const { return resolution_; }
+  [[nodiscard]] std::size_t size() const { return cells_.size(); }
+  [[nodiscard]] const std::vector<key_type>& keys() const { return cells_; }
+  [[nodiscard]] const std::vector<NDTCell2d>& cells() const { return data_; }
+  [[nodiscard]] std::optional<NDTCell2d> data_at(const key_type& key) const {
+    for (std::size_t i = 0; i < cells_.size(); ++i)
+      if (cells_[i] == key) return data_[i];
+    return std::nullopt;
+  }
+  [[nodiscard]] key_type cell_near(double x, double y) const {  // regular_grid.hpp:75-78
+    const double inv = 1. / resolution_;
+    return {static_cast<int>(std::floor(x * inv)), static_cast<int>(std::floor(y * inv))};
+  }
+
+ private:
+  std::vector<key_type> cells_;
+  std::vector<NDTCell2d> data_;
+  double resolution_{1.0};
+};
 
 /// A non-owning view of anything satisfying OccupancyGrid2 (sensor/data/occupancy_grid.hpp:39-75).
 struct OccupancyGridView {
@@ -283,6 +328,34 @@ class Amcl {
   Amcl(const OccupancyGridView& map, const MotionModelParam& motion, const SensorModelParam& sensor,
        const AmclParams& params = AmclParams{}, std::uint64_t seed = 0, int device = 0,
        const std::vector<std::pair<std::string, std::int64_t>>& options = {}, const Shard& shard = Shard{}) {
+    if (std::holds_alternative<NDTModelParam2d>(sensor)) throw std::invalid_argument("beluga_amd::Amcl: the NDT sensor model takes an NDTMap2d");
+    create(make_config(motion, sensor, params, seed, device, shard), params, options);
+    try {
+      update_map(map);
+    } catch (...) {
+      mcl_destroy(ctx_);
+      ctx_ = nullptr;
+      throw;
+    }
+  }
+  /// The filter of ndt_amcl_node (beluga_amcl/include/beluga_amcl/ndt_amcl_node.hpp:77-84): beluga::Amcl with the NDT sensor model.
+  /// Code written for `NdtAmcl<Motion, Policy>` switches by a type alias: construction from (map, motion, NDTModelParam2d, params).
+  Amcl(const NDTMap2d& map, const MotionModelParam& motion, const NDTModelParam2d& sensor, const AmclParams& params = AmclParams{},
+       std::uint64_t seed = 0, int device = 0, const std::vector<std::pair<std::string, std::int64_t>>& options = {})
+      : ndt_params_(sensor) {
+    create(make_config(motion, SensorModelParam{sensor}, params, seed, device, Shard{}), params, options);
+    try {
+      update_map(map);
+    } catch (...) {
+      mcl_destroy(ctx_);
+      ctx_ = nullptr;
+      throw;
+    }
+  }
+
+ private:
+  static mcl_config make_config(const MotionModelParam& motion, const SensorModelParam& sensor, const AmclParams& params, std::uint64_t seed,
+                                int device, const Shard& shard) {
     mcl_config cfg;
     mcl_default_config(&cfg);
     cfg.device_id = device;
@@ -323,23 +396,28 @@ class Amcl {
                                                                                      : MCL_SENSOR_LIKELIHOOD_FIELD;
       cfg.lf = mcl_lf_params{lf->max_obstacle_distance, lf->max_laser_distance, lf->z_hit, lf->z_random, lf->sigma_hit,
                              lf->model_unknown_space ? 1 : 0, lf->only_obstacle_boundaries ? 1 : 0};
-    } else {
-      const auto& b = std::get<BeamModelParam>(sensor);
+    } else if (const auto* b = std::get_if<BeamModelParam>(&sensor)) {
       cfg.sensor_kind = MCL_SENSOR_BEAM;
-      cfg.beam = mcl_beam_params{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range};
+      cfg.beam = mcl_beam_params{b->z_hit, b->z_short, b->z_max, b->z_rand, b->sigma_hit, b->lambda_short, b->beam_max_range};
+    } else {
+      cfg.sensor_kind = MCL_SENSOR_NDT;
     }
+    return cfg;
+  }
+  void create(const mcl_config& cfg, const AmclParams& params, const std::vector<std::pair<std::string, std::int64_t>>& options) {
     max_particles_ = params.max_particles;
     const mcl_status st = mcl_create(&cfg, &ctx_);
     if (st != MCL_OK) throw std::runtime_error(std::string("beluga_amd::Amcl: ") + mcl_last_error(nullptr));
     try {
       for (const auto& [name, value] : options) check(mcl_set_option(ctx_, name.c_str(), value));
-      update_map(map);
     } catch (...) {
       mcl_destroy(ctx_);
       ctx_ = nullptr;
       throw;
     }
   }
+
+ public:
   Amcl(const Amcl&) = delete;
   Amcl& operator=(const Amcl&) = delete;
   Amcl(Amcl&& other) noexcept
@@ -348,7 +426,8 @@ class Amcl {
         height_(other.height_),
         max_particles_(other.max_particles_),
         resolution_(other.resolution_),
-        has_field_(other.has_field_) {
+        has_field_(other.has_field_),
+        ndt_params_(std::move(other.ndt_params_)) {
     other.ctx_ = nullptr;
   }
   ~Amcl() { mcl_destroy(ctx_); }
@@ -381,6 +460,35 @@ class Amcl {
     const std::vector<double> ones(states.size(), 1.0);
     check(mcl_set_particles(ctx_, states.empty() ? nullptr : states.data()->data(), ones.data(), states.size()));
     dirty_ = true;
+  }
+
+  /// Update the NDT map used for localization (amcl_core.hpp:150 on the NDT filter).
+  void update_map(const NDTMap2d& map) {
+    if (ndt_params_.neighbors_kernel.empty() || ndt_params_.neighbors_kernel.size() > MCL_NDT_MAX_OFFSETS) throw std::invalid_argument("beluga_amd::Amcl: the neighbours kernel takes 1 .. 32 offsets");
+    std::vector<std::int32_t> keys;
+    std::vector<double> means, covs;
+    keys.reserve(2 * map.size());
+    means.reserve(2 * map.size());
+    covs.reserve(4 * map.size());
+    for (std::size_t i = 0; i < map.size(); ++i) {
+      keys.push_back(map.keys()[i][0]);
+      keys.push_back(map.keys()[i][1]);
+      means.insert(means.end(), map.cells()[i].mean.begin(), map.cells()[i].mean.end());
+      covs.insert(covs.end(), map.cells()[i].covariance.begin(), map.cells()[i].covariance.end());
+    }
+    mcl_ndt_params p;
+    mcl_default_ndt_params(&p);
+    p.minimum_likelihood = ndt_params_.minimum_likelihood;
+    p.d1 = ndt_params_.d1;
+    p.d2 = ndt_params_.d2;
+    p.num_offsets = static_cast<std::uint32_t>(ndt_params_.neighbors_kernel.size());
+    for (std::size_t k = 0; k < ndt_params_.neighbors_kernel.size(); ++k) {
+      p.offsets[2 * k] = ndt_params_.neighbors_kernel[k][0];
+      p.offsets[2 * k + 1] = ndt_params_.neighbors_kernel[k][1];
+    }
+    check(mcl_set_ndt_map(ctx_, keys.data(), means.data(), covs.data(), map.size(), map.resolution(), &p));
+    has_field_ = false;
+    field_.reset();
   }
 
   /// Update the map used for localization (amcl_core.hpp:150).
@@ -581,6 +689,7 @@ class Amcl {
   std::size_t max_particles_{0};
   double resolution_{0.0};
   bool has_field_{false};
+  NDTModelParam2d ndt_params_{};
   mutable ParticleSet mirror_;
   mutable bool dirty_{true};
   mutable std::optional<ValueGrid2<float>> field_;

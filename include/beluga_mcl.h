@@ -45,8 +45,10 @@ enum {
 };
 
 /* LikelihoodFieldModel (sensor/likelihood_field_model.hpp), BeamSensorModel (sensor/beam_model.hpp),
- * LikelihoodFieldProbModel (sensor/likelihood_field_prob_model.hpp): beluga_ros::Amcl's sensor variants. */
-enum { MCL_SENSOR_LIKELIHOOD_FIELD = 0, MCL_SENSOR_BEAM = 1, MCL_SENSOR_LIKELIHOOD_FIELD_PROB = 2 };
+ * LikelihoodFieldProbModel (sensor/likelihood_field_prob_model.hpp): beluga_ros::Amcl's sensor variants.
+ * NDTSensorModel over a SparseValueGrid2 of NDTCell2d (sensor/ndt_sensor_model.hpp): the filter of beluga_amcl's ndt_amcl_node
+ * (its map comes from mcl_set_ndt_map, see "2D NDT sensor model" below). */
+enum { MCL_SENSOR_LIKELIHOOD_FIELD = 0, MCL_SENSOR_BEAM = 1, MCL_SENSOR_LIKELIHOOD_FIELD_PROB = 2, MCL_SENSOR_NDT = 3 };
 /* DifferentialDriveModel, OmnidirectionalDriveModel (motion/omnidirectional_drive_model.hpp:102-146),
  * StationaryModel (motion/stationary_model.hpp:55-61): beluga_ros::Amcl's motion variants. */
 enum { MCL_MOTION_DIFFERENTIAL = 0, MCL_MOTION_OMNIDIRECTIONAL = 1, MCL_MOTION_STATIONARY = 2 };
@@ -211,6 +213,49 @@ mcl_status mcl_update_laser_scan(mcl_ctx* ctx, const double control_pose[4], con
 mcl_status mcl_project_point_cloud(const float* points_xyz, uint64_t num_points, const double origin_se3[7], double* points_xy);
 mcl_status mcl_update_point_cloud(mcl_ctx* ctx, const double control_pose[4], const float* points_xyz, uint64_t num_points,
                                   const double origin_se3[7], mcl_estimate* estimate, mcl_update_info* info);
+
+/* ---- 2D NDT sensor model (sensor/ndt_sensor_model.hpp; beluga_amcl/src/ndt_amcl_node.cpp) ----------------------------------
+ * A context created with sensor_kind = MCL_SENSOR_NDT takes its map from mcl_set_ndt_map instead of mcl_set_map: a sparse grid of
+ * NDT cells (SparseValueGrid2<unordered_map<Vector2i, NDTCell2d>>) at one resolution, no origin.  mcl_update (and _laser_scan,
+ * _point_cloud) then fits the measurement cells of the scan on the host (detail::to_cells, ndt_sensor_model.hpp:88-110) and weighs
+ * every particle on the device: w *= 1 + sum over the measurement cells of
+ *   max(sum over the kernel's offsets of the map cells present at cell_near(mu') + offset of d1 exp(-d2/2 e^T (S' + S_map)^-1 e),
+ *       minimum_likelihood)
+ * (operator() :216-226, likelihood_at :229-239, NDTCell::likelihood_at and SE2 * NDTCell: sensor/data/ndt_cell.hpp:49-68).
+ * random_intersperse's random states are drawn from N(estimate of the normalised set) instead of uniformly over free cells
+ * (ndt_amcl_node.cpp:248-254): estimated just before the draw, in cycles whose random state probability is > 0; a covariance the
+ * normal distribution rejects returns MCL_ERR_BAD_COVARIANCE before the draw: as where the reference throws (amcl_core.hpp:182), the set
+ * has then been propagated, reweighted and normalised and the recovery estimator and resample policy have advanced, but no particle
+ * has been replaced and the estimator has not been reset.
+ * Not on an NDT context (MCL_ERR_UNSUPPORTED): mcl_set_map[_async], mcl_initialize_from_map, mcl_get_likelihood_field_origin,
+ * mcl_set_likelihood_field, comm attach and the sharded resampling steps (mcl_resample_targets, mcl_commit_routed,
+ * mcl_finish_candidates); mcl_get_likelihood_field returns MCL_ERR_UNSUPPORTED and mcl_has_likelihood_field 0. */
+#define MCL_NDT_MAX_OFFSETS 32
+/* beluga::NDTModelParam2d (ndt_sensor_model.hpp:153-166). */
+typedef struct mcl_ndt_params {
+  double minimum_likelihood; /* 0 */
+  double d1;                 /* 1 */
+  double d2;                 /* 1 */
+  uint32_t num_offsets;      /* 9: the 3 x 3 block of kDefaultNeighborKernel2d (:113-123), in its order */
+  int32_t offsets[2 * MCL_NDT_MAX_OFFSETS]; /* (dx, dy) pairs */
+} mcl_ndt_params;
+/* Fills `params` with the reference struct's defaults (the node's are 0.01 / 1.0 / 0.6: ndt_amcl_node.cpp:87-107). */
+void mcl_default_ndt_params(mcl_ndt_params* params);
+/* NDTSensorModel's map (io::load_from_hdf5 layout): n cells with integer keys cells[n*2] (x, y), means[n*2] and covariances[n*4]
+ * (2 x 2 row-major), at `resolution` metres per cell; params NULL = mcl_default_ndt_params.  Replaces the map between updates
+ * (Amcl::update_map).  MCL_ERR_INVALID_ARGUMENT on a context of another sensor model, duplicate keys, no cells, a resolution that is
+ * not positive and finite, values that are not finite, an asymmetric covariance, more than MCL_NDT_MAX_OFFSETS offsets or an offset
+ * beyond 64 cells; MCL_ERR_UNSUPPORTED where the keys' bounding box (with a border of twice the kernel's reach) exceeds 2^26 cells. */
+mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* means, const double* covariances, uint64_t n,
+                           double resolution, const mcl_ndt_params* params);
+/* detail::to_cells (ndt_sensor_model.hpp:66-110) of a scan in the base frame: points grouped by (p / resolution) truncated toward
+ * zero, groups of fewer than 5 points dropped, each other group's mean and sample covariance (divided by n - 1, diagonal clamped to
+ * >= 1e-5).  Cells in ascending (x, y) key order.  Pure host arithmetic.  means_out / covs_out hold B / 5 cells (2 and 4 doubles each). */
+mcl_status mcl_ndt_measurement_cells(const double* points_xy, uint64_t num_points, double resolution, double* means_out,
+                                     double* covs_out, uint64_t* num_cells);
+/* Stage-level reweight from measurement cells fitted by the caller (means[k*2], covs[k*4] 2 x 2 row-major, base frame): w *= 1 +
+ * sum over the cells of likelihood_at(state * cell).  mcl_reweight on an NDT context fits the cells of its points first. */
+mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const double* covs, uint64_t num_cells);
 
 /* ---- Stage-level entry points (what update() composes; used by parity tests and by the
  * multi-GPU driver, which interleaves collectives between them). -------------------------------- */
