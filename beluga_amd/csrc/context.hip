@@ -233,13 +233,13 @@ struct mcl_ctx {
   // reductions / scans
   DeviceBuffer<double> d_chunk;      // [12][stride]
   uint32_t chunk_stride{0};
-  DeviceBuffer<double> d_scalars;    // 32 doubles
-  double* h_scalars{nullptr};        // pinned, 32 doubles
+  DeviceBuffer<double> d_scalars;    // kScalarSlots doubles, laid out as kernels.h ScalarSlot says
+  double* h_scalars{nullptr};        // pinned, kScalarSlots doubles
   double* hd_scalars{nullptr};       // the same memory as the device sees it: kernels mirror their scalar results into it
   DeviceBuffer<double> d_cdf;
   DeviceBuffer<double4> d_cloud;    // mcl_sample_particle_cloud staging
   DeviceBuffer<double> d_est_partials;  // [9][ceil(n / 256)] estimate sums left by the draw kernel
-  // The fixed-size cycle's completion word (Completion): ticket in d_scalars[27], word in h_scalars[31]; done_seq counts the
+  // The fixed-size cycle's completion word (Completion): ticket in kSlotDoneTicket, word in kSlotDoneWord; done_seq counts the
   // cycles that armed it, done_armed: this cycle's last kernel carries it.
   uint64_t done_seq{0};
   bool done_armed{false};
@@ -296,7 +296,7 @@ struct mcl_ctx {
   // state of the running KLD pass (do_resample, or mcl_kld_begin / mcl_kld_feed for the sharded driver)
   uint64_t kld_pos{0}, kld_table_slots{0};
   int kld_flip{0};
-  DeviceBuffer<unsigned long long> d_kld_scalars;  // [0]=first_fail, [1]=beam steps; as u32 view: k words at [4..]
+  DeviceBuffer<unsigned long long> d_kld_scalars;  // 8 words, laid out as KldWord says
   unsigned long long* h_kld_scalars{nullptr};      // pinned, 8 words
 
   // cluster_based_estimate scratch
@@ -325,7 +325,7 @@ struct mcl_ctx {
   double cloud_sigma[3]{0, 0, 0};  // standard deviations of x, y, theta
   uint64_t lf_fast_launches{0};    // launches of the FMA variant of the LF kernel (mcl_get_counter)
   // The LDS-patch kernel reports how many beam groups it planned and how many went through a patch (running totals in
-  // d_scalars[24..27), mirrored to h_scalars[28..30)); a launch that found few sends the next ones to the gather kernel,
+  // kSlotPatchTotals, copied to kSlotPatchMirror); a launch that found few sends the next ones to the gather kernel,
   // with a probe every 16th launch (option lf_patch = 1).
   uint64_t lf_patch_launches{0};
   uint64_t lf_queue_launches{0};  // of which by resident workgroups that take their blocks from a queue (k_reweight_lf_patch<true>)
@@ -336,6 +336,7 @@ struct mcl_ctx {
   // patches = the LDS-patch kernel; beams = a dispersed set goes to k_reweight_lf_beams (wave per particle, no ordering).
   struct LfMode { bool decided, patches, beams; } lf_mode{false, false, false};
   uint64_t lf_beams_launches{0};   // launches of k_reweight_lf_beams (mcl_get_counter)
+  uint64_t small_tail_launches{0};  // launches of k_small_tail (mcl_get_counter)
   uint64_t lf_far_launches{0};     // launches of the gather kernel with the far-tile bitmap (dispersed sets)
   uint64_t lf_far_beams_launches{0};  // those of them that were k_reweight_lf_far_beams (lf_dispersed = 2)
   // scratch of the spatial ordering
@@ -350,7 +351,7 @@ struct mcl_ctx {
   mcl_transport transport{};
   void* rccl_comm{nullptr};                 // ncclComm_t when the transport is the built-in RCCL one
   struct RcclUserStorage { void* comm; uint32_t rank, world; } rccl_user{nullptr, 0, 1};
-  DeviceBuffer<double> d_comm_f64;          // [0..8) locals | gathered scalars | ends, offsets | estimate gather
+  DeviceBuffer<double> d_comm_f64;          // laid out as CommSlot / CommAreas say
   DeviceBuffer<long long> d_comm_i64;       // counts[world] | gathered counts[world * world]
   DeviceBuffer<double> d_targets, d_send_targets, d_requests_in, d_replies_out, d_replies_in;
   DeviceBuffer<uint32_t> d_route_order;
@@ -479,7 +480,7 @@ void stage_collect(mcl_ctx* ctx) {
 mcl_status wait_for_cycle(mcl_ctx* ctx) {
   if (ctx->done_armed) {
     ctx->done_armed = false;
-    const volatile uint64_t* word = reinterpret_cast<const volatile uint64_t*>(ctx->h_scalars + 31);
+    const volatile uint64_t* word = reinterpret_cast<const volatile uint64_t*>(ctx->h_scalars + kSlotDoneWord);
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spins = 1;; ++spins) {
       if (*word == ctx->done_seq) {
@@ -541,14 +542,16 @@ mcl_status ensure_kld(mcl_ctx* ctx) {
   return MCL_OK;
 }
 
+// d_kld_scalars / h_kld_scalars: the KLD pass's first failing candidate, the beam model's cell steps, and from kKldCounts on 32-bit words
+enum KldWord : int { kKldFirstFail = 0, kKldBeamSteps = 1, kKldCounts = 4 };  // (the counts: k_base, k_total)
 // take_while_kld (views/take_while_kld.hpp:72-88,112-137) as a running pass over the candidate stream: kld_begin, then
 // kld_process(cnt) for every block of candidates whose hashes were appended to d_hashes[kld_pos ...).
 mcl_status kld_begin(mcl_ctx* ctx) {
   if (ctx->table_capacity == 0) {
     if (const mcl_status s = ensure_kld(ctx)) return s;
   }
-  MCL_HIP(ctx, hipMemsetAsync(ctx->d_kld_scalars.ptr, 0xFF, sizeof(unsigned long long), ctx->stream));  // first_fail = ~0
-  uint32_t* kwords = reinterpret_cast<uint32_t*>(ctx->d_kld_scalars.ptr + 4);                          // [0]=k_base,[1]=k_total
+  MCL_HIP(ctx, hipMemsetAsync(ctx->d_kld_scalars.ptr + kKldFirstFail, 0xFF, sizeof(unsigned long long), ctx->stream));  // ~0
+  uint32_t* kwords = reinterpret_cast<uint32_t*>(ctx->d_kld_scalars.ptr + kKldCounts);
   MCL_HIP(ctx, hipMemsetAsync(kwords, 0, 2 * sizeof(uint32_t), ctx->stream));
   ctx->kld_pos = 0;
   ctx->kld_table_slots = 0;
@@ -575,16 +578,16 @@ mcl_status kld_grow_table(mcl_ctx* ctx, uint64_t candidates) {
 mcl_status kld_process(mcl_ctx* ctx, uint64_t cnt, uint64_t* first_fail) {
   const mcl_amcl_params& a = ctx->cfg.amcl;
   const KldTable table{ctx->d_table_keys.ptr, ctx->d_table_first.ptr, ctx->kld_table_slots};
-  uint32_t* kwords = reinterpret_cast<uint32_t*>(ctx->d_kld_scalars.ptr + 4);
+  uint32_t* kwords = reinterpret_cast<uint32_t*>(ctx->d_kld_scalars.ptr + kKldCounts);
   launch_kld_insert(ctx->stream, ctx->d_hashes.ptr, ctx->kld_pos, cnt, table);
   launch_kld_scan(ctx->stream, ctx->d_hashes.ptr, ctx->kld_pos, cnt, table, ctx->d_flags.ptr, ctx->d_uchunk.ptr,
                   ctx->d_uchunk.ptr + ctx->kld_chunks, kwords + ctx->kld_flip, kwords + (ctx->kld_flip ^ 1), a.min_particles,
-                  a.kld_epsilon, a.kld_z, ctx->d_kld_scalars.ptr);
+                  a.kld_epsilon, a.kld_z, ctx->d_kld_scalars.ptr + kKldFirstFail);
   MCL_HIP(ctx, hipGetLastError());
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars, ctx->d_kld_scalars.ptr, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              ctx->stream));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars + kKldFirstFail, ctx->d_kld_scalars.ptr + kKldFirstFail, sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *first_fail = ctx->h_kld_scalars[0];
+  *first_fail = ctx->h_kld_scalars[kKldFirstFail];
   ctx->kld_pos += cnt;
   ctx->kld_flip ^= 1;
   return MCL_OK;
@@ -839,13 +842,55 @@ void remember_cloud_estimate(mcl_ctx* ctx, const mcl_estimate& est) {
                              std::isfinite(ctx->cloud_sigma[0]) && std::isfinite(ctx->cloud_sigma[1]);
 }
 
+// ---- steps of beluga::Amcl::update (amcl_core.hpp:165-201) that mcl_update and sharded_update share ------------------------------------
+// control_action_window_ << control (RollingWindow<SE2,2>: newest first, extrapolates when short); the cycle takes the next step number.
+void advance_window(mcl_ctx* ctx, const Pose2& pose) {
+  ctx->window1 = ctx->have_window ? ctx->window0 : pose;
+  ctx->window0 = pose;
+  ctx->have_window = true;
+  ctx->step += 1;
+}
+// every_n (every_n.hpp:47-50, :181): the counter as this cycle leaves it; the policy fires where it is 0.  Stored once a path takes the cycle.
+uint64_t next_every_n(const mcl_ctx* ctx) { return (ctx->every_n_current + 1) % ctx->cfg.amcl.resample_interval; }
+// The resampling decision on the host from the totals of the normalised weights of n particles: :179 ThrunRecoveryProbabilityEstimator
+// (thrun_recovery_probability_estimator.hpp:69-89), :181 every_n's verdict `fires` [&& on_effective_size_drop] (on_effective_size_drop.hpp:45-49,
+// effective_sample_size.hpp:46-59).  The filters' reset (:184-186) is the caller's.
+struct HostPolicy {
+  double random_state_probability{0.0}, ess{-1.0};  // (ess -1: not evaluated)
+  bool resample{false};
+};
+HostPolicy host_policy(mcl_ctx* ctx, bool fires, double norm_sum, double norm_sumsq, uint64_t n) {
+  HostPolicy r;
+  const double average = norm_sum / static_cast<double>(n);
+  const double fast_average = ctx->fast(average), slow_average = ctx->slow(average);
+  if (std::abs(slow_average) >= std::numeric_limits<double>::epsilon())
+    r.random_state_probability = std::clamp(1.0 - fast_average / slow_average, 0.0, 1.0);
+  r.resample = fires;
+  if (fires && ctx->cfg.amcl.selective_resampling) {
+    r.ess = norm_sum == 0.0 ? 0.0 : (norm_sum * norm_sum) / norm_sumsq;
+    r.resample = r.ess < static_cast<double>(n) * 0.5;
+  }
+  return r;
+}
+// :200-201: a finite estimate becomes the pivot of the next estimate sums and the cloud estimate centres the next ordering keys; the
+// caller's *estimate and *info take the results (report: what the cycle read, each value captured where it read it).
+void finish_cycle(mcl_ctx* ctx, const mcl_estimate& est, const mcl_update_info& report, mcl_estimate* estimate, mcl_update_info* info) {
+  if (std::isfinite(est.pose[2]) && std::isfinite(est.pose[3])) {
+    ctx->pivot[0] = est.pose[2];
+    ctx->pivot[1] = est.pose[3];
+  }
+  remember_cloud_estimate(ctx, est);
+  if (estimate) *estimate = est;
+  if (info) *info = report;
+}
+
 // Whether the next LF launch goes to the LDS-patch kernel (where its other preconditions hold): by the verdict of the last
 // launch that has reported.  A dispersed set (global localisation) has no group that fits a patch, and the patch kernel's
 // workgroups carry a wave that would then do nothing.
 // synchronised: the stream is idle (the two 64-bit totals are consistent); otherwise the pair comes from the packed word the
 // kernel stores last (low 32 bits of each total in one 8-byte store: never torn; differences are taken modulo 2^32).
 void patch_totals(const mcl_ctx* ctx, uint64_t* planned, uint64_t* through, bool synchronised = false) {
-  const volatile uint64_t* mirror = reinterpret_cast<const volatile uint64_t*>(ctx->h_scalars + 28);
+  const volatile uint64_t* mirror = reinterpret_cast<const volatile uint64_t*>(ctx->h_scalars + kSlotPatchMirror);
   if (synchronised) {
     *planned = mirror[0];
     *through = mirror[1];
@@ -1042,11 +1087,11 @@ mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_
     if (mode.beams) ctx->lf_beams_launches += 1;
     launch_reweight_lf(ctx->stream, ctx->cur(), ctx->n, ctx->field_view(), ctx->d_points.ptr, static_cast<uint32_t>(B), variant, &sort,
                        scan_is_short, ctx->tuning, use_patches,
-                       PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + 24),
-                                  reinterpret_cast<unsigned long long*>(ctx->hd_scalars + 28),
+                       PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
+                                  reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotPatchMirror),
                                   static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
                                   static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
-                                  reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + 30)},
+                                  reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)},
                        /*dispersed=*/!use_patches && (ctx->tuning.lf_far_tiles == 2 || (ctx->tuning.lf_patch == 1 && !ctx->patch_useful)),
                        &far_tiles_used, &ctx->lf_wsum_count, &queue_used, unit_weights, &far_beams_used);
     if (far_tiles_used) ctx->lf_far_launches += 1;
@@ -1077,7 +1122,7 @@ mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_
     }
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
     launch_reweight_beam(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model,
-                         ctx->d_points.ptr, static_cast<uint32_t>(B), ctx->d_kld_scalars.ptr + 1, ordered ? &sort : nullptr,
+                         ctx->d_points.ptr, static_cast<uint32_t>(B), ctx->d_kld_scalars.ptr + kKldBeamSteps, ordered ? &sort : nullptr,
                          ctx->d_nonfree_bits.ptr, ctx->d_beam_points.ptr, use_table ? ctx->d_beam_table.ptr : nullptr,
                          use_table ? ctx->beam_table_count : 0u, ctx->tuning.beam_free_ahead != 0, ctx->tuning.beam_sectors != 0);
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
@@ -1091,30 +1136,47 @@ mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_
   return MCL_OK;
 }
 
-// d_scalars layout: [0] weight sum, [1] norm_sum, [2] norm_sumsq, [3] factor override, [4] cdf total, [8..16] estimate sums
-// finalize == false (only with factor = NaN and read_back == false): the totals of the normalised weights in d_scalars[1..3)
-// are left to the next kernel (do_build_cdf with a policy, or launch_norm_finalize).
+// What a normalisation (kSlotWeightSum, kSlotNormSum, kSlotNormSumSq) left in the mirror.
+mcl_weight_stats mirrored_weight_stats(const mcl_ctx* ctx) {
+  return mcl_weight_stats{ctx->h_scalars[kSlotWeightSum], ctx->h_scalars[kSlotNormSum], ctx->h_scalars[kSlotNormSumSq]};
+}
+// The nine estimate sums a kernel left in the mirror (kSlotEstimate) and the pivot they were taken about: mcl_estimate_from_sums' input.
+void mirrored_sums(const mcl_ctx* ctx, const double pivot[2], double sums[12]) {
+  for (int k = 0; k < 9; ++k) sums[k] = ctx->h_scalars[kSlotEstimate + k];
+  sums[9] = pivot[0];
+  sums[10] = pivot[1];
+  sums[11] = 0.0;
+}
+mcl_status mirrored_estimate(const mcl_ctx* ctx, mcl_estimate* out) {
+  double sums[12];
+  mirrored_sums(ctx, ctx->pivot, sums);
+  return mcl_estimate_from_sums(sums, out);
+}
+
+// read_back == false: the caller reads the totals back later, with its own synchronisation.
+// finalize == false (only with factor = NaN and read_back == false): the totals of the normalised weights are left to the next kernel
+// (do_build_cdf with a policy, or launch_norm_finalize).
 // store_weights == false (mcl_update, a resampling follows at once): the normalised weights are not stored; do_build_cdf has to divide
 // (ctx->cdf_divides tells it).
-mcl_status do_normalize(mcl_ctx* ctx, double factor, mcl_weight_stats* stats, bool read_back = true, bool finalize = true,
-                        bool store_weights = true) {
+struct NormalizeOptions { bool read_back = true, finalize = true, store_weights = true; };
+mcl_status do_normalize(mcl_ctx* ctx, double factor, mcl_weight_stats* stats, const NormalizeOptions& opt = {}) {
   ctx->weights_unit = false;
   ctx->cdf_divides = false;
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
   if (std::isnan(factor)) {  // by the set's own total
     launch_sum_and_normalize(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->chunk_row(1), ctx->chunk_row(2),
-                             ctx->d_scalars.ptr + 0, ctx->hd_scalars + 0, finalize, ctx->lf_wsum_count ? ctx->d_lf_wsum.ptr : nullptr,
-                             ctx->lf_wsum_count, store_weights);
-    ctx->cdf_divides = !store_weights;
+                             ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum, opt.finalize,
+                             ctx->lf_wsum_count ? ctx->d_lf_wsum.ptr : nullptr, ctx->lf_wsum_count, opt.store_weights);
+    ctx->cdf_divides = !opt.store_weights;
     ctx->lf_wsum_count = 0;  // (they described the weights as the reweight left them)
   } else {
-    launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->d_scalars.ptr + 0, ctx->hd_scalars + 0);
-    ctx->h_scalars[3] = factor;
-    MCL_HIP(ctx, hipMemcpyAsync(ctx->d_scalars.ptr + 3, ctx->h_scalars + 3, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    launch_normalize(ctx->stream, ctx->cur().w, ctx->n, ctx->d_scalars.ptr + 3, ctx->chunk_row(1), ctx->chunk_row(2),
-                     ctx->d_scalars.ptr + 1, ctx->hd_scalars + 1);
+    launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum);
+    ctx->h_scalars[kSlotFactor] = factor;
+    MCL_HIP(ctx, hipMemcpyAsync(ctx->d_scalars.ptr + kSlotFactor, ctx->h_scalars + kSlotFactor, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_normalize(ctx->stream, ctx->cur().w, ctx->n, ctx->d_scalars.ptr + kSlotFactor, ctx->chunk_row(1), ctx->chunk_row(2),
+                     ctx->d_scalars.ptr + kSlotNormSum, ctx->hd_scalars + kSlotNormSum);
   }
-  if (!read_back) {  // the caller reads d_scalars[0..3) back later, with its own synchronisation
+  if (!opt.read_back) {
     stage_end(ctx, MCL_STAGE_NORMALIZE);
     MCL_HIP(ctx, hipGetLastError());
     return MCL_OK;
@@ -1122,16 +1184,12 @@ mcl_status do_normalize(mcl_ctx* ctx, double factor, mcl_weight_stats* stats, bo
   stage_end(ctx, MCL_STAGE_NORMALIZE);
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   stage_collect(ctx);
-  if (stats) {
-    stats->sum = ctx->h_scalars[0];
-    stats->norm_sum = ctx->h_scalars[1];
-    stats->norm_sumsq = ctx->h_scalars[2];
-  }
+  if (stats) *stats = mirrored_weight_stats(ctx);
   return MCL_OK;
 }
 
-// do_normalize(NaN, nullptr, false, false) + do_build_cdf(true, policy, true) in one launch where the set allows it (*done says whether it
-// did): the fixed-size cycle that resamples at once.  d_scalars[0..3) and [4] as the two leave them, the recovery estimator included.
+// do_normalize(NaN, nullptr, {false, false}) + do_build_cdf(true, policy, true) in one launch where the set allows it (*done says whether it
+// did): the fixed-size cycle that resamples at once.  The scalar slots as the two leave them, the recovery estimator included.
 mcl_status do_normalize_cdf(mcl_ctx* ctx, const RecoveryPolicy& policy, bool* done) {
   *done = false;
   if (ctx->tuning.scan_fused == 0 || !ctx->d_scan_state.ptr || (ctx->tuning.scan_fused == 1 && ctx->n > 65536)) return MCL_OK;
@@ -1139,9 +1197,9 @@ mcl_status do_normalize_cdf(mcl_ctx* ctx, const RecoveryPolicy& policy, bool* do
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
   if (++ctx->scan_epoch == 0) ctx->scan_epoch = 1;
   *done = launch_normalize_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->lf_wsum_count ? ctx->d_lf_wsum.ptr : nullptr,
-                               ctx->lf_wsum_count, ctx->d_scalars.ptr + 0, ctx->hd_scalars + 0, ctx->chunk_row(1), ctx->chunk_row(2),
-                               /*write_weights=*/false, ctx->d_cdf.ptr, ctx->d_scalars.ptr + 4, ctx->d_cdf_tree.ptr, &policy,
-                               ctx->d_scan_state.ptr, ctx->scan_epoch);
+                               ctx->lf_wsum_count, ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum, ctx->chunk_row(1),
+                               ctx->chunk_row(2), /*write_weights=*/false, ctx->d_cdf.ptr, ctx->d_scalars.ptr + kSlotCdfTotal, ctx->d_cdf_tree.ptr,
+                               &policy, ctx->d_scan_state.ptr, ctx->scan_epoch);
   if (*done) ctx->lf_wsum_count = 0;
   stage_end(ctx, MCL_STAGE_NORMALIZE);
   MCL_HIP(ctx, hipGetLastError());
@@ -1150,13 +1208,13 @@ mcl_status do_normalize_cdf(mcl_ctx* ctx, const RecoveryPolicy& policy, bool* do
 
 // normalized_just_now: the chunk sums k_normalize left in chunk_row(1) are those of the current weights (same summation,
 // same bits as k_chunk_sum would produce) and are reused.  policy (needs normalized_just_now): the CDF kernel's first
-// workgroup also finishes the normalisation's totals (d_scalars[1..3)) and runs the recovery estimator.
+// workgroup also finishes the normalisation's totals (kSlotNormSum, kSlotNormSumSq) and runs the recovery estimator.
 mcl_status do_build_cdf(mcl_ctx* ctx, bool normalized_just_now = false, const RecoveryPolicy* policy = nullptr,
                         bool finalize_norm = false) {
-  launch_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(3), ctx->chunk_row(4), ctx->d_cdf.ptr, ctx->d_scalars.ptr + 4,
+  launch_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(3), ctx->chunk_row(4), ctx->d_cdf.ptr, ctx->d_scalars.ptr + kSlotCdfTotal,
              ctx->d_cdf_tree.ptr, normalized_just_now ? ctx->chunk_row(1) : nullptr, finalize_norm ? ctx->chunk_row(2) : nullptr,
-             finalize_norm ? ctx->d_scalars.ptr + 1 : nullptr, finalize_norm ? ctx->hd_scalars + 1 : nullptr, policy,
-             (normalized_just_now && ctx->cdf_divides) ? ctx->d_scalars.ptr + 0 : nullptr);
+             finalize_norm ? ctx->d_scalars.ptr + kSlotNormSum : nullptr, finalize_norm ? ctx->hd_scalars + kSlotNormSum : nullptr, policy,
+             (normalized_just_now && ctx->cdf_divides) ? ctx->d_scalars.ptr + kSlotWeightSum : nullptr);
   ctx->cdf_divides = false;
   MCL_HIP(ctx, hipGetLastError());
   return MCL_OK;
@@ -1192,18 +1250,22 @@ mcl_status prepare_ndt_random(mcl_ctx* ctx, double random_state_probability) {
   return MCL_OK;
 }
 
-// with_estimate (fixed-N path only): the draw kernel also leaves the estimate sums of the new set in d_scalars[8..17) and
+// with_estimate (fixed-N path only): the draw kernel also leaves the estimate sums of the new set in kSlotEstimate and
 // their host mirror; *estimate_enqueued says whether it did.
-mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t step, uint64_t* n_out,
-                       const double* d_random_state_probability = nullptr, bool normalized_just_now = false,
-                       bool with_estimate = false, bool* estimate_enqueued = nullptr, const RecoveryPolicy* policy = nullptr,
-                       bool finalize_norm = false, bool cdf_ready = false) {
+struct ResampleOptions {
+  const double* d_random_state_probability = nullptr;  // if set, the draw reads the probability from device memory instead
+  bool normalized_just_now = false, with_estimate = false;
+  bool* estimate_enqueued = nullptr;
+  const RecoveryPolicy* policy = nullptr;  // (this, normalized_just_now and finalize_norm: do_build_cdf's)
+  bool finalize_norm = false, cdf_ready = false;  // cdf_ready: do_normalize_cdf left the CDF, the totals and the recovery probability
+};
+mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t step, uint64_t* n_out, const ResampleOptions& opt = {}) {
   const mcl_amcl_params& a = ctx->cfg.amcl;
   MCL_REQUIRE(ctx, ctx->n > 0, "mcl_resample: empty particle set");
   if (ctx->is_ndt()) {
     // the random states of this draw (prepare_ndt_random: mcl_update prepares them before the recovery estimator's reset; the stage-level
     // mcl_resample here); a rejected covariance fails before any particle is overwritten
-    MCL_REQUIRE(ctx, d_random_state_probability == nullptr, "NDT model: the random state probability has to be known on the host");
+    MCL_REQUIRE(ctx, opt.d_random_state_probability == nullptr, "NDT model: the random state probability has to be known on the host");
     if (!ctx->ndt_random_ready)
       if (const mcl_status s = prepare_ndt_random(ctx, random_state_probability)) return s;
     ctx->ndt_random_ready = false;  // (used by this draw only)
@@ -1211,24 +1273,25 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
   ctx->lf_wsum_count = 0;  // (the set changes: workgroup sums of an earlier reweight describe another one)
   const uint64_t max_p = std::min<uint64_t>(a.max_particles, ctx->capacity);
   stage_begin(ctx, MCL_STAGE_RESAMPLE);
-  if (!cdf_ready)  // (cdf_ready: do_normalize_cdf left the CDF, the totals and the recovery probability)
-    if (const mcl_status s = do_build_cdf(ctx, normalized_just_now, policy, finalize_norm)) return s;
+  if (!opt.cdf_ready)
+    if (const mcl_status s = do_build_cdf(ctx, opt.normalized_just_now, opt.policy, opt.finalize_norm)) return s;
   ResampleArgs ra{};
   ra.seed = ctx->cfg.seed;
   ra.step = step;
   ra.random_state_probability = random_state_probability;
-  ra.d_random_state_probability = d_random_state_probability;
+  ra.d_random_state_probability = opt.d_random_state_probability;
   ra.n_in = ctx->n;
   const FreeCells fc = ctx->random_source();
   const HashParams hp{a.spatial_resolution_x, a.spatial_resolution_y, a.spatial_resolution_theta};
   const GridView gv = ctx->grid_view();
+  const double* d_total = ctx->d_scalars.ptr + kSlotCdfTotal;
   uint64_t result = max_p;
   if (a.min_particles >= max_p) {
     // count <= min holds for every candidate (take_while_kld.hpp:86): plain take(max).
     ra.first_candidate = 0;
     ra.count = max_p;
     ra.out_offset = 0;
-    if (with_estimate) {
+    if (opt.with_estimate) {
       MCL_HIP(ctx, ctx->d_est_partials.ensure(static_cast<size_t>(9) * ((max_p + 1023) / 1024)));
       Completion done{};
       // (cycle_spin -1: where the cycle is long enough for the stream's completion signal to be what the host waits for last - measured
@@ -1236,10 +1299,10 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       const bool spin = ctx->tuning.cycle_spin > 0 || (ctx->tuning.cycle_spin < 0 && max_p >= 262144);
       // (profile 1 times the sensor kernel alone: its events are complete long before the cycle's last kernel stores the word; the per-stage
       // events of profile 2 include stages behind it, which need the stream's own completion)
-      ctx->done_armed = spin && ctx->profile <= 1 && estimate_enqueued;
+      ctx->done_armed = spin && ctx->profile <= 1 && opt.estimate_enqueued;
       if (ctx->done_armed) {
-        done.d_ticket = reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + 27);
-        done.host_flag = reinterpret_cast<unsigned long long*>(ctx->hd_scalars + 31);
+        done.d_ticket = reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotDoneTicket);
+        done.host_flag = reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotDoneWord);
         done.seq = ++ctx->done_seq;
       }
       // (behind the draw and its sums - the completion word is theirs -: the next cycle's propagation normals, while the host is away)
@@ -1256,9 +1319,9 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       KeyFrame ahead_frame{};
       const bool order_keys = noise_in_draw && ctx->done_armed && ctx->tuning.order_ahead != 0 && max_p < (1ull << 32) && wants_ordering(ctx) &&
                               predict_key_frame(ctx, &ctx->last_sampler, &ahead_frame, 2);
-      launch_resample_draw_and_estimate(ctx->stream, ctx->cur(), ctx->cdf_tree(), ctx->d_scalars.ptr + 4, ctx->other(), ra, gv, fc, hp,
-                                        ctx->pivot[0], ctx->pivot[1], ctx->d_est_partials.ptr, ctx->d_scalars.ptr + 8,
-                                        ctx->hd_scalars + 8, ctx->done_armed ? &done : nullptr,
+      launch_resample_draw_and_estimate(ctx->stream, ctx->cur(), ctx->cdf_tree(), d_total, ctx->other(), ra, gv, fc, hp,
+                                        ctx->pivot[0], ctx->pivot[1], ctx->d_est_partials.ptr, ctx->d_scalars.ptr + kSlotEstimate,
+                                        ctx->hd_scalars + kSlotEstimate, ctx->done_armed ? &done : nullptr,
                                         ((ctx->tuning.draw_fold == 2 || (ctx->tuning.draw_fold == 1 && max_p <= 65536)) && ctx->d_scan_state.ptr)
                                             ? reinterpret_cast<unsigned int*>(ctx->d_scan_state.ptr + 4)
                                             : nullptr,
@@ -1280,9 +1343,9 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
         ctx->order_sampler = ctx->last_sampler;
         ctx->order_layout = key_layout(ctx);
       }
-      if (estimate_enqueued) *estimate_enqueued = true;
+      if (opt.estimate_enqueued) *opt.estimate_enqueued = true;
     } else {
-      launch_resample_draw(ctx->stream, ctx->cur(), ctx->cdf_tree(), ctx->d_scalars.ptr + 4, ctx->other(), ra, gv, fc, hp, nullptr);
+      launch_resample_draw(ctx->stream, ctx->cur(), ctx->cdf_tree(), d_total, ctx->other(), ra, gv, fc, hp, nullptr);
     }
     MCL_HIP(ctx, hipGetLastError());
   } else {
@@ -1296,8 +1359,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       ra.first_candidate = pos;
       ra.count = cnt;
       ra.out_offset = pos;
-      launch_resample_draw(ctx->stream, ctx->cur(), ctx->cdf_tree(), ctx->d_scalars.ptr + 4, ctx->other(), ra, gv, fc, hp,
-                           ctx->d_hashes.ptr);
+      launch_resample_draw(ctx->stream, ctx->cur(), ctx->cdf_tree(), d_total, ctx->other(), ra, gv, fc, hp, ctx->d_hashes.ptr);
       uint64_t first_fail = ~0ull;
       if (const mcl_status s = kld_process(ctx, cnt, &first_fail)) return s;
       if (first_fail != ~0ull) {
@@ -1318,29 +1380,48 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
 
 mcl_status do_estimate_sums(mcl_ctx* ctx, const double pivot[2], double sums[12], double* scratch) {
   stage_begin(ctx, MCL_STAGE_ESTIMATE);
-  launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, pivot[0], pivot[1], scratch ? scratch : ctx->chunk_row(0), ctx->d_scalars.ptr + 8,
-                       ctx->hd_scalars + 8);
+  launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, pivot[0], pivot[1], scratch ? scratch : ctx->chunk_row(0),
+                       ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
   stage_end(ctx, MCL_STAGE_ESTIMATE);
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   stage_collect(ctx);
-  for (int k = 0; k < 9; ++k) sums[k] = ctx->h_scalars[8 + k];
-  sums[9] = pivot[0];
-  sums[10] = pivot[1];
-  sums[11] = 0.0;
+  mirrored_sums(ctx, pivot, sums);
   return MCL_OK;
 }
 
 
 // ---- particle shards: the cycle over a communicator --------------------------------------------------------------------
-constexpr size_t kCommScalars = 20;  // d_comm_f64[0] local sum | [1] cdf total | [2] norm sum | [3] norm sumsq | [4] global sum | [5..14) estimate sums |
-                                     // [14] this rank's overflow flag of the fixed-capacity exchange (gathered with the sums) | [16..18) the shard plan
-constexpr size_t kEstRecord = 10;    // doubles a rank contributes to the estimate's all-gather: nine sums + the overflow flag
+// d_comm_f64: this rank's scalars, then from kCommScalars on what the all-gathers fill (comm_areas).
+enum CommSlot : size_t {
+  kCommLocalSum = 0,   // this shard's weight sum (gathered)
+  kCommCdfTotal = 1,   // [1..4) the record of the statistics' all-gather (ShardStats): the shard's CDF total,
+  kCommNormSums = 2,   // the sum and the sum of squares of its normalised weights
+  kCommGlobalSum = 4,  // the global weight sum: the gathered sums, added in rank order
+  kCommEstimate = 5,   // [5..15) the record of the estimate's all-gather (kEstRecord): the nine sums,
+  kCommOverflow = 14,  // then this rank's overflow flag of the fixed-capacity exchange
+  kCommPlan = 16,      // [16..18) the shard plan (launch_shard_plan): {total, random state probability}
+  kCommScalars = 20
+};
+struct ShardStats { double cdf_total, norm_sum, norm_sumsq; };
+constexpr size_t kStatsRecord = sizeof(ShardStats) / sizeof(double), kEstRecord = 10;  // (kEstRecord: nine sums + the overflow flag)
+constexpr size_t kCommPerRank = 1 + kStatsRecord + 2 + kEstRecord, kMaxWorld = 64;  // doubles gathered per rank; ranks at most
+// The gathered areas: sums[world] | stats[world][kStatsRecord] | ends[world], offsets[world] | estimates[world][kEstRecord]
+struct CommAreas { double *sums, *stats, *intervals, *estimates; };
+CommAreas comm_areas(const mcl_ctx* ctx) {
+  const size_t world = ctx->comm_world;
+  double* sums = ctx->d_comm_f64.ptr + kCommScalars;
+  return CommAreas{sums, sums + world, sums + world * (1 + kStatsRecord), sums + world * (1 + kStatsRecord + 2)};
+}
+// h_comm: the global sum, the gathered statistics (ShardStats[world]) and the CDF intervals to upload from h_comm[0] on, then the
+// 64-bit words of the counts' all-gathers.
+long long* comm_host_words(const mcl_ctx* ctx) { return reinterpret_cast<long long*>(ctx->h_comm + kCommScalars + kMaxWorld * kCommPerRank); }
 
 mcl_status comm_scratch(mcl_ctx* ctx) {
   const size_t world = ctx->comm_world;
-  MCL_HIP(ctx, ctx->d_comm_f64.ensure(kCommScalars + world * (1 + 3 + 2 + kEstRecord)));
+  MCL_HIP(ctx, ctx->d_comm_f64.ensure(kCommScalars + world * kCommPerRank));
   MCL_HIP(ctx, ctx->d_comm_i64.ensure(world + world * world));
-  if (!ctx->h_comm) MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_comm), (kCommScalars + 64 * (1 + 3 + 2 + kEstRecord) + 64 * 64 + 64) * sizeof(double)));
+  const size_t host_doubles = kCommScalars + kMaxWorld * kCommPerRank + kMaxWorld * kMaxWorld + kMaxWorld;  // (the words: kMaxWorld + 1 rows)
+  if (!ctx->h_comm) MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_comm), host_doubles * sizeof(double)));
   return MCL_OK;
 }
 mcl_status comm_gather(mcl_ctx* ctx, const void* d_send, void* d_recv, uint64_t bytes) {
@@ -1401,7 +1482,7 @@ mcl_status comm_agree(mcl_ctx* ctx, const char* where) {
   if (const mcl_status s = comm_scratch(ctx)) return s;
   const uint32_t world = ctx->comm_world;
   long long* d_words = ctx->d_comm_i64.ptr;
-  long long* h_words = reinterpret_cast<long long*>(ctx->h_comm + kCommScalars + 64 * (1 + 3 + 2 + kEstRecord));
+  long long* h_words = comm_host_words(ctx);
   const uint64_t mine = comm_path_word(ctx);
   std::memcpy(h_words, &mine, sizeof(mine));
   MCL_HIP(ctx, hipMemcpyAsync(d_words, h_words, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
@@ -1419,33 +1500,29 @@ mcl_status comm_agree(mcl_ctx* ctx, const char* where) {
   return MCL_OK;
 }
 
-// The nine estimate sums (estimation.hpp:436-475) over all shards: local sums - of the particles whose cell carries cluster id
+// The estimate from the nine sums (estimation.hpp:436-475) over all shards: local sums - of the particles whose cell carries cluster id
 // wanted_plus_1 - 1 in t_cluster when t_cluster is given -, gathered, added in rank order by every rank.
-mcl_status sharded_estimate_sums(mcl_ctx* ctx, unsigned int* t_cluster, unsigned int wanted_plus_1, double sums[12], uint64_t slots = 0) {
+mcl_status sharded_estimate(mcl_ctx* ctx, unsigned int* t_cluster, unsigned int wanted_plus_1, mcl_estimate* out, uint64_t slots = 0) {
   if (const mcl_status s = comm_scratch(ctx)) return s;
   const uint32_t world = ctx->comm_world;
-  double* d = ctx->d_comm_f64.ptr;
-  double* d_gather_est = d + kCommScalars + world * (1 + 3 + 2);  // [world][kEstRecord]
+  double* d_est = ctx->d_comm_f64.ptr + kCommEstimate;
+  double* d_gather_est = comm_areas(ctx).estimates;  // [world][kEstRecord]
   if (ctx->n == 0) {
-    MCL_HIP(ctx, hipMemsetAsync(d + 5, 0, 9 * sizeof(double), ctx->stream));
+    MCL_HIP(ctx, hipMemsetAsync(d_est, 0, 9 * sizeof(double), ctx->stream));
   } else if (t_cluster) {
     launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, ctx->d_table_keys.ptr, t_cluster, slots, wanted_plus_1 - 1u,
-                                 ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0), d + 5);
+                                 ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0), d_est);
   } else {
-    launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0), d + 5);
+    launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0), d_est);
   }
   MCL_HIP(ctx, hipGetLastError());
-  // (with the nine sums travels d[14]: this rank's overflow flag of the cycle's fixed-capacity exchange - their sum lands in h_scalars[17])
-  if (const mcl_status s = comm_gather(ctx, d + 5, d_gather_est, kEstRecord * sizeof(double))) return s;
-  launch_sum_rows(ctx->stream, d_gather_est, world, kEstRecord, ctx->d_scalars.ptr + 8, ctx->hd_scalars + 8);
+  // (with the nine sums travels kCommOverflow: this rank's flag of the cycle's fixed-capacity exchange - their sum lands in kSlotOverflow)
+  if (const mcl_status s = comm_gather(ctx, d_est, d_gather_est, kEstRecord * sizeof(double))) return s;
+  launch_sum_rows(ctx->stream, d_gather_est, world, kEstRecord, ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
   MCL_HIP(ctx, hipGetLastError());
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->comm_host_syncs += 1;
-  for (int k = 0; k < 9; ++k) sums[k] = ctx->h_scalars[8 + k];
-  sums[9] = ctx->pivot[0];
-  sums[10] = ctx->pivot[1];
-  sums[11] = 0.0;
-  return MCL_OK;
+  return mirrored_estimate(ctx, out);
 }
 
 // algorithm/spatial_hash.hpp:45-75,87-94,190-193 on the host (neighbour cells of the cluster flood fill).
@@ -1604,7 +1681,7 @@ mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_e
     const uint32_t world = ctx->comm_world;
     constexpr size_t kRecord = 7;  // doubles per cell: key (bit pattern), weight sum, count (bit pattern), state[4]
     long long* d_counts = ctx->d_comm_i64.ptr;
-    long long* h_counts = reinterpret_cast<long long*>(ctx->h_comm + kCommScalars + 64 * (1 + 3 + 2 + kEstRecord));
+    long long* h_counts = comm_host_words(ctx);
     h_counts[0] = local_failure ? -1 : static_cast<long long>(m);  // -1: this rank's compaction failed
     MCL_HIP(ctx, hipMemcpyAsync(d_counts, h_counts, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
     if (const mcl_status s = comm_gather(ctx, d_counts, d_counts + world, sizeof(long long))) return s;
@@ -1728,13 +1805,10 @@ mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_e
   long best = -1;
   for (size_t c = 0; c < next_cluster_id; ++c)
     if (total_n[c] > 1 && (best < 0 || total_w[static_cast<size_t>(best)] < total_w[c])) best = static_cast<long>(c);
-  double sums[12];
   if (best < 0) {  // :424-427 no cluster: overall mean and covariance
-    if (sharded) {
-      if (const mcl_status s = sharded_estimate_sums(ctx, nullptr, 0, sums)) return s;
-    } else if (const mcl_status s = do_estimate_sums(ctx, ctx->pivot, sums)) {
-      return s;
-    }
+    if (sharded) return sharded_estimate(ctx, nullptr, 0, out);
+    double sums[12];
+    if (const mcl_status s = do_estimate_sums(ctx, ctx->pivot, sums)) return s;
     return mcl_estimate_from_sums(sums, out);
   }
   // this rank's cells -> their clusters (list order, the order of slot_list)
@@ -1753,30 +1827,19 @@ mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_e
   }
   if (small) {  // (the cells' keys and their cluster ids are in the mapped list: hk / hcl)
     launch_small_cluster_sums(ctx->stream, ctx->cur(), n, hp, dk, dcl, m, static_cast<unsigned int>(best), ctx->pivot[0], ctx->pivot[1],
-                              ctx->d_scalars.ptr + 8, ctx->hd_scalars + 8);
+                              ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
     MCL_HIP(ctx, hipGetLastError());
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 9; ++k) sums[k] = ctx->h_scalars[8 + k];
-    sums[9] = ctx->pivot[0];
-    sums[10] = ctx->pivot[1];
-    sums[11] = 0.0;
-    return mcl_estimate_from_sums(sums, out);
+    return mirrored_estimate(ctx, out);
   }
   if (m) launch_cell_set_cluster(ctx->stream, slot_list, cluster_list, m, t_cluster);
-  if (sharded) return [&] {
-    if (const mcl_status s = sharded_estimate_sums(ctx, t_cluster, static_cast<unsigned int>(best) + 1u, sums, slots)) return s;
-    return mcl_estimate_from_sums(sums, out);
-  }();
+  if (sharded) return sharded_estimate(ctx, t_cluster, static_cast<unsigned int>(best) + 1u, out, slots);
   launch_estimate_sums_cluster(ctx->stream, ctx->cur(), n, ctx->d_hashes.ptr, ctx->d_table_keys.ptr, t_cluster, slots,
-                               static_cast<unsigned int>(best), ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0), ctx->d_scalars.ptr + 8,
-                               ctx->hd_scalars + 8);
+                               static_cast<unsigned int>(best), ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0),
+                               ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
   MCL_HIP(ctx, hipGetLastError());
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (int k = 0; k < 9; ++k) sums[k] = ctx->h_scalars[8 + k];
-  sums[9] = ctx->pivot[0];
-  sums[10] = ctx->pivot[1];
-  sums[11] = 0.0;
-  return mcl_estimate_from_sums(sums, out);
+  return mirrored_estimate(ctx, out);
 }
 
 
@@ -1804,7 +1867,7 @@ uint64_t padded_capacity(uint64_t n_total, uint32_t world, uint32_t permille) {
 // The same exchange without a host read in the middle of the cycle: every pair of ranks moves `cap` entries whatever the counts are
 // (requests: cap doubles, NaN = none; replies: cap states), so that the sizes of both all-to-alls are known before anything is
 // computed.  6 % more bytes than the exact form; a rank whose requests to one shard do not fit sets its
-// overflow flag (d_comm_f64[14]), which travels with the estimate sums: sharded_update then runs the resampling again, exactly.
+// overflow flag (kCommOverflow), which travels with the estimate sums: sharded_update then runs the resampling again, exactly.
 // Leaves targets, replies and slots as sharded_draw does, in lists of world * cap entries.
 mcl_status sharded_draw_padded(mcl_ctx* ctx, const double* d_intervals, uint64_t first_slot, uint64_t m, const double* d_plan, uint64_t cap,
                                uint64_t* entries_out) {
@@ -1831,7 +1894,7 @@ mcl_status sharded_draw_padded(mcl_ctx* ctx, const double* d_intervals, uint64_t
     uint32_t* chunk_off = chunk_sum + (hist / kChunk + 1);
     uint8_t* dest = reinterpret_cast<uint8_t*>(chunk_off + (hist / kChunk + 1));
     launch_route_targets(ctx->stream, ctx->d_targets.ptr, m, d_intervals, d_intervals + world, world, rank, dest, block_hist, chunk_sum, chunk_off,
-                         ctx->d_send_targets.ptr, ctx->d_route_order.ptr, d_counts, static_cast<uint32_t>(cap), ctx->d_comm_f64.ptr + 14);
+                         ctx->d_send_targets.ptr, ctx->d_route_order.ptr, d_counts, static_cast<uint32_t>(cap), ctx->d_comm_f64.ptr + kCommOverflow);
     MCL_HIP(ctx, hipGetLastError());
   }
   std::vector<uint64_t> request_bytes(world, cap * sizeof(double)), reply_bytes(world, cap * 4 * sizeof(double));
@@ -1856,7 +1919,7 @@ mcl_status sharded_draw(mcl_ctx* ctx, double random_state_probability, double to
   if (const mcl_status s = mcl_route_targets(ctx, ctx->d_targets.ptr, m, d_intervals, d_intervals + world, world, rank, ctx->d_send_targets.ptr,
                                              ctx->d_route_order.ptr, reinterpret_cast<int64_t*>(d_counts))) return s;
   if (const mcl_status s = comm_gather(ctx, d_counts, d_all_counts, world * sizeof(long long))) return s;  // counts[r][q]: r asks q
-  long long* h_counts = reinterpret_cast<long long*>(ctx->h_comm + kCommScalars + 64 * (1 + 3 + 2 + kEstRecord));
+  long long* h_counts = comm_host_words(ctx);
   MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_all_counts, world * world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->comm_host_syncs += 1;
@@ -1985,7 +2048,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
     MCL_HIP(ctx, hipMemcpyAsync(d_counts, &mine, sizeof(mine), hipMemcpyHostToDevice, ctx->stream));
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (mine is a local)
     if (const mcl_status s = comm_gather(ctx, d_counts, d_counts + world, sizeof(long long))) return s;
-    long long* h_counts = reinterpret_cast<long long*>(ctx->h_comm + kCommScalars + 64 * (1 + 3 + 2 + kEstRecord));
+    long long* h_counts = comm_host_words(ctx);
     MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts + world, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t sum = 0, before = 0;
@@ -2000,51 +2063,42 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
   const uint64_t n_total = ctx->global_n ? ctx->global_n : ap.max_particles;  // particles over all shards before this cycle's resampling
   if (n_total == 0) return MCL_OK;
   if (const mcl_status s = stage_points(ctx, points_xy, num_points)) return s;
-  if (!ctx->have_window) {
-    ctx->window0 = ctx->window1 = pose;
-    ctx->have_window = true;
-  } else {
-    ctx->window1 = ctx->window0;
-    ctx->window0 = pose;
-  }
-  ctx->step += 1;
+  advance_window(ctx, pose);
   double* d = ctx->d_comm_f64.ptr;
-  double* d_gather_sums = d + kCommScalars;            // [world]
-  double* d_gather_stats = d_gather_sums + world;      // [world][3]
-  double* d_intervals = d_gather_stats + 3 * world;    // ends[world], offsets[world]; behind them [world][9] estimate sums
-  double* h = ctx->h_comm;
+  const CommAreas gathered = comm_areas(ctx);
+  double* d_intervals = gathered.intervals;  // ends[world], offsets[world]
 
-  MCL_HIP(ctx, hipMemsetAsync(d + 14, 0, sizeof(double), ctx->stream));  // this cycle's overflow flag (the fixed-capacity exchange)
+  MCL_HIP(ctx, hipMemsetAsync(d + kCommOverflow, 0, sizeof(double), ctx->stream));  // this cycle's overflow flag (the fixed-capacity exchange)
   bool keys_ready = false;
   if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, num_points, &keys_ready)) return s;  // :174-175
   if (const mcl_status s = do_reweight(ctx, points_xy, num_points, true, keys_ready)) return s;                         // :176
-  ctx->every_n_current = (ctx->every_n_current + 1) % ap.resample_interval;  // every_n does not depend on data
+  ctx->every_n_current = next_every_n(ctx);  // every_n does not depend on data
   const bool fires = ctx->every_n_current == 0;
   // :177 normalise by the GLOBAL sum: shard sums gathered, added in rank order by every rank
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
-  launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), d + 0);
-  if (const mcl_status s = comm_gather(ctx, d + 0, d_gather_sums, sizeof(double))) return s;
-  launch_sum_rows(ctx->stream, d_gather_sums, world, 1, d + 4, nullptr);
-  launch_normalize(ctx->stream, ctx->cur().w, ctx->n, d + 4, ctx->chunk_row(1), ctx->chunk_row(2), d + 2);
+  launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), d + kCommLocalSum);
+  if (const mcl_status s = comm_gather(ctx, d + kCommLocalSum, gathered.sums, sizeof(double))) return s;
+  launch_sum_rows(ctx->stream, gathered.sums, world, 1, d + kCommGlobalSum, nullptr);
+  launch_normalize(ctx->stream, ctx->cur().w, ctx->n, d + kCommGlobalSum, ctx->chunk_row(1), ctx->chunk_row(2), d + kCommNormSums);
   stage_end(ctx, MCL_STAGE_NORMALIZE);
   if (fires) {
-    launch_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(3), ctx->chunk_row(4), ctx->d_cdf.ptr, d + 1, ctx->d_cdf_tree.ptr,
+    launch_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(3), ctx->chunk_row(4), ctx->d_cdf.ptr, d + kCommCdfTotal, ctx->d_cdf_tree.ptr,
                ctx->chunk_row(1));
   } else {
-    MCL_HIP(ctx, hipMemsetAsync(d + 1, 0, sizeof(double), ctx->stream));
+    MCL_HIP(ctx, hipMemsetAsync(d + kCommCdfTotal, 0, sizeof(double), ctx->stream));
   }
   MCL_HIP(ctx, hipGetLastError());
-  if (const mcl_status s = comm_gather(ctx, d + 1, d_gather_stats, 3 * sizeof(double))) return s;
+  if (const mcl_status s = comm_gather(ctx, d + kCommCdfTotal, gathered.stats, sizeof(ShardStats))) return s;
   // A fixed-size cycle without selective resampling takes no decision that depends on the gathered numbers: the CDF intervals,
   // the totals and the recovery estimator are derived on the device by every rank (launch_shard_plan), the draw reads them
   // there, and the host reads them back with the estimate.  The cycle then has ONE host round trip before its end: the request
   // counts of the ancestor exchange (a collective's send / receive counts are host values).
   if (!adaptive && !ap.selective_resampling && ctx->tuning.device_policy != 0) {
-    constexpr int kPolicySlot = 20;  // d_scalars[20..23) = {slow, fast, p}, as in the single-context cycle
-    const RecoveryPolicy policy{ap.alpha_slow, ap.alpha_fast, fires ? 1 : 0, ctx->d_scalars.ptr + kPolicySlot, ctx->hd_scalars + kPolicySlot};
-    double* d_plan = d + 16;  // {total, p}
-    launch_shard_plan(ctx->stream, d_gather_stats, world, n_total, ctx->d_scalars.ptr + 1, ctx->hd_scalars + 1, policy, d_intervals, d_plan);
-    launch_sum_rows(ctx->stream, d + 4, 1, 1, ctx->d_scalars.ptr + 0, ctx->hd_scalars + 0);  // the global weight sum, for the info
+    const RecoveryPolicy policy{ap.alpha_slow, ap.alpha_fast, fires ? 1 : 0, ctx->d_scalars.ptr + kSlotPolicy, ctx->hd_scalars + kSlotPolicy};
+    double* d_plan = d + kCommPlan;  // {total, p}
+    launch_shard_plan(ctx->stream, gathered.stats, world, n_total, ctx->d_scalars.ptr + kSlotNormSum, ctx->hd_scalars + kSlotNormSum, policy,
+                      d_intervals, d_plan);
+    launch_sum_rows(ctx->stream, d + kCommGlobalSum, 1, 1, ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum);  // (info)
     MCL_HIP(ctx, hipGetLastError());
     // The ancestor exchange: fixed capacity per pair of ranks (no host read before the cycle's end) where the plain estimate follows -
     // its all-gather carries the overflow flags -, exact counts (one host read) otherwise.
@@ -2084,9 +2138,8 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
       MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
       ctx->comm_host_syncs += 1;
     } else {
-      double sums[12];
-      if (const mcl_status s = sharded_estimate_sums(ctx, nullptr, 0, sums)) return s;
-      if (padded && ctx->h_scalars[17] != 0.0) {
+      if (const mcl_status s = sharded_estimate(ctx, nullptr, 0, &est)) return s;
+      if (padded && ctx->h_scalars[kSlotOverflow] != 0.0) {
         // Some rank's requests to one shard did not fit the fixed capacity (every rank reads the same sum of flags and gets here
         // together): the new set is incomplete.  The old one and its CDF are untouched - the commit wrote the other buffer -: back to
         // it, the exchange again with exact counts, the estimate again.
@@ -2100,68 +2153,44 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
         stage_end(ctx, MCL_STAGE_RESAMPLE);
         if (retry != MCL_OK) return retry;
         stage_begin(ctx, MCL_STAGE_ESTIMATE);
-        if (const mcl_status s = sharded_estimate_sums(ctx, nullptr, 0, sums)) {
+        if (const mcl_status s = sharded_estimate(ctx, nullptr, 0, &est)) {
           stage_end(ctx, MCL_STAGE_ESTIMATE);
           return s;
         }
       }
       stage_end(ctx, MCL_STAGE_ESTIMATE);
-      if (const mcl_status s = mcl_estimate_from_sums(sums, &est)) return s;
     }
     stage_collect(ctx);
-    if (std::isfinite(est.pose[2]) && std::isfinite(est.pose[3])) {
-      ctx->pivot[0] = est.pose[2];
-      ctx->pivot[1] = est.pose[3];
-    }
-    remember_cloud_estimate(ctx, est);
-    if (estimate) *estimate = est;
-    if (info) {
-      info->updated = 1;
-      info->resampled = fires ? 1 : 0;
-      info->num_particles = n_total;
-      info->weight_sum = ctx->h_scalars[0];
-      info->effective_sample_size = -1.0;
-      info->random_state_probability = ctx->h_scalars[kPolicySlot + 2];
-    }
+    finish_cycle(ctx, est, mcl_update_info{1, fires, n_total, ctx->h_scalars[kSlotWeightSum], -1.0, ctx->h_scalars[kSlotPolicyP]}, estimate, info);
     return MCL_OK;
   }
-  MCL_HIP(ctx, hipMemcpyAsync(h, d + 4, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  MCL_HIP(ctx, hipMemcpyAsync(h + 1, d_gather_stats, 3 * world * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  double* h_sum = ctx->h_comm;  // (comm_host_words)
+  ShardStats* h_stats = reinterpret_cast<ShardStats*>(h_sum + 1);
+  MCL_HIP(ctx, hipMemcpyAsync(h_sum, d + kCommGlobalSum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipMemcpyAsync(h_stats, gathered.stats, world * sizeof(ShardStats), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->comm_host_syncs += 1;
   stage_collect(ctx);
-  const double weight_sum = h[0];
+  const double weight_sum = *h_sum;
   double norm_sum = 0.0, norm_sumsq = 0.0;
   for (uint32_t r = 0; r < world; ++r) {
-    norm_sum += h[1 + 3 * r + 1];
-    norm_sumsq += h[1 + 3 * r + 2];
+    norm_sum += h_stats[r].norm_sum;
+    norm_sumsq += h_stats[r].norm_sumsq;
   }
-  // :179 ThrunRecoveryProbabilityEstimator on the normalised weights
-  double random_state_probability = 0.0;
-  {
-    const double average = norm_sum / static_cast<double>(n_total);
-    const double fast_average = ctx->fast(average), slow_average = ctx->slow(average);
-    if (std::abs(slow_average) >= std::numeric_limits<double>::epsilon())
-      random_state_probability = std::clamp(1.0 - fast_average / slow_average, 0.0, 1.0);
-  }
-  bool do_resampling = fires;
-  double ess = -1.0;
-  if (do_resampling && ap.selective_resampling) {  // :181 && on_effective_size_drop
-    ess = norm_sum == 0.0 ? 0.0 : (norm_sum * norm_sum) / norm_sumsq;
-    do_resampling = ess < static_cast<double>(n_total) * 0.5;
-  }
-  if (do_resampling) {
+  const HostPolicy decision = host_policy(ctx, fires, norm_sum, norm_sumsq, n_total);  // :179, :181
+  const double random_state_probability = decision.random_state_probability;
+  if (decision.resample) {
     if (random_state_probability > 0.0) {  // :184-186
       ctx->slow.reset();
       ctx->fast.reset();
     }
     stage_begin(ctx, MCL_STAGE_RESAMPLE);
     // intervals of the global CDF: ends[r] = inclusive end of shard r, offsets[r] = its start
-    double* up = h + 1 + 3 * world;
+    double* up = reinterpret_cast<double*>(h_stats + world);
     double run = 0.0;
     for (uint32_t r = 0; r < world; ++r) {
       up[world + r] = run;
-      run += h[1 + 3 * r];
+      run += h_stats[r].cdf_total;
       up[r] = run;
     }
     const double total = run;
@@ -2187,26 +2216,12 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
     stage_end(ctx, MCL_STAGE_ESTIMATE);
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   } else {
-    double sums[12];
-    if (const mcl_status s = sharded_estimate_sums(ctx, nullptr, 0, sums)) return s;
+    if (const mcl_status s = sharded_estimate(ctx, nullptr, 0, &est)) return s;
     stage_end(ctx, MCL_STAGE_ESTIMATE);
-    if (const mcl_status s = mcl_estimate_from_sums(sums, &est)) return s;
   }
   stage_collect(ctx);
-  if (std::isfinite(est.pose[2]) && std::isfinite(est.pose[3])) {
-    ctx->pivot[0] = est.pose[2];
-    ctx->pivot[1] = est.pose[3];
-  }
-  remember_cloud_estimate(ctx, est);
-  if (estimate) *estimate = est;
-  if (info) {
-    info->updated = 1;
-    info->resampled = do_resampling ? 1 : 0;
-    info->num_particles = ctx->global_n ? ctx->global_n : ap.max_particles;
-    info->weight_sum = weight_sum;
-    info->effective_sample_size = ess;
-    info->random_state_probability = random_state_probability;
-  }
+  const uint64_t n_after = ctx->global_n ? ctx->global_n : ap.max_particles;
+  finish_cycle(ctx, est, mcl_update_info{1, decision.resample, n_after, weight_sum, decision.ess, random_state_probability}, estimate, info);
   return MCL_OK;
 }
 
@@ -2355,10 +2370,10 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
     }
     const uint64_t cap = cfg->shard_capacity ? cfg->shard_capacity : cfg->amcl.max_particles;
     if (const mcl_status s = ensure_capacity(ctx, cap)) return s;
-    MCL_HIP(ctx, ctx->d_scalars.ensure(32));
-    MCL_HIP(ctx, hipMemsetAsync(ctx->d_scalars.ptr, 0, 32 * sizeof(double), ctx->stream));  // incl. the recovery filters
-    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_scalars), 32 * sizeof(double), hipHostMallocMapped));
-    std::memset(ctx->h_scalars, 0, 32 * sizeof(double));  // host mirrors are read before their first kernel has written them
+    MCL_HIP(ctx, ctx->d_scalars.ensure(kScalarSlots));
+    MCL_HIP(ctx, hipMemsetAsync(ctx->d_scalars.ptr, 0, kScalarSlots * sizeof(double), ctx->stream));  // incl. the recovery filters
+    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_scalars), kScalarSlots * sizeof(double), hipHostMallocMapped));
+    std::memset(ctx->h_scalars, 0, kScalarSlots * sizeof(double));  // host mirrors are read before their first kernel has written them
     MCL_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->hd_scalars), ctx->h_scalars, 0));
     MCL_HIP(ctx, ctx->d_kld_scalars.ensure(8));
     MCL_HIP(ctx, hipMemsetAsync(ctx->d_kld_scalars.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
@@ -2746,10 +2761,10 @@ mcl_status mcl_reweight(mcl_ctx* ctx, const double* points_xy, uint64_t num_poin
 mcl_status mcl_weight_sum(mcl_ctx* ctx, double* sum) {
   if (!ctx || !sum) return MCL_ERR_INVALID_ARGUMENT;
   if (const mcl_status s = bind_device(ctx)) return s;
-  launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->d_scalars.ptr + 0);
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars.ptr, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotWeightSum);
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + kSlotWeightSum, ctx->d_scalars.ptr + kSlotWeightSum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *sum = ctx->h_scalars[0];
+  *sum = ctx->h_scalars[kSlotWeightSum];
   return MCL_OK;
 }
 
@@ -2839,40 +2854,23 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
   if (ctx->n == 0) return MCL_OK;  // amcl_core.hpp:166-168 -> nullopt
   const Pose2 pose = pose_from(control_pose);
   // update_policy_ = on_motion (policies/on_motion.hpp:63-67,121-133); evaluated even when forced (:170)
-  bool moved;
-  const bool had_latest = ctx->have_latest;
-  const Pose2 previous_latest = ctx->latest;
-  if (!ctx->have_latest) {
-    ctx->latest = pose;
-    ctx->have_latest = true;
-    moved = true;
-  } else {
+  bool moved = true;
+  if (ctx->have_latest) {
     const Pose2 delta = pose_mul(pose_inverse(ctx->latest), pose);
     moved = std::sqrt(delta.x * delta.x + delta.y * delta.y) > ctx->cfg.amcl.update_min_d ||
             std::abs(rot_log(delta.r)) > ctx->cfg.amcl.update_min_a;
-    if (moved) ctx->latest = pose;
   }
   if (!moved && !ctx->force_update) return MCL_OK;
   // Everything that can fail without touching a particle is checked before the filter state moves: an update that
   // fails here leaves the motion unconsumed, as if it had not been called (the reference has no partial-update state).
-  auto undo_policy = [&] {
-    ctx->have_latest = had_latest;
-    ctx->latest = previous_latest;
-  };
-  if (const mcl_status s = bind_device(ctx)) {
-    undo_policy();
-    return s;
-  }
-  if (const mcl_status s = reweight_preconditions(ctx, num_points)) {
-    undo_policy();
-    return s;
-  }
+  auto consume_motion = [&] { if (moved) { ctx->latest = pose; ctx->have_latest = true; } };
+  if (const mcl_status s = bind_device(ctx)) return s;
+  if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
   ctx->lf_mode.decided = false;  // whatever an earlier, failed cycle left behind
   if (ctx->have_comm && ctx->comm_world > 1) {
-    if (const mcl_status s = sharded_preconditions(ctx)) {  // before any rank-local state moves: the ranks must not diverge
-      undo_policy();
-      return s;
-    }
+    // before any rank-local state moves: the ranks must not diverge
+    if (const mcl_status s = sharded_preconditions(ctx)) return s;
+    consume_motion();
     return sharded_update(ctx, pose, points_xy, num_points, estimate, info);
   }
   if (ctx->is_ndt()) {  // the scan's measurement cells (detail::to_cells) are what the cycle uploads: kNdtRecord doubles per cell
@@ -2880,20 +2878,9 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
     points_xy = ctx->h_ndt_meas.data();
     num_points = ctx->h_ndt_meas.size() / 2;
   }
-  if (const mcl_status s = stage_points(ctx, points_xy, num_points)) {
-    undo_policy();
-    return s;
-  }
-
-  // control_action_window_ << control (RollingWindow<SE2,2>: newest first, extrapolates when short)
-  if (!ctx->have_window) {
-    ctx->window0 = ctx->window1 = pose;
-    ctx->have_window = true;
-  } else {
-    ctx->window1 = ctx->window0;
-    ctx->window0 = pose;
-  }
-  ctx->step += 1;
+  if (const mcl_status s = stage_points(ctx, points_xy, num_points)) return s;
+  consume_motion();
+  advance_window(ctx, pose);
 
   bool keys_ready = false;
   if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, num_points, &keys_ready)) return s;  // :174-175
@@ -2908,8 +2895,9 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
   if (const mcl_status s = do_reweight(ctx, points_xy, num_points, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0)) return s;  // :176
   // Small sets (the reference's own sizes): everything behind the reweight in ONE launch of one workgroup and one synchronisation
   // (k_small_tail) - the policies are evaluated on the device, the host keeps the recovery filters' state.
+  const uint64_t every_n = next_every_n(ctx);  // :181 (stored by the path that takes the cycle)
+  const bool fires = every_n == 0;
   if (ctx->tuning.small_fused != 0 && !ctx->is_ndt() && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096) {
-    ctx->every_n_current = (ctx->every_n_current + 1) % ap.resample_interval;  // :181
     SmallTail t{};
     t.src = ctx->cur();
     t.dst = ctx->other();
@@ -2918,7 +2906,7 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
     t.min_particles = static_cast<uint32_t>(std::min<uint64_t>(ap.min_particles, t.max_particles));
     t.seed = ctx->cfg.seed;
     t.step = ctx->step;
-    t.fires = ctx->every_n_current == 0;
+    t.fires = fires;
     t.selective = ap.selective_resampling != 0;
     t.alpha_slow = ap.alpha_slow;
     t.alpha_fast = ap.alpha_fast;
@@ -2936,112 +2924,80 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
     // (the completion word only where asked for: measured 10 us per cycle SLOWER than the stream's signal at 2000 particles, round 6)
     ctx->done_armed = ctx->tuning.cycle_spin > 0 && !ctx->profile;
     if (ctx->done_armed) {
-      t.done_flag = reinterpret_cast<unsigned long long*>(ctx->hd_scalars + 31);
+      t.done_flag = reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotDoneWord);
       t.done_seq = ++ctx->done_seq;
     }
     stage_begin(ctx, MCL_STAGE_RESAMPLE);
     const bool launched = launch_small_tail(ctx->stream, t);
     stage_end(ctx, MCL_STAGE_RESAMPLE);
     if (launched) {
+      ctx->every_n_current = every_n;
+      ctx->small_tail_launches += 1;
       MCL_HIP(ctx, hipGetLastError());
       ctx->lf_wsum_count = 0;
       ctx->weights_unit = false;
       if (const mcl_status s = wait_for_cycle(ctx)) return s;
       stage_collect(ctx);
       const double* h = ctx->h_scalars;
-      const bool resampled = h[5] != 0.0;
+      const bool resampled = h[kSlotResampled] != 0.0;
       if (resampled) {
         ctx->live ^= 1;
-        ctx->n = static_cast<uint64_t>(h[6]);
+        ctx->n = static_cast<uint64_t>(h[kSlotParticles]);
         ctx->weights_unit = true;  // particle_traits.hpp:105
       }
-      ctx->slow.output = h[18];
-      ctx->fast.output = h[19];
+      ctx->slow.output = h[kSlotSlow];
+      ctx->fast.output = h[kSlotFast];
       ctx->force_update = false;  // :199
       // (what the info reports, before another kernel's mirrored values take their place)
-      const double weight_sum = h[0], ess_seen = h[7], p_seen = h[22];
+      const mcl_update_info report{1, resampled, ctx->n, h[kSlotWeightSum], h[kSlotEss], h[kSlotPolicyP]};
       mcl_estimate est{};
       if (ctx->estimate_kind == 1) {  // beluga_ros::Amcl returns cluster_based_estimate (beluga_ros/src/amcl.cpp:125): its own kernels
         if (const mcl_status s = mcl_cluster_based_estimate(ctx, &ctx->cluster_params, &est)) return s;
-      } else {
-        double sums[12];
-        for (int k = 0; k < 9; ++k) sums[k] = h[8 + k];
-        sums[9] = ctx->pivot[0];
-        sums[10] = ctx->pivot[1];
-        sums[11] = 0.0;
-        if (const mcl_status s = mcl_estimate_from_sums(sums, &est)) return s;  // :200
+      } else if (const mcl_status s = mirrored_estimate(ctx, &est)) {  // :200
+        return s;
       }
-      if (std::isfinite(est.pose[2]) && std::isfinite(est.pose[3])) {
-        ctx->pivot[0] = est.pose[2];
-        ctx->pivot[1] = est.pose[3];
-      }
-      remember_cloud_estimate(ctx, est);
-      if (estimate) *estimate = est;
-      if (info) {
-        info->updated = 1;
-        info->resampled = resampled ? 1 : 0;
-        info->num_particles = ctx->n;
-        info->weight_sum = weight_sum;
-        info->effective_sample_size = ess_seen;
-        info->random_state_probability = p_seen;
-      }
+      finish_cycle(ctx, est, report, estimate, info);
       return MCL_OK;
     }
     ctx->done_armed = false;
-    ctx->every_n_current = (ctx->every_n_current + ap.resample_interval - 1) % ap.resample_interval;  // (not launched: the large path counts)
   }
   mcl_weight_stats stats{};
-  double random_state_probability = 0.0;
-  double ess = -1.0;
-  bool do_resampling = false;
+  HostPolicy decision{};  // (the device policy: read back with the estimate)
   bool estimate_enqueued = false;  // the estimate sums of the resampled set came out of the draw kernel
-  constexpr int kPolicySlot = 20;  // d_scalars[20..23) = {slow, fast, p}
   if (device_policy) {
     // :177; the totals of the normalised weights and the recovery estimator (:179, :184-186) ride on the next kernel
-    ctx->every_n_current = (ctx->every_n_current + 1) % ap.resample_interval;  // :181
-    do_resampling = ctx->every_n_current == 0;
-    const RecoveryPolicy policy{ap.alpha_slow, ap.alpha_fast, do_resampling ? 1 : 0, ctx->d_scalars.ptr + kPolicySlot,
-                                ctx->hd_scalars + kPolicySlot};
+    ctx->every_n_current = every_n;
+    decision.resample = fires;
+    const RecoveryPolicy policy{ap.alpha_slow, ap.alpha_fast, fires ? 1 : 0, ctx->d_scalars.ptr + kSlotPolicy, ctx->hd_scalars + kSlotPolicy};
     bool fused = false;  // :177 and the CDF of :188 in one launch (the normalised weights of a set that is resampled at once are not stored)
-    if (do_resampling)
+    if (fires)
       if (const mcl_status s = do_normalize_cdf(ctx, policy, &fused)) return s;
     if (!fused)
-      if (const mcl_status s = do_normalize(ctx, std::numeric_limits<double>::quiet_NaN(), nullptr, false, false,
-                                            /*store_weights=*/!do_resampling || ctx->tuning.norm_store != 0)) return s;
-    if (do_resampling) {
-      if (const mcl_status s = do_resample(ctx, 0.0, ctx->step, nullptr, ctx->d_scalars.ptr + kPolicySlot + 2, true,
-                                           ctx->estimate_kind == 0, &estimate_enqueued, &policy, true, fused)) return s;  // :188-196
+      if (const mcl_status s = do_normalize(ctx, std::numeric_limits<double>::quiet_NaN(), nullptr,
+                                            {.read_back = false, .finalize = false, .store_weights = !fires || ctx->tuning.norm_store != 0})) return s;
+    if (fires) {
+      const ResampleOptions opt{.d_random_state_probability = ctx->d_scalars.ptr + kSlotPolicyP, .normalized_just_now = true,
+                                .with_estimate = ctx->estimate_kind == 0, .estimate_enqueued = &estimate_enqueued, .policy = &policy,
+                                .finalize_norm = true, .cdf_ready = fused};
+      if (const mcl_status s = do_resample(ctx, 0.0, ctx->step, nullptr, opt)) return s;  // :188-196
     } else {
-      launch_norm_finalize(ctx->stream, ctx->chunk_row(1), ctx->chunk_row(2), ctx->n, ctx->d_scalars.ptr + 1, ctx->hd_scalars + 1, &policy);
+      launch_norm_finalize(ctx->stream, ctx->chunk_row(1), ctx->chunk_row(2), ctx->n, ctx->d_scalars.ptr + kSlotNormSum, ctx->hd_scalars + kSlotNormSum,
+                           &policy);
       MCL_HIP(ctx, hipGetLastError());
     }
   } else {
     if (const mcl_status s = do_normalize(ctx, std::numeric_limits<double>::quiet_NaN(), &stats)) return s;  // :177
-
-    // :179 ThrunRecoveryProbabilityEstimator on the NORMALISED weights (thrun_..._estimator.hpp:69-89)
-    {
-      const double average = stats.norm_sum / static_cast<double>(ctx->n);
-      const double fast_average = ctx->fast(average);
-      const double slow_average = ctx->slow(average);
-      if (std::abs(slow_average) >= std::numeric_limits<double>::epsilon())
-        random_state_probability = std::clamp(1.0 - fast_average / slow_average, 0.0, 1.0);
-    }
-    // :181 every_n [&& on_effective_size_drop] (every_n.hpp:47-50, on_effective_size_drop.hpp:45-49)
-    ctx->every_n_current = (ctx->every_n_current + 1) % ctx->cfg.amcl.resample_interval;
-    do_resampling = ctx->every_n_current == 0;
-    if (do_resampling && ctx->cfg.amcl.selective_resampling) {
-      ess = stats.norm_sum == 0.0 ? 0.0 : (stats.norm_sum * stats.norm_sum) / stats.norm_sumsq;  // effective_sample_size.hpp:46-59
-      do_resampling = ess < static_cast<double>(ctx->n) * 0.5;
-    }
-    if (do_resampling) {
+    ctx->every_n_current = every_n;
+    decision = host_policy(ctx, fires, stats.norm_sum, stats.norm_sumsq, ctx->n);  // :179, :181
+    if (decision.resample) {
       if (ctx->is_ndt())  // :182, the random state generator of ndt_amcl_node (its failure leaves the state the reference's throw leaves)
-        if (const mcl_status s = prepare_ndt_random(ctx, random_state_probability)) return s;
-      if (random_state_probability > 0.0) {  // :184-186
+        if (const mcl_status s = prepare_ndt_random(ctx, decision.random_state_probability)) return s;
+      if (decision.random_state_probability > 0.0) {  // :184-186
         ctx->slow.reset();
         ctx->fast.reset();
       }
-      if (const mcl_status s = do_resample(ctx, random_state_probability, ctx->step, nullptr, nullptr, true, ctx->estimate_kind == 0,
-                                           &estimate_enqueued)) return s;  // :188-196
+      const ResampleOptions opt{.normalized_just_now = true, .with_estimate = ctx->estimate_kind == 0, .estimate_enqueued = &estimate_enqueued};
+      if (const mcl_status s = do_resample(ctx, decision.random_state_probability, ctx->step, nullptr, opt)) return s;  // :188-196
     }
   }
   ctx->force_update = false;  // :199
@@ -3050,10 +3006,6 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
   bool host_timed = false;
   if (ctx->estimate_kind == 1) {  // beluga_ros::Amcl returns cluster_based_estimate (beluga_ros/src/amcl.cpp:125)
     if (const mcl_status s = mcl_cluster_based_estimate(ctx, &ctx->cluster_params, &est)) return s;
-    if (std::isfinite(est.pose[2]) && std::isfinite(est.pose[3])) {
-      ctx->pivot[0] = est.pose[2];
-      ctx->pivot[1] = est.pose[3];
-    }
   } else if (estimate_enqueued) {  // :200, sums already produced by the draw kernel
     stage_begin(ctx, MCL_STAGE_ESTIMATE);
     stage_end(ctx, MCL_STAGE_ESTIMATE);
@@ -3062,35 +3014,16 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
     t_waited = std::chrono::steady_clock::now();
     host_timed = true;
     stage_collect(ctx);
-    double sums[12];
-    for (int k = 0; k < 9; ++k) sums[k] = ctx->h_scalars[8 + k];
-    sums[9] = ctx->pivot[0];
-    sums[10] = ctx->pivot[1];
-    sums[11] = 0.0;
-    if (const mcl_status s = mcl_estimate_from_sums(sums, &est)) return s;
-    if (std::isfinite(est.pose[2]) && std::isfinite(est.pose[3])) {
-      ctx->pivot[0] = est.pose[2];
-      ctx->pivot[1] = est.pose[3];
-    }
+    if (const mcl_status s = mirrored_estimate(ctx, &est)) return s;
   } else if (const mcl_status s = mcl_estimate_pose(ctx, &est)) {  // :200
     return s;
   }
-  remember_cloud_estimate(ctx, est);  // where the ordering keys of the next cycle are centred
   if (device_policy) {  // read back together with the estimate
-    stats.sum = ctx->h_scalars[0];
-    stats.norm_sum = ctx->h_scalars[1];
-    stats.norm_sumsq = ctx->h_scalars[2];
-    random_state_probability = ctx->h_scalars[kPolicySlot + 2];
+    stats = mirrored_weight_stats(ctx);
+    decision.random_state_probability = ctx->h_scalars[kSlotPolicyP];
   }
-  if (estimate) *estimate = est;
-  if (info) {
-    info->updated = 1;
-    info->resampled = do_resampling ? 1 : 0;
-    info->num_particles = ctx->n;
-    info->weight_sum = stats.sum;
-    info->effective_sample_size = ess;
-    info->random_state_probability = random_state_probability;
-  }
+  const mcl_update_info report{1, decision.resample, ctx->n, stats.sum, decision.ess, decision.random_state_probability};
+  finish_cycle(ctx, est, report, estimate, info);  // (remember_cloud_estimate: where the ordering keys of the next cycle are centred)
   if (host_timed) {
     const auto ns = [](auto a, auto b) { return static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count()); };
     ctx->host_ns[0] += ns(t_entry, t_first);
@@ -3192,8 +3125,8 @@ mcl_status mcl_sample_particle_cloud(mcl_ctx* ctx, uint64_t size, uint32_t draw_
   ra.first_candidate = 0;
   ra.count = size;
   ra.out_offset = 0;
-  launch_resample_draw(ctx->stream, ctx->cur(), ctx->cdf_tree(), ctx->d_scalars.ptr + 4, Particles{ctx->d_cloud.ptr, ctx->d_cloud_w.ptr}, ra,
-                       ctx->grid_view(), FreeCells{nullptr, 0}, HashParams{1.0, 1.0, 1.0}, nullptr);
+  launch_resample_draw(ctx->stream, ctx->cur(), ctx->cdf_tree(), ctx->d_scalars.ptr + kSlotCdfTotal, Particles{ctx->d_cloud.ptr, ctx->d_cloud_w.ptr},
+                       ra, ctx->grid_view(), FreeCells{nullptr, 0}, HashParams{1.0, 1.0, 1.0}, nullptr);
   MCL_HIP(ctx, hipGetLastError());
   MCL_HIP(ctx, hipMemcpyAsync(states, ctx->d_cloud.ptr, size * sizeof(double4), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3232,9 +3165,9 @@ mcl_status mcl_build_cdf(mcl_ctx* ctx, double* total) {
   }
   if (const mcl_status s = do_build_cdf(ctx)) return s;
   if (total) {
-    MCL_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + 4, ctx->d_scalars.ptr + 4, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + kSlotCdfTotal, ctx->d_scalars.ptr + kSlotCdfTotal, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *total = ctx->h_scalars[4];
+    *total = ctx->h_scalars[kSlotCdfTotal];
   }
   return MCL_OK;
 }
@@ -3564,6 +3497,7 @@ mcl_status mcl_get_counter(mcl_ctx* ctx, const char* name, uint64_t* value) {
   else if (key == "lf_beams_launches") *value = ctx->lf_beams_launches;
   else if (key == "lf_far_launches") *value = ctx->lf_far_launches;
   else if (key == "lf_far_beams_launches") *value = ctx->lf_far_beams_launches;
+  else if (key == "small_tail_launches") *value = ctx->small_tail_launches;
   else if (key == "lf_far_tiles") *value = ctx->far_tiles;
   else if (key == "noise_ahead_used") *value = ctx->noise_ahead_used;
   else if (key == "order_ahead_used") *value = ctx->order_ahead_used;
@@ -3616,7 +3550,7 @@ mcl_status mcl_debug_set_recovery_filters(mcl_ctx* ctx, double slow, double fast
   ctx->fast.output = fast;
   const double both[2] = {slow, fast};
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  MCL_HIP(ctx, hipMemcpy(ctx->d_scalars.ptr + 20, both, sizeof(both), hipMemcpyHostToDevice));  // d_scalars[20..23) = {slow, fast, p}
+  MCL_HIP(ctx, hipMemcpy(ctx->d_scalars.ptr + kSlotPolicy, both, sizeof(both), hipMemcpyHostToDevice));  // {slow, fast} of {slow, fast, p}
   return MCL_OK;
 }
 
@@ -3821,11 +3755,11 @@ mcl_status mcl_sync(mcl_ctx* ctx) {
 mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset) {
   if (!ctx || !cells) return MCL_ERR_INVALID_ARGUMENT;
   if (const mcl_status s = bind_device(ctx)) return s;
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars + 1, ctx->d_kld_scalars.ptr + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                              ctx->stream));
-  if (reset) MCL_HIP(ctx, hipMemsetAsync(ctx->d_kld_scalars.ptr + 1, 0, sizeof(unsigned long long), ctx->stream));
+  unsigned long long* d_steps = ctx->d_kld_scalars.ptr + kKldBeamSteps;
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars + kKldBeamSteps, d_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  if (reset) MCL_HIP(ctx, hipMemsetAsync(d_steps, 0, sizeof(unsigned long long), ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *cells = ctx->h_kld_scalars[1];
+  *cells = ctx->h_kld_scalars[kKldBeamSteps];
   return MCL_OK;
 }
 

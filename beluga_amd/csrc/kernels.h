@@ -468,11 +468,39 @@ constexpr size_t kScanStateWords = 8 + 4 * 1024;
 bool launch_normalize_cdf(hipStream_t st, double* w, uint64_t n, double* d_partials, const double* known_partials, uint32_t known_count,
                           double* d_sums, double* sums_mirror, double* d_chunk_sum, double* d_chunk_sumsq, bool write_weights, double* cdf,
                           double* d_total, double* tree_levels, const RecoveryPolicy* policy, unsigned long long* scan_state, uint32_t epoch);
+// The context's block of kScalarSlots doubles, held twice: d_scalars in device memory and its mirror h_scalars in mapped host memory
+// (kernels see it as hd_scalars).  "mirrored": a kernel stores the value into both and the host reads the mirror behind a
+// synchronisation; "device": only the device block holds it; "host": only the mirror does.  A range names its first slot.
+enum ScalarSlot : int {
+  kSlotWeightSum = 0,     // mirrored: the total of the weights before the normalisation
+  kSlotNormSum = 1,       // mirrored: sum of the normalised weights
+  kSlotNormSumSq = 2,     // mirrored: sum of their squares
+  kSlotFactor = 3,        // device: the normalisation's factor when the caller gives one (uploaded through the same host slot)
+  kSlotCdfTotal = 4,      // device: the CDF's total (mcl_cdf_total copies it to the same host slot)
+  kSlotResampled = 5,     // mirrored, k_small_tail: 1 if the cycle resampled, else 0
+  kSlotParticles = 6,     // mirrored, k_small_tail: particles after the cycle
+  kSlotEss = 7,           // mirrored, k_small_tail: effective sample size (-1: not evaluated)
+  kSlotEstimate = 8,      // mirrored: [8..17) the nine sums of the estimate (estimation.hpp:436-475)
+  kSlotOverflow = 17,     // mirrored, sharded cycle: the ranks' overflow flags of the fixed-capacity exchange, summed with the estimate's
+  kSlotSlow = 18,         // mirrored, k_small_tail: the recovery filters' new outputs
+  kSlotFast = 19,
+  kSlotPolicy = 20,       // [20..23) the device-side recovery estimator (RecoveryPolicy::d_policy): {slow, fast, p}; p is mirrored
+  kSlotPolicyFast = 21,
+  kSlotPolicyP = 22,      // the random state probability
+  kSlotPatchTotals = 24,  // device: [24..27) the LDS-patch kernel's running totals (PatchStats::device, 64-bit words)
+  kSlotDoneTicket = 27,   // device: the completion ticket (Completion::d_ticket, a 64-bit word)
+  kSlotPatchMirror = 28,  // host: [28..31) the patch totals as the kernel copies them (PatchStats::mirror, 64-bit words)
+  kSlotPatchQueue = 30,   // device: the patch kernel's queue of blocks (PatchStats::arrivals, a 32-bit word)
+  kSlotDoneWord = 31,     // host: the completion word (Completion::host_flag, a 64-bit word)
+  kScalarSlots = 32
+};
+static_assert(kSlotEstimate + 9 == kSlotOverflow && kSlotPolicyP < kSlotPatchTotals && kSlotPatchTotals + 3 == kSlotDoneTicket &&
+                  kSlotDoneWord < kScalarSlots,
+              "the scalar block's ranges overlap or do not fit in kScalarSlots doubles");
 // The whole tail of a small set's cycle - normalise, policies, resample (fixed size or KLD-adaptive), estimate sums - in one launch of one
-// workgroup (k_small_tail; sets and candidate streams of up to 4096 particles).  Results through `mirror` (32 doubles of mapped host memory)
-// and d_scalars: [0] weight sum, [1] [2] sum and sum of squares of the normalised weights, [5] resampled (0 / 1), [6] particles after the
-// cycle, [7] effective sample size (-1: not evaluated), [8..17) the estimate's sums, [18] [19] the recovery filters' new outputs, [22] the
-// random state probability.  Returns false, nothing launched, where the set does not fit.
+// workgroup (k_small_tail; sets and candidate streams of up to 4096 particles).  Results through `mirror` (the mapped host block) and
+// d_scalars: the slots marked k_small_tail above, kSlotWeightSum .. kSlotNormSumSq, kSlotEstimate and kSlotPolicy's three.  fires: every_n
+// says so this cycle.  Returns false, nothing launched, where the set does not fit.
 struct SmallTail {
   Particles src, dst;
   uint32_t n, min_particles, max_particles;

@@ -3303,7 +3303,7 @@ struct SmallTailArgs {
   GridView g;
   FreeCells fc;
   double pivot_x, pivot_y;
-  double* out;              // [32] mirror in mapped host memory (the context's h_scalars): see the stores below
+  double* out;              // [kScalarSlots] mirror in mapped host memory (the context's h_scalars): see the stores below
   double* d_out;            // the same values in device memory (d_scalars)
   unsigned long long* done_flag;  // optional: a word of mapped host memory that takes done_seq behind everything mirrored (cycle_spin)
   unsigned long long done_seq;
@@ -3531,20 +3531,18 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_tail(SmallTailArgs a) {
   if (tid < 9) {
     double acc = s_wave[tid];
     for (uint32_t q = 1; q < kSmallBlock / 64; ++q) acc += s_wave[q * 9 + tid];
-    a.out[8 + tid] = acc;
-    a.d_out[8 + tid] = acc;
+    a.out[kSlotEstimate + tid] = acc;
+    a.d_out[kSlotEstimate + tid] = acc;
   }
   if (tid == 0) {
-    const double scalars[10] = {total, norm_sum, norm_sumsq, 0.0, 0.0, resample ? 1.0 : 0.0, static_cast<double>(n_out), ess, slow, fast};
-    for (int k = 0; k < 3; ++k) a.out[k] = a.d_out[k] = scalars[k];
-    a.out[5] = a.d_out[5] = scalars[5];
-    a.out[6] = a.d_out[6] = scalars[6];
-    a.out[7] = a.d_out[7] = scalars[7];
-    a.out[18] = a.d_out[18] = slow;
-    a.out[19] = a.d_out[19] = fast;
-    a.out[20] = a.d_out[20] = slow;  // (the device-side policy slot of the large path: {slow, fast, p})
-    a.out[21] = a.d_out[21] = fast;
-    a.out[22] = a.d_out[22] = p;
+    const double scalars[kSlotEss + 1] = {total, norm_sum, norm_sumsq, 0.0, 0.0, resample ? 1.0 : 0.0, static_cast<double>(n_out), ess};
+    for (int k = kSlotWeightSum; k <= kSlotNormSumSq; ++k) a.out[k] = a.d_out[k] = scalars[k];
+    for (int k = kSlotResampled; k <= kSlotEss; ++k) a.out[k] = a.d_out[k] = scalars[k];
+    a.out[kSlotSlow] = a.d_out[kSlotSlow] = slow;
+    a.out[kSlotFast] = a.d_out[kSlotFast] = fast;
+    a.out[kSlotPolicy] = a.d_out[kSlotPolicy] = slow;  // (the device-side policy slot of the large path: {slow, fast, p})
+    a.out[kSlotPolicyFast] = a.d_out[kSlotPolicyFast] = fast;
+    a.out[kSlotPolicyP] = a.d_out[kSlotPolicyP] = p;
   }
   if (a.done_flag) {  // (uniform) the host may be watching this word instead of the stream
     __threadfence_system();

@@ -539,6 +539,7 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *   kernel; lf_patch_groups_planned / lf_patch_groups_through = groups of 8 beams (per workgroup) that kernel has looked at /
  *   has read through a patch, running totals over a sample of the workgroups; lf_queue_launches = launches of the
  *   LDS-patch kernel with the queue of blocks; field_built_on_device, field_build_us = the last mcl_set_map;
+ *   small_tail_launches = cycles that ran their tail in the one launch of option small_fused;
  *   cluster_cells = occupied cells of the last cluster_based_estimate; comm_ranks_seen (ncclCommCount of the library's communicator, 0
  *   without one), comm_collectives, comm_bytes_out (running totals of this rank), comm_backend (0 = none, 1 = the caller's transport, 2 = RCCL inside the library). */
 mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value);

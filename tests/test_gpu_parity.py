@@ -1477,6 +1477,8 @@ def test_small_sets_one_launch_tail_matches_the_kernels_of_the_large_path(lo, hi
             e = f.update(se2_from_xytheta(*odom), pts)
             i = f.last_info
             rows.append((e, dict(i), f.particles()))
+        # (the tail took every cycle that updated - a tail that declined would leave the large path compared with itself)
+        assert f.counter("small_tail_launches") == (sum(r[1]["updated"] for r in rows) if fused else 0)
         outs.append(rows)
         f.close()
     flips = 0
