@@ -1018,13 +1018,13 @@ void launch_pack_nonfree(hipStream_t st, const int8_t* cells, uint32_t W, uint32
                      block_rows, b.row_words, block_columns, b.dist_stride, const_cast<uint8_t*>(b.dist));
 }
 
-// hipFuncSetAttribute is per device: contexts on several GPUs of one process each opt in (mcl_create calls this).
-void configure_device_kernels() {
-  const size_t lds = kBeamLds;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_beam_sorted<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_beam_sorted<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(lds));
+// (configure_device_kernels calls this)
+hipError_t configure_beam_kernels() {
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_beam_sorted<false>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kBeamLds));
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_beam_sorted<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             static_cast<int>(kBeamLds));
 }
 
 uint32_t beam_table_entries(double beam_max_range, double resolution) {

@@ -932,11 +932,6 @@ bool wants_patches(mcl_ctx* ctx) {
   return false;
 }
 
-// Likelihood-field sets below the threshold of the ordered kernels (the larger of the two options: the ordering itself and
-// the LF kernels' own crossover).
-bool lf_set_is_small(const mcl_ctx* ctx) {
-  return ctx->n < static_cast<uint64_t>(std::max(ctx->tuning.sort_min_particles, ctx->tuning.lf_small_particles));
-}
 // The LF launch of this cycle: the patch kernel, the gather kernel, or - for a set the patch kernel has reported as
 // dispersed (no probe due) - the wave-per-particle kernel, which needs no ordering pass.  Decided once per cycle, before the
 // propagation kernel (which emits the ordering keys); cleared by do_reweight.
@@ -954,16 +949,17 @@ void decide_lf_mode(mcl_ctx* ctx) {
   if (ctx->tuning.lf_variant != kLfSortedLanes) return;
   ctx->lf_mode.patches = wants_patches(ctx);
   ctx->lf_mode.beams = !ctx->lf_mode.patches && ctx->tuning.lf_patch == 1 && ctx->tuning.lf_dispersed == 1 && !ctx->patch_useful && palette &&
-                       !lf_set_is_small(ctx);
+                       !lf_set_is_small(ctx->n, ctx->tuning);
 }
 
+// Is the set spatially ordered before the reweight?  The one answer for k_propagate's keys, the order ahead and the LF kernel.
 bool wants_ordering(const mcl_ctx* ctx) {
   if (ctx->n >= (1ull << 32)) return false;
   if (ctx->is_ndt()) return false;  // (a lane per particle in index order: the NDT map lives in L2, locality buys nothing)
   if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) return ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles);
   if (ctx->n < static_cast<uint64_t>(ctx->tuning.sort_min_particles)) return false;
   if (ctx->lf_mode.decided && ctx->lf_mode.beams) return false;
-  return ctx->tuning.lf_variant == kLfSortedLanes && !(lf_set_is_small(ctx) && ctx->pal_count != 0 && ctx->tuning.lf_table == 0);
+  return ctx->tuning.lf_variant == kLfSortedLanes && !(lf_set_is_small(ctx->n, ctx->tuning) && ctx->pal_count != 0 && ctx->tuning.lf_table == 0);
 }
 
 // Is the control action that came close enough to the one the order was predicted with (launch_order_ahead)?  What matters is that the
@@ -1029,7 +1025,6 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
   }
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no map set");
   MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
-  // (no likelihood-field kernel stages the whole scan in LDS any more: lf_variant 0 launches the lane-per-particle kernel of variant 1)
   if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM && !(ctx->n < (1ull << 32) && ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles)))
     // the beam model's small-set kernel (a wave per particle) stages the scan in 64 KB of dynamic LDS
     MCL_REQUIRE(ctx, B * sizeof(double2) <= 64 * 1024, "scan too large for the beam model's small-set kernel (4096 points)");
@@ -1055,9 +1050,9 @@ mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_
   stage_begin(ctx, MCL_STAGE_REWEIGHT);
   decide_lf_mode(ctx);
   const mcl_ctx::LfMode mode = ctx->lf_mode;
-  ctx->lf_mode.decided = false;  // the next cycle decides again
+  const bool ordered = wants_ordering(ctx);  // (asked while this cycle's mode is decided)
+  ctx->lf_mode.decided = false;              // the next cycle decides again
   const SortScratch sort = ctx->sort_scratch();
-  const bool ordered = wants_ordering(ctx) && !mode.beams;
   const bool order_ready = ctx->order_ready;  // (launch_order_ahead's, accepted by this cycle's propagation)
   ctx->order_ready = false;
   if (ordered && !order_ready) {
@@ -1072,38 +1067,30 @@ mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_
     launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, static_cast<uint32_t>(2 * B / kNdtRecord));
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
-    // Below a few thousand particles the ordering passes cost more than they save.
-    // Sets below the ordering threshold (the reference's usual sizes): one or a few particles per wave, lanes over the beams
-    // (launch_reweight_lf falls back to the lane-per-particle kernel where the field has no palette form).
-    const int variant = mode.beams ? kLfBeamLanes
-                                   : ((ctx->tuning.lf_variant == kLfSortedLanes || ctx->tuning.lf_variant == kLfBeamLanes) && !ordered)
-                                         ? (lf_set_is_small(ctx) ? kLfBeamLanes : kLfLanePerParticle)
-                                         : ctx->tuning.lf_variant;
-    if (variant == kLfBeamLanes && !mode.beams) ctx->lf_beams_launches += 1;
-    const bool scan_is_short = ctx->scan_extent / ctx->resolution < 8192.0;
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    const bool use_patches = mode.patches;
-    bool far_tiles_used = false, queue_used = false, far_beams_used = false;
-    if (mode.beams) ctx->lf_beams_launches += 1;
-    launch_reweight_lf(ctx->stream, ctx->cur(), ctx->n, ctx->field_view(), ctx->d_points.ptr, static_cast<uint32_t>(B), variant, &sort,
-                       scan_is_short, ctx->tuning, use_patches,
-                       PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
-                                  reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotPatchMirror),
-                                  static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
-                                  static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
-                                  reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)},
-                       /*dispersed=*/!use_patches && (ctx->tuning.lf_far_tiles == 2 || (ctx->tuning.lf_patch == 1 && !ctx->patch_useful)),
-                       &far_tiles_used, &ctx->lf_wsum_count, &queue_used, unit_weights, &far_beams_used);
-    if (far_tiles_used) ctx->lf_far_launches += 1;
-    if (far_beams_used) ctx->lf_far_beams_launches += 1;
-    if (queue_used) ctx->lf_queue_launches += 1;
-    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
-    if (variant == kLfSortedLanes && ctx->tuning.lf_fast != 0 && scan_is_short && ctx->W < 16384 && ctx->H < 16384 && ctx->pal_count &&
-        ctx->tuning.lf_table == 0)
-    {
-      ctx->lf_fast_launches += 1;
-      if (use_patches) ctx->lf_patch_launches += 1;  // (unless the tables leave no room in LDS for the patches: launch_reweight_lf)
+    const LfLaunch launched = launch_reweight_lf(
+        ctx->stream,
+        LfReweightArgs{.p = ctx->cur(), .n = ctx->n, .f = ctx->field_view(), .d_points = ctx->d_points.ptr, .B = static_cast<uint32_t>(B),
+                       .sort = ordered ? &sort : nullptr, .patches = mode.patches, .beams = mode.beams,
+                       .dispersed = !mode.patches && (ctx->tuning.lf_far_tiles == 2 || (ctx->tuning.lf_patch == 1 && !ctx->patch_useful)),
+                       .scan_cells = ctx->scan_extent / ctx->resolution, .unit_weights = unit_weights,
+                       .stats = PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
+                                           reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotPatchMirror),
+                                           static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
+                                           static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
+                                           reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)}},
+        ctx->tuning);
+    ctx->lf_wsum_count = launched.weight_sums;
+    switch (launched.kernel) {  // (the counters as include/beluga_mcl.h states them)
+      case LfKernel::kPatchQueue: ctx->lf_queue_launches += 1; [[fallthrough]];
+      case LfKernel::kPatch: ctx->lf_patch_launches += 1; ctx->lf_fast_launches += 1; break;
+      case LfKernel::kFarBeams: ctx->lf_far_beams_launches += 1; [[fallthrough]];
+      case LfKernel::kPaletteFar: ctx->lf_far_launches += 1; [[fallthrough]];
+      case LfKernel::kPaletteFast: ctx->lf_fast_launches += 1; break;
+      case LfKernel::kBeams: ctx->lf_beams_launches += 1; break;
+      default: break;
     }
+    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else {
     const mcl_beam_params& b = ctx->cfg.beam;
     const BeamModel model{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range};
@@ -2381,7 +2368,7 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
     for (auto& pair : ctx->ev)
       for (auto& e : pair) MCL_HIP(ctx, hipEventCreate(&e));
     MCL_HIP(ctx, hipEventCreateWithFlags(&ctx->points_event, hipEventDisableTiming));
-    configure_device_kernels();
+    MCL_HIP(ctx, configure_device_kernels());
     {  // the device's compute units: the queue form of the LF patch kernel launches three workgroups per CU
       int count = 0;
       if (hipDeviceGetAttribute(&count, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || count <= 0) count = 256;

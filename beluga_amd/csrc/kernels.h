@@ -8,6 +8,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "se2.h"
@@ -336,9 +337,8 @@ void launch_order_particles(hipStream_t st, Particles p, uint64_t n, const SortS
 // The same order a cycle AHEAD: sort->keys hold the keys the draw kernel predicted for the next cycle (launch_resample_draw_and_estimate,
 // keys_ahead) - their block histograms and the three ordering kernels -> sort->perm.
 void launch_order_ahead(hipStream_t st, uint64_t n, const SortScratch* sort);
-// K2  actions/reweight.hpp:53-60 + likelihood_field_model.hpp:68-91 (kLfSortedLanes needs launch_order_particles first)
-// scan_is_short: every scan point lies within 8192 cells of the sensor (precondition of the kernel's FMA variant)
-// use_patches: the LDS-patch kernel where its preconditions hold (dense sets); patch_stats: running totals it reports
+// K2  actions/reweight.hpp:53-60 + likelihood_field_model.hpp:68-91
+// The LDS-patch kernel's running totals and scratch (LfReweightArgs::stats).
 struct PatchStats {
   unsigned long long* device;  // [3]: groups planned, groups through a patch, workgroups reported (never reset)
   unsigned long long* mirror;  // [3]: mapped host copy of the first two, written by the last workgroup of a launch, and their
@@ -350,12 +350,32 @@ struct PatchStats {
                                // normalisation's input: launch_sum_and_normalize); only written by single-segment launches
   unsigned int* arrivals;      // the queue of blocks (k_reweight_lf_patch<true>): the next block to take; wraps to 0 behind a launch's last fetch
 };
-// *weight_sums_written (optional): how many workgroup sums of the new weights the launch left in patch_stats.weight_sums (0: none -
-// another kernel ran, or the launch was segmented)
-void launch_reweight_lf(hipStream_t st, Particles p, uint64_t n, FieldView f, const double* d_points, uint32_t B, int variant,
-                        const SortScratch* sort, bool scan_is_short, const Tuning& tuning, bool use_patches, PatchStats patch_stats,
-                        bool dispersed = false, bool* far_tiles_used = nullptr, uint32_t* weight_sums_written = nullptr,
-                        bool* queue_used = nullptr, bool unit_weights = false, bool* far_beams_used = nullptr);
+// Likelihood-field sets below the threshold of the ordered kernels (the larger of the two options: the ordering itself and
+// the LF kernels' own crossover).
+inline bool lf_set_is_small(uint64_t n, const Tuning& t) {
+  return n < static_cast<uint64_t>(std::max(t.sort_min_particles, t.lf_small_particles));
+}
+// A cycle's inputs to the LF reweight.
+struct LfReweightArgs {
+  Particles p;
+  uint64_t n;
+  FieldView f;
+  const double* d_points;
+  uint32_t B;
+  const SortScratch* sort;  // the set is ordered (sort->perm, launch_order_particles): the ordered kernels; nullptr: not ordered
+  bool patches, beams;  // the cycle's mode: the LDS-patch kernel where it fits (dense sets); k_reweight_lf_beams (dispersed sets)
+  bool dispersed;       // the set is reported as dispersed: the far-tile bitmap where it applies
+  double scan_cells;    // max |x| + |y| of the scan points in cells (NaN: unknown); the FMA variant needs fewer than 8192
+  bool unit_weights;    // every old weight is 1.0 (the patch and far-beams kernels do not load them)
+  PatchStats stats;
+};
+// The kernel that ran: k_reweight_lf_patch<false> / <true>, _far_beams, _palette<true, true> / <true> / <false>, _sorted<true> /
+// <false> over the order, _beams, _sorted<false> in index order.  The first five are the FMA variant.
+enum class LfKernel { kNone, kPatch, kPatchQueue, kFarBeams, kPaletteFar, kPaletteFast, kPaletteExact, kSortedCube, kSortedField, kBeams, kIndexOrder };
+// kernel: kNone where n == 0; weight_sums: workgroup sums of the new weights left in stats.weight_sums (0: another kernel, or segments)
+struct LfLaunch { LfKernel kernel; uint32_t weight_sums; };
+// The one place that chooses the LF kernel (from the arguments and `tuning`); launches it.
+LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tuning& tuning);
 // K2' beam_model.hpp:104-150 + raycasting.hpp:62-107 + bresenham.hpp:84-160
 // `sorted` != nullptr: lane-per-ordered-particle variant (needs launch_order_particles first).
 // d_beam_points: scratch of kBeamPointDoubles * B doubles (per-beam terms shared by all particles; ordered variant only).
@@ -385,8 +405,10 @@ struct NonFreeBits {
 NonFreeBits nonfree_layout(uint32_t W, uint32_t H, uint32_t* base);
 size_t nonfree_words(uint32_t W, uint32_t H);
 void launch_pack_nonfree(hipStream_t st, const int8_t* cells, uint32_t W, uint32_t H, int8_t free_value, uint32_t* bits);
-// Per-device kernel attributes (dynamic LDS opt-in of the ordered beam kernel); call once per context after hipSetDevice.
-void configure_device_kernels();
+// The dynamic-LDS opt-ins of the kernels that need one (configure_beam_kernels: the ordered beam kernel's).  They are per device:
+// mcl_create calls this for every context, after hipSetDevice.
+hipError_t configure_device_kernels();
+hipError_t configure_beam_kernels();
 
 // Deterministic chunked reductions / scans.  Chunk = 2048 consecutive elements per workgroup.
 constexpr uint32_t kChunk = 2048;

@@ -4139,33 +4139,32 @@ uint32_t far_beams_points_at(const FieldView& f) {  // the scan's place in the w
 uint32_t far_beams_lds(const FieldView& f, uint32_t B) {
   return far_beams_points_at(f) + ((B + 63u) & ~63u) * 16u + (kFarBeamsBlock / kWave) * kFarBeamsChunk * 32u;
 }
-// (hipFuncSetAttribute is per device)
-bool far_beams_configured() {
-  static bool done[64] = {};
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess || device < 0 || device >= 64) return false;
-  if (!done[device]) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_lf_far_beams<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kFarBeamsMaxLds)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_lf_far_beams<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kFarBeamsMaxLds)) != hipSuccess)
-      return false;
-    done[device] = true;
-  }
-  return true;
-}
 }  // namespace
 
-void launch_reweight_lf(hipStream_t st, Particles p, uint64_t n, FieldView f, const double* d_points, uint32_t B, int variant,
-                        const SortScratch* sort, bool scan_is_short, const Tuning& tuning, bool use_patches, PatchStats patch_stats,
-                        bool dispersed, bool* far_tiles_used, uint32_t* weight_sums_written, bool* queue_used, bool unit_weights,
-                        bool* far_beams_used) {
-  if (far_beams_used) *far_beams_used = false;
-  if (weight_sums_written) *weight_sums_written = 0;
-  if (far_tiles_used) *far_tiles_used = false;
-  if (queue_used) *queue_used = false;
-  if (n == 0) return;
-  if (variant == kLfSortedLanes && sort && n < (1ull << 32)) {
+hipError_t configure_device_kernels() {
+  const struct { const void* kernel; size_t lds; } opt_ins[] = {
+      {reinterpret_cast<const void*>(k_reweight_lf_far_beams<false>), kFarBeamsMaxLds},
+      {reinterpret_cast<const void*>(k_reweight_lf_far_beams<true>), kFarBeamsMaxLds},
+      {reinterpret_cast<const void*>(k_small_tail), kSmallLdsBytes},
+      {reinterpret_cast<const void*>(k_small_cluster_cells), kSmallClusterLdsBytes},
+      {reinterpret_cast<const void*>(k_small_cluster_sums), kSmallClusterLdsBytes}};
+  for (const auto& o : opt_ins)
+    if (const hipError_t e = hipFuncSetAttribute(o.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(o.lds)); e != hipSuccess)
+      return e;
+  return configure_beam_kernels();
+}
+
+LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tuning& tuning) {
+  const Particles p = a.p;
+  const uint64_t n = a.n;
+  const FieldView& f = a.f;
+  const double* d_points = a.d_points;
+  const uint32_t B = a.B;
+  LfLaunch launched{LfKernel::kNone, 0};
+  if (n == 0) return launched;
+  const size_t pal_lds = static_cast<size_t>(f.pal_base) + static_cast<size_t>(f.pal_count) * sizeof(double);
+  const bool palette_ok = tuning.lf_table == 0 && f.pal_idx != nullptr && f.pal_count > 0 && pal_lds <= 65536;
+  if (const SortScratch* sort = a.sort) {
     const uint64_t cells = static_cast<uint64_t>(f.W) * f.H;
     const bool cube_ok = f.cube != nullptr && f.W < (1u << 21) && (cells + 1) * 8 < (1ull << 31);
     // One lane per particle fills the chip from ~260K particles (4096 waves).  Below that, split the scan into segments
@@ -4179,35 +4178,35 @@ void launch_reweight_lf(hipStream_t st, Particles p, uint64_t n, FieldView f, co
     const uint32_t per_segment = (B + segments - 1) / segments;
     double* partial = segments > 1 ? sort->partial : nullptr;
     const dim3 grid(blocks_for(n), segments);
-    const size_t pal_lds = static_cast<size_t>(f.pal_base) + static_cast<size_t>(f.pal_count) * sizeof(double);
-    const bool palette_ok = tuning.lf_table == 0 && f.pal_idx != nullptr && f.pal_count > 0 && pal_lds <= 65536;
     if (palette_ok) {
       const dim3 pgrid(static_cast<unsigned>((n + kPalBlock - 1) / kPalBlock), segments);
       // The FMA variant needs a scan within 8192 cells of the sensor and a grid below 2^14 cells per side (its exact
       // fallback handles everything else inside the kernel); tuning.lf_fast = 0 forces the separately rounded arithmetic.
-      const bool fast = tuning.lf_fast != 0 && scan_is_short && f.W < 16384 && f.H < 16384;
+      const bool fast = tuning.lf_fast != 0 && a.scan_cells < 8192.0 && f.W < 16384 && f.H < 16384;
       const uint32_t patch_base = (static_cast<uint32_t>(pal_lds) + 15u) & ~15u;
       const size_t patch_lds = patch_base + kPatchLdsBytes;
-      if (fast && use_patches && patch_lds <= 65536) {
+      if (fast && a.patches && patch_lds <= 65536) {
         const uint32_t per_group = kPatchParticles;
         const unsigned groups_x = static_cast<unsigned>((n + per_group - 1) / per_group);
+        PatchStats patch_stats = a.stats;
         if (segments > 1) patch_stats.weight_sums = nullptr;  // the segments' sums are combined by k_lf_combine
         // A queue of blocks and as many workgroups as stay resident (three per CU) instead of a workgroup per block, where the launch
         // has more blocks than that: see k_reweight_lf_patch.
         const uint32_t cus = tuning.device_cus > 0 ? static_cast<uint32_t>(tuning.device_cus) : 256u;
         const uint32_t resident = tuning.lf_queue_grid > 0 ? static_cast<uint32_t>(tuning.lf_queue_grid) : 3u * cus;
         const PatchArgs args{p.w, n, f, d_points, B, sort->perm, p.pose, partial, per_segment, patch_base, patch_stats, groups_x,
-                             tuning.lf_ends_first != 0 ? 1u : 0u, (unit_weights && segments == 1) ? 1u : 0u};
+                             tuning.lf_ends_first != 0 ? 1u : 0u, (a.unit_weights && segments == 1) ? 1u : 0u};
         if (tuning.lf_queue != 0 && segments == 1 && patch_stats.arrivals != nullptr && groups_x > resident) {
-          if (queue_used) *queue_used = true;
+          launched.kernel = LfKernel::kPatchQueue;
           hipLaunchKernelGGL(k_reweight_lf_patch<true>, dim3(resident), dim3(kPatchBlock), patch_lds, st, args);
         } else {
+          launched.kernel = LfKernel::kPatch;
           hipLaunchKernelGGL(k_reweight_lf_patch<false>, dim3(groups_x, segments), dim3(kPatchBlock), patch_lds, st, args);
         }
-        if (weight_sums_written && patch_stats.weight_sums) *weight_sums_written = groups_x;
+        if (patch_stats.weight_sums) launched.weight_sums = groups_x;
       }
-      else if (fast && dispersed && tuning.lf_far_tiles != 0 && tuning.lf_dispersed == 2 && f.far_linear != nullptr && B > 0 &&
-               f.far_linear_bytes <= kFarBeamsPalShift && far_beams_lds(f, B) <= kFarBeamsMaxLds && far_beams_configured()) {
+      else if (fast && a.dispersed && tuning.lf_far_tiles != 0 && tuning.lf_dispersed == 2 && f.far_linear != nullptr && B > 0 &&
+               f.far_linear_bytes <= kFarBeamsPalShift && far_beams_lds(f, B) <= kFarBeamsMaxLds) {
         // lanes over the beams of one pose, the poses in the position-major order (k_reweight_lf_far_beams); a small set needs no
         // segments of the scan to fill the chip: fewer poses per wave
         segments = 1;
@@ -4219,49 +4218,55 @@ void launch_reweight_lf(hipStream_t st, Particles p, uint64_t n, FieldView f, co
         if (f.prob)
           hipLaunchKernelGGL(k_reweight_lf_far_beams<true>, dim3(blocks), dim3(kFarBeamsBlock), far_beams_lds(f, B), st, p.w, n, f,
                              reinterpret_cast<const double2*>(d_points), B, sort->perm, p.pose, far_beams_points_at(f), per_wave,
-                             unit_weights ? 1u : 0u);
+                             a.unit_weights ? 1u : 0u);
         else
           hipLaunchKernelGGL(k_reweight_lf_far_beams<false>, dim3(blocks), dim3(kFarBeamsBlock), far_beams_lds(f, B), st, p.w, n, f,
                              reinterpret_cast<const double2*>(d_points), B, sort->perm, p.pose, far_beams_points_at(f), per_wave,
-                             unit_weights ? 1u : 0u);
-        if (far_tiles_used) *far_tiles_used = true;
-        if (far_beams_used) *far_beams_used = true;
+                             a.unit_weights ? 1u : 0u);
+        launched.kernel = LfKernel::kFarBeams;
       }
-      else if (fast && dispersed && tuning.lf_far_tiles != 0 && f.far_bits != nullptr && patch_base + f.far_bytes <= 65536) {
+      else if (fast && a.dispersed && tuning.lf_far_tiles != 0 && f.far_bits != nullptr && patch_base + f.far_bytes <= 65536) {
         const dim3 fgrid((pgrid.x + 7u) & ~7u, segments);
         hipLaunchKernelGGL((k_reweight_lf_palette<true, true>), fgrid, dim3(kPalBlock), patch_base + f.far_bytes, st, p.w, n, f, d_points, B,
                            sort->perm, p.pose, partial, per_segment, patch_base);
-        if (far_tiles_used) *far_tiles_used = true;
-      } else if (fast)
+        launched.kernel = LfKernel::kPaletteFar;
+      } else if (fast) {
         hipLaunchKernelGGL(k_reweight_lf_palette<true>, pgrid, dim3(kPalBlock), pal_lds, st, p.w, n, f, d_points, B, sort->perm, p.pose,
                            partial, per_segment, 0u);
-      else
+        launched.kernel = LfKernel::kPaletteFast;
+      } else {
         hipLaunchKernelGGL(k_reweight_lf_palette<false>, pgrid, dim3(kPalBlock), pal_lds, st, p.w, n, f, d_points, B, sort->perm, p.pose,
                            partial, per_segment, 0u);
+        launched.kernel = LfKernel::kPaletteExact;
+      }
     } else if (cube_ok) {
       hipLaunchKernelGGL(k_reweight_lf_sorted<true>, grid, dim3(kBlock), 0, st, p.w, n, f, d_points, B, sort->perm, p.pose, partial,
                          per_segment);
+      launched.kernel = LfKernel::kSortedCube;
     } else {
       hipLaunchKernelGGL(k_reweight_lf_sorted<false>, grid, dim3(kBlock), 0, st, p.w, n, f, d_points, B, sort->perm, p.pose, partial,
                          per_segment);
+      launched.kernel = LfKernel::kSortedField;
     }
     if (segments > 1)
       hipLaunchKernelGGL(k_lf_combine, dim3(blocks_for(n)), dim3(kBlock), 0, st, p.w, n, sort->perm, partial, segments, f.prob);
-  } else if (variant == kLfBeamLanes && tuning.lf_table == 0 && f.pal_idx != nullptr && f.pal_count > 0 &&
-             static_cast<size_t>(f.pal_base) + static_cast<size_t>(f.pal_count) * sizeof(double) <= 65536) {
+  } else if (palette_ok && (a.beams || ((tuning.lf_variant == kLfSortedLanes || tuning.lf_variant == kLfBeamLanes) && lf_set_is_small(n, tuning)))) {
+    // lanes over the beams (a dispersed set the cycle sent here, or a set below the ordered kernels' threshold);
     // particles per wave: enough waves to fill the chip (4096) before a wave takes a second particle
     const uint32_t per_wave = static_cast<uint32_t>(std::min<uint64_t>(kWave, std::max<uint64_t>(1, (n + 4095) / 4096)));
     const uint64_t tiles = (n + per_wave - 1) / per_wave;
     const dim3 grid(static_cast<unsigned>((tiles + (kBeamsBlock / kWave) - 1) / (kBeamsBlock / kWave)));
-    const size_t pal_lds = static_cast<size_t>(f.pal_base) + static_cast<size_t>(f.pal_count) * sizeof(double);
     hipLaunchKernelGGL(k_reweight_lf_beams, grid, dim3(kBeamsBlock), pal_lds, st, p, n, f, reinterpret_cast<const double2*>(d_points), B,
                        per_wave);
+    launched.kernel = LfKernel::kBeams;
   } else {
     // no order (option lf_variant 0 / 1, small sets whose field has too many distinct values for a palette, sets beyond 2^32 particles):
     // a lane per particle in index order over the f32 field
     hipLaunchKernelGGL(k_reweight_lf_sorted<false>, dim3(blocks_for(n)), dim3(kBlock), 0, st, p.w, n, f, d_points, B,
                        static_cast<const uint32_t*>(nullptr), p.pose, static_cast<double*>(nullptr), 0u);
+    launched.kernel = LfKernel::kIndexOrder;
   }
+  return launched;
 }
 
 }  // namespace mcl
@@ -4563,12 +4568,6 @@ void launch_kld_scan(hipStream_t st, const unsigned long long* d_hashes, uint64_
 
 bool launch_small_tail(hipStream_t st, const SmallTail& t) {
   if (t.n == 0 || t.n > kSmallMax || t.max_particles == 0 || t.max_particles > kSmallMax) return false;
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_small_tail), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kSmallLdsBytes)) != hipSuccess)
-      return false;
-    configured = true;
-  }
   SmallTailArgs a{};
   a.src = t.src;
   a.dst = t.dst;
@@ -4625,15 +4624,6 @@ bool launch_small_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashPar
                                 unsigned int* c_count, unsigned int* c_slot, double* c_wsum, double* c_state, unsigned int* c_size,
                                 unsigned int* size_mirror) {
   if (n == 0 || n > kSmallMax) return false;
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_small_cluster_cells), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kSmallClusterLdsBytes)) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_small_cluster_sums), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            static_cast<int>(kSmallClusterLdsBytes)) != hipSuccess)
-      return false;
-    configured = true;
-  }
   const CellList out{c_key, c_first, c_count, c_slot, c_wsum, reinterpret_cast<double4*>(c_state), c_size};
   hipLaunchKernelGGL(k_small_cluster_cells, dim3(1), dim3(kSmallBlock), kSmallClusterLdsBytes, st, p, static_cast<uint32_t>(n), hp, out, size_mirror);
   return true;

@@ -141,17 +141,19 @@ def test_reweight_lf_matches_oracle(variant, beams):
 def test_mid_size_sets_take_the_kernel_for_small_sets():
     """Default options: likelihood-field sets below 65 536 particles go to k_reweight_lf_beams (a wave per few particles, the
     lanes over the beams, no ordering pass - faster than the ordered kernels up to there), sets from there on to the ordered
-    kernels; same weights up to the rounding of the lane sums."""
+    kernels; same weights up to the rounding of the lane sums.  A set below the ordering threshold whose field has no palette form
+    (option lf_table = 1) goes to the lane-per-particle kernel in index order instead."""
     grid = rooms_grid()
     truth = synth.find_free_pose(grid.cells, grid.resolution, (grid.origin[2], grid.origin[3]), seed=2, clearance_cells=6)
     pts = make_scan(grid, truth, 360, max_range=12.0)
-    for n, beams_kernel in ((30_000, True), (65_535, True), (65_536, False)):
+    for n, table, beams_launches, fast_launches in ((30_000, 0, 1, 0), (65_535, 0, 1, 0), (65_536, 0, 0, 1), (10_000, 1, 0, 0)):
         states = synth.normal_particles(n, truth, (0.5, 0.5, 0.2), seed=5)
         f = Amcl(grid, MOTION, LF, AmclParams(min_particles=n, max_particles=n), seed=11)
+        f.set_option("lf_table", table)
         f.set_particles(states, np.ones(n))
         f.reweight(pts)
-        assert f.counter("lf_beams_launches") == (1 if beams_kernel else 0)
-        assert f.counter("lf_fast_launches") == (0 if beams_kernel else 1)
+        assert f.counter("lf_beams_launches") == beams_launches
+        assert f.counter("lf_fast_launches") == fast_launches
         sample = np.random.Generator(np.random.MT19937(2)).choice(n, 2048, replace=False)
         want = orc.lf_weights(f.likelihood_field(), grid.resolution, grid.origin, LF.max_laser_distance, states[sample], pts)
         np.testing.assert_allclose(f.particles()[1][sample], want, rtol=RTOL)
@@ -1503,6 +1505,30 @@ def test_small_sets_one_launch_tail_matches_the_kernels_of_the_large_path(lo, hi
     assert flips <= 3, flips
     if lo == 500 and hi == 2000:
         assert any(r[1]["random_state_probability"] > 0.3 for r in outs[0]), [r[1]["random_state_probability"] for r in outs[0]]
+
+
+def test_small_sets_on_two_devices_in_one_process():
+    """The dynamic-LDS opt-in of a kernel is per device: a filter on device 1, run after one on device 0, takes the one-launch tail
+    (k_small_tail) and the small-set cluster kernels as well, and computes the same bits."""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    grid = rooms_grid()
+    truth = synth.find_free_pose(grid.cells, 0.05, (-10.0, -10.0), seed=4, clearance_cells=8)
+    angles = synth.lidar_angles(180, 270.0)
+    pose = synth.odometry_step(truth, 0.3, 0.05)
+    pts = synth.scan_points(synth.cast_scan(grid.cells, 0.05, (-10.0, -10.0), pose, angles, 12.0, 0.01, seed=0), angles)
+    filters = [Amcl(grid, MOTION, LF, AmclParams(min_particles=2000, max_particles=2000), seed=11, device=d) for d in (0, 1)]
+    outs = []
+    for f in filters:
+        f.initialize(truth, np.diag([0.25, 0.25, 0.04]))
+        e = f.update(se2_from_xytheta(*synth.odometry_step((0.0, 0.0, 0.0), 0.3, 0.05)), pts)
+        assert e is not None and f.counter("small_tail_launches") == 1
+        outs.append((e, f.cluster_based_estimate()))
+    for f in filters:
+        f.close()
+    for a, b in zip(outs[0], outs[1]):
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
 @pytest.mark.parametrize("n", [1_000_000, 300_001])
