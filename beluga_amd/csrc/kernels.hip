@@ -2306,35 +2306,130 @@ __global__ __launch_bounds__(kBlock) void k_scan_chunks(const T* __restrict__ ch
   if (threadIdx.x == 0 && total) *total = s_carry;
 }
 
+// ---- The CDF's contract: non-decreasing, and flat across weights of zero ----------------------------------------------------
+// A parallel scan in f64 does not deliver either by itself: an exclusive prefix formed as (inclusive - own) is not bitwise the
+// neighbour's inclusive total, and a chunk's offset (a scan of the chunk sums) is not bitwise the last entry of the chunk before
+// it - by an ulp or so the raw scan can step down, or step up across a particle of weight zero, which then owns an interval of the
+// CDF and can be drawn.  The sums are therefore taken as before and the ORDER is enforced with max / min, which are exact and
+// associative - the result does not depend on the shape of any reduction tree:
+//   chunk level:  hi[c] = max over the chunks c' <= c with a sum > 0 of the raw inclusive scan of the chunk sums (0 if none),
+//                 lo[c] = hi[c - 1] (0 for the first chunk): chunks without weight do not move it;
+//   in a chunk:   cdf[i] = max(lo, max over j <= i in the chunk with w[j] > 0 of clamp(raw[j], lo, hi)), raw = lo + the chunk's own
+//                 scan; from the chunk's last particle with w > 0 on, cdf[i] = hi.
+// Every chunk ends on hi[c] = lo[c + 1], so the order holds across chunks as inside them, total == hi[last] == cdf[n - 1], and a
+// particle of weight zero never adds a candidate to the running maximum.  Clamping and the maximum pick values that are themselves
+// within the scan's error of the exact prefix sum of a particle at or before i with the same exact prefix: the error bound is the raw scan's.
+struct ChunkBounds {
+  double lo, hi;
+};
+// One tile of kBlock chunk sums (thread t holds the tile's t-th, 0 beyond the count); whole workgroup.  lds[0..3] wave sums,
+// lds[4..7] wave maxima, lds[8] the carried raw sum, lds[9] the carried maximum (both 0 before the first tile).  -> this
+// thread's chunk's bounds.
+__device__ __forceinline__ ChunkBounds chunk_bounds_tile(double v, double* lds) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double up = __shfl_up(incl, o);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) lds[wave] = incl;
+  __syncthreads();
+  double wave_prefix = 0.0;
+  for (int q = 0; q < wave; ++q) wave_prefix += lds[q];
+  const double raw = lds[8] + wave_prefix + incl;  // the raw inclusive scan up to this chunk
+  double mi = v > 0.0 ? raw : 0.0;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double up = __shfl_up(mi, o);
+    if (lane >= o) mi = fmax(mi, up);
+  }
+  const double before = __shfl_up(mi, 1);
+  if (lane == 63) lds[4 + wave] = mi;
+  __syncthreads();
+  double m = lds[9];
+  for (int q = 0; q < wave; ++q) m = fmax(m, lds[4 + q]);
+  const ChunkBounds r{lane ? fmax(m, before) : m, fmax(m, mi)};
+  __syncthreads();
+  if (threadIdx.x == kBlock - 1) {
+    lds[8] = raw;
+    lds[9] = r.hi;
+  }
+  __syncthreads();
+  return r;
+}
+// The bounds of `count` chunks from their sums, by one workgroup: hi[c] (lo[c] = hi[c - 1], lo[0] = 0).
+__global__ __launch_bounds__(kBlock) void k_scan_chunk_bounds(const double* __restrict__ chunk_sum, uint32_t count, double* __restrict__ hi) {
+  __shared__ double lds[10];
+  if (threadIdx.x == 0) lds[8] = lds[9] = 0.0;
+  __syncthreads();
+  for (uint32_t start = 0; start < count; start += kBlock) {
+    const uint32_t i = start + threadIdx.x;
+    const ChunkBounds b = chunk_bounds_tile(i < count ? chunk_sum[i] : 0.0, lds);
+    if (i < count) hi[i] = b.hi;
+  }
+}
+// The chunk's own part: loc[k] = the thread's running sums of its items (loc[kItems - 1] = its total), positive = bit k set where
+// item k has a weight > 0 (and lies inside the set); s_wave[kBlock / 64], s_max[kBlock / 64], s_last[kBlock / 64]; whole workgroup.
+// -> loc[k] = cdf of item k.
+__device__ __forceinline__ void chunk_cdf_ordered(double (&loc)[kChunk / kBlock], uint32_t positive, ChunkBounds b, double* s_wave, double* s_max,
+                                                  int* s_last) {
+  constexpr int kN = kChunk / kBlock;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double run = loc[kN - 1];
+  double incl = run;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double up = __shfl_up(incl, o);
+    if (lane >= o) incl += up;
+  }
+  if (lane == 63) s_wave[wave] = incl;
+  int last = positive ? static_cast<int>(threadIdx.x) * kN + (31 - __builtin_clz(positive)) : -1;  // the chunk's last item with w > 0
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o));
+  if (lane == 0) s_last[wave] = last;
+  __syncthreads();
+  double prefix = b.lo;
+  for (int q = 0; q < wave; ++q) prefix += s_wave[q];
+  prefix += incl - run;
+  double best = 0.0;  // the running maximum over this thread's items with w > 0 (every candidate is >= lo >= 0)
+#pragma unroll
+  for (int k = 0; k < kN; ++k) {
+    if ((positive >> k) & 1u) best = fmax(best, fmin(fmax(prefix + loc[k], b.lo), b.hi));
+    loc[k] = best;
+  }
+  double mi = best;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double up = __shfl_up(mi, o);
+    if (lane >= o) mi = fmax(mi, up);
+  }
+  const double before = __shfl_up(mi, 1);
+  if (lane == 63) s_max[wave] = mi;
+  __syncthreads();
+  double m = b.lo;
+  for (int q = 0; q < wave; ++q) m = fmax(m, s_max[q]);
+  if (lane) m = fmax(m, before);
+  last = max(max(s_last[0], s_last[1]), max(s_last[2], s_last[3]));
+#pragma unroll
+  for (int k = 0; k < kN; ++k) loc[k] = static_cast<int>(threadIdx.x) * kN + k >= last ? b.hi : fmax(m, loc[k]);
+}
+
 // Also writes the sampled levels of the search tree (CdfTree): element e is entry (e + 1) / 16^l - 1 of level l whenever
 // 16^l divides e + 1, and the last element closes the last (partial) group of every level.
-// The offset of chunk `me` exactly as k_scan_chunks<double> computes it (same tiles, same order, same bits), replayed by
+// The bounds of chunk `me` exactly as k_scan_chunk_bounds computes them (same tiles, same order, same bits), replayed by
 // a whole workgroup for itself: for a few hundred chunks this is cheaper than a single-workgroup kernel in between.
-__device__ __forceinline__ double chunk_offset_replay(const double* __restrict__ chunk_sum, uint32_t count, uint32_t me) {
-  __shared__ double r_wave[kBlock / 64];
-  __shared__ double r_carry, r_result;
-  if (threadIdx.x == 0) r_carry = 0.0;
+__device__ __forceinline__ ChunkBounds chunk_offset_replay(const double* __restrict__ chunk_sum, uint32_t count, uint32_t me) {
+  __shared__ double r_lds[10];
+  __shared__ ChunkBounds r_result;
+  if (threadIdx.x == 0) r_lds[8] = r_lds[9] = 0.0;
   __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (uint32_t start = 0; start <= me; start += kBlock) {
     const uint32_t i = start + threadIdx.x;
-    const double v = i < count ? chunk_sum[i] : 0.0;
-    double incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double up = __shfl_up(incl, o);
-      if (lane >= o) incl += up;
-    }
-    if (lane == 63) r_wave[wave] = incl;
-    __syncthreads();
-    double wave_prefix = 0.0;
-    for (int q = 0; q < wave; ++q) wave_prefix += r_wave[q];
-    const double carry = r_carry;
-    if (i == me) r_result = carry + wave_prefix + (incl - v);
-    __syncthreads();
-    if (threadIdx.x == kBlock - 1) r_carry = carry + wave_prefix + incl;
-    __syncthreads();
+    const ChunkBounds b = chunk_bounds_tile(i < count ? chunk_sum[i] : 0.0, r_lds);
+    if (i == me) r_result = b;
   }
+  __syncthreads();
   return r_result;
 }
 
@@ -2397,10 +2492,12 @@ __global__ __launch_bounds__(kBlock) void k_cdf(const double* __restrict__ w, ui
     norm_finalize(fin, s_wave);
     __syncthreads();
   }
-  const double my_offset = chunk_sum_to_scan ? chunk_offset_replay(chunk_sum_to_scan, chunk_count, blockIdx.x) : chunk_offset[blockIdx.x];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const ChunkBounds bounds = chunk_sum_to_scan ? chunk_offset_replay(chunk_sum_to_scan, chunk_count, blockIdx.x)
+                                               : ChunkBounds{blockIdx.x ? chunk_offset[blockIdx.x - 1] : 0.0, chunk_offset[blockIdx.x]};
   const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kChunk + threadIdx.x * kItems;
   __shared__ double s_items[kChunkPadded];
+  __shared__ double s_max[kBlock / 64];
+  __shared__ int s_last[kBlock / 64];
   double loc[kItems];
   chunk_items_load(w, n, s_items, loc);
   if (d_factor) {  // w holds the weights as the reweight left them: actions::normalize's division here (k_normalize did not store it)
@@ -2411,24 +2508,14 @@ __global__ __launch_bounds__(kBlock) void k_cdf(const double* __restrict__ w, ui
     }
   }
   double run = 0.0;
+  uint32_t positive = 0;
 #pragma unroll
   for (int k = 0; k < kItems; ++k) {
+    if (loc[k] > 0.0) positive |= 1u << k;
     run += loc[k];
     loc[k] = run;
   }
-  double incl = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double up = __shfl_up(incl, o);
-    if (lane >= o) incl += up;
-  }
-  if (lane == 63) s_wave[wave] = incl;
-  __syncthreads();
-  double prefix = my_offset;
-  for (int q = 0; q < wave; ++q) prefix += s_wave[q];
-  prefix += incl - run;
-#pragma unroll
-  for (int k = 0; k < kItems; ++k) loc[k] = prefix + loc[k];
+  chunk_cdf_ordered(loc, positive, bounds, s_wave, s_max, s_last);
   chunk_items_store(cdf, n, s_items, loc);
 #pragma unroll
   for (int k = 0; k < kItems; ++k) {
@@ -2485,34 +2572,19 @@ __device__ __forceinline__ double await_f64(unsigned long long* g, uint32_t epoc
   }
 }
 // chunk_offset_replay on values the threads hold: v[t] = the sum of chunk t * kBlock + threadIdx.x (0 from chunk `me` on).
-__device__ __forceinline__ double chunk_offset_replay_held(const double (&held)[kScanFusedMaxChunks / kBlock], uint32_t me) {
-  __shared__ double h_wave[kBlock / 64];
-  __shared__ double h_carry, h_result;
-  if (threadIdx.x == 0) h_carry = 0.0;
+__device__ __forceinline__ ChunkBounds chunk_offset_replay_held(const double (&held)[kScanFusedMaxChunks / kBlock], uint32_t me) {
+  __shared__ double h_lds[10];
+  __shared__ ChunkBounds h_result;
+  if (threadIdx.x == 0) h_lds[8] = h_lds[9] = 0.0;
   __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (uint32_t t = 0; t < kScanFusedMaxChunks / kBlock; ++t) {
     const uint32_t start = t * kBlock;
     if (start > me) break;  // (uniform)
-    const uint32_t i = start + threadIdx.x;
-    const double v = held[t];
-    double incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const double up = __shfl_up(incl, o);
-      if (lane >= o) incl += up;
-    }
-    if (lane == 63) h_wave[wave] = incl;
-    __syncthreads();
-    double wave_prefix = 0.0;
-    for (int q = 0; q < wave; ++q) wave_prefix += h_wave[q];
-    const double carry = h_carry;
-    if (i == me) h_result = carry + wave_prefix + (incl - v);
-    __syncthreads();
-    if (threadIdx.x == kBlock - 1) h_carry = carry + wave_prefix + incl;
-    __syncthreads();
+    const ChunkBounds b = chunk_bounds_tile(held[t], h_lds);
+    if (start + threadIdx.x == me) h_result = b;
   }
+  __syncthreads();
   return h_result;
 }
 __global__ __launch_bounds__(kBlock) void k_normalize_cdf(double* __restrict__ w, uint64_t n, const double* __restrict__ d_factor,
@@ -2561,22 +2633,17 @@ __global__ __launch_bounds__(kBlock) void k_normalize_cdf(double* __restrict__ w
     s_own[1] = v[1];
   }
   if (!skip && write_weights) chunk_items_store(w, n, s_items, x, me);
-  // the chunk's own scan (k_cdf)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ double s_wave[kBlock / 64];
+  // the chunk's own running sums (k_cdf)
+  __shared__ double s_wave[kBlock / 64], s_max[kBlock / 64];
+  __shared__ int s_last[kBlock / 64];
   double run = 0.0;
+  uint32_t positive = 0;
 #pragma unroll
   for (int k = 0; k < kItems; ++k) {
+    if (x[k] > 0.0) positive |= 1u << k;
     run += x[k];
     x[k] = run;
   }
-  double incl = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double up = __shfl_up(incl, o);
-    if (lane >= o) incl += up;
-  }
-  if (lane == 63) s_wave[wave] = incl;
   // the sums of the chunks before this one
   double held[kScanFusedMaxChunks / kBlock];
 #pragma unroll
@@ -2584,16 +2651,12 @@ __global__ __launch_bounds__(kBlock) void k_normalize_cdf(double* __restrict__ w
     const uint32_t i = t * kBlock + threadIdx.x;
     held[t] = i < me ? await_f64(state.granules + 4ull * i, state.epoch) : 0.0;
   }
-  __syncthreads();  // (s_wave, s_own)
+  __syncthreads();  // (s_own)
 #pragma unroll
   for (uint32_t t = 0; t < kScanFusedMaxChunks / kBlock; ++t)  // (the replay's scan runs over this chunk's own sum as well: same bits as k_cdf's)
     if (t * kBlock + threadIdx.x == me) held[t] = s_own[0];
-  const double my_offset = chunk_offset_replay_held(held, me);
-  double prefix = my_offset;
-  for (int q = 0; q < wave; ++q) prefix += s_wave[q];
-  prefix += incl - run;
-#pragma unroll
-  for (int k = 0; k < kItems; ++k) x[k] = prefix + x[k];
+  const ChunkBounds bounds = chunk_offset_replay_held(held, me);
+  chunk_cdf_ordered(x, positive, bounds, s_wave, s_max, s_last);
   __syncthreads();  // (s_items: chunk_items_store of the weights may still be read)
   chunk_items_store(cdf, n, s_items, x, me);
   const uint64_t base = static_cast<uint64_t>(me) * kChunk + threadIdx.x * kItems;
@@ -3386,8 +3449,10 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_tail(SmallTailArgs a) {
   } else {
     // ---- CDF: inclusive scan of the normalised weights, in workgroup memory
     double run = 0.0;
+    uint32_t positive = 0;
 #pragma unroll
     for (uint32_t k = 0; k < kSmallItems; ++k) {
+      if (x[k] > 0.0) positive |= 1u << k;
       run += x[k];
       x[k] = run;
     }
@@ -3402,10 +3467,30 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_tail(SmallTailArgs a) {
     __syncthreads();
     double prefix = incl - run;
     for (uint32_t q = 0; q < wave; ++q) prefix += s_wave[q];
+    // the order, as in the large path (chunk_cdf_ordered; one chunk, no bounds): the running maximum of the raw scan over the
+    // particles with w > 0 - non-decreasing, and flat across weights of zero
+    double best = 0.0;
+#pragma unroll
+    for (uint32_t k = 0; k < kSmallItems; ++k) {
+      if ((positive >> k) & 1u) best = fmax(best, prefix + x[k]);
+      x[k] = best;
+    }
+    double mi = best;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const double up = __shfl_up(mi, o);
+      if (lane >= static_cast<uint32_t>(o)) mi = fmax(mi, up);
+    }
+    const double before = __shfl_up(mi, 1);
+    __syncthreads();  // (s_wave: the sums have been read)
+    if (lane == 63) s_wave[wave] = mi;
+    __syncthreads();
+    double m = lane ? before : 0.0;
+    for (uint32_t q = 0; q < wave; ++q) m = fmax(m, s_wave[q]);
 #pragma unroll
     for (uint32_t k = 0; k < kSmallItems; ++k) {
       const uint32_t i = tid * kSmallItems + k;
-      if (i < n) s_cdf[i] = prefix + x[k];
+      if (i < n) s_cdf[i] = fmax(m, x[k]);
     }
     for (uint32_t s = tid; s < kSmallSlots; s += kSmallBlock) s_table[s] = 0xFFFFFFFFu;
     if (tid == 0) s_word[0] = 0xFFFFFFFFu;  // first candidate that fails kld_condition
@@ -4373,8 +4458,7 @@ void launch_cdf(hipStream_t st, const double* w, uint64_t n, double* d_chunk_sum
   }
   const bool replay = chunks <= 4 * kBlock;  // every workgroup re-derives its own offset: no single-workgroup scan in between
   if (!replay)
-    hipLaunchKernelGGL(k_scan_chunks<double>, dim3(1), dim3(kBlock), 0, st, sums, chunks, d_chunk_offset,
-                       static_cast<double*>(nullptr), static_cast<const double*>(nullptr));
+    hipLaunchKernelGGL(k_scan_chunk_bounds, dim3(1), dim3(kBlock), 0, st, sums, chunks, d_chunk_offset);
   NormFinalize fin{};
   if (finalize_sums) fin = make_norm_finalize(sums, finalize_sumsq, n, finalize_sums, finalize_mirror, policy);
   hipLaunchKernelGGL(k_cdf, dim3(chunks), dim3(kBlock), 0, st, w, n, d_chunk_offset, cdf, d_total,

@@ -355,7 +355,7 @@ mcl_status mcl_comm_attach_rccl(mcl_ctx* ctx, const uint8_t id[128], uint32_t ra
 typedef struct mcl_device_view {
   double* states;     /* n records of 4 doubles (cos, sin, x, y) */
   double* w;
-  double* cdf;        /* inclusive scan of the normalised weights (valid after mcl_build_cdf) */
+  double* cdf;        /* inclusive scan of the normalised weights (valid after mcl_build_cdf): non-decreasing, flat across weights of zero */
   uint64_t n;         /* live particles in this shard */
   uint64_t capacity;
   void* hip_stream;

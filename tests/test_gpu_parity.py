@@ -5,7 +5,9 @@ Tolerances (stated once, used below):
   * f64 stage outputs: relative 1e-12 (the device sums beams in a different association than the
     reference's sequential transform_reduce, and libm implementations differ by an ulp);
   * multinomial ancestors: identical except where the uniform lands within 1e-9 of a CDF step (parallel
-    prefix sums round differently from std::partial_sum) — such flips are counted and bounded.
+    prefix sums round differently from std::partial_sum) — such flips are counted and bounded.  What the CDF
+    itself is held to (its error against a high-precision prefix sum, its order, zero weights) and the searches
+    on targets chosen at its steps: test_gpu_resample_edges.py.
 """
 import math
 import os
