@@ -19,13 +19,12 @@
 #include <new>
 #include <numeric>
 #include <optional>
-#include <queue>
 #include <string>
-#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
 #include "beluga_mcl.h"
+#include "cluster_host.h"
 #include "kernels.h"
 #include "map_build.h"
 
@@ -1487,18 +1486,22 @@ mcl_status comm_agree(mcl_ctx* ctx, const char* where) {
   return MCL_OK;
 }
 
-// The estimate from the nine sums (estimation.hpp:436-475) over all shards: local sums - of the particles whose cell carries cluster id
-// wanted_plus_1 - 1 in t_cluster when t_cluster is given -, gathered, added in rank order by every rank.
-mcl_status sharded_estimate(mcl_ctx* ctx, unsigned int* t_cluster, unsigned int wanted_plus_1, mcl_estimate* out, uint64_t slots = 0) {
+// The estimate from the nine sums (estimation.hpp:436-475) over all shards: local sums - with a mask, of the particles whose cell
+// carries mask->cluster in mask->table only -, gathered, added in rank order by every rank.
+struct ClusterMask {
+  CellTable table;
+  unsigned int cluster;
+};
+mcl_status sharded_estimate(mcl_ctx* ctx, const ClusterMask* mask, mcl_estimate* out) {
   if (const mcl_status s = comm_scratch(ctx)) return s;
   const uint32_t world = ctx->comm_world;
   double* d_est = ctx->d_comm_f64.ptr + kCommEstimate;
   double* d_gather_est = comm_areas(ctx).estimates;  // [world][kEstRecord]
   if (ctx->n == 0) {
     MCL_HIP(ctx, hipMemsetAsync(d_est, 0, 9 * sizeof(double), ctx->stream));
-  } else if (t_cluster) {
-    launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, ctx->d_table_keys.ptr, t_cluster, slots, wanted_plus_1 - 1u,
-                                 ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0), d_est);
+  } else if (mask) {
+    launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, mask->table, mask->cluster, ctx->pivot[0], ctx->pivot[1],
+                                 ctx->chunk_row(0), d_est);
   } else {
     launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0), d_est);
   }
@@ -1512,20 +1515,204 @@ mcl_status sharded_estimate(mcl_ctx* ctx, unsigned int* t_cluster, unsigned int 
   return mirrored_estimate(ctx, out);
 }
 
-// algorithm/spatial_hash.hpp:45-75,87-94,190-193 on the host (neighbour cells of the cluster flood fill).
-uint64_t host_floor_and_fibo_hash(double value, unsigned shift) {
-  const int64_t sv = static_cast<int64_t>(std::floor(value));
-  const uint64_t h = 11400714819323198485ull * static_cast<uint64_t>(sv);
-  return shift ? ((h << shift) | (h >> (64 - shift))) : h;
+// ---- cluster_based_estimate (cluster_based_estimation.hpp:415-433) ------------------------------------------------------
+// Device: hashing, per-cell aggregation, masked sums (kernels.hip).  Host: the cluster assignment over the (few) occupied
+// cells, fed in first-occurrence order so that the containers evolve as they do in the reference (cluster_host.cpp).
+//
+// A CellList of `capacity` cells and, behind it, the cells' cluster ids, laid over one area per element type:
+//   u64: key[c] | f64: wsum[c], state[4 c] | u32: first[c], count[c], slot[c], cluster[c], size
+struct CellListView {
+  CellList list;
+  unsigned int* cluster;
+};
+constexpr size_t kListF64 = 5, kListU32 = 4;  // elements per cell (and one more u32: the size)
+CellListView lay_cell_list(unsigned long long* u64, double* f64, unsigned int* u32, size_t capacity) {
+  unsigned int* cluster = u32 + 3 * capacity;
+  return CellListView{CellList{u64, u32, u32 + capacity, u32 + 2 * capacity, f64, reinterpret_cast<double4*>(f64 + capacity), cluster + capacity},
+                      cluster};
 }
-uint64_t host_spatial_hash(const Pose2& s, double res_xy, double res_theta) {
-  return host_floor_and_fibo_hash(s.x / res_xy, 0) ^ host_floor_and_fibo_hash(s.y / res_xy, 21) ^
-         host_floor_and_fibo_hash(rot_log(s.r) / res_theta, 42);
+// ... the three areas behind one another in one block of cell_list_bytes(capacity) (capacity a multiple of 4: the states are double4)
+constexpr size_t cell_list_bytes(size_t capacity) {
+  return capacity * (sizeof(unsigned long long) + kListF64 * sizeof(double) + kListU32 * sizeof(unsigned int)) + 64;
+}
+CellListView lay_cell_list(unsigned char* base, size_t capacity) {
+  unsigned long long* u64 = reinterpret_cast<unsigned long long*>(base);
+  double* f64 = reinterpret_cast<double*>(u64 + capacity);
+  return lay_cell_list(u64, f64, reinterpret_cast<unsigned int*>(f64 + kListF64 * capacity), capacity);
 }
 
-// cluster_based_estimation.hpp:415-433.  Device: hashing, per-cell aggregation, masked sums.  Host: the cluster
-// assignment over the (few) occupied cells with std::unordered_map / std::priority_queue / std::nth_element, fed in
-// first-occurrence order so the containers evolve as they do in the reference.
+// The occupied cells come to the host through a list in MAPPED pinned memory that the compaction kernel writes itself (a
+// converged cloud has a few hundred cells): one synchronisation instead of seven.  A cloud with more cells than the list
+// holds (global localisation) is compacted again into the device arrays and copied.
+constexpr unsigned int kHostCells = 16384;
+struct CellScratch {
+  CellTable table;          // the KLD table's keys and first particles, the rest in d_cell_f64 / d_cell_u32; `slots` wide
+  CellListView arrays;      // the device arrays behind the table's, ctx->capacity cells
+  CellListView mapped;      // the mapped list as the host sees it
+  CellListView mapped_dev;  // ... as the device sees it
+  uint64_t m_cap;           // cells at most
+};
+mcl_status cluster_scratch(mcl_ctx* ctx, CellScratch* sc) {
+  const uint64_t n = ctx->n;
+  if (ctx->table_capacity == 0) {
+    if (const mcl_status s = ensure_kld(ctx)) return s;
+  }
+  uint64_t slots = 1024;
+  while (slots < 2 * n) slots <<= 1;
+  slots = std::min<uint64_t>(slots, ctx->table_capacity);
+  sc->m_cap = std::min<uint64_t>(n, slots);
+  const uint64_t tcap = ctx->table_capacity;
+  MCL_HIP(ctx, ctx->d_cell_f64.ensure(tcap + kListF64 * ctx->capacity));
+  MCL_HIP(ctx, ctx->d_cell_u32.ensure(2 * tcap + kListU32 * ctx->capacity + 4));
+  MCL_HIP(ctx, ctx->d_cell_u64.ensure(ctx->capacity));
+  if (!ctx->h_cells) {
+    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_cells), cell_list_bytes(kHostCells), hipHostMallocMapped));
+    MCL_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->hd_cells), ctx->h_cells, 0));
+  }
+  unsigned int* u32 = ctx->d_cell_u32.ptr;
+  sc->table = CellTable{ctx->d_table_keys.ptr, ctx->d_table_first.ptr, ctx->d_cell_f64.ptr, u32, u32 + tcap, slots};
+  sc->arrays = lay_cell_list(ctx->d_cell_u64.ptr, ctx->d_cell_f64.ptr + tcap, u32 + 2 * tcap, ctx->capacity);
+  sc->mapped = lay_cell_list(ctx->h_cells, kHostCells);
+  sc->mapped_dev = lay_cell_list(ctx->hd_cells, kHostCells);
+  return MCL_OK;
+}
+
+// This context's occupied cells, whichever path collected them.
+struct MyCells {
+  unsigned int m = 0;
+  bool small = false;          // one workgroup wrote them (k_small_cluster_cells); the masked sums take the small path too
+  bool local_failure = false;  // (sharded: reported to the peers with the count, so that every rank leaves together)
+  bool on_host_list = true;    // in the mapped list; otherwise in the device arrays, copied to `copy`
+  CellListView host;           // where the host reads them (and writes the cluster ids of the mapped list)
+  CellListView dev;            // where the device reads their slots and their cluster ids
+  std::vector<double4> copy;   // the block behind `host` beyond the mapped list
+  std::vector<uint32_t> order;  // the cells by first particle
+  Pose2 state(uint32_t k) const {
+    const double4 q = host.list.state[k];
+    return Pose2{Rot2{q.x, q.y}, q.z, q.w};
+  }
+};
+mcl_status collect_cells(mcl_ctx* ctx, const HashParams& hp, const CellScratch& sc, bool sharded, MyCells* c) {
+  const uint64_t n = ctx->n;
+  c->host = sc.mapped;
+  c->dev = sc.mapped_dev;
+  CellList out = sc.mapped_dev.list;
+  out.size = sc.arrays.list.size;  // (the counter the kernels' atomics work on stays in device memory)
+  unsigned int* hsize = sc.mapped.list.size;
+  // a small set on one context: one workgroup writes the cells straight into the mapped list (k_small_cluster_cells), another one adds the
+  // winning cluster's particles up (k_small_cluster_sums) - two launches instead of eight
+  if (n && !sharded && ctx->tuning.small_fused != 0 && n <= 4096)
+    c->small = launch_small_cluster_cells(ctx->stream, ctx->cur(), n, hp, out, sc.mapped_dev.list.size);
+  if (c->small) {
+    MCL_HIP(ctx, hipGetLastError());
+    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    c->m = *hsize;
+    if (!(c->m >= 1 && c->m <= sc.m_cap)) return fail(ctx, MCL_ERR_HIP, "cell compaction failed");
+  } else if (n) {
+    launch_cluster_cells(ctx->stream, ctx->cur(), n, hp, ctx->d_hashes.ptr, sc.table, out, kHostCells);
+    MCL_HIP(ctx, hipGetLastError());
+    MCL_HIP(ctx, hipMemcpyAsync(hsize, out.size, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    c->m = *hsize;
+    if (!(c->m >= 1 && c->m <= sc.m_cap)) {
+      if (!sharded) return fail(ctx, MCL_ERR_HIP, "cell compaction failed");
+      c->local_failure = true;
+      c->m = 0;
+    }
+  }
+  const unsigned int m = c->m;
+  ctx->cluster_cells = m;
+  c->on_host_list = m <= kHostCells;
+  if (!c->on_host_list) {
+    const CellList& big = sc.arrays.list;
+    MCL_HIP(ctx, hipMemsetAsync(big.size, 0, sizeof(unsigned int), ctx->stream));
+    launch_cluster_cells(ctx->stream, ctx->cur(), n, hp, ctx->d_hashes.ptr, sc.table, big,
+                         static_cast<unsigned int>(std::min<uint64_t>(ctx->capacity, 0xFFFFFFFFull)), /*table_ready=*/true);
+    MCL_HIP(ctx, hipGetLastError());
+    const size_t room = (static_cast<size_t>(m) + 3) & ~static_cast<size_t>(3);
+    c->copy.resize((cell_list_bytes(room) + sizeof(double4) - 1) / sizeof(double4));
+    c->host = lay_cell_list(reinterpret_cast<unsigned char*>(c->copy.data()), room);
+    c->dev = sc.arrays;
+    const CellList& h = c->host.list;
+    // on the context's stream, behind the compaction (the stream does not synchronise with the null stream)
+    MCL_HIP(ctx, hipMemcpyAsync(h.key, big.key, m * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(h.first, big.first, m * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(h.count, big.count, m * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(h.wsum, big.wsum, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(h.state, big.state, m * sizeof(double4), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  c->order.resize(m);
+  std::iota(c->order.begin(), c->order.end(), 0u);
+  const unsigned int* first = c->host.list.first;
+  std::sort(c->order.begin(), c->order.end(), [first](uint32_t a, uint32_t b) { return first[a] < first[b]; });
+  return MCL_OK;
+}
+
+// Over shards: every rank's cells in first-occurrence order (`mine`), gathered and merged rank by rank (merge_cluster_cells).
+// Leaves the global list in *cells and where each of this rank's cells went in *index_of_mine.
+mcl_status exchange_cells(mcl_ctx* ctx, bool local_failure, std::vector<ClusterCell>& mine, std::vector<ClusterCell>* cells,
+                          std::vector<uint32_t>* index_of_mine) {
+  if (const mcl_status s = comm_scratch(ctx)) return s;
+  const uint32_t world = ctx->comm_world;
+  long long* d_counts = ctx->d_comm_i64.ptr;
+  long long* h_counts = comm_host_words(ctx);
+  h_counts[0] = local_failure ? -1 : static_cast<long long>(mine.size());  // -1: this rank's compaction failed
+  MCL_HIP(ctx, hipMemcpyAsync(d_counts, h_counts, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+  if (const mcl_status s = comm_gather(ctx, d_counts, d_counts + world, sizeof(long long))) return s;
+  MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts + world, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<uint64_t> m_of(world);
+  uint64_t widest = 0;
+  for (uint32_t r = 0; r < world; ++r) {
+    if (h_counts[r] < 0)  // every rank sees it behind the same collective and returns here: nobody is left in the next one
+      return fail(ctx, MCL_ERR_HIP, "cluster_based_estimate: cell compaction failed on rank " + std::to_string(r));
+    m_of[r] = static_cast<uint64_t>(h_counts[r]);
+    widest = std::max(widest, m_of[r]);
+  }
+  mine.resize(widest, ClusterCell{});  // every rank sends the widest list's size: zero records behind its own
+  const size_t record_bytes = widest * sizeof(ClusterCell);
+  MCL_HIP(ctx, ctx->d_cell_exchange.ensure(kCellRecordDoubles * widest * (world + 1)));
+  double* d_send = ctx->d_cell_exchange.ptr;
+  double* d_recv = d_send + kCellRecordDoubles * widest;
+  MCL_HIP(ctx, hipMemcpyAsync(d_send, mine.data(), record_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (const mcl_status s = comm_gather(ctx, d_send, d_recv, record_bytes)) return s;
+  std::vector<ClusterCell> all(widest * world);
+  MCL_HIP(ctx, hipMemcpyAsync(all.data(), d_recv, all.size() * sizeof(ClusterCell), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *cells = merge_cluster_cells(all.data(), widest, m_of.data(), world, ctx->comm_rank, index_of_mine);
+  return MCL_OK;
+}
+
+// The cells' cluster ids back to the device (list order, next to the cells' slots) and the sums over the particles of cluster `wanted`.
+mcl_status cluster_sums(mcl_ctx* ctx, const HashParams& hp, const CellScratch& sc, const MyCells& c, const std::vector<unsigned int>& cluster_of,
+                        unsigned int wanted, bool sharded, mcl_estimate* out) {
+  const unsigned int m = c.m;
+  if (c.on_host_list) {  // the kernel reads the cluster ids from the mapped list
+    std::memcpy(c.host.cluster, cluster_of.data(), m * sizeof(unsigned int));
+  } else {
+    MCL_HIP(ctx, hipMemcpyAsync(c.dev.cluster, cluster_of.data(), m * sizeof(unsigned int), hipMemcpyHostToDevice, ctx->stream));
+    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (cluster_of is pageable host memory of the caller)
+  }
+  if (c.small) {  // (the cells' keys and their cluster ids are in the mapped list)
+    launch_small_cluster_sums(ctx->stream, ctx->cur(), ctx->n, hp, c.dev.list.key, c.dev.cluster, m, wanted, ctx->pivot[0], ctx->pivot[1],
+                              ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+    MCL_HIP(ctx, hipGetLastError());
+    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return mirrored_estimate(ctx, out);
+  }
+  if (m) launch_cell_set_cluster(ctx->stream, c.dev.list, c.dev.cluster, m, sc.table);
+  if (sharded) {
+    const ClusterMask mask{sc.table, wanted};
+    return sharded_estimate(ctx, &mask, out);
+  }
+  launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, sc.table, wanted, ctx->pivot[0], ctx->pivot[1],
+                               ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+  MCL_HIP(ctx, hipGetLastError());
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return mirrored_estimate(ctx, out);
+}
+
 mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_estimate* out) {
   const uint64_t n = ctx->n;
   const bool sharded = ctx->have_comm && ctx->comm_world > 1;
@@ -1533,300 +1720,40 @@ mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_e
   MCL_REQUIRE(ctx, cp.linear_hash_resolution > 0 && cp.angular_hash_resolution > 0 && cp.weight_cap_percentile >= 0 &&
                        cp.weight_cap_percentile < 1.0, "bad cluster parameters");
   MCL_REQUIRE(ctx, n < 0xFFFFFFFFull, "too many particles");
-  if (ctx->table_capacity == 0) {
-    if (const mcl_status s = ensure_kld(ctx)) return s;
-  }
-  uint64_t slots = 1024;
-  while (slots < 2 * n) slots <<= 1;
-  slots = std::min<uint64_t>(slots, ctx->table_capacity);
-  const uint64_t m_cap = std::min<uint64_t>(n, slots);
-  const uint64_t tcap = ctx->table_capacity;
-  MCL_HIP(ctx, ctx->d_cell_f64.ensure(tcap + 5 * ctx->capacity));
-  MCL_HIP(ctx, ctx->d_cell_u32.ensure(2 * tcap + 4 * ctx->capacity + 4));
-  MCL_HIP(ctx, ctx->d_cell_u64.ensure(ctx->capacity));
-  double* t_wsum = ctx->d_cell_f64.ptr;
-  double* c_wsum = t_wsum + tcap;
-  double* c_state = c_wsum + ctx->capacity;
-  unsigned int* t_count = ctx->d_cell_u32.ptr;
-  unsigned int* t_cluster = t_count + tcap;
-  unsigned int* c_first = t_cluster + tcap;
-  unsigned int* c_count = c_first + ctx->capacity;
-  unsigned int* c_slot = c_count + ctx->capacity;
-  unsigned int* c_cluster = c_slot + ctx->capacity;
-  unsigned int* c_size = c_cluster + ctx->capacity;
-  unsigned long long* c_key = ctx->d_cell_u64.ptr;
-
-  // The occupied cells come to the host through a list in MAPPED pinned memory that the compaction kernel writes itself (a
-  // converged cloud has a few hundred cells): one synchronisation instead of seven.  A cloud with more cells than the list
-  // holds (global localisation) is compacted again into the device arrays and copied.
-  constexpr unsigned int kHostCells = 16384;
-  if (!ctx->h_cells) {
-    const size_t bytes = kHostCells * (sizeof(unsigned long long) + 5 * sizeof(double) + 4 * sizeof(unsigned int)) + 64;
-    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_cells), bytes, hipHostMallocMapped));
-    MCL_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->hd_cells), ctx->h_cells, 0));
-  }
-  auto cell_views = [&](unsigned char* base, unsigned long long*& key, double*& wsum, double*& state, unsigned int*& first,
-                        unsigned int*& count, unsigned int*& slot, unsigned int*& cluster, unsigned int*& size) {
-    key = reinterpret_cast<unsigned long long*>(base);
-    wsum = reinterpret_cast<double*>(key + kHostCells);
-    state = wsum + kHostCells;
-    first = reinterpret_cast<unsigned int*>(state + 4 * kHostCells);
-    count = first + kHostCells;
-    slot = count + kHostCells;
-    cluster = slot + kHostCells;
-    size = cluster + kHostCells;
-  };
-  unsigned long long *hk, *dk;
-  double *hw, *hs, *dw, *ds;
-  unsigned int *hf, *hc, *hsl, *hcl, *hsize, *df, *dc, *dsl, *dcl, *dsize;
-  cell_views(ctx->h_cells, hk, hw, hs, hf, hc, hsl, hcl, hsize);
-  cell_views(ctx->hd_cells, dk, dw, ds, df, dc, dsl, dcl, dsize);
+  CellScratch sc;
+  if (const mcl_status s = cluster_scratch(ctx, &sc)) return s;
   const HashParams hp{cp.linear_hash_resolution, cp.linear_hash_resolution, cp.angular_hash_resolution};
-  unsigned int m = 0;
-  bool local_failure = false;  // (sharded: reported to the peers with the count, so that every rank leaves together)
-  // a small set on one context: one workgroup writes the cells straight into the mapped list (k_small_cluster_cells), another one adds the
-  // winning cluster's particles up (k_small_cluster_sums) - two launches instead of eight
-  bool small = false;
-  if (n && !sharded && ctx->tuning.small_fused != 0 && n <= 4096)
-    small = launch_small_cluster_cells(ctx->stream, ctx->cur(), n, hp, dk, df, dc, dsl, dw, ds, c_size, dsize);
-  if (small) {
-    MCL_HIP(ctx, hipGetLastError());
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    m = *hsize;
-    if (!(m >= 1 && m <= m_cap)) return fail(ctx, MCL_ERR_HIP, "cell compaction failed");
-  } else if (n) {
-    launch_cluster_cells(ctx->stream, ctx->cur(), n, hp, ctx->d_hashes.ptr, ctx->d_table_keys.ptr, ctx->d_table_first.ptr, t_wsum,
-                         t_count, t_cluster, slots, dk, df, dc, dsl, dw, ds, c_size, kHostCells);
-    MCL_HIP(ctx, hipGetLastError());
-    MCL_HIP(ctx, hipMemcpyAsync(hsize, c_size, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    m = *hsize;
-    if (!(m >= 1 && m <= m_cap)) {
-      if (!sharded) return fail(ctx, MCL_ERR_HIP, "cell compaction failed");
-      local_failure = true;
-      m = 0;
-    }
-  }
-  ctx->cluster_cells = m;
-  std::vector<unsigned long long> key_big;
-  std::vector<unsigned int> first_big, count_big;
-  std::vector<double> wsum_big, state_big;
-  const unsigned long long* key = hk;
-  const unsigned int *first = hf, *count = hc, *slot_list = dsl;
-  const double *wsum = hw, *state = hs;
-  const bool on_host_list = m <= kHostCells;
-  if (!on_host_list) {
-    MCL_HIP(ctx, hipMemsetAsync(c_size, 0, sizeof(unsigned int), ctx->stream));
-    launch_cluster_cells(ctx->stream, ctx->cur(), n, hp, ctx->d_hashes.ptr, ctx->d_table_keys.ptr, ctx->d_table_first.ptr, t_wsum,
-                         t_count, t_cluster, slots, c_key, c_first, c_count, c_slot, c_wsum, c_state, c_size,
-                         static_cast<unsigned int>(std::min<uint64_t>(ctx->capacity, 0xFFFFFFFFull)), /*table_ready=*/true);
-    MCL_HIP(ctx, hipGetLastError());
-    key_big.resize(m);
-    first_big.resize(m);
-    count_big.resize(m);
-    wsum_big.resize(m);
-    state_big.resize(4 * static_cast<size_t>(m));
-    // on the context's stream, behind the compaction (the stream does not synchronise with the null stream)
-    MCL_HIP(ctx, hipMemcpyAsync(key_big.data(), c_key, m * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipMemcpyAsync(first_big.data(), c_first, m * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipMemcpyAsync(count_big.data(), c_count, m * sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipMemcpyAsync(wsum_big.data(), c_wsum, m * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipMemcpyAsync(state_big.data(), c_state, 4 * static_cast<size_t>(m) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    key = key_big.data();
-    first = first_big.data();
-    count = count_big.data();
-    wsum = wsum_big.data();
-    state = state_big.data();
-    slot_list = c_slot;
-  }
+  MyCells mine;
+  if (const mcl_status s = collect_cells(ctx, hp, sc, sharded, &mine)) return s;
 
-  // The occupied cells in the order their first particle appears in the set (make_cluster_map :137-157 inserts them in that
-  // order).  Over shards: every rank's list in that order, gathered, and merged rank by rank - shards are contiguous pieces of
-  // the global index space, so rank order followed by local order IS the global first-occurrence order; a cell seen by
-  // several ranks keeps the state of its first particle and adds up weights and counts.
-  std::vector<uint32_t> order(m);
-  std::iota(order.begin(), order.end(), 0u);
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first[a] < first[b]; });
-  std::vector<unsigned long long> g_key;
-  std::vector<double> g_wsum, g_state;
-  std::vector<uint64_t> g_count;
-  if (!sharded) {
-    g_key.resize(m);
-    g_wsum.resize(m);
-    g_count.resize(m);
-    g_state.resize(4 * static_cast<size_t>(m));
-    for (uint32_t j = 0; j < m; ++j) {
-      const uint32_t k = order[j];
-      g_key[j] = key[k];
-      g_wsum[j] = wsum[k];
-      g_count[j] = count[k];
-      std::memcpy(&g_state[4 * static_cast<size_t>(j)], state + 4 * static_cast<size_t>(k), 4 * sizeof(double));
-    }
+  // The occupied cells in the order their first particle appears in the set; over shards, the ranks' lists merged.
+  std::vector<ClusterCell> cells(mine.m);
+  for (uint32_t j = 0; j < mine.m; ++j) {
+    const uint32_t k = mine.order[j];
+    const CellList& h = mine.host.list;
+    cells[j] = ClusterCell{h.key[k], h.wsum[k], h.count[k], mine.state(k)};
+  }
+  std::vector<uint32_t> index_of_mine;  // this context's j-th cell in `cells`: over shards, where the merge put it
+  if (sharded) {
+    std::vector<ClusterCell> local = std::move(cells);
+    if (const mcl_status s = exchange_cells(ctx, mine.local_failure, local, &cells, &index_of_mine)) return s;
   } else {
-    if (const mcl_status s = comm_scratch(ctx)) return s;
-    const uint32_t world = ctx->comm_world;
-    constexpr size_t kRecord = 7;  // doubles per cell: key (bit pattern), weight sum, count (bit pattern), state[4]
-    long long* d_counts = ctx->d_comm_i64.ptr;
-    long long* h_counts = comm_host_words(ctx);
-    h_counts[0] = local_failure ? -1 : static_cast<long long>(m);  // -1: this rank's compaction failed
-    MCL_HIP(ctx, hipMemcpyAsync(d_counts, h_counts, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-    if (const mcl_status s = comm_gather(ctx, d_counts, d_counts + world, sizeof(long long))) return s;
-    MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts + world, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<uint64_t> m_of(world);
-    uint64_t widest = 0;
-    for (uint32_t r = 0; r < world; ++r) {
-      if (h_counts[r] < 0)  // every rank sees it behind the same collective and returns here: nobody is left in the next one
-        return fail(ctx, MCL_ERR_HIP, "cluster_based_estimate: cell compaction failed on rank " + std::to_string(r));
-      m_of[r] = static_cast<uint64_t>(h_counts[r]);
-      widest = std::max(widest, m_of[r]);
-    }
-    std::vector<double> packed(kRecord * widest, 0.0);
-    for (uint32_t j = 0; j < m; ++j) {
-      const uint32_t k = order[j];
-      double* rec = &packed[kRecord * static_cast<size_t>(j)];
-      const unsigned long long cnt = count[k];
-      std::memcpy(rec + 0, &key[k], sizeof(double));
-      rec[1] = wsum[k];
-      std::memcpy(rec + 2, &cnt, sizeof(double));
-      std::memcpy(rec + 3, state + 4 * static_cast<size_t>(k), 4 * sizeof(double));
-    }
-    MCL_HIP(ctx, ctx->d_cell_exchange.ensure(kRecord * widest * (world + 1)));
-    double* d_send = ctx->d_cell_exchange.ptr;
-    double* d_recv = d_send + kRecord * widest;
-    MCL_HIP(ctx, hipMemcpyAsync(d_send, packed.data(), kRecord * widest * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (const mcl_status s = comm_gather(ctx, d_send, d_recv, kRecord * widest * sizeof(double))) return s;
-    std::vector<double> all(kRecord * widest * world);
-    MCL_HIP(ctx, hipMemcpyAsync(all.data(), d_recv, all.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    std::unordered_map<unsigned long long, size_t> seen;
-    for (uint32_t r = 0; r < world; ++r) {
-      for (uint64_t j = 0; j < m_of[r]; ++j) {
-        const double* rec = &all[kRecord * (static_cast<size_t>(r) * widest + j)];
-        unsigned long long k64, cnt;
-        std::memcpy(&k64, rec + 0, sizeof k64);
-        std::memcpy(&cnt, rec + 2, sizeof cnt);
-        const auto [it, fresh] = seen.try_emplace(k64, g_key.size());
-        if (fresh) {
-          g_key.push_back(k64);
-          g_wsum.push_back(rec[1]);
-          g_count.push_back(cnt);
-          g_state.insert(g_state.end(), rec + 3, rec + 7);
-        } else {
-          g_wsum[it->second] += rec[1];
-          g_count[it->second] += cnt;
-        }
-      }
-    }
+    index_of_mine.resize(mine.m);
+    std::iota(index_of_mine.begin(), index_of_mine.end(), 0u);
   }
-  const size_t cells = g_key.size();
-  if (cells == 0) return fail(ctx, MCL_ERR_NOT_READY, "no particles");
-  uint64_t n_global = 0;
-  for (const uint64_t c : g_count) n_global += c;
+  if (cells.empty()) return fail(ctx, MCL_ERR_NOT_READY, "no particles");
 
-  // make_cluster_map :137-157
-  struct Cell {
-    Pose2 representative_state;
-    double weight;
-    size_t num_particles;
-    std::optional<size_t> cluster_id;
-    size_t k;
-  };
-  std::unordered_map<size_t, Cell> map;
-  map.reserve(n_global / 5);
-  for (size_t k = 0; k < cells; ++k) {
-    map.try_emplace(static_cast<size_t>(g_key[k]),
-                    Cell{Pose2{Rot2{g_state[4 * k], g_state[4 * k + 1]}, g_state[4 * k + 2], g_state[4 * k + 3]}, g_wsum[k],
-                         static_cast<size_t>(g_count[k]), std::nullopt, k});
-  }
-  // normalize_and_cap_weights :173-189 (+ calculate_percentile_threshold :103-109)
-  for (auto& kv : map) kv.second.weight /= static_cast<double>(kv.second.num_particles);
-  {
-    std::vector<double> values;
-    values.reserve(map.size());
-    for (auto& kv : map) values.push_back(kv.second.weight);
-    const auto nth = static_cast<std::ptrdiff_t>(static_cast<double>(values.size()) * cp.weight_cap_percentile);
-    std::nth_element(values.begin(), values.begin() + nth, values.end());
-    const double max_weight = values[static_cast<size_t>(nth)];
-    for (auto& kv : map) kv.second.weight = std::min(kv.second.weight, max_weight);
-  }
-  // assign_clusters :203-238
-  struct KeyWithPriority {
-    double priority;
-    size_t key;
-    bool operator<(const KeyWithPriority& other) const { return priority < other.priority; }
-  };
-  std::vector<KeyWithPriority> init;
-  init.reserve(map.size());
-  for (auto& kv : map) init.push_back(KeyWithPriority{kv.second.weight, kv.first});
-  std::priority_queue<KeyWithPriority> queue(init.begin(), init.end());
-  const double max_priority = queue.top().priority;
-  const double lin = cp.linear_hash_resolution, ang = cp.angular_hash_resolution;
-  const Pose2 adjacent[6] = {Pose2{rot_exp(0.0), +lin, 0.0}, Pose2{rot_exp(0.0), -lin, 0.0}, Pose2{rot_exp(0.0), 0.0, +lin},
-                             Pose2{rot_exp(0.0), 0.0, -lin}, Pose2{rot_exp(+ang), 0.0, 0.0}, Pose2{rot_exp(-ang), 0.0, 0.0}};
-  size_t next_cluster_id = 0;
-  while (!queue.empty()) {
-    const size_t hash = queue.top().key;
-    queue.pop();
-    Cell& cell = map[hash];
-    if (!cell.cluster_id.has_value()) cell.cluster_id = next_cluster_id++;
-    for (const Pose2& adj : adjacent) {
-      uint64_t neighbor_hash = host_spatial_hash(pose_mul(cell.representative_state, adj), lin, ang);
-      if (neighbor_hash == ~0ull) neighbor_hash -= 1;  // the device table's reserved key
-      auto it = map.find(static_cast<size_t>(neighbor_hash));
-      if (it == map.end() || it->second.cluster_id.has_value() || !(it->second.weight <= cell.weight)) continue;
-      it->second.cluster_id = cell.cluster_id;
-      queue.push(KeyWithPriority{max_priority + it->second.weight, static_cast<size_t>(neighbor_hash)});
-    }
-  }
-  // estimate_clusters :345-411: clusters with more than one particle, the first one of maximum total weight
-  std::vector<double> total_w(next_cluster_id, 0.0);
-  std::vector<uint64_t> total_n(next_cluster_id, 0);
-  std::vector<unsigned int> cluster_of_cell(cells);
-  for (auto& kv : map) cluster_of_cell[kv.second.k] = static_cast<unsigned int>(kv.second.cluster_id.value());
-  for (size_t k = 0; k < cells; ++k) {  // particle-order accumulation is not reproducible from cell sums; cell order is fixed
-    total_w[cluster_of_cell[k]] += g_wsum[k];
-    total_n[cluster_of_cell[k]] += g_count[k];
-  }
-  long best = -1;
-  for (size_t c = 0; c < next_cluster_id; ++c)
-    if (total_n[c] > 1 && (best < 0 || total_w[static_cast<size_t>(best)] < total_w[c])) best = static_cast<long>(c);
-  if (best < 0) {  // :424-427 no cluster: overall mean and covariance
-    if (sharded) return sharded_estimate(ctx, nullptr, 0, out);
+  const ClusterAssignment assigned = assign_clusters(cells, cp.linear_hash_resolution, cp.angular_hash_resolution, cp.weight_cap_percentile);
+  if (!assigned.winner) {  // :424-427 no cluster: overall mean and covariance
+    if (sharded) return sharded_estimate(ctx, nullptr, out);
     double sums[12];
     if (const mcl_status s = do_estimate_sums(ctx, ctx->pivot, sums)) return s;
     return mcl_estimate_from_sums(sums, out);
   }
-  // this rank's cells -> their clusters (list order, the order of slot_list)
-  std::vector<unsigned int> cluster_of(m);
-  for (uint32_t j = 0; j < m; ++j) {
-    const uint32_t k = order[j];
-    cluster_of[k] = sharded ? static_cast<unsigned int>(map[static_cast<size_t>(key[k])].cluster_id.value()) : cluster_of_cell[j];
-  }
-  const unsigned int* cluster_list = c_cluster;
-  if (on_host_list) {  // the kernel reads the cluster ids from the mapped list
-    std::memcpy(hcl, cluster_of.data(), m * sizeof(unsigned int));
-    cluster_list = dcl;
-  } else {
-    MCL_HIP(ctx, hipMemcpyAsync(c_cluster, cluster_of.data(), m * sizeof(unsigned int), hipMemcpyHostToDevice, ctx->stream));
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (cluster_of is pageable host memory of this call)
-  }
-  if (small) {  // (the cells' keys and their cluster ids are in the mapped list: hk / hcl)
-    launch_small_cluster_sums(ctx->stream, ctx->cur(), n, hp, dk, dcl, m, static_cast<unsigned int>(best), ctx->pivot[0], ctx->pivot[1],
-                              ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
-    MCL_HIP(ctx, hipGetLastError());
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return mirrored_estimate(ctx, out);
-  }
-  if (m) launch_cell_set_cluster(ctx->stream, slot_list, cluster_list, m, t_cluster);
-  if (sharded) return sharded_estimate(ctx, t_cluster, static_cast<unsigned int>(best) + 1u, out, slots);
-  launch_estimate_sums_cluster(ctx->stream, ctx->cur(), n, ctx->d_hashes.ptr, ctx->d_table_keys.ptr, t_cluster, slots,
-                               static_cast<unsigned int>(best), ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0),
-                               ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
-  MCL_HIP(ctx, hipGetLastError());
-  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return mirrored_estimate(ctx, out);
+  // this rank's cells -> their clusters (list order, the order of the cells' slots)
+  std::vector<unsigned int> cluster_of(mine.m);
+  for (uint32_t j = 0; j < mine.m; ++j) cluster_of[mine.order[j]] = assigned.cluster_of_cell[index_of_mine[j]];
+  return cluster_sums(ctx, hp, sc, mine, cluster_of, *assigned.winner, sharded, out);
 }
 
 
@@ -2125,7 +2052,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
       MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
       ctx->comm_host_syncs += 1;
     } else {
-      if (const mcl_status s = sharded_estimate(ctx, nullptr, 0, &est)) return s;
+      if (const mcl_status s = sharded_estimate(ctx, nullptr, &est)) return s;
       if (padded && ctx->h_scalars[kSlotOverflow] != 0.0) {
         // Some rank's requests to one shard did not fit the fixed capacity (every rank reads the same sum of flags and gets here
         // together): the new set is incomplete.  The old one and its CDF are untouched - the commit wrote the other buffer -: back to
@@ -2140,7 +2067,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
         stage_end(ctx, MCL_STAGE_RESAMPLE);
         if (retry != MCL_OK) return retry;
         stage_begin(ctx, MCL_STAGE_ESTIMATE);
-        if (const mcl_status s = sharded_estimate(ctx, nullptr, 0, &est)) {
+        if (const mcl_status s = sharded_estimate(ctx, nullptr, &est)) {
           stage_end(ctx, MCL_STAGE_ESTIMATE);
           return s;
         }
@@ -2203,7 +2130,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
     stage_end(ctx, MCL_STAGE_ESTIMATE);
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   } else {
-    if (const mcl_status s = sharded_estimate(ctx, nullptr, 0, &est)) return s;
+    if (const mcl_status s = sharded_estimate(ctx, nullptr, &est)) return s;
     stage_end(ctx, MCL_STAGE_ESTIMATE);
   }
   stage_collect(ctx);

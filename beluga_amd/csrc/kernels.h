@@ -590,25 +590,40 @@ void launch_estimate_sums(hipStream_t st, Particles p, uint64_t n, double pivot_
                           double* d_out, double* host_mirror = nullptr);
 // cluster_based_estimate (algorithm/cluster_based_estimation.hpp): hash + per-cell aggregation + compaction of the occupied
 // cells (for the host's cluster assignment), the write-back of the cells' cluster ids and the masked estimate sums.
-void launch_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashParams hp, unsigned long long* d_hashes,
-                          unsigned long long* t_keys, unsigned int* t_first, double* t_wsum, unsigned int* t_count,
-                          unsigned int* t_cluster, uint64_t capacity, unsigned long long* c_key, unsigned int* c_first,
-                          unsigned int* c_count, unsigned int* c_slot, double* c_wsum, double* c_state, unsigned int* c_size,
-                          unsigned int list_capacity, bool table_ready = false);
+struct CellTable {  // the open-addressing table of the occupied cells
+  unsigned long long* keys;
+  unsigned int* first;
+  double* wsum;
+  unsigned int* count;
+  unsigned int* cluster;  // written by the host pass
+  uint64_t capacity;      // power of two
+  // What the masked sums read of a table: the keys and the cells' clusters, nothing else.
+  static CellTable keys_and_clusters(const CellTable& t) { return CellTable{t.keys, nullptr, nullptr, nullptr, t.cluster, t.capacity}; }
+};
+struct CellList {  // compacted occupied cells, arbitrary order (the host sorts by `first`)
+  unsigned long long* key;
+  unsigned int* first;
+  unsigned int* count;
+  unsigned int* slot;
+  double* wsum;
+  double4* state;  // representative state = state of particle `first` as (c, s, x, y)
+  unsigned int* size;
+};
+// (table_ready: only the compaction again, into a larger list)
+void launch_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashParams hp, unsigned long long* d_hashes, const CellTable& t,
+                          const CellList& out, unsigned int list_capacity, bool table_ready = false);
 // The same for a set of up to 4096 particles: one workgroup each (k_small_cluster_cells: straight into the caller's list - the mapped host
 // list - and its size into size_mirror as well; false = the set does not fit; k_small_cluster_sums: the cells' keys and cluster ids back
 // in, the sums of the particles of cluster `wanted` out).
-bool launch_small_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashParams hp, unsigned long long* c_key, unsigned int* c_first,
-                                unsigned int* c_count, unsigned int* c_slot, double* c_wsum, double* c_state, unsigned int* c_size,
-                                unsigned int* size_mirror);
+bool launch_small_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashParams hp, const CellList& out, unsigned int* size_mirror);
 void launch_small_cluster_sums(hipStream_t st, Particles p, uint64_t n, HashParams hp, const unsigned long long* d_keys,
                                const unsigned int* d_cluster, uint32_t cells, unsigned int wanted, double pivot_x, double pivot_y, double* d_out,
                                double* host_mirror);
-void launch_cell_set_cluster(hipStream_t st, const unsigned int* d_slot, const unsigned int* d_cluster, uint32_t m,
-                             unsigned int* t_cluster);
-void launch_estimate_sums_cluster(hipStream_t st, Particles p, uint64_t n, const unsigned long long* d_hashes,
-                                  unsigned long long* t_keys, unsigned int* t_cluster, uint64_t capacity, unsigned int wanted,
-                                  double pivot_x, double pivot_y, double* d_partials, double* d_out, double* host_mirror = nullptr);
+// t.cluster[cells.slot[k]] = d_cluster[k], k < m
+void launch_cell_set_cluster(hipStream_t st, const CellList& cells, const unsigned int* d_cluster, uint32_t m, const CellTable& t);
+void launch_estimate_sums_cluster(hipStream_t st, Particles p, uint64_t n, const unsigned long long* d_hashes, const CellTable& t,
+                                  unsigned int wanted, double pivot_x, double pivot_y, double* d_partials, double* d_out,
+                                  double* host_mirror = nullptr);
 // init: multivariate_normal_distribution.hpp:96-126 with T = V sqrt(L)
 void launch_init_normal(hipStream_t st, Particles p, uint64_t n, const double mean[3], const double T[9], uint64_t seed,
                         uint64_t index_offset);

@@ -3639,21 +3639,12 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_tail(SmallTailArgs a) {
 // ---- cluster_based_estimate (algorithm/cluster_based_estimation.hpp) ---------------------------------------------
 // Device side: spatial hash of every particle, per-cell aggregation (weight sum, count, first particle), compaction of
 // the occupied cells for the host, and the masked estimate of the winning cluster.  The cluster assignment itself is
-// a priority-queue flood fill over a few hundred cells and stays on the host (context.hip), with the reference's own
-// standard containers so that ties resolve the same way.
+// a priority-queue flood fill over a few hundred cells and stays on the host (cluster_host.cpp), with the reference's own
+// standard containers so that ties resolve the same way.  CellTable and CellList (kernels.h) are what the kernels work on.
 __global__ __launch_bounds__(kBlock) void k_cluster_hash(Particles p, uint64_t n, HashParams hp, unsigned long long* __restrict__ hashes) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i < n) hashes[i] = spatial_hash(load_pose(p, i), hp);
 }
-
-struct CellTable {
-  unsigned long long* keys;
-  unsigned int* first;
-  double* wsum;
-  unsigned int* count;
-  unsigned int* cluster;  // written by the host pass
-  uint64_t capacity;      // power of two
-};
 
 __global__ __launch_bounds__(kBlock) void k_cell_aggregate(const unsigned long long* __restrict__ hashes, const double* __restrict__ w,
                                                            uint64_t n, CellTable t) {
@@ -3701,16 +3692,6 @@ __global__ __launch_bounds__(kBlock) void k_cell_aggregate(const unsigned long l
     atomicAdd(&t.wsum[slot], lsum[s]);
   }
 }
-
-struct CellList {  // compacted occupied cells, arbitrary order (the host sorts by `first`)
-  unsigned long long* key;
-  unsigned int* first;
-  unsigned int* count;
-  unsigned int* slot;
-  double* wsum;
-  double4* state;  // representative state = state of particle `first` as (c, s, x, y)
-  unsigned int* size;
-};
 
 // One pass instead of six fills: the hash table's slots back to empty, the cell counter to zero.
 __global__ __launch_bounds__(kBlock) void k_cell_table_clear(CellTable t, unsigned int* __restrict__ list_size) {
@@ -4689,26 +4670,18 @@ void launch_estimate_sums(hipStream_t st, Particles p, uint64_t n, double pivot_
   hipLaunchKernelGGL(k_final_rows, dim3(kEstK), dim3(kBlock), 0, st, d_partials, chunks, chunks, d_out, host_mirror, Completion{});
 }
 
-void launch_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashParams hp, unsigned long long* d_hashes,
-                          unsigned long long* t_keys, unsigned int* t_first, double* t_wsum, unsigned int* t_count,
-                          unsigned int* t_cluster, uint64_t capacity, unsigned long long* c_key, unsigned int* c_first,
-                          unsigned int* c_count, unsigned int* c_slot, double* c_wsum, double* c_state, unsigned int* c_size,
-                          unsigned int list_capacity, bool table_ready) {
+void launch_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashParams hp, unsigned long long* d_hashes, const CellTable& t,
+                          const CellList& out, unsigned int list_capacity, bool table_ready) {
   if (n == 0) return;
-  const CellTable t{t_keys, t_first, t_wsum, t_count, t_cluster, capacity};
   if (!table_ready) {  // clear, hash, aggregate; table_ready: only the compaction again (into a larger list)
-    hipLaunchKernelGGL(k_cell_table_clear, dim3(blocks_for(capacity)), dim3(kBlock), 0, st, t, c_size);
+    hipLaunchKernelGGL(k_cell_table_clear, dim3(blocks_for(t.capacity)), dim3(kBlock), 0, st, t, out.size);
     hipLaunchKernelGGL(k_cluster_hash, dim3(blocks_for(n)), dim3(kBlock), 0, st, p, n, hp, d_hashes);
     hipLaunchKernelGGL(k_cell_aggregate, dim3(num_chunks(n)), dim3(kBlock), 0, st, d_hashes, p.w, n, t);
   }
-  const CellList out{c_key, c_first, c_count, c_slot, c_wsum, reinterpret_cast<double4*>(c_state), c_size};
-  hipLaunchKernelGGL(k_cell_compact, dim3(blocks_for(capacity)), dim3(kBlock), 0, st, t, p, out, list_capacity);
+  hipLaunchKernelGGL(k_cell_compact, dim3(blocks_for(t.capacity)), dim3(kBlock), 0, st, t, p, out, list_capacity);
 }
-bool launch_small_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashParams hp, unsigned long long* c_key, unsigned int* c_first,
-                                unsigned int* c_count, unsigned int* c_slot, double* c_wsum, double* c_state, unsigned int* c_size,
-                                unsigned int* size_mirror) {
+bool launch_small_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashParams hp, const CellList& out, unsigned int* size_mirror) {
   if (n == 0 || n > kSmallMax) return false;
-  const CellList out{c_key, c_first, c_count, c_slot, c_wsum, reinterpret_cast<double4*>(c_state), c_size};
   hipLaunchKernelGGL(k_small_cluster_cells, dim3(1), dim3(kSmallBlock), kSmallClusterLdsBytes, st, p, static_cast<uint32_t>(n), hp, out, size_mirror);
   return true;
 }
@@ -4718,19 +4691,17 @@ void launch_small_cluster_sums(hipStream_t st, Particles p, uint64_t n, HashPara
   hipLaunchKernelGGL(k_small_cluster_sums, dim3(1), dim3(kSmallBlock), kSmallClusterLdsBytes, st, p, static_cast<uint32_t>(n), hp, d_keys, d_cluster,
                      cells, wanted, pivot_x, pivot_y, d_out, host_mirror);
 }
-void launch_cell_set_cluster(hipStream_t st, const unsigned int* d_slot, const unsigned int* d_cluster, uint32_t m,
-                             unsigned int* t_cluster) {
+void launch_cell_set_cluster(hipStream_t st, const CellList& cells, const unsigned int* d_cluster, uint32_t m, const CellTable& t) {
   if (m == 0) return;
-  hipLaunchKernelGGL(k_cell_set_cluster, dim3(blocks_for(m)), dim3(kBlock), 0, st, d_slot, d_cluster, m, t_cluster);
+  hipLaunchKernelGGL(k_cell_set_cluster, dim3(blocks_for(m)), dim3(kBlock), 0, st, cells.slot, d_cluster, m, t.cluster);
 }
-void launch_estimate_sums_cluster(hipStream_t st, Particles p, uint64_t n, const unsigned long long* d_hashes,
-                                  unsigned long long* t_keys, unsigned int* t_cluster, uint64_t capacity, unsigned int wanted,
-                                  double pivot_x, double pivot_y, double* d_partials, double* d_out, double* host_mirror) {
+void launch_estimate_sums_cluster(hipStream_t st, Particles p, uint64_t n, const unsigned long long* d_hashes, const CellTable& t,
+                                  unsigned int wanted, double pivot_x, double pivot_y, double* d_partials, double* d_out,
+                                  double* host_mirror) {
   const uint32_t chunks = num_chunks(n);
-  const CellTable t{t_keys, nullptr, nullptr, nullptr, t_cluster, capacity};
   if (chunks)
-    hipLaunchKernelGGL(k_estimate_partials_cluster, dim3(chunks), dim3(kBlock), 0, st, p, n, d_hashes, t, wanted, pivot_x, pivot_y,
-                       d_partials, chunks);
+    hipLaunchKernelGGL(k_estimate_partials_cluster, dim3(chunks), dim3(kBlock), 0, st, p, n, d_hashes, CellTable::keys_and_clusters(t), wanted,
+                       pivot_x, pivot_y, d_partials, chunks);
   hipLaunchKernelGGL(k_final_rows, dim3(kEstK), dim3(kBlock), 0, st, d_partials, chunks, chunks, d_out, host_mirror, Completion{});
 }
 

@@ -8,6 +8,7 @@
 #include <cmath>
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // (a host-only source that hipcc compiles as HIP includes nothing else of it)
 #define MCL_HD __host__ __device__ __forceinline__
 #else
 #define MCL_HD inline

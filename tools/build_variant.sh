@@ -18,7 +18,7 @@ if [ -n "$tree" ]; then
   rev=$tree; [ "$tree" = "r04" ] && rev=83dc34d
   src=$out/src_$tree
   mkdir -p $src
-  for f in kernels.hip context.hip kernels.h se2.h rng.h map_build.h map_build.cpp; do git -C $root show $rev:beluga_amd/csrc/$f > $src/$f; done
+  for f in kernels.hip context.hip kernels.h se2.h rng.h map_build.h map_build.cpp cluster_host.h cluster_host.cpp; do git -C $root show $rev:beluga_amd/csrc/$f > $src/$f; done
   for f in beam_kernels.hip device_common.hpp; do git -C $root show $rev:beluga_amd/csrc/$f > $src/$f 2>/dev/null || rm -f $src/$f; done
   git -C $root show $rev:include/beluga_mcl.h > $src/beluga_mcl.h
 fi
@@ -29,9 +29,10 @@ if [ -f $src/beam_kernels.hip ]; then /opt/rocm/bin/hipcc $common -x hip -c $src
 if [ -n "$tree" ]; then
   /opt/rocm/bin/hipcc $common -x hip -c $src/context.hip -o $out/context.o
   /opt/rocm/bin/hipcc $common -c $src/map_build.cpp -o $out/map_build.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libbeluga_mcl.so $out/kernels.o $beam $out/context.o $out/map_build.o
+  /opt/rocm/bin/hipcc $common -c $src/cluster_host.cpp -o $out/cluster_host.o
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libbeluga_mcl.so $out/kernels.o $beam $out/context.o $out/map_build.o $out/cluster_host.o
 else
   [ -f $root/beluga_amd/lib/context.o ] || python -m beluga_amd.build
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libbeluga_mcl.so $out/kernels.o $beam $root/beluga_amd/lib/context.o $root/beluga_amd/lib/map_build.o
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libbeluga_mcl.so $out/kernels.o $beam $root/beluga_amd/lib/context.o $root/beluga_amd/lib/map_build.o $root/beluga_amd/lib/cluster_host.o
 fi
 echo built $out/libbeluga_mcl.so
