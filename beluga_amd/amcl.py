@@ -124,6 +124,99 @@ class NDTMap2d:
     resolution: float
 
 
+@dataclass
+class LandmarkModelParam:
+    """beluga::LandmarkModelParam (sensor/landmark_sensor_model.hpp:44-48)."""
+    sigma_range: float = 1.0
+    sigma_bearing: float = 1.0
+    random_prob: float = 1e-4
+
+
+@dataclass
+class BearingModelParam:
+    """beluga::BearingModelParam (sensor/bearing_sensor_model.hpp:42-45); the pose in Sophus::SE3d::data() order: quaternion x, y, z, w,
+    translation x, y, z."""
+    sigma_bearing: float = 1.0
+    sensor_pose_in_robot: Sequence[float] = (0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
+
+
+@dataclass
+class LandmarkPositionDetection:
+    """types/landmark_detection_types.hpp:39-42; as a map entry the position is in the world frame."""
+    detection_position_in_robot: Sequence[float]
+    category: int
+
+
+@dataclass
+class LandmarkBearingDetection:
+    """types/landmark_detection_types.hpp:45-48."""
+    detection_bearing_in_sensor: Sequence[float]
+    category: int
+
+
+@dataclass
+class LandmarkMapBoundaries:
+    """Eigen::AlignedBox3d (types/landmark_detection_types.hpp:36)."""
+    min: Sequence[float]
+    max: Sequence[float]
+
+
+class LandmarkMap:
+    """beluga::LandmarkMap (sensor/data/landmark_map.hpp:40-75): LandmarkMap(boundaries, landmarks) or LandmarkMap(landmarks), whose
+    boundaries are the landmarks' bounding box.  landmarks: LandmarkPositionDetection entries, or a (positions[n,3], categories[n]) pair."""
+
+    def __init__(self, *args):
+        if len(args) == 2 and isinstance(args[0], LandmarkMapBoundaries):
+            boundaries, landmarks = args
+        elif len(args) == 1:
+            boundaries, landmarks = None, args[0]
+        else:
+            raise TypeError("LandmarkMap(boundaries, landmarks) or LandmarkMap(landmarks)")
+        self.positions, self.categories = _detection_arrays(landmarks, "detection_position_in_robot")
+        if boundaries is None and len(self.positions):
+            boundaries = LandmarkMapBoundaries(self.positions.min(axis=0), self.positions.max(axis=0))
+        self.boundaries = boundaries  # (None: the empty box of the reference's empty map, which the library refuses)
+
+    def map_limits(self) -> Optional[LandmarkMapBoundaries]:
+        return self.boundaries
+
+
+def _detection_arrays(detections, attribute):
+    """(vectors[n,3] float64, categories[n] uint32) of a list of detections or of a (vectors, categories) pair."""
+    if isinstance(detections, tuple) and len(detections) == 2 and not hasattr(detections[0], "category"):
+        xyz, cat = detections
+    else:
+        detections = list(detections)
+        xyz = [getattr(d, attribute) for d in detections]
+        cat = [d.category for d in detections]
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    cat = np.ascontiguousarray(cat, dtype=np.uint32).reshape(-1)
+    if len(xyz) != len(cat):
+        raise ValueError("vectors and categories differ in length")
+    return xyz, cat
+
+
+def _landmark_params_struct(p):
+    if isinstance(p, LandmarkModelParam):
+        return capi.LandmarkParams(p.sigma_range, p.sigma_bearing, p.random_prob)
+    pose = [float(v) for v in p.sensor_pose_in_robot]
+    if len(pose) != 7:
+        raise ValueError("sensor_pose_in_robot takes 7 values (quaternion x, y, z, w, translation x, y, z)")
+    return capi.BearingParams(p.sigma_bearing, (C.c_double * 7)(*pose))
+
+
+def default_landmark_params() -> dict:
+    p = capi.LandmarkParams()
+    capi.load().mcl_default_landmark_params(C.byref(p))
+    return {"sigma_range": p.sigma_range, "sigma_bearing": p.sigma_bearing, "random_prob": p.random_prob}
+
+
+def default_bearing_params() -> dict:
+    p = capi.BearingParams()
+    capi.load().mcl_default_bearing_params(C.byref(p))
+    return {"sigma_bearing": p.sigma_bearing, "sensor_pose_in_robot": tuple(p.sensor_pose_in_robot)}
+
+
 def load_ndt_map_npz(path: str) -> NDTMap2d:
     """An NDT map saved as .npz with the HDF5 file's four datasets (cells, means, covariances, resolution)."""
     z = np.load(path)
@@ -211,8 +304,15 @@ class Amcl:
                 raise ValueError("the NDT sensor model takes an NDTMap2d")
             cfg.sensor_kind = capi.MCL_SENSOR_NDT
             self._ndt_params = sensor
+        elif isinstance(sensor, (LandmarkModelParam, BearingModelParam)):
+            if not isinstance(grid, LandmarkMap):
+                raise ValueError("the landmark and bearing sensor models take a LandmarkMap")
+            cfg.sensor_kind = capi.MCL_SENSOR_LANDMARK if isinstance(sensor, LandmarkModelParam) else capi.MCL_SENSOR_BEARING
+            self._landmark_params = sensor
         else:
-            raise ValueError("sensor must be LikelihoodFieldModelParam, BeamModelParam or NDTModelParam2d")
+            raise ValueError("sensor must be LikelihoodFieldModelParam, BeamModelParam, NDTModelParam2d, LandmarkModelParam or BearingModelParam")
+        if isinstance(grid, LandmarkMap) and not isinstance(sensor, (LandmarkModelParam, BearingModelParam)):
+            raise ValueError("a LandmarkMap needs the landmark or the bearing sensor model")
         if isinstance(grid, NDTMap2d) and not isinstance(sensor, NDTModelParam2d):
             raise ValueError("an NDTMap2d needs the NDT sensor model (NDTModelParam2d)")
         cfg.shard_offset = shard_offset
@@ -231,6 +331,7 @@ class Amcl:
         self._est_ref, self._info_ref = C.byref(self._est), C.byref(self._info)
         self._est_view = np.frombuffer(self._est, dtype=np.float64, count=13)  # pose[4] | covariance[9]
         self._have_info = False
+        self._landmark_kind = cfg.sensor_kind if cfg.sensor_kind in (capi.MCL_SENSOR_LANDMARK, capi.MCL_SENSOR_BEARING) else 0
         # a second handle of mcl_update that takes the arrays as raw addresses (no per-call pointer objects)
         self._update_fn = self._lib["mcl_update"]
         self._update_fn.restype = C.c_int32
@@ -257,7 +358,22 @@ class Amcl:
 
     # -- reference surface -------------------------------------------------------------------------
     def update_map(self, grid):
-        """Amcl::update_map (amcl_core.hpp:150): an OccupancyGrid, or an NDTMap2d for the NDT sensor model."""
+        """Amcl::update_map (amcl_core.hpp:150): an OccupancyGrid, an NDTMap2d for the NDT sensor model, or a LandmarkMap for the
+        landmark and bearing sensor models."""
+        if isinstance(grid, LandmarkMap):
+            pos = np.ascontiguousarray(grid.positions, dtype=np.float64).reshape(-1, 3)
+            cat = np.ascontiguousarray(grid.categories, dtype=np.uint32).reshape(-1)
+            box = None
+            if grid.boundaries is not None:
+                box = np.concatenate([np.asarray(grid.boundaries.min, dtype=np.float64).reshape(3),
+                                      np.asarray(grid.boundaries.max, dtype=np.float64).reshape(3)])
+            sensor = getattr(self, "_landmark_params", None)
+            prm = _landmark_params_struct(sensor) if sensor is not None else None
+            self._check(self._lib.mcl_set_landmark_map(self._ctx, _dp(pos), cat.ctypes.data_as(capi.c_u32_p), len(pos),
+                                                       _dp(box) if box is not None else None, C.byref(prm) if prm is not None else None))
+            self._shape = None
+            self._pending_shape = None
+            return
         if isinstance(grid, NDTMap2d):
             keys = np.ascontiguousarray(grid.cells, dtype=np.int32).reshape(-1, 2)
             means = np.ascontiguousarray(grid.means, dtype=np.float64).reshape(-1, 2)
@@ -392,6 +508,8 @@ class Amcl:
     def update(self, control_action, measurement) -> Optional[Tuple[np.ndarray, np.ndarray]]:
         """Amcl::update (amcl_core.hpp:165-201). Returns (pose (cos,sin,x,y), covariance 3x3) or None."""
         # This wrapper sits inside the measured cycle: no per-call ctypes objects, no dict, raw addresses for the arrays.
+        if self._landmark_kind:
+            return self._update_detections(control_action, measurement)
         ctrl = control_action if (type(control_action) is np.ndarray and control_action.dtype == np.float64
                                   and control_action.flags.c_contiguous) else np.ascontiguousarray(control_action, dtype=np.float64)
         pts = measurement if (type(measurement) is np.ndarray and measurement.dtype == np.float64
@@ -399,6 +517,19 @@ class Amcl:
         status = self._update_fn(self._ctx, ctrl.ctypes.data, pts.ctypes.data, pts.size // 2, self._est_ref, self._info_ref)
         if status != 0:
             self._check(status)
+        self._have_info = True
+        if not self._info.updated:
+            return None
+        out = self._est_view.copy()
+        return out[:4], out[4:13].reshape(3, 3)
+
+    def _update_detections(self, control_action, detections):
+        """update(control, std::vector<LandmarkPositionDetection>) / (control, std::vector<LandmarkBearingDetection>)."""
+        ctrl = np.ascontiguousarray(control_action, dtype=np.float64)
+        landmark = self._landmark_kind == capi.MCL_SENSOR_LANDMARK
+        xyz, cat = _detection_arrays(detections, "detection_position_in_robot" if landmark else "detection_bearing_in_sensor")
+        fn = self._lib.mcl_update_landmarks if landmark else self._lib.mcl_update_bearings
+        self._check(fn(self._ctx, _dp(ctrl), _dp(xyz), cat.ctypes.data_as(capi.c_u32_p), len(xyz), self._est_ref, self._info_ref))
         self._have_info = True
         if not self._info.updated:
             return None
@@ -444,6 +575,16 @@ class Amcl:
         if len(m) != len(c):
             raise ValueError("reweight_ndt_cells: means and covariances differ in length")
         self._check(self._lib.mcl_reweight_ndt_cells(self._ctx, _dp(m), _dp(c), len(m)))
+
+    def reweight_landmarks(self, detections):
+        """Landmark model: w *= product over the detections (LandmarkPositionDetection entries or a (positions, categories) pair)."""
+        xyz, cat = _detection_arrays(detections, "detection_position_in_robot")
+        self._check(self._lib.mcl_reweight_landmarks(self._ctx, _dp(xyz), cat.ctypes.data_as(capi.c_u32_p), len(xyz)))
+
+    def reweight_bearings(self, detections):
+        """Bearing model: w *= product over the detections (LandmarkBearingDetection entries or a (bearings, categories) pair)."""
+        xyz, cat = _detection_arrays(detections, "detection_bearing_in_sensor")
+        self._check(self._lib.mcl_reweight_bearings(self._ctx, _dp(xyz), cat.ctypes.data_as(capi.c_u32_p), len(xyz)))
 
     def weight_sum(self) -> float:
         v = C.c_double(0)

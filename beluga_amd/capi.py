@@ -26,6 +26,9 @@ MCL_SENSOR_BEAM = 1
 MCL_SENSOR_LIKELIHOOD_FIELD_PROB = 2
 MCL_SENSOR_NDT = 3
 MCL_NDT_MAX_OFFSETS = 32
+MCL_SENSOR_LANDMARK = 4
+MCL_SENSOR_BEARING = 5
+MCL_LANDMARK_MAX_DETECTIONS = 64
 MCL_MOTION_DIFFERENTIAL, MCL_MOTION_OMNIDIRECTIONAL, MCL_MOTION_STATIONARY = 0, 1, 2
 
 STAGES = ("propagate", "reweight", "normalize", "resample", "estimate", "sensor_kernel")
@@ -69,6 +72,14 @@ class BeamParams(C.Structure):
 class NdtParams(C.Structure):
     _fields_ = [("minimum_likelihood", C.c_double), ("d1", C.c_double), ("d2", C.c_double), ("num_offsets", C.c_uint32),
                 ("offsets", C.c_int32 * (2 * MCL_NDT_MAX_OFFSETS))]
+
+
+class LandmarkParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("sigma_range", "sigma_bearing", "random_prob")]
+
+
+class BearingParams(C.Structure):
+    _fields_ = [("sigma_bearing", C.c_double), ("sensor_pose_in_robot", C.c_double * 7)]
 
 
 class Config(C.Structure):
@@ -182,6 +193,13 @@ _SIGNATURES = {
     "mcl_set_ndt_map": (C.c_int32, [_ctx, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_uint64, C.c_double, C.POINTER(NdtParams)]),
     "mcl_ndt_measurement_cells": (C.c_int32, [c_double_p, C.c_uint64, C.c_double, c_double_p, c_double_p, c_u64_p]),
     "mcl_reweight_ndt_cells": (C.c_int32, [_ctx, c_double_p, c_double_p, C.c_uint64]),
+    "mcl_default_landmark_params": (None, [C.POINTER(LandmarkParams)]),
+    "mcl_default_bearing_params": (None, [C.POINTER(BearingParams)]),
+    "mcl_set_landmark_map": (C.c_int32, [_ctx, c_double_p, c_u32_p, C.c_uint64, c_double_p, C.c_void_p]),
+    "mcl_update_landmarks": (C.c_int32, [_ctx, c_double_p, c_double_p, c_u32_p, C.c_uint64, C.POINTER(Estimate), C.POINTER(UpdateInfo)]),
+    "mcl_update_bearings": (C.c_int32, [_ctx, c_double_p, c_double_p, c_u32_p, C.c_uint64, C.POINTER(Estimate), C.POINTER(UpdateInfo)]),
+    "mcl_reweight_landmarks": (C.c_int32, [_ctx, c_double_p, c_u32_p, C.c_uint64]),
+    "mcl_reweight_bearings": (C.c_int32, [_ctx, c_double_p, c_u32_p, C.c_uint64]),
     "mcl_version": (C.c_char_p, []),
     "mcl_measurement_build": (C.c_int, []),
 }

@@ -21,6 +21,7 @@
 #include <optional>
 #include <string>
 #include <unordered_set>
+#include <map>
 #include <vector>
 
 #include "beluga_mcl.h"
@@ -410,8 +411,22 @@ struct mcl_ctx {
   bool ndt_random_ready{false};        // ndt_random was prepared for the next draw (prepare_ndt_random)
   DeviceBuffer<double> d_ndt_est;      // scratch of the estimate behind ndt_random (9 rows of num_chunks(n))
   bool is_ndt() const { return cfg.sensor_kind == MCL_SENSOR_NDT; }
+
+  // Landmark and bearing sensor models (MCL_SENSOR_LANDMARK, MCL_SENSOR_BEARING): the map of mcl_set_landmark_map - the landmarks grouped
+  // by category on the device, each category's (first, count) on the host - and the box its random states are drawn from.
+  bool have_landmark_map{false};
+  DeviceBuffer<double> d_landmarks;
+  LandmarkMapView landmark_view{};
+  std::map<uint32_t, std::pair<uint32_t, uint32_t>> landmark_ranges;  // category -> (first, count) in d_landmarks
+  FreeCells landmark_random{nullptr, 0};
+  std::vector<double> h_landmark_meas;  // the detections, kLandmarkRecord doubles each (what stage_points uploads)
+  bool is_landmark() const { return cfg.sensor_kind == MCL_SENSOR_LANDMARK || cfg.sensor_kind == MCL_SENSOR_BEARING; }
+  // A sensor model with a map of its own: no occupancy grid, none of the likelihood-field machinery, the host-read policy path.
+  bool off_grid() const { return is_ndt() || is_landmark(); }
   // What random_intersperse's random states are drawn from (random_free_state).
-  FreeCells random_source() const { return is_ndt() ? ndt_random : FreeCells{d_free.ptr, have_map ? n_free : 0}; }
+  FreeCells random_source() const {
+    return is_ndt() ? ndt_random : is_landmark() ? landmark_random : FreeCells{d_free.ptr, have_map ? n_free : 0};
+  }
 };
 
 namespace {
@@ -757,7 +772,7 @@ void points_pulled(mcl_ctx* ctx, bool with_event) {
 uint32_t key_layout(const mcl_ctx* ctx) {
   const uint32_t curve = ctx->tuning.key_curve ? 0u : 2u;  // heading-major keys: Hilbert curve (default) / Morton order
   if (ctx->tuning.key_layout >= 0) return (ctx->tuning.key_layout ? 1u : 0u) | curve;
-  return (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM && !ctx->is_ndt() && ctx->tuning.lf_patch == 1 && !ctx->patch_useful && ctx->tuning.lf_far_tiles != 0 &&
+  return (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM && !ctx->off_grid() && ctx->tuning.lf_patch == 1 && !ctx->patch_useful && ctx->tuning.lf_far_tiles != 0 &&
                   ctx->far_tiles != 0
               ? 1u
               : 0u) |
@@ -939,7 +954,7 @@ void decide_lf_mode(mcl_ctx* ctx) {
   ctx->lf_mode.decided = true;
   ctx->lf_mode.patches = false;
   ctx->lf_mode.beams = false;
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM || ctx->is_ndt()) return;
+  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM || ctx->off_grid()) return;
   const bool palette = ctx->pal_count != 0 && ctx->tuning.lf_table == 0;
   if (ctx->tuning.lf_variant == kLfBeamLanes) {
     ctx->lf_mode.beams = palette;
@@ -954,7 +969,7 @@ void decide_lf_mode(mcl_ctx* ctx) {
 // Is the set spatially ordered before the reweight?  The one answer for k_propagate's keys, the order ahead and the LF kernel.
 bool wants_ordering(const mcl_ctx* ctx) {
   if (ctx->n >= (1ull << 32)) return false;
-  if (ctx->is_ndt()) return false;  // (a lane per particle in index order: the NDT map lives in L2, locality buys nothing)
+  if (ctx->off_grid()) return false;  // (a lane per particle in index order: these maps live in L2 or the scalar cache, locality buys nothing)
   if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) return ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles);
   if (ctx->n < static_cast<uint64_t>(ctx->tuning.sort_min_particles)) return false;
   if (ctx->lf_mode.decided && ctx->lf_mode.beams) return false;
@@ -1022,6 +1037,10 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
     MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
     return MCL_OK;
   }
+  if (ctx->is_landmark()) {
+    if (!ctx->have_landmark_map) return fail(ctx, MCL_ERR_NOT_READY, "no landmark map set (mcl_set_landmark_map)");
+    return MCL_OK;
+  }
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no map set");
   MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
   if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM && !(ctx->n < (1ull << 32) && ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles)))
@@ -1064,6 +1083,13 @@ mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_
     // B counts staged doubles in pairs (stage_points): the measurement cells are kNdtRecord doubles each
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
     launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, static_cast<uint32_t>(2 * B / kNdtRecord));
+    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
+  } else if (ctx->is_landmark()) {
+    // (B counts staged doubles in pairs as well: the detections are kLandmarkRecord doubles each)
+    const uint32_t k = static_cast<uint32_t>(2 * B / kLandmarkRecord);
+    stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
+    if (ctx->cfg.sensor_kind == MCL_SENSOR_LANDMARK) launch_reweight_landmarks(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    else launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
@@ -2254,7 +2280,7 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
   *out = nullptr;
   if (cfg->amcl.max_particles == 0 || cfg->amcl.resample_interval == 0)
     return fail(nullptr, MCL_ERR_INVALID_ARGUMENT, "mcl_create: max_particles and resample_interval must be > 0");
-  if (cfg->sensor_kind < MCL_SENSOR_LIKELIHOOD_FIELD || cfg->sensor_kind > MCL_SENSOR_NDT)
+  if (cfg->sensor_kind < MCL_SENSOR_LIKELIHOOD_FIELD || cfg->sensor_kind > MCL_SENSOR_BEARING)
     return fail(nullptr, MCL_ERR_INVALID_ARGUMENT, "mcl_create: unknown sensor_kind");
   if (cfg->motion_kind < MCL_MOTION_DIFFERENTIAL || cfg->motion_kind > MCL_MOTION_STATIONARY)
     return fail(nullptr, MCL_ERR_INVALID_ARGUMENT, "mcl_create: unknown motion_kind");
@@ -2371,6 +2397,7 @@ void mcl_destroy(mcl_ctx* ctx) {
   ctx->d_ndt_grid.release();
   ctx->d_ndt_cells.release();
   ctx->d_ndt_est.release();
+  ctx->d_landmarks.release();
   if (ctx->rccl_comm) {
     if (RcclApi* api = rccl_api(nullptr)) (void)api->CommDestroy(ctx->rccl_comm);
   }
@@ -2426,7 +2453,7 @@ extern "C" {
 mcl_status mcl_set_map(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32_t height, double resolution,
                        const double origin[4], const int8_t value_traits[3]) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_map: not on an NDT context (its map comes from mcl_set_ndt_map)");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_map: not on a context whose sensor model has a map of its own (mcl_set_ndt_map, mcl_set_landmark_map)");
   MCL_REQUIRE(ctx, cells && origin && value_traits && width > 0 && height > 0 && resolution > 0, "mcl_set_map: bad argument");
   MCL_REQUIRE(ctx, static_cast<uint64_t>(width) * height < 0xFFFFFFFFull, "mcl_set_map: grid too large");
   drop_pending_map(ctx);  // (a map given now replaces one that is still on its way)
@@ -2436,7 +2463,7 @@ mcl_status mcl_set_map(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32
 mcl_status mcl_set_map_async(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32_t height, double resolution,
                              const double origin[4], const int8_t value_traits[3]) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_map_async: not on an NDT context (its map comes from mcl_set_ndt_map)");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_map_async: not on a context whose sensor model has a map of its own (mcl_set_ndt_map, mcl_set_landmark_map)");
   MCL_REQUIRE(ctx, cells && origin && value_traits && width > 0 && height > 0 && resolution > 0, "mcl_set_map_async: bad argument");
   MCL_REQUIRE(ctx, static_cast<uint64_t>(width) * height < 0xFFFFFFFFull, "mcl_set_map_async: grid too large");
   if (ctx->have_comm && ctx->comm_world > 1)
@@ -2557,7 +2584,7 @@ extern "C" {
 mcl_status mcl_get_likelihood_field(mcl_ctx* ctx, float* out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, out, "null output");
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "The current sensor model does not support likelihood field");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "The current sensor model does not support likelihood field");
   if (!ctx->have_map || !ctx->d_field.ptr) return fail(ctx, MCL_ERR_NOT_READY, "no likelihood field");
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2568,7 +2595,7 @@ mcl_status mcl_get_likelihood_field(mcl_ctx* ctx, float* out) {
 mcl_status mcl_set_likelihood_field(mcl_ctx* ctx, const float* field) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, field, "null field");
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_likelihood_field: not on an NDT context (its map comes from mcl_set_ndt_map)");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_likelihood_field: not on a context whose sensor model has a map of its own (mcl_set_ndt_map, mcl_set_landmark_map)");
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "set the map first");
   if (const mcl_status s = bind_device(ctx)) return s;
   const size_t n = static_cast<size_t>(ctx->W) * ctx->H;
@@ -2662,6 +2689,7 @@ mcl_status mcl_propagate(mcl_ctx* ctx, const double pose[4], const double previo
 
 mcl_status mcl_reweight(mcl_ctx* ctx, const double* points_xy, uint64_t num_points) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_reweight: a landmark or bearing context takes mcl_reweight_landmarks / mcl_reweight_bearings");
   MCL_REQUIRE(ctx, num_points == 0 || points_xy, "null points");
   if (const mcl_status s = bind_device(ctx)) return s;
   if (ctx->is_ndt()) {
@@ -2753,9 +2781,10 @@ mcl_status mcl_estimate_pose(mcl_ctx* ctx, mcl_estimate* out) {
   return s;
 }
 
-mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* points_xy, uint64_t num_points,
-                      mcl_estimate* estimate, mcl_update_info* info) {
-  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+// Amcl::update (amcl_core.hpp:165-201) over a measurement in the form the context's reweight kernel reads: the scan's points, or the
+// detection records of a landmark / bearing context (mcl_update_landmarks, mcl_update_bearings).
+static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], const double* points_xy, uint64_t num_points,
+                               mcl_estimate* estimate, mcl_update_info* info) {
   MCL_REQUIRE(ctx, control_pose && (num_points == 0 || points_xy), "null argument");
   const auto t_entry = std::chrono::steady_clock::now();
   if (info) {
@@ -2802,16 +2831,17 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
   // With a fixed particle count and no selective resampling nothing in the cycle depends on a host-side decision: the
   // recovery estimator runs on the device as well and the cycle synchronises once, at the estimate.
   const mcl_amcl_params& ap = ctx->cfg.amcl;
-  // (not the NDT model: its random states need the estimate of the normalised set where the probability is > 0, a host decision)
+  // (not the NDT model: its random states need the estimate of the normalised set where the probability is > 0, a host decision; the
+  // landmark and bearing models follow it)
   const bool device_policy = !ap.selective_resampling && ap.min_particles >= std::min<uint64_t>(ap.max_particles, ctx->capacity) &&
-                             ctx->tuning.device_policy != 0 && !ctx->is_ndt();
+                             ctx->tuning.device_policy != 0 && !ctx->off_grid();
   // (the normalisation follows at once: the LF kernel leaves the sums it is built on)
   if (const mcl_status s = do_reweight(ctx, points_xy, num_points, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0)) return s;  // :176
   // Small sets (the reference's own sizes): everything behind the reweight in ONE launch of one workgroup and one synchronisation
   // (k_small_tail) - the policies are evaluated on the device, the host keeps the recovery filters' state.
   const uint64_t every_n = next_every_n(ctx);  // :181 (stored by the path that takes the cycle)
   const bool fires = every_n == 0;
-  if (ctx->tuning.small_fused != 0 && !ctx->is_ndt() && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096) {
+  if (ctx->tuning.small_fused != 0 && !ctx->off_grid() && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096) {
     SmallTail t{};
     t.src = ctx->cur();
     t.dst = ctx->other();
@@ -2949,6 +2979,13 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
   return MCL_OK;
 }
 
+mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* points_xy, uint64_t num_points,
+                      mcl_estimate* estimate, mcl_update_info* info) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_update: a landmark or bearing context takes mcl_update_landmarks / mcl_update_bearings");
+  return update_cycle(ctx, control_pose, points_xy, num_points, estimate, info);
+}
+
 mcl_status mcl_prepare_laser_scan(const mcl_laser_scan* scan, double* points_xy, uint64_t* num_points) {
   if (!scan || !num_points || (scan->num_ranges && (!scan->ranges || !points_xy))) return MCL_ERR_INVALID_ARGUMENT;
   const uint64_t n = scan->num_ranges, count = scan->max_beams;
@@ -2986,6 +3023,7 @@ mcl_status mcl_prepare_laser_scan(const mcl_laser_scan* scan, double* points_xy,
 mcl_status mcl_update_laser_scan(mcl_ctx* ctx, const double control_pose[4], const mcl_laser_scan* scan, mcl_estimate* estimate,
                                  mcl_update_info* info) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_update_laser_scan: not on a landmark or bearing context");
   MCL_REQUIRE(ctx, scan != nullptr, "null scan");
   std::vector<double> pts(2 * std::min<uint64_t>(scan->num_ranges, scan->max_beams) + 2);
   uint64_t m = 0;
@@ -3089,7 +3127,7 @@ mcl_status mcl_build_cdf(mcl_ctx* ctx, double* total) {
 mcl_status mcl_resample_targets(mcl_ctx* ctx, uint32_t step, double random_state_probability, double total,
                                 uint64_t first_slot, uint64_t count, double* d_targets) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_resample_targets: the sharded resampling steps are not available on an NDT context");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_resample_targets: the sharded resampling steps are not available on an NDT, landmark or bearing context");
   MCL_REQUIRE(ctx, count == 0 || d_targets, "null targets");
   if (const mcl_status s = bind_device(ctx)) return s;
   launch_resample_targets(ctx->stream, ctx->cfg.seed, step, random_state_probability, total, first_slot, count,
@@ -3131,7 +3169,7 @@ mcl_status mcl_serve_requests(mcl_ctx* ctx, const double* d_requests, uint64_t m
 mcl_status mcl_commit_routed(mcl_ctx* ctx, uint32_t step, uint64_t first_slot, uint64_t count, const double* d_replies,
                              const uint32_t* d_order, const double* d_targets) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_commit_routed: the sharded resampling steps are not available on an NDT context");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_commit_routed: the sharded resampling steps are not available on an NDT, landmark or bearing context");
   MCL_REQUIRE(ctx, count <= ctx->capacity, "count exceeds shard capacity");
   MCL_REQUIRE(ctx, count == 0 || (d_replies && d_order && d_targets), "null argument");
   if (const mcl_status s = bind_device(ctx)) return s;
@@ -3149,7 +3187,7 @@ mcl_status mcl_commit_routed(mcl_ctx* ctx, uint32_t step, uint64_t first_slot, u
 mcl_status mcl_finish_candidates(mcl_ctx* ctx, uint32_t step, uint64_t first_slot, uint64_t count, const double* d_replies,
                                  const uint32_t* d_order, const double* d_targets, double* d_states, uint64_t* d_hashes) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_finish_candidates: the sharded resampling steps are not available on an NDT context");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_finish_candidates: the sharded resampling steps are not available on an NDT, landmark or bearing context");
   MCL_REQUIRE(ctx, count == 0 || (d_replies && d_order && d_targets && d_states && d_hashes), "null argument");
   if (const mcl_status s = bind_device(ctx)) return s;
   const mcl_amcl_params& a = ctx->cfg.amcl;
@@ -3248,6 +3286,19 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
   ctx->lf_wsum_count = 0;  // (workgroup sums of an earlier reweight describe another set)
   ctx->order_valid = false;  // (and an order computed ahead describes the particles of another one)
   if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_initialize_from_map: not on an NDT context (its map comes from mcl_set_ndt_map)");
+  if (ctx->is_landmark()) {  // uniformly over the x-y extent of the map's boundaries: the generator of the recovery's random states, step 0
+    if (!ctx->have_landmark_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no landmark map set (mcl_set_landmark_map)");
+    if (const mcl_status s = bind_device(ctx)) return s;
+    const uint64_t n = std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity);
+    launch_init_from_map(ctx->stream, ctx->cur(), n, ctx->cfg.seed, ctx->cfg.shard_offset, ctx->grid_view(), ctx->landmark_random);
+    MCL_HIP(ctx, hipGetLastError());
+    ctx->weights_unit = true;
+    ctx->n = n;
+    ctx->global_n = 0;
+    ctx->global_n_unknown = false;
+    ctx->force_update = true;
+    return MCL_OK;
+  }
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no map set");
   MCL_REQUIRE(ctx, ctx->n_free > 0, "mcl_initialize_from_map: the map has no free cell");  // the reference asserts (:136)
   if (const mcl_status s = bind_device(ctx)) return s;
@@ -3293,7 +3344,7 @@ mcl_status mcl_has_likelihood_field(const mcl_ctx* ctx, int32_t* has) {
 mcl_status mcl_get_likelihood_field_origin(mcl_ctx* ctx, double origin[4]) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, origin, "null output");
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM || ctx->is_ndt())
+  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM || ctx->off_grid())
     return fail(ctx, MCL_ERR_UNSUPPORTED, "The current sensor model does not support likelihood field");
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "no likelihood field");
   // likelihood_field_model_base.hpp:105: world_to_likelihood_field_transform_.inverse(), i.e. inverse(inverse(grid.origin()))
@@ -3326,6 +3377,7 @@ mcl_status mcl_project_point_cloud(const float* points_xyz, uint64_t num_points,
 mcl_status mcl_update_point_cloud(mcl_ctx* ctx, const double control_pose[4], const float* points_xyz, uint64_t num_points,
                                   const double origin_se3[7], mcl_estimate* estimate, mcl_update_info* info) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_update_point_cloud: not on a landmark or bearing context");
   MCL_REQUIRE(ctx, origin_se3 && (num_points == 0 || points_xyz), "null argument");
   std::vector<double> pts(2 * num_points + 2);
   if (mcl_project_point_cloud(points_xyz, num_points, origin_se3, pts.data()) != MCL_OK) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, "bad point cloud");
@@ -3470,7 +3522,7 @@ mcl_status mcl_debug_set_recovery_filters(mcl_ctx* ctx, double slow, double fast
 
 mcl_status mcl_comm_attach(mcl_ctx* ctx, uint32_t rank, uint32_t world, const mcl_transport* transport) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach: the NDT model runs on one device");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach: the NDT, landmark and bearing models run on one device");
   MCL_REQUIRE(ctx, world >= 1 && world <= 64 && rank < world, "mcl_comm_attach: world must be 1..64, rank < world");
   MCL_REQUIRE(ctx, world == 1 || (transport && transport->all_gather && transport->all_to_all), "mcl_comm_attach: incomplete transport");
   MCL_REQUIRE(ctx, world == 1 || ctx->cfg.shard_capacity > 0, "mcl_comm_attach: create the context with its shard_offset / shard_capacity");
@@ -3504,7 +3556,7 @@ mcl_status mcl_comm_unique_id(uint8_t id[128]) {
 
 mcl_status mcl_comm_attach_rccl(mcl_ctx* ctx, const uint8_t id[128], uint32_t rank, uint32_t world) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach_rccl: the NDT model runs on one device");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach_rccl: the NDT, landmark and bearing models run on one device");
   MCL_REQUIRE(ctx, id && world >= 1 && world <= 64 && rank < world, "mcl_comm_attach_rccl: bad argument");
   std::string error;
   RcclApi* api = rccl_api(&error);
@@ -3545,6 +3597,7 @@ void mcl_default_ndt_params(mcl_ndt_params* params) {
 mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* means, const double* covariances, uint64_t n,
                            double resolution, const mcl_ndt_params* params) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_map: not on a landmark or bearing context (its map comes from mcl_set_landmark_map)");
   MCL_REQUIRE(ctx, ctx->is_ndt(), "mcl_set_ndt_map: the context's sensor model is not MCL_SENSOR_NDT");
   MCL_REQUIRE(ctx, cells && means && covariances && n > 0, "mcl_set_ndt_map: null argument or no cells");
   MCL_REQUIRE(ctx, n < (1ull << 31), "mcl_set_ndt_map: too many cells");
@@ -3656,6 +3709,160 @@ mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const doubl
   }
   if (const mcl_status s = bind_device(ctx)) return s;
   return do_reweight(ctx, recs.data(), recs.size() / 2);
+}
+
+// ---- Landmark and bearing sensor models ----------------------------------------------------------------------------------------
+void mcl_default_landmark_params(mcl_landmark_params* params) {
+  if (!params) return;
+  *params = mcl_landmark_params{1.0, 1.0, 1e-4};  // LandmarkModelParam (landmark_sensor_model.hpp:44-48)
+}
+
+void mcl_default_bearing_params(mcl_bearing_params* params) {
+  if (!params) return;
+  *params = mcl_bearing_params{1.0, {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0}};  // BearingModelParam (bearing_sensor_model.hpp:42-45)
+}
+
+mcl_status mcl_set_landmark_map(mcl_ctx* ctx, const double* positions_xyz, const uint32_t* categories, uint64_t n, const double boundaries[6],
+                                const void* params) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_landmark_map: the context's sensor model is not MCL_SENSOR_LANDMARK or MCL_SENSOR_BEARING");
+  MCL_REQUIRE(ctx, n == 0 || (positions_xyz && categories), "mcl_set_landmark_map: null argument");
+  MCL_REQUIRE(ctx, n < (1ull << 31), "mcl_set_landmark_map: too many landmarks");
+  MCL_REQUIRE(ctx, n > 0 || boundaries, "mcl_set_landmark_map: an empty map needs explicit boundaries");
+  for (uint64_t i = 0; i < 3 * n; ++i)
+    MCL_REQUIRE(ctx, std::isfinite(positions_xyz[i]), "mcl_set_landmark_map: landmark " + std::to_string(i / 3) + " has a value that is not finite");
+  LandmarkMapView v{};
+  if (ctx->cfg.sensor_kind == MCL_SENSOR_LANDMARK) {
+    mcl_landmark_params prm;
+    if (params) prm = *static_cast<const mcl_landmark_params*>(params);
+    else mcl_default_landmark_params(&prm);
+    MCL_REQUIRE(ctx, std::isfinite(prm.sigma_range) && prm.sigma_range > 0.0 && std::isfinite(prm.sigma_bearing) && prm.sigma_bearing > 0.0,
+                "mcl_set_landmark_map: sigma_range and sigma_bearing must be positive and finite");
+    MCL_REQUIRE(ctx, std::isfinite(prm.random_prob), "mcl_set_landmark_map: random_prob must be finite");
+    v.den_range = (2. * prm.sigma_range) * prm.sigma_range;  // landmark_sensor_model.hpp:147
+    v.den_bearing = (2. * prm.sigma_bearing) * prm.sigma_bearing;
+    v.random_prob = prm.random_prob;
+  } else {
+    mcl_bearing_params prm;
+    if (params) prm = *static_cast<const mcl_bearing_params*>(params);
+    else mcl_default_bearing_params(&prm);
+    MCL_REQUIRE(ctx, std::isfinite(prm.sigma_bearing) && prm.sigma_bearing > 0.0, "mcl_set_landmark_map: sigma_bearing must be positive and finite");
+    const double* q = prm.sensor_pose_in_robot;
+    for (int k = 0; k < 7; ++k) MCL_REQUIRE(ctx, std::isfinite(q[k]), "mcl_set_landmark_map: sensor_pose_in_robot must be finite");
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    MCL_REQUIRE(ctx, std::abs(std::sqrt(x * x + y * y + z * z + w * w) - 1.0) <= 1e-9, "mcl_set_landmark_map: sensor_pose_in_robot's quaternion is not of unit length");
+    v.den_bearing = (2. * prm.sigma_bearing) * prm.sigma_bearing;  // bearing_sensor_model.hpp:134
+    // Eigen's Quaternion::toRotationMatrix
+    const double tx = 2. * x, ty = 2. * y, tz = 2. * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    const double R[9] = {1. - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1. - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1. - (txx + tyy)};
+    std::copy(R, R + 9, v.Rs);
+    std::copy(q + 4, q + 7, v.ts);
+  }
+  double lo[3], hi[3];
+  if (boundaries) {
+    for (int k = 0; k < 6; ++k) MCL_REQUIRE(ctx, std::isfinite(boundaries[k]), "mcl_set_landmark_map: the boundaries must be finite");
+    std::copy(boundaries, boundaries + 3, lo);
+    std::copy(boundaries + 3, boundaries + 6, hi);
+    MCL_REQUIRE(ctx, lo[0] <= hi[0] && lo[1] <= hi[1], "mcl_set_landmark_map: boundaries with min > max");
+  } else {  // LandmarkMap(landmarks) (landmark_map.hpp:61-71): the landmarks' bounding box
+    for (int k = 0; k < 3; ++k) lo[k] = hi[k] = positions_xyz[k];
+    for (uint64_t i = 1; i < n; ++i)
+      for (int k = 0; k < 3; ++k) {
+        lo[k] = std::min(lo[k], positions_xyz[3 * i + k]);
+        hi[k] = std::max(hi[k], positions_xyz[3 * i + k]);
+      }
+  }
+  // grouped by category, the map's order kept inside a category (std::min_element returns the first of equal candidates)
+  std::vector<uint32_t> order(n);
+  for (uint64_t i = 0; i < n; ++i) order[i] = static_cast<uint32_t>(i);
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return categories[a] < categories[b]; });
+  std::vector<double> recs(static_cast<size_t>(n) * 4, 0.0);
+  std::map<uint32_t, std::pair<uint32_t, uint32_t>> ranges;
+  for (uint64_t i = 0; i < n; ++i) {
+    std::copy(positions_xyz + 3 * order[i], positions_xyz + 3 * order[i] + 3, recs.begin() + static_cast<ptrdiff_t>(4 * i));
+    auto it = ranges.find(categories[order[i]]);
+    if (it == ranges.end()) ranges[categories[order[i]]] = {static_cast<uint32_t>(i), 1u};
+    else it->second.second += 1;
+  }
+  if (const mcl_status s = bind_device(ctx)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a reweight in flight may still read the old map)
+  ctx->have_landmark_map = false;
+  if (n) {
+    MCL_HIP(ctx, ctx->d_landmarks.ensure(recs.size()));
+    MCL_HIP(ctx, hipMemcpy(ctx->d_landmarks.ptr, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  v.landmarks = ctx->d_landmarks.ptr;
+  v.count = static_cast<uint32_t>(n);
+  ctx->landmark_view = v;
+  ctx->landmark_ranges = std::move(ranges);
+  FreeCells box{nullptr, 1};
+  box.box = 1;
+  box.box_min[0] = lo[0];
+  box.box_min[1] = lo[1];
+  box.box_extent[0] = hi[0] - lo[0];
+  box.box_extent[1] = hi[1] - lo[1];
+  ctx->landmark_random = box;
+  ctx->have_landmark_map = true;
+  return MCL_OK;
+}
+
+// The detection records of a call (kernels.h, kLandmarkRecord): what does not depend on the particle - the norm, the normalized vector and
+// the category's range - is computed here, once.  The bearing model's detections are sorted by category (stable), each with its place in
+// the caller's order.  Everything is checked before the device is touched.
+static mcl_status landmark_records(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n) {
+  if (ctx->cfg.sensor_kind != kind)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the context's sensor model is not " + (kind == MCL_SENSOR_LANDMARK ? "MCL_SENSOR_LANDMARK" : "MCL_SENSOR_BEARING"));
+  MCL_REQUIRE(ctx, n == 0 || (xyz && categories), std::string(who) + ": null argument");
+  MCL_REQUIRE(ctx, n <= MCL_LANDMARK_MAX_DETECTIONS, std::string(who) + ": more than MCL_LANDMARK_MAX_DETECTIONS detections");
+  for (uint64_t i = 0; i < 3 * n; ++i) MCL_REQUIRE(ctx, std::isfinite(xyz[i]), std::string(who) + ": a detection has a value that is not finite");
+  if (!ctx->have_landmark_map) return fail(ctx, MCL_ERR_NOT_READY, std::string(who) + ": no landmark map set (mcl_set_landmark_map)");
+  std::vector<uint32_t> order(n);
+  for (uint64_t i = 0; i < n; ++i) order[i] = static_cast<uint32_t>(i);
+  if (kind == MCL_SENSOR_BEARING) std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return categories[a] < categories[b]; });
+  std::vector<double>& recs = ctx->h_landmark_meas;
+  recs.assign(static_cast<size_t>(n) * kLandmarkRecord, 0.0);
+  for (uint64_t i = 0; i < n; ++i) {
+    const double* d = xyz + 3 * order[i];
+    double* r = recs.data() + i * kLandmarkRecord;
+    const double n2 = d[0] * d[0] + (d[1] * d[1] + d[2] * d[2]);
+    const double norm = std::sqrt(n2);
+    r[0] = d[0], r[1] = d[1], r[2] = d[2], r[3] = norm;
+    for (int k = 0; k < 3; ++k) r[4 + k] = n2 > 0.0 ? d[k] / norm : d[k];  // Eigen's normalized()
+    const auto it = ctx->landmark_ranges.find(categories[order[i]]);
+    const uint32_t packed[4] = {it == ctx->landmark_ranges.end() ? 0xFFFFFFFFu : it->second.first,
+                                it == ctx->landmark_ranges.end() ? 0u : it->second.second, order[i], 0u};
+    std::memcpy(r + 7, packed, sizeof(packed));
+  }
+  return MCL_OK;
+}
+
+static mcl_status landmark_reweight(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (const mcl_status s = landmark_records(ctx, who, kind, xyz, categories, n)) return s;
+  if (const mcl_status s = bind_device(ctx)) return s;
+  return do_reweight(ctx, ctx->h_landmark_meas.data(), ctx->h_landmark_meas.size() / 2);
+}
+static mcl_status landmark_update(mcl_ctx* ctx, const char* who, int32_t kind, const double control_pose[4], const double* xyz,
+                                  const uint32_t* categories, uint64_t n, mcl_estimate* estimate, mcl_update_info* info) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (const mcl_status s = landmark_records(ctx, who, kind, xyz, categories, n)) return s;
+  return update_cycle(ctx, control_pose, ctx->h_landmark_meas.data(), ctx->h_landmark_meas.size() / 2, estimate, info);
+}
+
+mcl_status mcl_reweight_landmarks(mcl_ctx* ctx, const double* positions_xyz, const uint32_t* categories, uint64_t n) {
+  return landmark_reweight(ctx, "mcl_reweight_landmarks", MCL_SENSOR_LANDMARK, positions_xyz, categories, n);
+}
+mcl_status mcl_reweight_bearings(mcl_ctx* ctx, const double* bearings_xyz, const uint32_t* categories, uint64_t n) {
+  return landmark_reweight(ctx, "mcl_reweight_bearings", MCL_SENSOR_BEARING, bearings_xyz, categories, n);
+}
+mcl_status mcl_update_landmarks(mcl_ctx* ctx, const double control_pose[4], const double* positions_xyz, const uint32_t* categories, uint64_t n,
+                                mcl_estimate* estimate, mcl_update_info* info) {
+  return landmark_update(ctx, "mcl_update_landmarks", MCL_SENSOR_LANDMARK, control_pose, positions_xyz, categories, n, estimate, info);
+}
+mcl_status mcl_update_bearings(mcl_ctx* ctx, const double control_pose[4], const double* bearings_xyz, const uint32_t* categories, uint64_t n,
+                               mcl_estimate* estimate, mcl_update_info* info) {
+  return landmark_update(ctx, "mcl_update_bearings", MCL_SENSOR_BEARING, control_pose, bearings_xyz, categories, n, estimate, info);
 }
 
 mcl_status mcl_sync(mcl_ctx* ctx) {

@@ -96,13 +96,18 @@ struct DiffDriveSampler {
 // Where random_intersperse's random states come from (random_free_state, kernels.hip).  Likelihood-field and beam models: uniformly
 // over the free cells of the occupancy grid (multivariate_uniform_distribution.hpp:126-161).  NDT model (normal != 0): N(mean, T T^T)
 // as mean + T z (ndt_amcl_node.cpp:248-254; multivariate_normal_distribution.hpp:109-126), count = 1 so that the Bernoulli stream
-// selects the same slots; the host fills mean / T from the estimate of the normalised set just before the draw.
+// selects the same slots; the host fills mean / T from the estimate of the normalised set just before the draw.  Landmark and bearing
+// models (box != 0): uniformly over the x-y extent of LandmarkMap::map_limits() with a uniform heading
+// (MultivariateUniformDistribution<SE2d, AlignedBox2d>, multivariate_uniform_distribution.hpp:77-113), count = 1 as well.
 struct FreeCells {
   const uint32_t* index;  // linear indices of free cells
   uint64_t count;
   int normal{0};
   double mean[3]{0.0, 0.0, 0.0};  // x, y, theta
   double T[9]{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // row-major
+  int box{0};
+  double box_min[2]{0.0, 0.0};     // x, y
+  double box_extent[2]{0.0, 0.0};  // max - min
 };
 
 // The NDT model's map (ndt_kernels.hip): a dense int32 index grid over the bounding box of the map's keys with a border of 2 * reach
@@ -126,6 +131,31 @@ struct NdtMapView {
 // NDTSensorModel::operator() (ndt_sensor_model.hpp:216-239): w[i] *= 1 + sum over the k measurement cells (kNdtRecord doubles each,
 // base frame) of max(sum of the present neighbours' d1 exp(-d2/2 e^T (S' + S_map)^-1 e), minimum_likelihood).  A lane per particle.
 void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k);
+
+// The landmark and bearing models' map and measurement (landmark_kernels.hip).  The landmarks are grouped by category on the host with
+// a stable sort (map order inside a category: std::min_element's "first of equal" holds), 4 doubles each (x, y, z, 0).  A detection is
+// kLandmarkRecord doubles: the vector as given (x, y, z), its norm, its normalized() (x, y, z), then three uint32 in the place of
+// doubles 7 and 8: first and count of its category's landmarks (count 0 = no landmark of that category, first = 0xFFFFFFFF) and the
+// detection's place in the caller's order.
+constexpr int kLandmarkRecord = 10;
+constexpr int kLandmarkMaxDetections = 64;  // MCL_LANDMARK_MAX_DETECTIONS
+struct LandmarkMapView {
+  const double* landmarks;  // 4 doubles per landmark, grouped by category
+  uint32_t count;
+  double den_range, den_bearing;  // (2. * sigma) * sigma
+  double random_prob;
+  double Rs[9];  // bearing model: sensor_pose_in_robot's rotation (row-major, Eigen's toRotationMatrix) and translation
+  double ts[3];
+};
+// LandmarkSensorModel2d::operator() (landmark_sensor_model.hpp:92-157): w[i] *= product over the k detections of
+// exp(-range_error^2 / den_range) exp(-bearing_error^2 / den_bearing) + random_prob against the nearest landmark of the detection's
+// category (random_prob alone where there is none).  A lane per particle; detections in the caller's order.
+void launch_reweight_landmarks(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k);
+// BearingSensorModel2d::operator() (bearing_sensor_model.hpp:89-141): w[i] *= product over the k detections of exp(-e^2 / den_bearing), e
+// the aperture between the detection and the bearing of the landmark of its category whose bearing is closest (0 where there is
+// none).  `detections` are sorted by category (their record says where they stand in the caller's order, which the product follows):
+// a landmark's bearing in the sensor frame is computed once per particle and serves every detection of its category.
+void launch_reweight_bearings(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k);
 
 struct HashParams {
   double res_x, res_y, res_theta;

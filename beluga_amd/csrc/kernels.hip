@@ -2820,6 +2820,12 @@ __device__ __forceinline__ Pose2 random_free_state(uint64_t seed, uint32_t step,
     return Pose2{rot_exp(vt), vx, vy};
   }
   const RngWords q = rng_draw(seed, step, kRngRandomState, j);
+  if (fc.box) {  // landmark / bearing models: uniform over the map's x-y box (multivariate_uniform_distribution.hpp:77-113)
+    const RngWords qy = rng_draw(seed, step, kRngRandomBoxY, j);
+    const double vx = fc.box_min[0] + fc.box_extent[0] * rng_uniform53(q.w[0], q.w[1]);
+    const double vy = fc.box_min[1] + fc.box_extent[1] * rng_uniform53(qy.w[0], qy.w[1]);
+    return Pose2{rot_exp(-kPi + 2.0 * kPi * rng_uniform53(q.w[2], q.w[3])), vx, vy};
+  }
   uint64_t cell = static_cast<uint64_t>(rng_uniform53(q.w[0], q.w[1]) * static_cast<double>(fc.count));
   if (cell >= fc.count) cell = fc.count - 1;
   const double theta = -kPi + 2.0 * kPi * rng_uniform53(q.w[2], q.w[3]);

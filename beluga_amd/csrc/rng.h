@@ -21,6 +21,7 @@ enum RngPurpose : uint32_t {
   kRngInitB = 5,
   kRngRandomNormalA = 6,  // NDT model's random states N(estimate): words 0..3 -> (z0, z1)
   kRngRandomNormalB = 7,  //                                         words 0..3 -> (z2, -)
+  kRngRandomBoxY = 8,     // landmark / bearing models' random states over the map's box: words 0,1 -> y (x and the heading: kRngRandomState)
 };
 
 struct RngWords {

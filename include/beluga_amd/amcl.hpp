@@ -149,6 +149,63 @@ struct NDTCell2d {
   std::array<double, 4> covariance{};
 };
 
+/// beluga::LandmarkModelParam (sensor/landmark_sensor_model.hpp:44-48).
+struct LandmarkModelParam {
+  double sigma_range = 1.0;
+  double sigma_bearing = 1.0;
+  double random_prob = 1e-4;
+};
+/// beluga::BearingModelParam (sensor/bearing_sensor_model.hpp:42-45); the pose in Sophus::SE3d::data() order: quaternion x, y, z, w,
+/// translation x, y, z.
+struct BearingModelParam {
+  double sigma_bearing = 1.0;
+  std::array<double, 7> sensor_pose_in_robot{0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
+};
+/// types/landmark_detection_types.hpp:32-48, with plain arrays in the place of Eigen's vectors.
+using LandmarkCategory = std::uint32_t;
+using LandmarkPosition3 = std::array<double, 3>;
+using LandmarkBearing3 = std::array<double, 3>;
+struct LandmarkPositionDetection {
+  LandmarkPosition3 detection_position_in_robot;
+  LandmarkCategory category;
+};
+struct LandmarkBearingDetection {
+  LandmarkBearing3 detection_bearing_in_sensor;
+  LandmarkCategory category;
+};
+/// Eigen::AlignedBox3d's two corners.
+struct LandmarkMapBoundaries {
+  std::array<double, 3> min_corner{0.0, 0.0, 0.0}, max_corner{0.0, 0.0, 0.0};
+  [[nodiscard]] const std::array<double, 3>& min() const { return min_corner; }
+  [[nodiscard]] const std::array<double, 3>& max() const { return max_corner; }
+};
+/// beluga::LandmarkMap (sensor/data/landmark_map.hpp:40-75): both constructors and map_limits().  Built from the landmarks alone, its
+/// limits are their bounding box; an empty map built that way has no limits and is refused by the filter.
+class LandmarkMap {
+ public:
+  using landmarks_set_position_data = std::vector<LandmarkPositionDetection>;
+  LandmarkMap(const LandmarkMapBoundaries& boundaries, landmarks_set_position_data landmarks)
+      : landmarks_(std::move(landmarks)), boundaries_(boundaries), has_boundaries_(true) {}
+  explicit LandmarkMap(landmarks_set_position_data landmarks) : landmarks_(std::move(landmarks)) {
+    if (landmarks_.empty()) return;
+    has_boundaries_ = true;
+    boundaries_.min_corner = boundaries_.max_corner = landmarks_[0].detection_position_in_robot;
+    for (const auto& l : landmarks_)
+      for (std::size_t k = 0; k < 3; ++k) {
+        boundaries_.min_corner[k] = std::min(boundaries_.min_corner[k], l.detection_position_in_robot[k]);
+        boundaries_.max_corner[k] = std::max(boundaries_.max_corner[k], l.detection_position_in_robot[k]);
+      }
+  }
+  [[nodiscard]] LandmarkMapBoundaries map_limits() const { return boundaries_; }
+  [[nodiscard]] bool has_limits() const { return has_boundaries_; }
+  [[nodiscard]] const landmarks_set_position_data& landmarks() const { return landmarks_; }
+
+ private:
+  landmarks_set_position_data landmarks_;
+  LandmarkMapBoundaries boundaries_{};
+  bool has_boundaries_{false};
+};
+
 /// The NDT sensor model's map with the accessors of beluga::SparseValueGrid2 (sensor/data/sparse_value_grid.hpp) that code written
 /// against it reads: resolution(), size(), data_at(key) (std::nullopt where no cell is present), cell_near(point).  The cells are
 /// kept in the load_from_hdf5 layout, which is what the device map is built from.
@@ -352,10 +409,57 @@ class Amcl {
       throw;
     }
   }
+  /// beluga::Amcl with LandmarkSensorModel2d<LandmarkMap> / BearingSensorModel2d<LandmarkMap> (the reference has no node for them).
+  Amcl(const LandmarkMap& map, const MotionModelParam& motion, const LandmarkModelParam& sensor, const AmclParams& params = AmclParams{},
+       std::uint64_t seed = 0, int device = 0, const std::vector<std::pair<std::string, std::int64_t>>& options = {})
+      : landmark_params_(sensor) {
+    create_landmark(MCL_SENSOR_LANDMARK, map, motion, params, seed, device, options);
+  }
+  Amcl(const LandmarkMap& map, const MotionModelParam& motion, const BearingModelParam& sensor, const AmclParams& params = AmclParams{},
+       std::uint64_t seed = 0, int device = 0, const std::vector<std::pair<std::string, std::int64_t>>& options = {})
+      : bearing_params_(sensor) {
+    create_landmark(MCL_SENSOR_BEARING, map, motion, params, seed, device, options);
+  }
 
  private:
-  static mcl_config make_config(const MotionModelParam& motion, const SensorModelParam& sensor, const AmclParams& params, std::uint64_t seed,
-                                int device, const Shard& shard) {
+  void create_landmark(int kind, const LandmarkMap& map, const MotionModelParam& motion, const AmclParams& params, std::uint64_t seed, int device,
+                       const std::vector<std::pair<std::string, std::int64_t>>& options) {
+    mcl_config cfg = base_config(motion, params, seed, device, Shard{});
+    cfg.sensor_kind = kind;  // (its parameters travel with the map: mcl_set_landmark_map)
+    landmark_kind_ = kind;
+    create(cfg, params, options);
+    try {
+      update_map(map);
+    } catch (...) {
+      mcl_destroy(ctx_);
+      ctx_ = nullptr;
+      throw;
+    }
+  }
+  template <class Detection, class Get>
+  static void flatten(const std::vector<Detection>& detections, Get get, std::vector<double>& xyz, std::vector<std::uint32_t>& categories) {
+    xyz.clear();
+    categories.clear();
+    for (const auto& d : detections) {
+      const std::array<double, 3>& v = get(d);
+      xyz.insert(xyz.end(), v.begin(), v.end());
+      categories.push_back(d.category);
+    }
+  }
+  auto finish_update(const mcl_estimate& est, const mcl_update_info& info) -> std::optional<std::pair<SE2d, Matrix3d>> {
+    last_info_ = info;
+    if (!info.updated) return std::nullopt;
+    dirty_ = true;
+    std::pair<SE2d, Matrix3d> out;
+    out.first.c = est.pose[0];
+    out.first.s = est.pose[1];
+    out.first.x = est.pose[2];
+    out.first.y = est.pose[3];
+    for (int i = 0; i < 9; ++i) out.second[static_cast<std::size_t>(i)] = est.covariance[i];
+    return out;
+  }
+  /// Everything of the configuration but the sensor model.
+  static mcl_config base_config(const MotionModelParam& motion, const AmclParams& params, std::uint64_t seed, int device, const Shard& shard) {
     mcl_config cfg;
     mcl_default_config(&cfg);
     cfg.device_id = device;
@@ -389,6 +493,11 @@ class Amcl {
     } else {
       cfg.motion_kind = MCL_MOTION_STATIONARY;
     }
+    return cfg;
+  }
+  static mcl_config make_config(const MotionModelParam& motion, const SensorModelParam& sensor, const AmclParams& params, std::uint64_t seed,
+                                int device, const Shard& shard) {
+    mcl_config cfg = base_config(motion, params, seed, device, shard);
     const LikelihoodFieldModelParam* lf = std::get_if<LikelihoodFieldModelParam>(&sensor);
     if (!lf) lf = std::get_if<LikelihoodFieldProbModelParam>(&sensor);
     if (lf) {
@@ -427,7 +536,10 @@ class Amcl {
         max_particles_(other.max_particles_),
         resolution_(other.resolution_),
         has_field_(other.has_field_),
-        ndt_params_(std::move(other.ndt_params_)) {
+        ndt_params_(std::move(other.ndt_params_)),
+        landmark_params_(other.landmark_params_),
+        bearing_params_(other.bearing_params_),
+        landmark_kind_(other.landmark_kind_) {
     other.ctx_ = nullptr;
   }
   ~Amcl() { mcl_destroy(ctx_); }
@@ -462,6 +574,43 @@ class Amcl {
     dirty_ = true;
   }
 
+  /// Update the landmark map (LandmarkSensorModel::update_map, BearingSensorModel::update_map).
+  void update_map(const LandmarkMap& map) {
+    std::vector<double> xyz;
+    std::vector<std::uint32_t> categories;
+    flatten(map.landmarks(), [](const LandmarkPositionDetection& d) -> const std::array<double, 3>& { return d.detection_position_in_robot; }, xyz,
+            categories);
+    const LandmarkMapBoundaries limits = map.map_limits();
+    const double box[6] = {limits.min_corner[0], limits.min_corner[1], limits.min_corner[2],
+                           limits.max_corner[0], limits.max_corner[1], limits.max_corner[2]};
+    const mcl_landmark_params lp{landmark_params_.sigma_range, landmark_params_.sigma_bearing, landmark_params_.random_prob};
+    mcl_bearing_params bp{bearing_params_.sigma_bearing, {}};
+    for (std::size_t k = 0; k < 7; ++k) bp.sensor_pose_in_robot[k] = bearing_params_.sensor_pose_in_robot[k];
+    const void* prm = landmark_kind_ == MCL_SENSOR_BEARING ? static_cast<const void*>(&bp) : static_cast<const void*>(&lp);
+    check(mcl_set_landmark_map(ctx_, xyz.data(), categories.data(), categories.size(), map.has_limits() ? box : nullptr, prm));
+  }
+  /// update(control_action, std::vector<LandmarkPositionDetection>): the landmark sensor model's measurement.
+  auto update(const SE2d& control_action, const std::vector<LandmarkPositionDetection>& detections) -> std::optional<estimation_type> {
+    std::vector<double> xyz;
+    std::vector<std::uint32_t> categories;
+    flatten(detections, [](const LandmarkPositionDetection& d) -> const std::array<double, 3>& { return d.detection_position_in_robot; }, xyz,
+            categories);
+    mcl_estimate est;
+    mcl_update_info info;
+    check(mcl_update_landmarks(ctx_, control_action.data(), xyz.data(), categories.data(), categories.size(), &est, &info));
+    return finish_update(est, info);
+  }
+  /// update(control_action, std::vector<LandmarkBearingDetection>): the bearing sensor model's measurement.
+  auto update(const SE2d& control_action, const std::vector<LandmarkBearingDetection>& detections) -> std::optional<estimation_type> {
+    std::vector<double> xyz;
+    std::vector<std::uint32_t> categories;
+    flatten(detections, [](const LandmarkBearingDetection& d) -> const std::array<double, 3>& { return d.detection_bearing_in_sensor; }, xyz,
+            categories);
+    mcl_estimate est;
+    mcl_update_info info;
+    check(mcl_update_bearings(ctx_, control_action.data(), xyz.data(), categories.data(), categories.size(), &est, &info));
+    return finish_update(est, info);
+  }
   /// Update the NDT map used for localization (amcl_core.hpp:150 on the NDT filter).
   void update_map(const NDTMap2d& map) {
     if (ndt_params_.neighbors_kernel.empty() || ndt_params_.neighbors_kernel.size() > MCL_NDT_MAX_OFFSETS) throw std::invalid_argument("beluga_amd::Amcl: the neighbours kernel takes 1 .. 32 offsets");
@@ -690,6 +839,9 @@ class Amcl {
   double resolution_{0.0};
   bool has_field_{false};
   NDTModelParam2d ndt_params_{};
+  LandmarkModelParam landmark_params_{};
+  BearingModelParam bearing_params_{};
+  int landmark_kind_{0};
   mutable ParticleSet mirror_;
   mutable bool dirty_{true};
   mutable std::optional<ValueGrid2<float>> field_;

@@ -47,8 +47,18 @@ enum {
 /* LikelihoodFieldModel (sensor/likelihood_field_model.hpp), BeamSensorModel (sensor/beam_model.hpp),
  * LikelihoodFieldProbModel (sensor/likelihood_field_prob_model.hpp): beluga_ros::Amcl's sensor variants.
  * NDTSensorModel over a SparseValueGrid2 of NDTCell2d (sensor/ndt_sensor_model.hpp): the filter of beluga_amcl's ndt_amcl_node
- * (its map comes from mcl_set_ndt_map, see "2D NDT sensor model" below). */
-enum { MCL_SENSOR_LIKELIHOOD_FIELD = 0, MCL_SENSOR_BEAM = 1, MCL_SENSOR_LIKELIHOOD_FIELD_PROB = 2, MCL_SENSOR_NDT = 3 };
+ * (its map comes from mcl_set_ndt_map, see "2D NDT sensor model" below).
+ * LandmarkSensorModel2d and BearingSensorModel2d over a LandmarkMap (sensor/landmark_sensor_model.hpp, sensor/bearing_sensor_model.hpp):
+ * their map comes from mcl_set_landmark_map, their measurement through mcl_update_landmarks / mcl_update_bearings (see "Landmark and
+ * bearing sensor models" below). */
+enum {
+  MCL_SENSOR_LIKELIHOOD_FIELD = 0,
+  MCL_SENSOR_BEAM = 1,
+  MCL_SENSOR_LIKELIHOOD_FIELD_PROB = 2,
+  MCL_SENSOR_NDT = 3,
+  MCL_SENSOR_LANDMARK = 4,
+  MCL_SENSOR_BEARING = 5
+};
 /* DifferentialDriveModel, OmnidirectionalDriveModel (motion/omnidirectional_drive_model.hpp:102-146),
  * StationaryModel (motion/stationary_model.hpp:55-61): beluga_ros::Amcl's motion variants. */
 enum { MCL_MOTION_DIFFERENTIAL = 0, MCL_MOTION_OMNIDIRECTIONAL = 1, MCL_MOTION_STATIONARY = 2 };
@@ -256,6 +266,59 @@ mcl_status mcl_ndt_measurement_cells(const double* points_xy, uint64_t num_point
 /* Stage-level reweight from measurement cells fitted by the caller (means[k*2], covs[k*4] 2 x 2 row-major, base frame): w *= 1 +
  * sum over the cells of likelihood_at(state * cell).  mcl_reweight on an NDT context fits the cells of its points first. */
 mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const double* covs, uint64_t num_cells);
+
+/* ---- Landmark and bearing sensor models (sensor/landmark_sensor_model.hpp, sensor/bearing_sensor_model.hpp) -------------------
+ * A context created with sensor_kind = MCL_SENSOR_LANDMARK or MCL_SENSOR_BEARING takes its map from mcl_set_landmark_map: a
+ * beluga::LandmarkMap (sensor/data/landmark_map.hpp), 3D landmark positions with a category each, plus the map's boundaries.  The
+ * measurement is a list of detections with a category each: positions in the robot frame (mcl_update_landmarks) or bearing vectors
+ * in the sensor frame (mcl_update_bearings).  A particle (cos, sin, x, y) stands for the pose Rz(theta), (x, y, 0).  Per particle:
+ *   landmark: w *= product over the detections of exp(-range_error^2 / (2 sigma_range^2)) exp(-bearing_error^2 / (2 sigma_bearing^2))
+ *             + random_prob against the landmark of the detection's category nearest to the detection moved into the world
+ *             (random_prob alone where the map has none of that category);
+ *   bearing:  w *= product over the detections of exp(-e^2 / (2 sigma_bearing^2)), e the angle between the detection and the bearing,
+ *             in the sensor frame, of the landmark of its category that maximises the dot product with the detection as given (0
+ *             where the map has none of that category: the weight becomes 0).
+ * Equal candidates resolve to the first in the map's order, as std::min_element does.  No detections leave the weights unchanged.
+ * The reference has no node for these models; the library draws their random states (random_intersperse) and
+ * mcl_initialize_from_map's states uniformly over the x-y extent of the map's boundaries with a uniform heading
+ * (MultivariateUniformDistribution<SE2d, AlignedBox2d>): global localisation.
+ * Not on these contexts (MCL_ERR_UNSUPPORTED): mcl_update, mcl_update_laser_scan, mcl_update_point_cloud, mcl_reweight, the entry
+ * points of the other of the two kinds, mcl_set_map[_async], mcl_set_ndt_map, mcl_get_likelihood_field[_origin],
+ * mcl_set_likelihood_field, comm attach and the sharded resampling steps; mcl_has_likelihood_field says 0.  The four entry points
+ * below return MCL_ERR_UNSUPPORTED on a context of any other sensor model.  Every argument is checked before the device is used. */
+/* Most detections one call takes (the bearing kernel keeps 12 bytes of LDS per detection and lane); more: MCL_ERR_INVALID_ARGUMENT. */
+#define MCL_LANDMARK_MAX_DETECTIONS 64
+/* beluga::LandmarkModelParam (landmark_sensor_model.hpp:44-48). */
+typedef struct mcl_landmark_params {
+  double sigma_range;   /* 1.0 */
+  double sigma_bearing; /* 1.0 */
+  double random_prob;   /* 1e-4 */
+} mcl_landmark_params;
+/* beluga::BearingModelParam (bearing_sensor_model.hpp:42-45). */
+typedef struct mcl_bearing_params {
+  double sigma_bearing;           /* 1.0 */
+  double sensor_pose_in_robot[7]; /* identity; Sophus::SE3d::data() order: quaternion x, y, z, w, translation x, y, z */
+} mcl_bearing_params;
+void mcl_default_landmark_params(mcl_landmark_params* params);
+void mcl_default_bearing_params(mcl_bearing_params* params);
+/* The LandmarkMap: n landmarks positions_xyz[n*3] with categories[n]; boundaries = min x, y, z, max x, y, z (LandmarkMapBoundaries),
+ * NULL = the landmarks' bounding box (the reference's second constructor).  params points at the struct of the context's kind
+ * (mcl_landmark_params or mcl_bearing_params), NULL = its defaults.  Replaces the map between updates (update_map).  n = 0 with
+ * explicit boundaries is a valid, empty map.  MCL_ERR_INVALID_ARGUMENT: n = 0 with NULL boundaries (the reference keeps Eigen's empty
+ * box there, from which nothing can be drawn), values that are not finite, min > max in x or y, a sigma that is not positive and
+ * finite, a quaternion that is not finite or not of unit length within 1e-9. */
+mcl_status mcl_set_landmark_map(mcl_ctx* ctx, const double* positions_xyz, const uint32_t* categories, uint64_t n,
+                                const double boundaries[6], const void* params);
+/* Amcl::update with a std::vector<LandmarkPositionDetection> / <LandmarkBearingDetection>: n detections vectors_xyz[n*3] with
+ * categories[n]; otherwise as mcl_update.  MCL_ERR_INVALID_ARGUMENT for more than MCL_LANDMARK_MAX_DETECTIONS detections or values
+ * that are not finite. */
+mcl_status mcl_update_landmarks(mcl_ctx* ctx, const double control_pose[4], const double* positions_xyz, const uint32_t* categories,
+                                uint64_t n, mcl_estimate* estimate, mcl_update_info* info);
+mcl_status mcl_update_bearings(mcl_ctx* ctx, const double control_pose[4], const double* bearings_xyz, const uint32_t* categories,
+                               uint64_t n, mcl_estimate* estimate, mcl_update_info* info);
+/* Stage-level reweight of the two models (what the two updates compose with the other stages below). */
+mcl_status mcl_reweight_landmarks(mcl_ctx* ctx, const double* positions_xyz, const uint32_t* categories, uint64_t n);
+mcl_status mcl_reweight_bearings(mcl_ctx* ctx, const double* bearings_xyz, const uint32_t* categories, uint64_t n);
 
 /* ---- Stage-level entry points (what update() composes; used by parity tests and by the
  * multi-GPU driver, which interleaves collectives between them). -------------------------------- */
