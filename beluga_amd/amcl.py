@@ -123,6 +123,35 @@ class NDTMap2d:
     covariances: np.ndarray
     resolution: float
 
+    @classmethod
+    def from_points(cls, points, resolution: float) -> "NDTMap2d":
+        """The map of a point cloud (world frame) by the rule of detail::to_cells (ndt_sensor_model.hpp:88-110), on the host: keys by
+        (p / resolution) truncated toward zero, cells of 5 points or more, in ascending (x, y) key order, fitted by the library's
+        mcl_ndt_measurement_cells.  No device needed; Amcl.build_ndt_map builds the same cells on the device."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        means, covs = ndt_measurement_cells(pts, resolution)
+        q = pts / float(resolution)
+        q = q[np.all(np.abs(q) < 2147483647.0, axis=1)]  # (the others have no key: the fit drops them too)
+        keys, counts = np.unique(q.astype(np.int32), axis=0, return_counts=True)  # rows in ascending (x, y) order
+        keys = keys[counts >= 5].reshape(-1, 2)
+        if len(keys) != len(means):
+            raise RuntimeError("NDTMap2d.from_points: the keys and the fitted cells differ in number")
+        return cls(cells=keys.astype(np.int32), means=means, covariances=covs, resolution=float(resolution))
+
+    @classmethod
+    def from_occupancy_grid(cls, grid: "OccupancyGrid", resolution: float) -> "NDTMap2d":
+        """The same from the centres of the grid's occupied cells (occupied_cell_centres)."""
+        return cls.from_points(occupied_cell_centres(grid), resolution)
+
+
+def occupied_cell_centres(grid: "OccupancyGrid") -> np.ndarray:
+    """The centres of a grid's occupied cells in the world frame, origin * (resolution * (index + 0.5)), in row-major order: the
+    points mcl_build_ndt_map_from_grid fits, with its arithmetic."""
+    yi, xi = np.nonzero(np.asarray(grid.cells) == grid.value_traits[2])
+    c, s, ox, oy = (float(v) for v in grid.origin)
+    lx, ly = (xi + 0.5) * float(grid.resolution), (yi + 0.5) * float(grid.resolution)
+    return np.stack([(c * lx - s * ly) + ox, (s * lx + c * ly) + oy], 1)
+
 
 @dataclass
 class LandmarkModelParam:
@@ -383,6 +412,7 @@ class Amcl:
             prm = ndt_params_struct(getattr(self, "_ndt_params", None) or NDTModelParam2d())
             self._check(self._lib.mcl_set_ndt_map(self._ctx, keys.ctypes.data_as(C.POINTER(C.c_int32)), _dp(means), _dp(covs), len(keys),
                                                   float(grid.resolution), C.byref(prm)))
+            self._ndt_resolution = float(grid.resolution)
             self._shape = None
             self._pending_shape = None
             return
@@ -394,6 +424,31 @@ class Amcl:
                                           traits))
         self._shape = (H, W)
         self._pending_shape = None  # (a map given now replaces one that was still on its way)
+
+    def build_ndt_map(self, source, resolution: float):
+        """Extension (mcl_build_ndt_map_from_points / _from_grid): the NDT map built on the device from a point cloud (points[n,2], world
+        frame) or from the occupied cells of an OccupancyGrid with the default value traits, and installed in place of the filter's map.
+        The cells are NDTMap2d.from_points' bit for bit; the sensor model's parameters stay.  Read the result with ndt_map()."""
+        if isinstance(source, OccupancyGrid):
+            if tuple(source.value_traits) != (0, -1, 100):
+                raise ValueError("build_ndt_map: the grid form takes the default value traits (occupied = 100)")
+            cells = np.ascontiguousarray(source.cells, dtype=np.int8)
+            H, W = cells.shape
+            origin = np.ascontiguousarray(source.origin, dtype=np.float64)
+            self._check(self._lib.mcl_build_ndt_map_from_grid(self._ctx, cells.ctypes.data_as(capi.c_i8_p), W, H, float(source.resolution),
+                                                              _dp(origin), float(resolution)))
+        else:
+            pts = np.ascontiguousarray(source, dtype=np.float64).reshape(-1, 2)
+            self._check(self._lib.mcl_build_ndt_map_from_points(self._ctx, _dp(pts), len(pts), float(resolution)))
+        self._ndt_resolution = float(resolution)
+
+    def ndt_map(self) -> NDTMap2d:
+        """The NDT map the filter holds, however it was set (mcl_get_ndt_map)."""
+        n = C.c_uint64(0)
+        self._check(self._lib.mcl_get_ndt_map(self._ctx, None, None, None, 0, C.byref(n)))
+        keys, means, covs = np.zeros((n.value, 2), dtype=np.int32), np.zeros((n.value, 2)), np.zeros((n.value, 2, 2))
+        self._check(self._lib.mcl_get_ndt_map(self._ctx, keys.ctypes.data_as(C.POINTER(C.c_int32)), _dp(means), _dp(covs), n.value, C.byref(n)))
+        return NDTMap2d(cells=keys, means=means, covariances=covs, resolution=self._ndt_resolution)
 
     def update_map_async(self, grid: OccupancyGrid):
         """Extension (mcl_set_map_async): the new map's likelihood field is built on a worker thread while the filter keeps running on

@@ -193,6 +193,9 @@ _SIGNATURES = {
     "mcl_set_ndt_map": (C.c_int32, [_ctx, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_uint64, C.c_double, C.POINTER(NdtParams)]),
     "mcl_ndt_measurement_cells": (C.c_int32, [c_double_p, C.c_uint64, C.c_double, c_double_p, c_double_p, c_u64_p]),
     "mcl_reweight_ndt_cells": (C.c_int32, [_ctx, c_double_p, c_double_p, C.c_uint64]),
+    "mcl_build_ndt_map_from_points": (C.c_int32, [_ctx, c_double_p, C.c_uint64, C.c_double]),
+    "mcl_build_ndt_map_from_grid": (C.c_int32, [_ctx, c_i8_p, C.c_uint32, C.c_uint32, C.c_double, c_double_p, C.c_double]),
+    "mcl_get_ndt_map": (C.c_int32, [_ctx, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_uint64, c_u64_p]),
     "mcl_default_landmark_params": (None, [C.POINTER(LandmarkParams)]),
     "mcl_default_bearing_params": (None, [C.POINTER(BearingParams)]),
     "mcl_set_landmark_map": (C.c_int32, [_ctx, c_double_p, c_u32_p, C.c_uint64, c_double_p, C.c_void_p]),

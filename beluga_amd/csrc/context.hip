@@ -403,6 +403,9 @@ struct mcl_ctx {
   bool have_ndt_map{false};
   DeviceBuffer<int32_t> d_ndt_grid;
   DeviceBuffer<double> d_ndt_cells;
+  DeviceBuffer<int32_t> d_ndt_keys;  // the cells' keys (x, y) in the records' order (mcl_get_ndt_map)
+  mcl_ndt_params ndt_params{};       // the model parameters of the last mcl_set_ndt_map (the device builds keep them)
+  bool have_ndt_params{false};
   NdtMapView ndt_view{};
   uint64_t ndt_map_cells{0};
   double ndt_resolution{0.0};
@@ -724,6 +727,122 @@ void ndt_fit_cells(const double* pts, uint64_t B, double resolution, std::vector
   }
 }
 void ndt_fit_scan(mcl_ctx* ctx, const double* pts, uint64_t B) { ndt_fit_cells(pts, B, ctx->ndt_resolution, ctx->h_ndt_meas); }
+
+// The index grid of an NDT map over the keys' box [x0, x1] x [y0, y1] (kernels.h NdtMapView): the box with a border of 2 * reach.
+struct NdtGridShape {
+  int32_t reach;
+  int64_t x0, y0, x1, y1;
+  int64_t grid_x0, grid_y0;  // key of the grid's cell (0, 0)
+  int64_t gw, gh;
+  bool fits;  // within 2^26 cells
+};
+int32_t ndt_reach(const mcl_ndt_params& prm) {  // the largest |component| of a kernel offset, at least 1
+  int32_t reach = 1;
+  for (uint32_t k = 0; k < 2 * prm.num_offsets; ++k) reach = std::max(reach, std::abs(prm.offsets[k]));
+  return reach;
+}
+NdtGridShape ndt_grid_shape(int32_t reach, int64_t x0, int64_t x1, int64_t y0, int64_t y1) {
+  NdtGridShape g{reach, x0, y0, x1, y1, x0 - 2 * reach, y0 - 2 * reach, (x1 - x0 + 1) + 4 * reach, (y1 - y0 + 1) + 4 * reach, false};
+  constexpr int64_t kMaxGridCells = int64_t{1} << 26;
+  g.fits = !(g.gw > kMaxGridCells || g.gh > kMaxGridCells || g.gw * g.gh > kMaxGridCells);
+  return g;
+}
+// The map in d_ndt_grid / d_ndt_cells / d_ndt_keys (n cells, complete) becomes the context's.
+void ndt_install_view(mcl_ctx* ctx, const NdtGridShape& g, const mcl_ndt_params& prm, uint64_t n, double resolution) {
+  NdtMapView v{};
+  v.grid = ctx->d_ndt_grid.ptr;
+  v.cells = ctx->d_ndt_cells.ptr;
+  v.gw = static_cast<uint32_t>(g.gw);
+  v.inv_resolution = 1. / resolution;
+  v.key_x0 = static_cast<double>(g.x0 - g.reach);
+  v.key_y0 = static_cast<double>(g.y0 - g.reach);
+  v.box_w = static_cast<double>(g.x1 - g.x0 + 1 + 2 * g.reach);
+  v.box_h = static_cast<double>(g.y1 - g.y0 + 1 + 2 * g.reach);
+  v.reach = g.reach;
+  v.d1 = prm.d1;
+  v.d2 = prm.d2;
+  v.minimum_likelihood = prm.minimum_likelihood;
+  v.num_offsets = prm.num_offsets;
+  for (uint32_t k = 0; k < prm.num_offsets; ++k) v.delta[k] = prm.offsets[2 * k + 1] * static_cast<int32_t>(g.gw) + prm.offsets[2 * k];
+  ctx->ndt_view = v;
+  ctx->ndt_map_cells = n;
+  ctx->ndt_resolution = resolution;
+  ctx->have_ndt_map = true;
+}
+
+template <class T>
+struct ScopedBuffer : DeviceBuffer<T> {  // scratch of one call
+  ScopedBuffer() = default;
+  ScopedBuffer(const ScopedBuffer&) = delete;
+  ScopedBuffer& operator=(const ScopedBuffer&) = delete;
+  ~ScopedBuffer() { this->release(); }
+};
+uint32_t bits_of(uint64_t span) {  // bits that hold 0 .. span
+  uint32_t b = 0;
+  while (span >> b) ++b;
+  return b;
+}
+
+// detail::to_cells over n points in device memory, as ndt_fit_cells - same keys, same cells in the same order, the same bits (a cell's
+// sums in input order) - and the result installed as the context's map, laid out as mcl_set_ndt_map lays it out, without a visit to the
+// host (ndt_build_kernels.hip).  The model parameters are those of the last mcl_set_ndt_map, the defaults if there was none.  Nothing of
+// the context changes before every check has passed.
+mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, const double* d_pts, uint64_t n64, double resolution) {
+  const uint32_t n = static_cast<uint32_t>(n64);
+  hipStream_t st = ctx->stream;
+  mcl_ndt_params prm;
+  if (ctx->have_ndt_params) prm = ctx->ndt_params;
+  else mcl_default_ndt_params(&prm);
+  ScopedBuffer<int32_t> d_box;
+  MCL_HIP(ctx, d_box.ensure(5));
+  int32_t box[5] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN, 0};
+  MCL_HIP(ctx, hipMemcpy(d_box.ptr, box, sizeof(box), hipMemcpyHostToDevice));
+  launch_ndt_key_box(st, d_pts, n, resolution, d_box.ptr);
+  MCL_HIP(ctx, hipStreamSynchronize(st));
+  MCL_HIP(ctx, hipMemcpy(box, d_box.ptr, sizeof(box), hipMemcpyDeviceToHost));
+  MCL_REQUIRE(ctx, box[4] == 0, who + ": a point is not finite, or its key (p / resolution) does not fit an int32");
+  const uint32_t bits_x = bits_of(static_cast<uint64_t>(static_cast<int64_t>(box[1]) - box[0]));
+  const uint32_t bits_y = bits_of(static_cast<uint64_t>(static_cast<int64_t>(box[3]) - box[2]));
+  ScopedBuffer<unsigned long long> d_words;
+  ScopedBuffer<uint32_t> d_u32;
+  const size_t table = ndt_radix_table_words(n), chunks = num_chunks(std::max<size_t>(n, table)), starts = n / 5 + 1;
+  MCL_HIP(ctx, d_words.ensure(static_cast<size_t>(2) * n));
+  MCL_HIP(ctx, d_u32.ensure(static_cast<size_t>(3) * n + table + chunks + starts + kNdtCounters));
+  NdtBuildScratch sc{};
+  sc.words[0] = d_words.ptr;
+  sc.words[1] = d_words.ptr + n;
+  sc.idx[0] = d_u32.ptr;
+  sc.idx[1] = sc.idx[0] + n;
+  sc.flags = sc.idx[1] + n;
+  sc.table = sc.flags + n;
+  sc.chunk_tmp = sc.table + table;
+  sc.starts = sc.chunk_tmp + chunks;
+  sc.counters = sc.starts + starts;
+  uint32_t counters[kNdtCounters] = {0u, UINT32_MAX, 0u, UINT32_MAX, 0u, 0u};
+  MCL_HIP(ctx, hipMemcpy(sc.counters, counters, sizeof(counters), hipMemcpyHostToDevice));
+  const int sorted = launch_ndt_group_points(st, d_pts, n, resolution, box[0], box[2], bits_x, bits_y, sc);
+  MCL_HIP(ctx, hipStreamSynchronize(st));
+  MCL_HIP(ctx, hipMemcpy(counters, sc.counters, sizeof(counters), hipMemcpyDeviceToHost));
+  const uint32_t cells = counters[kNdtCountCells];
+  MCL_REQUIRE(ctx, cells > 0, who + ": no cell holds 5 points or more at this resolution (the map is kept as it was)");
+  const uint32_t* kb = counters + kNdtCountKeptBox;
+  const NdtGridShape g = ndt_grid_shape(ndt_reach(prm), int64_t{box[0]} + kb[0], int64_t{box[0]} + kb[1], int64_t{box[2]} + kb[2], int64_t{box[2]} + kb[3]);
+  if (!g.fits)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, who + ": the bounding box of the keys exceeds 2^26 cells (" + std::to_string(g.gw) + " x " +
+                                              std::to_string(g.gh) + " with its border)");
+  ctx->have_ndt_map = false;  // (until the new map is complete: ensure() may free the buffers the old view points at; the stream is idle)
+  const size_t grid_cells = static_cast<size_t>(g.gw * g.gh);
+  MCL_HIP(ctx, ctx->d_ndt_grid.ensure(grid_cells));
+  MCL_HIP(ctx, ctx->d_ndt_cells.ensure(static_cast<size_t>(cells) * kNdtRecord));
+  MCL_HIP(ctx, ctx->d_ndt_keys.ensure(static_cast<size_t>(2) * cells));
+  MCL_HIP(ctx, hipMemsetAsync(ctx->d_ndt_grid.ptr, 0xFF, grid_cells * sizeof(int32_t), st));  // -1: no cell
+  const NdtBuildLayout lay{box[0], box[2], g.grid_x0, g.grid_y0, g.gw};
+  launch_ndt_fit_cells(st, d_pts, n, sc, sorted, cells, lay, ctx->d_ndt_cells.ptr, ctx->d_ndt_keys.ptr, ctx->d_ndt_grid.ptr);
+  MCL_HIP(ctx, hipStreamSynchronize(st));
+  MCL_HIP(ctx, hipGetLastError());
+  ndt_install_view(ctx, g, prm, cells, resolution);
+  return MCL_OK;
+}
 
 // Stages the scan in mapped pinned memory; a kernel of the cycle pulls it into d_points (pull_scan_args / launch_pull_scan).
 mcl_status stage_points(mcl_ctx* ctx, const double* pts, uint64_t B) {
@@ -2396,6 +2515,7 @@ void mcl_destroy(mcl_ctx* ctx) {
   ctx->d_sort_f64.release();
   ctx->d_ndt_grid.release();
   ctx->d_ndt_cells.release();
+  ctx->d_ndt_keys.release();
   ctx->d_ndt_est.release();
   ctx->d_landmarks.release();
   if (ctx->rccl_comm) {
@@ -3627,16 +3747,15 @@ mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* mea
     MCL_REQUIRE(ctx, std::abs(c[1] - c[2]) <= 1e-12 * std::max(std::abs(c[1]), std::abs(c[2])),
                 "mcl_set_ndt_map: the covariance of cell " + std::to_string(i) + " is not symmetric");
   }
-  // index grid: the keys' box with a border of 2 * reach (kernels.h NdtMapView)
-  const int64_t gw = (x1 - x0 + 1) + 4 * reach, gh = (y1 - y0 + 1) + 4 * reach;
-  constexpr int64_t kMaxGridCells = int64_t{1} << 26;
-  if (gw > kMaxGridCells || gh > kMaxGridCells || gw * gh > kMaxGridCells)
-    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_map: the bounding box of the keys exceeds 2^26 cells (" + std::to_string(gw) + " x " +
-                                              std::to_string(gh) + " with its border)");
+  const NdtGridShape g = ndt_grid_shape(reach, x0, x1, y0, y1);
+  if (!g.fits)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_map: the bounding box of the keys exceeds 2^26 cells (" + std::to_string(g.gw) + " x " +
+                                              std::to_string(g.gh) + " with its border)");
+  const int64_t gw = g.gw, gh = g.gh;
   std::vector<int32_t> grid(static_cast<size_t>(gw * gh), -1);
   std::vector<double> recs(static_cast<size_t>(n) * kNdtRecord);
   for (uint64_t i = 0; i < n; ++i) {
-    const size_t at = static_cast<size_t>((cells[2 * i + 1] - y0 + 2 * reach) * gw + (cells[2 * i] - x0 + 2 * reach));
+    const size_t at = static_cast<size_t>((cells[2 * i + 1] - g.grid_y0) * gw + (cells[2 * i] - g.grid_x0));
     MCL_REQUIRE(ctx, grid[at] < 0, "mcl_set_ndt_map: duplicate key (" + std::to_string(cells[2 * i]) + ", " + std::to_string(cells[2 * i + 1]) + ")");
     grid[at] = static_cast<int32_t>(i);
     const double* m = means + 2 * i;
@@ -3649,27 +3768,13 @@ mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* mea
   ctx->have_ndt_map = false;  // (until the new map is complete: ensure() may free the buffers the old view points at)
   MCL_HIP(ctx, ctx->d_ndt_grid.ensure(grid.size()));
   MCL_HIP(ctx, ctx->d_ndt_cells.ensure(recs.size()));
+  MCL_HIP(ctx, ctx->d_ndt_keys.ensure(static_cast<size_t>(2 * n)));
   MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_grid.ptr, grid.data(), grid.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_cells.ptr, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
-  NdtMapView v{};
-  v.grid = ctx->d_ndt_grid.ptr;
-  v.cells = ctx->d_ndt_cells.ptr;
-  v.gw = static_cast<uint32_t>(gw);
-  v.inv_resolution = 1. / resolution;
-  v.key_x0 = static_cast<double>(x0 - reach);
-  v.key_y0 = static_cast<double>(y0 - reach);
-  v.box_w = static_cast<double>(x1 - x0 + 1 + 2 * reach);
-  v.box_h = static_cast<double>(y1 - y0 + 1 + 2 * reach);
-  v.reach = reach;
-  v.d1 = prm.d1;
-  v.d2 = prm.d2;
-  v.minimum_likelihood = prm.minimum_likelihood;
-  v.num_offsets = prm.num_offsets;
-  for (uint32_t k = 0; k < prm.num_offsets; ++k) v.delta[k] = prm.offsets[2 * k + 1] * static_cast<int32_t>(gw) + prm.offsets[2 * k];
-  ctx->ndt_view = v;
-  ctx->ndt_map_cells = n;
-  ctx->ndt_resolution = resolution;
-  ctx->have_ndt_map = true;
+  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_keys.ptr, cells, static_cast<size_t>(2 * n) * sizeof(int32_t), hipMemcpyHostToDevice));
+  ctx->ndt_params = prm;
+  ctx->have_ndt_params = true;
+  ndt_install_view(ctx, g, prm, n, resolution);
   return MCL_OK;
 }
 
@@ -3709,6 +3814,78 @@ mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const doubl
   }
   if (const mcl_status s = bind_device(ctx)) return s;
   return do_reweight(ctx, recs.data(), recs.size() / 2);
+}
+
+mcl_status mcl_build_ndt_map_from_points(mcl_ctx* ctx, const double* points_xy, uint64_t n, double resolution) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_build_ndt_map_from_points: the context's sensor model is not MCL_SENSOR_NDT");
+  MCL_REQUIRE(ctx, points_xy && n > 0, "mcl_build_ndt_map_from_points: null argument or no points");
+  MCL_REQUIRE(ctx, n < (1ull << 31), "mcl_build_ndt_map_from_points: too many points");
+  MCL_REQUIRE(ctx, std::isfinite(resolution) && resolution > 0.0, "mcl_build_ndt_map_from_points: resolution must be positive and finite");
+  if (const mcl_status s = bind_device(ctx)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a reweight in flight may still read the old map)
+  ScopedBuffer<double> d_pts;
+  MCL_HIP(ctx, d_pts.ensure(static_cast<size_t>(2) * n));
+  MCL_HIP(ctx, hipMemcpy(d_pts.ptr, points_xy, static_cast<size_t>(2) * n * sizeof(double), hipMemcpyHostToDevice));
+  return ndt_build_from_device_points(ctx, "mcl_build_ndt_map_from_points", d_pts.ptr, n, resolution);
+}
+
+mcl_status mcl_build_ndt_map_from_grid(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32_t height, double grid_resolution,
+                                       const double origin[4], double ndt_resolution) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_build_ndt_map_from_grid: the context's sensor model is not MCL_SENSOR_NDT");
+  MCL_REQUIRE(ctx, cells && origin && width > 0 && height > 0, "mcl_build_ndt_map_from_grid: null argument or an empty grid");
+  MCL_REQUIRE(ctx, static_cast<uint64_t>(width) * height < (1ull << 31), "mcl_build_ndt_map_from_grid: too many grid cells");
+  MCL_REQUIRE(ctx, std::isfinite(grid_resolution) && grid_resolution > 0.0 && std::isfinite(ndt_resolution) && ndt_resolution > 0.0,
+              "mcl_build_ndt_map_from_grid: the resolutions must be positive and finite");
+  MCL_REQUIRE(ctx, std::isfinite(origin[0]) && std::isfinite(origin[1]) && std::isfinite(origin[2]) && std::isfinite(origin[3]),
+              "mcl_build_ndt_map_from_grid: the origin is not finite");
+  if (const mcl_status s = bind_device(ctx)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const uint32_t count = width * height;
+  constexpr int8_t kOccupied = 100;  // the default value traits' occupied_value (mcl_set_map with traits == NULL)
+  ScopedBuffer<int8_t> d_cells;
+  ScopedBuffer<uint32_t> d_offsets;
+  ScopedBuffer<double> d_pts;
+  MCL_HIP(ctx, d_cells.ensure(count));
+  MCL_HIP(ctx, d_offsets.ensure(static_cast<size_t>(count) + num_chunks(count) + 1));
+  MCL_HIP(ctx, hipMemcpy(d_cells.ptr, cells, count, hipMemcpyHostToDevice));
+  uint32_t* d_total = d_offsets.ptr + count + num_chunks(count);
+  launch_ndt_grid_offsets(ctx->stream, d_cells.ptr, count, kOccupied, d_offsets.ptr, d_offsets.ptr + count, d_total);
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  uint32_t occupied = 0;
+  MCL_HIP(ctx, hipMemcpy(&occupied, d_total, sizeof(occupied), hipMemcpyDeviceToHost));
+  MCL_REQUIRE(ctx, occupied > 0, "mcl_build_ndt_map_from_grid: the grid has no occupied cell (the map is kept as it was)");
+  MCL_HIP(ctx, d_pts.ensure(static_cast<size_t>(2) * occupied));
+  launch_ndt_grid_points(ctx->stream, d_cells.ptr, width, height, kOccupied, d_offsets.ptr, grid_resolution, pose_from(origin), d_pts.ptr);
+  return ndt_build_from_device_points(ctx, "mcl_build_ndt_map_from_grid", d_pts.ptr, occupied, ndt_resolution);
+}
+
+mcl_status mcl_get_ndt_map(mcl_ctx* ctx, int32_t* cells_out, double* means_out, double* covariances_out, uint64_t capacity, uint64_t* n) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_get_ndt_map: the context's sensor model is not MCL_SENSOR_NDT");
+  MCL_REQUIRE(ctx, n != nullptr, "mcl_get_ndt_map: null argument");
+  if (!ctx->have_ndt_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_get_ndt_map: no NDT map set (mcl_set_ndt_map, mcl_build_ndt_map_from_*)");
+  const uint64_t k = ctx->ndt_map_cells;
+  *n = k;
+  if (!cells_out && !means_out && !covariances_out) return MCL_OK;  // (the size alone)
+  MCL_REQUIRE(ctx, cells_out && means_out && covariances_out, "mcl_get_ndt_map: null argument");
+  MCL_REQUIRE(ctx, capacity >= k, "mcl_get_ndt_map: the map holds " + std::to_string(k) + " cells, the arrays " + std::to_string(capacity));
+  if (const mcl_status s = bind_device(ctx)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<double> recs(static_cast<size_t>(k) * kNdtRecord);
+  MCL_HIP(ctx, hipMemcpy(cells_out, ctx->d_ndt_keys.ptr, static_cast<size_t>(2 * k) * sizeof(int32_t), hipMemcpyDeviceToHost));
+  MCL_HIP(ctx, hipMemcpy(recs.data(), ctx->d_ndt_cells.ptr, recs.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (uint64_t j = 0; j < k; ++j) {
+    const double* r = recs.data() + j * kNdtRecord;
+    means_out[2 * j] = r[0];
+    means_out[2 * j + 1] = r[1];
+    covariances_out[4 * j] = r[2];
+    covariances_out[4 * j + 1] = r[3];
+    covariances_out[4 * j + 2] = r[3];
+    covariances_out[4 * j + 3] = r[4];
+  }
+  return MCL_OK;
 }
 
 // ---- Landmark and bearing sensor models ----------------------------------------------------------------------------------------

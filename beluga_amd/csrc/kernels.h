@@ -132,6 +132,48 @@ struct NdtMapView {
 // base frame) of max(sum of the present neighbours' d1 exp(-d2/2 e^T (S' + S_map)^-1 e), minimum_likelihood).  A lane per particle.
 void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k);
 
+// The NDT map built on the device (ndt_build_kernels.hip): detail::to_cells with fit_points over n points, as ndt_fit_cells (context.hip)
+// does on the host - keys by truncation toward zero, cells of 5 points or more in ascending (x, y) key order, a cell's sums taken in
+// input order.  Every launcher takes n > 0 points (n < 2^31), x and y interleaved.
+struct NdtBuildScratch {
+  unsigned long long* words[2];  // [n] each: the points' keys relative to their box, (x << 32) | y; ping-pong of the sort
+  uint32_t* idx[2];              // [n] each: the point indices that travel with them
+  uint32_t* table;               // [ndt_radix_table_words(n)] chunk histograms of a pass
+  uint32_t* flags;               // [n] cell starts, then their exclusive scan
+  uint32_t* chunk_tmp;           // [num_chunks(max(n, ndt_radix_table_words(n)))] chunk sums of the scans
+  uint32_t* starts;              // [n / 5] first sorted position of every kept cell
+  uint32_t* counters;            // [kNdtCounters], see below
+};
+enum NdtBuildCounter : int {
+  kNdtCountCells = 0,    // cells kept (launch_ndt_group_points)
+  kNdtCountKeptBox = 1,  // [1..5): min x, max x, min y, max y of the kept cells' relative keys; the caller sets UINT_MAX, 0, UINT_MAX, 0
+  kNdtCountScratch = 5,
+  kNdtCounters = 6
+};
+struct NdtBuildLayout {
+  long long x0, y0;            // the key the relative keys count from
+  long long grid_x0, grid_y0;  // key of the index grid's cell (0, 0)
+  long long gw;
+};
+size_t ndt_radix_table_words(uint32_t n);
+// d_box[5] = {min x, max x, min y, max y} of the points' keys and a flag: != 0 if some point is not finite or its key does not fit an
+// int32.  The caller sets {INT_MAX, INT_MIN, INT_MAX, INT_MIN, 0} first.
+void launch_ndt_key_box(hipStream_t st, const double* pts, uint32_t n, double resolution, int32_t* d_box);
+// Stable sort of the points by key, relative to (x0, y0), over the low bits_x / bits_y bits the box's spans need; then the kept cells'
+// starts marked and scanned into s.flags, their number and box into s.counters.  Returns which of the scratch's two lists is sorted.
+int launch_ndt_group_points(hipStream_t st, const double* pts, uint32_t n, double resolution, int32_t x0, int32_t y0, uint32_t bits_x,
+                            uint32_t bits_y, const NdtBuildScratch& s);
+// The `cells` kept cells (s.counters[kNdtCountCells]) -> records (kNdtRecord doubles each), keys (x, y) and their entries in the index
+// grid (set to -1 by the caller), laid out as NdtMapView wants them.
+void launch_ndt_fit_cells(hipStream_t st, const double* pts, uint32_t n, const NdtBuildScratch& s, int sorted, uint32_t cells,
+                          const NdtBuildLayout& lay, double* records, int32_t* keys, int32_t* grid);
+// Occupancy grid -> points: offsets[i] = occupied cells before cell i in row-major order, *d_total = their number; then the centres of
+// the occupied cells, origin * (resolution * (index + 0.5)), in that order.
+void launch_ndt_grid_offsets(hipStream_t st, const int8_t* cells, uint32_t count, int8_t occupied, uint32_t* offsets, uint32_t* chunk_tmp,
+                             uint32_t* d_total);
+void launch_ndt_grid_points(hipStream_t st, const int8_t* cells, uint32_t W, uint32_t H, int8_t occupied, const uint32_t* offsets,
+                            double resolution, Pose2 origin, double* pts);
+
 // The landmark and bearing models' map and measurement (landmark_kernels.hip).  The landmarks are grouped by category on the host with
 // a stable sort (map order inside a category: std::min_element's "first of equal" holds), 4 doubles each (x, y, z, 0).  A detection is
 // kLandmarkRecord doubles: the vector as given (x, y, z), its norm, its normalized() (x, y, z), then three uint32 in the place of

@@ -230,6 +230,50 @@ class NDTMap2d {
     const double inv = 1. / resolution_;
     return {static_cast<int>(std::floor(x * inv)), static_cast<int>(std::floor(y * inv))};
   }
+  /// The map of a point cloud (world frame) by the rule of detail::to_cells (ndt_sensor_model.hpp:88-110), on the host: keys by
+  /// (p / resolution) truncated toward zero, cells of 5 points or more, in ascending key order (mcl_ndt_measurement_cells).
+  /// Amcl::build_ndt_map builds the same cells on the device.
+  static NDTMap2d from_points(const std::vector<std::pair<double, double>>& points, double resolution) {
+    std::vector<double> xy;
+    xy.reserve(2 * points.size());
+    std::vector<std::pair<key_type, std::size_t>> counts;  // ascending keys
+    for (const auto& p : points) {
+      xy.push_back(p.first);
+      xy.push_back(p.second);
+      const double qx = p.first / resolution, qy = p.second / resolution;
+      if (!(std::abs(qx) < 2147483647.0 && std::abs(qy) < 2147483647.0)) continue;
+      counts.push_back({key_type{static_cast<int>(qx), static_cast<int>(qy)}, 1});
+    }
+    std::sort(counts.begin(), counts.end());
+    std::vector<key_type> keys;
+    for (std::size_t a = 0; a < counts.size();) {
+      std::size_t b = a;
+      while (b < counts.size() && counts[b].first == counts[a].first) ++b;
+      if (b - a >= 5) keys.push_back(counts[a].first);
+      a = b;
+    }
+    std::vector<double> means(2 * (points.size() / 5 + 1)), covs(4 * (points.size() / 5 + 1));
+    std::uint64_t k = 0;
+    if (mcl_ndt_measurement_cells(xy.data(), points.size(), resolution, means.data(), covs.data(), &k) != MCL_OK || k != keys.size())
+      throw std::invalid_argument("NDTMap2d::from_points: the resolution must be positive and finite");
+    std::vector<NDTCell2d> data(k);
+    for (std::size_t j = 0; j < k; ++j) data[j] = NDTCell2d{{means[2 * j], means[2 * j + 1]}, {covs[4 * j], covs[4 * j + 1], covs[4 * j + 2], covs[4 * j + 3]}};
+    return NDTMap2d{std::move(keys), std::move(data), resolution};
+  }
+  /// The same from the centres of a grid's occupied cells, row-major, origin * (resolution * (index + 0.5)); `Grid` is an
+  /// OccupancyGridView.
+  template <class Grid>
+  static NDTMap2d from_occupancy_grid(const Grid& grid, double resolution) {
+    std::vector<std::pair<double, double>> points;
+    const double* o = grid.origin.data();
+    for (std::uint32_t yi = 0; yi < grid.height; ++yi)
+      for (std::uint32_t xi = 0; xi < grid.width; ++xi) {
+        if (grid.cells[static_cast<std::size_t>(yi) * grid.width + xi] != grid.occupied_value) continue;
+        const double lx = (static_cast<double>(xi) + 0.5) * grid.resolution, ly = (static_cast<double>(yi) + 0.5) * grid.resolution;
+        points.emplace_back((o[0] * lx - o[1] * ly) + o[2], (o[1] * lx + o[0] * ly) + o[3]);
+      }
+    return from_points(points, resolution);
+  }
 
  private:
   std::vector<key_type> cells_;
@@ -537,6 +581,7 @@ class Amcl {
         resolution_(other.resolution_),
         has_field_(other.has_field_),
         ndt_params_(std::move(other.ndt_params_)),
+        ndt_resolution_(other.ndt_resolution_),
         landmark_params_(other.landmark_params_),
         bearing_params_(other.bearing_params_),
         landmark_kind_(other.landmark_kind_) {
@@ -636,8 +681,42 @@ class Amcl {
       p.offsets[2 * k + 1] = ndt_params_.neighbors_kernel[k][1];
     }
     check(mcl_set_ndt_map(ctx_, keys.data(), means.data(), covs.data(), map.size(), map.resolution(), &p));
+    ndt_resolution_ = map.resolution();
     has_field_ = false;
     field_.reset();
+  }
+
+  /// Extension: the NDT map built on the device from a point cloud in the world frame, by the rule of NDTMap2d::from_points (the same
+  /// cells, bit for bit), and installed in place; the sensor model's parameters stay.
+  void build_ndt_map(const std::vector<std::pair<double, double>>& points, double resolution) {
+    std::vector<double> xy;
+    xy.reserve(2 * points.size());
+    for (const auto& p : points) {
+      xy.push_back(p.first);
+      xy.push_back(p.second);
+    }
+    check(mcl_build_ndt_map_from_points(ctx_, xy.data(), points.size(), resolution));
+    ndt_resolution_ = resolution;
+  }
+  /// ... from the occupied cells (value 100) of an occupancy grid.
+  void build_ndt_map(const OccupancyGridView& grid, double resolution) {
+    check(mcl_build_ndt_map_from_grid(ctx_, grid.cells, grid.width, grid.height, grid.resolution, grid.origin.data(), resolution));
+    ndt_resolution_ = resolution;
+  }
+  /// The NDT map the filter holds, however it was set.
+  [[nodiscard]] NDTMap2d ndt_map() const {
+    std::uint64_t n = 0;
+    check(mcl_get_ndt_map(ctx_, nullptr, nullptr, nullptr, 0, &n));
+    std::vector<std::int32_t> keys(2 * n);
+    std::vector<double> means(2 * n), covs(4 * n);
+    check(mcl_get_ndt_map(ctx_, keys.data(), means.data(), covs.data(), n, &n));
+    std::vector<NDTMap2d::key_type> k(n);
+    std::vector<NDTCell2d> data(n);
+    for (std::size_t j = 0; j < n; ++j) {
+      k[j] = {keys[2 * j], keys[2 * j + 1]};
+      data[j] = NDTCell2d{{means[2 * j], means[2 * j + 1]}, {covs[4 * j], covs[4 * j + 1], covs[4 * j + 2], covs[4 * j + 3]}};
+    }
+    return NDTMap2d{std::move(k), std::move(data), ndt_resolution_};
   }
 
   /// Update the map used for localization (amcl_core.hpp:150).
@@ -839,6 +918,7 @@ class Amcl {
   double resolution_{0.0};
   bool has_field_{false};
   NDTModelParam2d ndt_params_{};
+  double ndt_resolution_{0.0};  // of the NDT map the context holds
   LandmarkModelParam landmark_params_{};
   BearingModelParam bearing_params_{};
   int landmark_kind_{0};

@@ -267,6 +267,25 @@ mcl_status mcl_ndt_measurement_cells(const double* points_xy, uint64_t num_point
  * sum over the cells of likelihood_at(state * cell).  mcl_reweight on an NDT context fits the cells of its points first. */
 mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const double* covs, uint64_t num_cells);
 
+/* The map built on the device from what a user has at a cold start, a point cloud or an occupancy grid: detail::to_cells with
+ * fit_points over the n points (world frame), the rule of mcl_ndt_measurement_cells - keys by (p / resolution) truncated toward zero,
+ * cells of 5 points or more, mean and sample covariance with the diagonal clamped to >= 1e-5, cells in ascending (x, y) key order, a
+ * cell's sums taken in input order: the cells equal mcl_ndt_measurement_cells' bit for bit.  The result becomes the context's map as if
+ * passed to mcl_set_ndt_map, without a visit to the host; the model parameters are those of the last mcl_set_ndt_map on the context,
+ * mcl_default_ndt_params if there was none.  MCL_ERR_UNSUPPORTED on a context of another sensor model, or where the kept cells' bounding
+ * box (with its border) exceeds 2^26 cells; MCL_ERR_INVALID_ARGUMENT for no points, a point that is not finite or whose key does not
+ * fit an int32, a resolution that is not positive and finite, or an input without any cell of 5 points: the map is then kept as it was. */
+mcl_status mcl_build_ndt_map_from_points(mcl_ctx* ctx, const double* points_xy, uint64_t n, double resolution);
+/* The same from an occupancy grid (row-major int8 cells, grid_resolution metres per cell, origin as SE2 (cos, sin, x, y)): the points
+ * are the centres of the occupied cells - value 100, the default value traits' occupied_value - in row-major order,
+ * origin * (grid_resolution * (index + 0.5)). */
+mcl_status mcl_build_ndt_map_from_grid(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32_t height, double grid_resolution,
+                                       const double origin[4], double ndt_resolution);
+/* The context's map, however it was set, in mcl_set_ndt_map's formats (cells_out[n*2], means_out[n*2], covariances_out[n*4]); *n = its
+ * cells.  The three arrays hold `capacity` cells each (MCL_ERR_INVALID_ARGUMENT if fewer than the map's); all three NULL: *n alone.
+ * MCL_ERR_NOT_READY without a map. */
+mcl_status mcl_get_ndt_map(mcl_ctx* ctx, int32_t* cells_out, double* means_out, double* covariances_out, uint64_t capacity, uint64_t* n);
+
 /* ---- Landmark and bearing sensor models (sensor/landmark_sensor_model.hpp, sensor/bearing_sensor_model.hpp) -------------------
  * A context created with sensor_kind = MCL_SENSOR_LANDMARK or MCL_SENSOR_BEARING takes its map from mcl_set_landmark_map: a
  * beluga::LandmarkMap (sensor/data/landmark_map.hpp), 3D landmark positions with a category each, plus the map's boundaries.  The
