@@ -27,7 +27,9 @@
 #include "beluga_mcl.h"
 #include "cluster_host.h"
 #include "kernels.h"
+#include "landmark_host.h"
 #include "map_build.h"
+#include "ndt_host.h"
 
 namespace {
 
@@ -420,7 +422,7 @@ struct mcl_ctx {
   bool have_landmark_map{false};
   DeviceBuffer<double> d_landmarks;
   LandmarkMapView landmark_view{};
-  std::map<uint32_t, std::pair<uint32_t, uint32_t>> landmark_ranges;  // category -> (first, count) in d_landmarks
+  LandmarkRanges landmark_ranges;  // category -> (first, count) in d_landmarks
   FreeCells landmark_random{nullptr, 0};
   std::vector<double> h_landmark_meas;  // the detections, kLandmarkRecord doubles each (what stage_points uploads)
   bool is_landmark() const { return cfg.sensor_kind == MCL_SENSOR_LANDMARK || cfg.sensor_kind == MCL_SENSOR_BEARING; }
@@ -687,66 +689,22 @@ mcl_status rebuild_cube(mcl_ctx* ctx, const float* h_field) {
   return MCL_OK;
 }
 
-// detail::to_cells (ndt_sensor_model.hpp:88-110) with fit_points (:66-80): kNdtRecord doubles per cell (mean x, y, covariance xx, xy,
-// yy, 0) appended to `out`, the cells in ascending key order (the reference's order is an unordered_map's: only the rounding of the
-// weight's sum depends on it).  The group key is (p / resolution).cast<int>() - division and truncation toward zero, NOT the floor
-// of cell_near.  Points that are not finite or whose key does not fit an int are dropped (the reference's cast is undefined there).
-void ndt_fit_cells(const double* pts, uint64_t B, double resolution, std::vector<double>& out) {
-  out.clear();
-  std::vector<std::pair<std::pair<int32_t, int32_t>, uint64_t>> keyed;
-  keyed.reserve(B);
-  for (uint64_t i = 0; i < B; ++i) {
-    const double qx = pts[2 * i] / resolution, qy = pts[2 * i + 1] / resolution;
-    if (!(std::abs(qx) < 2147483647.0 && std::abs(qy) < 2147483647.0)) continue;
-    keyed.push_back({{static_cast<int32_t>(qx), static_cast<int32_t>(qy)}, i});
-  }
-  std::sort(keyed.begin(), keyed.end());
-  for (size_t a = 0; a < keyed.size();) {
-    size_t b = a;
-    while (b < keyed.size() && keyed[b].first == keyed[a].first) ++b;
-    const size_t m = b - a;
-    if (m >= 5) {  // kMinPointsPerCell
-      double sx = 0.0, sy = 0.0;
-      for (size_t t = a; t < b; ++t) {
-        sx += pts[2 * keyed[t].second];
-        sy += pts[2 * keyed[t].second + 1];
-      }
-      const double mx = sx / static_cast<double>(m), my = sy / static_cast<double>(m);
-      double cxx = 0.0, cxy = 0.0, cyy = 0.0;
-      for (size_t t = a; t < b; ++t) {
-        const double dx = pts[2 * keyed[t].second] - mx, dy = pts[2 * keyed[t].second + 1] - my;
-        cxx += dx * dx;
-        cxy += dx * dy;
-        cyy += dy * dy;
-      }
-      const double denom = static_cast<double>(m - 1);  // sample covariance
-      const double rec[kNdtRecord] = {mx, my, std::max(cxx / denom, 1e-5), cxy / denom, std::max(cyy / denom, 1e-5), 0.0};
-      out.insert(out.end(), rec, rec + kNdtRecord);
-    }
-    a = b;
-  }
-}
-void ndt_fit_scan(mcl_ctx* ctx, const double* pts, uint64_t B) { ndt_fit_cells(pts, B, ctx->ndt_resolution, ctx->h_ndt_meas); }
-
-// The index grid of an NDT map over the keys' box [x0, x1] x [y0, y1] (kernels.h NdtMapView): the box with a border of 2 * reach.
-struct NdtGridShape {
-  int32_t reach;
-  int64_t x0, y0, x1, y1;
-  int64_t grid_x0, grid_y0;  // key of the grid's cell (0, 0)
-  int64_t gw, gh;
-  bool fits;  // within 2^26 cells
+// What a cycle uploads for its reweight kernel, in the form that kernel reads: a scan's points (x, y; the grid models), the scan's
+// measurement cells (kNdtRecord doubles each) or the detection records of a landmark or bearing context (kLandmarkRecord doubles each).
+struct Measurement {
+  const double* data;
+  uint64_t doubles;
 };
-int32_t ndt_reach(const mcl_ndt_params& prm) {  // the largest |component| of a kernel offset, at least 1
-  int32_t reach = 1;
-  for (uint32_t k = 0; k < 2 * prm.num_offsets; ++k) reach = std::max(reach, std::abs(prm.offsets[k]));
-  return reach;
+// (the doubling saturates: the limit on a scan's points is checked against half of it)
+Measurement scan_measurement(const double* points_xy, uint64_t num_points) {
+  return Measurement{points_xy, 2 * std::min<uint64_t>(num_points, UINT64_MAX / 2)};
 }
-NdtGridShape ndt_grid_shape(int32_t reach, int64_t x0, int64_t x1, int64_t y0, int64_t y1) {
-  NdtGridShape g{reach, x0, y0, x1, y1, x0 - 2 * reach, y0 - 2 * reach, (x1 - x0 + 1) + 4 * reach, (y1 - y0 + 1) + 4 * reach, false};
-  constexpr int64_t kMaxGridCells = int64_t{1} << 26;
-  g.fits = !(g.gw > kMaxGridCells || g.gh > kMaxGridCells || g.gw * g.gh > kMaxGridCells);
-  return g;
+// The scan's measurement cells (ndt_fit_cells, ndt_host.cpp) at the context's resolution.
+Measurement ndt_fit_scan(mcl_ctx* ctx, const double* pts, uint64_t num_points) {
+  ndt_fit_cells(pts, num_points, ctx->ndt_resolution, ctx->h_ndt_meas);
+  return Measurement{ctx->h_ndt_meas.data(), ctx->h_ndt_meas.size()};
 }
+
 // The map in d_ndt_grid / d_ndt_cells / d_ndt_keys (n cells, complete) becomes the context's.
 void ndt_install_view(mcl_ctx* ctx, const NdtGridShape& g, const mcl_ndt_params& prm, uint64_t n, double resolution) {
   NdtMapView v{};
@@ -844,29 +802,33 @@ mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, co
   return MCL_OK;
 }
 
-// Stages the scan in mapped pinned memory; a kernel of the cycle pulls it into d_points (pull_scan_args / launch_pull_scan).
-mcl_status stage_points(mcl_ctx* ctx, const double* pts, uint64_t B) {
-  if (B == 0) return MCL_OK;
-  MCL_HIP(ctx, ctx->d_points.ensure(2 * B));
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) MCL_HIP(ctx, ctx->d_beam_points.ensure(kBeamPointDoubles * B));
+// Stages the measurement in mapped pinned memory; a kernel of the cycle pulls it into d_points (pull_scan_args / launch_pull_scan).
+mcl_status stage_points(mcl_ctx* ctx, const Measurement& m) {
+  if (m.doubles == 0) return MCL_OK;
+  MCL_HIP(ctx, ctx->d_points.ensure(m.doubles));
+  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) MCL_HIP(ctx, ctx->d_beam_points.ensure(kBeamPointDoubles * (m.doubles / 2)));
   if (ctx->points_in_flight) {  // an earlier call may still be reading the staging buffer
     if (ctx->points_event_valid) MCL_HIP(ctx, hipEventSynchronize(ctx->points_event));
     else MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->points_in_flight = false;
   }
-  if (ctx->h_points_cap < 2 * B) {
+  if (ctx->h_points_cap < m.doubles) {
     if (ctx->h_points) (void)hipHostFree(ctx->h_points);
     ctx->h_points = nullptr;
     ctx->hd_points = nullptr;
     ctx->h_points_cap = 0;
-    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_points), 2 * B * sizeof(double), hipHostMallocMapped));
+    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_points), m.doubles * sizeof(double), hipHostMallocMapped));
     MCL_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->hd_points), ctx->h_points, 0));
-    ctx->h_points_cap = 2 * B;
+    ctx->h_points_cap = m.doubles;
+  }
+  if (ctx->off_grid()) {  // records: nothing reads the extent of a scan on these contexts
+    std::copy(m.data, m.data + m.doubles, ctx->h_points);
+    return MCL_OK;
   }
   double extent = 0.0;  // maximum of |x| + |y| over the scan; a NaN point makes it NaN (and every comparison with it false)
   bool poisoned = false;
-  for (uint64_t i = 0; i < 2 * B; i += 2) {
-    const double x = pts[i], y = pts[i + 1];
+  for (uint64_t i = 0; i < m.doubles; i += 2) {
+    const double x = m.data[i], y = m.data[i + 1];
     ctx->h_points[i] = x;
     ctx->h_points[i + 1] = y;
     const double e = std::abs(x) + std::abs(y);
@@ -1115,7 +1077,7 @@ bool samplers_close(const DiffDriveSampler& now, const DiffDriveSampler& predict
 
 // fused (mcl_update): the scan staged by stage_points is pulled by the same kernel, and the ordering keys of the new poses
 // come out of it when the host knows where the set is (*keys_emitted).
-mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint32_t step, uint64_t scan_points = 0,
+mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint32_t step, uint64_t scan_doubles = 0,
                         bool* keys_emitted = nullptr) {
   stage_begin(ctx, MCL_STAGE_PROPAGATE);
   const DiffDriveSampler sampler = make_sampler(pose, prev, ctx->cfg.motion, ctx->cfg.motion_kind, ctx->cfg.strafe_noise_from_translation);
@@ -1139,10 +1101,10 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
   const bool ahead = ctx->d_noise.ptr && ctx->noise_n >= ctx->n && ctx->n > 65536 && ctx->noise_step == step && ctx->noise_seed == ctx->cfg.seed &&
                      ctx->noise_offset == ctx->cfg.shard_offset;
   launch_propagate(ctx->stream, ctx->cur(), ctx->n, sampler, ctx->cfg.seed, step, ctx->cfg.shard_offset,
-                   scan_points ? ctx->hd_points : nullptr, scan_points ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(2 * scan_points),
+                   scan_doubles ? ctx->hd_points : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
                    keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->noise_n);
   if (ahead) ctx->noise_ahead_used += 1;
-  if (scan_points) points_pulled(ctx, false);
+  if (scan_doubles) points_pulled(ctx, false);
   if (keys_emitted) *keys_emitted = keys;
   ctx->order_ready = use_ahead;
   stage_end(ctx, MCL_STAGE_PROPAGATE);
@@ -1150,6 +1112,7 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
   return MCL_OK;
 }
 
+// B: the points of the scan (a landmark or bearing context does not look at it: its records were bounded where they were made).
 mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
   if (ctx->is_ndt()) {
     if (!ctx->have_ndt_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no NDT map set (mcl_set_ndt_map)");
@@ -1171,16 +1134,17 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
 // points_staged: stage_points + the pull already happened (mcl_update); keys_ready: k_propagate emitted the ordering keys.
 // want_weight_sums: the normalisation follows at once (mcl_update): the LF patch kernel leaves the sums of its workgroups' new
 // weights in d_lf_wsum (ctx->lf_wsum_count of them; 0 if another kernel ran).
-mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_staged = false, bool keys_ready = false,
+mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = false, bool keys_ready = false,
                        bool want_weight_sums = false) {
   ctx->lf_wsum_count = 0;
+  const uint64_t B = ctx->off_grid() ? 0 : m.doubles / 2;  // the grid models' measurement is the scan itself: B points
   if (const mcl_status s = reweight_preconditions(ctx, B)) return s;
   const bool unit_weights = ctx->weights_unit && ctx->tuning.lf_unit_weights != 0;
   ctx->weights_unit = false;
   if (!points_staged) {
-    if (const mcl_status s = stage_points(ctx, pts, B)) return s;
-    if (B) {
-      launch_pull_scan(ctx->stream, ctx->hd_points, ctx->d_points.ptr, static_cast<uint32_t>(2 * B));
+    if (const mcl_status s = stage_points(ctx, m)) return s;
+    if (m.doubles) {
+      launch_pull_scan(ctx->stream, ctx->hd_points, ctx->d_points.ptr, static_cast<uint32_t>(m.doubles));
       points_pulled(ctx, true);
     }
   }
@@ -1199,13 +1163,11 @@ mcl_status do_reweight(mcl_ctx* ctx, const double* pts, uint64_t B, bool points_
     launch_order_particles(ctx->stream, ctx->cur(), ctx->n, &sort, have_frame ? &frame : nullptr, keys_ready, frame.layout);
   }
   if (ctx->is_ndt()) {
-    // B counts staged doubles in pairs (stage_points): the measurement cells are kNdtRecord doubles each
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, static_cast<uint32_t>(2 * B / kNdtRecord));
+    launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, static_cast<uint32_t>(m.doubles / kNdtRecord));
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else if (ctx->is_landmark()) {
-    // (B counts staged doubles in pairs as well: the detections are kLandmarkRecord doubles each)
-    const uint32_t k = static_cast<uint32_t>(2 * B / kLandmarkRecord);
+    const uint32_t k = static_cast<uint32_t>(m.doubles / kLandmarkRecord);
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
     if (ctx->cfg.sensor_kind == MCL_SENSOR_LANDMARK) launch_reweight_landmarks(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
     else launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
@@ -2095,8 +2057,7 @@ mcl_status sharded_preconditions(mcl_ctx* ctx) {
 // beluga::Amcl::update (amcl_core.hpp:165-201) over the sharded set; same statements as mcl_update, with the exchanges of
 // include/beluga_mcl.h ("Particle shards") between them.  Every rank takes the same decisions: they depend on the control
 // action (identical inputs) and on gathered sums (identical values, added in rank order everywhere).
-mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_xy, uint64_t num_points, mcl_estimate* estimate,
-                          mcl_update_info* info) {
+mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const Measurement& scan, mcl_estimate* estimate, mcl_update_info* info) {
   const mcl_amcl_params& ap = ctx->cfg.amcl;
   const uint32_t world = ctx->comm_world, rank = ctx->comm_rank;
   const bool adaptive = ap.min_particles < ap.max_particles;
@@ -2121,7 +2082,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
   }
   const uint64_t n_total = ctx->global_n ? ctx->global_n : ap.max_particles;  // particles over all shards before this cycle's resampling
   if (n_total == 0) return MCL_OK;
-  if (const mcl_status s = stage_points(ctx, points_xy, num_points)) return s;
+  if (const mcl_status s = stage_points(ctx, scan)) return s;
   advance_window(ctx, pose);
   double* d = ctx->d_comm_f64.ptr;
   const CommAreas gathered = comm_areas(ctx);
@@ -2129,8 +2090,8 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const double* points_
 
   MCL_HIP(ctx, hipMemsetAsync(d + kCommOverflow, 0, sizeof(double), ctx->stream));  // this cycle's overflow flag (the fixed-capacity exchange)
   bool keys_ready = false;
-  if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, num_points, &keys_ready)) return s;  // :174-175
-  if (const mcl_status s = do_reweight(ctx, points_xy, num_points, true, keys_ready)) return s;                         // :176
+  if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, scan.doubles, &keys_ready)) return s;  // :174-175
+  if (const mcl_status s = do_reweight(ctx, scan, true, keys_ready)) return s;                                            // :176
   ctx->every_n_current = next_every_n(ctx);  // every_n does not depend on data
   const bool fires = ctx->every_n_current == 0;
   // :177 normalise by the GLOBAL sum: shard sums gathered, added in rank order by every rank
@@ -2814,10 +2775,9 @@ mcl_status mcl_reweight(mcl_ctx* ctx, const double* points_xy, uint64_t num_poin
   if (const mcl_status s = bind_device(ctx)) return s;
   if (ctx->is_ndt()) {
     if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
-    ndt_fit_scan(ctx, points_xy, num_points);
-    return do_reweight(ctx, ctx->h_ndt_meas.data(), ctx->h_ndt_meas.size() / 2);
+    return do_reweight(ctx, ndt_fit_scan(ctx, points_xy, num_points));
   }
-  return do_reweight(ctx, points_xy, num_points);
+  return do_reweight(ctx, scan_measurement(points_xy, num_points));
 }
 
 mcl_status mcl_weight_sum(mcl_ctx* ctx, double* sum) {
@@ -2854,39 +2814,6 @@ mcl_status mcl_estimate_sums(mcl_ctx* ctx, const double pivot_xy[2], double sums
   return do_estimate_sums(ctx, pivot_xy ? pivot_xy : zero, sums);
 }
 
-// algorithm/estimation.hpp:436-475 from the single-pass sufficient statistics.
-mcl_status mcl_estimate_from_sums(const double sums[12], mcl_estimate* out) {
-  if (!sums || !out) return MCL_ERR_INVALID_ARGUMENT;
-  const double sw = sums[0], sw2 = sums[1];
-  const double mc = sums[2] / sw, ms = sums[3] / sw;
-  const double mdx = sums[4] / sw, mdy = sums[5] / sw;
-  const double sq = sw2 / (sw * sw);  // sum of squared normalised weights
-  const double corr = 1.0 - sq;       // estimation.hpp:270
-  const double cxx = (sums[6] / sw - mdx * mdx) / corr;
-  const double cxy = (sums[7] / sw - mdx * mdy) / corr;
-  const double cyy = (sums[8] / sw - mdy * mdy) / corr;
-  for (double& v : out->covariance) v = 0.0;
-  out->covariance[0] = cxx;
-  out->covariance[1] = cxy;
-  out->covariance[3] = cxy;
-  out->covariance[4] = cyy;
-  out->pose[2] = sums[9] + mdx;
-  out->pose[3] = sums[10] + mdy;
-  const double norm = std::sqrt(mc * mc + ms * ms);
-  if (norm < std::numeric_limits<double>::epsilon()) {  // estimation.hpp:460-466
-    out->covariance[8] = std::numeric_limits<double>::infinity();
-    const Rot2 zero = rot_exp(0.0);
-    out->pose[0] = zero.c;
-    out->pose[1] = zero.s;
-  } else {
-    out->covariance[8] = -2.0 * std::log(norm);
-    const Rot2 r = rot_from_complex(mc, ms);
-    out->pose[0] = r.c;
-    out->pose[1] = r.s;
-  }
-  return MCL_OK;
-}
-
 mcl_status mcl_estimate_pose(mcl_ctx* ctx, mcl_estimate* out) {
   if (!ctx || !out) return MCL_ERR_INVALID_ARGUMENT;
   if (ctx->n == 0) return fail(ctx, MCL_ERR_NOT_READY, "no particles");
@@ -2901,11 +2828,10 @@ mcl_status mcl_estimate_pose(mcl_ctx* ctx, mcl_estimate* out) {
   return s;
 }
 
-// Amcl::update (amcl_core.hpp:165-201) over a measurement in the form the context's reweight kernel reads: the scan's points, or the
-// detection records of a landmark / bearing context (mcl_update_landmarks, mcl_update_bearings).
-static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], const double* points_xy, uint64_t num_points,
-                               mcl_estimate* estimate, mcl_update_info* info) {
-  MCL_REQUIRE(ctx, control_pose && (num_points == 0 || points_xy), "null argument");
+// Amcl::update (amcl_core.hpp:165-201) over the scan's points, or the detection records of a landmark / bearing context
+// (mcl_update_landmarks, mcl_update_bearings).
+static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measurement m, mcl_estimate* estimate, mcl_update_info* info) {
+  MCL_REQUIRE(ctx, control_pose && (m.doubles == 0 || m.data), "null argument");
   const auto t_entry = std::chrono::steady_clock::now();
   if (info) {
     std::memset(info, 0, sizeof(*info));
@@ -2928,25 +2854,21 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], const
   // fails here leaves the motion unconsumed, as if it had not been called (the reference has no partial-update state).
   auto consume_motion = [&] { if (moved) { ctx->latest = pose; ctx->have_latest = true; } };
   if (const mcl_status s = bind_device(ctx)) return s;
-  if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
+  if (const mcl_status s = reweight_preconditions(ctx, m.doubles / 2)) return s;
   ctx->lf_mode.decided = false;  // whatever an earlier, failed cycle left behind
   if (ctx->have_comm && ctx->comm_world > 1) {
     // before any rank-local state moves: the ranks must not diverge
     if (const mcl_status s = sharded_preconditions(ctx)) return s;
     consume_motion();
-    return sharded_update(ctx, pose, points_xy, num_points, estimate, info);
+    return sharded_update(ctx, pose, m, estimate, info);
   }
-  if (ctx->is_ndt()) {  // the scan's measurement cells (detail::to_cells) are what the cycle uploads: kNdtRecord doubles per cell
-    ndt_fit_scan(ctx, points_xy, num_points);
-    points_xy = ctx->h_ndt_meas.data();
-    num_points = ctx->h_ndt_meas.size() / 2;
-  }
-  if (const mcl_status s = stage_points(ctx, points_xy, num_points)) return s;
+  if (ctx->is_ndt()) m = ndt_fit_scan(ctx, m.data, m.doubles / 2);  // the scan's measurement cells are what the cycle uploads
+  if (const mcl_status s = stage_points(ctx, m)) return s;
   consume_motion();
   advance_window(ctx, pose);
 
   bool keys_ready = false;
-  if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, num_points, &keys_ready)) return s;  // :174-175
+  if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, m.doubles, &keys_ready)) return s;  // :174-175
   const auto t_first = std::chrono::steady_clock::now();
   // With a fixed particle count and no selective resampling nothing in the cycle depends on a host-side decision: the
   // recovery estimator runs on the device as well and the cycle synchronises once, at the estimate.
@@ -2956,7 +2878,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], const
   const bool device_policy = !ap.selective_resampling && ap.min_particles >= std::min<uint64_t>(ap.max_particles, ctx->capacity) &&
                              ctx->tuning.device_policy != 0 && !ctx->off_grid();
   // (the normalisation follows at once: the LF kernel leaves the sums it is built on)
-  if (const mcl_status s = do_reweight(ctx, points_xy, num_points, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0)) return s;  // :176
+  if (const mcl_status s = do_reweight(ctx, m, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0)) return s;  // :176
   // Small sets (the reference's own sizes): everything behind the reweight in ONE launch of one workgroup and one synchronisation
   // (k_small_tail) - the policies are evaluated on the device, the host keeps the recovery filters' state.
   const uint64_t every_n = next_every_n(ctx);  // :181 (stored by the path that takes the cycle)
@@ -3103,41 +3025,7 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
                       mcl_estimate* estimate, mcl_update_info* info) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_update: a landmark or bearing context takes mcl_update_landmarks / mcl_update_bearings");
-  return update_cycle(ctx, control_pose, points_xy, num_points, estimate, info);
-}
-
-mcl_status mcl_prepare_laser_scan(const mcl_laser_scan* scan, double* points_xy, uint64_t* num_points) {
-  if (!scan || !num_points || (scan->num_ranges && (!scan->ranges || !points_xy))) return MCL_ERR_INVALID_ARGUMENT;
-  const uint64_t n = scan->num_ranges, count = scan->max_beams;
-  const double lo = std::max(static_cast<double>(scan->range_min), scan->min_range);  // laser_scan.hpp:61-62
-  const double hi = std::min(static_cast<double>(scan->range_max), scan->max_range);
-  const double qx = scan->origin_se3[0], qy = scan->origin_se3[1], qz = scan->origin_se3[2], qw = scan->origin_se3[3];
-  const uint64_t taken = n == 0 ? 0 : std::min(n, count);  // take_evenly.hpp:47-57
-  uint64_t m = 0;
-  for (uint64_t k = 0; k < taken; ++k) {
-    uint64_t i = k;  // take_evenly.hpp:126-148: ceil(k * (size - 1) / (count - 1))
-    if (count <= n && k > 0) {
-      if (count == 1) break;
-      const int64_t a = static_cast<int64_t>(k) * (static_cast<int64_t>(n) - 1), b = static_cast<int64_t>(count) - 1;
-      i = static_cast<uint64_t>(a / b + ((a % b == 0) ? 0 : 1));
-    }
-    if (i >= n) break;
-    const double range = static_cast<double>(scan->ranges[i]);
-    // float arithmetic first, then widened (laser_scan.hpp:73-77)
-    const double theta = static_cast<double>(scan->angle_min + static_cast<float>(static_cast<int>(i)) * scan->angle_increment);
-    if (std::isnan(range) || !(range >= lo) || !(range <= hi)) continue;  // sensor/data/laser_scan.hpp:79-83
-    const double px = range * std::cos(theta), py = range * std::sin(theta), pz = 0.0;
-    // origin * (x, y, 0): Sophus SO3 rotates with uv = 2 (q.vec x p); p + q.w uv + q.vec x uv, then adds the translation
-    double ux = qy * pz - qz * py, uy = qz * px - qx * pz, uz = qx * py - qy * px;
-    ux += ux;
-    uy += uy;
-    uz += uz;
-    points_xy[2 * m] = (px + qw * ux + (qy * uz - qz * uy)) + scan->origin_se3[4];
-    points_xy[2 * m + 1] = (py + qw * uy + (qz * ux - qx * uz)) + scan->origin_se3[5];
-    ++m;
-  }
-  *num_points = m;
-  return MCL_OK;
+  return update_cycle(ctx, control_pose, scan_measurement(points_xy, num_points), estimate, info);
 }
 
 mcl_status mcl_update_laser_scan(mcl_ctx* ctx, const double control_pose[4], const mcl_laser_scan* scan, mcl_estimate* estimate,
@@ -3476,24 +3364,6 @@ mcl_status mcl_get_likelihood_field_origin(mcl_ctx* ctx, double origin[4]) {
   return MCL_OK;
 }
 
-mcl_status mcl_project_point_cloud(const float* points_xyz, uint64_t num_points, const double origin_se3[7], double* points_xy) {
-  if (!origin_se3 || (num_points && (!points_xyz || !points_xy))) return MCL_ERR_INVALID_ARGUMENT;
-  const double qx = origin_se3[0], qy = origin_se3[1], qz = origin_se3[2], qw = origin_se3[3];
-  for (uint64_t i = 0; i < num_points; ++i) {
-    // beluga_ros/src/amcl.cpp:73-76: origin * p.cast<double>(), keep x and y.  Sophus SO3 rotates with
-    // uv = 2 (q.vec x p); p + q.w uv + q.vec x uv, then adds the translation.
-    const double px = static_cast<double>(points_xyz[3 * i]), py = static_cast<double>(points_xyz[3 * i + 1]),
-                 pz = static_cast<double>(points_xyz[3 * i + 2]);
-    double ux = qy * pz - qz * py, uy = qz * px - qx * pz, uz = qx * py - qy * px;
-    ux += ux;
-    uy += uy;
-    uz += uz;
-    points_xy[2 * i] = (px + qw * ux + (qy * uz - qz * uy)) + origin_se3[4];
-    points_xy[2 * i + 1] = (py + qw * uy + (qz * ux - qx * uz)) + origin_se3[5];
-  }
-  return MCL_OK;
-}
-
 mcl_status mcl_update_point_cloud(mcl_ctx* ctx, const double control_pose[4], const float* points_xyz, uint64_t num_points,
                                   const double origin_se3[7], mcl_estimate* estimate, mcl_update_info* info) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
@@ -3700,101 +3570,26 @@ mcl_status mcl_comm_attach_rccl(mcl_ctx* ctx, const uint8_t id[128], uint32_t ra
 }
 
 // ---- 2D NDT sensor model --------------------------------------------------------------------------------------------------
-void mcl_default_ndt_params(mcl_ndt_params* params) {
-  if (!params) return;
-  std::memset(params, 0, sizeof(*params));
-  params->minimum_likelihood = 0.0;  // NDTModelParam (ndt_sensor_model.hpp:153-166)
-  params->d1 = 1.0;
-  params->d2 = 1.0;
-  static const int32_t kernel[9][2] = {{-1, -1}, {-1, 0}, {-1, 1}, {0, -1}, {0, 0}, {0, 1}, {1, -1}, {1, 0}, {1, 1}};  // :113-123
-  params->num_offsets = 9;
-  for (int k = 0; k < 9; ++k) {
-    params->offsets[2 * k] = kernel[k][0];
-    params->offsets[2 * k + 1] = kernel[k][1];
-  }
-}
-
 mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* means, const double* covariances, uint64_t n,
                            double resolution, const mcl_ndt_params* params) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_map: not on a landmark or bearing context (its map comes from mcl_set_landmark_map)");
   MCL_REQUIRE(ctx, ctx->is_ndt(), "mcl_set_ndt_map: the context's sensor model is not MCL_SENSOR_NDT");
-  MCL_REQUIRE(ctx, cells && means && covariances && n > 0, "mcl_set_ndt_map: null argument or no cells");
-  MCL_REQUIRE(ctx, n < (1ull << 31), "mcl_set_ndt_map: too many cells");
-  MCL_REQUIRE(ctx, std::isfinite(resolution) && resolution > 0.0, "mcl_set_ndt_map: resolution must be positive and finite");
-  mcl_ndt_params prm;
-  if (params) prm = *params;
-  else mcl_default_ndt_params(&prm);
-  MCL_REQUIRE(ctx, prm.num_offsets >= 1 && prm.num_offsets <= MCL_NDT_MAX_OFFSETS, "mcl_set_ndt_map: 1 .. 32 kernel offsets");
-  MCL_REQUIRE(ctx, std::isfinite(prm.d1) && std::isfinite(prm.d2) && std::isfinite(prm.minimum_likelihood) && prm.minimum_likelihood >= 0.0,
-              "mcl_set_ndt_map: d1, d2 must be finite and minimum_likelihood finite and >= 0");
-  int32_t reach = 1;
-  for (uint32_t k = 0; k < 2 * prm.num_offsets; ++k) {
-    MCL_REQUIRE(ctx, prm.offsets[k] >= -64 && prm.offsets[k] <= 64, "mcl_set_ndt_map: kernel offsets are limited to 64 cells");
-    reach = std::max(reach, std::abs(prm.offsets[k]));
-  }
-  int64_t x0 = INT64_MAX, y0 = INT64_MAX, x1 = INT64_MIN, y1 = INT64_MIN;
-  for (uint64_t i = 0; i < n; ++i) {
-    x0 = std::min<int64_t>(x0, cells[2 * i]);
-    x1 = std::max<int64_t>(x1, cells[2 * i]);
-    y0 = std::min<int64_t>(y0, cells[2 * i + 1]);
-    y1 = std::max<int64_t>(y1, cells[2 * i + 1]);
-    const double* m = means + 2 * i;
-    const double* c = covariances + 4 * i;
-    MCL_REQUIRE(ctx, std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) &&
-                         std::isfinite(c[3]),
-                "mcl_set_ndt_map: cell " + std::to_string(i) + " has a value that is not finite");
-    MCL_REQUIRE(ctx, std::abs(c[1] - c[2]) <= 1e-12 * std::max(std::abs(c[1]), std::abs(c[2])),
-                "mcl_set_ndt_map: the covariance of cell " + std::to_string(i) + " is not symmetric");
-  }
-  const NdtGridShape g = ndt_grid_shape(reach, x0, x1, y0, y1);
-  if (!g.fits)
-    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_map: the bounding box of the keys exceeds 2^26 cells (" + std::to_string(g.gw) + " x " +
-                                              std::to_string(g.gh) + " with its border)");
-  const int64_t gw = g.gw, gh = g.gh;
-  std::vector<int32_t> grid(static_cast<size_t>(gw * gh), -1);
-  std::vector<double> recs(static_cast<size_t>(n) * kNdtRecord);
-  for (uint64_t i = 0; i < n; ++i) {
-    const size_t at = static_cast<size_t>((cells[2 * i + 1] - g.grid_y0) * gw + (cells[2 * i] - g.grid_x0));
-    MCL_REQUIRE(ctx, grid[at] < 0, "mcl_set_ndt_map: duplicate key (" + std::to_string(cells[2 * i]) + ", " + std::to_string(cells[2 * i + 1]) + ")");
-    grid[at] = static_cast<int32_t>(i);
-    const double* m = means + 2 * i;
-    const double* c = covariances + 4 * i;
-    const double r[kNdtRecord] = {m[0], m[1], c[0], c[1], c[3], 0.0};
-    std::copy(r, r + kNdtRecord, recs.begin() + static_cast<ptrdiff_t>(i * kNdtRecord));
-  }
+  NdtMapLayout map;
+  std::string error;
+  if (const mcl_status s = ndt_layout_map(cells, means, covariances, n, resolution, params, &map, &error)) return fail(ctx, s, error);
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a reweight in flight may still read the old map)
   ctx->have_ndt_map = false;  // (until the new map is complete: ensure() may free the buffers the old view points at)
-  MCL_HIP(ctx, ctx->d_ndt_grid.ensure(grid.size()));
-  MCL_HIP(ctx, ctx->d_ndt_cells.ensure(recs.size()));
+  MCL_HIP(ctx, ctx->d_ndt_grid.ensure(map.grid.size()));
+  MCL_HIP(ctx, ctx->d_ndt_cells.ensure(map.records.size()));
   MCL_HIP(ctx, ctx->d_ndt_keys.ensure(static_cast<size_t>(2 * n)));
-  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_grid.ptr, grid.data(), grid.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_cells.ptr, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
+  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_grid.ptr, map.grid.data(), map.grid.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_cells.ptr, map.records.data(), map.records.size() * sizeof(double), hipMemcpyHostToDevice));
   MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_keys.ptr, cells, static_cast<size_t>(2 * n) * sizeof(int32_t), hipMemcpyHostToDevice));
-  ctx->ndt_params = prm;
+  ctx->ndt_params = map.params;
   ctx->have_ndt_params = true;
-  ndt_install_view(ctx, g, prm, n, resolution);
-  return MCL_OK;
-}
-
-mcl_status mcl_ndt_measurement_cells(const double* points_xy, uint64_t num_points, double resolution, double* means_out, double* covs_out,
-                                     uint64_t* num_cells) {
-  if (!num_cells || (num_points && !points_xy) || !(std::isfinite(resolution) && resolution > 0.0)) return MCL_ERR_INVALID_ARGUMENT;
-  if (num_points >= 5 && (!means_out || !covs_out)) return MCL_ERR_INVALID_ARGUMENT;
-  std::vector<double> recs;
-  ndt_fit_cells(points_xy, num_points, resolution, recs);
-  const uint64_t k = recs.size() / kNdtRecord;
-  for (uint64_t j = 0; j < k; ++j) {
-    const double* r = recs.data() + j * kNdtRecord;
-    means_out[2 * j] = r[0];
-    means_out[2 * j + 1] = r[1];
-    covs_out[4 * j] = r[2];
-    covs_out[4 * j + 1] = r[3];
-    covs_out[4 * j + 2] = r[3];
-    covs_out[4 * j + 3] = r[4];
-  }
-  *num_cells = k;
+  ndt_install_view(ctx, map.shape, map.params, n, resolution);
   return MCL_OK;
 }
 
@@ -3809,11 +3604,10 @@ mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const doubl
   for (uint64_t j = 0; j < num_cells; ++j) {
     const double* c = covs + 4 * j;
     MCL_REQUIRE(ctx, std::abs(c[1] - c[2]) <= 1e-12 * std::max(std::abs(c[1]), std::abs(c[2])), "mcl_reweight_ndt_cells: asymmetric covariance");
-    const double r[kNdtRecord] = {means[2 * j], means[2 * j + 1], c[0], c[1], c[3], 0.0};
-    std::copy(r, r + kNdtRecord, recs.begin() + static_cast<ptrdiff_t>(j * kNdtRecord));
+    ndt_pack_record(means + 2 * j, c, recs.data() + j * kNdtRecord);
   }
   if (const mcl_status s = bind_device(ctx)) return s;
-  return do_reweight(ctx, recs.data(), recs.size() / 2);
+  return do_reweight(ctx, Measurement{recs.data(), recs.size()});
 }
 
 mcl_status mcl_build_ndt_map_from_points(mcl_ctx* ctx, const double* points_xy, uint64_t n, double resolution) {
@@ -3876,155 +3670,74 @@ mcl_status mcl_get_ndt_map(mcl_ctx* ctx, int32_t* cells_out, double* means_out, 
   std::vector<double> recs(static_cast<size_t>(k) * kNdtRecord);
   MCL_HIP(ctx, hipMemcpy(cells_out, ctx->d_ndt_keys.ptr, static_cast<size_t>(2 * k) * sizeof(int32_t), hipMemcpyDeviceToHost));
   MCL_HIP(ctx, hipMemcpy(recs.data(), ctx->d_ndt_cells.ptr, recs.size() * sizeof(double), hipMemcpyDeviceToHost));
-  for (uint64_t j = 0; j < k; ++j) {
-    const double* r = recs.data() + j * kNdtRecord;
-    means_out[2 * j] = r[0];
-    means_out[2 * j + 1] = r[1];
-    covariances_out[4 * j] = r[2];
-    covariances_out[4 * j + 1] = r[3];
-    covariances_out[4 * j + 2] = r[3];
-    covariances_out[4 * j + 3] = r[4];
-  }
+  for (uint64_t j = 0; j < k; ++j) ndt_unpack_record(recs.data() + j * kNdtRecord, means_out + 2 * j, covariances_out + 4 * j);
   return MCL_OK;
 }
 
 // ---- Landmark and bearing sensor models ----------------------------------------------------------------------------------------
-void mcl_default_landmark_params(mcl_landmark_params* params) {
-  if (!params) return;
-  *params = mcl_landmark_params{1.0, 1.0, 1e-4};  // LandmarkModelParam (landmark_sensor_model.hpp:44-48)
-}
-
-void mcl_default_bearing_params(mcl_bearing_params* params) {
-  if (!params) return;
-  *params = mcl_bearing_params{1.0, {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0}};  // BearingModelParam (bearing_sensor_model.hpp:42-45)
-}
-
 mcl_status mcl_set_landmark_map(mcl_ctx* ctx, const double* positions_xyz, const uint32_t* categories, uint64_t n, const double boundaries[6],
                                 const void* params) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (!ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_landmark_map: the context's sensor model is not MCL_SENSOR_LANDMARK or MCL_SENSOR_BEARING");
-  MCL_REQUIRE(ctx, n == 0 || (positions_xyz && categories), "mcl_set_landmark_map: null argument");
-  MCL_REQUIRE(ctx, n < (1ull << 31), "mcl_set_landmark_map: too many landmarks");
-  MCL_REQUIRE(ctx, n > 0 || boundaries, "mcl_set_landmark_map: an empty map needs explicit boundaries");
-  for (uint64_t i = 0; i < 3 * n; ++i)
-    MCL_REQUIRE(ctx, std::isfinite(positions_xyz[i]), "mcl_set_landmark_map: landmark " + std::to_string(i / 3) + " has a value that is not finite");
-  LandmarkMapView v{};
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_LANDMARK) {
-    mcl_landmark_params prm;
-    if (params) prm = *static_cast<const mcl_landmark_params*>(params);
-    else mcl_default_landmark_params(&prm);
-    MCL_REQUIRE(ctx, std::isfinite(prm.sigma_range) && prm.sigma_range > 0.0 && std::isfinite(prm.sigma_bearing) && prm.sigma_bearing > 0.0,
-                "mcl_set_landmark_map: sigma_range and sigma_bearing must be positive and finite");
-    MCL_REQUIRE(ctx, std::isfinite(prm.random_prob), "mcl_set_landmark_map: random_prob must be finite");
-    v.den_range = (2. * prm.sigma_range) * prm.sigma_range;  // landmark_sensor_model.hpp:147
-    v.den_bearing = (2. * prm.sigma_bearing) * prm.sigma_bearing;
-    v.random_prob = prm.random_prob;
-  } else {
-    mcl_bearing_params prm;
-    if (params) prm = *static_cast<const mcl_bearing_params*>(params);
-    else mcl_default_bearing_params(&prm);
-    MCL_REQUIRE(ctx, std::isfinite(prm.sigma_bearing) && prm.sigma_bearing > 0.0, "mcl_set_landmark_map: sigma_bearing must be positive and finite");
-    const double* q = prm.sensor_pose_in_robot;
-    for (int k = 0; k < 7; ++k) MCL_REQUIRE(ctx, std::isfinite(q[k]), "mcl_set_landmark_map: sensor_pose_in_robot must be finite");
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    MCL_REQUIRE(ctx, std::abs(std::sqrt(x * x + y * y + z * z + w * w) - 1.0) <= 1e-9, "mcl_set_landmark_map: sensor_pose_in_robot's quaternion is not of unit length");
-    v.den_bearing = (2. * prm.sigma_bearing) * prm.sigma_bearing;  // bearing_sensor_model.hpp:134
-    // Eigen's Quaternion::toRotationMatrix
-    const double tx = 2. * x, ty = 2. * y, tz = 2. * z;
-    const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    const double R[9] = {1. - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1. - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1. - (txx + tyy)};
-    std::copy(R, R + 9, v.Rs);
-    std::copy(q + 4, q + 7, v.ts);
-  }
-  double lo[3], hi[3];
-  if (boundaries) {
-    for (int k = 0; k < 6; ++k) MCL_REQUIRE(ctx, std::isfinite(boundaries[k]), "mcl_set_landmark_map: the boundaries must be finite");
-    std::copy(boundaries, boundaries + 3, lo);
-    std::copy(boundaries + 3, boundaries + 6, hi);
-    MCL_REQUIRE(ctx, lo[0] <= hi[0] && lo[1] <= hi[1], "mcl_set_landmark_map: boundaries with min > max");
-  } else {  // LandmarkMap(landmarks) (landmark_map.hpp:61-71): the landmarks' bounding box
-    for (int k = 0; k < 3; ++k) lo[k] = hi[k] = positions_xyz[k];
-    for (uint64_t i = 1; i < n; ++i)
-      for (int k = 0; k < 3; ++k) {
-        lo[k] = std::min(lo[k], positions_xyz[3 * i + k]);
-        hi[k] = std::max(hi[k], positions_xyz[3 * i + k]);
-      }
-  }
-  // grouped by category, the map's order kept inside a category (std::min_element returns the first of equal candidates)
-  std::vector<uint32_t> order(n);
-  for (uint64_t i = 0; i < n; ++i) order[i] = static_cast<uint32_t>(i);
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return categories[a] < categories[b]; });
-  std::vector<double> recs(static_cast<size_t>(n) * 4, 0.0);
-  std::map<uint32_t, std::pair<uint32_t, uint32_t>> ranges;
-  for (uint64_t i = 0; i < n; ++i) {
-    std::copy(positions_xyz + 3 * order[i], positions_xyz + 3 * order[i] + 3, recs.begin() + static_cast<ptrdiff_t>(4 * i));
-    auto it = ranges.find(categories[order[i]]);
-    if (it == ranges.end()) ranges[categories[order[i]]] = {static_cast<uint32_t>(i), 1u};
-    else it->second.second += 1;
-  }
+  LandmarkMapLayout map;
+  std::string error;
+  if (const mcl_status s = landmark_layout_map(ctx->cfg.sensor_kind, positions_xyz, categories, n, boundaries, params, &map, &error))
+    return fail(ctx, s, error);
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a reweight in flight may still read the old map)
   ctx->have_landmark_map = false;
   if (n) {
-    MCL_HIP(ctx, ctx->d_landmarks.ensure(recs.size()));
-    MCL_HIP(ctx, hipMemcpy(ctx->d_landmarks.ptr, recs.data(), recs.size() * sizeof(double), hipMemcpyHostToDevice));
+    MCL_HIP(ctx, ctx->d_landmarks.ensure(map.landmarks.size()));
+    MCL_HIP(ctx, hipMemcpy(ctx->d_landmarks.ptr, map.landmarks.data(), map.landmarks.size() * sizeof(double), hipMemcpyHostToDevice));
   }
+  LandmarkMapView v{};
   v.landmarks = ctx->d_landmarks.ptr;
   v.count = static_cast<uint32_t>(n);
+  v.den_range = map.den_range;
+  v.den_bearing = map.den_bearing;
+  v.random_prob = map.random_prob;
+  std::copy(map.Rs, map.Rs + 9, v.Rs);
+  std::copy(map.ts, map.ts + 3, v.ts);
   ctx->landmark_view = v;
-  ctx->landmark_ranges = std::move(ranges);
+  ctx->landmark_ranges = std::move(map.ranges);
   FreeCells box{nullptr, 1};
   box.box = 1;
-  box.box_min[0] = lo[0];
-  box.box_min[1] = lo[1];
-  box.box_extent[0] = hi[0] - lo[0];
-  box.box_extent[1] = hi[1] - lo[1];
+  box.box_min[0] = map.lo[0];
+  box.box_min[1] = map.lo[1];
+  box.box_extent[0] = map.hi[0] - map.lo[0];
+  box.box_extent[1] = map.hi[1] - map.lo[1];
   ctx->landmark_random = box;
   ctx->have_landmark_map = true;
   return MCL_OK;
 }
 
-// The detection records of a call (kernels.h, kLandmarkRecord): what does not depend on the particle - the norm, the normalized vector and
-// the category's range - is computed here, once.  The bearing model's detections are sorted by category (stable), each with its place in
-// the caller's order.  Everything is checked before the device is touched.
-static mcl_status landmark_records(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n) {
+// The detection records of a call (landmark_records, landmark_host.cpp) into h_landmark_meas.  Everything is checked before the device
+// is touched.
+static mcl_status landmark_measurement(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n,
+                                       Measurement* m) {
   if (ctx->cfg.sensor_kind != kind)
     return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the context's sensor model is not " + (kind == MCL_SENSOR_LANDMARK ? "MCL_SENSOR_LANDMARK" : "MCL_SENSOR_BEARING"));
-  MCL_REQUIRE(ctx, n == 0 || (xyz && categories), std::string(who) + ": null argument");
-  MCL_REQUIRE(ctx, n <= MCL_LANDMARK_MAX_DETECTIONS, std::string(who) + ": more than MCL_LANDMARK_MAX_DETECTIONS detections");
-  for (uint64_t i = 0; i < 3 * n; ++i) MCL_REQUIRE(ctx, std::isfinite(xyz[i]), std::string(who) + ": a detection has a value that is not finite");
-  if (!ctx->have_landmark_map) return fail(ctx, MCL_ERR_NOT_READY, std::string(who) + ": no landmark map set (mcl_set_landmark_map)");
-  std::vector<uint32_t> order(n);
-  for (uint64_t i = 0; i < n; ++i) order[i] = static_cast<uint32_t>(i);
-  if (kind == MCL_SENSOR_BEARING) std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return categories[a] < categories[b]; });
-  std::vector<double>& recs = ctx->h_landmark_meas;
-  recs.assign(static_cast<size_t>(n) * kLandmarkRecord, 0.0);
-  for (uint64_t i = 0; i < n; ++i) {
-    const double* d = xyz + 3 * order[i];
-    double* r = recs.data() + i * kLandmarkRecord;
-    const double n2 = d[0] * d[0] + (d[1] * d[1] + d[2] * d[2]);
-    const double norm = std::sqrt(n2);
-    r[0] = d[0], r[1] = d[1], r[2] = d[2], r[3] = norm;
-    for (int k = 0; k < 3; ++k) r[4 + k] = n2 > 0.0 ? d[k] / norm : d[k];  // Eigen's normalized()
-    const auto it = ctx->landmark_ranges.find(categories[order[i]]);
-    const uint32_t packed[4] = {it == ctx->landmark_ranges.end() ? 0xFFFFFFFFu : it->second.first,
-                                it == ctx->landmark_ranges.end() ? 0u : it->second.second, order[i], 0u};
-    std::memcpy(r + 7, packed, sizeof(packed));
-  }
+  std::string error;
+  if (const mcl_status s = landmark_records(who, kind, xyz, categories, n, ctx->have_landmark_map ? &ctx->landmark_ranges : nullptr,
+                                            ctx->h_landmark_meas, &error))
+    return fail(ctx, s, error);
+  *m = Measurement{ctx->h_landmark_meas.data(), ctx->h_landmark_meas.size()};
   return MCL_OK;
 }
 
 static mcl_status landmark_reweight(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (const mcl_status s = landmark_records(ctx, who, kind, xyz, categories, n)) return s;
+  Measurement m{};
+  if (const mcl_status s = landmark_measurement(ctx, who, kind, xyz, categories, n, &m)) return s;
   if (const mcl_status s = bind_device(ctx)) return s;
-  return do_reweight(ctx, ctx->h_landmark_meas.data(), ctx->h_landmark_meas.size() / 2);
+  return do_reweight(ctx, m);
 }
 static mcl_status landmark_update(mcl_ctx* ctx, const char* who, int32_t kind, const double control_pose[4], const double* xyz,
                                   const uint32_t* categories, uint64_t n, mcl_estimate* estimate, mcl_update_info* info) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (const mcl_status s = landmark_records(ctx, who, kind, xyz, categories, n)) return s;
-  return update_cycle(ctx, control_pose, ctx->h_landmark_meas.data(), ctx->h_landmark_meas.size() / 2, estimate, info);
+  Measurement m{};
+  if (const mcl_status s = landmark_measurement(ctx, who, kind, xyz, categories, n, &m)) return s;
+  return update_cycle(ctx, control_pose, m, estimate, info);
 }
 
 mcl_status mcl_reweight_landmarks(mcl_ctx* ctx, const double* positions_xyz, const uint32_t* categories, uint64_t n) {

@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "se2.h"
+#include "sensor_records.h"
 
 namespace mcl {
 
@@ -115,7 +116,6 @@ struct FreeCells {
 // measurement cell whose centre key lies farther than `reach` from the keys' box has no neighbour in the map (one test); any other
 // centre key's offsets stay inside the grid (no per-offset test).
 constexpr int kNdtMaxOffsets = 32;
-constexpr int kNdtRecord = 6;  // doubles per cell record: mean x, y, covariance xx, xy, yy, 0
 struct NdtMapView {
   const int32_t* grid;  // gw x gh, row-major
   const double* cells;  // kNdtRecord doubles per map cell
@@ -132,7 +132,7 @@ struct NdtMapView {
 // base frame) of max(sum of the present neighbours' d1 exp(-d2/2 e^T (S' + S_map)^-1 e), minimum_likelihood).  A lane per particle.
 void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k);
 
-// The NDT map built on the device (ndt_build_kernels.hip): detail::to_cells with fit_points over n points, as ndt_fit_cells (context.hip)
+// The NDT map built on the device (ndt_build_kernels.hip): detail::to_cells with fit_points over n points, as ndt_fit_cells (ndt_host.cpp)
 // does on the host - keys by truncation toward zero, cells of 5 points or more in ascending (x, y) key order, a cell's sums taken in
 // input order.  Every launcher takes n > 0 points (n < 2^31), x and y interleaved.
 struct NdtBuildScratch {
@@ -176,10 +176,9 @@ void launch_ndt_grid_points(hipStream_t st, const int8_t* cells, uint32_t W, uin
 
 // The landmark and bearing models' map and measurement (landmark_kernels.hip).  The landmarks are grouped by category on the host with
 // a stable sort (map order inside a category: std::min_element's "first of equal" holds), 4 doubles each (x, y, z, 0).  A detection is
-// kLandmarkRecord doubles: the vector as given (x, y, z), its norm, its normalized() (x, y, z), then three uint32 in the place of
+// kLandmarkRecord (10) doubles: the vector as given (x, y, z), its norm, its normalized() (x, y, z), then three uint32 in the place of
 // doubles 7 and 8: first and count of its category's landmarks (count 0 = no landmark of that category, first = 0xFFFFFFFF) and the
 // detection's place in the caller's order.
-constexpr int kLandmarkRecord = 10;
 constexpr int kLandmarkMaxDetections = 64;  // MCL_LANDMARK_MAX_DETECTIONS
 struct LandmarkMapView {
   const double* landmarks;  // 4 doubles per landmark, grouped by category
