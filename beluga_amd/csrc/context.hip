@@ -30,6 +30,7 @@
 #include "landmark_host.h"
 #include "map_build.h"
 #include "ndt_host.h"
+#include "set_facts.h"
 
 namespace {
 
@@ -254,26 +255,14 @@ struct mcl_ctx {
   DeviceBuffer<double> d_cdf_tree;  // sampled levels of the 16-ary search tree over d_cdf (CdfTree)
   DeviceBuffer<unsigned long long> d_scan_state;  // k_normalize_cdf: ticket word + the chunk sums' granules (kScanStateWords, zeroed once)
   uint32_t scan_epoch{0};           // of the last k_normalize_cdf launch on that state
-  DeviceBuffer<double> d_lf_wsum;   // sums of the new weights per workgroup of the LF patch kernel (PatchStats::weight_sums)
-  uint32_t lf_wsum_count{0};        // how many the last reweight left (0: none; consumed by the normalisation right behind it)
-  // k_noise_ahead: the propagation normals of step `noise_step` for the particles [noise_offset, noise_offset + noise_n) of the global index
-  // space, drawn behind the previous cycle (they depend on nothing else: any set of that size at that step may use them)
-  DeviceBuffer<double> d_noise;
-  uint32_t noise_step{0};
-  uint64_t noise_n{0}, noise_offset{0}, noise_seed{0};
-  // launch_order_ahead: the spatial order (sort_scratch().perm) of the particles as the propagation of step `order_step` will leave them, if the
-  // control action of that step is the predicted one (order_sampler); the frame it was computed in
-  bool order_valid{false};
-  uint32_t order_step{0};
-  uint64_t order_n{0};
+  SetFacts facts;                   // what the host knows about the live set, and every event that changes it (set_facts.h)
+  DeviceBuffer<double> d_lf_wsum;   // sums of the new weights per workgroup of the LF patch kernel (PatchStats::weight_sums; facts.lf_sums() of them)
+  DeviceBuffer<double> d_noise;     // k_noise_ahead: the propagation normals drawn behind the previous cycle (facts.noise_ahead_serves)
+  // launch_order_ahead: the spatial order (sort_scratch().perm) that facts.take_order_ahead answers for holds if the control action of that
+  // step is the predicted one
   DiffDriveSampler order_sampler{};
-  uint32_t order_layout{0};
-  bool order_ready{false};      // this cycle's propagation found it usable: do_reweight skips the ordering passes
   uint64_t order_ahead_used{0}, order_ahead_missed{0};
   DiffDriveSampler last_sampler{};  // of the last propagation (the prediction for the next one)
-  bool cdf_divides{false};          // the last normalisation left the weights undivided: the CDF kernel right behind it divides (do_normalize)
-  bool weights_unit{false};         // every weight of the live set is exactly 1.0: set by what writes them all (initialisation, resampling,
-                                    // particle_traits.hpp:105), cleared by whatever else touches a weight
   CdfTree cdf_tree() const { return make_cdf_tree(d_cdf.ptr, d_cdf_tree.ptr, n); }
   // mcl_set_map_async: the next map, its likelihood field being built on a worker thread (state 1) or built and waiting for its swap (2)
   struct PendingMap {
@@ -1086,27 +1075,25 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
   if (keys_emitted) decide_lf_mode(ctx);  // the fused cycle: the reweight follows, and the keys depend on its kernel
   // The order the previous cycle computed AHEAD for this step (launch_order_ahead) serves if the control action it predicted is close to the
   // one that came: then no keys, no ordering passes - the reweight follows the propagation at once.  Only locality depends on it.
-  ctx->order_ready = false;
+  ctx->facts.order_accepted(false);
   bool use_ahead = false;
-  if (keys_emitted && ctx->order_valid) {
-    ctx->order_valid = false;
-    use_ahead = ctx->tuning.order_ahead != 0 && ctx->order_step == step && ctx->order_n == ctx->n && wants_ordering(ctx) &&
-                ctx->order_layout == key_layout(ctx) && samplers_close(sampler, ctx->order_sampler);
+  if (keys_emitted) {
+    const SetFacts::OrderTaken ahead = ctx->facts.take_order_ahead(step, ctx->n, key_layout(ctx));
+    use_ahead = ahead.matched && ctx->tuning.order_ahead != 0 && wants_ordering(ctx) && samplers_close(sampler, ctx->order_sampler);
     if (use_ahead) ctx->order_ahead_used += 1;
-    else ctx->order_ahead_missed += 1;
+    else if (ahead.recorded) ctx->order_ahead_missed += 1;
   }
   ctx->last_sampler = sampler;
   const bool keys = !use_ahead && keys_emitted && wants_ordering(ctx) && predict_key_frame(ctx, &sampler, &frame);
   // (the normals of this step, if the previous cycle left them: k_noise_ahead)
-  const bool ahead = ctx->d_noise.ptr && ctx->noise_n >= ctx->n && ctx->n > 65536 && ctx->noise_step == step && ctx->noise_seed == ctx->cfg.seed &&
-                     ctx->noise_offset == ctx->cfg.shard_offset;
+  const bool ahead = ctx->d_noise.ptr && ctx->n > 65536 && ctx->facts.noise_ahead_serves(step, ctx->n, ctx->cfg.seed, ctx->cfg.shard_offset);
   launch_propagate(ctx->stream, ctx->cur(), ctx->n, sampler, ctx->cfg.seed, step, ctx->cfg.shard_offset,
                    scan_doubles ? ctx->hd_points : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
-                   keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->noise_n);
+                   keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->facts.noise_ahead_count());
   if (ahead) ctx->noise_ahead_used += 1;
   if (scan_doubles) points_pulled(ctx, false);
   if (keys_emitted) *keys_emitted = keys;
-  ctx->order_ready = use_ahead;
+  ctx->facts.order_accepted(use_ahead);
   stage_end(ctx, MCL_STAGE_PROPAGATE);
   MCL_HIP(ctx, hipGetLastError());
   return MCL_OK;
@@ -1133,14 +1120,13 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
 
 // points_staged: stage_points + the pull already happened (mcl_update); keys_ready: k_propagate emitted the ordering keys.
 // want_weight_sums: the normalisation follows at once (mcl_update): the LF patch kernel leaves the sums of its workgroups' new
-// weights in d_lf_wsum (ctx->lf_wsum_count of them; 0 if another kernel ran).
+// weights in d_lf_wsum (facts.lf_sums() of them; 0 if another kernel ran).
 mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = false, bool keys_ready = false,
                        bool want_weight_sums = false) {
-  ctx->lf_wsum_count = 0;
+  ctx->facts.lf_sums_dropped();
   const uint64_t B = ctx->off_grid() ? 0 : m.doubles / 2;  // the grid models' measurement is the scan itself: B points
   if (const mcl_status s = reweight_preconditions(ctx, B)) return s;
-  const bool unit_weights = ctx->weights_unit && ctx->tuning.lf_unit_weights != 0;
-  ctx->weights_unit = false;
+  const bool unit_weights = ctx->facts.take_unit_weights() && ctx->tuning.lf_unit_weights != 0;
   if (!points_staged) {
     if (const mcl_status s = stage_points(ctx, m)) return s;
     if (m.doubles) {
@@ -1154,9 +1140,8 @@ mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = 
   const bool ordered = wants_ordering(ctx);  // (asked while this cycle's mode is decided)
   ctx->lf_mode.decided = false;              // the next cycle decides again
   const SortScratch sort = ctx->sort_scratch();
-  const bool order_ready = ctx->order_ready;  // (launch_order_ahead's, accepted by this cycle's propagation)
-  ctx->order_ready = false;
-  if (ordered && !order_ready) {
+  const bool have_order = ctx->facts.take_order_accepted();  // (launch_order_ahead's, accepted by this cycle's propagation)
+  if (ordered && !have_order) {
     KeyFrame frame{};
     // The ordering also serves the beam model: both kernels gather the pose records through sort.perm.
     const bool have_frame = !keys_ready && predict_key_frame(ctx, nullptr, &frame);
@@ -1186,7 +1171,7 @@ mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = 
                                            static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
                                            reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)}},
         ctx->tuning);
-    ctx->lf_wsum_count = launched.weight_sums;
+    ctx->facts.lf_sums_left(launched.weight_sums);
     switch (launched.kernel) {  // (the counters as include/beluga_mcl.h states them)
       case LfKernel::kPatchQueue: ctx->lf_queue_launches += 1; [[fallthrough]];
       case LfKernel::kPatch: ctx->lf_patch_launches += 1; ctx->lf_fast_launches += 1; break;
@@ -1223,7 +1208,7 @@ mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = 
   stage_end(ctx, MCL_STAGE_REWEIGHT);
   ctx->profile_tick += 1;
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
-    ctx->lf_wsum_count = 0;  // (sums that no longer describe the weights must not reach a later normalisation)
+    ctx->facts.lf_sums_dropped();  // (sums that no longer describe the weights must not reach a later normalisation)
     return fail(ctx, MCL_ERR_HIP, std::string("reweight: ") + hipGetErrorString(e));
   }
   return MCL_OK;
@@ -1250,18 +1235,18 @@ mcl_status mirrored_estimate(const mcl_ctx* ctx, mcl_estimate* out) {
 // finalize == false (only with factor = NaN and read_back == false): the totals of the normalised weights are left to the next kernel
 // (do_build_cdf with a policy, or launch_norm_finalize).
 // store_weights == false (mcl_update, a resampling follows at once): the normalised weights are not stored; do_build_cdf has to divide
-// (ctx->cdf_divides tells it).
+// (facts.take_cdf_divides tells it).
 struct NormalizeOptions { bool read_back = true, finalize = true, store_weights = true; };
 mcl_status do_normalize(mcl_ctx* ctx, double factor, mcl_weight_stats* stats, const NormalizeOptions& opt = {}) {
-  ctx->weights_unit = false;
-  ctx->cdf_divides = false;
+  ctx->facts.weights_touched();
+  ctx->facts.weights_left_undivided(false);
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
   if (std::isnan(factor)) {  // by the set's own total
     launch_sum_and_normalize(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->chunk_row(1), ctx->chunk_row(2),
                              ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum, opt.finalize,
-                             ctx->lf_wsum_count ? ctx->d_lf_wsum.ptr : nullptr, ctx->lf_wsum_count, opt.store_weights);
-    ctx->cdf_divides = !opt.store_weights;
-    ctx->lf_wsum_count = 0;  // (they described the weights as the reweight left them)
+                             ctx->facts.lf_sums() ? ctx->d_lf_wsum.ptr : nullptr, ctx->facts.lf_sums(), opt.store_weights);
+    ctx->facts.weights_left_undivided(!opt.store_weights);
+    ctx->facts.lf_sums_dropped();  // (they described the weights as the reweight left them)
   } else {
     launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum);
     ctx->h_scalars[kSlotFactor] = factor;
@@ -1286,14 +1271,14 @@ mcl_status do_normalize(mcl_ctx* ctx, double factor, mcl_weight_stats* stats, co
 mcl_status do_normalize_cdf(mcl_ctx* ctx, const RecoveryPolicy& policy, bool* done) {
   *done = false;
   if (ctx->tuning.scan_fused == 0 || !ctx->d_scan_state.ptr || (ctx->tuning.scan_fused == 1 && ctx->n > 65536)) return MCL_OK;
-  ctx->weights_unit = false;
+  ctx->facts.weights_touched();
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
   if (++ctx->scan_epoch == 0) ctx->scan_epoch = 1;
-  *done = launch_normalize_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->lf_wsum_count ? ctx->d_lf_wsum.ptr : nullptr,
-                               ctx->lf_wsum_count, ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum, ctx->chunk_row(1),
+  *done = launch_normalize_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->facts.lf_sums() ? ctx->d_lf_wsum.ptr : nullptr,
+                               ctx->facts.lf_sums(), ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum, ctx->chunk_row(1),
                                ctx->chunk_row(2), /*write_weights=*/false, ctx->d_cdf.ptr, ctx->d_scalars.ptr + kSlotCdfTotal, ctx->d_cdf_tree.ptr,
                                &policy, ctx->d_scan_state.ptr, ctx->scan_epoch);
-  if (*done) ctx->lf_wsum_count = 0;
+  if (*done) ctx->facts.lf_sums_dropped();
   stage_end(ctx, MCL_STAGE_NORMALIZE);
   MCL_HIP(ctx, hipGetLastError());
   return MCL_OK;
@@ -1304,11 +1289,11 @@ mcl_status do_normalize_cdf(mcl_ctx* ctx, const RecoveryPolicy& policy, bool* do
 // workgroup also finishes the normalisation's totals (kSlotNormSum, kSlotNormSumSq) and runs the recovery estimator.
 mcl_status do_build_cdf(mcl_ctx* ctx, bool normalized_just_now = false, const RecoveryPolicy* policy = nullptr,
                         bool finalize_norm = false) {
+  const bool divides = ctx->facts.take_cdf_divides();
   launch_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(3), ctx->chunk_row(4), ctx->d_cdf.ptr, ctx->d_scalars.ptr + kSlotCdfTotal,
              ctx->d_cdf_tree.ptr, normalized_just_now ? ctx->chunk_row(1) : nullptr, finalize_norm ? ctx->chunk_row(2) : nullptr,
              finalize_norm ? ctx->d_scalars.ptr + kSlotNormSum : nullptr, finalize_norm ? ctx->hd_scalars + kSlotNormSum : nullptr, policy,
-             (normalized_just_now && ctx->cdf_divides) ? ctx->d_scalars.ptr + kSlotWeightSum : nullptr);
-  ctx->cdf_divides = false;
+             (normalized_just_now && divides) ? ctx->d_scalars.ptr + kSlotWeightSum : nullptr);
   MCL_HIP(ctx, hipGetLastError());
   return MCL_OK;
 }
@@ -1363,7 +1348,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       if (const mcl_status s = prepare_ndt_random(ctx, random_state_probability)) return s;
     ctx->ndt_random_ready = false;  // (used by this draw only)
   }
-  ctx->lf_wsum_count = 0;  // (the set changes: workgroup sums of an earlier reweight describe another one)
+  ctx->facts.lf_sums_dropped();
   const uint64_t max_p = std::min<uint64_t>(a.max_particles, ctx->capacity);
   stage_begin(ctx, MCL_STAGE_RESAMPLE);
   if (!opt.cdf_ready)
@@ -1421,20 +1406,12 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
                                         noise_in_draw ? ctx->d_noise.ptr : nullptr, max_p, ctx->cfg.shard_offset, step + 1,
                                         order_keys ? ctx->sort_scratch().keys : nullptr, &ctx->last_sampler, &ahead_frame);
       if (noise_ahead) launch_noise_ahead(ctx->stream, ctx->cfg.seed, step + 1, ctx->cfg.shard_offset, max_p, ctx->d_noise.ptr);
-      if (noise_ahead || noise_in_draw) {
-        ctx->noise_step = step + 1;
-        ctx->noise_n = max_p;
-        ctx->noise_offset = ctx->cfg.shard_offset;
-        ctx->noise_seed = ctx->cfg.seed;
-      }
+      if (noise_ahead || noise_in_draw) ctx->facts.noise_ahead_recorded(step + 1, max_p, ctx->cfg.shard_offset, ctx->cfg.seed);
       if (order_keys) {
         const SortScratch sort = ctx->sort_scratch();
         launch_order_ahead(ctx->stream, max_p, &sort);
-        ctx->order_valid = true;
-        ctx->order_step = step + 1;
-        ctx->order_n = max_p;
+        ctx->facts.order_ahead_recorded(step + 1, max_p, key_layout(ctx));
         ctx->order_sampler = ctx->last_sampler;
-        ctx->order_layout = key_layout(ctx);
       }
       if (opt.estimate_enqueued) *opt.estimate_enqueued = true;
     } else {
@@ -1466,7 +1443,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
   stage_end(ctx, MCL_STAGE_RESAMPLE);
   ctx->live ^= 1;
   ctx->n = result;
-  ctx->weights_unit = true;  // particle_traits.hpp:105: the draw kernel wrote 1.0 to every weight of the new set
+  ctx->facts.resampled_set_committed();
   if (n_out) *n_out = result;
   return MCL_OK;
 }
@@ -2133,7 +2110,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const Measurement& sc
       MCL_HIP(ctx, hipGetLastError());
       ctx->live ^= 1;
       ctx->n = m;
-      ctx->weights_unit = true;  // (every output slot took a weight of 1.0: particle_traits.hpp:105)
+      ctx->facts.resampled_set_committed();
       return MCL_OK;
     };
     if (fires) {
@@ -2165,7 +2142,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const Measurement& sc
         // it, the exchange again with exact counts, the estimate again.
         ctx->comm_overflows += 1;
         ctx->live ^= 1;
-        ctx->weights_unit = false;  // (the old set again: normalised weights)
+        ctx->facts.commit_rolled_back();
         stage_end(ctx, MCL_STAGE_ESTIMATE);  // (one stage open at a time: the retry's resampling is timed as resampling)
         stage_begin(ctx, MCL_STAGE_RESAMPLE);
         mcl_status retry = sharded_draw(ctx, 0.0, 0.0, d_intervals, first_slot, m, d_plan);
@@ -2659,6 +2636,40 @@ mcl_status set_map_impl(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint3
   ctx->have_map = true;
   return MCL_OK;
 }
+
+// The host side of installing a set that an entry point has just written into cur(): what each caller sets, and what it leaves as it was.
+struct InstallSet {
+  uint64_t n;
+  bool unit_weights;  // every weight of the new set is exactly 1.0
+  // the logical filter over all shards: as it was / every rank holds its share of max_particles again / a shard loaded by the caller: the
+  // ranks compare counts first
+  enum { kGlobalKept, kGlobalShares, kGlobalAsked } global;
+  bool force_update;  // (false: as it was)
+  // the estimate behind the ordering keys: as it was / none (a bounding-box pass until the next estimate) / mean and sigma of x, y, theta
+  enum { kCloudKept, kCloudUnknown, kCloudGiven } cloud;
+  double cloud_mean[3], cloud_sigma[3];
+  // the LF patch statistics: as they were / earlier launches' reports are history, the next LF launch finds out / history, and the set is
+  // what the patch kernel would report as dispersed: the first cycle already takes the kernel for dispersed sets
+  enum { kPatchesKept, kPatchesFresh, kPatchesDispersed } patches;
+};
+void install_set(mcl_ctx* ctx, const InstallSet& s) {
+  ctx->facts.set_replaced(s.unit_weights);
+  ctx->n = s.n;
+  if (s.global == InstallSet::kGlobalShares) ctx->global_n = 0;
+  if (s.global != InstallSet::kGlobalKept) ctx->global_n_unknown = s.global == InstallSet::kGlobalAsked && ctx->have_comm && ctx->comm_world > 1;
+  if (s.force_update) ctx->force_update = true;
+  if (s.cloud != InstallSet::kCloudKept) ctx->have_cloud_estimate = s.cloud == InstallSet::kCloudGiven;
+  if (s.cloud == InstallSet::kCloudGiven)
+    for (int k = 0; k < 3; ++k) {
+      ctx->cloud_mean[k] = s.cloud_mean[k];
+      ctx->cloud_sigma[k] = s.cloud_sigma[k];
+    }
+  if (s.patches != InstallSet::kPatchesKept) {
+    patch_totals(ctx, &ctx->patch_seen_planned, &ctx->patch_seen_through);
+    ctx->patch_useful = s.patches == InstallSet::kPatchesFresh;
+    if (s.patches == InstallSet::kPatchesDispersed) ctx->patch_probe_in = 16;
+  }
+}
 }  // namespace
 extern "C" {
 
@@ -2688,36 +2699,25 @@ mcl_status mcl_set_likelihood_field(mcl_ctx* ctx, const float* field) {
 
 mcl_status mcl_initialize_normal(mcl_ctx* ctx, const double mean_xytheta[3], const double cov[9]) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  ctx->lf_wsum_count = 0;  // (workgroup sums of an earlier reweight describe another set)
-  ctx->order_valid = false;  // (and an order computed ahead describes the particles of another one)
+  ctx->facts.set_changes();
   MCL_REQUIRE(ctx, mean_xytheta && cov, "null argument");
   double T[9];
   if (!covariance_to_transform(cov, T)) return fail(ctx, MCL_ERR_BAD_COVARIANCE, "Invalid covariance matrix");
   if (const mcl_status s = bind_device(ctx)) return s;
   const uint64_t n = std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity);  // take_exactly(max_particles)
-  ctx->weights_unit = false;
+  ctx->facts.weights_rewrite_begins();
   launch_init_normal(ctx->stream, ctx->cur(), n, mean_xytheta, T, ctx->cfg.seed, ctx->cfg.shard_offset);
   MCL_HIP(ctx, hipGetLastError());
-  ctx->weights_unit = true;  // (k_init_normal writes 1.0 to every weight)
-  ctx->n = n;
-  ctx->global_n = 0;  // (shards: every rank holds its share of max_particles again)
-  ctx->global_n_unknown = false;
-  ctx->force_update = true;  // amcl_core.hpp:136
-  for (int k = 0; k < 3; ++k) {
-    ctx->cloud_mean[k] = mean_xytheta[k];
-    ctx->cloud_sigma[k] = std::sqrt(std::max(cov[4 * k], 0.0));
-  }
-  ctx->have_cloud_estimate = true;
-  // a new set: whatever earlier launches reported about the old one is history; the next LF launch finds out
-  patch_totals(ctx, &ctx->patch_seen_planned, &ctx->patch_seen_through);
-  ctx->patch_useful = true;
+  install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalShares, .force_update = true /* amcl_core.hpp:136 */,
+                    .cloud = InstallSet::kCloudGiven, .cloud_mean = {mean_xytheta[0], mean_xytheta[1], mean_xytheta[2]},
+                    .cloud_sigma = {std::sqrt(std::max(cov[0], 0.0)), std::sqrt(std::max(cov[4], 0.0)), std::sqrt(std::max(cov[8], 0.0))},
+                    .patches = InstallSet::kPatchesFresh});
   return MCL_OK;
 }
 
 mcl_status mcl_set_particles(mcl_ctx* ctx, const double* states, const double* weights, uint64_t n) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  ctx->lf_wsum_count = 0;  // (workgroup sums of an earlier reweight describe another set)
-  ctx->order_valid = false;  // (and an order computed ahead describes the particles of another one)
+  ctx->facts.set_changes();
   MCL_REQUIRE(ctx, n == 0 || (states && weights), "null argument");
   MCL_REQUIRE(ctx, n <= ctx->capacity, "mcl_set_particles: n exceeds capacity");
   if (const mcl_status s = bind_device(ctx)) return s;
@@ -2726,13 +2726,8 @@ mcl_status mcl_set_particles(mcl_ctx* ctx, const double* states, const double* w
     MCL_HIP(ctx, hipMemcpy(ctx->cur().pose, states, n * 4 * sizeof(double), hipMemcpyHostToDevice));  // same record layout
     MCL_HIP(ctx, hipMemcpy(ctx->cur().w, weights, n * sizeof(double), hipMemcpyHostToDevice));
   }
-  ctx->weights_unit = false;
-  ctx->n = n;
-  ctx->global_n_unknown = ctx->have_comm && ctx->comm_world > 1;  // a shard loaded by the caller: the ranks compare notes first
-  ctx->force_update = true;
-  ctx->have_cloud_estimate = false;  // the ordering falls back to a bounding-box pass until the next estimate
-  patch_totals(ctx, &ctx->patch_seen_planned, &ctx->patch_seen_through);  // (as in mcl_initialize_normal)
-  ctx->patch_useful = true;
+  install_set(ctx, {.n = n, .unit_weights = false, .global = InstallSet::kGlobalAsked, .force_update = true, .cloud = InstallSet::kCloudUnknown,
+                    .patches = InstallSet::kPatchesFresh});
   return MCL_OK;
 }
 
@@ -2920,8 +2915,8 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
       ctx->every_n_current = every_n;
       ctx->small_tail_launches += 1;
       MCL_HIP(ctx, hipGetLastError());
-      ctx->lf_wsum_count = 0;
-      ctx->weights_unit = false;
+      ctx->facts.lf_sums_dropped();
+      ctx->facts.weights_touched();
       if (const mcl_status s = wait_for_cycle(ctx)) return s;
       stage_collect(ctx);
       const double* h = ctx->h_scalars;
@@ -2929,7 +2924,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
       if (resampled) {
         ctx->live ^= 1;
         ctx->n = static_cast<uint64_t>(h[kSlotParticles]);
-        ctx->weights_unit = true;  // particle_traits.hpp:105
+        ctx->facts.resampled_set_committed();
       }
       ctx->slow.output = h[kSlotSlow];
       ctx->fast.output = h[kSlotFast];
@@ -3096,7 +3091,7 @@ mcl_status mcl_sample_particle_cloud(mcl_ctx* ctx, uint64_t size, uint32_t draw_
 mcl_status mcl_get_device_view(mcl_ctx* ctx, mcl_device_view* view) {
   if (!ctx || !view) return MCL_ERR_INVALID_ARGUMENT;
   const Particles p = ctx->cur();
-  ctx->weights_unit = false;  // (the caller gets writable pointers)
+  ctx->facts.weights_touched();  // (the caller gets writable pointers)
   view->states = reinterpret_cast<double*>(p.pose);
   view->w = p.w;
   view->cdf = ctx->d_cdf.ptr;
@@ -3108,10 +3103,9 @@ mcl_status mcl_get_device_view(mcl_ctx* ctx, mcl_device_view* view) {
 
 mcl_status mcl_set_num_particles(mcl_ctx* ctx, uint64_t n) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  ctx->lf_wsum_count = 0;  // (workgroup sums of an earlier reweight describe another set)
-  ctx->order_valid = false;  // (and an order computed ahead describes the particles of another one)
+  ctx->facts.set_changes();
   MCL_REQUIRE(ctx, n <= ctx->capacity, "n exceeds capacity");
-  if (n > ctx->n) ctx->weights_unit = false;  // (what lies beyond the set is whatever was there)
+  ctx->facts.set_resized(/*grew=*/n > ctx->n);
   ctx->n = n;
   return MCL_OK;
 }
@@ -3188,7 +3182,7 @@ mcl_status mcl_commit_routed(mcl_ctx* ctx, uint32_t step, uint64_t first_slot, u
   MCL_HIP(ctx, hipGetLastError());
   ctx->live ^= 1;
   ctx->n = count;
-  ctx->weights_unit = true;
+  ctx->facts.resampled_set_committed();
   return MCL_OK;
 }
 
@@ -3232,19 +3226,17 @@ mcl_status mcl_kld_feed(mcl_ctx* ctx, const uint64_t* d_hashes, uint64_t count, 
 
 mcl_status mcl_load_shard(mcl_ctx* ctx, const double* d_states, uint64_t n, uint64_t shard_offset) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  ctx->lf_wsum_count = 0;
-  ctx->order_valid = false;
+  ctx->facts.set_changes();
   MCL_REQUIRE(ctx, n <= ctx->capacity, "n exceeds shard capacity");
   MCL_REQUIRE(ctx, n == 0 || d_states, "null states");
   if (const mcl_status s = bind_device(ctx)) return s;
   if (n) MCL_HIP(ctx, hipMemcpyAsync(ctx->cur().pose, d_states, n * sizeof(double4), hipMemcpyDeviceToDevice, ctx->stream));
-  ctx->weights_unit = false;
+  ctx->facts.weights_rewrite_begins();
   launch_fill(ctx->stream, ctx->cur().w, n, 1.0);  // particle_traits.hpp:105
   MCL_HIP(ctx, hipGetLastError());
-  ctx->weights_unit = true;
-  ctx->n = n;
+  install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalKept, .force_update = false, .cloud = InstallSet::kCloudUnknown,
+                    .patches = InstallSet::kPatchesKept});
   ctx->cfg.shard_offset = shard_offset;
-  ctx->have_cloud_estimate = false;
   return MCL_OK;
 }
 
@@ -3259,7 +3251,7 @@ mcl_status mcl_weight_sum_device(mcl_ctx* ctx, double* d_sum) {
 mcl_status mcl_normalize_device(mcl_ctx* ctx, const double* d_factor, double* d_stats) {
   if (!ctx || !d_factor || !d_stats) return MCL_ERR_INVALID_ARGUMENT;
   if (const mcl_status s = bind_device(ctx)) return s;
-  ctx->weights_unit = false;
+  ctx->facts.weights_touched();
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
   launch_normalize(ctx->stream, ctx->cur().w, ctx->n, d_factor, ctx->chunk_row(1), ctx->chunk_row(2), d_stats);
   stage_end(ctx, MCL_STAGE_NORMALIZE);
@@ -3291,8 +3283,7 @@ mcl_status mcl_estimate_sums_device(mcl_ctx* ctx, const double pivot_xy[2], doub
 
 mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  ctx->lf_wsum_count = 0;  // (workgroup sums of an earlier reweight describe another set)
-  ctx->order_valid = false;  // (and an order computed ahead describes the particles of another one)
+  ctx->facts.set_changes();
   if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_initialize_from_map: not on an NDT context (its map comes from mcl_set_ndt_map)");
   if (ctx->is_landmark()) {  // uniformly over the x-y extent of the map's boundaries: the generator of the recovery's random states, step 0
     if (!ctx->have_landmark_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no landmark map set (mcl_set_landmark_map)");
@@ -3300,26 +3291,18 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
     const uint64_t n = std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity);
     launch_init_from_map(ctx->stream, ctx->cur(), n, ctx->cfg.seed, ctx->cfg.shard_offset, ctx->grid_view(), ctx->landmark_random);
     MCL_HIP(ctx, hipGetLastError());
-    ctx->weights_unit = true;
-    ctx->n = n;
-    ctx->global_n = 0;
-    ctx->global_n_unknown = false;
-    ctx->force_update = true;
+    install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalShares, .force_update = true, .cloud = InstallSet::kCloudKept,
+                      .patches = InstallSet::kPatchesKept});
     return MCL_OK;
   }
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no map set");
   MCL_REQUIRE(ctx, ctx->n_free > 0, "mcl_initialize_from_map: the map has no free cell");  // the reference asserts (:136)
   if (const mcl_status s = bind_device(ctx)) return s;
   const uint64_t n = std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity);  // take_exactly(max_particles)
-  ctx->weights_unit = false;
+  ctx->facts.weights_rewrite_begins();
   launch_init_from_map(ctx->stream, ctx->cur(), n, ctx->cfg.seed, ctx->cfg.shard_offset, ctx->grid_view(),
                        FreeCells{ctx->d_free.ptr, ctx->n_free});
   MCL_HIP(ctx, hipGetLastError());
-  ctx->weights_unit = true;  // (k_init_from_map writes 1.0 to every weight)
-  ctx->n = n;
-  ctx->global_n = 0;
-  ctx->global_n_unknown = false;
-  ctx->force_update = true;  // beluga_ros/include/beluga_ros/amcl.hpp:197
   // the set covers the map: centre of the grid, the spread of a uniform distribution over its extent in the world's axes
   // (extent / sqrt(12)), every heading - what the estimate of such a set would say
   const double hx = 0.5 * ctx->W * ctx->resolution, hy = 0.5 * ctx->H * ctx->resolution;
@@ -3327,18 +3310,10 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
   rot_apply(ctx->origin.r, hx, hy, cx, cy);
   const double ex = 2.0 * (std::abs(ctx->origin.r.c) * hx + std::abs(ctx->origin.r.s) * hy);
   const double ey = 2.0 * (std::abs(ctx->origin.r.s) * hx + std::abs(ctx->origin.r.c) * hy);
-  ctx->cloud_mean[0] = cx + ctx->origin.x;
-  ctx->cloud_mean[1] = cy + ctx->origin.y;
-  ctx->cloud_mean[2] = 0.0;
-  ctx->cloud_sigma[0] = ex / std::sqrt(12.0);
-  ctx->cloud_sigma[1] = ey / std::sqrt(12.0);
-  ctx->cloud_sigma[2] = kPi;
-  ctx->have_cloud_estimate = true;
-  // A set spread over the whole map is what the patch kernel would report as dispersed after its first launch: say so now
-  // (reports of earlier launches are history), so that the first cycle already takes the kernel for dispersed sets.
-  patch_totals(ctx, &ctx->patch_seen_planned, &ctx->patch_seen_through);
-  ctx->patch_useful = false;
-  ctx->patch_probe_in = 16;
+  install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalShares,
+                    .force_update = true /* beluga_ros/include/beluga_ros/amcl.hpp:197 */, .cloud = InstallSet::kCloudGiven,
+                    .cloud_mean = {cx + ctx->origin.x, cy + ctx->origin.y, 0.0}, .cloud_sigma = {ex / std::sqrt(12.0), ey / std::sqrt(12.0), kPi},
+                    .patches = InstallSet::kPatchesDispersed});
   return MCL_OK;
 }
 

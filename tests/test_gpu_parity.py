@@ -1696,6 +1696,51 @@ def test_unit_weights_skip_the_old_weights_load_and_change_nothing(interval):
         assert set(outs[0][0][:, -1]) == {0.0, 1.0}
 
 
+@pytest.mark.parametrize("sequence", ["set_particles", "normalize_shrink_grow", "reweight_normalize", "load_shard"])
+def test_unit_weights_are_not_assumed_of_a_set_changed_between_stage_calls(sequence):
+    """What the library remembers about the weights (set_facts.h) follows every stage-level call that changes them from outside a cycle: a
+    reweight with lf_unit_weights = 1 equals the same sequence with lf_unit_weights = 0 bit for bit, over all weights, whether the set in
+    front of it holds the caller's weights, normalised ones in a set that shrank and grew again, reweighted and normalised ones, or a shard
+    filled with 1.0.  The smallest shape at which the patch kernel - the one that can skip the old weight's load - runs (it did: counter)."""
+    import torch
+    n, small = 32_768, 20_000
+    grid = rooms_grid(200, 3)
+    truth = synth.find_free_pose(grid.cells, grid.resolution, (grid.origin[2], grid.origin[3]), seed=4, clearance_cells=8)
+    pts = make_scan(grid, truth, 64, max_range=12.0)
+    states = synth.normal_particles(n, truth, (0.1, 0.1, 0.03), seed=5)
+    caller_weights = np.random.Generator(np.random.MT19937(6)).uniform(0.25, 4.0, n)
+    cov = np.diag([0.01, 0.01, 0.0009])
+    weights = []
+    for unit in (1, 0):
+        f = new_filter(grid, n, lf_small_particles=0)
+        for k, v in dict(sort_min_particles=0, lf_patch=2, lf_unit_weights=unit).items():
+            f.set_option(k, v)
+        if sequence == "set_particles":
+            f.initialize(truth, cov)
+            f.set_particles(states, caller_weights)
+        elif sequence == "normalize_shrink_grow":
+            f.initialize(truth, cov)
+            f.normalize()
+            f.set_num_particles(small)
+            f.set_num_particles(n)
+        elif sequence == "reweight_normalize":
+            f.initialize(truth, cov)
+            f.reweight(pts)
+            f.normalize()
+        else:
+            d = torch.from_numpy(np.ascontiguousarray(states)).cuda()
+            torch.cuda.synchronize()
+            f.load_shard(d.data_ptr(), n, 0)
+        before = f.counter("lf_patch_launches")
+        f.reweight(pts)
+        assert f.counter("lf_patch_launches") == before + 1
+        assert f.num_particles() == n
+        weights.append(f.particles()[1].copy())
+        f.close()
+    assert np.array_equal(weights[0], weights[1]), (sequence, int((weights[0] != weights[1]).sum()))
+    assert np.all(np.isfinite(weights[0])) and not np.all(weights[0] == weights[0][0])  # (a reweight that did something)
+
+
 @pytest.mark.parametrize("options", [
     dict(lf_split=3, lf_margin=1, key_curve=1),  # the defaults
     dict(lf_split=1), dict(lf_split=2), dict(lf_split=0, lf_margin=0, key_curve=0, key_bits_xy=6),

@@ -20,7 +20,7 @@ if [ -n "$tree" ]; then
   mkdir -p $src
   for f in kernels.hip context.hip kernels.h se2.h rng.h map_build.h map_build.cpp cluster_host.h cluster_host.cpp; do git -C $root show $rev:beluga_amd/csrc/$f > $src/$f; done
   # (translation units and headers that older revisions do not have)
-  for f in beam_kernels.hip device_common.hpp sensor_records.h ndt_host.h ndt_host.cpp landmark_host.h landmark_host.cpp scan_host.cpp; do
+  for f in beam_kernels.hip device_common.hpp sensor_records.h ndt_host.h ndt_host.cpp landmark_host.h landmark_host.cpp scan_host.cpp set_facts.h; do
     git -C $root show $rev:beluga_amd/csrc/$f > $src/$f 2>/dev/null || rm -f $src/$f
   done
   git -C $root show $rev:include/beluga_mcl.h > $src/beluga_mcl.h
