@@ -674,6 +674,29 @@ class Amcl:
         self._check(self._lib.mcl_cluster_based_estimate(self._ctx, C.byref(cp), C.byref(est)))
         return np.array(est.pose), np.array(est.covariance).reshape(3, 3)
 
+    def estimate_clusters(self, linear_hash_resolution=0.20, angular_hash_resolution=0.524, weight_cap_percentile=0.90, max_clusters=64):
+        """beluga::estimate_clusters (algorithm/cluster_based_estimation.hpp:337-399) over ParticleClusterizer's clusters: every
+        hypothesis of the set, not the heaviest alone.  Returns (total, [(id, count, weight, mean, cov), ...]): how many clusters
+        of more than one particle there are, and the heaviest min(max_clusters, 64, total) of them by descending weight (ties by
+        ascending id); the first one is cluster_based_estimate's."""
+        cp = capi.ClusterParams(linear_hash_resolution, angular_hash_resolution, weight_cap_percentile)
+        capacity = max(0, min(int(max_clusters), capi.MCL_MAX_CLUSTER_ESTIMATES))
+        out = (capi.ClusterEstimate * max(capacity, 1))()
+        total = C.c_uint64(0)
+        self._check(self._lib.mcl_estimate_clusters(self._ctx, C.byref(cp), out if capacity else None, capacity, C.byref(total)))
+        found = [(int(e.id), int(e.count), float(e.weight), np.array(e.estimate.pose), np.array(e.estimate.covariance).reshape(3, 3))
+                 for e in out[:min(capacity, total.value)]]
+        return int(total.value), found
+
+    def cluster_labels(self, linear_hash_resolution=0.20, angular_hash_resolution=0.524, weight_cap_percentile=0.90):
+        """ParticleClusterizer::operator() (:269-304): the cluster id of every particle, in particles()' order (np.uint32[n])."""
+        cp = capi.ClusterParams(linear_hash_resolution, angular_hash_resolution, weight_cap_percentile)
+        n = C.c_uint64(0)
+        self._check(self._lib.mcl_num_particles(self._ctx, C.byref(n)))
+        labels = np.empty(n.value, dtype=np.uint32)
+        self._check(self._lib.mcl_cluster_labels(self._ctx, C.byref(cp), labels.ctypes.data_as(capi.c_u32_p)))
+        return labels
+
     def set_estimate_kind(self, cluster_based: bool, **cluster_params):
         """What update() returns: beluga::estimate (beluga::Amcl) or cluster_based_estimate (beluga_ros::Amcl).
         On a sharded filter (comm_attach_rccl) a COLLECTIVE call: every rank makes it, concurrently, with the same arguments."""

@@ -118,6 +118,13 @@ class ClusterParams(C.Structure):
     _fields_ = [("linear_hash_resolution", C.c_double), ("angular_hash_resolution", C.c_double), ("weight_cap_percentile", C.c_double)]
 
 
+MCL_MAX_CLUSTER_ESTIMATES = 64
+
+
+class ClusterEstimate(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("reserved", C.c_uint32), ("count", C.c_uint64), ("weight", C.c_double), ("estimate", Estimate)]
+
+
 class DeviceView(C.Structure):
     _fields_ = [
         ("states", C.c_void_p), ("w", C.c_void_p), ("cdf", C.c_void_p),
@@ -155,6 +162,8 @@ _SIGNATURES = {
     "mcl_estimate_from_sums": (C.c_int32, [c_double_p, C.POINTER(Estimate)]),
     "mcl_estimate_pose": (C.c_int32, [_ctx, C.POINTER(Estimate)]),
     "mcl_cluster_based_estimate": (C.c_int32, [_ctx, C.POINTER(ClusterParams), C.POINTER(Estimate)]),
+    "mcl_estimate_clusters": (C.c_int32, [_ctx, C.POINTER(ClusterParams), C.POINTER(ClusterEstimate), C.c_uint64, c_u64_p]),
+    "mcl_cluster_labels": (C.c_int32, [_ctx, C.POINTER(ClusterParams), c_u32_p]),
     "mcl_set_estimate_kind": (C.c_int32, [_ctx, C.c_int32, C.POINTER(ClusterParams)]),
     "mcl_sample_particle_cloud": (C.c_int32, [_ctx, C.c_uint64, C.c_uint32, c_double_p]),
     "mcl_get_device_view": (C.c_int32, [_ctx, C.POINTER(DeviceView)]),

@@ -118,6 +118,22 @@ ClusterAssignment assign_clusters(const std::vector<ClusterCell>& g, double line
   for (size_t c = 0; c < next_cluster_id; ++c)
     if (total_n[c] > 1 && (best < 0 || total_w[static_cast<size_t>(best)] < total_w[c])) best = static_cast<long>(c);
   if (best >= 0) out.winner = static_cast<unsigned int>(best);
+  out.weight = std::move(total_w);
+  out.count = std::move(total_n);
+  return out;
+}
+
+ClusterSelection select_heaviest_clusters(const std::vector<double>& weight, const std::vector<uint64_t>& count, size_t k) {
+  ClusterSelection out;
+  out.rank_of_cluster.assign(weight.size(), kClusterNotSelected);
+  for (size_t c = 0; c < weight.size(); ++c)
+    if (count[c] > 1) out.selected.push_back(static_cast<unsigned int>(c));  // :382-389 one sample gives no covariance
+  out.eligible = out.selected.size();
+  const size_t keep = std::min(k, out.selected.size());
+  std::partial_sort(out.selected.begin(), out.selected.begin() + static_cast<std::ptrdiff_t>(keep), out.selected.end(),
+                    [&weight](unsigned int a, unsigned int b) { return weight[a] > weight[b] || (weight[a] == weight[b] && a < b); });
+  out.selected.resize(keep);
+  for (size_t r = 0; r < keep; ++r) out.rank_of_cluster[out.selected[r]] = static_cast<unsigned int>(r);
   return out;
 }
 

@@ -41,10 +41,22 @@ std::vector<ClusterCell> merge_cluster_cells(const ClusterCell* gathered, size_t
 struct ClusterAssignment {
   std::vector<unsigned int> cluster_of_cell;  // per cell, in the list's order
   std::optional<unsigned int> winner;         // none: no cluster holds more than one particle
+  std::vector<double> weight;                 // per cluster id: the sum of its cells' weight sums, added in the list's order
+  std::vector<uint64_t> count;                // per cluster id: its particles
 };
 // make_cluster_map, normalize_and_cap_weights, assign_clusters (:137-238) and the choice of estimate_clusters (:345-411):
 // among the clusters with more than one particle, the first one of maximum total weight.  `cells` is not empty.
 ClusterAssignment assign_clusters(const std::vector<ClusterCell>& cells, double linear_hash_resolution, double angular_hash_resolution,
                                   double weight_cap_percentile);
+
+// The clusters estimate_clusters (:337-399) reports - those of more than one particle - and the `k` heaviest of them by `weight`,
+// ties to the smaller id.
+constexpr unsigned int kClusterNotSelected = 0xFFFFFFFFu;
+struct ClusterSelection {
+  uint64_t eligible = 0;                       // clusters of more than one particle: the size of the reference's vector
+  std::vector<unsigned int> selected;          // min(k, eligible) cluster ids, by descending weight, then ascending id
+  std::vector<unsigned int> rank_of_cluster;   // per cluster id: its index in `selected`, or kClusterNotSelected
+};
+ClusterSelection select_heaviest_clusters(const std::vector<double>& weight, const std::vector<uint64_t>& count, size_t k);
 
 }  // namespace mcl

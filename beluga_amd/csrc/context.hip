@@ -295,6 +295,8 @@ struct mcl_ctx {
   DeviceBuffer<unsigned int> d_cell_u32;       // table count[cap_t] cluster[cap_t] | list first,count,slot,cluster[m_cap] | size
   DeviceBuffer<unsigned long long> d_cell_u64; // list key[m_cap]
   DeviceBuffer<double> d_cell_exchange;        // shards: this rank's cell records | the gathered records of all ranks
+  DeviceBuffer<double> d_cluster_sums;         // mcl_estimate_clusters: partial rows [K * 9][chunks] | the sums [K][9]
+  DeviceBuffer<unsigned int> d_cluster_labels; // mcl_cluster_labels: one id per particle
   int estimate_kind{0};
   mcl_cluster_params cluster_params{0.20, 0.524, 0.90};
 
@@ -1676,7 +1678,9 @@ struct MyCells {
     return Pose2{Rot2{q.x, q.y}, q.z, q.w};
   }
 };
-mcl_status collect_cells(mcl_ctx* ctx, const HashParams& hp, const CellScratch& sc, bool sharded, MyCells* c) {
+// allow_small = false: the kernels of the large path whatever the set's size (they leave the table and the hashes the per-particle
+// passes of mcl_estimate_clusters and mcl_cluster_labels probe)
+mcl_status collect_cells(mcl_ctx* ctx, const HashParams& hp, const CellScratch& sc, bool sharded, bool allow_small, MyCells* c) {
   const uint64_t n = ctx->n;
   c->host = sc.mapped;
   c->dev = sc.mapped_dev;
@@ -1685,7 +1689,7 @@ mcl_status collect_cells(mcl_ctx* ctx, const HashParams& hp, const CellScratch& 
   unsigned int* hsize = sc.mapped.list.size;
   // a small set on one context: one workgroup writes the cells straight into the mapped list (k_small_cluster_cells), another one adds the
   // winning cluster's particles up (k_small_cluster_sums) - two launches instead of eight
-  if (n && !sharded && ctx->tuning.small_fused != 0 && n <= 4096)
+  if (n && !sharded && allow_small && ctx->tuning.small_fused != 0 && n <= 4096)
     c->small = launch_small_cluster_cells(ctx->stream, ctx->cur(), n, hp, out, sc.mapped_dev.list.size);
   if (c->small) {
     MCL_HIP(ctx, hipGetLastError());
@@ -1768,16 +1772,22 @@ mcl_status exchange_cells(mcl_ctx* ctx, bool local_failure, std::vector<ClusterC
   return MCL_OK;
 }
 
-// The cells' cluster ids back to the device (list order, next to the cells' slots) and the sums over the particles of cluster `wanted`.
+// One value per cell (list order, next to the cells' slots) to where the device reads the cells' cluster ids.
+mcl_status upload_cell_values(mcl_ctx* ctx, const MyCells& c, const std::vector<unsigned int>& value_of) {
+  if (c.on_host_list) {  // the kernels read them from the mapped list
+    std::memcpy(c.host.cluster, value_of.data(), c.m * sizeof(unsigned int));
+  } else {
+    MCL_HIP(ctx, hipMemcpyAsync(c.dev.cluster, value_of.data(), c.m * sizeof(unsigned int), hipMemcpyHostToDevice, ctx->stream));
+    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (value_of is pageable host memory of the caller)
+  }
+  return MCL_OK;
+}
+
+// The cells' cluster ids back to the device and the sums over the particles of cluster `wanted`.
 mcl_status cluster_sums(mcl_ctx* ctx, const HashParams& hp, const CellScratch& sc, const MyCells& c, const std::vector<unsigned int>& cluster_of,
                         unsigned int wanted, bool sharded, mcl_estimate* out) {
   const unsigned int m = c.m;
-  if (c.on_host_list) {  // the kernel reads the cluster ids from the mapped list
-    std::memcpy(c.host.cluster, cluster_of.data(), m * sizeof(unsigned int));
-  } else {
-    MCL_HIP(ctx, hipMemcpyAsync(c.dev.cluster, cluster_of.data(), m * sizeof(unsigned int), hipMemcpyHostToDevice, ctx->stream));
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (cluster_of is pageable host memory of the caller)
-  }
+  if (const mcl_status s = upload_cell_values(ctx, c, cluster_of)) return s;
   if (c.small) {  // (the cells' keys and their cluster ids are in the mapped list)
     launch_small_cluster_sums(ctx->stream, ctx->cur(), ctx->n, hp, c.dev.list.key, c.dev.cluster, m, wanted, ctx->pivot[0], ctx->pivot[1],
                               ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
@@ -1797,18 +1807,33 @@ mcl_status cluster_sums(mcl_ctx* ctx, const HashParams& hp, const CellScratch& s
   return mirrored_estimate(ctx, out);
 }
 
-mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_estimate* out) {
+// The front half every clustering entry point shares: the scratch, this context's occupied cells, the list of all cells in
+// first-occurrence order (over shards: the ranks' lists merged) and the host's cluster assignment over it.
+struct ClusterFront {
+  bool sharded = false;
+  HashParams hp{};
+  CellScratch sc{};
+  MyCells mine;
+  std::vector<uint32_t> index_of_mine;  // this context's j-th cell (by first particle) in the list: over shards, where the merge put it
+  ClusterAssignment assigned;
+  // this context's cells -> their clusters (list order, the order of the cells' slots)
+  std::vector<unsigned int> cluster_of_my_cells() const {
+    std::vector<unsigned int> cluster_of(mine.m);
+    for (uint32_t j = 0; j < mine.m; ++j) cluster_of[mine.order[j]] = assigned.cluster_of_cell[index_of_mine[j]];
+    return cluster_of;
+  }
+};
+mcl_status cluster_front(mcl_ctx* ctx, const mcl_cluster_params& cp, bool allow_small, ClusterFront* f) {
   const uint64_t n = ctx->n;
-  const bool sharded = ctx->have_comm && ctx->comm_world > 1;
-  if (n == 0 && !sharded) return fail(ctx, MCL_ERR_NOT_READY, "no particles");  // (an empty shard still takes part in the exchange)
+  f->sharded = ctx->have_comm && ctx->comm_world > 1;
+  if (n == 0 && !f->sharded) return fail(ctx, MCL_ERR_NOT_READY, "no particles");  // (an empty shard still takes part in the exchange)
   MCL_REQUIRE(ctx, cp.linear_hash_resolution > 0 && cp.angular_hash_resolution > 0 && cp.weight_cap_percentile >= 0 &&
                        cp.weight_cap_percentile < 1.0, "bad cluster parameters");
   MCL_REQUIRE(ctx, n < 0xFFFFFFFFull, "too many particles");
-  CellScratch sc;
-  if (const mcl_status s = cluster_scratch(ctx, &sc)) return s;
-  const HashParams hp{cp.linear_hash_resolution, cp.linear_hash_resolution, cp.angular_hash_resolution};
-  MyCells mine;
-  if (const mcl_status s = collect_cells(ctx, hp, sc, sharded, &mine)) return s;
+  if (const mcl_status s = cluster_scratch(ctx, &f->sc)) return s;
+  f->hp = HashParams{cp.linear_hash_resolution, cp.linear_hash_resolution, cp.angular_hash_resolution};
+  MyCells& mine = f->mine;
+  if (const mcl_status s = collect_cells(ctx, f->hp, f->sc, f->sharded, allow_small, &mine)) return s;
 
   // The occupied cells in the order their first particle appears in the set; over shards, the ranks' lists merged.
   std::vector<ClusterCell> cells(mine.m);
@@ -1817,27 +1842,94 @@ mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_e
     const CellList& h = mine.host.list;
     cells[j] = ClusterCell{h.key[k], h.wsum[k], h.count[k], mine.state(k)};
   }
-  std::vector<uint32_t> index_of_mine;  // this context's j-th cell in `cells`: over shards, where the merge put it
-  if (sharded) {
+  if (f->sharded) {
     std::vector<ClusterCell> local = std::move(cells);
-    if (const mcl_status s = exchange_cells(ctx, mine.local_failure, local, &cells, &index_of_mine)) return s;
+    if (const mcl_status s = exchange_cells(ctx, mine.local_failure, local, &cells, &f->index_of_mine)) return s;
   } else {
-    index_of_mine.resize(mine.m);
-    std::iota(index_of_mine.begin(), index_of_mine.end(), 0u);
+    f->index_of_mine.resize(mine.m);
+    std::iota(f->index_of_mine.begin(), f->index_of_mine.end(), 0u);
   }
   if (cells.empty()) return fail(ctx, MCL_ERR_NOT_READY, "no particles");
+  f->assigned = assign_clusters(cells, cp.linear_hash_resolution, cp.angular_hash_resolution, cp.weight_cap_percentile);
+  return MCL_OK;
+}
 
-  const ClusterAssignment assigned = assign_clusters(cells, cp.linear_hash_resolution, cp.angular_hash_resolution, cp.weight_cap_percentile);
-  if (!assigned.winner) {  // :424-427 no cluster: overall mean and covariance
-    if (sharded) return sharded_estimate(ctx, nullptr, out);
+mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_estimate* out) {
+  ClusterFront f;
+  if (const mcl_status s = cluster_front(ctx, cp, /*allow_small=*/true, &f)) return s;
+  if (!f.assigned.winner) {  // :424-427 no cluster: overall mean and covariance
+    if (f.sharded) return sharded_estimate(ctx, nullptr, out);
     double sums[12];
     if (const mcl_status s = do_estimate_sums(ctx, ctx->pivot, sums)) return s;
     return mcl_estimate_from_sums(sums, out);
   }
-  // this rank's cells -> their clusters (list order, the order of the cells' slots)
-  std::vector<unsigned int> cluster_of(mine.m);
-  for (uint32_t j = 0; j < mine.m; ++j) cluster_of[mine.order[j]] = assigned.cluster_of_cell[index_of_mine[j]];
-  return cluster_sums(ctx, hp, sc, mine, cluster_of, *assigned.winner, sharded, out);
+  return cluster_sums(ctx, f.hp, f.sc, f.mine, f.cluster_of_my_cells(), *f.assigned.winner, f.sharded, out);
+}
+
+// ---- estimate_clusters (:337-399) and ParticleClusterizer::operator() (:269-304) -------------------------------------------------------
+// Host: which clusters count (more than one particle) and which K of them are summed, from the per-cluster totals of the assignment.
+// Device: one pass over the set for all K (k_estimate_partials_clusters), the cells' table carrying the RANK of each cell's cluster.
+static_assert(MCL_MAX_CLUSTER_ESTIMATES == kMaxClusterRanks, "the kernel's rows are sized for the header's cap");
+mcl_status unsharded_only(mcl_ctx* ctx, const char* what) {
+  if (ctx->have_comm && ctx->comm_world > 1)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(what) + ": not on a sharded filter (the sums are not exchanged yet)");
+  return MCL_OK;
+}
+mcl_status do_estimate_clusters(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_cluster_estimate* out, uint64_t capacity,
+                                uint64_t* num_clusters) {
+  if (const mcl_status s = unsharded_only(ctx, "mcl_estimate_clusters")) return s;
+  ClusterFront f;
+  if (const mcl_status s = cluster_front(ctx, cp, /*allow_small=*/false, &f)) return s;
+  const size_t k = static_cast<size_t>(std::min<uint64_t>(capacity, MCL_MAX_CLUSTER_ESTIMATES));
+  const ClusterSelection sel = select_heaviest_clusters(f.assigned.weight, f.assigned.count, k);
+  *num_clusters = sel.eligible;
+  const uint32_t ranks = static_cast<uint32_t>(sel.selected.size());
+  if (ranks == 0) return MCL_OK;  // the count alone, or an empty vector
+  // cell -> cluster -> rank, composed here: the table's cluster column carries the rank for this pass
+  std::vector<unsigned int> rank_of = f.cluster_of_my_cells();
+  for (unsigned int& c : rank_of) c = sel.rank_of_cluster[c];
+  if (const mcl_status s = upload_cell_values(ctx, f.mine, rank_of)) return s;
+  launch_cell_set_cluster(ctx->stream, f.mine.dev.list, f.mine.dev.cluster, f.mine.m, f.sc.table);
+  const size_t rows = static_cast<size_t>(ranks) * 9;
+  const size_t partials = rows * num_chunks(ctx->n);
+  MCL_HIP(ctx, ctx->d_cluster_sums.ensure(partials + rows));
+  double* d_sums = ctx->d_cluster_sums.ptr + partials;
+  launch_estimate_sums_clusters(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, f.sc.table, ranks, ctx->pivot[0], ctx->pivot[1],
+                                ctx->d_cluster_sums.ptr, d_sums);
+  MCL_HIP(ctx, hipGetLastError());
+  std::vector<double> sums(rows);
+  MCL_HIP(ctx, hipMemcpyAsync(sums.data(), d_sums, rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<mcl_cluster_estimate> found(ranks);
+  for (uint32_t r = 0; r < ranks; ++r) {
+    const unsigned int id = sel.selected[r];
+    double twelve[12] = {0};
+    std::memcpy(twelve, sums.data() + static_cast<size_t>(r) * 9, 9 * sizeof(double));
+    twelve[9] = ctx->pivot[0];
+    twelve[10] = ctx->pivot[1];
+    found[r] = mcl_cluster_estimate{id, 0u, f.assigned.count[id], twelve[0], {}};
+    if (const mcl_status s = mcl_estimate_from_sums(twelve, &found[r].estimate)) return fail(ctx, s, "mcl_estimate_clusters: bad sums");
+  }
+  // the reported weight is the sums pass's, and so is the order
+  std::sort(found.begin(), found.end(), [](const mcl_cluster_estimate& a, const mcl_cluster_estimate& b) {
+    return a.weight > b.weight || (a.weight == b.weight && a.id < b.id);
+  });
+  std::copy(found.begin(), found.end(), out);
+  return MCL_OK;
+}
+
+mcl_status do_cluster_labels(mcl_ctx* ctx, const mcl_cluster_params& cp, uint32_t* labels) {
+  if (const mcl_status s = unsharded_only(ctx, "mcl_cluster_labels")) return s;
+  ClusterFront f;
+  if (const mcl_status s = cluster_front(ctx, cp, /*allow_small=*/false, &f)) return s;
+  if (const mcl_status s = upload_cell_values(ctx, f.mine, f.cluster_of_my_cells())) return s;
+  launch_cell_set_cluster(ctx->stream, f.mine.dev.list, f.mine.dev.cluster, f.mine.m, f.sc.table);
+  MCL_HIP(ctx, ctx->d_cluster_labels.ensure(ctx->n));
+  launch_cluster_labels(ctx->stream, ctx->n, ctx->d_hashes.ptr, f.sc.table, ctx->d_cluster_labels.ptr);
+  MCL_HIP(ctx, hipGetLastError());
+  MCL_HIP(ctx, hipMemcpyAsync(labels, ctx->d_cluster_labels.ptr, ctx->n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MCL_OK;
 }
 
 
@@ -2449,6 +2541,8 @@ void mcl_destroy(mcl_ctx* ctx) {
   ctx->d_cell_u32.release();
   ctx->d_cell_u64.release();
   ctx->d_cell_exchange.release();
+  ctx->d_cluster_sums.release();
+  ctx->d_cluster_labels.release();
   ctx->d_sort_u64.release();
   ctx->d_sort_f64.release();
   ctx->d_ndt_grid.release();
@@ -3045,6 +3139,22 @@ mcl_status mcl_cluster_based_estimate(mcl_ctx* ctx, const mcl_cluster_params* pa
     stage_collect(ctx);
   }
   return s;
+}
+
+mcl_status mcl_estimate_clusters(mcl_ctx* ctx, const mcl_cluster_params* params, mcl_cluster_estimate* out, uint64_t capacity,
+                                 uint64_t* num_clusters) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  MCL_REQUIRE(ctx, num_clusters != nullptr, "mcl_estimate_clusters: null count");
+  MCL_REQUIRE(ctx, out != nullptr || capacity == 0, "mcl_estimate_clusters: null output");
+  if (const mcl_status s = bind_device(ctx)) return s;
+  return do_estimate_clusters(ctx, params ? *params : mcl_cluster_params{0.20, 0.524, 0.90}, out, capacity, num_clusters);
+}
+
+mcl_status mcl_cluster_labels(mcl_ctx* ctx, const mcl_cluster_params* params, uint32_t* labels) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  MCL_REQUIRE(ctx, labels != nullptr, "mcl_cluster_labels: null output");
+  if (const mcl_status s = bind_device(ctx)) return s;
+  return do_cluster_labels(ctx, params ? *params : mcl_cluster_params{0.20, 0.524, 0.90}, labels);
 }
 
 mcl_status mcl_set_estimate_kind(mcl_ctx* ctx, int32_t kind, const mcl_cluster_params* params) {

@@ -695,6 +695,14 @@ void launch_cell_set_cluster(hipStream_t st, const CellList& cells, const unsign
 void launch_estimate_sums_cluster(hipStream_t st, Particles p, uint64_t n, const unsigned long long* d_hashes, const CellTable& t,
                                   unsigned int wanted, double pivot_x, double pivot_y, double* d_partials, double* d_out,
                                   double* host_mirror = nullptr);
+// estimate_clusters (:337-399): t.cluster holds, per cell, the rank in [0, ranks) of its cluster among the selected ones (anything else:
+// not selected); d_out[ranks][9]: the nine sums of estimation.hpp:436-475 per rank.  d_partials: ranks * 9 * num_chunks(n) doubles.
+// ranks <= kMaxClusterRanks (the kernel keeps ranks * 288 bytes of LDS; more: nothing is launched).  Fixed-order reductions only.
+constexpr uint32_t kMaxClusterRanks = 64;  // = MCL_MAX_CLUSTER_ESTIMATES
+void launch_estimate_sums_clusters(hipStream_t st, Particles p, uint64_t n, const unsigned long long* d_hashes, const CellTable& t,
+                                   uint32_t ranks, double pivot_x, double pivot_y, double* d_partials, double* d_out);
+// ParticleClusterizer::operator() (:269-304): d_labels[i] = t.cluster of particle i's cell (d_hashes as launch_cluster_cells left them)
+void launch_cluster_labels(hipStream_t st, uint64_t n, const unsigned long long* d_hashes, const CellTable& t, unsigned int* d_labels);
 // init: multivariate_normal_distribution.hpp:96-126 with T = V sqrt(L)
 void launch_init_normal(hipStream_t st, Particles p, uint64_t n, const double mean[3], const double T[9], uint64_t seed,
                         uint64_t index_offset);

@@ -3770,6 +3770,107 @@ __global__ __launch_bounds__(kBlock) void k_estimate_partials_cluster(Particles 
   }
 }
 
+// ---- estimate_clusters (:337-399): the same sums for up to kMaxClusterRanks clusters in one pass over the set ------------------
+// The table's cluster column carries, for this launch, the RANK of the cell's cluster among the `ranks` selected ones (the host composes
+// cell -> cluster -> rank; any other value: not selected).  A lane adds its eight particles up in registers as long as their rank stays the same
+// (the spatially ordered set of an LF context: a whole wave of one rank).  Where a lane's rank changes, the WAVE flushes: for every distinct
+// rank its lanes hold, in the order of the first lane holding it, the nine sums of those lanes (the others add + 0.0) through the fixed
+// tree of wave_sum_f64, added by lane 0 to the wave's own row [ranks][9] in LDS.  Behind a barrier the four waves' rows are added in wave
+// order and stored as one partial row per (rank, sum); k_final_rows adds the chunks.  No atomics, nothing whose order depends on timing:
+// where the flushes fall is a function of the set alone, so two launches over the same set give the same bits - whatever mixture of
+// clusters a wave holds (64 different ones flush per particle: 9 wave sums each, still one read of the set).
+constexpr uint32_t kNoRank = 0xFFFFFFFFu;
+__global__ __launch_bounds__(kBlock) void k_estimate_partials_clusters(Particles p, uint64_t n, const unsigned long long* __restrict__ hashes,
+                                                                       CellTable t, uint32_t ranks, double pivot_x, double pivot_y,
+                                                                       double* __restrict__ partials, uint32_t stride) {
+  extern __shared__ __attribute__((aligned(16))) double s_rows[];  // [kBlock / 64][ranks][kEstK]
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t row = ranks * kEstK;
+  for (uint32_t j = threadIdx.x; j < (kBlock / 64) * row; j += kBlock) s_rows[j] = 0.0;
+  __syncthreads();
+  double* const mine = s_rows + wave * row;
+  const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kChunk + threadIdx.x * kItems;
+  const uint64_t mask = t.capacity - 1;
+  double v[kEstK];
+#pragma unroll
+  for (int k = 0; k < kEstK; ++k) v[k] = 0.0;
+  uint32_t held = kNoRank;  // the rank v belongs to
+  auto flush = [&]() {      // (entered by the whole wave)
+    unsigned long long todo = __ballot(held != kNoRank);
+    while (todo) {
+      const int first = __builtin_amdgcn_readfirstlane(__ffsll(todo) - 1);
+      const uint32_t r = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(held), first));
+      const bool in = held == r;
+      todo &= ~__ballot(in);
+#pragma unroll
+      for (int k = 0; k < kEstK; ++k) {
+        const double total = wave_sum_f64(in ? v[k] : 0.0);
+        if (lane == 0) mine[r * kEstK + k] += total;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kEstK; ++k) v[k] = 0.0;
+    held = kNoRank;
+  };
+  // the eight probes first, independent of one another (their loads in flight together); a rank takes a byte of `packed`
+  static_assert(kItems == 8 && kMaxClusterRanks < 0xFF, "eight ranks, a byte each, 0xFF = none");
+  unsigned long long packed = 0;
+#pragma unroll
+  for (int k = 0; k < kItems; ++k) {
+    const uint64_t i = base + k;
+    unsigned long long r = 0xFF;
+    if (i < n) {
+      const unsigned long long key = kld_key(hashes[i]);
+      uint64_t slot = kld_slot(key, mask);
+      while (t.keys[slot] != key) slot = (slot + 1) & mask;
+      const uint32_t c = t.cluster[slot];
+      if (c < ranks) r = c;  // (nothing indexes the rows beyond `ranks`)
+    }
+    packed |= r << (8 * k);
+  }
+#pragma unroll 1
+  for (int k = 0; k < kItems; ++k) {
+    const uint64_t i = base + k;
+    const uint32_t byte = static_cast<uint32_t>(packed >> (8 * k)) & 0xFFu;
+    const uint32_t r = byte == 0xFFu ? kNoRank : byte;
+    if (__ballot(r != kNoRank && held != kNoRank && r != held)) flush();
+    if (r != kNoRank) {
+      held = r;
+      const double w = p.w[i];
+      const double4 q = p.pose[i];
+      const double dx = q.z - pivot_x, dy = q.w - pivot_y;
+      v[0] += w;
+      v[1] += w * w;
+      v[2] += w * q.x;
+      v[3] += w * q.y;
+      v[4] += w * dx;
+      v[5] += w * dy;
+      v[6] += w * dx * dx;
+      v[7] += w * dx * dy;
+      v[8] += w * dy * dy;
+    }
+  }
+  flush();
+  __syncthreads();
+  for (uint32_t j = threadIdx.x; j < row; j += kBlock) {
+    double acc = s_rows[j];
+    for (uint32_t w = 1; w < kBlock / 64; ++w) acc += s_rows[w * row + j];
+    partials[static_cast<size_t>(j) * stride + blockIdx.x] = acc;
+  }
+}
+
+// ParticleClusterizer::operator() (:269-304): the cluster id of every particle's cell.
+__global__ __launch_bounds__(kBlock) void k_cluster_labels(uint64_t n, const unsigned long long* __restrict__ hashes, CellTable t,
+                                                           unsigned int* __restrict__ labels) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t mask = t.capacity - 1;
+  const unsigned long long key = kld_key(hashes[i]);
+  uint64_t slot = kld_slot(key, mask);
+  while (t.keys[slot] != key) slot = (slot + 1) & mask;
+  labels[i] = t.cluster[slot];
+}
+
 // ---- cluster_based_estimate of a small set (up to kSmallMax particles): two launches of one workgroup each around the host's pass --------
 // The large path is five launches and two synchronisations (clear, hash, aggregate, compact | set clusters, masked sums, final rows): a
 // tenth of a millisecond on a set of 2000 particles, twice the rest of its cycle - and cluster_based_estimate is what beluga_ros::Amcl
@@ -4709,6 +4810,21 @@ void launch_estimate_sums_cluster(hipStream_t st, Particles p, uint64_t n, const
     hipLaunchKernelGGL(k_estimate_partials_cluster, dim3(chunks), dim3(kBlock), 0, st, p, n, d_hashes, CellTable::keys_and_clusters(t), wanted,
                        pivot_x, pivot_y, d_partials, chunks);
   hipLaunchKernelGGL(k_final_rows, dim3(kEstK), dim3(kBlock), 0, st, d_partials, chunks, chunks, d_out, host_mirror, Completion{});
+}
+
+void launch_estimate_sums_clusters(hipStream_t st, Particles p, uint64_t n, const unsigned long long* d_hashes, const CellTable& t,
+                                   uint32_t ranks, double pivot_x, double pivot_y, double* d_partials, double* d_out) {
+  const uint32_t chunks = num_chunks(n);
+  const uint32_t rows = ranks * kEstK;
+  if (rows == 0 || ranks > kMaxClusterRanks) return;
+  if (chunks)
+    hipLaunchKernelGGL(k_estimate_partials_clusters, dim3(chunks), dim3(kBlock), (kBlock / 64) * rows * sizeof(double), st, p, n, d_hashes,
+                       CellTable::keys_and_clusters(t), ranks, pivot_x, pivot_y, d_partials, chunks);
+  hipLaunchKernelGGL(k_final_rows, dim3(rows), dim3(kBlock), 0, st, d_partials, chunks, chunks, d_out, static_cast<double*>(nullptr), Completion{});
+}
+void launch_cluster_labels(hipStream_t st, uint64_t n, const unsigned long long* d_hashes, const CellTable& t, unsigned int* d_labels) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_cluster_labels, dim3(blocks_for(n)), dim3(kBlock), 0, st, n, d_hashes, CellTable::keys_and_clusters(t), d_labels);
 }
 
 void launch_init_normal(hipStream_t st, Particles p, uint64_t n, const double mean[3], const double T[9], uint64_t seed,

@@ -418,6 +418,23 @@ struct Shard {
   }
 };
 
+/// beluga::ParticleClusterizerParam (algorithm/cluster_based_estimation.hpp:243-259).
+struct ParticleClusterizerParam {
+  double linear_hash_resolution = 0.20;    ///< cell size of the clustering's spatial hash, metres
+  double angular_hash_resolution = 0.524;  ///< ... and radians
+  double weight_cap_percentile = 0.90;     ///< the cells' mean weights are capped at this percentile of theirs
+};
+
+/// One entry of beluga::estimate_clusters' result (:356-360: weight, mean, covariance) and, beside the reference's fields, the cluster's id
+/// (what cluster_labels() gives its particles) and its number of particles.
+struct ClusterEstimate {
+  double weight{0};
+  SE2d mean;
+  Matrix3d covariance{};
+  std::uint32_t id{0};
+  std::uint64_t count{0};
+};
+
 class Amcl {
  public:
   using state_type = SE2d;
@@ -850,6 +867,41 @@ class Amcl {
     out.first.y = est.pose[3];
     for (int i = 0; i < 9; ++i) out.second[static_cast<std::size_t>(i)] = est.covariance[i];
     return out;
+  }
+
+  /// beluga::estimate_clusters (algorithm/cluster_based_estimation.hpp:337-399) over the clusters of ParticleClusterizer (:269-304):
+  /// the weight, mean and covariance of the clusters of more than one particle - every hypothesis of the set, where
+  /// cluster_based_estimate returns the heaviest alone.  The heaviest min(max_clusters, 64) of them, by descending weight (ties by
+  /// ascending id); the first one is cluster_based_estimate's.  Not on a sharded filter.
+  [[nodiscard]] std::vector<ClusterEstimate> estimate_clusters(const ParticleClusterizerParam& param = {}, std::size_t max_clusters = 64) const {
+    const mcl_cluster_params cp{param.linear_hash_resolution, param.angular_hash_resolution, param.weight_cap_percentile};
+    std::vector<mcl_cluster_estimate> raw(std::min<std::size_t>(max_clusters, MCL_MAX_CLUSTER_ESTIMATES));
+    std::uint64_t total = 0;
+    check(mcl_estimate_clusters(ctx_, &cp, raw.empty() ? nullptr : raw.data(), raw.size(), &total));
+    raw.resize(std::min<std::size_t>(raw.size(), total));
+    std::vector<ClusterEstimate> out(raw.size());
+    for (std::size_t k = 0; k < raw.size(); ++k) {
+      const mcl_estimate& est = raw[k].estimate;
+      out[k].weight = raw[k].weight;
+      out[k].mean.c = est.pose[0];
+      out[k].mean.s = est.pose[1];
+      out[k].mean.x = est.pose[2];
+      out[k].mean.y = est.pose[3];
+      for (int i = 0; i < 9; ++i) out[k].covariance[static_cast<std::size_t>(i)] = est.covariance[i];
+      out[k].id = raw[k].id;
+      out[k].count = raw[k].count;
+    }
+    return out;
+  }
+
+  /// ParticleClusterizer::operator() (:269-304): the cluster id of every particle, in particles()' order.  Not on a sharded filter.
+  [[nodiscard]] std::vector<std::uint32_t> cluster_labels(const ParticleClusterizerParam& param = {}) const {
+    const mcl_cluster_params cp{param.linear_hash_resolution, param.angular_hash_resolution, param.weight_cap_percentile};
+    std::uint64_t n = 0;
+    check(mcl_num_particles(ctx_, &n));
+    std::vector<std::uint32_t> labels(n);
+    if (n) check(mcl_cluster_labels(ctx_, &cp, labels.data()));
+    return labels;
   }
 
   /// Makes update() return cluster_based_estimate, as beluga_ros::Amcl does (beluga_ros/src/amcl.cpp:125), instead of

@@ -386,6 +386,32 @@ mcl_status mcl_cluster_based_estimate(mcl_ctx* ctx, const mcl_cluster_params* pa
 /* Selects what mcl_update returns: 0 = beluga::estimate (beluga::Amcl), 1 = cluster_based_estimate (beluga_ros::Amcl). */
 mcl_status mcl_set_estimate_kind(mcl_ctx* ctx, int32_t kind, const mcl_cluster_params* params /* NULL: defaults */);
 
+/* beluga::estimate_clusters (algorithm/cluster_based_estimation.hpp:337-399) over the clusters of ParticleClusterizer (:269-304):
+ * the weight, mean and covariance of EVERY cluster of more than one particle - the hypotheses of a filter that has not converged
+ * (global localisation, a symmetric building, a kidnapped robot), of which mcl_cluster_based_estimate returns the heaviest alone.
+ * *num_clusters: how many such clusters there are (the size of the reference's vector).  out receives the heaviest
+ * min(capacity, MCL_MAX_CLUSTER_ESTIMATES, *num_clusters) of them, by descending weight, ties by ascending id: out[0] is
+ * mcl_cluster_based_estimate's cluster.  No such cluster: MCL_OK, *num_clusters = 0, nothing written (the reference returns an empty
+ * vector; the fallback to the overall estimate is mcl_cluster_based_estimate's).  capacity = 0 with out = NULL: the count alone, without
+ * a pass over the particles.  The clusters are selected by the per-cell weight sums; the reported weight is the sum of the same pass over
+ * the particles that gives the estimate beside it, and the order is taken over the reported weights.  One pass over the set for all
+ * clusters, fixed-order sums: two calls on an unchanged set return the same bits.  The set is not modified.
+ * MCL_ERR_NOT_READY without particles; MCL_ERR_INVALID_ARGUMENT for bad parameters; any sensor model.
+ * Not on a context with a communicator of several ranks (MCL_ERR_UNSUPPORTED): the shards' sums are not exchanged yet. */
+#define MCL_MAX_CLUSTER_ESTIMATES 64
+typedef struct mcl_cluster_estimate {
+  uint32_t id;           /* the cluster id ParticleClusterizer assigns (what mcl_cluster_labels writes) */
+  uint32_t reserved;
+  uint64_t count;        /* particles in the cluster, > 1 */
+  double weight;         /* sum of the cluster's particle weights (estimate_clusters' Estimate::weight) */
+  mcl_estimate estimate; /* beluga::estimate over the cluster's particles alone */
+} mcl_cluster_estimate;
+mcl_status mcl_estimate_clusters(mcl_ctx* ctx, const mcl_cluster_params* params /* NULL: defaults */, mcl_cluster_estimate* out,
+                                 uint64_t capacity, uint64_t* num_clusters);
+/* ParticleClusterizer::operator() (:269-304): the cluster id of every particle, in the order mcl_get_particles returns the particles.
+ * labels: host memory, mcl_num_particles entries.  Errors as mcl_estimate_clusters, MCL_ERR_UNSUPPORTED over several ranks included. */
+mcl_status mcl_cluster_labels(mcl_ctx* ctx, const mcl_cluster_params* params /* NULL: defaults */, uint32_t* labels);
+
 /* beluga_ros::assign_particle_cloud(particles, size, PoseArray&) (beluga_ros/include/beluga_ros/particle_cloud.hpp:131-149):
  * `particles | views::sample | take_exactly(size)` — a weighted sample of `size` states of the current set, for
  * publication; the set itself is not modified.  states: size x 4 doubles (cos, sin, x, y), host memory.  The draws come
