@@ -26,6 +26,7 @@
 
 #include "beluga_mcl.h"
 #include "cluster_host.h"
+#include "cycle_host.h"
 #include "kernels.h"
 #include "landmark_host.h"
 #include "map_build.h"
@@ -37,16 +38,6 @@ namespace {
 using namespace mcl;
 
 thread_local std::string g_create_error;
-
-// algorithm/exponential_filter.hpp:32-44
-struct ExponentialFilter {
-  double alpha{0.}, output{0.};
-  void reset() { output = 0.; }
-  double operator()(double input) {
-    output += (output == 0.) ? input : alpha * (input - output);
-    return output;
-  }
-};
 
 template <class T>
 struct DeviceBuffer {
@@ -83,93 +74,6 @@ struct ParticleSet {
 };
 
 Pose2 pose_from(const double p[4]) { return Pose2{Rot2{p[0], p[1]}, p[2], p[3]}; }
-
-// motion/differential_drive_model.hpp:129-154,167-173
-double rotation_variance(const Rot2& r) {
-  const Rot2 flipped = rot_mul(r, rot_exp(kPi));
-  const double delta = std::min(std::abs(rot_log(r)), std::abs(rot_log(flipped)));
-  return delta * delta;
-}
-DiffDriveSampler make_sampler(const Pose2& pose, const Pose2& prev, const mcl_diffdrive_params& a, int kind, double alpha5) {
-  const double tx = pose.x - prev.x, ty = pose.y - prev.y;
-  const double distance = std::sqrt(tx * tx + ty * ty);
-  const double distance_variance = distance * distance;
-  const Rot2 heading = rot_exp(std::atan2(ty, tx));
-  const Rot2 first = distance > a.distance_threshold ? rot_mul(heading, rot_inverse(prev.r)) : Rot2{1.0, 0.0};
-  DiffDriveSampler s{};
-  s.kind = kind;
-  s.first_c = first.c;
-  s.first_s = first.s;
-  if (kind == MCL_MOTION_STATIONARY) return s;  // stationary_model.hpp:53-61 ignores the control action
-  if (kind == MCL_MOTION_OMNIDIRECTIONAL) {     // omnidirectional_drive_model.hpp:102-131
-    const Rot2 rotation = rot_mul(pose.r, rot_inverse(prev.r));
-    s.m1 = rot_log(rotation);
-    s.s1 = std::sqrt(a.rotation_noise_from_rotation * rotation_variance(rotation) + a.rotation_noise_from_translation * distance_variance);
-    s.mt = distance;
-    s.st = std::sqrt(a.translation_noise_from_translation * distance_variance + a.translation_noise_from_rotation * rotation_variance(rotation));
-    s.m2 = 0.0;
-    s.s2 = std::sqrt(alpha5 * distance_variance + a.translation_noise_from_rotation * rotation_variance(rotation));
-    return s;
-  }
-  const Rot2 second = rot_mul(rot_mul(pose.r, rot_inverse(prev.r)), rot_inverse(first));
-  s.m1 = rot_log(first);
-  s.s1 = std::sqrt(a.rotation_noise_from_rotation * rotation_variance(first) + a.rotation_noise_from_translation * distance_variance);
-  s.mt = distance;
-  s.st = std::sqrt(a.translation_noise_from_translation * distance_variance +
-                   a.translation_noise_from_rotation * (rotation_variance(first) + rotation_variance(second)));
-  s.m2 = rot_log(second);
-  s.s2 = std::sqrt(a.rotation_noise_from_rotation * rotation_variance(second) + a.rotation_noise_from_translation * distance_variance);
-  return s;
-}
-
-// Symmetric 3x3 eigen-decomposition (cyclic Jacobi): T = V sqrt(L)  (multivariate_normal_distribution.hpp:109-126).
-bool covariance_to_transform(const double cov[9], double T[9]) {
-  double a[3][3], v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) a[i][j] = cov[3 * i + j];
-  for (int i = 0; i < 3; ++i)
-    for (int j = i + 1; j < 3; ++j) {
-      const double scale = std::max(std::abs(a[i][j]), std::abs(a[j][i]));
-      if (std::abs(a[i][j] - a[j][i]) > 1e-12 * scale) return false;  // "not symmetric"
-      if (!std::isfinite(a[i][j])) return false;
-    }
-  for (int sweep = 0; sweep < 64; ++sweep) {
-    const double off = a[0][1] * a[0][1] + a[0][2] * a[0][2] + a[1][2] * a[1][2];
-    if (off < 1e-300) break;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        if (a[p][q] == 0.0) continue;
-        const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (std::abs(theta) + std::sqrt(theta * theta + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 3; ++k) {
-          const double akp = a[k][p], akq = a[k][q];
-          a[k][p] = c * akp - s * akq;
-          a[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double apk = a[p][k], aqk = a[q][k];
-          a[p][k] = c * apk - s * aqk;
-          a[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = v[k][p], vkq = v[k][q];
-          v[k][p] = c * vkp - s * vkq;
-          v[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  for (int j = 0; j < 3; ++j) {
-    if (!std::isfinite(a[j][j])) return false;
-    if (a[j][j] < 0.0) {
-      if (a[j][j] > -1e-14) a[j][j] = 0.0;
-      else return false;  // "negative eigenvalues"
-    }
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) T[3 * i + j] = v[i][j] * std::sqrt(a[j][j]);
-  return true;
-}
 
 }  // namespace
 
@@ -312,22 +216,13 @@ struct mcl_ctx {
   bool have_pivot{false};
   double pivot[2]{0, 0};
   Tuning tuning{};  // mcl_set_option / BELUGA_MCL_* at mcl_create (A/B measurements, tests)
-  // Key frame of the spatial ordering (kernels.h KeyFrame): the last estimate of the set, when the host has one.
-  bool have_cloud_estimate{false};
-  double cloud_mean[3]{0, 0, 0};   // x, y, theta
-  double cloud_sigma[3]{0, 0, 0};  // standard deviations of x, y, theta
+  CloudEstimate cloud;  // key frame of the spatial ordering (KeyFrame): the last estimate of the set, when the host has one
   uint64_t lf_fast_launches{0};    // launches of the FMA variant of the LF kernel (mcl_get_counter)
   // The LDS-patch kernel reports how many beam groups it planned and how many went through a patch (running totals in
-  // kSlotPatchTotals, copied to kSlotPatchMirror); a launch that found few sends the next ones to the gather kernel,
-  // with a probe every 16th launch (option lf_patch = 1).
+  // kSlotPatchTotals, copied to kSlotPatchMirror): the planner remembers them and decides this cycle's LF kernel (cycle_host.h).
+  LfPlanner lf_planner;
   uint64_t lf_patch_launches{0};
   uint64_t lf_queue_launches{0};  // of which by resident workgroups that take their blocks from a queue (k_reweight_lf_patch<true>)
-  uint64_t patch_seen_planned{0}, patch_seen_through{0};
-  bool patch_useful{true};
-  int patch_probe_in{0};
-  // What this cycle's LF launch uses, decided once per cycle (the ordering pass in front of it depends on it):
-  // patches = the LDS-patch kernel; beams = a dispersed set goes to k_reweight_lf_beams (wave per particle, no ordering).
-  struct LfMode { bool decided, patches, beams; } lf_mode{false, false, false};
   uint64_t lf_beams_launches{0};   // launches of k_reweight_lf_beams (mcl_get_counter)
   uint64_t small_tail_launches{0};  // launches of k_small_tail (mcl_get_counter)
   uint64_t lf_far_launches{0};     // launches of the gather kernel with the far-tile bitmap (dispersed sets)
@@ -422,6 +317,14 @@ struct mcl_ctx {
   // What random_intersperse's random states are drawn from (random_free_state).
   FreeCells random_source() const {
     return is_ndt() ? ndt_random : is_landmark() ? landmark_random : FreeCells{d_free.ptr, have_map ? n_free : 0};
+  }
+  // What the planner and the key frame read of the context (cycle_host.h).
+  LfSite lf_site() const { return LfSite{cfg.sensor_kind, n, pal_count != 0, far_tiles != 0, resolution, tuning}; }
+  uint32_t key_layout() const { return lf_planner.key_layout(lf_site()); }
+  bool wants_ordering() const { return lf_planner.wants_ordering(lf_site()); }
+  bool predict_key_frame(const DiffDriveSampler* motion, KeyFrame* out, int moves = 1) const {
+    const KeyFrameInputs in{lf_planner.patch_useful(), resolution, scan_extent, tuning.key_warp, tuning.key_bits_xy};
+    return mcl::predict_key_frame(cloud, motion, moves, key_layout(), in, out);
   }
 };
 
@@ -837,97 +740,6 @@ void points_pulled(mcl_ctx* ctx, bool with_event) {
   ctx->points_in_flight = true;
 }
 
-// The frame of the ordering keys for the set as it will be AFTER this propagation: the last estimate moved by the mean
-// motion, spans widened by the motion noise.  Only the balance of the key's bins depends on it.
-// KeyFrame::layout of the next ordering: position-major for likelihood-field sets reported as dispersed (their gather kernel
-// walks the order region by region, kernels.hip: k_reweight_lf_palette<true, true>), heading-major otherwise.
-uint32_t key_layout(const mcl_ctx* ctx) {
-  const uint32_t curve = ctx->tuning.key_curve ? 0u : 2u;  // heading-major keys: Hilbert curve (default) / Morton order
-  if (ctx->tuning.key_layout >= 0) return (ctx->tuning.key_layout ? 1u : 0u) | curve;
-  return (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM && !ctx->off_grid() && ctx->tuning.lf_patch == 1 && !ctx->patch_useful && ctx->tuning.lf_far_tiles != 0 &&
-                  ctx->far_tiles != 0
-              ? 1u
-              : 0u) |
-         curve;
-}
-// moves: how often the set's centre is moved by `motion` (2: the frame of the cycle AFTER the one that is running - launch_order_ahead -, whose
-// set is the remembered one moved twice; its spread grows once: the resampling in between takes it back to where it was).
-bool predict_key_frame(const mcl_ctx* ctx, const DiffDriveSampler* motion, KeyFrame* out, int moves = 1) {
-  out->layout = key_layout(ctx);
-  if (!ctx->have_cloud_estimate) return false;
-  double x = ctx->cloud_mean[0], y = ctx->cloud_mean[1], t = ctx->cloud_mean[2];
-  double sx = ctx->cloud_sigma[0], sy = ctx->cloud_sigma[1], st = ctx->cloud_sigma[2];
-  if (motion && motion->kind != MCL_MOTION_STATIONARY) {
-    for (int move = 1; move < moves; ++move) {  // (the centre alone)
-      const double heading = t + (motion->kind == MCL_MOTION_DIFFERENTIAL ? motion->m1 : std::atan2(motion->first_s, motion->first_c));
-      x += motion->mt * std::exp(-0.5 * st * st) * std::cos(heading);
-      y += motion->mt * std::exp(-0.5 * st * st) * std::sin(heading);
-      t += motion->kind == MCL_MOTION_DIFFERENTIAL ? motion->m1 + motion->m2 : motion->m1;
-    }
-    const double heading = t + (motion->kind == MCL_MOTION_DIFFERENTIAL ? motion->m1 : std::atan2(motion->first_s, motion->first_c));
-    // every pose moves along ITS heading: the set's mean moves by the translation times the mean resultant length of the headings
-    // (next to nothing for a set that points everywhere), and a heading error turns into a lateral one over the translation -
-    // mt * sigma_theta for a narrow set, at most mt / sqrt(2) per axis for headings all around
-    const double resultant = std::exp(-0.5 * st * st);
-    x += motion->mt * resultant * std::cos(heading);
-    y += motion->mt * resultant * std::sin(heading);
-    t += motion->kind == MCL_MOTION_DIFFERENTIAL ? motion->m1 + motion->m2 : motion->m1;
-    const double lateral = motion->mt * std::min(st, std::sqrt(0.5));
-    const double noise2 = motion->st * motion->st + lateral * lateral + (motion->kind == MCL_MOTION_OMNIDIRECTIONAL ? motion->s2 * motion->s2 : 0.0);
-    sx = std::sqrt(sx * sx + noise2);
-    sy = std::sqrt(sy * sy + noise2);
-    st = std::sqrt(st * st + motion->s1 * motion->s1 + (motion->kind == MCL_MOTION_DIFFERENTIAL ? motion->s2 * motion->s2 : 0.0));
-  } else if (motion) {
-    sx = std::sqrt(sx * sx + 0.02 * 0.02);
-    sy = std::sqrt(sy * sy + 0.02 * 0.02);
-    st = std::sqrt(st * st + 0.02 * 0.02);
-  }
-  if (!(std::isfinite(x) && std::isfinite(y) && std::isfinite(t) && std::isfinite(sx) && std::isfinite(sy) && std::isfinite(st))) return false;
-  // +- 4 sigma; a set reported as dispersed is closer to uniform than to normal: +- 2 sigma hold all of a uniform one
-  const double spans = ctx->patch_useful ? 8.0 : 4.0;
-  auto inverse_span = [spans](double sigma) { return sigma > 0.0 ? static_cast<float>(1.0 / (spans * sigma)) : 0.f; };
-  auto sigma_span_t = [](double sigma) { return sigma > 0.0 ? static_cast<float>(1.0 / (8.0 * sigma)) : 0.f; };
-  out->cx = x;
-  out->cy = y;
-  out->c0 = std::cos(t);
-  out->s0 = std::sin(t);
-  out->inv_x = inverse_span(sx);
-  out->inv_y = inverse_span(sy);
-  out->inv_t = sigma_span_t(std::min(st, kPi / 4.0));  // the heading bins never span more than the circle
-  out->t_off = 0.f;
-  if (ctx->tuning.key_warp && !(out->layout & 1u) && spans == 8.0) out->layout |= 4u;  // bins of equal mass over the +-4 sigma
-  // How the 20 bits are split: a run of the curve is roughly a cube of bins, and what a workgroup's LDS patch has to absorb is
-  // its extent in x (or y) PLUS its extent in heading times the scan's reach - so the split that minimises the sum of the two
-  // bin sizes, in cells: 8 sigma_xy / res / 2^b  +  8 sigma_theta reach / res / 2^(20 - 2 b), b = 4 .. 6.
-  out->bits_xy = 6;
-  if (ctx->tuning.key_bits_xy >= 4 && ctx->tuning.key_bits_xy <= 6) {
-    out->bits_xy = static_cast<uint32_t>(ctx->tuning.key_bits_xy);
-  } else if (ctx->tuning.key_bits_xy == 0 && ctx->resolution > 0.0 && std::isfinite(ctx->scan_extent)) {
-    const double reach = 0.5 * ctx->scan_extent / ctx->resolution;  // cells; scan_extent = max |x| + |y| of the scan, ~ sqrt 2 the longest beam
-    const double span_xy = spans * std::max(sx, sy) / ctx->resolution, span_t = 8.0 * std::min(st, kPi / 4.0) * reach;
-    double best = std::numeric_limits<double>::infinity();
-    for (uint32_t b = 4; b <= 6; ++b) {
-      const double cost = std::ldexp(span_xy, -static_cast<int>(b)) + std::ldexp(span_t, -static_cast<int>(20 - 2 * b));
-      if (cost < best) {
-        best = cost;
-        out->bits_xy = b;
-      }
-    }
-  }
-  return true;
-}
-void remember_cloud_estimate(mcl_ctx* ctx, const mcl_estimate& est) {
-  const double vx = est.covariance[0], vy = est.covariance[4], vt = est.covariance[8];
-  ctx->cloud_mean[0] = est.pose[2];
-  ctx->cloud_mean[1] = est.pose[3];
-  ctx->cloud_mean[2] = std::atan2(est.pose[1], est.pose[0]);
-  ctx->cloud_sigma[0] = vx > 0.0 ? std::sqrt(vx) : 0.0;
-  ctx->cloud_sigma[1] = vy > 0.0 ? std::sqrt(vy) : 0.0;
-  ctx->cloud_sigma[2] = std::isfinite(vt) ? (vt > 0.0 ? std::sqrt(vt) : 0.0) : kPi;  // infinite circular variance: all headings
-  ctx->have_cloud_estimate = std::isfinite(ctx->cloud_mean[0]) && std::isfinite(ctx->cloud_mean[1]) && std::isfinite(ctx->cloud_mean[2]) &&
-                             std::isfinite(ctx->cloud_sigma[0]) && std::isfinite(ctx->cloud_sigma[1]);
-}
-
 // ---- steps of beluga::Amcl::update (amcl_core.hpp:165-201) that mcl_update and sharded_update share ------------------------------------
 // control_action_window_ << control (RollingWindow<SE2,2>: newest first, extrapolates when short); the cycle takes the next step number.
 void advance_window(mcl_ctx* ctx, const Pose2& pose) {
@@ -936,28 +748,6 @@ void advance_window(mcl_ctx* ctx, const Pose2& pose) {
   ctx->have_window = true;
   ctx->step += 1;
 }
-// every_n (every_n.hpp:47-50, :181): the counter as this cycle leaves it; the policy fires where it is 0.  Stored once a path takes the cycle.
-uint64_t next_every_n(const mcl_ctx* ctx) { return (ctx->every_n_current + 1) % ctx->cfg.amcl.resample_interval; }
-// The resampling decision on the host from the totals of the normalised weights of n particles: :179 ThrunRecoveryProbabilityEstimator
-// (thrun_recovery_probability_estimator.hpp:69-89), :181 every_n's verdict `fires` [&& on_effective_size_drop] (on_effective_size_drop.hpp:45-49,
-// effective_sample_size.hpp:46-59).  The filters' reset (:184-186) is the caller's.
-struct HostPolicy {
-  double random_state_probability{0.0}, ess{-1.0};  // (ess -1: not evaluated)
-  bool resample{false};
-};
-HostPolicy host_policy(mcl_ctx* ctx, bool fires, double norm_sum, double norm_sumsq, uint64_t n) {
-  HostPolicy r;
-  const double average = norm_sum / static_cast<double>(n);
-  const double fast_average = ctx->fast(average), slow_average = ctx->slow(average);
-  if (std::abs(slow_average) >= std::numeric_limits<double>::epsilon())
-    r.random_state_probability = std::clamp(1.0 - fast_average / slow_average, 0.0, 1.0);
-  r.resample = fires;
-  if (fires && ctx->cfg.amcl.selective_resampling) {
-    r.ess = norm_sum == 0.0 ? 0.0 : (norm_sum * norm_sum) / norm_sumsq;
-    r.resample = r.ess < static_cast<double>(n) * 0.5;
-  }
-  return r;
-}
 // :200-201: a finite estimate becomes the pivot of the next estimate sums and the cloud estimate centres the next ordering keys; the
 // caller's *estimate and *info take the results (report: what the cycle read, each value captured where it read it).
 void finish_cycle(mcl_ctx* ctx, const mcl_estimate& est, const mcl_update_info& report, mcl_estimate* estimate, mcl_update_info* info) {
@@ -965,14 +755,12 @@ void finish_cycle(mcl_ctx* ctx, const mcl_estimate& est, const mcl_update_info& 
     ctx->pivot[0] = est.pose[2];
     ctx->pivot[1] = est.pose[3];
   }
-  remember_cloud_estimate(ctx, est);
+  ctx->cloud.remember(est);
   if (estimate) *estimate = est;
   if (info) *info = report;
 }
 
-// Whether the next LF launch goes to the LDS-patch kernel (where its other preconditions hold): by the verdict of the last
-// launch that has reported.  A dispersed set (global localisation) has no group that fits a patch, and the patch kernel's
-// workgroups carry a wave that would then do nothing.
+// The LDS-patch kernel's mirrored totals, as the planner (LfPlanner) and the counters read them.
 // synchronised: the stream is idle (the two 64-bit totals are consistent); otherwise the pair comes from the packed word the
 // kernel stores last (low 32 bits of each total in one 8-byte store: never torn; differences are taken modulo 2^32).
 void patch_totals(const mcl_ctx* ctx, uint64_t* planned, uint64_t* through, bool synchronised = false) {
@@ -986,86 +774,12 @@ void patch_totals(const mcl_ctx* ctx, uint64_t* planned, uint64_t* through, bool
   *planned = packed & 0xFFFFFFFFull;
   *through = packed >> 32;
 }
-// A workgroup of the patch kernel needs its 448 poses within a patch (64 x 64 cells less the margins) and within a few
-// hundredths of a radian.  From the last estimate's spread, taken as uniform (12 sigma_x sigma_y of area, sqrt(12) sigma_theta
-// of heading, at most the circle): the number of poses in such a volume.  Below an eighth of a workgroup no probe is worth it.
-bool hopelessly_sparse(const mcl_ctx* ctx) {
-  if (!ctx->have_cloud_estimate) return false;
-  const double side = 40.0 * ctx->resolution;
-  const double area = 12.0 * ctx->cloud_sigma[0] * ctx->cloud_sigma[1];
-  const double arc = std::min(2.0 * kPi, std::sqrt(12.0) * ctx->cloud_sigma[2]);
-  const double volume = std::max(area, side * side) * std::max(arc, 0.05);
-  const double poses = static_cast<double>(ctx->n) * (side * side * 0.05) / volume;
-  return poses < 448.0 / 8.0;
+// This cycle's LF kernel, decided on the first call of a cycle (LfPlanner::decide).
+LfPlanner::Mode plan_lf(mcl_ctx* ctx) {
+  uint64_t planned = 0, through = 0;
+  if (!ctx->lf_planner.decided()) patch_totals(ctx, &planned, &through);
+  return ctx->lf_planner.decide(ctx->lf_site(), ctx->cloud, planned, through);
 }
-bool wants_patches(mcl_ctx* ctx) {
-  if (ctx->tuning.lf_patch == 0) return false;
-  if (ctx->tuning.lf_patch != 1) return true;
-  uint64_t planned, through;
-  patch_totals(ctx, &planned, &through);
-  if (planned != ctx->patch_seen_planned) {  // a launch has reported since the last look
-    const uint64_t dp = (planned - ctx->patch_seen_planned) & 0xFFFFFFFFull, dt = (through - ctx->patch_seen_through) & 0xFFFFFFFFull;
-    ctx->patch_seen_planned = planned;
-    ctx->patch_seen_through = through;
-    ctx->patch_useful = 4 * dt >= dp;
-    if (!ctx->patch_useful) ctx->patch_probe_in = 16;
-  }
-  if (ctx->patch_useful) return true;
-  if (--ctx->patch_probe_in <= 0) {
-    ctx->patch_probe_in = 16;
-    return !hopelessly_sparse(ctx);  // a probe (3.7 ms instead of 1.1 on 1M dispersed particles: not where it cannot succeed)
-  }
-  return false;
-}
-
-// The LF launch of this cycle: the patch kernel, the gather kernel, or - for a set the patch kernel has reported as
-// dispersed (no probe due) - the wave-per-particle kernel, which needs no ordering pass.  Decided once per cycle, before the
-// propagation kernel (which emits the ordering keys); cleared by do_reweight.
-void decide_lf_mode(mcl_ctx* ctx) {
-  if (ctx->lf_mode.decided) return;
-  ctx->lf_mode.decided = true;
-  ctx->lf_mode.patches = false;
-  ctx->lf_mode.beams = false;
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM || ctx->off_grid()) return;
-  const bool palette = ctx->pal_count != 0 && ctx->tuning.lf_table == 0;
-  if (ctx->tuning.lf_variant == kLfBeamLanes) {
-    ctx->lf_mode.beams = palette;
-    return;
-  }
-  if (ctx->tuning.lf_variant != kLfSortedLanes) return;
-  ctx->lf_mode.patches = wants_patches(ctx);
-  ctx->lf_mode.beams = !ctx->lf_mode.patches && ctx->tuning.lf_patch == 1 && ctx->tuning.lf_dispersed == 1 && !ctx->patch_useful && palette &&
-                       !lf_set_is_small(ctx->n, ctx->tuning);
-}
-
-// Is the set spatially ordered before the reweight?  The one answer for k_propagate's keys, the order ahead and the LF kernel.
-bool wants_ordering(const mcl_ctx* ctx) {
-  if (ctx->n >= (1ull << 32)) return false;
-  if (ctx->off_grid()) return false;  // (a lane per particle in index order: these maps live in L2 or the scalar cache, locality buys nothing)
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) return ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles);
-  if (ctx->n < static_cast<uint64_t>(ctx->tuning.sort_min_particles)) return false;
-  if (ctx->lf_mode.decided && ctx->lf_mode.beams) return false;
-  return ctx->tuning.lf_variant == kLfSortedLanes && !(lf_set_is_small(ctx->n, ctx->tuning) && ctx->pal_count != 0 && ctx->tuning.lf_table == 0);
-}
-
-// Is the control action that came close enough to the one the order was predicted with (launch_order_ahead)?  What matters is that the
-// particles end up in the same ARRANGEMENT: a common shift does not change it, different noise scales or a translation along another
-// heading do.  Generous bounds: a miss costs look-ups that fit no LDS patch, a fallback costs the ordering passes on the critical path.
-bool samplers_close(const DiffDriveSampler& now, const DiffDriveSampler& predicted) {
-  if (now.kind != predicted.kind) return false;
-  auto ratio_ok = [](double a, double b) { return a <= 1.5 * b + 1e-3 && b <= 1.5 * a + 1e-3; };
-  if (!ratio_ok(now.s1, predicted.s1) || !ratio_ok(now.st, predicted.st) || !ratio_ok(now.s2, predicted.s2)) return false;
-  if (std::abs(now.mt - predicted.mt) > 0.3 * std::max(std::abs(predicted.mt), 0.02)) return false;
-  const double turn_now = now.kind == MCL_MOTION_DIFFERENTIAL ? now.m1 + now.m2 : now.m1;
-  const double turn_predicted = predicted.kind == MCL_MOTION_DIFFERENTIAL ? predicted.m1 + predicted.m2 : predicted.m1;
-  if (std::abs(turn_now - turn_predicted) > 0.15) return false;
-  // the direction of the translation in the robot's frame (differential: the first rotation; omnidirectional: `first`)
-  const double heading_now = now.kind == MCL_MOTION_DIFFERENTIAL ? now.m1 : std::atan2(now.first_s, now.first_c);
-  const double heading_predicted = predicted.kind == MCL_MOTION_DIFFERENTIAL ? predicted.m1 : std::atan2(predicted.first_s, predicted.first_c);
-  const double apart = std::abs(std::remainder(heading_now - heading_predicted, 2.0 * kPi));
-  return apart * std::max(std::abs(now.mt), std::abs(predicted.mt)) <= 0.05;  // (metres of lateral disagreement)
-}
-
 // fused (mcl_update): the scan staged by stage_points is pulled by the same kernel, and the ordering keys of the new poses
 // come out of it when the host knows where the set is (*keys_emitted).
 mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint32_t step, uint64_t scan_doubles = 0,
@@ -1074,19 +788,19 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
   const DiffDriveSampler sampler = make_sampler(pose, prev, ctx->cfg.motion, ctx->cfg.motion_kind, ctx->cfg.strafe_noise_from_translation);
   KeyFrame frame{};
   const SortScratch sort = ctx->sort_scratch();
-  if (keys_emitted) decide_lf_mode(ctx);  // the fused cycle: the reweight follows, and the keys depend on its kernel
+  if (keys_emitted) plan_lf(ctx);  // the fused cycle: the reweight follows, and the keys depend on its kernel
   // The order the previous cycle computed AHEAD for this step (launch_order_ahead) serves if the control action it predicted is close to the
   // one that came: then no keys, no ordering passes - the reweight follows the propagation at once.  Only locality depends on it.
   ctx->facts.order_accepted(false);
   bool use_ahead = false;
   if (keys_emitted) {
-    const SetFacts::OrderTaken ahead = ctx->facts.take_order_ahead(step, ctx->n, key_layout(ctx));
-    use_ahead = ahead.matched && ctx->tuning.order_ahead != 0 && wants_ordering(ctx) && samplers_close(sampler, ctx->order_sampler);
+    const SetFacts::OrderTaken ahead = ctx->facts.take_order_ahead(step, ctx->n, ctx->key_layout());
+    use_ahead = ahead.matched && ctx->tuning.order_ahead != 0 && ctx->wants_ordering() && samplers_close(sampler, ctx->order_sampler);
     if (use_ahead) ctx->order_ahead_used += 1;
     else if (ahead.recorded) ctx->order_ahead_missed += 1;
   }
   ctx->last_sampler = sampler;
-  const bool keys = !use_ahead && keys_emitted && wants_ordering(ctx) && predict_key_frame(ctx, &sampler, &frame);
+  const bool keys = !use_ahead && keys_emitted && ctx->wants_ordering() && ctx->predict_key_frame(&sampler, &frame);
   // (the normals of this step, if the previous cycle left them: k_noise_ahead)
   const bool ahead = ctx->d_noise.ptr && ctx->n > 65536 && ctx->facts.noise_ahead_serves(step, ctx->n, ctx->cfg.seed, ctx->cfg.shard_offset);
   launch_propagate(ctx->stream, ctx->cur(), ctx->n, sampler, ctx->cfg.seed, step, ctx->cfg.shard_offset,
@@ -1137,16 +851,16 @@ mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = 
     }
   }
   stage_begin(ctx, MCL_STAGE_REWEIGHT);
-  decide_lf_mode(ctx);
-  const mcl_ctx::LfMode mode = ctx->lf_mode;
-  const bool ordered = wants_ordering(ctx);  // (asked while this cycle's mode is decided)
-  ctx->lf_mode.decided = false;              // the next cycle decides again
+  const LfPlanner::Mode mode = plan_lf(ctx);
+  const bool ordered = ctx->wants_ordering();  // (asked while this cycle's mode is decided)
+  const bool dispersed = ctx->lf_planner.gathers_dispersed(ctx->tuning);
+  ctx->lf_planner.mode_consumed();  // the next cycle decides again
   const SortScratch sort = ctx->sort_scratch();
   const bool have_order = ctx->facts.take_order_accepted();  // (launch_order_ahead's, accepted by this cycle's propagation)
   if (ordered && !have_order) {
     KeyFrame frame{};
     // The ordering also serves the beam model: both kernels gather the pose records through sort.perm.
-    const bool have_frame = !keys_ready && predict_key_frame(ctx, nullptr, &frame);
+    const bool have_frame = !keys_ready && ctx->predict_key_frame(nullptr, &frame);
     launch_order_particles(ctx->stream, ctx->cur(), ctx->n, &sort, have_frame ? &frame : nullptr, keys_ready, frame.layout);
   }
   if (ctx->is_ndt()) {
@@ -1165,7 +879,7 @@ mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = 
         ctx->stream,
         LfReweightArgs{.p = ctx->cur(), .n = ctx->n, .f = ctx->field_view(), .d_points = ctx->d_points.ptr, .B = static_cast<uint32_t>(B),
                        .sort = ordered ? &sort : nullptr, .patches = mode.patches, .beams = mode.beams,
-                       .dispersed = !mode.patches && (ctx->tuning.lf_far_tiles == 2 || (ctx->tuning.lf_patch == 1 && !ctx->patch_useful)),
+                       .dispersed = dispersed,
                        .scan_cells = ctx->scan_extent / ctx->resolution, .unit_weights = unit_weights,
                        .stats = PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
                                            reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotPatchMirror),
@@ -1397,8 +1111,8 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       // after the NEXT propagation - through the predicted control action (this cycle's) and the frame of that set as the host predicts it
       // from the last estimate it has, moved twice -, and the ordering passes run behind the cycle's last kernel, while the host is away.
       KeyFrame ahead_frame{};
-      const bool order_keys = noise_in_draw && ctx->done_armed && ctx->tuning.order_ahead != 0 && max_p < (1ull << 32) && wants_ordering(ctx) &&
-                              predict_key_frame(ctx, &ctx->last_sampler, &ahead_frame, 2);
+      const bool order_keys = noise_in_draw && ctx->done_armed && ctx->tuning.order_ahead != 0 && max_p < (1ull << 32) && ctx->wants_ordering() &&
+                              ctx->predict_key_frame(&ctx->last_sampler, &ahead_frame, 2);
       launch_resample_draw_and_estimate(ctx->stream, ctx->cur(), ctx->cdf_tree(), d_total, ctx->other(), ra, gv, fc, hp,
                                         ctx->pivot[0], ctx->pivot[1], ctx->d_est_partials.ptr, ctx->d_scalars.ptr + kSlotEstimate,
                                         ctx->hd_scalars + kSlotEstimate, ctx->done_armed ? &done : nullptr,
@@ -1412,7 +1126,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       if (order_keys) {
         const SortScratch sort = ctx->sort_scratch();
         launch_order_ahead(ctx->stream, max_p, &sort);
-        ctx->facts.order_ahead_recorded(step + 1, max_p, key_layout(ctx));
+        ctx->facts.order_ahead_recorded(step + 1, max_p, ctx->key_layout());
         ctx->order_sampler = ctx->last_sampler;
       }
       if (opt.estimate_enqueued) *opt.estimate_enqueued = true;
@@ -1932,28 +1646,6 @@ mcl_status do_cluster_labels(mcl_ctx* ctx, const mcl_cluster_params& cp, uint32_
   return MCL_OK;
 }
 
-
-// Contiguous, balanced split of [0, n_total) over the ranks.
-void shard_bounds(uint64_t n_total, uint32_t world, uint32_t rank, uint64_t* first, uint64_t* count) {
-  const uint64_t base = n_total / world, rem = n_total % world;
-  *first = rank * base + std::min<uint64_t>(rank, rem);
-  *count = base + (rank < rem ? 1 : 0);
-}
-
-// The ancestor exchange for the output slots [first_slot, first_slot + m) of views::sample | random_intersperse: every
-// slot's point of the global CDF goes to the shard that owns it, which answers with the state.  Leaves the targets in
-// d_targets, the replies (request order) in d_replies_in and the slot of every request in d_route_order.
-// d_plan (optional): {total, random state probability} on the device (launch_shard_plan) instead of the two values.
-// Entries per pair of ranks in the fixed-capacity exchange: what a shard's m output slots ask of one other shard - m / world on average,
-// the shards' weight sums being those of equal random samples of one set - plus `permille` / 1000 - 1 of it, eight standard deviations
-// of the binomial count and 64.  Every rank derives the same number from the same arguments.
-uint64_t padded_capacity(uint64_t n_total, uint32_t world, uint32_t permille) {
-  const uint64_t m_max = (n_total + world - 1) / world;
-  const double mean = static_cast<double>(m_max) / world;
-  const double cap = mean * (permille / 1000.0) + 8.0 * std::sqrt(mean) + 64.0;
-  return (static_cast<uint64_t>(cap) + 63u) & ~63ull;
-}
-
 // The same exchange without a host read in the middle of the cycle: every pair of ranks moves `cap` entries whatever the counts are
 // (requests: cap doubles, NaN = none; replies: cap states), so that the sizes of both all-to-alls are known before anything is
 // computed.  6 % more bytes than the exact form; a rank whose requests to one shard do not fit sets its
@@ -1994,6 +1686,10 @@ mcl_status sharded_draw_padded(mcl_ctx* ctx, const double* d_intervals, uint64_t
   return comm_exchange(ctx, ctx->d_replies_out.ptr, reply_bytes.data(), ctx->d_replies_in.ptr, reply_bytes.data());
 }
 
+// The ancestor exchange for the output slots [first_slot, first_slot + m) of views::sample | random_intersperse: every
+// slot's point of the global CDF goes to the shard that owns it, which answers with the state.  Leaves the targets in
+// d_targets, the replies (request order) in d_replies_in and the slot of every request in d_route_order.
+// d_plan (optional): {total, random state probability} on the device (launch_shard_plan) instead of the two values.
 mcl_status sharded_draw(mcl_ctx* ctx, double random_state_probability, double total, const double* d_intervals, uint64_t first_slot,
                         uint64_t m, const double* d_plan = nullptr) {
   const uint32_t world = ctx->comm_world, rank = ctx->comm_rank;
@@ -2087,28 +1783,12 @@ mcl_status sharded_resample_kld(mcl_ctx* ctx, double random_state_probability, d
   uint64_t new_first, new_n;
   shard_bounds(n_out, world, rank, &new_first, &new_n);
   MCL_HIP(ctx, ctx->d_new_shard.ensure(std::max<uint64_t>(4 * new_n, 4)));
-  auto overlap = [](uint64_t a0, uint64_t a1, uint64_t b0, uint64_t b1) {
-    const uint64_t lo = std::max(a0, b0), hi = std::min(a1, b1);
-    return hi > lo ? hi - lo : 0;
-  };
   std::vector<uint64_t> send(world), recv(world);
   for (const Block& b : blocks) {
     if (b.pos >= n_out) break;
-    uint64_t received = 0;
-    for (uint32_t q = 0; q < world; ++q) {
-      uint64_t q_lo, q_m, span_first, span_n;
-      shard_bounds(b.cnt, world, q, &q_lo, &q_m);
-      shard_bounds(n_out, world, q, &span_first, &span_n);
-      uint64_t my_lo, my_m;
-      shard_bounds(b.cnt, world, rank, &my_lo, &my_m);
-      send[q] = overlap(b.pos + my_lo, std::min(b.pos + my_lo + my_m, n_out), span_first, span_first + span_n) * 4 * sizeof(double);
-      recv[q] = overlap(b.pos + q_lo, std::min(b.pos + q_lo + q_m, n_out), new_first, new_first + new_n) * 4 * sizeof(double);
-      received += recv[q];
-    }
-    const uint64_t out0 = std::max(b.pos, new_first) - new_first;
-    if (const mcl_status s = comm_exchange(ctx, ctx->d_cand_states.ptr + 4 * b.offset, send.data(),
-                                           ctx->d_new_shard.ptr + 4 * std::min(out0, new_n), recv.data())) return s;
-    (void)received;
+    const uint64_t out0 = rebalance_block(b.pos, b.cnt, n_out, world, rank, send.data(), recv.data());
+    if (const mcl_status s = comm_exchange(ctx, ctx->d_cand_states.ptr + 4 * b.offset, send.data(), ctx->d_new_shard.ptr + 4 * out0, recv.data()))
+      return s;
   }
   if (const mcl_status s = mcl_load_shard(ctx, ctx->d_new_shard.ptr, new_n, new_first)) return s;
   *n_out_total = n_out;
@@ -2161,7 +1841,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const Measurement& sc
   bool keys_ready = false;
   if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, scan.doubles, &keys_ready)) return s;  // :174-175
   if (const mcl_status s = do_reweight(ctx, scan, true, keys_ready)) return s;                                            // :176
-  ctx->every_n_current = next_every_n(ctx);  // every_n does not depend on data
+  ctx->every_n_current = next_every_n(ctx->every_n_current, ctx->cfg.amcl.resample_interval);  // every_n does not depend on data
   const bool fires = ctx->every_n_current == 0;
   // :177 normalise by the GLOBAL sum: shard sums gathered, added in rank order by every rank
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
@@ -2266,7 +1946,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const Measurement& sc
     norm_sum += h_stats[r].norm_sum;
     norm_sumsq += h_stats[r].norm_sumsq;
   }
-  const HostPolicy decision = host_policy(ctx, fires, norm_sum, norm_sumsq, n_total);  // :179, :181
+  const HostPolicy decision = host_policy(ctx->slow, ctx->fast, ap.selective_resampling != 0, fires, norm_sum, norm_sumsq, n_total);  // :179, :181
   const double random_state_probability = decision.random_state_probability;
   if (decision.resample) {
     if (random_state_probability > 0.0) {  // :184-186
@@ -2742,9 +2422,7 @@ struct InstallSet {
   // the estimate behind the ordering keys: as it was / none (a bounding-box pass until the next estimate) / mean and sigma of x, y, theta
   enum { kCloudKept, kCloudUnknown, kCloudGiven } cloud;
   double cloud_mean[3], cloud_sigma[3];
-  // the LF patch statistics: as they were / earlier launches' reports are history, the next LF launch finds out / history, and the set is
-  // what the patch kernel would report as dispersed: the first cycle already takes the kernel for dispersed sets
-  enum { kPatchesKept, kPatchesFresh, kPatchesDispersed } patches;
+  LfPlanner::Installed patches;  // the LF patch statistics: as they were / history / history, and the set is dispersed
 };
 void install_set(mcl_ctx* ctx, const InstallSet& s) {
   ctx->facts.set_replaced(s.unit_weights);
@@ -2752,17 +2430,11 @@ void install_set(mcl_ctx* ctx, const InstallSet& s) {
   if (s.global == InstallSet::kGlobalShares) ctx->global_n = 0;
   if (s.global != InstallSet::kGlobalKept) ctx->global_n_unknown = s.global == InstallSet::kGlobalAsked && ctx->have_comm && ctx->comm_world > 1;
   if (s.force_update) ctx->force_update = true;
-  if (s.cloud != InstallSet::kCloudKept) ctx->have_cloud_estimate = s.cloud == InstallSet::kCloudGiven;
-  if (s.cloud == InstallSet::kCloudGiven)
-    for (int k = 0; k < 3; ++k) {
-      ctx->cloud_mean[k] = s.cloud_mean[k];
-      ctx->cloud_sigma[k] = s.cloud_sigma[k];
-    }
-  if (s.patches != InstallSet::kPatchesKept) {
-    patch_totals(ctx, &ctx->patch_seen_planned, &ctx->patch_seen_through);
-    ctx->patch_useful = s.patches == InstallSet::kPatchesFresh;
-    if (s.patches == InstallSet::kPatchesDispersed) ctx->patch_probe_in = 16;
-  }
+  if (s.cloud == InstallSet::kCloudGiven) ctx->cloud.set(s.cloud_mean, s.cloud_sigma);
+  else if (s.cloud == InstallSet::kCloudUnknown) ctx->cloud.forget();
+  uint64_t planned = 0, through = 0;
+  if (s.patches != LfPlanner::Installed::kKept) patch_totals(ctx, &planned, &through);
+  ctx->lf_planner.set_installed(s.patches, planned, through);
 }
 }  // namespace
 extern "C" {
@@ -2805,7 +2477,7 @@ mcl_status mcl_initialize_normal(mcl_ctx* ctx, const double mean_xytheta[3], con
   install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalShares, .force_update = true /* amcl_core.hpp:136 */,
                     .cloud = InstallSet::kCloudGiven, .cloud_mean = {mean_xytheta[0], mean_xytheta[1], mean_xytheta[2]},
                     .cloud_sigma = {std::sqrt(std::max(cov[0], 0.0)), std::sqrt(std::max(cov[4], 0.0)), std::sqrt(std::max(cov[8], 0.0))},
-                    .patches = InstallSet::kPatchesFresh});
+                    .patches = LfPlanner::Installed::kFresh});
   return MCL_OK;
 }
 
@@ -2821,7 +2493,7 @@ mcl_status mcl_set_particles(mcl_ctx* ctx, const double* states, const double* w
     MCL_HIP(ctx, hipMemcpy(ctx->cur().w, weights, n * sizeof(double), hipMemcpyHostToDevice));
   }
   install_set(ctx, {.n = n, .unit_weights = false, .global = InstallSet::kGlobalAsked, .force_update = true, .cloud = InstallSet::kCloudUnknown,
-                    .patches = InstallSet::kPatchesFresh});
+                    .patches = LfPlanner::Installed::kFresh});
   return MCL_OK;
 }
 
@@ -2932,19 +2604,14 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   if (ctx->n == 0) return MCL_OK;  // amcl_core.hpp:166-168 -> nullopt
   const Pose2 pose = pose_from(control_pose);
   // update_policy_ = on_motion (policies/on_motion.hpp:63-67,121-133); evaluated even when forced (:170)
-  bool moved = true;
-  if (ctx->have_latest) {
-    const Pose2 delta = pose_mul(pose_inverse(ctx->latest), pose);
-    moved = std::sqrt(delta.x * delta.x + delta.y * delta.y) > ctx->cfg.amcl.update_min_d ||
-            std::abs(rot_log(delta.r)) > ctx->cfg.amcl.update_min_a;
-  }
+  const bool moved = !ctx->have_latest || moved_enough(ctx->latest, pose, ctx->cfg.amcl.update_min_d, ctx->cfg.amcl.update_min_a);
   if (!moved && !ctx->force_update) return MCL_OK;
   // Everything that can fail without touching a particle is checked before the filter state moves: an update that
   // fails here leaves the motion unconsumed, as if it had not been called (the reference has no partial-update state).
   auto consume_motion = [&] { if (moved) { ctx->latest = pose; ctx->have_latest = true; } };
   if (const mcl_status s = bind_device(ctx)) return s;
   if (const mcl_status s = reweight_preconditions(ctx, m.doubles / 2)) return s;
-  ctx->lf_mode.decided = false;  // whatever an earlier, failed cycle left behind
+  ctx->lf_planner.cycle_begins();  // whatever an earlier, failed cycle left behind
   if (ctx->have_comm && ctx->comm_world > 1) {
     // before any rank-local state moves: the ranks must not diverge
     if (const mcl_status s = sharded_preconditions(ctx)) return s;
@@ -2970,7 +2637,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   if (const mcl_status s = do_reweight(ctx, m, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0)) return s;  // :176
   // Small sets (the reference's own sizes): everything behind the reweight in ONE launch of one workgroup and one synchronisation
   // (k_small_tail) - the policies are evaluated on the device, the host keeps the recovery filters' state.
-  const uint64_t every_n = next_every_n(ctx);  // :181 (stored by the path that takes the cycle)
+  const uint64_t every_n = next_every_n(ctx->every_n_current, ap.resample_interval);  // :181 (stored by the path that takes the cycle)
   const bool fires = every_n == 0;
   if (ctx->tuning.small_fused != 0 && !ctx->off_grid() && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096) {
     SmallTail t{};
@@ -3063,7 +2730,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   } else {
     if (const mcl_status s = do_normalize(ctx, std::numeric_limits<double>::quiet_NaN(), &stats)) return s;  // :177
     ctx->every_n_current = every_n;
-    decision = host_policy(ctx, fires, stats.norm_sum, stats.norm_sumsq, ctx->n);  // :179, :181
+    decision = host_policy(ctx->slow, ctx->fast, ap.selective_resampling != 0, fires, stats.norm_sum, stats.norm_sumsq, ctx->n);  // :179, :181
     if (decision.resample) {
       if (ctx->is_ndt())  // :182, the random state generator of ndt_amcl_node (its failure leaves the state the reference's throw leaves)
         if (const mcl_status s = prepare_ndt_random(ctx, decision.random_state_probability)) return s;
@@ -3098,7 +2765,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
     decision.random_state_probability = ctx->h_scalars[kSlotPolicyP];
   }
   const mcl_update_info report{1, decision.resample, ctx->n, stats.sum, decision.ess, decision.random_state_probability};
-  finish_cycle(ctx, est, report, estimate, info);  // (remember_cloud_estimate: where the ordering keys of the next cycle are centred)
+  finish_cycle(ctx, est, report, estimate, info);  // (cloud.remember: where the ordering keys of the next cycle are centred)
   if (host_timed) {
     const auto ns = [](auto a, auto b) { return static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count()); };
     ctx->host_ns[0] += ns(t_entry, t_first);
@@ -3345,7 +3012,7 @@ mcl_status mcl_load_shard(mcl_ctx* ctx, const double* d_states, uint64_t n, uint
   launch_fill(ctx->stream, ctx->cur().w, n, 1.0);  // particle_traits.hpp:105
   MCL_HIP(ctx, hipGetLastError());
   install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalKept, .force_update = false, .cloud = InstallSet::kCloudUnknown,
-                    .patches = InstallSet::kPatchesKept});
+                    .patches = LfPlanner::Installed::kKept});
   ctx->cfg.shard_offset = shard_offset;
   return MCL_OK;
 }
@@ -3402,7 +3069,7 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
     launch_init_from_map(ctx->stream, ctx->cur(), n, ctx->cfg.seed, ctx->cfg.shard_offset, ctx->grid_view(), ctx->landmark_random);
     MCL_HIP(ctx, hipGetLastError());
     install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalShares, .force_update = true, .cloud = InstallSet::kCloudKept,
-                      .patches = InstallSet::kPatchesKept});
+                      .patches = LfPlanner::Installed::kKept});
     return MCL_OK;
   }
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no map set");
@@ -3423,7 +3090,7 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
   install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalShares,
                     .force_update = true /* beluga_ros/include/beluga_ros/amcl.hpp:197 */, .cloud = InstallSet::kCloudGiven,
                     .cloud_mean = {cx + ctx->origin.x, cy + ctx->origin.y, 0.0}, .cloud_sigma = {ex / std::sqrt(12.0), ey / std::sqrt(12.0), kPi},
-                    .patches = InstallSet::kPatchesDispersed});
+                    .patches = LfPlanner::Installed::kDispersed});
   return MCL_OK;
 }
 
@@ -3575,7 +3242,7 @@ mcl_status mcl_debug_order(mcl_ctx* ctx, uint32_t* perm, uint32_t* keys) {
   if (const mcl_status s = bind_device(ctx)) return s;
   const SortScratch sort = ctx->sort_scratch();
   KeyFrame frame{};
-  const bool have_frame = predict_key_frame(ctx, nullptr, &frame);
+  const bool have_frame = ctx->predict_key_frame(nullptr, &frame);
   launch_order_particles(ctx->stream, ctx->cur(), ctx->n, &sort, have_frame ? &frame : nullptr, false, frame.layout);
   MCL_HIP(ctx, hipGetLastError());
   MCL_HIP(ctx, hipMemcpyAsync(perm, sort.perm, ctx->n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
