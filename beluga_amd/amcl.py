@@ -299,6 +299,18 @@ class Amcl:
                  options: Optional[dict] = None):
         """options: library switches applied before the map is installed (mcl_set_option), e.g. {"field_build": 1} to build
         the likelihood field with the device's exact distance transform instead of the reference's wavefront on the host."""
+        cfg = self._configure(grid, motion, sensor, params, seed=seed, device=device, shard_offset=shard_offset,
+                              shard_capacity=shard_capacity, hip_stream=hip_stream)
+        ctx = capi._ctx()
+        st = self._lib.mcl_create(C.byref(cfg), C.byref(ctx))
+        if st != capi.MCL_OK:
+            msg = self._lib.mcl_last_error(None).decode()
+            self._ctx = None
+            raise capi.MclError(st, msg)
+        self._attach(ctx, grid, options, owned=True)
+
+    def _configure(self, grid, motion, sensor, params, *, seed=0, device=0, shard_offset=0, shard_capacity=0, hip_stream=0):
+        """The mcl_config of these constructor arguments (and what the object remembers of them)."""
         self._lib = capi.load()
         cfg = capi.Config()
         self._lib.mcl_default_config(C.byref(cfg))
@@ -349,12 +361,13 @@ class Amcl:
         cfg.hip_stream = hip_stream or None
         self.params = params
         self._cfg = cfg
-        self._ctx = capi._ctx()
-        st = self._lib.mcl_create(C.byref(cfg), C.byref(self._ctx))
-        if st != capi.MCL_OK:
-            msg = self._lib.mcl_last_error(None).decode()
-            self._ctx = None
-            raise capi.MclError(st, msg)
+        return cfg
+
+    def _attach(self, ctx, grid, options, owned):
+        """Binds the object to a created context.  owned = False: a member of an AmclBatch, which destroys it."""
+        cfg = self._cfg
+        self._ctx = ctx
+        self._owned = owned
         self._shape = None
         self._est, self._info = capi.Estimate(), capi.UpdateInfo()
         self._est_ref, self._info_ref = C.byref(self._est), C.byref(self._info)
@@ -367,11 +380,12 @@ class Amcl:
         self._update_fn.argtypes = [capi._ctx, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         for name, value in (options or {}).items():
             self.set_option(name, value)
-        self.update_map(grid)
+        if grid is not None:  # (only a member of an AmclBatch may start without a map)
+            self.update_map(grid)
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
-        if getattr(self, "_ctx", None):
+        if getattr(self, "_ctx", None) and getattr(self, "_owned", True):
             self._lib.mcl_destroy(self._ctx)
             self._ctx = None
 
@@ -806,6 +820,131 @@ class Amcl:
         cnt = (C.c_uint64 * len(capi.STAGES))()
         self._check(self._lib.mcl_profile_read(self._ctx, ms, cnt, int(reset)))
         return {name: (ms[i], cnt[i]) for i, name in enumerate(capi.STAGES)}
+
+
+class AmclBatch:
+    """A fleet of small filters that share their launches (mcl_batch_*): one update call, three kernel launches for all members whose
+    cycle is the small one, one synchronisation.  specs: one entry per member, the argument set of Amcl(...) - a dict of keyword
+    arguments, or a tuple of positional ones that may end with such a dict; `grid` may be None (the member gets its map later).
+    Every member is on one device and one stream (`hip_stream`: all 0, or all the same).  members[i] are Amcl objects bound to the
+    batch's contexts: every Amcl method works on them between batch updates; they do not own their contexts (close() does nothing)."""
+
+    def __init__(self, specs):
+        self._lib = capi.load()
+        self.members = []
+        grids, options, cfgs = [], [], (capi.Config * len(specs))()
+        for i, spec in enumerate(specs):
+            args, kwargs = (), {}
+            if isinstance(spec, dict):
+                kwargs = dict(spec)
+            else:
+                args = tuple(spec)
+                if args and isinstance(args[-1], dict):
+                    args, kwargs = args[:-1], dict(args[-1])
+            names = ("grid", "motion", "sensor", "params")
+            kwargs.update(zip(names, args))
+            member = Amcl.__new__(Amcl)
+            grids.append(kwargs.pop("grid", None))
+            options.append(kwargs.pop("options", None))
+            cfgs[i] = member._configure(grids[-1], kwargs.pop("motion"), kwargs.pop("sensor"), kwargs.pop("params", AmclParams()), **kwargs)
+            self.members.append(member)
+        self._batch = capi._batch()
+        st = self._lib.mcl_batch_create(cfgs, len(specs), C.byref(self._batch))
+        if st != capi.MCL_OK:
+            self._batch = None
+            for member in self.members:
+                member._ctx = None
+            raise capi.MclError(st, self._lib.mcl_batch_last_error(None).decode())
+        n = len(self.members)
+        for i, member in enumerate(self.members):
+            ctx = capi._ctx()
+            self._check(self._lib.mcl_batch_member(self._batch, i, C.byref(ctx)))
+            member._attach(ctx, grids[i], options[i], owned=False)
+        self._controls = np.zeros((n, 4), dtype=np.float64)
+        self._offsets = np.zeros(n + 1, dtype=np.uint64)
+        self._estimates = (capi.Estimate * n)()
+        self._infos = (capi.UpdateInfo * n)()
+        self._statuses = (C.c_int32 * n)()
+        self._est_view = np.frombuffer(self._estimates, dtype=np.float64).reshape(n, 13)
+        self._have_info = False
+        self.last_status = capi.MCL_OK
+
+    def close(self):
+        if getattr(self, "_batch", None):
+            self._lib.mcl_batch_destroy(self._batch)
+            self._batch = None
+            for member in self.members:
+                member._ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return len(self.members)
+
+    def _check(self, st):
+        if st != capi.MCL_OK:
+            raise capi.MclError(st, self._lib.mcl_batch_last_error(self._batch).decode())
+
+    def update(self, control_actions, measurements, check: bool = True):
+        """Amcl::update on every member: control_actions[i] and measurements[i] (points[n_i, 2]) are member i's.  Returns a list with
+        (pose, covariance) or None per member, bit for bit what members[i].update(...) returns.  check = False: a member's failure does
+        not raise; its entry is None and `statuses` / `last_status` tell."""
+        n = len(self.members)
+        if len(control_actions) != n or len(measurements) != n:
+            raise ValueError("AmclBatch.update: one control action and one measurement per member")
+        for i in range(n):
+            self._controls[i] = control_actions[i]
+        scans = [np.ascontiguousarray(m, dtype=np.float64).reshape(-1, 2) for m in measurements]
+        self._offsets[1:] = np.cumsum([len(m) for m in scans])
+        points = np.concatenate(scans) if n else np.zeros((0, 2))
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        self.last_status = self._lib.mcl_batch_update(self._batch, _dp(self._controls), _dp(points), self._offsets.ctypes.data_as(capi.c_u64_p),
+                                                      self._estimates, self._infos, self._statuses)
+        self._have_info = True
+        if check:
+            self._check(self.last_status)
+        out = []
+        for i in range(n):
+            if self._statuses[i] != capi.MCL_OK or not self._infos[i].updated:
+                out.append(None)
+                continue
+            e = self._est_view[i].copy()
+            out.append((e[:4], e[4:13].reshape(3, 3)))
+        return out
+
+    def update_offsets(self, control_actions, points_xy, point_offsets):
+        """The C call as it is: all scans in one points_xy[total, 2] with point_offsets[n + 1]; returns the call's status."""
+        ctrl = np.ascontiguousarray(control_actions, dtype=np.float64).reshape(len(self.members), 4)
+        pts = np.ascontiguousarray(points_xy, dtype=np.float64)
+        off = np.ascontiguousarray(point_offsets, dtype=np.uint64)
+        self.last_status = self._lib.mcl_batch_update(self._batch, _dp(ctrl), _dp(pts), off.ctypes.data_as(capi.c_u64_p), self._estimates,
+                                                      self._infos, self._statuses)
+        self._have_info = True
+        return self.last_status
+
+    @property
+    def statuses(self):
+        """Every member's status of the last update."""
+        return [int(s) for s in self._statuses]
+
+    @property
+    def last_infos(self):
+        """mcl_update_info of every member's last batch update, as Amcl.last_info's dicts (None before the first update)."""
+        if not self._have_info:
+            return None
+        return [{"updated": bool(info.updated), "resampled": bool(info.resampled), "num_particles": info.num_particles,
+                 "weight_sum": info.weight_sum, "ess": info.effective_sample_size,
+                 "random_state_probability": info.random_state_probability} for info in self._infos]
+
+    def counter(self, name: str) -> int:
+        """cycles, kernel_launches, members_fused, members_alone (mcl_batch_get_counter)."""
+        value = C.c_uint64(0)
+        self._check(self._lib.mcl_batch_get_counter(self._batch, name.encode(), C.byref(value)))
+        return value.value
 
 
 def make_laser_scan(ranges, angle_min, angle_increment, range_min, range_max, origin_se3=(0, 0, 0, 1, 0, 0, 0), max_beams=2 ** 64 - 1,

@@ -133,6 +133,7 @@ class DeviceView(C.Structure):
 
 
 _ctx = C.c_void_p
+_batch = C.c_void_p
 
 _SIGNATURES = {
     "mcl_default_config": (None, [C.POINTER(Config)]),
@@ -212,6 +213,13 @@ _SIGNATURES = {
     "mcl_update_bearings": (C.c_int32, [_ctx, c_double_p, c_double_p, c_u32_p, C.c_uint64, C.POINTER(Estimate), C.POINTER(UpdateInfo)]),
     "mcl_reweight_landmarks": (C.c_int32, [_ctx, c_double_p, c_u32_p, C.c_uint64]),
     "mcl_reweight_bearings": (C.c_int32, [_ctx, c_double_p, c_u32_p, C.c_uint64]),
+    "mcl_batch_create": (C.c_int32, [C.POINTER(Config), C.c_uint32, C.POINTER(_batch)]),
+    "mcl_batch_destroy": (None, [_batch]),
+    "mcl_batch_size": (C.c_int32, [_batch, c_u32_p]),
+    "mcl_batch_member": (C.c_int32, [_batch, C.c_uint32, C.POINTER(_ctx)]),
+    "mcl_batch_update": (C.c_int32, [_batch, c_double_p, c_double_p, c_u64_p, C.POINTER(Estimate), C.POINTER(UpdateInfo), C.POINTER(C.c_int32)]),
+    "mcl_batch_get_counter": (C.c_int32, [_batch, C.c_char_p, c_u64_p]),
+    "mcl_batch_last_error": (C.c_char_p, [_batch]),
     "mcl_version": (C.c_char_p, []),
     "mcl_measurement_build": (C.c_int, []),
 }

@@ -1,0 +1,43 @@
+// batch_host.cpp — see batch_host.h.
+#include "batch_host.h"
+
+#include <algorithm>
+
+namespace mcl {
+
+bool batch_member_fused(const BatchMemberFacts& m) {
+  const bool likelihood_field = m.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD || m.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB;
+  return likelihood_field && !m.sharded && m.small_fused && m.n >= 1 && m.n <= kBatchMaxParticles && m.max_particles >= 1 &&
+         m.max_particles <= kBatchMaxParticles && m.palette_beams && !m.profiling;
+}
+
+BatchGrid batch_layout(const uint64_t* n, const uint32_t* lds, uint32_t members, uint32_t* first_propagate, uint32_t* first_reweight) {
+  BatchGrid g{members, 0, 0, 0};
+  for (uint32_t m = 0; m < members; ++m) {
+    first_propagate[m] = g.propagate_blocks;
+    first_reweight[m] = g.reweight_blocks;
+    g.propagate_blocks += batch_propagate_blocks(n[m]);
+    g.reweight_blocks += batch_reweight_blocks(n[m]);
+    g.reweight_lds = std::max(g.reweight_lds, lds[m]);
+  }
+  return g;
+}
+
+const char* batch_check_configs(const mcl_config* cfgs, uint32_t count) {
+  if (!cfgs) return "mcl_batch_create: null configs";
+  if (count < 1 || count > kBatchMaxMembers) return "mcl_batch_create: count must be 1 .. 1024";
+  for (uint32_t i = 1; i < count; ++i) {
+    if (cfgs[i].device_id != cfgs[0].device_id) return "mcl_batch_create: every member must be on the same device";
+    if (cfgs[i].hip_stream != cfgs[0].hip_stream) return "mcl_batch_create: hip_stream must be NULL for every member or the same stream for all";
+  }
+  return nullptr;
+}
+
+const char* batch_check_offsets(const uint64_t* offsets, uint32_t members) {
+  if (!offsets) return "mcl_batch_update: null point_offsets";
+  for (uint32_t i = 0; i < members; ++i)
+    if (offsets[i + 1] < offsets[i]) return "mcl_batch_update: point_offsets decrease";
+  return nullptr;
+}
+
+}  // namespace mcl

@@ -1,0 +1,67 @@
+// batch_host.h — the arithmetic of a batch of small filters (mcl_batch_*) that touches no device memory: which members of a cycle share
+// the three launches, where each member's blocks lie in the two gridded launches, how a block finds its member, how much workgroup memory
+// the shared reweight needs, and the validation of mcl_batch_create's configs and mcl_batch_update's scan offsets.  context.hip calls
+// them between its launches; batch_member_of is also what the batched kernels run (kernels.hip).  Plain C++17, no HIP.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "beluga_mcl.h"
+#include "se2.h"  // MCL_HD
+
+namespace mcl {
+
+constexpr uint32_t kBatchMaxMembers = 1024;   // mcl_batch_create's count
+constexpr uint64_t kBatchMaxParticles = 4096;  // of a fused member: one workgroup of k_small_tail holds the set (kSmallMax)
+constexpr uint32_t kBatchPropagateBlock = 256;  // particles of a block of k_propagate_small (kBlock)
+constexpr uint32_t kBatchReweightBlock = 4;     // ... of k_reweight_lf_beams with a wave per particle (kBeamsBlock / kWave)
+
+// ---- which members share the launches ------------------------------------------------------------------------------------------------
+// What the predicate reads of a member in the cycle that is being prepared.
+struct BatchMemberFacts {
+  int sensor_kind;         // MCL_SENSOR_*
+  bool sharded;            // the context is one rank of a sharded filter
+  bool small_fused;        // option small_fused
+  uint64_t n;              // particles of the live set
+  uint64_t max_particles;  // min(max_particles, capacity): the candidates of a resampling
+  bool palette_beams;      // the cycle's reweight is k_reweight_lf_beams over the palette table, no ordering pass (lf_takes_beams)
+  bool profiling;          // stage profiling on: the member's own events bracket its own launches
+};
+// The member's own mcl_update would run exactly k_propagate_small, k_reweight_lf_beams with a wave per particle, k_small_tail.
+bool batch_member_fused(const BatchMemberFacts& m);
+
+// ---- where the members' blocks are ---------------------------------------------------------------------------------------------------
+MCL_HD uint32_t batch_propagate_blocks(uint64_t n) { return static_cast<uint32_t>((n + kBatchPropagateBlock - 1) / kBatchPropagateBlock); }
+MCL_HD uint32_t batch_reweight_blocks(uint64_t n) { return static_cast<uint32_t>((n + kBatchReweightBlock - 1) / kBatchReweightBlock); }
+// The launch geometry of a cycle's fused members.
+struct BatchGrid {
+  uint32_t members;           // = workgroups of k_batch_small_tail
+  uint32_t propagate_blocks;  // grid of k_batch_propagate
+  uint32_t reweight_blocks;   // grid of k_batch_reweight_lf_beams
+  uint32_t reweight_lds;      // its dynamic workgroup memory: the largest palette layout of the members
+};
+// n[m], lds[m] (lf_palette_lds of the member's field) for m < members  ->  first_propagate[m], first_reweight[m]: the member's first
+// block in each gridded launch (running sums; a member with n = 0 has no block and is never found), and the grids.
+BatchGrid batch_layout(const uint64_t* n, const uint32_t* lds, uint32_t members, uint32_t* first_propagate, uint32_t* first_reweight);
+// The member whose blocks include `block`: the LAST m with first_of(m) <= block (members without a block share their successor's first
+// block and are skipped).  Needs first_of(0) == 0 and block < the grid.  ceil(log2(members)) steps, each one read.
+template <class FirstOf>
+MCL_HD uint32_t batch_member_of(uint32_t members, uint32_t block, FirstOf first_of) {
+  uint32_t lo = 0, hi = members;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (first_of(mid) <= block) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// ---- validation ----------------------------------------------------------------------------------------------------------------------
+// mcl_batch_create: 1 .. kBatchMaxMembers configs on one device, their hip_stream all NULL or all the same stream.  nullptr: fine;
+// otherwise what is wrong.
+const char* batch_check_configs(const mcl_config* cfgs, uint32_t count);
+// mcl_batch_update: offsets[0 .. members] do not decrease.  nullptr: fine.
+const char* batch_check_offsets(const uint64_t* offsets, uint32_t members);
+
+}  // namespace mcl

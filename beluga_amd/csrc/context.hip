@@ -83,6 +83,7 @@ struct mcl_ctx {
   int device{0};
   hipStream_t stream{nullptr};
   bool own_stream{false};
+  mcl_batch* batch{nullptr};  // the batch that owns this context (mcl_batch_create): mcl_destroy leaves it alone
 
   uint64_t capacity{0};
   uint64_t n{0};
@@ -780,10 +781,27 @@ LfPlanner::Mode plan_lf(mcl_ctx* ctx) {
   if (!ctx->lf_planner.decided()) patch_totals(ctx, &planned, &through);
   return ctx->lf_planner.decide(ctx->lf_site(), ctx->cloud, planned, through);
 }
+// A member's cycle inside mcl_batch_update.  The host steps are the lone cycle's own, in the lone cycle's order; what differs is who
+// launches: where the cycle is the small one - k_propagate_small, k_reweight_lf_beams with a wave per particle, k_small_tail -
+// do_propagate, do_reweight and update_cycle fill `item` instead of launching, and the batch launches the three kernels once for all
+// such members (launch_batch_cycle), then calls small_tail_launched and finish_small_cycle for each.
+struct HeldCycle {
+  bool propagate_held{false};  // do_propagate held k_propagate_small back: do_reweight decides (fused) or launches it after all
+  bool fused{false};           // the member's cycle is the small one: nothing of it has been launched
+  bool pending{false};         // ... and its record is complete
+  BatchItem item{};
+  uint64_t every_n{0};         // the counter as the cycle leaves it
+};
+void launch_held_propagate(mcl_ctx* ctx, HeldCycle* hold) {
+  const BatchItem& it = hold->item;
+  launch_propagate(ctx->stream, it.p, it.n, it.smp, it.seed, it.step, it.index_offset, it.scan_src, it.scan_dst, it.scan_doubles, nullptr, nullptr,
+                   nullptr, 0);
+  hold->propagate_held = false;
+}
 // fused (mcl_update): the scan staged by stage_points is pulled by the same kernel, and the ordering keys of the new poses
 // come out of it when the host knows where the set is (*keys_emitted).
 mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint32_t step, uint64_t scan_doubles = 0,
-                        bool* keys_emitted = nullptr) {
+                        bool* keys_emitted = nullptr, HeldCycle* hold = nullptr) {
   stage_begin(ctx, MCL_STAGE_PROPAGATE);
   const DiffDriveSampler sampler = make_sampler(pose, prev, ctx->cfg.motion, ctx->cfg.motion_kind, ctx->cfg.strafe_noise_from_translation);
   KeyFrame frame{};
@@ -803,9 +821,24 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
   const bool keys = !use_ahead && keys_emitted && ctx->wants_ordering() && ctx->predict_key_frame(&sampler, &frame);
   // (the normals of this step, if the previous cycle left them: k_noise_ahead)
   const bool ahead = ctx->d_noise.ptr && ctx->n > 65536 && ctx->facts.noise_ahead_serves(step, ctx->n, ctx->cfg.seed, ctx->cfg.shard_offset);
-  launch_propagate(ctx->stream, ctx->cur(), ctx->n, sampler, ctx->cfg.seed, step, ctx->cfg.shard_offset,
-                   scan_doubles ? ctx->hd_points : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
-                   keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->facts.noise_ahead_count());
+  // (launch_propagate takes k_propagate_small for these arguments: no keys, at most 65536 particles)
+  if (hold && !keys && !ahead && ctx->n >= 1 && ctx->n <= kBatchMaxParticles && !ctx->profile) {
+    BatchItem& it = hold->item;
+    it.p = ctx->cur();
+    it.n = ctx->n;
+    it.smp = sampler;
+    it.seed = ctx->cfg.seed;
+    it.step = step;
+    it.index_offset = ctx->cfg.shard_offset;
+    it.scan_src = scan_doubles ? ctx->hd_points : nullptr;
+    it.scan_dst = scan_doubles ? ctx->d_points.ptr : nullptr;
+    it.scan_doubles = static_cast<uint32_t>(scan_doubles);
+    hold->propagate_held = true;
+  } else {
+    launch_propagate(ctx->stream, ctx->cur(), ctx->n, sampler, ctx->cfg.seed, step, ctx->cfg.shard_offset,
+                     scan_doubles ? ctx->hd_points : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
+                     keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->facts.noise_ahead_count());
+  }
   if (ahead) ctx->noise_ahead_used += 1;
   if (scan_doubles) points_pulled(ctx, false);
   if (keys_emitted) *keys_emitted = keys;
@@ -838,7 +871,7 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
 // want_weight_sums: the normalisation follows at once (mcl_update): the LF patch kernel leaves the sums of its workgroups' new
 // weights in d_lf_wsum (facts.lf_sums() of them; 0 if another kernel ran).
 mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = false, bool keys_ready = false,
-                       bool want_weight_sums = false) {
+                       bool want_weight_sums = false, HeldCycle* hold = nullptr) {
   ctx->facts.lf_sums_dropped();
   const uint64_t B = ctx->off_grid() ? 0 : m.doubles / 2;  // the grid models' measurement is the scan itself: B points
   if (const mcl_status s = reweight_preconditions(ctx, B)) return s;
@@ -857,6 +890,24 @@ mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = 
   ctx->lf_planner.mode_consumed();  // the next cycle decides again
   const SortScratch sort = ctx->sort_scratch();
   const bool have_order = ctx->facts.take_order_accepted();  // (launch_order_ahead's, accepted by this cycle's propagation)
+  const bool lf_kind = !ctx->off_grid() && ctx->cfg.sensor_kind != MCL_SENSOR_BEAM;
+  LfReweightArgs lf_args{};
+  if (lf_kind)
+    lf_args = LfReweightArgs{.p = ctx->cur(), .n = ctx->n, .f = ctx->field_view(), .d_points = ctx->d_points.ptr, .B = static_cast<uint32_t>(B),
+                             .sort = ordered ? &sort : nullptr, .patches = mode.patches, .beams = mode.beams,
+                             .dispersed = dispersed,
+                             .scan_cells = ctx->scan_extent / ctx->resolution, .unit_weights = unit_weights,
+                             .stats = PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
+                                                 reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotPatchMirror),
+                                                 static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
+                                                 static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
+                                                 reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)}};
+  if (hold && hold->propagate_held) {  // mcl_batch_update: is this member's cycle the small one?  If not, its propagation goes out now
+    hold->fused = lf_kind && batch_member_fused(BatchMemberFacts{
+                                 ctx->cfg.sensor_kind, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0, ctx->n,
+                                 std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), lf_takes_beams(lf_args, ctx->tuning), ctx->profile != 0});
+    if (!hold->fused) launch_held_propagate(ctx, hold);
+  }
   if (ordered && !have_order) {
     KeyFrame frame{};
     // The ordering also serves the beam model: both kernels gather the pose records through sort.perm.
@@ -875,18 +926,13 @@ mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = 
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    const LfLaunch launched = launch_reweight_lf(
-        ctx->stream,
-        LfReweightArgs{.p = ctx->cur(), .n = ctx->n, .f = ctx->field_view(), .d_points = ctx->d_points.ptr, .B = static_cast<uint32_t>(B),
-                       .sort = ordered ? &sort : nullptr, .patches = mode.patches, .beams = mode.beams,
-                       .dispersed = dispersed,
-                       .scan_cells = ctx->scan_extent / ctx->resolution, .unit_weights = unit_weights,
-                       .stats = PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
-                                           reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotPatchMirror),
-                                           static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
-                                           static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
-                                           reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)}},
-        ctx->tuning);
+    LfLaunch launched{LfKernel::kBeams, 0};  // (a held cycle: the batch launches k_batch_reweight_lf_beams)
+    if (hold && hold->fused) {
+      hold->item.f = lf_args.f;
+      hold->item.B = lf_args.B;
+    } else {
+      launched = launch_reweight_lf(ctx->stream, lf_args, ctx->tuning);
+    }
     ctx->facts.lf_sums_left(launched.weight_sums);
     switch (launched.kernel) {  // (the counters as include/beluga_mcl.h states them)
       case LfKernel::kPatchQueue: ctx->lf_queue_launches += 1; [[fallthrough]];
@@ -2179,8 +2225,8 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
 }
 
 void mcl_destroy(mcl_ctx* ctx) {
-  if (ctx) drop_pending_map(ctx);
-  if (!ctx) return;
+  if (!ctx || ctx->batch) return;  // (a batch's member: mcl_batch_destroy is the owner)
+  drop_pending_map(ctx);
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (auto& set : ctx->sets) set.release();
@@ -2589,9 +2635,74 @@ mcl_status mcl_estimate_pose(mcl_ctx* ctx, mcl_estimate* out) {
   return s;
 }
 
+// ---- the small cycle's tail in three steps, shared by mcl_update and mcl_batch_update ------------------------------------------------------
+// prepare: k_small_tail's record for the live set as the reweight leaves it (fires: every_n's verdict, :181); no completion word.
+static SmallTail small_tail_record(const mcl_ctx* ctx, bool fires) {
+  const mcl_amcl_params& ap = ctx->cfg.amcl;
+  SmallTail t{};
+  t.src = ctx->cur();
+  t.dst = ctx->other();
+  t.n = static_cast<uint32_t>(ctx->n);
+  t.max_particles = static_cast<uint32_t>(std::min<uint64_t>(ap.max_particles, ctx->capacity));
+  t.min_particles = static_cast<uint32_t>(std::min<uint64_t>(ap.min_particles, t.max_particles));
+  t.seed = ctx->cfg.seed;
+  t.step = ctx->step;
+  t.fires = fires;
+  t.selective = ap.selective_resampling != 0;
+  t.alpha_slow = ap.alpha_slow;
+  t.alpha_fast = ap.alpha_fast;
+  t.slow = ctx->slow.output;
+  t.fast = ctx->fast.output;
+  t.kld_epsilon = ap.kld_epsilon;
+  t.kld_z = ap.kld_z;
+  t.hp = HashParams{ap.spatial_resolution_x, ap.spatial_resolution_y, ap.spatial_resolution_theta};
+  t.g = ctx->grid_view();
+  t.fc = ctx->random_source();
+  t.pivot_x = ctx->pivot[0];
+  t.pivot_y = ctx->pivot[1];
+  t.mirror = ctx->hd_scalars;
+  t.d_scalars = ctx->d_scalars.ptr;
+  return t;
+}
+// launch: what the host notes once the tail kernel is enqueued (every_n: the counter as this cycle leaves it).
+static void small_tail_launched(mcl_ctx* ctx, uint64_t every_n) {
+  ctx->every_n_current = every_n;
+  ctx->small_tail_launches += 1;
+  ctx->facts.lf_sums_dropped();
+  ctx->facts.weights_touched();
+}
+// finish: behind the synchronisation.  The mirror's verdict flips the live set, the recovery filters take their new outputs, the
+// estimate (:200) and the pivot follow.
+static mcl_status finish_small_cycle(mcl_ctx* ctx, mcl_estimate* estimate, mcl_update_info* info) {
+  stage_collect(ctx);
+  const double* h = ctx->h_scalars;
+  const bool resampled = h[kSlotResampled] != 0.0;
+  if (resampled) {
+    ctx->live ^= 1;
+    ctx->n = static_cast<uint64_t>(h[kSlotParticles]);
+    ctx->facts.resampled_set_committed();
+  }
+  ctx->slow.output = h[kSlotSlow];
+  ctx->fast.output = h[kSlotFast];
+  ctx->force_update = false;  // :199
+  // (what the info reports, before another kernel's mirrored values take their place)
+  const mcl_update_info report{1, resampled, ctx->n, h[kSlotWeightSum], h[kSlotEss], h[kSlotPolicyP]};
+  mcl_estimate est{};
+  if (ctx->estimate_kind == 1) {  // beluga_ros::Amcl returns cluster_based_estimate (beluga_ros/src/amcl.cpp:125): its own kernels
+    if (const mcl_status s = mcl_cluster_based_estimate(ctx, &ctx->cluster_params, &est)) return s;
+  } else if (const mcl_status s = mirrored_estimate(ctx, &est)) {  // :200
+    return s;
+  }
+  finish_cycle(ctx, est, report, estimate, info);
+  return MCL_OK;
+}
+
 // Amcl::update (amcl_core.hpp:165-201) over the scan's points, or the detection records of a landmark / bearing context
 // (mcl_update_landmarks, mcl_update_bearings).
-static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measurement m, mcl_estimate* estimate, mcl_update_info* info) {
+// hold (mcl_batch_update): where the cycle turns out to be the small one, nothing is launched and the cycle stops behind its prepare
+// step, with hold->pending set; every other cycle runs to its end here.
+static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measurement m, mcl_estimate* estimate, mcl_update_info* info,
+                               HeldCycle* hold = nullptr) {
   MCL_REQUIRE(ctx, control_pose && (m.doubles == 0 || m.data), "null argument");
   const auto t_entry = std::chrono::steady_clock::now();
   if (info) {
@@ -2624,7 +2735,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   advance_window(ctx, pose);
 
   bool keys_ready = false;
-  if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, m.doubles, &keys_ready)) return s;  // :174-175
+  if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, m.doubles, &keys_ready, hold)) return s;  // :174-175
   const auto t_first = std::chrono::steady_clock::now();
   // With a fixed particle count and no selective resampling nothing in the cycle depends on a host-side decision: the
   // recovery estimator runs on the device as well and the cycle synchronises once, at the estimate.
@@ -2634,35 +2745,21 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   const bool device_policy = !ap.selective_resampling && ap.min_particles >= std::min<uint64_t>(ap.max_particles, ctx->capacity) &&
                              ctx->tuning.device_policy != 0 && !ctx->off_grid();
   // (the normalisation follows at once: the LF kernel leaves the sums it is built on)
-  if (const mcl_status s = do_reweight(ctx, m, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0)) return s;  // :176
+  if (const mcl_status s = do_reweight(ctx, m, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0, hold)) return s;  // :176
   // Small sets (the reference's own sizes): everything behind the reweight in ONE launch of one workgroup and one synchronisation
   // (k_small_tail) - the policies are evaluated on the device, the host keeps the recovery filters' state.
   const uint64_t every_n = next_every_n(ctx->every_n_current, ap.resample_interval);  // :181 (stored by the path that takes the cycle)
   const bool fires = every_n == 0;
-  if (ctx->tuning.small_fused != 0 && !ctx->off_grid() && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096) {
-    SmallTail t{};
-    t.src = ctx->cur();
-    t.dst = ctx->other();
-    t.n = static_cast<uint32_t>(ctx->n);
-    t.max_particles = static_cast<uint32_t>(std::min<uint64_t>(ap.max_particles, ctx->capacity));
-    t.min_particles = static_cast<uint32_t>(std::min<uint64_t>(ap.min_particles, t.max_particles));
-    t.seed = ctx->cfg.seed;
-    t.step = ctx->step;
-    t.fires = fires;
-    t.selective = ap.selective_resampling != 0;
-    t.alpha_slow = ap.alpha_slow;
-    t.alpha_fast = ap.alpha_fast;
-    t.slow = ctx->slow.output;
-    t.fast = ctx->fast.output;
-    t.kld_epsilon = ap.kld_epsilon;
-    t.kld_z = ap.kld_z;
-    t.hp = HashParams{ap.spatial_resolution_x, ap.spatial_resolution_y, ap.spatial_resolution_theta};
-    t.g = ctx->grid_view();
-    t.fc = ctx->random_source();
-    t.pivot_x = ctx->pivot[0];
-    t.pivot_y = ctx->pivot[1];
-    t.mirror = ctx->hd_scalars;
-    t.d_scalars = ctx->d_scalars.ptr;
+  const bool small = ctx->tuning.small_fused != 0 && !ctx->off_grid() && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096;
+  if (hold && hold->fused) {  // the batch launches this cycle and finishes it
+    if (!small) return fail(ctx, MCL_ERR_HIP, "mcl_batch_update: a held cycle is not a small one");
+    hold->item.tail = small_tail_args(small_tail_record(ctx, fires));
+    hold->every_n = every_n;
+    hold->pending = true;
+    return MCL_OK;
+  }
+  if (small) {
+    SmallTail t = small_tail_record(ctx, fires);
     // (the completion word only where asked for: measured 10 us per cycle SLOWER than the stream's signal at 2000 particles, round 6)
     ctx->done_armed = ctx->tuning.cycle_spin > 0 && !ctx->profile;
     if (ctx->done_armed) {
@@ -2673,33 +2770,10 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
     const bool launched = launch_small_tail(ctx->stream, t);
     stage_end(ctx, MCL_STAGE_RESAMPLE);
     if (launched) {
-      ctx->every_n_current = every_n;
-      ctx->small_tail_launches += 1;
+      small_tail_launched(ctx, every_n);
       MCL_HIP(ctx, hipGetLastError());
-      ctx->facts.lf_sums_dropped();
-      ctx->facts.weights_touched();
       if (const mcl_status s = wait_for_cycle(ctx)) return s;
-      stage_collect(ctx);
-      const double* h = ctx->h_scalars;
-      const bool resampled = h[kSlotResampled] != 0.0;
-      if (resampled) {
-        ctx->live ^= 1;
-        ctx->n = static_cast<uint64_t>(h[kSlotParticles]);
-        ctx->facts.resampled_set_committed();
-      }
-      ctx->slow.output = h[kSlotSlow];
-      ctx->fast.output = h[kSlotFast];
-      ctx->force_update = false;  // :199
-      // (what the info reports, before another kernel's mirrored values take their place)
-      const mcl_update_info report{1, resampled, ctx->n, h[kSlotWeightSum], h[kSlotEss], h[kSlotPolicyP]};
-      mcl_estimate est{};
-      if (ctx->estimate_kind == 1) {  // beluga_ros::Amcl returns cluster_based_estimate (beluga_ros/src/amcl.cpp:125): its own kernels
-        if (const mcl_status s = mcl_cluster_based_estimate(ctx, &ctx->cluster_params, &est)) return s;
-      } else if (const mcl_status s = mirrored_estimate(ctx, &est)) {  // :200
-        return s;
-      }
-      finish_cycle(ctx, est, report, estimate, info);
-      return MCL_OK;
+      return finish_small_cycle(ctx, estimate, info);
     }
     ctx->done_armed = false;
   }
@@ -2782,6 +2856,204 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_update: a landmark or bearing context takes mcl_update_landmarks / mcl_update_bearings");
   return update_cycle(ctx, control_pose, scan_measurement(points_xy, num_points), estimate, info);
+}
+
+// ---- a batch of small filters: one update call, three launches for the fleet (DESIGN.md "Batched small filters") ------------------------
+// All filter state lives in the members; the batch owns the shared stream (unless the caller gave one), the members' lifetime and the
+// table of the cycle's records.
+}  // extern "C"
+struct mcl_batch {
+  std::string error;
+  int device{0};
+  hipStream_t stream{nullptr};
+  bool own_stream{false};
+  std::vector<mcl_ctx*> members;
+  BatchItem* h_items{nullptr};  // the cycle's records, pinned; copied to d_items in front of the three launches
+  DeviceBuffer<BatchItem> d_items;
+  std::vector<HeldCycle> held;  // per member, this cycle
+  std::vector<uint32_t> fused;  // the members whose cycle the batch launches, in index order
+  std::vector<uint64_t> fused_n;
+  std::vector<uint32_t> fused_lds, first_propagate, first_reweight;
+  uint64_t cycles{0}, kernel_launches{0}, members_fused{0}, members_alone{0};
+};
+namespace {
+mcl_status batch_fail(mcl_batch* b, mcl_status code, const std::string& msg) {
+  if (b) b->error = msg;
+  else g_create_error = msg;
+  return code;
+}
+// Enqueues the cycle of the members in b->fused (their records complete in b->held) and waits for it: one copy, three launches, one
+// synchronisation.
+mcl_status batch_launch(mcl_batch* b) {
+  const uint32_t count = static_cast<uint32_t>(b->fused.size());
+  b->fused_n.resize(count);
+  b->fused_lds.resize(count);
+  b->first_propagate.resize(count);
+  b->first_reweight.resize(count);
+  for (uint32_t k = 0; k < count; ++k) {
+    const BatchItem& it = b->held[b->fused[k]].item;
+    b->fused_n[k] = it.n;
+    b->fused_lds[k] = static_cast<uint32_t>(lf_palette_lds(it.f));
+  }
+  const BatchGrid grid = batch_layout(b->fused_n.data(), b->fused_lds.data(), count, b->first_propagate.data(), b->first_reweight.data());
+  for (uint32_t k = 0; k < count; ++k) {
+    BatchItem& it = b->h_items[k];
+    it = b->held[b->fused[k]].item;
+    it.first_propagate_block = b->first_propagate[k];
+    it.first_reweight_block = b->first_reweight[k];
+  }
+  if (hipMemcpyAsync(b->d_items.ptr, b->h_items, count * sizeof(BatchItem), hipMemcpyHostToDevice, b->stream) != hipSuccess)
+    return batch_fail(b, MCL_ERR_HIP, "mcl_batch_update: the copy of the cycle's records failed");
+  launch_batch_cycle(b->stream, b->d_items.ptr, grid);
+  b->kernel_launches += 3;
+  for (const uint32_t i : b->fused) small_tail_launched(b->members[i], b->held[i].every_n);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+  if (e != hipSuccess) return batch_fail(b, MCL_ERR_HIP, std::string("mcl_batch_update: ") + hipGetErrorString(e));
+  return MCL_OK;
+}
+}  // namespace
+extern "C" {
+
+mcl_status mcl_batch_create(const mcl_config* cfgs, uint32_t count, mcl_batch** out) {
+  if (!out) return batch_fail(nullptr, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_create: null argument");
+  *out = nullptr;
+  if (const char* wrong = batch_check_configs(cfgs, count)) return batch_fail(nullptr, MCL_ERR_INVALID_ARGUMENT, wrong);
+  mcl_batch* b = new (std::nothrow) mcl_batch();
+  if (!b) return batch_fail(nullptr, MCL_ERR_OUT_OF_MEMORY, "mcl_batch_create: host allocation failed");
+  b->device = cfgs[0].device_id;
+  b->stream = static_cast<hipStream_t>(cfgs[0].hip_stream);
+  mcl_status st = MCL_OK;
+  for (uint32_t i = 0; i < count && st == MCL_OK; ++i) {
+    mcl_config cfg = cfgs[i];
+    cfg.hip_stream = b->stream;  // (member 0 of a batch without a stream creates the one all share; the batch takes it over)
+    mcl_ctx* ctx = nullptr;
+    st = mcl_create(&cfg, &ctx);
+    if (st != MCL_OK) break;  // (g_create_error has the text)
+    if (i == 0) {
+      b->stream = ctx->stream;
+      b->own_stream = ctx->own_stream;
+      ctx->own_stream = false;
+    }
+    ctx->batch = b;
+    b->members.push_back(ctx);
+  }
+  if (st == MCL_OK) {
+    hipError_t e = hipSetDevice(b->device);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b->h_items), count * sizeof(BatchItem), hipHostMallocDefault);
+    if (e == hipSuccess) e = b->d_items.ensure(count);
+    if (e != hipSuccess) st = batch_fail(nullptr, e == hipErrorOutOfMemory ? MCL_ERR_OUT_OF_MEMORY : MCL_ERR_HIP,
+                                         std::string("mcl_batch_create: ") + hipGetErrorString(e));
+  }
+  if (st != MCL_OK) {
+    mcl_batch_destroy(b);
+    return st;
+  }
+  b->held.resize(count);
+  *out = b;
+  return MCL_OK;
+}
+
+void mcl_batch_destroy(mcl_batch* batch) {
+  if (!batch) return;
+  (void)hipSetDevice(batch->device);
+  for (mcl_ctx* ctx : batch->members) {
+    ctx->batch = nullptr;
+    mcl_destroy(ctx);  // (synchronises the shared stream first)
+  }
+  if (batch->h_items) (void)hipHostFree(batch->h_items);
+  batch->d_items.release();
+  if (batch->own_stream && batch->stream) (void)hipStreamDestroy(batch->stream);
+  delete batch;
+}
+
+const char* mcl_batch_last_error(const mcl_batch* batch) { return batch ? batch->error.c_str() : g_create_error.c_str(); }
+
+mcl_status mcl_batch_size(const mcl_batch* batch, uint32_t* count) {
+  if (!batch || !count) return MCL_ERR_INVALID_ARGUMENT;
+  *count = static_cast<uint32_t>(batch->members.size());
+  return MCL_OK;
+}
+
+mcl_status mcl_batch_member(mcl_batch* batch, uint32_t index, mcl_ctx** ctx) {
+  if (!batch || !ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (index >= batch->members.size()) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_member: index beyond the batch");
+  *ctx = batch->members[index];
+  return MCL_OK;
+}
+
+mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const double* points_xy, const uint64_t* point_offsets,
+                            mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses) {
+  if (!batch) return MCL_ERR_INVALID_ARGUMENT;
+  const uint32_t count = static_cast<uint32_t>(batch->members.size());
+  if (!control_poses) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_update: null control_poses");
+  if (const char* wrong = batch_check_offsets(point_offsets, count)) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, wrong);
+  if (point_offsets[count] != point_offsets[0] && !points_xy) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_update: null points");
+  // prepare: every member's own cycle up to its launches; a cycle that is not the small one runs to its end here
+  std::vector<mcl_status> status(count, MCL_OK);
+  batch->fused.clear();
+  bool any_updated = false;
+  for (uint32_t i = 0; i < count; ++i) {
+    mcl_ctx* ctx = batch->members[i];
+    HeldCycle& hold = batch->held[i];
+    hold = HeldCycle{};
+    mcl_update_info own{};
+    mcl_update_info* info = infos ? &infos[i] : &own;
+    const uint64_t first = point_offsets[i], points = point_offsets[i + 1] - first;
+    if (ctx->is_landmark())
+      status[i] = fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_update: a landmark or bearing context takes mcl_update_landmarks / mcl_update_bearings");
+    else
+      status[i] = update_cycle(ctx, control_poses + 4 * static_cast<size_t>(i), scan_measurement(points ? points_xy + 2 * first : nullptr, points),
+                               estimates ? &estimates[i] : nullptr, info, &hold);
+    if (status[i] != MCL_OK) continue;
+    if (hold.pending) {
+      batch->fused.push_back(i);
+    } else if (info->updated) {
+      batch->members_alone += 1;
+      any_updated = true;
+    }
+  }
+  // launch, and finish behind the one synchronisation
+  if (!batch->fused.empty()) {
+    const mcl_status launched = batch_launch(batch);
+    for (const uint32_t i : batch->fused) {
+      mcl_ctx* ctx = batch->members[i];
+      if (launched != MCL_OK) {
+        status[i] = fail(ctx, launched, batch->error);
+        continue;
+      }
+      if (const mcl_status s = bind_device(ctx)) {
+        status[i] = s;
+        continue;
+      }
+      status[i] = finish_small_cycle(ctx, estimates ? &estimates[i] : nullptr, infos ? &infos[i] : nullptr);
+      if (status[i] == MCL_OK) {
+        batch->members_fused += 1;
+        any_updated = true;
+      }
+    }
+  }
+  if (any_updated) batch->cycles += 1;
+  mcl_status first_error = MCL_OK;
+  for (uint32_t i = 0; i < count; ++i) {
+    if (statuses) statuses[i] = status[i];
+    if (first_error == MCL_OK && status[i] != MCL_OK) {
+      first_error = status[i];
+      batch->error = "member " + std::to_string(i) + ": " + batch->members[i]->error;
+    }
+  }
+  return first_error;
+}
+
+mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* value) {
+  if (!batch || !name || !value) return MCL_ERR_INVALID_ARGUMENT;
+  const std::string key(name);
+  if (key == "cycles") *value = batch->cycles;
+  else if (key == "kernel_launches") *value = batch->kernel_launches;
+  else if (key == "members_fused") *value = batch->members_fused;
+  else if (key == "members_alone") *value = batch->members_alone;
+  else return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_get_counter: unknown counter " + key);
+  return MCL_OK;
 }
 
 mcl_status mcl_update_laser_scan(mcl_ctx* ctx, const double control_pose[4], const mcl_laser_scan* scan, mcl_estimate* estimate,

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "batch_host.h"
 #include "cycle_types.h"
 #include "se2.h"
 #include "sensor_records.h"
@@ -327,6 +328,9 @@ enum class LfKernel { kNone, kPatch, kPatchQueue, kFarBeams, kPaletteFar, kPalet
 struct LfLaunch { LfKernel kernel; uint32_t weight_sums; };
 // The one place that chooses the LF kernel (from the arguments and `tuning`); launches it.
 LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tuning& tuning);
+// Its answer where that is k_reweight_lf_beams (LfKernel::kBeams), without launching; lf_palette_lds: that kernel's workgroup memory.
+bool lf_takes_beams(const LfReweightArgs& a, const Tuning& tuning);
+inline size_t lf_palette_lds(const FieldView& f) { return static_cast<size_t>(f.pal_base) + static_cast<size_t>(f.pal_count) * sizeof(double); }
 // K2' beam_model.hpp:104-150 + raycasting.hpp:62-107 + bresenham.hpp:84-160
 // `sorted` != nullptr: lane-per-ordered-particle variant (needs launch_order_particles first).
 // d_beam_points: scratch of kBeamPointDoubles * B doubles (per-beam terms shared by all particles; ordered variant only).
@@ -491,6 +495,50 @@ struct SmallTail {
   unsigned long long done_seq{0};
 };
 bool launch_small_tail(hipStream_t st, const SmallTail& t);
+// The kernel's own argument record (k_small_tail takes it by value, k_batch_small_tail from its member's BatchItem).
+struct SmallTailArgs {
+  Particles src, dst;
+  uint32_t n;               // live particles
+  uint32_t min_particles, max_particles;
+  uint64_t seed;
+  uint32_t step;
+  int fires;                // every_n says so
+  int selective;            // && on_effective_size_drop
+  int adaptive;             // min < max: take_while_kld
+  double alpha_slow, alpha_fast, slow, fast;  // the recovery estimator's filters (the host keeps their state)
+  double two_epsilon, z;
+  HashParams hp;
+  GridView g;
+  FreeCells fc;
+  double pivot_x, pivot_y;
+  double* out;              // [kScalarSlots] mirror in mapped host memory (the context's h_scalars): see the stores below
+  double* d_out;            // the same values in device memory (d_scalars)
+  unsigned long long* done_flag;  // optional: a word of mapped host memory that takes done_seq behind everything mirrored (cycle_spin)
+  unsigned long long done_seq;
+};
+SmallTailArgs small_tail_args(const SmallTail& t);
+bool small_tail_fits(uint64_t n, uint64_t max_particles);  // launch_small_tail's own test: both 1 .. 4096
+
+// ---- a batch of small filters (mcl_batch_update): the small cycle's three kernels over many sets in one launch each ----------------------
+// One member's cycle, as k_propagate_small, k_reweight_lf_beams (a wave per particle) and k_small_tail take it.  The host fills one
+// record per fused member and cycle; every kernel of the cycle gets the device table.
+struct BatchItem {
+  Particles p;  // the live set
+  uint64_t n;
+  DiffDriveSampler smp;  // k_propagate_small's arguments
+  uint64_t seed;
+  uint32_t step;
+  uint64_t index_offset;
+  const double* scan_src;  // the member's staged scan in mapped host memory (nullptr: an empty scan, nothing pulled)
+  double* scan_dst;        // ... and where the reweight reads it
+  uint32_t scan_doubles;
+  FieldView f;  // k_reweight_lf_beams' arguments (its points are scan_dst)
+  uint32_t B;
+  SmallTailArgs tail;
+  uint32_t first_propagate_block, first_reweight_block;  // batch_layout
+};
+// k_batch_propagate, k_batch_reweight_lf_beams, k_batch_small_tail over d_items[0 .. grid.members), in this order on `st`.
+void launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid);
 // K6: one thread per candidate (views/sample.hpp:102,133-135; random_intersperse.hpp:90-115; particle_traits.hpp:105).
 void launch_resample_draw(hipStream_t st, Particles src, CdfTree cdf, const double* d_total, Particles dst,
                           ResampleArgs a, GridView g, FreeCells fc, HashParams hp, unsigned long long* d_hashes);

@@ -252,12 +252,18 @@ __device__ __forceinline__ Pose2 propagate_one(const Pose2& state, const DiffDri
 // Small sets (no ordering keys): one particle per lane, 256 per workgroup - 2000 particles are 8 workgroups on 8 CUs, a wave
 // per SIMD, instead of one workgroup of the chunked kernel working through them on one (256 lanes rather than 64 for the sake
 // of the scan pull, which is bound by the reads in flight over PCIe).
+// (the body: block `block` of `blocks` of ONE set - the grid's own numbers in k_propagate_small, a member's local ones in k_batch_propagate)
+__device__ __forceinline__ void propagate_small_block(uint32_t block, uint32_t blocks, const Particles& p, uint64_t n, const DiffDriveSampler& smp,
+                                                      uint64_t seed, uint32_t step, uint64_t index_offset, const double* __restrict__ scan_src,
+                                                      double* __restrict__ scan_dst, uint32_t scan_doubles) {
+  if (scan_dst && block == blocks - 1) pull_scan(scan_src, scan_dst, scan_doubles);
+  const uint64_t i = static_cast<uint64_t>(block) * kBlock + threadIdx.x;
+  if (i < n) store_pose(p, i, propagate_one(load_pose(p, i), smp, seed, step, index_offset + i));
+}
 __global__ __launch_bounds__(kBlock) void k_propagate_small(Particles p, uint64_t n, DiffDriveSampler smp, uint64_t seed, uint32_t step,
                                                            uint64_t index_offset, const double* __restrict__ scan_src,
                                                            double* __restrict__ scan_dst, uint32_t scan_doubles) {
-  if (scan_dst && blockIdx.x == gridDim.x - 1) pull_scan(scan_src, scan_dst, scan_doubles);
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (i < n) store_pose(p, i, propagate_one(load_pose(p, i), smp, seed, step, index_offset + i));
+  propagate_small_block(blockIdx.x, gridDim.x, p, n, smp, seed, step, index_offset, scan_src, scan_dst, scan_doubles);
 }
 
 // 512 threads, four particles each: at the kernel's 100 registers a CU holds 16 waves - one workgroup of 1024 threads (round 4: 489
@@ -703,8 +709,10 @@ __global__ __launch_bounds__(kPalBlock) void k_reweight_lf_palette(double* __res
 // added in a fixed tree (wave_sum_f64): the weight differs from the sum of the lane-per-particle kernels in rounding only.
 // Workgroup memory as in k_reweight_lf_palette: [0, (H+2)*4) row offsets, [pal_base, ...) the palette; no other LDS.
 constexpr int kBeamsBlock = 256;
-__global__ __launch_bounds__(kBeamsBlock) void k_reweight_lf_beams(Particles p, uint64_t n, FieldView f, const double2* __restrict__ pts,
-                                                                   uint32_t B, uint32_t per_wave /* particles of a wave: 1 .. 64 */) {
+// (the body: block `block` of ONE set - blockIdx.x in k_reweight_lf_beams, a member's local block in k_batch_reweight_lf_beams)
+__device__ __forceinline__ void reweight_lf_beams_block(uint32_t block, const Particles& p, uint64_t n, const FieldView& f,
+                                                        const double2* __restrict__ pts, uint32_t B,
+                                                        uint32_t per_wave /* particles of a wave: 1 .. 64 */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   {
     uint32_t* s_row = reinterpret_cast<uint32_t*>(smem);
@@ -714,7 +722,7 @@ __global__ __launch_bounds__(kBeamsBlock) void k_reweight_lf_beams(Particles p, 
   }
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63;
-  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * (kBeamsBlock / kWave) + (threadIdx.x >> 6);
+  const uint64_t tile = static_cast<uint64_t>(block) * (kBeamsBlock / kWave) + (threadIdx.x >> 6);
   const uint64_t base = tile * per_wave;
   if (base >= n) return;
   const uint32_t cnt = static_cast<uint32_t>(n - base < per_wave ? n - base : per_wave);
@@ -757,6 +765,10 @@ __global__ __launch_bounds__(kBeamsBlock) void k_reweight_lf_beams(Particles p, 
     if (lane == q) mine = total;
   }
   if (lane < cnt) p.w[i] = p.w[i] * (f.prob ? exp(mine) : 1.0 + mine);
+}
+__global__ __launch_bounds__(kBeamsBlock) void k_reweight_lf_beams(Particles p, uint64_t n, FieldView f, const double2* __restrict__ pts,
+                                                                   uint32_t B, uint32_t per_wave /* particles of a wave: 1 .. 64 */) {
+  reweight_lf_beams_block(blockIdx.x, p, n, f, pts, B, per_wave);
 }
 
 // Variant D for large DISPERSED sets, round 6 (option lf_dispersed = 2): the lanes over the beams of a pose as above, but with everything
@@ -3357,26 +3369,6 @@ __global__ __launch_bounds__(kBlock) void k_estimate_partials(Particles p, uint6
 // the parity tests' tolerances, the KLD cut and the particle counts exact).
 constexpr uint32_t kSmallMax = 4096, kSmallBlock = 1024, kSmallItems = kSmallMax / kSmallBlock, kSmallSlots = 2 * kSmallMax;
 constexpr size_t kSmallLdsBytes = kSmallMax * 8 /* cdf */ + kSmallMax * 8 /* hashes */ + kSmallSlots * 4 /* table */ + 16 * 9 * 8 + 128;
-struct SmallTailArgs {
-  Particles src, dst;
-  uint32_t n;               // live particles
-  uint32_t min_particles, max_particles;
-  uint64_t seed;
-  uint32_t step;
-  int fires;                // every_n says so
-  int selective;            // && on_effective_size_drop
-  int adaptive;             // min < max: take_while_kld
-  double alpha_slow, alpha_fast, slow, fast;  // the recovery estimator's filters (the host keeps their state)
-  double two_epsilon, z;
-  HashParams hp;
-  GridView g;
-  FreeCells fc;
-  double pivot_x, pivot_y;
-  double* out;              // [kScalarSlots] mirror in mapped host memory (the context's h_scalars): see the stores below
-  double* d_out;            // the same values in device memory (d_scalars)
-  unsigned long long* done_flag;  // optional: a word of mapped host memory that takes done_seq behind everything mirrored (cycle_spin)
-  unsigned long long done_seq;
-};
 __device__ __forceinline__ double small_block_sum(double v, double* s_wave /* [16] */) {  // every thread gets the total; fixed order
   v = wave_sum_f64(v);
   __syncthreads();
@@ -3386,7 +3378,8 @@ __device__ __forceinline__ double small_block_sum(double v, double* s_wave /* [1
   for (uint32_t q = 1; q < kSmallBlock / 64; ++q) total += s_wave[q];
   return total;
 }
-__global__ __launch_bounds__(kSmallBlock) void k_small_tail(SmallTailArgs a) {
+// (the body: the one workgroup of k_small_tail, a member's workgroup of k_batch_small_tail)
+__device__ __forceinline__ void small_tail_block(const SmallTailArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* s_cdf = reinterpret_cast<double*>(smem);
   unsigned long long* s_hash = reinterpret_cast<unsigned long long*>(smem + kSmallMax * 8);
@@ -3640,6 +3633,31 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_tail(SmallTailArgs a) {
     __syncthreads();
     if (tid == 0) __hip_atomic_store(a.done_flag, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
+}
+__global__ __launch_bounds__(kSmallBlock) void k_small_tail(SmallTailArgs a) { small_tail_block(a); }
+
+// ---- a fleet of small filters: the three kernels of the small cycle over MANY sets in one launch each (mcl_batch_update) -----------------
+// items[0 .. count): one record per member that takes the cycle (BatchItem, kernels.h), its first block in the two gridded launches a
+// running sum over the members.  A block finds its member by a search over that prefix (batch_member_of, batch_host.h: the member is
+// uniform over the workgroup, so the record is read through uniform addresses) and then runs the lone kernel's body with its LOCAL block
+// number where the lone kernel has blockIdx.x: the same expressions in the same order on the same values - the same bits.
+static_assert(kBatchPropagateBlock == kBlock && kBatchReweightBlock == kBeamsBlock / kWave && kBatchMaxParticles == kSmallMax,
+              "batch_host.h restates the small cycle's launch geometry");
+__device__ __forceinline__ uint32_t batch_member_here(const BatchItem* __restrict__ items, uint32_t count, uint32_t BatchItem::*first) {
+  return batch_member_of(count, blockIdx.x, [items, first](uint32_t m) { return items[m].*first; });
+}
+__global__ __launch_bounds__(kBlock) void k_batch_propagate(const BatchItem* __restrict__ items, uint32_t count) {
+  const BatchItem& it = items[batch_member_here(items, count, &BatchItem::first_propagate_block)];
+  propagate_small_block(blockIdx.x - it.first_propagate_block, batch_propagate_blocks(it.n), it.p, it.n, it.smp, it.seed, it.step, it.index_offset,
+                        it.scan_src, it.scan_dst, it.scan_doubles);
+}
+__global__ __launch_bounds__(kBeamsBlock) void k_batch_reweight_lf_beams(const BatchItem* __restrict__ items, uint32_t count) {
+  const BatchItem& it = items[batch_member_here(items, count, &BatchItem::first_reweight_block)];
+  reweight_lf_beams_block(blockIdx.x - it.first_reweight_block, it.p, it.n, it.f, reinterpret_cast<const double2*>(it.scan_dst), it.B, 1u);
+}
+__global__ __launch_bounds__(kSmallBlock) void k_batch_small_tail(const BatchItem* __restrict__ items) {
+  const SmallTailArgs a = items[blockIdx.x].tail;
+  small_tail_block(a);
 }
 
 // ---- cluster_based_estimate (algorithm/cluster_based_estimation.hpp) ---------------------------------------------
@@ -4319,12 +4337,23 @@ hipError_t configure_device_kernels() {
       {reinterpret_cast<const void*>(k_reweight_lf_far_beams<false>), kFarBeamsMaxLds},
       {reinterpret_cast<const void*>(k_reweight_lf_far_beams<true>), kFarBeamsMaxLds},
       {reinterpret_cast<const void*>(k_small_tail), kSmallLdsBytes},
+      {reinterpret_cast<const void*>(k_batch_small_tail), kSmallLdsBytes},
       {reinterpret_cast<const void*>(k_small_cluster_cells), kSmallClusterLdsBytes},
       {reinterpret_cast<const void*>(k_small_cluster_sums), kSmallClusterLdsBytes}};
   for (const auto& o : opt_ins)
     if (const hipError_t e = hipFuncSetAttribute(o.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(o.lds)); e != hipSuccess)
       return e;
   return configure_beam_kernels();
+}
+
+namespace {
+bool lf_palette_ok(const FieldView& f, const Tuning& tuning) {
+  return tuning.lf_table == 0 && f.pal_idx != nullptr && f.pal_count > 0 && lf_palette_lds(f) <= 65536;
+}
+}  // namespace
+bool lf_takes_beams(const LfReweightArgs& a, const Tuning& tuning) {
+  return a.n != 0 && !a.sort && lf_palette_ok(a.f, tuning) &&
+         (a.beams || ((tuning.lf_variant == kLfSortedLanes || tuning.lf_variant == kLfBeamLanes) && lf_set_is_small(a.n, tuning)));
 }
 
 LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tuning& tuning) {
@@ -4335,8 +4364,8 @@ LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tunin
   const uint32_t B = a.B;
   LfLaunch launched{LfKernel::kNone, 0};
   if (n == 0) return launched;
-  const size_t pal_lds = static_cast<size_t>(f.pal_base) + static_cast<size_t>(f.pal_count) * sizeof(double);
-  const bool palette_ok = tuning.lf_table == 0 && f.pal_idx != nullptr && f.pal_count > 0 && pal_lds <= 65536;
+  const size_t pal_lds = lf_palette_lds(f);
+  const bool palette_ok = lf_palette_ok(f, tuning);
   if (const SortScratch* sort = a.sort) {
     const uint64_t cells = static_cast<uint64_t>(f.W) * f.H;
     const bool cube_ok = f.cube != nullptr && f.W < (1u << 21) && (cells + 1) * 8 < (1ull << 31);
@@ -4423,7 +4452,7 @@ LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tunin
     }
     if (segments > 1)
       hipLaunchKernelGGL(k_lf_combine, dim3(blocks_for(n)), dim3(kBlock), 0, st, p.w, n, sort->perm, partial, segments, f.prob);
-  } else if (palette_ok && (a.beams || ((tuning.lf_variant == kLfSortedLanes || tuning.lf_variant == kLfBeamLanes) && lf_set_is_small(n, tuning)))) {
+  } else if (lf_takes_beams(a, tuning)) {
     // lanes over the beams (a dispersed set the cycle sent here, or a set below the ordered kernels' threshold);
     // particles per wave: enough waves to fill the chip (4096) before a wave takes a second particle
     const uint32_t per_wave = static_cast<uint32_t>(std::min<uint64_t>(kWave, std::max<uint64_t>(1, (n + 4095) / 4096)));
@@ -4738,8 +4767,10 @@ void launch_kld_scan(hipStream_t st, const unsigned long long* d_hashes, uint64_
                      2 * epsilon, z, d_first_fail);
 }
 
-bool launch_small_tail(hipStream_t st, const SmallTail& t) {
-  if (t.n == 0 || t.n > kSmallMax || t.max_particles == 0 || t.max_particles > kSmallMax) return false;
+bool small_tail_fits(uint64_t n, uint64_t max_particles) {
+  return !(n == 0 || n > kSmallMax || max_particles == 0 || max_particles > kSmallMax);
+}
+SmallTailArgs small_tail_args(const SmallTail& t) {
   SmallTailArgs a{};
   a.src = t.src;
   a.dst = t.dst;
@@ -4766,8 +4797,19 @@ bool launch_small_tail(hipStream_t st, const SmallTail& t) {
   a.d_out = t.d_scalars;
   a.done_flag = t.done_flag;
   a.done_seq = t.done_seq;
-  hipLaunchKernelGGL(k_small_tail, dim3(1), dim3(kSmallBlock), kSmallLdsBytes, st, a);
+  return a;
+}
+bool launch_small_tail(hipStream_t st, const SmallTail& t) {
+  if (!small_tail_fits(t.n, t.max_particles)) return false;
+  hipLaunchKernelGGL(k_small_tail, dim3(1), dim3(kSmallBlock), kSmallLdsBytes, st, small_tail_args(t));
   return true;
+}
+
+void launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid) {
+  if (grid.members == 0) return;
+  hipLaunchKernelGGL(k_batch_propagate, dim3(grid.propagate_blocks), dim3(kBlock), 0, st, d_items, grid.members);
+  hipLaunchKernelGGL(k_batch_reweight_lf_beams, dim3(grid.reweight_blocks), dim3(kBeamsBlock), grid.reweight_lds, st, d_items, grid.members);
+  hipLaunchKernelGGL(k_batch_small_tail, dim3(grid.members), dim3(kSmallBlock), kSmallLdsBytes, st, d_items);
 }
 
 void launch_estimate_sums(hipStream_t st, Particles p, uint64_t n, double pivot_x, double pivot_y, double* d_partials,

@@ -435,6 +435,8 @@ struct ClusterEstimate {
   std::uint64_t count{0};
 };
 
+class AmclBatch;
+
 class Amcl {
  public:
   using state_type = SE2d;
@@ -978,6 +980,121 @@ class Amcl {
   mutable bool dirty_{true};
   mutable std::optional<ValueGrid2<float>> field_;
   mcl_update_info last_info_{};
+
+  friend class AmclBatch;
+  /// A member of an AmclBatch: bound to a context the batch owns (mcl_destroy does nothing on it).
+  struct Adopted {};
+  Amcl(Adopted, mcl_ctx* ctx, const AmclParams& params) : ctx_(ctx), max_particles_(params.max_particles) {}
+};
+
+/// One member of an AmclBatch: the arguments of Amcl's constructor for an occupancy grid (the likelihood-field, likelihood-field-prob and
+/// beam sensor models).  The map is installed by the batch's constructor; `map.cells == nullptr`: the member gets its map later
+/// (update_map on the member).
+struct AmclBatchSpec {
+  OccupancyGridView map;
+  MotionModelParam motion;
+  SensorModelParam sensor;
+  AmclParams params{};
+  std::uint64_t seed{0};
+  std::vector<std::pair<std::string, std::int64_t>> options{};
+};
+
+/// A fleet of small filters that share their launches (mcl_batch_*): one update call, three kernel launches for all members whose cycle
+/// is the small one (likelihood-field models, at most 4096 particles), one synchronisation; every other member runs its ordinary cycle
+/// inside the same call.  member(i) is a beluga_amd::Amcl bound to the batch's i-th context: every method of Amcl works on it between
+/// batch updates, all filter state lives in it, and for every member update() below does, bit for bit, what member(i).update(...) does.
+class AmclBatch {
+ public:
+  using measurement_type = Amcl::measurement_type;
+  using estimation_type = Amcl::estimation_type;
+
+  explicit AmclBatch(const std::vector<AmclBatchSpec>& specs, int device = 0) {
+    std::vector<mcl_config> cfgs;
+    for (const AmclBatchSpec& s : specs) {
+      if (std::holds_alternative<NDTModelParam2d>(s.sensor)) throw std::invalid_argument("beluga_amd::AmclBatch: an occupancy-grid sensor model");
+      cfgs.push_back(Amcl::make_config(s.motion, s.sensor, s.params, s.seed, device, Shard{}));
+    }
+    const mcl_status st = mcl_batch_create(cfgs.data(), static_cast<std::uint32_t>(cfgs.size()), &batch_);
+    if (st != MCL_OK) throw std::runtime_error(std::string("beluga_amd::AmclBatch: ") + mcl_batch_last_error(nullptr));
+    try {
+      members_.reserve(specs.size());
+      for (std::size_t i = 0; i < specs.size(); ++i) {
+        mcl_ctx* ctx = nullptr;
+        check(mcl_batch_member(batch_, static_cast<std::uint32_t>(i), &ctx));
+        members_.push_back(Amcl(Amcl::Adopted{}, ctx, specs[i].params));
+        for (const auto& [name, value] : specs[i].options) members_.back().check(mcl_set_option(ctx, name.c_str(), value));
+        if (specs[i].map.cells) members_.back().update_map(specs[i].map);
+      }
+    } catch (...) {
+      release();
+      throw;
+    }
+    estimates_.resize(specs.size());
+    infos_.resize(specs.size());
+    statuses_.assign(specs.size(), MCL_OK);
+  }
+  AmclBatch(const AmclBatch&) = delete;
+  AmclBatch& operator=(const AmclBatch&) = delete;
+  ~AmclBatch() { release(); }
+
+  [[nodiscard]] std::size_t size() const { return members_.size(); }
+  [[nodiscard]] Amcl& member(std::size_t i) { return members_.at(i); }
+  [[nodiscard]] std::vector<Amcl>& members() { return members_; }
+
+  /// Amcl::update on every member (amcl_core.hpp:165-201): control_actions[i] and measurements[i] are member i's.  An entry is
+  /// std::nullopt where the member did not update (no motion, no particles).  \throw std::runtime_error where a member fails;
+  /// statuses() then tells which, and the other members have updated.
+  auto update(const std::vector<SE2d>& control_actions, const std::vector<measurement_type>& measurements)
+      -> std::vector<std::optional<estimation_type>> {
+    static_assert(sizeof(std::pair<double, double>) == 2 * sizeof(double), "measurement points must be packed pairs");
+    static_assert(sizeof(SE2d) == 4 * sizeof(double), "control actions must be packed (cos, sin, x, y) records");
+    if (control_actions.size() != size() || measurements.size() != size())
+      throw std::invalid_argument("beluga_amd::AmclBatch: one control action and one measurement per member");
+    offsets_.assign(size() + 1, 0);
+    points_.clear();
+    for (std::size_t i = 0; i < size(); ++i) {
+      for (const auto& p : measurements[i]) {
+        points_.push_back(p.first);
+        points_.push_back(p.second);
+      }
+      offsets_[i + 1] = points_.size() / 2;
+    }
+    const mcl_status st = mcl_batch_update(batch_, size() ? control_actions.front().data() : nullptr, points_.data(), offsets_.data(),
+                                           estimates_.data(), infos_.data(), statuses_.data());
+    std::vector<std::optional<estimation_type>> out(size());
+    for (std::size_t i = 0; i < size(); ++i)
+      if (statuses_[i] == MCL_OK) out[i] = members_[i].finish_update(estimates_[i], infos_[i]);
+    check(st);
+    return out;
+  }
+
+  [[nodiscard]] const std::vector<mcl_update_info>& last_infos() const { return infos_; }
+  [[nodiscard]] const std::vector<mcl_status>& statuses() const { return statuses_; }
+  /// cycles, kernel_launches, members_fused, members_alone (mcl_batch_get_counter).
+  [[nodiscard]] std::uint64_t counter(const std::string& name) const {
+    std::uint64_t value = 0;
+    check(mcl_batch_get_counter(batch_, name.c_str(), &value));
+    return value;
+  }
+  [[nodiscard]] mcl_batch* native_handle() const { return batch_; }
+
+ private:
+  void check(mcl_status st) const {
+    if (st != MCL_OK) throw std::runtime_error(std::string("beluga_amd::AmclBatch: ") + mcl_batch_last_error(batch_));
+  }
+  void release() {
+    for (Amcl& m : members_) m.ctx_ = nullptr;  // (the batch destroys the contexts)
+    members_.clear();
+    mcl_batch_destroy(batch_);
+    batch_ = nullptr;
+  }
+  mcl_batch* batch_{nullptr};
+  std::vector<Amcl> members_;
+  std::vector<double> points_;
+  std::vector<std::uint64_t> offsets_;
+  std::vector<mcl_estimate> estimates_;
+  std::vector<mcl_update_info> infos_;
+  std::vector<mcl_status> statuses_;
 };
 
 }  // namespace beluga_amd

@@ -31,6 +31,7 @@ extern "C" {
 #endif
 
 typedef struct mcl_ctx mcl_ctx;
+typedef struct mcl_batch mcl_batch; /* a fleet of contexts that share their launches ("Batches of small filters" below) */
 typedef int32_t mcl_status;
 
 enum {
@@ -130,7 +131,7 @@ void mcl_default_config(mcl_config* cfg);
 
 /* beluga::Amcl ctor (amcl_core.hpp:105-124). */
 mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out);
-void mcl_destroy(mcl_ctx* ctx);
+void mcl_destroy(mcl_ctx* ctx); /* does nothing on a member of a batch: mcl_batch_destroy is its owner */
 const char* mcl_last_error(const mcl_ctx* ctx); /* ctx may be NULL: error of the last failed mcl_create */
 
 /* Sensor-model ctor / Amcl::update_map (amcl_core.hpp:150; likelihood_field_model_base.hpp:96-99,113-116,
@@ -417,6 +418,47 @@ mcl_status mcl_cluster_labels(mcl_ctx* ctx, const mcl_cluster_params* params /* 
  * publication; the set itself is not modified.  states: size x 4 doubles (cos, sin, x, y), host memory.  The draws come
  * from the counter-based stream (seed; index, 0x80000000 | draw_id): pass a different draw_id per publication. */
 mcl_status mcl_sample_particle_cloud(mcl_ctx* ctx, uint64_t size, uint32_t draw_id, double* states);
+
+/* ---- Batches of small filters: many beluga::Amcl objects, one update call, three launches for the fleet ---------------------
+ * A fleet server, a simulation farm or a multi-hypothesis tracker runs tens to hundreds of filters of the reference's own sizes (500 ..
+ * 2000 particles).  One such update is three kernels around nanoseconds of work; a batch runs those three kernels ONCE for all its
+ * members, with the members' blocks side by side in one grid, behind one synchronisation.
+ *
+ * mcl_batch_create stands for `count` beluga::Amcl constructors (amcl_core.hpp:105-124): member i is a full mcl_ctx made from cfgs[i],
+ * all on ONE device and ONE stream - every device_id equal; every hip_stream NULL (the batch creates a stream and owns it) or all the
+ * same non-NULL stream; anything else is MCL_ERR_INVALID_ARGUMENT.  count is 1 .. 1024.  Members may differ in every other
+ * parameter: map, seed, particle bounds, motion model, sensor kind, scan size.  ALL filter state lives in the members, none in the
+ * batch: mcl_batch_member hands member `index` out, and every call of this header works on it - mcl_set_map, mcl_initialize_*,
+ * mcl_set_particles, mcl_get_particles, mcl_set_option, mcl_set_estimate_kind, mcl_update itself - between batch updates, from the
+ * thread that drives the batch.  mcl_destroy on a member does nothing; mcl_batch_destroy destroys the members too.
+ *
+ * mcl_batch_update stands for Amcl::update (amcl_core.hpp:165-201) on every member: member i takes the control action
+ * control_poses[4 i .. 4 i + 4) and the scan points_xy[2 point_offsets[i] .. 2 point_offsets[i + 1]) (point_offsets: count + 1 entries
+ * that do not decrease).  For every member the call's effect and outputs - estimates[i], infos[i], the particle set, the recovery
+ * filters, the every_n counter, the step number, force_update - are those of
+ *   mcl_update(member_i, control_i, scan_i, points_i, &estimates[i], &infos[i])
+ * BIT FOR BIT, and statuses[i] is that call's status: a member that fails its preconditions (no map, ...) is left as its own failing
+ * mcl_update leaves it, one whose control has not moved far enough reports updated = 0, and the others proceed.  Returns the first
+ * non-zero member status in index order, or MCL_ERR_INVALID_ARGUMENT of its own for null control_poses / point_offsets or offsets that
+ * decrease (then no member has moved).  estimates, infos and statuses may each be NULL.
+ *
+ * Which members share the launches is decided per member and cycle: those whose own mcl_update would run exactly the small cycle -
+ * likelihood-field or likelihood-field-prob model, not sharded, option small_fused on, the set and min(max_particles, capacity) both at
+ * most 4096, the field's palette table usable, stage profiling off.  Every other member (larger sets, the beam, NDT and landmark models,
+ * profiling on) runs its ordinary cycle inside the same call; a pending mcl_set_map_async map is swapped in where mcl_update would.
+ *
+ * Counters (mcl_batch_get_counter): cycles = calls that updated at least one member; kernel_launches = kernels the shared path has
+ * enqueued, a running total (3 per cycle with a fused member, however many members there are); members_fused / members_alone = running
+ * totals of members that updated through the shared launches / through their ordinary cycle.  A fused member's own counters
+ * (small_tail_launches, lf_beams_launches) advance as in a lone cycle. */
+mcl_status mcl_batch_create(const mcl_config* cfgs, uint32_t count, mcl_batch** out);
+void mcl_batch_destroy(mcl_batch* batch);
+mcl_status mcl_batch_size(const mcl_batch* batch, uint32_t* count);
+mcl_status mcl_batch_member(mcl_batch* batch, uint32_t index, mcl_ctx** ctx);
+mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const double* points_xy, const uint64_t* point_offsets,
+                            mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses);
+mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* value);
+const char* mcl_batch_last_error(const mcl_batch* batch); /* batch may be NULL: error of the last failed mcl_batch_create */
 
 /* ---- Particle shards across the GPUs of one node (one context per GPU, one process or thread per context) -------------
  * The logical filter's particles are split into contiguous shards of the global index space (mcl_config.shard_offset /
