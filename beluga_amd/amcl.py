@@ -803,6 +803,13 @@ class Amcl:
         """Test hook (mcl_debug_set_recovery_filters): the outputs of the recovery estimator's two exponential filters."""
         self._check(self._lib.mcl_debug_set_recovery_filters(self._ctx, float(slow), float(fast)))
 
+    def last_sampler(self) -> np.ndarray:
+        """Test hook (mcl_debug_last_sampler): the sampler the last propagation's kernel received, bit for bit -
+        (m1, s1, mt, st, m2, s2, kind, first_c, first_s).  Raises before the first propagation."""
+        out = np.zeros(9)
+        self._check(self._lib.mcl_debug_last_sampler(self._ctx, _dp(out)))
+        return out
+
     def counter(self, name: str) -> int:
         v = C.c_uint64(0)
         self._check(self._lib.mcl_get_counter(self._ctx, name.encode(), C.byref(v)))

@@ -198,6 +198,7 @@ _SIGNATURES = {
     "mcl_get_counter": (C.c_int32, [_ctx, C.c_char_p, c_u64_p]),
     "mcl_debug_order": (C.c_int32, [_ctx, c_u32_p, c_u32_p]),
     "mcl_debug_set_recovery_filters": (C.c_int32, [_ctx, C.c_double, C.c_double]),
+    "mcl_debug_last_sampler": (C.c_int32, [_ctx, c_double_p]),
     "mcl_debug_curve_index": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "mcl_default_ndt_params": (None, [C.POINTER(NdtParams)]),
     "mcl_set_ndt_map": (C.c_int32, [_ctx, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_uint64, C.c_double, C.POINTER(NdtParams)]),

@@ -168,6 +168,7 @@ struct mcl_ctx {
   DiffDriveSampler order_sampler{};
   uint64_t order_ahead_used{0}, order_ahead_missed{0};
   DiffDriveSampler last_sampler{};  // of the last propagation (the prediction for the next one)
+  bool have_last_sampler{false};    // (mcl_debug_last_sampler: a propagation has been made)
   CdfTree cdf_tree() const { return make_cdf_tree(d_cdf.ptr, d_cdf_tree.ptr, n); }
   // mcl_set_map_async: the next map, its likelihood field being built on a worker thread (state 1) or built and waiting for its swap (2)
   struct PendingMap {
@@ -818,6 +819,7 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
     else if (ahead.recorded) ctx->order_ahead_missed += 1;
   }
   ctx->last_sampler = sampler;
+  ctx->have_last_sampler = true;
   const bool keys = !use_ahead && keys_emitted && ctx->wants_ordering() && ctx->predict_key_frame(&sampler, &frame);
   // (the normals of this step, if the previous cycle left them: k_noise_ahead)
   const bool ahead = ctx->d_noise.ptr && ctx->n > 65536 && ctx->facts.noise_ahead_serves(step, ctx->n, ctx->cfg.seed, ctx->cfg.shard_offset);
@@ -3531,6 +3533,15 @@ mcl_status mcl_debug_set_recovery_filters(mcl_ctx* ctx, double slow, double fast
   const double both[2] = {slow, fast};
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   MCL_HIP(ctx, hipMemcpy(ctx->d_scalars.ptr + kSlotPolicy, both, sizeof(both), hipMemcpyHostToDevice));  // {slow, fast} of {slow, fast, p}
+  return MCL_OK;
+}
+
+mcl_status mcl_debug_last_sampler(mcl_ctx* ctx, double out[9]) {
+  if (!ctx || !out) return MCL_ERR_INVALID_ARGUMENT;
+  MCL_REQUIRE(ctx, ctx->have_last_sampler, "mcl_debug_last_sampler: no propagation yet");
+  const DiffDriveSampler& s = ctx->last_sampler;
+  const double fields[9] = {s.m1, s.s1, s.mt, s.st, s.m2, s.s2, static_cast<double>(s.kind), s.first_c, s.first_s};
+  std::copy(fields, fields + 9, out);
   return MCL_OK;
 }
 

@@ -119,11 +119,14 @@ __global__ __launch_bounds__(kBlock) void k_pull_scan(const double* __restrict__
 // One particle through the motion model (the body of actions::propagate for the three models).
 // The propagation's own forms of the shared helpers (se2.h, rng.h: library sin / cos / hypot and two divisions per
 // normalisation - 1150 vector instructions per particle, four fifths of them in eight trigonometric calls and six normalisations).
-// Same expressions, evaluated another way; each within 2 ulp of the shared form (the parity tests' tolerance for a propagated
-// state is 1e-11 relative):
+// Same expressions, evaluated another way; each within 2 ulp of the shared form.  What holds them to that:
+// tests/test_gpu_propagate_edges.py - both propagation kernels against an extended-precision restatement of the motion models
+// (tests/propagate_reference.py), in units of what the inputs' own rounding allows, at most max(4, 4 * the double-precision oracle's
+// error) of them per output: angles on both sides of every quadrant boundary, k negative and up to 6e5, both sides of the 1e6
+// fallback, rotations that are not unit; DESIGN.md, "The propagation's own forms", has the figures and the mutants it catches.
 //  * sin and cos of one argument together: Cody-Waite reduction by pi/2 in two fused steps (the product k * pi/2_hi is exact
 //    inside the FMA; |theta| < 1e6, anything else - NaN included - goes to the library), fdlibm's kernel polynomials on
-//    [-pi/4, pi/4] (k_sin.c, k_cos.c: 1.1e-16 / 1.4e-16 absolute against long double, checked over 2M points);
+//    [-pi/4, pi/4] (k_sin.c, k_cos.c);
 //  * z / |z| as z * rsqrt(|z|^2): v_rsq_f64 and two Newton steps instead of hypot and two divisions.
 // (out of line: inlined at its four call sites per particle, the library's argument reduction brought 64 bytes of workgroup memory per
 // thread - its private arrays, promoted - and its registers into a path that an angle beyond a million radians alone takes)

@@ -705,6 +705,12 @@ mcl_status mcl_debug_order(mcl_ctx* ctx, uint32_t* perm, uint32_t* keys);
  * On an attached filter every rank has to make the same call. */
 mcl_status mcl_debug_set_recovery_filters(mcl_ctx* ctx, double slow, double fast);
 
+/* Test hook, read-only: the motion sampler the last propagation (mcl_propagate, or the propagation of an update) handed to its kernel, bit
+ * for bit - out = {m1, s1, mt, st, m2, s2, kind (MCL_MOTION_*), first_c, first_s}: the means and standard deviations of the first rotation,
+ * the translation and the second rotation (omnidirectional: rotation, translation, strafe; first_c / first_s = the rotation to the direction
+ * of travel).  MCL_ERR_INVALID_ARGUMENT before the first propagation.  No device work. */
+mcl_status mcl_debug_last_sampler(mcl_ctx* ctx, double out[9]);
+
 /* Position of the cell (heading, y, x), `bits` bits each, along the 3-D Hilbert curve the heading-major ordering key follows
  * (kernels.h hilbert_index_3; pure host arithmetic, no device needed): consecutive positions are face neighbours. */
 uint32_t mcl_debug_curve_index(uint32_t heading_bin, uint32_t y_bin, uint32_t x_bin, uint32_t bits /* per axis, 1 .. 6 */);

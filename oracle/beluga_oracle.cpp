@@ -1187,6 +1187,21 @@ void orc_diffdrive_sampler(const double pose[4], const double prev[4], const dou
   out[5] = s.s2;
 }
 
+// The sampler orc_propagate_kind builds for (kind, pose, prev), in the layout of mcl_debug_last_sampler:
+// {m1, s1, mt, st, m2, s2, kind, first_c, first_s} (omnidirectional: rotation, translation, strafe; stationary: zeros, first = identity).
+void orc_motion_sampler(int kind, const double pose[4], const double prev[4], const double alphas[5], double distance_threshold, double out[9]) {
+  for (int i = 0; i < 9; ++i) out[i] = 0.0;
+  out[6] = static_cast<double>(kind);
+  out[7] = 1.0;
+  if (kind == 1) {
+    const OmniSampler s = omni_sampler(se2_load(pose), se2_load(prev), alphas, distance_threshold);
+    out[0] = s.m_rot, out[1] = s.s_rot, out[2] = s.m_trans, out[3] = s.s_trans, out[5] = s.s_strafe;
+    out[7] = s.first.c, out[8] = s.first.s;
+  } else if (kind == 0) {
+    orc_diffdrive_sampler(pose, prev, alphas, distance_threshold, out);
+  }
+}
+
 void orc_propagate(double* states, uint64_t n, const double sampler[6], uint64_t seed, uint32_t step, uint64_t index_offset, int threads) {
   const DiffDriveSampler s{sampler[0], sampler[1], sampler[2], sampler[3], sampler[4], sampler[5]};
   (void)threads;

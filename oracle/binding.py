@@ -239,6 +239,15 @@ def propagate_kind(states, kind, pose, prev, alphas, seed, step, index_offset=0,
     return s
 
 
+def motion_sampler(kind, pose, prev, alphas, distance_threshold=0.01):
+    """The sampler propagate_kind builds, as (m1, s1, mt, st, m2, s2, kind, first_c, first_s)."""
+    pose, prev = _dbl(pose), _dbl(prev)
+    a = (C.c_double * 5)(*(list(alphas) + [0.0] * (5 - len(alphas))))
+    out = np.zeros(9)
+    lib().orc_motion_sampler(C.c_int(MOTION_KINDS[kind]), _d(pose), _d(prev), a, C.c_double(distance_threshold), _d(out))
+    return out
+
+
 def beam_weights(cells, res, origin, beam_params, states, points, traits=ROS_TRAITS, threads=1, return_steps=False):
     cells = np.ascontiguousarray(cells, dtype=np.int8)
     H, W = cells.shape

@@ -19,6 +19,7 @@ from beluga_amd import synth
 from beluga_amd.amcl import (Amcl, AmclParams, BeamModelParam, DifferentialDriveModelParam, LikelihoodFieldModelParam,
                              OccupancyGrid, se2_from_xytheta)
 from oracle import binding as orc
+import propagate_families as fam
 
 pytestmark = pytest.mark.gpu
 
@@ -416,13 +417,20 @@ def test_propagate_matches_oracle():
     got, _ = f.particles()
     sampler = orc.diffdrive_sampler(pose, prev, MOTION_T)
     want = orc.propagate(states, sampler, seed=11, step=7)
-    np.testing.assert_allclose(got, want, rtol=1e-11, atol=1e-13)
+    np.testing.assert_allclose(got, want, rtol=1e-11, atol=1e-13)  # (on the ORACLE's sampler: the device's own agrees with it)
+    # ... and in conditioned units against the extended-precision restatement, on the sampler the kernel received: at most
+    # max(4, 4 * the oracle's own worst) units (propagate_families.hold; the edges: test_gpu_propagate_edges.py)
+    held, oracle_errors = fam.yardstick("differential", "parity", states, f.last_sampler(), (pose, prev), MOTION_T, 7)
+    fam.hold("parity differential", got, held, oracle_errors)
     # in-place rotation branch (distance <= 0.01)
     f.set_particles(states, np.ones(n))
     pose2 = se2_from_xytheta(1.0, 0.3, 0.9)
     f.propagate(pose2, prev, step=8)
     want = orc.propagate(states, orc.diffdrive_sampler(pose2, prev, MOTION_T), seed=11, step=8)
-    np.testing.assert_allclose(f.particles()[0], want, rtol=1e-11, atol=1e-13)
+    got = f.particles()[0]
+    np.testing.assert_allclose(got, want, rtol=1e-11, atol=1e-13)
+    held, oracle_errors = fam.yardstick("differential", "parity", states, f.last_sampler(), (pose2, prev), MOTION_T, 8)
+    fam.hold("parity differential in place", got, held, oracle_errors)
     f.close()
 
 
@@ -871,13 +879,20 @@ def test_omnidirectional_and_stationary_propagation_match_oracle():
     f.set_particles(states, np.ones(n))
     f.propagate(pose, prev, step=7)
     want = orc.propagate_kind(states, "omnidirectional", pose, prev, alphas, seed=11, step=7)
-    np.testing.assert_allclose(f.particles()[0], want, rtol=1e-11, atol=1e-13)
+    got = f.particles()[0]
+    np.testing.assert_allclose(got, want, rtol=1e-11, atol=1e-13)
+    # (in conditioned units against the extended-precision restatement, as in test_propagate_matches_oracle)
+    held, oracle_errors = fam.yardstick("omnidirectional", "parity", states, f.last_sampler(), (pose, prev), alphas, 7)
+    fam.hold("parity omnidirectional", got, held, oracle_errors)
     f.close()
     f = Amcl(grid, StationaryModelParam(), LF, AmclParams(min_particles=n, max_particles=n), seed=11)
     f.set_particles(states, np.ones(n))
     f.propagate(pose, prev, step=3)
     want = orc.propagate_kind(states, "stationary", pose, prev, (0.0,) * 5, seed=11, step=3)
-    np.testing.assert_allclose(f.particles()[0], want, rtol=1e-11, atol=1e-13)
+    got = f.particles()[0]
+    np.testing.assert_allclose(got, want, rtol=1e-11, atol=1e-13)
+    held, oracle_errors = fam.yardstick("stationary", "parity", states, f.last_sampler(), (pose, prev), (0.0,) * 5, 3)
+    fam.hold("parity stationary", got, held, oracle_errors)
     f.close()
 
 
