@@ -215,8 +215,6 @@ struct mcl_ctx {
   bool have_window{false};
   Pose2 window0{}, window1{};
   uint32_t step{0};
-  bool have_pivot{false};
-  double pivot[2]{0, 0};
   Tuning tuning{};  // mcl_set_option / BELUGA_MCL_* at mcl_create (A/B measurements, tests)
   CloudEstimate cloud;  // key frame of the spatial ordering (KeyFrame): the last estimate of the set, when the host has one
   uint64_t lf_fast_launches{0};    // launches of the FMA variant of the LF kernel (mcl_get_counter)
@@ -226,6 +224,7 @@ struct mcl_ctx {
   uint64_t lf_patch_launches{0};
   uint64_t lf_queue_launches{0};  // of which by resident workgroups that take their blocks from a queue (k_reweight_lf_patch<true>)
   uint64_t lf_beams_launches{0};   // launches of k_reweight_lf_beams (mcl_get_counter)
+  uint64_t estimate_repivots{0};    // second passes of the estimate sums about the new mean (estimate_needs_repivot)
   uint64_t small_tail_launches{0};  // launches of k_small_tail (mcl_get_counter)
   uint64_t lf_far_launches{0};     // launches of the gather kernel with the far-tile bitmap (dispersed sets)
   uint64_t lf_far_beams_launches{0};  // those of them that were k_reweight_lf_far_beams (lf_dispersed = 2)
@@ -749,14 +748,13 @@ void advance_window(mcl_ctx* ctx, const Pose2& pose) {
   ctx->window0 = pose;
   ctx->have_window = true;
   ctx->step += 1;
+  const Pose2 action = pose_mul(pose_inverse(ctx->window1), ctx->window0);  // what the propagation applies to every particle, noise apart
+  ctx->facts.pivot_carried(action.r.c, action.r.s, action.x, action.y);
 }
 // :200-201: a finite estimate becomes the pivot of the next estimate sums and the cloud estimate centres the next ordering keys; the
 // caller's *estimate and *info take the results (report: what the cycle read, each value captured where it read it).
 void finish_cycle(mcl_ctx* ctx, const mcl_estimate& est, const mcl_update_info& report, mcl_estimate* estimate, mcl_update_info* info) {
-  if (std::isfinite(est.pose[2]) && std::isfinite(est.pose[3])) {
-    ctx->pivot[0] = est.pose[2];
-    ctx->pivot[1] = est.pose[3];
-  }
+  ctx->facts.estimate_reported(est.pose[0], est.pose[1], est.pose[2], est.pose[3]);
   ctx->cloud.remember(est);
   if (estimate) *estimate = est;
   if (info) *info = report;
@@ -989,10 +987,24 @@ void mirrored_sums(const mcl_ctx* ctx, const double pivot[2], double sums[12]) {
   sums[10] = pivot[1];
   sums[11] = 0.0;
 }
-mcl_status mirrored_estimate(const mcl_ctx* ctx, mcl_estimate* out) {
-  double sums[12];
-  mirrored_sums(ctx, ctx->pivot, sums);
+// The estimate from sums about a pivot; where the pivot turns out to lie outside the set (estimate_needs_repivot, cycle_host.h), `again`
+// takes the sums once more about the mean just computed - one more pass and its synchronisation, counted in estimate_repivots.  On a
+// sharded filter every rank holds the same gathered sums, takes the same decision and makes the same collective calls.
+template <class Again>
+mcl_status finish_sums(mcl_ctx* ctx, double sums[12], mcl_estimate* out, Again&& again) {
+  if (const mcl_status s = mcl_estimate_from_sums(sums, out)) return s;
+  if (!estimate_needs_repivot(sums) || !(std::isfinite(out->pose[2]) && std::isfinite(out->pose[3]))) return MCL_OK;
+  const double mean[2] = {out->pose[2], out->pose[3]};
+  ctx->estimate_repivots += 1;
+  if (const mcl_status s = again(mean, sums)) return s;
   return mcl_estimate_from_sums(sums, out);
+}
+mcl_status do_estimate_sums(mcl_ctx* ctx, const double pivot[2], double sums[12], double* scratch = nullptr);
+// ... of the whole live set, from the sums a kernel of the cycle left in the mirror about the live pivot
+mcl_status mirrored_estimate(mcl_ctx* ctx, mcl_estimate* out) {
+  double sums[12];
+  mirrored_sums(ctx, ctx->facts.pivot(), sums);
+  return finish_sums(ctx, sums, out, [&](const double* p, double* again) { return do_estimate_sums(ctx, p, again); });
 }
 
 // read_back == false: the caller reads the totals back later, with its own synchronisation.
@@ -1063,8 +1075,6 @@ mcl_status do_build_cdf(mcl_ctx* ctx, bool normalized_just_now = false, const Re
 }
 
 // scratch: the per-chunk partial sums (9 rows of num_chunks(n)); nullptr = d_chunk's rows from 0 on (which overlap chunk_row(1..8))
-mcl_status do_estimate_sums(mcl_ctx* ctx, const double pivot[2], double sums[12], double* scratch = nullptr);
-
 // NDT model: the random-state source of the next draw, N(estimate(particles)) of the set as it stands (ndt_amcl_node.cpp:248-254: built
 // where amcl_core.hpp:182 builds it - after the recovery estimator and the resample policy, before the estimator's reset at :184-186).
 // Only where states can be injected (p > 0): one estimate pass and its synchronisation.  The estimate's partial sums go to a buffer of
@@ -1077,7 +1087,7 @@ mcl_status prepare_ndt_random(mcl_ctx* ctx, double random_state_probability) {
   ctx->ndt_random_ready = false;
   MCL_HIP(ctx, ctx->d_ndt_est.ensure(static_cast<size_t>(9) * std::max<uint32_t>(num_chunks(ctx->n), 1u)));
   double sums[12];
-  if (const mcl_status s = do_estimate_sums(ctx, ctx->pivot, sums, ctx->d_ndt_est.ptr)) return s;
+  if (const mcl_status s = do_estimate_sums(ctx, ctx->facts.pivot(), sums, ctx->d_ndt_est.ptr)) return s;
   mcl_estimate est{};
   (void)mcl_estimate_from_sums(sums, &est);
   FreeCells src{nullptr, 1};
@@ -1162,7 +1172,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       const bool order_keys = noise_in_draw && ctx->done_armed && ctx->tuning.order_ahead != 0 && max_p < (1ull << 32) && ctx->wants_ordering() &&
                               ctx->predict_key_frame(&ctx->last_sampler, &ahead_frame, 2);
       launch_resample_draw_and_estimate(ctx->stream, ctx->cur(), ctx->cdf_tree(), d_total, ctx->other(), ra, gv, fc, hp,
-                                        ctx->pivot[0], ctx->pivot[1], ctx->d_est_partials.ptr, ctx->d_scalars.ptr + kSlotEstimate,
+                                        ctx->facts.pivot()[0], ctx->facts.pivot()[1], ctx->d_est_partials.ptr, ctx->d_scalars.ptr + kSlotEstimate,
                                         ctx->hd_scalars + kSlotEstimate, ctx->done_armed ? &done : nullptr,
                                         ((ctx->tuning.draw_fold == 2 || (ctx->tuning.draw_fold == 1 && max_p <= 65536)) && ctx->d_scan_state.ptr)
                                             ? reinterpret_cast<unsigned int*>(ctx->d_scan_state.ptr + 4)
@@ -1340,7 +1350,7 @@ struct ClusterMask {
   CellTable table;
   unsigned int cluster;
 };
-mcl_status sharded_estimate(mcl_ctx* ctx, const ClusterMask* mask, mcl_estimate* out) {
+mcl_status sharded_sums(mcl_ctx* ctx, const ClusterMask* mask, const double pivot[2], double sums[12]) {
   if (const mcl_status s = comm_scratch(ctx)) return s;
   const uint32_t world = ctx->comm_world;
   double* d_est = ctx->d_comm_f64.ptr + kCommEstimate;
@@ -1348,10 +1358,10 @@ mcl_status sharded_estimate(mcl_ctx* ctx, const ClusterMask* mask, mcl_estimate*
   if (ctx->n == 0) {
     MCL_HIP(ctx, hipMemsetAsync(d_est, 0, 9 * sizeof(double), ctx->stream));
   } else if (mask) {
-    launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, mask->table, mask->cluster, ctx->pivot[0], ctx->pivot[1],
+    launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, mask->table, mask->cluster, pivot[0], pivot[1],
                                  ctx->chunk_row(0), d_est);
   } else {
-    launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, ctx->pivot[0], ctx->pivot[1], ctx->chunk_row(0), d_est);
+    launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, pivot[0], pivot[1], ctx->chunk_row(0), d_est);
   }
   MCL_HIP(ctx, hipGetLastError());
   // (with the nine sums travels kCommOverflow: this rank's flag of the cycle's fixed-capacity exchange - their sum lands in kSlotOverflow)
@@ -1360,7 +1370,13 @@ mcl_status sharded_estimate(mcl_ctx* ctx, const ClusterMask* mask, mcl_estimate*
   MCL_HIP(ctx, hipGetLastError());
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->comm_host_syncs += 1;
-  return mirrored_estimate(ctx, out);
+  mirrored_sums(ctx, pivot, sums);
+  return MCL_OK;
+}
+mcl_status sharded_estimate(mcl_ctx* ctx, const ClusterMask* mask, mcl_estimate* out) {
+  double sums[12];
+  if (const mcl_status s = sharded_sums(ctx, mask, ctx->facts.pivot(), sums)) return s;
+  return finish_sums(ctx, sums, out, [&](const double* p, double* again) { return sharded_sums(ctx, mask, p, again); });
 }
 
 // ---- cluster_based_estimate (cluster_based_estimation.hpp:415-433) ------------------------------------------------------
@@ -1551,22 +1567,34 @@ mcl_status cluster_sums(mcl_ctx* ctx, const HashParams& hp, const CellScratch& s
   const unsigned int m = c.m;
   if (const mcl_status s = upload_cell_values(ctx, c, cluster_of)) return s;
   if (c.small) {  // (the cells' keys and their cluster ids are in the mapped list)
-    launch_small_cluster_sums(ctx->stream, ctx->cur(), ctx->n, hp, c.dev.list.key, c.dev.cluster, m, wanted, ctx->pivot[0], ctx->pivot[1],
-                              ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
-    MCL_HIP(ctx, hipGetLastError());
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return mirrored_estimate(ctx, out);
+    auto small = [&](const double* p, double* sums) -> mcl_status {
+      launch_small_cluster_sums(ctx->stream, ctx->cur(), ctx->n, hp, c.dev.list.key, c.dev.cluster, m, wanted, p[0], p[1],
+                                ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+      MCL_HIP(ctx, hipGetLastError());
+      MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      mirrored_sums(ctx, p, sums);
+      return MCL_OK;
+    };
+    double sums[12];
+    if (const mcl_status s = small(ctx->facts.pivot(), sums)) return s;
+    return finish_sums(ctx, sums, out, small);  // (a cluster far from the overall estimate: its sums once more about its own mean)
   }
   if (m) launch_cell_set_cluster(ctx->stream, c.dev.list, c.dev.cluster, m, sc.table);
   if (sharded) {
     const ClusterMask mask{sc.table, wanted};
     return sharded_estimate(ctx, &mask, out);
   }
-  launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, sc.table, wanted, ctx->pivot[0], ctx->pivot[1],
-                               ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
-  MCL_HIP(ctx, hipGetLastError());
-  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return mirrored_estimate(ctx, out);
+  auto masked = [&](const double* p, double* sums) -> mcl_status {
+    launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, sc.table, wanted, p[0], p[1],
+                                 ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+    MCL_HIP(ctx, hipGetLastError());
+    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    mirrored_sums(ctx, p, sums);
+    return MCL_OK;
+  };
+  double sums[12];
+  if (const mcl_status s = masked(ctx->facts.pivot(), sums)) return s;
+  return finish_sums(ctx, sums, out, masked);
 }
 
 // The front half every clustering entry point shares: the scratch, this context's occupied cells, the list of all cells in
@@ -1622,8 +1650,8 @@ mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_e
   if (!f.assigned.winner) {  // :424-427 no cluster: overall mean and covariance
     if (f.sharded) return sharded_estimate(ctx, nullptr, out);
     double sums[12];
-    if (const mcl_status s = do_estimate_sums(ctx, ctx->pivot, sums)) return s;
-    return mcl_estimate_from_sums(sums, out);
+    if (const mcl_status s = do_estimate_sums(ctx, ctx->facts.pivot(), sums)) return s;
+    return finish_sums(ctx, sums, out, [&](const double* p, double* again) { return do_estimate_sums(ctx, p, again); });
   }
   return cluster_sums(ctx, f.hp, f.sc, f.mine, f.cluster_of_my_cells(), *f.assigned.winner, f.sharded, out);
 }
@@ -1656,7 +1684,7 @@ mcl_status do_estimate_clusters(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_
   const size_t partials = rows * num_chunks(ctx->n);
   MCL_HIP(ctx, ctx->d_cluster_sums.ensure(partials + rows));
   double* d_sums = ctx->d_cluster_sums.ptr + partials;
-  launch_estimate_sums_clusters(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, f.sc.table, ranks, ctx->pivot[0], ctx->pivot[1],
+  launch_estimate_sums_clusters(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, f.sc.table, ranks, ctx->facts.pivot()[0], ctx->facts.pivot()[1],
                                 ctx->d_cluster_sums.ptr, d_sums);
   MCL_HIP(ctx, hipGetLastError());
   std::vector<double> sums(rows);
@@ -1667,10 +1695,19 @@ mcl_status do_estimate_clusters(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_
     const unsigned int id = sel.selected[r];
     double twelve[12] = {0};
     std::memcpy(twelve, sums.data() + static_cast<size_t>(r) * 9, 9 * sizeof(double));
-    twelve[9] = ctx->pivot[0];
-    twelve[10] = ctx->pivot[1];
+    twelve[9] = ctx->facts.pivot()[0];
+    twelve[10] = ctx->facts.pivot()[1];
     found[r] = mcl_cluster_estimate{id, 0u, f.assigned.count[id], twelve[0], {}};
-    if (const mcl_status s = mcl_estimate_from_sums(twelve, &found[r].estimate)) return fail(ctx, s, "mcl_estimate_clusters: bad sums");
+    // (a cluster far from the overall estimate: one masked pass of its own about its own mean - the table's column carries the ranks)
+    auto masked = [&](const double* p, double* again) -> mcl_status {
+      launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, f.sc.table, r, p[0], p[1], ctx->chunk_row(0),
+                                   ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+      MCL_HIP(ctx, hipGetLastError());
+      MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      mirrored_sums(ctx, p, again);
+      return MCL_OK;
+    };
+    if (const mcl_status s = finish_sums(ctx, twelve, &found[r].estimate, masked)) return fail(ctx, s, "mcl_estimate_clusters: bad sums");
   }
   // the reported weight is the sums pass's, and so is the order
   std::sort(found.begin(), found.end(), [](const mcl_cluster_estimate& a, const mcl_cluster_estimate& b) {
@@ -2471,15 +2508,25 @@ struct InstallSet {
   enum { kCloudKept, kCloudUnknown, kCloudGiven } cloud;
   double cloud_mean[3], cloud_sigma[3];
   LfPlanner::Installed patches;  // the LF patch statistics: as they were / history / history, and the set is dispersed
+  // the pivot of the estimate sums (SetFacts): with kCloudGiven the cloud's mean; otherwise a point of the set if the caller has one.
+  // pivot_kept: a shard of a sharded filter - every rank has to sum about the same point and none knows the others' states, so the
+  // pivot stays what the last collective estimate made it on every rank (SetFacts::set_replaced; the origin before the first: the
+  // first estimate then takes its second pass, collectively)
+  bool pivot_known = false;
+  double pivot[2] = {0.0, 0.0};
+  bool pivot_kept = false;
 };
 void install_set(mcl_ctx* ctx, const InstallSet& s) {
-  ctx->facts.set_replaced(s.unit_weights);
+  ctx->facts.set_replaced(s.unit_weights, s.pivot_kept);
   ctx->n = s.n;
   if (s.global == InstallSet::kGlobalShares) ctx->global_n = 0;
   if (s.global != InstallSet::kGlobalKept) ctx->global_n_unknown = s.global == InstallSet::kGlobalAsked && ctx->have_comm && ctx->comm_world > 1;
   if (s.force_update) ctx->force_update = true;
   if (s.cloud == InstallSet::kCloudGiven) ctx->cloud.set(s.cloud_mean, s.cloud_sigma);
   else if (s.cloud == InstallSet::kCloudUnknown) ctx->cloud.forget();
+  if (s.cloud == InstallSet::kCloudGiven)  // (the mean's heading carries the pivot through the first control action)
+    ctx->facts.estimate_reported(std::cos(s.cloud_mean[2]), std::sin(s.cloud_mean[2]), s.cloud_mean[0], s.cloud_mean[1]);
+  else if (s.pivot_known) ctx->facts.pivot_given(s.pivot[0], s.pivot[1]);
   uint64_t planned = 0, through = 0;
   if (s.patches != LfPlanner::Installed::kKept) patch_totals(ctx, &planned, &through);
   ctx->lf_planner.set_installed(s.patches, planned, through);
@@ -2540,8 +2587,14 @@ mcl_status mcl_set_particles(mcl_ctx* ctx, const double* states, const double* w
     MCL_HIP(ctx, hipMemcpy(ctx->cur().pose, states, n * 4 * sizeof(double), hipMemcpyHostToDevice));  // same record layout
     MCL_HIP(ctx, hipMemcpy(ctx->cur().w, weights, n * sizeof(double), hipMemcpyHostToDevice));
   }
+  // the pivot: the first state that carries weight lies within the set; a shard's first state is another on every rank
+  uint64_t first = 0;
+  while (first < n && !(weights[first] > 0.0)) ++first;
+  const bool sharded = ctx->have_comm && ctx->comm_world > 1;
+  const bool pivot_known = first < n && !sharded;
   install_set(ctx, {.n = n, .unit_weights = false, .global = InstallSet::kGlobalAsked, .force_update = true, .cloud = InstallSet::kCloudUnknown,
-                    .patches = LfPlanner::Installed::kFresh});
+                    .patches = LfPlanner::Installed::kFresh, .pivot_known = pivot_known,
+                    .pivot = {pivot_known ? states[4 * first + 2] : 0.0, pivot_known ? states[4 * first + 3] : 0.0}, .pivot_kept = sharded});
   return MCL_OK;
 }
 
@@ -2628,12 +2681,9 @@ mcl_status mcl_estimate_pose(mcl_ctx* ctx, mcl_estimate* out) {
   if (ctx->n == 0) return fail(ctx, MCL_ERR_NOT_READY, "no particles");
   if (const mcl_status s = bind_device(ctx)) return s;
   double sums[12];
-  if (const mcl_status s = do_estimate_sums(ctx, ctx->pivot, sums)) return s;
-  const mcl_status s = mcl_estimate_from_sums(sums, out);
-  if (s == MCL_OK && std::isfinite(out->pose[2]) && std::isfinite(out->pose[3])) {
-    ctx->pivot[0] = out->pose[2];
-    ctx->pivot[1] = out->pose[3];
-  }
+  if (const mcl_status s = do_estimate_sums(ctx, ctx->facts.pivot(), sums)) return s;
+  const mcl_status s = finish_sums(ctx, sums, out, [&](const double* p, double* again) { return do_estimate_sums(ctx, p, again); });
+  if (s == MCL_OK) ctx->facts.estimate_reported(out->pose[0], out->pose[1], out->pose[2], out->pose[3]);
   return s;
 }
 
@@ -2660,8 +2710,8 @@ static SmallTail small_tail_record(const mcl_ctx* ctx, bool fires) {
   t.hp = HashParams{ap.spatial_resolution_x, ap.spatial_resolution_y, ap.spatial_resolution_theta};
   t.g = ctx->grid_view();
   t.fc = ctx->random_source();
-  t.pivot_x = ctx->pivot[0];
-  t.pivot_y = ctx->pivot[1];
+  t.pivot_x = ctx->facts.pivot()[0];
+  t.pivot_y = ctx->facts.pivot()[1];
   t.mirror = ctx->hd_scalars;
   t.d_scalars = ctx->d_scalars.ptr;
   return t;
@@ -3286,7 +3336,7 @@ mcl_status mcl_load_shard(mcl_ctx* ctx, const double* d_states, uint64_t n, uint
   launch_fill(ctx->stream, ctx->cur().w, n, 1.0);  // particle_traits.hpp:105
   MCL_HIP(ctx, hipGetLastError());
   install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalKept, .force_update = false, .cloud = InstallSet::kCloudUnknown,
-                    .patches = LfPlanner::Installed::kKept});
+                    .patches = LfPlanner::Installed::kKept, .pivot_kept = true});
   ctx->cfg.shard_offset = shard_offset;
   return MCL_OK;
 }
@@ -3480,6 +3530,7 @@ mcl_status mcl_get_counter(mcl_ctx* ctx, const char* name, uint64_t* value) {
   else if (key == "lf_far_launches") *value = ctx->lf_far_launches;
   else if (key == "lf_far_beams_launches") *value = ctx->lf_far_beams_launches;
   else if (key == "small_tail_launches") *value = ctx->small_tail_launches;
+  else if (key == "estimate_repivots") *value = ctx->estimate_repivots;
   else if (key == "lf_far_tiles") *value = ctx->far_tiles;
   else if (key == "noise_ahead_used") *value = ctx->noise_ahead_used;
   else if (key == "order_ahead_used") *value = ctx->order_ahead_used;

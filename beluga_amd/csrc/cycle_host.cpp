@@ -343,4 +343,13 @@ uint64_t rebalance_block(uint64_t pos, uint64_t cnt, uint64_t n_out, uint32_t wo
   return std::min(std::max(pos, new_first) - new_first, new_n);
 }
 
+bool estimate_needs_repivot(const double sums[12]) {
+  const double w = sums[0];
+  if (!(w > 0.0)) return false;
+  const double mx = sums[4] / w, my = sums[5] / w;
+  const double m2 = mx * mx + my * my, second = (sums[6] + sums[8]) / w;
+  if (!(m2 - m2 == 0.0 && second - second == 0.0)) return false;
+  return (1.0 + kRepivotMultiple) * m2 > kRepivotMultiple * second;
+}
+
 }  // namespace mcl

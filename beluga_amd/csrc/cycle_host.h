@@ -54,6 +54,20 @@ struct KeyFrameInputs {
 bool predict_key_frame(const CloudEstimate& cloud, const DiffDriveSampler* motion, int moves, uint32_t layout, const KeyFrameInputs& in,
                        KeyFrame* out);
 
+// ---- is the pivot of the estimate sums still inside the set? -----------------------------------------------------------------------------
+// sums: the twelve of mcl_estimate_from_sums.  With m = (S w dx, S w dy) / W the offset of the mean from the pivot and
+// M = (S w dx^2 + S w dy^2) / W the second moment about the pivot (a sum of positive terms: well conditioned whatever the pivot), the
+// biased variance is T = M - |m|^2.  A sum's rounding error is a count of roundings times u M; the estimate is held to the same count
+// times u D^2, D the diagonal of the set's bounding box, so the sums serve while M <= D^2.  The host does not know D, but each axis'
+// variance is at most a quarter of its extent squared (Popoviciu), so T <= D^2 / 4 and M = T + |m|^2 <= D^2 wherever |m|^2 <= 3 T:
+// the multiple is kRepivotMultiple = 3, and written on the well-conditioned quantities the test is |m|^2 > 3/4 M.  True: take the
+// sums once more about the mean just computed (then m is a rounding of zero and M = T).  False for sums that are not finite.
+// A set with no spread at all (one particle, a set collapsed onto one state, one particle holding all the weight: T = 0) answers true
+// for any m != 0: its covariance is exact only about the state itself.  Such a filter pays the second pass on every cycle whose carried
+// pivot is not bit-equal to that state; a filter with any spread does not (the carried pivot lands within it).
+constexpr double kRepivotMultiple = 3.0;
+bool estimate_needs_repivot(const double sums[12]);
+
 // ---- which likelihood-field kernel a cycle takes -------------------------------------------------------------------------------------
 // What the planner reads of the context.
 struct LfSite {

@@ -8,10 +8,16 @@
 //             once this cycle's propagation found it usable: the reweight then skips the ordering passes
 //   normals   the propagation normals of (step, seed) for the global indices [offset, offset + n), drawn a cycle ahead; they depend on
 //             nothing else, so any set of that size at that step may use them
+//   pivot     the point the estimate sums of the live set are taken about (dx = x - pivot): it has to lie within the set, or the
+//             covariance loses (distance / spread)^2 of its digits.  Known from whoever installed the set (the mean it drew about, the
+//             first state it copied) or from the set's last finite estimate; void once another set has replaced it
 //
 //   event                              unit            lf sums    divides    order       normals
 //   set_changes                        .               void       .          void        .
-//   set_replaced(unit)                 = unit          void       .          void        .
+//   pivot_given(x, y)                  .               .          .          .           .             (pivot: = (x, y) if finite)
+//   estimate_reported(c, s, x, y)      .               .          .          .           .             (pivot: = (x, y) if finite, heading (c, s))
+//   pivot_carried(dc, ds, tx, ty)      .               .          .          .           .             (pivot: moved by the control action if its heading is known)
+//   set_replaced(unit[, keep_pivot])   = unit          void       .          void        .             (pivot: void unless kept)
 //   set_resized(grew)                  false if grew   void       .          void        .
 //   weights_rewrite_begins             false           .          .          .           .
 //   weights_touched                    false           .          .          .           .
@@ -31,6 +37,9 @@
 // still voided what described the old set.  A rewrite that begins and fails leaves unit false; one that succeeds ends in
 // set_replaced(true).  lf_sums_dropped is both the normalisation consuming the sums and anything that makes them stale (a failed
 // launch, a resampling that begins, the small tail).  `unit_weights()` is read by nothing but tests: the reweight takes it.
+// set_replaced voids the pivot; the entry point gives the new one behind it (pivot_given, through install_set).  set_changes alone
+// and set_resized keep it: a call that fails leaves the old set live, and a resized set still holds the particles the pivot lay among.  A resampling
+// does not void it: the new set is drawn from the old one's particles.  An estimate that is not finite leaves the pivot as it was.
 #pragma once
 
 #include <cstdint>
@@ -49,8 +58,37 @@ class SetFacts {
     return noise_n_ >= n && noise_step_ == step && noise_seed_ == seed && noise_offset_ == offset;
   }
 
+  bool pivot_known() const { return pivot_known_; }
+  bool pivot_heading_known() const { return pivot_known_ && heading_known_; }
+  const double* pivot() const { return pivot_; }  // (0, 0) while void
+
   void set_changes() { lf_sums_ = 0; order_recorded_ = false; }
-  void set_replaced(bool unit) { set_changes(); unit_ = unit; }
+  void pivot_given(double x, double y) {
+    if (!(x - x == 0.0 && y - y == 0.0)) return;  // (neither NaN nor infinite)
+    pivot_known_ = true; heading_known_ = false; pivot_[0] = x; pivot_[1] = y;
+  }
+  // (c, s): the heading of the estimate, a unit complex number; one that is not finite leaves the position alone known
+  void estimate_reported(double c, double s, double x, double y) {
+    if (!(x - x == 0.0 && y - y == 0.0)) return;
+    pivot_given(x, y);
+    if (c - c == 0.0 && s - s == 0.0) { heading_known_ = true; heading_[0] = c; heading_[1] = s; }
+  }
+  // The control action (dc, ds, tx, ty) = previous^-1 * current, as the propagation applies it to every particle: the pivot goes where
+  // a particle at the last estimate goes, noise apart.  Without a heading (a pivot that was given, not estimated) it stays.
+  void pivot_carried(double dc, double ds, double tx, double ty) {
+    if (!pivot_heading_known() || !(dc - dc == 0.0 && ds - ds == 0.0 && tx - tx == 0.0 && ty - ty == 0.0)) return;
+    const double c = heading_[0], s = heading_[1];
+    pivot_[0] += c * tx - s * ty;
+    pivot_[1] += s * tx + c * ty;
+    heading_[0] = c * dc - s * ds;
+    heading_[1] = s * dc + c * ds;
+  }
+  // keep_pivot: a shard of a sharded filter - every rank sums about the same point and none knows the others' states, so the pivot
+  // stays what the ranks' last collective estimate made it (finish_sums' second pass, context.hip, moves it into the set).
+  void set_replaced(bool unit, bool keep_pivot = false) {
+    set_changes(); unit_ = unit;
+    if (!keep_pivot) { pivot_known_ = heading_known_ = false; pivot_[0] = pivot_[1] = 0.0; }
+  }
   void set_resized(bool grew) { set_changes(); if (grew) unit_ = false; }  // (what lies beyond the old set is whatever was there)
   void weights_rewrite_begins() { unit_ = false; }
   void weights_touched() { unit_ = false; }
@@ -80,6 +118,8 @@ class SetFacts {
   bool unit_{false}, divides_{false}, order_recorded_{false}, order_accepted_{false};
   uint32_t lf_sums_{0}, order_step_{0}, order_layout_{0}, noise_step_{0};
   uint64_t order_n_{0}, noise_n_{0}, noise_offset_{0}, noise_seed_{0};
+  bool pivot_known_{false}, heading_known_{false};
+  double pivot_[2]{0.0, 0.0}, heading_[2]{1.0, 0.0};
 };
 
 }  // namespace mcl

@@ -558,6 +558,11 @@ def test_estimate_matches_oracle():
     want_pose, want_cov = orc.estimate(states, w)
     np.testing.assert_allclose(pose, want_pose, rtol=0, atol=1e-9)
     np.testing.assert_allclose(cov, want_cov, rtol=1e-9, atol=1e-12)
+    # ... and in the conditioned units of the exact reference (tests/estimate_reference.py), the oracle's own error the yardstick
+    import estimate_families as fam
+    import estimate_reference as est_ref
+    exact = est_ref.estimate(states, w)
+    fam.hold("test_estimate_matches_oracle", n, est_ref.errors(exact, pose, cov), est_ref.errors(exact, want_pose, want_cov))
     # degenerate orientation (test_estimation.cpp:184-197)
     two = np.array([se2_from_xytheta(0, 0, math.pi / 2), se2_from_xytheta(0, 0, -math.pi / 2)])
     f.set_particles(two, [1.0, 1.0])

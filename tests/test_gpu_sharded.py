@@ -126,6 +126,67 @@ def test_sharded_ranks_sharing_one_gpu_match_single_context(world, min_p, max_p,
     np.testing.assert_allclose(got["w"], wa, rtol=1e-12)
 
 
+# ---- a map frame far from the origin ---------------------------------------------------------------------------------------
+FAR_ORIGIN = (5e5, 4e6)
+
+
+def _far_workload(n_cycles=3, beams=180):
+    cells = synth.make_rooms_map(128, 128, seed=5, n_rooms=4)
+    grid = OccupancyGrid(cells, 0.05, origin=se2_from_xytheta(FAR_ORIGIN[0], FAR_ORIGIN[1], 0.0))
+    truth = synth.find_free_pose(cells, 0.05, FAR_ORIGIN, seed=3, clearance_cells=6)
+    angles = synth.lidar_angles(beams, 270.0)
+    pose, odom, steps = truth, (0.0, 0.0, 0.0), []
+    for c in range(n_cycles):
+        pose = synth.odometry_step(pose, 0.3, 0.05)
+        odom = synth.odometry_step(odom, 0.3, 0.05)
+        pts = synth.scan_points(synth.cast_scan(cells, 0.05, FAR_ORIGIN, pose, angles, 8.0, 0.01, seed=c), angles)
+        steps.append((se2_from_xytheta(*odom), pts))
+    return grid, truth, steps
+
+
+def _far_worker(rank, world, init_file, params, out_dir):
+    import torch
+    import torch.distributed as dist
+
+    from beluga_amd.sharded import ShardedAmcl
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", init_method=f"file://{init_file}", rank=rank, world_size=world)
+    grid, truth, steps = _far_workload()
+    f = ShardedAmcl(grid, MOTION, LF, params, seed=9, device=0)
+    f.initialize(truth, np.diag([0.04, 0.04, 0.01]))
+    outs, sets = [], []
+    for c, p in steps:
+        outs.append(f.update(c, p))
+        sets.append(f.gather_particles())  # (collective: the whole set as this cycle leaves it)
+    np.savez(os.path.join(out_dir, f"rank{rank}.npz"), poses=np.array([o[0] for o in outs]), covs=np.array([o[1] for o in outs]),
+             **{f"states{c}": s for c, (s, _) in enumerate(sets)}, **{f"w{c}": w for c, (_, w) in enumerate(sets)})
+    dist.barrier()
+    f.close()
+    dist.destroy_process_group()
+
+
+def test_sharded_ranks_on_a_far_map_return_the_same_bits_within_the_exact_reference(tmp_path):
+    """Two ranks on the one GPU, a grid whose origin is (5e5, 4e6): every rank returns the same bits, and each cycle's estimate is
+    within the limit of the exact reference over the concatenated shards that cycle leaves (tests/estimate_reference.py; the limit
+    counts one more addition per rank)."""
+    import torch.multiprocessing as mp
+
+    import estimate_families as fam
+    import estimate_reference as est_ref
+    from oracle import binding as orc
+    world, n = 2, 20_001
+    params = AmclParams(min_particles=n, max_particles=n)
+    mp.spawn(_far_worker, args=(world, str(tmp_path / "rendezvous"), params, str(tmp_path)), nprocs=world, join=True)
+    got = [np.load(str(tmp_path / f"rank{r}.npz")) for r in range(world)]
+    assert got[0]["poses"].tobytes() == got[1]["poses"].tobytes() and got[0]["covs"].tobytes() == got[1]["covs"].tobytes()
+    for c in range(len(got[0]["poses"])):
+        s, w = got[0][f"states{c}"], got[0][f"w{c}"]
+        assert len(w) == n
+        r = est_ref.estimate(s, w)
+        fam.hold(f"2 ranks, far map, cycle {c}", n, est_ref.errors(r, got[0]["poses"][c], got[0]["covs"][c]),
+                 est_ref.errors(r, *orc.estimate(s, w)), world=world)
+
+
 def test_sharded_kld_world1_nccl_matches_single_gpu():
     import torch
     import torch.distributed as dist
