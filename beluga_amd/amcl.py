@@ -831,7 +831,7 @@ class Amcl:
 
 class AmclBatch:
     """A fleet of small filters that share their launches (mcl_batch_*): one update call, three kernel launches for all members whose
-    cycle is the small one, one synchronisation.  specs: one entry per member, the argument set of Amcl(...) - a dict of keyword
+    cycle is the small one, one synchronisation - and two more shared launches for those of them that return the cluster-based estimate.  specs: one entry per member, the argument set of Amcl(...) - a dict of keyword
     arguments, or a tuple of positional ones that may end with such a dict; `grid` may be None (the member gets its map later).
     Every member is on one device and one stream (`hip_stream`: all 0, or all the same).  members[i] are Amcl objects bound to the
     batch's contexts: every Amcl method works on them between batch updates; they do not own their contexts (close() does nothing)."""
@@ -947,8 +947,15 @@ class AmclBatch:
                  "weight_sum": info.weight_sum, "ess": info.effective_sample_size,
                  "random_state_probability": info.random_state_probability} for info in self._infos]
 
+    def set_option(self, name: str, value: int):
+        """mcl_set_option on every member, e.g. batch_cluster_fused (default 1; 0: the member's cluster-based estimate through its own
+        kernels instead of the fleet's two shared launches)."""
+        for member in self.members:
+            member.set_option(name, value)
+
     def counter(self, name: str) -> int:
-        """cycles, kernel_launches, members_fused, members_alone (mcl_batch_get_counter)."""
+        """cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns
+        (mcl_batch_get_counter)."""
         value = C.c_uint64(0)
         self._check(self._lib.mcl_batch_get_counter(self._batch, name.encode(), C.byref(value)))
         return value.value

@@ -11,6 +11,23 @@ bool batch_member_fused(const BatchMemberFacts& m) {
          m.max_particles <= kBatchMaxParticles && m.palette_beams && !m.profiling;
 }
 
+bool batch_cluster_member(const BatchClusterFacts& m) {
+  return m.status == MCL_OK && m.estimate_kind == 1 && m.cluster_fused && m.n >= 1 && m.n <= kBatchMaxParticles &&
+         cluster_params_ok(m.linear_hash_resolution, m.angular_hash_resolution, m.weight_cap_percentile);
+}
+
+uint32_t batch_cluster_select(const BatchClusterFacts* m, uint32_t members, uint32_t* picked) {
+  uint32_t count = 0;
+  for (uint32_t i = 0; i < members; ++i)
+    if (batch_cluster_member(m[i])) picked[count++] = i;
+  return count;
+}
+
+uint32_t batch_cluster_launches(uint32_t cells_members, uint32_t sums_members) {
+  if (cells_members == 0) return 0;
+  return sums_members ? 2 : 1;
+}
+
 BatchGrid batch_layout(const uint64_t* n, const uint32_t* lds, uint32_t members, uint32_t* first_propagate, uint32_t* first_reweight) {
   BatchGrid g{members, 0, 0, 0};
   for (uint32_t m = 0; m < members; ++m) {

@@ -1,6 +1,6 @@
 // batch_host.h — the arithmetic of a batch of small filters (mcl_batch_*) that touches no device memory: which members of a cycle share
 // the three launches, where each member's blocks lie in the two gridded launches, how a block finds its member, how much workgroup memory
-// the shared reweight needs, and the validation of mcl_batch_create's configs and mcl_batch_update's scan offsets.  context.hip calls
+// the shared reweight needs, which members share the cluster-based estimate's two launches, and the validation of mcl_batch_create's configs and mcl_batch_update's scan offsets.  context.hip calls
 // them between its launches; batch_member_of is also what the batched kernels run (kernels.hip).  Plain C++17, no HIP.
 #pragma once
 
@@ -30,6 +30,28 @@ struct BatchMemberFacts {
 };
 // The member's own mcl_update would run exactly k_propagate_small, k_reweight_lf_beams with a wave per particle, k_small_tail.
 bool batch_member_fused(const BatchMemberFacts& m);
+
+// ---- which fused members share the cluster-based estimate's two launches ------------------------------------------------------------------
+// What cluster_front checks of cluster parameters before anything is launched.
+inline bool cluster_params_ok(double linear_hash_resolution, double angular_hash_resolution, double weight_cap_percentile) {
+  return linear_hash_resolution > 0 && angular_hash_resolution > 0 && weight_cap_percentile >= 0 && weight_cap_percentile < 1.0;
+}
+// A fused member behind the state half of its cycle (the live set is the one the estimate is taken of).
+struct BatchClusterFacts {
+  int status;         // of the state half: MCL_OK, or the member has left the cycle
+  int estimate_kind;  // 0: beluga::estimate, 1: cluster_based_estimate
+  bool cluster_fused; // the member's option batch_cluster_fused
+  uint64_t n;         // particles of the live set
+  double linear_hash_resolution, angular_hash_resolution, weight_cap_percentile;  // the member's mcl_cluster_params
+};
+// The member's estimate goes through k_batch_small_cluster_cells / k_batch_small_cluster_sums: the small path of its own
+// mcl_cluster_based_estimate would take it, and nothing about it is refused.
+bool batch_cluster_member(const BatchClusterFacts& m);
+// picked[0 .. returned count): the indices m < members with batch_cluster_member, in order.
+uint32_t batch_cluster_select(const BatchClusterFacts* m, uint32_t members, uint32_t* picked);
+// Shared cluster launches of a cycle: `cells_members` records went to the first kernel, `sums_members` of them - those whose assignment
+// has a winner - to the second.  0, 1 or 2.
+uint32_t batch_cluster_launches(uint32_t cells_members, uint32_t sums_members);
 
 // ---- where the members' blocks are ---------------------------------------------------------------------------------------------------
 MCL_HD uint32_t batch_propagate_blocks(uint64_t n) { return static_cast<uint32_t>((n + kBatchPropagateBlock - 1) / kBatchPropagateBlock); }

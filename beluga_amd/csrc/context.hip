@@ -1456,6 +1456,12 @@ struct MyCells {
     return Pose2{Rot2{q.x, q.y}, q.z, q.w};
   }
 };
+void order_by_first(MyCells* c) {
+  c->order.resize(c->m);
+  std::iota(c->order.begin(), c->order.end(), 0u);
+  const unsigned int* first = c->host.list.first;
+  std::sort(c->order.begin(), c->order.end(), [first](uint32_t a, uint32_t b) { return first[a] < first[b]; });
+}
 // allow_small = false: the kernels of the large path whatever the set's size (they leave the table and the hashes the per-particle
 // passes of mcl_estimate_clusters and mcl_cluster_labels probe)
 mcl_status collect_cells(mcl_ctx* ctx, const HashParams& hp, const CellScratch& sc, bool sharded, bool allow_small, MyCells* c) {
@@ -1508,10 +1514,20 @@ mcl_status collect_cells(mcl_ctx* ctx, const HashParams& hp, const CellScratch& 
     MCL_HIP(ctx, hipMemcpyAsync(h.state, big.state, m * sizeof(double4), hipMemcpyDeviceToHost, ctx->stream));
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
-  c->order.resize(m);
-  std::iota(c->order.begin(), c->order.end(), 0u);
-  const unsigned int* first = c->host.list.first;
-  std::sort(c->order.begin(), c->order.end(), [first](uint32_t a, uint32_t b) { return first[a] < first[b]; });
+  order_by_first(c);
+  return MCL_OK;
+}
+// The cells a shared launch of k_batch_small_cluster_cells left in this member's mapped list (mcl_batch_update, behind its
+// synchronisation): what collect_cells does behind its own launch of the lone kernel.
+mcl_status collect_batched_cells(mcl_ctx* ctx, const CellScratch& sc, MyCells* c) {
+  c->host = sc.mapped;
+  c->dev = sc.mapped_dev;
+  c->small = true;
+  c->m = *sc.mapped.list.size;
+  if (!(c->m >= 1 && c->m <= sc.m_cap)) return fail(ctx, MCL_ERR_HIP, "cell compaction failed");
+  ctx->cluster_cells = c->m;
+  c->on_host_list = true;  // (at most 4096 cells)
+  order_by_first(c);
   return MCL_OK;
 }
 
@@ -1561,20 +1577,23 @@ mcl_status upload_cell_values(mcl_ctx* ctx, const MyCells& c, const std::vector<
   return MCL_OK;
 }
 
+// k_small_cluster_sums over this context's set about `p`, launched on its own and waited for (the cells' keys and their cluster ids are
+// in the mapped list).
+mcl_status small_cluster_sums_pass(mcl_ctx* ctx, const HashParams& hp, const MyCells& c, unsigned int wanted, const double* p, double* sums) {
+  launch_small_cluster_sums(ctx->stream, ctx->cur(), ctx->n, hp, c.dev.list.key, c.dev.cluster, c.m, wanted, p[0], p[1],
+                            ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+  MCL_HIP(ctx, hipGetLastError());
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  mirrored_sums(ctx, p, sums);
+  return MCL_OK;
+}
 // The cells' cluster ids back to the device and the sums over the particles of cluster `wanted`.
 mcl_status cluster_sums(mcl_ctx* ctx, const HashParams& hp, const CellScratch& sc, const MyCells& c, const std::vector<unsigned int>& cluster_of,
                         unsigned int wanted, bool sharded, mcl_estimate* out) {
   const unsigned int m = c.m;
   if (const mcl_status s = upload_cell_values(ctx, c, cluster_of)) return s;
-  if (c.small) {  // (the cells' keys and their cluster ids are in the mapped list)
-    auto small = [&](const double* p, double* sums) -> mcl_status {
-      launch_small_cluster_sums(ctx->stream, ctx->cur(), ctx->n, hp, c.dev.list.key, c.dev.cluster, m, wanted, p[0], p[1],
-                                ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
-      MCL_HIP(ctx, hipGetLastError());
-      MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      mirrored_sums(ctx, p, sums);
-      return MCL_OK;
-    };
+  if (c.small) {
+    auto small = [&](const double* p, double* sums) { return small_cluster_sums_pass(ctx, hp, c, wanted, p, sums); };
     double sums[12];
     if (const mcl_status s = small(ctx->facts.pivot(), sums)) return s;
     return finish_sums(ctx, sums, out, small);  // (a cluster far from the overall estimate: its sums once more about its own mean)
@@ -1613,18 +1632,21 @@ struct ClusterFront {
     return cluster_of;
   }
 };
+mcl_status cluster_front_assign(mcl_ctx* ctx, const mcl_cluster_params& cp, ClusterFront* f);
 mcl_status cluster_front(mcl_ctx* ctx, const mcl_cluster_params& cp, bool allow_small, ClusterFront* f) {
   const uint64_t n = ctx->n;
   f->sharded = ctx->have_comm && ctx->comm_world > 1;
   if (n == 0 && !f->sharded) return fail(ctx, MCL_ERR_NOT_READY, "no particles");  // (an empty shard still takes part in the exchange)
-  MCL_REQUIRE(ctx, cp.linear_hash_resolution > 0 && cp.angular_hash_resolution > 0 && cp.weight_cap_percentile >= 0 &&
-                       cp.weight_cap_percentile < 1.0, "bad cluster parameters");
+  MCL_REQUIRE(ctx, cluster_params_ok(cp.linear_hash_resolution, cp.angular_hash_resolution, cp.weight_cap_percentile), "bad cluster parameters");
   MCL_REQUIRE(ctx, n < 0xFFFFFFFFull, "too many particles");
   if (const mcl_status s = cluster_scratch(ctx, &f->sc)) return s;
   f->hp = HashParams{cp.linear_hash_resolution, cp.linear_hash_resolution, cp.angular_hash_resolution};
+  if (const mcl_status s = collect_cells(ctx, f->hp, f->sc, f->sharded, allow_small, &f->mine)) return s;
+  return cluster_front_assign(ctx, cp, f);
+}
+// ... from the collected cells (f->mine) on: mcl_batch_update enters here behind its shared launch.
+mcl_status cluster_front_assign(mcl_ctx* ctx, const mcl_cluster_params& cp, ClusterFront* f) {
   MyCells& mine = f->mine;
-  if (const mcl_status s = collect_cells(ctx, f->hp, f->sc, f->sharded, allow_small, &mine)) return s;
-
   // The occupied cells in the order their first particle appears in the set; over shards, the ranks' lists merged.
   std::vector<ClusterCell> cells(mine.m);
   for (uint32_t j = 0; j < mine.m; ++j) {
@@ -2243,7 +2265,7 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
     }
     // Environment defaults of the per-context switches (mcl_set_option changes them at run time).
     for (const char* name : {"lf_variant", "lf_fast", "lf_table", "lf_patch", "lf_dispersed", "lf_far_tiles", "key_layout", "lf_loose_below", "lf_small_particles", "device_policy",
-                             "sort_min_particles", "beam_sort_min_particles", "field_build", "key_curve", "key_warp", "key_bits_xy", "lf_margin", "lf_split", "lf_queue_grid", "shard_pad_permille", "lf_queue", "lf_ends_first", "beam_free_ahead", "beam_sectors", "lf_weight_sums", "beam_table", "cycle_spin", "scan_fused", "draw_fold", "lf_unit_weights", "small_fused", "norm_store", "noise_ahead", "order_ahead", "lf_far_beams_per_wave"}) {
+                             "sort_min_particles", "beam_sort_min_particles", "field_build", "key_curve", "key_warp", "key_bits_xy", "lf_margin", "lf_split", "lf_queue_grid", "shard_pad_permille", "lf_queue", "lf_ends_first", "beam_free_ahead", "beam_sectors", "lf_weight_sums", "beam_table", "cycle_spin", "scan_fused", "draw_fold", "lf_unit_weights", "small_fused", "norm_store", "noise_ahead", "order_ahead", "lf_far_beams_per_wave", "batch_cluster_fused"}) {
       std::string env = "BELUGA_MCL_";
       for (const char* c = name; *c; ++c) env += static_cast<char>(std::toupper(static_cast<unsigned char>(*c)));
       if (const char* v = std::getenv(env.c_str())) {
@@ -2723,9 +2745,11 @@ static void small_tail_launched(mcl_ctx* ctx, uint64_t every_n) {
   ctx->facts.lf_sums_dropped();
   ctx->facts.weights_touched();
 }
-// finish: behind the synchronisation.  The mirror's verdict flips the live set, the recovery filters take their new outputs, the
-// estimate (:200) and the pivot follow.
-static mcl_status finish_small_cycle(mcl_ctx* ctx, mcl_estimate* estimate, mcl_update_info* info) {
+// finish: behind the synchronisation, in three parts.  The state half: the mirror's verdict flips the live set, the recovery filters take
+// their new outputs; returns what the info reports.  The estimate (:200).  finish_cycle: the pivot and the caller's outputs.  mcl_update
+// runs them back to back (finish_small_cycle); mcl_batch_update runs the state half of every member, then the estimates - those of
+// the cluster-based kind through two shared launches (batch_cluster_estimates) - then finish_cycle.
+static mcl_update_info small_cycle_state(mcl_ctx* ctx) {
   stage_collect(ctx);
   const double* h = ctx->h_scalars;
   const bool resampled = h[kSlotResampled] != 0.0;
@@ -2738,13 +2762,17 @@ static mcl_status finish_small_cycle(mcl_ctx* ctx, mcl_estimate* estimate, mcl_u
   ctx->fast.output = h[kSlotFast];
   ctx->force_update = false;  // :199
   // (what the info reports, before another kernel's mirrored values take their place)
-  const mcl_update_info report{1, resampled, ctx->n, h[kSlotWeightSum], h[kSlotEss], h[kSlotPolicyP]};
+  return mcl_update_info{1, resampled, ctx->n, h[kSlotWeightSum], h[kSlotEss], h[kSlotPolicyP]};
+}
+static mcl_status small_cycle_estimate(mcl_ctx* ctx, mcl_estimate* est) {
+  // beluga_ros::Amcl returns cluster_based_estimate (beluga_ros/src/amcl.cpp:125): its own kernels
+  if (ctx->estimate_kind == 1) return mcl_cluster_based_estimate(ctx, &ctx->cluster_params, est);
+  return mirrored_estimate(ctx, est);  // :200
+}
+static mcl_status finish_small_cycle(mcl_ctx* ctx, mcl_estimate* estimate, mcl_update_info* info) {
+  const mcl_update_info report = small_cycle_state(ctx);
   mcl_estimate est{};
-  if (ctx->estimate_kind == 1) {  // beluga_ros::Amcl returns cluster_based_estimate (beluga_ros/src/amcl.cpp:125): its own kernels
-    if (const mcl_status s = mcl_cluster_based_estimate(ctx, &ctx->cluster_params, &est)) return s;
-  } else if (const mcl_status s = mirrored_estimate(ctx, &est)) {  // :200
-    return s;
-  }
+  if (const mcl_status s = small_cycle_estimate(ctx, &est)) return s;
   finish_cycle(ctx, est, report, estimate, info);
   return MCL_OK;
 }
@@ -2914,6 +2942,15 @@ mcl_status mcl_update(mcl_ctx* ctx, const double control_pose[4], const double* 
 // All filter state lives in the members; the batch owns the shared stream (unless the caller gave one), the members' lifetime and the
 // table of the cycle's records.
 }  // extern "C"
+namespace {
+// A member on its way through the cluster-based estimate's two shared launches (batch_cluster_estimates).
+struct BatchClusterMember {
+  uint32_t index{0};
+  mcl_ctx* ctx{nullptr};
+  ClusterFront f;
+  std::vector<unsigned int> cluster_of;
+};
+}  // namespace
 struct mcl_batch {
   std::string error;
   int device{0};
@@ -2926,7 +2963,23 @@ struct mcl_batch {
   std::vector<uint32_t> fused;  // the members whose cycle the batch launches, in index order
   std::vector<uint64_t> fused_n;
   std::vector<uint32_t> fused_lds, first_propagate, first_reweight;
-  uint64_t cycles{0}, kernel_launches{0}, members_fused{0}, members_alone{0};
+  // the cluster-based estimate's two shared launches: a record per member and launch, pinned and on the device
+  BatchClusterCells* h_cluster_cells{nullptr};
+  BatchClusterSums* h_cluster_sums{nullptr};
+  DeviceBuffer<BatchClusterCells> d_cluster_cells;
+  DeviceBuffer<BatchClusterSums> d_cluster_sums;
+  uint64_t cycles{0}, kernel_launches{0}, members_fused{0}, members_alone{0}, cluster_launches{0}, members_cluster_fused{0};
+  uint64_t cluster_host_ns{0};  // host time between the two shared launches: every member's cells ordered, assigned, ids written
+  // per call, kept for the next one: by member ...
+  std::vector<mcl_status> status;
+  std::vector<mcl_update_info> report;
+  std::vector<mcl_estimate> est;
+  std::vector<uint8_t> shared;  // the member's estimate went through the shared cluster launches
+  // ... and by fused member
+  std::vector<BatchClusterFacts> cluster_facts;
+  std::vector<uint32_t> picked, summed;
+  std::vector<BatchClusterMember> cluster_members;  // the first cluster_count of them are this cycle's
+  uint32_t cluster_count{0};
 };
 namespace {
 mcl_status batch_fail(mcl_batch* b, mcl_status code, const std::string& msg) {
@@ -2964,6 +3017,109 @@ mcl_status batch_launch(mcl_batch* b) {
   if (e != hipSuccess) return batch_fail(b, MCL_ERR_HIP, std::string("mcl_batch_update: ") + hipGetErrorString(e));
   return MCL_OK;
 }
+// One table of records to the device and one launch over them, waited for.  *enqueued: the launch went out.
+template <class Record, class Launch>
+mcl_status batch_cluster_launch(mcl_batch* b, const Record* h_items, DeviceBuffer<Record>& d_items, uint32_t count, Launch&& launch, bool* enqueued) {
+  hipError_t e = hipMemcpyAsync(d_items.ptr, h_items, count * sizeof(Record), hipMemcpyHostToDevice, b->stream);
+  if (e == hipSuccess) {
+    launch(b->stream, d_items.ptr, count);
+    e = hipGetLastError();
+    *enqueued = e == hipSuccess;
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+  if (e != hipSuccess) return batch_fail(b, MCL_ERR_HIP, std::string("mcl_batch_update (cluster-based estimate): ") + hipGetErrorString(e));
+  return MCL_OK;
+}
+// cluster_based_estimate of the members b->picked (batch_cluster_select) through two shared launches and two synchronisations; the host
+// steps between them are each member's own, as do_cluster_estimate takes them.  b->est[i], b->status[i]: by member.  A member that
+// fails leaves with its own status; the others proceed.  Returns the shared launches that went out (batch_cluster_launches).
+uint32_t batch_cluster_estimates(mcl_batch* b) {
+  std::vector<mcl_status>& status = b->status;
+  b->cluster_count = 0;
+  for (const uint32_t i : b->picked) {  // 1. the scratch, 2. the records
+    mcl_ctx* ctx = b->members[i];
+    BatchClusterMember& m = b->cluster_members[b->cluster_count];
+    m.index = i;
+    m.ctx = ctx;
+    const mcl_cluster_params& cp = ctx->cluster_params;
+    m.f.hp = HashParams{cp.linear_hash_resolution, cp.linear_hash_resolution, cp.angular_hash_resolution};
+    if (const mcl_status s = cluster_scratch(ctx, &m.f.sc)) {
+      status[i] = s;
+      continue;
+    }
+    CellList out = m.f.sc.mapped_dev.list;
+    out.size = m.f.sc.arrays.list.size;  // (as collect_cells hands it to the lone kernel)
+    b->h_cluster_cells[b->cluster_count++] = BatchClusterCells{ctx->cur(), static_cast<uint32_t>(ctx->n), m.f.hp, out, m.f.sc.mapped_dev.list.size};
+  }
+  const uint32_t count = b->cluster_count;
+  if (count == 0) return 0;
+  BatchClusterMember* const members = b->cluster_members.data();
+  auto drop_all = [&](mcl_status s) {
+    for (uint32_t k = 0; k < count; ++k)
+      if (status[members[k].index] == MCL_OK) status[members[k].index] = fail(members[k].ctx, s, b->error);
+  };
+  // 3. 4. the cells of every member
+  bool cells_out = false, sums_out = false;
+  if (const mcl_status s = batch_cluster_launch(b, b->h_cluster_cells, b->d_cluster_cells, count, launch_batch_small_cluster_cells, &cells_out)) {
+    drop_all(s);
+    return batch_cluster_launches(cells_out ? count : 0, 0);
+  }
+  // 5. per member: its cells in first-occurrence order, the host's assignment, the cluster ids into its mapped list
+  const auto t0 = std::chrono::steady_clock::now();
+  b->summed.clear();
+  for (uint32_t k = 0; k < count; ++k) {
+    BatchClusterMember& m = members[k];
+    mcl_ctx* ctx = m.ctx;
+    if (const mcl_status s = collect_batched_cells(ctx, m.f.sc, &m.f.mine)) {
+      status[m.index] = s;
+      continue;
+    }
+    if (const mcl_status s = cluster_front_assign(ctx, ctx->cluster_params, &m.f)) {
+      status[m.index] = s;
+      continue;
+    }
+    if (!m.f.assigned.winner) continue;  // (below, on its own)
+    m.cluster_of = m.f.cluster_of_my_cells();
+    if (const mcl_status s = upload_cell_values(ctx, m.f.mine, m.cluster_of)) {
+      status[m.index] = s;
+      continue;
+    }
+    const MyCells& c = m.f.mine;
+    b->h_cluster_sums[b->summed.size()] = BatchClusterSums{ctx->cur(), static_cast<uint32_t>(ctx->n), m.f.hp, c.dev.list.key, c.dev.cluster, c.m,
+                                                           *m.f.assigned.winner, ctx->facts.pivot()[0], ctx->facts.pivot()[1],
+                                                           ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate};
+    b->summed.push_back(k);
+  }
+  b->cluster_host_ns += static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
+  // 6. 7. the sums of every member that has a winner
+  const uint32_t summed = static_cast<uint32_t>(b->summed.size());
+  if (summed)
+    if (const mcl_status s = batch_cluster_launch(b, b->h_cluster_sums, b->d_cluster_sums, summed, launch_batch_small_cluster_sums, &sums_out)) {
+      drop_all(s);
+      return batch_cluster_launches(count, sums_out ? summed : 0);
+    }
+  // 8. the estimates; the two rare cases run the member's own kernels
+  for (uint32_t k = 0; k < count; ++k) {
+    BatchClusterMember& m = members[k];
+    mcl_ctx* ctx = m.ctx;
+    if (status[m.index] != MCL_OK) continue;
+    double sums[12];
+    mcl_estimate* out = &b->est[m.index];
+    if (!m.f.assigned.winner) {  // :424-427 no cluster: overall mean and covariance
+      status[m.index] = do_estimate_sums(ctx, ctx->facts.pivot(), sums);
+      if (status[m.index] == MCL_OK)
+        status[m.index] = finish_sums(ctx, sums, out, [&](const double* p, double* again) { return do_estimate_sums(ctx, p, again); });
+    } else {
+      mirrored_sums(ctx, ctx->facts.pivot(), sums);
+      // (a cluster far from the overall estimate: its sums once more about its own mean)
+      status[m.index] = finish_sums(ctx, sums, out, [&](const double* p, double* again) {
+        return small_cluster_sums_pass(ctx, m.f.hp, m.f.mine, *m.f.assigned.winner, p, again);
+      });
+    }
+    if (status[m.index] == MCL_OK) b->members_cluster_fused += 1;
+  }
+  return batch_cluster_launches(count, summed);
+}
 }  // namespace
 extern "C" {
 
@@ -2994,6 +3150,10 @@ mcl_status mcl_batch_create(const mcl_config* cfgs, uint32_t count, mcl_batch** 
     hipError_t e = hipSetDevice(b->device);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b->h_items), count * sizeof(BatchItem), hipHostMallocDefault);
     if (e == hipSuccess) e = b->d_items.ensure(count);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b->h_cluster_cells), count * sizeof(BatchClusterCells), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b->h_cluster_sums), count * sizeof(BatchClusterSums), hipHostMallocDefault);
+    if (e == hipSuccess) e = b->d_cluster_cells.ensure(count);
+    if (e == hipSuccess) e = b->d_cluster_sums.ensure(count);
     if (e != hipSuccess) st = batch_fail(nullptr, e == hipErrorOutOfMemory ? MCL_ERR_OUT_OF_MEMORY : MCL_ERR_HIP,
                                          std::string("mcl_batch_create: ") + hipGetErrorString(e));
   }
@@ -3002,6 +3162,14 @@ mcl_status mcl_batch_create(const mcl_config* cfgs, uint32_t count, mcl_batch** 
     return st;
   }
   b->held.resize(count);
+  b->status.resize(count);
+  b->report.resize(count);
+  b->est.resize(count);
+  b->shared.resize(count);
+  b->cluster_facts.resize(count);
+  b->picked.reserve(count);
+  b->summed.reserve(count);
+  b->cluster_members.resize(count);
   *out = b;
   return MCL_OK;
 }
@@ -3014,7 +3182,11 @@ void mcl_batch_destroy(mcl_batch* batch) {
     mcl_destroy(ctx);  // (synchronises the shared stream first)
   }
   if (batch->h_items) (void)hipHostFree(batch->h_items);
+  if (batch->h_cluster_cells) (void)hipHostFree(batch->h_cluster_cells);
+  if (batch->h_cluster_sums) (void)hipHostFree(batch->h_cluster_sums);
   batch->d_items.release();
+  batch->d_cluster_cells.release();
+  batch->d_cluster_sums.release();
   if (batch->own_stream && batch->stream) (void)hipStreamDestroy(batch->stream);
   delete batch;
 }
@@ -3042,7 +3214,8 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
   if (const char* wrong = batch_check_offsets(point_offsets, count)) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, wrong);
   if (point_offsets[count] != point_offsets[0] && !points_xy) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_update: null points");
   // prepare: every member's own cycle up to its launches; a cycle that is not the small one runs to its end here
-  std::vector<mcl_status> status(count, MCL_OK);
+  std::vector<mcl_status>& status = batch->status;
+  std::fill(status.begin(), status.end(), MCL_OK);
   batch->fused.clear();
   bool any_updated = false;
   for (uint32_t i = 0; i < count; ++i) {
@@ -3068,21 +3241,36 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
   // launch, and finish behind the one synchronisation
   if (!batch->fused.empty()) {
     const mcl_status launched = batch_launch(batch);
+    const uint32_t fused = static_cast<uint32_t>(batch->fused.size());
+    std::vector<mcl_update_info>& report = batch->report;
+    std::vector<mcl_estimate>& est = batch->est;
+    for (uint32_t k = 0; k < fused; ++k) {  // the state half of every member
+      const uint32_t i = batch->fused[k];
+      mcl_ctx* ctx = batch->members[i];
+      if (launched != MCL_OK) status[i] = fail(ctx, launched, batch->error);
+      else status[i] = bind_device(ctx);
+      if (status[i] == MCL_OK) report[i] = small_cycle_state(ctx);
+      est[i] = mcl_estimate{};
+      const mcl_cluster_params& cp = ctx->cluster_params;
+      batch->cluster_facts[k] = BatchClusterFacts{status[i], ctx->estimate_kind, ctx->tuning.batch_cluster_fused != 0, ctx->n, cp.linear_hash_resolution,
+                                                  cp.angular_hash_resolution, cp.weight_cap_percentile};
+    }
+    // the estimates: the cluster-based ones that qualify through the shared launches, every other one as the lone cycle takes it
+    batch->picked.resize(fused);
+    batch->picked.resize(batch_cluster_select(batch->cluster_facts.data(), fused, batch->picked.data()));
+    std::fill(batch->shared.begin(), batch->shared.end(), uint8_t{0});
+    for (uint32_t& k : batch->picked) {
+      k = batch->fused[k];
+      batch->shared[k] = 1;
+    }
+    batch->cluster_launches += batch_cluster_estimates(batch);
     for (const uint32_t i : batch->fused) {
       mcl_ctx* ctx = batch->members[i];
-      if (launched != MCL_OK) {
-        status[i] = fail(ctx, launched, batch->error);
-        continue;
-      }
-      if (const mcl_status s = bind_device(ctx)) {
-        status[i] = s;
-        continue;
-      }
-      status[i] = finish_small_cycle(ctx, estimates ? &estimates[i] : nullptr, infos ? &infos[i] : nullptr);
-      if (status[i] == MCL_OK) {
-        batch->members_fused += 1;
-        any_updated = true;
-      }
+      if (status[i] == MCL_OK && !batch->shared[i]) status[i] = small_cycle_estimate(ctx, &est[i]);
+      if (status[i] != MCL_OK) continue;
+      finish_cycle(ctx, est[i], report[i], estimates ? &estimates[i] : nullptr, infos ? &infos[i] : nullptr);
+      batch->members_fused += 1;
+      any_updated = true;
     }
   }
   if (any_updated) batch->cycles += 1;
@@ -3104,6 +3292,9 @@ mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* v
   else if (key == "kernel_launches") *value = batch->kernel_launches;
   else if (key == "members_fused") *value = batch->members_fused;
   else if (key == "members_alone") *value = batch->members_alone;
+  else if (key == "cluster_launches") *value = batch->cluster_launches;
+  else if (key == "members_cluster_fused") *value = batch->members_cluster_fused;
+  else if (key == "cluster_host_ns") *value = batch->cluster_host_ns;
   else return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_get_counter: unknown counter " + key);
   return MCL_OK;
 }
@@ -3510,6 +3701,7 @@ mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value) {
   else if (key == "draw_fold") t.draw_fold = static_cast<int>(std::clamp<int64_t>(value, 0, 2));
   else if (key == "lf_unit_weights") t.lf_unit_weights = value ? 1 : 0;
   else if (key == "small_fused") t.small_fused = value ? 1 : 0;
+  else if (key == "batch_cluster_fused") t.batch_cluster_fused = value ? 1 : 0;
   else if (key == "norm_store") t.norm_store = value ? 1 : 0;
   else if (key == "order_ahead") t.order_ahead = value ? 1 : 0;
   else if (key == "noise_ahead") t.noise_ahead = static_cast<int>(std::clamp<int64_t>(value, 0, 2));

@@ -100,6 +100,8 @@ struct Tuning {
   int norm_store = 0;               // fixed-size cycle that resamples at once: 0 = k_normalize leaves the chunk sums of the normalised weights
                                     // but does not store them - the CDF kernel divides again (same division, same bits), nothing else reads them;
                                     // 1 = stored
+  int batch_cluster_fused = 1;      // a member of a batch (mcl_batch_update) whose cycle was fused and which returns the cluster-based estimate: 1 = that
+                                    // estimate through the batch's two shared launches, 0 = through its own mcl_cluster_based_estimate
   int small_fused = 1;              // sets of up to 4096 particles (plain estimate, one context): everything behind the reweight - normalise,
                                     // policies, fixed-size or KLD resampling, estimate sums - in one launch of one workgroup and one host
                                     // synchronisation (k_small_tail); 0 = the kernels of the large path

@@ -618,6 +618,29 @@ bool launch_small_cluster_cells(hipStream_t st, Particles p, uint64_t n, HashPar
 void launch_small_cluster_sums(hipStream_t st, Particles p, uint64_t n, HashParams hp, const unsigned long long* d_keys,
                                const unsigned int* d_cluster, uint32_t cells, unsigned int wanted, double pivot_x, double pivot_y, double* d_out,
                                double* host_mirror);
+// The two kernels over a fleet (mcl_batch_update): one workgroup per record, every record one member's arguments of the lone kernel.  The
+// host fills a table per launch (the sums' table holds only the members whose assignment has a winner).
+struct BatchClusterCells {
+  Particles p;  // the live set
+  uint32_t n;   // 1 .. 4096
+  HashParams hp;
+  CellList out;               // the member's own mapped list, out.size its size word in device memory
+  unsigned int* size_mirror;  // ... and the list's size word in the mapped memory
+};
+struct BatchClusterSums {
+  Particles p;
+  uint32_t n;
+  HashParams hp;
+  const unsigned long long* keys;  // the list's keys and the host's cluster ids, `cells` of each
+  const unsigned int* cluster;
+  uint32_t cells;
+  unsigned int wanted;
+  double pivot_x, pivot_y;
+  double* d_out;   // the member's d_scalars + kSlotEstimate
+  double* mirror;  // ... and hd_scalars + kSlotEstimate
+};
+void launch_batch_small_cluster_cells(hipStream_t st, const BatchClusterCells* d_items, uint32_t members);
+void launch_batch_small_cluster_sums(hipStream_t st, const BatchClusterSums* d_items, uint32_t members);
 // t.cluster[cells.slot[k]] = d_cluster[k], k < m
 void launch_cell_set_cluster(hipStream_t st, const CellList& cells, const unsigned int* d_cluster, uint32_t m, const CellTable& t);
 void launch_estimate_sums_cluster(hipStream_t st, Particles p, uint64_t n, const unsigned long long* d_hashes, const CellTable& t,

@@ -3901,7 +3901,9 @@ __global__ __launch_bounds__(kBlock) void k_cluster_labels(uint64_t n, const uns
 // particle and its state).  k_small_cluster_sums: the host's cluster ids per cell back into a table, the estimate's sums over the particles
 // of the winning cluster (estimate_clusters :345-411 over estimation.hpp:436-475).
 constexpr size_t kSmallClusterLdsBytes = kSmallMax * 8 /* hashes */ + kSmallSlots * 4 /* table */ + kSmallMax * 4 /* counts */ + kSmallMax * 8 /* sums */ + 64;
-__global__ __launch_bounds__(kSmallBlock) void k_small_cluster_cells(Particles p, uint32_t n, HashParams hp, CellList out, unsigned int* size_mirror) {
+// (the bodies: ONE set in one workgroup - the lone kernels' own arguments, or a member's record in the batched forms below)
+__device__ __forceinline__ void small_cluster_cells_block(const Particles& p, uint32_t n, const HashParams& hp, const CellList& out,
+                                                          unsigned int* size_mirror) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned long long* s_hash = reinterpret_cast<unsigned long long*>(smem);
   uint32_t* s_table = reinterpret_cast<uint32_t*>(smem + kSmallMax * 8);
@@ -3956,10 +3958,29 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_cluster_cells(Particles p
     *size_mirror = *s_size;
   }
 }
-__global__ __launch_bounds__(kSmallBlock) void k_small_cluster_sums(Particles p, uint32_t n, HashParams hp, const unsigned long long* __restrict__ keys,
-                                                                    const unsigned int* __restrict__ cluster, uint32_t cells, unsigned int wanted,
-                                                                    double pivot_x, double pivot_y, double* __restrict__ d_out,
-                                                                    double* __restrict__ mirror) {
+__global__ __launch_bounds__(kSmallBlock) void k_small_cluster_cells(Particles p, uint32_t n, HashParams hp, CellList out, unsigned int* size_mirror) {
+  small_cluster_cells_block(p, n, hp, out, size_mirror);
+}
+// (its pointers are typed as pointers to GLOBAL memory: a kernel's own arguments are known to be that, a pointer read out of a record is
+// a generic one to the compiler and would be followed with flat instructions and 64-bit addresses in registers.  The poses are read as
+// four doubles each, since double4's copy constructor takes a generic reference.)
+#define MCL_GLOBAL __attribute__((address_space(1)))
+struct GlobalSums {
+  const MCL_GLOBAL double* pose;  // [n][4]: (c, s, x, y)
+  const MCL_GLOBAL double* w;
+  const MCL_GLOBAL unsigned long long* keys;
+  const MCL_GLOBAL unsigned int* cluster;
+  MCL_GLOBAL double* d_out;
+  MCL_GLOBAL double* mirror;
+};
+__device__ __forceinline__ GlobalSums global_sums(const Particles& p, const unsigned long long* keys, const unsigned int* cluster, double* d_out,
+                                                  double* mirror) {
+  return GlobalSums{(const MCL_GLOBAL double*)reinterpret_cast<const double*>(p.pose), (const MCL_GLOBAL double*)p.w,
+                    (const MCL_GLOBAL unsigned long long*)keys, (const MCL_GLOBAL unsigned int*)cluster, (MCL_GLOBAL double*)d_out,
+                    (MCL_GLOBAL double*)mirror};
+}
+__device__ __forceinline__ void small_cluster_sums_block(const GlobalSums g, uint32_t n, const HashParams& hp, uint32_t cells, unsigned int wanted,
+                                                         double pivot_x, double pivot_y) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned long long* s_key = reinterpret_cast<unsigned long long*>(smem);  // [kSmallMax] the cells' keys
   uint32_t* s_table = reinterpret_cast<uint32_t*>(smem + kSmallMax * 8);   // [kSmallSlots] -> cell
@@ -3968,8 +3989,8 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_cluster_sums(Particles p,
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (uint32_t s = tid; s < kSmallSlots; s += kSmallBlock) s_table[s] = 0xFFFFFFFFu;
   for (uint32_t j = tid; j < cells; j += kSmallBlock) {
-    s_key[j] = keys[j];
-    s_cluster[j] = cluster[j];
+    s_key[j] = g.keys[j];
+    s_cluster[j] = g.cluster[j];
   }
   __syncthreads();
   for (uint32_t j = tid; j < cells; j += kSmallBlock) {  // (the keys are distinct)
@@ -3979,7 +4000,8 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_cluster_sums(Particles p,
   __syncthreads();
   double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (uint32_t i = tid; i < n; i += kSmallBlock) {
-    const double4 q = p.pose[i];
+    const MCL_GLOBAL double* at = g.pose + 4 * static_cast<size_t>(i);
+    const double4 q = make_double4(at[0], at[1], at[2], at[3]);
     const unsigned long long key = kld_key(spatial_hash(Pose2{Rot2{q.x, q.y}, q.z, q.w}, hp));
     uint32_t slot = static_cast<uint32_t>(kld_slot(key, kSmallSlots - 1));
     uint32_t cell = s_table[slot];
@@ -3988,7 +4010,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_cluster_sums(Particles p,
       cell = s_table[slot];
     }
     if (cell == 0xFFFFFFFFu || s_cluster[cell] != wanted) continue;
-    const double w = p.w[i];
+    const double w = g.w[i];
     const double dx = q.z - pivot_x, dy = q.w - pivot_y;
     v[0] += w;
     v[1] += w * w;
@@ -4010,9 +4032,28 @@ __global__ __launch_bounds__(kSmallBlock) void k_small_cluster_sums(Particles p,
   if (tid < 9) {
     double acc = s_wave[tid];
     for (uint32_t q = 1; q < kSmallBlock / 64; ++q) acc += s_wave[q * 9 + tid];
-    d_out[tid] = acc;
-    mirror[tid] = acc;
+    g.d_out[tid] = acc;
+    g.mirror[tid] = acc;
   }
+}
+__global__ __launch_bounds__(kSmallBlock) void k_small_cluster_sums(Particles p, uint32_t n, HashParams hp, const unsigned long long* __restrict__ keys,
+                                                                    const unsigned int* __restrict__ cluster, uint32_t cells, unsigned int wanted,
+                                                                    double pivot_x, double pivot_y, double* __restrict__ d_out,
+                                                                    double* __restrict__ mirror) {
+  small_cluster_sums_block(global_sums(p, keys, cluster, d_out, mirror), n, hp, cells, wanted, pivot_x, pivot_y);
+}
+// The same over a fleet (mcl_batch_update): one workgroup per member, blockIdx.x its record.  A member writes its own list, its own size
+// words and its own sums, nothing else; the record is uniform over the workgroup.
+// (amdgpu_waves_per_eu(5) on the sums: with the 128 registers that 1024 threads allow, the scheduler spreads spatial_hash's three
+// divisions over 105 registers where the lone kernel, scheduled the same way but for other scalar registers, takes 90; five waves per
+// SIMD is what the lone kernel's 90 amount to, and asking for it gives the same 90, no scratch - DESIGN 9a)
+__global__ __launch_bounds__(kSmallBlock) void k_batch_small_cluster_cells(const BatchClusterCells* __restrict__ items) {
+  const BatchClusterCells it = items[blockIdx.x];
+  small_cluster_cells_block(it.p, it.n, it.hp, it.out, it.size_mirror);
+}
+__global__ __launch_bounds__(kSmallBlock) __attribute__((amdgpu_waves_per_eu(5))) void k_batch_small_cluster_sums(const BatchClusterSums* __restrict__ items) {
+  const BatchClusterSums it = items[blockIdx.x];
+  small_cluster_sums_block(global_sums(it.p, it.keys, it.cluster, it.d_out, it.mirror), it.n, it.hp, it.cells, it.wanted, it.pivot_x, it.pivot_y);
 }
 
 
@@ -4342,7 +4383,9 @@ hipError_t configure_device_kernels() {
       {reinterpret_cast<const void*>(k_small_tail), kSmallLdsBytes},
       {reinterpret_cast<const void*>(k_batch_small_tail), kSmallLdsBytes},
       {reinterpret_cast<const void*>(k_small_cluster_cells), kSmallClusterLdsBytes},
-      {reinterpret_cast<const void*>(k_small_cluster_sums), kSmallClusterLdsBytes}};
+      {reinterpret_cast<const void*>(k_small_cluster_sums), kSmallClusterLdsBytes},
+      {reinterpret_cast<const void*>(k_batch_small_cluster_cells), kSmallClusterLdsBytes},
+      {reinterpret_cast<const void*>(k_batch_small_cluster_sums), kSmallClusterLdsBytes}};
   for (const auto& o : opt_ins)
     if (const hipError_t e = hipFuncSetAttribute(o.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(o.lds)); e != hipSuccess)
       return e;
@@ -4842,6 +4885,14 @@ void launch_small_cluster_sums(hipStream_t st, Particles p, uint64_t n, HashPara
                                double* host_mirror) {
   hipLaunchKernelGGL(k_small_cluster_sums, dim3(1), dim3(kSmallBlock), kSmallClusterLdsBytes, st, p, static_cast<uint32_t>(n), hp, d_keys, d_cluster,
                      cells, wanted, pivot_x, pivot_y, d_out, host_mirror);
+}
+void launch_batch_small_cluster_cells(hipStream_t st, const BatchClusterCells* d_items, uint32_t members) {
+  if (members == 0) return;
+  hipLaunchKernelGGL(k_batch_small_cluster_cells, dim3(members), dim3(kSmallBlock), kSmallClusterLdsBytes, st, d_items);
+}
+void launch_batch_small_cluster_sums(hipStream_t st, const BatchClusterSums* d_items, uint32_t members) {
+  if (members == 0) return;
+  hipLaunchKernelGGL(k_batch_small_cluster_sums, dim3(members), dim3(kSmallBlock), kSmallClusterLdsBytes, st, d_items);
 }
 void launch_cell_set_cluster(hipStream_t st, const CellList& cells, const unsigned int* d_cluster, uint32_t m, const CellTable& t) {
   if (m == 0) return;

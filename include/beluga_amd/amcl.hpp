@@ -1070,7 +1070,12 @@ class AmclBatch {
 
   [[nodiscard]] const std::vector<mcl_update_info>& last_infos() const { return infos_; }
   [[nodiscard]] const std::vector<mcl_status>& statuses() const { return statuses_; }
-  /// cycles, kernel_launches, members_fused, members_alone (mcl_batch_get_counter).
+  /// mcl_set_option on every member, e.g. batch_cluster_fused (default 1; 0: the member's cluster-based estimate through its own kernels
+  /// instead of the fleet's two shared launches).
+  void set_option(const std::string& name, std::int64_t value) {
+    for (Amcl& m : members_) m.check(mcl_set_option(m.ctx_, name.c_str(), value));
+  }
+  /// cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns (mcl_batch_get_counter).
   [[nodiscard]] std::uint64_t counter(const std::string& name) const {
     std::uint64_t value = 0;
     check(mcl_batch_get_counter(batch_, name.c_str(), &value));

@@ -450,7 +450,23 @@ mcl_status mcl_sample_particle_cloud(mcl_ctx* ctx, uint64_t size, uint32_t draw_
  * Counters (mcl_batch_get_counter): cycles = calls that updated at least one member; kernel_launches = kernels the shared path has
  * enqueued, a running total (3 per cycle with a fused member, however many members there are); members_fused / members_alone = running
  * totals of members that updated through the shared launches / through their ordinary cycle.  A fused member's own counters
- * (small_tail_launches, lf_beams_launches) advance as in a lone cycle. */
+ * (small_tail_launches, lf_beams_launches) advance as in a lone cycle.
+ *
+ * The cluster-based estimate (mcl_set_estimate_kind 1: what beluga_ros::Amcl::update returns) of the fused members is batched as well:
+ * behind the cycle's synchronisation, TWO shared launches of one workgroup per member - the occupied cells of every member into its own
+ * mapped list, then, behind each member's own host pass (assign_clusters), the sums of every member's winning cluster - with one
+ * synchronisation each, in place of two launches and two synchronisations per member.  A member takes them if its cycle was fused, its
+ * estimate kind is 1, its option batch_cluster_fused is on, its live set holds 1 .. 4096 particles and its cluster parameters are valid; every other member calls its own
+ * mcl_cluster_based_estimate as before.  Two rare cases run that member's own kernels behind the shared ones: no cluster of more than
+ * one particle (the overall estimate, cluster_based_estimation.hpp:424-427) and a cluster far from the pivot (a second pass of its sums,
+ * counted in the member's estimate_repivots as in a lone cycle).  A member whose cell list fails its bounds check gets MCL_ERR_HIP as its
+ * own status and the others proceed.  kernel_launches does not count these launches.  Further counters: cluster_launches = shared
+ * cluster kernels enqueued, a running total (2 per cycle in which a member took the shared cluster path, 1 if none of them had a
+ * winner, 0 if there was none); members_cluster_fused = running total of members whose estimate came through them; cluster_host_ns =
+ * host time between the two launches (every member's cells ordered and assigned, one member after the other).
+ *
+ * The switch is a member's option: mcl_set_option(member, "batch_cluster_fused", 0) sends that member through its own
+ * mcl_cluster_based_estimate (default 1; the batch has no entry point of its own for it). */
 mcl_status mcl_batch_create(const mcl_config* cfgs, uint32_t count, mcl_batch** out);
 void mcl_batch_destroy(mcl_batch* batch);
 mcl_status mcl_batch_size(const mcl_batch* batch, uint32_t* count);
@@ -668,6 +684,8 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *                   Counters order_ahead_used / order_ahead_missed.
  *   norm_store (0)  fixed-size cycle that resamples at once: 0 = the normalisation kernel does not store the normalised weights (nothing reads
  *                   them), the CDF kernel divides again; 1 = stored.  Bit-identical.
+ *   batch_cluster_fused (1)  a member of a batch that returns the cluster-based estimate: 1 = through the batch's two shared launches
+ *                   ("Batches of small filters"), 0 = through its own mcl_cluster_based_estimate.  The same bits either way.
  *   small_fused (1)  sets of up to 4096 particles: everything behind the reweight - normalise, policies, fixed-size or KLD resampling, estimate
  *                   sums - in one launch of one workgroup and one host synchronisation (and two one-workgroup kernels around the host's pass of
  *                   cluster_based_estimate); 0 = the kernels of the large path
