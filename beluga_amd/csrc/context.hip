@@ -133,7 +133,8 @@ struct mcl_ctx {
   bool beam_table_ready{false};        // d_beam_table holds the table of the current map (built lazily: do_reweight)
   double* h_points{nullptr};   // pinned, mapped
   double* hd_points{nullptr};  // the same memory as the device sees it
-  double scan_extent{0.0};     // max |x| + |y| of the uploaded scan points (NaN if any is NaN)
+  double scan_extent{0.0};     // max |x| + |y| of the staged scan points
+  uint64_t scan_no_cell{0};    // points of the scan taken out where it was staged: NaN or infinite, without a cell for any pose (FieldView::acc0)
   size_t h_points_cap{0};
   hipEvent_t points_event{nullptr};  // recorded behind the kernel that pulls h_points
   bool points_in_flight{false}, points_event_valid{false};
@@ -269,7 +270,8 @@ struct mcl_ctx {
                      d_cube.ptr, cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB ? 1 : 0,
                      pal_count ? d_pal_idx.ptr : nullptr, d_pal_val.ptr, pal_count, pal_pitch, pal_base, pal_bytes,
                      pal_count && far_tiles ? d_far_bits.ptr : nullptr, far_row_bytes, far_bytes, far_entry,
-                     pal_count && far_tiles && far_linear_bytes ? d_far_linear.ptr : nullptr, far_linear_bytes};
+                     pal_count && far_tiles && far_linear_bytes ? d_far_linear.ptr : nullptr, far_linear_bytes,
+                     lf_acc0(cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB, static_cast<float>(1. / cfg.lf.max_laser_distance), scan_no_cell)};
   }
   SortScratch sort_scratch() {
     SortScratch s{};
@@ -698,7 +700,13 @@ mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, co
 }
 
 // Stages the measurement in mapped pinned memory; a kernel of the cycle pulls it into d_points (pull_scan_args / launch_pull_scan).
-mcl_status stage_points(mcl_ctx* ctx, const Measurement& m) {
+// The likelihood-field models: a point with a NaN or infinite coordinate has no cell whatever the pose (the reference's
+// static_cast<int>(std::floor(.)) of it is undefined; as compiled it gives INT_MIN, "not in the grid": the unknown-space term).  Such
+// points are taken out here, counted (scan_no_cell -> FieldView::acc0), and *staged is left describing what was staged: the kernels' floor
+// by the low mantissa word would read cell (0, 0) for them.
+mcl_status stage_points(mcl_ctx* ctx, Measurement* staged) {
+  const Measurement m = *staged;
+  ctx->scan_no_cell = 0;
   if (m.doubles == 0) return MCL_OK;
   MCL_HIP(ctx, ctx->d_points.ensure(m.doubles));
   if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) MCL_HIP(ctx, ctx->d_beam_points.ensure(kBeamPointDoubles * (m.doubles / 2)));
@@ -721,14 +729,31 @@ mcl_status stage_points(mcl_ctx* ctx, const Measurement& m) {
     return MCL_OK;
   }
   double extent = 0.0;  // maximum of |x| + |y| over the scan; a NaN point makes it NaN (and every comparison with it false)
-  bool poisoned = false;
-  for (uint64_t i = 0; i < m.doubles; i += 2) {
+  bool poisoned = false, unbounded = false;
+  for (uint64_t i = 0; i < m.doubles; i += 2) {  // (one straight pass, as before: the common scan has nothing to take out)
     const double x = m.data[i], y = m.data[i + 1];
     ctx->h_points[i] = x;
     ctx->h_points[i + 1] = y;
     const double e = std::abs(x) + std::abs(y);
     if (e != e) poisoned = true;
+    if (e == std::numeric_limits<double>::infinity()) unbounded = true;
     extent = e > extent ? e : extent;
+  }
+  if ((poisoned || unbounded) && ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {  // (the beam model walks rays: its own rules)
+    uint64_t kept = 0;
+    extent = 0.0;
+    for (uint64_t i = 0; i < m.doubles; i += 2) {
+      const double x = m.data[i], y = m.data[i + 1];
+      if (!(std::isfinite(x) && std::isfinite(y))) continue;  // a NaN or infinite coordinate (finite ones whose sum overflows stay)
+      const double e = std::abs(x) + std::abs(y);
+      ctx->h_points[kept] = x;
+      ctx->h_points[kept + 1] = y;
+      kept += 2;
+      extent = e > extent ? e : extent;
+    }
+    poisoned = false;
+    ctx->scan_no_cell = (m.doubles - kept) / 2;
+    staged->doubles = kept;
   }
   ctx->scan_extent = poisoned ? std::numeric_limits<double>::quiet_NaN() : extent;
   return MCL_OK;
@@ -870,19 +895,19 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
 // points_staged: stage_points + the pull already happened (mcl_update); keys_ready: k_propagate emitted the ordering keys.
 // want_weight_sums: the normalisation follows at once (mcl_update): the LF patch kernel leaves the sums of its workgroups' new
 // weights in d_lf_wsum (facts.lf_sums() of them; 0 if another kernel ran).
-mcl_status do_reweight(mcl_ctx* ctx, const Measurement& m, bool points_staged = false, bool keys_ready = false,
+mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, bool keys_ready = false,
                        bool want_weight_sums = false, HeldCycle* hold = nullptr) {
   ctx->facts.lf_sums_dropped();
-  const uint64_t B = ctx->off_grid() ? 0 : m.doubles / 2;  // the grid models' measurement is the scan itself: B points
-  if (const mcl_status s = reweight_preconditions(ctx, B)) return s;
+  if (const mcl_status s = reweight_preconditions(ctx, ctx->off_grid() ? 0 : m.doubles / 2)) return s;
   const bool unit_weights = ctx->facts.take_unit_weights() && ctx->tuning.lf_unit_weights != 0;
   if (!points_staged) {
-    if (const mcl_status s = stage_points(ctx, m)) return s;
+    if (const mcl_status s = stage_points(ctx, &m)) return s;
     if (m.doubles) {
       launch_pull_scan(ctx->stream, ctx->hd_points, ctx->d_points.ptr, static_cast<uint32_t>(m.doubles));
       points_pulled(ctx, true);
     }
   }
+  const uint64_t B = ctx->off_grid() ? 0 : m.doubles / 2;  // the grid models' measurement is the scan itself: B points (as staged)
   stage_begin(ctx, MCL_STAGE_REWEIGHT);
   const LfPlanner::Mode mode = plan_lf(ctx);
   const bool ordered = ctx->wants_ordering();  // (asked while this cycle's mode is decided)
@@ -1913,7 +1938,7 @@ mcl_status sharded_preconditions(mcl_ctx* ctx) {
 // beluga::Amcl::update (amcl_core.hpp:165-201) over the sharded set; same statements as mcl_update, with the exchanges of
 // include/beluga_mcl.h ("Particle shards") between them.  Every rank takes the same decisions: they depend on the control
 // action (identical inputs) and on gathered sums (identical values, added in rank order everywhere).
-mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const Measurement& scan, mcl_estimate* estimate, mcl_update_info* info) {
+mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, Measurement scan, mcl_estimate* estimate, mcl_update_info* info) {
   const mcl_amcl_params& ap = ctx->cfg.amcl;
   const uint32_t world = ctx->comm_world, rank = ctx->comm_rank;
   const bool adaptive = ap.min_particles < ap.max_particles;
@@ -1938,7 +1963,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, const Measurement& sc
   }
   const uint64_t n_total = ctx->global_n ? ctx->global_n : ap.max_particles;  // particles over all shards before this cycle's resampling
   if (n_total == 0) return MCL_OK;
-  if (const mcl_status s = stage_points(ctx, scan)) return s;
+  if (const mcl_status s = stage_points(ctx, &scan)) return s;
   advance_window(ctx, pose);
   double* d = ctx->d_comm_f64.ptr;
   const CommAreas gathered = comm_areas(ctx);
@@ -2810,7 +2835,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
     return sharded_update(ctx, pose, m, estimate, info);
   }
   if (ctx->is_ndt()) m = ndt_fit_scan(ctx, m.data, m.doubles / 2);  // the scan's measurement cells are what the cycle uploads
-  if (const mcl_status s = stage_points(ctx, m)) return s;
+  if (const mcl_status s = stage_points(ctx, &m)) return s;
   consume_motion();
   advance_window(ctx, pose);
 

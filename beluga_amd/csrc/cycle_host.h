@@ -43,7 +43,7 @@ class CloudEstimate {
 struct KeyFrameInputs {
   bool patch_useful;    // LfPlanner::patch_useful(): a set reported as dispersed takes +- 2 sigma and bins of equal width
   double resolution;    // of the map (0: none)
-  double scan_extent;   // max |x| + |y| of the uploaded scan points (NaN if any is NaN)
+  double scan_extent;   // max |x| + |y| of the staged scan points (NaN if the beam model's scan holds a NaN)
   int key_warp, key_bits_xy;  // Tuning
 };
 // The frame of the ordering keys for the set as it will be AFTER this propagation: the last estimate moved by the mean motion, spans
@@ -161,6 +161,17 @@ struct ExponentialFilter {
 bool moved_enough(const Pose2& latest, const Pose2& pose, double min_d, double min_a);
 // every_n (every_n.hpp:47-50, :181): the counter as this cycle leaves it; the policy fires where it is 0.
 inline uint64_t next_every_n(uint64_t current, uint64_t interval) { return (current + 1) % interval; }
+
+// Where a particle's sum over the scan starts in the likelihood-field kernels (FieldView::acc0): the model's own start - 1
+// (likelihood_field_model.hpp:76) or 0 (the prob model's sum of logs, likelihood_field_prob_model.hpp:77) - plus the terms of the
+// `no_cell` scan points taken out where the scan was staged (NaN or infinite: outside every grid for every pose), each the
+// unknown-space term pz^3 or log(pz) of pz = double(unknown_value) (likelihood_field_model.hpp:75,84-88).  Exactly the model's start
+// for a scan without such points.
+inline double lf_acc0(bool prob, float unknown_value, uint64_t no_cell) {
+  const double pz = static_cast<double>(unknown_value);
+  if (no_cell == 0) return prob ? 0.0 : 1.0;
+  return prob ? static_cast<double>(no_cell) * std::log(pz) : 1.0 + static_cast<double>(no_cell) * (pz * pz * pz);
+}
 // The resampling decision on the host from the totals of the normalised weights of n particles: :179 ThrunRecoveryProbabilityEstimator
 // (thrun_recovery_probability_estimator.hpp:69-89), :181 every_n's verdict `fires` [&& on_effective_size_drop] (on_effective_size_drop.hpp:45-49,
 // effective_sample_size.hpp:46-59).  The filters' reset (:184-186) is the caller's.

@@ -60,6 +60,10 @@ struct FieldView {
   // index >> 3 - the test then starts from the offset a look-up has computed anyway (k_reweight_lf_far_beams).  nullptr = none.
   const uint8_t* far_linear;
   uint32_t far_linear_bytes;  // a multiple of 16
+  // Where a particle's sum over the scan starts: 1 (likelihood_field_model.hpp:76) or 0 (the prob model's sum of logs), plus the terms
+  // of the scan points that have no cell for ANY pose - NaN or infinite coordinates, taken out where the scan is staged
+  // (stage_points): their count times the unknown-space term.  No kernel ever sees such a point.
+  double acc0;
 };
 
 constexpr uint32_t kMaxPalette = 2048;

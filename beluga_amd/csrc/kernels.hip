@@ -391,7 +391,7 @@ __device__ __forceinline__ double lf_cube_fetch(__amdgpu_buffer_rsrc_t rsrc, con
 // per lane, once per kernel (the ordering passes move 8 bytes per particle, not the poses).
 __device__ __forceinline__ Pose2 ordered_pose(const Pose2& to_frame, const double4* __restrict__ pose, uint64_t i) {
   const double4 q = pose[i];
-  return pose_mul(to_frame, Pose2{Rot2{q.x, q.y}, q.z, q.w});
+  return pose_mul_ieee(to_frame, Pose2{Rot2{q.x, q.y}, q.z, q.w});  // (the host's bits: the product's last bit decides cells)
 }
 
 template <bool kCube>
@@ -406,7 +406,7 @@ __global__ __launch_bounds__(kBlock) void k_reweight_lf_sorted(double* __restric
   const double ct = T.r.c, st = T.r.s, xt = T.x, yt = T.y;
   const uint32_t b_begin = partial ? blockIdx.y * beams_per_segment : 0u;
   const uint32_t b_end = partial ? (b_begin + beams_per_segment < B ? b_begin + beams_per_segment : B) : B;
-  double acc = (f.prob || partial) ? 0.0 : 1.0;
+  double acc = partial ? 0.0 : f.acc0;
   if (kCube) {
     const uint32_t cells = f.W * f.H;
     const __amdgpu_buffer_rsrc_t rsrc =
@@ -567,7 +567,7 @@ __global__ __launch_bounds__(kPalBlock) void k_reweight_lf_palette(double* __res
   const double ct = T.r.c, st = T.r.s, xt = T.x, yt = T.y;
   const uint32_t b_begin = partial ? blockIdx.y * beams_per_segment : 0u;
   const uint32_t b_end = partial ? (b_begin + beams_per_segment < B ? b_begin + beams_per_segment : B) : B;
-  double acc = (f.prob || partial) ? 0.0 : 1.0;
+  double acc = partial ? 0.0 : f.acc0;
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(f.pal_idx), 0, static_cast<int>(f.pal_bytes), 0x00020000);
   // Software-pipelined over groups of 8 beams, two groups (A, B) in flight alternately: the index gathers of one group
@@ -732,7 +732,7 @@ __device__ __forceinline__ void reweight_lf_beams_block(uint32_t block, const Pa
   const uint64_t i = base + lane;
   Pose2 state = pose_identity();
   if (lane < cnt) state = load_pose(p, i);
-  const Pose2 T = pose_mul(f.world_to_field, state);  // likelihood_field_model.hpp:70
+  const Pose2 T = pose_mul_ieee(f.world_to_field, state);  // likelihood_field_model.hpp:70
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(f.pal_idx), 0, static_cast<int>(f.pal_bytes), 0x00020000);
   const uint32_t full = B & ~255u;  // beams taken four per lane at a time (their gathers in flight together)
@@ -767,7 +767,7 @@ __device__ __forceinline__ void reweight_lf_beams_block(uint32_t block, const Pa
     const double total = wave_sum_f64(acc);
     if (lane == q) mine = total;
   }
-  if (lane < cnt) p.w[i] = p.w[i] * (f.prob ? exp(mine) : 1.0 + mine);
+  if (lane < cnt) p.w[i] = p.w[i] * (f.prob ? exp(f.acc0 + mine) : f.acc0 + mine);
 }
 __global__ __launch_bounds__(kBeamsBlock) void k_reweight_lf_beams(Particles p, uint64_t n, FieldView f, const double2* __restrict__ pts,
                                                                    uint32_t B, uint32_t per_wave /* particles of a wave: 1 .. 64 */) {
@@ -960,7 +960,7 @@ __global__ __launch_bounds__(kFarBeamsBlock) __attribute__((amdgpu_waves_per_eu(
         if (lane == q0 + j) mine = total;
       }
     }
-    if (lane < m) w[i] = (unit_weights != 0u ? 1.0 : w[i]) * (kProb ? exp(mine) : 1.0 + mine);
+    if (lane < m) w[i] = (unit_weights != 0u ? 1.0 : w[i]) * (kProb ? exp(f.acc0 + mine) : f.acc0 + mine);
   }
 }
 
@@ -1464,7 +1464,7 @@ __global__ __launch_bounds__(kPatchBlock) __attribute__((amdgpu_waves_per_eu(6, 
     return;
   }
 
-  double acc = (f.prob || partial) ? 0.0 : 1.0;
+  double acc = partial ? 0.0 : f.acc0;
   // A wave that holds a far particle goes through the exact evaluation group by group - by the main loop's own means: its end-point
   // constants are replaced by ones that put every end-point ON a cell boundary (the guard word comes out zero), so that every group is
   // marked for add_exact; what its look-ups read meanwhile (cell 0 of whatever patch, an address that may lie outside LDS: zero) is dropped.
@@ -1680,11 +1680,12 @@ __global__ __launch_bounds__(kPatchBlock) __attribute__((amdgpu_waves_per_eu(6, 
 }
 
 __global__ __launch_bounds__(kBlock) void k_lf_combine(double* __restrict__ w, uint64_t n, const uint32_t* __restrict__ perm,
-                                                       const double* __restrict__ partial, uint32_t segments, int mode) {
-  // mode 0: w *= 1 + sum (likelihood field), 1: w *= exp(sum) (its log form), 2: w *= sum (beam model)
+                                                       const double* __restrict__ partial, uint32_t segments, int mode, double acc0) {
+  // mode 0: w *= 1 + sum (likelihood field), 1: w *= exp(sum) (its log form), 2: w *= sum (beam model); acc0: where the sum starts
+  // (1, 0, 0; the likelihood-field models': FieldView::acc0)
   const uint64_t t = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (t >= n) return;
-  double acc = mode == 0 ? 1.0 : 0.0;
+  double acc = acc0;
   for (uint32_t s = 0; s < segments; ++s) acc += partial[static_cast<size_t>(s) * n + t];
   const uint32_t i = perm[t];
   w[i] = w[i] * (mode == 1 ? exp(acc) : acc);
@@ -4497,7 +4498,7 @@ LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tunin
       launched.kernel = LfKernel::kSortedField;
     }
     if (segments > 1)
-      hipLaunchKernelGGL(k_lf_combine, dim3(blocks_for(n)), dim3(kBlock), 0, st, p.w, n, sort->perm, partial, segments, f.prob);
+      hipLaunchKernelGGL(k_lf_combine, dim3(blocks_for(n)), dim3(kBlock), 0, st, p.w, n, sort->perm, partial, segments, f.prob, f.acc0);
   } else if (lf_takes_beams(a, tuning)) {
     // lanes over the beams (a dispersed set the cycle sent here, or a set below the ordered kernels' threshold);
     // particles per wave: enough waves to fill the chip (4096) before a wave takes a second particle
@@ -4529,7 +4530,7 @@ extern "C" int mcl_measurement_build(void) {
 }
 namespace mcl {
 void launch_lf_combine(hipStream_t st, double* w, uint64_t n, const uint32_t* perm, const double* partial, uint32_t segments, int mode) {
-  hipLaunchKernelGGL(k_lf_combine, dim3(blocks_for(n)), dim3(kBlock), 0, st, w, n, perm, partial, segments, mode);
+  hipLaunchKernelGGL(k_lf_combine, dim3(blocks_for(n)), dim3(kBlock), 0, st, w, n, perm, partial, segments, mode, mode == 0 ? 1.0 : 0.0);
 }
 
 void launch_weight_sum(hipStream_t st, const double* w, uint64_t n, double* d_partials, double* d_out, double* host_mirror) {

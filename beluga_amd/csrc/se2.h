@@ -26,6 +26,37 @@ struct Pose2 {
   double x, y;
 };
 
+// hypot for the device (pose_mul_ieee below), bit for bit the host library's on normal-range arguments: a square root corrected by its own rounding error
+// (C. F. Borges, "An Improved Algorithm for hypot(a, b)", 2019, the variant without fused operations - the one the reference's host
+// library evaluates), in IEEE operations alone, each rounded on its own.  The device library's hypot is accurate to an ulp but not the
+// same function: one pose in a few had a world -> field rotation one ulp off the reference's, which moves every end-point of that pose by
+// an ulp and with it the cell of any end-point that close to a cell boundary (tests/test_gpu_lf_edges.py, family ulp_straddle).
+// Held to std::hypot by tests/test_lf_reference_cpu.py.  "The host library" is the C library the oracle and numpy run on (glibc 2.35 and
+// later evaluate exactly this sequence); on a host whose hypot is another function that test fails and says so - the kernels then
+// agree with THIS sequence, and the oracle and tests/lf_reference.py would have to normalise with it too to stay the yardstick.
+MCL_HD double hypot_ieee(double x, double y) {
+  double ax = fabs(x), ay = fabs(y);
+  if (ax < ay) {
+    const double t = ax;
+    ax = ay;
+    ay = t;
+  }
+  if (!(ax < 0x1p+500 && ay > 0x1p-500)) return hypot(x, y);  // zeros, infinities, NaN, scales a rotation never has
+  if (ay <= ax * 0x1p-54) return ax + ay;
+  const double h = sqrt(ax * ax + ay * ay);
+  double t1, t2;
+  if (h <= 2.0 * ay) {
+    const double d = h - ay;
+    t1 = ax * (2.0 * d - ax);
+    t2 = (d - 2.0 * (ax - ay)) * d;
+  } else {
+    const double d = h - ax;
+    t1 = 2.0 * d * (ax - 2.0 * ay);
+    t2 = (4.0 * d - ay) * ay + d * d;
+  }
+  return h - (t1 + t2) / (2.0 * h);
+}
+
 // SO2(real, imag): store then normalize() (hypot).
 MCL_HD Rot2 rot_from_complex(double re, double im) {
   const double len = hypot(re, im);
@@ -53,6 +84,27 @@ MCL_HD void rot_apply(const Rot2& r, double px, double py, double& ox, double& o
 MCL_HD Pose2 pose_mul(const Pose2& a, const Pose2& b) {
   Pose2 o;
   o.r = rot_mul(a.r, b.r);
+  double tx, ty;
+  rot_apply(a.r, b.x, b.y, tx, ty);
+  o.x = a.x + tx;
+  o.y = a.y + ty;
+  return o;
+}
+// pose_mul with the rotation normalised by hypot_ieee: on the device the same bits as the host's pose_mul.  For the ONE product whose last
+// bit decides a map cell - world -> field times the particle's pose in the likelihood-field kernels, once per particle and launch; every
+// other rotation on the device keeps the device library's hypot (an ulp is within every other stage's tolerance).
+MCL_HD Pose2 pose_mul_ieee(const Pose2& a, const Pose2& b) {
+  double re = a.r.c * b.r.c - a.r.s * b.r.s;
+  double im = a.r.c * b.r.s + a.r.s * b.r.c;
+  const double n2 = re * re + im * im;
+  if (n2 != 1.0) {
+    const double scale = 2.0 / (1.0 + n2);
+    re = re * scale;
+    im = im * scale;
+  }
+  const double len = hypot_ieee(re, im);
+  Pose2 o;
+  o.r = Rot2{re / len, im / len};
   double tx, ty;
   rot_apply(a.r, b.x, b.y, tx, ty);
   o.x = a.x + tx;

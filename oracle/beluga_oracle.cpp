@@ -324,6 +324,19 @@ struct ScanPoint {  // std::pair<double, double> of the reference's measurement_
 };
 static_assert(sizeof(ScanPoint) == 2 * sizeof(double), "ScanPoint must be two packed doubles");
 
+// sensor/likelihood_field_model.hpp:82-85 (regular_grid.hpp:75-78: cell_near = floor(p / resolution) cast to int) - the cell of ONE
+// end-point, each product and sum rounded on its own (-ffp-contract=off).  The cast of a value that has no int (NaN, +-inf,
+// |floor| >= 2^31) is undefined in C++; what this compiler makes of it is recorded by tests/test_lf_reference_cpu.py, and the rule
+// the project holds itself to is written out in tests/lf_reference.py.
+inline void lf_cell(
+    const ScanPoint& point, double cos_theta, double sin_theta, double x_offset, double y_offset, double inv_resolution, int* xi,
+    int* yi) {
+  const double x = point.first * cos_theta - point.second * sin_theta + x_offset;
+  const double y = point.first * sin_theta + point.second * cos_theta + y_offset;
+  *xi = static_cast<int>(std::floor(x * inv_resolution));
+  *yi = static_cast<int>(std::floor(y * inv_resolution));
+}
+
 // sensor/likelihood_field_model.hpp:68-91 — ONE particle.
 inline double lf_weight(
     const float* field, int W, int H, double res, const SE2& world_to_field, double max_laser_distance, const SE2& state,
@@ -338,10 +351,8 @@ inline double lf_weight(
   // libstdc++: blocks of four, (f0 + f1) + (f2 + f3), added to the running sum, the rest one by one.
   const ScanPoint* points = reinterpret_cast<const ScanPoint*>(pts);
   return std::transform_reduce(points, points + B, 1.0, std::plus<>{}, [&](const ScanPoint& point) {
-    const double x = point.first * cos_theta - point.second * sin_theta + x_offset;
-    const double y = point.first * sin_theta + point.second * cos_theta + y_offset;
-    const int xi = static_cast<int>(std::floor(x * inv_resolution));
-    const int yi = static_cast<int>(std::floor(y * inv_resolution));
+    int xi, yi;
+    lf_cell(point, cos_theta, sin_theta, x_offset, y_offset, inv_resolution, &xi, &yi);
     float v = unknown_space_occupancy_prob;
     if (xi >= 0 && yi >= 0 && xi < W && yi < H) v = field[static_cast<size_t>(yi) * W + static_cast<size_t>(xi)];
     const double pz = static_cast<double>(v);
@@ -360,10 +371,8 @@ inline double lf_prob_weight(
   const double inv_resolution = 1. / res;
   const ScanPoint* points = reinterpret_cast<const ScanPoint*>(pts);  // std::transform_reduce as in lf_weight (:77)
   return std::exp(std::transform_reduce(points, points + B, 0.0, std::plus<>{}, [&](const ScanPoint& point) {
-    const double x = point.first * cos_theta - point.second * sin_theta + x_offset;
-    const double y = point.first * sin_theta + point.second * cos_theta + y_offset;
-    const int xi = static_cast<int>(std::floor(x * inv_resolution));
-    const int yi = static_cast<int>(std::floor(y * inv_resolution));
+    int xi, yi;
+    lf_cell(point, cos_theta, sin_theta, x_offset, y_offset, inv_resolution, &xi, &yi);
     float v = unknown_space_occupancy_prob;
     if (xi >= 0 && yi >= 0 && xi < W && yi < H) v = field[static_cast<size_t>(yi) * W + static_cast<size_t>(xi)];
     return std::log(static_cast<double>(v));
@@ -1126,6 +1135,25 @@ void orc_lf_prob_weights(
     uint64_t n, const double* pts, uint64_t B, double* out) {
   const SE2 w2f = se2_inverse(se2_load(origin));
   for (uint64_t i = 0; i < n; ++i) out[i] = lf_prob_weight(field, W, H, res, w2f, max_laser_distance, se2_load(states + 4 * i), pts, B);
+}
+
+// The cells lf_weight and lf_prob_weight look up: xi, yi [n][B] as the compiled cast leaves them, inside [n][B] the containment test.
+void orc_lf_cells(
+    int W, int H, double res, const double origin[4], const double* states, uint64_t n, const double* pts, uint64_t B, int32_t* xi,
+    int32_t* yi, uint8_t* inside) {
+  const SE2 w2f = se2_inverse(se2_load(origin));
+  const double inv_resolution = 1. / res;
+  const ScanPoint* points = reinterpret_cast<const ScanPoint*>(pts);
+  for (uint64_t i = 0; i < n; ++i) {
+    const SE2 transform = se2_mul(w2f, se2_load(states + 4 * i));
+    for (uint64_t b = 0; b < B; ++b) {
+      int x, y;
+      lf_cell(points[b], transform.r.c, transform.r.s, transform.x, transform.y, inv_resolution, &x, &y);
+      xi[i * B + b] = x;
+      yi[i * B + b] = y;
+      inside[i * B + b] = (x >= 0 && y >= 0 && x < W && y < H) ? 1 : 0;
+    }
+  }
 }
 
 // kind 1 = omnidirectional (alphas[5]), kind 2 = stationary (control ignored)

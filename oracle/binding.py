@@ -227,6 +227,20 @@ def lf_prob_weights(field, res, origin, max_laser_distance, states, points):
     return out
 
 
+def lf_cells(shape, res, origin, states, points):
+    """The cells lf_weights looks up: (xi[n, B], yi[n, B], inside[n, B]) for a field of shape (H, W)."""
+    H, W = shape
+    states = _dbl(states).reshape(-1, 4)
+    points = _dbl(points).reshape(-1, 2)
+    origin = _dbl(origin)
+    n, B = len(states), len(points)
+    xi, yi = np.zeros((n, B), dtype=np.int32), np.zeros((n, B), dtype=np.int32)
+    inside = np.zeros((n, B), dtype=np.uint8)
+    lib().orc_lf_cells(C.c_int(W), C.c_int(H), C.c_double(res), _d(origin), _d(states), C.c_uint64(n), _d(points), C.c_uint64(B),
+                       xi.ctypes.data_as(c_i32_p), yi.ctypes.data_as(c_i32_p), inside.ctypes.data_as(c_u8_p))
+    return xi, yi, inside.astype(bool)
+
+
 MOTION_KINDS = {"differential": 0, "omnidirectional": 1, "stationary": 2}
 
 

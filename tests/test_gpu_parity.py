@@ -8,6 +8,8 @@ Tolerances (stated once, used below):
     prefix sums round differently from std::partial_sum) — such flips are counted and bounded.  What the CDF
     itself is held to (its error against a high-precision prefix sum, its order, zero weights) and the searches
     on targets chosen at its steps: test_gpu_resample_edges.py.
+What the likelihood-field kernels' CELL DECISION is held to (end-points engineered onto cell boundaries, the fast path's trigger, the
+grid's borders, scan points without a cell; weights within (B + 4) 2^-53 of an exact sum): test_gpu_lf_edges.py.
 """
 import math
 import os
