@@ -293,6 +293,63 @@ def _dp(a: np.ndarray):
     return a.ctypes.data_as(capi.c_double_p)
 
 
+class SharedMap:
+    """One map on the device for any number of filters (mcl_shared_map_*): built once, for the device and the sensor model given -
+    which every filter that uses it must share (the likelihood-field models: the same model and equal parameters) - and never
+    changed.  Amcl.use_map attaches a filter to it.  close() gives up this object's reference only: the map lives until the last
+    filter that uses it has left it.  field_build = 1: the field by the device's exact distance transform."""
+
+    def __init__(self, grid: OccupancyGrid, sensor, *, device: int = 0, field_build: int = 0):
+        self._lib = capi.load()
+        self._map = None
+        cfg = capi.Config()
+        self._lib.mcl_default_config(C.byref(cfg))
+        cfg.device_id = device
+        if isinstance(sensor, LikelihoodFieldModelParam):
+            cfg.sensor_kind = (capi.MCL_SENSOR_LIKELIHOOD_FIELD_PROB if isinstance(sensor, LikelihoodFieldProbModelParam)
+                               else capi.MCL_SENSOR_LIKELIHOOD_FIELD)
+            for k in ("max_obstacle_distance", "max_laser_distance", "z_hit", "z_random", "sigma_hit"):
+                setattr(cfg.lf, k, getattr(sensor, k))
+            cfg.lf.model_unknown_space = int(sensor.model_unknown_space)
+            cfg.lf.only_obstacle_boundaries = int(sensor.only_obstacle_boundaries)
+        elif isinstance(sensor, BeamModelParam):
+            cfg.sensor_kind = capi.MCL_SENSOR_BEAM
+        else:
+            raise ValueError("SharedMap: sensor must be LikelihoodFieldModelParam, LikelihoodFieldProbModelParam or BeamModelParam")
+        cells = np.ascontiguousarray(grid.cells, dtype=np.int8)
+        H, W = cells.shape
+        origin = np.ascontiguousarray(grid.origin, dtype=np.float64)
+        traits = (C.c_int8 * 3)(*grid.value_traits)
+        handle = capi._shared_map()
+        st = self._lib.mcl_shared_map_create(C.byref(cfg), cells.ctypes.data_as(capi.c_i8_p), W, H, float(grid.resolution), _dp(origin),
+                                             traits, int(field_build), C.byref(handle))
+        if st != capi.MCL_OK:
+            raise capi.MclError(st, self._lib.mcl_shared_map_last_error(None).decode())
+        self._map = handle
+        self.shape = (H, W)
+
+    def info(self) -> dict:
+        """width, height, resolution, sensor_kind, device_id, device_bytes, host_bytes, users (filters attached now)."""
+        if not self._map:
+            raise ValueError("SharedMap: closed")
+        out = capi.SharedMapInfo()
+        st = self._lib.mcl_shared_map_get_info(self._map, C.byref(out))
+        if st != capi.MCL_OK:
+            raise capi.MclError(st, "mcl_shared_map_get_info")
+        return {name: getattr(out, name) for name, _ in capi.SharedMapInfo._fields_}
+
+    def close(self):
+        if getattr(self, "_map", None):
+            self._lib.mcl_shared_map_release(self._map)
+            self._map = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Amcl:
     def __init__(self, grid: OccupancyGrid, motion, sensor, params: AmclParams = AmclParams(), *,
                  seed: int = 0, device: int = 0, shard_offset: int = 0, shard_capacity: int = 0, hip_stream: int = 0,
@@ -437,6 +494,16 @@ class Amcl:
         self._check(self._lib.mcl_set_map(self._ctx, cells.ctypes.data_as(capi.c_i8_p), W, H, float(grid.resolution), _dp(origin),
                                           traits))
         self._shape = (H, W)
+        self._pending_shape = None  # (a map given now replaces one that was still on its way)
+
+    def use_map(self, shared: SharedMap):
+        """update_map with a map that other filters read as well (mcl_use_shared_map): nothing is built or uploaded, and the filter's
+        results are those of update_map with the same grid, bit for bit.  Raises MclError, and leaves the filter as it was, if the map
+        was built for another device or sensor model."""
+        if not shared._map:
+            raise ValueError("SharedMap: closed")
+        self._check(self._lib.mcl_use_shared_map(self._ctx, shared._map))
+        self._shape = shared.shape
         self._pending_shape = None  # (a map given now replaces one that was still on its way)
 
     def build_ndt_map(self, source, resolution: float):

@@ -132,8 +132,14 @@ class DeviceView(C.Structure):
     ]
 
 
+class SharedMapInfo(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("resolution", C.c_double), ("sensor_kind", C.c_int32),
+                ("device_id", C.c_int32), ("device_bytes", C.c_uint64), ("host_bytes", C.c_uint64), ("users", C.c_uint32)]
+
+
 _ctx = C.c_void_p
 _batch = C.c_void_p
+_shared_map = C.c_void_p
 
 _SIGNATURES = {
     "mcl_default_config": (None, [C.POINTER(Config)]),
@@ -221,6 +227,12 @@ _SIGNATURES = {
     "mcl_batch_update": (C.c_int32, [_batch, c_double_p, c_double_p, c_u64_p, C.POINTER(Estimate), C.POINTER(UpdateInfo), C.POINTER(C.c_int32)]),
     "mcl_batch_get_counter": (C.c_int32, [_batch, C.c_char_p, c_u64_p]),
     "mcl_batch_last_error": (C.c_char_p, [_batch]),
+    "mcl_shared_map_create": (C.c_int32, [C.POINTER(Config), c_i8_p, C.c_uint32, C.c_uint32, C.c_double, c_double_p, c_i8_p, C.c_int32,
+                                          C.POINTER(_shared_map)]),
+    "mcl_shared_map_release": (None, [_shared_map]),
+    "mcl_shared_map_get_info": (C.c_int32, [_shared_map, C.POINTER(SharedMapInfo)]),
+    "mcl_shared_map_last_error": (C.c_char_p, [_shared_map]),
+    "mcl_use_shared_map": (C.c_int32, [_ctx, _shared_map]),
     "mcl_version": (C.c_char_p, []),
     "mcl_measurement_build": (C.c_int, []),
 }

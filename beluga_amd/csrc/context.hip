@@ -30,6 +30,7 @@
 #include "kernels.h"
 #include "landmark_host.h"
 #include "map_build.h"
+#include "map_store.h"
 #include "ndt_host.h"
 #include "set_facts.h"
 
@@ -38,26 +39,6 @@ namespace {
 using namespace mcl;
 
 thread_local std::string g_create_error;
-
-template <class T>
-struct DeviceBuffer {
-  T* ptr{nullptr};
-  size_t count{0};
-  hipError_t ensure(size_t n) {
-    if (n <= count) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    count = 0;
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T));
-    if (e == hipSuccess) count = n;
-    return e;
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    count = 0;
-  }
-};
 
 struct ParticleSet {
   DeviceBuffer<double4> pose;
@@ -92,30 +73,10 @@ struct mcl_ctx {
 
   // map
   bool have_map{false};
-  uint32_t W{0}, H{0};
-  double resolution{0};
-  Pose2 origin{}, origin_inverse{};
-  OccupancyTraits traits{0, -1, 100};
-  DeviceBuffer<float> d_field;
-  DeviceBuffer<double> d_cube;  // pz^3 table of the field (+1 slot for out-of-grid beams)
-  // palette form of the same table (FieldView::pal_*), built when the field has <= kMaxPalette distinct values
-  DeviceBuffer<uint16_t> d_pal_idx;
-  DeviceBuffer<double> d_pal_val;
-  DeviceBuffer<uint32_t> d_pal_keys;
-  uint32_t pal_count{0}, pal_pitch{0}, pal_base{0}, pal_bytes{0};
-  DeviceBuffer<uint8_t> d_far_bits;   // FieldView::far_bits: tiles of d_pal_idx uniformly equal to the table's most common entry
-  DeviceBuffer<uint32_t> d_far_votes;
-  uint32_t far_row_bytes{0}, far_bytes{0}, far_entry{0};
-  DeviceBuffer<uint8_t> d_far_linear;  // FieldView::far_linear: the same bits by the tiles' linear index
-  uint32_t far_linear_bytes{0};
-  uint64_t far_tiles{0};  // number of set bits' worth of tiles voted for far_entry (0 = no bitmap)
-  DeviceBuffer<int8_t> d_cells;
-  DeviceBuffer<uint32_t> d_nonfree_bits;  // beam model: 1 bit per cell
-  DeviceBuffer<uint32_t> d_free;
-  uint64_t n_free{0};
-  std::vector<float> h_field;
+  // What the context reads its occupancy-grid map through (map_store.h): a private store (mcl_set_map) or a shared one
+  // (mcl_use_shared_map).  Never empty: a store of no cells stands for "no map".
+  MapHold<MapStore> map{std::make_shared<MapStore>()};
   DeviceBuffer<uint32_t> d_field_scratch;  // device field build: uint16 column distances + int16 offsets per cell
-  bool field_built_on_device{false};
   uint64_t comm_bytes_out{0};   // bytes this rank has handed to the transport (all-gather contributions + all-to-all sends), cumulative
   uint64_t comm_collectives{0}; // collectives called, cumulative
   uint64_t comm_host_syncs{0};  // host synchronisations inside sharded update cycles, cumulative
@@ -123,7 +84,6 @@ struct mcl_ctx {
   uint64_t comm_ranks_seen{0};  // ranks the communicator reports (ncclCommCount), or the attached world size
   int comm_backend{0};          // 0 none, 1 caller's transport, 2 RCCL inside the library
   uint64_t cluster_cells{0};  // occupied cells of the last cluster_based_estimate on this context (before the merge over shards)
-  double field_build_ms{0.0};
 
   // scan: staged in mapped pinned host memory and pulled into d_points by a kernel of the cycle (no copy-engine hand-off)
   DeviceBuffer<double> d_points;
@@ -266,11 +226,12 @@ struct mcl_ctx {
   Particles other() const { return sets[live ^ 1].view(); }
   double* chunk_row(int k) { return d_chunk.ptr + static_cast<size_t>(k) * chunk_stride; }
   FieldView field_view() const {
-    return FieldView{d_field.ptr, W, H, 1. / resolution, origin_inverse, static_cast<float>(1. / cfg.lf.max_laser_distance),
-                     d_cube.ptr, cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB ? 1 : 0,
-                     pal_count ? d_pal_idx.ptr : nullptr, d_pal_val.ptr, pal_count, pal_pitch, pal_base, pal_bytes,
-                     pal_count && far_tiles ? d_far_bits.ptr : nullptr, far_row_bytes, far_bytes, far_entry,
-                     pal_count && far_tiles && far_linear_bytes ? d_far_linear.ptr : nullptr, far_linear_bytes,
+    const MapStore& m = *map;
+    return FieldView{m.d_field.ptr, m.W, m.H, 1. / m.resolution, m.origin_inverse, static_cast<float>(1. / cfg.lf.max_laser_distance),
+                     m.d_cube.ptr, cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB ? 1 : 0,
+                     m.pal_count ? m.d_pal_idx.ptr : nullptr, m.d_pal_val.ptr, m.pal_count, m.pal_pitch, m.pal_base, m.pal_bytes,
+                     m.pal_count && m.far_tiles ? m.d_far_bits.ptr : nullptr, m.far_row_bytes, m.far_bytes, m.far_entry,
+                     m.pal_count && m.far_tiles && m.far_linear_bytes ? m.d_far_linear.ptr : nullptr, m.far_linear_bytes,
                      lf_acc0(cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB, static_cast<float>(1. / cfg.lf.max_laser_distance), scan_no_cell)};
   }
   SortScratch sort_scratch() {
@@ -286,7 +247,7 @@ struct mcl_ctx {
     s.partial = s.bbox + 8 + 6 * nblocks;
     return s;
   }
-  GridView grid_view() const { return GridView{d_cells.ptr, W, H, resolution, origin, origin_inverse, traits.free_value}; }
+  GridView grid_view() const { return GridView{map->d_cells.ptr, map->W, map->H, map->resolution, map->origin, map->origin_inverse, map->traits.free_value}; }
 
   // NDT sensor model (MCL_SENSOR_NDT).  `have_map` above is the occupancy grid's (likelihood-field and beam models); an NDT context has
   // none and keeps its own state: the map of mcl_set_ndt_map (NdtMapView: index grid + cell records), and the random-state source of
@@ -319,14 +280,14 @@ struct mcl_ctx {
   bool off_grid() const { return is_ndt() || is_landmark(); }
   // What random_intersperse's random states are drawn from (random_free_state).
   FreeCells random_source() const {
-    return is_ndt() ? ndt_random : is_landmark() ? landmark_random : FreeCells{d_free.ptr, have_map ? n_free : 0};
+    return is_ndt() ? ndt_random : is_landmark() ? landmark_random : FreeCells{map->d_free.ptr, have_map ? map->n_free : 0};
   }
   // What the planner and the key frame read of the context (cycle_host.h).
-  LfSite lf_site() const { return LfSite{cfg.sensor_kind, n, pal_count != 0, far_tiles != 0, resolution, tuning}; }
+  LfSite lf_site() const { return LfSite{cfg.sensor_kind, n, map->pal_count != 0, map->far_tiles != 0, map->resolution, tuning}; }
   uint32_t key_layout() const { return lf_planner.key_layout(lf_site()); }
   bool wants_ordering() const { return lf_planner.wants_ordering(lf_site()); }
   bool predict_key_frame(const DiffDriveSampler* motion, KeyFrame* out, int moves = 1) const {
-    const KeyFrameInputs in{lf_planner.patch_useful(), resolution, scan_extent, tuning.key_warp, tuning.key_bits_xy};
+    const KeyFrameInputs in{lf_planner.patch_useful(), map->resolution, scan_extent, tuning.key_warp, tuning.key_bits_xy};
     return mcl::predict_key_frame(cloud, motion, moves, key_layout(), in, out);
   }
 };
@@ -509,20 +470,32 @@ mcl_status kld_process(mcl_ctx* ctx, uint64_t cnt, uint64_t* first_fail) {
   return MCL_OK;
 }
 
-mcl_status rebuild_cube(mcl_ctx* ctx, const float* h_field) {
-  const uint64_t cells = static_cast<uint64_t>(ctx->W) * ctx->H;
-  const float unknown_value = static_cast<float>(1. / ctx->cfg.lf.max_laser_distance);
-  const int prob = ctx->cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB ? 1 : 0;
-  MCL_HIP(ctx, ctx->d_cube.ensure(cells + 1));
-  launch_cube_table(ctx->stream, ctx->d_field.ptr, cells, unknown_value, ctx->d_cube.ptr, prob);
-  MCL_HIP(ctx, hipGetLastError());
+// ---- building a map store (map_store.h) ----------------------------------------------------------------------------------------------
+// The builders touch no context: they work on the stream they are given and leave it synchronised, and say what went wrong in *err.
+#define MAP_HIP(err, expr)                                                        \
+  do {                                                                            \
+    const hipError_t e_ = (expr);                                                 \
+    if (e_ != hipSuccess) {                                                       \
+      *(err) = std::string(#expr) + ": " + hipGetErrorString(e_);                 \
+      return e_ == hipErrorOutOfMemory ? MCL_ERR_OUT_OF_MEMORY : MCL_ERR_HIP;     \
+    }                                                                             \
+  } while (0)
+
+// The tables over s.d_field: the pz^3 table, and - given the field's values on the host - the palette and the far-tile bitmaps.
+mcl_status build_field_tables(MapStore& s, const float* h_field, hipStream_t st, std::string* err) {
+  const uint64_t cells = static_cast<uint64_t>(s.W) * s.H;
+  const float unknown_value = static_cast<float>(1. / s.key.lf.max_laser_distance);
+  const int prob = s.key.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB ? 1 : 0;
+  MAP_HIP(err, s.d_cube.ensure(cells + 1));
+  launch_cube_table(st, s.d_field.ptr, cells, unknown_value, s.d_cube.ptr, prob);
+  MAP_HIP(err, hipGetLastError());
   // Palette: the distinct values of the field (a distance map quantised to cell offsets has a few hundred).
-  ctx->pal_count = 0;
-  ctx->far_tiles = 0;
-  const uint64_t tiles_x = (ctx->W + 7) / 8 + 2, tiles_y = (ctx->H + 7) / 8 + 2;  // one border tile on every side
-  const uint32_t pal_base = ((ctx->H + 2) * 4u + 7u) & ~7u;                       // the kernel's row-offset table comes first in LDS
-  if (h_field && tiles_x * tiles_y * 128 < (1ull << 31) && ctx->W < (1u << 26) && pal_base + 8 <= 65536) {
-    const size_t max_entries = std::min<size_t>(kMaxPalette, (65536 - pal_base) / 8);
+  s.pal_count = 0;
+  s.far_tiles = 0;
+  const MapTableLayout t = map_table_layout(s.W, s.H);
+  static_assert(kMapMaxPalette == kMaxPalette, "map_store_host.h restates kernels.h");
+  if (h_field && t.palette_possible) {
+    const size_t max_entries = t.max_entries;
     std::vector<uint32_t> keys;
     {
       std::unordered_set<uint32_t> seen;
@@ -541,49 +514,122 @@ mcl_status rebuild_cube(mcl_ctx* ctx, const float* h_field) {
     }
     if (!keys.empty()) {
       std::sort(keys.begin(), keys.end());
-      MCL_HIP(ctx, ctx->d_pal_keys.ensure(keys.size()));
-      MCL_HIP(ctx, ctx->d_pal_val.ensure(keys.size()));
-      MCL_HIP(ctx, ctx->d_pal_idx.ensure(tiles_x * tiles_y * 64));
-      MCL_HIP(ctx, hipMemcpyAsync(ctx->d_pal_keys.ptr, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-      launch_palette_table(ctx->stream, ctx->d_field.ptr, ctx->W, ctx->H, unknown_value, ctx->d_pal_keys.ptr,
-                           static_cast<uint32_t>(keys.size()), prob, ctx->d_pal_idx.ptr, ctx->d_pal_val.ptr, pal_base);
-      MCL_HIP(ctx, hipGetLastError());
-      MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // keys is a local
-      ctx->pal_count = static_cast<uint32_t>(keys.size());
-      ctx->pal_pitch = static_cast<uint32_t>(tiles_x * 128);
-      ctx->pal_base = pal_base;
-      ctx->pal_bytes = static_cast<uint32_t>(tiles_x * tiles_y * 128);
+      const uint32_t tiles = static_cast<uint32_t>(t.tiles_x * t.tiles_y);
+      MAP_HIP(err, s.d_pal_keys.ensure(keys.size()));
+      MAP_HIP(err, s.d_pal_val.ensure(keys.size()));
+      MAP_HIP(err, s.d_pal_idx.ensure(t.pal_idx_count));
+      MAP_HIP(err, hipMemcpyAsync(s.d_pal_keys.ptr, keys.data(), keys.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      launch_palette_table(st, s.d_field.ptr, s.W, s.H, unknown_value, s.d_pal_keys.ptr, static_cast<uint32_t>(keys.size()), prob,
+                           s.d_pal_idx.ptr, s.d_pal_val.ptr, t.pal_base);
+      MAP_HIP(err, hipGetLastError());
+      MAP_HIP(err, hipStreamSynchronize(st));  // keys is a local
+      s.pal_count = static_cast<uint32_t>(keys.size());
+      s.pal_pitch = t.pal_pitch;
+      s.pal_base = t.pal_base;
+      s.pal_bytes = t.pal_bytes;
       // Far tiles: the entry most tiles are uniformly equal to, and the bitmap of those tiles (FieldView::far_bits).
-      ctx->far_tiles = 0;
-      const uint32_t row_bytes = static_cast<uint32_t>((tiles_x + 7) / 8);
-      const uint32_t far_bytes = static_cast<uint32_t>((static_cast<uint64_t>(row_bytes) * tiles_y + 15) & ~15ull);
-      if (tiles_x * tiles_y < (1ull << 31) && far_bytes <= 48 * 1024 && row_bytes < (1u << 13)) {
-        MCL_HIP(ctx, ctx->d_far_votes.ensure(keys.size()));
-        MCL_HIP(ctx, ctx->d_far_bits.ensure(far_bytes));
-        launch_far_tile_votes(ctx->stream, ctx->d_pal_idx.ptr, static_cast<uint32_t>(tiles_x * tiles_y), pal_base,
-                              static_cast<uint32_t>(keys.size()), ctx->d_far_votes.ptr);
+      if (t.far_possible) {
+        MAP_HIP(err, s.d_far_votes.ensure(keys.size()));
+        MAP_HIP(err, s.d_far_bits.ensure(t.far_bytes));
+        launch_far_tile_votes(st, s.d_pal_idx.ptr, tiles, t.pal_base, static_cast<uint32_t>(keys.size()), s.d_far_votes.ptr);
         std::vector<uint32_t> votes(keys.size());
-        MCL_HIP(ctx, hipMemcpyAsync(votes.data(), ctx->d_far_votes.ptr, votes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        MAP_HIP(err, hipMemcpyAsync(votes.data(), s.d_far_votes.ptr, votes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        MAP_HIP(err, hipStreamSynchronize(st));
         const size_t best = static_cast<size_t>(std::max_element(votes.begin(), votes.end()) - votes.begin());
-        if (votes[best] * 8ull >= tiles_x * tiles_y) {  // worth a test per look-up from one tile in eight
-          ctx->far_entry = pal_base + static_cast<uint32_t>(best) * 8u;
-          ctx->far_row_bytes = row_bytes;
-          ctx->far_bytes = far_bytes;
-          launch_far_tile_bits(ctx->stream, ctx->d_pal_idx.ptr, static_cast<uint32_t>(tiles_x), static_cast<uint32_t>(tiles_y), ctx->far_entry,
-                               row_bytes, far_bytes, ctx->d_far_bits.ptr);
-          ctx->far_linear_bytes = static_cast<uint32_t>(((tiles_x * tiles_y + 7) / 8 + 15) & ~15ull);
-          MCL_HIP(ctx, ctx->d_far_linear.ensure(ctx->far_linear_bytes));
-          launch_far_tile_bits_linear(ctx->stream, ctx->d_pal_idx.ptr, static_cast<uint32_t>(tiles_x * tiles_y), ctx->far_entry,
-                                      ctx->far_linear_bytes, ctx->d_far_linear.ptr);
-          MCL_HIP(ctx, hipGetLastError());
-          ctx->far_tiles = votes[best];
+        if (votes[best] * 8ull >= t.tiles_x * t.tiles_y) {  // worth a test per look-up from one tile in eight
+          s.far_entry = t.pal_base + static_cast<uint32_t>(best) * 8u;
+          s.far_row_bytes = t.far_row_bytes;
+          s.far_bytes = t.far_bytes;
+          launch_far_tile_bits(st, s.d_pal_idx.ptr, static_cast<uint32_t>(t.tiles_x), static_cast<uint32_t>(t.tiles_y), s.far_entry,
+                               t.far_row_bytes, t.far_bytes, s.d_far_bits.ptr);
+          s.far_linear_bytes = t.far_linear_bytes;
+          MAP_HIP(err, s.d_far_linear.ensure(s.far_linear_bytes));
+          launch_far_tile_bits_linear(st, s.d_pal_idx.ptr, tiles, s.far_entry, s.far_linear_bytes, s.d_far_linear.ptr);
+          MAP_HIP(err, hipGetLastError());
+          s.far_tiles = votes[best];
         }
       }
     }
   }
-  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MAP_HIP(err, hipStreamSynchronize(st));
   return MCL_OK;
+}
+
+// One occupancy grid as a caller hands it over.  prebuilt_field (mcl_set_map_async): the likelihood field of exactly these cells and
+// the store's parameters, built ahead by the worker.
+struct MapSource {
+  const int8_t* cells;
+  uint32_t W, H;
+  double resolution;
+  const double* origin;
+  const int8_t* traits;
+  int field_build;  // 0: the reference's wavefront on the host, 1: the exact distance transform on the device
+  std::vector<float>* prebuilt_field;
+};
+// Fills a store whose key is set (and which may have taken over the buffers of a private store nobody reads any more) with everything
+// mcl_set_map builds for a context of that key.  scratch: the device field build's; timing: two events to bracket it, or nullptr.
+mcl_status build_map_store(MapStore& s, const MapSource& in, hipStream_t st, DeviceBuffer<uint32_t>* scratch, hipEvent_t* timing, std::string* err) {
+  const size_t n = static_cast<size_t>(in.W) * in.H;
+  s.W = in.W;
+  s.H = in.H;
+  s.resolution = in.resolution;
+  s.origin = pose_from(in.origin);
+  s.origin_inverse = pose_inverse(s.origin);  // likelihood_field_model_base.hpp:99 ; raycasting.hpp:69
+  s.traits = OccupancyTraits{in.traits[0], in.traits[1], in.traits[2]};
+  MAP_HIP(err, s.d_cells.ensure(n));
+  MAP_HIP(err, hipMemcpyAsync(s.d_cells.ptr, in.cells, n, hipMemcpyHostToDevice, st));
+  MAP_HIP(err, hipStreamSynchronize(st));
+  std::vector<uint32_t> free_cells;
+  collect_free_cells(in.cells, in.W, in.H, s.traits, free_cells);
+  s.n_free = free_cells.size();
+  MAP_HIP(err, s.d_free.ensure(std::max<size_t>(free_cells.size(), 1)));
+  if (!free_cells.empty()) {
+    MAP_HIP(err, hipMemcpyAsync(s.d_free.ptr, free_cells.data(), free_cells.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    MAP_HIP(err, hipStreamSynchronize(st));  // free_cells is a local
+  }
+  if (s.key.sensor_kind == MCL_SENSOR_BEAM) {
+    if (!(n < (1ull << 31))) {
+      *err = "mcl_set_map: beam model grids are limited to 2^31 cells";
+      return MCL_ERR_INVALID_ARGUMENT;
+    }
+    MAP_HIP(err, s.d_nonfree_bits.ensure(nonfree_words(in.W, in.H)));
+    launch_pack_nonfree(st, s.d_cells.ptr, in.W, in.H, s.traits.free_value, s.d_nonfree_bits.ptr);
+    MAP_HIP(err, hipGetLastError());
+    MAP_HIP(err, hipStreamSynchronize(st));
+    return MCL_OK;
+  }
+  MAP_HIP(err, s.d_field.ensure(n));
+  bool on_device = false;
+  s.field_build_ms = 0.0;
+  if (in.field_build == 1) {
+    // Exact Euclidean distance transform on the device (kernels.hip, "likelihood field on the device"); equal to the
+    // reference's wavefront at all but a few cells.  The default below is the bit-identical host wavefront.
+    const mcl_lf_params& lf = s.key.lf;
+    const FieldBuildParams fp{lf.max_obstacle_distance, lf.max_laser_distance, lf.z_hit, lf.z_random, lf.sigma_hit,
+                              lf.model_unknown_space, lf.only_obstacle_boundaries};
+    MAP_HIP(err, scratch->ensure(n));
+    if (timing) MAP_HIP(err, hipEventRecord(timing[0], st));
+    on_device = launch_build_field(st, s.d_cells.ptr, in.W, in.H, in.resolution, s.traits.free_value, s.traits.unknown_value,
+                                   s.traits.occupied_value, fp, reinterpret_cast<uint16_t*>(scratch->ptr),
+                                   reinterpret_cast<int16_t*>(scratch->ptr) + n, s.d_field.ptr);
+    MAP_HIP(err, hipGetLastError());
+    if (on_device) {
+      if (timing) MAP_HIP(err, hipEventRecord(timing[1], st));
+      s.h_field.resize(n);
+      MAP_HIP(err, hipMemcpyAsync(s.h_field.data(), s.d_field.ptr, n * sizeof(float), hipMemcpyDeviceToHost, st));
+      MAP_HIP(err, hipStreamSynchronize(st));
+      float ms = 0.f;
+      if (timing && hipEventElapsedTime(&ms, timing[0], timing[1]) == hipSuccess) s.field_build_ms = ms;
+    }
+  }
+  if (!on_device) {
+    if (in.prebuilt_field) s.h_field.swap(*in.prebuilt_field);
+    else build_likelihood_field(in.cells, in.W, in.H, in.resolution, s.traits, s.key.lf, s.h_field);
+    MAP_HIP(err, hipMemcpyAsync(s.d_field.ptr, s.h_field.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
+    MAP_HIP(err, hipStreamSynchronize(st));
+  }
+  s.field_built_on_device = on_device;
+  return build_field_tables(s, s.h_field.data(), st, err);
 }
 
 // What a cycle uploads for its reweight kernel, in the form that kernel reads: a scan's points (x, y; the grid models), the scan's
@@ -921,7 +967,7 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
     lf_args = LfReweightArgs{.p = ctx->cur(), .n = ctx->n, .f = ctx->field_view(), .d_points = ctx->d_points.ptr, .B = static_cast<uint32_t>(B),
                              .sort = ordered ? &sort : nullptr, .patches = mode.patches, .beams = mode.beams,
                              .dispersed = dispersed,
-                             .scan_cells = ctx->scan_extent / ctx->resolution, .unit_weights = unit_weights,
+                             .scan_cells = ctx->scan_extent / ctx->map->resolution, .unit_weights = unit_weights,
                              .stats = PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
                                                  reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotPatchMirror),
                                                  static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
@@ -976,7 +1022,7 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
     if (use_table && !ctx->beam_table_ready) {
       hipError_t e = ctx->d_beam_table.ensure(4 * static_cast<size_t>(ctx->beam_table_count));
       if (e == hipSuccess) {
-        launch_beam_table(ctx->stream, model, ctx->resolution, ctx->beam_table_count, ctx->d_beam_table.ptr);
+        launch_beam_table(ctx->stream, model, ctx->map->resolution, ctx->beam_table_count, ctx->d_beam_table.ptr);
         e = hipGetLastError();
       }
       if (e != hipSuccess) {
@@ -988,7 +1034,7 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
     launch_reweight_beam(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model,
                          ctx->d_points.ptr, static_cast<uint32_t>(B), ctx->d_kld_scalars.ptr + kKldBeamSteps, ordered ? &sort : nullptr,
-                         ctx->d_nonfree_bits.ptr, ctx->d_beam_points.ptr, use_table ? ctx->d_beam_table.ptr : nullptr,
+                         ctx->map->d_nonfree_bits.ptr, ctx->d_beam_points.ptr, use_table ? ctx->d_beam_table.ptr : nullptr,
                          use_table ? ctx->beam_table_count : 0u, ctx->tuning.beam_free_ahead != 0, ctx->tuning.beam_sectors != 0);
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   }
@@ -1797,7 +1843,7 @@ mcl_status sharded_draw_padded(mcl_ctx* ctx, const double* d_intervals, uint64_t
   MCL_HIP(ctx, ctx->d_replies_out.ensure(4 * entries));
   MCL_HIP(ctx, hipMemsetAsync(ctx->d_send_targets.ptr, 0xFF, entries * sizeof(double), ctx->stream));    // NaN: no request
   MCL_HIP(ctx, hipMemsetAsync(ctx->d_route_order.ptr, 0xFF, entries * sizeof(uint32_t), ctx->stream));    // 0xFFFFFFFF: no slot
-  launch_resample_targets(ctx->stream, ctx->cfg.seed, ctx->step, 0.0, 0.0, first_slot, m, ctx->have_map ? ctx->n_free : 0, ctx->d_targets.ptr, d_plan);
+  launch_resample_targets(ctx->stream, ctx->cfg.seed, ctx->step, 0.0, 0.0, first_slot, m, ctx->have_map ? ctx->map->n_free : 0, ctx->d_targets.ptr, d_plan);
   MCL_HIP(ctx, hipGetLastError());
   {
     const size_t nblocks = num_chunks(m);
@@ -1831,7 +1877,7 @@ mcl_status sharded_draw(mcl_ctx* ctx, double random_state_probability, double to
   MCL_HIP(ctx, ctx->d_send_targets.ensure(std::max<uint64_t>(m, 1)));
   MCL_HIP(ctx, ctx->d_route_order.ensure(std::max<uint64_t>(m, 1)));
   MCL_HIP(ctx, ctx->d_replies_in.ensure(std::max<uint64_t>(4 * m, 4)));
-  launch_resample_targets(ctx->stream, ctx->cfg.seed, ctx->step, random_state_probability, total, first_slot, m, ctx->have_map ? ctx->n_free : 0,
+  launch_resample_targets(ctx->stream, ctx->cfg.seed, ctx->step, random_state_probability, total, first_slot, m, ctx->have_map ? ctx->map->n_free : 0,
                           ctx->d_targets.ptr, d_plan);
   MCL_HIP(ctx, hipGetLastError());
   if (const mcl_status s = mcl_route_targets(ctx, ctx->d_targets.ptr, m, d_intervals, d_intervals + world, world, rank, ctx->d_send_targets.ptr,
@@ -2316,18 +2362,8 @@ void mcl_destroy(mcl_ctx* ctx) {
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   for (auto& set : ctx->sets) set.release();
-  ctx->d_field.release();
+  ctx->map.drop();  // (a private store frees its buffers here; a shared one loses a user)
   ctx->d_field_scratch.release();
-  ctx->d_cube.release();
-  ctx->d_pal_idx.release();
-  ctx->d_far_bits.release();
-  ctx->d_far_linear.release();
-  ctx->d_far_votes.release();
-  ctx->d_pal_val.release();
-  ctx->d_pal_keys.release();
-  ctx->d_cells.release();
-  ctx->d_nonfree_bits.release();
-  ctx->d_free.release();
   ctx->d_points.release();
   ctx->d_beam_points.release();
   ctx->d_beam_table.release();
@@ -2473,73 +2509,33 @@ mcl_status mcl_map_commit(mcl_ctx* ctx, int32_t wait) {
 
 }  // extern "C"
 namespace {
+// What a context keeps of its own about the map it has just been given, a private store or a shared one.
+void map_installed(mcl_ctx* ctx) {
+  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) {
+    // (the table itself - 32 bytes per squared cell distance up to the range, 46 MB at 60 m / 5 cm - is built by the first
+    // launch of the ordered kernel that wants it: the usual 2000-particle filter never does; do_reweight)
+    ctx->beam_table_count = beam_table_entries(ctx->cfg.beam.beam_max_range, ctx->map->resolution);
+    ctx->beam_table_ready = false;
+  }
+  ctx->have_map = true;
+}
+
 mcl_status set_map_impl(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint32_t height, double resolution, const double origin[4],
                         const int8_t value_traits[3], std::vector<float>* prebuilt_field) {
   if (const mcl_status s = bind_device(ctx)) return s;
-  const size_t n = static_cast<size_t>(width) * height;
-  ctx->W = width;
-  ctx->H = height;
-  ctx->resolution = resolution;
-  ctx->origin = pose_from(origin);
-  ctx->origin_inverse = pose_inverse(ctx->origin);  // likelihood_field_model_base.hpp:99 ; raycasting.hpp:69
-  ctx->traits = OccupancyTraits{value_traits[0], value_traits[1], value_traits[2]};
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  MCL_HIP(ctx, ctx->d_cells.ensure(n));
-  MCL_HIP(ctx, hipMemcpy(ctx->d_cells.ptr, cells, n, hipMemcpyHostToDevice));
-  std::vector<uint32_t> free_cells;
-  collect_free_cells(cells, width, height, ctx->traits, free_cells);
-  ctx->n_free = free_cells.size();
-  MCL_HIP(ctx, ctx->d_free.ensure(std::max<size_t>(free_cells.size(), 1)));
-  if (!free_cells.empty())
-    MCL_HIP(ctx, hipMemcpy(ctx->d_free.ptr, free_cells.data(), free_cells.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) {
-    MCL_REQUIRE(ctx, n < (1ull << 31), "mcl_set_map: beam model grids are limited to 2^31 cells");
-    MCL_HIP(ctx, ctx->d_nonfree_bits.ensure(nonfree_words(width, height)));
-    launch_pack_nonfree(ctx->stream, ctx->d_cells.ptr, width, height, ctx->traits.free_value, ctx->d_nonfree_bits.ptr);
-    MCL_HIP(ctx, hipGetLastError());
-    {
-      const mcl_beam_params& b = ctx->cfg.beam;
-      // (the table itself - 32 bytes per squared cell distance up to the range, 46 MB at 60 m / 5 cm - is built by the first
-      // launch of the ordered kernel that wants it: the usual 2000-particle filter never does; do_reweight)
-      ctx->beam_table_count = beam_table_entries(b.beam_max_range, resolution);
-      ctx->beam_table_ready = false;
-    }
-    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
-    MCL_HIP(ctx, ctx->d_field.ensure(n));
-    bool on_device = false;
-    ctx->field_build_ms = 0.0;
-    if (ctx->tuning.field_build == 1) {
-      // Exact Euclidean distance transform on the device (kernels.hip, "likelihood field on the device"); equal to the
-      // reference's wavefront at all but a few cells.  The default below is the bit-identical host wavefront.
-      const mcl_lf_params& lf = ctx->cfg.lf;
-      const FieldBuildParams fp{lf.max_obstacle_distance, lf.max_laser_distance, lf.z_hit, lf.z_random, lf.sigma_hit,
-                                lf.model_unknown_space, lf.only_obstacle_boundaries};
-      MCL_HIP(ctx, ctx->d_field_scratch.ensure(n));
-      MCL_HIP(ctx, hipEventRecord(ctx->ev[MCL_STAGE_REWEIGHT][0], ctx->stream));
-      on_device = launch_build_field(ctx->stream, ctx->d_cells.ptr, width, height, resolution, ctx->traits.free_value, ctx->traits.unknown_value,
-                                     ctx->traits.occupied_value, fp, reinterpret_cast<uint16_t*>(ctx->d_field_scratch.ptr),
-                                     reinterpret_cast<int16_t*>(ctx->d_field_scratch.ptr) + n, ctx->d_field.ptr);
-      MCL_HIP(ctx, hipGetLastError());
-      if (on_device) {
-        MCL_HIP(ctx, hipEventRecord(ctx->ev[MCL_STAGE_REWEIGHT][1], ctx->stream));
-        ctx->h_field.resize(n);
-        MCL_HIP(ctx, hipMemcpyAsync(ctx->h_field.data(), ctx->d_field.ptr, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->ev[MCL_STAGE_REWEIGHT][0], ctx->ev[MCL_STAGE_REWEIGHT][1]) == hipSuccess) ctx->field_build_ms = ms;
-      }
-    }
-    if (!on_device) {
-      if (prebuilt_field) ctx->h_field.swap(*prebuilt_field);
-      else build_likelihood_field(cells, width, height, resolution, ctx->traits, ctx->cfg.lf, ctx->h_field);
-      MCL_HIP(ctx, hipMemcpy(ctx->d_field.ptr, ctx->h_field.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    }
-    ctx->field_built_on_device = on_device;
-    if (const mcl_status s = rebuild_cube(ctx, ctx->h_field.data())) return s;
-  }
-  ctx->have_map = true;
+  // A private store, built in the buffers of the one it replaces where the context was that one's only reader; a context that read a
+  // shared store leaves it here.
+  auto store = std::make_shared<MapStore>();
+  if (const std::shared_ptr<MapStore> old = ctx->map.take_private()) store->take_buffers(*old);
+  ctx->map.drop();
+  ctx->have_map = false;
+  store->key = MapStoreKey{ctx->device, ctx->cfg.sensor_kind, ctx->cfg.lf};
+  const MapSource in{cells, width, height, resolution, origin, value_traits, ctx->tuning.field_build, prebuilt_field};
+  std::string err;
+  if (const mcl_status s = build_map_store(*store, in, ctx->stream, &ctx->d_field_scratch, ctx->ev[MCL_STAGE_REWEIGHT], &err)) return fail(ctx, s, err);
+  ctx->map.own(std::move(store));
+  map_installed(ctx);
   return MCL_OK;
 }
 
@@ -2585,10 +2581,10 @@ mcl_status mcl_get_likelihood_field(mcl_ctx* ctx, float* out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, out, "null output");
   if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "The current sensor model does not support likelihood field");
-  if (!ctx->have_map || !ctx->d_field.ptr) return fail(ctx, MCL_ERR_NOT_READY, "no likelihood field");
+  if (!ctx->have_map || !ctx->map->d_field.ptr) return fail(ctx, MCL_ERR_NOT_READY, "no likelihood field");
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  MCL_HIP(ctx, hipMemcpy(out, ctx->d_field.ptr, static_cast<size_t>(ctx->W) * ctx->H * sizeof(float), hipMemcpyDeviceToHost));
+  MCL_HIP(ctx, hipMemcpy(out, ctx->map->d_field.ptr, static_cast<size_t>(ctx->map->W) * ctx->map->H * sizeof(float), hipMemcpyDeviceToHost));
   return MCL_OK;
 }
 
@@ -2597,12 +2593,121 @@ mcl_status mcl_set_likelihood_field(mcl_ctx* ctx, const float* field) {
   MCL_REQUIRE(ctx, field, "null field");
   if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_likelihood_field: not on a context whose sensor model has a map of its own (mcl_set_ndt_map, mcl_set_landmark_map)");
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "set the map first");
+  if (ctx->map.shared())
+    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_likelihood_field: the context reads a shared map, which does not change (mcl_set_map gives it a map of its own)");
   if (const mcl_status s = bind_device(ctx)) return s;
-  const size_t n = static_cast<size_t>(ctx->W) * ctx->H;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  MCL_HIP(ctx, ctx->d_field.ensure(n));
-  MCL_HIP(ctx, hipMemcpy(ctx->d_field.ptr, field, n * sizeof(float), hipMemcpyHostToDevice));
-  return rebuild_cube(ctx, field);
+  // A new private store in the buffers of the old one: the same grid and free cells, this field, and the tables over it.
+  const std::shared_ptr<MapStore> old = ctx->map.take_private();
+  if (!old) return fail(ctx, MCL_ERR_NOT_READY, "set the map first");
+  ctx->have_map = false;
+  auto store = std::make_shared<MapStore>();
+  store->take_buffers(*old);
+  store->key = old->key;
+  store->W = old->W;
+  store->H = old->H;
+  store->resolution = old->resolution;
+  store->origin = old->origin;
+  store->origin_inverse = old->origin_inverse;
+  store->traits = old->traits;
+  store->n_free = old->n_free;
+  store->field_built_on_device = old->field_built_on_device;
+  store->field_build_ms = old->field_build_ms;
+  const size_t n = static_cast<size_t>(store->W) * store->H;
+  MCL_HIP(ctx, store->d_field.ensure(n));
+  MCL_HIP(ctx, hipMemcpy(store->d_field.ptr, field, n * sizeof(float), hipMemcpyHostToDevice));
+  store->h_field.assign(field, field + n);
+  std::string err;
+  if (const mcl_status s = build_field_tables(*store, field, ctx->stream, &err)) return fail(ctx, s, err);
+  ctx->map.own(std::move(store));
+  ctx->have_map = true;
+  return MCL_OK;
+}
+
+// ---- shared maps ---------------------------------------------------------------------------------------------------------------------
+}  // extern "C"
+// The caller's reference to a store that any number of contexts read (mcl_use_shared_map).
+struct mcl_shared_map {
+  std::shared_ptr<const MapStore> store;
+  std::string error;
+};
+namespace {
+thread_local std::string g_shared_map_error;
+mcl_status fail_shared_map(mcl_status code, const std::string& msg) {
+  g_shared_map_error = msg;
+  return code;
+}
+}  // namespace
+extern "C" {
+
+mcl_status mcl_shared_map_create(const mcl_config* cfg, const int8_t* cells, uint32_t width, uint32_t height, double resolution,
+                                 const double origin[4], const int8_t value_traits[3], int32_t field_build, mcl_shared_map** out) {
+  if (!cfg || !out) return fail_shared_map(MCL_ERR_INVALID_ARGUMENT, "mcl_shared_map_create: null argument");
+  *out = nullptr;
+  if (const char* why = map_store_check_kind(cfg->sensor_kind)) return fail_shared_map(MCL_ERR_UNSUPPORTED, why);
+  if (!(cells && origin && value_traits && width > 0 && height > 0 && resolution > 0) || (field_build != 0 && field_build != 1))
+    return fail_shared_map(MCL_ERR_INVALID_ARGUMENT, "mcl_shared_map_create: bad argument");
+  if (!(static_cast<uint64_t>(width) * height < 0xFFFFFFFFull)) return fail_shared_map(MCL_ERR_INVALID_ARGUMENT, "mcl_shared_map_create: grid too large");
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
+    return fail_shared_map(MCL_ERR_NO_DEVICE, "mcl_shared_map_create: no HIP device (this library has no CPU fallback)");
+  if (cfg->device_id < 0 || cfg->device_id >= count) return fail_shared_map(MCL_ERR_INVALID_ARGUMENT, "mcl_shared_map_create: bad device_id");
+  mcl_shared_map* map = new (std::nothrow) mcl_shared_map();
+  if (!map) return fail_shared_map(MCL_ERR_OUT_OF_MEMORY, "mcl_shared_map_create: host allocation failed");
+  // A stream of the builder's own, synchronised before the store is handed out: any stream may read it, and no context is touched.
+  hipStream_t stream = nullptr;
+  DeviceBuffer<uint32_t> scratch;
+  auto store = std::make_shared<MapStore>();
+  store->key = MapStoreKey{cfg->device_id, cfg->sensor_kind, cfg->lf};
+  std::string err;
+  auto build = [&]() -> mcl_status {
+    MAP_HIP(&err, hipSetDevice(cfg->device_id));
+    MAP_HIP(&err, configure_device_kernels());
+    MAP_HIP(&err, hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    const MapSource in{cells, width, height, resolution, origin, value_traits, field_build, nullptr};
+    if (const mcl_status s = build_map_store(*store, in, stream, &scratch, nullptr, &err)) return s;
+    MAP_HIP(&err, hipStreamSynchronize(stream));
+    return MCL_OK;
+  };
+  const mcl_status st = build();
+  if (stream) {
+    (void)hipStreamSynchronize(stream);
+    (void)hipStreamDestroy(stream);
+  }
+  scratch.release();
+  if (st != MCL_OK) {
+    delete map;
+    return fail_shared_map(st, "mcl_shared_map_create: " + err);
+  }
+  map->store = std::move(store);
+  *out = map;
+  return MCL_OK;
+}
+
+void mcl_shared_map_release(mcl_shared_map* map) { delete map; }  // (the store lives on while a context reads it)
+
+mcl_status mcl_shared_map_get_info(const mcl_shared_map* map, mcl_shared_map_info* info) {
+  if (!map || !info) return MCL_ERR_INVALID_ARGUMENT;
+  const MapStore& s = *map->store;
+  *info = mcl_shared_map_info{s.W, s.H, s.resolution, s.key.sensor_kind, s.key.device, s.device_bytes(), s.host_bytes(),
+                              s.users.load(std::memory_order_relaxed)};
+  return MCL_OK;
+}
+
+const char* mcl_shared_map_last_error(const mcl_shared_map* map) { return map ? map->error.c_str() : g_shared_map_error.c_str(); }
+
+mcl_status mcl_use_shared_map(mcl_ctx* ctx, mcl_shared_map* map) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  MCL_REQUIRE(ctx, map, "mcl_use_shared_map: null map");
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_use_shared_map: not on a context whose sensor model has a map of its own (mcl_set_ndt_map, mcl_set_landmark_map)");
+  if (const char* why = map_store_mismatch(map->store->key, ctx->device, ctx->cfg.sensor_kind, ctx->cfg.lf))
+    return fail(ctx, MCL_ERR_INVALID_ARGUMENT, why);  // (the context is as it was)
+  drop_pending_map(ctx);  // (as mcl_set_map: a map given now replaces one that is still on its way)
+  if (const mcl_status s = bind_device(ctx)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // nothing of the context reads the old store any more
+  ctx->map.attach(map->store);
+  map_installed(ctx);
+  return MCL_OK;
 }
 
 mcl_status mcl_initialize_normal(mcl_ctx* ctx, const double mean_xytheta[3], const double cov[9]) {
@@ -3450,7 +3555,7 @@ mcl_status mcl_resample_targets(mcl_ctx* ctx, uint32_t step, double random_state
   MCL_REQUIRE(ctx, count == 0 || d_targets, "null targets");
   if (const mcl_status s = bind_device(ctx)) return s;
   launch_resample_targets(ctx->stream, ctx->cfg.seed, step, random_state_probability, total, first_slot, count,
-                          ctx->have_map ? ctx->n_free : 0, d_targets);
+                          ctx->have_map ? ctx->map->n_free : 0, d_targets);
   MCL_HIP(ctx, hipGetLastError());
   return MCL_OK;
 }
@@ -3613,23 +3718,24 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
     return MCL_OK;
   }
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no map set");
-  MCL_REQUIRE(ctx, ctx->n_free > 0, "mcl_initialize_from_map: the map has no free cell");  // the reference asserts (:136)
+  MCL_REQUIRE(ctx, ctx->map->n_free > 0, "mcl_initialize_from_map: the map has no free cell");  // the reference asserts (:136)
   if (const mcl_status s = bind_device(ctx)) return s;
   const uint64_t n = std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity);  // take_exactly(max_particles)
   ctx->facts.weights_rewrite_begins();
   launch_init_from_map(ctx->stream, ctx->cur(), n, ctx->cfg.seed, ctx->cfg.shard_offset, ctx->grid_view(),
-                       FreeCells{ctx->d_free.ptr, ctx->n_free});
+                       FreeCells{ctx->map->d_free.ptr, ctx->map->n_free});
   MCL_HIP(ctx, hipGetLastError());
   // the set covers the map: centre of the grid, the spread of a uniform distribution over its extent in the world's axes
   // (extent / sqrt(12)), every heading - what the estimate of such a set would say
-  const double hx = 0.5 * ctx->W * ctx->resolution, hy = 0.5 * ctx->H * ctx->resolution;
+  const Pose2 origin = ctx->map->origin;
+  const double hx = 0.5 * ctx->map->W * ctx->map->resolution, hy = 0.5 * ctx->map->H * ctx->map->resolution;
   double cx, cy;
-  rot_apply(ctx->origin.r, hx, hy, cx, cy);
-  const double ex = 2.0 * (std::abs(ctx->origin.r.c) * hx + std::abs(ctx->origin.r.s) * hy);
-  const double ey = 2.0 * (std::abs(ctx->origin.r.s) * hx + std::abs(ctx->origin.r.c) * hy);
+  rot_apply(origin.r, hx, hy, cx, cy);
+  const double ex = 2.0 * (std::abs(origin.r.c) * hx + std::abs(origin.r.s) * hy);
+  const double ey = 2.0 * (std::abs(origin.r.s) * hx + std::abs(origin.r.c) * hy);
   install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalShares,
                     .force_update = true /* beluga_ros/include/beluga_ros/amcl.hpp:197 */, .cloud = InstallSet::kCloudGiven,
-                    .cloud_mean = {cx + ctx->origin.x, cy + ctx->origin.y, 0.0}, .cloud_sigma = {ex / std::sqrt(12.0), ey / std::sqrt(12.0), kPi},
+                    .cloud_mean = {cx + origin.x, cy + origin.y, 0.0}, .cloud_sigma = {ex / std::sqrt(12.0), ey / std::sqrt(12.0), kPi},
                     .patches = LfPlanner::Installed::kDispersed});
   return MCL_OK;
 }
@@ -3648,7 +3754,7 @@ mcl_status mcl_get_likelihood_field_origin(mcl_ctx* ctx, double origin[4]) {
     return fail(ctx, MCL_ERR_UNSUPPORTED, "The current sensor model does not support likelihood field");
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "no likelihood field");
   // likelihood_field_model_base.hpp:105: world_to_likelihood_field_transform_.inverse(), i.e. inverse(inverse(grid.origin()))
-  const Pose2 o = pose_inverse(ctx->origin_inverse);
+  const Pose2 o = pose_inverse(ctx->map->origin_inverse);
   origin[0] = o.r.c;
   origin[1] = o.r.s;
   origin[2] = o.x;
@@ -3748,7 +3854,7 @@ mcl_status mcl_get_counter(mcl_ctx* ctx, const char* name, uint64_t* value) {
   else if (key == "lf_far_beams_launches") *value = ctx->lf_far_beams_launches;
   else if (key == "small_tail_launches") *value = ctx->small_tail_launches;
   else if (key == "estimate_repivots") *value = ctx->estimate_repivots;
-  else if (key == "lf_far_tiles") *value = ctx->far_tiles;
+  else if (key == "lf_far_tiles") *value = ctx->map->far_tiles;
   else if (key == "noise_ahead_used") *value = ctx->noise_ahead_used;
   else if (key == "order_ahead_used") *value = ctx->order_ahead_used;
   else if (key == "order_ahead_missed") *value = ctx->order_ahead_missed;
@@ -3764,8 +3870,10 @@ mcl_status mcl_get_counter(mcl_ctx* ctx, const char* name, uint64_t* value) {
   else if (key == "host_ns_wait") *value = ctx->host_ns[2];
   else if (key == "host_ns_after_wait") *value = ctx->host_ns[3];
   else if (key == "host_cycles") *value = ctx->host_cycles;
-  else if (key == "field_build_us") *value = static_cast<uint64_t>(ctx->field_build_ms * 1e3);  // kernels of the last device field build
-  else if (key == "field_built_on_device") *value = ctx->field_built_on_device ? 1 : 0;
+  else if (key == "field_build_us") *value = static_cast<uint64_t>(ctx->map->field_build_ms * 1e3);  // kernels of the last device field build
+  else if (key == "field_built_on_device") *value = ctx->map->field_built_on_device ? 1 : 0;
+  else if (key == "map_device_bytes") *value = ctx->map.shared() ? 0 : ctx->map->device_bytes();  // what the context itself owns for its map
+  else if (key == "map_shared") *value = ctx->map.shared() ? 1 : 0;
   else if (key == "cluster_cells") *value = ctx->cluster_cells;
   else if (key == "comm_bytes_out") *value = ctx->comm_bytes_out;
   else if (key == "comm_collectives") *value = ctx->comm_collectives;

@@ -1,0 +1,128 @@
+// map_store.h — MapStore: everything that is held on behalf of one occupancy-grid map, on the host and on one device.  A context reads
+// its map only through a store (mcl_ctx::map, a MapHold): a private one that mcl_set_map built for it, or one that
+// mcl_shared_map_create built and any number of contexts read (mcl_use_shared_map).  A store does not change once its builder
+// (context.hip build_map_store) has returned it; a new map, or a new field, is a new store.  What a context builds lazily or from
+// parameters of its own - the beam range table, scratch, the planner's statistics - stays in the context.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+#include "kernels.h"
+#include "map_build.h"
+#include "map_store_host.h"
+
+namespace mcl {
+
+template <class T>
+struct DeviceBuffer {
+  T* ptr{nullptr};
+  size_t count{0};
+  hipError_t ensure(size_t n) {
+    if (n <= count) return hipSuccess;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    count = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T));
+    if (e == hipSuccess) count = n;
+    return e;
+  }
+  void release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    count = 0;
+  }
+  // The other buffer's memory instead of this one's (a store built in the place of a private one takes its buffers over).
+  void take(DeviceBuffer& other) {
+    release();
+    std::swap(ptr, other.ptr);
+    std::swap(count, other.count);
+  }
+  uint64_t bytes() const { return static_cast<uint64_t>(count) * sizeof(T); }
+};
+
+struct MapStore {
+  MapStoreKey key{0, MCL_SENSOR_LIKELIHOOD_FIELD, {}};
+  // geometry
+  uint32_t W{0}, H{0};
+  double resolution{0};
+  Pose2 origin{}, origin_inverse{};
+  OccupancyTraits traits{0, -1, 100};
+  // occupancy and the free cells (every kind)
+  DeviceBuffer<int8_t> d_cells;
+  DeviceBuffer<uint32_t> d_free;
+  uint64_t n_free{0};
+  DeviceBuffer<uint32_t> d_nonfree_bits;  // beam model: 1 bit per cell and the coarse bitmaps (NonFreeBits)
+  // the likelihood-field kinds
+  std::vector<float> h_field;
+  DeviceBuffer<float> d_field;
+  DeviceBuffer<double> d_cube;  // pz^3 table of the field (+1 slot for out-of-grid beams)
+  // palette form of the same table (FieldView::pal_*), built when the field has <= kMaxPalette distinct values
+  DeviceBuffer<uint16_t> d_pal_idx;
+  DeviceBuffer<double> d_pal_val;
+  DeviceBuffer<uint32_t> d_pal_keys;
+  uint32_t pal_count{0}, pal_pitch{0}, pal_base{0}, pal_bytes{0};
+  DeviceBuffer<uint8_t> d_far_bits;   // FieldView::far_bits: tiles of d_pal_idx uniformly equal to the table's most common entry
+  DeviceBuffer<uint32_t> d_far_votes;
+  uint32_t far_row_bytes{0}, far_bytes{0}, far_entry{0};
+  DeviceBuffer<uint8_t> d_far_linear;  // FieldView::far_linear: the same bits by the tiles' linear index
+  uint32_t far_linear_bytes{0};
+  uint64_t far_tiles{0};  // number of set bits' worth of tiles voted for far_entry (0 = no bitmap)
+  // how the field came to be
+  bool field_built_on_device{false};
+  double field_build_ms{0.0};
+  // contexts that read the store through mcl_use_shared_map (MapHold)
+  mutable std::atomic<uint32_t> users{0};
+
+  MapStore() = default;
+  MapStore(const MapStore&) = delete;
+  MapStore& operator=(const MapStore&) = delete;
+  ~MapStore() {
+    if (!device_bytes()) return;
+    int current = 0;
+    const bool restore = hipGetDevice(&current) == hipSuccess && current != key.device;
+    (void)hipSetDevice(key.device);
+    release_device();
+    if (restore) (void)hipSetDevice(current);
+  }
+
+  uint64_t device_bytes() const {
+    return d_cells.bytes() + d_free.bytes() + d_nonfree_bits.bytes() + d_field.bytes() + d_cube.bytes() + d_pal_idx.bytes() + d_pal_val.bytes() +
+           d_pal_keys.bytes() + d_far_bits.bytes() + d_far_votes.bytes() + d_far_linear.bytes();
+  }
+  uint64_t host_bytes() const { return static_cast<uint64_t>(h_field.size()) * sizeof(float); }
+  // The buffers of a private store that nobody reads any more, to be filled again.
+  void take_buffers(MapStore& old) {
+    d_cells.take(old.d_cells);
+    d_free.take(old.d_free);
+    d_nonfree_bits.take(old.d_nonfree_bits);
+    d_field.take(old.d_field);
+    d_cube.take(old.d_cube);
+    d_pal_idx.take(old.d_pal_idx);
+    d_pal_val.take(old.d_pal_val);
+    d_pal_keys.take(old.d_pal_keys);
+    d_far_bits.take(old.d_far_bits);
+    d_far_votes.take(old.d_far_votes);
+    d_far_linear.take(old.d_far_linear);
+    h_field.swap(old.h_field);
+  }
+  void release_device() {
+    d_cells.release();
+    d_free.release();
+    d_nonfree_bits.release();
+    d_field.release();
+    d_cube.release();
+    d_pal_idx.release();
+    d_pal_val.release();
+    d_pal_keys.release();
+    d_far_bits.release();
+    d_far_votes.release();
+    d_far_linear.release();
+  }
+};
+
+}  // namespace mcl

@@ -437,6 +437,39 @@ struct ClusterEstimate {
 
 class AmclBatch;
 
+/// One map on the device for any number of filters (mcl_shared_map_*): built once - for the device and the sensor model given, which
+/// every filter that uses it must share (the likelihood-field models: the same model and equal parameters) - and never changed.
+/// Amcl::use_map / AmclBatch::use_map attach filters to it; the object holds the caller's reference only and may go out of scope while
+/// filters still use the map, which lives until the last of them has left it.  The constructor touches no filter: it may run on another
+/// thread while filters update.
+class SharedMap {
+ public:
+  /// `device_field_build`: the likelihood field by the device's exact distance transform instead of the reference's wavefront on the host.
+  inline SharedMap(const OccupancyGridView& map, const SensorModelParam& sensor, int device = 0, bool device_field_build = false);
+  SharedMap(const SharedMap&) = delete;
+  SharedMap& operator=(const SharedMap&) = delete;
+  SharedMap(SharedMap&& other) noexcept : map_(other.map_) { other.map_ = nullptr; }
+  SharedMap& operator=(SharedMap&& other) noexcept {
+    if (this != &other) {
+      mcl_shared_map_release(map_);
+      map_ = other.map_;
+      other.map_ = nullptr;
+    }
+    return *this;
+  }
+  ~SharedMap() { mcl_shared_map_release(map_); }
+  /// Size, sensor kind, device, the bytes the map holds and the filters attached now.
+  [[nodiscard]] mcl_shared_map_info info() const {
+    mcl_shared_map_info out{};
+    if (mcl_shared_map_get_info(map_, &out) != MCL_OK) throw std::runtime_error("beluga_amd::SharedMap: no map (moved from)");
+    return out;
+  }
+  [[nodiscard]] mcl_shared_map* native_handle() const { return map_; }
+
+ private:
+  mcl_shared_map* map_{nullptr};
+};
+
 class Amcl {
  public:
   using state_type = SE2d;
@@ -752,6 +785,22 @@ class Amcl {
     field_.reset();
   }
 
+  /// update_map with a map that other filters read as well (mcl_use_shared_map): nothing is built or uploaded, and the filter's results
+  /// are those of update_map with the same grid, bit for bit.  \throw std::runtime_error if the map was built for another device or
+  /// sensor model (the filter is unchanged).
+  void use_map(const SharedMap& map) {
+    const mcl_shared_map_info info = map.info();
+    check(mcl_use_shared_map(ctx_, map.native_handle()));
+    have_pending_ = false;  // (a map given now replaces one that was still on its way)
+    width_ = info.width;
+    height_ = info.height;
+    resolution_ = info.resolution;
+    std::int32_t has = 0;
+    check(mcl_has_likelihood_field(ctx_, &has));
+    has_field_ = has != 0;
+    field_.reset();
+  }
+
   /// Extension (mcl_set_map_async): the new map's likelihood field is built on a worker thread - the reference's update_map blocks the
   /// caller for the build, seconds at 16 M cells - while the filter keeps running on the map it has; the swap happens at the start of the
   /// first update() after the build is done, or in map_commit().  `map` is copied before the call returns.
@@ -982,6 +1031,7 @@ class Amcl {
   mcl_update_info last_info_{};
 
   friend class AmclBatch;
+  friend class SharedMap;
   /// A member of an AmclBatch: bound to a context the batch owns (mcl_destroy does nothing on it).
   struct Adopted {};
   Amcl(Adopted, mcl_ctx* ctx, const AmclParams& params) : ctx_(ctx), max_particles_(params.max_particles) {}
@@ -1068,6 +1118,12 @@ class AmclBatch {
     return out;
   }
 
+  /// Every member, or member `index`, reads the shared map from now on (Amcl::use_map): a fleet on one building's map holds it once.
+  void use_map(const SharedMap& map) {
+    for (Amcl& m : members_) m.use_map(map);
+  }
+  void use_map(std::size_t index, const SharedMap& map) { members_.at(index).use_map(map); }
+
   [[nodiscard]] const std::vector<mcl_update_info>& last_infos() const { return infos_; }
   [[nodiscard]] const std::vector<mcl_status>& statuses() const { return statuses_; }
   /// mcl_set_option on every member, e.g. batch_cluster_fused (default 1; 0: the member's cluster-based estimate through its own kernels
@@ -1101,6 +1157,15 @@ class AmclBatch {
   std::vector<mcl_update_info> infos_;
   std::vector<mcl_status> statuses_;
 };
+
+inline SharedMap::SharedMap(const OccupancyGridView& map, const SensorModelParam& sensor, int device, bool device_field_build) {
+  if (std::holds_alternative<NDTModelParam2d>(sensor)) throw std::invalid_argument("beluga_amd::SharedMap: an occupancy-grid sensor model");
+  const mcl_config cfg = Amcl::make_config(StationaryModelParam{}, sensor, AmclParams{}, 0, device, Shard{});
+  const std::int8_t traits[3] = {map.free_value, map.unknown_value, map.occupied_value};
+  const mcl_status st = mcl_shared_map_create(&cfg, map.cells, map.width, map.height, map.resolution, map.origin.data(), traits,
+                                              device_field_build ? 1 : 0, &map_);
+  if (st != MCL_OK) throw std::runtime_error(std::string("beluga_amd::SharedMap: ") + mcl_shared_map_last_error(nullptr));
+}
 
 }  // namespace beluga_amd
 

@@ -127,6 +127,9 @@ class Amcl {
     map_ = std::move(map);
     filter_.update_map(OccupancyGridView::from(map_));
   }
+  /// Extension: a map that other filters read as well (beluga_amd::SharedMap), built for this filter's sensor model.  The grid the
+  /// filter was constructed with stays in map_ but is no longer what the filter localises on.
+  void update_map(const SharedMap& map) { filter_.use_map(map); }
 
   /// Update particles using laser scan data (:227-228, beluga_ros/src/amcl.cpp:54-63): the scan's points in cartesian
   /// coordinates, moved into the base frame with the scan's origin (an SE3: `origin() * Vector3d{x, y, 0}`).

@@ -476,6 +476,45 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
 mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* value);
 const char* mcl_batch_last_error(const mcl_batch* batch); /* batch may be NULL: error of the last failed mcl_batch_create */
 
+/* ---- Shared maps: one uploaded map, many filters ------------------------------------------------------------------------------
+ * A fleet on one building's map needs that map on the device once.  mcl_shared_map_create builds, for the device, sensor_kind and lf
+ * of `cfg`, everything mcl_set_map would build for a context made from that config - the occupancy, the free-cell list, and for the
+ * likelihood-field kinds the field (field_build 0: the reference's wavefront on the host, 1: the exact distance transform on the
+ * device), its pz^3 table, the palette and the far-tile bitmaps; for the beam model the packed occupancy - on a stream of its own,
+ * synchronised before it returns.  It touches no context, so it may run on any thread while filters update.  NDT, landmark and bearing
+ * kinds have maps of their own: MCL_ERR_UNSUPPORTED.  A shared map never changes.
+ *
+ * mcl_use_shared_map stands for update_map on the context, wherever mcl_set_map is allowed (a batch member between two batch updates
+ * included): it leaves the context as mcl_set_map with the same grid leaves it - a pending mcl_set_map_async map is dropped - except
+ * that the context owns nothing of the map.  Every result of an attached context equals, bit for bit, that of a context given the same
+ * grid through mcl_set_map.  It is accepted if the map is on the context's device and was built for its sensor family: the beam model
+ * for a beam context; for the likelihood-field kinds the same sensor_kind and an mcl_lf_params equal field for field.  Otherwise
+ * MCL_ERR_INVALID_ARGUMENT, mcl_last_error names the mismatch, and the context is unchanged.  A shared map holds every table a
+ * private one holds, so no option of an attached context is refused.
+ *
+ * While attached, every read and every update entry point works as before; mcl_set_likelihood_field answers MCL_ERR_UNSUPPORTED and
+ * changes nothing; mcl_set_map / mcl_set_map_async (at its swap) detach the context and give it a map of its own.
+ * mcl_shared_map_release gives up the caller's reference only: the map lives until the last context that reads it has left it or is
+ * destroyed.  Thread rules: create, release and get_info from any thread; mcl_use_shared_map from the thread that drives the context.
+ *
+ * mcl_shared_map_info: device_bytes / host_bytes = what the map holds; users = contexts attached now.  Counters of a context
+ * (mcl_get_counter): map_device_bytes = device bytes the context itself owns for its map (0 while attached), map_shared = 0 / 1. */
+typedef struct mcl_shared_map mcl_shared_map;
+typedef struct mcl_shared_map_info {
+  uint32_t width, height;
+  double resolution;
+  int32_t sensor_kind;
+  int32_t device_id;
+  uint64_t device_bytes, host_bytes;
+  uint32_t users;
+} mcl_shared_map_info;
+mcl_status mcl_shared_map_create(const mcl_config* cfg, const int8_t* cells, uint32_t width, uint32_t height, double resolution,
+                                 const double origin[4], const int8_t value_traits[3], int32_t field_build, mcl_shared_map** out);
+void mcl_shared_map_release(mcl_shared_map* map);
+mcl_status mcl_shared_map_get_info(const mcl_shared_map* map, mcl_shared_map_info* info);
+const char* mcl_shared_map_last_error(const mcl_shared_map* map); /* map may be NULL: error of the last failed mcl_shared_map_create */
+mcl_status mcl_use_shared_map(mcl_ctx* ctx, mcl_shared_map* map);
+
 /* ---- Particle shards across the GPUs of one node (one context per GPU, one process or thread per context) -------------
  * The logical filter's particles are split into contiguous shards of the global index space (mcl_config.shard_offset /
  * shard_capacity); the map is replicated and every rank passes the same control action and scan to mcl_update.  With a
