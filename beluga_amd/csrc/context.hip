@@ -1242,19 +1242,20 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       KeyFrame ahead_frame{};
       const bool order_keys = noise_in_draw && ctx->done_armed && ctx->tuning.order_ahead != 0 && max_p < (1ull << 32) && ctx->wants_ordering() &&
                               ctx->predict_key_frame(&ctx->last_sampler, &ahead_frame, 2);
-      launch_resample_draw_and_estimate(ctx->stream, ctx->cur(), ctx->cdf_tree(), d_total, ctx->other(), ra, gv, fc, hp,
+      const SortScratch ahead_sort = order_keys ? ctx->sort_scratch() : SortScratch{};
+      const OrderAheadDone order_done = launch_resample_draw_and_estimate(ctx->stream, ctx->cur(), ctx->cdf_tree(), d_total, ctx->other(), ra, gv, fc, hp,
                                         ctx->facts.pivot()[0], ctx->facts.pivot()[1], ctx->d_est_partials.ptr, ctx->d_scalars.ptr + kSlotEstimate,
                                         ctx->hd_scalars + kSlotEstimate, ctx->done_armed ? &done : nullptr,
                                         ((ctx->tuning.draw_fold == 2 || (ctx->tuning.draw_fold == 1 && max_p <= 65536)) && ctx->d_scan_state.ptr)
                                             ? reinterpret_cast<unsigned int*>(ctx->d_scan_state.ptr + 4)
                                             : nullptr,
                                         noise_in_draw ? ctx->d_noise.ptr : nullptr, max_p, ctx->cfg.shard_offset, step + 1,
-                                        order_keys ? ctx->sort_scratch().keys : nullptr, &ctx->last_sampler, &ahead_frame);
+                                        order_keys ? ahead_sort.keys : nullptr, &ctx->last_sampler, &ahead_frame,
+                                        (order_keys && ctx->tuning.draw_key_hist) ? &ahead_sort : nullptr, ctx->tuning.rows_merged != 0);
       if (noise_ahead) launch_noise_ahead(ctx->stream, ctx->cfg.seed, step + 1, ctx->cfg.shard_offset, max_p, ctx->d_noise.ptr);
       if (noise_ahead || noise_in_draw) ctx->facts.noise_ahead_recorded(step + 1, max_p, ctx->cfg.shard_offset, ctx->cfg.seed);
       if (order_keys) {
-        const SortScratch sort = ctx->sort_scratch();
-        launch_order_ahead(ctx->stream, max_p, &sort);
+        launch_order_ahead(ctx->stream, max_p, &ahead_sort, order_done);
         ctx->facts.order_ahead_recorded(step + 1, max_p, ctx->key_layout());
         ctx->order_sampler = ctx->last_sampler;
       }
@@ -2336,7 +2337,7 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
     }
     // Environment defaults of the per-context switches (mcl_set_option changes them at run time).
     for (const char* name : {"lf_variant", "lf_fast", "lf_table", "lf_patch", "lf_dispersed", "lf_far_tiles", "key_layout", "lf_loose_below", "lf_small_particles", "device_policy",
-                             "sort_min_particles", "beam_sort_min_particles", "field_build", "key_curve", "key_warp", "key_bits_xy", "lf_margin", "lf_split", "lf_queue_grid", "shard_pad_permille", "lf_queue", "lf_ends_first", "beam_free_ahead", "beam_sectors", "lf_weight_sums", "beam_table", "cycle_spin", "scan_fused", "draw_fold", "lf_unit_weights", "small_fused", "norm_store", "noise_ahead", "order_ahead", "lf_far_beams_per_wave", "batch_cluster_fused"}) {
+                             "sort_min_particles", "beam_sort_min_particles", "field_build", "key_curve", "key_warp", "key_bits_xy", "lf_margin", "lf_split", "lf_queue_grid", "shard_pad_permille", "lf_queue", "lf_ends_first", "beam_free_ahead", "beam_sectors", "lf_weight_sums", "beam_table", "cycle_spin", "scan_fused", "draw_fold", "lf_unit_weights", "small_fused", "norm_store", "noise_ahead", "order_ahead", "lf_far_beams_per_wave", "batch_cluster_fused", "draw_key_hist", "rows_merged"}) {
       std::string env = "BELUGA_MCL_";
       for (const char* c = name; *c; ++c) env += static_cast<char>(std::toupper(static_cast<unsigned char>(*c)));
       if (const char* v = std::getenv(env.c_str())) {
@@ -3835,6 +3836,8 @@ mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value) {
   else if (key == "batch_cluster_fused") t.batch_cluster_fused = value ? 1 : 0;
   else if (key == "norm_store") t.norm_store = value ? 1 : 0;
   else if (key == "order_ahead") t.order_ahead = value ? 1 : 0;
+  else if (key == "draw_key_hist") t.draw_key_hist = value ? 1 : 0;
+  else if (key == "rows_merged") t.rows_merged = value ? 1 : 0;
   else if (key == "noise_ahead") t.noise_ahead = static_cast<int>(std::clamp<int64_t>(value, 0, 2));
   else if (key == "lf_split") t.lf_split = static_cast<int>(value & 3);  // 1: side by side only, 2: stacked only, 3: both
   else if (key == "sort_min_particles") t.sort_min_particles = static_cast<int>(std::clamp<int64_t>(value, 0, 1ll << 30));

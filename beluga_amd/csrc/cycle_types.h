@@ -97,6 +97,20 @@ struct Tuning {
   int order_ahead = 1;              // with noise_ahead = 1: the NEXT cycle's spatial order is computed behind a cycle's last kernel, while the host is
                                     // away, from the predicted control action (the one of the cycle that ends); the next cycle uses it if the action it
                                     // gets is close to the prediction, else it orders by the real poses as before.  Only locality depends on the order.
+  int draw_key_hist = 1;            // with order_ahead: the draw kernel counts the high digit of every predicted key it stores (an LDS counter per
+                                    // digit and workgroup) and stores its 1024 counts side by side - a half column of the ordering's table, a draw
+                                    // workgroup covering half a chunk - which k_row_scan adds in pairs on its way: no k_key_hist pass over the keys.
+                                    // 0 = k_key_hist.  Measured at 1M: the draw 62.0 -> 62.9 us, k_key_hist's 7.4 us gone; alone (its row scan a
+                                    // launch of its own: unmeasured) above every parent run only once the cloud has settled, + 0.9 %.  Digit-major
+                                    // half columns - a 4-byte store per line - cost the draw 7.4 us, all that k_key_hist took.  Integer counts
+                                    // only: bit-identical.
+  int rows_merged = 1;              // with draw_key_hist: the nine workgroups of k_final_rows and the workgroups of k_row_scan - both read the draw's
+                                    // output alone, neither the other's - in ONE launch, roles by blockIdx.x (k_final_rows_row_scan; nothing is handed
+                                    // over inside it).  0 = two launches.  Measured at 1M: 9.8 us against k_final_rows' 5.2 + k_row_scan's 6.1 (from
+                                    // whole columns).  Both options against the parent, three alternating runs of 65 cycles: 1924 against 1889 and
+                                    // 1941 against 1911 cycles/s in the two settled windows (every run above every parent run), 1774 against 1744
+                                    // in the driver's window (above the parent in every round, but inside the parent's own spread of 30: no gain
+                                    // shown there).  Bit-identical.
   int norm_store = 0;               // fixed-size cycle that resamples at once: 0 = k_normalize leaves the chunk sums of the normalised weights
                                     // but does not store them - the CDF kernel divides again (same division, same bits), nothing else reads them;
                                     // 1 = stored

@@ -296,8 +296,14 @@ void launch_pull_scan(hipStream_t st, const double* scan_src, double* scan_dst, 
 void launch_order_particles(hipStream_t st, Particles p, uint64_t n, const SortScratch* sort, const KeyFrame* frame, bool keys_ready,
                             uint32_t layout = 0);
 // The same order a cycle AHEAD: sort->keys hold the keys the draw kernel predicted for the next cycle (launch_resample_draw_and_estimate,
-// keys_ahead) - their block histograms and the three ordering kernels -> sort->perm.
-void launch_order_ahead(hipStream_t st, uint64_t n, const SortScratch* sort);
+// keys_ahead) - their block histograms and the three ordering kernels -> sort->perm.  `done`: how much of that the draw's launcher has
+// enqueued already (its return value); the rest follows here.
+enum OrderAheadDone : int {
+  kOrderAheadKeys = 0,         // the keys alone: k_key_hist, k_row_scan and the two sorting kernels follow
+  kOrderAheadHalfColumns = 1,  // the draw kernel counted its keys (half-column histograms in the words of sort->keyidx): from k_row_scan on
+  kOrderAheadTable = 2         // and the row scan ran in k_final_rows' launch: the two sorting kernels follow
+};
+void launch_order_ahead(hipStream_t st, uint64_t n, const SortScratch* sort, OrderAheadDone done = kOrderAheadKeys);
 // K2  actions/reweight.hpp:53-60 + likelihood_field_model.hpp:68-91
 // The LDS-patch kernel's running totals and scratch (LfReweightArgs::stats).
 struct PatchStats {
@@ -546,12 +552,17 @@ void launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGri
 // K6: one thread per candidate (views/sample.hpp:102,133-135; random_intersperse.hpp:90-115; particle_traits.hpp:105).
 void launch_resample_draw(hipStream_t st, Particles src, CdfTree cdf, const double* d_total, Particles dst,
                           ResampleArgs a, GridView g, FreeCells fc, HashParams hp, unsigned long long* d_hashes);
-void launch_resample_draw_and_estimate(hipStream_t st, Particles src, CdfTree cdf, const double* d_total, Particles dst, ResampleArgs a,
-                                       GridView g, FreeCells fc, HashParams hp, double pivot_x, double pivot_y, double* d_partials,
-                                       double* d_sums, double* host_mirror, const Completion* done = nullptr,
-                                       unsigned int* fold_ticket = nullptr, double* normals_ahead = nullptr, uint64_t normals_stride = 0,
-                                       uint64_t normals_index_offset = 0, uint32_t normals_step = 0, uint32_t* keys_ahead = nullptr,
-                                       const DiffDriveSampler* predicted = nullptr, const KeyFrame* frame_ahead = nullptr);
+// hist_sort (with keys_ahead = hist_sort->keys; Tuning::draw_key_hist): the draw kernel also counts the high digits of the keys it stores, the
+// ordering's first-pass histograms; rows_merged (Tuning::rows_merged): the row scan over them runs in the launch of k_final_rows.  Returns how
+// far the ordering of the keys got (launch_order_ahead's `done`).
+OrderAheadDone launch_resample_draw_and_estimate(hipStream_t st, Particles src, CdfTree cdf, const double* d_total, Particles dst, ResampleArgs a,
+                                                 GridView g, FreeCells fc, HashParams hp, double pivot_x, double pivot_y, double* d_partials,
+                                                 double* d_sums, double* host_mirror, const Completion* done = nullptr,
+                                                 unsigned int* fold_ticket = nullptr, double* normals_ahead = nullptr,
+                                                 uint64_t normals_stride = 0, uint64_t normals_index_offset = 0, uint32_t normals_step = 0,
+                                                 uint32_t* keys_ahead = nullptr, const DiffDriveSampler* predicted = nullptr,
+                                                 const KeyFrame* frame_ahead = nullptr, const SortScratch* hist_sort = nullptr,
+                                                 bool rows_merged = false);
 // Sharded variant: targets given, no RNG (mcl_gather_by_cdf).
 // Sharded resampling helpers (mcl_resample_targets / mcl_commit_resampled).
 void launch_resample_targets(hipStream_t st, uint64_t seed, uint32_t step, double p, double total, uint64_t first_slot,

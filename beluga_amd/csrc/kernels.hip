@@ -1831,13 +1831,26 @@ __global__ __launch_bounds__(kWide) void k_key_hist(const uint32_t* __restrict__
 // totals[d] = sum of row d of the [digit][block] table; one wave per digit.
 // Row d of the table (block histograms of digit d) becomes its exclusive scan; totals[d] = the row's sum.  The scatter
 // kernels add the sum of all smaller digits themselves (digit_bases): one launch less per pass.
-__global__ __launch_bounds__(kBlock) void k_row_scan(uint32_t* __restrict__ table, uint32_t nblocks, uint32_t* __restrict__ totals) {
-  const uint32_t d = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+// halves (optional): the block histograms come as HALF columns, column-major - [half column][digit], half column 2 b + h the counts of half h
+// of chunk b, `nhalves` of them written (the draw kernel's, a workgroup per kChunk / 2 output slots, each storing its kSortDigits counters
+// side by side: DrawNormals::half_hist) - and a chunk's count is the sum of its two; the table this leaves is the one it leaves from whole
+// columns, integer for integer.
+__device__ __forceinline__ void row_scan_rows(uint32_t block, uint32_t* __restrict__ table, uint32_t nblocks, uint32_t* __restrict__ totals,
+                                              const uint32_t* __restrict__ halves, uint32_t nhalves) {
+  const uint32_t d = block * (kBlock / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   uint32_t* row = table + static_cast<size_t>(d) * nblocks;
   uint32_t carry = 0;
   for (uint32_t start = 0; start < nblocks; start += 64) {
     const uint32_t b = start + lane;
-    const uint32_t v = b < nblocks ? row[b] : 0u;
+    uint32_t v = 0u;
+    if (b < nblocks) {
+      if (halves) {
+        const uint32_t* first = halves + static_cast<size_t>(2u * b) * kSortDigits + d;
+        v = (2u * b < nhalves ? first[0] : 0u) + (2u * b + 1u < nhalves ? first[kSortDigits] : 0u);
+      } else {
+        v = row[b];
+      }
+    }
     uint32_t incl = v;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -1848,6 +1861,10 @@ __global__ __launch_bounds__(kBlock) void k_row_scan(uint32_t* __restrict__ tabl
     carry += __shfl(incl, 63);
   }
   if (lane == 0) totals[d] = carry;
+}
+__global__ __launch_bounds__(kBlock) void k_row_scan(uint32_t* __restrict__ table, uint32_t nblocks, uint32_t* __restrict__ totals,
+                                                     const uint32_t* __restrict__ halves, uint32_t nhalves) {
+  row_scan_rows(blockIdx.x, table, nblocks, totals, halves, nhalves);
 }
 // s_base[d] = sum of totals[q], q < d, for the kSortDigits digits; T threads, every one of them.
 template <int T>
@@ -2226,10 +2243,9 @@ __device__ __forceinline__ double row_total(const double* __restrict__ row, uint
 }
 // done (optional, Completion): the launch's last workgroup to finish stores done.seq to a word of mapped host memory, behind
 // everything the launch mirrored - the host can wait for that word instead of the stream's completion signal.
-__global__ __launch_bounds__(kBlock) void k_final_rows(const double* __restrict__ partials, uint32_t count, uint32_t stride,
-                                                       double* __restrict__ out, double* __restrict__ host_mirror, Completion done) {
-  __shared__ double scratch[kBlock / 64];
-  const uint32_t k = blockIdx.x;
+// Row k of `rows` (one workgroup each).
+__device__ __forceinline__ void final_row(uint32_t k, uint32_t rows, const double* __restrict__ partials, uint32_t count, uint32_t stride,
+                                          double* __restrict__ out, double* __restrict__ host_mirror, const Completion& done, double* scratch) {
   const double total = row_total(partials + static_cast<size_t>(k) * stride, count, scratch);
   if (threadIdx.x == 0) {
     out[k] = total;
@@ -2237,12 +2253,29 @@ __global__ __launch_bounds__(kBlock) void k_final_rows(const double* __restrict_
     if (done.host_flag) {
       __threadfence_system();  // this workgroup's mirrored value is visible to the host before its ticket counts
       const unsigned long long ticket = atomicAdd(done.d_ticket, 1ull);
-      if (ticket % gridDim.x == gridDim.x - 1) {
+      if (ticket % rows == rows - 1) {
         __threadfence_system();
         __hip_atomic_store(done.host_flag, done.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
   }
+}
+__global__ __launch_bounds__(kBlock) void k_final_rows(const double* __restrict__ partials, uint32_t count, uint32_t stride,
+                                                       double* __restrict__ out, double* __restrict__ host_mirror, Completion done) {
+  __shared__ double scratch[kBlock / 64];
+  final_row(blockIdx.x, gridDim.x, partials, count, stride, out, host_mirror, done, scratch);
+}
+// k_final_rows (workgroups [0, rows): the completion word counts those alone) and k_row_scan over half columns (the workgroups behind them) in
+// one grid: both read what the draw kernel left and neither reads the other's output, so nothing is handed over inside the launch.
+__global__ __launch_bounds__(kBlock) void k_final_rows_row_scan(uint32_t rows, const double* __restrict__ partials, uint32_t count, uint32_t stride,
+                                                                double* __restrict__ out, double* __restrict__ host_mirror, Completion done,
+                                                                uint32_t* __restrict__ table, uint32_t nblocks, uint32_t* __restrict__ totals,
+                                                                const uint32_t* __restrict__ halves, uint32_t nhalves) {
+  __shared__ double scratch[kBlock / 64];
+  if (blockIdx.x < rows)  // (uniform)
+    final_row(blockIdx.x, rows, partials, count, stride, out, host_mirror, done, scratch);
+  else
+    row_scan_rows(blockIdx.x - rows, table, nblocks, totals, halves, nhalves);
 }
 
 // sum_partials != nullptr: the factor is the total of these chunk sums, added up by every workgroup exactly as
@@ -2894,7 +2927,13 @@ struct DrawNormals {
   uint32_t* keys{nullptr};
   DiffDriveSampler predicted{};
   KeyFrame frame{};
+  // Option draw_key_hist (with keys, out_offset 0): the workgroup counts the high digit of the keys it stores - the ordering's first-pass
+  // histogram of its kChunk / 2 slots - and leaves its kSortDigits counts side by side as half column blockIdx.x of [half columns][kSortDigits]
+  // (k_row_scan's `halves`; sixteen coalesced stores - digit-major half columns, a 4-byte store per line, cost the draw what k_key_hist took):
+  // no pass over the keys behind the draw.  An LDS counter increment per output, in the shadow of the fabric like the normals.
+  uint32_t* half_hist{nullptr};
 };
+static_assert(kDrawBlock == static_cast<int>(kSortDigits) && kChunk == 2 * kDrawBlock, "a thread per digit counter; two draw workgroups per chunk");
 // Where a pose goes under the motion model with the given normals, to first order and in single precision: (c, s, x, y).
 __device__ __forceinline__ double4 predicted_pose_f32(const Pose2& p, const DiffDriveSampler& m, float z0, float z1, float z2) {
   const float c = static_cast<float>(p.r.c), s = static_cast<float>(p.r.s);
@@ -2933,6 +2972,8 @@ __global__ __launch_bounds__(kDrawBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* staged = reinterpret_cast<double*>(smem);
   __shared__ double scratch[kEstimate ? (kDrawBlock / 64) * 9 : 1];
+  __shared__ uint32_t key_hist[kEstimate ? kSortDigits : 1];
+  if (kEstimate && ahead.half_hist) key_hist[threadIdx.x] = 0u;  // (uniform)
   if (first_staged < cdf.depth) {
     const double* from = cdf.levels + cdf.offset[first_staged];
     for (uint32_t k = threadIdx.x; k < staged_doubles; k += kDrawBlock) staged[k] = from[k];
@@ -2967,9 +3008,12 @@ __global__ __launch_bounds__(kDrawBlock) __attribute__((amdgpu_waves_per_eu(8, 8
       ahead.normals[o] = z.x;
       ahead.normals[ahead.stride + o] = z.y;
       ahead.normals[2 * ahead.stride + o] = z.z;
-      if (ahead.keys)  // (uniform)
-        ahead.keys[o] = order_key(predicted_pose_f32(s, ahead.predicted, static_cast<float>(z.x), static_cast<float>(z.y), static_cast<float>(z.z)),
-                                  ahead.frame);
+      if (ahead.keys) {  // (uniform)
+        const uint32_t key = order_key(predicted_pose_f32(s, ahead.predicted, static_cast<float>(z.x), static_cast<float>(z.y), static_cast<float>(z.z)),
+                                       ahead.frame);
+        ahead.keys[o] = key;
+        if (kEstimate && ahead.half_hist) atomicAdd(&key_hist[key >> kDigitBits], 1u);  // (uniform)
+      }
     }
     if (kEstimate) {
       const double dx = s.x - pivot_x, dy = s.y - pivot_y;
@@ -2986,6 +3030,8 @@ __global__ __launch_bounds__(kDrawBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   }
   if (kEstimate) {
     block_reduce<9, kDrawBlock>(v, scratch);
+    if (ahead.half_hist)  // (uniform; behind the reduction's barriers: every wave's increments have landed)
+      ahead.half_hist[static_cast<size_t>(blockIdx.x) * kSortDigits + threadIdx.x] = key_hist[threadIdx.x];
     if (fold.ticket == nullptr) {
       if (threadIdx.x == 0) {
 #pragma unroll
@@ -4348,19 +4394,30 @@ void launch_order_particles(hipStream_t st, Particles p, uint64_t n, const SortS
                        sort->table, nblocks);
   }
   const dim3 rows(kSortDigits / (kBlock / 64));
-  hipLaunchKernelGGL(k_row_scan, rows, dim3(kBlock), 0, st, sort->table, nblocks, sort->totals);
+  hipLaunchKernelGGL(k_row_scan, rows, dim3(kBlock), 0, st, sort->table, nblocks, sort->totals, static_cast<const uint32_t*>(nullptr), 0u);
   hipLaunchKernelGGL(k_sort_scatter_high, dim3(nblocks), dim3(kStable), 0, st, sort->keys, n, sort->table, nblocks, sort->totals,
                      sort->keyidx, sort->totals + kSortDigits);
   hipLaunchKernelGGL(k_sort_buckets, dim3(kSortDigits), dim3(kStable), 0, st, sort->keyidx, sort->totals, sort->totals + kSortDigits,
                      sort->perm);
 }
 
-void launch_order_ahead(hipStream_t st, uint64_t n, const SortScratch* sort) {
+namespace {
+// The draw kernel's half-column histograms live where the ordering's first pass writes only BEHIND the row scan that consumes them: keyidx.
+uint32_t* order_half_columns(const SortScratch* sort) { return reinterpret_cast<uint32_t*>(sort->keyidx); }
+uint32_t draw_workgroups(uint64_t n) { return static_cast<uint32_t>((n + kDrawBlock - 1) / kDrawBlock); }
+}  // namespace
+
+void launch_order_ahead(hipStream_t st, uint64_t n, const SortScratch* sort, OrderAheadDone done) {
   if (n == 0 || !sort || n >= (1ull << 32)) return;
   const uint32_t nblocks = num_chunks(n);
-  hipLaunchKernelGGL(k_key_hist, dim3(nblocks), dim3(kWide), 0, st, sort->keys, n, sort->table, nblocks);
   const dim3 rows(kSortDigits / (kBlock / 64));
-  hipLaunchKernelGGL(k_row_scan, rows, dim3(kBlock), 0, st, sort->table, nblocks, sort->totals);
+  if (done == kOrderAheadKeys) {
+    hipLaunchKernelGGL(k_key_hist, dim3(nblocks), dim3(kWide), 0, st, sort->keys, n, sort->table, nblocks);
+    hipLaunchKernelGGL(k_row_scan, rows, dim3(kBlock), 0, st, sort->table, nblocks, sort->totals, static_cast<const uint32_t*>(nullptr), 0u);
+  } else if (done == kOrderAheadHalfColumns) {
+    hipLaunchKernelGGL(k_row_scan, rows, dim3(kBlock), 0, st, sort->table, nblocks, sort->totals,
+                       static_cast<const uint32_t*>(order_half_columns(sort)), draw_workgroups(n));
+  }
   hipLaunchKernelGGL(k_sort_scatter_high, dim3(nblocks), dim3(kStable), 0, st, sort->keys, n, sort->table, nblocks, sort->totals,
                      sort->keyidx, sort->totals + kSortDigits);
   hipLaunchKernelGGL(k_sort_buckets, dim3(kSortDigits), dim3(kStable), 0, st, sort->keyidx, sort->totals, sort->totals + kSortDigits,
@@ -4675,15 +4732,22 @@ void launch_resample_draw(hipStream_t st, Particles src, CdfTree cdf, const doub
 }
 
 // The draw plus the estimate sums of the set it produces: d_partials needs 9 * ceil(count / 1024) doubles.
-void launch_resample_draw_and_estimate(hipStream_t st, Particles src, CdfTree cdf, const double* d_total, Particles dst, ResampleArgs a,
-                                       GridView g, FreeCells fc, HashParams hp, double pivot_x, double pivot_y, double* d_partials,
-                                       double* d_sums, double* host_mirror, const Completion* done, unsigned int* fold_ticket,
-                                       double* normals_ahead, uint64_t normals_stride, uint64_t normals_index_offset, uint32_t normals_step,
-                                       uint32_t* keys_ahead, const DiffDriveSampler* predicted, const KeyFrame* frame_ahead) {
+OrderAheadDone launch_resample_draw_and_estimate(hipStream_t st, Particles src, CdfTree cdf, const double* d_total, Particles dst, ResampleArgs a,
+                                                 GridView g, FreeCells fc, HashParams hp, double pivot_x, double pivot_y, double* d_partials,
+                                                 double* d_sums, double* host_mirror, const Completion* done, unsigned int* fold_ticket,
+                                                 double* normals_ahead, uint64_t normals_stride, uint64_t normals_index_offset,
+                                                 uint32_t normals_step, uint32_t* keys_ahead, const DiffDriveSampler* predicted,
+                                                 const KeyFrame* frame_ahead, const SortScratch* hist_sort, bool rows_merged) {
   int first;
   uint32_t doubles;
   draw_staging(cdf, first, doubles);
-  const unsigned blocks = static_cast<unsigned>((a.count + kDrawBlock - 1) / kDrawBlock);
+  const unsigned blocks = draw_workgroups(a.count);
+  uint32_t* const keys = (normals_ahead && predicted && frame_ahead) ? keys_ahead : nullptr;
+  // The draw counts its keys' high digits where its slots are the set's (slot = particle, from 0) and the half columns fit the words of keyidx
+  const uint32_t nblocks = num_chunks(a.count);
+  const bool count_keys = keys && hist_sort && keys == hist_sort->keys && a.out_offset == 0 && a.count < (1ull << 32) &&
+                          static_cast<uint64_t>(kSortDigits) * 2u * nblocks <= 2u * a.count;
+  OrderAheadDone order = kOrderAheadKeys;
   // fold_ticket: the sums are added up by the draw's own last workgroup (k_resample_draw, DrawFold) while one workgroup reads them back in
   // a few loads per thread (4096 workgroups = 4M particles: 36 loads); beyond that, and without a ticket word, k_final_rows follows.
   const bool fold = fold_ticket != nullptr && blocks > 0 && blocks <= 4096u;
@@ -4692,12 +4756,22 @@ void launch_resample_draw_and_estimate(hipStream_t st, Particles src, CdfTree cd
     if (fold) f = DrawFold{fold_ticket, d_sums, host_mirror, done ? *done : Completion{}};
     hipLaunchKernelGGL(k_resample_draw<true>, dim3(blocks), dim3(kDrawBlock), doubles * sizeof(double), st, src, cdf, d_total, dst, a, g,
                        fc, hp, static_cast<unsigned long long*>(nullptr), pivot_x, pivot_y, d_partials, blocks, first, doubles, f,
-                       DrawNormals{normals_ahead, normals_stride, normals_index_offset, normals_step,
-                                   (normals_ahead && predicted && frame_ahead) ? keys_ahead : nullptr,
-                                   predicted ? *predicted : DiffDriveSampler{}, frame_ahead ? *frame_ahead : KeyFrame{}});
+                       DrawNormals{normals_ahead, normals_stride, normals_index_offset, normals_step, keys,
+                                   predicted ? *predicted : DiffDriveSampler{}, frame_ahead ? *frame_ahead : KeyFrame{},
+                                   count_keys ? order_half_columns(hist_sort) : nullptr});
+    if (count_keys) order = kOrderAheadHalfColumns;
   }
-  if (!fold)
-    hipLaunchKernelGGL(k_final_rows, dim3(9), dim3(kBlock), 0, st, d_partials, blocks, blocks, d_sums, host_mirror, done ? *done : Completion{});
+  if (!fold) {
+    if (order == kOrderAheadHalfColumns && rows_merged) {
+      hipLaunchKernelGGL(k_final_rows_row_scan, dim3(9 + kSortDigits / (kBlock / 64)), dim3(kBlock), 0, st, 9u, d_partials, blocks, blocks, d_sums,
+                         host_mirror, done ? *done : Completion{}, hist_sort->table, nblocks, hist_sort->totals,
+                         static_cast<const uint32_t*>(order_half_columns(hist_sort)), blocks);
+      order = kOrderAheadTable;
+    } else {
+      hipLaunchKernelGGL(k_final_rows, dim3(9), dim3(kBlock), 0, st, d_partials, blocks, blocks, d_sums, host_mirror, done ? *done : Completion{});
+    }
+  }
+  return order;
 }
 
 void launch_resample_targets(hipStream_t st, uint64_t seed, uint32_t step, double p, double total, uint64_t first_slot,

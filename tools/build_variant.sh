@@ -20,7 +20,8 @@ if [ -n "$tree" ]; then
   mkdir -p $src
   for f in kernels.hip context.hip kernels.h se2.h rng.h map_build.h map_build.cpp cluster_host.h cluster_host.cpp; do git -C $root show $rev:beluga_amd/csrc/$f > $src/$f; done
   # (translation units and headers that older revisions do not have)
-  for f in beam_kernels.hip device_common.hpp sensor_records.h ndt_host.h ndt_host.cpp landmark_host.h landmark_host.cpp scan_host.cpp set_facts.h cycle_types.h cycle_host.h cycle_host.cpp; do
+  for f in beam_kernels.hip device_common.hpp sensor_records.h ndt_host.h ndt_host.cpp landmark_host.h landmark_host.cpp scan_host.cpp set_facts.h cycle_types.h cycle_host.h cycle_host.cpp \
+           ndt_kernels.hip ndt_build_kernels.hip landmark_kernels.hip batch_host.h batch_host.cpp map_store.h map_store_host.h map_store_host.cpp; do
     git -C $root show $rev:beluga_amd/csrc/$f > $src/$f 2>/dev/null || rm -f $src/$f
   done
   git -C $root show $rev:include/beluga_mcl.h > $src/beluga_mcl.h
@@ -34,8 +35,11 @@ if [ -n "$tree" ]; then
   /opt/rocm/bin/hipcc $common -c $src/map_build.cpp -o $out/map_build.o
   /opt/rocm/bin/hipcc $common -c $src/cluster_host.cpp -o $out/cluster_host.o
   host=""   # (the sensor models' and the cycle's host passes are translation units of their own; older revisions have them inside context.hip)
-  for f in ndt_host landmark_host scan_host cycle_host; do
+  for f in ndt_host landmark_host scan_host cycle_host batch_host map_store_host; do
     if [ -f $src/$f.cpp ]; then /opt/rocm/bin/hipcc $common -c $src/$f.cpp -o $out/$f.o; host="$host $out/$f.o"; fi
+  done
+  for f in ndt_kernels ndt_build_kernels landmark_kernels; do
+    if [ -f $src/$f.hip ]; then /opt/rocm/bin/hipcc $common -x hip -c $src/$f.hip -o $out/$f.o; host="$host $out/$f.o"; fi
   done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libbeluga_mcl.so $out/kernels.o $beam $out/context.o $out/map_build.o $out/cluster_host.o $host
 else
