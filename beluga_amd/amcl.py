@@ -1021,8 +1021,8 @@ class AmclBatch:
             member.set_option(name, value)
 
     def counter(self, name: str) -> int:
-        """cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns
-        (mcl_batch_get_counter)."""
+        """cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns, beam_launches,
+        members_beam_fused (mcl_batch_get_counter)."""
         value = C.c_uint64(0)
         self._check(self._lib.mcl_batch_get_counter(self._batch, name.encode(), C.byref(value)))
         return value.value

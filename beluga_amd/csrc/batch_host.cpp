@@ -11,6 +11,11 @@ bool batch_member_fused(const BatchMemberFacts& m) {
          m.max_particles <= kBatchMaxParticles && m.palette_beams && !m.profiling;
 }
 
+bool batch_beam_member_fused(const BatchBeamFacts& m) {
+  return m.sensor_kind == MCL_SENSOR_BEAM && !m.sharded && m.small_fused && m.beam_fused && m.n >= 1 && m.n <= kBatchMaxParticles &&
+         m.max_particles >= 1 && m.max_particles <= kBatchMaxParticles && m.n < m.beam_sort_min_particles && !m.profiling;
+}
+
 bool batch_cluster_member(const BatchClusterFacts& m) {
   return m.status == MCL_OK && m.estimate_kind == 1 && m.cluster_fused && m.n >= 1 && m.n <= kBatchMaxParticles &&
          cluster_params_ok(m.linear_hash_resolution, m.angular_hash_resolution, m.weight_cap_percentile);
@@ -36,6 +41,17 @@ BatchGrid batch_layout(const uint64_t* n, const uint32_t* lds, uint32_t members,
     g.propagate_blocks += batch_propagate_blocks(n[m]);
     g.reweight_blocks += batch_reweight_blocks(n[m]);
     g.reweight_lds = std::max(g.reweight_lds, lds[m]);
+  }
+  return g;
+}
+
+BatchBeamGrid batch_beam_layout(const uint64_t* n, const uint32_t* B, uint32_t members, uint32_t* first_beam) {
+  BatchBeamGrid g{0, 0};
+  for (uint32_t m = 0; m < members; ++m) {
+    first_beam[m] = g.blocks;
+    const uint32_t blocks = batch_beam_blocks(n[m], B[m]);
+    g.blocks += blocks;
+    if (blocks) g.lds = std::max(g.lds, B[m] * kBatchBeamPointBytes);
   }
   return g;
 }

@@ -1,5 +1,5 @@
 // batch_host.h — the arithmetic of a batch of small filters (mcl_batch_*) that touches no device memory: which members of a cycle share
-// the three launches, where each member's blocks lie in the two gridded launches, how a block finds its member, how much workgroup memory
+// the cycle's launches (likelihood-field and beam-model members, a reweight launch per family), where each member's blocks lie in the gridded launches, how a block finds its member, how much workgroup memory
 // the shared reweight needs, which members share the cluster-based estimate's two launches, and the validation of mcl_batch_create's configs and mcl_batch_update's scan offsets.  context.hip calls
 // them between its launches; batch_member_of is also what the batched kernels run (kernels.hip).  Plain C++17, no HIP.
 #pragma once
@@ -16,6 +16,10 @@ constexpr uint32_t kBatchMaxMembers = 1024;   // mcl_batch_create's count
 constexpr uint64_t kBatchMaxParticles = 4096;  // of a fused member: one workgroup of k_small_tail holds the set (kSmallMax)
 constexpr uint32_t kBatchPropagateBlock = 256;  // particles of a block of k_propagate_small (kBlock)
 constexpr uint32_t kBatchReweightBlock = 4;     // ... of k_reweight_lf_beams with a wave per particle (kBeamsBlock / kWave)
+constexpr uint32_t kBatchBeamThreads = 256;     // threads of a block of k_reweight_beam (kBlock)
+constexpr uint32_t kBatchBeamBlock = 4;         // ... and its particles, a wave each (kBlock / kWave)
+constexpr uint32_t kBatchBeamPointBytes = 16;   // a scan point staged in its workgroup memory (double2)
+constexpr uint32_t kBatchBeamMaxPoints = 4096;  // 64 KB of it: the lone kernel's own limit (reweight_preconditions)
 
 // ---- which members share the launches ------------------------------------------------------------------------------------------------
 // What the predicate reads of a member in the cycle that is being prepared.
@@ -30,6 +34,20 @@ struct BatchMemberFacts {
 };
 // The member's own mcl_update would run exactly k_propagate_small, k_reweight_lf_beams with a wave per particle, k_small_tail.
 bool batch_member_fused(const BatchMemberFacts& m);
+
+// The same for a beam-model member (batch_member_fused answers 0 for it): what k_batch_reweight_beam's members must satisfy.
+struct BatchBeamFacts {
+  int sensor_kind;                   // MCL_SENSOR_*
+  bool sharded;                      // the context is one rank of a sharded filter
+  bool small_fused;                  // option small_fused
+  bool beam_fused;                   // option batch_beam_fused
+  uint64_t n;                        // particles of the live set
+  uint64_t max_particles;            // min(max_particles, capacity)
+  uint64_t beam_sort_min_particles;  // option beam_sort_min_particles: from this size on the member wants the ordering and the ordered kernel
+  bool profiling;                    // stage profiling on
+};
+// The member's own mcl_update would run exactly k_propagate_small, k_reweight_beam (a wave per particle), k_small_tail.
+bool batch_beam_member_fused(const BatchBeamFacts& m);
 
 // ---- which fused members share the cluster-based estimate's two launches ------------------------------------------------------------------
 // What cluster_front checks of cluster parameters before anything is launched.
@@ -66,6 +84,17 @@ struct BatchGrid {
 // n[m], lds[m] (lf_palette_lds of the member's field) for m < members  ->  first_propagate[m], first_reweight[m]: the member's first
 // block in each gridded launch (running sums; a member with n = 0 has no block and is never found), and the grids.
 BatchGrid batch_layout(const uint64_t* n, const uint32_t* lds, uint32_t members, uint32_t* first_propagate, uint32_t* first_reweight);
+// The beam members' launch (k_batch_reweight_beam).  A member with n = 0 or B = 0 has no block: the lone launch returns at once there.
+MCL_HD uint32_t batch_beam_blocks(uint64_t n, uint32_t B) {
+  return (n == 0 || B == 0) ? 0u : static_cast<uint32_t>((n + kBatchBeamBlock - 1) / kBatchBeamBlock);
+}
+struct BatchBeamGrid {
+  uint32_t blocks;  // grid of k_batch_reweight_beam (0: nothing to launch)
+  uint32_t lds;     // its dynamic workgroup memory: the largest staged scan of the members that have a block
+};
+// n[m], B[m] (scan points) for m < members  ->  first_beam[m]: the member's first block (a running sum; a member that is no beam member
+// of the cycle comes with n = 0 or B = 0, has no block and is never found), and the grid.
+BatchBeamGrid batch_beam_layout(const uint64_t* n, const uint32_t* B, uint32_t members, uint32_t* first_beam);
 // The member whose blocks include `block`: the LAST m with first_of(m) <= block (members without a block share their successor's first
 // block and are skipped).  Needs first_of(0) == 0 and block < the grid.  ceil(log2(members)) steps, each one read.
 template <class FirstOf>

@@ -693,14 +693,16 @@ __device__ __forceinline__ double beam_term(const GridView& g, const BeamModel& 
 }
 
 // Variant A: one wavefront per particle, one lane per beam (small particle sets).
-__global__ __launch_bounds__(kBlock) void k_reweight_beam(Particles p, uint64_t n, GridView g, BeamModel m, NonFreeBits bits,
-                                                          const double2* __restrict__ pts, uint32_t B, unsigned long long* d_steps) {
+// (the body: block `block` of ONE set - blockIdx.x in k_reweight_beam, a member's local block in k_batch_reweight_beam)
+__device__ __forceinline__ void reweight_beam_block(uint32_t block, const Particles& p, uint64_t n, const GridView& g, const BeamModel& m,
+                                                    const NonFreeBits& bits, const double2* __restrict__ pts, uint32_t B,
+                                                    unsigned long long* d_steps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double2* s_pts = reinterpret_cast<double2*>(smem);
   for (uint32_t i = threadIdx.x; i < B; i += kBlock) s_pts[i] = pts[i];
   __syncthreads();
   const uint32_t lane = threadIdx.x & 63;
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * (kBlock / kWave) + (threadIdx.x >> 6);
+  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
   if (i >= n) return;
   const Pose2 src = pose_mul(g.origin_inverse, load_pose(p, i));
   int sx, sy;
@@ -723,6 +725,23 @@ __global__ __launch_bounds__(kBlock) void k_reweight_beam(Particles p, uint64_t 
     if (lane == 0) atomicAdd(d_steps, steps);
   }
   if (lane == 0) p.w[i] = p.w[i] * total;
+}
+__global__ __launch_bounds__(kBlock) void k_reweight_beam(Particles p, uint64_t n, GridView g, BeamModel m, NonFreeBits bits,
+                                                          const double2* __restrict__ pts, uint32_t B, unsigned long long* d_steps) {
+  reweight_beam_block(blockIdx.x, p, n, g, m, bits, pts, B, d_steps);
+}
+// The same over a fleet's beam members (mcl_batch_update; the pattern is k_batch_reweight_lf_beams, kernels.hip): a workgroup finds its
+// member over the first_beam_block prefix - a member without a block (n = 0, an empty scan, a likelihood-field member) is never found -
+// and runs the body with its LOCAL block number on the member's own record.  The member is uniform over the workgroup, so the record
+// is read through uniform addresses.  The workgroup memory of the launch is the largest staged scan among the members; a workgroup
+// stages its member's B points, which fit.
+static_assert(kBatchBeamThreads == kBlock && kBatchBeamBlock == kBlock / kWave && kBatchBeamPointBytes == sizeof(double2) &&
+                  kBatchBeamMaxPoints * kBatchBeamPointBytes == 64 * 1024,
+              "batch_host.h restates the wave-per-particle beam kernel's launch geometry");
+__global__ __launch_bounds__(kBlock) void k_batch_reweight_beam(const BatchItem* __restrict__ items, uint32_t count) {
+  const BatchItem& it = items[batch_member_of(count, blockIdx.x, [items](uint32_t m) { return items[m].first_beam_block; })];
+  reweight_beam_block(blockIdx.x - it.first_beam_block, it.p, it.n, it.beam.g, it.beam.m, it.beam.bits,
+                      reinterpret_cast<const double2*>(it.scan_dst), it.B, it.beam.d_steps);
 }
 
 // Variant B (default above 16K particles): one lane per spatially ordered particle, every lane walks the same beam at
@@ -1071,6 +1090,15 @@ void launch_reweight_beam(hipStream_t st, Particles p, uint64_t n, GridView g, B
   hipLaunchKernelGGL(k_reweight_beam, grid, dim3(kBlock), static_cast<size_t>(B) * sizeof(double2), st, p, n, g, m,
                      nonfree_bits ? nonfree_layout(g.W, g.H, const_cast<uint32_t*>(nonfree_bits)) : NonFreeBits{},
                      reinterpret_cast<const double2*>(d_points), B, d_steps);
+}
+
+BatchBeam batch_beam_record(GridView g, BeamModel m, const uint32_t* nonfree_bits, unsigned long long* d_steps) {
+  // (the occupancy as launch_reweight_beam hands it to k_reweight_beam: without the packed bits the walk is cast_ray's)
+  return BatchBeam{g, m, nonfree_bits ? nonfree_layout(g.W, g.H, const_cast<uint32_t*>(nonfree_bits)) : NonFreeBits{}, d_steps};
+}
+void launch_batch_reweight_beam(hipStream_t st, const BatchItem* d_items, uint32_t members, const BatchBeamGrid& grid) {
+  if (grid.blocks == 0) return;
+  hipLaunchKernelGGL(k_batch_reweight_beam, dim3(grid.blocks), dim3(kBlock), grid.lds, st, d_items, members);
 }
 
 }  // namespace mcl

@@ -852,13 +852,15 @@ LfPlanner::Mode plan_lf(mcl_ctx* ctx) {
   return ctx->lf_planner.decide(ctx->lf_site(), ctx->cloud, planned, through);
 }
 // A member's cycle inside mcl_batch_update.  The host steps are the lone cycle's own, in the lone cycle's order; what differs is who
-// launches: where the cycle is the small one - k_propagate_small, k_reweight_lf_beams with a wave per particle, k_small_tail -
-// do_propagate, do_reweight and update_cycle fill `item` instead of launching, and the batch launches the three kernels once for all
-// such members (launch_batch_cycle), then calls small_tail_launched and finish_small_cycle for each.
+// launches: where the cycle is the small one - k_propagate_small, k_reweight_lf_beams with a wave per particle (or, for a beam member
+// with the option batch_beam_fused, k_reweight_beam), k_small_tail - do_propagate, do_reweight and update_cycle fill `item` instead of
+// launching, and the batch launches the kernels once for all such members (launch_batch_cycle), then calls small_tail_launched and
+// finish_small_cycle for each.
 struct HeldCycle {
   bool propagate_held{false};  // do_propagate held k_propagate_small back: do_reweight decides (fused) or launches it after all
   bool fused{false};           // the member's cycle is the small one: nothing of it has been launched
   bool pending{false};         // ... and its record is complete
+  bool beam{false};            // fused, and the reweight is the beam model's (k_batch_reweight_beam)
   BatchItem item{};
   uint64_t every_n{0};         // the counter as the cycle leaves it
 };
@@ -977,6 +979,12 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
     hold->fused = lf_kind && batch_member_fused(BatchMemberFacts{
                                  ctx->cfg.sensor_kind, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0, ctx->n,
                                  std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), lf_takes_beams(lf_args, ctx->tuning), ctx->profile != 0});
+    // (a beam member: the wave-per-particle kernel, i.e. no ordering - `ordered` is the same question asked of the planner)
+    hold->beam = !lf_kind && !ordered && batch_beam_member_fused(BatchBeamFacts{
+                                 ctx->cfg.sensor_kind, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
+                                 ctx->tuning.batch_beam_fused != 0, ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity),
+                                 static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles), ctx->profile != 0});
+    hold->fused = hold->fused || hold->beam;
     if (!hold->fused) launch_held_propagate(ctx, hold);
   }
   if (ordered && !have_order) {
@@ -1032,10 +1040,15 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
       ctx->beam_table_ready = true;
     }
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    launch_reweight_beam(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model,
-                         ctx->d_points.ptr, static_cast<uint32_t>(B), ctx->d_kld_scalars.ptr + kKldBeamSteps, ordered ? &sort : nullptr,
-                         ctx->map->d_nonfree_bits.ptr, ctx->d_beam_points.ptr, use_table ? ctx->d_beam_table.ptr : nullptr,
-                         use_table ? ctx->beam_table_count : 0u, ctx->tuning.beam_free_ahead != 0, ctx->tuning.beam_sectors != 0);
+    if (hold && hold->fused) {  // (a held cycle: the batch launches k_batch_reweight_beam; never ordered, so no table was built above)
+      hold->item.B = static_cast<uint32_t>(B);
+      hold->item.beam = batch_beam_record(ctx->grid_view(), model, ctx->map->d_nonfree_bits.ptr, ctx->d_kld_scalars.ptr + kKldBeamSteps);
+    } else {
+      launch_reweight_beam(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model,
+                           ctx->d_points.ptr, static_cast<uint32_t>(B), ctx->d_kld_scalars.ptr + kKldBeamSteps, ordered ? &sort : nullptr,
+                           ctx->map->d_nonfree_bits.ptr, ctx->d_beam_points.ptr, use_table ? ctx->d_beam_table.ptr : nullptr,
+                           use_table ? ctx->beam_table_count : 0u, ctx->tuning.beam_free_ahead != 0, ctx->tuning.beam_sectors != 0);
+    }
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   }
   stage_end(ctx, MCL_STAGE_REWEIGHT);
@@ -2337,7 +2350,7 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
     }
     // Environment defaults of the per-context switches (mcl_set_option changes them at run time).
     for (const char* name : {"lf_variant", "lf_fast", "lf_table", "lf_patch", "lf_dispersed", "lf_far_tiles", "key_layout", "lf_loose_below", "lf_small_particles", "device_policy",
-                             "sort_min_particles", "beam_sort_min_particles", "field_build", "key_curve", "key_warp", "key_bits_xy", "lf_margin", "lf_split", "lf_queue_grid", "shard_pad_permille", "lf_queue", "lf_ends_first", "beam_free_ahead", "beam_sectors", "lf_weight_sums", "beam_table", "cycle_spin", "scan_fused", "draw_fold", "lf_unit_weights", "small_fused", "norm_store", "noise_ahead", "order_ahead", "lf_far_beams_per_wave", "batch_cluster_fused", "draw_key_hist", "rows_merged"}) {
+                             "sort_min_particles", "beam_sort_min_particles", "field_build", "key_curve", "key_warp", "key_bits_xy", "lf_margin", "lf_split", "lf_queue_grid", "shard_pad_permille", "lf_queue", "lf_ends_first", "beam_free_ahead", "beam_sectors", "lf_weight_sums", "beam_table", "cycle_spin", "scan_fused", "draw_fold", "lf_unit_weights", "small_fused", "norm_store", "noise_ahead", "order_ahead", "lf_far_beams_per_wave", "batch_cluster_fused", "batch_beam_fused", "draw_key_hist", "rows_merged"}) {
       std::string env = "BELUGA_MCL_";
       for (const char* c = name; *c; ++c) env += static_cast<char>(std::toupper(static_cast<unsigned char>(*c)));
       if (const char* v = std::getenv(env.c_str())) {
@@ -3094,12 +3107,15 @@ struct mcl_batch {
   std::vector<uint32_t> fused;  // the members whose cycle the batch launches, in index order
   std::vector<uint64_t> fused_n;
   std::vector<uint32_t> fused_lds, first_propagate, first_reweight;
+  std::vector<uint64_t> lf_n, beam_n;  // fused_n of the members of one family, 0 for the other's (each family's reweight launch)
+  std::vector<uint32_t> beam_B, first_beam, first_unused;
   // the cluster-based estimate's two shared launches: a record per member and launch, pinned and on the device
   BatchClusterCells* h_cluster_cells{nullptr};
   BatchClusterSums* h_cluster_sums{nullptr};
   DeviceBuffer<BatchClusterCells> d_cluster_cells;
   DeviceBuffer<BatchClusterSums> d_cluster_sums;
   uint64_t cycles{0}, kernel_launches{0}, members_fused{0}, members_alone{0}, cluster_launches{0}, members_cluster_fused{0};
+  uint64_t beam_launches{0}, members_beam_fused{0};  // shared beam reweight kernels enqueued; beam members that updated through the shared cycle
   uint64_t cluster_host_ns{0};  // host time between the two shared launches: every member's cells ordered, assigned, ids written
   // per call, kept for the next one: by member ...
   std::vector<mcl_status> status;
@@ -3118,30 +3134,53 @@ mcl_status batch_fail(mcl_batch* b, mcl_status code, const std::string& msg) {
   else g_create_error = msg;
   return code;
 }
-// Enqueues the cycle of the members in b->fused (their records complete in b->held) and waits for it: one copy, three launches, one
-// synchronisation.
+// Enqueues the cycle of the members in b->fused (their records complete in b->held) and waits for it: one copy, the launches (three for
+// members of one family, four where likelihood-field and beam members are both present), one synchronisation.
 mcl_status batch_launch(mcl_batch* b) {
   const uint32_t count = static_cast<uint32_t>(b->fused.size());
   b->fused_n.resize(count);
   b->fused_lds.resize(count);
   b->first_propagate.resize(count);
   b->first_reweight.resize(count);
+  b->beam_n.resize(count);
+  b->beam_B.resize(count);
+  b->first_beam.resize(count);
+  bool any_beam = false;
   for (uint32_t k = 0; k < count; ++k) {
-    const BatchItem& it = b->held[b->fused[k]].item;
+    const HeldCycle& held = b->held[b->fused[k]];
+    const BatchItem& it = held.item;
     b->fused_n[k] = it.n;
-    b->fused_lds[k] = static_cast<uint32_t>(lf_palette_lds(it.f));
+    b->fused_lds[k] = held.beam ? 0u : static_cast<uint32_t>(lf_palette_lds(it.f));
+    b->beam_n[k] = held.beam ? it.n : 0;
+    b->beam_B[k] = held.beam ? it.B : 0u;
+    any_beam = any_beam || held.beam;
   }
-  const BatchGrid grid = batch_layout(b->fused_n.data(), b->fused_lds.data(), count, b->first_propagate.data(), b->first_reweight.data());
+  BatchGrid grid = batch_layout(b->fused_n.data(), b->fused_lds.data(), count, b->first_propagate.data(), b->first_reweight.data());
+  BatchBeamGrid beam{0, 0};
+  if (any_beam) {
+    // The likelihood-field reweight's blocks are those of its own members: the same layout over sizes with the beam members' at 0 (a
+    // member without a block is never found).  The propagation's blocks stay those of all members.
+    b->lf_n.resize(count);
+    b->first_unused.resize(count);
+    for (uint32_t k = 0; k < count; ++k) b->lf_n[k] = b->beam_n[k] ? 0 : b->fused_n[k];
+    const BatchGrid lf = batch_layout(b->lf_n.data(), b->fused_lds.data(), count, b->first_unused.data(), b->first_reweight.data());
+    grid.reweight_blocks = lf.reweight_blocks;
+    grid.reweight_lds = lf.reweight_lds;
+    beam = batch_beam_layout(b->beam_n.data(), b->beam_B.data(), count, b->first_beam.data());
+  } else {
+    std::fill(b->first_beam.begin(), b->first_beam.end(), 0u);
+  }
   for (uint32_t k = 0; k < count; ++k) {
     BatchItem& it = b->h_items[k];
     it = b->held[b->fused[k]].item;
     it.first_propagate_block = b->first_propagate[k];
     it.first_reweight_block = b->first_reweight[k];
+    it.first_beam_block = b->first_beam[k];
   }
   if (hipMemcpyAsync(b->d_items.ptr, b->h_items, count * sizeof(BatchItem), hipMemcpyHostToDevice, b->stream) != hipSuccess)
     return batch_fail(b, MCL_ERR_HIP, "mcl_batch_update: the copy of the cycle's records failed");
-  launch_batch_cycle(b->stream, b->d_items.ptr, grid);
-  b->kernel_launches += 3;
+  b->kernel_launches += launch_batch_cycle(b->stream, b->d_items.ptr, grid, beam);
+  if (beam.blocks) b->beam_launches += 1;
   for (const uint32_t i : b->fused) small_tail_launched(b->members[i], b->held[i].every_n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
@@ -3401,6 +3440,7 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
       if (status[i] != MCL_OK) continue;
       finish_cycle(ctx, est[i], report[i], estimates ? &estimates[i] : nullptr, infos ? &infos[i] : nullptr);
       batch->members_fused += 1;
+      if (batch->held[i].beam) batch->members_beam_fused += 1;
       any_updated = true;
     }
   }
@@ -3426,6 +3466,8 @@ mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* v
   else if (key == "cluster_launches") *value = batch->cluster_launches;
   else if (key == "members_cluster_fused") *value = batch->members_cluster_fused;
   else if (key == "cluster_host_ns") *value = batch->cluster_host_ns;
+  else if (key == "beam_launches") *value = batch->beam_launches;
+  else if (key == "members_beam_fused") *value = batch->members_beam_fused;
   else return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_get_counter: unknown counter " + key);
   return MCL_OK;
 }
@@ -3834,6 +3876,7 @@ mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value) {
   else if (key == "lf_unit_weights") t.lf_unit_weights = value ? 1 : 0;
   else if (key == "small_fused") t.small_fused = value ? 1 : 0;
   else if (key == "batch_cluster_fused") t.batch_cluster_fused = value ? 1 : 0;
+  else if (key == "batch_beam_fused") t.batch_beam_fused = value ? 1 : 0;
   else if (key == "norm_store") t.norm_store = value ? 1 : 0;
   else if (key == "order_ahead") t.order_ahead = value ? 1 : 0;
   else if (key == "draw_key_hist") t.draw_key_hist = value ? 1 : 0;

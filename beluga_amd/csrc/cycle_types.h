@@ -116,6 +116,10 @@ struct Tuning {
                                     // 1 = stored
   int batch_cluster_fused = 1;      // a member of a batch (mcl_batch_update) whose cycle was fused and which returns the cluster-based estimate: 1 = that
                                     // estimate through the batch's two shared launches, 0 = through its own mcl_cluster_based_estimate
+  int batch_beam_fused = 0;         // a beam-model member of a batch (mcl_batch_update) whose cycle is the small one with the wave-per-particle
+                                    // kernel: 1 = its three kernels ride on the fleet's shared launches, the reweight on one launch for all such
+                                    // members (k_batch_reweight_beam); 0 = it runs its own cycle inside the call.  Bit-identical.  Off until the
+                                    // path has been measured ("Batched small filters").
   int small_fused = 1;              // sets of up to 4096 particles (plain estimate, one context): everything behind the reweight - normalise,
                                     // policies, fixed-size or KLD resampling, estimate sums - in one launch of one workgroup and one host
                                     // synchronisation (k_small_tail); 0 = the kernels of the large path

@@ -530,8 +530,17 @@ SmallTailArgs small_tail_args(const SmallTail& t);
 bool small_tail_fits(uint64_t n, uint64_t max_particles);  // launch_small_tail's own test: both 1 .. 4096
 
 // ---- a batch of small filters (mcl_batch_update): the small cycle's three kernels over many sets in one launch each ----------------------
-// One member's cycle, as k_propagate_small, k_reweight_lf_beams (a wave per particle) and k_small_tail take it.  The host fills one
-// record per fused member and cycle; every kernel of the cycle gets the device table.
+// One member's cycle, as k_propagate_small, its reweight kernel - k_reweight_lf_beams (a wave per particle) for the likelihood-field
+// kinds, k_reweight_beam for the beam model - and k_small_tail take it.  The host fills one record per fused member and cycle; every
+// kernel of the cycle gets the device table.
+// k_reweight_beam's arguments beyond the set and the scan (batch_beam_record fills it as launch_reweight_beam fills the lone launch).
+struct BatchBeam {
+  GridView g;
+  BeamModel m;
+  NonFreeBits bits;             // all zero: no packed occupancy, the walk reads the cells
+  unsigned long long* d_steps;  // the member's count of cells visited (mcl_beam_cells_visited)
+};
+BatchBeam batch_beam_record(GridView g, BeamModel m, const uint32_t* nonfree_bits, unsigned long long* d_steps);
 struct BatchItem {
   Particles p;  // the live set
   uint64_t n;
@@ -542,13 +551,17 @@ struct BatchItem {
   const double* scan_src;  // the member's staged scan in mapped host memory (nullptr: an empty scan, nothing pulled)
   double* scan_dst;        // ... and where the reweight reads it
   uint32_t scan_doubles;
-  FieldView f;  // k_reweight_lf_beams' arguments (its points are scan_dst)
-  uint32_t B;
+  FieldView f;  // k_reweight_lf_beams' arguments (its points are scan_dst); a beam member's stays zero
+  uint32_t B;   // the scan's points, of either family
   SmallTailArgs tail;
-  uint32_t first_propagate_block, first_reweight_block;  // batch_layout
+  uint32_t first_propagate_block, first_reweight_block;  // batch_layout (a beam member has no block in the second)
+  BatchBeam beam;             // a beam member's k_reweight_beam arguments; a likelihood-field member's stays zero
+  uint32_t first_beam_block;  // batch_beam_layout (a likelihood-field member has no block)
 };
-// k_batch_propagate, k_batch_reweight_lf_beams, k_batch_small_tail over d_items[0 .. grid.members), in this order on `st`.
-void launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid);
+// k_batch_propagate, k_batch_reweight_lf_beams (if grid.reweight_blocks), k_batch_reweight_beam (if beam.blocks), k_batch_small_tail over
+// d_items[0 .. grid.members), in this order on `st`.  Returns the kernels enqueued.
+uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam);
+void launch_batch_reweight_beam(hipStream_t st, const BatchItem* d_items, uint32_t members, const BatchBeamGrid& grid);  // (beam_kernels.hip)
 // K6: one thread per candidate (views/sample.hpp:102,133-135; random_intersperse.hpp:90-115; particle_traits.hpp:105).
 void launch_resample_draw(hipStream_t st, Particles src, CdfTree cdf, const double* d_total, Particles dst,
                           ResampleArgs a, GridView g, FreeCells fc, HashParams hp, unsigned long long* d_hashes);

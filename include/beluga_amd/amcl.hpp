@@ -1131,7 +1131,8 @@ class AmclBatch {
   void set_option(const std::string& name, std::int64_t value) {
     for (Amcl& m : members_) m.check(mcl_set_option(m.ctx_, name.c_str(), value));
   }
-  /// cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns (mcl_batch_get_counter).
+  /// cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns, beam_launches, members_beam_fused
+  /// (mcl_batch_get_counter).
   [[nodiscard]] std::uint64_t counter(const std::string& name) const {
     std::uint64_t value = 0;
     check(mcl_batch_get_counter(batch_, name.c_str(), &value));

@@ -444,13 +444,23 @@ mcl_status mcl_sample_particle_cloud(mcl_ctx* ctx, uint64_t size, uint32_t draw_
  *
  * Which members share the launches is decided per member and cycle: those whose own mcl_update would run exactly the small cycle -
  * likelihood-field or likelihood-field-prob model, not sharded, option small_fused on, the set and min(max_particles, capacity) both at
- * most 4096, the field's palette table usable, stage profiling off.  Every other member (larger sets, the beam, NDT and landmark models,
- * profiling on) runs its ordinary cycle inside the same call; a pending mcl_set_map_async map is swapped in where mcl_update would.
+ * most 4096, the field's palette table usable, stage profiling off.  A beam-model member shares them too where its option
+ * batch_beam_fused is on (default 0) and its own mcl_update would run the small cycle with the beam model's wave-per-particle kernel:
+ * not sharded, option small_fused on, the set and min(max_particles, capacity) both 1 .. 4096, the set below the option
+ * beam_sort_min_particles (from there on the member wants the ordered kernel), stage profiling off.  The beam members' reweight is one
+ * more shared launch, between the propagation and the tail: a fleet of one family takes three launches per cycle, a fleet of both
+ * takes four.  A scan of more than 4096 points is refused for such a member as by its own mcl_update (the kernel stages the scan in 64 KB
+ * of workgroup memory): its status is its own, its state untouched, the others proceed.  Every other member (larger sets, beam members
+ * with the option off or of the ordered kernel's size, the NDT and landmark models, profiling on) runs its ordinary cycle inside the same
+ * call; a pending mcl_set_map_async map is swapped in where mcl_update would.
  *
- * Counters (mcl_batch_get_counter): cycles = calls that updated at least one member; kernel_launches = kernels the shared path has
- * enqueued, a running total (3 per cycle with a fused member, however many members there are); members_fused / members_alone = running
- * totals of members that updated through the shared launches / through their ordinary cycle.  A fused member's own counters
- * (small_tail_launches, lf_beams_launches) advance as in a lone cycle.
+ * Counters (mcl_batch_get_counter): cycles = calls that updated at least one member; kernel_launches = kernels the shared cycle has
+ * enqueued, a running total (per cycle with a fused member, however many members there are: 3 where the fused members are of one family,
+ * 4 where likelihood-field and beam members are both present; the beam launch is left out where no fused beam member has a scan point);
+ * members_fused / members_alone = running totals of members that updated through the shared launches / through their ordinary cycle;
+ * beam_launches = shared beam reweight kernels enqueued, a running total; members_beam_fused = running total of beam members that updated
+ * through the shared launches (they count in members_fused as well).  A fused member's own counters (small_tail_launches,
+ * lf_beams_launches, the cells of mcl_beam_cells_visited) advance as in a lone cycle.
  *
  * The cluster-based estimate (mcl_set_estimate_kind 1: what beluga_ros::Amcl::update returns) of the fused members is batched as well:
  * behind the cycle's synchronisation, TWO shared launches of one workgroup per member - the occupied cells of every member into its own
@@ -729,6 +739,9 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *                   them), the CDF kernel divides again; 1 = stored.  Bit-identical.
  *   batch_cluster_fused (1)  a member of a batch that returns the cluster-based estimate: 1 = through the batch's two shared launches
  *                   ("Batches of small filters"), 0 = through its own mcl_cluster_based_estimate.  The same bits either way.
+ *   batch_beam_fused (0)  a beam-model member of a batch whose cycle is the small one with the wave-per-particle kernel: 1 = its kernels
+ *                   ride on the fleet's shared launches, the reweight on one launch for all such members ("Batches of small filters"),
+ *                   0 = it runs its own cycle inside mcl_batch_update.  The same bits either way.  Off until the path has been measured.
  *   small_fused (1)  sets of up to 4096 particles: everything behind the reweight - normalise, policies, fixed-size or KLD resampling, estimate
  *                   sums - in one launch of one workgroup and one host synchronisation (and two one-workgroup kernels around the host's pass of
  *                   cluster_based_estimate); 0 = the kernels of the large path
