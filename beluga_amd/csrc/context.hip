@@ -32,6 +32,7 @@
 #include "map_build.h"
 #include "map_store.h"
 #include "ndt_host.h"
+#include "options_host.h"
 #include "set_facts.h"
 
 namespace {
@@ -46,10 +47,6 @@ struct ParticleSet {
   hipError_t ensure(size_t n) {
     if (const hipError_t e = pose.ensure(n); e != hipSuccess) return e;
     return w.ensure(n);
-  }
-  void release() {
-    pose.release();
-    w.release();
   }
   Particles view() const { return Particles{pose.ptr, w.ptr}; }
 };
@@ -91,11 +88,9 @@ struct mcl_ctx {
   DeviceBuffer<double> d_beam_table;   // beam model: 4 doubles per squared cell distance of a hit (launch_beam_table), built by mcl_set_map
   uint32_t beam_table_count{0};
   bool beam_table_ready{false};        // d_beam_table holds the table of the current map (built lazily: do_reweight)
-  double* h_points{nullptr};   // pinned, mapped
-  double* hd_points{nullptr};  // the same memory as the device sees it
+  HostBuffer<double> h_points;  // pinned, mapped
   double scan_extent{0.0};     // max |x| + |y| of the staged scan points
   uint64_t scan_no_cell{0};    // points of the scan taken out where it was staged: NaN or infinite, without a cell for any pose (FieldView::acc0)
-  size_t h_points_cap{0};
   hipEvent_t points_event{nullptr};  // recorded behind the kernel that pulls h_points
   bool points_in_flight{false}, points_event_valid{false};
 
@@ -103,8 +98,7 @@ struct mcl_ctx {
   DeviceBuffer<double> d_chunk;      // [12][stride]
   uint32_t chunk_stride{0};
   DeviceBuffer<double> d_scalars;    // kScalarSlots doubles, laid out as kernels.h ScalarSlot says
-  double* h_scalars{nullptr};        // pinned, kScalarSlots doubles
-  double* hd_scalars{nullptr};       // the same memory as the device sees it: kernels mirror their scalar results into it
+  HostBuffer<double> h_scalars;      // pinned and mapped, kScalarSlots doubles: kernels mirror their scalar results into it
   DeviceBuffer<double> d_cdf;
   DeviceBuffer<double4> d_cloud;    // mcl_sample_particle_cloud staging
   DeviceBuffer<double> d_est_partials;  // [9][ceil(n / 256)] estimate sums left by the draw kernel
@@ -155,7 +149,7 @@ struct mcl_ctx {
   uint64_t kld_pos{0}, kld_table_slots{0};
   int kld_flip{0};
   DeviceBuffer<unsigned long long> d_kld_scalars;  // 8 words, laid out as KldWord says
-  unsigned long long* h_kld_scalars{nullptr};      // pinned, 8 words
+  HostBuffer<unsigned long long> h_kld_scalars;    // pinned, 8 words
 
   // cluster_based_estimate scratch
   DeviceBuffer<double> d_cell_f64;             // table wsum[cap_t] | list wsum[m_cap] | list state[4*m_cap]
@@ -210,9 +204,8 @@ struct mcl_ctx {
   DeviceBuffer<unsigned long long> d_cand_hashes, d_block_hashes;
   uint64_t global_n{0};                     // particles of the logical filter over all shards (0: max_particles)
   bool global_n_unknown{false};             // the caller loaded this shard itself (mcl_set_particles): counts are gathered first
-  double* h_comm{nullptr};                  // pinned staging for the exchange's host reads / uploads
-  unsigned char* h_cells{nullptr};          // cluster_based_estimate: the list of occupied cells in mapped pinned memory
-  unsigned char* hd_cells{nullptr};         // ... its device address
+  HostBuffer<double> h_comm;                // pinned staging for the exchange's host reads / uploads
+  HostBuffer<unsigned char> h_cells;        // cluster_based_estimate: the list of occupied cells in mapped pinned memory
 
   // profiling: 0 = off, 1 = the sensor kernel only (two events per cycle), 2 = every stage
   int profile{0};
@@ -357,7 +350,7 @@ void stage_collect(mcl_ctx* ctx) {
 mcl_status wait_for_cycle(mcl_ctx* ctx) {
   if (ctx->done_armed) {
     ctx->done_armed = false;
-    const volatile uint64_t* word = reinterpret_cast<const volatile uint64_t*>(ctx->h_scalars + kSlotDoneWord);
+    const volatile uint64_t* word = reinterpret_cast<const volatile uint64_t*>(ctx->h_scalars.host + kSlotDoneWord);
     const auto t0 = std::chrono::steady_clock::now();
     for (uint32_t spins = 1;; ++spins) {
       if (*word == ctx->done_seq) {
@@ -461,10 +454,10 @@ mcl_status kld_process(mcl_ctx* ctx, uint64_t cnt, uint64_t* first_fail) {
                   ctx->d_uchunk.ptr + ctx->kld_chunks, kwords + ctx->kld_flip, kwords + (ctx->kld_flip ^ 1), a.min_particles,
                   a.kld_epsilon, a.kld_z, ctx->d_kld_scalars.ptr + kKldFirstFail);
   MCL_HIP(ctx, hipGetLastError());
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars + kKldFirstFail, ctx->d_kld_scalars.ptr + kKldFirstFail, sizeof(unsigned long long),
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars.host + kKldFirstFail, ctx->d_kld_scalars.ptr + kKldFirstFail, sizeof(unsigned long long),
                               hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *first_fail = ctx->h_kld_scalars[kKldFirstFail];
+  *first_fail = ctx->h_kld_scalars.host[kKldFirstFail];
   ctx->kld_pos += cnt;
   ctx->kld_flip ^= 1;
   return MCL_OK;
@@ -671,13 +664,6 @@ void ndt_install_view(mcl_ctx* ctx, const NdtGridShape& g, const mcl_ndt_params&
   ctx->have_ndt_map = true;
 }
 
-template <class T>
-struct ScopedBuffer : DeviceBuffer<T> {  // scratch of one call
-  ScopedBuffer() = default;
-  ScopedBuffer(const ScopedBuffer&) = delete;
-  ScopedBuffer& operator=(const ScopedBuffer&) = delete;
-  ~ScopedBuffer() { this->release(); }
-};
 uint32_t bits_of(uint64_t span) {  // bits that hold 0 .. span
   uint32_t b = 0;
   while (span >> b) ++b;
@@ -694,7 +680,7 @@ mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, co
   mcl_ndt_params prm;
   if (ctx->have_ndt_params) prm = ctx->ndt_params;
   else mcl_default_ndt_params(&prm);
-  ScopedBuffer<int32_t> d_box;
+  DeviceBuffer<int32_t> d_box;
   MCL_HIP(ctx, d_box.ensure(5));
   int32_t box[5] = {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN, 0};
   MCL_HIP(ctx, hipMemcpy(d_box.ptr, box, sizeof(box), hipMemcpyHostToDevice));
@@ -704,8 +690,8 @@ mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, co
   MCL_REQUIRE(ctx, box[4] == 0, who + ": a point is not finite, or its key (p / resolution) does not fit an int32");
   const uint32_t bits_x = bits_of(static_cast<uint64_t>(static_cast<int64_t>(box[1]) - box[0]));
   const uint32_t bits_y = bits_of(static_cast<uint64_t>(static_cast<int64_t>(box[3]) - box[2]));
-  ScopedBuffer<unsigned long long> d_words;
-  ScopedBuffer<uint32_t> d_u32;
+  DeviceBuffer<unsigned long long> d_words;
+  DeviceBuffer<uint32_t> d_u32;
   const size_t table = ndt_radix_table_words(n), chunks = num_chunks(std::max<size_t>(n, table)), starts = n / 5 + 1;
   MCL_HIP(ctx, d_words.ensure(static_cast<size_t>(2) * n));
   MCL_HIP(ctx, d_u32.ensure(static_cast<size_t>(3) * n + table + chunks + starts + kNdtCounters));
@@ -761,25 +747,17 @@ mcl_status stage_points(mcl_ctx* ctx, Measurement* staged) {
     else MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->points_in_flight = false;
   }
-  if (ctx->h_points_cap < m.doubles) {
-    if (ctx->h_points) (void)hipHostFree(ctx->h_points);
-    ctx->h_points = nullptr;
-    ctx->hd_points = nullptr;
-    ctx->h_points_cap = 0;
-    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_points), m.doubles * sizeof(double), hipHostMallocMapped));
-    MCL_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->hd_points), ctx->h_points, 0));
-    ctx->h_points_cap = m.doubles;
-  }
+  MCL_HIP(ctx, ctx->h_points.ensure(m.doubles, /*mapped=*/true));
   if (ctx->off_grid()) {  // records: nothing reads the extent of a scan on these contexts
-    std::copy(m.data, m.data + m.doubles, ctx->h_points);
+    std::copy(m.data, m.data + m.doubles, ctx->h_points.host);
     return MCL_OK;
   }
   double extent = 0.0;  // maximum of |x| + |y| over the scan; a NaN point makes it NaN (and every comparison with it false)
   bool poisoned = false, unbounded = false;
   for (uint64_t i = 0; i < m.doubles; i += 2) {  // (one straight pass, as before: the common scan has nothing to take out)
     const double x = m.data[i], y = m.data[i + 1];
-    ctx->h_points[i] = x;
-    ctx->h_points[i + 1] = y;
+    ctx->h_points.host[i] = x;
+    ctx->h_points.host[i + 1] = y;
     const double e = std::abs(x) + std::abs(y);
     if (e != e) poisoned = true;
     if (e == std::numeric_limits<double>::infinity()) unbounded = true;
@@ -792,8 +770,8 @@ mcl_status stage_points(mcl_ctx* ctx, Measurement* staged) {
       const double x = m.data[i], y = m.data[i + 1];
       if (!(std::isfinite(x) && std::isfinite(y))) continue;  // a NaN or infinite coordinate (finite ones whose sum overflows stay)
       const double e = std::abs(x) + std::abs(y);
-      ctx->h_points[kept] = x;
-      ctx->h_points[kept + 1] = y;
+      ctx->h_points.host[kept] = x;
+      ctx->h_points.host[kept + 1] = y;
       kept += 2;
       extent = e > extent ? e : extent;
     }
@@ -835,7 +813,7 @@ void finish_cycle(mcl_ctx* ctx, const mcl_estimate& est, const mcl_update_info& 
 // synchronised: the stream is idle (the two 64-bit totals are consistent); otherwise the pair comes from the packed word the
 // kernel stores last (low 32 bits of each total in one 8-byte store: never torn; differences are taken modulo 2^32).
 void patch_totals(const mcl_ctx* ctx, uint64_t* planned, uint64_t* through, bool synchronised = false) {
-  const volatile uint64_t* mirror = reinterpret_cast<const volatile uint64_t*>(ctx->h_scalars + kSlotPatchMirror);
+  const volatile uint64_t* mirror = reinterpret_cast<const volatile uint64_t*>(ctx->h_scalars.host + kSlotPatchMirror);
   if (synchronised) {
     *planned = mirror[0];
     *through = mirror[1];
@@ -903,13 +881,13 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
     it.seed = ctx->cfg.seed;
     it.step = step;
     it.index_offset = ctx->cfg.shard_offset;
-    it.scan_src = scan_doubles ? ctx->hd_points : nullptr;
+    it.scan_src = scan_doubles ? ctx->h_points.device : nullptr;
     it.scan_dst = scan_doubles ? ctx->d_points.ptr : nullptr;
     it.scan_doubles = static_cast<uint32_t>(scan_doubles);
     hold->propagate_held = true;
   } else {
     launch_propagate(ctx->stream, ctx->cur(), ctx->n, sampler, ctx->cfg.seed, step, ctx->cfg.shard_offset,
-                     scan_doubles ? ctx->hd_points : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
+                     scan_doubles ? ctx->h_points.device : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
                      keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->facts.noise_ahead_count());
   }
   if (ahead) ctx->noise_ahead_used += 1;
@@ -951,7 +929,7 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
   if (!points_staged) {
     if (const mcl_status s = stage_points(ctx, &m)) return s;
     if (m.doubles) {
-      launch_pull_scan(ctx->stream, ctx->hd_points, ctx->d_points.ptr, static_cast<uint32_t>(m.doubles));
+      launch_pull_scan(ctx->stream, ctx->h_points.device, ctx->d_points.ptr, static_cast<uint32_t>(m.doubles));
       points_pulled(ctx, true);
     }
   }
@@ -971,7 +949,7 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
                              .dispersed = dispersed,
                              .scan_cells = ctx->scan_extent / ctx->map->resolution, .unit_weights = unit_weights,
                              .stats = PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
-                                                 reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotPatchMirror),
+                                                 reinterpret_cast<unsigned long long*>(ctx->h_scalars.device + kSlotPatchMirror),
                                                  static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
                                                  static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
                                                  reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)}};
@@ -1062,11 +1040,11 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
 
 // What a normalisation (kSlotWeightSum, kSlotNormSum, kSlotNormSumSq) left in the mirror.
 mcl_weight_stats mirrored_weight_stats(const mcl_ctx* ctx) {
-  return mcl_weight_stats{ctx->h_scalars[kSlotWeightSum], ctx->h_scalars[kSlotNormSum], ctx->h_scalars[kSlotNormSumSq]};
+  return mcl_weight_stats{ctx->h_scalars.host[kSlotWeightSum], ctx->h_scalars.host[kSlotNormSum], ctx->h_scalars.host[kSlotNormSumSq]};
 }
 // The nine estimate sums a kernel left in the mirror (kSlotEstimate) and the pivot they were taken about: mcl_estimate_from_sums' input.
 void mirrored_sums(const mcl_ctx* ctx, const double pivot[2], double sums[12]) {
-  for (int k = 0; k < 9; ++k) sums[k] = ctx->h_scalars[kSlotEstimate + k];
+  for (int k = 0; k < 9; ++k) sums[k] = ctx->h_scalars.host[kSlotEstimate + k];
   sums[9] = pivot[0];
   sums[10] = pivot[1];
   sums[11] = 0.0;
@@ -1103,16 +1081,16 @@ mcl_status do_normalize(mcl_ctx* ctx, double factor, mcl_weight_stats* stats, co
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
   if (std::isnan(factor)) {  // by the set's own total
     launch_sum_and_normalize(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->chunk_row(1), ctx->chunk_row(2),
-                             ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum, opt.finalize,
+                             ctx->d_scalars.ptr + kSlotWeightSum, ctx->h_scalars.device + kSlotWeightSum, opt.finalize,
                              ctx->facts.lf_sums() ? ctx->d_lf_wsum.ptr : nullptr, ctx->facts.lf_sums(), opt.store_weights);
     ctx->facts.weights_left_undivided(!opt.store_weights);
     ctx->facts.lf_sums_dropped();  // (they described the weights as the reweight left them)
   } else {
-    launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum);
-    ctx->h_scalars[kSlotFactor] = factor;
-    MCL_HIP(ctx, hipMemcpyAsync(ctx->d_scalars.ptr + kSlotFactor, ctx->h_scalars + kSlotFactor, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotWeightSum, ctx->h_scalars.device + kSlotWeightSum);
+    ctx->h_scalars.host[kSlotFactor] = factor;
+    MCL_HIP(ctx, hipMemcpyAsync(ctx->d_scalars.ptr + kSlotFactor, ctx->h_scalars.host + kSlotFactor, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     launch_normalize(ctx->stream, ctx->cur().w, ctx->n, ctx->d_scalars.ptr + kSlotFactor, ctx->chunk_row(1), ctx->chunk_row(2),
-                     ctx->d_scalars.ptr + kSlotNormSum, ctx->hd_scalars + kSlotNormSum);
+                     ctx->d_scalars.ptr + kSlotNormSum, ctx->h_scalars.device + kSlotNormSum);
   }
   if (!opt.read_back) {
     stage_end(ctx, MCL_STAGE_NORMALIZE);
@@ -1135,7 +1113,7 @@ mcl_status do_normalize_cdf(mcl_ctx* ctx, const RecoveryPolicy& policy, bool* do
   stage_begin(ctx, MCL_STAGE_NORMALIZE);
   if (++ctx->scan_epoch == 0) ctx->scan_epoch = 1;
   *done = launch_normalize_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->facts.lf_sums() ? ctx->d_lf_wsum.ptr : nullptr,
-                               ctx->facts.lf_sums(), ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum, ctx->chunk_row(1),
+                               ctx->facts.lf_sums(), ctx->d_scalars.ptr + kSlotWeightSum, ctx->h_scalars.device + kSlotWeightSum, ctx->chunk_row(1),
                                ctx->chunk_row(2), /*write_weights=*/false, ctx->d_cdf.ptr, ctx->d_scalars.ptr + kSlotCdfTotal, ctx->d_cdf_tree.ptr,
                                &policy, ctx->d_scan_state.ptr, ctx->scan_epoch);
   if (*done) ctx->facts.lf_sums_dropped();
@@ -1152,7 +1130,7 @@ mcl_status do_build_cdf(mcl_ctx* ctx, bool normalized_just_now = false, const Re
   const bool divides = ctx->facts.take_cdf_divides();
   launch_cdf(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(3), ctx->chunk_row(4), ctx->d_cdf.ptr, ctx->d_scalars.ptr + kSlotCdfTotal,
              ctx->d_cdf_tree.ptr, normalized_just_now ? ctx->chunk_row(1) : nullptr, finalize_norm ? ctx->chunk_row(2) : nullptr,
-             finalize_norm ? ctx->d_scalars.ptr + kSlotNormSum : nullptr, finalize_norm ? ctx->hd_scalars + kSlotNormSum : nullptr, policy,
+             finalize_norm ? ctx->d_scalars.ptr + kSlotNormSum : nullptr, finalize_norm ? ctx->h_scalars.device + kSlotNormSum : nullptr, policy,
              (normalized_just_now && divides) ? ctx->d_scalars.ptr + kSlotWeightSum : nullptr);
   MCL_HIP(ctx, hipGetLastError());
   return MCL_OK;
@@ -1238,7 +1216,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       ctx->done_armed = spin && ctx->profile <= 1 && opt.estimate_enqueued;
       if (ctx->done_armed) {
         done.d_ticket = reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotDoneTicket);
-        done.host_flag = reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotDoneWord);
+        done.host_flag = reinterpret_cast<unsigned long long*>(ctx->h_scalars.device + kSlotDoneWord);
         done.seq = ++ctx->done_seq;
       }
       // (behind the draw and its sums - the completion word is theirs -: the next cycle's propagation normals, while the host is away)
@@ -1258,7 +1236,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
       const SortScratch ahead_sort = order_keys ? ctx->sort_scratch() : SortScratch{};
       const OrderAheadDone order_done = launch_resample_draw_and_estimate(ctx->stream, ctx->cur(), ctx->cdf_tree(), d_total, ctx->other(), ra, gv, fc, hp,
                                         ctx->facts.pivot()[0], ctx->facts.pivot()[1], ctx->d_est_partials.ptr, ctx->d_scalars.ptr + kSlotEstimate,
-                                        ctx->hd_scalars + kSlotEstimate, ctx->done_armed ? &done : nullptr,
+                                        ctx->h_scalars.device + kSlotEstimate, ctx->done_armed ? &done : nullptr,
                                         ((ctx->tuning.draw_fold == 2 || (ctx->tuning.draw_fold == 1 && max_p <= 65536)) && ctx->d_scan_state.ptr)
                                             ? reinterpret_cast<unsigned int*>(ctx->d_scan_state.ptr + 4)
                                             : nullptr,
@@ -1310,7 +1288,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
 mcl_status do_estimate_sums(mcl_ctx* ctx, const double pivot[2], double sums[12], double* scratch) {
   stage_begin(ctx, MCL_STAGE_ESTIMATE);
   launch_estimate_sums(ctx->stream, ctx->cur(), ctx->n, pivot[0], pivot[1], scratch ? scratch : ctx->chunk_row(0),
-                       ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+                       ctx->d_scalars.ptr + kSlotEstimate, ctx->h_scalars.device + kSlotEstimate);
   stage_end(ctx, MCL_STAGE_ESTIMATE);
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   stage_collect(ctx);
@@ -1343,14 +1321,14 @@ CommAreas comm_areas(const mcl_ctx* ctx) {
 }
 // h_comm: the global sum, the gathered statistics (ShardStats[world]) and the CDF intervals to upload from h_comm[0] on, then the
 // 64-bit words of the counts' all-gathers.
-long long* comm_host_words(const mcl_ctx* ctx) { return reinterpret_cast<long long*>(ctx->h_comm + kCommScalars + kMaxWorld * kCommPerRank); }
+long long* comm_host_words(const mcl_ctx* ctx) { return reinterpret_cast<long long*>(ctx->h_comm.host + kCommScalars + kMaxWorld * kCommPerRank); }
 
 mcl_status comm_scratch(mcl_ctx* ctx) {
   const size_t world = ctx->comm_world;
   MCL_HIP(ctx, ctx->d_comm_f64.ensure(kCommScalars + world * kCommPerRank));
   MCL_HIP(ctx, ctx->d_comm_i64.ensure(world + world * world));
   const size_t host_doubles = kCommScalars + kMaxWorld * kCommPerRank + kMaxWorld * kMaxWorld + kMaxWorld;  // (the words: kMaxWorld + 1 rows)
-  if (!ctx->h_comm) MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_comm), host_doubles * sizeof(double)));
+  MCL_HIP(ctx, ctx->h_comm.ensure(host_doubles, /*mapped=*/false));
   return MCL_OK;
 }
 mcl_status comm_gather(mcl_ctx* ctx, const void* d_send, void* d_recv, uint64_t bytes) {
@@ -1451,7 +1429,7 @@ mcl_status sharded_sums(mcl_ctx* ctx, const ClusterMask* mask, const double pivo
   MCL_HIP(ctx, hipGetLastError());
   // (with the nine sums travels kCommOverflow: this rank's flag of the cycle's fixed-capacity exchange - their sum lands in kSlotOverflow)
   if (const mcl_status s = comm_gather(ctx, d_est, d_gather_est, kEstRecord * sizeof(double))) return s;
-  launch_sum_rows(ctx->stream, d_gather_est, world, kEstRecord, ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+  launch_sum_rows(ctx->stream, d_gather_est, world, kEstRecord, ctx->d_scalars.ptr + kSlotEstimate, ctx->h_scalars.device + kSlotEstimate);
   MCL_HIP(ctx, hipGetLastError());
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->comm_host_syncs += 1;
@@ -1514,15 +1492,12 @@ mcl_status cluster_scratch(mcl_ctx* ctx, CellScratch* sc) {
   MCL_HIP(ctx, ctx->d_cell_f64.ensure(tcap + kListF64 * ctx->capacity));
   MCL_HIP(ctx, ctx->d_cell_u32.ensure(2 * tcap + kListU32 * ctx->capacity + 4));
   MCL_HIP(ctx, ctx->d_cell_u64.ensure(ctx->capacity));
-  if (!ctx->h_cells) {
-    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_cells), cell_list_bytes(kHostCells), hipHostMallocMapped));
-    MCL_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->hd_cells), ctx->h_cells, 0));
-  }
+  MCL_HIP(ctx, ctx->h_cells.ensure(cell_list_bytes(kHostCells), /*mapped=*/true));
   unsigned int* u32 = ctx->d_cell_u32.ptr;
   sc->table = CellTable{ctx->d_table_keys.ptr, ctx->d_table_first.ptr, ctx->d_cell_f64.ptr, u32, u32 + tcap, slots};
   sc->arrays = lay_cell_list(ctx->d_cell_u64.ptr, ctx->d_cell_f64.ptr + tcap, u32 + 2 * tcap, ctx->capacity);
-  sc->mapped = lay_cell_list(ctx->h_cells, kHostCells);
-  sc->mapped_dev = lay_cell_list(ctx->hd_cells, kHostCells);
+  sc->mapped = lay_cell_list(ctx->h_cells.host, kHostCells);
+  sc->mapped_dev = lay_cell_list(ctx->h_cells.device, kHostCells);
   return MCL_OK;
 }
 
@@ -1666,7 +1641,7 @@ mcl_status upload_cell_values(mcl_ctx* ctx, const MyCells& c, const std::vector<
 // in the mapped list).
 mcl_status small_cluster_sums_pass(mcl_ctx* ctx, const HashParams& hp, const MyCells& c, unsigned int wanted, const double* p, double* sums) {
   launch_small_cluster_sums(ctx->stream, ctx->cur(), ctx->n, hp, c.dev.list.key, c.dev.cluster, c.m, wanted, p[0], p[1],
-                            ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+                            ctx->d_scalars.ptr + kSlotEstimate, ctx->h_scalars.device + kSlotEstimate);
   MCL_HIP(ctx, hipGetLastError());
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   mirrored_sums(ctx, p, sums);
@@ -1690,7 +1665,7 @@ mcl_status cluster_sums(mcl_ctx* ctx, const HashParams& hp, const CellScratch& s
   }
   auto masked = [&](const double* p, double* sums) -> mcl_status {
     launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, sc.table, wanted, p[0], p[1],
-                                 ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+                                 ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotEstimate, ctx->h_scalars.device + kSlotEstimate);
     MCL_HIP(ctx, hipGetLastError());
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     mirrored_sums(ctx, p, sums);
@@ -1808,7 +1783,7 @@ mcl_status do_estimate_clusters(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_
     // (a cluster far from the overall estimate: one masked pass of its own about its own mean - the table's column carries the ranks)
     auto masked = [&](const double* p, double* again) -> mcl_status {
       launch_estimate_sums_cluster(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, f.sc.table, r, p[0], p[1], ctx->chunk_row(0),
-                                   ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate);
+                                   ctx->d_scalars.ptr + kSlotEstimate, ctx->h_scalars.device + kSlotEstimate);
       MCL_HIP(ctx, hipGetLastError());
       MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
       mirrored_sums(ctx, p, again);
@@ -2055,11 +2030,11 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, Measurement scan, mcl
   // there, and the host reads them back with the estimate.  The cycle then has ONE host round trip before its end: the request
   // counts of the ancestor exchange (a collective's send / receive counts are host values).
   if (!adaptive && !ap.selective_resampling && ctx->tuning.device_policy != 0) {
-    const RecoveryPolicy policy{ap.alpha_slow, ap.alpha_fast, fires ? 1 : 0, ctx->d_scalars.ptr + kSlotPolicy, ctx->hd_scalars + kSlotPolicy};
+    const RecoveryPolicy policy{ap.alpha_slow, ap.alpha_fast, fires ? 1 : 0, ctx->d_scalars.ptr + kSlotPolicy, ctx->h_scalars.device + kSlotPolicy};
     double* d_plan = d + kCommPlan;  // {total, p}
-    launch_shard_plan(ctx->stream, gathered.stats, world, n_total, ctx->d_scalars.ptr + kSlotNormSum, ctx->hd_scalars + kSlotNormSum, policy,
+    launch_shard_plan(ctx->stream, gathered.stats, world, n_total, ctx->d_scalars.ptr + kSlotNormSum, ctx->h_scalars.device + kSlotNormSum, policy,
                       d_intervals, d_plan);
-    launch_sum_rows(ctx->stream, d + kCommGlobalSum, 1, 1, ctx->d_scalars.ptr + kSlotWeightSum, ctx->hd_scalars + kSlotWeightSum);  // (info)
+    launch_sum_rows(ctx->stream, d + kCommGlobalSum, 1, 1, ctx->d_scalars.ptr + kSlotWeightSum, ctx->h_scalars.device + kSlotWeightSum);  // (info)
     MCL_HIP(ctx, hipGetLastError());
     // The ancestor exchange: fixed capacity per pair of ranks (no host read before the cycle's end) where the plain estimate follows -
     // its all-gather carries the overflow flags -, exact counts (one host read) otherwise.
@@ -2100,7 +2075,7 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, Measurement scan, mcl
       ctx->comm_host_syncs += 1;
     } else {
       if (const mcl_status s = sharded_estimate(ctx, nullptr, &est)) return s;
-      if (padded && ctx->h_scalars[kSlotOverflow] != 0.0) {
+      if (padded && ctx->h_scalars.host[kSlotOverflow] != 0.0) {
         // Some rank's requests to one shard did not fit the fixed capacity (every rank reads the same sum of flags and gets here
         // together): the new set is incomplete.  The old one and its CDF are untouched - the commit wrote the other buffer -: back to
         // it, the exchange again with exact counts, the estimate again.
@@ -2122,10 +2097,10 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, Measurement scan, mcl
       stage_end(ctx, MCL_STAGE_ESTIMATE);
     }
     stage_collect(ctx);
-    finish_cycle(ctx, est, mcl_update_info{1, fires, n_total, ctx->h_scalars[kSlotWeightSum], -1.0, ctx->h_scalars[kSlotPolicyP]}, estimate, info);
+    finish_cycle(ctx, est, mcl_update_info{1, fires, n_total, ctx->h_scalars.host[kSlotWeightSum], -1.0, ctx->h_scalars.host[kSlotPolicyP]}, estimate, info);
     return MCL_OK;
   }
-  double* h_sum = ctx->h_comm;  // (comm_host_words)
+  double* h_sum = ctx->h_comm.host;  // (comm_host_words)
   ShardStats* h_stats = reinterpret_cast<ShardStats*>(h_sum + 1);
   MCL_HIP(ctx, hipMemcpyAsync(h_sum, d + kCommGlobalSum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipMemcpyAsync(h_stats, gathered.stats, world * sizeof(ShardStats), hipMemcpyDeviceToHost, ctx->stream));
@@ -2333,12 +2308,11 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
     if (const mcl_status s = ensure_capacity(ctx, cap)) return s;
     MCL_HIP(ctx, ctx->d_scalars.ensure(kScalarSlots));
     MCL_HIP(ctx, hipMemsetAsync(ctx->d_scalars.ptr, 0, kScalarSlots * sizeof(double), ctx->stream));  // incl. the recovery filters
-    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_scalars), kScalarSlots * sizeof(double), hipHostMallocMapped));
-    std::memset(ctx->h_scalars, 0, kScalarSlots * sizeof(double));  // host mirrors are read before their first kernel has written them
-    MCL_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&ctx->hd_scalars), ctx->h_scalars, 0));
+    MCL_HIP(ctx, ctx->h_scalars.ensure(kScalarSlots, /*mapped=*/true));
+    std::memset(ctx->h_scalars.host, 0, kScalarSlots * sizeof(double));  // host mirrors are read before their first kernel has written them
     MCL_HIP(ctx, ctx->d_kld_scalars.ensure(8));
     MCL_HIP(ctx, hipMemsetAsync(ctx->d_kld_scalars.ptr, 0, 8 * sizeof(unsigned long long), ctx->stream));
-    MCL_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->h_kld_scalars), 8 * sizeof(unsigned long long)));
+    MCL_HIP(ctx, ctx->h_kld_scalars.ensure(8, /*mapped=*/false));
     for (auto& pair : ctx->ev)
       for (auto& e : pair) MCL_HIP(ctx, hipEventCreate(&e));
     MCL_HIP(ctx, hipEventCreateWithFlags(&ctx->points_event, hipEventDisableTiming));
@@ -2348,16 +2322,9 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
       if (hipDeviceGetAttribute(&count, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || count <= 0) count = 256;
       ctx->tuning.device_cus = count;
     }
-    // Environment defaults of the per-context switches (mcl_set_option changes them at run time).
-    for (const char* name : {"lf_variant", "lf_fast", "lf_table", "lf_patch", "lf_dispersed", "lf_far_tiles", "key_layout", "lf_loose_below", "lf_small_particles", "device_policy",
-                             "sort_min_particles", "beam_sort_min_particles", "field_build", "key_curve", "key_warp", "key_bits_xy", "lf_margin", "lf_split", "lf_queue_grid", "shard_pad_permille", "lf_queue", "lf_ends_first", "beam_free_ahead", "beam_sectors", "lf_weight_sums", "beam_table", "cycle_spin", "scan_fused", "draw_fold", "lf_unit_weights", "small_fused", "norm_store", "noise_ahead", "order_ahead", "lf_far_beams_per_wave", "batch_cluster_fused", "batch_beam_fused", "draw_key_hist", "rows_merged"}) {
-      std::string env = "BELUGA_MCL_";
-      for (const char* c = name; *c; ++c) env += static_cast<char>(std::toupper(static_cast<unsigned char>(*c)));
-      if (const char* v = std::getenv(env.c_str())) {
-        if (std::string(name) == "lf_table") (void)mcl_set_option(ctx, name, std::string(v) == "cube" ? 1 : std::atoi(v));
-        else (void)mcl_set_option(ctx, name, std::atoi(v));
-      }
-    }
+    // Environment defaults of the per-context switches (mcl_set_option changes them at run time).  Straight into the table: the three
+    // options with a side effect have none here - no communicator yet (comm_agree returns at once), no beam table yet.
+    tuning_from_environment(ctx->tuning, [](const char* name) -> const char* { return std::getenv(name); });
     return MCL_OK;
   };
   st = init();
@@ -2375,68 +2342,16 @@ void mcl_destroy(mcl_ctx* ctx) {
   drop_pending_map(ctx);
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  for (auto& set : ctx->sets) set.release();
-  ctx->map.drop();  // (a private store frees its buffers here; a shared one loses a user)
-  ctx->d_field_scratch.release();
-  ctx->d_points.release();
-  ctx->d_beam_points.release();
-  ctx->d_beam_table.release();
-  ctx->d_chunk.release();
-  ctx->d_scalars.release();
-  ctx->d_cdf.release();
-  ctx->d_cdf_tree.release();
-  ctx->d_lf_wsum.release();
-  ctx->d_scan_state.release();
-  ctx->d_noise.release();
-  ctx->d_cloud.release();
-  ctx->d_est_partials.release();
-  ctx->d_cloud_w.release();
-  ctx->d_hashes.release();
-  ctx->d_table_keys.release();
-  ctx->d_table_first.release();
-  ctx->d_flags.release();
-  ctx->d_uchunk.release();
-  ctx->d_kld_scalars.release();
-  ctx->d_sort_u32.release();
-  ctx->d_route_u32.release();
-  ctx->d_cell_f64.release();
-  ctx->d_cell_u32.release();
-  ctx->d_cell_u64.release();
-  ctx->d_cell_exchange.release();
-  ctx->d_cluster_sums.release();
-  ctx->d_cluster_labels.release();
-  ctx->d_sort_u64.release();
-  ctx->d_sort_f64.release();
-  ctx->d_ndt_grid.release();
-  ctx->d_ndt_cells.release();
-  ctx->d_ndt_keys.release();
-  ctx->d_ndt_est.release();
-  ctx->d_landmarks.release();
   if (ctx->rccl_comm) {
     if (RcclApi* api = rccl_api(nullptr)) (void)api->CommDestroy(ctx->rccl_comm);
   }
-  if (ctx->h_comm) (void)hipHostFree(ctx->h_comm);
-  if (ctx->h_cells) (void)hipHostFree(ctx->h_cells);
-  ctx->d_comm_f64.release();
-  ctx->d_comm_i64.release();
-  ctx->d_targets.release();
-  ctx->d_send_targets.release();
-  ctx->d_requests_in.release();
-  ctx->d_replies_out.release();
-  ctx->d_replies_in.release();
-  ctx->d_route_order.release();
-  ctx->d_cand_states.release();
-  ctx->d_new_shard.release();
-  ctx->d_cand_hashes.release();
-  ctx->d_block_hashes.release();
-  if (ctx->h_points) (void)hipHostFree(ctx->h_points);
   if (ctx->points_event) (void)hipEventDestroy(ctx->points_event);
-  if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);
-  if (ctx->h_kld_scalars) (void)hipHostFree(ctx->h_kld_scalars);
   for (auto& pair : ctx->ev)
     for (auto& e : pair)
       if (e) (void)hipEventDestroy(e);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
+  // Every buffer is a member that frees itself (DeviceBuffer, HostBuffer, the map's hold: a private store frees its buffers, a shared
+  // one loses a user).  Relied on: the device is bound, and the stream was idle before it went - freeing memory takes no stream.
   delete ctx;
 }
 
@@ -2812,9 +2727,9 @@ mcl_status mcl_weight_sum(mcl_ctx* ctx, double* sum) {
   if (!ctx || !sum) return MCL_ERR_INVALID_ARGUMENT;
   if (const mcl_status s = bind_device(ctx)) return s;
   launch_weight_sum(ctx->stream, ctx->cur().w, ctx->n, ctx->chunk_row(0), ctx->d_scalars.ptr + kSlotWeightSum);
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + kSlotWeightSum, ctx->d_scalars.ptr + kSlotWeightSum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_scalars.host + kSlotWeightSum, ctx->d_scalars.ptr + kSlotWeightSum, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *sum = ctx->h_scalars[kSlotWeightSum];
+  *sum = ctx->h_scalars.host[kSlotWeightSum];
   return MCL_OK;
 }
 
@@ -2878,7 +2793,7 @@ static SmallTail small_tail_record(const mcl_ctx* ctx, bool fires) {
   t.fc = ctx->random_source();
   t.pivot_x = ctx->facts.pivot()[0];
   t.pivot_y = ctx->facts.pivot()[1];
-  t.mirror = ctx->hd_scalars;
+  t.mirror = ctx->h_scalars.device;
   t.d_scalars = ctx->d_scalars.ptr;
   return t;
 }
@@ -2895,7 +2810,7 @@ static void small_tail_launched(mcl_ctx* ctx, uint64_t every_n) {
 // the cluster-based kind through two shared launches (batch_cluster_estimates) - then finish_cycle.
 static mcl_update_info small_cycle_state(mcl_ctx* ctx) {
   stage_collect(ctx);
-  const double* h = ctx->h_scalars;
+  const double* h = ctx->h_scalars.host;
   const bool resampled = h[kSlotResampled] != 0.0;
   if (resampled) {
     ctx->live ^= 1;
@@ -2987,7 +2902,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
     // (the completion word only where asked for: measured 10 us per cycle SLOWER than the stream's signal at 2000 particles, round 6)
     ctx->done_armed = ctx->tuning.cycle_spin > 0 && !ctx->profile;
     if (ctx->done_armed) {
-      t.done_flag = reinterpret_cast<unsigned long long*>(ctx->hd_scalars + kSlotDoneWord);
+      t.done_flag = reinterpret_cast<unsigned long long*>(ctx->h_scalars.device + kSlotDoneWord);
       t.done_seq = ++ctx->done_seq;
     }
     stage_begin(ctx, MCL_STAGE_RESAMPLE);
@@ -3008,7 +2923,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
     // :177; the totals of the normalised weights and the recovery estimator (:179, :184-186) ride on the next kernel
     ctx->every_n_current = every_n;
     decision.resample = fires;
-    const RecoveryPolicy policy{ap.alpha_slow, ap.alpha_fast, fires ? 1 : 0, ctx->d_scalars.ptr + kSlotPolicy, ctx->hd_scalars + kSlotPolicy};
+    const RecoveryPolicy policy{ap.alpha_slow, ap.alpha_fast, fires ? 1 : 0, ctx->d_scalars.ptr + kSlotPolicy, ctx->h_scalars.device + kSlotPolicy};
     bool fused = false;  // :177 and the CDF of :188 in one launch (the normalised weights of a set that is resampled at once are not stored)
     if (fires)
       if (const mcl_status s = do_normalize_cdf(ctx, policy, &fused)) return s;
@@ -3021,7 +2936,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
                                 .finalize_norm = true, .cdf_ready = fused};
       if (const mcl_status s = do_resample(ctx, 0.0, ctx->step, nullptr, opt)) return s;  // :188-196
     } else {
-      launch_norm_finalize(ctx->stream, ctx->chunk_row(1), ctx->chunk_row(2), ctx->n, ctx->d_scalars.ptr + kSlotNormSum, ctx->hd_scalars + kSlotNormSum,
+      launch_norm_finalize(ctx->stream, ctx->chunk_row(1), ctx->chunk_row(2), ctx->n, ctx->d_scalars.ptr + kSlotNormSum, ctx->h_scalars.device + kSlotNormSum,
                            &policy);
       MCL_HIP(ctx, hipGetLastError());
     }
@@ -3060,7 +2975,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   }
   if (device_policy) {  // read back together with the estimate
     stats = mirrored_weight_stats(ctx);
-    decision.random_state_probability = ctx->h_scalars[kSlotPolicyP];
+    decision.random_state_probability = ctx->h_scalars.host[kSlotPolicyP];
   }
   const mcl_update_info report{1, decision.resample, ctx->n, stats.sum, decision.ess, decision.random_state_probability};
   finish_cycle(ctx, est, report, estimate, info);  // (cloud.remember: where the ordering keys of the next cycle are centred)
@@ -3101,7 +3016,7 @@ struct mcl_batch {
   hipStream_t stream{nullptr};
   bool own_stream{false};
   std::vector<mcl_ctx*> members;
-  BatchItem* h_items{nullptr};  // the cycle's records, pinned; copied to d_items in front of the three launches
+  HostBuffer<BatchItem> h_items;  // the cycle's records, pinned; copied to d_items in front of the three launches
   DeviceBuffer<BatchItem> d_items;
   std::vector<HeldCycle> held;  // per member, this cycle
   std::vector<uint32_t> fused;  // the members whose cycle the batch launches, in index order
@@ -3110,8 +3025,8 @@ struct mcl_batch {
   std::vector<uint64_t> lf_n, beam_n;  // fused_n of the members of one family, 0 for the other's (each family's reweight launch)
   std::vector<uint32_t> beam_B, first_beam, first_unused;
   // the cluster-based estimate's two shared launches: a record per member and launch, pinned and on the device
-  BatchClusterCells* h_cluster_cells{nullptr};
-  BatchClusterSums* h_cluster_sums{nullptr};
+  HostBuffer<BatchClusterCells> h_cluster_cells;
+  HostBuffer<BatchClusterSums> h_cluster_sums;
   DeviceBuffer<BatchClusterCells> d_cluster_cells;
   DeviceBuffer<BatchClusterSums> d_cluster_sums;
   uint64_t cycles{0}, kernel_launches{0}, members_fused{0}, members_alone{0}, cluster_launches{0}, members_cluster_fused{0};
@@ -3171,13 +3086,13 @@ mcl_status batch_launch(mcl_batch* b) {
     std::fill(b->first_beam.begin(), b->first_beam.end(), 0u);
   }
   for (uint32_t k = 0; k < count; ++k) {
-    BatchItem& it = b->h_items[k];
+    BatchItem& it = b->h_items.host[k];
     it = b->held[b->fused[k]].item;
     it.first_propagate_block = b->first_propagate[k];
     it.first_reweight_block = b->first_reweight[k];
     it.first_beam_block = b->first_beam[k];
   }
-  if (hipMemcpyAsync(b->d_items.ptr, b->h_items, count * sizeof(BatchItem), hipMemcpyHostToDevice, b->stream) != hipSuccess)
+  if (hipMemcpyAsync(b->d_items.ptr, b->h_items.host, count * sizeof(BatchItem), hipMemcpyHostToDevice, b->stream) != hipSuccess)
     return batch_fail(b, MCL_ERR_HIP, "mcl_batch_update: the copy of the cycle's records failed");
   b->kernel_launches += launch_batch_cycle(b->stream, b->d_items.ptr, grid, beam);
   if (beam.blocks) b->beam_launches += 1;
@@ -3219,7 +3134,7 @@ uint32_t batch_cluster_estimates(mcl_batch* b) {
     }
     CellList out = m.f.sc.mapped_dev.list;
     out.size = m.f.sc.arrays.list.size;  // (as collect_cells hands it to the lone kernel)
-    b->h_cluster_cells[b->cluster_count++] = BatchClusterCells{ctx->cur(), static_cast<uint32_t>(ctx->n), m.f.hp, out, m.f.sc.mapped_dev.list.size};
+    b->h_cluster_cells.host[b->cluster_count++] = BatchClusterCells{ctx->cur(), static_cast<uint32_t>(ctx->n), m.f.hp, out, m.f.sc.mapped_dev.list.size};
   }
   const uint32_t count = b->cluster_count;
   if (count == 0) return 0;
@@ -3230,7 +3145,7 @@ uint32_t batch_cluster_estimates(mcl_batch* b) {
   };
   // 3. 4. the cells of every member
   bool cells_out = false, sums_out = false;
-  if (const mcl_status s = batch_cluster_launch(b, b->h_cluster_cells, b->d_cluster_cells, count, launch_batch_small_cluster_cells, &cells_out)) {
+  if (const mcl_status s = batch_cluster_launch(b, b->h_cluster_cells.host, b->d_cluster_cells, count, launch_batch_small_cluster_cells, &cells_out)) {
     drop_all(s);
     return batch_cluster_launches(cells_out ? count : 0, 0);
   }
@@ -3255,16 +3170,16 @@ uint32_t batch_cluster_estimates(mcl_batch* b) {
       continue;
     }
     const MyCells& c = m.f.mine;
-    b->h_cluster_sums[b->summed.size()] = BatchClusterSums{ctx->cur(), static_cast<uint32_t>(ctx->n), m.f.hp, c.dev.list.key, c.dev.cluster, c.m,
+    b->h_cluster_sums.host[b->summed.size()] = BatchClusterSums{ctx->cur(), static_cast<uint32_t>(ctx->n), m.f.hp, c.dev.list.key, c.dev.cluster, c.m,
                                                            *m.f.assigned.winner, ctx->facts.pivot()[0], ctx->facts.pivot()[1],
-                                                           ctx->d_scalars.ptr + kSlotEstimate, ctx->hd_scalars + kSlotEstimate};
+                                                           ctx->d_scalars.ptr + kSlotEstimate, ctx->h_scalars.device + kSlotEstimate};
     b->summed.push_back(k);
   }
   b->cluster_host_ns += static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
   // 6. 7. the sums of every member that has a winner
   const uint32_t summed = static_cast<uint32_t>(b->summed.size());
   if (summed)
-    if (const mcl_status s = batch_cluster_launch(b, b->h_cluster_sums, b->d_cluster_sums, summed, launch_batch_small_cluster_sums, &sums_out)) {
+    if (const mcl_status s = batch_cluster_launch(b, b->h_cluster_sums.host, b->d_cluster_sums, summed, launch_batch_small_cluster_sums, &sums_out)) {
       drop_all(s);
       return batch_cluster_launches(count, sums_out ? summed : 0);
     }
@@ -3318,10 +3233,10 @@ mcl_status mcl_batch_create(const mcl_config* cfgs, uint32_t count, mcl_batch** 
   }
   if (st == MCL_OK) {
     hipError_t e = hipSetDevice(b->device);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b->h_items), count * sizeof(BatchItem), hipHostMallocDefault);
+    if (e == hipSuccess) e = b->h_items.ensure(count, /*mapped=*/false);
     if (e == hipSuccess) e = b->d_items.ensure(count);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b->h_cluster_cells), count * sizeof(BatchClusterCells), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&b->h_cluster_sums), count * sizeof(BatchClusterSums), hipHostMallocDefault);
+    if (e == hipSuccess) e = b->h_cluster_cells.ensure(count, /*mapped=*/false);
+    if (e == hipSuccess) e = b->h_cluster_sums.ensure(count, /*mapped=*/false);
     if (e == hipSuccess) e = b->d_cluster_cells.ensure(count);
     if (e == hipSuccess) e = b->d_cluster_sums.ensure(count);
     if (e != hipSuccess) st = batch_fail(nullptr, e == hipErrorOutOfMemory ? MCL_ERR_OUT_OF_MEMORY : MCL_ERR_HIP,
@@ -3351,14 +3266,8 @@ void mcl_batch_destroy(mcl_batch* batch) {
     ctx->batch = nullptr;
     mcl_destroy(ctx);  // (synchronises the shared stream first)
   }
-  if (batch->h_items) (void)hipHostFree(batch->h_items);
-  if (batch->h_cluster_cells) (void)hipHostFree(batch->h_cluster_cells);
-  if (batch->h_cluster_sums) (void)hipHostFree(batch->h_cluster_sums);
-  batch->d_items.release();
-  batch->d_cluster_cells.release();
-  batch->d_cluster_sums.release();
   if (batch->own_stream && batch->stream) (void)hipStreamDestroy(batch->stream);
-  delete batch;
+  delete batch;  // (its records free themselves: the device is bound, the members' destruction left the stream idle)
 }
 
 const char* mcl_batch_last_error(const mcl_batch* batch) { return batch ? batch->error.c_str() : g_create_error.c_str(); }
@@ -3458,18 +3367,27 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
 
 mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* value) {
   if (!batch || !name || !value) return MCL_ERR_INVALID_ARGUMENT;
+  static constexpr struct {
+    const char* name;
+    uint64_t mcl_batch::*member;
+  } kCounters[] = {
+      {"cycles", &mcl_batch::cycles},
+      {"kernel_launches", &mcl_batch::kernel_launches},
+      {"members_fused", &mcl_batch::members_fused},
+      {"members_alone", &mcl_batch::members_alone},
+      {"cluster_launches", &mcl_batch::cluster_launches},
+      {"members_cluster_fused", &mcl_batch::members_cluster_fused},
+      {"cluster_host_ns", &mcl_batch::cluster_host_ns},
+      {"beam_launches", &mcl_batch::beam_launches},
+      {"members_beam_fused", &mcl_batch::members_beam_fused},
+  };
   const std::string key(name);
-  if (key == "cycles") *value = batch->cycles;
-  else if (key == "kernel_launches") *value = batch->kernel_launches;
-  else if (key == "members_fused") *value = batch->members_fused;
-  else if (key == "members_alone") *value = batch->members_alone;
-  else if (key == "cluster_launches") *value = batch->cluster_launches;
-  else if (key == "members_cluster_fused") *value = batch->members_cluster_fused;
-  else if (key == "cluster_host_ns") *value = batch->cluster_host_ns;
-  else if (key == "beam_launches") *value = batch->beam_launches;
-  else if (key == "members_beam_fused") *value = batch->members_beam_fused;
-  else return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_get_counter: unknown counter " + key);
-  return MCL_OK;
+  for (const auto& c : kCounters) {
+    if (key != c.name) continue;
+    *value = batch->*c.member;
+    return MCL_OK;
+  }
+  return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_get_counter: unknown counter " + key);
 }
 
 mcl_status mcl_update_laser_scan(mcl_ctx* ctx, const double control_pose[4], const mcl_laser_scan* scan, mcl_estimate* estimate,
@@ -3584,9 +3502,9 @@ mcl_status mcl_build_cdf(mcl_ctx* ctx, double* total) {
   }
   if (const mcl_status s = do_build_cdf(ctx)) return s;
   if (total) {
-    MCL_HIP(ctx, hipMemcpyAsync(ctx->h_scalars + kSlotCdfTotal, ctx->d_scalars.ptr + kSlotCdfTotal, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(ctx->h_scalars.host + kSlotCdfTotal, ctx->d_scalars.ptr + kSlotCdfTotal, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *total = ctx->h_scalars[kSlotCdfTotal];
+    *total = ctx->h_scalars.host[kSlotCdfTotal];
   }
   return MCL_OK;
 }
@@ -3818,92 +3736,65 @@ mcl_status mcl_update_point_cloud(mcl_ctx* ctx, const double control_pose[4], co
 mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value) {
   if (!ctx || !name) return MCL_ERR_INVALID_ARGUMENT;
   const std::string key(name);
-  Tuning& t = ctx->tuning;
-  if (key == "lf_variant") t.lf_variant = value == 0 ? kLfWavePerParticle : (value == 1 ? kLfLanePerParticle : (value == 3 ? kLfBeamLanes : kLfSortedLanes));
-  else if (key == "lf_dispersed") t.lf_dispersed = value < 0 ? 0 : static_cast<int>(std::min<int64_t>(value, 2));
-  else if (key == "lf_far_beams_per_wave") t.lf_far_beams_per_wave = value < 0 ? 0 : static_cast<int>(std::min<int64_t>(value, 4096));
-  else if (key == "key_layout") t.key_layout = value < 0 ? -1 : (value ? 1 : 0);
-  else if (key == "lf_far_tiles") t.lf_far_tiles = value < 0 ? 0 : static_cast<int>(std::min<int64_t>(value, 2));
-  else if (key == "lf_loose_below") t.lf_loose_below = static_cast<int>(std::clamp<int64_t>(value, 0, 257));
-  else if (key == "lf_small_particles") t.lf_small_particles = value < 0 ? 0 : static_cast<int>(std::min<int64_t>(value, INT32_MAX));
-  else if (key == "lf_fast") t.lf_fast = value < 0 ? -1 : (value ? 1 : 0);
-  else if (key == "lf_table") t.lf_table = value ? 1 : 0;
-  else if (key == "lf_patch") t.lf_patch = value < 0 || value > 2 ? 1 : static_cast<int>(value);
-  else if (key == "device_policy") {
-    const int before = t.device_policy;
-    t.device_policy = value ? 1 : 0;
-    // On a sharded filter it selects the cycle's collectives: a COLLECTIVE call there - every rank makes it, concurrently, with the
-    // same value, whatever its value was before (a rank that skipped the exchange because nothing changed for IT would leave the
-    // others waiting).  A mismatch leaves the option as it was.
-    if (const mcl_status s = comm_agree(ctx, "mcl_set_option(device_policy)")) {
-      t.device_policy = before;
+  const Tuning before = ctx->tuning;
+  if (!set_tuning(ctx->tuning, name, value)) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, "mcl_set_option: unknown option " + key);
+  if (key == "device_policy" || key == "shard_pad_permille") {
+    // device_policy selects a sharded cycle's collectives, shard_pad_permille the capacity every pair of ranks exchanges (ranks with
+    // different capacities would post all-to-alls of different sizes).  On a sharded filter they are COLLECTIVE calls - every rank makes
+    // them, concurrently, with the same value, whatever its value was before (a rank that skipped the exchange because nothing changed
+    // for IT would leave the others waiting).  A mismatch leaves the option as it was.
+    if (const mcl_status s = comm_agree(ctx, ("mcl_set_option(" + key + ")").c_str())) {
+      ctx->tuning = before;
       return s;
     }
-  }
-  else if (key == "field_build") t.field_build = value ? 1 : 0;
-  else if (key == "key_curve") t.key_curve = value ? 1 : 0;
-  else if (key == "key_warp") t.key_warp = value ? 1 : 0;
-  else if (key == "key_bits_xy") t.key_bits_xy = (value >= 4 && value <= 6) ? static_cast<int>(value) : 0;
-  else if (key == "lf_margin") t.lf_margin = value ? 1 : 0;
-  else if (key == "lf_queue") t.lf_queue = value ? 1 : 0;
-  else if (key == "lf_ends_first") t.lf_ends_first = value ? 1 : 0;
-  else if (key == "beam_free_ahead") t.beam_free_ahead = value ? 1 : 0;
-  else if (key == "beam_sectors") t.beam_sectors = value ? 1 : 0;
-  else if (key == "shard_pad_permille") {
-    // The capacity every pair of ranks exchanges: on a sharded filter a COLLECTIVE call like device_policy (ranks with different
-    // capacities would post all-to-alls of different sizes); a mismatch leaves the option as it was.
-    const int before = t.shard_pad_permille;
-    t.shard_pad_permille = static_cast<int>(std::clamp<int64_t>(value, 0, 8000));
-    if (const mcl_status s = comm_agree(ctx, "mcl_set_option(shard_pad_permille)")) {
-      t.shard_pad_permille = before;
-      return s;
+  } else if (key == "beam_table" && !ctx->tuning.beam_table && ctx->beam_table_ready) {  // its memory goes back at once
+    if (bind_device(ctx) == MCL_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) {
+      ctx->d_beam_table.release();
+      ctx->beam_table_ready = false;
     }
   }
-  else if (key == "lf_queue_grid") t.lf_queue_grid = static_cast<int>(std::clamp<int64_t>(value, 0, 1 << 20));
-  else if (key == "cycle_spin") t.cycle_spin = value < 0 ? -1 : (value ? 1 : 0);
-  else if (key == "beam_table") {
-    t.beam_table = value ? 1 : 0;
-    if (!t.beam_table && ctx->beam_table_ready) {  // its memory goes back at once
-      if (bind_device(ctx) == MCL_OK && hipStreamSynchronize(ctx->stream) == hipSuccess) {
-        ctx->d_beam_table.release();
-        ctx->beam_table_ready = false;
-      }
-    }
-  }
-  else if (key == "lf_weight_sums") t.lf_weight_sums = value ? 1 : 0;
-  else if (key == "scan_fused") t.scan_fused = static_cast<int>(std::clamp<int64_t>(value, 0, 2));
-  else if (key == "draw_fold") t.draw_fold = static_cast<int>(std::clamp<int64_t>(value, 0, 2));
-  else if (key == "lf_unit_weights") t.lf_unit_weights = value ? 1 : 0;
-  else if (key == "small_fused") t.small_fused = value ? 1 : 0;
-  else if (key == "batch_cluster_fused") t.batch_cluster_fused = value ? 1 : 0;
-  else if (key == "batch_beam_fused") t.batch_beam_fused = value ? 1 : 0;
-  else if (key == "norm_store") t.norm_store = value ? 1 : 0;
-  else if (key == "order_ahead") t.order_ahead = value ? 1 : 0;
-  else if (key == "draw_key_hist") t.draw_key_hist = value ? 1 : 0;
-  else if (key == "rows_merged") t.rows_merged = value ? 1 : 0;
-  else if (key == "noise_ahead") t.noise_ahead = static_cast<int>(std::clamp<int64_t>(value, 0, 2));
-  else if (key == "lf_split") t.lf_split = static_cast<int>(value & 3);  // 1: side by side only, 2: stacked only, 3: both
-  else if (key == "sort_min_particles") t.sort_min_particles = static_cast<int>(std::clamp<int64_t>(value, 0, 1ll << 30));
-  else if (key == "beam_sort_min_particles") t.beam_sort_min_particles = static_cast<int>(std::clamp<int64_t>(value, 0, 1ll << 30));
-  else return fail(ctx, MCL_ERR_INVALID_ARGUMENT, "mcl_set_option: unknown option " + key);
   return MCL_OK;
 }
+
+}  // extern "C"
+namespace {
+// The counters that are a member of the context read as it stands; the others follow the table in mcl_get_counter.
+struct Counter {
+  const char* name;
+  uint64_t mcl_ctx::*member;
+};
+constexpr Counter kCounters[] = {
+    {"lf_fast_launches", &mcl_ctx::lf_fast_launches},
+    {"lf_patch_launches", &mcl_ctx::lf_patch_launches},
+    {"lf_queue_launches", &mcl_ctx::lf_queue_launches},
+    {"lf_beams_launches", &mcl_ctx::lf_beams_launches},
+    {"lf_far_launches", &mcl_ctx::lf_far_launches},
+    {"lf_far_beams_launches", &mcl_ctx::lf_far_beams_launches},
+    {"small_tail_launches", &mcl_ctx::small_tail_launches},
+    {"estimate_repivots", &mcl_ctx::estimate_repivots},
+    {"noise_ahead_used", &mcl_ctx::noise_ahead_used},
+    {"order_ahead_used", &mcl_ctx::order_ahead_used},
+    {"order_ahead_missed", &mcl_ctx::order_ahead_missed},
+    {"host_cycles", &mcl_ctx::host_cycles},
+    {"cluster_cells", &mcl_ctx::cluster_cells},
+    {"comm_bytes_out", &mcl_ctx::comm_bytes_out},
+    {"comm_collectives", &mcl_ctx::comm_collectives},
+    {"comm_host_syncs", &mcl_ctx::comm_host_syncs},
+    {"comm_overflows", &mcl_ctx::comm_overflows},
+    {"comm_ranks_seen", &mcl_ctx::comm_ranks_seen},
+};
+}  // namespace
+extern "C" {
 
 mcl_status mcl_get_counter(mcl_ctx* ctx, const char* name, uint64_t* value) {
   if (!ctx || !name || !value) return MCL_ERR_INVALID_ARGUMENT;
   const std::string key(name);
-  if (key == "lf_fast_launches") *value = ctx->lf_fast_launches;
-  else if (key == "lf_patch_launches") *value = ctx->lf_patch_launches;
-  else if (key == "lf_queue_launches") *value = ctx->lf_queue_launches;
-  else if (key == "lf_beams_launches") *value = ctx->lf_beams_launches;
-  else if (key == "lf_far_launches") *value = ctx->lf_far_launches;
-  else if (key == "lf_far_beams_launches") *value = ctx->lf_far_beams_launches;
-  else if (key == "small_tail_launches") *value = ctx->small_tail_launches;
-  else if (key == "estimate_repivots") *value = ctx->estimate_repivots;
-  else if (key == "lf_far_tiles") *value = ctx->map->far_tiles;
-  else if (key == "noise_ahead_used") *value = ctx->noise_ahead_used;
-  else if (key == "order_ahead_used") *value = ctx->order_ahead_used;
-  else if (key == "order_ahead_missed") *value = ctx->order_ahead_missed;
+  for (const Counter& c : kCounters) {
+    if (key != c.name) continue;
+    *value = ctx->*c.member;
+    return MCL_OK;
+  }
+  if (key == "lf_far_tiles") *value = ctx->map->far_tiles;
   else if (key == "lf_patch_groups_planned" || key == "lf_patch_groups_through") {
     if (const mcl_status s = bind_device(ctx)) return s;
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -3915,17 +3806,10 @@ mcl_status mcl_get_counter(mcl_ctx* ctx, const char* name, uint64_t* value) {
   else if (key == "host_ns_other_launches") *value = ctx->host_ns[1];
   else if (key == "host_ns_wait") *value = ctx->host_ns[2];
   else if (key == "host_ns_after_wait") *value = ctx->host_ns[3];
-  else if (key == "host_cycles") *value = ctx->host_cycles;
   else if (key == "field_build_us") *value = static_cast<uint64_t>(ctx->map->field_build_ms * 1e3);  // kernels of the last device field build
   else if (key == "field_built_on_device") *value = ctx->map->field_built_on_device ? 1 : 0;
   else if (key == "map_device_bytes") *value = ctx->map.shared() ? 0 : ctx->map->device_bytes();  // what the context itself owns for its map
   else if (key == "map_shared") *value = ctx->map.shared() ? 1 : 0;
-  else if (key == "cluster_cells") *value = ctx->cluster_cells;
-  else if (key == "comm_bytes_out") *value = ctx->comm_bytes_out;
-  else if (key == "comm_collectives") *value = ctx->comm_collectives;
-  else if (key == "comm_host_syncs") *value = ctx->comm_host_syncs;
-  else if (key == "comm_overflows") *value = ctx->comm_overflows;
-  else if (key == "comm_ranks_seen") *value = ctx->comm_ranks_seen;
   else if (key == "comm_backend") *value = static_cast<uint64_t>(ctx->comm_backend);
   else return fail(ctx, MCL_ERR_INVALID_ARGUMENT, "mcl_get_counter: unknown counter " + key);
   return MCL_OK;
@@ -4075,7 +3959,7 @@ mcl_status mcl_build_ndt_map_from_points(mcl_ctx* ctx, const double* points_xy, 
   MCL_REQUIRE(ctx, std::isfinite(resolution) && resolution > 0.0, "mcl_build_ndt_map_from_points: resolution must be positive and finite");
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a reweight in flight may still read the old map)
-  ScopedBuffer<double> d_pts;
+  DeviceBuffer<double> d_pts;
   MCL_HIP(ctx, d_pts.ensure(static_cast<size_t>(2) * n));
   MCL_HIP(ctx, hipMemcpy(d_pts.ptr, points_xy, static_cast<size_t>(2) * n * sizeof(double), hipMemcpyHostToDevice));
   return ndt_build_from_device_points(ctx, "mcl_build_ndt_map_from_points", d_pts.ptr, n, resolution);
@@ -4095,9 +3979,9 @@ mcl_status mcl_build_ndt_map_from_grid(mcl_ctx* ctx, const int8_t* cells, uint32
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const uint32_t count = width * height;
   constexpr int8_t kOccupied = 100;  // the default value traits' occupied_value (mcl_set_map with traits == NULL)
-  ScopedBuffer<int8_t> d_cells;
-  ScopedBuffer<uint32_t> d_offsets;
-  ScopedBuffer<double> d_pts;
+  DeviceBuffer<int8_t> d_cells;
+  DeviceBuffer<uint32_t> d_offsets;
+  DeviceBuffer<double> d_pts;
   MCL_HIP(ctx, d_cells.ensure(count));
   MCL_HIP(ctx, d_offsets.ensure(static_cast<size_t>(count) + num_chunks(count) + 1));
   MCL_HIP(ctx, hipMemcpy(d_cells.ptr, cells, count, hipMemcpyHostToDevice));
@@ -4224,10 +4108,10 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset) 
   if (!ctx || !cells) return MCL_ERR_INVALID_ARGUMENT;
   if (const mcl_status s = bind_device(ctx)) return s;
   unsigned long long* d_steps = ctx->d_kld_scalars.ptr + kKldBeamSteps;
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars + kKldBeamSteps, d_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars.host + kKldBeamSteps, d_steps, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   if (reset) MCL_HIP(ctx, hipMemsetAsync(d_steps, 0, sizeof(unsigned long long), ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *cells = ctx->h_kld_scalars[kKldBeamSteps];
+  *cells = ctx->h_kld_scalars.host[kKldBeamSteps];
   return MCL_OK;
 }
 

@@ -22,6 +22,11 @@ template <class T>
 struct DeviceBuffer {
   T* ptr{nullptr};
   size_t count{0};
+  DeviceBuffer() = default;
+  DeviceBuffer(const DeviceBuffer&) = delete;
+  DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+  // (hipFree takes no stream: the owner sees to it that the device is bound and that nothing on it still reads the memory)
+  ~DeviceBuffer() { release(); }
   hipError_t ensure(size_t n) {
     if (n <= count) return hipSuccess;
     if (ptr) (void)hipFree(ptr);
@@ -45,8 +50,39 @@ struct DeviceBuffer {
   uint64_t bytes() const { return static_cast<uint64_t>(count) * sizeof(T); }
 };
 
+// Pinned host memory, and - mapped - the address the device sees it at.
+template <class T>
+struct HostBuffer {
+  T* host{nullptr};
+  T* device{nullptr};
+  size_t count{0};
+  HostBuffer() = default;
+  HostBuffer(const HostBuffer&) = delete;
+  HostBuffer& operator=(const HostBuffer&) = delete;
+  ~HostBuffer() { release(); }
+  hipError_t ensure(size_t n, bool mapped) {
+    if (n <= count) return hipSuccess;
+    release();
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), n * sizeof(T), mapped ? hipHostMallocMapped : hipHostMallocDefault);
+    if (e == hipSuccess && mapped) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&device), host, 0);
+    if (e == hipSuccess) count = n;
+    return e;
+  }
+  void release() {
+    if (host) (void)hipHostFree(host);
+    host = device = nullptr;
+    count = 0;
+  }
+};
+
 struct MapStore {
   MapStoreKey key{0, MCL_SENSOR_LIKELIHOOD_FIELD, {}};
+  struct Rebind {  // (see ~MapStore)
+    int device{-1};
+    ~Rebind() {
+      if (device >= 0) (void)hipSetDevice(device);
+    }
+  } rebind;
   // geometry
   uint32_t W{0}, H{0};
   double resolution{0};
@@ -81,13 +117,13 @@ struct MapStore {
   MapStore() = default;
   MapStore(const MapStore&) = delete;
   MapStore& operator=(const MapStore&) = delete;
+  // Binds the store's device for the buffers' destructors, which run behind this body; `rebind`, declared in front of every buffer and
+  // so destroyed behind them all, gives the caller its device back.
   ~MapStore() {
     if (!device_bytes()) return;
     int current = 0;
-    const bool restore = hipGetDevice(&current) == hipSuccess && current != key.device;
+    if (hipGetDevice(&current) == hipSuccess && current != key.device) rebind.device = current;
     (void)hipSetDevice(key.device);
-    release_device();
-    if (restore) (void)hipSetDevice(current);
   }
 
   uint64_t device_bytes() const {
@@ -109,19 +145,6 @@ struct MapStore {
     d_far_votes.take(old.d_far_votes);
     d_far_linear.take(old.d_far_linear);
     h_field.swap(old.h_field);
-  }
-  void release_device() {
-    d_cells.release();
-    d_free.release();
-    d_nonfree_bits.release();
-    d_field.release();
-    d_cube.release();
-    d_pal_idx.release();
-    d_pal_val.release();
-    d_pal_keys.release();
-    d_far_bits.release();
-    d_far_votes.release();
-    d_far_linear.release();
   }
 };
 

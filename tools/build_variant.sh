@@ -30,21 +30,20 @@ common="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused
 /opt/rocm/bin/hipcc $common -x hip -c $src/kernels.hip -o $out/kernels.o
 beam=""   # (the beam model's kernels are a translation unit of their own from round 5 on; older revisions have them inside kernels.hip)
 if [ -f $src/beam_kernels.hip ]; then /opt/rocm/bin/hipcc $common -x hip -c $src/beam_kernels.hip -o $out/beam_kernels.o; beam=$out/beam_kernels.o; fi
+# Every other translation unit: the list is beluga_amd.build's SOURCES, so a file added there needs no edit here.  A revision's own tree
+# is compiled name by name, skipping what that revision lacks (older revisions have the later files' code inside context.hip).
+units=$(cd $root && python -c "from beluga_amd.build import SOURCES; print(' '.join(s for s in SOURCES if s not in ('kernels.hip', 'beam_kernels.hip')))")
+rest=""
 if [ -n "$tree" ]; then
-  /opt/rocm/bin/hipcc $common -x hip -c $src/context.hip -o $out/context.o
-  /opt/rocm/bin/hipcc $common -c $src/map_build.cpp -o $out/map_build.o
-  /opt/rocm/bin/hipcc $common -c $src/cluster_host.cpp -o $out/cluster_host.o
-  host=""   # (the sensor models' and the cycle's host passes are translation units of their own; older revisions have them inside context.hip)
-  for f in ndt_host landmark_host scan_host cycle_host batch_host map_store_host; do
-    if [ -f $src/$f.cpp ]; then /opt/rocm/bin/hipcc $common -c $src/$f.cpp -o $out/$f.o; host="$host $out/$f.o"; fi
+  for f in $units; do
+    [ -f $src/$f ] || continue
+    case $f in *.hip) lang="-x hip";; *) lang="";; esac
+    /opt/rocm/bin/hipcc $common $lang -c $src/$f -o $out/${f%.*}.o
+    rest="$rest $out/${f%.*}.o"
   done
-  for f in ndt_kernels ndt_build_kernels landmark_kernels; do
-    if [ -f $src/$f.hip ]; then /opt/rocm/bin/hipcc $common -x hip -c $src/$f.hip -o $out/$f.o; host="$host $out/$f.o"; fi
-  done
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libbeluga_mcl.so $out/kernels.o $beam $out/context.o $out/map_build.o $out/cluster_host.o $host
 else
   [ -f $root/beluga_amd/lib/context.o ] || python -m beluga_amd.build
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libbeluga_mcl.so $out/kernels.o $beam $root/beluga_amd/lib/context.o $root/beluga_amd/lib/map_build.o $root/beluga_amd/lib/cluster_host.o \
-    $root/beluga_amd/lib/ndt_host.o $root/beluga_amd/lib/landmark_host.o $root/beluga_amd/lib/scan_host.o $root/beluga_amd/lib/cycle_host.o
+  for f in $units; do rest="$rest $root/beluga_amd/lib/${f%.*}.o"; done
 fi
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libbeluga_mcl.so $out/kernels.o $beam $rest
 echo built $out/libbeluga_mcl.so
