@@ -118,6 +118,13 @@ struct mcl_ctx {
   SetFacts facts;                   // what the host knows about the live set, and every event that changes it (set_facts.h)
   DeviceBuffer<double> d_lf_wsum;   // sums of the new weights per workgroup of the LF patch kernel (PatchStats::weight_sums; facts.lf_sums() of them)
   DeviceBuffer<double> d_noise;     // k_noise_ahead: the propagation normals drawn behind the previous cycle (facts.noise_ahead_serves)
+  // Likelihood-field contexts: world_to_field * pose of every particle of the live set (FieldPoseOut; facts.field_poses_current(map_generation)
+  // says whether it describes the set), [capacity]; map_generation counts the maps the context has been given - every change of world_to_field
+  DeviceBuffer<double4> d_field_pose;
+  uint64_t map_generation{0};
+  uint64_t field_pose_rebuilds{0};  // launches of k_field_pose (mcl_get_counter)
+  bool lf_kind() const { return cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD || cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB; }
+  FieldPoseOut field_pose_out() const { return FieldPoseOut{d_field_pose.ptr, map->origin_inverse}; }
   // launch_order_ahead: the spatial order (sort_scratch().perm) that facts.take_order_ahead answers for holds if the control action of that
   // step is the predicted one
   DiffDriveSampler order_sampler{};
@@ -381,6 +388,7 @@ mcl_status ensure_capacity(mcl_ctx* ctx, uint64_t cap) {
   MCL_HIP(ctx, ctx->d_cdf.ensure(cap));
   MCL_HIP(ctx, ctx->d_cdf_tree.ensure(cdf_tree_doubles(cap)));
   MCL_HIP(ctx, ctx->d_lf_wsum.ensure(cap / 448 + 2));
+  if (ctx->lf_kind()) MCL_HIP(ctx, ctx->d_field_pose.ensure(cap));
   if (!ctx->d_scan_state.ptr) {
     MCL_HIP(ctx, ctx->d_scan_state.ensure(kScanStateWords));
     MCL_HIP(ctx, hipMemset(ctx->d_scan_state.ptr, 0, kScanStateWords * sizeof(unsigned long long)));
@@ -845,7 +853,7 @@ struct HeldCycle {
 void launch_held_propagate(mcl_ctx* ctx, HeldCycle* hold) {
   const BatchItem& it = hold->item;
   launch_propagate(ctx->stream, it.p, it.n, it.smp, it.seed, it.step, it.index_offset, it.scan_src, it.scan_dst, it.scan_doubles, nullptr, nullptr,
-                   nullptr, 0);
+                   nullptr, 0, it.field_out);
   hold->propagate_held = false;
 }
 // fused (mcl_update): the scan staged by stage_points is pulled by the same kernel, and the ordering keys of the new poses
@@ -872,6 +880,9 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
   const bool keys = !use_ahead && keys_emitted && ctx->wants_ordering() && ctx->predict_key_frame(&sampler, &frame);
   // (the normals of this step, if the previous cycle left them: k_noise_ahead)
   const bool ahead = ctx->d_noise.ptr && ctx->n > 65536 && ctx->facts.noise_ahead_serves(step, ctx->n, ctx->cfg.seed, ctx->cfg.shard_offset);
+  // (the new poses' field-frame form beside them: the reweight that follows loads it)
+  const bool field_poses = propagation_writes_field_poses(ctx->tuning, ctx->d_field_pose.ptr != nullptr, ctx->have_map);
+  const FieldPoseOut field_out = field_poses ? ctx->field_pose_out() : FieldPoseOut{nullptr, pose_identity()};
   // (launch_propagate takes k_propagate_small for these arguments: no keys, at most 65536 particles)
   if (hold && !keys && !ahead && ctx->n >= 1 && ctx->n <= kBatchMaxParticles && !ctx->profile) {
     BatchItem& it = hold->item;
@@ -884,12 +895,16 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
     it.scan_src = scan_doubles ? ctx->h_points.device : nullptr;
     it.scan_dst = scan_doubles ? ctx->d_points.ptr : nullptr;
     it.scan_doubles = static_cast<uint32_t>(scan_doubles);
+    it.field_out = field_out;
     hold->propagate_held = true;
   } else {
     launch_propagate(ctx->stream, ctx->cur(), ctx->n, sampler, ctx->cfg.seed, step, ctx->cfg.shard_offset,
                      scan_doubles ? ctx->h_points.device : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
-                     keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->facts.noise_ahead_count());
+                     keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->facts.noise_ahead_count(),
+                     field_out);
   }
+  if (field_poses) ctx->facts.field_poses_written(ctx->map_generation);
+  else ctx->facts.poses_moved();
   if (ahead) ctx->noise_ahead_used += 1;
   if (scan_doubles) points_pulled(ctx, false);
   if (keys_emitted) *keys_emitted = keys;
@@ -943,6 +958,8 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
   const bool have_order = ctx->facts.take_order_accepted();  // (launch_order_ahead's, accepted by this cycle's propagation)
   const bool lf_kind = !ctx->off_grid() && ctx->cfg.sensor_kind != MCL_SENSOR_BEAM;
   LfReweightArgs lf_args{};
+  const FieldPosePlan field_poses = lf_kind ? field_pose_plan(ctx->tuning, ctx->d_field_pose.ptr != nullptr, ctx->facts, ctx->map_generation)
+                                            : FieldPosePlan{false, false};
   if (lf_kind)
     lf_args = LfReweightArgs{.p = ctx->cur(), .n = ctx->n, .f = ctx->field_view(), .d_points = ctx->d_points.ptr, .B = static_cast<uint32_t>(B),
                              .sort = ordered ? &sort : nullptr, .patches = mode.patches, .beams = mode.beams,
@@ -952,7 +969,8 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
                                                  reinterpret_cast<unsigned long long*>(ctx->h_scalars.device + kSlotPatchMirror),
                                                  static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
                                                  static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
-                                                 reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)}};
+                                                 reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)},
+                             .field_pose = field_poses.load ? ctx->d_field_pose.ptr : nullptr};
   if (hold && hold->propagate_held) {  // mcl_batch_update: is this member's cycle the small one?  If not, its propagation goes out now
     hold->fused = lf_kind && batch_member_fused(BatchMemberFacts{
                                  ctx->cfg.sensor_kind, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0, ctx->n,
@@ -982,11 +1000,19 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
     else launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
+    const bool held = hold && hold->fused;
+    if (field_poses.rebuild_first && !held) {  // the set's poses were not written by a propagation of this map's: k_field_pose first
+      launch_field_pose(ctx->stream, ctx->cur().pose, ctx->n, ctx->field_pose_out());
+      ctx->facts.field_poses_written(ctx->map_generation);
+      ctx->field_pose_rebuilds += 1;
+    }
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
     LfLaunch launched{LfKernel::kBeams, 0};  // (a held cycle: the batch launches k_batch_reweight_lf_beams)
-    if (hold && hold->fused) {
+    if (held) {
       hold->item.f = lf_args.f;
       hold->item.B = lf_args.B;
+      // (a held cycle's own propagation writes the field-frame poses in the batch's launch; without them the kernel forms the product)
+      hold->item.field_pose = field_poses.rebuild_first ? nullptr : lf_args.field_pose;
     } else {
       launched = launch_reweight_lf(ctx->stream, lf_args, ctx->tuning);
     }
@@ -2459,6 +2485,7 @@ mcl_status set_map_impl(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint3
   if (const std::shared_ptr<MapStore> old = ctx->map.take_private()) store->take_buffers(*old);
   ctx->map.drop();
   ctx->have_map = false;
+  ctx->map_generation += 1;  // (mcl_set_map and the swap of a map built ahead: another world_to_field)
   store->key = MapStoreKey{ctx->device, ctx->cfg.sensor_kind, ctx->cfg.lf};
   const MapSource in{cells, width, height, resolution, origin, value_traits, ctx->tuning.field_build, prebuilt_field};
   std::string err;
@@ -2530,6 +2557,7 @@ mcl_status mcl_set_likelihood_field(mcl_ctx* ctx, const float* field) {
   const std::shared_ptr<MapStore> old = ctx->map.take_private();
   if (!old) return fail(ctx, MCL_ERR_NOT_READY, "set the map first");
   ctx->have_map = false;
+  ctx->map_generation += 1;
   auto store = std::make_shared<MapStore>();
   store->take_buffers(*old);
   store->key = old->key;
@@ -2635,6 +2663,7 @@ mcl_status mcl_use_shared_map(mcl_ctx* ctx, mcl_shared_map* map) {
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // nothing of the context reads the old store any more
   ctx->map.attach(map->store);
+  ctx->map_generation += 1;
   map_installed(ctx);
   return MCL_OK;
 }
@@ -3775,6 +3804,7 @@ constexpr Counter kCounters[] = {
     {"noise_ahead_used", &mcl_ctx::noise_ahead_used},
     {"order_ahead_used", &mcl_ctx::order_ahead_used},
     {"order_ahead_missed", &mcl_ctx::order_ahead_missed},
+    {"field_pose_rebuilds", &mcl_ctx::field_pose_rebuilds},
     {"host_cycles", &mcl_ctx::host_cycles},
     {"cluster_cells", &mcl_ctx::cluster_cells},
     {"comm_bytes_out", &mcl_ctx::comm_bytes_out},

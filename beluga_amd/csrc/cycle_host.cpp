@@ -352,4 +352,13 @@ bool estimate_needs_repivot(const double sums[12]) {
   return (1.0 + kRepivotMultiple) * m2 > kRepivotMultiple * second;
 }
 
+bool propagation_writes_field_poses(const Tuning& tuning, bool have_buffer, bool have_map) {
+  return tuning.lf_pose_ahead != 0 && have_buffer && have_map;
+}
+
+FieldPosePlan field_pose_plan(const Tuning& tuning, bool have_buffer, const SetFacts& facts, uint64_t map_generation) {
+  if (tuning.lf_pose_ahead == 0 || !have_buffer) return FieldPosePlan{false, false};
+  return FieldPosePlan{true, !facts.field_poses_current(map_generation)};
+}
+
 }  // namespace mcl

@@ -8,6 +8,7 @@
 #include "beluga_mcl.h"
 #include "cycle_types.h"
 #include "se2.h"
+#include "set_facts.h"
 
 namespace mcl {
 
@@ -146,6 +147,18 @@ class LfPlanner {
   bool decided_{false};
   Mode mode_{false, false};
 };
+
+// ---- the field-frame poses of the live set (option lf_pose_ahead) --------------------------------------------------------------------
+// world_to_field * pose, what every likelihood-field kernel starts from, is kept per particle in a buffer of the context (FieldPoseOut,
+// kernels.h; likelihood-field contexts alone have one) and SetFacts knows whether it describes the live set under the current map.
+// Does a propagation store them beside the poses it writes?  With the option on, where there is a buffer and a map whose frame they are
+// taken in.  It then reports field_poses_written(generation), otherwise poses_moved.
+bool propagation_writes_field_poses(const Tuning& tuning, bool have_buffer, bool have_map);
+// What a likelihood-field launch does: `load` - its kernel reads the buffer instead of forming the product; `rebuild_first` - and
+// k_field_pose fills it before (the set's poses were written by something that stores none - a resampling, an exchange,
+// mcl_set_particles, an initialisation - or the map has changed since).  The steady propagate -> reweight cycle never rebuilds.
+struct FieldPosePlan { bool load, rebuild_first; };
+FieldPosePlan field_pose_plan(const Tuning& tuning, bool have_buffer, const SetFacts& facts, uint64_t map_generation);
 
 // ---- policies (amcl_core.hpp:170-186) ------------------------------------------------------------------------------------------------
 // algorithm/exponential_filter.hpp:32-44

@@ -123,6 +123,10 @@ struct Tuning {
   int small_fused = 1;              // sets of up to 4096 particles (plain estimate, one context): everything behind the reweight - normalise,
                                     // policies, fixed-size or KLD resampling, estimate sums - in one launch of one workgroup and one host
                                     // synchronisation (k_small_tail); 0 = the kernels of the large path
+  int lf_pose_ahead = 1;            // likelihood-field models: world_to_field * pose of every particle is stored by the propagation that writes the
+                                    // pose (k_field_pose for a set nothing has propagated) and the LF kernels load it; 0 = every LF kernel forms
+                                    // the product itself, per particle and launch.  The same expression on the same values: bit-identical.
+                                    // Measured: profiles/field_pose_ab.txt.
   int lf_unit_weights = 1;          // LF patch kernel on a set whose weights are all 1.0 (fresh from a resampling or an initialisation):
                                     // the old weight is not loaded (1.0 x = x: bit-identical); 0 = always loaded
 };

@@ -26,6 +26,14 @@ struct Particles {
   double* w;
 };
 
+// Where a kernel that writes poses into the live set also leaves their field-frame form, world_to_field * pose as (cos, sin, x, y) with
+// the host's bits (se2.h pose_mul_ieee), indexed like Particles::pose - what every likelihood-field kernel starts from (option
+// lf_pose_ahead).  pose == nullptr: nowhere (another sensor model, or the option is off).
+struct FieldPoseOut {
+  double4* pose;
+  Pose2 world_to_field;  // FieldView::world_to_field of the map the poses will be read against
+};
+
 struct FieldView {
   const float* data;
   uint32_t W, H;
@@ -284,7 +292,10 @@ constexpr uint64_t kLfSegmentedBelow = 262144;  // particles
 void launch_propagate(hipStream_t st, Particles p, uint64_t n, DiffDriveSampler smp, uint64_t seed, uint32_t step,
                       uint64_t index_offset, const double* scan_src = nullptr, double* scan_dst = nullptr, uint32_t scan_doubles = 0,
                       const SortScratch* sort = nullptr, const KeyFrame* frame = nullptr, const double* normals_ahead = nullptr,
-                      uint64_t normals_stride = 0);
+                      uint64_t normals_stride = 0, FieldPoseOut field = FieldPoseOut{nullptr, Pose2{Rot2{1.0, 0.0}, 0.0, 0.0}});
+// field.pose[i] = world_to_field * pose[i], i < n, as a propagation with `field` leaves it: the rebuild for a set whose poses something
+// else has written (k_field_pose; cycle_host.h field_pose_plan says when).
+void launch_field_pose(hipStream_t st, const double4* pose, uint64_t n, const FieldPoseOut& field);
 // The propagation's standard normals per particle for `step`, drawn ahead of the cycle that uses them (k_noise_ahead: the three the motion
 // models use, as three arrays of n doubles): launch_propagate(..., normals_ahead, stride = that n) then reads them instead of drawing (not the
 // small-set kernel).  Same bits.
@@ -330,6 +341,7 @@ struct LfReweightArgs {
   double scan_cells;    // max |x| + |y| of the scan points in cells (NaN: unknown); the FMA variant needs fewer than 8192
   bool unit_weights;    // every old weight is 1.0 (the patch and far-beams kernels do not load them)
   PatchStats stats;
+  const double4* field_pose;  // the field-frame poses of p, current (FieldPoseOut): the kernels load them; nullptr: they form the product
 };
 // The kernel that ran: k_reweight_lf_patch<false> / <true>, _far_beams, _palette<true, true> / <true> / <false>, _sorted<true> /
 // <false> over the order, _beams, _sorted<false> in index order.  The first five are the FMA variant.
@@ -551,6 +563,8 @@ struct BatchItem {
   const double* scan_src;  // the member's staged scan in mapped host memory (nullptr: an empty scan, nothing pulled)
   double* scan_dst;        // ... and where the reweight reads it
   uint32_t scan_doubles;
+  FieldPoseOut field_out;      // ... and where it leaves the field-frame poses (a likelihood-field member with lf_pose_ahead; else null)
+  const double4* field_pose;   // k_reweight_lf_beams' field-frame poses (nullptr: it forms them)
   FieldView f;  // k_reweight_lf_beams' arguments (its points are scan_dst); a beam member's stays zero
   uint32_t B;   // the scan's points, of either family
   SmallTailArgs tail;

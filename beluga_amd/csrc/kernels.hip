@@ -252,21 +252,32 @@ __device__ __forceinline__ Pose2 propagate_one(const Pose2& state, const DiffDri
   return propagate_with_normals(state, smp, z0, z1, z2);
 }
 
+// world_to_field * state as the likelihood-field kernels want it (FieldPoseOut, kernels.h): formed where a pose is written - the
+// propagation holds it in registers and its vector units wait for memory - instead of once per particle in every LF launch.
+__device__ __forceinline__ double4 field_pose_record(const Pose2& world_to_field, const Pose2& state) {
+  const Pose2 T = pose_mul_ieee(world_to_field, state);  // (the host's bits: the product's last bit decides cells)
+  return double4{T.r.c, T.r.s, T.x, T.y};
+}
+
 // Small sets (no ordering keys): one particle per lane, 256 per workgroup - 2000 particles are 8 workgroups on 8 CUs, a wave
 // per SIMD, instead of one workgroup of the chunked kernel working through them on one (256 lanes rather than 64 for the sake
 // of the scan pull, which is bound by the reads in flight over PCIe).
 // (the body: block `block` of `blocks` of ONE set - the grid's own numbers in k_propagate_small, a member's local ones in k_batch_propagate)
 __device__ __forceinline__ void propagate_small_block(uint32_t block, uint32_t blocks, const Particles& p, uint64_t n, const DiffDriveSampler& smp,
                                                       uint64_t seed, uint32_t step, uint64_t index_offset, const double* __restrict__ scan_src,
-                                                      double* __restrict__ scan_dst, uint32_t scan_doubles) {
+                                                      double* __restrict__ scan_dst, uint32_t scan_doubles, const FieldPoseOut& field) {
   if (scan_dst && block == blocks - 1) pull_scan(scan_src, scan_dst, scan_doubles);
   const uint64_t i = static_cast<uint64_t>(block) * kBlock + threadIdx.x;
-  if (i < n) store_pose(p, i, propagate_one(load_pose(p, i), smp, seed, step, index_offset + i));
+  if (i < n) {
+    const Pose2 out = propagate_one(load_pose(p, i), smp, seed, step, index_offset + i);
+    store_pose(p, i, out);
+    if (field.pose) field.pose[i] = field_pose_record(field.world_to_field, out);  // (uniform)
+  }
 }
 __global__ __launch_bounds__(kBlock) void k_propagate_small(Particles p, uint64_t n, DiffDriveSampler smp, uint64_t seed, uint32_t step,
                                                            uint64_t index_offset, const double* __restrict__ scan_src,
-                                                           double* __restrict__ scan_dst, uint32_t scan_doubles) {
-  propagate_small_block(blockIdx.x, gridDim.x, p, n, smp, seed, step, index_offset, scan_src, scan_dst, scan_doubles);
+                                                           double* __restrict__ scan_dst, uint32_t scan_doubles, FieldPoseOut field) {
+  propagate_small_block(blockIdx.x, gridDim.x, p, n, smp, seed, step, index_offset, scan_src, scan_dst, scan_doubles, field);
 }
 
 // 512 threads, four particles each: at the kernel's 100 registers a CU holds 16 waves - one workgroup of 1024 threads (round 4: 489
@@ -277,7 +288,7 @@ __global__ __launch_bounds__(kPropBlock) void k_propagate(Particles p, uint64_t 
                                                       uint64_t index_offset, const double* __restrict__ scan_src,
                                                       double* __restrict__ scan_dst, uint32_t scan_doubles, KeyFrame kf,
                                                       uint32_t* __restrict__ keys, uint32_t* __restrict__ table, uint32_t nblocks,
-                                                      const double* __restrict__ normals_ahead, uint64_t normals_stride) {
+                                                      const double* __restrict__ normals_ahead, uint64_t normals_stride, FieldPoseOut field) {
   __shared__ uint32_t hist[kKeys ? kSortDigits : 1];
   if (kKeys) {
     for (uint32_t d = threadIdx.x; d < kSortDigits; d += kPropBlock) hist[d] = 0;
@@ -291,6 +302,7 @@ __global__ __launch_bounds__(kPropBlock) void k_propagate(Particles p, uint64_t 
     if (i >= n) break;
     const Pose2 out = propagate_one(load_pose(p, i), smp, seed, step, index_offset + i, normals_ahead, i, normals_stride);
     store_pose(p, i, out);
+    if (field.pose) field.pose[i] = field_pose_record(field.world_to_field, out);  // (uniform; 32 more bytes stored per particle)
     if (kKeys) {
       const uint32_t key = order_key(double4{out.r.c, out.r.s, out.x, out.y}, kf);
       keys[i] = key;
@@ -389,20 +401,34 @@ __device__ __forceinline__ double lf_cube_fetch(__amdgpu_buffer_rsrc_t rsrc, con
 // order — same terms, fixed association, bit-reproducible, differs from the whole-scan sum only in rounding.
 // The pose of the particle at a position of the spatial order, moved into the table's frame.  A 32-byte record gather
 // per lane, once per kernel (the ordering passes move 8 bytes per particle, not the poses).
-__device__ __forceinline__ Pose2 ordered_pose(const Pose2& to_frame, const double4* __restrict__ pose, uint64_t i) {
+// `ahead` (launch-uniform; option lf_pose_ahead): `pose` is the buffer of FIELD-FRAME poses - the same product, formed once per set of
+// poses by the propagation that wrote them (field_pose_record) or by k_field_pose - and the gather is all there is to do; otherwise the
+// particles' own poses, and the product is formed here.  The same expression on the same values either way: the same bits.
+__device__ __forceinline__ Pose2 ordered_pose(const Pose2& to_frame, const double4* __restrict__ pose, uint64_t i, bool ahead) {
   const double4 q = pose[i];
-  return pose_mul_ieee(to_frame, Pose2{Rot2{q.x, q.y}, q.z, q.w});  // (the host's bits: the product's last bit decides cells)
+  if (ahead) return Pose2{Rot2{q.x, q.y}, q.z, q.w};
+  return pose_mul_ieee(to_frame, Pose2{Rot2{q.x, q.y}, q.z, q.w});
+}
+// The rebuild on demand: a live set whose poses no propagation has just written (a resampling, an exchange, mcl_set_particles, an
+// initialisation) or whose map frame has changed, in front of an LF launch that reads the buffer.  A thread per particle, coalesced.
+__global__ __launch_bounds__(kBlock) void k_field_pose(const double4* __restrict__ pose, uint64_t n, Pose2 world_to_field,
+                                                       double4* __restrict__ field_pose) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const double4 q = pose[i];
+  field_pose[i] = field_pose_record(world_to_field, Pose2{Rot2{q.x, q.y}, q.z, q.w});
 }
 
 template <bool kCube>
 __global__ __launch_bounds__(kBlock) void k_reweight_lf_sorted(double* __restrict__ w, uint64_t n, FieldView f,
                                                                const double* __restrict__ pts, uint32_t B,
                                                                const uint32_t* __restrict__ perm, const double4* __restrict__ pose,
-                                                               double* __restrict__ partial, uint32_t beams_per_segment) {
+                                                               double* __restrict__ partial, uint32_t beams_per_segment,
+                                                               uint32_t pose_ahead) {
   const uint64_t t = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   const uint64_t tt = t < n ? t : n - 1;
   const uint64_t i = perm ? perm[tt] : tt;  // (no order: small sets without a palette, sets beyond 2^32 particles)
-  const Pose2 T = ordered_pose(f.world_to_field, pose, i);  // likelihood_field_model.hpp:70
+  const Pose2 T = ordered_pose(f.world_to_field, pose, i, pose_ahead != 0u);  // likelihood_field_model.hpp:70
   const double ct = T.r.c, st = T.r.s, xt = T.x, yt = T.y;
   const uint32_t b_begin = partial ? blockIdx.y * beams_per_segment : 0u;
   const uint32_t b_end = partial ? (b_begin + beams_per_segment < B ? b_begin + beams_per_segment : B) : B;
@@ -539,7 +565,7 @@ __global__ __launch_bounds__(kPalBlock) void k_reweight_lf_palette(double* __res
                                                                    const double* __restrict__ pts, uint32_t B,
                                                                    const uint32_t* __restrict__ perm, const double4* __restrict__ pose,
                                                                    double* __restrict__ partial, uint32_t beams_per_segment,
-                                                                   uint32_t far_base) {
+                                                                   uint32_t far_base, uint32_t pose_ahead) {
   static_assert(kFast || !kFar, "far tiles ride on the biased coordinates of the FMA variant");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if constexpr (kFar) {
@@ -563,7 +589,7 @@ __global__ __launch_bounds__(kPalBlock) void k_reweight_lf_palette(double* __res
   const uint64_t t = static_cast<uint64_t>(block) * kPalBlock + threadIdx.x;
   const uint64_t tt = t < n ? t : n - 1;
   const uint32_t i = perm[tt];
-  const Pose2 T = ordered_pose(f.world_to_field, pose, i);  // likelihood_field_model.hpp:70
+  const Pose2 T = ordered_pose(f.world_to_field, pose, i, pose_ahead != 0u);  // likelihood_field_model.hpp:70
   const double ct = T.r.c, st = T.r.s, xt = T.x, yt = T.y;
   const uint32_t b_begin = partial ? blockIdx.y * beams_per_segment : 0u;
   const uint32_t b_end = partial ? (b_begin + beams_per_segment < B ? b_begin + beams_per_segment : B) : B;
@@ -715,7 +741,8 @@ constexpr int kBeamsBlock = 256;
 // (the body: block `block` of ONE set - blockIdx.x in k_reweight_lf_beams, a member's local block in k_batch_reweight_lf_beams)
 __device__ __forceinline__ void reweight_lf_beams_block(uint32_t block, const Particles& p, uint64_t n, const FieldView& f,
                                                         const double2* __restrict__ pts, uint32_t B,
-                                                        uint32_t per_wave /* particles of a wave: 1 .. 64 */) {
+                                                        uint32_t per_wave /* particles of a wave: 1 .. 64 */,
+                                                        const double4* __restrict__ field_pose /* nullptr: formed here */) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   {
     uint32_t* s_row = reinterpret_cast<uint32_t*>(smem);
@@ -730,9 +757,8 @@ __device__ __forceinline__ void reweight_lf_beams_block(uint32_t block, const Pa
   if (base >= n) return;
   const uint32_t cnt = static_cast<uint32_t>(n - base < per_wave ? n - base : per_wave);
   const uint64_t i = base + lane;
-  Pose2 state = pose_identity();
-  if (lane < cnt) state = load_pose(p, i);
-  const Pose2 T = pose_mul_ieee(f.world_to_field, state);  // likelihood_field_model.hpp:70
+  Pose2 T = pose_identity();  // likelihood_field_model.hpp:70; (a lane without a particle: never broadcast below)
+  if (lane < cnt) T = ordered_pose(f.world_to_field, field_pose ? field_pose : p.pose, i, field_pose != nullptr);
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(f.pal_idx), 0, static_cast<int>(f.pal_bytes), 0x00020000);
   const uint32_t full = B & ~255u;  // beams taken four per lane at a time (their gathers in flight together)
@@ -770,8 +796,9 @@ __device__ __forceinline__ void reweight_lf_beams_block(uint32_t block, const Pa
   if (lane < cnt) p.w[i] = p.w[i] * (f.prob ? exp(f.acc0 + mine) : f.acc0 + mine);
 }
 __global__ __launch_bounds__(kBeamsBlock) void k_reweight_lf_beams(Particles p, uint64_t n, FieldView f, const double2* __restrict__ pts,
-                                                                   uint32_t B, uint32_t per_wave /* particles of a wave: 1 .. 64 */) {
-  reweight_lf_beams_block(blockIdx.x, p, n, f, pts, B, per_wave);
+                                                                   uint32_t B, uint32_t per_wave /* particles of a wave: 1 .. 64 */,
+                                                                   const double4* __restrict__ field_pose) {
+  reweight_lf_beams_block(blockIdx.x, p, n, f, pts, B, per_wave, field_pose);
 }
 
 // Variant D for large DISPERSED sets, round 6 (option lf_dispersed = 2): the lanes over the beams of a pose as above, but with everything
@@ -802,7 +829,8 @@ template <bool kProb>
 __global__ __launch_bounds__(kFarBeamsBlock) __attribute__((amdgpu_waves_per_eu(kFarBeamsWaves, kFarBeamsWaves))) void k_reweight_lf_far_beams(double* __restrict__ w, uint64_t n, FieldView f,
                                                                           const double2* __restrict__ pts, uint32_t B,
                                                                           const uint32_t* __restrict__ perm, const double4* __restrict__ pose,
-                                                                          uint32_t pts_at, uint32_t per_wave, uint32_t unit_weights) {
+                                                                          uint32_t pts_at, uint32_t per_wave, uint32_t unit_weights,
+                                                                          uint32_t pose_ahead) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int J = kFarBeamsPoses;
   const uint32_t rows_at = f.far_linear_bytes;  // (a multiple of 16)
@@ -841,7 +869,7 @@ __global__ __launch_bounds__(kFarBeamsBlock) __attribute__((amdgpu_waves_per_eu(
     Pose2 T = pose_identity();
     if (lane < m) {
       i = perm[first + c0 + lane];
-      T = ordered_pose(f.world_to_field, pose, i);  // likelihood_field_model.hpp:70
+      T = ordered_pose(f.world_to_field, pose, i, pose_ahead != 0u);  // likelihood_field_model.hpp:70
     }
     unsigned long long large;
     {
@@ -933,7 +961,7 @@ __global__ __launch_bounds__(kFarBeamsBlock) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll 1
         for (int j = 0; j < J; ++j) {
           const uint32_t iq = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(i), static_cast<int>(q0) + j));
-          const Pose2 Tq = ordered_pose(f.world_to_field, pose, iq);
+          const Pose2 Tq = ordered_pose(f.world_to_field, pose, iq, pose_ahead != 0u);
           double sum = 0.0;
 #pragma unroll 1
           for (uint32_t k = 0; k < rounds; ++k) {
@@ -1038,7 +1066,9 @@ struct PatchArgs {
                           // the host knows): the new weight is the sensor term itself, 1.0 x = x, and the scattered load of the old weight -
                           // the last dependent memory round trip of a block's end, 8 us of a 1M launch - is not made
 };
-template <bool kQueue>
+// kAhead: args.pose is the buffer of field-frame poses (ordered_pose's `ahead`) - a template flag here and not an argument: the product's
+// registers are what the prologue of the other instance spills.
+template <bool kQueue, bool kAhead>
 __global__ __launch_bounds__(kPatchBlock) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_reweight_lf_patch(PatchArgs args) {
   // The arguments are read from the kernel argument segment at the start of every block (scalar loads), its address through an empty asm
   // statement so that the loads are not hoisted out of the queue's loop (kQueue): held in registers from the kernel's entry on they would all
@@ -1123,7 +1153,7 @@ __global__ __launch_bounds__(kPatchBlock) __attribute__((amdgpu_waves_per_eu(6, 
   const uint64_t t = producer ? first : first + tid;  // (the producer holds no particle; it reads a valid one)
   const uint64_t tt = t < n ? t : n - 1;
   const uint32_t i = perm[tt];
-  const Pose2 T = ordered_pose(f.world_to_field, pose, i);  // likelihood_field_model.hpp:70
+  const Pose2 T = ordered_pose(f.world_to_field, pose, i, kAhead);  // likelihood_field_model.hpp:70
   const double ct = T.r.c, st = T.r.s, xt = T.x, yt = T.y;
   const uint32_t b_begin = partial ? blockIdx.y * beams_per_segment : 0u;
   const uint32_t b_end = partial ? (b_begin + beams_per_segment < B ? b_begin + beams_per_segment : B) : B;
@@ -1500,7 +1530,7 @@ __global__ __launch_bounds__(kPatchBlock) __attribute__((amdgpu_waves_per_eu(6, 
     const double4* pose_again = pose;
     asm volatile("" : "+s"(pose_again));
     uint64_t position;
-    const Pose2 T_again = ordered_pose(f.world_to_field, pose_again, particle_again(position));
+    const Pose2 T_again = ordered_pose(f.world_to_field, pose_again, particle_again(position), kAhead);
     const double ct = T_again.r.c, st = T_again.r.s, xt = T_again.x, yt = T_again.y;
     auto term = [&](uint32_t at) {
       const double px = pts[2 * at], py = pts[2 * at + 1];
@@ -3699,11 +3729,11 @@ __device__ __forceinline__ uint32_t batch_member_here(const BatchItem* __restric
 __global__ __launch_bounds__(kBlock) void k_batch_propagate(const BatchItem* __restrict__ items, uint32_t count) {
   const BatchItem& it = items[batch_member_here(items, count, &BatchItem::first_propagate_block)];
   propagate_small_block(blockIdx.x - it.first_propagate_block, batch_propagate_blocks(it.n), it.p, it.n, it.smp, it.seed, it.step, it.index_offset,
-                        it.scan_src, it.scan_dst, it.scan_doubles);
+                        it.scan_src, it.scan_dst, it.scan_doubles, it.field_out);
 }
 __global__ __launch_bounds__(kBeamsBlock) void k_batch_reweight_lf_beams(const BatchItem* __restrict__ items, uint32_t count) {
   const BatchItem& it = items[batch_member_here(items, count, &BatchItem::first_reweight_block)];
-  reweight_lf_beams_block(blockIdx.x - it.first_reweight_block, it.p, it.n, it.f, reinterpret_cast<const double2*>(it.scan_dst), it.B, 1u);
+  reweight_lf_beams_block(blockIdx.x - it.first_reweight_block, it.p, it.n, it.f, reinterpret_cast<const double2*>(it.scan_dst), it.B, 1u, it.field_pose);
 }
 __global__ __launch_bounds__(kSmallBlock) void k_batch_small_tail(const BatchItem* __restrict__ items) {
   const SmallTailArgs a = items[blockIdx.x].tail;
@@ -4348,7 +4378,7 @@ __global__ __launch_bounds__(kBlock) void k_fill(double* p, uint64_t n, double v
 // =====================================================================================================
 void launch_propagate(hipStream_t st, Particles p, uint64_t n, DiffDriveSampler smp, uint64_t seed, uint32_t step,
                       uint64_t index_offset, const double* scan_src, double* scan_dst, uint32_t scan_doubles, const SortScratch* sort,
-                      const KeyFrame* frame, const double* normals_ahead, uint64_t normals_stride) {
+                      const KeyFrame* frame, const double* normals_ahead, uint64_t normals_stride, FieldPoseOut field) {
   if (n == 0) {
     if (scan_dst && scan_doubles) launch_pull_scan(st, scan_src, scan_dst, scan_doubles);
     return;
@@ -4356,21 +4386,26 @@ void launch_propagate(hipStream_t st, Particles p, uint64_t n, DiffDriveSampler 
   const uint32_t nblocks = num_chunks(n);
   if (!(sort && frame) && n <= 65536) {
     hipLaunchKernelGGL(k_propagate_small, dim3(blocks_for(n)), dim3(kBlock), 0, st, p, n, smp, seed, step,
-                       index_offset, scan_src, scan_dst, scan_doubles);
+                       index_offset, scan_src, scan_dst, scan_doubles, field);
     return;
   }
   if (sort && frame && n < (1ull << 32))
     hipLaunchKernelGGL(k_propagate<true>, dim3(nblocks), dim3(kPropBlock), 0, st, p, n, smp, seed, step, index_offset, scan_src, scan_dst,
-                       scan_doubles, *frame, sort->keys, sort->table, nblocks, normals_ahead, normals_stride);
+                       scan_doubles, *frame, sort->keys, sort->table, nblocks, normals_ahead, normals_stride, field);
   else
     hipLaunchKernelGGL(k_propagate<false>, dim3(nblocks), dim3(kPropBlock), 0, st, p, n, smp, seed, step, index_offset, scan_src, scan_dst,
                        scan_doubles, KeyFrame{}, static_cast<uint32_t*>(nullptr), static_cast<uint32_t*>(nullptr), nblocks, normals_ahead,
-                       normals_stride);
+                       normals_stride, field);
 }
 
 void launch_noise_ahead(hipStream_t st, uint64_t seed, uint32_t step, uint64_t index_offset, uint64_t n, double* d_normals) {
   if (n == 0) return;
   hipLaunchKernelGGL(k_noise_ahead, dim3(blocks_for(n)), dim3(kBlock), 0, st, seed, step, index_offset, n, d_normals);
+}
+
+void launch_field_pose(hipStream_t st, const double4* pose, uint64_t n, const FieldPoseOut& field) {
+  if (n == 0 || !field.pose) return;
+  hipLaunchKernelGGL(k_field_pose, dim3(blocks_for(n)), dim3(kBlock), 0, st, pose, n, field.world_to_field, field.pose);
 }
 
 void launch_pull_scan(hipStream_t st, const double* scan_src, double* scan_dst, uint32_t scan_doubles) {
@@ -4468,6 +4503,9 @@ LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tunin
   const uint32_t B = a.B;
   LfLaunch launched{LfKernel::kNone, 0};
   if (n == 0) return launched;
+  // (option lf_pose_ahead: the ordered kernels gather the field-frame poses where they gathered the particles' own)
+  const double4* const poses = a.field_pose ? a.field_pose : p.pose;
+  const uint32_t ahead = a.field_pose ? 1u : 0u;
   const size_t pal_lds = lf_palette_lds(f);
   const bool palette_ok = lf_palette_ok(f, tuning);
   if (const SortScratch* sort = a.sort) {
@@ -4500,14 +4538,16 @@ LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tunin
         // has more blocks than that: see k_reweight_lf_patch.
         const uint32_t cus = tuning.device_cus > 0 ? static_cast<uint32_t>(tuning.device_cus) : 256u;
         const uint32_t resident = tuning.lf_queue_grid > 0 ? static_cast<uint32_t>(tuning.lf_queue_grid) : 3u * cus;
-        const PatchArgs args{p.w, n, f, d_points, B, sort->perm, p.pose, partial, per_segment, patch_base, patch_stats, groups_x,
+        const PatchArgs args{p.w, n, f, d_points, B, sort->perm, poses, partial, per_segment, patch_base, patch_stats, groups_x,
                              tuning.lf_ends_first != 0 ? 1u : 0u, (a.unit_weights && segments == 1) ? 1u : 0u};
         if (tuning.lf_queue != 0 && segments == 1 && patch_stats.arrivals != nullptr && groups_x > resident) {
           launched.kernel = LfKernel::kPatchQueue;
-          hipLaunchKernelGGL(k_reweight_lf_patch<true>, dim3(resident), dim3(kPatchBlock), patch_lds, st, args);
+          if (ahead) hipLaunchKernelGGL((k_reweight_lf_patch<true, true>), dim3(resident), dim3(kPatchBlock), patch_lds, st, args);
+          else hipLaunchKernelGGL((k_reweight_lf_patch<true, false>), dim3(resident), dim3(kPatchBlock), patch_lds, st, args);
         } else {
           launched.kernel = LfKernel::kPatch;
-          hipLaunchKernelGGL(k_reweight_lf_patch<false>, dim3(groups_x, segments), dim3(kPatchBlock), patch_lds, st, args);
+          if (ahead) hipLaunchKernelGGL((k_reweight_lf_patch<false, true>), dim3(groups_x, segments), dim3(kPatchBlock), patch_lds, st, args);
+          else hipLaunchKernelGGL((k_reweight_lf_patch<false, false>), dim3(groups_x, segments), dim3(kPatchBlock), patch_lds, st, args);
         }
         if (patch_stats.weight_sums) launched.weight_sums = groups_x;
       }
@@ -4523,35 +4563,35 @@ LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tunin
         const unsigned blocks = (static_cast<unsigned>((n + per_block - 1) / per_block) + 7u) & ~7u;
         if (f.prob)
           hipLaunchKernelGGL(k_reweight_lf_far_beams<true>, dim3(blocks), dim3(kFarBeamsBlock), far_beams_lds(f, B), st, p.w, n, f,
-                             reinterpret_cast<const double2*>(d_points), B, sort->perm, p.pose, far_beams_points_at(f), per_wave,
-                             a.unit_weights ? 1u : 0u);
+                             reinterpret_cast<const double2*>(d_points), B, sort->perm, poses, far_beams_points_at(f), per_wave,
+                             a.unit_weights ? 1u : 0u, ahead);
         else
           hipLaunchKernelGGL(k_reweight_lf_far_beams<false>, dim3(blocks), dim3(kFarBeamsBlock), far_beams_lds(f, B), st, p.w, n, f,
-                             reinterpret_cast<const double2*>(d_points), B, sort->perm, p.pose, far_beams_points_at(f), per_wave,
-                             a.unit_weights ? 1u : 0u);
+                             reinterpret_cast<const double2*>(d_points), B, sort->perm, poses, far_beams_points_at(f), per_wave,
+                             a.unit_weights ? 1u : 0u, ahead);
         launched.kernel = LfKernel::kFarBeams;
       }
       else if (fast && a.dispersed && tuning.lf_far_tiles != 0 && f.far_bits != nullptr && patch_base + f.far_bytes <= 65536) {
         const dim3 fgrid((pgrid.x + 7u) & ~7u, segments);
         hipLaunchKernelGGL((k_reweight_lf_palette<true, true>), fgrid, dim3(kPalBlock), patch_base + f.far_bytes, st, p.w, n, f, d_points, B,
-                           sort->perm, p.pose, partial, per_segment, patch_base);
+                           sort->perm, poses, partial, per_segment, patch_base, ahead);
         launched.kernel = LfKernel::kPaletteFar;
       } else if (fast) {
-        hipLaunchKernelGGL(k_reweight_lf_palette<true>, pgrid, dim3(kPalBlock), pal_lds, st, p.w, n, f, d_points, B, sort->perm, p.pose,
-                           partial, per_segment, 0u);
+        hipLaunchKernelGGL(k_reweight_lf_palette<true>, pgrid, dim3(kPalBlock), pal_lds, st, p.w, n, f, d_points, B, sort->perm, poses,
+                           partial, per_segment, 0u, ahead);
         launched.kernel = LfKernel::kPaletteFast;
       } else {
-        hipLaunchKernelGGL(k_reweight_lf_palette<false>, pgrid, dim3(kPalBlock), pal_lds, st, p.w, n, f, d_points, B, sort->perm, p.pose,
-                           partial, per_segment, 0u);
+        hipLaunchKernelGGL(k_reweight_lf_palette<false>, pgrid, dim3(kPalBlock), pal_lds, st, p.w, n, f, d_points, B, sort->perm, poses,
+                           partial, per_segment, 0u, ahead);
         launched.kernel = LfKernel::kPaletteExact;
       }
     } else if (cube_ok) {
-      hipLaunchKernelGGL(k_reweight_lf_sorted<true>, grid, dim3(kBlock), 0, st, p.w, n, f, d_points, B, sort->perm, p.pose, partial,
-                         per_segment);
+      hipLaunchKernelGGL(k_reweight_lf_sorted<true>, grid, dim3(kBlock), 0, st, p.w, n, f, d_points, B, sort->perm, poses, partial,
+                         per_segment, ahead);
       launched.kernel = LfKernel::kSortedCube;
     } else {
-      hipLaunchKernelGGL(k_reweight_lf_sorted<false>, grid, dim3(kBlock), 0, st, p.w, n, f, d_points, B, sort->perm, p.pose, partial,
-                         per_segment);
+      hipLaunchKernelGGL(k_reweight_lf_sorted<false>, grid, dim3(kBlock), 0, st, p.w, n, f, d_points, B, sort->perm, poses, partial,
+                         per_segment, ahead);
       launched.kernel = LfKernel::kSortedField;
     }
     if (segments > 1)
@@ -4563,13 +4603,13 @@ LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tunin
     const uint64_t tiles = (n + per_wave - 1) / per_wave;
     const dim3 grid(static_cast<unsigned>((tiles + (kBeamsBlock / kWave) - 1) / (kBeamsBlock / kWave)));
     hipLaunchKernelGGL(k_reweight_lf_beams, grid, dim3(kBeamsBlock), pal_lds, st, p, n, f, reinterpret_cast<const double2*>(d_points), B,
-                       per_wave);
+                       per_wave, a.field_pose);
     launched.kernel = LfKernel::kBeams;
   } else {
     // no order (option lf_variant 0 / 1, small sets whose field has too many distinct values for a palette, sets beyond 2^32 particles):
     // a lane per particle in index order over the f32 field
     hipLaunchKernelGGL(k_reweight_lf_sorted<false>, dim3(blocks_for(n)), dim3(kBlock), 0, st, p.w, n, f, d_points, B,
-                       static_cast<const uint32_t*>(nullptr), p.pose, static_cast<double*>(nullptr), 0u);
+                       static_cast<const uint32_t*>(nullptr), poses, static_cast<double*>(nullptr), 0u, ahead);
     launched.kernel = LfKernel::kIndexOrder;
   }
   return launched;

@@ -69,6 +69,12 @@ constexpr Option kOptions[] = {
     {"rows_merged", &Tuning::rows_merged, Rule::kFlag, 0, 0},
 };
 constexpr size_t kOptionCount = sizeof(kOptions) / sizeof(kOptions[0]);
+// Options added since the rows above were recorded.  tests/test_options_host_cpu.py pins those rows - the names tuning_names lists, one
+// environment look-up each - against the record of what they stored before the table existed; a row here is read by set_tuning
+// (mcl_set_option) alone: it is no part of that list and has no BELUGA_MCL_* variable.
+constexpr Option kLaterOptions[] = {
+    {"lf_pose_ahead", &Tuning::lf_pose_ahead, Rule::kFlag, 0, 0},
+};
 
 int normalised(const Option& o, int64_t value) {
   switch (o.rule) {
@@ -98,6 +104,11 @@ const char* const* tuning_names(size_t* count) {
 
 bool set_tuning(Tuning& t, const char* name, int64_t value) {
   for (const Option& o : kOptions) {
+    if (std::strcmp(o.name, name) != 0) continue;
+    t.*o.member = normalised(o, value);
+    return true;
+  }
+  for (const Option& o : kLaterOptions) {
     if (std::strcmp(o.name, name) != 0) continue;
     t.*o.member = normalised(o, value);
     return true;

@@ -11,7 +11,8 @@
 
 namespace mcl {
 
-// The option names, in the table's order.
+// The option names, in the table's order (the recorded rows: an option added since - lf_pose_ahead - is set by name through set_tuning
+// and is neither listed here nor read from the environment; options_host.cpp says why).
 const char* const* tuning_names(size_t* count);
 
 // The option `name` takes `value`, normalised by its rule; false (and nothing changes) for a name that is no option.

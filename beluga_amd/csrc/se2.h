@@ -91,8 +91,12 @@ MCL_HD Pose2 pose_mul(const Pose2& a, const Pose2& b) {
   return o;
 }
 // pose_mul with the rotation normalised by hypot_ieee: on the device the same bits as the host's pose_mul.  For the ONE product whose last
-// bit decides a map cell - world -> field times the particle's pose in the likelihood-field kernels, once per particle and launch; every
-// other rotation on the device keeps the device library's hypot (an ulp is within every other stage's tolerance).
+// bit decides a map cell - world -> field times the particle's pose, which the likelihood-field kernels start from.  Formed once per
+// set of poses, where a pose is written (the propagation kernels, or k_field_pose for a set that something else wrote) and kept in a
+// buffer the LF kernels load (option lf_pose_ahead; with 0 each LF kernel forms it, once per particle and launch): a complex product, a
+// renormalisation, a square root and a division behind two branches and two more divisions are too much for the prologue of a kernel at
+// its register cap.  Every other rotation on the device keeps the device library's hypot (an ulp is within every other stage's
+// tolerance).
 MCL_HD Pose2 pose_mul_ieee(const Pose2& a, const Pose2& b) {
   double re = a.r.c * b.r.c - a.r.s * b.r.s;
   double im = a.r.c * b.r.s + a.r.s * b.r.c;

@@ -11,6 +11,9 @@
 //   pivot     the point the estimate sums of the live set are taken about (dx = x - pivot): it has to lie within the set, or the
 //             covariance loses (distance / spread)^2 of its digits.  Known from whoever installed the set (the mean it drew about, the
 //             first state it copied) or from the set's last finite estimate; void once another set has replaced it
+//   field poses  the buffer of field-frame poses (FieldPoseOut, kernels.h) holds world_to_field * pose of every particle of the live set,
+//             for the map frame of generation G (the context counts the maps it has been given): the likelihood-field kernels load them
+//             instead of forming the product (option lf_pose_ahead).  Void behind anything that writes poses without them
 //
 //   event                              unit            lf sums    divides    order       normals
 //   set_changes                        .               void       .          void        .
@@ -32,6 +35,15 @@
 //   take_order_ahead(s, n, l)          .               .          .          read, void  .
 //   order_accepted(yes) / take_...     .               .          .          accepted    .
 //   noise_ahead_recorded(s, n, o, sd)  .               .          .          .           = (s, n, o, sd)
+//
+//   event                              field poses
+//   field_poses_written(G)             = G            (a propagation that stored them beside the poses; k_field_pose)
+//   poses_moved                        void           (a propagation that stored none)
+//   set_changes, set_replaced, set_resized, resampled_set_committed, commit_rolled_back
+//                                      void           (an initialisation, mcl_set_particles, a loaded shard, a resampling or an exchange
+//                                                      and its roll-back: none of their kernels writes the buffer)
+//   field_poses_current(G)             read           (false for any other generation: mcl_set_map, the swap of a map built ahead,
+//                                                      mcl_use_shared_map and mcl_set_likelihood_field each begin a new one)
 //
 // set_changes comes first in every entry point that replaces or resizes the set, ahead of its argument checks: a call that fails has
 // still voided what described the old set.  A rewrite that begins and fails leaves unit false; one that succeeds ends in
@@ -58,11 +70,13 @@ class SetFacts {
     return noise_n_ >= n && noise_step_ == step && noise_seed_ == seed && noise_offset_ == offset;
   }
 
+  bool field_poses_current(uint64_t generation) const { return field_poses_ && field_generation_ == generation; }
+
   bool pivot_known() const { return pivot_known_; }
   bool pivot_heading_known() const { return pivot_known_ && heading_known_; }
   const double* pivot() const { return pivot_; }  // (0, 0) while void
 
-  void set_changes() { lf_sums_ = 0; order_recorded_ = false; }
+  void set_changes() { lf_sums_ = 0; order_recorded_ = false; field_poses_ = false; }
   void pivot_given(double x, double y) {
     if (!(x - x == 0.0 && y - y == 0.0)) return;  // (neither NaN nor infinite)
     pivot_known_ = true; heading_known_ = false; pivot_[0] = x; pivot_[1] = y;
@@ -97,8 +111,10 @@ class SetFacts {
   void lf_sums_dropped() { lf_sums_ = 0; }
   void weights_left_undivided(bool yes) { divides_ = yes; }
   bool take_cdf_divides() { const bool was = divides_; divides_ = false; return was; }
-  void resampled_set_committed() { unit_ = true; }  // (every output slot took a weight of 1.0)
-  void commit_rolled_back() { unit_ = false; }      // (the old set is live again: its weights are normalised)
+  void resampled_set_committed() { unit_ = true; field_poses_ = false; }  // (every output slot took a weight of 1.0)
+  void commit_rolled_back() { unit_ = false; field_poses_ = false; }      // (the old set is live again: its weights are normalised)
+  void field_poses_written(uint64_t generation) { field_poses_ = true; field_generation_ = generation; }
+  void poses_moved() { field_poses_ = false; }
   void order_ahead_recorded(uint32_t step, uint64_t n, uint32_t layout) {
     order_recorded_ = true; order_step_ = step; order_n_ = n; order_layout_ = layout;
   }
@@ -118,6 +134,8 @@ class SetFacts {
   bool unit_{false}, divides_{false}, order_recorded_{false}, order_accepted_{false};
   uint32_t lf_sums_{0}, order_step_{0}, order_layout_{0}, noise_step_{0};
   uint64_t order_n_{0}, noise_n_{0}, noise_offset_{0}, noise_seed_{0};
+  bool field_poses_{false};
+  uint64_t field_generation_{0};
   bool pivot_known_{false}, heading_known_{false};
   double pivot_[2]{0.0, 0.0}, heading_[2]{1.0, 0.0};
 };

@@ -735,6 +735,12 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *                   row scan adds those counts up - no pass of its own over the keys; 0 = a kernel reads the keys back.  Bit-identical.
  *   rows_merged (1)  with draw_key_hist: the estimate sums' last additions and that row scan in one launch; 0 = two.  Bit-identical.
  *                   Both measured at 1M particles: + 1.6 % once the cloud has settled, nothing shown before.
+ *   lf_pose_ahead (1)  likelihood-field models: world_to_field * pose of every particle - what each of their kernels starts from - is
+ *                   stored beside the pose by the propagation that writes it (by a kernel of its own, k_field_pose, in front of a reweight
+ *                   of a set that nothing has propagated under the current map: after mcl_set_particles, an initialisation, a
+ *                   resampling, a map given since) and the kernels load it; 32 bytes per particle of capacity.  0 = every kernel forms
+ *                   the product itself, per particle and launch.  Bit-identical; counter field_pose_rebuilds (launches of k_field_pose).
+ *                   Set through mcl_set_option alone: it has no BELUGA_MCL_* variable.
  *   norm_store (0)  fixed-size cycle that resamples at once: 0 = the normalisation kernel does not store the normalised weights (nothing reads
  *                   them), the CDF kernel divides again; 1 = stored.  Bit-identical.
  *   batch_cluster_fused (1)  a member of a batch that returns the cluster-based estimate: 1 = through the batch's two shared launches
