@@ -353,11 +353,12 @@ class SharedMap:
 class Amcl:
     def __init__(self, grid: OccupancyGrid, motion, sensor, params: AmclParams = AmclParams(), *,
                  seed: int = 0, device: int = 0, shard_offset: int = 0, shard_capacity: int = 0, hip_stream: int = 0,
-                 options: Optional[dict] = None):
+                 options: Optional[dict] = None, ndt_small_cycle: bool = False):
         """options: library switches applied before the map is installed (mcl_set_option), e.g. {"field_build": 1} to build
-        the likelihood field with the device's exact distance transform instead of the reference's wavefront on the host."""
+        the likelihood field with the device's exact distance transform instead of the reference's wavefront on the host.
+        ndt_small_cycle (NDT sensor model only): set_ndt_small_cycle(True) once the context exists."""
         cfg = self._configure(grid, motion, sensor, params, seed=seed, device=device, shard_offset=shard_offset,
-                              shard_capacity=shard_capacity, hip_stream=hip_stream)
+                              shard_capacity=shard_capacity, hip_stream=hip_stream, ndt_small_cycle=ndt_small_cycle)
         ctx = capi._ctx()
         st = self._lib.mcl_create(C.byref(cfg), C.byref(ctx))
         if st != capi.MCL_OK:
@@ -366,9 +367,13 @@ class Amcl:
             raise capi.MclError(st, msg)
         self._attach(ctx, grid, options, owned=True)
 
-    def _configure(self, grid, motion, sensor, params, *, seed=0, device=0, shard_offset=0, shard_capacity=0, hip_stream=0):
+    def _configure(self, grid, motion, sensor, params, *, seed=0, device=0, shard_offset=0, shard_capacity=0, hip_stream=0,
+                   ndt_small_cycle=False):
         """The mcl_config of these constructor arguments (and what the object remembers of them)."""
         self._lib = capi.load()
+        if ndt_small_cycle and not isinstance(sensor, NDTModelParam2d):
+            raise ValueError("ndt_small_cycle needs the NDT sensor model (NDTModelParam2d)")
+        self._ndt_small_cycle = bool(ndt_small_cycle)
         cfg = capi.Config()
         self._lib.mcl_default_config(C.byref(cfg))
         cfg.device_id = device
@@ -437,6 +442,8 @@ class Amcl:
         self._update_fn.argtypes = [capi._ctx, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         for name, value in (options or {}).items():
             self.set_option(name, value)
+        if getattr(self, "_ndt_small_cycle", False):
+            self.set_ndt_small_cycle(True)
         if grid is not None:  # (only a member of an AmclBatch may start without a map)
             self.update_map(grid)
 
@@ -711,6 +718,23 @@ class Amcl:
         if len(m) != len(c):
             raise ValueError("reweight_ndt_cells: means and covariances differ in length")
         self._check(self._lib.mcl_reweight_ndt_cells(self._ctx, _dp(m), _dp(c), len(m)))
+
+    def set_ndt_small_cycle(self, on: bool = True):
+        """mcl_set_ndt_small_cycle: small NDT sets (up to 4096 particles) take the wave-per-particle reweight and the one-launch tail
+        with one host synchronisation; a cycle that would inject random states is handed back to the host behind the policies.  In an
+        AmclBatch such a member rides the fleet's shared launches.  Off by default; raises on another sensor model."""
+        self._check(self._lib.mcl_set_ndt_small_cycle(self._ctx, int(bool(on))))
+
+    def ndt_small_cycle(self) -> bool:
+        on = C.c_int32(0)
+        self._check(self._lib.mcl_get_ndt_small_cycle(self._ctx, C.byref(on)))
+        return bool(on.value)
+
+    def ndt_small_cycle_counts(self) -> Tuple[int, int]:
+        """(small cycles that ended inside the one-launch tail, small cycles the tail handed back): running totals."""
+        done, back = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.mcl_get_ndt_small_cycle_counts(self._ctx, C.byref(done), C.byref(back)))
+        return done.value, back.value
 
     def reweight_landmarks(self, detections):
         """Landmark model: w *= product over the detections (LandmarkPositionDetection entries or a (positions, categories) pair)."""
@@ -1019,6 +1043,13 @@ class AmclBatch:
         kernels instead of the fleet's two shared launches)."""
         for member in self.members:
             member.set_option(name, value)
+
+    def ndt_counts(self) -> Tuple[int, int]:
+        """(shared NDT reweight launches enqueued, NDT members that updated through the shared launches): running totals
+        (mcl_ndt_batch_counts)."""
+        launches, members = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._lib.mcl_ndt_batch_counts(self._batch, C.byref(launches), C.byref(members)))
+        return launches.value, members.value
 
     def counter(self, name: str) -> int:
         """cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns, beam_launches,

@@ -210,6 +210,9 @@ _SIGNATURES = {
     "mcl_set_ndt_map": (C.c_int32, [_ctx, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_uint64, C.c_double, C.POINTER(NdtParams)]),
     "mcl_ndt_measurement_cells": (C.c_int32, [c_double_p, C.c_uint64, C.c_double, c_double_p, c_double_p, c_u64_p]),
     "mcl_reweight_ndt_cells": (C.c_int32, [_ctx, c_double_p, c_double_p, C.c_uint64]),
+    "mcl_set_ndt_small_cycle": (C.c_int32, [_ctx, C.c_int32]),
+    "mcl_get_ndt_small_cycle": (C.c_int32, [_ctx, C.POINTER(C.c_int32)]),
+    "mcl_get_ndt_small_cycle_counts": (C.c_int32, [_ctx, c_u64_p, c_u64_p]),
     "mcl_build_ndt_map_from_points": (C.c_int32, [_ctx, c_double_p, C.c_uint64, C.c_double]),
     "mcl_build_ndt_map_from_grid": (C.c_int32, [_ctx, c_i8_p, C.c_uint32, C.c_uint32, C.c_double, c_double_p, C.c_double]),
     "mcl_get_ndt_map": (C.c_int32, [_ctx, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_uint64, c_u64_p]),
@@ -226,6 +229,7 @@ _SIGNATURES = {
     "mcl_batch_member": (C.c_int32, [_batch, C.c_uint32, C.POINTER(_ctx)]),
     "mcl_batch_update": (C.c_int32, [_batch, c_double_p, c_double_p, c_u64_p, C.POINTER(Estimate), C.POINTER(UpdateInfo), C.POINTER(C.c_int32)]),
     "mcl_batch_get_counter": (C.c_int32, [_batch, C.c_char_p, c_u64_p]),
+    "mcl_ndt_batch_counts": (C.c_int32, [_batch, c_u64_p, c_u64_p]),
     "mcl_batch_last_error": (C.c_char_p, [_batch]),
     "mcl_shared_map_create": (C.c_int32, [C.POINTER(Config), c_i8_p, C.c_uint32, C.c_uint32, C.c_double, c_double_p, c_i8_p, C.c_int32,
                                           C.POINTER(_shared_map)]),
@@ -237,7 +241,9 @@ _SIGNATURES = {
     "mcl_measurement_build": (C.c_int, []),
 }
 
-_OPTIONAL = {"mcl_measurement_build"}  # symbols a library may lack and still load
+# symbols a library may lack and still load (an older build named by BELUGA_MCL_LIB: tools/exp_ndt_small.py measures against one)
+_OPTIONAL = {"mcl_measurement_build", "mcl_set_ndt_small_cycle", "mcl_get_ndt_small_cycle", "mcl_get_ndt_small_cycle_counts",
+             "mcl_ndt_batch_counts"}
 _lib = None
 
 

@@ -16,6 +16,11 @@ bool batch_beam_member_fused(const BatchBeamFacts& m) {
          m.max_particles >= 1 && m.max_particles <= kBatchMaxParticles && m.n < m.beam_sort_min_particles && !m.profiling;
 }
 
+bool batch_ndt_member_fused(const BatchNdtFacts& m) {
+  return m.sensor_kind == MCL_SENSOR_NDT && m.small_cycle && !m.sharded && m.small_fused && m.n >= 1 && m.n <= kBatchMaxParticles &&
+         m.max_particles >= 1 && m.max_particles <= kBatchMaxParticles && m.have_map && !m.profiling;
+}
+
 bool batch_cluster_member(const BatchClusterFacts& m) {
   return m.status == MCL_OK && m.estimate_kind == 1 && m.cluster_fused && m.n >= 1 && m.n <= kBatchMaxParticles &&
          cluster_params_ok(m.linear_hash_resolution, m.angular_hash_resolution, m.weight_cap_percentile);
@@ -54,6 +59,15 @@ BatchBeamGrid batch_beam_layout(const uint64_t* n, const uint32_t* B, uint32_t m
     if (blocks) g.lds = std::max(g.lds, B[m] * kBatchBeamPointBytes);
   }
   return g;
+}
+
+uint32_t batch_ndt_layout(const uint64_t* n, const uint32_t* K, uint32_t members, uint32_t* first_ndt) {
+  uint32_t blocks = 0;
+  for (uint32_t m = 0; m < members; ++m) {
+    first_ndt[m] = blocks;
+    blocks += batch_ndt_blocks(n[m], K[m]);
+  }
+  return blocks;
 }
 
 const char* batch_check_configs(const mcl_config* cfgs, uint32_t count) {

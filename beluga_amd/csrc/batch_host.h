@@ -20,6 +20,8 @@ constexpr uint32_t kBatchBeamThreads = 256;     // threads of a block of k_rewei
 constexpr uint32_t kBatchBeamBlock = 4;         // ... and its particles, a wave each (kBlock / kWave)
 constexpr uint32_t kBatchBeamPointBytes = 16;   // a scan point staged in its workgroup memory (double2)
 constexpr uint32_t kBatchBeamMaxPoints = 4096;  // 64 KB of it: the lone kernel's own limit (reweight_preconditions)
+constexpr uint32_t kBatchNdtThreads = 256;      // threads of a block of k_reweight_ndt_wave (kBlock)
+constexpr uint32_t kBatchNdtBlock = 4;          // ... and its particles, a wave each (kBlock / kWave)
 
 // ---- which members share the launches ------------------------------------------------------------------------------------------------
 // What the predicate reads of a member in the cycle that is being prepared.
@@ -48,6 +50,20 @@ struct BatchBeamFacts {
 };
 // The member's own mcl_update would run exactly k_propagate_small, k_reweight_beam (a wave per particle), k_small_tail.
 bool batch_beam_member_fused(const BatchBeamFacts& m);
+
+// The same for an NDT member (mcl_set_ndt_small_cycle): what k_batch_reweight_ndt's members must satisfy.
+struct BatchNdtFacts {
+  int sensor_kind;         // MCL_SENSOR_*
+  bool small_cycle;        // the context's switch (mcl_set_ndt_small_cycle)
+  bool sharded;            // the context is one rank of a sharded filter
+  bool small_fused;        // option small_fused
+  uint64_t n;              // particles of the live set
+  uint64_t max_particles;  // min(max_particles, capacity)
+  bool have_map;           // an NDT map is installed
+  bool profiling;          // stage profiling on
+};
+// The member's own mcl_update would run exactly k_propagate_small, k_reweight_ndt_wave, k_small_tail.
+bool batch_ndt_member_fused(const BatchNdtFacts& m);
 
 // ---- which fused members share the cluster-based estimate's two launches ------------------------------------------------------------------
 // What cluster_front checks of cluster parameters before anything is launched.
@@ -95,6 +111,13 @@ struct BatchBeamGrid {
 // n[m], B[m] (scan points) for m < members  ->  first_beam[m]: the member's first block (a running sum; a member that is no beam member
 // of the cycle comes with n = 0 or B = 0, has no block and is never found), and the grid.
 BatchBeamGrid batch_beam_layout(const uint64_t* n, const uint32_t* B, uint32_t members, uint32_t* first_beam);
+// The NDT members' launch (k_batch_reweight_ndt).  A member with n = 0 or K = 0 measurement cells has no block: its weights stay (x 1.0).
+MCL_HD uint32_t batch_ndt_blocks(uint64_t n, uint32_t K) {
+  return (n == 0 || K == 0) ? 0u : static_cast<uint32_t>((n + kBatchNdtBlock - 1) / kBatchNdtBlock);
+}
+// n[m], K[m] for m < members  ->  first_ndt[m]: the member's first block (a running sum; a member that is no NDT member of the cycle
+// comes with n = 0 or K = 0, has no block and is never found).  Returns the grid (0: nothing to launch).
+uint32_t batch_ndt_layout(const uint64_t* n, const uint32_t* K, uint32_t members, uint32_t* first_ndt);
 // The member whose blocks include `block`: the LAST m with first_of(m) <= block (members without a block share their successor's first
 // block and are skipped).  Needs first_of(0) == 0 and block < the grid.  ceil(log2(members)) steps, each one read.
 template <class FirstOf>

@@ -265,6 +265,12 @@ struct mcl_ctx {
   FreeCells ndt_random{nullptr, 0};
   bool ndt_random_ready{false};        // ndt_random was prepared for the next draw (prepare_ndt_random)
   DeviceBuffer<double> d_ndt_est;      // scratch of the estimate behind ndt_random (9 rows of num_chunks(n))
+  bool ndt_small_cycle{false};         // mcl_set_ndt_small_cycle: the wave-per-particle reweight and the one-launch tail for small sets
+  uint64_t ndt_small_completed{0};     // small cycles that ended inside k_small_tail (mcl_get_ndt_small_cycle_counts)
+  uint64_t ndt_small_handed_back{0};   // ... and those the tail handed back to the host behind the policies
+  NdtCycleFacts ndt_cycle_facts() const {
+    return NdtCycleFacts{ndt_small_cycle, tuning.small_fused != 0, profile != 0, n, std::min<uint64_t>(cfg.amcl.max_particles, capacity)};
+  }
   bool is_ndt() const { return cfg.sensor_kind == MCL_SENSOR_NDT; }
 
   // Landmark and bearing sensor models (MCL_SENSOR_LANDMARK, MCL_SENSOR_BEARING): the map of mcl_set_landmark_map - the landmarks grouped
@@ -847,6 +853,7 @@ struct HeldCycle {
   bool fused{false};           // the member's cycle is the small one: nothing of it has been launched
   bool pending{false};         // ... and its record is complete
   bool beam{false};            // fused, and the reweight is the beam model's (k_batch_reweight_beam)
+  bool ndt{false};             // fused, and the reweight is the NDT model's (k_batch_reweight_ndt)
   BatchItem item{};
   uint64_t every_n{0};         // the counter as the cycle leaves it
 };
@@ -980,7 +987,10 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
                                  ctx->cfg.sensor_kind, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
                                  ctx->tuning.batch_beam_fused != 0, ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity),
                                  static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles), ctx->profile != 0});
-    hold->fused = hold->fused || hold->beam;
+    hold->ndt = ctx->is_ndt() && batch_ndt_member_fused(BatchNdtFacts{
+                                     ctx->cfg.sensor_kind, ctx->ndt_small_cycle, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
+                                     ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), ctx->have_ndt_map, ctx->profile != 0});
+    hold->fused = hold->fused || hold->beam || hold->ndt;
     if (!hold->fused) launch_held_propagate(ctx, hold);
   }
   if (ordered && !have_order) {
@@ -991,7 +1001,15 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
   }
   if (ctx->is_ndt()) {
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, static_cast<uint32_t>(m.doubles / kNdtRecord));
+    const uint32_t cells = static_cast<uint32_t>(m.doubles / kNdtRecord);
+    if (hold && hold->fused) {  // (a held cycle: the batch launches k_batch_reweight_ndt)
+      hold->item.ndt = ctx->ndt_view;
+      hold->item.ndt_cells = cells;
+    } else if (ndt_reweight_takes_waves(ctx->ndt_small_cycle, ctx->n)) {
+      launch_reweight_ndt_wave(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, cells);
+    } else {
+      launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, cells);
+    }
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else if (ctx->is_landmark()) {
     const uint32_t k = static_cast<uint32_t>(m.doubles / kLandmarkRecord);
@@ -2820,6 +2838,10 @@ static SmallTail small_tail_record(const mcl_ctx* ctx, bool fires) {
   t.hp = HashParams{ap.spatial_resolution_x, ap.spatial_resolution_y, ap.spatial_resolution_theta};
   t.g = ctx->grid_view();
   t.fc = ctx->random_source();
+  if (ctx->is_ndt()) {  // a cycle that would inject random states is handed back: the tail itself draws none
+    t.fc = FreeCells{nullptr, 0};
+    t.hand_back = true;
+  }
   t.pivot_x = ctx->facts.pivot()[0];
   t.pivot_y = ctx->facts.pivot()[1];
   t.mirror = ctx->h_scalars.device;
@@ -2849,6 +2871,7 @@ static mcl_update_info small_cycle_state(mcl_ctx* ctx) {
   ctx->slow.output = h[kSlotSlow];
   ctx->fast.output = h[kSlotFast];
   ctx->force_update = false;  // :199
+  if (ctx->is_ndt()) ctx->ndt_small_completed += 1;
   // (what the info reports, before another kernel's mirrored values take their place)
   return mcl_update_info{1, resampled, ctx->n, h[kSlotWeightSum], h[kSlotEss], h[kSlotPolicyP]};
 }
@@ -2857,7 +2880,43 @@ static mcl_status small_cycle_estimate(mcl_ctx* ctx, mcl_estimate* est) {
   if (ctx->estimate_kind == 1) return mcl_cluster_based_estimate(ctx, &ctx->cluster_params, est);
   return mirrored_estimate(ctx, est);  // :200
 }
+// An NDT cycle that the tail handed back (SmallTail::hand_back): it resamples with a random state probability > 0.  Behind the
+// synchronisation the set is normalised, the mirror holds the policies' scalars, nothing has been drawn.
+static bool small_cycle_handed_back(const mcl_ctx* ctx) { return ctx->is_ndt() && ctx->h_scalars.host[kSlotHandBack] != 0.0; }
+// The host's end of such a cycle - the general path's own steps from :182 on: the generator of the random states, the recovery filters'
+// reset, the draw, the estimate.  The CDF adds its own chunk sums (the tail left none in d_chunk: normalized_just_now stays false).  A
+// refused generator returns MCL_ERR_BAD_COVARIANCE with the state the general path leaves (ndt_hand_back_taken, cycle_host.h).
+static mcl_status finish_handed_back_cycle(mcl_ctx* ctx, mcl_estimate* est, mcl_update_info* report) {
+  stage_collect(ctx);
+  const double* h = ctx->h_scalars.host;
+  const NdtHandBack back{h[kSlotSlow], h[kSlotFast], h[kSlotPolicyP], h[kSlotEss], h[kSlotWeightSum]};
+  ctx->ndt_small_handed_back += 1;
+  ndt_hand_back_taken(back, ctx->slow, ctx->fast);                                // :179
+  if (const mcl_status s = prepare_ndt_random(ctx, back.p)) return s;              // :182
+  ndt_hand_back_resamples(back, ctx->slow, ctx->fast, &ctx->force_update);        // :184-186, :199
+  bool estimate_enqueued = false;
+  const ResampleOptions opt{.normalized_just_now = false, .with_estimate = ctx->estimate_kind == 0, .estimate_enqueued = &estimate_enqueued};
+  if (const mcl_status s = do_resample(ctx, back.p, ctx->step, nullptr, opt)) return s;  // :188-196
+  if (ctx->estimate_kind == 1) {
+    if (const mcl_status s = mcl_cluster_based_estimate(ctx, &ctx->cluster_params, est)) return s;
+  } else if (estimate_enqueued) {  // :200, sums already produced by the draw kernel
+    if (const mcl_status s = wait_for_cycle(ctx)) return s;
+    stage_collect(ctx);
+    if (const mcl_status s = mirrored_estimate(ctx, est)) return s;
+  } else if (const mcl_status s = mcl_estimate_pose(ctx, est)) {
+    return s;
+  }
+  *report = mcl_update_info{1, 1, ctx->n, back.weight_sum, back.ess, back.p};
+  return MCL_OK;
+}
 static mcl_status finish_small_cycle(mcl_ctx* ctx, mcl_estimate* estimate, mcl_update_info* info) {
+  if (small_cycle_handed_back(ctx)) {
+    mcl_estimate est{};
+    mcl_update_info report{};
+    if (const mcl_status s = finish_handed_back_cycle(ctx, &est, &report)) return s;
+    finish_cycle(ctx, est, report, estimate, info);
+    return MCL_OK;
+  }
   const mcl_update_info report = small_cycle_state(ctx);
   mcl_estimate est{};
   if (const mcl_status s = small_cycle_estimate(ctx, &est)) return s;
@@ -2918,7 +2977,10 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   // (k_small_tail) - the policies are evaluated on the device, the host keeps the recovery filters' state.
   const uint64_t every_n = next_every_n(ctx->every_n_current, ap.resample_interval);  // :181 (stored by the path that takes the cycle)
   const bool fires = every_n == 0;
-  const bool small = ctx->tuning.small_fused != 0 && !ctx->off_grid() && ctx->n <= 4096 && std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096;
+  // (an NDT context only with its switch on, mcl_set_ndt_small_cycle: the tail hands a cycle that would inject random states back)
+  const bool small = ctx->is_ndt() ? ndt_cycle_is_small(ctx->ndt_cycle_facts())
+                                   : ctx->tuning.small_fused != 0 && !ctx->off_grid() && ctx->n <= 4096 &&
+                                         std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096;
   if (hold && hold->fused) {  // the batch launches this cycle and finishes it
     if (!small) return fail(ctx, MCL_ERR_HIP, "mcl_batch_update: a held cycle is not a small one");
     hold->item.tail = small_tail_args(small_tail_record(ctx, fires));
@@ -3053,6 +3115,9 @@ struct mcl_batch {
   std::vector<uint32_t> fused_lds, first_propagate, first_reweight;
   std::vector<uint64_t> lf_n, beam_n;  // fused_n of the members of one family, 0 for the other's (each family's reweight launch)
   std::vector<uint32_t> beam_B, first_beam, first_unused;
+  std::vector<uint64_t> ndt_n;                // ... and the NDT members' (k_batch_reweight_ndt)
+  std::vector<uint32_t> ndt_cells, first_ndt;
+  std::vector<uint8_t> handed_back;           // by member: its tail handed the cycle back and it finished it itself
   // the cluster-based estimate's two shared launches: a record per member and launch, pinned and on the device
   HostBuffer<BatchClusterCells> h_cluster_cells;
   HostBuffer<BatchClusterSums> h_cluster_sums;
@@ -3060,6 +3125,7 @@ struct mcl_batch {
   DeviceBuffer<BatchClusterSums> d_cluster_sums;
   uint64_t cycles{0}, kernel_launches{0}, members_fused{0}, members_alone{0}, cluster_launches{0}, members_cluster_fused{0};
   uint64_t beam_launches{0}, members_beam_fused{0};  // shared beam reweight kernels enqueued; beam members that updated through the shared cycle
+  uint64_t ndt_launches{0}, members_ndt_fused{0};    // the same for the NDT members (mcl_ndt_batch_counts)
   uint64_t cluster_host_ns{0};  // host time between the two shared launches: every member's cells ordered, assigned, ids written
   // per call, kept for the next one: by member ...
   std::vector<mcl_status> status;
@@ -3079,7 +3145,7 @@ mcl_status batch_fail(mcl_batch* b, mcl_status code, const std::string& msg) {
   return code;
 }
 // Enqueues the cycle of the members in b->fused (their records complete in b->held) and waits for it: one copy, the launches (three for
-// members of one family, four where likelihood-field and beam members are both present), one synchronisation.
+// members of one family, one more for every further family - likelihood-field, beam, NDT - that is present), one synchronisation.
 mcl_status batch_launch(mcl_batch* b) {
   const uint32_t count = static_cast<uint32_t>(b->fused.size());
   b->fused_n.resize(count);
@@ -3089,30 +3155,39 @@ mcl_status batch_launch(mcl_batch* b) {
   b->beam_n.resize(count);
   b->beam_B.resize(count);
   b->first_beam.resize(count);
-  bool any_beam = false;
+  b->ndt_n.resize(count);
+  b->ndt_cells.resize(count);
+  b->first_ndt.resize(count);
+  bool any_beam = false, any_ndt = false;
   for (uint32_t k = 0; k < count; ++k) {
     const HeldCycle& held = b->held[b->fused[k]];
     const BatchItem& it = held.item;
     b->fused_n[k] = it.n;
-    b->fused_lds[k] = held.beam ? 0u : static_cast<uint32_t>(lf_palette_lds(it.f));
+    b->fused_lds[k] = (held.beam || held.ndt) ? 0u : static_cast<uint32_t>(lf_palette_lds(it.f));
+    b->ndt_n[k] = held.ndt ? it.n : 0;
+    b->ndt_cells[k] = held.ndt ? it.ndt_cells : 0u;
+    any_ndt = any_ndt || held.ndt;
     b->beam_n[k] = held.beam ? it.n : 0;
     b->beam_B[k] = held.beam ? it.B : 0u;
     any_beam = any_beam || held.beam;
   }
   BatchGrid grid = batch_layout(b->fused_n.data(), b->fused_lds.data(), count, b->first_propagate.data(), b->first_reweight.data());
   BatchBeamGrid beam{0, 0};
-  if (any_beam) {
-    // The likelihood-field reweight's blocks are those of its own members: the same layout over sizes with the beam members' at 0 (a
+  uint32_t ndt_blocks = 0;
+  if (any_beam || any_ndt) {
+    // The likelihood-field reweight's blocks are those of its own members: the same layout over sizes with the other families' at 0 (a
     // member without a block is never found).  The propagation's blocks stay those of all members.
     b->lf_n.resize(count);
     b->first_unused.resize(count);
-    for (uint32_t k = 0; k < count; ++k) b->lf_n[k] = b->beam_n[k] ? 0 : b->fused_n[k];
+    for (uint32_t k = 0; k < count; ++k) b->lf_n[k] = (b->beam_n[k] || b->ndt_n[k]) ? 0 : b->fused_n[k];
     const BatchGrid lf = batch_layout(b->lf_n.data(), b->fused_lds.data(), count, b->first_unused.data(), b->first_reweight.data());
     grid.reweight_blocks = lf.reweight_blocks;
     grid.reweight_lds = lf.reweight_lds;
     beam = batch_beam_layout(b->beam_n.data(), b->beam_B.data(), count, b->first_beam.data());
+    ndt_blocks = batch_ndt_layout(b->ndt_n.data(), b->ndt_cells.data(), count, b->first_ndt.data());
   } else {
     std::fill(b->first_beam.begin(), b->first_beam.end(), 0u);
+    std::fill(b->first_ndt.begin(), b->first_ndt.end(), 0u);
   }
   for (uint32_t k = 0; k < count; ++k) {
     BatchItem& it = b->h_items.host[k];
@@ -3120,11 +3195,13 @@ mcl_status batch_launch(mcl_batch* b) {
     it.first_propagate_block = b->first_propagate[k];
     it.first_reweight_block = b->first_reweight[k];
     it.first_beam_block = b->first_beam[k];
+    it.first_ndt_block = b->first_ndt[k];
   }
   if (hipMemcpyAsync(b->d_items.ptr, b->h_items.host, count * sizeof(BatchItem), hipMemcpyHostToDevice, b->stream) != hipSuccess)
     return batch_fail(b, MCL_ERR_HIP, "mcl_batch_update: the copy of the cycle's records failed");
-  b->kernel_launches += launch_batch_cycle(b->stream, b->d_items.ptr, grid, beam);
+  b->kernel_launches += launch_batch_cycle(b->stream, b->d_items.ptr, grid, beam, ndt_blocks);
   if (beam.blocks) b->beam_launches += 1;
+  if (ndt_blocks) b->ndt_launches += 1;
   for (const uint32_t i : b->fused) small_tail_launched(b->members[i], b->held[i].every_n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
@@ -3280,6 +3357,7 @@ mcl_status mcl_batch_create(const mcl_config* cfgs, uint32_t count, mcl_batch** 
   b->report.resize(count);
   b->est.resize(count);
   b->shared.resize(count);
+  b->handed_back.resize(count);
   b->cluster_facts.resize(count);
   b->picked.reserve(count);
   b->summed.reserve(count);
@@ -3357,10 +3435,13 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
       mcl_ctx* ctx = batch->members[i];
       if (launched != MCL_OK) status[i] = fail(ctx, launched, batch->error);
       else status[i] = bind_device(ctx);
-      if (status[i] == MCL_OK) report[i] = small_cycle_state(ctx);
       est[i] = mcl_estimate{};
+      // (an NDT member whose tail handed back finishes its own cycle here, estimate included, as its lone mcl_update does)
+      batch->handed_back[i] = status[i] == MCL_OK && small_cycle_handed_back(ctx);
+      if (batch->handed_back[i]) status[i] = finish_handed_back_cycle(ctx, &est[i], &report[i]);
+      else if (status[i] == MCL_OK) report[i] = small_cycle_state(ctx);
       const mcl_cluster_params& cp = ctx->cluster_params;
-      batch->cluster_facts[k] = BatchClusterFacts{status[i], ctx->estimate_kind, ctx->tuning.batch_cluster_fused != 0, ctx->n, cp.linear_hash_resolution,
+      batch->cluster_facts[k] = BatchClusterFacts{batch->handed_back[i] ? MCL_ERR_UNSUPPORTED : status[i], ctx->estimate_kind, ctx->tuning.batch_cluster_fused != 0, ctx->n, cp.linear_hash_resolution,
                                                   cp.angular_hash_resolution, cp.weight_cap_percentile};
     }
     // the estimates: the cluster-based ones that qualify through the shared launches, every other one as the lone cycle takes it
@@ -3374,11 +3455,12 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
     batch->cluster_launches += batch_cluster_estimates(batch);
     for (const uint32_t i : batch->fused) {
       mcl_ctx* ctx = batch->members[i];
-      if (status[i] == MCL_OK && !batch->shared[i]) status[i] = small_cycle_estimate(ctx, &est[i]);
+      if (status[i] == MCL_OK && !batch->shared[i] && !batch->handed_back[i]) status[i] = small_cycle_estimate(ctx, &est[i]);
       if (status[i] != MCL_OK) continue;
       finish_cycle(ctx, est[i], report[i], estimates ? &estimates[i] : nullptr, infos ? &infos[i] : nullptr);
       batch->members_fused += 1;
       if (batch->held[i].beam) batch->members_beam_fused += 1;
+      if (batch->held[i].ndt) batch->members_ndt_fused += 1;
       any_updated = true;
     }
   }
@@ -3417,6 +3499,13 @@ mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* v
     return MCL_OK;
   }
   return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_get_counter: unknown counter " + key);
+}
+
+mcl_status mcl_ndt_batch_counts(mcl_batch* batch, uint64_t* launches, uint64_t* members) {
+  if (!batch) return MCL_ERR_INVALID_ARGUMENT;
+  if (launches) *launches = batch->ndt_launches;
+  if (members) *members = batch->members_ndt_fused;
+  return MCL_OK;
 }
 
 mcl_status mcl_update_laser_scan(mcl_ctx* ctx, const double control_pose[4], const mcl_laser_scan* scan, mcl_estimate* estimate,
@@ -3961,6 +4050,29 @@ mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* mea
   ctx->ndt_params = map.params;
   ctx->have_ndt_params = true;
   ndt_install_view(ctx, map.shape, map.params, n, resolution);
+  return MCL_OK;
+}
+
+mcl_status mcl_set_ndt_small_cycle(mcl_ctx* ctx, int32_t on) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_small_cycle: the context's sensor model is not MCL_SENSOR_NDT");
+  if (on != 0 && on != 1) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, "mcl_set_ndt_small_cycle: the value must be 0 or 1");
+  ctx->ndt_small_cycle = on != 0;
+  return MCL_OK;
+}
+
+mcl_status mcl_get_ndt_small_cycle(mcl_ctx* ctx, int32_t* on) {
+  if (!ctx || !on) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_get_ndt_small_cycle: the context's sensor model is not MCL_SENSOR_NDT");
+  *on = ctx->ndt_small_cycle ? 1 : 0;
+  return MCL_OK;
+}
+
+mcl_status mcl_get_ndt_small_cycle_counts(mcl_ctx* ctx, uint64_t* completed, uint64_t* handed_back) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_get_ndt_small_cycle_counts: the context's sensor model is not MCL_SENSOR_NDT");
+  if (completed) *completed = ctx->ndt_small_completed;
+  if (handed_back) *handed_back = ctx->ndt_small_handed_back;
   return MCL_OK;
 }
 

@@ -312,6 +312,24 @@ HostPolicy host_policy(ExponentialFilter& slow, ExponentialFilter& fast, bool se
 
 // ---- particle shards -----------------------------------------------------------------------------------------------------------------
 
+bool ndt_cycle_is_small(const NdtCycleFacts& f) {
+  return f.small_cycle && f.small_fused && !f.profiling && f.n >= 1 && f.n <= kSmallCycleMaxParticles && f.max_particles >= 1 &&
+         f.max_particles <= kSmallCycleMaxParticles;
+}
+
+void ndt_hand_back_taken(const NdtHandBack& h, ExponentialFilter& slow, ExponentialFilter& fast) {
+  slow.output = h.slow;
+  fast.output = h.fast;
+}
+
+void ndt_hand_back_resamples(const NdtHandBack& h, ExponentialFilter& slow, ExponentialFilter& fast, bool* force_update) {
+  if (h.p > 0.0) {  // :184-186
+    slow.reset();
+    fast.reset();
+  }
+  *force_update = false;  // :199
+}
+
 void shard_bounds(uint64_t n_total, uint32_t world, uint32_t rank, uint64_t* first, uint64_t* count) {
   const uint64_t base = n_total / world, rem = n_total % world;
   *first = rank * base + std::min<uint64_t>(rank, rem);

@@ -195,6 +195,34 @@ struct HostPolicy {
 HostPolicy host_policy(ExponentialFilter& slow, ExponentialFilter& fast, bool selective_resampling, bool fires, double norm_sum,
                        double norm_sumsq, uint64_t n);
 
+// ---- the small cycle of an NDT context (mcl_set_ndt_small_cycle) ----------------------------------------------------------------------
+// Does this NDT cycle run k_propagate_small, k_reweight_ndt_wave, k_small_tail with one synchronisation?  The size rule is the
+// likelihood-field small cycle's (one workgroup of k_small_tail holds the set and the candidates of a resampling).
+struct NdtCycleFacts {
+  bool small_cycle;        // the context's switch
+  bool small_fused;        // option small_fused
+  bool profiling;          // stage profiling on
+  uint64_t n;              // particles of the live set
+  uint64_t max_particles;  // min(max_particles, capacity)
+};
+constexpr uint64_t kSmallCycleMaxParticles = 4096;
+bool ndt_cycle_is_small(const NdtCycleFacts& f);
+// The wave-per-particle kernel for a stage-level reweight (mcl_reweight, mcl_reweight_ndt_cells)?
+inline bool ndt_reweight_takes_waves(bool small_cycle, uint64_t n) { return small_cycle && n <= kSmallCycleMaxParticles; }
+// The tail ends an NDT cycle that resamples with a random state probability > 0 behind the policies, without drawing: the generator of
+// the random states is N(estimate of the normalised set), which the host forms (amcl_core.hpp:182).  What it leaves in the mirror:
+struct NdtHandBack {
+  double slow, fast;  // the recovery filters' outputs as :179 leaves them - NOT reset (:184-186 comes behind :182, which may throw)
+  double p, ess, weight_sum;
+};
+// The host's side of such a cycle, in the reference's order of events (:179-199).  every_n was stored when the tail was launched
+// (:181 has run on the device) and the step number when the cycle began: neither moves here.
+// taken: :179 - the filters take the tail's outputs.  A generator that is refused (MCL_ERR_BAD_COVARIANCE) ends the cycle here: estimator
+// and policy advanced, no reset, no particle replaced, force_update as it was.
+void ndt_hand_back_taken(const NdtHandBack& h, ExponentialFilter& slow, ExponentialFilter& fast);
+// resamples: the generator stands - :184-186 the filters' reset (p > 0, as in every handed-back cycle), :199 force_update cleared.
+void ndt_hand_back_resamples(const NdtHandBack& h, ExponentialFilter& slow, ExponentialFilter& fast, bool* force_update);
+
 // ---- particle shards -----------------------------------------------------------------------------------------------------------------
 // Contiguous, balanced split of [0, n_total) over the ranks.
 void shard_bounds(uint64_t n_total, uint32_t world, uint32_t rank, uint64_t* first, uint64_t* count);

@@ -135,6 +135,8 @@ struct NdtMapView {
 // NDTSensorModel::operator() (ndt_sensor_model.hpp:216-239): w[i] *= 1 + sum over the k measurement cells (kNdtRecord doubles each,
 // base frame) of max(sum of the present neighbours' d1 exp(-d2/2 e^T (S' + S_map)^-1 e), minimum_likelihood).  A lane per particle.
 void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k);
+// The same weights, bit for bit, from a wave per particle with the lanes over the measurement cells (k_reweight_ndt_wave): small sets.
+void launch_reweight_ndt_wave(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k);
 
 // The NDT map built on the device (ndt_build_kernels.hip): detail::to_cells with fit_points over n points, as ndt_fit_cells (ndt_host.cpp)
 // does on the host - keys by truncation toward zero, cells of 5 points or more in ascending (x, y) key order, a cell's sums taken in
@@ -486,6 +488,7 @@ enum ScalarSlot : int {
   kSlotPolicy = 20,       // [20..23) the device-side recovery estimator (RecoveryPolicy::d_policy): {slow, fast, p}; p is mirrored
   kSlotPolicyFast = 21,
   kSlotPolicyP = 22,      // the random state probability
+  kSlotHandBack = 23,     // mirrored, k_small_tail on an NDT context: 1 if the tail handed the cycle back behind the policies, else 0
   kSlotPatchTotals = 24,  // device: [24..27) the LDS-patch kernel's running totals (PatchStats::device, 64-bit words)
   kSlotDoneTicket = 27,   // device: the completion ticket (Completion::d_ticket, a 64-bit word)
   kSlotPatchMirror = 28,  // host: [28..31) the patch totals as the kernel copies them (PatchStats::mirror, 64-bit words)
@@ -493,13 +496,16 @@ enum ScalarSlot : int {
   kSlotDoneWord = 31,     // host: the completion word (Completion::host_flag, a 64-bit word)
   kScalarSlots = 32
 };
-static_assert(kSlotEstimate + 9 == kSlotOverflow && kSlotPolicyP < kSlotPatchTotals && kSlotPatchTotals + 3 == kSlotDoneTicket &&
+static_assert(kSlotEstimate + 9 == kSlotOverflow && kSlotPolicyP < kSlotHandBack && kSlotHandBack < kSlotPatchTotals && kSlotPatchTotals + 3 == kSlotDoneTicket &&
                   kSlotDoneWord < kScalarSlots,
               "the scalar block's ranges overlap or do not fit in kScalarSlots doubles");
 // The whole tail of a small set's cycle - normalise, policies, resample (fixed size or KLD-adaptive), estimate sums - in one launch of one
 // workgroup (k_small_tail; sets and candidate streams of up to 4096 particles).  Results through `mirror` (the mapped host block) and
 // d_scalars: the slots marked k_small_tail above, kSlotWeightSum .. kSlotNormSumSq, kSlotEstimate and kSlotPolicy's three.  fires: every_n
 // says so this cycle.  Returns false, nothing launched, where the set does not fit.
+// hand_back (an NDT context, mcl_set_ndt_small_cycle): a cycle that resamples with a random state probability > 0 ends behind the
+// policies - the normalised weights stored, the scalars mirrored with the recovery filters NOT reset, kSlotResampled 0, kSlotHandBack 1 -
+// and draws nothing: the host builds the generator of the random states and finishes the cycle.  Every other cycle as without it.
 struct SmallTail {
   Particles src, dst;
   uint32_t n, min_particles, max_particles;
@@ -515,6 +521,7 @@ struct SmallTail {
   double* d_scalars;
   unsigned long long* done_flag{nullptr};  // completion word in mapped host memory (optional) and the value it takes
   unsigned long long done_seq{0};
+  bool hand_back{false};
 };
 bool launch_small_tail(hipStream_t st, const SmallTail& t);
 // The kernel's own argument record (k_small_tail takes it by value, k_batch_small_tail from its member's BatchItem).
@@ -537,6 +544,7 @@ struct SmallTailArgs {
   double* d_out;            // the same values in device memory (d_scalars)
   unsigned long long* done_flag;  // optional: a word of mapped host memory that takes done_seq behind everything mirrored (cycle_spin)
   unsigned long long done_seq;
+  int hand_back;            // NDT: end behind the policies where the cycle resamples with p > 0 (SmallTail::hand_back)
 };
 SmallTailArgs small_tail_args(const SmallTail& t);
 bool small_tail_fits(uint64_t n, uint64_t max_particles);  // launch_small_tail's own test: both 1 .. 4096
@@ -571,10 +579,14 @@ struct BatchItem {
   uint32_t first_propagate_block, first_reweight_block;  // batch_layout (a beam member has no block in the second)
   BatchBeam beam;             // a beam member's k_reweight_beam arguments; a likelihood-field member's stays zero
   uint32_t first_beam_block;  // batch_beam_layout (a likelihood-field member has no block)
+  NdtMapView ndt;             // an NDT member's k_reweight_ndt_wave arguments (its measurement cells are scan_dst); another member's stays zero
+  uint32_t ndt_cells;         // ... the staged measurement cells, kNdtRecord doubles each
+  uint32_t first_ndt_block;   // batch_ndt_layout (a member of another family has no block)
 };
-// k_batch_propagate, k_batch_reweight_lf_beams (if grid.reweight_blocks), k_batch_reweight_beam (if beam.blocks), k_batch_small_tail over
-// d_items[0 .. grid.members), in this order on `st`.  Returns the kernels enqueued.
-uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam);
+// k_batch_propagate, k_batch_reweight_lf_beams (if grid.reweight_blocks), k_batch_reweight_beam (if beam.blocks), k_batch_reweight_ndt (if
+// ndt_blocks), k_batch_small_tail over d_items[0 .. grid.members), in this order on `st`.  Returns the kernels enqueued.
+uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam, uint32_t ndt_blocks = 0);
+void launch_batch_reweight_ndt(hipStream_t st, const BatchItem* d_items, uint32_t members, uint32_t blocks);  // (ndt_kernels.hip)
 void launch_batch_reweight_beam(hipStream_t st, const BatchItem* d_items, uint32_t members, const BatchBeamGrid& grid);  // (beam_kernels.hip)
 // K6: one thread per candidate (views/sample.hpp:102,133-135; random_intersperse.hpp:90-115; particle_traits.hpp:105).
 void launch_resample_draw(hipStream_t st, Particles src, CdfTree cdf, const double* d_total, Particles dst,

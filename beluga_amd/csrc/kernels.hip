@@ -3501,6 +3501,10 @@ __device__ __forceinline__ void small_tail_block(const SmallTailArgs& a) {
     ess = norm_sum == 0.0 ? 0.0 : (norm_sum * norm_sum) / norm_sumsq;
     resample = ess < static_cast<double>(n) * 0.5;
   }
+  // (uniform) an NDT cycle that would inject random states: their generator, N(estimate of the normalised set), is the host's to build
+  // (amcl_core.hpp:182) - the set stays as normalised, the filters are not reset, and the host draws (SmallTail::hand_back)
+  const bool hand_back = a.hand_back != 0 && resample && p > 0.0;
+  if (hand_back) resample = false;
   if (resample && p > 0.0) slow = fast = 0.0;  // amcl_core.hpp:184-186
   double v[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint32_t n_out = n;
@@ -3707,6 +3711,7 @@ __device__ __forceinline__ void small_tail_block(const SmallTailArgs& a) {
     a.out[kSlotPolicy] = a.d_out[kSlotPolicy] = slow;  // (the device-side policy slot of the large path: {slow, fast, p})
     a.out[kSlotPolicyFast] = a.d_out[kSlotPolicyFast] = fast;
     a.out[kSlotPolicyP] = a.d_out[kSlotPolicyP] = p;
+    if (a.hand_back) a.out[kSlotHandBack] = a.d_out[kSlotHandBack] = hand_back ? 1.0 : 0.0;
   }
   if (a.done_flag) {  // (uniform) the host may be watching this word instead of the stream
     __threadfence_system();
@@ -4958,6 +4963,7 @@ SmallTailArgs small_tail_args(const SmallTail& t) {
   a.d_out = t.d_scalars;
   a.done_flag = t.done_flag;
   a.done_seq = t.done_seq;
+  a.hand_back = t.hand_back ? 1 : 0;
   return a;
 }
 bool launch_small_tail(hipStream_t st, const SmallTail& t) {
@@ -4966,14 +4972,15 @@ bool launch_small_tail(hipStream_t st, const SmallTail& t) {
   return true;
 }
 
-uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam) {
+uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam, uint32_t ndt_blocks) {
   if (grid.members == 0) return 0;
   hipLaunchKernelGGL(k_batch_propagate, dim3(grid.propagate_blocks), dim3(kBlock), 0, st, d_items, grid.members);
   if (grid.reweight_blocks)  // (the likelihood-field members' reweight: every fused member of a fleet without beam members)
     hipLaunchKernelGGL(k_batch_reweight_lf_beams, dim3(grid.reweight_blocks), dim3(kBeamsBlock), grid.reweight_lds, st, d_items, grid.members);
   launch_batch_reweight_beam(st, d_items, grid.members, beam);
+  launch_batch_reweight_ndt(st, d_items, grid.members, ndt_blocks);
   hipLaunchKernelGGL(k_batch_small_tail, dim3(grid.members), dim3(kSmallBlock), kSmallLdsBytes, st, d_items);
-  return 2u + (grid.reweight_blocks ? 1u : 0u) + (beam.blocks ? 1u : 0u);
+  return 2u + (grid.reweight_blocks ? 1u : 0u) + (beam.blocks ? 1u : 0u) + (ndt_blocks ? 1u : 0u);
 }
 
 void launch_estimate_sums(hipStream_t st, Particles p, uint64_t n, double pivot_x, double pivot_y, double* d_partials,

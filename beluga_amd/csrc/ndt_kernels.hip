@@ -8,6 +8,7 @@
 // few hundred KB for a building-sized map at 1 m: they stay in L2.
 #include <hip/hip_runtime.h>
 
+#include "batch_host.h"
 #include "device_common.hpp"
 
 namespace mcl {
@@ -68,11 +69,61 @@ __global__ __launch_bounds__(kBlock) void k_reweight_ndt(Particles p, uint64_t n
   p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
 }
 
+// The same weights from a wave per particle (small sets: at 2000 particles a lane per particle is eight workgroups on 256 CUs, each lane
+// walking K cells x up to 9 neighbours x one f64 exp in a row).  Lane l of pass q takes measurement cell 64 q + l, each lane loading
+// its own record; the sum keeps k_reweight_ndt's association, so the weight is the same bits: a pass of 64 cells is sixteen aligned blocks
+// of four, each block's (l0 + l1) + (l2 + l3) is formed across its four lanes by two quad permutations (a + b = b + a: lane 0 of the
+// quad holds exactly sum4), and the quad sums are chained into the running sum in cell order through v_readlane; the last K mod 4 cells
+// follow one by one.  Every lane carries the same running sum.  No workgroup memory, no atomics.
+// (the body: block `block` of ONE set - blockIdx.x in k_reweight_ndt_wave, a member's local block in k_batch_reweight_ndt)
+__device__ __forceinline__ void reweight_ndt_wave_block(uint32_t block, const Particles& p, uint64_t n, const NdtMapView& m,
+                                                        const double* __restrict__ meas, uint32_t k) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n) return;  // (the whole wave)
+  const Pose2 s = load_pose(p, i);
+  double acc = 1.0;
+  for (uint32_t base = 0; base < k; base += kWave) {
+    const uint32_t j = base + lane;
+    double l = 0.0;
+    if (j < k) l = ndt_cell_likelihood(m, meas + static_cast<size_t>(j) * kNdtRecord, s);
+    double quad = l + dpp_f64<0xB1>(l);  // quad_perm [1,0,3,2]: lanes 0 and 2 of a quad hold l0 + l1 and l2 + l3
+    quad = quad + dpp_f64<0x4E>(quad);   // quad_perm [2,3,0,1]: lane 0 holds (l0 + l1) + (l2 + l3)
+    const uint32_t left = k - base;      // cells from this pass on
+    const uint32_t full = left >= kWave ? kWave / 4 : left / 4;
+#pragma unroll
+    for (uint32_t b = 0; b < kWave / 4; ++b)
+      if (b < full) acc += readlane_f64(quad, 4 * b);
+    if (left < kWave)
+      for (uint32_t r = 4 * full; r < left; ++r) acc += readlane_f64(l, static_cast<int>(r));
+  }
+  if (lane == 0) p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
+}
+__global__ __launch_bounds__(kBlock) void k_reweight_ndt_wave(Particles p, uint64_t n, NdtMapView m, const double* __restrict__ meas, uint32_t k) {
+  reweight_ndt_wave_block(blockIdx.x, p, n, m, meas, k);
+}
+// The same over a fleet's NDT members (mcl_batch_update; the pattern is k_batch_reweight_beam, beam_kernels.hip): a workgroup finds its
+// member over the first_ndt_block prefix - a member without a block (n = 0, no measurement cell, another family's member) is never found -
+// and runs the body with its LOCAL block number on the member's own map and staged cells.
+static_assert(kBatchNdtThreads == kBlock && kBatchNdtBlock == kBlock / kWave, "batch_host.h restates the wave-per-particle NDT kernel's launch geometry");
+__global__ __launch_bounds__(kBlock) void k_batch_reweight_ndt(const BatchItem* __restrict__ items, uint32_t count) {
+  const BatchItem& it = items[batch_member_of(count, blockIdx.x, [items](uint32_t m) { return items[m].first_ndt_block; })];
+  reweight_ndt_wave_block(blockIdx.x - it.first_ndt_block, it.p, it.n, it.ndt, it.scan_dst, it.ndt_cells);
+}
+
 }  // namespace
 
 void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k) {
   if (n == 0) return;
   hipLaunchKernelGGL(k_reweight_ndt, dim3(blocks_for(n)), dim3(kBlock), 0, st, p, n, m, meas, k);
+}
+void launch_reweight_ndt_wave(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_reweight_ndt_wave, dim3(batch_ndt_blocks(n, 1)), dim3(kBlock), 0, st, p, n, m, meas, k);
+}
+void launch_batch_reweight_ndt(hipStream_t st, const BatchItem* d_items, uint32_t members, uint32_t blocks) {
+  if (blocks == 0) return;
+  hipLaunchKernelGGL(k_batch_reweight_ndt, dim3(blocks), dim3(kBlock), 0, st, d_items, members);
 }
 
 }  // namespace mcl

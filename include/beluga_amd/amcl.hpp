@@ -738,6 +738,22 @@ class Amcl {
     field_.reset();
   }
 
+  /// Extension (the NDT constructor form only; throws on another sensor model): the small cycle of an NDT filter,
+  /// mcl_set_ndt_small_cycle.  Sets of up to 4096 particles take a wave-per-particle reweight and the one-launch tail with one host
+  /// synchronisation; a cycle that would inject random states is handed back to the host behind the policies.  Off by default.
+  void set_ndt_small_cycle(bool on) { check(mcl_set_ndt_small_cycle(ctx_, on ? 1 : 0)); }
+  [[nodiscard]] bool ndt_small_cycle() const {
+    std::int32_t on = 0;
+    check(mcl_get_ndt_small_cycle(ctx_, &on));
+    return on != 0;
+  }
+  /// {small cycles that ended inside the one-launch tail, small cycles the tail handed back}: running totals.
+  [[nodiscard]] std::pair<std::uint64_t, std::uint64_t> ndt_small_cycle_counts() const {
+    std::uint64_t completed = 0, handed_back = 0;
+    check(mcl_get_ndt_small_cycle_counts(ctx_, &completed, &handed_back));
+    return {completed, handed_back};
+  }
+
   /// Extension: the NDT map built on the device from a point cloud in the world frame, by the rule of NDTMap2d::from_points (the same
   /// cells, bit for bit), and installed in place; the sensor model's parameters stay.
   void build_ndt_map(const std::vector<std::pair<double, double>>& points, double resolution) {

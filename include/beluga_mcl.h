@@ -267,6 +267,24 @@ mcl_status mcl_ndt_measurement_cells(const double* points_xy, uint64_t num_point
 /* Stage-level reweight from measurement cells fitted by the caller (means[k*2], covs[k*4] 2 x 2 row-major, base frame): w *= 1 +
  * sum over the cells of likelihood_at(state * cell).  mcl_reweight on an NDT context fits the cells of its points first. */
 mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const double* covs, uint64_t num_cells);
+/* The small cycle of an NDT context, off by default.  on = 1: a cycle whose set and min(max_particles, capacity) are both at most 4096,
+ * with the option small_fused on and stage profiling off, runs three launches and ONE host synchronisation, as a likelihood-field
+ * filter of that size does - the propagation, a reweight with a wave per particle and its lanes over the measurement cells (every
+ * weight bit for bit that of the lane-per-particle kernel), and the one-launch tail (normalisation, policies, resampling, estimate
+ * sums).  One kind of cycle does not end inside the tail: one that resamples with a random state probability > 0.  The generator of
+ * its random states, N(estimate of the normalised set), is the host's to build (amcl_core.hpp:182), so the tail stores the normalised
+ * weights and the policies' scalars, draws nothing and hands the cycle back; the host then takes the steps of the ordinary cycle from
+ * there on - the generator, the recovery filters' reset, the draw, the estimate.  The recovery filters, the every_n counter, the step
+ * number and force_update end up where the ordinary cycle leaves them, a generator that is refused (MCL_ERR_BAD_COVARIANCE) included:
+ * set propagated, reweighted and normalised, estimator and policy advanced, no particle replaced, estimator not reset.  Results agree
+ * with the ordinary cycle's within the rounding of the tail's sums (as the likelihood-field small cycle's do).  mcl_reweight and
+ * mcl_reweight_ndt_cells take the wave-per-particle kernel for sets of up to 4096 particles.  on = 0: everything as without the call.
+ * MCL_ERR_UNSUPPORTED on a context of another sensor model, MCL_ERR_INVALID_ARGUMENT for a value other than 0 or 1.
+ * mcl_get_ndt_small_cycle_counts: running totals of the small cycles that ended inside the tail and of those it handed back (either
+ * pointer may be NULL).  In a batch (mcl_batch_update) a member with the switch on rides the fleet's shared launches: see there. */
+mcl_status mcl_set_ndt_small_cycle(mcl_ctx* ctx, int32_t on);
+mcl_status mcl_get_ndt_small_cycle(mcl_ctx* ctx, int32_t* on);
+mcl_status mcl_get_ndt_small_cycle_counts(mcl_ctx* ctx, uint64_t* completed, uint64_t* handed_back);
 
 /* The map built on the device from what a user has at a cold start, a point cloud or an occupancy grid: detail::to_cells with
  * fit_points over the n points (world frame), the rule of mcl_ndt_measurement_cells - keys by (p / resolution) truncated toward zero,
@@ -450,9 +468,16 @@ mcl_status mcl_sample_particle_cloud(mcl_ctx* ctx, uint64_t size, uint32_t draw_
  * beam_sort_min_particles (from there on the member wants the ordered kernel), stage profiling off.  The beam members' reweight is one
  * more shared launch, between the propagation and the tail: a fleet of one family takes three launches per cycle, a fleet of both
  * takes four.  A scan of more than 4096 points is refused for such a member as by its own mcl_update (the kernel stages the scan in 64 KB
- * of workgroup memory): its status is its own, its state untouched, the others proceed.  Every other member (larger sets, beam members
- * with the option off or of the ordered kernel's size, the NDT and landmark models, profiling on) runs its ordinary cycle inside the same
- * call; a pending mcl_set_map_async map is swapped in where mcl_update would.
+ * of workgroup memory): its status is its own, its state untouched, the others proceed.  An NDT member shares the launches where its
+ * switch mcl_set_ndt_small_cycle is on and its own mcl_update would run the small cycle: not sharded, option small_fused on, the set
+ * and min(max_particles, capacity) both 1 .. 4096, an NDT map installed, stage profiling off.  Its scan is fitted on the host and
+ * staged per member as in its lone cycle; the NDT members' reweight is one more shared launch (a member without a measurement cell has
+ * no block in it).  A fleet of all three families takes five launches per cycle.  An NDT member whose tail hands its cycle back
+ * (mcl_set_ndt_small_cycle) finishes it inside the call, behind the shared synchronisation, with its own launches: its status - that
+ * of a refused generator, MCL_ERR_BAD_COVARIANCE, included -, estimate and info are its lone mcl_update's, and the others are not
+ * disturbed.  Every other member (larger sets, beam members with the option off or of the ordered kernel's size, NDT members with
+ * the switch off, the landmark models, profiling on) runs its ordinary cycle inside the same call; a pending mcl_set_map_async map is
+ * swapped in where mcl_update would.
  *
  * Counters (mcl_batch_get_counter): cycles = calls that updated at least one member; kernel_launches = kernels the shared cycle has
  * enqueued, a running total (per cycle with a fused member, however many members there are: 3 where the fused members are of one family,
@@ -460,7 +485,10 @@ mcl_status mcl_sample_particle_cloud(mcl_ctx* ctx, uint64_t size, uint32_t draw_
  * members_fused / members_alone = running totals of members that updated through the shared launches / through their ordinary cycle;
  * beam_launches = shared beam reweight kernels enqueued, a running total; members_beam_fused = running total of beam members that updated
  * through the shared launches (they count in members_fused as well).  A fused member's own counters (small_tail_launches,
- * lf_beams_launches, the cells of mcl_beam_cells_visited) advance as in a lone cycle.
+ * lf_beams_launches, the cells of mcl_beam_cells_visited) advance as in a lone cycle.  kernel_launches counts the NDT members' shared
+ * reweight as well (one more per cycle in which a fused NDT member has a measurement cell); mcl_ndt_batch_counts reads the running
+ * totals of those launches and of the NDT members that updated through the shared launches (they count in members_fused as well;
+ * either pointer may be NULL).
  *
  * The cluster-based estimate (mcl_set_estimate_kind 1: what beluga_ros::Amcl::update returns) of the fused members is batched as well:
  * behind the cycle's synchronisation, TWO shared launches of one workgroup per member - the occupied cells of every member into its own
@@ -484,6 +512,7 @@ mcl_status mcl_batch_member(mcl_batch* batch, uint32_t index, mcl_ctx** ctx);
 mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const double* points_xy, const uint64_t* point_offsets,
                             mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses);
 mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* value);
+mcl_status mcl_ndt_batch_counts(mcl_batch* batch, uint64_t* launches, uint64_t* members);
 const char* mcl_batch_last_error(const mcl_batch* batch); /* batch may be NULL: error of the last failed mcl_batch_create */
 
 /* ---- Shared maps: one uploaded map, many filters ------------------------------------------------------------------------------
