@@ -353,12 +353,14 @@ class SharedMap:
 class Amcl:
     def __init__(self, grid: OccupancyGrid, motion, sensor, params: AmclParams = AmclParams(), *,
                  seed: int = 0, device: int = 0, shard_offset: int = 0, shard_capacity: int = 0, hip_stream: int = 0,
-                 options: Optional[dict] = None, ndt_small_cycle: bool = False):
+                 options: Optional[dict] = None, ndt_small_cycle: bool = False, landmark_small_cycle: bool = False):
         """options: library switches applied before the map is installed (mcl_set_option), e.g. {"field_build": 1} to build
         the likelihood field with the device's exact distance transform instead of the reference's wavefront on the host.
-        ndt_small_cycle (NDT sensor model only): set_ndt_small_cycle(True) once the context exists."""
+        ndt_small_cycle (NDT sensor model only): set_ndt_small_cycle(True) once the context exists.
+        landmark_small_cycle (landmark and bearing sensor models only): set_landmark_small_cycle(True) likewise."""
         cfg = self._configure(grid, motion, sensor, params, seed=seed, device=device, shard_offset=shard_offset,
-                              shard_capacity=shard_capacity, hip_stream=hip_stream, ndt_small_cycle=ndt_small_cycle)
+                              shard_capacity=shard_capacity, hip_stream=hip_stream, ndt_small_cycle=ndt_small_cycle,
+                              landmark_small_cycle=landmark_small_cycle)
         ctx = capi._ctx()
         st = self._lib.mcl_create(C.byref(cfg), C.byref(ctx))
         if st != capi.MCL_OK:
@@ -368,12 +370,15 @@ class Amcl:
         self._attach(ctx, grid, options, owned=True)
 
     def _configure(self, grid, motion, sensor, params, *, seed=0, device=0, shard_offset=0, shard_capacity=0, hip_stream=0,
-                   ndt_small_cycle=False):
+                   ndt_small_cycle=False, landmark_small_cycle=False):
         """The mcl_config of these constructor arguments (and what the object remembers of them)."""
         self._lib = capi.load()
         if ndt_small_cycle and not isinstance(sensor, NDTModelParam2d):
             raise ValueError("ndt_small_cycle needs the NDT sensor model (NDTModelParam2d)")
         self._ndt_small_cycle = bool(ndt_small_cycle)
+        if landmark_small_cycle and not isinstance(sensor, (LandmarkModelParam, BearingModelParam)):
+            raise ValueError("landmark_small_cycle needs the landmark or the bearing sensor model")
+        self._landmark_small_cycle = bool(landmark_small_cycle)
         cfg = capi.Config()
         self._lib.mcl_default_config(C.byref(cfg))
         cfg.device_id = device
@@ -444,6 +449,8 @@ class Amcl:
             self.set_option(name, value)
         if getattr(self, "_ndt_small_cycle", False):
             self.set_ndt_small_cycle(True)
+        if getattr(self, "_landmark_small_cycle", False):
+            self.set_landmark_small_cycle(True)
         if grid is not None:  # (only a member of an AmclBatch may start without a map)
             self.update_map(grid)
 
@@ -736,6 +743,17 @@ class Amcl:
         self._check(self._lib.mcl_get_ndt_small_cycle_counts(self._ctx, C.byref(done), C.byref(back)))
         return done.value, back.value
 
+    def set_landmark_small_cycle(self, on: bool = True):
+        """mcl_set_landmark_small_cycle: small landmark and bearing sets (up to 4096 particles) take the wave-per-particle reweight and
+        the one-launch tail with one host synchronisation.  In an AmclBatch such a member rides the fleet's shared launches
+        (update_detections).  Off by default; raises on another sensor model."""
+        self._check(self._lib.mcl_set_landmark_small_cycle(self._ctx, int(bool(on))))
+
+    def landmark_small_cycle(self) -> bool:
+        on = C.c_int32(0)
+        self._check(self._lib.mcl_get_landmark_small_cycle(self._ctx, C.byref(on)))
+        return bool(on.value)
+
     def reweight_landmarks(self, detections):
         """Landmark model: w *= product over the detections (LandmarkPositionDetection entries or a (positions, categories) pair)."""
         xyz, cat = _detection_arrays(detections, "detection_position_in_robot")
@@ -1005,14 +1023,51 @@ class AmclBatch:
         self._have_info = True
         if check:
             self._check(self.last_status)
+        return self._results()
+
+    def _results(self):
+        """(pose, covariance) or None per member, from what the last call left."""
         out = []
-        for i in range(n):
+        for i in range(len(self.members)):
             if self._statuses[i] != capi.MCL_OK or not self._infos[i].updated:
                 out.append(None)
                 continue
             e = self._est_view[i].copy()
             out.append((e[:4], e[4:13].reshape(3, 3)))
         return out
+
+    def update_detections(self, controls, detections_per_member, check: bool = True):
+        """Amcl::update on every member of a fleet of landmark and bearing filters (mcl_landmark_batch_update): controls[i] and
+        detections_per_member[i] - a list of LandmarkPositionDetection / LandmarkBearingDetection or a (vectors, categories) pair -
+        are member i's.  Returns what update returns: (pose, covariance) or None per member, bit for bit members[i].update(...)'s.
+        Members with set_landmark_small_cycle(True) share three launches; the others run their own cycle inside the call."""
+        n = len(self.members)
+        if len(controls) != n or len(detections_per_member) != n:
+            raise ValueError("AmclBatch.update_detections: one control action and one list of detections per member")
+        vectors, categories = [], []
+        for i, member in enumerate(self.members):
+            self._controls[i] = controls[i]
+            attribute = "detection_bearing_in_sensor" if member._landmark_kind == capi.MCL_SENSOR_BEARING else "detection_position_in_robot"
+            xyz, cat = _detection_arrays(detections_per_member[i], attribute)
+            vectors.append(xyz)
+            categories.append(cat)
+        self._offsets[1:] = np.cumsum([len(v) for v in vectors])
+        return self.update_detection_offsets(self._controls, np.concatenate(vectors) if n else np.zeros((0, 3)),
+                                             np.concatenate(categories) if n else np.zeros(0, dtype=np.uint32), self._offsets, check=check)
+
+    def update_detection_offsets(self, controls, vectors_xyz, categories, detection_offsets, check: bool = False):
+        """The C call as it is: all detections in one vectors_xyz[total, 3] and categories[total] with detection_offsets[n + 1].
+        Returns the members' results; `last_status` and `statuses` tell what the call and every member answered."""
+        ctrl = np.ascontiguousarray(controls, dtype=np.float64).reshape(len(self.members), 4)
+        xyz = np.ascontiguousarray(vectors_xyz, dtype=np.float64)
+        cat = np.ascontiguousarray(categories, dtype=np.uint32)
+        off = np.ascontiguousarray(detection_offsets, dtype=np.uint64)
+        self.last_status = self._lib.mcl_landmark_batch_update(self._batch, _dp(ctrl), _dp(xyz), cat.ctypes.data_as(capi.c_u32_p),
+                                                               off.ctypes.data_as(capi.c_u64_p), self._estimates, self._infos, self._statuses)
+        self._have_info = True
+        if check:
+            self._check(self.last_status)
+        return self._results()
 
     def update_offsets(self, control_actions, points_xy, point_offsets):
         """The C call as it is: all scans in one points_xy[total, 2] with point_offsets[n + 1]; returns the call's status."""
@@ -1053,7 +1108,7 @@ class AmclBatch:
 
     def counter(self, name: str) -> int:
         """cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns, beam_launches,
-        members_beam_fused (mcl_batch_get_counter)."""
+        members_beam_fused, landmark_launches, members_landmark_fused (mcl_batch_get_counter)."""
         value = C.c_uint64(0)
         self._check(self._lib.mcl_batch_get_counter(self._batch, name.encode(), C.byref(value)))
         return value.value

@@ -230,6 +230,10 @@ _SIGNATURES = {
     "mcl_batch_update": (C.c_int32, [_batch, c_double_p, c_double_p, c_u64_p, C.POINTER(Estimate), C.POINTER(UpdateInfo), C.POINTER(C.c_int32)]),
     "mcl_batch_get_counter": (C.c_int32, [_batch, C.c_char_p, c_u64_p]),
     "mcl_ndt_batch_counts": (C.c_int32, [_batch, c_u64_p, c_u64_p]),
+    "mcl_landmark_batch_update": (C.c_int32, [_batch, c_double_p, c_double_p, c_u32_p, c_u64_p, C.POINTER(Estimate), C.POINTER(UpdateInfo),
+                                              C.POINTER(C.c_int32)]),
+    "mcl_set_landmark_small_cycle": (C.c_int32, [_ctx, C.c_int32]),
+    "mcl_get_landmark_small_cycle": (C.c_int32, [_ctx, C.POINTER(C.c_int32)]),
     "mcl_batch_last_error": (C.c_char_p, [_batch]),
     "mcl_shared_map_create": (C.c_int32, [C.POINTER(Config), c_i8_p, C.c_uint32, C.c_uint32, C.c_double, c_double_p, c_i8_p, C.c_int32,
                                           C.POINTER(_shared_map)]),
@@ -241,9 +245,9 @@ _SIGNATURES = {
     "mcl_measurement_build": (C.c_int, []),
 }
 
-# symbols a library may lack and still load (an older build named by BELUGA_MCL_LIB: tools/exp_ndt_small.py measures against one)
+# symbols a library may lack and still load (an older build named by BELUGA_MCL_LIB: tools/exp_ndt_small.py and tools/exp_landmark_small.py measure against one)
 _OPTIONAL = {"mcl_measurement_build", "mcl_set_ndt_small_cycle", "mcl_get_ndt_small_cycle", "mcl_get_ndt_small_cycle_counts",
-             "mcl_ndt_batch_counts"}
+             "mcl_ndt_batch_counts", "mcl_set_landmark_small_cycle", "mcl_get_landmark_small_cycle", "mcl_landmark_batch_update"}
 _lib = None
 
 

@@ -21,6 +21,11 @@ bool batch_ndt_member_fused(const BatchNdtFacts& m) {
          m.max_particles >= 1 && m.max_particles <= kBatchMaxParticles && m.have_map && !m.profiling;
 }
 
+bool batch_landmark_member_fused(const BatchLandmarkFacts& m) {
+  return (m.sensor_kind == MCL_SENSOR_LANDMARK || m.sensor_kind == MCL_SENSOR_BEARING) && m.small_cycle && !m.sharded && m.small_fused &&
+         m.n >= 1 && m.n <= kBatchMaxParticles && m.max_particles >= 1 && m.max_particles <= kBatchMaxParticles && !m.profiling;
+}
+
 bool batch_cluster_member(const BatchClusterFacts& m) {
   return m.status == MCL_OK && m.estimate_kind == 1 && m.cluster_fused && m.n >= 1 && m.n <= kBatchMaxParticles &&
          cluster_params_ok(m.linear_hash_resolution, m.angular_hash_resolution, m.weight_cap_percentile);
@@ -66,6 +71,15 @@ uint32_t batch_ndt_layout(const uint64_t* n, const uint32_t* K, uint32_t members
   for (uint32_t m = 0; m < members; ++m) {
     first_ndt[m] = blocks;
     blocks += batch_ndt_blocks(n[m], K[m]);
+  }
+  return blocks;
+}
+
+uint32_t batch_landmark_layout(const uint64_t* n, const uint32_t* k, uint32_t members, uint32_t* first_landmark) {
+  uint32_t blocks = 0;
+  for (uint32_t m = 0; m < members; ++m) {
+    first_landmark[m] = blocks;
+    blocks += batch_landmark_blocks(n[m], k[m]);
   }
   return blocks;
 }

@@ -22,6 +22,9 @@ constexpr uint32_t kBatchBeamPointBytes = 16;   // a scan point staged in its wo
 constexpr uint32_t kBatchBeamMaxPoints = 4096;  // 64 KB of it: the lone kernel's own limit (reweight_preconditions)
 constexpr uint32_t kBatchNdtThreads = 256;      // threads of a block of k_reweight_ndt_wave (kBlock)
 constexpr uint32_t kBatchNdtBlock = 4;          // ... and its particles, a wave each (kBlock / kWave)
+constexpr uint32_t kBatchLandmarkThreads = 256;  // threads of a block of k_reweight_landmarks_wave / k_reweight_bearings_wave (kBlock)
+constexpr uint32_t kBatchLandmarkBlock = 4;      // ... and its particles, a wave each (kBlock / kWave)
+constexpr uint32_t kBatchLandmarkMaxDetections = 64;  // MCL_LANDMARK_MAX_DETECTIONS: a wave's lanes
 
 // ---- which members share the launches ------------------------------------------------------------------------------------------------
 // What the predicate reads of a member in the cycle that is being prepared.
@@ -64,6 +67,19 @@ struct BatchNdtFacts {
 };
 // The member's own mcl_update would run exactly k_propagate_small, k_reweight_ndt_wave, k_small_tail.
 bool batch_ndt_member_fused(const BatchNdtFacts& m);
+
+// The same for a landmark or bearing member (mcl_set_landmark_small_cycle): what k_batch_reweight_landmarks' members must satisfy.
+struct BatchLandmarkFacts {
+  int sensor_kind;         // MCL_SENSOR_*
+  bool small_cycle;        // the context's switch (mcl_set_landmark_small_cycle)
+  bool sharded;            // the context is one rank of a sharded filter
+  bool small_fused;        // option small_fused
+  uint64_t n;              // particles of the live set
+  uint64_t max_particles;  // min(max_particles, capacity)
+  bool profiling;          // stage profiling on
+};
+// The member's own mcl_update_landmarks / mcl_update_bearings would run exactly k_propagate_small, the wave kernel of its kind, k_small_tail.
+bool batch_landmark_member_fused(const BatchLandmarkFacts& m);
 
 // ---- which fused members share the cluster-based estimate's two launches ------------------------------------------------------------------
 // What cluster_front checks of cluster parameters before anything is launched.
@@ -118,6 +134,14 @@ MCL_HD uint32_t batch_ndt_blocks(uint64_t n, uint32_t K) {
 // n[m], K[m] for m < members  ->  first_ndt[m]: the member's first block (a running sum; a member that is no NDT member of the cycle
 // comes with n = 0 or K = 0, has no block and is never found).  Returns the grid (0: nothing to launch).
 uint32_t batch_ndt_layout(const uint64_t* n, const uint32_t* K, uint32_t members, uint32_t* first_ndt);
+// The landmark and bearing members' launch (k_batch_reweight_landmarks).  A member with n = 0 or k = 0 detections has no block: its
+// weights stay (x 1.0).
+MCL_HD uint32_t batch_landmark_blocks(uint64_t n, uint32_t k) {
+  return (n == 0 || k == 0) ? 0u : static_cast<uint32_t>((n + kBatchLandmarkBlock - 1) / kBatchLandmarkBlock);
+}
+// n[m], k[m] for m < members  ->  first_landmark[m]: the member's first block (a running sum; a member that is no landmark member of the
+// cycle comes with n = 0 or k = 0, has no block and is never found).  Returns the grid (0: nothing to launch).
+uint32_t batch_landmark_layout(const uint64_t* n, const uint32_t* k, uint32_t members, uint32_t* first_landmark);
 // The member whose blocks include `block`: the LAST m with first_of(m) <= block (members without a block share their successor's first
 // block and are skipped).  Needs first_of(0) == 0 and block < the grid.  ceil(log2(members)) steps, each one read.
 template <class FirstOf>

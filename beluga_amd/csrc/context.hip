@@ -281,6 +281,11 @@ struct mcl_ctx {
   LandmarkRanges landmark_ranges;  // category -> (first, count) in d_landmarks
   FreeCells landmark_random{nullptr, 0};
   std::vector<double> h_landmark_meas;  // the detections, kLandmarkRecord doubles each (what stage_points uploads)
+  bool landmark_small_cycle{false};     // mcl_set_landmark_small_cycle: the wave-per-particle reweight and the one-launch tail for small sets
+  uint64_t landmark_wave_launches{0};   // launches of k_reweight_landmarks_wave / k_reweight_bearings_wave, a fleet's shared one included (mcl_get_counter)
+  LandmarkCycleFacts landmark_cycle_facts() const {
+    return LandmarkCycleFacts{landmark_small_cycle, tuning.small_fused != 0, profile != 0, n, std::min<uint64_t>(cfg.amcl.max_particles, capacity)};
+  }
   bool is_landmark() const { return cfg.sensor_kind == MCL_SENSOR_LANDMARK || cfg.sensor_kind == MCL_SENSOR_BEARING; }
   // A sensor model with a map of its own: no occupancy grid, none of the likelihood-field machinery, the host-read policy path.
   bool off_grid() const { return is_ndt() || is_landmark(); }
@@ -854,6 +859,7 @@ struct HeldCycle {
   bool pending{false};         // ... and its record is complete
   bool beam{false};            // fused, and the reweight is the beam model's (k_batch_reweight_beam)
   bool ndt{false};             // fused, and the reweight is the NDT model's (k_batch_reweight_ndt)
+  bool landmark{false};        // fused, and the reweight is the landmark or bearing model's (k_batch_reweight_landmarks)
   BatchItem item{};
   uint64_t every_n{0};         // the counter as the cycle leaves it
 };
@@ -990,7 +996,10 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
     hold->ndt = ctx->is_ndt() && batch_ndt_member_fused(BatchNdtFacts{
                                      ctx->cfg.sensor_kind, ctx->ndt_small_cycle, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
                                      ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), ctx->have_ndt_map, ctx->profile != 0});
-    hold->fused = hold->fused || hold->beam || hold->ndt;
+    hold->landmark = ctx->is_landmark() && batch_landmark_member_fused(BatchLandmarkFacts{
+                                     ctx->cfg.sensor_kind, ctx->landmark_small_cycle, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
+                                     ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), ctx->profile != 0});
+    hold->fused = hold->fused || hold->beam || hold->ndt || hold->landmark;
     if (!hold->fused) launch_held_propagate(ctx, hold);
   }
   if (ordered && !have_order) {
@@ -1014,8 +1023,22 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
   } else if (ctx->is_landmark()) {
     const uint32_t k = static_cast<uint32_t>(m.doubles / kLandmarkRecord);
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    if (ctx->cfg.sensor_kind == MCL_SENSOR_LANDMARK) launch_reweight_landmarks(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
-    else launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    const bool bearing = ctx->cfg.sensor_kind == MCL_SENSOR_BEARING;
+    const bool held = hold && hold->fused;
+    if (held) {  // (a held cycle: the batch launches k_batch_reweight_landmarks)
+      hold->item.landmark = ctx->landmark_view;
+      hold->item.landmark_k = k;
+      hold->item.landmark_bearing = bearing ? 1u : 0u;
+    }
+    if (held || landmark_reweight_takes_waves(ctx->landmark_small_cycle, ctx->n)) {
+      if (!held && bearing) launch_reweight_bearings_wave(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+      else if (!held) launch_reweight_landmarks_wave(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+      if (ctx->n != 0 && k != 0) ctx->landmark_wave_launches += 1;  // (no detection: no launch)
+    } else if (bearing) {
+      launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    } else {
+      launch_reweight_landmarks(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    }
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
     const bool held = hold && hold->fused;
@@ -2978,7 +3001,9 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   const uint64_t every_n = next_every_n(ctx->every_n_current, ap.resample_interval);  // :181 (stored by the path that takes the cycle)
   const bool fires = every_n == 0;
   // (an NDT context only with its switch on, mcl_set_ndt_small_cycle: the tail hands a cycle that would inject random states back)
-  const bool small = ctx->is_ndt() ? ndt_cycle_is_small(ctx->ndt_cycle_facts())
+  // (a landmark or bearing context likewise, mcl_set_landmark_small_cycle: its random states come from the map's box, inside the tail)
+  const bool small = ctx->is_ndt()        ? ndt_cycle_is_small(ctx->ndt_cycle_facts())
+                     : ctx->is_landmark() ? landmark_cycle_is_small(ctx->landmark_cycle_facts())
                                    : ctx->tuning.small_fused != 0 && !ctx->off_grid() && ctx->n <= 4096 &&
                                          std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096;
   if (hold && hold->fused) {  // the batch launches this cycle and finishes it
@@ -3117,6 +3142,8 @@ struct mcl_batch {
   std::vector<uint32_t> beam_B, first_beam, first_unused;
   std::vector<uint64_t> ndt_n;                // ... and the NDT members' (k_batch_reweight_ndt)
   std::vector<uint32_t> ndt_cells, first_ndt;
+  std::vector<uint64_t> landmark_n;           // ... and the landmark and bearing members' (k_batch_reweight_landmarks)
+  std::vector<uint32_t> landmark_k, first_landmark;
   std::vector<uint8_t> handed_back;           // by member: its tail handed the cycle back and it finished it itself
   // the cluster-based estimate's two shared launches: a record per member and launch, pinned and on the device
   HostBuffer<BatchClusterCells> h_cluster_cells;
@@ -3126,6 +3153,7 @@ struct mcl_batch {
   uint64_t cycles{0}, kernel_launches{0}, members_fused{0}, members_alone{0}, cluster_launches{0}, members_cluster_fused{0};
   uint64_t beam_launches{0}, members_beam_fused{0};  // shared beam reweight kernels enqueued; beam members that updated through the shared cycle
   uint64_t ndt_launches{0}, members_ndt_fused{0};    // the same for the NDT members (mcl_ndt_batch_counts)
+  uint64_t landmark_launches{0}, members_landmark_fused{0};  // the same for the landmark and bearing members
   uint64_t cluster_host_ns{0};  // host time between the two shared launches: every member's cells ordered, assigned, ids written
   // per call, kept for the next one: by member ...
   std::vector<mcl_status> status;
@@ -3158,12 +3186,18 @@ mcl_status batch_launch(mcl_batch* b) {
   b->ndt_n.resize(count);
   b->ndt_cells.resize(count);
   b->first_ndt.resize(count);
-  bool any_beam = false, any_ndt = false;
+  b->landmark_n.resize(count);
+  b->landmark_k.resize(count);
+  b->first_landmark.resize(count);
+  bool any_beam = false, any_ndt = false, any_landmark = false;
   for (uint32_t k = 0; k < count; ++k) {
     const HeldCycle& held = b->held[b->fused[k]];
     const BatchItem& it = held.item;
     b->fused_n[k] = it.n;
-    b->fused_lds[k] = (held.beam || held.ndt) ? 0u : static_cast<uint32_t>(lf_palette_lds(it.f));
+    b->fused_lds[k] = (held.beam || held.ndt || held.landmark) ? 0u : static_cast<uint32_t>(lf_palette_lds(it.f));
+    b->landmark_n[k] = held.landmark ? it.n : 0;
+    b->landmark_k[k] = held.landmark ? it.landmark_k : 0u;
+    any_landmark = any_landmark || held.landmark;
     b->ndt_n[k] = held.ndt ? it.n : 0;
     b->ndt_cells[k] = held.ndt ? it.ndt_cells : 0u;
     any_ndt = any_ndt || held.ndt;
@@ -3173,19 +3207,21 @@ mcl_status batch_launch(mcl_batch* b) {
   }
   BatchGrid grid = batch_layout(b->fused_n.data(), b->fused_lds.data(), count, b->first_propagate.data(), b->first_reweight.data());
   BatchBeamGrid beam{0, 0};
-  uint32_t ndt_blocks = 0;
-  if (any_beam || any_ndt) {
+  uint32_t ndt_blocks = 0, landmark_blocks = 0;
+  if (any_beam || any_ndt || any_landmark) {
     // The likelihood-field reweight's blocks are those of its own members: the same layout over sizes with the other families' at 0 (a
     // member without a block is never found).  The propagation's blocks stay those of all members.
     b->lf_n.resize(count);
     b->first_unused.resize(count);
-    for (uint32_t k = 0; k < count; ++k) b->lf_n[k] = (b->beam_n[k] || b->ndt_n[k]) ? 0 : b->fused_n[k];
+    for (uint32_t k = 0; k < count; ++k) b->lf_n[k] = (b->beam_n[k] || b->ndt_n[k] || b->landmark_n[k]) ? 0 : b->fused_n[k];
     const BatchGrid lf = batch_layout(b->lf_n.data(), b->fused_lds.data(), count, b->first_unused.data(), b->first_reweight.data());
     grid.reweight_blocks = lf.reweight_blocks;
     grid.reweight_lds = lf.reweight_lds;
     beam = batch_beam_layout(b->beam_n.data(), b->beam_B.data(), count, b->first_beam.data());
     ndt_blocks = batch_ndt_layout(b->ndt_n.data(), b->ndt_cells.data(), count, b->first_ndt.data());
+    landmark_blocks = batch_landmark_layout(b->landmark_n.data(), b->landmark_k.data(), count, b->first_landmark.data());
   } else {
+    std::fill(b->first_landmark.begin(), b->first_landmark.end(), 0u);
     std::fill(b->first_beam.begin(), b->first_beam.end(), 0u);
     std::fill(b->first_ndt.begin(), b->first_ndt.end(), 0u);
   }
@@ -3196,12 +3232,14 @@ mcl_status batch_launch(mcl_batch* b) {
     it.first_reweight_block = b->first_reweight[k];
     it.first_beam_block = b->first_beam[k];
     it.first_ndt_block = b->first_ndt[k];
+    it.first_landmark_block = b->first_landmark[k];
   }
   if (hipMemcpyAsync(b->d_items.ptr, b->h_items.host, count * sizeof(BatchItem), hipMemcpyHostToDevice, b->stream) != hipSuccess)
     return batch_fail(b, MCL_ERR_HIP, "mcl_batch_update: the copy of the cycle's records failed");
-  b->kernel_launches += launch_batch_cycle(b->stream, b->d_items.ptr, grid, beam, ndt_blocks);
+  b->kernel_launches += launch_batch_cycle(b->stream, b->d_items.ptr, grid, beam, ndt_blocks, landmark_blocks);
   if (beam.blocks) b->beam_launches += 1;
   if (ndt_blocks) b->ndt_launches += 1;
+  if (landmark_blocks) b->landmark_launches += 1;
   for (const uint32_t i : b->fused) small_tail_launched(b->members[i], b->held[i].every_n);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
@@ -3392,13 +3430,13 @@ mcl_status mcl_batch_member(mcl_batch* batch, uint32_t index, mcl_ctx** ctx) {
   return MCL_OK;
 }
 
-mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const double* points_xy, const uint64_t* point_offsets,
-                            mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses) {
-  if (!batch) return MCL_ERR_INVALID_ARGUMENT;
+}  // extern "C"
+namespace {
+// The fleet's update, shared by mcl_batch_update and mcl_landmark_batch_update.  member_cycle(i, ctx, estimate, info, hold): member i's
+// own update with ITS measurement - update_cycle with the hold, or the member's refusal.
+template <class MemberCycle>
+mcl_status batch_update_driver(mcl_batch* batch, mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses, MemberCycle&& member_cycle) {
   const uint32_t count = static_cast<uint32_t>(batch->members.size());
-  if (!control_poses) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_update: null control_poses");
-  if (const char* wrong = batch_check_offsets(point_offsets, count)) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, wrong);
-  if (point_offsets[count] != point_offsets[0] && !points_xy) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_update: null points");
   // prepare: every member's own cycle up to its launches; a cycle that is not the small one runs to its end here
   std::vector<mcl_status>& status = batch->status;
   std::fill(status.begin(), status.end(), MCL_OK);
@@ -3410,12 +3448,7 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
     hold = HeldCycle{};
     mcl_update_info own{};
     mcl_update_info* info = infos ? &infos[i] : &own;
-    const uint64_t first = point_offsets[i], points = point_offsets[i + 1] - first;
-    if (ctx->is_landmark())
-      status[i] = fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_update: a landmark or bearing context takes mcl_update_landmarks / mcl_update_bearings");
-    else
-      status[i] = update_cycle(ctx, control_poses + 4 * static_cast<size_t>(i), scan_measurement(points ? points_xy + 2 * first : nullptr, points),
-                               estimates ? &estimates[i] : nullptr, info, &hold);
+    status[i] = member_cycle(i, ctx, estimates ? &estimates[i] : nullptr, info, &hold);
     if (status[i] != MCL_OK) continue;
     if (hold.pending) {
       batch->fused.push_back(i);
@@ -3461,6 +3494,7 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
       batch->members_fused += 1;
       if (batch->held[i].beam) batch->members_beam_fused += 1;
       if (batch->held[i].ndt) batch->members_ndt_fused += 1;
+      if (batch->held[i].landmark) batch->members_landmark_fused += 1;
       any_updated = true;
     }
   }
@@ -3474,6 +3508,49 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
     }
   }
   return first_error;
+}
+}  // namespace
+extern "C" {
+
+static mcl_status landmark_measurement(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n,
+                                       Measurement* m);
+
+mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const double* points_xy, const uint64_t* point_offsets,
+                            mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses) {
+  if (!batch) return MCL_ERR_INVALID_ARGUMENT;
+  const uint32_t count = static_cast<uint32_t>(batch->members.size());
+  if (!control_poses) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_update: null control_poses");
+  if (const char* wrong = batch_check_offsets(point_offsets, count)) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, wrong);
+  if (point_offsets[count] != point_offsets[0] && !points_xy) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_batch_update: null points");
+  return batch_update_driver(batch, estimates, infos, statuses, [&](uint32_t i, mcl_ctx* ctx, mcl_estimate* estimate, mcl_update_info* info, HeldCycle* hold) {
+    const uint64_t first = point_offsets[i], points = point_offsets[i + 1] - first;
+    if (ctx->is_landmark())
+      return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_update: a landmark or bearing context takes mcl_update_landmarks / mcl_update_bearings");
+    return update_cycle(ctx, control_poses + 4 * static_cast<size_t>(i), scan_measurement(points ? points_xy + 2 * first : nullptr, points), estimate, info,
+                        hold);
+  });
+}
+
+mcl_status mcl_landmark_batch_update(mcl_batch* batch, const double* control_poses, const double* vectors_xyz, const uint32_t* categories,
+                                     const uint64_t* detection_offsets, mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses) {
+  if (!batch) return MCL_ERR_INVALID_ARGUMENT;
+  const uint32_t count = static_cast<uint32_t>(batch->members.size());
+  if (!control_poses) return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_landmark_batch_update: null control_poses");
+  if (batch_check_offsets(detection_offsets, count))
+    return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_landmark_batch_update: detection_offsets must be non-null and must not decrease");
+  if (detection_offsets[count] != detection_offsets[0] && (!vectors_xyz || !categories))
+    return batch_fail(batch, MCL_ERR_INVALID_ARGUMENT, "mcl_landmark_batch_update: null detections");
+  return batch_update_driver(batch, estimates, infos, statuses, [&](uint32_t i, mcl_ctx* ctx, mcl_estimate* estimate, mcl_update_info* info, HeldCycle* hold) {
+    const uint64_t first = detection_offsets[i], k = detection_offsets[i + 1] - first;
+    if (!ctx->is_landmark())
+      return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_landmark_batch_update: the member's sensor model is not MCL_SENSOR_LANDMARK or MCL_SENSOR_BEARING");
+    const bool bearing = ctx->cfg.sensor_kind == MCL_SENSOR_BEARING;
+    Measurement m{};
+    if (const mcl_status s = landmark_measurement(ctx, bearing ? "mcl_update_bearings" : "mcl_update_landmarks", ctx->cfg.sensor_kind,
+                                                  k ? vectors_xyz + 3 * first : nullptr, k ? categories + first : nullptr, k, &m))
+      return s;
+    return update_cycle(ctx, control_poses + 4 * static_cast<size_t>(i), m, estimate, info, hold);
+  });
 }
 
 mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* value) {
@@ -3491,6 +3568,8 @@ mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* v
       {"cluster_host_ns", &mcl_batch::cluster_host_ns},
       {"beam_launches", &mcl_batch::beam_launches},
       {"members_beam_fused", &mcl_batch::members_beam_fused},
+      {"landmark_launches", &mcl_batch::landmark_launches},
+      {"members_landmark_fused", &mcl_batch::members_landmark_fused},
   };
   const std::string key(name);
   for (const auto& c : kCounters) {
@@ -3889,6 +3968,7 @@ constexpr Counter kCounters[] = {
     {"lf_far_launches", &mcl_ctx::lf_far_launches},
     {"lf_far_beams_launches", &mcl_ctx::lf_far_beams_launches},
     {"small_tail_launches", &mcl_ctx::small_tail_launches},
+    {"landmark_wave_launches", &mcl_ctx::landmark_wave_launches},
     {"estimate_repivots", &mcl_ctx::estimate_repivots},
     {"noise_ahead_used", &mcl_ctx::noise_ahead_used},
     {"order_ahead_used", &mcl_ctx::order_ahead_used},
@@ -4205,6 +4285,23 @@ static mcl_status landmark_measurement(mcl_ctx* ctx, const char* who, int32_t ki
                                             ctx->h_landmark_meas, &error))
     return fail(ctx, s, error);
   *m = Measurement{ctx->h_landmark_meas.data(), ctx->h_landmark_meas.size()};
+  return MCL_OK;
+}
+
+mcl_status mcl_set_landmark_small_cycle(mcl_ctx* ctx, int32_t on) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_landmark())
+    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_landmark_small_cycle: the context's sensor model is not MCL_SENSOR_LANDMARK or MCL_SENSOR_BEARING");
+  if (on != 0 && on != 1) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, "mcl_set_landmark_small_cycle: the value must be 0 or 1");
+  ctx->landmark_small_cycle = on != 0;
+  return MCL_OK;
+}
+
+mcl_status mcl_get_landmark_small_cycle(mcl_ctx* ctx, int32_t* on) {
+  if (!ctx || !on) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_landmark())
+    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_get_landmark_small_cycle: the context's sensor model is not MCL_SENSOR_LANDMARK or MCL_SENSOR_BEARING");
+  *on = ctx->landmark_small_cycle ? 1 : 0;
   return MCL_OK;
 }
 

@@ -317,6 +317,11 @@ bool ndt_cycle_is_small(const NdtCycleFacts& f) {
          f.max_particles <= kSmallCycleMaxParticles;
 }
 
+bool landmark_cycle_is_small(const LandmarkCycleFacts& f) {
+  return f.small_cycle && f.small_fused && !f.profiling && f.n >= 1 && f.n <= kSmallCycleMaxParticles && f.max_particles >= 1 &&
+         f.max_particles <= kSmallCycleMaxParticles;
+}
+
 void ndt_hand_back_taken(const NdtHandBack& h, ExponentialFilter& slow, ExponentialFilter& fast) {
   slow.output = h.slow;
   fast.output = h.fast;

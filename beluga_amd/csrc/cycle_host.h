@@ -223,6 +223,20 @@ void ndt_hand_back_taken(const NdtHandBack& h, ExponentialFilter& slow, Exponent
 // resamples: the generator stands - :184-186 the filters' reset (p > 0, as in every handed-back cycle), :199 force_update cleared.
 void ndt_hand_back_resamples(const NdtHandBack& h, ExponentialFilter& slow, ExponentialFilter& fast, bool* force_update);
 
+// ---- the small cycle of a landmark or bearing context (mcl_set_landmark_small_cycle) --------------------------------------------------
+// Does this cycle run k_propagate_small, the wave-per-particle kernel of the context's kind, k_small_tail with one synchronisation?  The
+// size rule is the likelihood-field small cycle's.  Nothing is handed back: the random states come from the map's box, inside the tail.
+struct LandmarkCycleFacts {
+  bool small_cycle;        // the context's switch
+  bool small_fused;        // option small_fused
+  bool profiling;          // stage profiling on
+  uint64_t n;              // particles of the live set
+  uint64_t max_particles;  // min(max_particles, capacity)
+};
+bool landmark_cycle_is_small(const LandmarkCycleFacts& f);
+// The wave-per-particle kernels for a stage-level reweight (mcl_reweight_landmarks, mcl_reweight_bearings)?
+inline bool landmark_reweight_takes_waves(bool small_cycle, uint64_t n) { return small_cycle && n <= kSmallCycleMaxParticles; }
+
 // ---- particle shards -----------------------------------------------------------------------------------------------------------------
 // Contiguous, balanced split of [0, n_total) over the ranks.
 void shard_bounds(uint64_t n_total, uint32_t world, uint32_t rank, uint64_t* first, uint64_t* count);

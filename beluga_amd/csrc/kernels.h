@@ -203,6 +203,10 @@ void launch_reweight_landmarks(hipStream_t st, Particles p, uint64_t n, const La
 // none).  `detections` are sorted by category (their record says where they stand in the caller's order, which the product follows):
 // a landmark's bearing in the sensor frame is computed once per particle and serves every detection of its category.
 void launch_reweight_bearings(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k);
+// The same weights, bit for bit, from a wave per particle: the lanes over the detections, the search of a detection split over the lanes
+// of its group (k_reweight_landmarks_wave, k_reweight_bearings_wave): small sets, mcl_set_landmark_small_cycle.  k <= 64.
+void launch_reweight_landmarks_wave(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k);
+void launch_reweight_bearings_wave(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k);
 
 struct HashParams {
   double res_x, res_y, res_theta;
@@ -582,10 +586,17 @@ struct BatchItem {
   NdtMapView ndt;             // an NDT member's k_reweight_ndt_wave arguments (its measurement cells are scan_dst); another member's stays zero
   uint32_t ndt_cells;         // ... the staged measurement cells, kNdtRecord doubles each
   uint32_t first_ndt_block;   // batch_ndt_layout (a member of another family has no block)
+  LandmarkMapView landmark;   // a landmark or bearing member's wave kernel arguments (its detection records are scan_dst); else zero
+  uint32_t landmark_k;        // ... the staged detection records, kLandmarkRecord doubles each
+  uint32_t landmark_bearing;  // ... 1: the bearing model's body, 0: the landmark model's
+  uint32_t first_landmark_block;  // batch_landmark_layout (a member of another family has no block)
 };
 // k_batch_propagate, k_batch_reweight_lf_beams (if grid.reweight_blocks), k_batch_reweight_beam (if beam.blocks), k_batch_reweight_ndt (if
-// ndt_blocks), k_batch_small_tail over d_items[0 .. grid.members), in this order on `st`.  Returns the kernels enqueued.
-uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam, uint32_t ndt_blocks = 0);
+// ndt_blocks), k_batch_reweight_landmarks (if landmark_blocks), k_batch_small_tail over d_items[0 .. grid.members), in this order on `st`.
+// Returns the kernels enqueued.
+uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam, uint32_t ndt_blocks = 0,
+                            uint32_t landmark_blocks = 0);
+void launch_batch_reweight_landmarks(hipStream_t st, const BatchItem* d_items, uint32_t members, uint32_t blocks);  // (landmark_kernels.hip)
 void launch_batch_reweight_ndt(hipStream_t st, const BatchItem* d_items, uint32_t members, uint32_t blocks);  // (ndt_kernels.hip)
 void launch_batch_reweight_beam(hipStream_t st, const BatchItem* d_items, uint32_t members, const BatchBeamGrid& grid);  // (beam_kernels.hip)
 // K6: one thread per candidate (views/sample.hpp:102,133-135; random_intersperse.hpp:90-115; particle_traits.hpp:105).

@@ -4972,15 +4972,17 @@ bool launch_small_tail(hipStream_t st, const SmallTail& t) {
   return true;
 }
 
-uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam, uint32_t ndt_blocks) {
+uint32_t launch_batch_cycle(hipStream_t st, const BatchItem* d_items, const BatchGrid& grid, const BatchBeamGrid& beam, uint32_t ndt_blocks,
+                            uint32_t landmark_blocks) {
   if (grid.members == 0) return 0;
   hipLaunchKernelGGL(k_batch_propagate, dim3(grid.propagate_blocks), dim3(kBlock), 0, st, d_items, grid.members);
   if (grid.reweight_blocks)  // (the likelihood-field members' reweight: every fused member of a fleet without beam members)
     hipLaunchKernelGGL(k_batch_reweight_lf_beams, dim3(grid.reweight_blocks), dim3(kBeamsBlock), grid.reweight_lds, st, d_items, grid.members);
   launch_batch_reweight_beam(st, d_items, grid.members, beam);
   launch_batch_reweight_ndt(st, d_items, grid.members, ndt_blocks);
+  launch_batch_reweight_landmarks(st, d_items, grid.members, landmark_blocks);
   hipLaunchKernelGGL(k_batch_small_tail, dim3(grid.members), dim3(kSmallBlock), kSmallLdsBytes, st, d_items);
-  return 2u + (grid.reweight_blocks ? 1u : 0u) + (beam.blocks ? 1u : 0u) + (ndt_blocks ? 1u : 0u);
+  return 2u + (grid.reweight_blocks ? 1u : 0u) + (beam.blocks ? 1u : 0u) + (ndt_blocks ? 1u : 0u) + (landmark_blocks ? 1u : 0u);
 }
 
 void launch_estimate_sums(hipStream_t st, Particles p, uint64_t n, double pivot_x, double pivot_y, double* d_partials,

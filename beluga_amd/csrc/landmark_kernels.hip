@@ -14,6 +14,7 @@
 // reading the header, not from a run of the reference.  It moves last bits only.
 #include <hip/hip_runtime.h>
 
+#include "batch_host.h"
 #include "device_common.hpp"
 
 namespace mcl {
@@ -58,24 +59,18 @@ __device__ __forceinline__ Vec3 load_landmark(const double* __restrict__ landmar
   return Vec3{xy.x, xy.y, z.x};
 }
 
-// detection_weight of landmark_sensor_model.hpp:109-153 for the pose s
-__device__ __forceinline__ double landmark_term(const LandmarkMapView& m, const double* __restrict__ r, const Pose2& s) {
-  const Detection q = load_detection(r);
-  if (q.count == 0) return m.random_prob;  // :126-128
+// The pieces of detection_weight (landmark_sensor_model.hpp:109-153) that the lane-per-particle and the wave-per-particle kernel share:
+// the same expressions in both, so the same bits (-ffp-contract=off).
+// robot_pose_in_world * detection (:119)
+__device__ __forceinline__ Vec3 detection_in_world(const Pose2& s, const Vec3& d) {
   const double rc = s.r.c, rs = s.r.s;
-  // robot_pose_in_world * detection (:119)
-  const Vec3 p{(rc * q.d.x - rs * q.d.y) + s.x, (rs * q.d.x + rc * q.d.y) + s.y, q.d.z};
-  // find_nearest_landmark (landmark_map.hpp:81-110)
-  Vec3 match = load_landmark(m.landmarks, q.first);
-  double best = squared_norm(Vec3{match.x - p.x, match.y - p.y, match.z - p.z});
-  for (uint32_t t = 1; t < q.count; ++t) {
-    const Vec3 l = load_landmark(m.landmarks, q.first + t);
-    const double d2 = squared_norm(Vec3{l.x - p.x, l.y - p.y, l.z - p.z});
-    if (d2 < best) {
-      best = d2;
-      match = l;
-    }
-  }
+  return Vec3{(rc * d.x - rs * d.y) + s.x, (rs * d.x + rc * d.y) + s.y, d.z};
+}
+// what find_nearest_landmark minimises (landmark_map.hpp:81-110)
+__device__ __forceinline__ double squared_distance(const Vec3& l, const Vec3& p) { return squared_norm(Vec3{l.x - p.x, l.y - p.y, l.z - p.z}); }
+// the term of a detection against the landmark `match` that the search picked (:133-153)
+__device__ __forceinline__ double landmark_match_term(const LandmarkMapView& m, const Detection& q, const Pose2& s, const Vec3& match) {
+  const double rc = s.r.c, rs = s.r.s;
   // the landmark in the robot frame, R^T (l - t) (:133)
   const double vx = match.x - s.x, vy = match.y - s.y;
   const Vec3 in_robot{rc * vx + rs * vy, rc * vy - rs * vx, match.z};
@@ -83,6 +78,25 @@ __device__ __forceinline__ double landmark_term(const LandmarkMapView& m, const 
   const double bearing_error = aperture(normalized(in_robot), q.unit);  // :139-141
   const double range_error = q.range - landmark_range;
   return exp(-range_error * range_error / m.den_range) * exp(-bearing_error * bearing_error / m.den_bearing) + m.random_prob;
+}
+
+// detection_weight of landmark_sensor_model.hpp:109-153 for the pose s
+__device__ __forceinline__ double landmark_term(const LandmarkMapView& m, const double* __restrict__ r, const Pose2& s) {
+  const Detection q = load_detection(r);
+  if (q.count == 0) return m.random_prob;  // :126-128
+  const Vec3 p = detection_in_world(s, q.d);
+  // find_nearest_landmark (landmark_map.hpp:81-110)
+  Vec3 match = load_landmark(m.landmarks, q.first);
+  double best = squared_distance(match, p);
+  for (uint32_t t = 1; t < q.count; ++t) {
+    const Vec3 l = load_landmark(m.landmarks, q.first + t);
+    const double d2 = squared_distance(l, p);
+    if (d2 < best) {
+      best = d2;
+      match = l;
+    }
+  }
+  return landmark_match_term(m, q, s, match);
 }
 
 __global__ __launch_bounds__(kBlock) void k_reweight_landmarks(Particles p, uint64_t n, LandmarkMapView m, const double* __restrict__ det,
@@ -116,6 +130,25 @@ __device__ __forceinline__ Vec3 bearing_of(const SensorFrame& f, const Vec3& l) 
                          f.r[2] * v.x + (f.r[5] * v.y + f.r[8] * v.z)});
 }
 
+// sensor_pose_in_world for the pose s (:107)
+__device__ __forceinline__ SensorFrame sensor_frame(const LandmarkMapView& m, const Pose2& s) {
+  const double rc = s.r.c, rs = s.r.s;
+  SensorFrame f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    f.r[c] = rc * m.Rs[c] - rs * m.Rs[3 + c];
+    f.r[3 + c] = rs * m.Rs[c] + rc * m.Rs[3 + c];
+    f.r[6 + c] = m.Rs[6 + c];
+  }
+  f.t = Vec3{(rc * m.ts[0] - rs * m.ts[1]) + s.x, (rs * m.ts[0] + rc * m.ts[1]) + s.y, m.ts[2]};
+  return f;
+}
+// the term of a detection (its normalized() vector `unit`) against the bearing `b` of the landmark that the search picked (:120-130)
+__device__ __forceinline__ double bearing_match_term(const LandmarkMapView& m, const Vec3& unit, const Vec3& b) {
+  const double e = aperture(unit, b);
+  return exp(-e * e / m.den_bearing);
+}
+
 // One wave per workgroup, a lane per particle.  The detections arrive sorted by category; for each run of one category the landmarks of
 // that category are visited ONCE: the landmark's bearing is normalised once and every detection of the run is compared against it (the
 // reference normalises it again for every detection).  The state of a detection's search - the best dot product so far and the place
@@ -129,16 +162,7 @@ __global__ __launch_bounds__(kWave) void k_reweight_bearings(Particles p, uint64
   const uint32_t lane = threadIdx.x;
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWave + lane;
   if (i >= n) return;
-  const Pose2 s = load_pose(p, i);
-  const double rc = s.r.c, rs = s.r.s;
-  SensorFrame f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    f.r[c] = rc * m.Rs[c] - rs * m.Rs[3 + c];
-    f.r[3 + c] = rs * m.Rs[c] + rc * m.Rs[3 + c];
-    f.r[6 + c] = m.Rs[6 + c];
-  }
-  f.t = Vec3{(rc * m.ts[0] - rs * m.ts[1]) + s.x, (rs * m.ts[0] + rc * m.ts[1]) + s.y, m.ts[2]};
+  const SensorFrame f = sensor_frame(m, load_pose(p, i));
   for (uint32_t j = 0; j < k;) {
     const Detection head = load_detection(det + j * kLandmarkRecord);
     if (head.count == 0) {  // no landmark of that category: 0.0 (bearing_sensor_model.hpp:115-117)
@@ -164,8 +188,7 @@ __global__ __launch_bounds__(kWave) void k_reweight_bearings(Particles p, uint64
       const Detection d = load_detection(det + q * kLandmarkRecord);
       const uint32_t at = d.place * kWave + lane;
       const Vec3 b = bearing_of(f, load_landmark(m.landmarks, head.first + s_pick[at]));  // (the same bits as in the search)
-      const double e = aperture(d.unit, b);  // :120-130
-      s_value[at] = exp(-e * e / m.den_bearing);
+      s_value[at] = bearing_match_term(m, d.unit, b);
     }
     j = end;
   }
@@ -180,6 +203,151 @@ __global__ __launch_bounds__(kWave) void k_reweight_bearings(Particles p, uint64
   p.w[i] *= acc;
 }
 
+// ---- a wave per particle (small sets: mcl_set_landmark_small_cycle) -------------------------------------------------------------------
+// At 2000 particles a lane per particle is 32 waves on 256 CUs, each lane walking k detections x L landmarks in a row.  Here a wave
+// takes one particle (kBlock threads, four particles per workgroup, as k_reweight_ndt_wave) and its lanes take the detections: with P
+// the smallest power of two >= k and g = 64 / P, record j owns the aligned lanes [j g, (j + 1) g), and lane r of that group scans the
+// landmarks first + r, first + r + g, ... of the record's category in ascending order, replacing its candidate on a strictly better
+// value - the lane kernel's rule.  The group then reduces in log2 g xor steps, which stay inside the aligned group: the better value
+// wins, an equal value goes to the smaller landmark index, a lane that scanned nothing (r >= count) carries the index 0xFFFFFFFF
+// and the worst value, so it loses to every lane that scanned.  (value, index) in this order is a total order on finite inputs, so
+// the result is its minimum over the category whatever the shape of the reduction: the landmark the sequential scan picks, the first of
+// equal ones.  The group's first lane forms the term from the pick with the lane kernel's own functions; the product is then chained
+// through v_readlane in the lane kernel's order and association, every lane carrying the same running product.
+struct GroupShape {
+  uint32_t shift;  // log2 g
+  uint32_t g;      // lanes of a record's group
+};
+__device__ __forceinline__ GroupShape group_shape(uint32_t k) {  // 1 <= k <= kWave
+  uint32_t shift = 6;
+  while ((static_cast<uint32_t>(kWave) >> shift) < k) --shift;  // the largest g = 2^shift with 64 / g >= k
+  return GroupShape{shift, 1u << shift};
+}
+constexpr uint32_t kNoPick = 0xFFFFFFFFu;
+// kLarger = false: the smaller value is the better one (squared distances); true: the larger one (dot products)
+template <bool kLarger>
+__device__ __forceinline__ bool pick_beats(double v, uint32_t at, double other_v, uint32_t other_at) {
+  if (other_at == kNoPick) return true;   // (the other lane scanned nothing; two such lanes are alike)
+  if (at == kNoPick) return false;
+  if (v == other_v) return at < other_at;
+  return kLarger ? v > other_v : v < other_v;
+}
+template <bool kLarger>
+__device__ __forceinline__ void group_reduce(uint32_t g, double* v, uint32_t* at) {  // every lane of the wave takes part
+  for (uint32_t step = g >> 1; step >= 1; step >>= 1) {
+    const double other_v = __shfl_xor(*v, static_cast<int>(step));
+    const uint32_t other_at = __shfl_xor(*at, static_cast<int>(step));
+    if (!pick_beats<kLarger>(*v, *at, other_v, other_at)) {
+      *v = other_v;
+      *at = other_at;
+    }
+  }
+}
+// terms 0 .. k-1 are held by the lanes 0, stride, 2 stride, ...: the product as libstdc++ multiplies it, blocks of four, the rest one by one
+__device__ __forceinline__ double chained_product(double term, uint32_t k, uint32_t shift) {
+  double acc = 1.0;
+  uint32_t j = 0;
+  for (; j + 4 <= k; j += 4) {
+    const double t0 = readlane_f64(term, static_cast<int>((j + 0) << shift)), t1 = readlane_f64(term, static_cast<int>((j + 1) << shift));
+    const double t2 = readlane_f64(term, static_cast<int>((j + 2) << shift)), t3 = readlane_f64(term, static_cast<int>((j + 3) << shift));
+    acc = acc * ((t0 * t1) * (t2 * t3));
+  }
+  for (; j < k; ++j) acc = acc * readlane_f64(term, static_cast<int>(j << shift));
+  return acc;
+}
+
+// (the bodies: block `block` of ONE set - blockIdx.x in the lone kernels, a member's local block in k_batch_reweight_landmarks)
+__device__ __forceinline__ void reweight_landmarks_wave_block(uint32_t block, const Particles& p, uint64_t n, const LandmarkMapView& m,
+                                                              const double* __restrict__ det, uint32_t k) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n || k == 0 || k > static_cast<uint32_t>(kWave)) return;  // (the whole wave)
+  const Pose2 s = load_pose(p, i);
+  const GroupShape shape = group_shape(k);
+  const uint32_t j = lane >> shape.shift, r = lane & (shape.g - 1);
+  const bool mine = j < k;
+  Detection q{};
+  double best = 0.0;
+  uint32_t at = kNoPick;
+  if (mine) {
+    q = load_detection(det + j * kLandmarkRecord);
+    const Vec3 w = detection_in_world(s, q.d);
+    for (uint32_t t = r; t < q.count; t += shape.g) {
+      const double d2 = squared_distance(load_landmark(m.landmarks, q.first + t), w);
+      if (t == r || d2 < best) {
+        best = d2;
+        at = t;
+      }
+    }
+  }
+  group_reduce<false>(shape.g, &best, &at);
+  double term = 1.0;
+  if (mine && r == 0) term = q.count == 0 ? m.random_prob : landmark_match_term(m, q, s, load_landmark(m.landmarks, q.first + at));
+  const double acc = chained_product(term, k, shape.shift);  // record order
+  if (lane == 0) p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
+}
+
+// The bearing model.  A record's term goes to the slot of its `place` in the wave's row of workgroup memory (the records arrive sorted
+// by category, the product follows the caller's order); lane t then takes slot t back and the chain runs over the lanes 0 .. k-1.
+__device__ __forceinline__ void reweight_bearings_wave_block(uint32_t block, const Particles& p, uint64_t n, const LandmarkMapView& m,
+                                                             const double* __restrict__ det, uint32_t k, double* s_terms /* [kBlock] */) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n || k == 0 || k > static_cast<uint32_t>(kWave)) return;  // (the whole wave)
+  const SensorFrame f = sensor_frame(m, load_pose(p, i));
+  const GroupShape shape = group_shape(k);
+  const uint32_t j = lane >> shape.shift, r = lane & (shape.g - 1);
+  const bool mine = j < k;
+  Detection q{};
+  double best = 0.0;
+  uint32_t at = kNoPick;
+  if (mine) {
+    q = load_detection(det + j * kLandmarkRecord);
+    // find_closest_bearing_landmark (landmark_map.hpp:117-161): the largest dot product with the detection as given
+    for (uint32_t t = r; t < q.count; t += shape.g) {
+      const double v = dot(bearing_of(f, load_landmark(m.landmarks, q.first + t)), q.d);
+      if (t == r || v > best) {
+        best = v;
+        at = t;
+      }
+    }
+  }
+  group_reduce<true>(shape.g, &best, &at);
+  double* row = s_terms + (threadIdx.x & ~63u);
+  if (mine && r == 0)  // no landmark of that category: 0.0 (bearing_sensor_model.hpp:115-117); q.place < k: the places are a permutation
+    row[q.place & 63u] = q.count == 0 ? 0.0 : bearing_match_term(m, q.unit, bearing_of(f, load_landmark(m.landmarks, q.first + at)));
+  // (one wave wrote, the same wave reads: its LDS operations complete in order)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const double term = lane < k ? row[lane] : 1.0;
+  const double acc = chained_product(term, k, 0);  // the caller's order
+  if (lane == 0) p.w[i] *= acc;
+}
+
+__global__ __launch_bounds__(kBlock) void k_reweight_landmarks_wave(Particles p, uint64_t n, LandmarkMapView m, const double* __restrict__ det,
+                                                                    uint32_t k) {
+  reweight_landmarks_wave_block(blockIdx.x, p, n, m, det, k);
+}
+__global__ __launch_bounds__(kBlock) void k_reweight_bearings_wave(Particles p, uint64_t n, LandmarkMapView m, const double* __restrict__ det,
+                                                                   uint32_t k) {
+  __shared__ double s_terms[kBlock];
+  reweight_bearings_wave_block(blockIdx.x, p, n, m, det, k, s_terms);
+}
+
+// The same over a fleet's landmark and bearing members (mcl_landmark_batch_update; the pattern is k_batch_reweight_ndt): a workgroup finds
+// its member over the first_landmark_block prefix - a member without a block (no particle, no detection, another family's member) is
+// never found - and runs the body of the member's kind, a workgroup-uniform branch, with its LOCAL block number on the member's own map
+// and staged records.
+static_assert(kBatchLandmarkThreads == kBlock && kBatchLandmarkBlock == kBlock / kWave, "batch_host.h restates the wave-per-particle landmark kernels' launch geometry");
+__global__ __launch_bounds__(kBlock) void k_batch_reweight_landmarks(const BatchItem* __restrict__ items, uint32_t count) {
+  __shared__ double s_terms[kBlock];
+  const BatchItem& it = items[batch_member_of(count, blockIdx.x, [items](uint32_t m) { return items[m].first_landmark_block; })];
+  const uint32_t block = blockIdx.x - it.first_landmark_block;
+  if (it.landmark_bearing) reweight_bearings_wave_block(block, it.p, it.n, it.landmark, it.scan_dst, it.landmark_k, s_terms);
+  else reweight_landmarks_wave_block(block, it.p, it.n, it.landmark, it.scan_dst, it.landmark_k);
+}
+
 }  // namespace
 
 void launch_reweight_landmarks(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k) {
@@ -191,6 +359,20 @@ void launch_reweight_bearings(hipStream_t st, Particles p, uint64_t n, const Lan
   if (n == 0 || k == 0) return;
   const size_t lds = static_cast<size_t>(k) * kWave * (sizeof(double) + sizeof(uint32_t));  // <= 48 KB at kLandmarkMaxDetections
   hipLaunchKernelGGL(k_reweight_bearings, dim3(static_cast<unsigned>((n + kWave - 1) / kWave)), dim3(kWave), lds, st, p, n, m, detections, k);
+}
+
+void launch_reweight_landmarks_wave(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k) {
+  if (n == 0 || k == 0) return;
+  hipLaunchKernelGGL(k_reweight_landmarks_wave, dim3(batch_landmark_blocks(n, k)), dim3(kBlock), 0, st, p, n, m, detections, k);
+}
+void launch_reweight_bearings_wave(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k) {
+  if (n == 0 || k == 0) return;
+  hipLaunchKernelGGL(k_reweight_bearings_wave, dim3(batch_landmark_blocks(n, k)), dim3(kBlock), 0, st, p, n, m, detections, k);
+}
+
+void launch_batch_reweight_landmarks(hipStream_t st, const BatchItem* d_items, uint32_t members, uint32_t blocks) {
+  if (blocks == 0) return;
+  hipLaunchKernelGGL(k_batch_reweight_landmarks, dim3(blocks), dim3(kBlock), 0, st, d_items, members);
 }
 
 }  // namespace mcl

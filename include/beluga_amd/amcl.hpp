@@ -708,6 +708,15 @@ class Amcl {
     check(mcl_update_bearings(ctx_, control_action.data(), xyz.data(), categories.data(), categories.size(), &est, &info));
     return finish_update(est, info);
   }
+  /// Extension (the landmark and bearing constructor forms only; throws on another sensor model): the small cycle of a landmark or
+  /// bearing filter, mcl_set_landmark_small_cycle.  Sets of up to 4096 particles take a wave-per-particle reweight (bit for bit the
+  /// lane-per-particle kernels' weights) and the one-launch tail with one host synchronisation.  Off by default.
+  void set_landmark_small_cycle(bool on) { check(mcl_set_landmark_small_cycle(ctx_, on ? 1 : 0)); }
+  [[nodiscard]] bool landmark_small_cycle() const {
+    std::int32_t on = 0;
+    check(mcl_get_landmark_small_cycle(ctx_, &on));
+    return on != 0;
+  }
   /// Update the NDT map used for localization (amcl_core.hpp:150 on the NDT filter).
   void update_map(const NDTMap2d& map) {
     if (ndt_params_.neighbors_kernel.empty() || ndt_params_.neighbors_kernel.size() > MCL_NDT_MAX_OFFSETS) throw std::invalid_argument("beluga_amd::Amcl: the neighbours kernel takes 1 .. 32 offsets");
@@ -1065,6 +1074,18 @@ struct AmclBatchSpec {
   std::vector<std::pair<std::string, std::int64_t>> options{};
 };
 
+/// One member of an AmclBatch of landmark or bearing filters: the arguments of Amcl's constructor over a LandmarkMap.  `small_cycle`:
+/// set_landmark_small_cycle(true) on the member, so that it shares the fleet's launches (at most 4096 particles).
+struct AmclLandmarkBatchSpec {
+  LandmarkMap map;
+  MotionModelParam motion;
+  std::variant<LandmarkModelParam, BearingModelParam> sensor;
+  AmclParams params{};
+  std::uint64_t seed{0};
+  bool small_cycle{false};
+  std::vector<std::pair<std::string, std::int64_t>> options{};
+};
+
 /// A fleet of small filters that share their launches (mcl_batch_*): one update call, three kernel launches for all members whose cycle
 /// is the small one (likelihood-field models, at most 4096 particles), one synchronisation; every other member runs its ordinary cycle
 /// inside the same call.  member(i) is a beluga_amd::Amcl bound to the batch's i-th context: every method of Amcl works on it between
@@ -1090,6 +1111,38 @@ class AmclBatch {
         members_.push_back(Amcl(Amcl::Adopted{}, ctx, specs[i].params));
         for (const auto& [name, value] : specs[i].options) members_.back().check(mcl_set_option(ctx, name.c_str(), value));
         if (specs[i].map.cells) members_.back().update_map(specs[i].map);
+      }
+    } catch (...) {
+      release();
+      throw;
+    }
+    estimates_.resize(specs.size());
+    infos_.resize(specs.size());
+    statuses_.assign(specs.size(), MCL_OK);
+  }
+  /// A fleet of landmark and bearing filters (mcl_landmark_batch_update): update() over one vector of detections per member.
+  explicit AmclBatch(const std::vector<AmclLandmarkBatchSpec>& specs, int device = 0) {
+    std::vector<mcl_config> cfgs;
+    for (const AmclLandmarkBatchSpec& s : specs) {
+      mcl_config cfg = Amcl::base_config(s.motion, s.params, s.seed, device, Shard{});
+      cfg.sensor_kind = std::holds_alternative<BearingModelParam>(s.sensor) ? MCL_SENSOR_BEARING : MCL_SENSOR_LANDMARK;
+      cfgs.push_back(cfg);
+    }
+    const mcl_status st = mcl_batch_create(cfgs.data(), static_cast<std::uint32_t>(cfgs.size()), &batch_);
+    if (st != MCL_OK) throw std::runtime_error(std::string("beluga_amd::AmclBatch: ") + mcl_batch_last_error(nullptr));
+    try {
+      members_.reserve(specs.size());
+      for (std::size_t i = 0; i < specs.size(); ++i) {
+        mcl_ctx* ctx = nullptr;
+        check(mcl_batch_member(batch_, static_cast<std::uint32_t>(i), &ctx));
+        members_.push_back(Amcl(Amcl::Adopted{}, ctx, specs[i].params));
+        Amcl& m = members_.back();
+        m.landmark_kind_ = cfgs[i].sensor_kind;
+        if (const auto* bearing = std::get_if<BearingModelParam>(&specs[i].sensor)) m.bearing_params_ = *bearing;
+        else m.landmark_params_ = std::get<LandmarkModelParam>(specs[i].sensor);
+        for (const auto& [name, value] : specs[i].options) m.check(mcl_set_option(ctx, name.c_str(), value));
+        if (specs[i].small_cycle) m.set_landmark_small_cycle(true);
+        m.update_map(specs[i].map);
       }
     } catch (...) {
       release();
@@ -1134,6 +1187,20 @@ class AmclBatch {
     return out;
   }
 
+  /// Amcl::update on every member of a fleet of landmark filters / of bearing filters (mcl_landmark_batch_update): control_actions[i] and
+  /// detections[i] are member i's; for every member, bit for bit, what member(i).update(control_actions[i], detections[i]) does.  Members
+  /// with set_landmark_small_cycle(true) share three launches; every other one runs its own cycle inside the call.  Throws as above.
+  auto update(const std::vector<SE2d>& control_actions, const std::vector<std::vector<LandmarkPositionDetection>>& detections)
+      -> std::vector<std::optional<estimation_type>> {
+    return update_detections(control_actions, detections,
+                             [](const LandmarkPositionDetection& d) -> const std::array<double, 3>& { return d.detection_position_in_robot; });
+  }
+  auto update(const std::vector<SE2d>& control_actions, const std::vector<std::vector<LandmarkBearingDetection>>& detections)
+      -> std::vector<std::optional<estimation_type>> {
+    return update_detections(control_actions, detections,
+                             [](const LandmarkBearingDetection& d) -> const std::array<double, 3>& { return d.detection_bearing_in_sensor; });
+  }
+
   /// Every member, or member `index`, reads the shared map from now on (Amcl::use_map): a fleet on one building's map holds it once.
   void use_map(const SharedMap& map) {
     for (Amcl& m : members_) m.use_map(map);
@@ -1147,8 +1214,8 @@ class AmclBatch {
   void set_option(const std::string& name, std::int64_t value) {
     for (Amcl& m : members_) m.check(mcl_set_option(m.ctx_, name.c_str(), value));
   }
-  /// cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns, beam_launches, members_beam_fused
-  /// (mcl_batch_get_counter).
+  /// cycles, kernel_launches, members_fused, members_alone, cluster_launches, members_cluster_fused, cluster_host_ns, beam_launches, members_beam_fused,
+  /// landmark_launches, members_landmark_fused (mcl_batch_get_counter).
   [[nodiscard]] std::uint64_t counter(const std::string& name) const {
     std::uint64_t value = 0;
     check(mcl_batch_get_counter(batch_, name.c_str(), &value));
@@ -1160,6 +1227,31 @@ class AmclBatch {
   void check(mcl_status st) const {
     if (st != MCL_OK) throw std::runtime_error(std::string("beluga_amd::AmclBatch: ") + mcl_batch_last_error(batch_));
   }
+  template <class Detection, class Get>
+  auto update_detections(const std::vector<SE2d>& control_actions, const std::vector<std::vector<Detection>>& detections, Get get)
+      -> std::vector<std::optional<estimation_type>> {
+    static_assert(sizeof(SE2d) == 4 * sizeof(double), "control actions must be packed (cos, sin, x, y) records");
+    if (control_actions.size() != size() || detections.size() != size())
+      throw std::invalid_argument("beluga_amd::AmclBatch: one control action and one vector of detections per member");
+    offsets_.assign(size() + 1, 0);
+    points_.clear();
+    categories_.clear();
+    for (std::size_t i = 0; i < size(); ++i) {
+      for (const Detection& d : detections[i]) {
+        const std::array<double, 3>& v = get(d);
+        points_.insert(points_.end(), v.begin(), v.end());
+        categories_.push_back(d.category);
+      }
+      offsets_[i + 1] = categories_.size();
+    }
+    const mcl_status st = mcl_landmark_batch_update(batch_, size() ? control_actions.front().data() : nullptr, points_.data(), categories_.data(),
+                                                    offsets_.data(), estimates_.data(), infos_.data(), statuses_.data());
+    std::vector<std::optional<estimation_type>> out(size());
+    for (std::size_t i = 0; i < size(); ++i)
+      if (statuses_[i] == MCL_OK) out[i] = members_[i].finish_update(estimates_[i], infos_[i]);
+    check(st);
+    return out;
+  }
   void release() {
     for (Amcl& m : members_) m.ctx_ = nullptr;  // (the batch destroys the contexts)
     members_.clear();
@@ -1169,6 +1261,7 @@ class AmclBatch {
   mcl_batch* batch_{nullptr};
   std::vector<Amcl> members_;
   std::vector<double> points_;
+  std::vector<std::uint32_t> categories_;
   std::vector<std::uint64_t> offsets_;
   std::vector<mcl_estimate> estimates_;
   std::vector<mcl_update_info> infos_;

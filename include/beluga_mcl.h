@@ -354,6 +354,27 @@ mcl_status mcl_update_landmarks(mcl_ctx* ctx, const double control_pose[4], cons
                                 uint64_t n, mcl_estimate* estimate, mcl_update_info* info);
 mcl_status mcl_update_bearings(mcl_ctx* ctx, const double control_pose[4], const double* bearings_xyz, const uint32_t* categories,
                                uint64_t n, mcl_estimate* estimate, mcl_update_info* info);
+
+/* The small cycle of a landmark or bearing context, off by default.  on = 1: a cycle whose set and min(max_particles, capacity) are both
+ * 1 .. 4096, with the option small_fused on and stage profiling off, runs three launches and ONE host synchronisation, as a
+ * likelihood-field filter of that size does - the propagation (it pulls the staged detection records), a reweight with a wave per
+ * particle (no launch where there is no detection), and the one-launch tail (normalisation, policies, resampling with the random states
+ * drawn from the map's boundaries, estimate sums).  Nothing is handed back to the host.  The wave-per-particle kernels spread the
+ * detections over the lanes: with P the smallest power of two >= k and g = 64 / P, detection j owns lanes [j g, (j + 1) g), lane r of
+ * them scans the landmarks r, r + g, ... of the detection's category in ascending order (replacing on a strictly nearer landmark, or a
+ * strictly larger dot product for the bearing model), and the group reduces with ties going to the smaller landmark index: the landmark
+ * picked is the sequential scan's, the first of equal ones, and every weight is bit for bit that of the lane-per-particle kernels.  The
+ * recovery filters, the every_n counter, the step number and force_update end up where the ordinary cycle leaves them; results agree
+ * with the ordinary cycle's within the rounding of the tail's sums (as the likelihood-field small cycle's do).  The counter
+ * small_tail_launches advances as on a likelihood-field context, landmark_wave_launches with every wave-per-particle reweight.
+ * mcl_reweight_landmarks and mcl_reweight_bearings take the wave-per-particle kernels for sets of up to 4096 particles, and so does
+ * the reweight of an update that is NOT the small cycle while the switch is on (small_fused off, stage profiling on, or
+ * min(max_particles, capacity) above 4096 with a set of at most 4096): the same bits from the other kernel, inside the ordinary cycle;
+ * landmark_wave_launches counts those launches too.  on = 0:
+ * everything as without the call.  MCL_ERR_UNSUPPORTED on a context of another sensor model, MCL_ERR_INVALID_ARGUMENT for a value other
+ * than 0 or 1.  In a batch (mcl_landmark_batch_update) a member with the switch on rides the fleet's shared launches: see there. */
+mcl_status mcl_set_landmark_small_cycle(mcl_ctx* ctx, int32_t on);
+mcl_status mcl_get_landmark_small_cycle(mcl_ctx* ctx, int32_t* on);
 /* Stage-level reweight of the two models (what the two updates compose with the other stages below). */
 mcl_status mcl_reweight_landmarks(mcl_ctx* ctx, const double* positions_xyz, const uint32_t* categories, uint64_t n);
 mcl_status mcl_reweight_bearings(mcl_ctx* ctx, const double* bearings_xyz, const uint32_t* categories, uint64_t n);
@@ -513,6 +534,23 @@ mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const
                             mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses);
 mcl_status mcl_batch_get_counter(mcl_batch* batch, const char* name, uint64_t* value);
 mcl_status mcl_ndt_batch_counts(mcl_batch* batch, uint64_t* launches, uint64_t* members);
+/* The fleet's update for landmark and bearing members: mcl_batch_update's contract with detections in the place of scans.  Member i
+ * takes the detections [detection_offsets[i], detection_offsets[i + 1]) of vectors_xyz (3 doubles each) and categories: positions in
+ * the robot frame for a landmark member, bearings in the sensor frame for a bearing member.  Every member's effect and outputs are bit
+ * for bit those of its own mcl_update_landmarks / mcl_update_bearings, and statuses[i] is that call's status: more than
+ * MCL_LANDMARK_MAX_DETECTIONS detections or a value that is not finite is the member's own MCL_ERR_INVALID_ARGUMENT, its state untouched,
+ * the others proceed.  A member of any other sensor model gets MCL_ERR_UNSUPPORTED and is untouched (a fleet of scan and detection
+ * members takes two calls; mcl_batch_update keeps refusing landmark and bearing members).  Offsets that decrease, or a null table, are
+ * refused with no member moved.  A member shares the launches where its switch mcl_set_landmark_small_cycle is on and its own update
+ * would run the small cycle: not sharded, option small_fused on, the set and min(max_particles, capacity) both 1 .. 4096, stage
+ * profiling off.  Those members take k_batch_propagate, ONE shared reweight launch for both kinds (a workgroup finds its member and
+ * branches on the member's kind; a member without a particle or a detection has no block in it) and k_batch_small_tail: three launches
+ * per cycle for the fleet, one synchronisation.  Every other landmark or bearing member runs its own cycle inside the call.  The
+ * cluster-based estimate of fused members goes through the two shared cluster launches as in mcl_batch_update.  Counters
+ * (mcl_batch_get_counter): landmark_launches = shared landmark reweight kernels enqueued, members_landmark_fused = members that updated
+ * through the shared launches (running totals; kernel_launches and members_fused count them as well). */
+mcl_status mcl_landmark_batch_update(mcl_batch* batch, const double* control_poses, const double* vectors_xyz, const uint32_t* categories,
+                                     const uint64_t* detection_offsets, mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses);
 const char* mcl_batch_last_error(const mcl_batch* batch); /* batch may be NULL: error of the last failed mcl_batch_create */
 
 /* ---- Shared maps: one uploaded map, many filters ------------------------------------------------------------------------------
