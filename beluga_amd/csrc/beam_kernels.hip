@@ -424,7 +424,7 @@ __device__ __forceinline__ void walk_blocks(const BlockMaps& maps, int& lx, int&
   // 2. whole block columns.  8 * dminor = trips8 * dmajor + rest8 (dminor <= dmajor: trips8 <= 8).
   int trips8 = 0;
   if (dmajor > 0) {
-    const int x = 8 * dminor;  // < 2^24: one float multiply and a +-1 correction
+    const int x = 8 * dminor;  // <= 8 dmajor < 2^31 (kBeamMaxReachCells): the float quotient is at most 8, off by one at most, corrected by the remainder
     int q = static_cast<int>(static_cast<float>(x) * inv_dmajor);
     const int rem = x - q * dmajor;
     q += (rem >= dmajor ? 1 : 0) - (rem < 0 ? 1 : 0);

@@ -88,6 +88,8 @@ struct mcl_ctx {
   DeviceBuffer<double> d_beam_table;   // beam model: 4 doubles per squared cell distance of a hit (launch_beam_table), built by mcl_set_map
   uint32_t beam_table_count{0};
   bool beam_table_ready{false};        // d_beam_table holds the table of the current map (built lazily: do_reweight)
+  uint64_t beam_wave_launches{0};      // lone launches of k_reweight_beam (a wave per particle) and of k_reweight_beam_sorted (ordered lanes):
+  uint64_t beam_ordered_launches{0};   // mcl_get_counter; a fleet's shared k_batch_reweight_beam is the batch's beam_launches, not these
   HostBuffer<double> h_points;  // pinned, mapped
   double scan_extent{0.0};     // max |x| + |y| of the staged scan points
   uint64_t scan_no_cell{0};    // points of the scan taken out where it was staged: NaN or infinite, without a cell for any pose (FieldView::acc0)
@@ -940,6 +942,10 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
   }
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no map set");
   MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
+  // the beam kernels' walks keep 16 * span in an int (walk_blocks: 8 * dminor, q * dmajor): lines of 2^27 cells and more are refused
+  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM)
+    MCL_REQUIRE(ctx, ctx->cfg.beam.beam_max_range / ctx->map->resolution < kBeamMaxReachCells,
+                "beam_max_range / resolution must stay below 2^27 - 2 cells for the beam model");
   if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM && !(ctx->n < (1ull << 32) && ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles)))
     // the beam model's small-set kernel (a wave per particle) stages the scan in 64 KB of dynamic LDS
     MCL_REQUIRE(ctx, B * sizeof(double2) <= 64 * 1024, "scan too large for the beam model's small-set kernel (4096 points)");
@@ -1093,6 +1099,7 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
                            ctx->d_points.ptr, static_cast<uint32_t>(B), ctx->d_kld_scalars.ptr + kKldBeamSteps, ordered ? &sort : nullptr,
                            ctx->map->d_nonfree_bits.ptr, ctx->d_beam_points.ptr, use_table ? ctx->d_beam_table.ptr : nullptr,
                            use_table ? ctx->beam_table_count : 0u, ctx->tuning.beam_free_ahead != 0, ctx->tuning.beam_sectors != 0);
+      if (ctx->n != 0 && B != 0) (ordered ? ctx->beam_ordered_launches : ctx->beam_wave_launches) += 1;  // (launch_reweight_beam's own test)
     }
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   }
@@ -3969,6 +3976,8 @@ constexpr Counter kCounters[] = {
     {"lf_far_beams_launches", &mcl_ctx::lf_far_beams_launches},
     {"small_tail_launches", &mcl_ctx::small_tail_launches},
     {"landmark_wave_launches", &mcl_ctx::landmark_wave_launches},
+    {"beam_wave_launches", &mcl_ctx::beam_wave_launches},
+    {"beam_ordered_launches", &mcl_ctx::beam_ordered_launches},
     {"estimate_repivots", &mcl_ctx::estimate_repivots},
     {"noise_ahead_used", &mcl_ctx::noise_ahead_used},
     {"order_ahead_used", &mcl_ctx::order_ahead_used},

@@ -372,6 +372,9 @@ void launch_reweight_beam(hipStream_t st, Particles p, uint64_t n, GridView g, B
 // The beam model's terms that depend on the expected range alone, tabulated over the squared cell distance of the hit (beam_kernels.hip
 // BeamTable): entries = beam_table_entries(...) (0: the range spans too many cells for a table), 4 doubles each.
 constexpr double kBeamTableMaxCells = 2046.0;
+// The longest line the beam kernels walk, in cells between the source and the far end (beam_max_range / resolution, + a cell for the
+// roundings): below 2^27, so that 16 * span - walk_blocks' 8 * dminor and q * dmajor - stays an int.  mcl_reweight / mcl_update refuse more.
+constexpr double kBeamMaxReachCells = 134217726.0;  // 2^27 - 2
 uint32_t beam_table_entries(double beam_max_range, double resolution);
 void launch_beam_table(hipStream_t st, BeamModel m, double resolution, uint32_t entries, double* table);
 // The occupancy the ray walks read, in one buffer of nonfree_words(W, H) words: one bit per cell (1 = not free), ceil(W/32)

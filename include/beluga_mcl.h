@@ -104,6 +104,8 @@ typedef struct mcl_lf_params {
 } mcl_lf_params;
 
 /* beluga::BeamModelParam (sensor/beam_model.hpp:43-58). */
+/* beam_max_range / (the map's resolution) must stay below 2^27 - 2 cells (6 700 km at 5 cm): the ray walks keep 16 x the line's span in
+ * an int.  mcl_reweight, mcl_update and a batch member's update return MCL_ERR_INVALID_ARGUMENT otherwise, the set untouched. */
 typedef struct mcl_beam_params {
   double z_hit, z_short, z_max, z_rand, sigma_hit, lambda_short, beam_max_range;
 } mcl_beam_params;
@@ -837,6 +839,9 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *   has read through a patch, running totals over a sample of the workgroups; lf_queue_launches = launches of the
  *   LDS-patch kernel with the queue of blocks; field_built_on_device, field_build_us = the last mcl_set_map;
  *   small_tail_launches = cycles that ran their tail in the one launch of option small_fused;
+ *   beam_wave_launches / beam_ordered_launches = a beam context's own reweight launches of the wave-per-particle kernel / of the
+ *   ordered-lanes kernel (beam_sort_min_particles decides; no launch for an empty set or scan; a fleet's shared launch counts in the
+ *   batch's beam_launches instead);
  *   cluster_cells = occupied cells of the last cluster_based_estimate; comm_ranks_seen (ncclCommCount of the library's communicator, 0
  *   without one), comm_collectives, comm_bytes_out (running totals of this rank), comm_backend (0 = none, 1 = the caller's transport, 2 = RCCL inside the library). */
 mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value);
