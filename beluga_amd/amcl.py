@@ -353,14 +353,17 @@ class SharedMap:
 class Amcl:
     def __init__(self, grid: OccupancyGrid, motion, sensor, params: AmclParams = AmclParams(), *,
                  seed: int = 0, device: int = 0, shard_offset: int = 0, shard_capacity: int = 0, hip_stream: int = 0,
-                 options: Optional[dict] = None, ndt_small_cycle: bool = False, landmark_small_cycle: bool = False):
+                 options: Optional[dict] = None, ndt_small_cycle: bool = False, landmark_small_cycle: bool = False,
+                 ndt_map_layout: int = 0):
         """options: library switches applied before the map is installed (mcl_set_option), e.g. {"field_build": 1} to build
         the likelihood field with the device's exact distance transform instead of the reference's wavefront on the host.
         ndt_small_cycle (NDT sensor model only): set_ndt_small_cycle(True) once the context exists.
-        landmark_small_cycle (landmark and bearing sensor models only): set_landmark_small_cycle(True) likewise."""
+        landmark_small_cycle (landmark and bearing sensor models only): set_landmark_small_cycle(True) likewise.
+        ndt_map_layout (NDT sensor model only): set_ndt_map_layout(mode) before the first map is installed - 0 the dense index grid,
+        1 the hashed table where the grid does not fit, 2 the hashed table always."""
         cfg = self._configure(grid, motion, sensor, params, seed=seed, device=device, shard_offset=shard_offset,
                               shard_capacity=shard_capacity, hip_stream=hip_stream, ndt_small_cycle=ndt_small_cycle,
-                              landmark_small_cycle=landmark_small_cycle)
+                              landmark_small_cycle=landmark_small_cycle, ndt_map_layout=ndt_map_layout)
         ctx = capi._ctx()
         st = self._lib.mcl_create(C.byref(cfg), C.byref(ctx))
         if st != capi.MCL_OK:
@@ -370,12 +373,15 @@ class Amcl:
         self._attach(ctx, grid, options, owned=True)
 
     def _configure(self, grid, motion, sensor, params, *, seed=0, device=0, shard_offset=0, shard_capacity=0, hip_stream=0,
-                   ndt_small_cycle=False, landmark_small_cycle=False):
+                   ndt_small_cycle=False, landmark_small_cycle=False, ndt_map_layout=0):
         """The mcl_config of these constructor arguments (and what the object remembers of them)."""
         self._lib = capi.load()
         if ndt_small_cycle and not isinstance(sensor, NDTModelParam2d):
             raise ValueError("ndt_small_cycle needs the NDT sensor model (NDTModelParam2d)")
         self._ndt_small_cycle = bool(ndt_small_cycle)
+        if ndt_map_layout and not isinstance(sensor, NDTModelParam2d):
+            raise ValueError("ndt_map_layout needs the NDT sensor model (NDTModelParam2d)")
+        self._ndt_map_layout = int(ndt_map_layout)
         if landmark_small_cycle and not isinstance(sensor, (LandmarkModelParam, BearingModelParam)):
             raise ValueError("landmark_small_cycle needs the landmark or the bearing sensor model")
         self._landmark_small_cycle = bool(landmark_small_cycle)
@@ -451,6 +457,8 @@ class Amcl:
             self.set_ndt_small_cycle(True)
         if getattr(self, "_landmark_small_cycle", False):
             self.set_landmark_small_cycle(True)
+        if getattr(self, "_ndt_map_layout", 0):
+            self.set_ndt_map_layout(self._ndt_map_layout)
         if grid is not None:  # (only a member of an AmclBatch may start without a map)
             self.update_map(grid)
 
@@ -742,6 +750,19 @@ class Amcl:
         done, back = C.c_uint64(0), C.c_uint64(0)
         self._check(self._lib.mcl_get_ndt_small_cycle_counts(self._ctx, C.byref(done), C.byref(back)))
         return done.value, back.value
+
+    def set_ndt_map_layout(self, mode: int):
+        """mcl_set_ndt_map_layout: how the NEXT update_map / build_ndt_map lays the NDT map out on the device - 0 the dense index grid
+        over the keys' bounding box (the default; a box beyond 2^26 cells is refused), 1 the hashed table where that grid does not
+        fit, 2 the hashed table always.  The same weights, bit for bit, on every map both layouts hold.  The installed map stays as
+        it is.  Raises on another sensor model or another value."""
+        self._check(self._lib.mcl_set_ndt_map_layout(self._ctx, int(mode)))
+
+    def ndt_map_layout(self) -> Tuple[int, int]:
+        """(mode, in_use): the mode as set, and what the installed map uses - 0 dense, 1 hashed, -1 no map."""
+        mode, in_use = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.mcl_get_ndt_map_layout(self._ctx, C.byref(mode), C.byref(in_use)))
+        return mode.value, in_use.value
 
     def set_landmark_small_cycle(self, on: bool = True):
         """mcl_set_landmark_small_cycle: small landmark and bearing sets (up to 4096 particles) take the wave-per-particle reweight and

@@ -213,6 +213,8 @@ _SIGNATURES = {
     "mcl_set_ndt_small_cycle": (C.c_int32, [_ctx, C.c_int32]),
     "mcl_get_ndt_small_cycle": (C.c_int32, [_ctx, C.POINTER(C.c_int32)]),
     "mcl_get_ndt_small_cycle_counts": (C.c_int32, [_ctx, c_u64_p, c_u64_p]),
+    "mcl_set_ndt_map_layout": (C.c_int32, [_ctx, C.c_int32]),
+    "mcl_get_ndt_map_layout": (C.c_int32, [_ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mcl_build_ndt_map_from_points": (C.c_int32, [_ctx, c_double_p, C.c_uint64, C.c_double]),
     "mcl_build_ndt_map_from_grid": (C.c_int32, [_ctx, c_i8_p, C.c_uint32, C.c_uint32, C.c_double, c_double_p, C.c_double]),
     "mcl_get_ndt_map": (C.c_int32, [_ctx, C.POINTER(C.c_int32), c_double_p, c_double_p, C.c_uint64, c_u64_p]),
@@ -247,7 +249,8 @@ _SIGNATURES = {
 
 # symbols a library may lack and still load (an older build named by BELUGA_MCL_LIB: tools/exp_ndt_small.py and tools/exp_landmark_small.py measure against one)
 _OPTIONAL = {"mcl_measurement_build", "mcl_set_ndt_small_cycle", "mcl_get_ndt_small_cycle", "mcl_get_ndt_small_cycle_counts",
-             "mcl_ndt_batch_counts", "mcl_set_landmark_small_cycle", "mcl_get_landmark_small_cycle", "mcl_landmark_batch_update"}
+             "mcl_ndt_batch_counts", "mcl_set_landmark_small_cycle", "mcl_get_landmark_small_cycle", "mcl_landmark_batch_update",
+             "mcl_set_ndt_map_layout", "mcl_get_ndt_map_layout"}
 _lib = None
 
 

@@ -62,7 +62,8 @@ struct BatchNdtFacts {
   bool small_fused;        // option small_fused
   uint64_t n;              // particles of the live set
   uint64_t max_particles;  // min(max_particles, capacity)
-  bool have_map;           // an NDT map is installed
+  bool have_map;           // an NDT map is installed, in the dense layout (k_batch_reweight_ndt reads the index grid; a member on a
+                           // hashed map, mcl_set_ndt_map_layout, runs its own cycle)
   bool profiling;          // stage profiling on
 };
 // The member's own mcl_update would run exactly k_propagate_small, k_reweight_ndt_wave, k_small_tail.

@@ -261,6 +261,12 @@ struct mcl_ctx {
   mcl_ndt_params ndt_params{};       // the model parameters of the last mcl_set_ndt_map (the device builds keep them)
   bool have_ndt_params{false};
   NdtMapView ndt_view{};
+  // the layout of the NEXT map install (mcl_set_ndt_map_layout, NdtLayoutMode) and that of the installed map: hashed = d_ndt_slots and
+  // ndt_hash_view instead of d_ndt_grid and ndt_view (the records and the keys are the same in both)
+  int32_t ndt_layout_mode{kNdtLayoutDense};
+  bool ndt_map_hashed{false};
+  DeviceBuffer<NdtSlot> d_ndt_slots;
+  NdtHashView ndt_hash_view{};
   uint64_t ndt_map_cells{0};
   double ndt_resolution{0.0};
   std::vector<double> h_ndt_meas;  // the scan's measurement cells, kNdtRecord doubles each (what stage_points uploads)
@@ -662,8 +668,37 @@ Measurement ndt_fit_scan(mcl_ctx* ctx, const double* pts, uint64_t num_points) {
   return Measurement{ctx->h_ndt_meas.data(), ctx->h_ndt_meas.size()};
 }
 
-// The map in d_ndt_grid / d_ndt_cells / d_ndt_keys (n cells, complete) becomes the context's.
-void ndt_install_view(mcl_ctx* ctx, const NdtGridShape& g, const mcl_ndt_params& prm, uint64_t n, double resolution) {
+// The map in d_ndt_grid / d_ndt_cells / d_ndt_keys (n cells, complete) becomes the context's.  table != nullptr: the map is in the
+// hashed layout, d_ndt_slots instead of d_ndt_grid (which goes back to the device: an index grid of the last dense map may be large).
+void ndt_install_view(mcl_ctx* ctx, const NdtGridShape& g, const mcl_ndt_params& prm, uint64_t n, double resolution,
+                      const NdtHashTable* table = nullptr) {
+  ctx->ndt_map_hashed = table != nullptr;
+  if (table) {
+    NdtHashView h{};
+    h.table = *table;
+    h.cells = ctx->d_ndt_cells.ptr;
+    h.inv_resolution = 1. / resolution;
+    h.centre_x0 = g.x0 - g.reach;
+    h.centre_y0 = g.y0 - g.reach;
+    h.key_x0 = static_cast<double>(h.centre_x0);
+    h.key_y0 = static_cast<double>(h.centre_y0);
+    h.box_w = static_cast<double>(g.x1 - g.x0 + 1 + 2 * g.reach);
+    h.box_h = static_cast<double>(g.y1 - g.y0 + 1 + 2 * g.reach);
+    h.d1 = prm.d1;
+    h.d2 = prm.d2;
+    h.minimum_likelihood = prm.minimum_likelihood;
+    h.num_offsets = prm.num_offsets;
+    for (uint32_t k = 0; k < 2 * prm.num_offsets; ++k) h.offsets[k] = prm.offsets[k];
+    ctx->ndt_hash_view = h;
+    ctx->ndt_view = NdtMapView{};
+    ctx->d_ndt_grid.release();
+    ctx->ndt_map_cells = n;
+    ctx->ndt_resolution = resolution;
+    ctx->have_ndt_map = true;
+    return;
+  }
+  ctx->ndt_hash_view = NdtHashView{};
+  ctx->d_ndt_slots.release();
   NdtMapView v{};
   v.grid = ctx->d_ndt_grid.ptr;
   v.cells = ctx->d_ndt_cells.ptr;
@@ -683,6 +718,19 @@ void ndt_install_view(mcl_ctx* ctx, const NdtGridShape& g, const mcl_ndt_params&
   ctx->ndt_map_cells = n;
   ctx->ndt_resolution = resolution;
   ctx->have_ndt_map = true;
+}
+
+// The NDT reweight of the live set against the installed map, `cells` measurement cells in d_points: the kernel by the map's layout and
+// by the size of the set (mcl_update, mcl_reweight and mcl_reweight_ndt_cells all come through here).
+void launch_ndt_reweight(mcl_ctx* ctx, uint32_t cells) {
+  const bool waves = ndt_reweight_takes_waves(ctx->ndt_small_cycle, ctx->n);
+  if (ctx->ndt_map_hashed) {
+    if (waves) launch_reweight_ndt_wave_hashed(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_hash_view, ctx->d_points.ptr, cells);
+    else launch_reweight_ndt_hashed(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_hash_view, ctx->d_points.ptr, cells);
+  } else {
+    if (waves) launch_reweight_ndt_wave(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, cells);
+    else launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, cells);
+  }
 }
 
 uint32_t bits_of(uint64_t span) {  // bits that hold 0 .. span
@@ -726,7 +774,7 @@ mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, co
   sc.chunk_tmp = sc.table + table;
   sc.starts = sc.chunk_tmp + chunks;
   sc.counters = sc.starts + starts;
-  uint32_t counters[kNdtCounters] = {0u, UINT32_MAX, 0u, UINT32_MAX, 0u, 0u};
+  uint32_t counters[kNdtCounters] = {0u, UINT32_MAX, 0u, UINT32_MAX, 0u, 0u, 0u};
   MCL_HIP(ctx, hipMemcpy(sc.counters, counters, sizeof(counters), hipMemcpyHostToDevice));
   const int sorted = launch_ndt_group_points(st, d_pts, n, resolution, box[0], box[2], bits_x, bits_y, sc);
   MCL_HIP(ctx, hipStreamSynchronize(st));
@@ -735,16 +783,32 @@ mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, co
   MCL_REQUIRE(ctx, cells > 0, who + ": no cell holds 5 points or more at this resolution (the map is kept as it was)");
   const uint32_t* kb = counters + kNdtCountKeptBox;
   const NdtGridShape g = ndt_grid_shape(ndt_reach(prm), int64_t{box[0]} + kb[0], int64_t{box[0]} + kb[1], int64_t{box[2]} + kb[2], int64_t{box[2]} + kb[3]);
-  if (!g.fits)
+  const bool hashed = ndt_map_is_hashed(ctx->ndt_layout_mode, g.fits);
+  if (!g.fits && !hashed)
     return fail(ctx, MCL_ERR_UNSUPPORTED, who + ": the bounding box of the keys exceeds 2^26 cells (" + std::to_string(g.gw) + " x " +
                                               std::to_string(g.gh) + " with its border)");
   ctx->have_ndt_map = false;  // (until the new map is complete: ensure() may free the buffers the old view points at; the stream is idle)
-  const size_t grid_cells = static_cast<size_t>(g.gw * g.gh);
-  MCL_HIP(ctx, ctx->d_ndt_grid.ensure(grid_cells));
   MCL_HIP(ctx, ctx->d_ndt_cells.ensure(static_cast<size_t>(cells) * kNdtRecord));
   MCL_HIP(ctx, ctx->d_ndt_keys.ensure(static_cast<size_t>(2) * cells));
-  MCL_HIP(ctx, hipMemsetAsync(ctx->d_ndt_grid.ptr, 0xFF, grid_cells * sizeof(int32_t), st));  // -1: no cell
   const NdtBuildLayout lay{box[0], box[2], g.grid_x0, g.grid_y0, g.gw};
+  if (hashed) {  // no index grid: the kept cells' keys go into the table, and the longest probe comes back with the counters
+    const uint32_t log2_capacity = ndt_hash_log2_capacity(cells);
+    const size_t capacity = size_t{1} << log2_capacity;
+    MCL_HIP(ctx, ctx->d_ndt_slots.ensure(capacity));
+    MCL_HIP(ctx, hipMemsetAsync(ctx->d_ndt_slots.ptr, 0xFF, capacity * sizeof(NdtSlot), st));  // record kNdtNoRecord: empty
+    launch_ndt_fit_cells(st, d_pts, n, sc, sorted, cells, lay, ctx->d_ndt_cells.ptr, ctx->d_ndt_keys.ptr, nullptr);
+    NdtHashTable table{ctx->d_ndt_slots.ptr, static_cast<uint32_t>(capacity - 1), 64 - log2_capacity, 0};
+    launch_ndt_hash_insert(st, ctx->d_ndt_keys.ptr, cells, ctx->d_ndt_slots.ptr, table.mask, table.shift, sc.counters + kNdtCountLongestProbe);
+    MCL_HIP(ctx, hipStreamSynchronize(st));
+    MCL_HIP(ctx, hipGetLastError());
+    MCL_HIP(ctx, hipMemcpy(counters, sc.counters, sizeof(counters), hipMemcpyDeviceToHost));
+    table.longest_probe = counters[kNdtCountLongestProbe];
+    ndt_install_view(ctx, g, prm, cells, resolution, &table);
+    return MCL_OK;
+  }
+  const size_t grid_cells = static_cast<size_t>(g.gw * g.gh);
+  MCL_HIP(ctx, ctx->d_ndt_grid.ensure(grid_cells));
+  MCL_HIP(ctx, hipMemsetAsync(ctx->d_ndt_grid.ptr, 0xFF, grid_cells * sizeof(int32_t), st));  // -1: no cell
   launch_ndt_fit_cells(st, d_pts, n, sc, sorted, cells, lay, ctx->d_ndt_cells.ptr, ctx->d_ndt_keys.ptr, ctx->d_ndt_grid.ptr);
   MCL_HIP(ctx, hipStreamSynchronize(st));
   MCL_HIP(ctx, hipGetLastError());
@@ -1001,7 +1065,7 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
                                  static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles), ctx->profile != 0});
     hold->ndt = ctx->is_ndt() && batch_ndt_member_fused(BatchNdtFacts{
                                      ctx->cfg.sensor_kind, ctx->ndt_small_cycle, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
-                                     ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), ctx->have_ndt_map, ctx->profile != 0});
+                                     ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), ctx->have_ndt_map && !ctx->ndt_map_hashed, ctx->profile != 0});
     hold->landmark = ctx->is_landmark() && batch_landmark_member_fused(BatchLandmarkFacts{
                                      ctx->cfg.sensor_kind, ctx->landmark_small_cycle, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
                                      ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), ctx->profile != 0});
@@ -1020,10 +1084,8 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
     if (hold && hold->fused) {  // (a held cycle: the batch launches k_batch_reweight_ndt)
       hold->item.ndt = ctx->ndt_view;
       hold->item.ndt_cells = cells;
-    } else if (ndt_reweight_takes_waves(ctx->ndt_small_cycle, ctx->n)) {
-      launch_reweight_ndt_wave(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, cells);
     } else {
-      launch_reweight_ndt(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_view, ctx->d_points.ptr, cells);
+      launch_ndt_reweight(ctx, cells);
     }
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
   } else if (ctx->is_landmark()) {
@@ -4125,20 +4187,54 @@ mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* mea
   if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_map: not on a landmark or bearing context (its map comes from mcl_set_landmark_map)");
   MCL_REQUIRE(ctx, ctx->is_ndt(), "mcl_set_ndt_map: the context's sensor model is not MCL_SENSOR_NDT");
   NdtMapLayout map;
+  NdtHashLayout hashed_map;
   std::string error;
-  if (const mcl_status s = ndt_layout_map(cells, means, covariances, n, resolution, params, &map, &error)) return fail(ctx, s, error);
+  // the layout by the context's mode, chosen from the keys' box before anything is checked: a map is checked once
+  const bool hashed = ndt_map_is_hashed(ctx->ndt_layout_mode, ctx->ndt_layout_mode != kNdtLayoutAuto || ndt_keys_fit_grid(cells, n, params));
+  if (const mcl_status s = hashed ? ndt_layout_map_hashed(cells, means, covariances, n, resolution, params, &hashed_map, &error)
+                                  : ndt_layout_map(cells, means, covariances, n, resolution, params, &map, &error))
+    return fail(ctx, s, error);
+  const std::vector<double>& records = hashed ? hashed_map.records : map.records;
+  const mcl_ndt_params& prm = hashed ? hashed_map.params : map.params;
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a reweight in flight may still read the old map)
   ctx->have_ndt_map = false;  // (until the new map is complete: ensure() may free the buffers the old view points at)
-  MCL_HIP(ctx, ctx->d_ndt_grid.ensure(map.grid.size()));
-  MCL_HIP(ctx, ctx->d_ndt_cells.ensure(map.records.size()));
+  if (hashed) {
+    MCL_HIP(ctx, ctx->d_ndt_slots.ensure(hashed_map.slots.size()));
+    MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_slots.ptr, hashed_map.slots.data(), hashed_map.slots.size() * sizeof(NdtSlot), hipMemcpyHostToDevice));
+  } else {
+    MCL_HIP(ctx, ctx->d_ndt_grid.ensure(map.grid.size()));
+    MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_grid.ptr, map.grid.data(), map.grid.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  MCL_HIP(ctx, ctx->d_ndt_cells.ensure(records.size()));
   MCL_HIP(ctx, ctx->d_ndt_keys.ensure(static_cast<size_t>(2 * n)));
-  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_grid.ptr, map.grid.data(), map.grid.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_cells.ptr, map.records.data(), map.records.size() * sizeof(double), hipMemcpyHostToDevice));
+  MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_cells.ptr, records.data(), records.size() * sizeof(double), hipMemcpyHostToDevice));
   MCL_HIP(ctx, hipMemcpy(ctx->d_ndt_keys.ptr, cells, static_cast<size_t>(2 * n) * sizeof(int32_t), hipMemcpyHostToDevice));
-  ctx->ndt_params = map.params;
+  ctx->ndt_params = prm;
   ctx->have_ndt_params = true;
-  ndt_install_view(ctx, map.shape, map.params, n, resolution);
+  if (hashed) {
+    NdtHashTable table = hashed_map.table();
+    table.slots = ctx->d_ndt_slots.ptr;
+    ndt_install_view(ctx, hashed_map.shape, prm, n, resolution, &table);
+  } else {
+    ndt_install_view(ctx, map.shape, prm, n, resolution);
+  }
+  return MCL_OK;
+}
+
+mcl_status mcl_set_ndt_map_layout(mcl_ctx* ctx, int32_t mode) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_ndt_map_layout: the context's sensor model is not MCL_SENSOR_NDT");
+  if (!ndt_layout_mode_valid(mode)) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, "mcl_set_ndt_map_layout: the mode must be 0 (dense), 1 (automatic) or 2 (hashed)");
+  ctx->ndt_layout_mode = mode;  // (the next map install reads it; the installed map stays as it is)
+  return MCL_OK;
+}
+
+mcl_status mcl_get_ndt_map_layout(mcl_ctx* ctx, int32_t* mode, int32_t* in_use) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_get_ndt_map_layout: the context's sensor model is not MCL_SENSOR_NDT");
+  if (mode) *mode = ctx->ndt_layout_mode;
+  if (in_use) *in_use = !ctx->have_ndt_map ? -1 : ctx->ndt_map_hashed ? 1 : 0;
   return MCL_OK;
 }
 

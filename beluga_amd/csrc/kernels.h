@@ -13,6 +13,7 @@
 
 #include "batch_host.h"
 #include "cycle_types.h"
+#include "ndt_hash.h"
 #include "se2.h"
 #include "sensor_records.h"
 
@@ -138,6 +139,25 @@ void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapVi
 // The same weights, bit for bit, from a wave per particle with the lanes over the measurement cells (k_reweight_ndt_wave): small sets.
 void launch_reweight_ndt_wave(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k);
 
+// The same map in the hashed layout (mcl_set_ndt_map_layout; ndt_hash.h has the table, its hash and the bound on the probe): no index
+// grid, so the keys' box may be of any extent.  The centre box is tested first, in doubles, exactly as with NdtMapView; inside it the
+// centre key is an integer, every neighbour key is centre + (dx, dy) in 64 bits, and only a neighbour that fits an int32 is probed.
+// A view of its own, not fields of NdtMapView: the three kernels that take that one (BatchItem included) stay as they are.
+struct NdtHashView {
+  NdtHashTable table;
+  const double* cells;             // kNdtRecord doubles per map cell
+  double inv_resolution;
+  double key_x0, key_y0;           // as NdtMapView's ...
+  double box_w, box_h;
+  long long centre_x0, centre_y0;  // ... and key_x0, key_y0 as integers
+  double d1, d2, minimum_likelihood;
+  uint32_t num_offsets;
+  int32_t offsets[2 * kNdtMaxOffsets];  // (dx, dy) of each kernel offset, in the kernel's order
+};
+// launch_reweight_ndt and launch_reweight_ndt_wave on such a map: the same weights, bit for bit, on every map both layouts hold.
+void launch_reweight_ndt_hashed(hipStream_t st, Particles p, uint64_t n, const NdtHashView& m, const double* meas, uint32_t k);
+void launch_reweight_ndt_wave_hashed(hipStream_t st, Particles p, uint64_t n, const NdtHashView& m, const double* meas, uint32_t k);
+
 // The NDT map built on the device (ndt_build_kernels.hip): detail::to_cells with fit_points over n points, as ndt_fit_cells (ndt_host.cpp)
 // does on the host - keys by truncation toward zero, cells of 5 points or more in ascending (x, y) key order, a cell's sums taken in
 // input order.  Every launcher takes n > 0 points (n < 2^31), x and y interleaved.
@@ -154,7 +174,8 @@ enum NdtBuildCounter : int {
   kNdtCountCells = 0,    // cells kept (launch_ndt_group_points)
   kNdtCountKeptBox = 1,  // [1..5): min x, max x, min y, max y of the kept cells' relative keys; the caller sets UINT_MAX, 0, UINT_MAX, 0
   kNdtCountScratch = 5,
-  kNdtCounters = 6
+  kNdtCountLongestProbe = 6,  // launch_ndt_hash_insert: the most slots any key needed; the caller sets 0
+  kNdtCounters = 7
 };
 struct NdtBuildLayout {
   long long x0, y0;            // the key the relative keys count from
@@ -170,9 +191,13 @@ void launch_ndt_key_box(hipStream_t st, const double* pts, uint32_t n, double re
 int launch_ndt_group_points(hipStream_t st, const double* pts, uint32_t n, double resolution, int32_t x0, int32_t y0, uint32_t bits_x,
                             uint32_t bits_y, const NdtBuildScratch& s);
 // The `cells` kept cells (s.counters[kNdtCountCells]) -> records (kNdtRecord doubles each), keys (x, y) and their entries in the index
-// grid (set to -1 by the caller), laid out as NdtMapView wants them.
+// grid (set to -1 by the caller), laid out as NdtMapView wants them.  grid == nullptr (the hashed layout): no entries.
 void launch_ndt_fit_cells(hipStream_t st, const double* pts, uint32_t n, const NdtBuildScratch& s, int sorted, uint32_t cells,
                           const NdtBuildLayout& lay, double* records, int32_t* keys, int32_t* grid);
+// The hashed layout's table over `cells` distinct keys (x, y pairs, as launch_ndt_fit_cells leaves them): slots[0 .. mask] set to 0xFF
+// bytes by the caller (every record kNdtNoRecord), mask and shift as NdtHashTable's.  Which slot a key lands in depends on the race
+// between the lanes; what ndt_hash_find returns does not.  *d_longest takes the most slots any key needed (atomic max).
+void launch_ndt_hash_insert(hipStream_t st, const int32_t* keys, uint32_t cells, NdtSlot* slots, uint32_t mask, uint32_t shift, uint32_t* d_longest);
 // Occupancy grid -> points: offsets[i] = occupied cells before cell i in row-major order, *d_total = their number; then the centres of
 // the occupied cells, origin * (resolution * (index + 0.5)), in that order.
 void launch_ndt_grid_offsets(hipStream_t st, const int8_t* cells, uint32_t count, int8_t occupied, uint32_t* offsets, uint32_t* chunk_tmp,

@@ -298,7 +298,28 @@ __global__ __launch_bounds__(kBlock) void k_ndt_fit_cells(const double2* __restr
   const long long kx = lay.x0 + static_cast<long long>(w >> 32), ky = lay.y0 + static_cast<long long>(w & 0xFFFFFFFFull);
   keys[2 * c] = static_cast<int32_t>(kx);
   keys[2 * c + 1] = static_cast<int32_t>(ky);
-  grid[(ky - lay.grid_y0) * lay.gw + (kx - lay.grid_x0)] = static_cast<int32_t>(c);
+  if (grid) grid[(ky - lay.grid_y0) * lay.gw + (kx - lay.grid_x0)] = static_cast<int32_t>(c);
+}
+
+// A lane per cell of the hashed layout (ndt_hash.h): the first empty slot from the key's home on is claimed by a compare-and-swap on its
+// record word (the explicit empty marker), then takes the key.  The keys are distinct, so no lane ever needs to read another's key; a
+// claimed slot stays claimed, so every slot between a key's home and its own is occupied - what ndt_hash_find relies on.  The walk is
+// bounded by the capacity: with a load of at most 1/2 it ends long before, and a table that something else has filled loses the cell.
+__global__ __launch_bounds__(kBlock) void k_ndt_hash_insert(const int32_t* __restrict__ keys, uint32_t cells, NdtSlot* __restrict__ slots,
+                                                            uint32_t mask, uint32_t shift, uint32_t* __restrict__ longest) {
+  const uint32_t c = blockIdx.x * kBlock + threadIdx.x;
+  if (c >= cells) return;
+  const uint64_t key = ndt_pack_key(keys[2 * c], keys[2 * c + 1]);
+  uint32_t at = ndt_hash_home(key, shift);
+  for (uint32_t probe = 1;; ++probe, ++at) {
+    NdtSlot* slot = slots + (at & mask);
+    if (atomicCAS(&slot->record, kNdtNoRecord, static_cast<int32_t>(c)) == kNdtNoRecord) {
+      slot->key = key;
+      atomicMax(longest, probe);
+      return;
+    }
+    if (probe > mask) return;  // (every slot seen)
+  }
 }
 
 // ---- occupancy grid -> points ------------------------------------------------------------------------------------------------------
@@ -355,6 +376,10 @@ void launch_ndt_fit_cells(hipStream_t st, const double* pts, uint32_t n, const N
   hipLaunchKernelGGL(k_ndt_cell_starts, dim3(blocks_for(n)), dim3(kBlock), 0, st, s.flags, n, s.starts);
   hipLaunchKernelGGL(k_ndt_fit_cells, dim3(blocks_for(cells)), dim3(kBlock), 0, st, reinterpret_cast<const double2*>(pts), s.words[sorted],
                      s.idx[sorted], n, s.starts, cells, lay, records, keys, grid);
+}
+
+void launch_ndt_hash_insert(hipStream_t st, const int32_t* keys, uint32_t cells, NdtSlot* slots, uint32_t mask, uint32_t shift, uint32_t* d_longest) {
+  hipLaunchKernelGGL(k_ndt_hash_insert, dim3(blocks_for(cells)), dim3(kBlock), 0, st, keys, cells, slots, mask, shift, d_longest);
 }
 
 void launch_ndt_grid_offsets(hipStream_t st, const int8_t* cells, uint32_t count, int8_t occupied, uint32_t* offsets, uint32_t* chunk_tmp,

@@ -61,12 +61,14 @@ NdtGridShape ndt_grid_shape(int32_t reach, int64_t x0, int64_t x1, int64_t y0, i
   return g;
 }
 
-mcl_status ndt_layout_map(const int32_t* cells, const double* means, const double* covariances, uint64_t n, double resolution,
-                          const mcl_ndt_params* params, NdtMapLayout* out, std::string* error) {
+namespace {
+
+// What both layouts check before the box matters: the arguments, the parameters into `prm`, every cell's values; the keys' box.
+mcl_status ndt_check_map(const int32_t* cells, const double* means, const double* covariances, uint64_t n, double resolution,
+                         const mcl_ndt_params* params, mcl_ndt_params& prm, NdtGridShape* shape, std::string* error) {
   NDT_REQUIRE(cells && means && covariances && n > 0, "mcl_set_ndt_map: null argument or no cells");
   NDT_REQUIRE(n < (1ull << 31), "mcl_set_ndt_map: too many cells");
   NDT_REQUIRE(std::isfinite(resolution) && resolution > 0.0, "mcl_set_ndt_map: resolution must be positive and finite");
-  mcl_ndt_params& prm = out->params;
   if (params) prm = *params;
   else mcl_default_ndt_params(&prm);
   NDT_REQUIRE(prm.num_offsets >= 1 && prm.num_offsets <= MCL_NDT_MAX_OFFSETS, "mcl_set_ndt_map: 1 .. 32 kernel offsets");
@@ -88,7 +90,16 @@ mcl_status ndt_layout_map(const int32_t* cells, const double* means, const doubl
     NDT_REQUIRE(std::abs(c[1] - c[2]) <= 1e-12 * std::max(std::abs(c[1]), std::abs(c[2])),
                 "mcl_set_ndt_map: the covariance of cell " + std::to_string(i) + " is not symmetric");
   }
-  const NdtGridShape g = out->shape = ndt_grid_shape(ndt_reach(prm), x0, x1, y0, y1);
+  *shape = ndt_grid_shape(ndt_reach(prm), x0, x1, y0, y1);
+  return MCL_OK;
+}
+
+}  // namespace
+
+mcl_status ndt_layout_map(const int32_t* cells, const double* means, const double* covariances, uint64_t n, double resolution,
+                          const mcl_ndt_params* params, NdtMapLayout* out, std::string* error) {
+  if (const mcl_status s = ndt_check_map(cells, means, covariances, n, resolution, params, out->params, &out->shape, error)) return s;
+  const NdtGridShape g = out->shape;
   if (!g.fits) {
     if (error)
       *error = "mcl_set_ndt_map: the bounding box of the keys exceeds 2^26 cells (" + std::to_string(g.gw) + " x " + std::to_string(g.gh) +
@@ -101,6 +112,43 @@ mcl_status ndt_layout_map(const int32_t* cells, const double* means, const doubl
     const size_t at = static_cast<size_t>((cells[2 * i + 1] - g.grid_y0) * g.gw + (cells[2 * i] - g.grid_x0));
     NDT_REQUIRE(out->grid[at] < 0, "mcl_set_ndt_map: duplicate key (" + std::to_string(cells[2 * i]) + ", " + std::to_string(cells[2 * i + 1]) + ")");
     out->grid[at] = static_cast<int32_t>(i);
+    ndt_pack_record(means + 2 * i, covariances + 4 * i, out->records.data() + i * kNdtRecord);
+  }
+  return MCL_OK;
+}
+
+bool ndt_keys_fit_grid(const int32_t* cells, uint64_t n, const mcl_ndt_params* params) {
+  mcl_ndt_params prm;
+  if (params) prm = *params;
+  else mcl_default_ndt_params(&prm);
+  if (!cells || n == 0 || n >= (1ull << 31) || prm.num_offsets < 1 || prm.num_offsets > MCL_NDT_MAX_OFFSETS) return true;
+  int64_t x0 = INT64_MAX, y0 = INT64_MAX, x1 = INT64_MIN, y1 = INT64_MIN;
+  for (uint64_t i = 0; i < n; ++i) {
+    x0 = std::min<int64_t>(x0, cells[2 * i]);
+    x1 = std::max<int64_t>(x1, cells[2 * i]);
+    y0 = std::min<int64_t>(y0, cells[2 * i + 1]);
+    y1 = std::max<int64_t>(y1, cells[2 * i + 1]);
+  }
+  // (an offset beyond 64 cells is refused later; here it only widens the border)
+  return ndt_grid_shape(ndt_reach(prm), x0, x1, y0, y1).fits;
+}
+
+mcl_status ndt_layout_map_hashed(const int32_t* cells, const double* means, const double* covariances, uint64_t n, double resolution,
+                                 const mcl_ndt_params* params, NdtHashLayout* out, std::string* error) {
+  if (const mcl_status s = ndt_check_map(cells, means, covariances, n, resolution, params, out->params, &out->shape, error)) return s;
+  out->log2_capacity = ndt_hash_log2_capacity(n);
+  out->longest_probe = 1;
+  out->slots.assign(size_t{1} << out->log2_capacity, NdtSlot{~uint64_t{0}, kNdtNoRecord, kNdtNoRecord});
+  out->records.resize(static_cast<size_t>(n) * kNdtRecord);
+  const uint32_t mask = static_cast<uint32_t>(out->slots.size() - 1), shift = 64 - out->log2_capacity;
+  for (uint64_t i = 0; i < n; ++i) {
+    const uint64_t key = ndt_pack_key(cells[2 * i], cells[2 * i + 1]);
+    uint32_t at = ndt_hash_home(key, shift), probe = 1;
+    for (; out->slots[at & mask].record >= 0; ++at, ++probe)  // (ends: the load is at most 1/2)
+      NDT_REQUIRE(out->slots[at & mask].key != key,
+                  "mcl_set_ndt_map: duplicate key (" + std::to_string(cells[2 * i]) + ", " + std::to_string(cells[2 * i + 1]) + ")");
+    out->slots[at & mask] = NdtSlot{key, static_cast<int32_t>(i), 0};
+    out->longest_probe = std::max(out->longest_probe, probe);
     ndt_pack_record(means + 2 * i, covariances + 4 * i, out->records.data() + i * kNdtRecord);
   }
   return MCL_OK;

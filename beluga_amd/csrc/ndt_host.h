@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "beluga_mcl.h"
+#include "ndt_hash.h"
 #include "sensor_records.h"
 
 namespace mcl {
@@ -48,5 +49,28 @@ struct NdtMapLayout {
 };
 mcl_status ndt_layout_map(const int32_t* cells, const double* means, const double* covariances, uint64_t n, double resolution,
                           const mcl_ndt_params* params, NdtMapLayout* out, std::string* error);
+
+// The layout mode of a context (mcl_set_ndt_map_layout) and what it makes of the next map: the hashed table (ndt_hash.h) instead of
+// the index grid - always, or where the grid would not fit.
+enum NdtLayoutMode : int32_t { kNdtLayoutDense = 0, kNdtLayoutAuto = 1, kNdtLayoutHashed = 2 };
+inline bool ndt_layout_mode_valid(int32_t mode) { return mode >= kNdtLayoutDense && mode <= kNdtLayoutHashed; }
+inline bool ndt_map_is_hashed(int32_t mode, bool grid_fits) { return mode == kNdtLayoutHashed || (mode == kNdtLayoutAuto && !grid_fits); }
+
+// The same map laid out as NdtHashView wants it: ndt_layout_map's checks in its order and its words, except that no box is too large
+// (shape.fits only reports what the dense layout would have said; shape's box and reach are what the kernels test first).
+struct NdtHashLayout {
+  mcl_ndt_params params;
+  NdtGridShape shape;
+  uint32_t log2_capacity;      // ndt_hash_log2_capacity(n)
+  uint32_t longest_probe;      // the most slots any key needed, its own included
+  std::vector<NdtSlot> slots;  // 2^log2_capacity
+  std::vector<double> records;  // one per cell, in the caller's order
+  NdtHashTable table() const { return NdtHashTable{slots.data(), static_cast<uint32_t>(slots.size() - 1), 64 - log2_capacity, longest_probe}; }
+};
+// Whether the dense index grid of these keys would fit (ndt_grid_shape of their box), asked BEFORE any layout so that mode 1 checks a
+// map once: arguments that both layouts refuse anyway (no cells, too many, a bad number of offsets) count as fitting.
+bool ndt_keys_fit_grid(const int32_t* cells, uint64_t n, const mcl_ndt_params* params);
+mcl_status ndt_layout_map_hashed(const int32_t* cells, const double* means, const double* covariances, uint64_t n, double resolution,
+                                 const mcl_ndt_params* params, NdtHashLayout* out, std::string* error);
 
 }  // namespace mcl

@@ -6,7 +6,13 @@
 // by the pose, its centre key, then for each offset of the neighbour kernel one int32 look-up in the index grid (kernels.h
 // NdtMapView) and, where a map cell is present, one record of 48 bytes and one f64 exponential.  The grid and the records are a
 // few hundred KB for a building-sized map at 1 m: they stay in L2.
+//
+// A map in the hashed layout (NdtHashView, ndt_hash.h) runs the same source: the arithmetic below is a template over the view, and only
+// the neighbour look-up differs - a bounded probe of the table instead of one load from the grid.  The offsets are visited in the same
+// order and the present cells added in it, so the two layouts give the same bits on every map that both can hold.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "batch_host.h"
 #include "device_common.hpp"
@@ -14,8 +20,15 @@
 namespace mcl {
 namespace {
 
+// The one place where the layouts differ, written inside the arithmetic (if constexpr): the dense layout's statements are the ones the
+// kernels had before the hashed layout existed, in their places, so that its three kernels keep their registers and occupancy (with
+// the look-up in a helper of its own the lane kernel came out with other figures; DESIGN.md "Hashed map layout").
+template <class View>
+constexpr bool kNdtDense = std::is_same<View, NdtMapView>::value;
+
 // likelihood_at(state * measurement) (ndt_sensor_model.hpp:229-239) of measurement cell `c` for the pose (c, s, x, y).
-__device__ __forceinline__ double ndt_cell_likelihood(const NdtMapView& m, const double* __restrict__ c, const Pose2& p) {
+template <class View>
+__device__ __forceinline__ double ndt_cell_likelihood(const View& m, const double* __restrict__ c, const Pose2& p) {
   const double mx = c[0], my = c[1], sa = c[2], sb = c[3], sd = c[4];
   const double rc = p.r.c, rs = p.r.s;
   // SE2 * NDTCell (ndt_cell.hpp:61-66): mean = so2 * mean + t (Sophus: real * x - imag * y, imag * x + real * y),
@@ -31,10 +44,16 @@ __device__ __forceinline__ double ndt_cell_likelihood(const NdtMapView& m, const
   const double fy = floor(uy * m.inv_resolution) - m.key_y0;
   double likelihood = 0.0;
   if (fx >= 0.0 && fx < m.box_w && fy >= 0.0 && fy < m.box_h) {
-    const int32_t centre = (static_cast<int32_t>(fy) + m.reach) * static_cast<int32_t>(m.gw) + static_cast<int32_t>(fx) + m.reach;
+    // the centre: its index in the grid, or (hashed) the key itself = box position + the box's first key, |.| < 2^33
+    const auto centre = [&] {
+      if constexpr (kNdtDense<View>) return (static_cast<int32_t>(fy) + m.reach) * static_cast<int32_t>(m.gw) + static_cast<int32_t>(fx) + m.reach;
+      else return longlong2{static_cast<long long>(fx) + m.centre_x0, static_cast<long long>(fy) + m.centre_y0};
+    }();
     const double scale = -m.d2 / 2.0;
     for (uint32_t o = 0; o < m.num_offsets; ++o) {
-      const int32_t idx = m.grid[centre + m.delta[o]];
+      int32_t idx;
+      if constexpr (kNdtDense<View>) idx = m.grid[centre + m.delta[o]];
+      else idx = ndt_hash_find_neighbour(m.table, centre.x, centre.y, m.offsets[2 * o], m.offsets[2 * o + 1]);
       if (idx < 0) continue;
       const double2* rec = reinterpret_cast<const double2*>(m.cells + static_cast<size_t>(idx) * kNdtRecord);
       const double2 mean = rec[0], ab = rec[1], d_ = rec[2];
@@ -51,7 +70,8 @@ __device__ __forceinline__ double ndt_cell_likelihood(const NdtMapView& m, const
   return likelihood > m.minimum_likelihood ? likelihood : m.minimum_likelihood;  // std::max(likelihood, minimum_likelihood)
 }
 
-__global__ __launch_bounds__(kBlock) void k_reweight_ndt(Particles p, uint64_t n, NdtMapView m, const double* __restrict__ meas, uint32_t k) {
+template <class View>
+__device__ __forceinline__ void reweight_ndt_lanes(const Particles& p, uint64_t n, const View& m, const double* __restrict__ meas, uint32_t k) {
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
   if (i >= n) return;
   const Pose2 s = load_pose(p, i);
@@ -68,6 +88,12 @@ __global__ __launch_bounds__(kBlock) void k_reweight_ndt(Particles p, uint64_t n
   for (; j < k; ++j) acc += ndt_cell_likelihood(m, meas + j * kNdtRecord, s);
   p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
 }
+__global__ __launch_bounds__(kBlock) void k_reweight_ndt(Particles p, uint64_t n, NdtMapView m, const double* __restrict__ meas, uint32_t k) {
+  reweight_ndt_lanes(p, n, m, meas, k);
+}
+__global__ __launch_bounds__(kBlock) void k_reweight_ndt_hashed(Particles p, uint64_t n, NdtHashView m, const double* __restrict__ meas, uint32_t k) {
+  reweight_ndt_lanes(p, n, m, meas, k);
+}
 
 // The same weights from a wave per particle (small sets: at 2000 particles a lane per particle is eight workgroups on 256 CUs, each lane
 // walking K cells x up to 9 neighbours x one f64 exp in a row).  Lane l of pass q takes measurement cell 64 q + l, each lane loading
@@ -76,7 +102,8 @@ __global__ __launch_bounds__(kBlock) void k_reweight_ndt(Particles p, uint64_t n
 // quad holds exactly sum4), and the quad sums are chained into the running sum in cell order through v_readlane; the last K mod 4 cells
 // follow one by one.  Every lane carries the same running sum.  No workgroup memory, no atomics.
 // (the body: block `block` of ONE set - blockIdx.x in k_reweight_ndt_wave, a member's local block in k_batch_reweight_ndt)
-__device__ __forceinline__ void reweight_ndt_wave_block(uint32_t block, const Particles& p, uint64_t n, const NdtMapView& m,
+template <class View>
+__device__ __forceinline__ void reweight_ndt_wave_block(uint32_t block, const Particles& p, uint64_t n, const View& m,
                                                         const double* __restrict__ meas, uint32_t k) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
@@ -102,6 +129,9 @@ __device__ __forceinline__ void reweight_ndt_wave_block(uint32_t block, const Pa
 __global__ __launch_bounds__(kBlock) void k_reweight_ndt_wave(Particles p, uint64_t n, NdtMapView m, const double* __restrict__ meas, uint32_t k) {
   reweight_ndt_wave_block(blockIdx.x, p, n, m, meas, k);
 }
+__global__ __launch_bounds__(kBlock) void k_reweight_ndt_wave_hashed(Particles p, uint64_t n, NdtHashView m, const double* __restrict__ meas, uint32_t k) {
+  reweight_ndt_wave_block(blockIdx.x, p, n, m, meas, k);
+}
 // The same over a fleet's NDT members (mcl_batch_update; the pattern is k_batch_reweight_beam, beam_kernels.hip): a workgroup finds its
 // member over the first_ndt_block prefix - a member without a block (n = 0, no measurement cell, another family's member) is never found -
 // and runs the body with its LOCAL block number on the member's own map and staged cells.
@@ -120,6 +150,14 @@ void launch_reweight_ndt(hipStream_t st, Particles p, uint64_t n, const NdtMapVi
 void launch_reweight_ndt_wave(hipStream_t st, Particles p, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k) {
   if (n == 0) return;
   hipLaunchKernelGGL(k_reweight_ndt_wave, dim3(batch_ndt_blocks(n, 1)), dim3(kBlock), 0, st, p, n, m, meas, k);
+}
+void launch_reweight_ndt_hashed(hipStream_t st, Particles p, uint64_t n, const NdtHashView& m, const double* meas, uint32_t k) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_reweight_ndt_hashed, dim3(blocks_for(n)), dim3(kBlock), 0, st, p, n, m, meas, k);
+}
+void launch_reweight_ndt_wave_hashed(hipStream_t st, Particles p, uint64_t n, const NdtHashView& m, const double* meas, uint32_t k) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_reweight_ndt_wave_hashed, dim3(batch_ndt_blocks(n, 1)), dim3(kBlock), 0, st, p, n, m, meas, k);
 }
 void launch_batch_reweight_ndt(hipStream_t st, const BatchItem* d_items, uint32_t members, uint32_t blocks) {
   if (blocks == 0) return;

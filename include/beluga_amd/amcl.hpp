@@ -493,11 +493,14 @@ class Amcl {
   }
   /// The filter of ndt_amcl_node (beluga_amcl/include/beluga_amcl/ndt_amcl_node.hpp:77-84): beluga::Amcl with the NDT sensor model.
   /// Code written for `NdtAmcl<Motion, Policy>` switches by a type alias: construction from (map, motion, NDTModelParam2d, params).
+  /// `ndt_map_layout`: set_ndt_map_layout before `map` is installed (0 dense, 1 hashed where the dense grid does not fit, 2 hashed).
   Amcl(const NDTMap2d& map, const MotionModelParam& motion, const NDTModelParam2d& sensor, const AmclParams& params = AmclParams{},
-       std::uint64_t seed = 0, int device = 0, const std::vector<std::pair<std::string, std::int64_t>>& options = {})
+       std::uint64_t seed = 0, int device = 0, const std::vector<std::pair<std::string, std::int64_t>>& options = {},
+       std::int32_t ndt_map_layout = 0)
       : ndt_params_(sensor) {
     create(make_config(motion, SensorModelParam{sensor}, params, seed, device, Shard{}), params, options);
     try {
+      if (ndt_map_layout != 0) set_ndt_map_layout(ndt_map_layout);
       update_map(map);
     } catch (...) {
       mcl_destroy(ctx_);
@@ -761,6 +764,18 @@ class Amcl {
     std::uint64_t completed = 0, handed_back = 0;
     check(mcl_get_ndt_small_cycle_counts(ctx_, &completed, &handed_back));
     return {completed, handed_back};
+  }
+
+  /// Extension (the NDT constructor form only; throws on another sensor model or another value): mcl_set_ndt_map_layout, how the NEXT
+  /// update_map / build_ndt_map lays the map out on the device.  0: the dense index grid over the keys' bounding box, the default (a box
+  /// beyond 2^26 cells is refused); 1: the hashed table where that grid does not fit; 2: the hashed table always.  The same weights, bit
+  /// for bit, on every map both layouts hold; the installed map stays as it is.
+  void set_ndt_map_layout(std::int32_t mode) { check(mcl_set_ndt_map_layout(ctx_, mode)); }
+  /// {the mode as set, what the installed map uses: 0 dense, 1 hashed, -1 no map}.
+  [[nodiscard]] std::pair<std::int32_t, std::int32_t> ndt_map_layout() const {
+    std::int32_t mode = 0, in_use = 0;
+    check(mcl_get_ndt_map_layout(ctx_, &mode, &in_use));
+    return {mode, in_use};
   }
 
   /// Extension: the NDT map built on the device from a point cloud in the world frame, by the rule of NDTMap2d::from_points (the same

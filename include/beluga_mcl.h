@@ -258,7 +258,8 @@ void mcl_default_ndt_params(mcl_ndt_params* params);
  * (2 x 2 row-major), at `resolution` metres per cell; params NULL = mcl_default_ndt_params.  Replaces the map between updates
  * (Amcl::update_map).  MCL_ERR_INVALID_ARGUMENT on a context of another sensor model, duplicate keys, no cells, a resolution that is
  * not positive and finite, values that are not finite, an asymmetric covariance, more than MCL_NDT_MAX_OFFSETS offsets or an offset
- * beyond 64 cells; MCL_ERR_UNSUPPORTED where the keys' bounding box (with a border of twice the kernel's reach) exceeds 2^26 cells. */
+ * beyond 64 cells; MCL_ERR_UNSUPPORTED where the keys' bounding box (with a border of twice the kernel's reach) exceeds 2^26 cells
+ * and the context's map layout is the dense one, the default: mcl_set_ndt_map_layout(ctx, 1) beforehand takes such a map as well. */
 mcl_status mcl_set_ndt_map(mcl_ctx* ctx, const int32_t* cells, const double* means, const double* covariances, uint64_t n,
                            double resolution, const mcl_ndt_params* params);
 /* detail::to_cells (ndt_sensor_model.hpp:66-110) of a scan in the base frame: points grouped by (p / resolution) truncated toward
@@ -287,6 +288,20 @@ mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const doubl
 mcl_status mcl_set_ndt_small_cycle(mcl_ctx* ctx, int32_t on);
 mcl_status mcl_get_ndt_small_cycle(mcl_ctx* ctx, int32_t* on);
 mcl_status mcl_get_ndt_small_cycle_counts(mcl_ctx* ctx, uint64_t* completed, uint64_t* handed_back);
+/* How the NEXT map install (mcl_set_ndt_map, mcl_build_ndt_map_from_points / _from_grid) lays the map out on the device.
+ *   0  dense, the default: an int32 index grid over the keys' bounding box; a box beyond 2^26 cells is MCL_ERR_UNSUPPORTED.
+ *   1  automatic: the dense grid where the box fits 2^26 cells, the hashed table where it does not.
+ *   2  hashed always.
+ * The hashed table maps a key (int32 x, int32 y) to its cell by open addressing (a power of two of slots, load at most 1/2, linear
+ * probing bounded by the longest probe of any stored key): memory in proportion to the cells, keys anywhere in the int32 range, as the
+ * reference's SparseValueGrid2 over an unordered_map.  On every map that both layouts hold the weights are the same bits, and so is
+ * everything that follows from them; mcl_get_ndt_map does not depend on the layout.  The installed map is never laid out again by this
+ * call: the mode waits for the next install.  In a batch a member whose installed map is hashed runs its own cycle inside
+ * mcl_batch_update and is not counted by mcl_ndt_batch_counts.
+ * mcl_get_ndt_map_layout: *mode as set, *in_use what the installed map uses - 0 dense, 1 hashed, -1 no map (either pointer may be NULL).
+ * MCL_ERR_UNSUPPORTED on a context of another sensor model, MCL_ERR_INVALID_ARGUMENT for any other mode. */
+mcl_status mcl_set_ndt_map_layout(mcl_ctx* ctx, int32_t mode);
+mcl_status mcl_get_ndt_map_layout(mcl_ctx* ctx, int32_t* mode, int32_t* in_use);
 
 /* The map built on the device from what a user has at a cold start, a point cloud or an occupancy grid: detail::to_cells with
  * fit_points over the n points (world frame), the rule of mcl_ndt_measurement_cells - keys by (p / resolution) truncated toward zero,
@@ -294,7 +309,8 @@ mcl_status mcl_get_ndt_small_cycle_counts(mcl_ctx* ctx, uint64_t* completed, uin
  * cell's sums taken in input order: the cells equal mcl_ndt_measurement_cells' bit for bit.  The result becomes the context's map as if
  * passed to mcl_set_ndt_map, without a visit to the host; the model parameters are those of the last mcl_set_ndt_map on the context,
  * mcl_default_ndt_params if there was none.  MCL_ERR_UNSUPPORTED on a context of another sensor model, or where the kept cells' bounding
- * box (with its border) exceeds 2^26 cells; MCL_ERR_INVALID_ARGUMENT for no points, a point that is not finite or whose key does not
+ * box (with its border) exceeds 2^26 cells under the dense map layout (the default; not under mcl_set_ndt_map_layout's modes 1 and 2,
+ * where the kept cells' keys go into the hashed table on the device); MCL_ERR_INVALID_ARGUMENT for no points, a point that is not finite or whose key does not
  * fit an int32, a resolution that is not positive and finite, or an input without any cell of 5 points: the map is then kept as it was. */
 mcl_status mcl_build_ndt_map_from_points(mcl_ctx* ctx, const double* points_xy, uint64_t n, double resolution);
 /* The same from an occupancy grid (row-major int8 cells, grid_resolution metres per cell, origin as SE2 (cos, sin, x, y)): the points
