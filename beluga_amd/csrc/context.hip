@@ -67,6 +67,9 @@ struct mcl_ctx {
   uint64_t n{0};
   ParticleSet sets[2];
   int live{0};
+  // Which sensor model the context has, by what its cycle runs (cycle_types.h): the one question every dispatch site asks.
+  SensorFamily family() const { return sensor_family(cfg.sensor_kind); }
+  uint64_t max_live() const { return std::min<uint64_t>(cfg.amcl.max_particles, capacity); }  // the most particles a set of this context holds
 
   // map
   bool have_map{false};
@@ -125,7 +128,6 @@ struct mcl_ctx {
   DeviceBuffer<double4> d_field_pose;
   uint64_t map_generation{0};
   uint64_t field_pose_rebuilds{0};  // launches of k_field_pose (mcl_get_counter)
-  bool lf_kind() const { return cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD || cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB; }
   FieldPoseOut field_pose_out() const { return FieldPoseOut{d_field_pose.ptr, map->origin_inverse}; }
   // launch_order_ahead: the spatial order (sort_scratch().perm) that facts.take_order_ahead answers for holds if the control action of that
   // step is the predicted one
@@ -201,6 +203,7 @@ struct mcl_ctx {
   // particle shards: communicator + scratch of the exchange (sharded_update)
   bool have_comm{false};
   uint32_t comm_rank{0}, comm_world{1};
+  bool sharded() const { return have_comm && comm_world > 1; }  // the filter's particles are spread over several contexts
   mcl_transport transport{};
   void* rccl_comm{nullptr};                 // ncclComm_t when the transport is the built-in RCCL one
   struct RcclUserStorage { void* comm; uint32_t rank, world; } rccl_user{nullptr, 0, 1};
@@ -277,9 +280,9 @@ struct mcl_ctx {
   uint64_t ndt_small_completed{0};     // small cycles that ended inside k_small_tail (mcl_get_ndt_small_cycle_counts)
   uint64_t ndt_small_handed_back{0};   // ... and those the tail handed back to the host behind the policies
   NdtCycleFacts ndt_cycle_facts() const {
-    return NdtCycleFacts{ndt_small_cycle, tuning.small_fused != 0, profile != 0, n, std::min<uint64_t>(cfg.amcl.max_particles, capacity)};
+    return NdtCycleFacts{ndt_small_cycle, tuning.small_fused != 0, profile != 0, n, max_live()};
   }
-  bool is_ndt() const { return cfg.sensor_kind == MCL_SENSOR_NDT; }
+  bool is_ndt() const { return family() == SensorFamily::kNdt; }
 
   // Landmark and bearing sensor models (MCL_SENSOR_LANDMARK, MCL_SENSOR_BEARING): the map of mcl_set_landmark_map - the landmarks grouped
   // by category on the device, each category's (first, count) on the host - and the box its random states are drawn from.
@@ -292,14 +295,18 @@ struct mcl_ctx {
   bool landmark_small_cycle{false};     // mcl_set_landmark_small_cycle: the wave-per-particle reweight and the one-launch tail for small sets
   uint64_t landmark_wave_launches{0};   // launches of k_reweight_landmarks_wave / k_reweight_bearings_wave, a fleet's shared one included (mcl_get_counter)
   LandmarkCycleFacts landmark_cycle_facts() const {
-    return LandmarkCycleFacts{landmark_small_cycle, tuning.small_fused != 0, profile != 0, n, std::min<uint64_t>(cfg.amcl.max_particles, capacity)};
+    return LandmarkCycleFacts{landmark_small_cycle, tuning.small_fused != 0, profile != 0, n, max_live()};
   }
-  bool is_landmark() const { return cfg.sensor_kind == MCL_SENSOR_LANDMARK || cfg.sensor_kind == MCL_SENSOR_BEARING; }
+  bool is_landmark() const { return family() == SensorFamily::kLandmark; }
   // A sensor model with a map of its own: no occupancy grid, none of the likelihood-field machinery, the host-read policy path.
   bool off_grid() const { return is_ndt() || is_landmark(); }
   // What random_intersperse's random states are drawn from (random_free_state).
   FreeCells random_source() const {
-    return is_ndt() ? ndt_random : is_landmark() ? landmark_random : FreeCells{map->d_free.ptr, have_map ? map->n_free : 0};
+    switch (family()) {
+      case SensorFamily::kNdt: return ndt_random;
+      case SensorFamily::kLandmark: return landmark_random;
+      default: return FreeCells{map->d_free.ptr, have_map ? map->n_free : 0};  // the grid models: the map's free cells
+    }
   }
   // What the planner and the key frame read of the context (cycle_host.h).
   LfSite lf_site() const { return LfSite{cfg.sensor_kind, n, map->pal_count != 0, map->far_tiles != 0, map->resolution, tuning}; }
@@ -407,7 +414,7 @@ mcl_status ensure_capacity(mcl_ctx* ctx, uint64_t cap) {
   MCL_HIP(ctx, ctx->d_cdf.ensure(cap));
   MCL_HIP(ctx, ctx->d_cdf_tree.ensure(cdf_tree_doubles(cap)));
   MCL_HIP(ctx, ctx->d_lf_wsum.ensure(cap / 448 + 2));
-  if (ctx->lf_kind()) MCL_HIP(ctx, ctx->d_field_pose.ensure(cap));
+  if (ctx->family() == SensorFamily::kLikelihoodField) MCL_HIP(ctx, ctx->d_field_pose.ensure(cap));
   if (!ctx->d_scan_state.ptr) {
     MCL_HIP(ctx, ctx->d_scan_state.ensure(kScanStateWords));
     MCL_HIP(ctx, hipMemset(ctx->d_scan_state.ptr, 0, kScanStateWords * sizeof(unsigned long long)));
@@ -826,7 +833,7 @@ mcl_status stage_points(mcl_ctx* ctx, Measurement* staged) {
   ctx->scan_no_cell = 0;
   if (m.doubles == 0) return MCL_OK;
   MCL_HIP(ctx, ctx->d_points.ensure(m.doubles));
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) MCL_HIP(ctx, ctx->d_beam_points.ensure(kBeamPointDoubles * (m.doubles / 2)));
+  if (ctx->family() == SensorFamily::kBeam) MCL_HIP(ctx, ctx->d_beam_points.ensure(kBeamPointDoubles * (m.doubles / 2)));
   if (ctx->points_in_flight) {  // an earlier call may still be reading the staging buffer
     if (ctx->points_event_valid) MCL_HIP(ctx, hipEventSynchronize(ctx->points_event));
     else MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -848,7 +855,7 @@ mcl_status stage_points(mcl_ctx* ctx, Measurement* staged) {
     if (e == std::numeric_limits<double>::infinity()) unbounded = true;
     extent = e > extent ? e : extent;
   }
-  if ((poisoned || unbounded) && ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {  // (the beam model walks rays: its own rules)
+  if ((poisoned || unbounded) && ctx->family() == SensorFamily::kLikelihoodField) {  // (the beam model walks rays: its own rules)
     uint64_t kept = 0;
     extent = 0.0;
     for (uint64_t i = 0; i < m.doubles; i += 2) {
@@ -923,9 +930,9 @@ struct HeldCycle {
   bool propagate_held{false};  // do_propagate held k_propagate_small back: do_reweight decides (fused) or launches it after all
   bool fused{false};           // the member's cycle is the small one: nothing of it has been launched
   bool pending{false};         // ... and its record is complete
-  bool beam{false};            // fused, and the reweight is the beam model's (k_batch_reweight_beam)
-  bool ndt{false};             // fused, and the reweight is the NDT model's (k_batch_reweight_ndt)
-  bool landmark{false};        // fused, and the reweight is the landmark or bearing model's (k_batch_reweight_landmarks)
+  // fused: whose reweight the batch launches for it - k_batch_reweight_lf_beams, k_batch_reweight_beam, k_batch_reweight_ndt or
+  // k_batch_reweight_landmarks
+  SensorFamily family{SensorFamily::kLikelihoodField};
   BatchItem item{};
   uint64_t every_n{0};         // the counter as the cycle leaves it
 };
@@ -995,25 +1002,182 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
 
 // B: the points of the scan (a landmark or bearing context does not look at it: its records were bounded where they were made).
 mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
-  if (ctx->is_ndt()) {
-    if (!ctx->have_ndt_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no NDT map set (mcl_set_ndt_map)");
-    MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
-    return MCL_OK;
+  switch (ctx->family()) {
+    case SensorFamily::kNdt:
+      if (!ctx->have_ndt_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no NDT map set (mcl_set_ndt_map)");
+      MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
+      return MCL_OK;
+    case SensorFamily::kLandmark:
+      if (!ctx->have_landmark_map) return fail(ctx, MCL_ERR_NOT_READY, "no landmark map set (mcl_set_landmark_map)");
+      return MCL_OK;
+    case SensorFamily::kLikelihoodField:
+      if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no map set");
+      MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
+      return MCL_OK;
+    case SensorFamily::kBeam:
+      if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no map set");
+      MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
+      // the beam kernels' walks keep 16 * span in an int (walk_blocks: 8 * dminor, q * dmajor): lines of 2^27 cells and more are refused
+      MCL_REQUIRE(ctx, ctx->cfg.beam.beam_max_range / ctx->map->resolution < kBeamMaxReachCells,
+                  "beam_max_range / resolution must stay below 2^27 - 2 cells for the beam model");
+      if (!(ctx->n < (1ull << 32) && ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles)))
+        // the beam model's small-set kernel (a wave per particle) stages the scan in 64 KB of dynamic LDS
+        MCL_REQUIRE(ctx, B * sizeof(double2) <= 64 * 1024, "scan too large for the beam model's small-set kernel (4096 points)");
+      return MCL_OK;
   }
-  if (ctx->is_landmark()) {
-    if (!ctx->have_landmark_map) return fail(ctx, MCL_ERR_NOT_READY, "no landmark map set (mcl_set_landmark_map)");
-    return MCL_OK;
-  }
-  if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_reweight: no map set");
-  MCL_REQUIRE(ctx, B <= 0x7FFFFFFFull, "too many points");
-  // the beam kernels' walks keep 16 * span in an int (walk_blocks: 8 * dminor, q * dmajor): lines of 2^27 cells and more are refused
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM)
-    MCL_REQUIRE(ctx, ctx->cfg.beam.beam_max_range / ctx->map->resolution < kBeamMaxReachCells,
-                "beam_max_range / resolution must stay below 2^27 - 2 cells for the beam model");
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM && !(ctx->n < (1ull << 32) && ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles)))
-    // the beam model's small-set kernel (a wave per particle) stages the scan in 64 KB of dynamic LDS
-    MCL_REQUIRE(ctx, B * sizeof(double2) <= 64 * 1024, "scan too large for the beam model's small-set kernel (4096 points)");
   return MCL_OK;
+}
+
+// What do_reweight's prologue settles for the steps behind it: the hold decision, the ordering and the family's own reweight.
+struct ReweightStep {
+  Measurement m;   // as staged
+  uint64_t B;      // the grid models' measurement is the scan itself: B points (0 where the measurement is a list of records)
+  bool ordered, dispersed, unit_weights, want_weight_sums;
+  LfPlanner::Mode mode;
+  SortScratch sort;
+  HeldCycle* hold;     // mcl_batch_update's record of this member's cycle, or nullptr
+  bool held{false};    // ... and the batch launches the cycle (decide_hold): the family's step fills hold->item instead of launching
+  // The likelihood-field family alone (plan_reweight_lf): the launch's arguments - decide_hold asks lf_takes_beams of them, reweight_lf
+  // launches with them - and what the launch does about the field-frame poses.  lf.sort points at `sort`: a step is not copied.
+  FieldPosePlan field_poses{false, false};
+  LfReweightArgs lf{};
+};
+void plan_reweight_lf(mcl_ctx* ctx, ReweightStep* step) {
+  step->field_poses = field_pose_plan(ctx->tuning, ctx->d_field_pose.ptr != nullptr, ctx->facts, ctx->map_generation);
+  step->lf = LfReweightArgs{.p = ctx->cur(), .n = ctx->n, .f = ctx->field_view(), .d_points = ctx->d_points.ptr, .B = static_cast<uint32_t>(step->B),
+                            .sort = step->ordered ? &step->sort : nullptr, .patches = step->mode.patches, .beams = step->mode.beams,
+                            .dispersed = step->dispersed,
+                            .scan_cells = ctx->scan_extent / ctx->map->resolution, .unit_weights = step->unit_weights,
+                            .stats = PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
+                                                reinterpret_cast<unsigned long long*>(ctx->h_scalars.device + kSlotPatchMirror),
+                                                static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
+                                                static_cast<uint32_t>(ctx->tuning.lf_split), step->want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
+                                                reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)},
+                            .field_pose = step->field_poses.load ? ctx->d_field_pose.ptr : nullptr};
+}
+
+// What the predicates of batch_host.h read of a member, family by family.
+BatchMemberFacts batch_lf_facts(const mcl_ctx* ctx, const LfReweightArgs& lf) {
+  return BatchMemberFacts{ctx->cfg.sensor_kind, ctx->sharded(), ctx->tuning.small_fused != 0, ctx->n, ctx->max_live(),
+                          lf_takes_beams(lf, ctx->tuning), ctx->profile != 0};
+}
+BatchBeamFacts batch_beam_facts(const mcl_ctx* ctx) {
+  return BatchBeamFacts{ctx->cfg.sensor_kind, ctx->sharded(), ctx->tuning.small_fused != 0, ctx->tuning.batch_beam_fused != 0, ctx->n, ctx->max_live(),
+                        static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles), ctx->profile != 0};
+}
+BatchNdtFacts batch_ndt_facts(const mcl_ctx* ctx) {
+  return BatchNdtFacts{ctx->cfg.sensor_kind, ctx->ndt_small_cycle, ctx->sharded(), ctx->tuning.small_fused != 0, ctx->n, ctx->max_live(),
+                       ctx->have_ndt_map && !ctx->ndt_map_hashed, ctx->profile != 0};
+}
+BatchLandmarkFacts batch_landmark_facts(const mcl_ctx* ctx) {
+  return BatchLandmarkFacts{ctx->cfg.sensor_kind, ctx->landmark_small_cycle, ctx->sharded(), ctx->tuning.small_fused != 0, ctx->n, ctx->max_live(),
+                            ctx->profile != 0};
+}
+// mcl_batch_update, a member whose propagation do_propagate held back: is its cycle the small one, which the batch launches
+// (hold->fused, and hold->family says whose reweight)?  If not, the propagation goes out now.
+void decide_hold(mcl_ctx* ctx, const ReweightStep& step) {
+  HeldCycle* hold = step.hold;
+  if (!hold || !hold->propagate_held) return;
+  hold->family = ctx->family();
+  switch (hold->family) {
+    case SensorFamily::kLikelihoodField: hold->fused = batch_member_fused(batch_lf_facts(ctx, step.lf)); break;
+    // (the wave-per-particle kernel, i.e. no ordering - `ordered` is the same question asked of the planner)
+    case SensorFamily::kBeam: hold->fused = !step.ordered && batch_beam_member_fused(batch_beam_facts(ctx)); break;
+    case SensorFamily::kNdt: hold->fused = batch_ndt_member_fused(batch_ndt_facts(ctx)); break;
+    case SensorFamily::kLandmark: hold->fused = batch_landmark_member_fused(batch_landmark_facts(ctx)); break;
+  }
+  if (!hold->fused) launch_held_propagate(ctx, hold);
+}
+
+// The families' own steps of do_reweight: each launches its kernel, or fills the record of a held cycle (the batch launches
+// k_batch_reweight_lf_beams, _beam, _ndt, _landmarks), and keeps its own counters.
+void reweight_lf(mcl_ctx* ctx, const ReweightStep& step) {
+  if (step.field_poses.rebuild_first && !step.held) {  // the set's poses were not written by a propagation of this map's: k_field_pose first
+    launch_field_pose(ctx->stream, ctx->cur().pose, ctx->n, ctx->field_pose_out());
+    ctx->facts.field_poses_written(ctx->map_generation);
+    ctx->field_pose_rebuilds += 1;
+  }
+  stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
+  LfLaunch launched{LfKernel::kBeams, 0};  // (what a held cycle counts: the batch's launch is k_reweight_lf_beams' body)
+  if (step.held) {
+    step.hold->item.f = step.lf.f;
+    step.hold->item.B = step.lf.B;
+    // (a held cycle's own propagation writes the field-frame poses in the batch's launch; without them the kernel forms the product)
+    step.hold->item.field_pose = step.field_poses.rebuild_first ? nullptr : step.lf.field_pose;
+  } else {
+    launched = launch_reweight_lf(ctx->stream, step.lf, ctx->tuning);
+  }
+  ctx->facts.lf_sums_left(launched.weight_sums);
+  switch (launched.kernel) {  // (the counters as include/beluga_mcl.h states them)
+    case LfKernel::kPatchQueue: ctx->lf_queue_launches += 1; [[fallthrough]];
+    case LfKernel::kPatch: ctx->lf_patch_launches += 1; ctx->lf_fast_launches += 1; break;
+    case LfKernel::kFarBeams: ctx->lf_far_beams_launches += 1; [[fallthrough]];
+    case LfKernel::kPaletteFar: ctx->lf_far_launches += 1; [[fallthrough]];
+    case LfKernel::kPaletteFast: ctx->lf_fast_launches += 1; break;
+    case LfKernel::kBeams: ctx->lf_beams_launches += 1; break;
+    default: break;
+  }
+  stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
+}
+// Not MCL_OK: the table of the ordered kernel could not be built (nothing was launched; the caller closes its stage).
+mcl_status reweight_beam(mcl_ctx* ctx, const ReweightStep& step) {
+  const mcl_beam_params& b = ctx->cfg.beam;
+  const BeamModel model{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range};
+  const bool use_table = step.ordered && ctx->tuning.beam_table != 0 && ctx->beam_table_count != 0;  // (only the ordered kernel reads it)
+  if (use_table && !ctx->beam_table_ready) {
+    hipError_t e = ctx->d_beam_table.ensure(4 * static_cast<size_t>(ctx->beam_table_count));
+    if (e == hipSuccess) {
+      launch_beam_table(ctx->stream, model, ctx->map->resolution, ctx->beam_table_count, ctx->d_beam_table.ptr);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("reweight (beam table): ") + hipGetErrorString(e));
+    ctx->beam_table_ready = true;
+  }
+  stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
+  if (step.held) {  // (never ordered, so no table was built above)
+    step.hold->item.B = static_cast<uint32_t>(step.B);
+    step.hold->item.beam = batch_beam_record(ctx->grid_view(), model, ctx->map->d_nonfree_bits.ptr, ctx->d_kld_scalars.ptr + kKldBeamSteps);
+  } else {
+    launch_reweight_beam(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model,
+                         ctx->d_points.ptr, static_cast<uint32_t>(step.B), ctx->d_kld_scalars.ptr + kKldBeamSteps, step.ordered ? &step.sort : nullptr,
+                         ctx->map->d_nonfree_bits.ptr, ctx->d_beam_points.ptr, use_table ? ctx->d_beam_table.ptr : nullptr,
+                         use_table ? ctx->beam_table_count : 0u, ctx->tuning.beam_free_ahead != 0, ctx->tuning.beam_sectors != 0);
+    // (launch_reweight_beam's own test; a fleet's shared launch is the batch's beam_launches, not these)
+    if (ctx->n != 0 && step.B != 0) (step.ordered ? ctx->beam_ordered_launches : ctx->beam_wave_launches) += 1;
+  }
+  stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
+  return MCL_OK;
+}
+void reweight_ndt(mcl_ctx* ctx, const ReweightStep& step) {
+  stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
+  const uint32_t cells = static_cast<uint32_t>(step.m.doubles / kNdtRecord);
+  if (step.held) {
+    step.hold->item.ndt = ctx->ndt_view;
+    step.hold->item.ndt_cells = cells;
+  } else {
+    launch_ndt_reweight(ctx, cells);
+  }
+  stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
+}
+void reweight_landmark(mcl_ctx* ctx, const ReweightStep& step) {
+  const uint32_t k = static_cast<uint32_t>(step.m.doubles / kLandmarkRecord);
+  stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
+  const bool bearing = ctx->cfg.sensor_kind == MCL_SENSOR_BEARING;
+  if (step.held) {
+    step.hold->item.landmark = ctx->landmark_view;
+    step.hold->item.landmark_k = k;
+    step.hold->item.landmark_bearing = bearing ? 1u : 0u;
+  }
+  if (step.held || landmark_reweight_takes_waves(ctx->landmark_small_cycle, ctx->n)) {
+    if (!step.held && bearing) launch_reweight_bearings_wave(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    else if (!step.held) launch_reweight_landmarks_wave(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    if (ctx->n != 0 && k != 0) ctx->landmark_wave_launches += 1;  // (no detection: no launch; a fleet's shared launch counts here too)
+  } else if (bearing) {
+    launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+  } else {
+    launch_reweight_landmarks(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+  }
+  stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
 }
 
 // points_staged: stage_points + the pull already happened (mcl_update); keys_ready: k_propagate emitted the ordering keys.
@@ -1021,6 +1185,7 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
 // weights in d_lf_wsum (facts.lf_sums() of them; 0 if another kernel ran).
 mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, bool keys_ready = false,
                        bool want_weight_sums = false, HeldCycle* hold = nullptr) {
+  const SensorFamily family = ctx->family();
   ctx->facts.lf_sums_dropped();
   if (const mcl_status s = reweight_preconditions(ctx, ctx->off_grid() ? 0 : m.doubles / 2)) return s;
   const bool unit_weights = ctx->facts.take_unit_weights() && ctx->tuning.lf_unit_weights != 0;
@@ -1031,141 +1196,32 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
       points_pulled(ctx, true);
     }
   }
-  const uint64_t B = ctx->off_grid() ? 0 : m.doubles / 2;  // the grid models' measurement is the scan itself: B points (as staged)
   stage_begin(ctx, MCL_STAGE_REWEIGHT);
   const LfPlanner::Mode mode = plan_lf(ctx);
   const bool ordered = ctx->wants_ordering();  // (asked while this cycle's mode is decided)
   const bool dispersed = ctx->lf_planner.gathers_dispersed(ctx->tuning);
   ctx->lf_planner.mode_consumed();  // the next cycle decides again
-  const SortScratch sort = ctx->sort_scratch();
+  ReweightStep step{.m = m, .B = ctx->off_grid() ? 0 : m.doubles / 2, .ordered = ordered, .dispersed = dispersed, .unit_weights = unit_weights,
+                    .want_weight_sums = want_weight_sums, .mode = mode, .sort = ctx->sort_scratch(), .hold = hold};
   const bool have_order = ctx->facts.take_order_accepted();  // (launch_order_ahead's, accepted by this cycle's propagation)
-  const bool lf_kind = !ctx->off_grid() && ctx->cfg.sensor_kind != MCL_SENSOR_BEAM;
-  LfReweightArgs lf_args{};
-  const FieldPosePlan field_poses = lf_kind ? field_pose_plan(ctx->tuning, ctx->d_field_pose.ptr != nullptr, ctx->facts, ctx->map_generation)
-                                            : FieldPosePlan{false, false};
-  if (lf_kind)
-    lf_args = LfReweightArgs{.p = ctx->cur(), .n = ctx->n, .f = ctx->field_view(), .d_points = ctx->d_points.ptr, .B = static_cast<uint32_t>(B),
-                             .sort = ordered ? &sort : nullptr, .patches = mode.patches, .beams = mode.beams,
-                             .dispersed = dispersed,
-                             .scan_cells = ctx->scan_extent / ctx->map->resolution, .unit_weights = unit_weights,
-                             .stats = PatchStats{reinterpret_cast<unsigned long long*>(ctx->d_scalars.ptr + kSlotPatchTotals),
-                                                 reinterpret_cast<unsigned long long*>(ctx->h_scalars.device + kSlotPatchMirror),
-                                                 static_cast<uint32_t>(ctx->tuning.lf_loose_below), ctx->tuning.lf_margin ? 0u : 1u,
-                                                 static_cast<uint32_t>(ctx->tuning.lf_split), want_weight_sums ? ctx->d_lf_wsum.ptr : nullptr,
-                                                 reinterpret_cast<unsigned int*>(ctx->d_scalars.ptr + kSlotPatchQueue)},
-                             .field_pose = field_poses.load ? ctx->d_field_pose.ptr : nullptr};
-  if (hold && hold->propagate_held) {  // mcl_batch_update: is this member's cycle the small one?  If not, its propagation goes out now
-    hold->fused = lf_kind && batch_member_fused(BatchMemberFacts{
-                                 ctx->cfg.sensor_kind, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0, ctx->n,
-                                 std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), lf_takes_beams(lf_args, ctx->tuning), ctx->profile != 0});
-    // (a beam member: the wave-per-particle kernel, i.e. no ordering - `ordered` is the same question asked of the planner)
-    hold->beam = !lf_kind && !ordered && batch_beam_member_fused(BatchBeamFacts{
-                                 ctx->cfg.sensor_kind, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
-                                 ctx->tuning.batch_beam_fused != 0, ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity),
-                                 static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles), ctx->profile != 0});
-    hold->ndt = ctx->is_ndt() && batch_ndt_member_fused(BatchNdtFacts{
-                                     ctx->cfg.sensor_kind, ctx->ndt_small_cycle, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
-                                     ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), ctx->have_ndt_map && !ctx->ndt_map_hashed, ctx->profile != 0});
-    hold->landmark = ctx->is_landmark() && batch_landmark_member_fused(BatchLandmarkFacts{
-                                     ctx->cfg.sensor_kind, ctx->landmark_small_cycle, ctx->have_comm && ctx->comm_world > 1, ctx->tuning.small_fused != 0,
-                                     ctx->n, std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity), ctx->profile != 0});
-    hold->fused = hold->fused || hold->beam || hold->ndt || hold->landmark;
-    if (!hold->fused) launch_held_propagate(ctx, hold);
-  }
+  if (family == SensorFamily::kLikelihoodField) plan_reweight_lf(ctx, &step);
+  decide_hold(ctx, step);
+  step.held = hold && hold->fused;
   if (ordered && !have_order) {
     KeyFrame frame{};
     // The ordering also serves the beam model: both kernels gather the pose records through sort.perm.
     const bool have_frame = !keys_ready && ctx->predict_key_frame(nullptr, &frame);
-    launch_order_particles(ctx->stream, ctx->cur(), ctx->n, &sort, have_frame ? &frame : nullptr, keys_ready, frame.layout);
+    launch_order_particles(ctx->stream, ctx->cur(), ctx->n, &step.sort, have_frame ? &frame : nullptr, keys_ready, frame.layout);
   }
-  if (ctx->is_ndt()) {
-    stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    const uint32_t cells = static_cast<uint32_t>(m.doubles / kNdtRecord);
-    if (hold && hold->fused) {  // (a held cycle: the batch launches k_batch_reweight_ndt)
-      hold->item.ndt = ctx->ndt_view;
-      hold->item.ndt_cells = cells;
-    } else {
-      launch_ndt_reweight(ctx, cells);
-    }
-    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
-  } else if (ctx->is_landmark()) {
-    const uint32_t k = static_cast<uint32_t>(m.doubles / kLandmarkRecord);
-    stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    const bool bearing = ctx->cfg.sensor_kind == MCL_SENSOR_BEARING;
-    const bool held = hold && hold->fused;
-    if (held) {  // (a held cycle: the batch launches k_batch_reweight_landmarks)
-      hold->item.landmark = ctx->landmark_view;
-      hold->item.landmark_k = k;
-      hold->item.landmark_bearing = bearing ? 1u : 0u;
-    }
-    if (held || landmark_reweight_takes_waves(ctx->landmark_small_cycle, ctx->n)) {
-      if (!held && bearing) launch_reweight_bearings_wave(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
-      else if (!held) launch_reweight_landmarks_wave(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
-      if (ctx->n != 0 && k != 0) ctx->landmark_wave_launches += 1;  // (no detection: no launch)
-    } else if (bearing) {
-      launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
-    } else {
-      launch_reweight_landmarks(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
-    }
-    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
-  } else if (ctx->cfg.sensor_kind != MCL_SENSOR_BEAM) {
-    const bool held = hold && hold->fused;
-    if (field_poses.rebuild_first && !held) {  // the set's poses were not written by a propagation of this map's: k_field_pose first
-      launch_field_pose(ctx->stream, ctx->cur().pose, ctx->n, ctx->field_pose_out());
-      ctx->facts.field_poses_written(ctx->map_generation);
-      ctx->field_pose_rebuilds += 1;
-    }
-    stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    LfLaunch launched{LfKernel::kBeams, 0};  // (a held cycle: the batch launches k_batch_reweight_lf_beams)
-    if (held) {
-      hold->item.f = lf_args.f;
-      hold->item.B = lf_args.B;
-      // (a held cycle's own propagation writes the field-frame poses in the batch's launch; without them the kernel forms the product)
-      hold->item.field_pose = field_poses.rebuild_first ? nullptr : lf_args.field_pose;
-    } else {
-      launched = launch_reweight_lf(ctx->stream, lf_args, ctx->tuning);
-    }
-    ctx->facts.lf_sums_left(launched.weight_sums);
-    switch (launched.kernel) {  // (the counters as include/beluga_mcl.h states them)
-      case LfKernel::kPatchQueue: ctx->lf_queue_launches += 1; [[fallthrough]];
-      case LfKernel::kPatch: ctx->lf_patch_launches += 1; ctx->lf_fast_launches += 1; break;
-      case LfKernel::kFarBeams: ctx->lf_far_beams_launches += 1; [[fallthrough]];
-      case LfKernel::kPaletteFar: ctx->lf_far_launches += 1; [[fallthrough]];
-      case LfKernel::kPaletteFast: ctx->lf_fast_launches += 1; break;
-      case LfKernel::kBeams: ctx->lf_beams_launches += 1; break;
-      default: break;
-    }
-    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
-  } else {
-    const mcl_beam_params& b = ctx->cfg.beam;
-    const BeamModel model{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range};
-    const bool use_table = ordered && ctx->tuning.beam_table != 0 && ctx->beam_table_count != 0;  // (only the ordered kernel reads it)
-    if (use_table && !ctx->beam_table_ready) {
-      hipError_t e = ctx->d_beam_table.ensure(4 * static_cast<size_t>(ctx->beam_table_count));
-      if (e == hipSuccess) {
-        launch_beam_table(ctx->stream, model, ctx->map->resolution, ctx->beam_table_count, ctx->d_beam_table.ptr);
-        e = hipGetLastError();
-      }
-      if (e != hipSuccess) {
-        stage_end(ctx, MCL_STAGE_REWEIGHT);  // (the stage opened above is closed on this way out as well)
-        return fail(ctx, MCL_ERR_HIP, std::string("reweight (beam table): ") + hipGetErrorString(e));
-      }
-      ctx->beam_table_ready = true;
-    }
-    stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    if (hold && hold->fused) {  // (a held cycle: the batch launches k_batch_reweight_beam; never ordered, so no table was built above)
-      hold->item.B = static_cast<uint32_t>(B);
-      hold->item.beam = batch_beam_record(ctx->grid_view(), model, ctx->map->d_nonfree_bits.ptr, ctx->d_kld_scalars.ptr + kKldBeamSteps);
-    } else {
-      launch_reweight_beam(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model,
-                           ctx->d_points.ptr, static_cast<uint32_t>(B), ctx->d_kld_scalars.ptr + kKldBeamSteps, ordered ? &sort : nullptr,
-                           ctx->map->d_nonfree_bits.ptr, ctx->d_beam_points.ptr, use_table ? ctx->d_beam_table.ptr : nullptr,
-                           use_table ? ctx->beam_table_count : 0u, ctx->tuning.beam_free_ahead != 0, ctx->tuning.beam_sectors != 0);
-      if (ctx->n != 0 && B != 0) (ordered ? ctx->beam_ordered_launches : ctx->beam_wave_launches) += 1;  // (launch_reweight_beam's own test)
-    }
-    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
+  mcl_status launched = MCL_OK;
+  switch (family) {
+    case SensorFamily::kLikelihoodField: reweight_lf(ctx, step); break;
+    case SensorFamily::kBeam: launched = reweight_beam(ctx, step); break;
+    case SensorFamily::kNdt: reweight_ndt(ctx, step); break;
+    case SensorFamily::kLandmark: reweight_landmark(ctx, step); break;
   }
   stage_end(ctx, MCL_STAGE_REWEIGHT);
+  if (launched != MCL_OK) return launched;  // (the beam table: the stage opened above is closed on this way out as well)
   ctx->profile_tick += 1;
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
     ctx->facts.lf_sums_dropped();  // (sums that no longer describe the weights must not reach a later normalisation)
@@ -1312,7 +1368,7 @@ struct ResampleOptions {
 mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t step, uint64_t* n_out, const ResampleOptions& opt = {}) {
   const mcl_amcl_params& a = ctx->cfg.amcl;
   MCL_REQUIRE(ctx, ctx->n > 0, "mcl_resample: empty particle set");
-  if (ctx->is_ndt()) {
+  if (ctx->family() == SensorFamily::kNdt) {
     // the random states of this draw (prepare_ndt_random: mcl_update prepares them before the recovery estimator's reset; the stage-level
     // mcl_resample here); a rejected covariance fails before any particle is overwritten
     MCL_REQUIRE(ctx, opt.d_random_state_probability == nullptr, "NDT model: the random state probability has to be known on the host");
@@ -1321,7 +1377,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
     ctx->ndt_random_ready = false;  // (used by this draw only)
   }
   ctx->facts.lf_sums_dropped();
-  const uint64_t max_p = std::min<uint64_t>(a.max_particles, ctx->capacity);
+  const uint64_t max_p = ctx->max_live();
   stage_begin(ctx, MCL_STAGE_RESAMPLE);
   if (!opt.cdf_ready)
     if (const mcl_status s = do_build_cdf(ctx, opt.normalized_just_now, opt.policy, opt.finalize_norm)) return s;
@@ -1831,7 +1887,7 @@ struct ClusterFront {
 mcl_status cluster_front_assign(mcl_ctx* ctx, const mcl_cluster_params& cp, ClusterFront* f);
 mcl_status cluster_front(mcl_ctx* ctx, const mcl_cluster_params& cp, bool allow_small, ClusterFront* f) {
   const uint64_t n = ctx->n;
-  f->sharded = ctx->have_comm && ctx->comm_world > 1;
+  f->sharded = ctx->sharded();
   if (n == 0 && !f->sharded) return fail(ctx, MCL_ERR_NOT_READY, "no particles");  // (an empty shard still takes part in the exchange)
   MCL_REQUIRE(ctx, cluster_params_ok(cp.linear_hash_resolution, cp.angular_hash_resolution, cp.weight_cap_percentile), "bad cluster parameters");
   MCL_REQUIRE(ctx, n < 0xFFFFFFFFull, "too many particles");
@@ -1879,7 +1935,7 @@ mcl_status do_cluster_estimate(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_e
 // Device: one pass over the set for all K (k_estimate_partials_clusters), the cells' table carrying the RANK of each cell's cluster.
 static_assert(MCL_MAX_CLUSTER_ESTIMATES == kMaxClusterRanks, "the kernel's rows are sized for the header's cap");
 mcl_status unsharded_only(mcl_ctx* ctx, const char* what) {
-  if (ctx->have_comm && ctx->comm_world > 1)
+  if (ctx->sharded())
     return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(what) + ": not on a sharded filter (the sums are not exchanged yet)");
   return MCL_OK;
 }
@@ -2531,7 +2587,7 @@ mcl_status mcl_set_map_async(mcl_ctx* ctx, const int8_t* cells, uint32_t width, 
   if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_map_async: not on a context whose sensor model has a map of its own (mcl_set_ndt_map, mcl_set_landmark_map)");
   MCL_REQUIRE(ctx, cells && origin && value_traits && width > 0 && height > 0 && resolution > 0, "mcl_set_map_async: bad argument");
   MCL_REQUIRE(ctx, static_cast<uint64_t>(width) * height < 0xFFFFFFFFull, "mcl_set_map_async: grid too large");
-  if (ctx->have_comm && ctx->comm_world > 1)
+  if (ctx->sharded())
     return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_map_async: not on a sharded filter (the ranks would swap maps in different cycles)");
   drop_pending_map(ctx);
   auto* p = new (std::nothrow) mcl_ctx::PendingMap();
@@ -2629,7 +2685,7 @@ void install_set(mcl_ctx* ctx, const InstallSet& s) {
   ctx->facts.set_replaced(s.unit_weights, s.pivot_kept);
   ctx->n = s.n;
   if (s.global == InstallSet::kGlobalShares) ctx->global_n = 0;
-  if (s.global != InstallSet::kGlobalKept) ctx->global_n_unknown = s.global == InstallSet::kGlobalAsked && ctx->have_comm && ctx->comm_world > 1;
+  if (s.global != InstallSet::kGlobalKept) ctx->global_n_unknown = s.global == InstallSet::kGlobalAsked && ctx->sharded();
   if (s.force_update) ctx->force_update = true;
   if (s.cloud == InstallSet::kCloudGiven) ctx->cloud.set(s.cloud_mean, s.cloud_sigma);
   else if (s.cloud == InstallSet::kCloudUnknown) ctx->cloud.forget();
@@ -2785,7 +2841,7 @@ mcl_status mcl_initialize_normal(mcl_ctx* ctx, const double mean_xytheta[3], con
   double T[9];
   if (!covariance_to_transform(cov, T)) return fail(ctx, MCL_ERR_BAD_COVARIANCE, "Invalid covariance matrix");
   if (const mcl_status s = bind_device(ctx)) return s;
-  const uint64_t n = std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity);  // take_exactly(max_particles)
+  const uint64_t n = ctx->max_live();  // take_exactly(max_particles)
   ctx->facts.weights_rewrite_begins();
   launch_init_normal(ctx->stream, ctx->cur(), n, mean_xytheta, T, ctx->cfg.seed, ctx->cfg.shard_offset);
   MCL_HIP(ctx, hipGetLastError());
@@ -2810,7 +2866,7 @@ mcl_status mcl_set_particles(mcl_ctx* ctx, const double* states, const double* w
   // the pivot: the first state that carries weight lies within the set; a shard's first state is another on every rank
   uint64_t first = 0;
   while (first < n && !(weights[first] > 0.0)) ++first;
-  const bool sharded = ctx->have_comm && ctx->comm_world > 1;
+  const bool sharded = ctx->sharded();
   const bool pivot_known = first < n && !sharded;
   install_set(ctx, {.n = n, .unit_weights = false, .global = InstallSet::kGlobalAsked, .force_update = true, .cloud = InstallSet::kCloudUnknown,
                     .patches = LfPlanner::Installed::kFresh, .pivot_known = pivot_known,
@@ -2855,7 +2911,7 @@ mcl_status mcl_reweight(mcl_ctx* ctx, const double* points_xy, uint64_t num_poin
   if (ctx->is_landmark()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_reweight: a landmark or bearing context takes mcl_reweight_landmarks / mcl_reweight_bearings");
   MCL_REQUIRE(ctx, num_points == 0 || points_xy, "null points");
   if (const mcl_status s = bind_device(ctx)) return s;
-  if (ctx->is_ndt()) {
+  if (ctx->family() == SensorFamily::kNdt) {
     if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
     return do_reweight(ctx, ndt_fit_scan(ctx, points_xy, num_points));
   }
@@ -2915,7 +2971,7 @@ static SmallTail small_tail_record(const mcl_ctx* ctx, bool fires) {
   t.src = ctx->cur();
   t.dst = ctx->other();
   t.n = static_cast<uint32_t>(ctx->n);
-  t.max_particles = static_cast<uint32_t>(std::min<uint64_t>(ap.max_particles, ctx->capacity));
+  t.max_particles = static_cast<uint32_t>(ctx->max_live());
   t.min_particles = static_cast<uint32_t>(std::min<uint64_t>(ap.min_particles, t.max_particles));
   t.seed = ctx->cfg.seed;
   t.step = ctx->step;
@@ -2930,7 +2986,7 @@ static SmallTail small_tail_record(const mcl_ctx* ctx, bool fires) {
   t.hp = HashParams{ap.spatial_resolution_x, ap.spatial_resolution_y, ap.spatial_resolution_theta};
   t.g = ctx->grid_view();
   t.fc = ctx->random_source();
-  if (ctx->is_ndt()) {  // a cycle that would inject random states is handed back: the tail itself draws none
+  if (ctx->family() == SensorFamily::kNdt) {  // a cycle that would inject random states is handed back: the tail itself draws none
     t.fc = FreeCells{nullptr, 0};
     t.hand_back = true;
   }
@@ -2963,7 +3019,7 @@ static mcl_update_info small_cycle_state(mcl_ctx* ctx) {
   ctx->slow.output = h[kSlotSlow];
   ctx->fast.output = h[kSlotFast];
   ctx->force_update = false;  // :199
-  if (ctx->is_ndt()) ctx->ndt_small_completed += 1;
+  if (ctx->family() == SensorFamily::kNdt) ctx->ndt_small_completed += 1;
   // (what the info reports, before another kernel's mirrored values take their place)
   return mcl_update_info{1, resampled, ctx->n, h[kSlotWeightSum], h[kSlotEss], h[kSlotPolicyP]};
 }
@@ -2974,7 +3030,9 @@ static mcl_status small_cycle_estimate(mcl_ctx* ctx, mcl_estimate* est) {
 }
 // An NDT cycle that the tail handed back (SmallTail::hand_back): it resamples with a random state probability > 0.  Behind the
 // synchronisation the set is normalised, the mirror holds the policies' scalars, nothing has been drawn.
-static bool small_cycle_handed_back(const mcl_ctx* ctx) { return ctx->is_ndt() && ctx->h_scalars.host[kSlotHandBack] != 0.0; }
+static bool small_cycle_handed_back(const mcl_ctx* ctx) {
+  return ctx->family() == SensorFamily::kNdt && ctx->h_scalars.host[kSlotHandBack] != 0.0;
+}
 // The host's end of such a cycle - the general path's own steps from :182 on: the generator of the random states, the recovery filters'
 // reset, the draw, the estimate.  The CDF adds its own chunk sums (the tail left none in d_chunk: normalized_just_now stays false).  A
 // refused generator returns MCL_ERR_BAD_COVARIANCE with the state the general path leaves (ndt_hand_back_taken, cycle_host.h).
@@ -3016,6 +3074,15 @@ static mcl_status finish_small_cycle(mcl_ctx* ctx, mcl_estimate* estimate, mcl_u
   return MCL_OK;
 }
 
+// Is this cycle the small one - everything behind the reweight in one launch of k_small_tail?  Each family's own rule (cycle_host.h).
+static bool cycle_is_small(const mcl_ctx* ctx) {
+  switch (ctx->family()) {
+    case SensorFamily::kNdt: return ndt_cycle_is_small(ctx->ndt_cycle_facts());
+    case SensorFamily::kLandmark: return landmark_cycle_is_small(ctx->landmark_cycle_facts());
+    default: return grid_cycle_is_small(GridCycleFacts{ctx->tuning.small_fused != 0, ctx->n, ctx->max_live()});
+  }
+}
+
 // Amcl::update (amcl_core.hpp:165-201) over the scan's points, or the detection records of a landmark / bearing context
 // (mcl_update_landmarks, mcl_update_bearings).
 // hold (mcl_batch_update): where the cycle turns out to be the small one, nothing is launched and the cycle stops behind its prepare
@@ -3042,13 +3109,13 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   if (const mcl_status s = bind_device(ctx)) return s;
   if (const mcl_status s = reweight_preconditions(ctx, m.doubles / 2)) return s;
   ctx->lf_planner.cycle_begins();  // whatever an earlier, failed cycle left behind
-  if (ctx->have_comm && ctx->comm_world > 1) {
+  if (ctx->sharded()) {
     // before any rank-local state moves: the ranks must not diverge
     if (const mcl_status s = sharded_preconditions(ctx)) return s;
     consume_motion();
     return sharded_update(ctx, pose, m, estimate, info);
   }
-  if (ctx->is_ndt()) m = ndt_fit_scan(ctx, m.data, m.doubles / 2);  // the scan's measurement cells are what the cycle uploads
+  if (ctx->family() == SensorFamily::kNdt) m = ndt_fit_scan(ctx, m.data, m.doubles / 2);  // the scan's measurement cells are what the cycle uploads
   if (const mcl_status s = stage_points(ctx, &m)) return s;
   consume_motion();
   advance_window(ctx, pose);
@@ -3061,8 +3128,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   const mcl_amcl_params& ap = ctx->cfg.amcl;
   // (not the NDT model: its random states need the estimate of the normalised set where the probability is > 0, a host decision; the
   // landmark and bearing models follow it)
-  const bool device_policy = !ap.selective_resampling && ap.min_particles >= std::min<uint64_t>(ap.max_particles, ctx->capacity) &&
-                             ctx->tuning.device_policy != 0 && !ctx->off_grid();
+  const bool device_policy = !ap.selective_resampling && ap.min_particles >= ctx->max_live() && ctx->tuning.device_policy != 0 && !ctx->off_grid();
   // (the normalisation follows at once: the LF kernel leaves the sums it is built on)
   if (const mcl_status s = do_reweight(ctx, m, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0, hold)) return s;  // :176
   // Small sets (the reference's own sizes): everything behind the reweight in ONE launch of one workgroup and one synchronisation
@@ -3071,10 +3137,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   const bool fires = every_n == 0;
   // (an NDT context only with its switch on, mcl_set_ndt_small_cycle: the tail hands a cycle that would inject random states back)
   // (a landmark or bearing context likewise, mcl_set_landmark_small_cycle: its random states come from the map's box, inside the tail)
-  const bool small = ctx->is_ndt()        ? ndt_cycle_is_small(ctx->ndt_cycle_facts())
-                     : ctx->is_landmark() ? landmark_cycle_is_small(ctx->landmark_cycle_facts())
-                                   : ctx->tuning.small_fused != 0 && !ctx->off_grid() && ctx->n <= 4096 &&
-                                         std::min<uint64_t>(ap.max_particles, ctx->capacity) <= 4096;
+  const bool small = cycle_is_small(ctx);
   if (hold && hold->fused) {  // the batch launches this cycle and finishes it
     if (!small) return fail(ctx, MCL_ERR_HIP, "mcl_batch_update: a held cycle is not a small one");
     hold->item.tail = small_tail_args(small_tail_record(ctx, fires));
@@ -3130,7 +3193,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
     ctx->every_n_current = every_n;
     decision = host_policy(ctx->slow, ctx->fast, ap.selective_resampling != 0, fires, stats.norm_sum, stats.norm_sumsq, ctx->n);  // :179, :181
     if (decision.resample) {
-      if (ctx->is_ndt())  // :182, the random state generator of ndt_amcl_node (its failure leaves the state the reference's throw leaves)
+      if (ctx->family() == SensorFamily::kNdt)  // :182, the random state generator of ndt_amcl_node (its failure leaves the state the reference's throw leaves)
         if (const mcl_status s = prepare_ndt_random(ctx, decision.random_state_probability)) return s;
       if (decision.random_state_probability > 0.0) {  // :184-186
         ctx->slow.reset();
@@ -3263,16 +3326,18 @@ mcl_status batch_launch(mcl_batch* b) {
     const HeldCycle& held = b->held[b->fused[k]];
     const BatchItem& it = held.item;
     b->fused_n[k] = it.n;
-    b->fused_lds[k] = (held.beam || held.ndt || held.landmark) ? 0u : static_cast<uint32_t>(lf_palette_lds(it.f));
-    b->landmark_n[k] = held.landmark ? it.n : 0;
-    b->landmark_k[k] = held.landmark ? it.landmark_k : 0u;
-    any_landmark = any_landmark || held.landmark;
-    b->ndt_n[k] = held.ndt ? it.n : 0;
-    b->ndt_cells[k] = held.ndt ? it.ndt_cells : 0u;
-    any_ndt = any_ndt || held.ndt;
-    b->beam_n[k] = held.beam ? it.n : 0;
-    b->beam_B[k] = held.beam ? it.B : 0u;
-    any_beam = any_beam || held.beam;
+    const bool lf = held.family == SensorFamily::kLikelihoodField, landmark = held.family == SensorFamily::kLandmark;
+    const bool ndt = held.family == SensorFamily::kNdt, beam = held.family == SensorFamily::kBeam;
+    b->fused_lds[k] = lf ? static_cast<uint32_t>(lf_palette_lds(it.f)) : 0u;
+    b->landmark_n[k] = landmark ? it.n : 0;
+    b->landmark_k[k] = landmark ? it.landmark_k : 0u;
+    any_landmark = any_landmark || landmark;
+    b->ndt_n[k] = ndt ? it.n : 0;
+    b->ndt_cells[k] = ndt ? it.ndt_cells : 0u;
+    any_ndt = any_ndt || ndt;
+    b->beam_n[k] = beam ? it.n : 0;
+    b->beam_B[k] = beam ? it.B : 0u;
+    any_beam = any_beam || beam;
   }
   BatchGrid grid = batch_layout(b->fused_n.data(), b->fused_lds.data(), count, b->first_propagate.data(), b->first_reweight.data());
   BatchBeamGrid beam{0, 0};
@@ -3561,9 +3626,12 @@ mcl_status batch_update_driver(mcl_batch* batch, mcl_estimate* estimates, mcl_up
       if (status[i] != MCL_OK) continue;
       finish_cycle(ctx, est[i], report[i], estimates ? &estimates[i] : nullptr, infos ? &infos[i] : nullptr);
       batch->members_fused += 1;
-      if (batch->held[i].beam) batch->members_beam_fused += 1;
-      if (batch->held[i].ndt) batch->members_ndt_fused += 1;
-      if (batch->held[i].landmark) batch->members_landmark_fused += 1;
+      switch (batch->held[i].family) {
+        case SensorFamily::kLikelihoodField: break;  // (members_fused alone)
+        case SensorFamily::kBeam: batch->members_beam_fused += 1; break;
+        case SensorFamily::kNdt: batch->members_ndt_fused += 1; break;
+        case SensorFamily::kLandmark: batch->members_landmark_fused += 1; break;
+      }
       any_updated = true;
     }
   }
@@ -3933,11 +4001,12 @@ mcl_status mcl_estimate_sums_device(mcl_ctx* ctx, const double pivot_xy[2], doub
 mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   ctx->facts.set_changes();
-  if (ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_initialize_from_map: not on an NDT context (its map comes from mcl_set_ndt_map)");
-  if (ctx->is_landmark()) {  // uniformly over the x-y extent of the map's boundaries: the generator of the recovery's random states, step 0
+  const SensorFamily family = ctx->family();
+  if (family == SensorFamily::kNdt) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_initialize_from_map: not on an NDT context (its map comes from mcl_set_ndt_map)");
+  if (family == SensorFamily::kLandmark) {  // uniformly over the x-y extent of the map's boundaries: the generator of the recovery's random states, step 0
     if (!ctx->have_landmark_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no landmark map set (mcl_set_landmark_map)");
     if (const mcl_status s = bind_device(ctx)) return s;
-    const uint64_t n = std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity);
+    const uint64_t n = ctx->max_live();
     launch_init_from_map(ctx->stream, ctx->cur(), n, ctx->cfg.seed, ctx->cfg.shard_offset, ctx->grid_view(), ctx->landmark_random);
     MCL_HIP(ctx, hipGetLastError());
     install_set(ctx, {.n = n, .unit_weights = true, .global = InstallSet::kGlobalShares, .force_update = true, .cloud = InstallSet::kCloudKept,
@@ -3947,7 +4016,7 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "mcl_initialize_from_map: no map set");
   MCL_REQUIRE(ctx, ctx->map->n_free > 0, "mcl_initialize_from_map: the map has no free cell");  // the reference asserts (:136)
   if (const mcl_status s = bind_device(ctx)) return s;
-  const uint64_t n = std::min<uint64_t>(ctx->cfg.amcl.max_particles, ctx->capacity);  // take_exactly(max_particles)
+  const uint64_t n = ctx->max_live();  // take_exactly(max_particles)
   ctx->facts.weights_rewrite_begins();
   launch_init_from_map(ctx->stream, ctx->cur(), n, ctx->cfg.seed, ctx->cfg.shard_offset, ctx->grid_view(),
                        FreeCells{ctx->map->d_free.ptr, ctx->map->n_free});
@@ -3970,14 +4039,14 @@ mcl_status mcl_initialize_from_map(mcl_ctx* ctx) {
 mcl_status mcl_has_likelihood_field(const mcl_ctx* ctx, int32_t* has) {
   if (!ctx || !has) return MCL_ERR_INVALID_ARGUMENT;
   // beam_model.hpp and ndt_sensor_model.hpp have no likelihood_field() (has_likelihood_field_v)
-  *has = ctx->cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD || ctx->cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB ? 1 : 0;
+  *has = ctx->family() == SensorFamily::kLikelihoodField ? 1 : 0;
   return MCL_OK;
 }
 
 mcl_status mcl_get_likelihood_field_origin(mcl_ctx* ctx, double origin[4]) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, origin, "null output");
-  if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM || ctx->off_grid())
+  if (ctx->family() != SensorFamily::kLikelihoodField)
     return fail(ctx, MCL_ERR_UNSUPPORTED, "The current sensor model does not support likelihood field");
   if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, "no likelihood field");
   // likelihood_field_model_base.hpp:105: world_to_likelihood_field_transform_.inverse(), i.e. inverse(inverse(grid.origin()))

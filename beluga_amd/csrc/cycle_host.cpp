@@ -22,6 +22,16 @@ bool off_grid(int sensor_kind) {
 
 }  // namespace
 
+SensorFamily sensor_family(int sensor_kind) {
+  switch (sensor_kind) {
+    case MCL_SENSOR_BEAM: return SensorFamily::kBeam;
+    case MCL_SENSOR_NDT: return SensorFamily::kNdt;
+    case MCL_SENSOR_LANDMARK:
+    case MCL_SENSOR_BEARING: return SensorFamily::kLandmark;
+    default: return SensorFamily::kLikelihoodField;  // MCL_SENSOR_LIKELIHOOD_FIELD, MCL_SENSOR_LIKELIHOOD_FIELD_PROB
+  }
+}
+
 // ---- motion --------------------------------------------------------------------------------------------------------------------------
 
 DiffDriveSampler make_sampler(const Pose2& pose, const Pose2& prev, const mcl_diffdrive_params& a, int kind, double alpha5) {
@@ -311,6 +321,10 @@ HostPolicy host_policy(ExponentialFilter& slow, ExponentialFilter& fast, bool se
 }
 
 // ---- particle shards -----------------------------------------------------------------------------------------------------------------
+
+bool grid_cycle_is_small(const GridCycleFacts& f) {
+  return f.small_fused && f.n <= kSmallCycleMaxParticles && f.max_particles <= kSmallCycleMaxParticles;
+}
 
 bool ndt_cycle_is_small(const NdtCycleFacts& f) {
   return f.small_cycle && f.small_fused && !f.profiling && f.n >= 1 && f.n <= kSmallCycleMaxParticles && f.max_particles >= 1 &&

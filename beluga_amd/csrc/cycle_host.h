@@ -195,9 +195,21 @@ struct HostPolicy {
 HostPolicy host_policy(ExponentialFilter& slow, ExponentialFilter& fast, bool selective_resampling, bool fires, double norm_sum,
                        double norm_sumsq, uint64_t n);
 
+// ---- the small cycle of a likelihood-field or beam context ---------------------------------------------------------------------------
+// Does everything behind the reweight run in one launch of one workgroup and one synchronisation (k_small_tail, option small_fused)?
+// One workgroup holds the set and the candidates of a resampling: the size rule the other families' small cycles share.  (A cycle
+// reaches the question with n >= 1; where k_small_tail refuses its record - no particle may be kept - the large path takes over.)
+struct GridCycleFacts {
+  bool small_fused;        // option small_fused
+  uint64_t n;              // particles of the live set
+  uint64_t max_particles;  // min(max_particles, capacity)
+};
+constexpr uint64_t kSmallCycleMaxParticles = 4096;
+bool grid_cycle_is_small(const GridCycleFacts& f);
+
 // ---- the small cycle of an NDT context (mcl_set_ndt_small_cycle) ----------------------------------------------------------------------
 // Does this NDT cycle run k_propagate_small, k_reweight_ndt_wave, k_small_tail with one synchronisation?  The size rule is the
-// likelihood-field small cycle's (one workgroup of k_small_tail holds the set and the candidates of a resampling).
+// likelihood-field small cycle's.
 struct NdtCycleFacts {
   bool small_cycle;        // the context's switch
   bool small_fused;        // option small_fused
@@ -205,7 +217,6 @@ struct NdtCycleFacts {
   uint64_t n;              // particles of the live set
   uint64_t max_particles;  // min(max_particles, capacity)
 };
-constexpr uint64_t kSmallCycleMaxParticles = 4096;
 bool ndt_cycle_is_small(const NdtCycleFacts& f);
 // The wave-per-particle kernel for a stage-level reweight (mcl_reweight, mcl_reweight_ndt_cells)?
 inline bool ndt_reweight_takes_waves(bool small_cycle, uint64_t n) { return small_cycle && n <= kSmallCycleMaxParticles; }

@@ -7,6 +7,12 @@
 
 namespace mcl {
 
+// The sensor models by what their update cycle runs: one family, one arm at every place that asks which model a context has
+// ("Adding a sensor family").  Every MCL_SENSOR_* value (sensor_kind) has exactly one; a value outside them, which
+// mcl_create refuses, answers kLikelihoodField, the arm such a kind has always fallen to.  (cycle_host.cpp)
+enum class SensorFamily : uint8_t { kLikelihoodField, kBeam, kNdt, kLandmark };
+SensorFamily sensor_family(int sensor_kind);
+
 // Per-cycle constants of the motion model's sampling function (computed on the host from the control action).
 //   differential   : three (mean, stddev) pairs: first rotation, translation, second rotation
 //   omnidirectional: (mean, stddev) of the rotation and of the translation, stddev of the strafe, first rotation

@@ -4,6 +4,7 @@ function returned.  The motion sampler, the covariance transform, the planner of
 policies and the shard arithmetic are checked against restatements written here and against the oracle, without a GPU."""
 import math
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -28,6 +29,8 @@ DRIVER = r"""
 //   capacity n world permille                                                    -> the capacity
 //   block    pos cnt n_out world                                                 -> per rank: out0 send[world] recv[world]
 //   planner  events ...   (below)                                                -> a line per event
+//   family   sensor_kind                                                         -> 0 .. 3 (SensorFamily, in its declared order)
+//   gridsmall small_fused n max_particles                                        -> 0 / 1 (grid_cycle_is_small)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -194,6 +197,12 @@ int main(int argc, char** argv) {
     const uint64_t n = uword();
     const uint32_t world = static_cast<uint32_t>(uword()), permille = static_cast<uint32_t>(uword());
     std::printf("%llu\n", static_cast<unsigned long long>(padded_capacity(n, world, permille)));
+  } else if (what == "family") {
+    std::printf("%d\n", static_cast<int>(sensor_family(static_cast<int>(word()))));
+  } else if (what == "gridsmall") {
+    GridCycleFacts f{};
+    f.small_fused = word() != 0, f.n = uword(), f.max_particles = uword();
+    std::printf("%d\n", grid_cycle_is_small(f) ? 1 : 0);
   } else if (what == "block") {
     const uint64_t pos = uword(), cnt = uword(), n_out = uword();
     const uint32_t world = static_cast<uint32_t>(uword());
@@ -213,16 +222,19 @@ int main(int argc, char** argv) {
 """
 
 
-@pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    d = tmp_path_factory.mktemp("cycle_host")
+def _compile(d, name, extra):
     src = d / "driver.cpp"
     src.write_text(DRIVER)
-    exe = d / "driver"
+    exe = d / name
     csrc = os.path.join(ROOT, "beluga_amd", "csrc")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-I", csrc, "-I", os.path.join(ROOT, "include"), str(src),
-                           os.path.join(csrc, "cycle_host.cpp"), "-o", str(exe)])
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror"] + extra +
+                          ["-I", csrc, "-I", os.path.join(ROOT, "include"), str(src), os.path.join(csrc, "cycle_host.cpp"), "-o", str(exe)])
     return str(exe)
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    return _compile(tmp_path_factory.mktemp("cycle_host"), "driver", [])
 
 
 def _arg(v):
@@ -905,3 +917,45 @@ def test_rebalance_blocks_agree_between_every_pair_of_ranks(driver, world):
                     slices = bounds(driver, cnt, world)
                     assert sum(send[r]) == 32 * _overlap(pos + slices[r][0], pos + slices[r][0] + slices[r][1], 0, n_out)
             assert received == [32 * count for _, count in new]
+
+
+# ---- which family a sensor kind belongs to, and the grid models' small cycle ----------------------------------------------------------------
+LIKELIHOOD_FIELD, BEAM, NDT, LANDMARK = 0, 1, 2, 3  # SensorFamily, in its declared order (cycle_types.h)
+# MCL_SENSOR_* (include/beluga_mcl.h) -> its one family
+FAMILY_OF = {0: LIKELIHOOD_FIELD, 1: BEAM, 2: LIKELIHOOD_FIELD, 3: NDT, 4: LANDMARK, 5: LANDMARK}
+
+
+def test_the_sensor_kinds_of_the_header_are_the_six_of_the_table():
+    """A kind added to the header is a kind to add to FAMILY_OF (and to sensor_family)."""
+    header = open(os.path.join(ROOT, "include", "beluga_mcl.h")).read()
+    declared = re.findall(r"\bMCL_SENSOR_(\w+) = (\d+)", header)
+    assert declared == [("LIKELIHOOD_FIELD", "0"), ("BEAM", "1"), ("LIKELIHOOD_FIELD_PROB", "2"), ("NDT", "3"), ("LANDMARK", "4"), ("BEARING", "5")]
+    assert sorted(FAMILY_OF) == [int(value) for _, value in declared]
+
+
+@pytest.mark.parametrize("kind", sorted(FAMILY_OF))
+def test_every_sensor_kind_has_its_one_family(driver, kind):
+    assert call(driver, "family", kind) == [[FAMILY_OF[kind]]]
+
+
+@pytest.mark.parametrize("kind", [-1, 6, 1 << 20])
+def test_a_kind_outside_the_six_answers_the_likelihood_field_family(driver, kind):
+    """mcl_create refuses such a kind; the function still answers, with the arm those kinds have always fallen to."""
+    assert call(driver, "family", kind) == [[LIKELIHOOD_FIELD]]
+
+
+@pytest.mark.parametrize("small_fused", [0, 1])
+@pytest.mark.parametrize("max_live", [4096, 4097])
+@pytest.mark.parametrize("n", [0, 1, 4096, 4097])
+def test_grid_cycle_is_small_at_the_edges(driver, n, max_live, small_fused):
+    """Restated: the option is on, and the set and the most particles a resampling may leave both fit one workgroup of k_small_tail."""
+    want = int(small_fused != 0 and n <= 4096 and max_live <= 4096)
+    assert call(driver, "gridsmall", small_fused, n, max_live) == [[want]]
+
+
+def test_driver_under_address_and_undefined_behaviour_sanitizers(tmp_path):
+    exe = _compile(tmp_path, "driver_san", ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+    for args in ([["family", k] for k in (-1, 0, 1, 2, 3, 4, 5, 6)] + [["gridsmall", 1, 4096, 4096], ["gridsmall", 1, 4097, 4096], ["gridsmall", 0, 0, 4097]] +
+                 [["bounds", 1000, 3], ["capacity", 1000000, 8, 1063], ["everyn", 3, 4]]):
+        done = subprocess.run([exe] + [str(a) for a in args], capture_output=True, text=True)
+        assert done.returncode == 0 and "runtime error" not in done.stderr and "AddressSanitizer" not in done.stderr, (args, done.stderr)
