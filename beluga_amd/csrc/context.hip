@@ -93,6 +93,8 @@ struct mcl_ctx {
   bool beam_table_ready{false};        // d_beam_table holds the table of the current map (built lazily: do_reweight)
   uint64_t beam_wave_launches{0};      // lone launches of k_reweight_beam (a wave per particle) and of k_reweight_beam_sorted (ordered lanes):
   uint64_t beam_ordered_launches{0};   // mcl_get_counter; a fleet's shared k_batch_reweight_beam is the batch's beam_launches, not these
+  uint64_t ndt_lane_launches{0};       // lone NDT reweight launches of the lane-per-particle kernels and of the wave-per-particle ones, either
+  uint64_t ndt_wave_launches{0};       // layout (launch_ndt_reweight; mcl_get_counter); a fleet's shared launch is mcl_ndt_batch_counts, not these
   HostBuffer<double> h_points;  // pinned, mapped
   double scan_extent{0.0};     // max |x| + |y| of the staged scan points
   uint64_t scan_no_cell{0};    // points of the scan taken out where it was staged: NaN or infinite, without a cell for any pose (FieldView::acc0)
@@ -731,6 +733,7 @@ void ndt_install_view(mcl_ctx* ctx, const NdtGridShape& g, const mcl_ndt_params&
 // by the size of the set (mcl_update, mcl_reweight and mcl_reweight_ndt_cells all come through here).
 void launch_ndt_reweight(mcl_ctx* ctx, uint32_t cells) {
   const bool waves = ndt_reweight_takes_waves(ctx->ndt_small_cycle, ctx->n);
+  if (ctx->n != 0 && cells != 0) (waves ? ctx->ndt_wave_launches : ctx->ndt_lane_launches) += 1;  // (an empty set or scan: not counted)
   if (ctx->ndt_map_hashed) {
     if (waves) launch_reweight_ndt_wave_hashed(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_hash_view, ctx->d_points.ptr, cells);
     else launch_reweight_ndt_hashed(ctx->stream, ctx->cur(), ctx->n, ctx->ndt_hash_view, ctx->d_points.ptr, cells);
@@ -4109,6 +4112,8 @@ constexpr Counter kCounters[] = {
     {"landmark_wave_launches", &mcl_ctx::landmark_wave_launches},
     {"beam_wave_launches", &mcl_ctx::beam_wave_launches},
     {"beam_ordered_launches", &mcl_ctx::beam_ordered_launches},
+    {"ndt_lane_launches", &mcl_ctx::ndt_lane_launches},
+    {"ndt_wave_launches", &mcl_ctx::ndt_wave_launches},
     {"estimate_repivots", &mcl_ctx::estimate_repivots},
     {"noise_ahead_used", &mcl_ctx::noise_ahead_used},
     {"order_ahead_used", &mcl_ctx::order_ahead_used},

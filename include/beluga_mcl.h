@@ -858,6 +858,9 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *   beam_wave_launches / beam_ordered_launches = a beam context's own reweight launches of the wave-per-particle kernel / of the
  *   ordered-lanes kernel (beam_sort_min_particles decides; no launch for an empty set or scan; a fleet's shared launch counts in the
  *   batch's beam_launches instead);
+ *   ndt_lane_launches / ndt_wave_launches = an NDT context's own reweight launches of the lane-per-particle kernel / of the
+ *   wave-per-particle kernel, in either map layout (mcl_set_ndt_small_cycle and the size of the set decide; not counted for an empty set
+ *   or a scan without a measurement cell; a fleet's shared launch counts in mcl_ndt_batch_counts instead);
  *   cluster_cells = occupied cells of the last cluster_based_estimate; comm_ranks_seen (ncclCommCount of the library's communicator, 0
  *   without one), comm_collectives, comm_bytes_out (running totals of this rank), comm_backend (0 = none, 1 = the caller's transport, 2 = RCCL inside the library). */
 mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value);

@@ -1,6 +1,10 @@
 """The 2D NDT sensor model on the GPU (ndt_kernels.hip through the C ABI) against the numpy restatement of the reference
 (tests/ndt_reference.py) and the CPU oracle's cycle stages.  Tolerances as in test_gpu_parity.py: weights relative 1e-12,
-resampling counts and KLD cut bit-exact, ancestors except at CDF-step ties, estimates 1e-9."""
+resampling counts and KLD cut bit-exact, ancestors except at CDF-step ties, estimates 1e-9.
+
+These tests draw random poses and scans: they cover real maps through the measurement fit, every kernel shape, large n (to 1M
+particles) and whole cycles, but a random pose never puts a transformed mean on a cell edge.  The cell CHOICE - edges, the centre box,
+the ends of int32, singular sums - is held by tests/test_gpu_ndt_edges.py against ndt_reference.weights_exact, with a derived tolerance."""
 import math
 import os
 import subprocess
