@@ -295,6 +295,7 @@ struct mcl_ctx {
   FreeCells landmark_random{nullptr, 0};
   std::vector<double> h_landmark_meas;  // the detections, kLandmarkRecord doubles each (what stage_points uploads)
   bool landmark_small_cycle{false};     // mcl_set_landmark_small_cycle: the wave-per-particle reweight and the one-launch tail for small sets
+  uint64_t landmark_lane_launches{0};   // lone launches of k_reweight_landmarks / k_reweight_bearings (mcl_get_counter)
   uint64_t landmark_wave_launches{0};   // launches of k_reweight_landmarks_wave / k_reweight_bearings_wave, a fleet's shared one included (mcl_get_counter)
   LandmarkCycleFacts landmark_cycle_facts() const {
     return LandmarkCycleFacts{landmark_small_cycle, tuning.small_fused != 0, profile != 0, n, max_live()};
@@ -1175,10 +1176,10 @@ void reweight_landmark(mcl_ctx* ctx, const ReweightStep& step) {
     if (!step.held && bearing) launch_reweight_bearings_wave(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
     else if (!step.held) launch_reweight_landmarks_wave(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
     if (ctx->n != 0 && k != 0) ctx->landmark_wave_launches += 1;  // (no detection: no launch; a fleet's shared launch counts here too)
-  } else if (bearing) {
-    launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
   } else {
-    launch_reweight_landmarks(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    if (bearing) launch_reweight_bearings(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    else launch_reweight_landmarks(ctx->stream, ctx->cur(), ctx->n, ctx->landmark_view, ctx->d_points.ptr, k);
+    if (ctx->n != 0 && k != 0) ctx->landmark_lane_launches += 1;  // (the launchers' own test)
   }
   stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
 }
@@ -4109,6 +4110,7 @@ constexpr Counter kCounters[] = {
     {"lf_far_launches", &mcl_ctx::lf_far_launches},
     {"lf_far_beams_launches", &mcl_ctx::lf_far_beams_launches},
     {"small_tail_launches", &mcl_ctx::small_tail_launches},
+    {"landmark_lane_launches", &mcl_ctx::landmark_lane_launches},
     {"landmark_wave_launches", &mcl_ctx::landmark_wave_launches},
     {"beam_wave_launches", &mcl_ctx::beam_wave_launches},
     {"beam_ordered_launches", &mcl_ctx::beam_ordered_launches},

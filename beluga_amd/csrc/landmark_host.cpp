@@ -27,6 +27,9 @@ mcl_status landmark_layout_map(int32_t kind, const double* positions_xyz, const 
     LANDMARK_REQUIRE(std::isfinite(prm.random_prob), "mcl_set_landmark_map: random_prob must be finite");
     v.den_range = (2. * prm.sigma_range) * prm.sigma_range;  // landmark_sensor_model.hpp:147
     v.den_bearing = (2. * prm.sigma_bearing) * prm.sigma_bearing;
+    // (a sigma whose (2 sigma) sigma leaves the finite positive range would divide an exact zero error by zero, or inf by inf: NaN weights)
+    LANDMARK_REQUIRE(v.den_range > 0.0 && std::isfinite(v.den_range) && v.den_bearing > 0.0 && std::isfinite(v.den_bearing),
+                     "mcl_set_landmark_map: (2 sigma) sigma must be positive and finite for sigma_range and sigma_bearing");
     v.random_prob = prm.random_prob;
   } else {
     mcl_bearing_params prm;
@@ -39,6 +42,7 @@ mcl_status landmark_layout_map(int32_t kind, const double* positions_xyz, const 
     LANDMARK_REQUIRE(std::abs(std::sqrt(x * x + y * y + z * z + w * w) - 1.0) <= 1e-9,
                      "mcl_set_landmark_map: sensor_pose_in_robot's quaternion is not of unit length");
     v.den_bearing = (2. * prm.sigma_bearing) * prm.sigma_bearing;  // bearing_sensor_model.hpp:134
+    LANDMARK_REQUIRE(v.den_bearing > 0.0 && std::isfinite(v.den_bearing), "mcl_set_landmark_map: (2 sigma) sigma must be positive and finite for sigma_bearing");
     // Eigen's Quaternion::toRotationMatrix
     const double tx = 2. * x, ty = 2. * y, tz = 2. * z;
     const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;

@@ -362,7 +362,9 @@ void mcl_default_bearing_params(mcl_bearing_params* params);
  * (mcl_landmark_params or mcl_bearing_params), NULL = its defaults.  Replaces the map between updates (update_map).  n = 0 with
  * explicit boundaries is a valid, empty map.  MCL_ERR_INVALID_ARGUMENT: n = 0 with NULL boundaries (the reference keeps Eigen's empty
  * box there, from which nothing can be drawn), values that are not finite, min > max in x or y, a sigma that is not positive and
- * finite, a quaternion that is not finite or not of unit length within 1e-9. */
+ * finite or whose (2 sigma) sigma, the exponents' denominator, underflows to 0 or overflows (about sigma < 1.1e-162 or > 9.4e153: an
+ * exact error of 0 would give 0 / 0, a NaN weight from finite inputs), a quaternion that is not finite or not of unit length within
+ * 1e-9. */
 mcl_status mcl_set_landmark_map(mcl_ctx* ctx, const double* positions_xyz, const uint32_t* categories, uint64_t n,
                                 const double boundaries[6], const void* params);
 /* Amcl::update with a std::vector<LandmarkPositionDetection> / <LandmarkBearingDetection>: n detections vectors_xyz[n*3] with
@@ -861,6 +863,9 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *   ndt_lane_launches / ndt_wave_launches = an NDT context's own reweight launches of the lane-per-particle kernel / of the
  *   wave-per-particle kernel, in either map layout (mcl_set_ndt_small_cycle and the size of the set decide; not counted for an empty set
  *   or a scan without a measurement cell; a fleet's shared launch counts in mcl_ndt_batch_counts instead);
+ *   landmark_lane_launches / landmark_wave_launches = a landmark or bearing context's reweight launches of the lane-per-particle kernel /
+ *   of the wave-per-particle kernel (mcl_set_landmark_small_cycle and the size of the set decide; not counted for an empty set or a call
+ *   without detections; a fleet's shared launch counts in the member's landmark_wave_launches);
  *   cluster_cells = occupied cells of the last cluster_based_estimate; comm_ranks_seen (ncclCommCount of the library's communicator, 0
  *   without one), comm_collectives, comm_bytes_out (running totals of this rank), comm_backend (0 = none, 1 = the caller's transport, 2 = RCCL inside the library). */
 mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value);
