@@ -33,6 +33,7 @@
 #include "map_store.h"
 #include "ndt_host.h"
 #include "options_host.h"
+#include "scratch_layout.h"
 #include "set_facts.h"
 
 namespace {
@@ -102,13 +103,13 @@ struct mcl_ctx {
   bool points_in_flight{false}, points_event_valid{false};
 
   // reductions / scans
-  DeviceBuffer<double> d_chunk;      // [12][stride]
-  uint32_t chunk_stride{0};
+  DeviceBuffer<double> d_chunk;      // chunk_rows (scratch_layout.h)
+  RowsLayout chunk_layout{};
   DeviceBuffer<double> d_scalars;    // kScalarSlots doubles, laid out as kernels.h ScalarSlot says
   HostBuffer<double> h_scalars;      // pinned and mapped, kScalarSlots doubles: kernels mirror their scalar results into it
   DeviceBuffer<double> d_cdf;
   DeviceBuffer<double4> d_cloud;    // mcl_sample_particle_cloud staging
-  DeviceBuffer<double> d_est_partials;  // [9][ceil(n / 256)] estimate sums left by the draw kernel
+  DeviceBuffer<double> d_est_partials;  // estimate sums left by the draw kernel: draw_estimate_rows (scratch_layout.h)
   // The fixed-size cycle's completion word (Completion): ticket in kSlotDoneTicket, word in kSlotDoneWord; done_seq counts the
   // cycles that armed it, done_armed: this cycle's last kernel carries it.
   uint64_t done_seq{0};
@@ -155,9 +156,9 @@ struct mcl_ctx {
   DeviceBuffer<unsigned long long> d_table_keys;
   DeviceBuffer<unsigned int> d_table_first;
   uint64_t table_capacity{0};
-  DeviceBuffer<uint32_t> d_flags, d_uchunk;  // flags[kld_capacity]; uchunk[2][kld_chunks]
+  DeviceBuffer<uint32_t> d_flags, d_uchunk;  // flags[kld_capacity]; uchunk: kld_chunk_rows (scratch_layout.h)
   uint64_t kld_capacity{0};                  // candidates one KLD pass can hold (a shard sees the GLOBAL candidate stream)
-  uint32_t kld_chunks{0};
+  RowsLayout kld_chunk_layout{};
   // state of the running KLD pass (do_resample, or mcl_kld_begin / mcl_kld_feed for the sharded driver)
   uint64_t kld_pos{0}, kld_table_slots{0};
   int kld_flip{0};
@@ -165,11 +166,11 @@ struct mcl_ctx {
   HostBuffer<unsigned long long> h_kld_scalars;    // pinned, 8 words
 
   // cluster_based_estimate scratch
-  DeviceBuffer<double> d_cell_f64;             // table wsum[cap_t] | list wsum[m_cap] | list state[4*m_cap]
-  DeviceBuffer<unsigned int> d_cell_u32;       // table count[cap_t] cluster[cap_t] | list first,count,slot,cluster[m_cap] | size
-  DeviceBuffer<unsigned long long> d_cell_u64; // list key[m_cap]
-  DeviceBuffer<double> d_cell_exchange;        // shards: this rank's cell records | the gathered records of all ranks
-  DeviceBuffer<double> d_cluster_sums;         // mcl_estimate_clusters: partial rows [K * 9][chunks] | the sums [K][9]
+  DeviceBuffer<double> d_cell_f64;             // the cell table's columns and the device list of cells, by element type:
+  DeviceBuffer<unsigned int> d_cell_u32;       // ClusterLayout (scratch_layout.h)
+  DeviceBuffer<unsigned long long> d_cell_u64;
+  DeviceBuffer<double> d_cell_exchange;        // shards: cell_exchange_rows (scratch_layout.h)
+  DeviceBuffer<double> d_cluster_sums;         // mcl_estimate_clusters: ClusterSumsLayout (scratch_layout.h)
   DeviceBuffer<unsigned int> d_cluster_labels; // mcl_cluster_labels: one id per particle
   int estimate_kind{0};
   mcl_cluster_params cluster_params{0.20, 0.524, 0.90};
@@ -197,10 +198,10 @@ struct mcl_ctx {
   uint64_t lf_far_launches{0};     // launches of the gather kernel with the far-tile bitmap (dispersed sets)
   uint64_t lf_far_beams_launches{0};  // those of them that were k_reweight_lf_far_beams (lf_dispersed = 2)
   // scratch of the spatial ordering
-  DeviceBuffer<uint32_t> d_route_u32;           // scratch of mcl_route_targets
-  DeviceBuffer<uint32_t> d_sort_u32;            // keys[cap] perm[cap] table[1024 * nblocks] totals[1024] bases[1024] flags[16]
-  DeviceBuffer<unsigned long long> d_sort_u64;  // keyidx[cap]
-  DeviceBuffer<double> d_sort_f64;              // frame[8] bbox[8 + 6*nblocks] partial[...]
+  DeviceBuffer<uint32_t> d_route_u32;           // scratch of launch_route_targets: RouteLayout (scratch_layout.h)
+  DeviceBuffer<uint32_t> d_sort_u32;            // SortLayout (scratch_layout.h) of `capacity` particles, carved by sort_scratch()
+  DeviceBuffer<unsigned long long> d_sort_u64;
+  DeviceBuffer<double> d_sort_f64;
 
   // particle shards: communicator + scratch of the exchange (sharded_update)
   bool have_comm{false};
@@ -209,8 +210,8 @@ struct mcl_ctx {
   mcl_transport transport{};
   void* rccl_comm{nullptr};                 // ncclComm_t when the transport is the built-in RCCL one
   struct RcclUserStorage { void* comm; uint32_t rank, world; } rccl_user{nullptr, 0, 1};
-  DeviceBuffer<double> d_comm_f64;          // laid out as CommSlot / CommAreas say
-  DeviceBuffer<long long> d_comm_i64;       // counts[world] | gathered counts[world * world]
+  DeviceBuffer<double> d_comm_f64;          // CommSlot at its head, then the gathered areas: CommLayout (scratch_layout.h)
+  DeviceBuffer<long long> d_comm_i64;       // CommLayout's counts and gathered counts
   DeviceBuffer<double> d_targets, d_send_targets, d_requests_in, d_replies_out, d_replies_in;
   DeviceBuffer<uint32_t> d_route_order;
   // KLD-adaptive resampling over shards: this rank's slices of the candidate blocks, hash staging, the re-balanced shard
@@ -218,7 +219,7 @@ struct mcl_ctx {
   DeviceBuffer<unsigned long long> d_cand_hashes, d_block_hashes;
   uint64_t global_n{0};                     // particles of the logical filter over all shards (0: max_particles)
   bool global_n_unknown{false};             // the caller loaded this shard itself (mcl_set_particles): counts are gathered first
-  HostBuffer<double> h_comm;                // pinned staging for the exchange's host reads / uploads
+  HostBuffer<double> h_comm;                // pinned staging for the exchange's host reads / uploads: CommHostLayout (scratch_layout.h)
   HostBuffer<unsigned char> h_cells;        // cluster_based_estimate: the list of occupied cells in mapped pinned memory
 
   // profiling: 0 = off, 1 = the sensor kernel only (two events per cycle), 2 = every stage
@@ -231,7 +232,7 @@ struct mcl_ctx {
 
   Particles cur() const { return sets[live].view(); }
   Particles other() const { return sets[live ^ 1].view(); }
-  double* chunk_row(int k) { return d_chunk.ptr + static_cast<size_t>(k) * chunk_stride; }
+  double* chunk_row(int k) { return d_chunk.ptr + chunk_layout.row(static_cast<size_t>(k)); }
   FieldView field_view() const {
     const MapStore& m = *map;
     return FieldView{m.d_field.ptr, m.W, m.H, 1. / m.resolution, m.origin_inverse, static_cast<float>(1. / cfg.lf.max_laser_distance),
@@ -242,16 +243,20 @@ struct mcl_ctx {
                      lf_acc0(cfg.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB, static_cast<float>(1. / cfg.lf.max_laser_distance), scan_no_cell)};
   }
   SortScratch sort_scratch() {
+    const SortLayout lay(capacity);
+    uint32_t* const u32 = d_sort_u32.ptr;
+    double* const f64 = d_sort_f64.ptr;
     SortScratch s{};
-    const size_t nblocks = num_chunks(capacity);
-    s.keys = d_sort_u32.ptr;
-    s.perm = s.keys + capacity;
-    s.table = s.perm + capacity;
-    s.totals = s.table + kSortDigits * nblocks;
-    s.keyidx = d_sort_u64.ptr;
-    s.frame = reinterpret_cast<KeyFrame*>(d_sort_f64.ptr);
-    s.bbox = d_sort_f64.ptr + 8;
-    s.partial = s.bbox + 8 + 6 * nblocks;
+    s.keys = u32 + lay.keys;
+    s.perm = u32 + lay.perm;
+    s.table = u32 + lay.table;
+    s.totals = u32 + lay.totals;
+    s.bases = u32 + lay.bases;
+    s.keyidx = d_sort_u64.ptr + lay.keyidx;
+    s.frame = reinterpret_cast<KeyFrame*>(f64 + lay.frame);
+    s.bbox = f64 + lay.bbox;
+    s.bbox_partials = f64 + lay.bbox_partials;
+    s.partial = f64 + lay.partial;
     return s;
   }
   GridView grid_view() const { return GridView{map->d_cells.ptr, map->W, map->H, map->resolution, map->origin, map->origin_inverse, map->traits.free_value}; }
@@ -277,7 +282,7 @@ struct mcl_ctx {
   std::vector<double> h_ndt_meas;  // the scan's measurement cells, kNdtRecord doubles each (what stage_points uploads)
   FreeCells ndt_random{nullptr, 0};
   bool ndt_random_ready{false};        // ndt_random was prepared for the next draw (prepare_ndt_random)
-  DeviceBuffer<double> d_ndt_est;      // scratch of the estimate behind ndt_random (9 rows of num_chunks(n))
+  DeviceBuffer<double> d_ndt_est;      // scratch of the estimate behind ndt_random: estimate_rows (scratch_layout.h)
   bool ndt_small_cycle{false};         // mcl_set_ndt_small_cycle: the wave-per-particle reweight and the one-launch tail for small sets
   uint64_t ndt_small_completed{0};     // small cycles that ended inside k_small_tail (mcl_get_ndt_small_cycle_counts)
   uint64_t ndt_small_handed_back{0};   // ... and those the tail handed back to the host behind the policies
@@ -411,12 +416,11 @@ mcl_status wait_for_cycle(mcl_ctx* ctx) {
 
 mcl_status ensure_capacity(mcl_ctx* ctx, uint64_t cap) {
   for (auto& set : ctx->sets) MCL_HIP(ctx, set.ensure(cap));
-  const uint32_t chunks = num_chunks(cap) + 1;
-  ctx->chunk_stride = chunks;
-  MCL_HIP(ctx, ctx->d_chunk.ensure(static_cast<size_t>(12) * chunks));
+  ctx->chunk_layout = chunk_rows(cap);
+  MCL_HIP(ctx, ctx->d_chunk.ensure(ctx->chunk_layout.size()));
   MCL_HIP(ctx, ctx->d_cdf.ensure(cap));
   MCL_HIP(ctx, ctx->d_cdf_tree.ensure(cdf_tree_doubles(cap)));
-  MCL_HIP(ctx, ctx->d_lf_wsum.ensure(cap / 448 + 2));
+  MCL_HIP(ctx, ctx->d_lf_wsum.ensure(lf_weight_sums_size(cap)));
   if (ctx->family() == SensorFamily::kLikelihoodField) MCL_HIP(ctx, ctx->d_field_pose.ensure(cap));
   if (!ctx->d_scan_state.ptr) {
     MCL_HIP(ctx, ctx->d_scan_state.ensure(kScanStateWords));
@@ -424,11 +428,11 @@ mcl_status ensure_capacity(mcl_ctx* ctx, uint64_t cap) {
   }
   ctx->capacity = cap;
   {
-    static_assert(sizeof(KeyFrame) <= 8 * sizeof(double), "the key frame sits in the first 8 doubles of d_sort_f64");
-    const size_t table = static_cast<size_t>(kSortDigits) * num_chunks(cap);
-    MCL_HIP(ctx, ctx->d_sort_u32.ensure(2 * cap + table + 2 * kSortDigits + 16));
-    MCL_HIP(ctx, ctx->d_sort_u64.ensure(cap));
-    MCL_HIP(ctx, ctx->d_sort_f64.ensure(8 + 8 + 6 * static_cast<size_t>(chunks) + kLfMaxSegments * std::min<uint64_t>(cap, kLfSegmentedBelow)));
+    static_assert(sizeof(KeyFrame) <= kKeyFrameDoubles * sizeof(double), "the key frame sits in SortLayout::frame");
+    const SortLayout sort(cap);
+    MCL_HIP(ctx, ctx->d_sort_u32.ensure(sort.u32_size));
+    MCL_HIP(ctx, ctx->d_sort_u64.ensure(sort.u64_size));
+    MCL_HIP(ctx, ctx->d_sort_f64.ensure(sort.f64_size));
   }
   return MCL_OK;
 }
@@ -438,8 +442,8 @@ mcl_status ensure_kld(mcl_ctx* ctx) {
   const uint64_t cap = std::max<uint64_t>(ctx->capacity, ctx->cfg.shard_capacity ? ctx->cfg.amcl.max_particles : 0);
   MCL_HIP(ctx, ctx->d_hashes.ensure(cap));
   MCL_HIP(ctx, ctx->d_flags.ensure(cap));
-  ctx->kld_chunks = num_chunks(cap) + 1;
-  MCL_HIP(ctx, ctx->d_uchunk.ensure(static_cast<size_t>(2) * ctx->kld_chunks));
+  ctx->kld_chunk_layout = kld_chunk_rows(cap);
+  MCL_HIP(ctx, ctx->d_uchunk.ensure(ctx->kld_chunk_layout.size()));
   uint64_t tc = 1024;
   while (tc < 2 * cap) tc <<= 1;
   MCL_HIP(ctx, ctx->d_table_keys.ensure(tc));
@@ -487,8 +491,8 @@ mcl_status kld_process(mcl_ctx* ctx, uint64_t cnt, uint64_t* first_fail) {
   const KldTable table{ctx->d_table_keys.ptr, ctx->d_table_first.ptr, ctx->kld_table_slots};
   uint32_t* kwords = reinterpret_cast<uint32_t*>(ctx->d_kld_scalars.ptr + kKldCounts);
   launch_kld_insert(ctx->stream, ctx->d_hashes.ptr, ctx->kld_pos, cnt, table);
-  launch_kld_scan(ctx->stream, ctx->d_hashes.ptr, ctx->kld_pos, cnt, table, ctx->d_flags.ptr, ctx->d_uchunk.ptr,
-                  ctx->d_uchunk.ptr + ctx->kld_chunks, kwords + ctx->kld_flip, kwords + (ctx->kld_flip ^ 1), a.min_particles,
+  launch_kld_scan(ctx->stream, ctx->d_hashes.ptr, ctx->kld_pos, cnt, table, ctx->d_flags.ptr, ctx->d_uchunk.ptr + ctx->kld_chunk_layout.row(0),
+                  ctx->d_uchunk.ptr + ctx->kld_chunk_layout.row(1), kwords + ctx->kld_flip, kwords + (ctx->kld_flip ^ 1), a.min_particles,
                   a.kld_epsilon, a.kld_z, ctx->d_kld_scalars.ptr + kKldFirstFail);
   MCL_HIP(ctx, hipGetLastError());
   MCL_HIP(ctx, hipMemcpyAsync(ctx->h_kld_scalars.host + kKldFirstFail, ctx->d_kld_scalars.ptr + kKldFirstFail, sizeof(unsigned long long),
@@ -772,19 +776,20 @@ mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, co
   const uint32_t bits_y = bits_of(static_cast<uint64_t>(static_cast<int64_t>(box[3]) - box[2]));
   DeviceBuffer<unsigned long long> d_words;
   DeviceBuffer<uint32_t> d_u32;
-  const size_t table = ndt_radix_table_words(n), chunks = num_chunks(std::max<size_t>(n, table)), starts = n / 5 + 1;
-  MCL_HIP(ctx, d_words.ensure(static_cast<size_t>(2) * n));
-  MCL_HIP(ctx, d_u32.ensure(static_cast<size_t>(3) * n + table + chunks + starts + kNdtCounters));
+  const RowsLayout words = ndt_word_rows(n);
+  const NdtBuildScratchLayout lay_u32(n, ndt_radix_table_words(n));
+  MCL_HIP(ctx, d_words.ensure(words.size()));
+  MCL_HIP(ctx, d_u32.ensure(lay_u32.size));
   NdtBuildScratch sc{};
-  sc.words[0] = d_words.ptr;
-  sc.words[1] = d_words.ptr + n;
-  sc.idx[0] = d_u32.ptr;
-  sc.idx[1] = sc.idx[0] + n;
-  sc.flags = sc.idx[1] + n;
-  sc.table = sc.flags + n;
-  sc.chunk_tmp = sc.table + table;
-  sc.starts = sc.chunk_tmp + chunks;
-  sc.counters = sc.starts + starts;
+  sc.words[0] = d_words.ptr + words.row(0);
+  sc.words[1] = d_words.ptr + words.row(1);
+  sc.idx[0] = d_u32.ptr + lay_u32.idx0;
+  sc.idx[1] = d_u32.ptr + lay_u32.idx1;
+  sc.flags = d_u32.ptr + lay_u32.flags;
+  sc.table = d_u32.ptr + lay_u32.table;
+  sc.chunk_tmp = d_u32.ptr + lay_u32.chunk_tmp;
+  sc.starts = d_u32.ptr + lay_u32.starts;
+  sc.counters = d_u32.ptr + lay_u32.counters;
   uint32_t counters[kNdtCounters] = {0u, UINT32_MAX, 0u, UINT32_MAX, 0u, 0u, 0u};
   MCL_HIP(ctx, hipMemcpy(sc.counters, counters, sizeof(counters), hipMemcpyHostToDevice));
   const int sorted = launch_ndt_group_points(st, d_pts, n, resolution, box[0], box[2], bits_x, bits_y, sc);
@@ -1343,7 +1348,7 @@ mcl_status prepare_ndt_random(mcl_ctx* ctx, double random_state_probability) {
   ctx->ndt_random_ready = true;
   if (!(random_state_probability > 0.0)) return MCL_OK;
   ctx->ndt_random_ready = false;
-  MCL_HIP(ctx, ctx->d_ndt_est.ensure(static_cast<size_t>(9) * std::max<uint32_t>(num_chunks(ctx->n), 1u)));
+  MCL_HIP(ctx, ctx->d_ndt_est.ensure(estimate_rows(ctx->n).size()));
   double sums[12];
   if (const mcl_status s = do_estimate_sums(ctx, ctx->facts.pivot(), sums, ctx->d_ndt_est.ptr)) return s;
   mcl_estimate est{};
@@ -1402,7 +1407,7 @@ mcl_status do_resample(mcl_ctx* ctx, double random_state_probability, uint32_t s
     ra.count = max_p;
     ra.out_offset = 0;
     if (opt.with_estimate) {
-      MCL_HIP(ctx, ctx->d_est_partials.ensure(static_cast<size_t>(9) * ((max_p + 1023) / 1024)));
+      MCL_HIP(ctx, ctx->d_est_partials.ensure(draw_estimate_rows(max_p).size()));
       Completion done{};
       // (cycle_spin -1: where the cycle is long enough for the stream's completion signal to be what the host waits for last - measured
       // + 1 % at 1M particles in alternating runs, profiles/r06_ab_cycle_end.txt; small sets are bound by the host, which the spin costs)
@@ -1502,29 +1507,29 @@ enum CommSlot : size_t {
   kCommGlobalSum = 4,  // the global weight sum: the gathered sums, added in rank order
   kCommEstimate = 5,   // [5..15) the record of the estimate's all-gather (kEstRecord): the nine sums,
   kCommOverflow = 14,  // then this rank's overflow flag of the fixed-capacity exchange
-  kCommPlan = 16,      // [16..18) the shard plan (launch_shard_plan): {total, random state probability}
-  kCommScalars = 20
-};
+  kCommPlan = 16       // [16..18) the shard plan (launch_shard_plan): {total, random state probability}
+};                     // (kCommScalars of them: scratch_layout.h)
 struct ShardStats { double cdf_total, norm_sum, norm_sumsq; };
-constexpr size_t kStatsRecord = sizeof(ShardStats) / sizeof(double), kEstRecord = 10;  // (kEstRecord: nine sums + the overflow flag)
-constexpr size_t kCommPerRank = 1 + kStatsRecord + 2 + kEstRecord, kMaxWorld = 64;  // doubles gathered per rank; ranks at most
-// The gathered areas: sums[world] | stats[world][kStatsRecord] | ends[world], offsets[world] | estimates[world][kEstRecord]
+static_assert(sizeof(ShardStats) == kStatsRecord * sizeof(double), "CommLayout::stats holds a ShardStats per rank");
+// The gathered areas of d_comm_f64 (CommLayout), the device's 64-bit words and the host's (CommHostLayout).
 struct CommAreas { double *sums, *stats, *intervals, *estimates; };
 CommAreas comm_areas(const mcl_ctx* ctx) {
-  const size_t world = ctx->comm_world;
-  double* sums = ctx->d_comm_f64.ptr + kCommScalars;
-  return CommAreas{sums, sums + world, sums + world * (1 + kStatsRecord), sums + world * (1 + kStatsRecord + 2)};
+  const CommLayout lay(ctx->comm_world);
+  double* d = ctx->d_comm_f64.ptr;
+  return CommAreas{d + lay.sums, d + lay.stats, d + lay.intervals, d + lay.estimates};
 }
-// h_comm: the global sum, the gathered statistics (ShardStats[world]) and the CDF intervals to upload from h_comm[0] on, then the
-// 64-bit words of the counts' all-gathers.
-long long* comm_host_words(const mcl_ctx* ctx) { return reinterpret_cast<long long*>(ctx->h_comm.host + kCommScalars + kMaxWorld * kCommPerRank); }
+struct CommCounts { long long *mine, *gathered; };  // [world], [world][world]
+CommCounts comm_counts(const mcl_ctx* ctx) {
+  const CommLayout lay(ctx->comm_world);
+  return CommCounts{ctx->d_comm_i64.ptr + lay.counts, ctx->d_comm_i64.ptr + lay.gathered};
+}
+long long* comm_host_words(const mcl_ctx* ctx) { return reinterpret_cast<long long*>(ctx->h_comm.host + CommHostLayout().words); }
 
 mcl_status comm_scratch(mcl_ctx* ctx) {
-  const size_t world = ctx->comm_world;
-  MCL_HIP(ctx, ctx->d_comm_f64.ensure(kCommScalars + world * kCommPerRank));
-  MCL_HIP(ctx, ctx->d_comm_i64.ensure(world + world * world));
-  const size_t host_doubles = kCommScalars + kMaxWorld * kCommPerRank + kMaxWorld * kMaxWorld + kMaxWorld;  // (the words: kMaxWorld + 1 rows)
-  MCL_HIP(ctx, ctx->h_comm.ensure(host_doubles, /*mapped=*/false));
+  const CommLayout lay(ctx->comm_world);
+  MCL_HIP(ctx, ctx->d_comm_f64.ensure(lay.f64_size));
+  MCL_HIP(ctx, ctx->d_comm_i64.ensure(lay.i64_size));
+  MCL_HIP(ctx, ctx->h_comm.ensure(CommHostLayout().size, /*mapped=*/false));
   return MCL_OK;
 }
 mcl_status comm_gather(mcl_ctx* ctx, const void* d_send, void* d_recv, uint64_t bytes) {
@@ -1584,13 +1589,13 @@ mcl_status comm_agree(mcl_ctx* ctx, const char* where) {
   if (const mcl_status s = bind_device(ctx)) return s;
   if (const mcl_status s = comm_scratch(ctx)) return s;
   const uint32_t world = ctx->comm_world;
-  long long* d_words = ctx->d_comm_i64.ptr;
+  const CommCounts d_words = comm_counts(ctx);
   long long* h_words = comm_host_words(ctx);
   const uint64_t mine = comm_path_word(ctx);
   std::memcpy(h_words, &mine, sizeof(mine));
-  MCL_HIP(ctx, hipMemcpyAsync(d_words, h_words, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-  if (const mcl_status s = comm_gather(ctx, d_words, d_words + world, sizeof(long long))) return s;
-  MCL_HIP(ctx, hipMemcpyAsync(h_words, d_words + world, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipMemcpyAsync(d_words.mine, h_words, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+  if (const mcl_status s = comm_gather(ctx, d_words.mine, d_words.gathered, sizeof(long long))) return s;
+  MCL_HIP(ctx, hipMemcpyAsync(h_words, d_words.gathered, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (uint32_t r = 0; r < world; ++r) {
     uint64_t theirs;
@@ -1642,26 +1647,21 @@ mcl_status sharded_estimate(mcl_ctx* ctx, const ClusterMask* mask, mcl_estimate*
 // Device: hashing, per-cell aggregation, masked sums (kernels.hip).  Host: the cluster assignment over the (few) occupied
 // cells, fed in first-occurrence order so that the containers evolve as they do in the reference (cluster_host.cpp).
 //
-// A CellList of `capacity` cells and, behind it, the cells' cluster ids, laid over one area per element type:
-//   u64: key[c] | f64: wsum[c], state[4 c] | u32: first[c], count[c], slot[c], cluster[c], size
+// A CellList of lay.capacity cells and, behind it, the cells' cluster ids, over one area per element type (CellListLayout).
 struct CellListView {
   CellList list;
   unsigned int* cluster;
 };
-constexpr size_t kListF64 = 5, kListU32 = 4;  // elements per cell (and one more u32: the size)
-CellListView lay_cell_list(unsigned long long* u64, double* f64, unsigned int* u32, size_t capacity) {
-  unsigned int* cluster = u32 + 3 * capacity;
-  return CellListView{CellList{u64, u32, u32 + capacity, u32 + 2 * capacity, f64, reinterpret_cast<double4*>(f64 + capacity), cluster + capacity},
-                      cluster};
+CellListView lay_cell_list(unsigned long long* u64, double* f64, unsigned int* u32, const CellListLayout& lay) {
+  return CellListView{CellList{u64 + lay.key, u32 + lay.first, u32 + lay.count, u32 + lay.slot, f64 + lay.wsum,
+                               reinterpret_cast<double4*>(f64 + lay.state), u32 + lay.size_word},
+                      u32 + lay.cluster};
 }
-// ... the three areas behind one another in one block of cell_list_bytes(capacity) (capacity a multiple of 4: the states are double4)
-constexpr size_t cell_list_bytes(size_t capacity) {
-  return capacity * (sizeof(unsigned long long) + kListF64 * sizeof(double) + kListU32 * sizeof(unsigned int)) + 64;
-}
+// ... the three areas behind one another in one block of CellListLayout(capacity).bytes (capacity a multiple of 4: the states are double4)
 CellListView lay_cell_list(unsigned char* base, size_t capacity) {
-  unsigned long long* u64 = reinterpret_cast<unsigned long long*>(base);
-  double* f64 = reinterpret_cast<double*>(u64 + capacity);
-  return lay_cell_list(u64, f64, reinterpret_cast<unsigned int*>(f64 + kListF64 * capacity), capacity);
+  const CellListLayout lay(capacity);
+  return lay_cell_list(reinterpret_cast<unsigned long long*>(base + lay.u64_byte), reinterpret_cast<double*>(base + lay.f64_byte),
+                       reinterpret_cast<unsigned int*>(base + lay.u32_byte), lay);
 }
 
 // The occupied cells come to the host through a list in MAPPED pinned memory that the compaction kernel writes itself (a
@@ -1684,14 +1684,15 @@ mcl_status cluster_scratch(mcl_ctx* ctx, CellScratch* sc) {
   while (slots < 2 * n) slots <<= 1;
   slots = std::min<uint64_t>(slots, ctx->table_capacity);
   sc->m_cap = std::min<uint64_t>(n, slots);
-  const uint64_t tcap = ctx->table_capacity;
-  MCL_HIP(ctx, ctx->d_cell_f64.ensure(tcap + kListF64 * ctx->capacity));
-  MCL_HIP(ctx, ctx->d_cell_u32.ensure(2 * tcap + kListU32 * ctx->capacity + 4));
-  MCL_HIP(ctx, ctx->d_cell_u64.ensure(ctx->capacity));
-  MCL_HIP(ctx, ctx->h_cells.ensure(cell_list_bytes(kHostCells), /*mapped=*/true));
+  const ClusterLayout lay(ctx->table_capacity, ctx->capacity);
+  MCL_HIP(ctx, ctx->d_cell_f64.ensure(lay.f64_size));
+  MCL_HIP(ctx, ctx->d_cell_u32.ensure(lay.u32_size));
+  MCL_HIP(ctx, ctx->d_cell_u64.ensure(lay.u64_size));
+  MCL_HIP(ctx, ctx->h_cells.ensure(CellListLayout(kHostCells).bytes, /*mapped=*/true));
   unsigned int* u32 = ctx->d_cell_u32.ptr;
-  sc->table = CellTable{ctx->d_table_keys.ptr, ctx->d_table_first.ptr, ctx->d_cell_f64.ptr, u32, u32 + tcap, slots};
-  sc->arrays = lay_cell_list(ctx->d_cell_u64.ptr, ctx->d_cell_f64.ptr + tcap, u32 + 2 * tcap, ctx->capacity);
+  double* f64 = ctx->d_cell_f64.ptr;
+  sc->table = CellTable{ctx->d_table_keys.ptr, ctx->d_table_first.ptr, f64 + lay.table_wsum, u32 + lay.table_count, u32 + lay.table_cluster, slots};
+  sc->arrays = lay_cell_list(ctx->d_cell_u64.ptr + lay.list_u64, f64 + lay.list_f64, u32 + lay.list_u32, lay.list);
   sc->mapped = lay_cell_list(ctx->h_cells.host, kHostCells);
   sc->mapped_dev = lay_cell_list(ctx->h_cells.device, kHostCells);
   return MCL_OK;
@@ -1757,8 +1758,8 @@ mcl_status collect_cells(mcl_ctx* ctx, const HashParams& hp, const CellScratch& 
     launch_cluster_cells(ctx->stream, ctx->cur(), n, hp, ctx->d_hashes.ptr, sc.table, big,
                          static_cast<unsigned int>(std::min<uint64_t>(ctx->capacity, 0xFFFFFFFFull)), /*table_ready=*/true);
     MCL_HIP(ctx, hipGetLastError());
-    const size_t room = (static_cast<size_t>(m) + 3) & ~static_cast<size_t>(3);
-    c->copy.resize((cell_list_bytes(room) + sizeof(double4) - 1) / sizeof(double4));
+    const size_t room = cell_list_capacity(m);
+    c->copy.resize((CellListLayout(room).bytes + sizeof(double4) - 1) / sizeof(double4));
     c->host = lay_cell_list(reinterpret_cast<unsigned char*>(c->copy.data()), room);
     c->dev = sc.arrays;
     const CellList& h = c->host.list;
@@ -1793,12 +1794,12 @@ mcl_status exchange_cells(mcl_ctx* ctx, bool local_failure, std::vector<ClusterC
                           std::vector<uint32_t>* index_of_mine) {
   if (const mcl_status s = comm_scratch(ctx)) return s;
   const uint32_t world = ctx->comm_world;
-  long long* d_counts = ctx->d_comm_i64.ptr;
+  const CommCounts d_counts = comm_counts(ctx);
   long long* h_counts = comm_host_words(ctx);
   h_counts[0] = local_failure ? -1 : static_cast<long long>(mine.size());  // -1: this rank's compaction failed
-  MCL_HIP(ctx, hipMemcpyAsync(d_counts, h_counts, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
-  if (const mcl_status s = comm_gather(ctx, d_counts, d_counts + world, sizeof(long long))) return s;
-  MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts + world, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipMemcpyAsync(d_counts.mine, h_counts, sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+  if (const mcl_status s = comm_gather(ctx, d_counts.mine, d_counts.gathered, sizeof(long long))) return s;
+  MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts.gathered, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   std::vector<uint64_t> m_of(world);
   uint64_t widest = 0;
@@ -1810,9 +1811,10 @@ mcl_status exchange_cells(mcl_ctx* ctx, bool local_failure, std::vector<ClusterC
   }
   mine.resize(widest, ClusterCell{});  // every rank sends the widest list's size: zero records behind its own
   const size_t record_bytes = widest * sizeof(ClusterCell);
-  MCL_HIP(ctx, ctx->d_cell_exchange.ensure(kCellRecordDoubles * widest * (world + 1)));
-  double* d_send = ctx->d_cell_exchange.ptr;
-  double* d_recv = d_send + kCellRecordDoubles * widest;
+  const RowsLayout exchange = cell_exchange_rows(kCellRecordDoubles, widest, world);
+  MCL_HIP(ctx, ctx->d_cell_exchange.ensure(exchange.size()));
+  double* d_send = ctx->d_cell_exchange.ptr + exchange.row(0);
+  double* d_recv = ctx->d_cell_exchange.ptr + exchange.row(1);
   MCL_HIP(ctx, hipMemcpyAsync(d_send, mine.data(), record_bytes, hipMemcpyHostToDevice, ctx->stream));
   if (const mcl_status s = comm_gather(ctx, d_send, d_recv, record_bytes)) return s;
   std::vector<ClusterCell> all(widest * world);
@@ -1958,15 +1960,14 @@ mcl_status do_estimate_clusters(mcl_ctx* ctx, const mcl_cluster_params& cp, mcl_
   for (unsigned int& c : rank_of) c = sel.rank_of_cluster[c];
   if (const mcl_status s = upload_cell_values(ctx, f.mine, rank_of)) return s;
   launch_cell_set_cluster(ctx->stream, f.mine.dev.list, f.mine.dev.cluster, f.mine.m, f.sc.table);
-  const size_t rows = static_cast<size_t>(ranks) * 9;
-  const size_t partials = rows * num_chunks(ctx->n);
-  MCL_HIP(ctx, ctx->d_cluster_sums.ensure(partials + rows));
-  double* d_sums = ctx->d_cluster_sums.ptr + partials;
+  const ClusterSumsLayout lay(ranks, ctx->n);
+  MCL_HIP(ctx, ctx->d_cluster_sums.ensure(lay.size));
+  double* d_sums = ctx->d_cluster_sums.ptr + lay.sums;
   launch_estimate_sums_clusters(ctx->stream, ctx->cur(), ctx->n, ctx->d_hashes.ptr, f.sc.table, ranks, ctx->facts.pivot()[0], ctx->facts.pivot()[1],
-                                ctx->d_cluster_sums.ptr, d_sums);
+                                ctx->d_cluster_sums.ptr + lay.partials, d_sums);
   MCL_HIP(ctx, hipGetLastError());
-  std::vector<double> sums(rows);
-  MCL_HIP(ctx, hipMemcpyAsync(sums.data(), d_sums, rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<double> sums(lay.rows);
+  MCL_HIP(ctx, hipMemcpyAsync(sums.data(), d_sums, lay.rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   std::vector<mcl_cluster_estimate> found(ranks);
   for (uint32_t r = 0; r < ranks; ++r) {
@@ -2009,6 +2010,16 @@ mcl_status do_cluster_labels(mcl_ctx* ctx, const mcl_cluster_params& cp, uint32_
   return MCL_OK;
 }
 
+// The scratch of launch_route_targets over m targets and `world` shards, ensured and carved (RouteLayout).
+struct RouteScratch { uint8_t* dest; uint32_t *block_hist, *chunk_sum, *chunk_off; };
+mcl_status route_scratch(mcl_ctx* ctx, uint32_t world, uint64_t m, RouteScratch* out) {
+  const RouteLayout lay(world, m);
+  MCL_HIP(ctx, ctx->d_route_u32.ensure(lay.size));
+  uint32_t* u32 = ctx->d_route_u32.ptr;
+  *out = RouteScratch{reinterpret_cast<uint8_t*>(u32 + lay.dest), u32 + lay.block_hist, u32 + lay.chunk_sum, u32 + lay.chunk_off};
+  return MCL_OK;
+}
+
 // The same exchange without a host read in the middle of the cycle: every pair of ranks moves `cap` entries whatever the counts are
 // (requests: cap doubles, NaN = none; replies: cap states), so that the sizes of both all-to-alls are known before anything is
 // computed.  6 % more bytes than the exact form; a rank whose requests to one shard do not fit sets its
@@ -2019,7 +2030,7 @@ mcl_status sharded_draw_padded(mcl_ctx* ctx, const double* d_intervals, uint64_t
   const uint32_t world = ctx->comm_world, rank = ctx->comm_rank;
   const uint64_t entries = cap * world;
   MCL_REQUIRE(ctx, entries < (1ull << 32), "too many exchange entries");
-  long long* d_counts = ctx->d_comm_i64.ptr;  // [world] (not read by the host here)
+  long long* d_counts = comm_counts(ctx).mine;  // (not read by the host here)
   MCL_HIP(ctx, ctx->d_targets.ensure(std::max<uint64_t>(m, 1)));
   MCL_HIP(ctx, ctx->d_send_targets.ensure(entries));
   MCL_HIP(ctx, ctx->d_route_order.ensure(entries));
@@ -2030,18 +2041,12 @@ mcl_status sharded_draw_padded(mcl_ctx* ctx, const double* d_intervals, uint64_t
   MCL_HIP(ctx, hipMemsetAsync(ctx->d_route_order.ptr, 0xFF, entries * sizeof(uint32_t), ctx->stream));    // 0xFFFFFFFF: no slot
   launch_resample_targets(ctx->stream, ctx->cfg.seed, ctx->step, 0.0, 0.0, first_slot, m, ctx->have_map ? ctx->map->n_free : 0, ctx->d_targets.ptr, d_plan);
   MCL_HIP(ctx, hipGetLastError());
-  {
-    const size_t nblocks = num_chunks(m);
-    const size_t hist = static_cast<size_t>(world) * nblocks;
-    MCL_HIP(ctx, ctx->d_route_u32.ensure(hist + 2 * (hist / kChunk + 1) + (m + 3) / 4 + 4));
-    uint32_t* block_hist = ctx->d_route_u32.ptr;
-    uint32_t* chunk_sum = block_hist + hist;
-    uint32_t* chunk_off = chunk_sum + (hist / kChunk + 1);
-    uint8_t* dest = reinterpret_cast<uint8_t*>(chunk_off + (hist / kChunk + 1));
-    launch_route_targets(ctx->stream, ctx->d_targets.ptr, m, d_intervals, d_intervals + world, world, rank, dest, block_hist, chunk_sum, chunk_off,
-                         ctx->d_send_targets.ptr, ctx->d_route_order.ptr, d_counts, static_cast<uint32_t>(cap), ctx->d_comm_f64.ptr + kCommOverflow);
-    MCL_HIP(ctx, hipGetLastError());
-  }
+  RouteScratch rs{};
+  if (const mcl_status s = route_scratch(ctx, world, m, &rs)) return s;
+  launch_route_targets(ctx->stream, ctx->d_targets.ptr, m, d_intervals, d_intervals + world, world, rank, rs.dest, rs.block_hist, rs.chunk_sum,
+                       rs.chunk_off, ctx->d_send_targets.ptr, ctx->d_route_order.ptr, d_counts, static_cast<uint32_t>(cap),
+                       ctx->d_comm_f64.ptr + kCommOverflow);
+  MCL_HIP(ctx, hipGetLastError());
   std::vector<uint64_t> request_bytes(world, cap * sizeof(double)), reply_bytes(world, cap * 4 * sizeof(double));
   if (const mcl_status s = comm_exchange(ctx, ctx->d_send_targets.ptr, request_bytes.data(), ctx->d_requests_in.ptr, request_bytes.data())) return s;
   if (const mcl_status s = mcl_serve_requests(ctx, ctx->d_requests_in.ptr, entries, ctx->d_replies_out.ptr)) return s;
@@ -2056,8 +2061,8 @@ mcl_status sharded_draw_padded(mcl_ctx* ctx, const double* d_intervals, uint64_t
 mcl_status sharded_draw(mcl_ctx* ctx, double random_state_probability, double total, const double* d_intervals, uint64_t first_slot,
                         uint64_t m, const double* d_plan = nullptr) {
   const uint32_t world = ctx->comm_world, rank = ctx->comm_rank;
-  long long* d_counts = ctx->d_comm_i64.ptr;   // [world]
-  long long* d_all_counts = d_counts + world;  // [world][world]
+  long long* d_counts = comm_counts(ctx).mine;
+  long long* d_all_counts = comm_counts(ctx).gathered;
   MCL_HIP(ctx, ctx->d_targets.ensure(std::max<uint64_t>(m, 1)));
   MCL_HIP(ctx, ctx->d_send_targets.ensure(std::max<uint64_t>(m, 1)));
   MCL_HIP(ctx, ctx->d_route_order.ensure(std::max<uint64_t>(m, 1)));
@@ -2175,13 +2180,13 @@ mcl_status sharded_update(mcl_ctx* ctx, const Pose2& pose, Measurement scan, mcl
   const bool adaptive = ap.min_particles < ap.max_particles;
   if (const mcl_status s = comm_scratch(ctx)) return s;
   if (ctx->global_n_unknown) {  // shards loaded by the caller: total = sum of the counts, this shard starts behind the ranks before it
-    long long* d_counts = ctx->d_comm_i64.ptr;
+    const CommCounts d_counts = comm_counts(ctx);
     long long mine = static_cast<long long>(ctx->n);
-    MCL_HIP(ctx, hipMemcpyAsync(d_counts, &mine, sizeof(mine), hipMemcpyHostToDevice, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(d_counts.mine, &mine, sizeof(mine), hipMemcpyHostToDevice, ctx->stream));
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (mine is a local)
-    if (const mcl_status s = comm_gather(ctx, d_counts, d_counts + world, sizeof(long long))) return s;
+    if (const mcl_status s = comm_gather(ctx, d_counts.mine, d_counts.gathered, sizeof(long long))) return s;
     long long* h_counts = comm_host_words(ctx);
-    MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts + world, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts.gathered, world * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
     MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t sum = 0, before = 0;
     for (uint32_t r = 0; r < world; ++r) {
@@ -3650,11 +3655,22 @@ mcl_status batch_update_driver(mcl_batch* batch, mcl_estimate* estimates, mcl_up
   }
   return first_error;
 }
+
+// The detection records of a call (landmark_records, landmark_host.cpp) into h_landmark_meas.  Everything is checked before the device
+// is touched.
+mcl_status landmark_measurement(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n,
+                                Measurement* m) {
+  if (ctx->cfg.sensor_kind != kind)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the context's sensor model is not " + (kind == MCL_SENSOR_LANDMARK ? "MCL_SENSOR_LANDMARK" : "MCL_SENSOR_BEARING"));
+  std::string error;
+  if (const mcl_status s = landmark_records(who, kind, xyz, categories, n, ctx->have_landmark_map ? &ctx->landmark_ranges : nullptr,
+                                            ctx->h_landmark_meas, &error))
+    return fail(ctx, s, error);
+  *m = Measurement{ctx->h_landmark_meas.data(), ctx->h_landmark_meas.size()};
+  return MCL_OK;
+}
 }  // namespace
 extern "C" {
-
-static mcl_status landmark_measurement(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n,
-                                       Measurement* m);
 
 mcl_status mcl_batch_update(mcl_batch* batch, const double* control_poses, const double* points_xy, const uint64_t* point_offsets,
                             mcl_estimate* estimates, mcl_update_info* infos, mcl_status* statuses) {
@@ -3866,14 +3882,9 @@ mcl_status mcl_route_targets(mcl_ctx* ctx, const double* d_targets, uint64_t cou
   MCL_REQUIRE(ctx, d_ends && d_offsets && d_counts && (count == 0 || (d_targets && d_send_targets && d_order)), "null argument");
   MCL_REQUIRE(ctx, count < (1ull << 32), "too many targets");
   if (const mcl_status s = bind_device(ctx)) return s;
-  const size_t nblocks = num_chunks(count);
-  const size_t hist = static_cast<size_t>(world) * nblocks;
-  MCL_HIP(ctx, ctx->d_route_u32.ensure(hist + 2 * (hist / kChunk + 1) + (count + 3) / 4 + 4));
-  uint32_t* block_hist = ctx->d_route_u32.ptr;
-  uint32_t* chunk_sum = block_hist + hist;
-  uint32_t* chunk_off = chunk_sum + (hist / kChunk + 1);
-  uint8_t* dest = reinterpret_cast<uint8_t*>(chunk_off + (hist / kChunk + 1));
-  launch_route_targets(ctx->stream, d_targets, count, d_ends, d_offsets, world, self_rank, dest, block_hist, chunk_sum, chunk_off,
+  RouteScratch rs{};
+  if (const mcl_status s = route_scratch(ctx, world, count, &rs)) return s;
+  launch_route_targets(ctx->stream, d_targets, count, d_ends, d_offsets, world, self_rank, rs.dest, rs.block_hist, rs.chunk_sum, rs.chunk_off,
                        d_send_targets, d_order, reinterpret_cast<long long*>(d_counts));
   MCL_HIP(ctx, hipGetLastError());
   return MCL_OK;
@@ -4386,16 +4397,17 @@ mcl_status mcl_build_ndt_map_from_grid(mcl_ctx* ctx, const int8_t* cells, uint32
   DeviceBuffer<uint32_t> d_offsets;
   DeviceBuffer<double> d_pts;
   MCL_HIP(ctx, d_cells.ensure(count));
-  MCL_HIP(ctx, d_offsets.ensure(static_cast<size_t>(count) + num_chunks(count) + 1));
+  const NdtGridOffsetsLayout lay(count);
+  MCL_HIP(ctx, d_offsets.ensure(lay.size));
   MCL_HIP(ctx, hipMemcpy(d_cells.ptr, cells, count, hipMemcpyHostToDevice));
-  uint32_t* d_total = d_offsets.ptr + count + num_chunks(count);
-  launch_ndt_grid_offsets(ctx->stream, d_cells.ptr, count, kOccupied, d_offsets.ptr, d_offsets.ptr + count, d_total);
+  uint32_t* d_total = d_offsets.ptr + lay.total;
+  launch_ndt_grid_offsets(ctx->stream, d_cells.ptr, count, kOccupied, d_offsets.ptr + lay.offsets, d_offsets.ptr + lay.chunk_tmp, d_total);
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   uint32_t occupied = 0;
   MCL_HIP(ctx, hipMemcpy(&occupied, d_total, sizeof(occupied), hipMemcpyDeviceToHost));
   MCL_REQUIRE(ctx, occupied > 0, "mcl_build_ndt_map_from_grid: the grid has no occupied cell (the map is kept as it was)");
   MCL_HIP(ctx, d_pts.ensure(static_cast<size_t>(2) * occupied));
-  launch_ndt_grid_points(ctx->stream, d_cells.ptr, width, height, kOccupied, d_offsets.ptr, grid_resolution, pose_from(origin), d_pts.ptr);
+  launch_ndt_grid_points(ctx->stream, d_cells.ptr, width, height, kOccupied, d_offsets.ptr + lay.offsets, grid_resolution, pose_from(origin), d_pts.ptr);
   return ndt_build_from_device_points(ctx, "mcl_build_ndt_map_from_grid", d_pts.ptr, occupied, ndt_resolution);
 }
 
@@ -4452,20 +4464,6 @@ mcl_status mcl_set_landmark_map(mcl_ctx* ctx, const double* positions_xyz, const
   box.box_extent[1] = map.hi[1] - map.lo[1];
   ctx->landmark_random = box;
   ctx->have_landmark_map = true;
-  return MCL_OK;
-}
-
-// The detection records of a call (landmark_records, landmark_host.cpp) into h_landmark_meas.  Everything is checked before the device
-// is touched.
-static mcl_status landmark_measurement(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t n,
-                                       Measurement* m) {
-  if (ctx->cfg.sensor_kind != kind)
-    return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the context's sensor model is not " + (kind == MCL_SENSOR_LANDMARK ? "MCL_SENSOR_LANDMARK" : "MCL_SENSOR_BEARING"));
-  std::string error;
-  if (const mcl_status s = landmark_records(who, kind, xyz, categories, n, ctx->have_landmark_map ? &ctx->landmark_ranges : nullptr,
-                                            ctx->h_landmark_meas, &error))
-    return fail(ctx, s, error);
-  *m = Measurement{ctx->h_landmark_meas.data(), ctx->h_landmark_meas.size()};
   return MCL_OK;
 }
 

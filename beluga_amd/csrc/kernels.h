@@ -14,6 +14,7 @@
 #include "batch_host.h"
 #include "cycle_types.h"
 #include "ndt_hash.h"
+#include "scratch_layout.h"
 #include "se2.h"
 #include "sensor_records.h"
 
@@ -175,7 +176,7 @@ enum NdtBuildCounter : int {
   kNdtCountKeptBox = 1,  // [1..5): min x, max x, min y, max y of the kept cells' relative keys; the caller sets UINT_MAX, 0, UINT_MAX, 0
   kNdtCountScratch = 5,
   kNdtCountLongestProbe = 6,  // launch_ndt_hash_insert: the most slots any key needed; the caller sets 0
-  kNdtCounters = 7
+  kNdtCounters = kNdtBuildCounters  // (scratch_layout.h sizes the area)
 };
 struct NdtBuildLayout {
   long long x0, y0;            // the key the relative keys count from
@@ -248,7 +249,6 @@ struct ResampleArgs {
   uint64_t out_offset;      // where candidate `first_candidate` lands in the output set
 };
 
-constexpr uint32_t kSortDigits = 1024;  // two least-significant-digit-first passes of 10 bits each
 // Position of the cell (a0, a1, a2), `bits` bits each (bits <= 6), along the 3-D Hilbert curve through the (2^bits)^3 cells
 // (Skilling's transpose form, "Programming the Hilbert curve", 2004: undo the excess work, Gray-encode, interleave with a0 most
 // significant).  Consecutive positions are face neighbours, so ANY run of the order is a connected, compact set of cells - a run
@@ -306,15 +306,15 @@ struct SortScratch {
   uint32_t* keys;                // [n] key of particle i
   uint32_t* perm;                // [n] sorted position -> particle index
   uint32_t* table;               // [kSortDigits][nblocks] block histograms -> exclusive offsets (reused by both passes)
-  uint32_t* totals;              // [kSortDigits] digit totals, then [kSortDigits] their exclusive scan (the buckets' first positions) and
-                                 // [16] flags ([0]: some bucket is beyond kSortHugeBucket) - written by the first pass's first workgroup
+  uint32_t* totals;              // [kSortDigits] digit totals
+  uint32_t* bases;               // [kSortDigits] their exclusive scan (the buckets' first positions), then [16] flags ([0]: some bucket
+                                 // is beyond kSortHugeBucket) - written by the first pass's first workgroup
   unsigned long long* keyidx;    // [n] (high digit << 32 | index) after the first pass
-  double* bbox;                  // [8] min/max of x, y, relative heading (+ [6 * nblocks] partials behind it)
+  double* bbox;                  // [8] min/max of x, y, relative heading
+  double* bbox_partials;         // [6][nblocks] their per-chunk partials
   KeyFrame* frame;               // key frame derived from the bounding box (device-resident fallback)
   double* partial;               // [kLfMaxSegments][min(n, 262144)] scan-segment sums (medium particle counts); may be null
 };
-constexpr uint32_t kLfMaxSegments = 16;
-constexpr uint64_t kLfSegmentedBelow = 262144;  // particles
 
 // K1  actions/propagate.hpp:57-79 + differential_drive_model.hpp:156-163
 // scan_src / scan_dst (optional): the cycle's scan, copied by the kernel from mapped pinned host memory into HBM (no
@@ -421,9 +421,7 @@ void launch_pack_nonfree(hipStream_t st, const int8_t* cells, uint32_t W, uint32
 hipError_t configure_device_kernels();
 hipError_t configure_beam_kernels();
 
-// Deterministic chunked reductions / scans.  Chunk = 2048 consecutive elements per workgroup.
-constexpr uint32_t kChunk = 2048;
-inline uint32_t num_chunks(uint64_t n) { return static_cast<uint32_t>((n + kChunk - 1) / kChunk); }
+// Deterministic chunked reductions / scans: kChunk consecutive elements per workgroup, num_chunks(n) of them (scratch_layout.h).
 
 // K3a: partial[b] = sum of w over chunk b ; then d_out[0] = sum of partials (fixed order).
 // host_mirror (here and below, optional): mapped pinned-host memory that also receives the result

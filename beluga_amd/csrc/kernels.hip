@@ -4425,7 +4425,7 @@ void launch_order_particles(hipStream_t st, Particles p, uint64_t n, const SortS
   if (!keys_ready) {
     const KeyFrame* device_frame = nullptr;
     if (!frame) {  // no estimate of the set on the host: bins over its bounding box
-      double* partials = sort->bbox + 8;
+      double* partials = sort->bbox_partials;
       hipLaunchKernelGGL(k_bbox_partials, dim3(nblocks), dim3(kBlock), 0, st, p, n, partials, nblocks);
       hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(kBlock), 0, st, partials, nblocks, nblocks, sort->bbox, p, sort->frame, layout);
       device_frame = sort->frame;
@@ -4436,8 +4436,8 @@ void launch_order_particles(hipStream_t st, Particles p, uint64_t n, const SortS
   const dim3 rows(kSortDigits / (kBlock / 64));
   hipLaunchKernelGGL(k_row_scan, rows, dim3(kBlock), 0, st, sort->table, nblocks, sort->totals, static_cast<const uint32_t*>(nullptr), 0u);
   hipLaunchKernelGGL(k_sort_scatter_high, dim3(nblocks), dim3(kStable), 0, st, sort->keys, n, sort->table, nblocks, sort->totals,
-                     sort->keyidx, sort->totals + kSortDigits);
-  hipLaunchKernelGGL(k_sort_buckets, dim3(kSortDigits), dim3(kStable), 0, st, sort->keyidx, sort->totals, sort->totals + kSortDigits,
+                     sort->keyidx, sort->bases);
+  hipLaunchKernelGGL(k_sort_buckets, dim3(kSortDigits), dim3(kStable), 0, st, sort->keyidx, sort->totals, sort->bases,
                      sort->perm);
 }
 
@@ -4459,8 +4459,8 @@ void launch_order_ahead(hipStream_t st, uint64_t n, const SortScratch* sort, Ord
                        static_cast<const uint32_t*>(order_half_columns(sort)), draw_workgroups(n));
   }
   hipLaunchKernelGGL(k_sort_scatter_high, dim3(nblocks), dim3(kStable), 0, st, sort->keys, n, sort->table, nblocks, sort->totals,
-                     sort->keyidx, sort->totals + kSortDigits);
-  hipLaunchKernelGGL(k_sort_buckets, dim3(kSortDigits), dim3(kStable), 0, st, sort->keyidx, sort->totals, sort->totals + kSortDigits,
+                     sort->keyidx, sort->bases);
+  hipLaunchKernelGGL(k_sort_buckets, dim3(kSortDigits), dim3(kStable), 0, st, sort->keyidx, sort->totals, sort->bases,
                      sort->perm);
 }
 
