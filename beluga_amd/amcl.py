@@ -225,6 +225,34 @@ def _detection_arrays(detections, attribute):
     return xyz, cat
 
 
+def _f64_rows(what, value, columns):
+    """`value` as a C-contiguous float64 array of shape (n, columns), for Amcl.likelihoods*: an array of another dtype or another
+    shape is refused here, before any library call (a sequence of Python floats is float64; nothing empty is refused)."""
+    a = np.asarray(value)
+    if a.size == 0:
+        return np.zeros((0, columns), dtype=np.float64)
+    if a.dtype != np.float64:
+        raise TypeError(f"{what}: expected float64, got {a.dtype}")
+    if a.ndim != 2 or a.shape[1] != columns:
+        raise ValueError(f"{what}: expected shape (n, {columns}), got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _likelihood_detections(detections, attribute):
+    """_detection_arrays with the checks of Amcl.likelihoods*: vectors (k, 3) float64, one category each."""
+    if isinstance(detections, tuple) and len(detections) == 2 and not hasattr(detections[0], "category"):
+        xyz = _f64_rows("detections", detections[0], 3)
+        cat = np.asarray(detections[1])
+        if cat.size and not np.issubdtype(cat.dtype, np.integer):
+            raise TypeError(f"categories: expected integers, got {cat.dtype}")
+        if cat.ndim > 1 or cat.size != len(xyz):
+            raise ValueError("vectors and categories differ in length")
+        if cat.size and (cat.min() < 0 or cat.max() > 0xFFFFFFFF):
+            raise ValueError("categories: out of the range of uint32")
+        return xyz, np.ascontiguousarray(cat, dtype=np.uint32).reshape(-1)
+    return _detection_arrays(detections, attribute)
+
+
 def _landmark_params_struct(p):
     if isinstance(p, LandmarkModelParam):
         return capi.LandmarkParams(p.sigma_range, p.sigma_bearing, p.random_prob)
@@ -784,6 +812,67 @@ class Amcl:
         """Bearing model: w *= product over the detections (LandmarkBearingDetection entries or a (bearings, categories) pair)."""
         xyz, cat = _detection_arrays(detections, "detection_bearing_in_sensor")
         self._check(self._lib.mcl_reweight_bearings(self._ctx, _dp(xyz), cat.ctypes.data_as(capi.c_u32_p), len(xyz)))
+
+    # -- the sensor model as a function: sensor_model(measurement)(state) at caller-given poses -----------------------------
+    def likelihoods(self, poses, measurement) -> np.ndarray:
+        """states | views::likelihoods(sensor_model(measurement)) (views/likelihoods.hpp:44-59): the factor by which a reweight with
+        `measurement` would multiply the weight of a particle at each of `poses` - float64 (n, 4) as (cos, sin, x, y), in any order,
+        anywhere on or off the map.  The filter is untouched.  measurement: the scan's points, float64 (B, 2), on a likelihood-field,
+        beam or NDT filter; the detections - entries or a (vectors, categories) pair - on a landmark or bearing filter.  Wrong shapes
+        and dtypes raise before the library is called."""
+        p = _f64_rows("poses", poses, 4)
+        out = np.empty(len(p), dtype=np.float64)
+        if self._landmark_kind:
+            landmark = self._landmark_kind == capi.MCL_SENSOR_LANDMARK
+            xyz, cat = _likelihood_detections(measurement, "detection_position_in_robot" if landmark else "detection_bearing_in_sensor")
+            fn = self._lib.mcl_likelihoods_landmarks if landmark else self._lib.mcl_likelihoods_bearings
+            self._check(fn(self._ctx, _dp(p), len(p), _dp(xyz), cat.ctypes.data_as(capi.c_u32_p), len(xyz), _dp(out)))
+            return out
+        pts = _f64_rows("points", measurement, 2)
+        self._check(self._lib.mcl_likelihoods(self._ctx, _dp(p), len(p), _dp(pts), len(pts), _dp(out)))
+        return out
+
+    def likelihoods_ndt_cells(self, poses, means, covariances) -> np.ndarray:
+        """likelihoods() of an NDT filter from caller-fitted measurement cells (means (K, 2), covariances (K, 4) or (K, 2, 2))."""
+        p = _f64_rows("poses", poses, 4)
+        m = _f64_rows("means", means, 2)
+        c = np.asarray(covariances)
+        c = _f64_rows("covariances", c.reshape(len(c), 4) if c.ndim == 3 and c.shape[1:] == (2, 2) else c, 4)
+        if len(m) != len(c):
+            raise ValueError("likelihoods_ndt_cells: means and covariances differ in length")
+        out = np.empty(len(p), dtype=np.float64)
+        self._check(self._lib.mcl_likelihoods_ndt_cells(self._ctx, _dp(p), len(p), _dp(m), _dp(c), len(m), _dp(out)))
+        return out
+
+    def likelihoods_device(self, poses, points, out=None, synchronize: bool = True):
+        """likelihoods() over torch tensors already on the filter's device: poses float64 (n, 4) contiguous, the scores into `out`
+        (float64 (n,); made here if None), which is returned.  The points stay host memory.  What this saves is the two copies, not
+        the waits: the work is enqueued on the FILTER's stream, which torch does not know, so the host first waits for torch's
+        current stream (the tensors' producers) and, with synchronize (the default), for the filter's stream before the return -
+        the default is fully synchronous.  synchronize=False drops the second wait: call sync() before reading `out` or handing
+        it to torch.  A caller who needs no host wait at all orders the streams itself and calls mcl_likelihoods_device."""
+        import torch
+
+        if not isinstance(poses, torch.Tensor) or not poses.is_cuda:
+            raise TypeError("poses: expected a torch tensor on the filter's device")
+        if poses.device.index != self._cfg.device_id:
+            raise ValueError(f"poses: on device {poses.device.index}, the filter is on device {self._cfg.device_id}")
+        if poses.dtype != torch.float64:
+            raise TypeError(f"poses: expected float64, got {poses.dtype}")
+        if poses.dim() != 2 or poses.shape[1] != 4 or not poses.is_contiguous():
+            raise ValueError(f"poses: expected a contiguous tensor of shape (n, 4), got {tuple(poses.shape)}")
+        n = poses.shape[0]
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=poses.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != poses.device or out.dtype != torch.float64 or tuple(out.shape) != (n,)
+              or not out.is_contiguous()):
+            raise ValueError("out: expected a contiguous float64 tensor of shape (n,) on the poses' device")
+        pts = _f64_rows("points", points, 2)
+        torch.cuda.current_stream(poses.device).synchronize()
+        self._check(self._lib.mcl_likelihoods_device(self._ctx, poses.data_ptr(), n, _dp(pts), len(pts), out.data_ptr()))
+        if synchronize:
+            self.sync()
+        return out
 
     def weight_sum(self) -> float:
         v = C.c_double(0)

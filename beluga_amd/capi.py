@@ -162,6 +162,11 @@ _SIGNATURES = {
     "mcl_update_laser_scan": (C.c_int32, [_ctx, c_double_p, C.POINTER(LaserScan), C.POINTER(Estimate), C.POINTER(UpdateInfo)]),
     "mcl_propagate": (C.c_int32, [_ctx, c_double_p, c_double_p, C.c_uint32]),
     "mcl_reweight": (C.c_int32, [_ctx, c_double_p, C.c_uint64]),
+    "mcl_likelihoods": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, C.c_uint64, c_double_p]),
+    "mcl_likelihoods_ndt_cells": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_double_p, C.c_uint64, c_double_p]),
+    "mcl_likelihoods_landmarks": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_u32_p, C.c_uint64, c_double_p]),
+    "mcl_likelihoods_bearings": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_u32_p, C.c_uint64, c_double_p]),
+    "mcl_likelihoods_device": (C.c_int32, [_ctx, C.c_void_p, C.c_uint64, c_double_p, C.c_uint64, C.c_void_p]),
     "mcl_weight_sum": (C.c_int32, [_ctx, c_double_p]),
     "mcl_normalize": (C.c_int32, [_ctx, C.c_double, C.POINTER(WeightStats)]),
     "mcl_resample": (C.c_int32, [_ctx, C.c_double, C.c_uint32, c_u64_p]),

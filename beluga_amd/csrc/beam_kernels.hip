@@ -693,18 +693,10 @@ __device__ __forceinline__ double beam_term(const GridView& g, const BeamModel& 
 }
 
 // Variant A: one wavefront per particle, one lane per beam (small particle sets).
-// (the body: block `block` of ONE set - blockIdx.x in k_reweight_beam, a member's local block in k_batch_reweight_beam)
-__device__ __forceinline__ void reweight_beam_block(uint32_t block, const Particles& p, uint64_t n, const GridView& g, const BeamModel& m,
-                                                    const NonFreeBits& bits, const double2* __restrict__ pts, uint32_t B,
-                                                    unsigned long long* d_steps) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  double2* s_pts = reinterpret_cast<double2*>(smem);
-  for (uint32_t i = threadIdx.x; i < B; i += kBlock) s_pts[i] = pts[i];
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
-  if (i >= n) return;
-  const Pose2 src = pose_mul(g.origin_inverse, load_pose(p, i));
+// (the sum over the scan staged in s_pts for the pose `pose`, in the world frame: every lane of the wave returns it)
+__device__ __forceinline__ double beam_wave_total(uint32_t lane, const Pose2& pose, const GridView& g, const BeamModel& m, const NonFreeBits& bits,
+                                                  const double2* s_pts, uint32_t B, unsigned long long* d_steps) {
+  const Pose2 src = pose_mul(g.origin_inverse, pose);
   int sx, sy;
   cell_near(g, src.x, src.y, sx, sy);
   const double norm_hit = 1. / (sqrt(2. * kPi) * m.sigma_hit);
@@ -724,11 +716,41 @@ __device__ __forceinline__ void reweight_beam_block(uint32_t block, const Partic
     for (int o = 32; o > 0; o >>= 1) steps += __shfl_down(steps, o);
     if (lane == 0) atomicAdd(d_steps, steps);
   }
+  return total;
+}
+// (the body: block `block` of ONE set - blockIdx.x in k_reweight_beam, a member's local block in k_batch_reweight_beam)
+__device__ __forceinline__ void reweight_beam_block(uint32_t block, const Particles& p, uint64_t n, const GridView& g, const BeamModel& m,
+                                                    const NonFreeBits& bits, const double2* __restrict__ pts, uint32_t B,
+                                                    unsigned long long* d_steps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double2* s_pts = reinterpret_cast<double2*>(smem);
+  for (uint32_t i = threadIdx.x; i < B; i += kBlock) s_pts[i] = pts[i];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const double total = beam_wave_total(lane, load_pose(p, i), g, m, bits, s_pts, B, d_steps);
   if (lane == 0) p.w[i] = p.w[i] * total;
 }
 __global__ __launch_bounds__(kBlock) void k_reweight_beam(Particles p, uint64_t n, GridView g, BeamModel m, NonFreeBits bits,
                                                           const double2* __restrict__ pts, uint32_t B, unsigned long long* d_steps) {
   reweight_beam_block(blockIdx.x, p, n, g, m, bits, pts, B, d_steps);
+}
+// The sensor model as a function (mcl_likelihoods on a beam context): out[i] = the sum for the caller's pose i - the factor k_reweight_beam
+// multiplies a particle at that pose by, from its own sum (beam_wave_total).  A plain array of poses (cos, sin, x, y) in, a plain array
+// out; nothing of a filter is read or written, the cells visited are not counted.
+__global__ __launch_bounds__(kBlock) void k_likelihoods_beam(const double4* __restrict__ poses, uint64_t n, GridView g, BeamModel m, NonFreeBits bits,
+                                                             const double2* __restrict__ pts, uint32_t B, double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double2* s_pts = reinterpret_cast<double2*>(smem);
+  for (uint32_t i = threadIdx.x; i < B; i += kBlock) s_pts[i] = pts[i];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const double4 v = poses[i];
+  const double total = beam_wave_total(lane, Pose2{Rot2{v.x, v.y}, v.z, v.w}, g, m, bits, s_pts, B, nullptr);
+  if (lane == 0) out[i] = total;
 }
 // The same over a fleet's beam members (mcl_batch_update; the pattern is k_batch_reweight_lf_beams, kernels.hip): a workgroup finds its
 // member over the first_beam_block prefix - a member without a block (n = 0, an empty scan, a likelihood-field member) is never found -
@@ -1090,6 +1112,22 @@ void launch_reweight_beam(hipStream_t st, Particles p, uint64_t n, GridView g, B
   hipLaunchKernelGGL(k_reweight_beam, grid, dim3(kBlock), static_cast<size_t>(B) * sizeof(double2), st, p, n, g, m,
                      nonfree_bits ? nonfree_layout(g.W, g.H, const_cast<uint32_t*>(nonfree_bits)) : NonFreeBits{},
                      reinterpret_cast<const double2*>(d_points), B, d_steps);
+}
+
+void launch_likelihoods_beam(hipStream_t st, const double4* poses, uint64_t n, GridView g, BeamModel m, const double* d_points, uint32_t B,
+                             const uint32_t* nonfree_bits, double* out) {
+  if (n == 0) return;
+  if (B == 0) {  // (launch_reweight_beam leaves the weights as they are)
+    launch_fill(st, out, n, 1.0);
+    return;
+  }
+  const NonFreeBits bits = nonfree_bits ? nonfree_layout(g.W, g.H, const_cast<uint32_t*>(nonfree_bits)) : NonFreeBits{};
+  for (uint64_t at = 0; at < n; at += kLikelihoodsWaveChunk) {  // (a grid dimension holds 2^31 - 1 blocks)
+    const uint64_t count = std::min<uint64_t>(kLikelihoodsWaveChunk, n - at);
+    const dim3 grid(static_cast<unsigned>((count + (kBlock / kWave) - 1) / (kBlock / kWave)));
+    hipLaunchKernelGGL(k_likelihoods_beam, grid, dim3(kBlock), static_cast<size_t>(B) * sizeof(double2), st, poses + at, count, g, m, bits,
+                       reinterpret_cast<const double2*>(d_points), B, out + at);
+  }
 }
 
 BatchBeam batch_beam_record(GridView g, BeamModel m, const uint32_t* nonfree_bits, unsigned long long* d_steps) {

@@ -306,6 +306,16 @@ struct mcl_ctx {
     return LandmarkCycleFacts{landmark_small_cycle, tuning.small_fused != 0, profile != 0, n, max_live()};
   }
   bool is_landmark() const { return family() == SensorFamily::kLandmark; }
+
+  // mcl_likelihoods*: the sensor model evaluated at caller-given poses.  Buffers of the call's own - nothing the cycle reads or writes:
+  // the measurement as its kernel reads it, staged in pinned memory and copied on the stream; the host forms' poses and scores
+  // (LikelihoodsLayout, scratch_layout.h).  likelihoods_event, made on the first call, stands behind the copy of the staged
+  // measurement: the next call waits for it before it writes the staging memory again.
+  DeviceBuffer<double> d_likelihoods;
+  HostBuffer<double> h_likelihoods_meas;
+  std::vector<double> likelihoods_records;  // the NDT cells or detection records of the call, before they are staged
+  hipEvent_t likelihoods_event{nullptr};
+  bool likelihoods_in_flight{false};
   // A sensor model with a map of its own: no occupancy grid, none of the likelihood-field machinery, the host-read policy path.
   bool off_grid() const { return is_ndt() || is_landmark(); }
   // What random_intersperse's random states are drawn from (random_free_state).
@@ -1033,6 +1043,21 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
         // the beam model's small-set kernel (a wave per particle) stages the scan in 64 KB of dynamic LDS
         MCL_REQUIRE(ctx, B * sizeof(double2) <= 64 * 1024, "scan too large for the beam model's small-set kernel (4096 points)");
       return MCL_OK;
+  }
+  return MCL_OK;
+}
+
+// Caller-fitted measurement cells (means[k*2], covs[k*4]) checked and packed into `recs`, kNdtRecord doubles each: what
+// mcl_reweight_ndt_cells and mcl_likelihoods_ndt_cells hand their kernels.  Host work only.
+mcl_status ndt_cell_records(mcl_ctx* ctx, const char* who, const double* means, const double* covs, uint64_t num_cells, std::vector<double>& recs) {
+  MCL_REQUIRE(ctx, num_cells == 0 || (means && covs), "null argument");
+  MCL_REQUIRE(ctx, num_cells < (1ull << 28), "too many cells");
+  if (const mcl_status s = reweight_preconditions(ctx, 0)) return s;
+  recs.assign(static_cast<size_t>(num_cells) * kNdtRecord, 0.0);
+  for (uint64_t j = 0; j < num_cells; ++j) {
+    const double* c = covs + 4 * j;
+    MCL_REQUIRE(ctx, std::abs(c[1] - c[2]) <= 1e-12 * std::max(std::abs(c[1]), std::abs(c[2])), std::string(who) + ": asymmetric covariance");
+    ndt_pack_record(means + 2 * j, c, recs.data() + j * kNdtRecord);
   }
   return MCL_OK;
 }
@@ -2547,6 +2572,7 @@ void mcl_destroy(mcl_ctx* ctx) {
     if (RcclApi* api = rccl_api(nullptr)) (void)api->CommDestroy(ctx->rccl_comm);
   }
   if (ctx->points_event) (void)hipEventDestroy(ctx->points_event);
+  if (ctx->likelihoods_event) (void)hipEventDestroy(ctx->likelihoods_event);
   for (auto& pair : ctx->ev)
     for (auto& e : pair)
       if (e) (void)hipEventDestroy(e);
@@ -4351,16 +4377,8 @@ mcl_status mcl_get_ndt_small_cycle_counts(mcl_ctx* ctx, uint64_t* completed, uin
 mcl_status mcl_reweight_ndt_cells(mcl_ctx* ctx, const double* means, const double* covs, uint64_t num_cells) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   MCL_REQUIRE(ctx, ctx->is_ndt(), "mcl_reweight_ndt_cells: the context's sensor model is not MCL_SENSOR_NDT");
-  MCL_REQUIRE(ctx, num_cells == 0 || (means && covs), "null argument");
-  MCL_REQUIRE(ctx, num_cells < (1ull << 28), "too many cells");
-  if (const mcl_status s = reweight_preconditions(ctx, 0)) return s;
   std::vector<double>& recs = ctx->h_ndt_meas;
-  recs.assign(static_cast<size_t>(num_cells) * kNdtRecord, 0.0);
-  for (uint64_t j = 0; j < num_cells; ++j) {
-    const double* c = covs + 4 * j;
-    MCL_REQUIRE(ctx, std::abs(c[1] - c[2]) <= 1e-12 * std::max(std::abs(c[1]), std::abs(c[2])), "mcl_reweight_ndt_cells: asymmetric covariance");
-    ndt_pack_record(means + 2 * j, c, recs.data() + j * kNdtRecord);
-  }
+  if (const mcl_status s = ndt_cell_records(ctx, "mcl_reweight_ndt_cells", means, covs, num_cells, recs)) return s;
   if (const mcl_status s = bind_device(ctx)) return s;
   return do_reweight(ctx, Measurement{recs.data(), recs.size()});
 }
@@ -4512,6 +4530,186 @@ mcl_status mcl_update_landmarks(mcl_ctx* ctx, const double control_pose[4], cons
 mcl_status mcl_update_bearings(mcl_ctx* ctx, const double control_pose[4], const double* bearings_xyz, const uint32_t* categories, uint64_t n,
                                mcl_estimate* estimate, mcl_update_info* info) {
   return landmark_update(ctx, "mcl_update_bearings", MCL_SENSOR_BEARING, control_pose, bearings_xyz, categories, n, estimate, info);
+}
+
+// ---- the sensor model as a function: sensor_model(measurement)(pose) for caller-given poses (views/likelihoods.hpp:44-59) ---------------
+// Every entry checks everything first, on the host, and only then uses the device: the measurement in the form the family's kernel
+// reads (likelihoods_measurement: its own vectors, none of the cycle's), staged and copied on the context's stream (likelihoods_stage),
+// the family's kernel over the poses (likelihoods_launch).  Nothing the update cycle reads is written: not the particle sets, d_points,
+// the scan's extent and no-cell count, the set facts, the planner, the counters or the scalar block.
+struct LikelihoodsMeasurement {
+  const double* data;  // host memory, as the kernel reads it
+  uint64_t doubles;
+  uint64_t no_cell;    // likelihood-field models: points taken out because no pose gives them a cell (FieldView::acc0)
+};
+static mcl_status likelihoods_check_poses(mcl_ctx* ctx, const char* who, const double* poses, uint64_t n, const double* out) {
+  if (n == 0) return MCL_OK;
+  MCL_REQUIRE(ctx, poses && out, std::string(who) + ": null argument");
+  for (uint64_t i = 0; i < 4 * n; ++i)
+    if (!std::isfinite(poses[i])) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, std::string(who) + ": pose " + std::to_string(i / 4) + " has a value that is not finite");
+  return MCL_OK;
+}
+// The points form: mcl_reweight's checks, and the scan as stage_points would stage it (into ctx->likelihoods_records).
+static mcl_status likelihoods_points(mcl_ctx* ctx, const char* who, const double* points_xy, uint64_t num_points, LikelihoodsMeasurement* m) {
+  if (ctx->is_landmark())
+    return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": a landmark or bearing context takes mcl_likelihoods_landmarks / mcl_likelihoods_bearings");
+  MCL_REQUIRE(ctx, num_points == 0 || points_xy, "null points");
+  if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
+  std::vector<double>& recs = ctx->likelihoods_records;
+  *m = LikelihoodsMeasurement{nullptr, 0, 0};
+  switch (ctx->family()) {
+    case SensorFamily::kNdt:
+      ndt_fit_cells(points_xy, num_points, ctx->ndt_resolution, recs);
+      break;
+    case SensorFamily::kLikelihoodField:  // a point with a NaN or infinite coordinate has no cell for any pose (stage_points)
+      recs.clear();
+      recs.reserve(2 * num_points);
+      for (uint64_t i = 0; i < num_points; ++i) {
+        const double x = points_xy[2 * i], y = points_xy[2 * i + 1];
+        if (!(std::isfinite(x) && std::isfinite(y))) continue;
+        recs.push_back(x);
+        recs.push_back(y);
+      }
+      m->no_cell = num_points - recs.size() / 2;
+      break;
+    case SensorFamily::kBeam:
+      // (k_likelihoods_beam is the wave-per-pose form, whatever n is: its scan lies in 64 KB of LDS, as the reweight's small-set kernel's)
+      MCL_REQUIRE(ctx, num_points * sizeof(double2) <= 64 * 1024, std::string(who) + ": scan too large for the beam model's wave-per-pose kernel (4096 points)");
+      recs.assign(points_xy, points_xy + 2 * num_points);
+      break;
+    default: break;
+  }
+  m->data = recs.data();
+  m->doubles = recs.size();
+  return MCL_OK;
+}
+static mcl_status likelihoods_ndt_cells(mcl_ctx* ctx, const char* who, const double* means, const double* covs, uint64_t num_cells,
+                                        LikelihoodsMeasurement* m) {
+  if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the context's sensor model is not MCL_SENSOR_NDT");
+  std::vector<double>& recs = ctx->likelihoods_records;
+  if (const mcl_status s = ndt_cell_records(ctx, who, means, covs, num_cells, recs)) return s;
+  *m = LikelihoodsMeasurement{recs.data(), recs.size(), 0};
+  return MCL_OK;
+}
+static mcl_status likelihoods_detections(mcl_ctx* ctx, const char* who, int32_t kind, const double* xyz, const uint32_t* categories, uint64_t k,
+                                         LikelihoodsMeasurement* m) {
+  if (ctx->cfg.sensor_kind != kind)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the context's sensor model is not " + (kind == MCL_SENSOR_LANDMARK ? "MCL_SENSOR_LANDMARK" : "MCL_SENSOR_BEARING"));
+  std::string error;
+  if (const mcl_status s = landmark_records(who, kind, xyz, categories, k, ctx->have_landmark_map ? &ctx->landmark_ranges : nullptr,
+                                            ctx->likelihoods_records, &error))
+    return fail(ctx, s, error);
+  if (const mcl_status s = reweight_preconditions(ctx, 0)) return s;
+  *m = LikelihoodsMeasurement{ctx->likelihoods_records.data(), ctx->likelihoods_records.size(), 0};
+  return MCL_OK;
+}
+// The measurement into the device block's measurement area, behind whatever the stream holds; n_host: the poses the block also takes.
+static mcl_status likelihoods_stage(mcl_ctx* ctx, const LikelihoodsMeasurement& m, uint64_t n_host, LikelihoodsLayout* layout) {
+  const LikelihoodsLayout lay(n_host, m.doubles);
+  if (ctx->likelihoods_in_flight) {  // the previous call's copy may still be reading the staging memory
+    MCL_HIP(ctx, hipEventSynchronize(ctx->likelihoods_event));
+    ctx->likelihoods_in_flight = false;
+  }
+  if (lay.size > ctx->d_likelihoods.count) MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier call may still be using the block)
+  MCL_HIP(ctx, ctx->d_likelihoods.ensure(std::max<size_t>(lay.size, 4)));
+  *layout = lay;
+  if (m.doubles == 0) return MCL_OK;
+  MCL_HIP(ctx, ctx->h_likelihoods_meas.ensure(m.doubles, /*mapped=*/false));
+  std::copy(m.data, m.data + m.doubles, ctx->h_likelihoods_meas.host);
+  if (!ctx->likelihoods_event) MCL_HIP(ctx, hipEventCreateWithFlags(&ctx->likelihoods_event, hipEventDisableTiming));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->d_likelihoods.ptr + lay.measurement, ctx->h_likelihoods_meas.host, m.doubles * sizeof(double), hipMemcpyHostToDevice,
+                              ctx->stream));
+  MCL_HIP(ctx, hipEventRecord(ctx->likelihoods_event, ctx->stream));
+  ctx->likelihoods_in_flight = true;
+  return MCL_OK;
+}
+// The family's kernel over n poses in device memory; the measurement lies staged at d_meas.  Reads the map through the views the
+// reweight reads, as they are now (a map that mcl_set_map_async has not swapped in yet is not the context's map).
+static mcl_status likelihoods_launch(mcl_ctx* ctx, const double* d_poses, uint64_t n, const LikelihoodsMeasurement& m, const double* d_meas,
+                                     double* d_out) {
+  const double4* poses = reinterpret_cast<const double4*>(d_poses);
+  switch (ctx->family()) {
+    case SensorFamily::kLikelihoodField: {
+      FieldView f = ctx->field_view();
+      f.acc0 = lf_acc0(f.prob != 0, f.unknown_value, m.no_cell);  // (field_view() counts the CYCLE's scan)
+      launch_likelihoods_lf(ctx->stream, poses, n, f, d_meas, static_cast<uint32_t>(m.doubles / 2), ctx->tuning, d_out);
+      break;
+    }
+    case SensorFamily::kBeam: {
+      const mcl_beam_params& b = ctx->cfg.beam;
+      launch_likelihoods_beam(ctx->stream, poses, n, ctx->grid_view(), BeamModel{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range},
+                              d_meas, static_cast<uint32_t>(m.doubles / 2), ctx->map->d_nonfree_bits.ptr, d_out);
+      break;
+    }
+    case SensorFamily::kNdt: {
+      const uint32_t cells = static_cast<uint32_t>(m.doubles / kNdtRecord);
+      if (ctx->ndt_map_hashed) launch_likelihoods_ndt_hashed(ctx->stream, poses, n, ctx->ndt_hash_view, d_meas, cells, d_out);
+      else launch_likelihoods_ndt(ctx->stream, poses, n, ctx->ndt_view, d_meas, cells, d_out);
+      break;
+    }
+    case SensorFamily::kLandmark:
+      launch_likelihoods_landmarks(ctx->stream, poses, n, ctx->landmark_view, d_meas, static_cast<uint32_t>(m.doubles / kLandmarkRecord),
+                                   ctx->cfg.sensor_kind == MCL_SENSOR_BEARING, d_out);
+      break;
+  }
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("likelihoods: ") + hipGetErrorString(e));
+  return MCL_OK;
+}
+// The host forms: poses up, scores down, one synchronisation at the end.  `out` is written by that last copy alone.
+static mcl_status likelihoods_host(mcl_ctx* ctx, const double* poses, uint64_t n, const LikelihoodsMeasurement& m, double* out) {
+  if (n == 0) return MCL_OK;
+  if (const mcl_status s = bind_device(ctx)) return s;
+  LikelihoodsLayout lay(0, 0);
+  if (const mcl_status s = likelihoods_stage(ctx, m, n, &lay)) return s;
+  double* const block = ctx->d_likelihoods.ptr;
+  MCL_HIP(ctx, hipMemcpyAsync(block + lay.poses, poses, n * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (const mcl_status s = likelihoods_launch(ctx, block + lay.poses, n, m, block + lay.measurement, block + lay.out)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MCL_HIP(ctx, hipMemcpy(out, block + lay.out, n * sizeof(double), hipMemcpyDeviceToHost));
+  return MCL_OK;
+}
+
+mcl_status mcl_likelihoods(mcl_ctx* ctx, const double* poses, uint64_t n, const double* points_xy, uint64_t num_points, double* out) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  LikelihoodsMeasurement m{};
+  if (const mcl_status s = likelihoods_points(ctx, "mcl_likelihoods", points_xy, num_points, &m)) return s;
+  if (const mcl_status s = likelihoods_check_poses(ctx, "mcl_likelihoods", poses, n, out)) return s;
+  return likelihoods_host(ctx, poses, n, m, out);
+}
+mcl_status mcl_likelihoods_ndt_cells(mcl_ctx* ctx, const double* poses, uint64_t n, const double* means, const double* covs, uint64_t num_cells,
+                                     double* out) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  LikelihoodsMeasurement m{};
+  if (const mcl_status s = likelihoods_ndt_cells(ctx, "mcl_likelihoods_ndt_cells", means, covs, num_cells, &m)) return s;
+  if (const mcl_status s = likelihoods_check_poses(ctx, "mcl_likelihoods_ndt_cells", poses, n, out)) return s;
+  return likelihoods_host(ctx, poses, n, m, out);
+}
+mcl_status mcl_likelihoods_landmarks(mcl_ctx* ctx, const double* poses, uint64_t n, const double* positions_xyz, const uint32_t* categories,
+                                     uint64_t k, double* out) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  LikelihoodsMeasurement m{};
+  if (const mcl_status s = likelihoods_detections(ctx, "mcl_likelihoods_landmarks", MCL_SENSOR_LANDMARK, positions_xyz, categories, k, &m)) return s;
+  if (const mcl_status s = likelihoods_check_poses(ctx, "mcl_likelihoods_landmarks", poses, n, out)) return s;
+  return likelihoods_host(ctx, poses, n, m, out);
+}
+mcl_status mcl_likelihoods_bearings(mcl_ctx* ctx, const double* poses, uint64_t n, const double* bearings_xyz, const uint32_t* categories,
+                                    uint64_t k, double* out) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  LikelihoodsMeasurement m{};
+  if (const mcl_status s = likelihoods_detections(ctx, "mcl_likelihoods_bearings", MCL_SENSOR_BEARING, bearings_xyz, categories, k, &m)) return s;
+  if (const mcl_status s = likelihoods_check_poses(ctx, "mcl_likelihoods_bearings", poses, n, out)) return s;
+  return likelihoods_host(ctx, poses, n, m, out);
+}
+mcl_status mcl_likelihoods_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* points_xy, uint64_t num_points, double* d_out) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  LikelihoodsMeasurement m{};
+  if (const mcl_status s = likelihoods_points(ctx, "mcl_likelihoods_device", points_xy, num_points, &m)) return s;
+  MCL_REQUIRE(ctx, n == 0 || (d_poses && d_out), "mcl_likelihoods_device: null argument");
+  if (n == 0) return MCL_OK;
+  if (const mcl_status s = bind_device(ctx)) return s;
+  LikelihoodsLayout lay(0, 0);
+  if (const mcl_status s = likelihoods_stage(ctx, m, 0, &lay)) return s;
+  return likelihoods_launch(ctx, d_poses, n, m, ctx->d_likelihoods.ptr + lay.measurement, d_out);
 }
 
 mcl_status mcl_sync(mcl_ctx* ctx) {

@@ -234,6 +234,27 @@ void launch_reweight_bearings(hipStream_t st, Particles p, uint64_t n, const Lan
 void launch_reweight_landmarks_wave(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k);
 void launch_reweight_bearings_wave(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k);
 
+// ---- the sensor model as a function (mcl_likelihoods*): out[i] = sensor_model(measurement)(poses[i]) -------------------------------------
+// The factor a reweight kernel multiplies the weight of a particle at poses[i] by, computed by that kernel's own per-pose functions, for
+// n caller-given poses (cos, sin, x, y) in the caller's order.  Plain arrays in device memory: no particle set, no order, no weight.
+// A launcher chunks its launches where a grid dimension would overflow; n is limited by memory alone.
+constexpr uint64_t kLikelihoodsWaveMax = 4096;               // NDT, landmark, bearing: a wave per pose up to here, a lane per pose above
+constexpr uint64_t kLikelihoodsLaneChunk = 1ull << 38;       // poses per launch of a lane-per-pose kernel (2^30 blocks of 256)
+constexpr uint64_t kLikelihoodsWaveChunk = 1ull << 32;       // ... of a wave-per-pose kernel (2^30 blocks of four waves)
+// Likelihood-field models (kernels.hip): a wave per pose, the lanes over the beams, the scan staged in LDS where it fits beside the
+// palette (else read from memory); a field without a palette: a lane per pose over the f32 field.  f.acc0 as stage_points would set it.
+void launch_likelihoods_lf(hipStream_t st, const double4* poses, uint64_t n, const FieldView& f, const double* d_points, uint32_t B,
+                           const Tuning& tuning, double* out);
+// Beam model (beam_kernels.hip): k_reweight_beam's form, a wave per pose over the scan staged in LDS (B <= 4096 points); no cell count.
+// B == 0: 1.0, as launch_reweight_beam leaves the weights.
+void launch_likelihoods_beam(hipStream_t st, const double4* poses, uint64_t n, GridView g, BeamModel m, const double* d_points, uint32_t B,
+                             const uint32_t* nonfree_bits, double* out);
+void launch_likelihoods_ndt(hipStream_t st, const double4* poses, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k, double* out);
+void launch_likelihoods_ndt_hashed(hipStream_t st, const double4* poses, uint64_t n, const NdtHashView& m, const double* meas, uint32_t k, double* out);
+// k <= kLandmarkMaxDetections; k == 0: 1.0.  bearing: the records sorted by category, as launch_reweight_bearings takes them.
+void launch_likelihoods_landmarks(hipStream_t st, const double4* poses, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k,
+                                  bool bearing, double* out);
+
 struct HashParams {
   double res_x, res_y, res_theta;
 };

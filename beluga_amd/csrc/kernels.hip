@@ -1722,6 +1722,99 @@ __global__ __launch_bounds__(kBlock) void k_lf_combine(double* __restrict__ w, u
 }
 
 // [lf-kernels-end]
+// -- the likelihood-field models as functions (mcl_likelihoods) ---------------------------------------------------------------------
+// out[i] = sensor_model(scan)(poses[i]) for caller-given poses, in the caller's order: 1 + sum pz^3, or exp(sum log pz) for the prob model.
+// k_reweight_lf_beams' form - a wave per pose (per_wave poses one after the other), the lanes over the beams - from its own pieces: the
+// field-frame pose by ordered_pose, the end-points by the separately rounded arithmetic, the cells by floor_rd_*, the terms by
+// lf_palette_fetch / lf_palette_value, a lane's beams added in scan order (lane, lane + 64, ...), the lanes by wave_sum_f64, then
+// f.acc0 + that: the same bits as that kernel's factor.  What differs is around it: a plain array of poses in, a plain array out - no
+// particle set, no weight - and the scan staged in LDS behind the palette (kStaged; 16 bytes per beam) where the two fit 64 KB, so
+// that a beam is one LDS read for every pose of the workgroup.  (It stands behind the marker above, and k_reweight_lf_beams' body is
+// restated, not shared: the traffic record is keyed by the source between the markers.)
+// Workgroup memory: [0, (H+2)*4) row offsets, [pal_base, ...) the palette - absolute addresses, as the palette kernels have them - and
+// the scan at pts_at, a multiple of 16.
+template <bool kStaged>
+__global__ __launch_bounds__(kBeamsBlock) void k_likelihoods_lf(const double4* __restrict__ poses, uint64_t n, FieldView f,
+                                                                const double2* __restrict__ pts, uint32_t B, uint32_t per_wave, uint32_t pts_at,
+                                                                double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  {
+    uint32_t* s_row = reinterpret_cast<uint32_t*>(smem);
+    for (uint32_t j = threadIdx.x; j < f.H + 2; j += kBeamsBlock) s_row[j] = palette_row_offset(static_cast<int32_t>(j) - 1, f.pal_pitch);
+    double* s_pal = reinterpret_cast<double*>(smem + f.pal_base);
+    for (uint32_t k = threadIdx.x; k < f.pal_count; k += kBeamsBlock) s_pal[k] = f.pal_val[k];
+    if constexpr (kStaged) {
+      double2* s_pts = reinterpret_cast<double2*>(smem + pts_at);
+      for (uint32_t b = threadIdx.x; b < B; b += kBeamsBlock) s_pts[b] = pts[b];
+    }
+  }
+  __syncthreads();
+  const double2* const scan = kStaged ? reinterpret_cast<const double2*>(smem + pts_at) : pts;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t tile = static_cast<uint64_t>(blockIdx.x) * (kBeamsBlock / kWave) + (threadIdx.x >> 6);
+  const uint64_t base = tile * per_wave;
+  if (base >= n) return;
+  const uint32_t cnt = static_cast<uint32_t>(n - base < per_wave ? n - base : per_wave);
+  const uint64_t i = base + lane;
+  Pose2 T = pose_identity();  // (a lane without a pose: never broadcast below)
+  if (lane < cnt) T = ordered_pose(f.world_to_field, poses, i, false);  // likelihood_field_model.hpp:70
+  const __amdgpu_buffer_rsrc_t rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(f.pal_idx), 0, static_cast<int>(f.pal_bytes), 0x00020000);
+  const uint32_t full = B & ~255u;  // beams taken four per lane at a time (their gathers in flight together)
+  double mine = 0.0;
+#pragma unroll 1
+  for (uint32_t q = 0; q < cnt; ++q) {
+    const double ct = readlane_f64(T.r.c, q), st = readlane_f64(T.r.s, q);
+    const double xt = readlane_f64(T.x, q), yt = readlane_f64(T.y, q);
+    double acc = 0.0;
+#pragma unroll 1
+    for (uint32_t b0 = 0; b0 < full; b0 += 256) {
+      double v[8];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const double2 pt = scan[b0 + 64 * k + lane];
+        v[2 * k] = (pt.x * ct - pt.y * st + xt) * f.inv_resolution;
+        v[2 * k + 1] = (pt.x * st + pt.y * ct + yt) * f.inv_resolution;
+      }
+      floor_rd_8(v);
+      uint32_t e[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e[k] = lf_palette_fetch(rsrc, f, floor_rd_result(v[2 * k]), floor_rd_result(v[2 * k + 1]), 0u);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc += lf_palette_value(e[k]);
+    }
+    for (uint32_t b = full + lane; b < B; b += kWave) {
+      const double2 pt = scan[b];
+      double vx = (pt.x * ct - pt.y * st + xt) * f.inv_resolution, vy = (pt.x * st + pt.y * ct + yt) * f.inv_resolution;
+      floor_rd_2(vx, vy);
+      acc += lf_palette_value(lf_palette_fetch(rsrc, f, floor_rd_result(vx), floor_rd_result(vy), 0u));
+    }
+    const double total = wave_sum_f64(acc);
+    if (lane == q) mine = total;
+  }
+  if (lane < cnt) out[i] = f.prob ? exp(f.acc0 + mine) : f.acc0 + mine;
+}
+// A field with too many distinct values for a palette: a lane per pose over the f32 field, the scan through scalar loads, the terms by
+// lf_beam and added as the index-order reweight adds them (sum4 from f.acc0 on: k_reweight_lf_sorted<false> without an order).
+__global__ __launch_bounds__(kBlock) void k_likelihoods_lf_field(const double4* __restrict__ poses, uint64_t n, FieldView f,
+                                                                 const double* __restrict__ pts, uint32_t B, double* __restrict__ out) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const Pose2 T = ordered_pose(f.world_to_field, poses, i, false);  // likelihood_field_model.hpp:70
+  const double ct = T.r.c, st = T.r.s, xt = T.x, yt = T.y;
+  double acc = f.acc0;
+  uint32_t b = 0;
+#pragma unroll 2
+  for (; b + 4 <= B; b += 4) {
+    double t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t[k] = lf_beam(f, pts[2 * (b + k)], pts[2 * (b + k) + 1], ct, st, xt, yt);
+    acc += sum4(t[0], t[1], t[2], t[3]);
+  }
+  for (; b < B; ++b) acc += lf_beam(f, pts[2 * b], pts[2 * b + 1], ct, st, xt, yt);
+  out[i] = f.prob ? exp(acc) : acc;
+}
+
 // -- spatial ordering of the particles --------------------------------------------------------------
 // A full sort of (key, index) by the 20-bit ordering key, most significant digit first, two digits of 10 bits:
 //   keys + block histograms of the HIGH digit (inside k_propagate, or k_order_keys)  ->  row scan (+ digit totals)  ->
@@ -4618,6 +4711,35 @@ LfLaunch launch_reweight_lf(hipStream_t st, const LfReweightArgs& a, const Tunin
     launched.kernel = LfKernel::kIndexOrder;
   }
   return launched;
+}
+
+void launch_likelihoods_lf(hipStream_t st, const double4* poses, uint64_t n, const FieldView& f, const double* d_points, uint32_t B,
+                           const Tuning& tuning, double* out) {
+  if (n == 0) return;
+  if (!lf_palette_ok(f, tuning)) {
+    for (uint64_t at = 0; at < n; at += kLikelihoodsLaneChunk) {  // (a grid dimension holds 2^31 - 1 blocks)
+      const uint64_t count = std::min<uint64_t>(kLikelihoodsLaneChunk, n - at);
+      hipLaunchKernelGGL(k_likelihoods_lf_field, dim3(blocks_for(count)), dim3(kBlock), 0, st, poses + at, count, f, d_points, B, out + at);
+    }
+    return;
+  }
+  // poses per wave as launch_reweight_lf has them for k_reweight_lf_beams: enough waves to fill the chip (4096) before a wave takes a second
+  const uint32_t per_wave = static_cast<uint32_t>(std::min<uint64_t>(kWave, std::max<uint64_t>(1, (n + 4095) / 4096)));
+  const uint32_t pts_at = (static_cast<uint32_t>(lf_palette_lds(f)) + 15u) & ~15u;
+  const size_t staged_lds = static_cast<size_t>(pts_at) + static_cast<size_t>(B) * sizeof(double2);
+  const bool staged = B != 0 && staged_lds <= 65536;
+  const uint64_t chunk = kLikelihoodsWaveChunk * per_wave;
+  for (uint64_t at = 0; at < n; at += chunk) {
+    const uint64_t count = std::min<uint64_t>(chunk, n - at);
+    const uint64_t tiles = (count + per_wave - 1) / per_wave;
+    const dim3 grid(static_cast<unsigned>((tiles + (kBeamsBlock / kWave) - 1) / (kBeamsBlock / kWave)));
+    if (staged)
+      hipLaunchKernelGGL(k_likelihoods_lf<true>, grid, dim3(kBeamsBlock), staged_lds, st, poses + at, count, f,
+                         reinterpret_cast<const double2*>(d_points), B, per_wave, pts_at, out + at);
+    else
+      hipLaunchKernelGGL(k_likelihoods_lf<false>, grid, dim3(kBeamsBlock), lf_palette_lds(f), st, poses + at, count, f,
+                         reinterpret_cast<const double2*>(d_points), B, per_wave, pts_at, out + at);
+  }
 }
 
 }  // namespace mcl

@@ -99,11 +99,8 @@ __device__ __forceinline__ double landmark_term(const LandmarkMapView& m, const 
   return landmark_match_term(m, q, s, match);
 }
 
-__global__ __launch_bounds__(kBlock) void k_reweight_landmarks(Particles p, uint64_t n, LandmarkMapView m, const double* __restrict__ det,
-                                                               uint32_t k) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const Pose2 s = load_pose(p, i);
+// the product over the k detections for the pose s, as a lane multiplies it: what a particle's weight is multiplied by
+__device__ __forceinline__ double landmark_lane_product(const LandmarkMapView& m, const double* __restrict__ det, uint32_t k, const Pose2& s) {
   // std::transform_reduce(detections, 1.0, multiplies, ...) (:155) as libstdc++ multiplies it: blocks of four, the rest one by one
   double acc = 1.0;
   uint32_t j = 0;
@@ -115,7 +112,13 @@ __global__ __launch_bounds__(kBlock) void k_reweight_landmarks(Particles p, uint
     acc = acc * ((t0 * t1) * (t2 * t3));
   }
   for (; j < k; ++j) acc = acc * landmark_term(m, det + j * kLandmarkRecord, s);
-  p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
+  return acc;
+}
+__global__ __launch_bounds__(kBlock) void k_reweight_landmarks(Particles p, uint64_t n, LandmarkMapView m, const double* __restrict__ det,
+                                                               uint32_t k) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  p.w[i] *= landmark_lane_product(m, det, k, load_pose(p, i));  // actions::reweight (actions/reweight.hpp:53-60)
 }
 
 // The bearing model.  sensor_pose_in_world = robot * sensor_pose_in_robot (bearing_sensor_model.hpp:107): rotation Rz Rs, translation
@@ -155,14 +158,10 @@ __device__ __forceinline__ double bearing_match_term(const LandmarkMapView& m, c
 // of its landmark in the category - lives in LDS, k slots per lane, [slot][lane] (each lane touches its own column only: no barrier,
 // no bank conflict); the slot is the detection's place in the caller's order, and once the run is searched it holds the detection's
 // term, so that the product at the end follows the caller's order in blocks of four.
-__global__ __launch_bounds__(kWave) void k_reweight_bearings(Particles p, uint64_t n, LandmarkMapView m, const double* __restrict__ det,
-                                                             uint32_t k) {
-  extern __shared__ double s_value[];                                      // [k][kWave]
-  uint32_t* s_pick = reinterpret_cast<uint32_t*>(s_value + k * kWave);     // [k][kWave]
-  const uint32_t lane = threadIdx.x;
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWave + lane;
-  if (i >= n) return;
-  const SensorFrame f = sensor_frame(m, load_pose(p, i));
+// (the product itself for the pose s, by the lane `lane` of a one-wave workgroup: s_value and s_pick are its [k][kWave] columns)
+__device__ __forceinline__ double bearings_lane_product(const LandmarkMapView& m, const double* __restrict__ det, uint32_t k, const Pose2& s,
+                                                        uint32_t lane, double* s_value, uint32_t* s_pick) {
+  const SensorFrame f = sensor_frame(m, s);
   for (uint32_t j = 0; j < k;) {
     const Detection head = load_detection(det + j * kLandmarkRecord);
     if (head.count == 0) {  // no landmark of that category: 0.0 (bearing_sensor_model.hpp:115-117)
@@ -200,7 +199,16 @@ __global__ __launch_bounds__(kWave) void k_reweight_bearings(Particles p, uint64
     acc = acc * ((t0 * t1) * (t2 * t3));
   }
   for (; j < k; ++j) acc = acc * s_value[j * kWave + lane];
-  p.w[i] *= acc;
+  return acc;
+}
+__global__ __launch_bounds__(kWave) void k_reweight_bearings(Particles p, uint64_t n, LandmarkMapView m, const double* __restrict__ det,
+                                                             uint32_t k) {
+  extern __shared__ double s_value[];                                      // [k][kWave]
+  uint32_t* s_pick = reinterpret_cast<uint32_t*>(s_value + k * kWave);     // [k][kWave]
+  const uint32_t lane = threadIdx.x;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWave + lane;
+  if (i >= n) return;
+  p.w[i] *= bearings_lane_product(m, det, k, load_pose(p, i), lane, s_value, s_pick);
 }
 
 // ---- a wave per particle (small sets: mcl_set_landmark_small_cycle) -------------------------------------------------------------------
@@ -256,13 +264,9 @@ __device__ __forceinline__ double chained_product(double term, uint32_t k, uint3
   return acc;
 }
 
-// (the bodies: block `block` of ONE set - blockIdx.x in the lone kernels, a member's local block in k_batch_reweight_landmarks)
-__device__ __forceinline__ void reweight_landmarks_wave_block(uint32_t block, const Particles& p, uint64_t n, const LandmarkMapView& m,
-                                                              const double* __restrict__ det, uint32_t k) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
-  if (i >= n || k == 0 || k > static_cast<uint32_t>(kWave)) return;  // (the whole wave)
-  const Pose2 s = load_pose(p, i);
+// (the products themselves, for the pose s and 1 <= k <= kWave detections: every lane of the wave returns the product)
+__device__ __forceinline__ double landmarks_wave_product(uint32_t lane, const Pose2& s, const LandmarkMapView& m, const double* __restrict__ det,
+                                                         uint32_t k) {
   const GroupShape shape = group_shape(k);
   const uint32_t j = lane >> shape.shift, r = lane & (shape.g - 1);
   const bool mine = j < k;
@@ -283,18 +287,13 @@ __device__ __forceinline__ void reweight_landmarks_wave_block(uint32_t block, co
   group_reduce<false>(shape.g, &best, &at);
   double term = 1.0;
   if (mine && r == 0) term = q.count == 0 ? m.random_prob : landmark_match_term(m, q, s, load_landmark(m.landmarks, q.first + at));
-  const double acc = chained_product(term, k, shape.shift);  // record order
-  if (lane == 0) p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
+  return chained_product(term, k, shape.shift);  // record order
 }
-
 // The bearing model.  A record's term goes to the slot of its `place` in the wave's row of workgroup memory (the records arrive sorted
 // by category, the product follows the caller's order); lane t then takes slot t back and the chain runs over the lanes 0 .. k-1.
-__device__ __forceinline__ void reweight_bearings_wave_block(uint32_t block, const Particles& p, uint64_t n, const LandmarkMapView& m,
-                                                             const double* __restrict__ det, uint32_t k, double* s_terms /* [kBlock] */) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
-  if (i >= n || k == 0 || k > static_cast<uint32_t>(kWave)) return;  // (the whole wave)
-  const SensorFrame f = sensor_frame(m, load_pose(p, i));
+__device__ __forceinline__ double bearings_wave_product(uint32_t lane, const Pose2& s, const LandmarkMapView& m, const double* __restrict__ det,
+                                                        uint32_t k, double* s_terms /* [kBlock] */) {
+  const SensorFrame f = sensor_frame(m, s);
   const GroupShape shape = group_shape(k);
   const uint32_t j = lane >> shape.shift, r = lane & (shape.g - 1);
   const bool mine = j < k;
@@ -321,7 +320,24 @@ __device__ __forceinline__ void reweight_bearings_wave_block(uint32_t block, con
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   const double term = lane < k ? row[lane] : 1.0;
-  const double acc = chained_product(term, k, 0);  // the caller's order
+  return chained_product(term, k, 0);  // the caller's order
+}
+
+// (the bodies: block `block` of ONE set - blockIdx.x in the lone kernels, a member's local block in k_batch_reweight_landmarks)
+__device__ __forceinline__ void reweight_landmarks_wave_block(uint32_t block, const Particles& p, uint64_t n, const LandmarkMapView& m,
+                                                              const double* __restrict__ det, uint32_t k) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n || k == 0 || k > static_cast<uint32_t>(kWave)) return;  // (the whole wave)
+  const double acc = landmarks_wave_product(lane, load_pose(p, i), m, det, k);
+  if (lane == 0) p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
+}
+__device__ __forceinline__ void reweight_bearings_wave_block(uint32_t block, const Particles& p, uint64_t n, const LandmarkMapView& m,
+                                                             const double* __restrict__ det, uint32_t k, double* s_terms /* [kBlock] */) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n || k == 0 || k > static_cast<uint32_t>(kWave)) return;  // (the whole wave)
+  const double acc = bearings_wave_product(lane, load_pose(p, i), m, det, k, s_terms);
   if (lane == 0) p.w[i] *= acc;
 }
 
@@ -333,6 +349,41 @@ __global__ __launch_bounds__(kBlock) void k_reweight_bearings_wave(Particles p, 
                                                                    uint32_t k) {
   __shared__ double s_terms[kBlock];
   reweight_bearings_wave_block(blockIdx.x, p, n, m, det, k, s_terms);
+}
+
+// The sensor models as functions (mcl_likelihoods_landmarks, mcl_likelihoods_bearings): out[i] = the product for the caller's pose i - the
+// factor the reweight kernels above multiply a particle at that pose by, from their own products (the same bits from the lane and the
+// wave form).  A plain array of poses (cos, sin, x, y) in, a plain array out; nothing of a filter is read or written.
+__device__ __forceinline__ Pose2 pose_at(const double4* __restrict__ poses, uint64_t i) {
+  const double4 v = poses[i];
+  return Pose2{Rot2{v.x, v.y}, v.z, v.w};
+}
+__global__ __launch_bounds__(kBlock) void k_likelihoods_landmarks(const double4* __restrict__ poses, uint64_t n, LandmarkMapView m,
+                                                                  const double* __restrict__ det, uint32_t k, double* __restrict__ out) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  out[i] = landmark_lane_product(m, det, k, pose_at(poses, i));
+}
+__global__ __launch_bounds__(kWave) void k_likelihoods_bearings(const double4* __restrict__ poses, uint64_t n, LandmarkMapView m,
+                                                                const double* __restrict__ det, uint32_t k, double* __restrict__ out) {
+  extern __shared__ double s_value[];                                      // [k][kWave]
+  uint32_t* s_pick = reinterpret_cast<uint32_t*>(s_value + k * kWave);     // [k][kWave]
+  const uint32_t lane = threadIdx.x;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kWave + lane;
+  if (i >= n) return;
+  out[i] = bearings_lane_product(m, det, k, pose_at(poses, i), lane, s_value, s_pick);
+}
+template <bool kBearing>
+__global__ __launch_bounds__(kBlock) void k_likelihoods_landmarks_wave(const double4* __restrict__ poses, uint64_t n, LandmarkMapView m,
+                                                                       const double* __restrict__ det, uint32_t k, double* __restrict__ out) {
+  __shared__ double s_terms[kBearing ? kBlock : 1];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n || k == 0 || k > static_cast<uint32_t>(kWave)) return;  // (the whole wave)
+  double acc;
+  if constexpr (kBearing) acc = bearings_wave_product(lane, pose_at(poses, i), m, det, k, s_terms);
+  else acc = landmarks_wave_product(lane, pose_at(poses, i), m, det, k);
+  if (lane == 0) out[i] = acc;
 }
 
 // The same over a fleet's landmark and bearing members (mcl_landmark_batch_update; the pattern is k_batch_reweight_ndt): a workgroup finds
@@ -368,6 +419,35 @@ void launch_reweight_landmarks_wave(hipStream_t st, Particles p, uint64_t n, con
 void launch_reweight_bearings_wave(hipStream_t st, Particles p, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k) {
   if (n == 0 || k == 0) return;
   hipLaunchKernelGGL(k_reweight_bearings_wave, dim3(batch_landmark_blocks(n, k)), dim3(kBlock), 0, st, p, n, m, detections, k);
+}
+
+void launch_likelihoods_landmarks(hipStream_t st, const double4* poses, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k,
+                                  bool bearing, double* out) {
+  if (n == 0) return;
+  if (k == 0) {  // (no detection: the product is 1.0)
+    launch_fill(st, out, n, 1.0);
+    return;
+  }
+  if (n <= kLikelihoodsWaveMax) {
+    const dim3 grid(batch_landmark_blocks(n, k));
+    if (bearing) hipLaunchKernelGGL(k_likelihoods_landmarks_wave<true>, grid, dim3(kBlock), 0, st, poses, n, m, detections, k, out);
+    else hipLaunchKernelGGL(k_likelihoods_landmarks_wave<false>, grid, dim3(kBlock), 0, st, poses, n, m, detections, k, out);
+    return;
+  }
+  if (bearing) {
+    const size_t lds = static_cast<size_t>(k) * kWave * (sizeof(double) + sizeof(uint32_t));  // <= 48 KB at kLandmarkMaxDetections
+    constexpr uint64_t chunk = kLikelihoodsLaneChunk / (kBlock / kWave);  // (a one-wave workgroup: 2^30 blocks of 64)
+    for (uint64_t at = 0; at < n; at += chunk) {
+      const uint64_t count = std::min<uint64_t>(chunk, n - at);
+      hipLaunchKernelGGL(k_likelihoods_bearings, dim3(static_cast<unsigned>((count + kWave - 1) / kWave)), dim3(kWave), lds, st, poses + at, count, m,
+                         detections, k, out + at);
+    }
+    return;
+  }
+  for (uint64_t at = 0; at < n; at += kLikelihoodsLaneChunk) {
+    const uint64_t count = std::min<uint64_t>(kLikelihoodsLaneChunk, n - at);
+    hipLaunchKernelGGL(k_likelihoods_landmarks, dim3(blocks_for(count)), dim3(kBlock), 0, st, poses + at, count, m, detections, k, out + at);
+  }
 }
 
 void launch_batch_reweight_landmarks(hipStream_t st, const BatchItem* d_items, uint32_t members, uint32_t blocks) {

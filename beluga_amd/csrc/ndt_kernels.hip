@@ -70,11 +70,9 @@ __device__ __forceinline__ double ndt_cell_likelihood(const View& m, const doubl
   return likelihood > m.minimum_likelihood ? likelihood : m.minimum_likelihood;  // std::max(likelihood, minimum_likelihood)
 }
 
+// 1 + the sum over the k measurement cells for the pose s, as a lane adds it: what a particle's weight is multiplied by.
 template <class View>
-__device__ __forceinline__ void reweight_ndt_lanes(const Particles& p, uint64_t n, const View& m, const double* __restrict__ meas, uint32_t k) {
-  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const Pose2 s = load_pose(p, i);
+__device__ __forceinline__ double ndt_lane_sum(const Pose2& s, const View& m, const double* __restrict__ meas, uint32_t k) {
   // std::transform_reduce(cells, 1.0, plus, ...) (ndt_sensor_model.hpp:219-224) as libstdc++ adds it: blocks of four, the rest one by one
   double acc = 1.0;
   uint32_t j = 0;
@@ -86,7 +84,13 @@ __device__ __forceinline__ void reweight_ndt_lanes(const Particles& p, uint64_t 
     acc += sum4(l0, l1, l2, l3);
   }
   for (; j < k; ++j) acc += ndt_cell_likelihood(m, meas + j * kNdtRecord, s);
-  p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
+  return acc;
+}
+template <class View>
+__device__ __forceinline__ void reweight_ndt_lanes(const Particles& p, uint64_t n, const View& m, const double* __restrict__ meas, uint32_t k) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  p.w[i] *= ndt_lane_sum(load_pose(p, i), m, meas, k);  // actions::reweight (actions/reweight.hpp:53-60)
 }
 __global__ __launch_bounds__(kBlock) void k_reweight_ndt(Particles p, uint64_t n, NdtMapView m, const double* __restrict__ meas, uint32_t k) {
   reweight_ndt_lanes(p, n, m, meas, k);
@@ -102,13 +106,9 @@ __global__ __launch_bounds__(kBlock) void k_reweight_ndt_hashed(Particles p, uin
 // quad holds exactly sum4), and the quad sums are chained into the running sum in cell order through v_readlane; the last K mod 4 cells
 // follow one by one.  Every lane carries the same running sum.  No workgroup memory, no atomics.
 // (the body: block `block` of ONE set - blockIdx.x in k_reweight_ndt_wave, a member's local block in k_batch_reweight_ndt)
+// (the sum itself, for the pose s: every lane of the wave returns it)
 template <class View>
-__device__ __forceinline__ void reweight_ndt_wave_block(uint32_t block, const Particles& p, uint64_t n, const View& m,
-                                                        const double* __restrict__ meas, uint32_t k) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
-  if (i >= n) return;  // (the whole wave)
-  const Pose2 s = load_pose(p, i);
+__device__ __forceinline__ double ndt_wave_sum(uint32_t lane, const Pose2& s, const View& m, const double* __restrict__ meas, uint32_t k) {
   double acc = 1.0;
   for (uint32_t base = 0; base < k; base += kWave) {
     const uint32_t j = base + lane;
@@ -124,6 +124,15 @@ __device__ __forceinline__ void reweight_ndt_wave_block(uint32_t block, const Pa
     if (left < kWave)
       for (uint32_t r = 4 * full; r < left; ++r) acc += readlane_f64(l, static_cast<int>(r));
   }
+  return acc;
+}
+template <class View>
+__device__ __forceinline__ void reweight_ndt_wave_block(uint32_t block, const Particles& p, uint64_t n, const View& m,
+                                                        const double* __restrict__ meas, uint32_t k) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(block) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n) return;  // (the whole wave)
+  const double acc = ndt_wave_sum(lane, load_pose(p, i), m, meas, k);
   if (lane == 0) p.w[i] *= acc;  // actions::reweight (actions/reweight.hpp:53-60)
 }
 __global__ __launch_bounds__(kBlock) void k_reweight_ndt_wave(Particles p, uint64_t n, NdtMapView m, const double* __restrict__ meas, uint32_t k) {
@@ -132,6 +141,42 @@ __global__ __launch_bounds__(kBlock) void k_reweight_ndt_wave(Particles p, uint6
 __global__ __launch_bounds__(kBlock) void k_reweight_ndt_wave_hashed(Particles p, uint64_t n, NdtHashView m, const double* __restrict__ meas, uint32_t k) {
   reweight_ndt_wave_block(blockIdx.x, p, n, m, meas, k);
 }
+// The sensor model as a function (mcl_likelihoods, mcl_likelihoods_ndt_cells): out[i] = 1 + the sum for the caller's pose i - the factor the
+// reweight kernels above multiply a particle at that pose by, from their own sums (ndt_lane_sum, ndt_wave_sum: the same bits from
+// either).  A plain array of poses (cos, sin, x, y) in, a plain array out; nothing of a filter is read or written.
+__device__ __forceinline__ Pose2 pose_at(const double4* __restrict__ poses, uint64_t i) {
+  const double4 v = poses[i];
+  return Pose2{Rot2{v.x, v.y}, v.z, v.w};
+}
+template <class View>
+__global__ __launch_bounds__(kBlock) void k_likelihoods_ndt(const double4* __restrict__ poses, uint64_t n, View m, const double* __restrict__ meas,
+                                                            uint32_t k, double* __restrict__ out) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= n) return;
+  out[i] = ndt_lane_sum(pose_at(poses, i), m, meas, k);
+}
+template <class View>
+__global__ __launch_bounds__(kBlock) void k_likelihoods_ndt_wave(const double4* __restrict__ poses, uint64_t n, View m,
+                                                                 const double* __restrict__ meas, uint32_t k, double* __restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n) return;  // (the whole wave)
+  const double acc = ndt_wave_sum(lane, pose_at(poses, i), m, meas, k);
+  if (lane == 0) out[i] = acc;
+}
+template <class View>
+void launch_likelihoods_ndt_view(hipStream_t st, const double4* poses, uint64_t n, const View& m, const double* meas, uint32_t k, double* out) {
+  if (n == 0) return;
+  if (n <= kLikelihoodsWaveMax) {
+    hipLaunchKernelGGL(k_likelihoods_ndt_wave<View>, dim3(batch_ndt_blocks(n, 1)), dim3(kBlock), 0, st, poses, n, m, meas, k, out);
+    return;
+  }
+  for (uint64_t at = 0; at < n; at += kLikelihoodsLaneChunk) {  // (a grid dimension holds 2^31 - 1 blocks)
+    const uint64_t count = std::min<uint64_t>(kLikelihoodsLaneChunk, n - at);
+    hipLaunchKernelGGL(k_likelihoods_ndt<View>, dim3(blocks_for(count)), dim3(kBlock), 0, st, poses + at, count, m, meas, k, out + at);
+  }
+}
+
 // The same over a fleet's NDT members (mcl_batch_update; the pattern is k_batch_reweight_beam, beam_kernels.hip): a workgroup finds its
 // member over the first_ndt_block prefix - a member without a block (n = 0, no measurement cell, another family's member) is never found -
 // and runs the body with its LOCAL block number on the member's own map and staged cells.
@@ -158,6 +203,12 @@ void launch_reweight_ndt_hashed(hipStream_t st, Particles p, uint64_t n, const N
 void launch_reweight_ndt_wave_hashed(hipStream_t st, Particles p, uint64_t n, const NdtHashView& m, const double* meas, uint32_t k) {
   if (n == 0) return;
   hipLaunchKernelGGL(k_reweight_ndt_wave_hashed, dim3(batch_ndt_blocks(n, 1)), dim3(kBlock), 0, st, p, n, m, meas, k);
+}
+void launch_likelihoods_ndt(hipStream_t st, const double4* poses, uint64_t n, const NdtMapView& m, const double* meas, uint32_t k, double* out) {
+  launch_likelihoods_ndt_view(st, poses, n, m, meas, k, out);
+}
+void launch_likelihoods_ndt_hashed(hipStream_t st, const double4* poses, uint64_t n, const NdtHashView& m, const double* meas, uint32_t k, double* out) {
+  launch_likelihoods_ndt_view(st, poses, n, m, meas, k, out);
 }
 void launch_batch_reweight_ndt(hipStream_t st, const BatchItem* d_items, uint32_t members, uint32_t blocks) {
   if (blocks == 0) return;

@@ -231,4 +231,18 @@ struct CommHostLayout {
   }
 };
 
+// ---- mcl_likelihoods*: d_likelihoods, the call's own doubles - the caller's n poses (4 each), their n scores, the staged measurement ----
+// The measurement lies first, rounded up to whole pose records: every area then starts at a multiple of 32 bytes (the kernels read the
+// poses as double4 and the measurement as double2).  The device form takes the measurement area alone (n = 0).
+struct LikelihoodsLayout {
+  size_t measurement, poses, out, size;
+  LikelihoodsLayout(uint64_t n, size_t measurement_doubles) {
+    Cursor c;
+    measurement = c.take((measurement_doubles + 3) / 4 * 4);
+    poses = c.take(4 * static_cast<size_t>(n));
+    out = c.take(static_cast<size_t>(n));
+    size = c.at;
+  }
+};
+
 }  // namespace mcl

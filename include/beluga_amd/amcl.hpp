@@ -711,6 +711,38 @@ class Amcl {
     check(mcl_update_bearings(ctx_, control_action.data(), xyz.data(), categories.data(), categories.size(), &est, &info));
     return finish_update(est, info);
   }
+  /// Extension: states | views::likelihoods(sensor_model(measurement)) (views/likelihoods.hpp:44-59) on the device - for each of
+  /// `states`, in their order, the factor by which a reweight with `measurement` would multiply the weight of a particle there
+  /// (mcl_likelihoods).  The filter is untouched: particles, weights, random stream, policies and counters stay as they are.
+  /// Points in the base frame on a likelihood-field, beam or NDT filter; detections on a landmark or bearing filter (throws on a
+  /// filter of another sensor model).
+  [[nodiscard]] std::vector<double> likelihoods(const std::vector<SE2d>& states, const std::vector<std::pair<double, double>>& measurement) {
+    static_assert(sizeof(std::pair<double, double>) == 2 * sizeof(double), "points are handed over as (x, y) doubles");
+    std::vector<double> out(states.size());
+    check(mcl_likelihoods(ctx_, states.empty() ? nullptr : states.data()->data(), states.size(),
+                          measurement.empty() ? nullptr : &measurement.data()->first, measurement.size(), out.data()));
+    return out;
+  }
+  [[nodiscard]] std::vector<double> likelihoods(const std::vector<SE2d>& states, const std::vector<LandmarkPositionDetection>& detections) {
+    std::vector<double> xyz;
+    std::vector<std::uint32_t> categories;
+    flatten(detections, [](const LandmarkPositionDetection& d) -> const std::array<double, 3>& { return d.detection_position_in_robot; }, xyz,
+            categories);
+    std::vector<double> out(states.size());
+    check(mcl_likelihoods_landmarks(ctx_, states.empty() ? nullptr : states.data()->data(), states.size(), xyz.data(), categories.data(),
+                                    categories.size(), out.data()));
+    return out;
+  }
+  [[nodiscard]] std::vector<double> likelihoods(const std::vector<SE2d>& states, const std::vector<LandmarkBearingDetection>& detections) {
+    std::vector<double> xyz;
+    std::vector<std::uint32_t> categories;
+    flatten(detections, [](const LandmarkBearingDetection& d) -> const std::array<double, 3>& { return d.detection_bearing_in_sensor; }, xyz,
+            categories);
+    std::vector<double> out(states.size());
+    check(mcl_likelihoods_bearings(ctx_, states.empty() ? nullptr : states.data()->data(), states.size(), xyz.data(), categories.data(),
+                                   categories.size(), out.data()));
+    return out;
+  }
   /// Extension (the landmark and bearing constructor forms only; throws on another sensor model): the small cycle of a landmark or
   /// bearing filter, mcl_set_landmark_small_cycle.  Sets of up to 4096 particles take a wave-per-particle reweight (bit for bit the
   /// lane-per-particle kernels' weights) and the one-launch tail with one host synchronisation.  Off by default.

@@ -147,6 +147,12 @@ class Amcl {
     return filter_.update(base_pose_in_odom, measurement);
   }
 
+  /// Extension: the sensor model evaluated at caller-given states with points in the base frame (beluga_amd::Amcl::likelihoods):
+  /// scores for a list of candidate poses, the filter untouched.
+  [[nodiscard]] std::vector<double> likelihoods(const std::vector<SE2d>& states, const std::vector<std::pair<double, double>>& measurement) {
+    return filter_.likelihoods(states, measurement);
+  }
+
   /// Force a manual update of the particles on the next iteration of the filter (:263).
   void force_update() { filter_.force_update(); }
 

@@ -409,6 +409,42 @@ mcl_status mcl_propagate(mcl_ctx* ctx, const double pose[4], const double previo
  * likelihood_field_model.hpp:68-91 or beam_model.hpp:104-150): w[i] *= model(state[i]). */
 mcl_status mcl_reweight(mcl_ctx* ctx, const double* points_xy, uint64_t num_points);
 
+/* ---- The sensor model as a function: sensor_model(measurement)(state) at caller-given poses -------------------------------------
+ * The reference's sensor models are functions - sensor_model(measurement) returns state -> weight, and states | views::likelihoods(model)
+ * applies it to any range of states (views/likelihoods.hpp:44-59).  These entries are that: out[i] = the factor by which the matching
+ * mcl_reweight* would multiply the weight of a particle at poses[i], for n poses (cos, sin, x, y) - mcl_set_particles' layout - in the
+ * caller's order, anywhere on or off the map.  Scoring a list of candidate poses to relocalise, the current estimate as a quality
+ * signal, a pose from another source before mcl_initialize_normal, a new map against a recorded scan.
+ *
+ * THE FILTER IS UNTOUCHED.  Particles, weights and count, step number and random stream, recovery filters, every_n counter,
+ * force_update, control window, cached set facts, spatial order, the work the cycle keeps in flight and every counter of
+ * mcl_get_counter are what they are on a context on which the call was never made.  The call has buffers of its own, runs on the
+ * context's stream behind whatever is in flight, and reads the map the context reads NOW: a shared map, a hashed NDT map; a map
+ * given by mcl_set_map_async counts from its swap on.  Allowed between the updates of a batch on its members, and on a sharded
+ * context (the map is whole on every rank: no collective, every rank may ask on its own).
+ *
+ * mcl_likelihoods: likelihood-field, likelihood-field-prob, beam and NDT contexts (an NDT context fits the measurement cells of the
+ * points first, as its mcl_reweight does); a beam context takes at most 4096 points here, whatever n is.  The other entries are the
+ * counterparts of mcl_reweight_ndt_cells, mcl_reweight_landmarks and mcl_reweight_bearings.  poses and out are host memory, n doubles
+ * out.  An empty measurement scores 1.0 where the reweight leaves the weights as they are.  The kernels are the reweight kernels' own
+ * per-pose functions: NDT, landmark and bearing scores equal the reweight's factor bit for bit, likelihood-field and beam scores
+ * within the rounding of the sum over the scan (the reweight picks among several kernel forms by the set it has).
+ * Checks, all before the device is used; on any error out is not written: MCL_ERR_UNSUPPORTED on a context of another sensor model,
+ * MCL_ERR_NOT_READY without a map, MCL_ERR_INVALID_ARGUMENT for a null argument, a pose with a value that is not finite, and whatever
+ * the matching mcl_reweight* refuses of the measurement.  n == 0 is MCL_OK and does nothing.  n is limited by memory only. */
+mcl_status mcl_likelihoods(mcl_ctx* ctx, const double* poses, uint64_t n, const double* points_xy, uint64_t num_points, double* out);
+mcl_status mcl_likelihoods_ndt_cells(mcl_ctx* ctx, const double* poses, uint64_t n, const double* means, const double* covs, uint64_t num_cells,
+                                     double* out);
+mcl_status mcl_likelihoods_landmarks(mcl_ctx* ctx, const double* poses, uint64_t n, const double* positions_xyz, const uint32_t* categories,
+                                     uint64_t k, double* out);
+mcl_status mcl_likelihoods_bearings(mcl_ctx* ctx, const double* poses, uint64_t n, const double* bearings_xyz, const uint32_t* categories,
+                                    uint64_t k, double* out);
+/* mcl_likelihoods with d_poses and d_out in device memory of the context's device (points_xy stays host memory): enqueued on the
+ * context's stream, no host synchronisation beyond the measurement's upload (the call waits for the PREVIOUS call's upload before it
+ * stages its own) - synchronise the stream, or order your own work behind it, before reading d_out.  The poses are not looked at on
+ * the host: a pose that is not finite scores whatever the arithmetic gives. */
+mcl_status mcl_likelihoods_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* points_xy, uint64_t num_points, double* d_out);
+
 typedef struct mcl_weight_stats {
   double sum;        /* sum of weights before normalisation (actions/normalize.hpp:70) */
   double norm_sum;   /* sum of the normalised weights (the Thrun estimator's total, Q1) */

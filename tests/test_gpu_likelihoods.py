@@ -1,0 +1,741 @@
+"""mcl_likelihoods*: the sensor model as a function, sensor_model(measurement)(pose) at caller-given poses, on the GPU.
+
+What each group holds the call to:
+  1. the reference's own unit-test vectors, as tests/test_oracle_golden.py, tests/test_ndt_cpu.py and tests/test_landmark_cpu.py pin
+     them (likelihood field, its prob form, beam, NDT, landmark, bearing), at their upstream tolerances;
+  2. independent references: the CPU oracle's likelihood functions (the ones tests/test_gpu_parity.py uses) for the likelihood-field
+     models and the beam model at relative 1e-12, the tolerance the project holds weights to - every n x every beam count of the
+     issue, poses off the map, a far-origin map, a field without a palette, and two longer scans that reach the LF kernel's main loop
+     and its form without LDS staging; ndt_reference.weights_exact and landmark_reference.weights_exact for NDT (dense and hashed),
+     landmark and bearing on every case of the edge families, within the bounds test_gpu_ndt_edges.py and test_gpu_landmark_edges.py
+     derive, through both the wave and the lane launch;
+  3. the filter's OWN reweight on a twin context - set_particles(poses, ones), reweight, weights - over the edge families of
+     tests/lf_families.py, tests/ndt_families.py and tests/landmark_families.py (imported, not edited): equal bits for NDT, landmark
+     and bearing, relative 1e-12 for the likelihood-field models and for the beam model on both sides of its reweight's kernel switch;
+  4. the filter is untouched: twin filters, one of them asked for scores before the first update and between every two, stay equal
+     bit for bit in particles, weights, estimates, mcl_update_info and the cycle's counters;
+  5. the device form gives the host form's bits;
+  6. refusals leave `out` as it was.
+1e-12 is not fitted: a likelihood-field or beam score is a sum of B positive terms, each within an ulp or two of the oracle's (libm's
+exp, erf and log against the device's), added in another association: (B + 4) 2^-53 < 1.3e-13 at B = 1080.  The prob model's score
+is exp of such a sum: see where its longer scans are compared.
+"""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+
+import landmark_families as lmfam
+import lf_families as lffam
+import lf_reference as lfref
+import landmark_reference as lmref
+import ndt_families as ndtfam
+import ndt_reference as ndtref
+import test_landmark_cpu as lmcpu  # (the reference's landmark and bearing unit-test cases, as that file pins them)
+import test_ndt_cpu as ndtcpu      # (the reference's NDT unit-test vectors)
+from beluga_amd import capi, synth
+from beluga_amd.amcl import (Amcl, AmclBatch, AmclParams, BeamModelParam, BearingModelParam, DifferentialDriveModelParam, LandmarkMap,
+                             LandmarkMapBoundaries, LandmarkModelParam, LandmarkPositionDetection, LikelihoodFieldModelParam, LikelihoodFieldProbModelParam, NDTMap2d, NDTModelParam2d,
+                             OccupancyGrid, SharedMap, load_ndt_map_npz, se2_from_xytheta)
+from oracle import binding as orc
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-12
+MOTION = DifferentialDriveModelParam(0.1, 0.05, 0.1, 0.05)
+LF = LikelihoodFieldModelParam(max_obstacle_distance=2.0, max_laser_distance=100.0, z_hit=0.5, z_random=0.5, sigma_hit=0.2,
+                               model_unknown_space=True)
+LF_PROB = LikelihoodFieldProbModelParam(max_obstacle_distance=2.0, max_laser_distance=100.0, z_hit=0.5, z_random=0.5, sigma_hit=0.2,
+                                        model_unknown_space=True)
+BEAM = BeamModelParam(0.5, 0.05, 0.05, 0.5, 0.2, 0.1, 60.0)
+BEAM_T = (0.5, 0.05, 0.05, 0.5, 0.2, 0.1, 60.0)
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SIZES = (1, 63, 64, 65, 257, 4096, 4097)
+BEAMS = (0, 1, 63, 64, 65, 180)
+IDENT = np.array([[1.0, 0.0, 0.0, 0.0]])
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    nan = np.isnan(a)
+    return np.array_equal(nan, np.isnan(b)) and np.array_equal(bits(a[~nan]), bits(b[~nan]))
+
+
+def rooms_grid(size=400, seed=3, origin=None):
+    cells = synth.make_rooms_map(size, size, seed=seed, n_rooms=12)
+    return OccupancyGrid(cells=cells, resolution=0.05, origin=se2_from_xytheta(*(origin or (-size * 0.025, -size * 0.025, 0.0))))
+
+
+def make_scan(grid, pose, beams, max_range=12.0, seed=1):
+    if beams == 0:
+        return np.zeros((0, 2))
+    angles = synth.lidar_angles(beams, 270.0)
+    ranges = synth.cast_scan(grid.cells, grid.resolution, (grid.origin[2], grid.origin[3]), pose, angles, max_range, 0.01, seed)
+    return synth.scan_points(ranges, angles)
+
+
+def poses_around(truth, n, seed=5):
+    states = synth.normal_particles(n, truth, (0.5, 0.5, 0.2), seed=seed)
+    states[: min(8, n - 1), 2] += 100.0  # poses far outside the map: every beam out of the grid
+    return states
+
+
+def reweight_factor(f, poses, *measurement, how="reweight"):
+    """The factor the filter's own reweight multiplies a particle at each pose by: unit weights in, weights out."""
+    f.set_particles(poses, np.ones(len(poses)))
+    getattr(f, how)(*measurement)
+    return f.particles()[1]
+
+
+# ---- 1. the reference's own vectors ---------------------------------------------------------------------------------------------------
+def grid5(rows):
+    return np.array(rows, dtype=np.int8).reshape(5, 5)
+
+
+F_, T_ = 0, 100
+CENTER = grid5([F_] * 12 + [T_] + [F_] * 12)
+CORNER = grid5([F_] * 24 + [T_])
+LF_GOLD = LikelihoodFieldModelParam(2.0, 20.0, 0.5, 0.5, 0.2)
+
+
+def score(grid, sensor, pose, points):
+    f = Amcl(grid, MOTION, sensor, AmclParams(max_particles=4), seed=1)
+    got = f.likelihoods(np.asarray(pose, dtype=np.float64).reshape(1, 4), np.asarray(points, dtype=np.float64).reshape(-1, 2))
+    f.close()
+    assert got.shape == (1,)
+    return got[0]
+
+
+def test_reference_vectors_likelihood_field():
+    """test_likelihood_field_model.cpp:34-197, through mcl_likelihoods."""
+    g = OccupancyGrid(CENTER, 0.5)
+    assert score(g, LF_GOLD, IDENT, [(1.25, 1.25)]) == pytest.approx(2.068, abs=0.003)
+    assert score(g, LF_GOLD, IDENT, [(2.25, 2.25)]) == pytest.approx(1.000, abs=0.003)
+    assert score(g, LF_GOLD, IDENT, [(-50.0, 50.0)]) == pytest.approx(1.000, abs=0.003)
+    assert score(g, LF_GOLD, IDENT, [(1.20, 1.20), (1.25, 1.25), (1.30, 1.30)]) == pytest.approx(4.205, abs=0.01)
+    assert score(g, LF_GOLD, se2_from_xytheta(1.25, 1.25, 0.0), [(0.0, 0.0)]) == pytest.approx(2.068, abs=0.003)
+    assert score(g, LF_GOLD, IDENT, [(1.0, 1.0)]) == pytest.approx(2.068577607986223, abs=1e-6)
+    assert score(OccupancyGrid(CORNER, 0.5), LF_GOLD, IDENT, [(1.0, 1.0)]) == pytest.approx(1.0, abs=1e-3)
+    c, s = math.cos(math.pi / 2), math.sin(math.pi / 2)
+    for origin, seen in ((se2_from_xytheta(-5, -5, 0.0), (4.5, 4.5)), (se2_from_xytheta(0.0, 0.0, math.pi / 2), (-9.5, 9.5)),
+                         (se2_from_xytheta(c * -5 - s * -5, s * -5 + c * -5, math.pi / 2), (-4.5, 4.5))):  # offset, rotation, both
+        g = OccupancyGrid(CORNER, 2.0, origin=origin)
+        assert score(g, LF_GOLD, IDENT, [seen]) == pytest.approx(2.068, abs=0.003)
+        assert score(g, LF_GOLD, origin, [(9.5, 9.5)]) == pytest.approx(2.068, abs=0.003)
+
+
+def test_reference_vectors_beam():
+    """test_beam_model.cpp:40-122."""
+    g = OccupancyGrid(CENTER, 0.5)
+    assert score(g, BEAM, IDENT, [(1.0, 1.0)]) == pytest.approx(1.0171643824743635, abs=1e-6)
+    assert score(g, BEAM, IDENT, [(0.75, 0.75)]) == pytest.approx(0.015905891701088148, abs=1e-6)
+    assert score(g, BEAM, IDENT, [(2.25, 2.25)]) == pytest.approx(0.000, abs=1e-6)
+    assert score(g, BEAM, IDENT, [(60.0, 60.0)]) == pytest.approx(0.00012500000000000003, abs=1e-6)
+    assert score(OccupancyGrid(grid5([F_] * 25), 0.5), BEAM, IDENT, [(1.0, 1.0)]) == pytest.approx(0.0, abs=1e-3)
+
+
+def test_reference_vectors_likelihood_field_prob():
+    """test_likelihood_field_prob_model.cpp:35-76 (tests/test_oracle_golden.py test_lf_prob_importance_weight)."""
+    g = OccupancyGrid(CENTER, 0.5)
+    prob = LikelihoodFieldProbModelParam(2.0, 20.0, 0.5, 0.5, 0.2)
+    assert score(g, prob, IDENT, [(1.25, 1.25)]) == pytest.approx(1.022, abs=0.003)
+    assert score(g, prob, IDENT, [(2.25, 2.25)]) == pytest.approx(0.025, abs=0.003)
+    assert score(g, prob, IDENT, [(-50.0, 50.0)]) == pytest.approx(0.050, abs=0.003)
+    assert score(g, prob, IDENT, [(1.20, 1.20), (1.25, 1.25), (1.30, 1.30)]) == pytest.approx(1.068, abs=0.01)
+    assert score(g, prob, se2_from_xytheta(1.25, 1.25, 0.0), [(0.0, 0.0)]) == pytest.approx(1.022, abs=0.003)
+
+
+def facade_ndt_map(m):
+    """ndt_reference.NdtMap -> the facade's map."""
+    keys = sorted(m.data)
+    return NDTMap2d(np.array(keys, dtype=np.int32).reshape(-1, 2), np.array([m.data[k][0] for k in keys]), np.array([m.data[k][1] for k in keys]),
+                    m.resolution)
+
+
+def test_reference_vectors_ndt():
+    """test_ndt_model.cpp Likelihoood and SensorModel, the vectors tests/test_ndt_cpu.py pins the restatement to: likelihood_at of a
+    cell is the score of that one cell at the identity less the 1 the sum starts from (mcl_likelihoods_ndt_cells); the sensor model
+    over the fit of its own measurement scores 2 at the origin, 1 far away and more than 1 nearby (mcl_likelihoods, the points form).
+    EXPECT_DOUBLE_EQ upstream: four ulps."""
+    ulps4 = 4 * 2.0**-52
+    gm = ndtcpu.golden_map()
+    f = Amcl(facade_ndt_map(gm), MOTION,
+             NDTModelParam2d(1e-6, 1.0, 1.0), AmclParams(max_particles=4), seed=1)
+    for mean, want in ndtcpu.GOLDEN_LIKELIHOOD:
+        got = f.likelihoods_ndt_cells(IDENT, np.array([mean]), ndtcpu.DIAG.reshape(1, 4))[0]
+        assert got == pytest.approx(1.0 + want, rel=ulps4), mean
+    far = f.likelihoods_ndt_cells(np.array([[1.0, 0.0, 50.0, 50.0]]), np.array([[0.5, 0.5]]), ndtcpu.DIAG.reshape(1, 4))[0]
+    assert far == pytest.approx(1.0 + 1e-6, rel=ulps4)  # MinLikelihood: no cell near
+    f.close()
+    m, means, covs = ndtcpu.sensor_model_map()
+    f = Amcl(facade_ndt_map(m), MOTION,
+             NDTModelParam2d(0.0, 1.0, 1.0), AmclParams(max_particles=4), seed=1)
+    pts = np.array(ndtcpu.SENSOR_MODEL_POINTS)
+    st = lambda x, y: np.array([[1.0, 0.0, x, y]])
+    assert f.likelihoods(st(0.0, 0.0), pts)[0] == pytest.approx(2.0, rel=ulps4)
+    assert f.likelihoods(st(-10.0, -10.0), pts)[0] == pytest.approx(1.0, rel=ulps4)
+    assert f.likelihoods(st(0.1, 0.1), pts)[0] > 1.0
+    f.close()
+
+
+def facade_landmark_map(entries):
+    return LandmarkMap(LandmarkMapBoundaries(*lmcpu.BOX), [LandmarkPositionDetection(tuple(map(float, p)), c) for p, c in entries])
+
+
+def detections_of(cases_entry):
+    det = cases_entry[1]
+    return (np.array([d[0] for d in det], dtype=np.float64).reshape(-1, 3), np.array([d[1] for d in det], dtype=np.uint32))
+
+
+@pytest.mark.parametrize("name", sorted(lmcpu.LANDMARK_CASES))
+def test_reference_vectors_landmark(name):
+    """test_landmark_sensor_model.cpp, the cases tests/test_landmark_cpu.py pins the restatement to, at their upstream tolerances."""
+    entries, _, expected, tolerance, closed = lmcpu.LANDMARK_CASES[name]
+    f = Amcl(facade_landmark_map(entries), MOTION, LandmarkModelParam(**lmcpu.LANDMARK), AmclParams(max_particles=4), seed=1)
+    got = f.likelihoods(lmcpu.POSE.reshape(1, 4), detections_of(lmcpu.LANDMARK_CASES[name]))[0]
+    f.close()
+    assert abs(got - expected) <= tolerance
+    if closed is not None:
+        assert got == pytest.approx(closed, rel=1e-12, abs=1e-300)
+
+
+@pytest.mark.parametrize("name", sorted(lmcpu.BEARING_CASES))
+def test_reference_vectors_bearing(name):
+    """test_bearing_sensor_model.cpp, likewise."""
+    entries, _, expected, tolerance, closed = lmcpu.BEARING_CASES[name]
+    f = Amcl(facade_landmark_map(entries), MOTION, BearingModelParam(**lmcpu.BEARING), AmclParams(max_particles=4), seed=1)
+    got = f.likelihoods(lmcpu.POSE.reshape(1, 4), detections_of(lmcpu.BEARING_CASES[name]))[0]
+    f.close()
+    assert abs(got - expected) <= tolerance
+    assert got == pytest.approx(closed, rel=1e-12, abs=0.0)
+
+
+# ---- 2. against the oracle ---------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def world():
+    grid = rooms_grid()
+    truth = synth.find_free_pose(grid.cells, grid.resolution, (grid.origin[2], grid.origin[3]), seed=2, clearance_cells=6)
+    return grid, truth
+
+
+@pytest.mark.parametrize("prob", [False, True])
+def test_likelihood_field_matches_the_oracle(world, prob):
+    grid, truth = world
+    f = Amcl(grid, MOTION, LF_PROB if prob else LF, AmclParams(max_particles=64), seed=1)
+    field = f.likelihood_field()
+    oracle = orc.lf_prob_weights if prob else orc.lf_weights
+    states = poses_around(truth, max(SIZES))
+    for beams in BEAMS:
+        pts = make_scan(grid, truth, beams)
+        want = oracle(field, grid.resolution, grid.origin, LF.max_laser_distance, states, pts) if beams else np.ones(len(states))
+        for n in SIZES:
+            got = f.likelihoods(states[:n], pts)
+            np.testing.assert_allclose(got, want[:n], rtol=RTOL, atol=0, err_msg=f"beams {beams} n {n}")
+    # beyond the issue's counts: 1080 beams run the kernel's main loop (256 beams a pass, four per lane) and its tail; 4200 points are
+    # more than fit into LDS beside the palette, so the kernel reads the scan from memory (k_likelihoods_lf<false>)
+    long_scan = np.concatenate([make_scan(grid, truth, 1050, seed=k) for k in range(4)])
+    for pts in (make_scan(grid, truth, 1080), long_scan):
+        want = oracle(field, grid.resolution, grid.origin, LF.max_laser_distance, states, pts)
+        # The prob model's score is exp(S), S the sum of B logarithms, all negative: a relative error of exp(S) is an absolute error of S,
+        # and two f64 sums of B terms in different associations differ by up to 2 (B + 4) 2^-53 sum |term| = 2 (B + 4) 2^-53 |ln score|
+        # (each side within (B + 4) 2^-53 sum |term| of the real sum; the terms' own ulps are inside the + 4).  At the issue's counts that
+        # stays below 1e-12 and the loop above holds 1e-12; at B = 1080 and |S| in the thousands it does not, so these two shapes add it.
+        # A score that underflows to 0 in the oracle (|S| > 745) has to be 0 here as well (atol = 0).
+        B = len(pts)
+        slack = 2 * (B + 4) * 2.0**-53 * np.abs(np.log(np.where(want > 0, want, 1.0))) if prob else np.zeros(len(want))
+        for n in (65, 4097):
+            got = f.likelihoods(states[:n], pts)
+            err = np.abs(got - want[:n]) / np.where(want[:n] > 0, want[:n], 1.0)
+            print("likelihoods lf oracle prob=%d beams=%d n=%d worst=%.3g, worst against its bound %.2f" %
+                  (prob, B, n, err.max(), (err / (RTOL + slack[:n])).max()))
+            assert np.all(err <= RTOL + slack[:n]) and np.all(got[want[:n] == 0] == 0), (B, n)
+    f.close()
+
+
+def test_likelihood_field_on_a_far_origin_map_and_a_field_without_a_palette():
+    grid = rooms_grid(160, 5, origin=(1.0e6 - 4.0, -2.0e6 - 4.0, 0.3))
+    truth = synth.find_free_pose(grid.cells, grid.resolution, (grid.origin[2], grid.origin[3]), seed=2, clearance_cells=6)
+    pts = make_scan(grid, truth, 65)
+    states = poses_around(truth, 257)
+    for table in (0, 1):  # 1: the palette is switched off - a lane per pose over the f32 field
+        f = Amcl(grid, MOTION, LF, AmclParams(max_particles=64), seed=1, options={"lf_table": table})
+        want = orc.lf_weights(f.likelihood_field(), grid.resolution, grid.origin, LF.max_laser_distance, states, pts)
+        np.testing.assert_allclose(f.likelihoods(states, pts), want, rtol=RTOL, atol=0)
+        f.close()
+
+
+def test_beam_matches_the_oracle(world):
+    """Every n x every beam count at relative 1e-12, the bound the issue sets (the project's own beam REWEIGHT test allows 1e-10,
+    tests/test_gpu_parity.py: erf and exp differ by ulps between the libms; this test does not take that allowance).  A zero of
+    the oracle has to be a zero here: atol = 0.  The worst figure is printed before the assertion."""
+    grid, truth = world
+    f = Amcl(grid, MOTION, BEAM, AmclParams(max_particles=64), seed=1)
+    states = poses_around(truth, max(SIZES))
+    worst = 0.0
+    for beams in BEAMS:
+        pts = make_scan(grid, truth, beams)
+        # (an empty scan: mcl_reweight leaves the weights as they are - the factor is 1)
+        want = orc.beam_weights(grid.cells, grid.resolution, grid.origin, BEAM_T, states, pts) if beams else np.ones(len(states))
+        for n in SIZES:
+            got = f.likelihoods(states[:n], pts)
+            nz = want[:n] != 0
+            worst = max(worst, float(np.max(np.abs(got[nz] - want[:n][nz]) / want[:n][nz], initial=0.0)))
+            print("likelihoods beam oracle beams=%d n=%d worst so far %.3g" % (beams, n, worst))
+            np.testing.assert_allclose(got, want[:n], rtol=RTOL, atol=0, err_msg=f"beams {beams} n {n}")
+    assert f.beam_cells_visited(reset=False) == 0  # the cycle's counter of visited cells is not the call's
+    f.close()
+
+
+# ---- 3. against the filter's own reweight, on the edge families ------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(lffam.FAMILIES))
+def test_likelihood_field_edge_families_against_the_reweight(name):
+    for case in lffam.FAMILIES[name]():
+        H, W = case["shape"]
+        grid = OccupancyGrid(cells=np.zeros((H, W), dtype=np.int8), resolution=case["resolution"], origin=case["origin"])
+        n = len(case["states"])
+        for sensor in (LF, LF_PROB):
+            pair = [Amcl(grid, MOTION, sensor, AmclParams(min_particles=n, max_particles=n), seed=11) for _ in range(2)]
+            for f in pair:
+                f.set_likelihood_field(lfref.revealing_field(H, W, "palette"))
+            want = reweight_factor(pair[1], case["states"], case["points"])
+            got = pair[0].likelihoods(case["states"], case["points"])
+            np.testing.assert_allclose(got, want, rtol=RTOL, atol=0, err_msg=name)
+            for f in pair:
+                f.close()
+
+
+def finite_rows(states):
+    return states[np.isfinite(states).all(axis=1)]
+
+
+@pytest.mark.parametrize("name", list(ndtfam.FAMILIES))
+def test_ndt_edge_families_equal_the_reweight_bit_for_bit(name):
+    for case in ndtfam.FAMILIES[name]():
+        states = finite_rows(case.states)  # (a pose that is not finite is refused: test_refusals)
+        big = states[np.arange(4097) % len(states)]
+        for layout in ((0, 2) if case.layout == "both" else (2,)):
+            ndt_map = NDTMap2d(case.keys.astype(np.int32), case.means, case.covs, case.resolution)
+            sensor = NDTModelParam2d(case.minimum, case.d1, case.d2, case.kernel)
+            pair = [Amcl(ndt_map, MOTION, sensor, AmclParams(min_particles=4097, max_particles=4097), seed=11, ndt_map_layout=layout)
+                    for _ in range(2)]
+            covs = case.cell_covs.reshape(-1, 4)
+            for n in (len(states), 4096, 4097):  # a wave per pose up to 4096, a lane per pose above
+                want = reweight_factor(pair[1], big[:n], case.cell_means, covs, how="reweight_ndt_cells")
+                got = pair[0].likelihoods_ndt_cells(big[:n], case.cell_means, covs)
+                assert same_bits(got, want), (case.tag, layout, n)
+            for f in pair:
+                f.close()
+
+
+@pytest.mark.parametrize("name", list(lmfam.FAMILIES))
+def test_landmark_edge_families_equal_the_reweight_bit_for_bit(name):
+    for case in lmfam.FAMILIES[name]():
+        states = finite_rows(case.states)
+        if len(states) == 0:
+            continue
+        big = states[np.arange(4097) % len(states)]
+        sensor = (BearingModelParam(case.params["sigma_bearing"], tuple(case.params["sensor_pose_in_robot"])) if case.bearing else
+                  LandmarkModelParam(case.params["sigma_range"], case.params["sigma_bearing"], case.params["random_prob"]))
+        pair = [Amcl(LandmarkMap((case.positions, case.categories)), MOTION, sensor, AmclParams(min_particles=4097, max_particles=4097), seed=11)
+                for _ in range(2)]
+        for n in (len(states), 4096, 4097):
+            want = reweight_factor(pair[1], big[:n], (case.det, case.dcat), how="reweight_bearings" if case.bearing else "reweight_landmarks")
+            got = pair[0].likelihoods(big[:n], (case.det, case.dcat))
+            assert same_bits(got, want), (case.tag, n)
+        for f in pair:
+            f.close()
+
+
+def test_ndt_points_form_on_the_turtlebot_map_dense_and_hashed():
+    """mcl_likelihoods on an NDT context fits the cells of the points first, as mcl_reweight does: the same bits, either layout."""
+    ndt_map = load_ndt_map_npz(os.path.join(GOLDEN, "turtlebot3_world_ndt.npz"))
+    z = np.load(os.path.join(GOLDEN, "turtlebot3_world_grid.npz"))
+    ox, oy, ot = z["origin_xytheta"]
+    grid = OccupancyGrid(cells=z["cells"], resolution=float(z["resolution"]), origin=se2_from_xytheta(ox, oy, ot))
+    truth = synth.find_free_pose(grid.cells, grid.resolution, (grid.origin[2], grid.origin[3]), seed=2, clearance_cells=4)
+    pts = make_scan(grid, truth, 180, max_range=3.5)
+    states = poses_around(truth, 4097)
+    results = []
+    for layout in (0, 2):
+        pair = [Amcl(ndt_map, MOTION, NDTModelParam2d(), AmclParams(min_particles=4097, max_particles=4097), seed=11, ndt_map_layout=layout)
+                for _ in range(2)]
+        for n in SIZES:
+            want = reweight_factor(pair[1], states[:n], pts)
+            got = pair[0].likelihoods(states[:n], pts)
+            assert same_bits(got, want), (layout, n)
+        results.append(got)
+        assert (got > 1.0).any()  # (the scan does fit somewhere)
+        for f in pair:
+            f.close()
+    assert same_bits(results[0], results[1])
+
+
+# ---- 2b. NDT, landmark and bearing against the exact references, on the edge families ---------------------------------------------------
+# The references of test_gpu_ndt_edges.py and test_gpu_landmark_edges.py (ndt_reference.weights_exact, landmark_reference.weights_exact:
+# the cell or the match by the reference's own f64 sequence, the rest in 60-digit arithmetic) with unit prior weights, and those tests'
+# own bounds, 4 MEASURED_F64_ERROR[family] + (K + 4) 2^-53 - derived there from the CPU loop form's error, not from a device.  Every
+# case of every family, every finite pose of it: the host forms refuse a pose that is not finite (test_refusals_leave_out_as_it_was),
+# which is what far_poses' two such states meet.  Each case runs the wave form (its own states) and the lane form (4097 poses).
+def run_sizes(states):
+    return (len(states), states), (4097, states[np.arange(4097) % len(states)])
+
+
+@pytest.mark.parametrize("name", ndtfam.EXACT_FAMILIES)
+def test_ndt_edge_families_against_the_exact_reference(name):
+    for case in ndtfam.FAMILIES[name]():
+        finite = np.isfinite(case.states).all(axis=1)
+        states = case.states[finite]
+        want = np.asarray(ndtref.weights_exact(case.ref_map(), states, case.cell_means, case.cell_covs, np.ones(len(states)), variant=ndtref.REFERENCE,
+                                               **case.model())[0], dtype=np.float64)
+        K = len(case.cell_means)
+        bound = 4 * ndtfam.MEASURED_F64_ERROR[name] + (K + 4) * 2.0**-53
+        for layout in ((0, 2) if case.layout == "both" else (2,)):
+            f = Amcl(NDTMap2d(case.keys.astype(np.int32), case.means, case.covs, case.resolution), MOTION,
+                     NDTModelParam2d(case.minimum, case.d1, case.d2, case.kernel), AmclParams(max_particles=4), seed=11, ndt_map_layout=layout)
+            for n, poses in run_sizes(states):
+                got = f.likelihoods_ndt_cells(poses, case.cell_means, case.cell_covs.reshape(-1, 4))
+                w = want[np.arange(n) % len(states)]
+                err = float(np.max(np.abs(got - w) / w))
+                print("likelihoods ndt exact %s layout=%d n=%d K=%d worst=%.3g (%.2f of the bound)" % (case.tag, layout, n, K, err, err / bound))
+                assert err <= bound, (case.tag, layout, n, err, bound)
+            f.close()
+
+
+@pytest.mark.parametrize("name", sorted(lmfam.FAMILIES))
+def test_landmark_edge_families_against_the_exact_reference(name):
+    for case in lmfam.FAMILIES[name]():
+        states = case.states[np.isfinite(case.states).all(axis=1)]
+        want = lmref.weights_exact(case.ref_map(), states, case.det, case.dcat, np.ones(len(states)), case.bearing, **case.params)[0]
+        bound = 4 * lmfam.MEASURED_F64_ERROR[name] + (case.k + 4) * 2.0**-53
+        sensor = (BearingModelParam(case.params["sigma_bearing"], tuple(case.params["sensor_pose_in_robot"])) if case.bearing else
+                  LandmarkModelParam(case.params["sigma_range"], case.params["sigma_bearing"], case.params["random_prob"]))
+        f = Amcl(LandmarkMap((case.positions, case.categories)), MOTION, sensor, AmclParams(max_particles=4), seed=11)
+        for n, poses in run_sizes(states):
+            got = f.likelihoods(poses, (case.det, case.dcat))
+            assert not np.isnan(got).any() and not np.signbit(got).any(), (case.tag, n)
+            w = [want[i % len(states)] for i in range(n)]
+            err = float(lmref.excess_errors(got, w, case.absolute_steps()).max())
+            print("likelihoods landmark exact %s n=%d k=%d worst=%.3g (%.2f of the bound)" % (case.tag, n, case.k, err, err / bound))
+            assert err <= bound, (case.tag, n, err, bound)
+        f.close()
+
+
+def test_no_measurement_scores_one_on_every_path():
+    """K = 0 cells and k = 0 detections: 1.0 exactly, from the wave and the lane launch (NDT) and from the fill (landmark, bearing)."""
+    case = ndtfam.FAMILIES["axis_edges"]()[0]
+    f = Amcl(NDTMap2d(case.keys.astype(np.int32), case.means, case.covs, case.resolution), MOTION, NDTModelParam2d(), AmclParams(max_particles=4), seed=1)
+    lm = lmfam.FAMILIES["near_ties"]()[0]
+    g = Amcl(LandmarkMap((lm.positions, lm.categories)), MOTION, LandmarkModelParam(0.3, 0.2, 0.1), AmclParams(max_particles=4), seed=1)
+    for n, poses in run_sizes(case.states[np.isfinite(case.states).all(axis=1)]):
+        assert np.array_equal(f.likelihoods_ndt_cells(poses, np.zeros((0, 2)), np.zeros((0, 4))), np.ones(n))
+        assert np.array_equal(f.likelihoods(poses, np.zeros((0, 2))), np.ones(n))
+        assert np.array_equal(g.likelihoods(poses, (np.zeros((0, 3)), np.zeros(0, dtype=np.uint32))), np.ones(n))
+    f.close()
+    g.close()
+
+
+# ---- 3b. the beam model against the filter's own reweight, on both sides of its kernel switch ------------------------------------------
+@pytest.mark.parametrize("n", [4097, 16_383, 16_411])
+def test_beam_against_the_reweight_on_both_sides_of_its_kernel_switch(world, n):
+    """mcl_likelihoods is always the wave-per-pose form; the reweight is that form below beam_sort_min_particles (16 384) and the
+    ordered-lanes kernel with its range table from there on (the counters pin which one ran).  Relative 1e-12, the issue's bound."""
+    grid, truth = world
+    pts = make_scan(grid, truth, 180)
+    states = poses_around(truth, n)
+    pair = [Amcl(grid, MOTION, BEAM, AmclParams(min_particles=n, max_particles=n), seed=11) for _ in range(2)]
+    want = reweight_factor(pair[1], states, pts)
+    assert pair[1].counter("beam_ordered_launches") == (1 if n >= 16_384 else 0) and pair[1].counter("beam_wave_launches") == (0 if n >= 16_384 else 1)
+    got = pair[0].likelihoods(states, pts)
+    nz = want != 0
+    print("likelihoods beam twin n=%d worst=%.3g" % (n, float(np.max(np.abs(got[nz] - want[nz]) / want[nz], initial=0.0))))
+    np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
+    for f in pair:
+        f.close()
+
+
+# ---- 4. the filter is untouched ---------------------------------------------------------------------------------------------------------
+CYCLE_COUNTERS = ("lf_fast_launches", "lf_patch_launches", "lf_beams_launches", "lf_far_launches", "small_tail_launches", "field_pose_rebuilds",
+                  "estimate_repivots", "noise_ahead_used", "order_ahead_used", "order_ahead_missed", "ndt_lane_launches", "ndt_wave_launches")
+COV = np.diag([0.25, 0.25, 0.04])
+
+
+def snapshot(f):
+    s, w = f.particles()
+    counters = {}
+    for name in CYCLE_COUNTERS:
+        try:
+            counters[name] = f.counter(name)
+        except capi.MclError:
+            pass
+    return bits(s).tobytes(), bits(w).tobytes(), f.last_info, counters
+
+
+def run_twins(asked, twin, grid, truth, scan_of, probe, before_cycle=None, cycles=5):
+    """Five update cycles on both; `asked` scores 4097 poses before the first and between every two.  Returns the scores of each call."""
+    scores = [asked.likelihoods(probe, scan_of(truth, 0))]
+    pose, odom = truth, (0.0, 0.0, 0.0)
+    for c in range(cycles):
+        if before_cycle:
+            before_cycle(c)
+        pose, odom = synth.odometry_step(pose, 0.3, 0.05), synth.odometry_step(odom, 0.3, 0.05)
+        pts = scan_of(pose, c)
+        a, b = asked.update(se2_from_xytheta(*odom), pts), twin.update(se2_from_xytheta(*odom), pts)
+        assert (a is None) == (b is None)
+        if a is not None:
+            assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1])), c
+        assert snapshot(asked) == snapshot(twin), c
+        scores.append(asked.likelihoods(probe, pts))
+        assert snapshot(asked) == snapshot(twin), c  # (the call itself moved nothing either)
+    return scores
+
+
+def lf_scan(grid, beams=180):
+    return lambda pose, c: make_scan(grid, pose, beams, seed=c)
+
+
+def test_untouched_lf_kld_adaptive_large_path(world):
+    grid, truth = world
+    params = AmclParams(min_particles=2000, max_particles=100_000, update_min_d=0.0, update_min_a=0.0, resample_interval=1)
+    pair = [Amcl(grid, MOTION, LF, params, seed=42) for _ in range(2)]
+    for f in pair:
+        f.initialize(truth, COV)
+    scores = run_twins(pair[0], pair[1], grid, truth, lf_scan(grid), poses_around(truth, 4097))
+    assert pair[0].num_particles() != 100_000  # (the set's size did change)
+    assert all(np.isfinite(s).all() for s in scores)
+    for f in pair:
+        f.close()
+
+
+def test_untouched_on_a_shared_map_and_across_an_async_map_swap(world):
+    grid, truth = world
+    grid_b = rooms_grid(400, 9)
+    shared = SharedMap(grid, LF)
+    params = AmclParams(min_particles=500, max_particles=2000, update_min_d=0.0, update_min_a=0.0, resample_interval=1)
+    on_shared = [Amcl(grid, MOTION, LF, params, seed=7) for _ in range(2)]
+    for f in on_shared:
+        f.use_map(shared)
+        f.initialize(truth, COV)
+    probe = poses_around(truth, 4097)
+    run_twins(on_shared[0], on_shared[1], grid, truth, lf_scan(grid), probe)
+    for f in on_shared:
+        f.close()
+    shared.close()
+    swapping = [Amcl(grid, MOTION, LF, params, seed=7) for _ in range(2)]
+    for f in swapping:
+        f.initialize(truth, COV)
+
+    def before_cycle(c):
+        if c == 1:
+            for f in swapping:
+                f.update_map_async(grid_b)
+        if c == 3:
+            for f in swapping:
+                f.map_commit(wait=True)
+
+    scores = run_twins(swapping[0], swapping[1], grid, truth, lf_scan(grid, 65), probe, before_cycle)
+    # the scores follow the map the context reads: the old one while the new one is pending, the new one from its swap on
+    pose, scans = truth, []
+    for c in range(5):
+        pose = synth.odometry_step(pose, 0.3, 0.05)
+        scans.append(make_scan(grid, pose, 65, seed=c))
+    field_a = orc.make_likelihood_field(grid.cells, grid.resolution, (2.0, 100.0, 0.5, 0.5, 0.2), True, False)
+    field_b = orc.make_likelihood_field(grid_b.cells, grid_b.resolution, (2.0, 100.0, 0.5, 0.5, 0.2), True, False)
+    for c in range(5):
+        field = field_a if c < 3 else field_b
+        want = orc.lf_weights(field, grid.resolution, grid.origin, LF.max_laser_distance, probe, scans[c])
+        np.testing.assert_allclose(scores[c + 1], want, rtol=RTOL, atol=0, err_msg=f"after cycle {c}")
+    for f in swapping:
+        f.close()
+
+
+def test_untouched_small_cycle_ndt():
+    ndt_map = load_ndt_map_npz(os.path.join(GOLDEN, "turtlebot3_world_ndt.npz"))
+    z = np.load(os.path.join(GOLDEN, "turtlebot3_world_grid.npz"))
+    ox, oy, ot = z["origin_xytheta"]
+    grid = OccupancyGrid(cells=z["cells"], resolution=float(z["resolution"]), origin=se2_from_xytheta(ox, oy, ot))
+    truth = synth.find_free_pose(grid.cells, grid.resolution, (grid.origin[2], grid.origin[3]), seed=2, clearance_cells=4)
+    params = AmclParams(min_particles=500, max_particles=2000, update_min_d=0.0, update_min_a=0.0, resample_interval=1)
+    pair = [Amcl(ndt_map, MOTION, NDTModelParam2d(), params, seed=9, ndt_small_cycle=True) for _ in range(2)]
+    for f in pair:
+        f.initialize(truth, COV)
+    run_twins(pair[0], pair[1], grid, truth, lambda pose, c: make_scan(grid, pose, 180, max_range=3.5, seed=c), poses_around(truth, 4097))
+    assert pair[0].ndt_small_cycle_counts() == pair[1].ndt_small_cycle_counts()
+    for f in pair:
+        f.close()
+
+
+BATCH_COUNTERS = ("cycles", "kernel_launches", "members_fused", "members_alone", "cluster_launches", "beam_launches")
+
+
+def test_untouched_member_of_a_batch(world):
+    grid, truth = world
+    params = AmclParams(min_particles=500, max_particles=1000, update_min_d=0.0, update_min_a=0.0, resample_interval=1)
+    specs = [dict(grid=grid, motion=MOTION, sensor=LF, params=params, seed=20 + k) for k in range(3)]
+    fleets = [AmclBatch(specs) for _ in range(2)]
+    for fleet in fleets:
+        for m in fleet.members:
+            m.initialize(truth, COV)
+    probe = poses_around(truth, 4097)
+    asked = fleets[0].members[1]
+    asked.likelihoods(probe, make_scan(grid, truth, 65))
+    pose, odom = truth, (0.0, 0.0, 0.0)
+    for c in range(5):
+        pose, odom = synth.odometry_step(pose, 0.3, 0.05), synth.odometry_step(odom, 0.3, 0.05)
+        pts = make_scan(grid, pose, 65, seed=c)
+        results = [fleet.update([se2_from_xytheta(*odom)] * 3, [pts] * 3) for fleet in fleets]
+        for a, b in zip(*results):
+            assert (a is None) == (b is None)
+            if a is not None:
+                assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1])), c
+        for a, b in zip(fleets[0].members, fleets[1].members):
+            assert a.particles()[0].tobytes() == b.particles()[0].tobytes() and a.particles()[1].tobytes() == b.particles()[1].tobytes(), c
+        assert fleets[0].last_infos == fleets[1].last_infos
+        for a, b in zip(fleets[0].members, fleets[1].members):
+            assert snapshot(a)[3] == snapshot(b)[3], c  # the members' cycle counters
+        assert all(fleets[0].counter(name) == fleets[1].counter(name) for name in BATCH_COUNTERS), c
+        got = asked.likelihoods(probe, pts)
+        want = orc.lf_weights(asked.likelihood_field(), grid.resolution, grid.origin, LF.max_laser_distance, probe, pts)
+        np.testing.assert_allclose(got, want, rtol=RTOL, atol=0)
+    for fleet in fleets:
+        fleet.close()
+
+
+# ---- 5. the device form -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sensor", [LF, BEAM], ids=["lf", "beam"])
+def test_device_form_gives_the_host_forms_bits(world, sensor):
+    import torch
+
+    grid, truth = world
+    f = Amcl(grid, MOTION, sensor, AmclParams(max_particles=64), seed=1)
+    pts = make_scan(grid, truth, 180)
+    for n in (1, 65, 4097):
+        states = poses_around(truth, max(n, 2))[:n]
+        host = f.likelihoods(states, pts)
+        d_poses = torch.from_numpy(states).to("cuda:0")
+        got = f.likelihoods_device(d_poses, pts)
+        assert got.shape == (n,) and got.dtype == torch.float64
+        assert np.array_equal(bits(got.cpu().numpy()), bits(host)), n
+        out = torch.full((n,), -7.0, dtype=torch.float64, device="cuda:0")
+        assert f.likelihoods_device(d_poses, pts, out=out) is out
+        assert np.array_equal(bits(out.cpu().numpy()), bits(host)), n
+    f.close()
+
+
+# ---- 6. refusals ----------------------------------------------------------------------------------------------------------------------------
+SENTINEL = -12345.0
+
+
+def raw(f, entry, poses, *measurement):
+    """A raw call of an entry with `out` filled with the sentinel: (status, out)."""
+    lib = capi.load()
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
+    out = np.full(max(len(poses), 1), SENTINEL)
+    dp = lambda a: a.ctypes.data_as(capi.c_double_p)
+    args = []
+    for a in measurement:
+        a = np.ascontiguousarray(a)
+        args.append(a.ctypes.data_as(capi.c_u32_p) if a.dtype == np.uint32 else dp(a))
+    count = len(measurement[0])
+    status = getattr(lib, entry)(f._ctx, dp(poses), len(poses), *args, count, dp(out))
+    return status, out
+
+
+class Bare:
+    """A context of another filter's configuration that has been given no map."""
+
+    def __init__(self, like):
+        self._lib, self._ctx = capi.load(), capi._ctx()
+        status = self._lib.mcl_create(C.byref(like._cfg), C.byref(self._ctx))
+        assert status == capi.MCL_OK
+
+    def close(self):
+        self._lib.mcl_destroy(self._ctx)
+
+
+def test_refusals_leave_out_as_it_was(world):
+    grid, truth = world
+    poses = poses_around(truth, 5)
+    pts = make_scan(grid, truth, 65)
+    cat = np.zeros(2, dtype=np.uint32)
+    xyz = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+    means, covs = np.array([[1.0, 0.0]]), np.array([[0.1, 0.0, 0.0, 0.1]])
+    lf = Amcl(grid, MOTION, LF, AmclParams(max_particles=64), seed=1)
+    beam = Amcl(grid, MOTION, BEAM, AmclParams(max_particles=64), seed=1)
+    ndt = Amcl(NDTMap2d(np.array([[0, 0]], dtype=np.int32), np.array([[0.5, 0.5]]), np.array([[[0.1, 0.0], [0.0, 0.1]]]), 1.0), MOTION,
+               NDTModelParam2d(), AmclParams(max_particles=64), seed=1)
+    landmark_map = LandmarkMap((np.array([[1.0, 1.0, 0.0], [2.0, 0.0, 0.0]]), np.array([0, 1], dtype=np.uint32)))
+    lm = Amcl(landmark_map, MOTION, LandmarkModelParam(0.3, 0.2, 0.1), AmclParams(max_particles=64), seed=1)
+    br = Amcl(landmark_map, MOTION, BearingModelParam(0.2, (0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.5)), AmclParams(max_particles=64), seed=1)
+    no_map = AmclBatch([dict(grid=None, motion=MOTION, sensor=LF, params=AmclParams(min_particles=100, max_particles=100))])
+
+    def refused(status, out, want):
+        assert status == want and (out == SENTINEL).all()
+
+    U, A, R = capi.MCL_ERR_UNSUPPORTED, capi.MCL_ERR_INVALID_ARGUMENT, capi.MCL_ERR_NOT_READY
+    # each entry on a context of another kind
+    for f in (lm, br):
+        refused(*raw(f, "mcl_likelihoods", poses, pts), U)
+    for f in (lf, beam, lm, br):
+        refused(*raw(f, "mcl_likelihoods_ndt_cells", poses, means, covs), U)
+    for f in (lf, beam, ndt, br):
+        refused(*raw(f, "mcl_likelihoods_landmarks", poses, xyz, cat), U)
+    for f in (lf, beam, ndt, lm):
+        refused(*raw(f, "mcl_likelihoods_bearings", poses, xyz, cat), U)
+    # a missing map, every kind
+    refused(*raw(no_map.members[0], "mcl_likelihoods", poses, pts), R)
+    bare = [Bare(f) for f in (ndt, lm, br)]  # (the facade gives these kinds their map at once: contexts made from their configurations)
+    refused(*raw(bare[0], "mcl_likelihoods", poses, pts), R)
+    refused(*raw(bare[0], "mcl_likelihoods_ndt_cells", poses, means, covs), R)
+    refused(*raw(bare[1], "mcl_likelihoods_landmarks", poses, xyz, cat), R)
+    refused(*raw(bare[2], "mcl_likelihoods_bearings", poses, xyz, cat), R)
+    for b in bare:
+        b.close()
+    # the device form: another kind, no map, a scan the beam kernel cannot stage - the device memory keeps the sentinel
+    import torch
+    d_poses = torch.from_numpy(poses).to("cuda:0")
+    d_out = torch.full((len(poses),), SENTINEL, dtype=torch.float64, device="cuda:0")
+    lib = capi.load()
+
+    def device_form(f, points):
+        points = np.ascontiguousarray(points, dtype=np.float64)
+        status = lib.mcl_likelihoods_device(f._ctx, d_poses.data_ptr(), len(poses), points.ctypes.data_as(capi.c_double_p), len(points), d_out.data_ptr())
+        torch.cuda.synchronize()
+        return status, d_out.cpu().numpy()
+
+    for f in (lm, br):
+        refused(*device_form(f, pts), U)
+    refused(*device_form(no_map.members[0], pts), R)
+    refused(*device_form(beam, np.ones((4097, 2))), A)
+    # a pose or a measurement value that is not finite
+    for bad in (np.nan, np.inf):
+        broken = poses.copy()
+        broken[3, 2] = bad
+        refused(*raw(lf, "mcl_likelihoods", broken, pts), A)
+        refused(*raw(beam, "mcl_likelihoods", broken, pts), A)
+        refused(*raw(ndt, "mcl_likelihoods_ndt_cells", broken, means, covs), A)
+        refused(*raw(lm, "mcl_likelihoods_landmarks", broken, xyz, cat), A)
+        broken_xyz = xyz.copy()
+        broken_xyz[1, 1] = bad
+        refused(*raw(lm, "mcl_likelihoods_landmarks", poses, broken_xyz, cat), A)
+        refused(*raw(br, "mcl_likelihoods_bearings", poses, broken_xyz, cat), A)
+    # more detections than the landmark kernels take, more points than the beam kernel's workgroup memory
+    many = np.tile(xyz, (33, 1))[:65]
+    refused(*raw(lm, "mcl_likelihoods_landmarks", poses, many, np.zeros(65, dtype=np.uint32)), A)
+    refused(*raw(beam, "mcl_likelihoods", poses, np.zeros((4097, 2)) + 1.0), A)
+    # n == 0 is fine and writes nothing
+    status, out = raw(lf, "mcl_likelihoods", np.zeros((0, 4)), pts)
+    assert status == capi.MCL_OK and (out == SENTINEL).all()
+    # a likelihood-field scan point that is not finite is no refusal: it has no cell for any pose, as in mcl_reweight
+    holed = pts.copy()
+    holed[7] = (np.nan, 1.0)
+    twin = Amcl(grid, MOTION, LF, AmclParams(min_particles=5, max_particles=5), seed=1)
+    np.testing.assert_allclose(lf.likelihoods(poses, holed), reweight_factor(twin, poses, holed), rtol=RTOL, atol=0)
+    for f in (lf, beam, ndt, lm, br, twin):
+        f.close()
+    no_map.close()
