@@ -874,6 +874,48 @@ class Amcl:
             self.sync()
         return out
 
+    # -- beam skipping (Nav2's do_beamskip; likelihood-field filters) -------------------------------------------------------------
+    def set_beam_skip(self, enabled: bool = True, distance: Optional[float] = None, threshold: Optional[float] = None,
+                      error_threshold: Optional[float] = None):
+        """mcl_set_beam_skip: before every reweight the cloud votes on each beam, and beams whose end-point lands within `distance` of
+        an obstacle for no more than `threshold` of the particles are left out of that update - unless `error_threshold` of the scan
+        or more would go, in which case all of it is used.  A value left None keeps what the filter has (Nav2's defaults at first:
+        0.5 m, 0.3, 0.9)."""
+        p = capi.BeamSkipParams()
+        self._check(self._lib.mcl_get_beam_skip(self._ctx, C.byref(p)))
+        p.enabled = int(bool(enabled))
+        for name, value in (("distance", distance), ("threshold", threshold), ("error_threshold", error_threshold)):
+            if value is not None:
+                setattr(p, name, float(value))
+        self._check(self._lib.mcl_set_beam_skip(self._ctx, C.byref(p)))
+
+    def beam_skip(self) -> dict:
+        """The parameters in force (mcl_get_beam_skip)."""
+        p = capi.BeamSkipParams()
+        self._check(self._lib.mcl_get_beam_skip(self._ctx, C.byref(p)))
+        return {"enabled": bool(p.enabled), "distance": p.distance, "threshold": p.threshold, "error_threshold": p.error_threshold}
+
+    def beam_skip_result(self) -> dict:
+        """The decision of the last update or reweight with beam skipping on (mcl_get_beam_skip_result): valid, num_beams,
+        num_particles, num_skipped, used_all, level, and per point of that call's scan `counts` (uint32) and `kept` (bool)."""
+        r = capi.BeamSkipResult()
+        self._check(self._lib.mcl_get_beam_skip_result(self._ctx, C.byref(r), None, None, 0))
+        counts = np.zeros(r.num_beams if r.valid else 0, dtype=np.uint32)
+        kept = np.zeros(len(counts), dtype=np.uint8)
+        if len(counts):
+            self._check(self._lib.mcl_get_beam_skip_result(self._ctx, C.byref(r), counts.ctypes.data_as(capi.c_u32_p),
+                                                           kept.ctypes.data_as(C.POINTER(C.c_uint8)), len(counts)))
+        return {"valid": bool(r.valid), "num_beams": r.num_beams, "num_particles": r.num_particles, "num_skipped": r.num_skipped,
+                "used_all": bool(r.used_all), "level": r.level, "counts": counts, "kept": kept.astype(bool)}
+
+    def beam_agreement(self, measurement) -> np.ndarray:
+        """mcl_beam_agreement: for each point of `measurement` (float64 (B, 2), base frame) the number of particles of the current set
+        whose end-point of it lands within the beam-skip distance of an obstacle - uint32 (B,).  The filter is untouched."""
+        pts = _f64_rows("points", measurement, 2)
+        counts = np.zeros(len(pts), dtype=np.uint32)
+        self._check(self._lib.mcl_beam_agreement(self._ctx, _dp(pts), len(pts), counts.ctypes.data_as(capi.c_u32_p)))
+        return counts
+
     def weight_sum(self) -> float:
         v = C.c_double(0)
         self._check(self._lib.mcl_weight_sum(self._ctx, C.byref(v)))

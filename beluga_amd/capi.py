@@ -132,6 +132,16 @@ class DeviceView(C.Structure):
     ]
 
 
+class BeamSkipParams(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("reserved0", C.c_int32), ("distance", C.c_double), ("threshold", C.c_double),
+                ("error_threshold", C.c_double)]
+
+
+class BeamSkipResult(C.Structure):
+    _fields_ = [("valid", C.c_int32), ("used_all", C.c_int32), ("num_beams", C.c_uint64), ("num_particles", C.c_uint64),
+                ("num_skipped", C.c_uint64), ("level", C.c_double)]
+
+
 class SharedMapInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("resolution", C.c_double), ("sensor_kind", C.c_int32),
                 ("device_id", C.c_int32), ("device_bytes", C.c_uint64), ("host_bytes", C.c_uint64), ("users", C.c_uint32)]
@@ -167,6 +177,11 @@ _SIGNATURES = {
     "mcl_likelihoods_landmarks": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_u32_p, C.c_uint64, c_double_p]),
     "mcl_likelihoods_bearings": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_u32_p, C.c_uint64, c_double_p]),
     "mcl_likelihoods_device": (C.c_int32, [_ctx, C.c_void_p, C.c_uint64, c_double_p, C.c_uint64, C.c_void_p]),
+    "mcl_default_beam_skip_params": (None, [C.POINTER(BeamSkipParams)]),
+    "mcl_set_beam_skip": (C.c_int32, [_ctx, C.POINTER(BeamSkipParams)]),
+    "mcl_get_beam_skip": (C.c_int32, [_ctx, C.POINTER(BeamSkipParams)]),
+    "mcl_get_beam_skip_result": (C.c_int32, [_ctx, C.POINTER(BeamSkipResult), c_u32_p, C.POINTER(C.c_uint8), C.c_uint64]),
+    "mcl_beam_agreement": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_u32_p]),
     "mcl_weight_sum": (C.c_int32, [_ctx, c_double_p]),
     "mcl_normalize": (C.c_int32, [_ctx, C.c_double, C.POINTER(WeightStats)]),
     "mcl_resample": (C.c_int32, [_ctx, C.c_double, C.c_uint32, c_u64_p]),
@@ -255,7 +270,9 @@ _SIGNATURES = {
 # symbols a library may lack and still load (an older build named by BELUGA_MCL_LIB: tools/exp_ndt_small.py and tools/exp_landmark_small.py measure against one)
 _OPTIONAL = {"mcl_measurement_build", "mcl_set_ndt_small_cycle", "mcl_get_ndt_small_cycle", "mcl_get_ndt_small_cycle_counts",
              "mcl_ndt_batch_counts", "mcl_set_landmark_small_cycle", "mcl_get_landmark_small_cycle", "mcl_landmark_batch_update",
-             "mcl_set_ndt_map_layout", "mcl_get_ndt_map_layout"}
+             "mcl_set_ndt_map_layout", "mcl_get_ndt_map_layout",
+             # (tools/exp_beam_skip.py measures against a build of the commit before beam skipping)
+             "mcl_default_beam_skip_params", "mcl_set_beam_skip", "mcl_get_beam_skip", "mcl_get_beam_skip_result", "mcl_beam_agreement"}
 _lib = None
 
 

@@ -8,7 +8,7 @@ namespace mcl {
 bool batch_member_fused(const BatchMemberFacts& m) {
   const bool likelihood_field = m.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD || m.sensor_kind == MCL_SENSOR_LIKELIHOOD_FIELD_PROB;
   return likelihood_field && !m.sharded && m.small_fused && m.n >= 1 && m.n <= kBatchMaxParticles && m.max_particles >= 1 &&
-         m.max_particles <= kBatchMaxParticles && m.palette_beams && !m.profiling;
+         m.max_particles <= kBatchMaxParticles && m.palette_beams && !m.profiling && !m.beam_skip;
 }
 
 bool batch_beam_member_fused(const BatchBeamFacts& m) {

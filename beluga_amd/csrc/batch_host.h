@@ -36,6 +36,7 @@ struct BatchMemberFacts {
   uint64_t max_particles;  // min(max_particles, capacity): the candidates of a resampling
   bool palette_beams;      // the cycle's reweight is k_reweight_lf_beams over the palette table, no ordering pass (lf_takes_beams)
   bool profiling;          // stage profiling on: the member's own events bracket its own launches
+  bool beam_skip;          // beam skipping enabled (mcl_set_beam_skip): a count and a synchronisation stand between its propagation and its reweight
 };
 // The member's own mcl_update would run exactly k_propagate_small, k_reweight_lf_beams with a wave per particle, k_small_tail.
 bool batch_member_fused(const BatchMemberFacts& m);

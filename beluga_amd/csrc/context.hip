@@ -24,6 +24,7 @@
 #include <map>
 #include <vector>
 
+#include "beam_skip_host.h"
 #include "beluga_mcl.h"
 #include "cluster_host.h"
 #include "cycle_host.h"
@@ -316,6 +317,23 @@ struct mcl_ctx {
   std::vector<double> likelihoods_records;  // the NDT cells or detection records of the call, before they are staged
   hipEvent_t likelihoods_event{nullptr};
   bool likelihoods_in_flight{false};
+
+  // Beam skipping (mcl_set_beam_skip; likelihood-field contexts): the parameters, the last decision by the caller's points, and the
+  // count's own buffers - the finite points of the scan up, their counts down (BeamSkipLayout, scratch_layout.h; every count ends in a
+  // synchronisation, so nothing of it is ever in flight at the next).  Nothing is derived from the field: the count reads it as it is.
+  mcl_beam_skip_params beam_skip{0, 0, 0.5, 0.3, 0.9};
+  DeviceBuffer<double> d_beam_skip;
+  HostBuffer<double> h_beam_skip;
+  std::vector<uint32_t> beam_skip_slot;    // staged point -> the caller's point
+  std::vector<uint32_t> beam_skip_counts;  // the last decision's counts and mask, by the caller's points
+  std::vector<uint8_t> beam_skip_kept;
+  std::vector<double> beam_skip_points;    // the kept points: the scan the reweight stages
+  mcl_beam_skip_result beam_skip_last{};
+  uint64_t beam_skip_launches{0};    // count launches of enabled cycles and reweights (mcl_get_counter)
+  uint64_t beam_skip_used_all{0};    // decisions that fell back to the whole scan
+  uint64_t beam_agreement_calls{0};  // calls of mcl_beam_agreement that reached the device
+  float beam_skip_level() const { return mcl::beam_skip_level(cfg.lf, beam_skip.distance); }
+  bool beam_skip_on() const { return beam_skip.enabled != 0; }
   // A sensor model with a map of its own: no occupancy grid, none of the likelihood-field machinery, the host-read policy path.
   bool off_grid() const { return is_ndt() || is_landmark(); }
   // What random_intersperse's random states are drawn from (random_free_state).
@@ -1062,6 +1080,83 @@ mcl_status ndt_cell_records(mcl_ctx* ctx, const char* who, const double* means, 
   return MCL_OK;
 }
 
+// ---- beam skipping (DESIGN.md "Beam skipping") ---------------------------------------------------------------------------------------
+// The count's buffers for a scan of B points (BeamSkipLayout), made before anything of a cycle moves.
+mcl_status beam_skip_reserve(mcl_ctx* ctx, uint64_t B) {
+  const BeamSkipLayout lay(B);
+  MCL_HIP(ctx, ctx->d_beam_skip.ensure(std::max<size_t>(lay.size, 4)));
+  MCL_HIP(ctx, ctx->h_beam_skip.ensure(std::max<size_t>(lay.size, 4), /*mapped=*/false));
+  return MCL_OK;
+}
+// counts[b], b < B: the live particles that point b of the caller's scan agrees with (include/beluga_mcl.h "Beam skipping"), on the
+// field the context reads now.  The finite points go up (a point with a NaN or infinite coordinate agrees with no pose: stage_points'
+// rule, and no kernel sees it), the kernel runs over the live set - its stored field-frame poses where they describe it, as the reweight
+// would load them; otherwise the product, formed as the reweight forms it: nothing is rebuilt, the set facts stay - and the counts come
+// down behind ONE synchronisation of the stream.  Writes nothing the cycle reads.  *launches: the kernel launches it took.
+mcl_status beam_skip_count(mcl_ctx* ctx, const double* points_xy, uint64_t B, uint32_t* counts, uint32_t* launches) {
+  *launches = 0;
+  std::fill(counts, counts + B, 0u);
+  if (const mcl_status s = beam_skip_reserve(ctx, B)) return s;
+  const BeamSkipLayout lay(B);
+  std::vector<uint32_t>& slot = ctx->beam_skip_slot;
+  slot.clear();
+  double* const h_points = ctx->h_beam_skip.host + lay.points;
+  for (uint64_t b = 0; b < B; ++b) {
+    const double x = points_xy[2 * b], y = points_xy[2 * b + 1];
+    if (!(std::isfinite(x) && std::isfinite(y))) continue;
+    h_points[2 * slot.size()] = x;
+    h_points[2 * slot.size() + 1] = y;
+    slot.push_back(static_cast<uint32_t>(b));
+  }
+  const uint32_t staged = static_cast<uint32_t>(slot.size());
+  if (staged == 0 || ctx->n == 0) return MCL_OK;
+  double* const block = ctx->d_beam_skip.ptr;
+  uint32_t* const d_counts = reinterpret_cast<uint32_t*>(block + lay.counts);
+  MCL_HIP(ctx, hipMemcpyAsync(block + lay.points, h_points, 2 * static_cast<size_t>(staged) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const FieldPosePlan poses = field_pose_plan(ctx->tuning, ctx->d_field_pose.ptr != nullptr, ctx->facts, ctx->map_generation);
+  const bool ahead = poses.load && !poses.rebuild_first;
+  *launches = launch_beam_agreement(ctx->stream, ahead ? ctx->d_field_pose.ptr : ctx->cur().pose, ahead, ctx->n, ctx->field_view(), ctx->beam_skip_level(),
+                                    block + lay.points, staged, d_counts);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("beam agreement: ") + hipGetErrorString(e));
+  uint32_t* const h_counts = reinterpret_cast<uint32_t*>(ctx->h_beam_skip.host + lay.counts);
+  MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts, static_cast<size_t>(staged) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint32_t k = 0; k < staged; ++k) counts[slot[k]] = h_counts[k];
+  return MCL_OK;
+}
+// An enabled cycle's or reweight's step between the propagation and the reweight: the count over the live set, the one added
+// synchronisation, the decision (beam_skip_decide) - recorded for mcl_get_beam_skip_result - and *m becomes the scan the reweight
+// stages: the kept points in the caller's order, or the caller's scan as it came where the whole of it is used.  Opens
+// MCL_STAGE_REWEIGHT: the do_reweight behind it is told so.  An empty set takes no decision.
+mcl_status beam_skip_select(mcl_ctx* ctx, Measurement* m) {
+  stage_begin(ctx, MCL_STAGE_REWEIGHT);
+  if (ctx->n == 0) return MCL_OK;
+  const uint64_t B = m->doubles / 2;
+  ctx->beam_skip_counts.resize(B);
+  ctx->beam_skip_kept.resize(B);
+  uint32_t launches = 0;
+  if (const mcl_status s = beam_skip_count(ctx, m->data, B, ctx->beam_skip_counts.data(), &launches)) return s;
+  ctx->beam_skip_launches += launches;
+  const BeamSkipDecision d = beam_skip_decide(ctx->beam_skip_counts.data(), B, ctx->n, ctx->beam_skip.threshold, ctx->beam_skip.error_threshold,
+                                              ctx->beam_skip_kept.data());
+  ctx->beam_skip_last = mcl_beam_skip_result{1, d.used_all ? 1 : 0, B, ctx->n, d.skipped, static_cast<double>(ctx->beam_skip_level())};
+  if (d.used_all) {
+    ctx->beam_skip_used_all += 1;
+    return MCL_OK;
+  }
+  if (d.skipped == 0) return MCL_OK;
+  std::vector<double>& kept = ctx->beam_skip_points;
+  kept.clear();
+  kept.reserve(2 * (B - d.skipped));
+  for (uint64_t b = 0; b < B; ++b) {
+    if (!ctx->beam_skip_kept[b]) continue;
+    kept.push_back(m->data[2 * b]);
+    kept.push_back(m->data[2 * b + 1]);
+  }
+  *m = Measurement{kept.data(), kept.size()};
+  return MCL_OK;
+}
+
 // What do_reweight's prologue settles for the steps behind it: the hold decision, the ordering and the family's own reweight.
 struct ReweightStep {
   Measurement m;   // as staged
@@ -1093,7 +1188,7 @@ void plan_reweight_lf(mcl_ctx* ctx, ReweightStep* step) {
 // What the predicates of batch_host.h read of a member, family by family.
 BatchMemberFacts batch_lf_facts(const mcl_ctx* ctx, const LfReweightArgs& lf) {
   return BatchMemberFacts{ctx->cfg.sensor_kind, ctx->sharded(), ctx->tuning.small_fused != 0, ctx->n, ctx->max_live(),
-                          lf_takes_beams(lf, ctx->tuning), ctx->profile != 0};
+                          lf_takes_beams(lf, ctx->tuning), ctx->profile != 0, ctx->beam_skip_on()};
 }
 BatchBeamFacts batch_beam_facts(const mcl_ctx* ctx) {
   return BatchBeamFacts{ctx->cfg.sensor_kind, ctx->sharded(), ctx->tuning.small_fused != 0, ctx->tuning.batch_beam_fused != 0, ctx->n, ctx->max_live(),
@@ -1216,9 +1311,9 @@ void reweight_landmark(mcl_ctx* ctx, const ReweightStep& step) {
 
 // points_staged: stage_points + the pull already happened (mcl_update); keys_ready: k_propagate emitted the ordering keys.
 // want_weight_sums: the normalisation follows at once (mcl_update): the LF patch kernel leaves the sums of its workgroups' new
-// weights in d_lf_wsum (facts.lf_sums() of them; 0 if another kernel ran).
+// weights in d_lf_wsum (facts.lf_sums() of them; 0 if another kernel ran).  stage_open: beam_skip_select has opened MCL_STAGE_REWEIGHT.
 mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, bool keys_ready = false,
-                       bool want_weight_sums = false, HeldCycle* hold = nullptr) {
+                       bool want_weight_sums = false, HeldCycle* hold = nullptr, bool stage_open = false) {
   const SensorFamily family = ctx->family();
   ctx->facts.lf_sums_dropped();
   if (const mcl_status s = reweight_preconditions(ctx, ctx->off_grid() ? 0 : m.doubles / 2)) return s;
@@ -1230,7 +1325,7 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
       points_pulled(ctx, true);
     }
   }
-  stage_begin(ctx, MCL_STAGE_REWEIGHT);
+  if (!stage_open) stage_begin(ctx, MCL_STAGE_REWEIGHT);
   const LfPlanner::Mode mode = plan_lf(ctx);
   const bool ordered = ctx->wants_ordering();  // (asked while this cycle's mode is decided)
   const bool dispersed = ctx->lf_planner.gathers_dispersed(ctx->tuning);
@@ -2950,6 +3045,12 @@ mcl_status mcl_reweight(mcl_ctx* ctx, const double* points_xy, uint64_t num_poin
     if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
     return do_reweight(ctx, ndt_fit_scan(ctx, points_xy, num_points));
   }
+  if (ctx->beam_skip_on()) {  // the vote first, then the reweight with the scan it leaves
+    if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
+    Measurement m = scan_measurement(points_xy, num_points);
+    if (const mcl_status s = beam_skip_select(ctx, &m)) return s;
+    return do_reweight(ctx, m, false, false, false, nullptr, /*stage_open=*/true);
+  }
   return do_reweight(ctx, scan_measurement(points_xy, num_points));
 }
 
@@ -3151,12 +3252,24 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
     return sharded_update(ctx, pose, m, estimate, info);
   }
   if (ctx->family() == SensorFamily::kNdt) m = ndt_fit_scan(ctx, m.data, m.doubles / 2);  // the scan's measurement cells are what the cycle uploads
-  if (const mcl_status s = stage_points(ctx, &m)) return s;
+  // Beam skipping: the scan the reweight stages is known only behind the propagation - the cycle takes the stage-level form of both,
+  // mcl_propagate and mcl_reweight, with the vote between them (beam_skip_select), and runs as its own inside a batch.
+  const bool skipping = ctx->beam_skip_on();
+  if (skipping) {
+    hold = nullptr;
+    if (const mcl_status s = beam_skip_reserve(ctx, m.doubles / 2)) return s;
+  } else if (const mcl_status s = stage_points(ctx, &m)) {
+    return s;
+  }
   consume_motion();
   advance_window(ctx, pose);
 
   bool keys_ready = false;
-  if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, m.doubles, &keys_ready, hold)) return s;  // :174-175
+  if (skipping) {
+    if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step)) return s;  // :174-175
+  } else if (const mcl_status s = do_propagate(ctx, ctx->window0, ctx->window1, ctx->step, m.doubles, &keys_ready, hold)) {  // :174-175
+    return s;
+  }
   const auto t_first = std::chrono::steady_clock::now();
   // With a fixed particle count and no selective resampling nothing in the cycle depends on a host-side decision: the
   // recovery estimator runs on the device as well and the cycle synchronises once, at the estimate.
@@ -3165,7 +3278,9 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   // landmark and bearing models follow it)
   const bool device_policy = !ap.selective_resampling && ap.min_particles >= ctx->max_live() && ctx->tuning.device_policy != 0 && !ctx->off_grid();
   // (the normalisation follows at once: the LF kernel leaves the sums it is built on)
-  if (const mcl_status s = do_reweight(ctx, m, true, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0, hold)) return s;  // :176
+  if (skipping)
+    if (const mcl_status s = beam_skip_select(ctx, &m)) return s;
+  if (const mcl_status s = do_reweight(ctx, m, !skipping, keys_ready, /*want_weight_sums=*/ctx->tuning.lf_weight_sums != 0, hold, skipping)) return s;  // :176
   // Small sets (the reference's own sizes): everything behind the reweight in ONE launch of one workgroup and one synchronisation
   // (k_small_tail) - the policies are evaluated on the device, the host keeps the recovery filters' state.
   const uint64_t every_n = next_every_n(ctx->every_n_current, ap.resample_interval);  // :181 (stored by the path that takes the cycle)
@@ -4158,6 +4273,9 @@ constexpr Counter kCounters[] = {
     {"order_ahead_used", &mcl_ctx::order_ahead_used},
     {"order_ahead_missed", &mcl_ctx::order_ahead_missed},
     {"field_pose_rebuilds", &mcl_ctx::field_pose_rebuilds},
+    {"beam_skip_launches", &mcl_ctx::beam_skip_launches},
+    {"beam_skip_used_all", &mcl_ctx::beam_skip_used_all},
+    {"beam_agreement_calls", &mcl_ctx::beam_agreement_calls},
     {"host_cycles", &mcl_ctx::host_cycles},
     {"cluster_cells", &mcl_ctx::cluster_cells},
     {"comm_bytes_out", &mcl_ctx::comm_bytes_out},
@@ -4237,6 +4355,8 @@ mcl_status mcl_debug_last_sampler(mcl_ctx* ctx, double out[9]) {
 mcl_status mcl_comm_attach(mcl_ctx* ctx, uint32_t rank, uint32_t world, const mcl_transport* transport) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach: the NDT, landmark and bearing models run on one device");
+  if (world > 1 && ctx->beam_skip_on())  // (before any collective: the ranks' counts are not exchanged yet)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach: beam skipping is enabled, and a sharded filter does not vote yet (mcl_set_beam_skip)");
   MCL_REQUIRE(ctx, world >= 1 && world <= 64 && rank < world, "mcl_comm_attach: world must be 1..64, rank < world");
   MCL_REQUIRE(ctx, world == 1 || (transport && transport->all_gather && transport->all_to_all), "mcl_comm_attach: incomplete transport");
   MCL_REQUIRE(ctx, world == 1 || ctx->cfg.shard_capacity > 0, "mcl_comm_attach: create the context with its shard_offset / shard_capacity");
@@ -4271,6 +4391,8 @@ mcl_status mcl_comm_unique_id(uint8_t id[128]) {
 mcl_status mcl_comm_attach_rccl(mcl_ctx* ctx, const uint8_t id[128], uint32_t rank, uint32_t world) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach_rccl: the NDT, landmark and bearing models run on one device");
+  if (world > 1 && ctx->beam_skip_on())  // (before the communicator is made: ncclCommInitRank is a collective)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach_rccl: beam skipping is enabled, and a sharded filter does not vote yet (mcl_set_beam_skip)");
   MCL_REQUIRE(ctx, id && world >= 1 && world <= 64 && rank < world, "mcl_comm_attach_rccl: bad argument");
   std::string error;
   RcclApi* api = rccl_api(&error);
@@ -4710,6 +4832,61 @@ mcl_status mcl_likelihoods_device(mcl_ctx* ctx, const double* d_poses, uint64_t 
   LikelihoodsLayout lay(0, 0);
   if (const mcl_status s = likelihoods_stage(ctx, m, 0, &lay)) return s;
   return likelihoods_launch(ctx, d_poses, n, m, ctx->d_likelihoods.ptr + lay.measurement, d_out);
+}
+
+// ---- beam skipping: the parameters, the last decision, and the count as a call of its own -------------------------------------------
+void mcl_default_beam_skip_params(mcl_beam_skip_params* params) {
+  if (params) *params = mcl_beam_skip_params{0, 0, 0.5, 0.3, 0.9};  // Nav2's defaults
+}
+static mcl_status beam_skip_supported(mcl_ctx* ctx, const char* who) {
+  if (ctx->family() != SensorFamily::kLikelihoodField)
+    return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": beam skipping is for the likelihood-field models");
+  return MCL_OK;
+}
+mcl_status mcl_set_beam_skip(mcl_ctx* ctx, const mcl_beam_skip_params* params) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (const mcl_status s = beam_skip_supported(ctx, "mcl_set_beam_skip")) return s;
+  MCL_REQUIRE(ctx, params, "mcl_set_beam_skip: null params");
+  if (const char* wrong = beam_skip_check_params(*params)) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, std::string("mcl_set_beam_skip: ") + wrong);
+  if (params->enabled && ctx->sharded())
+    return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_beam_skip: the context is one rank of a sharded filter, whose counts are not exchanged yet");
+  ctx->beam_skip = *params;
+  ctx->beam_skip.reserved0 = 0;
+  ctx->beam_skip_last = mcl_beam_skip_result{};  // (a decision under other parameters is no answer to a question about these)
+  return MCL_OK;
+}
+mcl_status mcl_get_beam_skip(mcl_ctx* ctx, mcl_beam_skip_params* params) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (const mcl_status s = beam_skip_supported(ctx, "mcl_get_beam_skip")) return s;
+  MCL_REQUIRE(ctx, params, "mcl_get_beam_skip: null params");
+  *params = ctx->beam_skip;
+  return MCL_OK;
+}
+mcl_status mcl_get_beam_skip_result(mcl_ctx* ctx, mcl_beam_skip_result* result, uint32_t* counts, uint8_t* kept, uint64_t capacity) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (const mcl_status s = beam_skip_supported(ctx, "mcl_get_beam_skip_result")) return s;
+  MCL_REQUIRE(ctx, result, "mcl_get_beam_skip_result: null result");
+  const mcl_beam_skip_result& last = ctx->beam_skip_last;
+  MCL_REQUIRE(ctx, !(counts || kept) || capacity >= last.num_beams, "mcl_get_beam_skip_result: capacity is below num_beams");
+  *result = last;
+  result->level = static_cast<double>(ctx->beam_skip_level());
+  if (!last.valid) return MCL_OK;
+  if (counts) std::copy(ctx->beam_skip_counts.begin(), ctx->beam_skip_counts.begin() + last.num_beams, counts);
+  if (kept) std::copy(ctx->beam_skip_kept.begin(), ctx->beam_skip_kept.begin() + last.num_beams, kept);
+  return MCL_OK;
+}
+mcl_status mcl_beam_agreement(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, uint32_t* counts) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (const mcl_status s = beam_skip_supported(ctx, "mcl_beam_agreement")) return s;
+  MCL_REQUIRE(ctx, num_points == 0 || (points_xy && counts), "mcl_beam_agreement: null argument");
+  if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;  // (no map: MCL_ERR_NOT_READY)
+  if (ctx->n == 0) return fail(ctx, MCL_ERR_NOT_READY, "mcl_beam_agreement: no particles");
+  if (num_points == 0) return MCL_OK;
+  if (const mcl_status s = bind_device(ctx)) return s;
+  uint32_t launches = 0;
+  if (const mcl_status s = beam_skip_count(ctx, points_xy, num_points, counts, &launches)) return s;
+  ctx->beam_agreement_calls += 1;
+  return MCL_OK;
 }
 
 mcl_status mcl_sync(mcl_ctx* ctx) {

@@ -255,6 +255,18 @@ void launch_likelihoods_ndt_hashed(hipStream_t st, const double4* poses, uint64_
 void launch_likelihoods_landmarks(hipStream_t st, const double4* poses, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k,
                                   bool bearing, double* out);
 
+// ---- beam skipping: the cloud's vote on every beam (mcl_beam_agreement, the enabled cycle; DESIGN.md "Beam skipping") ---------------------
+// count[b] = the poses i < n whose end-point of scan point b has a cell inside the grid with f.data[cell] > level - the exact cell of
+// lf_beam, the f32 field itself (whatever field the view reads: nothing derived, nothing to rebuild).  pose: the particles' poses, or
+// (pose_ahead) their field-frame form as FieldPoseOut left it.  d_points: B finite points (stage_points' rule: the others agree with
+// no pose and are never sent).  A lane per pose, a bounded grid striding over the set, the beam uniform across the wave: a ballot and
+// a popcount per beam into the workgroup's LDS counters, one vector atomicAdd per counter and workgroup at the end - integer adds, so
+// the result does not depend on the geometry.  A scan of more than kBeamSkipPass beams takes a launch per pass.  Zeroes count first.
+// Returns the kernel launches (0 for n == 0 or B == 0: count is not touched).
+constexpr uint32_t kBeamSkipPass = 4096;  // beams of one launch: its LDS counters (16 KB)
+uint32_t launch_beam_agreement(hipStream_t st, const double4* pose, bool pose_ahead, uint64_t n, const FieldView& f, float level,
+                               const double* d_points, uint32_t B, uint32_t* count);
+
 struct HashParams {
   double res_x, res_y, res_theta;
 };

@@ -1815,6 +1815,56 @@ __global__ __launch_bounds__(kBlock) void k_likelihoods_lf_field(const double4* 
   out[i] = f.prob ? exp(acc) : acc;
 }
 
+// -- beam skipping: how many poses does each beam agree with (launch_beam_agreement, kernels.h) ---------------------------------------
+// The end-point and its cell are lf_beam's, expression for expression (each product and sum rounded on its own, floor, the unsigned
+// in-grid test); an end-point without an int32 cell (NaN, |v| >= 2^31: the conversion would saturate or give 0) is not in the grid.
+// The beam index is uniform: the points come through scalar loads; eight beams' gathers are in flight together.  The loop over the
+// set runs whole workgroups (a lane past n votes no), so that every wave reaches every ballot with all its lanes.
+constexpr uint32_t kBeamSkipMaxBlocks = 1024;  // four workgroups per CU: enough lanes to hide the gathers, few enough flushes
+__device__ __forceinline__ bool beam_agrees(const FieldView& f, float level, double px, double py, double ct, double st, double xt, double yt) {
+  const double vx = (px * ct - py * st + xt) * f.inv_resolution;
+  const double vy = (px * st + py * ct + yt) * f.inv_resolution;
+  const int xi = static_cast<int>(floor(vx));
+  const int yi = static_cast<int>(floor(vy));
+  const bool inside = fabs(vx) < 2147483648.0 && fabs(vy) < 2147483648.0 && static_cast<unsigned>(xi) < f.W && static_cast<unsigned>(yi) < f.H;
+  const size_t idx = inside ? static_cast<size_t>(yi) * f.W + static_cast<size_t>(xi) : size_t{0};  // (branch-free, as lf_beam)
+  return inside && f.data[idx] > level;
+}
+__global__ __launch_bounds__(kBlock) void k_beam_agreement(const double4* __restrict__ pose, uint32_t pose_ahead, uint64_t n, FieldView f,
+                                                           float level, const double* __restrict__ pts, uint32_t B,
+                                                           uint32_t* __restrict__ count) {
+  __shared__ uint32_t s_count[kBeamSkipPass];
+  for (uint32_t b = threadIdx.x; b < B; b += kBlock) s_count[b] = 0u;
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t whole = (n + kBlock - 1) / kBlock * kBlock;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * kBlock;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x; i < whole; i += stride) {
+    const bool live = i < n;
+    const Pose2 T = ordered_pose(f.world_to_field, pose, live ? i : n - 1, pose_ahead != 0u);  // likelihood_field_model.hpp:70
+    const double ct = T.r.c, st = T.r.s, xt = T.x, yt = T.y;
+    uint32_t b = 0;
+#pragma unroll 1
+    for (; b + 8 <= B; b += 8) {
+      bool a[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) a[k] = beam_agrees(f, level, pts[2 * (b + k)], pts[2 * (b + k) + 1], ct, st, xt, yt);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const uint32_t votes = static_cast<uint32_t>(__popcll(__ballot(a[k] && live)));
+        if (lane == 0 && votes) atomicAdd(&s_count[b + k], votes);
+      }
+    }
+    for (; b < B; ++b) {
+      const uint32_t votes = static_cast<uint32_t>(__popcll(__ballot(beam_agrees(f, level, pts[2 * b], pts[2 * b + 1], ct, st, xt, yt) && live)));
+      if (lane == 0 && votes) atomicAdd(&s_count[b], votes);
+    }
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < B; b += kBlock)
+    if (const uint32_t c = s_count[b]) atomicAdd(&count[b], c);
+}
+
 // -- spatial ordering of the particles --------------------------------------------------------------
 // A full sort of (key, index) by the 20-bit ordering key, most significant digit first, two digits of 10 bits:
 //   keys + block histograms of the HIGH digit (inside k_propagate, or k_order_keys)  ->  row scan (+ digit totals)  ->
@@ -4740,6 +4790,18 @@ void launch_likelihoods_lf(hipStream_t st, const double4* poses, uint64_t n, con
       hipLaunchKernelGGL(k_likelihoods_lf<false>, grid, dim3(kBeamsBlock), lf_palette_lds(f), st, poses + at, count, f,
                          reinterpret_cast<const double2*>(d_points), B, per_wave, pts_at, out + at);
   }
+}
+
+uint32_t launch_beam_agreement(hipStream_t st, const double4* pose, bool pose_ahead, uint64_t n, const FieldView& f, float level,
+                               const double* d_points, uint32_t B, uint32_t* count) {
+  if (n == 0 || B == 0) return 0;
+  (void)hipMemsetAsync(count, 0, static_cast<size_t>(B) * sizeof(uint32_t), st);
+  const unsigned blocks = static_cast<unsigned>(std::min<uint64_t>((n + kBlock - 1) / kBlock, kBeamSkipMaxBlocks));
+  uint32_t launches = 0;
+  for (uint32_t b0 = 0; b0 < B; b0 += kBeamSkipPass, ++launches)
+    hipLaunchKernelGGL(k_beam_agreement, dim3(blocks), dim3(kBlock), 0, st, pose, pose_ahead ? 1u : 0u, n, f, level, d_points + 2 * static_cast<size_t>(b0),
+                       std::min(kBeamSkipPass, B - b0), count + b0);
+  return launches;
 }
 
 }  // namespace mcl

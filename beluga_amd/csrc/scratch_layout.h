@@ -245,4 +245,17 @@ struct LikelihoodsLayout {
   }
 };
 
+// ---- beam skipping: d_beam_skip and h_beam_skip, the count's own doubles - the staged scan (x, y per point) and, behind it, the counts ----
+// The counts are uint32, two to a double: the area is rounded up to whole doubles and starts at a multiple of 16 bytes (the points
+// take an even number of doubles).  The same layout in device memory and in the pinned host block that stages one and receives the other.
+struct BeamSkipLayout {
+  size_t points, counts, size;
+  explicit BeamSkipLayout(uint64_t num_points) {
+    Cursor c;
+    points = c.take(2 * static_cast<size_t>(num_points));
+    counts = c.take((static_cast<size_t>(num_points) + 1) / 2);
+    size = c.at;
+  }
+};
+
 }  // namespace mcl

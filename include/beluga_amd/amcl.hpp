@@ -743,6 +743,36 @@ class Amcl {
                                    categories.size(), out.data()));
     return out;
   }
+  /// Extension: beam skipping (mcl_set_beam_skip; Nav2 AMCL's do_beamskip, beam_skip_distance, beam_skip_threshold,
+  /// beam_skip_error_threshold).  Before every reweight the cloud votes on each beam; beams that too few particles can explain are
+  /// left out of that update, unless so much of the scan would go that all of it is used.  Likelihood-field sensor models only.
+  void set_beam_skip(bool enabled, double distance = 0.5, double threshold = 0.3, double error_threshold = 0.9) {
+    const mcl_beam_skip_params p{enabled ? 1 : 0, 0, distance, threshold, error_threshold};
+    check(mcl_set_beam_skip(ctx_, &p));
+  }
+  /// The decision of the last update with beam skipping on (mcl_get_beam_skip_result), counts and mask by the points of that scan.
+  struct BeamSkipResult {
+    mcl_beam_skip_result summary{};
+    std::vector<std::uint32_t> counts;
+    std::vector<std::uint8_t> kept;
+  };
+  [[nodiscard]] BeamSkipResult beam_skip_result() {
+    BeamSkipResult r;
+    check(mcl_get_beam_skip_result(ctx_, &r.summary, nullptr, nullptr, 0));
+    if (!r.summary.valid) return r;
+    r.counts.resize(r.summary.num_beams);
+    r.kept.resize(r.summary.num_beams);
+    check(mcl_get_beam_skip_result(ctx_, &r.summary, r.counts.data(), r.kept.data(), r.summary.num_beams));
+    return r;
+  }
+  /// For each point of `measurement` (base frame), the particles of the current set it agrees with (mcl_beam_agreement).  The filter
+  /// is untouched: particles, weights, random stream, policies and counters stay as they are.
+  [[nodiscard]] std::vector<std::uint32_t> beam_agreement(const std::vector<std::pair<double, double>>& measurement) {
+    static_assert(sizeof(std::pair<double, double>) == 2 * sizeof(double), "points are handed over as (x, y) doubles");
+    std::vector<std::uint32_t> counts(measurement.size());
+    check(mcl_beam_agreement(ctx_, measurement.empty() ? nullptr : &measurement.data()->first, measurement.size(), counts.data()));
+    return counts;
+  }
   /// Extension (the landmark and bearing constructor forms only; throws on another sensor model): the small cycle of a landmark or
   /// bearing filter, mcl_set_landmark_small_cycle.  Sets of up to 4096 particles take a wave-per-particle reweight (bit for bit the
   /// lane-per-particle kernels' weights) and the one-launch tail with one host synchronisation.  Off by default.

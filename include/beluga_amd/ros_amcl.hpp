@@ -74,6 +74,15 @@ namespace ros {
 /// beluga_ros::AmclParams (beluga_ros/include/beluga_ros/amcl.hpp:54-98): same fields, same defaults.
 using AmclParams = beluga_amd::AmclParams;
 
+/// Extension: Nav2 AMCL's four beam-skipping parameters under their ROS names (the reference has none: "Beluga AMCL does not support
+/// beam skipping").  Kept beside AmclParams, which goes on mirroring the reference's struct; hand it to Amcl::set_beam_skip.
+struct BeamSkipParams {
+  bool do_beamskip = false;
+  double beam_skip_distance = 0.5;
+  double beam_skip_threshold = 0.3;
+  double beam_skip_error_threshold = 0.9;
+};
+
 /// beluga_ros::Amcl (beluga_ros/include/beluga_ros/amcl.hpp:102-282).
 template <class OccupancyGrid>
 class Amcl {
@@ -151,6 +160,15 @@ class Amcl {
   /// scores for a list of candidate poses, the filter untouched.
   [[nodiscard]] std::vector<double> likelihoods(const std::vector<SE2d>& states, const std::vector<std::pair<double, double>>& measurement) {
     return filter_.likelihoods(states, measurement);
+  }
+
+  /// Extension: beam skipping with Nav2's parameters (beluga_amd::Amcl::set_beam_skip; likelihood-field sensor models only).
+  void set_beam_skip(const BeamSkipParams& p) {
+    filter_.set_beam_skip(p.do_beamskip, p.beam_skip_distance, p.beam_skip_threshold, p.beam_skip_error_threshold);
+  }
+  /// Extension: per point of the scan, how many particles it agrees with (beluga_amd::Amcl::beam_agreement); the filter untouched.
+  [[nodiscard]] std::vector<std::uint32_t> beam_agreement(const std::vector<std::pair<double, double>>& measurement) {
+    return filter_.beam_agreement(measurement);
   }
 
   /// Force a manual update of the particles on the next iteration of the filter (:263).

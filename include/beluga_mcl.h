@@ -445,6 +445,65 @@ mcl_status mcl_likelihoods_bearings(mcl_ctx* ctx, const double* poses, uint64_t 
  * the host: a pose that is not finite scores whatever the arithmetic gives. */
 mcl_status mcl_likelihoods_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* points_xy, uint64_t num_points, double* d_out);
 
+/* ---- Beam skipping (Nav2 AMCL's do_beamskip) for the likelihood-field models ----------------------------------------------------
+ * A beam that hits something the map does not know - a person, a pallet, an open door - pulls the weight of EVERY particle down
+ * together and flattens the posterior.  With beam skipping the cloud votes on each beam before the reweight: beams that too few
+ * particles can explain are left out of this update.  The vote is per beam over ALL live particles, unweighted - which a sensor
+ * model that is a function of one state cannot express (the reference has none) and a device that visits the (particle x beam)
+ * grid anyway takes as one integer reduction.  MCL_SENSOR_LIKELIHOOD_FIELD and MCL_SENSOR_LIKELIHOOD_FIELD_PROB only.
+ *
+ * level: the value the field builder gives a cell at squared distance float(distance * distance) from the nearest obstacle,
+ *   float(amplitude * exp(-double(float(distance^2)) / (2 sigma_hit^2)) + z_random / max_laser_distance), from the context's
+ *   mcl_lf_params - parameters only, never the map.
+ * agreement: a point of the scan AGREES with a pose iff its end-point's cell - the cell the reweight reads, mcl_reweight's exact
+ *   rule - is inside the grid and field[cell] > level, strictly, on the field mcl_get_likelihood_field returns NOW: host-built,
+ *   device-built, given by mcl_set_likelihood_field, shared, swapped in by mcl_set_map_async.  Off the grid: no.  A point with a
+ *   NaN or infinite coordinate agrees with no pose.
+ * count[b]: the live particles beam b agrees with, taken behind the propagation and in front of the reweight.
+ * decision (n live particles, B points): kept[b] = double(count[b]) / double(n) > threshold; skipped = B - sum kept;
+ *   used_all = B > 0 && double(skipped) / double(B) >= error_threshold.  used_all: too much of the scan disagrees with the cloud, the
+ *   cloud is probably wrong, and the whole scan is used (Nav2's rule).
+ * reweight: with used_all, or disabled, everything is as without the feature.  Otherwise the weights are those mcl_reweight gives for
+ *   the kept points alone, in the caller's order, bit for bit (the same staging, kernel choice and order of the sum).
+ * Applies to mcl_update, mcl_update_laser_scan, mcl_update_point_cloud, mcl_reweight and to a member's cycle in mcl_batch_update
+ * (such a member runs its own cycle: it counts in members_alone; the results are its lone mcl_update's).  mcl_likelihoods* ignore
+ * it.  An enabled cycle costs one launch and ONE more host synchronisation between the propagation and the reweight; a disabled one
+ * nothing at all. */
+typedef struct mcl_beam_skip_params {
+  int32_t enabled;        /* 0 (do_beamskip) */
+  int32_t reserved0;
+  double distance;        /* 0.5 m (beam_skip_distance): how far from an obstacle an end-point may land and still agree */
+  double threshold;       /* 0.3 (beam_skip_threshold): share of the particles a kept beam must agree with, exceeded strictly */
+  double error_threshold; /* 0.9 (beam_skip_error_threshold): share of skipped beams from which on the whole scan is used */
+} mcl_beam_skip_params;
+void mcl_default_beam_skip_params(mcl_beam_skip_params* params);
+/* Allowed between updates, on batch members and on contexts attached to a shared map.  MCL_ERR_UNSUPPORTED on a beam, NDT, landmark
+ * or bearing context, and for enabled = 1 on a context attached to a communicator of several ranks (the counts are not exchanged
+ * yet: mcl_comm_attach* with world > 1 on an enabled context is refused likewise, before any collective);
+ * MCL_ERR_INVALID_ARGUMENT for a value outside its range or not finite.  A refused call leaves the old parameters in place. */
+mcl_status mcl_set_beam_skip(mcl_ctx* ctx, const mcl_beam_skip_params* params);
+mcl_status mcl_get_beam_skip(mcl_ctx* ctx, mcl_beam_skip_params* params);
+typedef struct mcl_beam_skip_result {
+  int32_t valid;          /* an enabled update or reweight has taken a decision (cleared by mcl_set_beam_skip) */
+  int32_t used_all;       /* the whole scan was used after all */
+  uint64_t num_beams;     /* B: the caller's points */
+  uint64_t num_particles; /* n: the live particles that voted */
+  uint64_t num_skipped;   /* beams the vote skipped (with used_all they were used all the same) */
+  double level;           /* the level, widened */
+} mcl_beam_skip_result;
+/* The last decision taken by an update or a reweight of this context; counts[b] and kept[b] (1 / 0) by the caller's points, capacity
+ * entries each, either may be NULL.  MCL_ERR_INVALID_ARGUMENT if capacity < num_beams with an array given.  Without a decision yet:
+ * valid = 0, level filled in, nothing written to the arrays. */
+mcl_status mcl_get_beam_skip_result(mcl_ctx* ctx, mcl_beam_skip_result* result, uint32_t* counts, uint8_t* kept, uint64_t capacity);
+/* The function form: counts[b], b < num_points, of the CURRENT set for a scan - which beams of this scan does the filter think are
+ * not the map?  A dynamic-obstacle mask, a filtered scan for a costmap.  Uses the context's distance whether enabled or not.
+ * THE FILTER IS UNTOUCHED.  Particles, weights and count, step number and random stream, recovery filters, every_n counter,
+ * force_update, control window, cached set facts, spatial order, the work the cycle keeps in flight and every counter of
+ * mcl_get_counter are what they are on a context on which the call was never made.  The call has buffers of its own, runs on the
+ * context's stream behind whatever is in flight, and reads the map the context reads NOW.  (Its own counter, beam_agreement_calls,
+ * apart.)  MCL_ERR_NOT_READY without a map or without particles; num_points == 0 is MCL_OK and does nothing. */
+mcl_status mcl_beam_agreement(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, uint32_t* counts);
+
 typedef struct mcl_weight_stats {
   double sum;        /* sum of weights before normalisation (actions/normalize.hpp:70) */
   double norm_sum;   /* sum of the normalised weights (the Thrun estimator's total, Q1) */
@@ -902,6 +961,9 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *   landmark_lane_launches / landmark_wave_launches = a landmark or bearing context's reweight launches of the lane-per-particle kernel /
  *   of the wave-per-particle kernel (mcl_set_landmark_small_cycle and the size of the set decide; not counted for an empty set or a call
  *   without detections; a fleet's shared launch counts in the member's landmark_wave_launches);
+ *   beam_skip_launches = count launches of enabled cycles and reweights ("Beam skipping": one per pass of 4096 beams; none for an
+ *   empty set or scan), beam_skip_used_all = those decisions that fell back to the whole scan, beam_agreement_calls = calls of
+ *   mcl_beam_agreement that reached the device;
  *   cluster_cells = occupied cells of the last cluster_based_estimate; comm_ranks_seen (ncclCommCount of the library's communicator, 0
  *   without one), comm_collectives, comm_bytes_out (running totals of this rank), comm_backend (0 = none, 1 = the caller's transport, 2 = RCCL inside the library). */
 mcl_status mcl_set_option(mcl_ctx* ctx, const char* name, int64_t value);
