@@ -355,6 +355,7 @@ class SharedMap:
             raise capi.MclError(st, self._lib.mcl_shared_map_last_error(None).decode())
         self._map = handle
         self.shape = (H, W)
+        self.resolution = float(grid.resolution)
 
     def info(self) -> dict:
         """width, height, resolution, sensor_kind, device_id, device_bytes, host_bytes, users (filters attached now)."""
@@ -376,6 +377,16 @@ class SharedMap:
             self.close()
         except Exception:
             pass
+
+
+@dataclass
+class SearchHit:
+    """A candidate of Amcl.global_search: pose (cos, sin, x, y), its score, id = cell * headings + heading, cell = y * width + x."""
+    pose: np.ndarray
+    score: float
+    id: int
+    cell: int
+    heading: int
 
 
 class Amcl:
@@ -544,6 +555,7 @@ class Amcl:
         self._check(self._lib.mcl_set_map(self._ctx, cells.ctypes.data_as(capi.c_i8_p), W, H, float(grid.resolution), _dp(origin),
                                           traits))
         self._shape = (H, W)
+        self._resolution = float(grid.resolution)
         self._pending_shape = None  # (a map given now replaces one that was still on its way)
 
     def use_map(self, shared: SharedMap):
@@ -554,6 +566,7 @@ class Amcl:
             raise ValueError("SharedMap: closed")
         self._check(self._lib.mcl_use_shared_map(self._ctx, shared._map))
         self._shape = shared.shape
+        self._resolution = shared.resolution
         self._pending_shape = None  # (a map given now replaces one that was still on its way)
 
     def build_ndt_map(self, source, resolution: float):
@@ -591,6 +604,7 @@ class Amcl:
         self._check(self._lib.mcl_set_map_async(self._ctx, cells.ctypes.data_as(capi.c_i8_p), W, H, float(grid.resolution), _dp(origin),
                                                 traits))
         self._pending_shape = (H, W)
+        self._pending_resolution = float(grid.resolution)
 
     def map_pending(self) -> int:
         """0: no map on its way, 1: its field is being built, 2: built, waiting for the swap."""
@@ -598,6 +612,7 @@ class Amcl:
         self._check(self._lib.mcl_map_pending(self._ctx, C.byref(v)))
         if v.value == 0 and getattr(self, "_pending_shape", None) is not None:
             self._shape, self._pending_shape = self._pending_shape, None
+            self._resolution = self._pending_resolution
         return v.value
 
     def map_commit(self, wait: bool = True):
@@ -873,6 +888,73 @@ class Amcl:
         if synchronize:
             self.sync()
         return out
+
+    # -- global pose search: every free cell and heading scored by the sensor model, the best kept (mcl_global_search*) ------------
+    def _search_params(self, cell_stride, headings, pool, max_results, separation_xy, separation_theta):
+        """The facade's metres and radians as cells and heading steps, by round()."""
+        headings = int(headings)
+        if not (separation_xy >= 0.0 and math.isfinite(separation_xy) and separation_theta >= 0.0 and math.isfinite(separation_theta)):
+            raise ValueError("global_search: a separation is negative or not finite")
+        # One more call of the library per search, and harmless: a map given by update_map_async is swapped in inside an update(), and
+        # map_pending() is where this object learns of it (_shape, _resolution).
+        self.map_pending()
+        resolution = getattr(self, "_resolution", None)
+        if not resolution:
+            raise ValueError("global_search: the filter has no occupancy grid whose resolution the separation could be counted in")
+        cells = min(int(round(float(separation_xy) / resolution)), 0xFFFFFFFF)
+        steps = min(int(round(float(separation_theta) / (2.0 * math.pi / headings))), 0xFFFFFFFF) if headings > 0 else 0
+        return capi.SearchParams(int(cell_stride), headings, int(pool), int(max_results), cells, steps)
+
+    @staticmethod
+    def _search_hits(hits, count):
+        return [SearchHit(np.array(h.pose, dtype=np.float64), h.score, h.id, h.cell, h.heading) for h in hits[:count]]
+
+    def _search(self, fn, capacity, measurement, params):
+        pts = _f64_rows("points", measurement, 2)
+        hits = (capi.SearchHit * max(int(capacity), 1))()
+        count = C.c_uint64(0)
+        info = capi.SearchInfo()
+        self._check(fn(self._ctx, _dp(pts), len(pts), C.byref(params), hits, int(capacity), C.byref(count), C.byref(info)))
+        self.last_search_info = {name: getattr(info, name) for name, _ in capi.SearchInfo._fields_}
+        return self._search_hits(hits, count.value)
+
+    def global_search(self, measurement, cell_stride=2, headings=72, pool=1024, max_results=16, separation_xy=0.5,
+                      separation_theta=math.radians(30)):
+        """Localising without an initial guess: every free cell of the map whose x and y are multiples of cell_stride, at `headings`
+        headings each, is scored with the sensor model on the device as likelihoods() would score it; of the best `pool` candidates those
+        that lie neither within separation_xy (metres) nor within separation_theta (radians) of a better kept one are returned, best
+        first, at most max_results SearchHit.  The filter is untouched.  Likelihood-field and beam filters; the scan's points (B, 2).
+        last_search_info holds the call's counts."""
+        params = self._search_params(cell_stride, headings, pool, max_results, separation_xy, separation_theta)
+        return self._search(self._lib.mcl_global_search, params.max_results, measurement, params)
+
+    def global_search_pool(self, measurement, cell_stride=2, headings=72, pool=1024):
+        """The pool global_search chooses from, before the suppression: the best `pool` candidates by (score descending, id ascending)."""
+        params = capi.SearchParams(int(cell_stride), int(headings), int(pool), 1, 0, 0)
+        return self._search(self._lib.mcl_global_search_pool, params.pool, measurement, params)
+
+    def search_candidates(self, cell_stride=2, headings=72, first=0, count=None):
+        """The candidates as the device makes them, in id order: (ids uint64 (k,), poses float64 (k, 4), total).  count None: all."""
+        params = capi.SearchParams(int(cell_stride), int(headings), 1, 1, 0, 0)
+        total = C.c_uint64(0)
+        if count is None:
+            self._check(self._lib.mcl_global_search_candidates(self._ctx, C.byref(params), 0, 0, None, None, C.byref(total)))
+            count = max(total.value - int(first), 0)
+        ids = np.zeros(int(count), dtype=np.uint64)
+        poses = np.zeros((int(count), 4), dtype=np.float64)
+        self._check(self._lib.mcl_global_search_candidates(self._ctx, C.byref(params), int(first), int(count), ids.ctypes.data_as(capi.c_u64_p),
+                                                           _dp(poses), C.byref(total)))
+        k = min(int(count), max(total.value - int(first), 0))
+        return ids[:k], poses[:k], total.value
+
+    def relocalize(self, measurement, covariance, **search):
+        """global_search(measurement, **search), then initialize(best pose, covariance): host glue.  Returns the hits; with none
+        (a map without a candidate cell) the filter is left as it was."""
+        hits = self.global_search(measurement, **search)
+        if hits:
+            best = hits[0]
+            self.initialize([best.pose[2], best.pose[3], math.atan2(best.pose[1], best.pose[0])], covariance)
+        return hits
 
     # -- beam skipping (Nav2's do_beamskip; likelihood-field filters) -------------------------------------------------------------
     def set_beam_skip(self, enabled: bool = True, distance: Optional[float] = None, threshold: Optional[float] = None,

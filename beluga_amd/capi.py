@@ -142,6 +142,18 @@ class BeamSkipResult(C.Structure):
                 ("num_skipped", C.c_uint64), ("level", C.c_double)]
 
 
+class SearchParams(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("cell_stride", "headings", "pool", "max_results", "separation_cells", "separation_headings")]
+
+
+class SearchHit(C.Structure):
+    _fields_ = [("pose", C.c_double * 4), ("score", C.c_double), ("id", C.c_uint64), ("cell", C.c_uint32), ("heading", C.c_uint32)]
+
+
+class SearchInfo(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("candidates", C.c_uint64), ("pool_filled", C.c_uint64), ("chunks", C.c_uint32), ("launches", C.c_uint32)]
+
+
 class SharedMapInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("resolution", C.c_double), ("sensor_kind", C.c_int32),
                 ("device_id", C.c_int32), ("device_bytes", C.c_uint64), ("host_bytes", C.c_uint64), ("users", C.c_uint32)]
@@ -177,6 +189,13 @@ _SIGNATURES = {
     "mcl_likelihoods_landmarks": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_u32_p, C.c_uint64, c_double_p]),
     "mcl_likelihoods_bearings": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_u32_p, C.c_uint64, c_double_p]),
     "mcl_likelihoods_device": (C.c_int32, [_ctx, C.c_void_p, C.c_uint64, c_double_p, C.c_uint64, C.c_void_p]),
+    "mcl_default_search_params": (None, [C.POINTER(SearchParams)]),
+    "mcl_global_search": (C.c_int32, [_ctx, c_double_p, C.c_uint64, C.POINTER(SearchParams), C.POINTER(SearchHit), C.c_uint64, c_u64_p,
+                                      C.POINTER(SearchInfo)]),
+    "mcl_global_search_pool": (C.c_int32, [_ctx, c_double_p, C.c_uint64, C.POINTER(SearchParams), C.POINTER(SearchHit), C.c_uint64, c_u64_p,
+                                           C.POINTER(SearchInfo)]),
+    "mcl_global_search_candidates": (C.c_int32, [_ctx, C.POINTER(SearchParams), C.c_uint64, C.c_uint64, c_u64_p, c_double_p, c_u64_p]),
+    "mcl_search_suppress": (C.c_int32, [C.POINTER(SearchHit), C.c_uint64, C.c_uint32, C.POINTER(SearchParams), c_u32_p, c_u64_p]),
     "mcl_default_beam_skip_params": (None, [C.POINTER(BeamSkipParams)]),
     "mcl_set_beam_skip": (C.c_int32, [_ctx, C.POINTER(BeamSkipParams)]),
     "mcl_get_beam_skip": (C.c_int32, [_ctx, C.POINTER(BeamSkipParams)]),

@@ -35,6 +35,7 @@
 #include "ndt_host.h"
 #include "options_host.h"
 #include "scratch_layout.h"
+#include "search_host.h"
 #include "set_facts.h"
 
 namespace {
@@ -317,6 +318,14 @@ struct mcl_ctx {
   std::vector<double> likelihoods_records;  // the NDT cells or detection records of the call, before they are staged
   hipEvent_t likelihoods_event{nullptr};
   bool likelihoods_in_flight{false};
+
+  // mcl_global_search*: the call's own buffers (SearchLayout, scratch_layout.h), sized by the chunk; the measurement is staged as
+  // mcl_likelihoods_device stages it.  Every call ends in a synchronisation, a device error's return included (search_settled): nothing
+  // of it is in flight at the next.
+  DeviceBuffer<double> d_search_f64;
+  DeviceBuffer<unsigned long long> d_search_u64;
+  DeviceBuffer<uint32_t> d_search_u32;
+  HostBuffer<unsigned long long> h_search;
 
   // Beam skipping (mcl_set_beam_skip; likelihood-field contexts): the parameters, the last decision by the caller's points, and the
   // count's own buffers - the finite points of the scan up, their counts down (BeamSkipLayout, scratch_layout.h; every count ends in a
@@ -4832,6 +4841,196 @@ mcl_status mcl_likelihoods_device(mcl_ctx* ctx, const double* d_poses, uint64_t 
   LikelihoodsLayout lay(0, 0);
   if (const mcl_status s = likelihoods_stage(ctx, m, 0, &lay)) return s;
   return likelihoods_launch(ctx, d_poses, n, m, ctx->d_likelihoods.ptr + lay.measurement, d_out);
+}
+
+// ---- global pose search: every free cell and heading scored by likelihoods_launch, the best kept (DESIGN.md "Global pose search") --------
+// The host rule is search_host.cpp's; the chunks are ranges of the map's free-cell list.  Per chunk: the cells that pass the stride test
+// (one launch, and the call's one synchronisation per chunk: their count sizes the next launches), their poses and ids, their scores by
+// the kernels of mcl_likelihoods_device, and the pool's update.  Nothing the update cycle reads is written.
+struct SearchCall {
+  mcl_search_params p;
+  SearchPlan plan;
+  SearchLayout lay;
+  SearchScratch scratch;
+  uint32_t launches;
+};
+static mcl_status search_check(mcl_ctx* ctx, const char* who, const mcl_search_params* params, mcl_search_params* p) {
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the search goes over the free cells of an occupancy grid (likelihood-field and beam contexts)");
+  *p = params ? *params : search_default_params();
+  if (const char* wrong = search_check_params(*p)) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, std::string(who) + ": " + wrong);
+  return MCL_OK;
+}
+// The call's buffers, and the heading table behind whatever the stream holds.
+static mcl_status search_begin(mcl_ctx* ctx, const mcl_search_params& p, SearchCall* call) {
+  const SearchPlan plan = search_plan(ctx->map->n_free, p.headings, ctx->tuning.search_chunk);
+  const SearchLayout lay(p.headings, plan.cells_per_chunk, plan.chunk_candidates, plan.tiles, kSearchTile, kSearchMaxPool);
+  MCL_HIP(ctx, ctx->d_search_f64.ensure(lay.f64_size));
+  MCL_HIP(ctx, ctx->d_search_u64.ensure(lay.u64_size));
+  MCL_HIP(ctx, ctx->d_search_u32.ensure(lay.u32_size));
+  MCL_HIP(ctx, ctx->h_search.ensure(lay.h_size, /*mapped=*/false));
+  std::vector<double> table;
+  search_heading_table(p.headings, table);
+  std::memcpy(ctx->h_search.host + lay.h_table, table.data(), table.size() * sizeof(double));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->d_search_f64.ptr + lay.table, ctx->h_search.host + lay.h_table, table.size() * sizeof(double), hipMemcpyHostToDevice,
+                              ctx->stream));
+  unsigned long long* const u64 = ctx->d_search_u64.ptr;
+  *call = SearchCall{p, plan, lay, SearchScratch{{u64 + lay.run_keys[0], u64 + lay.run_keys[1]}, {u64 + lay.run_ids[0], u64 + lay.run_ids[1]},
+                                                   {u64 + lay.pool_keys[0], u64 + lay.pool_keys[1]}, {u64 + lay.pool_ids[0], u64 + lay.pool_ids[1]}}, 0};
+  return MCL_OK;
+}
+// Chunk c's candidate cells into the `selected` area; *cells = their number, read behind the call's synchronisation of this chunk.
+static mcl_status search_select_chunk(mcl_ctx* ctx, SearchCall* call, uint32_t c, uint32_t* cells) {
+  const uint64_t first = static_cast<uint64_t>(c) * call->plan.cells_per_chunk;
+  const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(call->plan.cells_per_chunk, ctx->map->n_free - first));
+  uint32_t* const u32 = ctx->d_search_u32.ptr;
+  call->launches += launch_search_select(ctx->stream, ctx->map->d_free.ptr + first, count, ctx->map->W, call->p.cell_stride, u32 + call->lay.selected,
+                                         u32 + call->lay.count);
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_search.host + call->lay.h_count, u32 + call->lay.count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(cells, ctx->h_search.host + call->lay.h_count, sizeof(uint32_t));
+  if (*cells > count) return fail(ctx, MCL_ERR_HIP, "global search: the chunk's cell count is beyond its range");
+  return MCL_OK;
+}
+static mcl_status search_generate_chunk(mcl_ctx* ctx, SearchCall* call, uint32_t cells) {
+  const MapStore& map = *ctx->map;
+  call->launches += launch_search_poses(ctx->stream, ctx->d_search_u32.ptr + call->lay.selected, cells, call->p.headings, ctx->d_search_f64.ptr + call->lay.table,
+                                        SearchGrid{map.W, map.resolution, map.origin}, reinterpret_cast<double4*>(ctx->d_search_f64.ptr + call->lay.poses),
+                                        ctx->d_search_u64.ptr + call->lay.ids);
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("global search: ") + hipGetErrorString(e));
+  return MCL_OK;
+}
+static void search_hit_from(const mcl_ctx* ctx, const mcl_search_params& p, const std::vector<double>& table, uint64_t key, uint64_t id, mcl_search_hit* hit) {
+  const MapStore& map = *ctx->map;
+  hit->id = id;
+  hit->cell = static_cast<uint32_t>(id / p.headings);
+  hit->heading = static_cast<uint32_t>(id % p.headings);
+  hit->score = search_score(key);
+  hit->pose[0] = table[2 * hit->heading];
+  hit->pose[1] = table[2 * hit->heading + 1];
+  search_cell_position(hit->cell, map.W, map.resolution, map.origin, hit->pose[2], hit->pose[3]);
+}
+// A device error in the middle of a call (MCL_ERR_HIP, MCL_ERR_OUT_OF_MEMORY: the only statuses that arise once the device is in use) may
+// leave the call's work on the stream: wait for it, so that the next call finds h_search and d_search_* idle, as after every other return.
+static mcl_status search_settled(mcl_ctx* ctx, mcl_status s) {
+  if (s == MCL_ERR_HIP || s == MCL_ERR_OUT_OF_MEMORY) (void)hipStreamSynchronize(ctx->stream);
+  return s;
+}
+static mcl_status global_search(mcl_ctx* ctx, const char* who, const double* points_xy, uint64_t num_points, const mcl_search_params* params,
+                                mcl_search_hit* hits, uint64_t capacity, uint64_t* count, mcl_search_info* info, bool suppress) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  mcl_search_params p{};
+  if (const mcl_status s = search_check(ctx, who, params, &p)) return s;
+  MCL_REQUIRE(ctx, hits && count, std::string(who) + ": null argument");
+  MCL_REQUIRE(ctx, capacity >= (suppress ? p.max_results : p.pool), std::string(who) + ": capacity is below " + (suppress ? "max_results" : "pool"));
+  LikelihoodsMeasurement m{};
+  if (const mcl_status s = likelihoods_points(ctx, who, points_xy, num_points, &m)) return s;
+  if (const mcl_status s = bind_device(ctx)) return s;
+  SearchCall call{p, {}, SearchLayout(1, 0, 0, 0, 0, 0), {}, 0};
+  if (const mcl_status s = search_begin(ctx, p, &call)) return s;
+  LikelihoodsLayout meas(0, 0);
+  if (const mcl_status s = likelihoods_stage(ctx, m, 0, &meas)) return s;
+  double* const f64 = ctx->d_search_f64.ptr;
+  unsigned long long* const u64 = ctx->d_search_u64.ptr;
+  uint64_t cells_total = 0;
+  uint32_t pool_len = 0;
+  int pool_at = 0;
+  for (uint32_t c = 0; c < call.plan.chunks; ++c) {
+    uint32_t cells = 0;
+    if (const mcl_status s = search_select_chunk(ctx, &call, c, &cells)) return s;
+    if (cells == 0) continue;
+    if (const mcl_status s = search_generate_chunk(ctx, &call, cells)) return s;
+    const uint64_t n = static_cast<uint64_t>(cells) * p.headings;
+    if (const mcl_status s = likelihoods_launch(ctx, f64 + call.lay.poses, n, m, ctx->d_likelihoods.ptr + meas.measurement, f64 + call.lay.scores)) return s;
+    call.launches += 1;
+    call.launches += launch_search_pool(ctx->stream, f64 + call.lay.scores, u64 + call.lay.ids, n, call.scratch, p.pool, pool_len, &pool_at);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    pool_len = static_cast<uint32_t>(std::min<uint64_t>(p.pool, pool_len + n));
+    cells_total += cells;
+  }
+  if (pool_len) {
+    MCL_HIP(ctx, hipMemcpyAsync(ctx->h_search.host + call.lay.h_pool_keys, call.scratch.pool_keys[pool_at], pool_len * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, ctx->stream));
+    MCL_HIP(ctx, hipMemcpyAsync(ctx->h_search.host + call.lay.h_pool_ids, call.scratch.pool_ids[pool_at], pool_len * sizeof(unsigned long long),
+                                hipMemcpyDeviceToHost, ctx->stream));
+  }
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<double> table;
+  search_heading_table(p.headings, table);
+  std::vector<mcl_search_hit> pool(pool_len);
+  for (uint32_t i = 0; i < pool_len; ++i)
+    search_hit_from(ctx, p, table, ctx->h_search.host[call.lay.h_pool_keys + i], ctx->h_search.host[call.lay.h_pool_ids + i], &pool[i]);
+  if (suppress) {
+    std::vector<uint32_t> kept(p.max_results);
+    const uint64_t k = search_suppress(pool.data(), pool.size(), ctx->map->W, p, kept.data());
+    for (uint64_t i = 0; i < k; ++i) hits[i] = pool[kept[i]];
+    *count = k;
+  } else {
+    std::copy(pool.begin(), pool.end(), hits);
+    *count = pool_len;
+  }
+  if (info) *info = mcl_search_info{cells_total, cells_total * p.headings, pool_len, call.plan.chunks, call.launches};
+  return MCL_OK;
+}
+
+mcl_status mcl_global_search(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, const mcl_search_params* params, mcl_search_hit* hits,
+                             uint64_t capacity, uint64_t* count, mcl_search_info* info) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  return search_settled(ctx, global_search(ctx, "mcl_global_search", points_xy, num_points, params, hits, capacity, count, info, /*suppress=*/true));
+}
+mcl_status mcl_global_search_pool(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, const mcl_search_params* params, mcl_search_hit* hits,
+                                  uint64_t capacity, uint64_t* count, mcl_search_info* info) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  return search_settled(ctx, global_search(ctx, "mcl_global_search_pool", points_xy, num_points, params, hits, capacity, count, info, /*suppress=*/false));
+}
+static mcl_status search_candidates(mcl_ctx* ctx, const mcl_search_params* params, uint64_t first_id_rank, uint64_t count, uint64_t* ids_out,
+                                    double* poses_out, uint64_t* total) {
+  const char* who = "mcl_global_search_candidates";
+  mcl_search_params p{};
+  if (const mcl_status s = search_check(ctx, who, params, &p)) return s;
+  MCL_REQUIRE(ctx, total && (count == 0 || (ids_out && poses_out)), std::string(who) + ": null argument");
+  if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, std::string(who) + ": no map set");
+  if (const mcl_status s = bind_device(ctx)) return s;
+  SearchCall call{p, {}, SearchLayout(1, 0, 0, 0, 0, 0), {}, 0};
+  if (const mcl_status s = search_begin(ctx, p, &call)) return s;
+  // The free list ascends, a chunk is a range of it: a chunk's ids lie behind those of every chunk before it, and a chunk's rank in
+  // the id order starts where the chunks before it end.  Inside a chunk the compaction's order is undone by a sort.
+  const uint64_t last = first_id_rank + std::min<uint64_t>(count, ~0ull - first_id_rank);
+  std::vector<uint64_t> ids, ids_found;
+  std::vector<double> poses, poses_found;
+  std::vector<uint32_t> order;
+  uint64_t base = 0;
+  for (uint32_t c = 0; c < call.plan.chunks; ++c) {
+    uint32_t cells = 0;
+    if (const mcl_status s = search_select_chunk(ctx, &call, c, &cells)) return s;
+    const uint64_t n = static_cast<uint64_t>(cells) * p.headings;
+    if (n != 0 && base < last && base + n > first_id_rank) {
+      if (const mcl_status s = search_generate_chunk(ctx, &call, cells)) return s;
+      ids.resize(n);
+      poses.resize(4 * n);
+      MCL_HIP(ctx, hipMemcpyAsync(ids.data(), ctx->d_search_u64.ptr + call.lay.ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+      MCL_HIP(ctx, hipMemcpyAsync(poses.data(), ctx->d_search_f64.ptr + call.lay.poses, 4 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      order.resize(n);
+      std::iota(order.begin(), order.end(), 0u);
+      std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return ids[a] < ids[b]; });
+      for (uint64_t r = std::max(base, first_id_rank); r < std::min(base + n, last); ++r) {
+        const uint32_t at = order[r - base];
+        ids_found.push_back(ids[at]);
+        poses_found.insert(poses_found.end(), poses.begin() + 4 * static_cast<size_t>(at), poses.begin() + 4 * static_cast<size_t>(at) + 4);
+      }
+    }
+    base += n;
+  }
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ids_out) std::copy(ids_found.begin(), ids_found.end(), ids_out);
+  if (poses_out) std::copy(poses_found.begin(), poses_found.end(), poses_out);
+  *total = base;
+  return MCL_OK;
+}
+mcl_status mcl_global_search_candidates(mcl_ctx* ctx, const mcl_search_params* params, uint64_t first_id_rank, uint64_t count, uint64_t* ids_out,
+                                        double* poses_out, uint64_t* total) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  return search_settled(ctx, search_candidates(ctx, params, first_id_rank, count, ids_out, poses_out, total));
 }
 
 // ---- beam skipping: the parameters, the last decision, and the count as a call of its own -------------------------------------------

@@ -135,6 +135,8 @@ struct Tuning {
                                     // Measured: profiles/field_pose_ab.txt.
   int lf_unit_weights = 1;          // LF patch kernel on a set whose weights are all 1.0 (fresh from a resampling or an initialisation):
                                     // the old weight is not loaded (1.0 x = x: bit-identical); 0 = always loaded
+  int search_chunk = 1 << 20;       // mcl_global_search*: candidates a chunk holds (64 .. 2^22) - what bounds the call's device memory; the result
+                                    // does not depend on it
 };
 
 // Spatial ordering of the particles (kLfSortedLanes, ordered beam kernel): the 64 lanes of a wave should hold neighbouring

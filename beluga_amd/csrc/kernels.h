@@ -16,6 +16,7 @@
 #include "ndt_hash.h"
 #include "scratch_layout.h"
 #include "se2.h"
+#include "search_host.h"
 #include "sensor_records.h"
 
 namespace mcl {
@@ -266,6 +267,28 @@ void launch_likelihoods_landmarks(hipStream_t st, const double4* poses, uint64_t
 constexpr uint32_t kBeamSkipPass = 4096;  // beams of one launch: its LDS counters (16 KB)
 uint32_t launch_beam_agreement(hipStream_t st, const double4* pose, bool pose_ahead, uint64_t n, const FieldView& f, float level,
                                const double* d_points, uint32_t B, uint32_t* count);
+
+// ---- global pose search (mcl_global_search*; DESIGN.md "Global pose search"; the host rule: search_host.h) -------------------------------
+struct SearchGrid {
+  uint32_t W;
+  double resolution;
+  Pose2 origin;
+};
+// The selection's device arrays (SearchLayout, scratch_layout.h): two sets of sorted runs, the pool twice.
+struct SearchScratch {
+  unsigned long long *run_keys[2], *run_ids[2], *pool_keys[2], *pool_ids[2];
+};
+// Zeroes *selected_count, then compacts the cells of free_cells[0, count) that pass the stride test into `selected` (room for count; any
+// order) and counts them.  Each launcher returns its kernel launches.
+uint32_t launch_search_select(hipStream_t st, const uint32_t* free_cells, uint32_t count, uint32_t W, uint32_t stride, uint32_t* selected,
+                              uint32_t* selected_count);
+// poses[c * headings + h] = (table[h], the centre of cell selected[c] in the world), ids[...] = selected[c] * headings + h.
+uint32_t launch_search_poses(hipStream_t st, const uint32_t* selected, uint32_t cells, uint32_t headings, const double* table, const SearchGrid& g,
+                             double4* poses, unsigned long long* ids);
+// The pool (pool_len entries in set *pool_at, sorted) becomes the best `pool` of itself and the chunk's n (score, id), sorted, in the
+// other set; *pool_at is flipped.  By (key descending, id ascending), exact whatever ties there are.  n == 0: nothing.
+uint32_t launch_search_pool(hipStream_t st, const double* scores, const unsigned long long* ids, uint64_t n, const SearchScratch& s, uint32_t pool,
+                            uint32_t pool_len, int* pool_at);
 
 struct HashParams {
   double res_x, res_y, res_theta;

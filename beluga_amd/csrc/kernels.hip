@@ -4804,6 +4804,167 @@ uint32_t launch_beam_agreement(hipStream_t st, const double4* pose, bool pose_ah
   return launches;
 }
 
+// ---- global pose search (mcl_global_search*; DESIGN.md "Global pose search") -------------------------------------------------------------
+// Generation: the cells of a range of the free list that pass the stride test, compacted in whatever order the waves arrive (the id
+// travels with the pose, so the order decides nothing); then a lane per candidate writes the pose and the id.
+__global__ __launch_bounds__(kBlock) void k_search_select(const uint32_t* __restrict__ free_cells, uint32_t count, uint32_t W, uint32_t stride,
+                                                          uint32_t* __restrict__ selected, uint32_t* __restrict__ selected_count) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  uint32_t cell = 0;
+  bool take = false;
+  if (i < count) {
+    cell = free_cells[i];
+    take = (cell % W) % stride == 0 && (cell / W) % stride == 0;
+  }
+  const unsigned long long ballot = __ballot(take);
+  if (ballot == 0) return;
+  const int lane = threadIdx.x & (kWave - 1), leader = __ffsll(ballot) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(selected_count, static_cast<uint32_t>(__popcll(ballot)));
+  base = __shfl(base, leader);
+  if (take) selected[base + static_cast<uint32_t>(__popcll(ballot & ((1ull << lane) - 1ull)))] = cell;  // (at most `count` cells: the area's size)
+}
+__global__ __launch_bounds__(kBlock) void k_search_generate(const uint32_t* __restrict__ selected, uint32_t cells, uint32_t headings,
+                                                            const double2* __restrict__ table, SearchGrid g, double4* __restrict__ poses,
+                                                            unsigned long long* __restrict__ ids) {
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (i >= static_cast<uint64_t>(cells) * headings) return;
+  const uint32_t c = static_cast<uint32_t>(i / headings), h = static_cast<uint32_t>(i - static_cast<uint64_t>(c) * headings);
+  const uint32_t idx = selected[c];
+  // random_free_state's expressions
+  const double lx = (static_cast<double>(static_cast<int>(idx % g.W)) + 0.5) * g.resolution;
+  const double ly = (static_cast<double>(static_cast<int>(idx / g.W)) + 0.5) * g.resolution;
+  double gx, gy;
+  rot_apply(g.origin.r, lx, ly, gx, gy);
+  const double2 r = table[h];
+  poses[i] = double4{r.x, r.y, gx + g.origin.x, gy + g.origin.y};
+  ids[i] = static_cast<unsigned long long>(idx) * headings + h;
+}
+
+// Selection.  An entry is (key, id): the key is the order-preserving image of the score (search_key, search_host.h; NaN = 0, the lowest),
+// and `a` comes before `b` when its key is higher, or the keys are equal and its id lower.  Ids are unique, so the order is total and a
+// run of equal scores is ordered like anything else: ties need no pass of their own.  Padding is (0, all ones): behind every candidate.
+__device__ __forceinline__ bool search_before(unsigned long long ka, unsigned long long ia, unsigned long long kb, unsigned long long ib) {
+  return ka > kb || (ka == kb && ia < ib);
+}
+__device__ __forceinline__ unsigned long long search_key_of(double score) {
+  if (score != score) return 0ull;
+  const unsigned long long bits = static_cast<unsigned long long>(__double_as_longlong(score));
+  return (bits >> 63) ? ~bits : (bits | (1ull << 63));
+}
+// A workgroup sorts a tile of kSearchTile candidates of the chunk in LDS (bitonic network, 64 KB) and writes the whole tile, padding
+// included, as one sorted run.
+constexpr int kSearchSortBlock = 1024;
+__global__ __launch_bounds__(kSearchSortBlock) void k_search_sort_tiles(const double* __restrict__ scores, const unsigned long long* __restrict__ ids,
+                                                                        uint64_t n, unsigned long long* __restrict__ run_keys,
+                                                                        unsigned long long* __restrict__ run_ids) {
+  __shared__ unsigned long long s_key[kSearchTile];
+  __shared__ unsigned long long s_id[kSearchTile];
+  const uint64_t base = static_cast<uint64_t>(blockIdx.x) * kSearchTile;
+  for (uint32_t t = threadIdx.x; t < kSearchTile; t += kSearchSortBlock) {
+    const uint64_t i = base + t;
+    s_key[t] = i < n ? search_key_of(scores[i]) : 0ull;
+    s_id[t] = i < n ? ids[i] : ~0ull;
+  }
+  __syncthreads();
+  for (uint32_t k = 2; k <= kSearchTile; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = threadIdx.x; t < kSearchTile / 2; t += kSearchSortBlock) {
+        const uint32_t lo = ((t / j) * 2u * j) + (t % j), hi = lo + j;
+        const unsigned long long kl = s_key[lo], il = s_id[lo], kh = s_key[hi], ih = s_id[hi];
+        const bool best_first = (lo & k) == 0;
+        if (best_first ? search_before(kh, ih, kl, il) : search_before(kl, il, kh, ih)) {
+          s_key[lo] = kh;
+          s_id[lo] = ih;
+          s_key[hi] = kl;
+          s_id[hi] = il;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (uint32_t t = threadIdx.x; t < kSearchTile; t += kSearchSortBlock) {
+    run_keys[base + t] = s_key[t];
+    run_ids[base + t] = s_id[t];
+  }
+}
+// Entries of the sorted run (keys, ids)[0, len) that come before (k, i).
+__device__ __forceinline__ uint32_t search_rank_in(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ ids, uint32_t len,
+                                                   unsigned long long k, unsigned long long i) {
+  uint32_t lo = 0, hi = len;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (search_before(keys[mid], ids[mid], k, i)) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+// The best `pool` of two sorted runs, as one sorted run: every entry finds its rank in the union - its own index plus the entries of the
+// other run before it (unique ids: no two entries share a rank) - and is written there if the rank is below `pool`.  A lane per entry.
+__device__ __forceinline__ void search_merge(const unsigned long long* __restrict__ ak, const unsigned long long* __restrict__ ai, uint32_t la,
+                                             const unsigned long long* __restrict__ bk, const unsigned long long* __restrict__ bi, uint32_t lb,
+                                             uint32_t pool, unsigned long long* __restrict__ ok, unsigned long long* __restrict__ oi, uint32_t t) {
+  if (t >= la + lb) return;
+  const bool first = t < la;
+  const uint32_t at = first ? t : t - la;
+  const unsigned long long k = first ? ak[at] : bk[at], i = first ? ai[at] : bi[at];
+  const uint32_t rank = at + (first ? search_rank_in(bk, bi, lb, k, i) : search_rank_in(ak, ai, la, k, i));
+  if (rank < pool) {
+    ok[rank] = k;
+    oi[rank] = i;
+  }
+}
+// One level of the chunk's merge tree: the runs lie `stride` entries apart and hold the best min(pool, candidates of their span) of it;
+// pair blockIdx.y merges runs 2 y and 2 y + 1 into the other buffer, at run 2 y's place.  n: the chunk's candidates.
+__global__ __launch_bounds__(kBlock) void k_search_merge_runs(const unsigned long long* __restrict__ src_keys, const unsigned long long* __restrict__ src_ids,
+                                                              uint64_t n, uint64_t stride, uint32_t pool, unsigned long long* __restrict__ dst_keys,
+                                                              unsigned long long* __restrict__ dst_ids) {
+  const uint64_t a = static_cast<uint64_t>(blockIdx.y) * 2u * stride, b = a + stride;
+  const uint64_t in_a = a < n ? (n - a < stride ? n - a : stride) : 0, in_b = b < n ? (n - b < stride ? n - b : stride) : 0;
+  const uint32_t la = static_cast<uint32_t>(in_a < pool ? in_a : pool), lb = static_cast<uint32_t>(in_b < pool ? in_b : pool);
+  search_merge(src_keys + a, src_ids + a, la, src_keys + b, src_ids + b, lb, pool, dst_keys + a, dst_ids + a, blockIdx.x * kBlock + threadIdx.x);
+}
+// The chunk's last run and the running pool into the next pool.
+__global__ __launch_bounds__(kBlock) void k_search_merge_pool(const unsigned long long* __restrict__ run_keys, const unsigned long long* __restrict__ run_ids,
+                                                              uint32_t run_len, const unsigned long long* __restrict__ pool_keys,
+                                                              const unsigned long long* __restrict__ pool_ids, uint32_t pool_len, uint32_t pool,
+                                                              unsigned long long* __restrict__ next_keys, unsigned long long* __restrict__ next_ids) {
+  search_merge(pool_keys, pool_ids, pool_len, run_keys, run_ids, run_len, pool, next_keys, next_ids, blockIdx.x * kBlock + threadIdx.x);
+}
+
+uint32_t launch_search_select(hipStream_t st, const uint32_t* free_cells, uint32_t count, uint32_t W, uint32_t stride, uint32_t* selected,
+                              uint32_t* selected_count) {
+  (void)hipMemsetAsync(selected_count, 0, sizeof(uint32_t), st);
+  if (count == 0) return 0;
+  hipLaunchKernelGGL(k_search_select, dim3(blocks_for(count)), dim3(kBlock), 0, st, free_cells, count, W, stride, selected, selected_count);
+  return 1;
+}
+uint32_t launch_search_poses(hipStream_t st, const uint32_t* selected, uint32_t cells, uint32_t headings, const double* table, const SearchGrid& g,
+                             double4* poses, unsigned long long* ids) {
+  if (cells == 0) return 0;
+  hipLaunchKernelGGL(k_search_generate, dim3(blocks_for(static_cast<uint64_t>(cells) * headings)), dim3(kBlock), 0, st, selected, cells, headings,
+                     reinterpret_cast<const double2*>(table), g, poses, ids);
+  return 1;
+}
+uint32_t launch_search_pool(hipStream_t st, const double* scores, const unsigned long long* ids, uint64_t n, const SearchScratch& s, uint32_t pool,
+                            uint32_t pool_len, int* pool_at) {
+  if (n == 0) return 0;
+  const uint64_t tiles = (n + kSearchTile - 1) / kSearchTile;
+  uint32_t launches = 1;
+  int at = 0;
+  hipLaunchKernelGGL(k_search_sort_tiles, dim3(static_cast<unsigned>(tiles)), dim3(kSearchSortBlock), 0, st, scores, ids, n, s.run_keys[0], s.run_ids[0]);
+  const unsigned merge_blocks = blocks_for(2ull * pool);
+  uint64_t stride = kSearchTile;
+  for (uint64_t runs = tiles; runs > 1; runs = (runs + 1) / 2, stride *= 2, at ^= 1, ++launches)
+    hipLaunchKernelGGL(k_search_merge_runs, dim3(merge_blocks, static_cast<unsigned>((runs + 1) / 2)), dim3(kBlock), 0, st, s.run_keys[at], s.run_ids[at], n,
+                       stride, pool, s.run_keys[at ^ 1], s.run_ids[at ^ 1]);
+  const int from = *pool_at, to = from ^ 1;
+  hipLaunchKernelGGL(k_search_merge_pool, dim3(merge_blocks), dim3(kBlock), 0, st, s.run_keys[at], s.run_ids[at],
+                     static_cast<uint32_t>(std::min<uint64_t>(pool, n)), s.pool_keys[from], s.pool_ids[from], pool_len, pool, s.pool_keys[to], s.pool_ids[to]);
+  *pool_at = to;
+  return launches + 1;
+}
+
 }  // namespace mcl
 // Nonzero for a measurement build of the kernels (tools/build_variant.sh: ablations compute nonsense by design, timing builds
 // distort): beluga_amd/capi.py refuses to load one as the product library unless told so.

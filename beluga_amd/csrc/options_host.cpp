@@ -74,6 +74,7 @@ constexpr size_t kOptionCount = sizeof(kOptions) / sizeof(kOptions[0]);
 // (mcl_set_option) alone: it is no part of that list and has no BELUGA_MCL_* variable.
 constexpr Option kLaterOptions[] = {
     {"lf_pose_ahead", &Tuning::lf_pose_ahead, Rule::kFlag, 0, 0},
+    {"search_chunk", &Tuning::search_chunk, Rule::kClamp, 64, 1ll << 22},
 };
 
 int normalised(const Option& o, int64_t value) {

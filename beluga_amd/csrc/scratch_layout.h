@@ -258,4 +258,45 @@ struct BeamSkipLayout {
   }
 };
 
+// ---- mcl_global_search*: d_search_f64, d_search_u64, d_search_u32 and the pinned h_search, the call's own ---------------------------------
+// Sized by the chunk (`candidates` = SearchPlan::chunk_candidates, `cells` = its cells, `tiles` sort tiles of `tile` entries), never by
+// the number of candidates of the map.
+//   f64: the heading table (cos, sin per heading, rounded up to whole poses: the poses behind it are read as double4) | the chunk's
+//        poses | its scores
+//   u64: the chunk's ids | two sets of sorted runs (keys, ids: the tile sort's output and the merge levels' ping and pong) | the pool
+//        (keys, ids), twice: a merge reads one and writes the other
+//   u32: the chunk's selected cells | the count of them (one word in a granule of four)
+//   h_search (pinned, 8-byte words): the heading table to upload | the final pool's keys and ids | the count word of a chunk
+struct SearchLayout {
+  size_t table, poses, scores, f64_size;
+  size_t ids, run_keys[2], run_ids[2], pool_keys[2], pool_ids[2], u64_size;
+  size_t selected, count, u32_size;
+  size_t h_table, h_pool_keys, h_pool_ids, h_count, h_size;
+  SearchLayout(uint32_t headings, size_t cells, size_t candidates, size_t tiles, size_t tile, size_t pool_capacity) {
+    Cursor f64, u64, u32, host;
+    table = f64.take((2 * static_cast<size_t>(headings) + 3) / 4 * 4);
+    poses = f64.take(4 * candidates);
+    scores = f64.take(candidates);
+    f64_size = f64.at;
+    ids = u64.take(candidates);
+    for (int k = 0; k < 2; ++k) {
+      run_keys[k] = u64.take(tiles * tile);
+      run_ids[k] = u64.take(tiles * tile);
+    }
+    for (int k = 0; k < 2; ++k) {
+      pool_keys[k] = u64.take(pool_capacity);
+      pool_ids[k] = u64.take(pool_capacity);
+    }
+    u64_size = u64.at;
+    selected = u32.take(cells);
+    count = u32.take(4);
+    u32_size = u32.at;
+    h_table = host.take(2 * static_cast<size_t>(headings));
+    h_pool_keys = host.take(pool_capacity);
+    h_pool_ids = host.take(pool_capacity);
+    h_count = host.take(1);
+    h_size = host.at;
+  }
+};
+
 }  // namespace mcl

@@ -711,6 +711,58 @@ class Amcl {
     check(mcl_update_bearings(ctx_, control_action.data(), xyz.data(), categories.data(), categories.size(), &est, &info));
     return finish_update(est, info);
   }
+  /// Extension: the global pose search (mcl_global_search): every free cell of the map whose x and y are multiples of cell_stride,
+  /// at `headings` headings each, scored with the sensor model on the device as likelihoods() would score it; of the best `pool`
+  /// those not within separation_xy (metres) and separation_theta (radians) of a better kept one, best first, at most max_results.
+  /// The filter is untouched.  Likelihood-field and beam filters (throws on another); points in the base frame.  The separations are
+  /// handed over as round(separation_xy / the map's resolution) cells and round(separation_theta / (2 pi / headings)) heading steps;
+  /// the resolution is that of the map the filter holds (a map given by update_map_async counts from its swap on).
+  /// \throw std::invalid_argument for a separation that is negative or not finite.
+  struct SearchParams {
+    std::uint32_t cell_stride = 2, headings = 72, pool = 1024, max_results = 16;
+    double separation_xy = 0.5, separation_theta = 0.5235987755982988;  // 30 degrees
+  };
+  struct SearchHit {
+    SE2d pose;
+    double score = 0.0;
+    std::uint64_t id = 0;
+    std::uint32_t cell = 0, heading = 0;
+  };
+  [[nodiscard]] std::vector<SearchHit> global_search(const std::vector<std::pair<double, double>>& measurement, const SearchParams& search) {
+    static_assert(sizeof(std::pair<double, double>) == 2 * sizeof(double), "points are handed over as (x, y) doubles");
+    if (!(search.separation_xy >= 0.0 && std::isfinite(search.separation_xy) && search.separation_theta >= 0.0 && std::isfinite(search.separation_theta)))
+      throw std::invalid_argument("global_search: a separation is negative or not finite");
+    (void)map_pending();  // (a swap inside an update() may have changed the map, and with it the resolution)
+    const double step = search.headings ? 2.0 * 3.14159265358979323846 / search.headings : 1.0;
+    const auto steps_of = [](double separation, double unit) {  // beyond 2^32 - 1 units: everything is within reach anyway
+      return unit > 0.0 ? static_cast<std::uint32_t>(std::min(std::round(separation / unit), 4294967295.0)) : 0u;
+    };
+    const mcl_search_params p{search.cell_stride, search.headings, search.pool, search.max_results, steps_of(search.separation_xy, resolution_),
+                              steps_of(search.separation_theta, step)};
+    std::vector<mcl_search_hit> raw(std::max<std::uint32_t>(p.max_results, 1));
+    std::uint64_t count = 0;
+    check(mcl_global_search(ctx_, measurement.empty() ? nullptr : &measurement.data()->first, measurement.size(), &p, raw.data(), raw.size(), &count,
+                            &last_search_info_));
+    std::vector<SearchHit> hits(count);
+    for (std::uint64_t i = 0; i < count; ++i) {
+      hits[i].pose.c = raw[i].pose[0], hits[i].pose.s = raw[i].pose[1], hits[i].pose.x = raw[i].pose[2], hits[i].pose.y = raw[i].pose[3];
+      hits[i].score = raw[i].score, hits[i].id = raw[i].id, hits[i].cell = raw[i].cell, hits[i].heading = raw[i].heading;
+    }
+    return hits;
+  }
+  [[nodiscard]] std::vector<SearchHit> global_search(const std::vector<std::pair<double, double>>& measurement) {
+    return global_search(measurement, SearchParams{});
+  }
+  /// The counts of the last global_search (mcl_search_info).
+  [[nodiscard]] const mcl_search_info& last_search_info() const { return last_search_info_; }
+  /// global_search, then initialize(best pose, covariance): host glue.  With no hit (a map without a candidate cell) the filter is
+  /// left as it was.  Returns the hits.
+  std::vector<SearchHit> relocalize(const std::vector<std::pair<double, double>>& measurement, const SearchParams& search, const Matrix3d& covariance) {
+    std::vector<SearchHit> hits = global_search(measurement, search);
+    if (!hits.empty()) initialize(hits.front().pose, covariance);
+    return hits;
+  }
+
   /// Extension: states | views::likelihoods(sensor_model(measurement)) (views/likelihoods.hpp:44-59) on the device - for each of
   /// `states`, in their order, the factor by which a reweight with `measurement` would multiply the weight of a particle there
   /// (mcl_likelihoods).  The filter is untouched: particles, weights, random stream, policies and counters stay as they are.
@@ -1112,6 +1164,7 @@ class Amcl {
     if (st != MCL_OK) throw std::runtime_error(std::string("beluga_amd::Amcl: ") + mcl_last_error(ctx_));
   }
   mcl_ctx* ctx_{nullptr};
+  mcl_search_info last_search_info_{};
   struct PendingShape {
     std::uint32_t width{0}, height{0};
     double resolution{0.0};

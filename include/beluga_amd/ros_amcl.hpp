@@ -162,6 +162,24 @@ class Amcl {
     return filter_.likelihoods(states, measurement);
   }
 
+  /// Extension: the global pose search (beluga_amd::Amcl::global_search) over the scan types update() takes - a laser scan, a point
+  /// cloud, or points already in the base frame - projected exactly as update() projects them: the best poses of the whole map for
+  /// this measurement, the filter untouched.
+  using SearchParams = beluga_amd::Amcl::SearchParams;
+  using SearchHit = beluga_amd::Amcl::SearchHit;
+  template <class LaserScan, class = decltype(std::declval<const LaserScan&>().points_in_cartesian_coordinates())>
+  [[nodiscard]] std::vector<SearchHit> global_search(const LaserScan& laser_scan, const SearchParams& search = SearchParams()) {
+    return filter_.global_search(projected<false>(laser_scan.points_in_cartesian_coordinates(), se3_data(laser_scan.origin())), search);
+  }
+  template <class PointCloud, class = decltype(std::declval<const PointCloud&>().points()), class = void>
+  [[nodiscard]] std::vector<SearchHit> global_search(const PointCloud& point_cloud, const SearchParams& search = SearchParams()) {
+    return filter_.global_search(projected<true>(point_cloud.points(), se3_data(point_cloud.origin())), search);
+  }
+  [[nodiscard]] std::vector<SearchHit> global_search(const std::vector<std::pair<double, double>>& measurement,
+                                                     const SearchParams& search = SearchParams()) {
+    return filter_.global_search(measurement, search);
+  }
+
   /// Extension: beam skipping with Nav2's parameters (beluga_amd::Amcl::set_beam_skip; likelihood-field sensor models only).
   void set_beam_skip(const BeamSkipParams& p) {
     filter_.set_beam_skip(p.do_beamskip, p.beam_skip_distance, p.beam_skip_threshold, p.beam_skip_error_threshold);
@@ -211,6 +229,10 @@ class Amcl {
   template <bool kFloatPoints, class Points>
   auto update_projected(const SE2d& base_pose_in_odom, Points&& points, const std::array<double, 7>& origin)
       -> std::optional<estimation_type> {
+    return filter_.update(base_pose_in_odom, projected<kFloatPoints>(points, origin));
+  }
+  template <bool kFloatPoints, class Points>
+  static std::vector<std::pair<double, double>> projected(Points&& points, const std::array<double, 7>& origin) {
     std::vector<std::pair<double, double>> measurement;
     if constexpr (kFloatPoints) {
       std::vector<float> xyz;
@@ -234,7 +256,7 @@ class Amcl {
         measurement.emplace_back((px + qw * ux + (qy * uz - qz * uy)) + origin[4], (py + qw * uy + (qz * ux - qx * uz)) + origin[5]);
       }
     }
-    return filter_.update(base_pose_in_odom, measurement);
+    return measurement;
   }
 
   OccupancyGrid map_;

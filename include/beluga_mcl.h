@@ -445,6 +445,77 @@ mcl_status mcl_likelihoods_bearings(mcl_ctx* ctx, const double* poses, uint64_t 
  * the host: a pose that is not finite scores whatever the arithmetic gives. */
 mcl_status mcl_likelihoods_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* points_xy, uint64_t num_points, double* d_out);
 
+/* ---- Global pose search: score every free cell and heading with the sensor model, keep the best -------------------------------------
+ * Localising without an initial guess (a kidnapped robot, a start without a pose, "is there a better place than where the filter
+ * sits"): the candidates are made on the device, scored there by mcl_likelihoods' kernels, and only the winners come back.  Contexts of
+ * a grid sensor model (likelihood field, likelihood-field prob, beam) with a map.  tests/search_reference.py restates all of this.
+ *
+ * Candidate cells: the map's free cells (those mcl_initialize_from_map draws from) whose x % cell_stride == 0 && y % cell_stride == 0.
+ * Headings: theta_h = -pi + h * (2 pi / headings), h < headings <= 4096; the rotation (cos, sin) of each heading is computed once per
+ *   call on the host and uploaded as a table: every candidate of heading h carries the same bits.
+ * Position: the centre of the cell in the world, by the expressions the random states of mcl_initialize_from_map use:
+ *   (x + 0.5) * resolution, rotated by the origin, + the origin.
+ * Candidate id: linear_cell_index * headings + h.  Every order and every tie below is decided by the id: the result does not depend on
+ *   the chunking (option search_chunk), on the order of the compaction or on the launch geometry.
+ * Score: score(id) is what mcl_likelihoods returns for that pose and that measurement, bit for bit (the same kernels, the same order
+ *   of the sum over the scan).  The measurement's checks and staging are mcl_likelihoods' own: at most 4096 points on a beam context,
+ *   a point that is not finite has no cell for any pose.
+ * Pool: the `pool` (1 .. 4096) candidates that come first by (score descending, id ascending).  A NaN score cannot arise from finite
+ *   poses; it is defined as the lowest, so that the order is total.
+ * Suppression: greedy, in pool order, on the host.  A candidate is kept unless an already kept one lies within separation_cells of it
+ *   AND within separation_headings of it: dx*dx + dy*dy <= separation_cells * separation_cells in integer cell coordinates, and
+ *   min(|dh|, headings - |dh|) <= separation_headings.  Integers only, so the rule is exact.  With both separations 0 only a candidate
+ *   identical to a kept one would be dropped, which cannot happen: nothing is dropped.  It stops after max_results (1 .. pool) kept.
+ *
+ * The filter is untouched, by mcl_likelihoods' own contract: the call has buffers of its own, runs on the context's stream and reads the
+ * map the filter holds through the views the reweight reads, as they are now - a shared map (mcl_use_shared_map) as well; a map given
+ * by mcl_set_map_async counts from its swap on.  Allowed between the updates of a batch on its members, and on a sharded context on
+ * each rank by itself (the map is whole on every rank: no collective).
+ *
+ * Device memory is bounded by the chunk (option search_chunk: 64 .. 2^22 candidates, default 2^20), not by the number of candidates.
+ * At most one host synchronisation per chunk, and one at the end.
+ *
+ * Checks, all before the device is used; on any error no output is written: MCL_ERR_UNSUPPORTED on NDT, landmark and bearing contexts,
+ * MCL_ERR_NOT_READY without a map, MCL_ERR_INVALID_ARGUMENT for a null argument, cell_stride == 0, headings or pool outside 1 .. 4096,
+ * max_results outside 1 .. pool, capacity < max_results (mcl_global_search_pool: < pool), and whatever mcl_likelihoods refuses of the
+ * measurement.  A map with no candidate cell is MCL_OK with count == 0. */
+typedef struct mcl_search_params {
+  uint32_t cell_stride, headings, pool, max_results, separation_cells, separation_headings;
+} mcl_search_params;
+typedef struct mcl_search_hit {
+  double pose[4]; /* cos, sin, x, y: mcl_set_particles' layout */
+  double score;
+  uint64_t id;
+  uint32_t cell, heading; /* id = cell * headings + heading; cell = y * width + x */
+} mcl_search_hit;
+typedef struct mcl_search_info {
+  uint64_t cells;       /* candidate cells */
+  uint64_t candidates;  /* cells * headings */
+  uint64_t pool_filled; /* min(pool, candidates) */
+  uint32_t chunks;      /* ranges of the free-cell list the call went through: ceil(free cells / max(1, search_chunk / headings)) */
+  uint32_t launches;    /* kernel launches of the call: its own kernels, and one per chunk for the scoring (a chunk's candidates are one
+                           launch of mcl_likelihoods_device's kernel); copies and fills of the stream are not counted */
+} mcl_search_info;
+/* cell_stride 2, headings 72 (5 degrees), pool 1024, max_results 16, separation_cells 10, separation_headings 6 (30 degrees): choices
+ * of a reasonable start, not measurements. */
+void mcl_default_search_params(mcl_search_params* params);
+/* The hits that survive the suppression, best first; params NULL: the defaults; info may be NULL. */
+mcl_status mcl_global_search(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, const mcl_search_params* params, mcl_search_hit* hits,
+                             uint64_t capacity, uint64_t* count, mcl_search_info* info);
+/* The pool before the suppression, in pool order (capacity >= pool). */
+mcl_status mcl_global_search_pool(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, const mcl_search_params* params, mcl_search_hit* hits,
+                                  uint64_t capacity, uint64_t* count, mcl_search_info* info);
+/* The candidates themselves, as the device makes them, in id order: those of rank first_id_rank .. first_id_rank + count - 1 (fewer
+ * where the list ends) into ids_out and poses_out (4 doubles each; host memory; either may be NULL with count == 0); *total = the
+ * number of candidates.  Only cell_stride and headings of the parameters matter, all are checked. */
+mcl_status mcl_global_search_candidates(mcl_ctx* ctx, const mcl_search_params* params, uint64_t first_id_rank, uint64_t count, uint64_t* ids_out,
+                                        double* poses_out, uint64_t* total);
+/* The suppression alone, on the host: needs no device and no context.  pool: n hits in pool order (cell and heading are read),
+ * grid_width: the map's width in cells; kept_index (room for max_results): the pool indices of the kept hits, *kept their number.
+ * MCL_ERR_INVALID_ARGUMENT: a null argument, grid_width == 0, parameters mcl_global_search refuses, a heading >= headings. */
+mcl_status mcl_search_suppress(const mcl_search_hit* pool, uint64_t n, uint32_t grid_width, const mcl_search_params* params, uint32_t* kept_index,
+                               uint64_t* kept);
+
 /* ---- Beam skipping (Nav2 AMCL's do_beamskip) for the likelihood-field models ----------------------------------------------------
  * A beam that hits something the map does not know - a person, a pallet, an open door - pulls the weight of EVERY particle down
  * together and flattens the posterior.  With beam skipping the cloud votes on each beam before the reweight: beams that too few
