@@ -889,6 +889,84 @@ class Amcl:
             self.sync()
         return out
 
+    # -- ray casting as a function: the range the map predicts along a bearing from a pose (mcl_cast_rays*) ---------------------------
+    @staticmethod
+    def _cast_bearings(bearings, angles, points):
+        """The (B, 2) table of (c, s) from exactly one of: bearings as they are; angles by numpy's cos and sin; scan points as
+        (px / z, py / z) with z = sqrt(px * px + py * py), the beam model's own expressions, one rounding each."""
+        if sum(v is not None for v in (bearings, angles, points)) != 1:
+            raise ValueError("cast_rays: give exactly one of bearings, angles, points")
+        if bearings is not None:
+            return _f64_rows("bearings", bearings, 2)
+        if angles is not None:
+            a = np.asarray(angles, dtype=np.float64).reshape(-1)
+            return np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], axis=1))
+        p = _f64_rows("points", points, 2)
+        z = np.sqrt(p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1])
+        with np.errstate(invalid="ignore", divide="ignore"):  # (a point of range 0 gives a NaN, which the library refuses)
+            return np.ascontiguousarray(np.stack([p[:, 0] / z, p[:, 1] / z], axis=1))
+
+    def cast_rays(self, poses, bearings=None, angles=None, points=None, max_range=None, hit_cells: bool = False, cells_visited: bool = False):
+        """Ray2d::cast from each of `poses` - float64 (n, 4) as (cos, sin, x, y) - along each bearing: the ranges the map predicts,
+        float64 (n, B); with hit_cells also the linear index y * width + x of each hit cell (int64 (n, B), -1 without a hit); with
+        cells_visited also the cells the walks looked at, an int.  Returned alone or as a tuple in that order.  Give exactly one of
+        bearings ((B, 2) unit vectors (c, s), used as they are), angles ((B,) radians in the pose's frame) and points ((B, 2) scan
+        points: their bearings as the beam model forms them).  max_range: metres; default: the beam model's beam_max_range on a beam
+        filter.  The filter is untouched.  Likelihood-field and beam filters."""
+        p = _f64_rows("poses", poses, 4)
+        table = self._cast_bearings(bearings, angles, points)
+        if max_range is None:
+            if self._cfg.sensor_kind != capi.MCL_SENSOR_BEAM:
+                raise ValueError("cast_rays: max_range is needed (only a beam filter has one of its own)")
+            max_range = self._cfg.beam.beam_max_range
+        n, B = len(p), len(table)
+        ranges = np.empty((n, B), dtype=np.float64)
+        hits = np.empty((n, B), dtype=np.int64) if hit_cells else None
+        visited = C.c_uint64(0)
+        self._check(self._lib.mcl_cast_rays(self._ctx, _dp(p), n, _dp(table), B, float(max_range), _dp(ranges),
+                                            hits.ctypes.data_as(capi.c_i64_p) if hit_cells else None, C.byref(visited) if cells_visited else None))
+        result = (ranges,) + ((hits,) if hit_cells else ()) + ((int(visited.value),) if cells_visited else ())
+        return result[0] if len(result) == 1 else result
+
+    def expected_scan(self, pose_xytheta, angles, max_range=None) -> np.ndarray:
+        """The scan the map predicts at (x, y, theta): the range along each of `angles` (radians in the robot's frame), float64 (B,)."""
+        x, y, theta = (float(v) for v in pose_xytheta)
+        pose = np.array([[math.cos(theta), math.sin(theta), x, y]], dtype=np.float64)
+        return self.cast_rays(pose, angles=angles, max_range=max_range)[0]
+
+    def cast_rays_device(self, poses, bearings=None, angles=None, points=None, max_range=None, hit_cells: bool = False,
+                         cells_visited: bool = False, synchronize: bool = True):
+        """cast_rays() over a torch tensor of poses already on the filter's device (float64 (n, 4), contiguous): the ranges, and with
+        hit_cells the hit cells, come back as torch tensors on that device.  The bearings stay host memory.  The waits are
+        likelihoods_device's: the host waits for torch's current stream first and, with synchronize (the default) or cells_visited,
+        for the filter's stream before the return; with synchronize=False call sync() before reading the outputs."""
+        import torch
+
+        if not isinstance(poses, torch.Tensor) or not poses.is_cuda:
+            raise TypeError("poses: expected a torch tensor on the filter's device")
+        if poses.device.index != self._cfg.device_id:
+            raise ValueError(f"poses: on device {poses.device.index}, the filter is on device {self._cfg.device_id}")
+        if poses.dtype != torch.float64:
+            raise TypeError(f"poses: expected float64, got {poses.dtype}")
+        if poses.dim() != 2 or poses.shape[1] != 4 or not poses.is_contiguous():
+            raise ValueError(f"poses: expected a contiguous tensor of shape (n, 4), got {tuple(poses.shape)}")
+        table = self._cast_bearings(bearings, angles, points)
+        if max_range is None:
+            if self._cfg.sensor_kind != capi.MCL_SENSOR_BEAM:
+                raise ValueError("cast_rays_device: max_range is needed (only a beam filter has one of its own)")
+            max_range = self._cfg.beam.beam_max_range
+        n, B = poses.shape[0], len(table)
+        ranges = torch.empty((n, B), dtype=torch.float64, device=poses.device)
+        hits = torch.empty((n, B), dtype=torch.int64, device=poses.device) if hit_cells else None
+        visited = C.c_uint64(0)
+        torch.cuda.current_stream(poses.device).synchronize()
+        self._check(self._lib.mcl_cast_rays_device(self._ctx, poses.data_ptr(), n, _dp(table), B, float(max_range), ranges.data_ptr(),
+                                                   hits.data_ptr() if hit_cells else None, C.byref(visited) if cells_visited else None))
+        if synchronize:
+            self.sync()
+        result = (ranges,) + ((hits,) if hit_cells else ()) + ((int(visited.value),) if cells_visited else ())
+        return result[0] if len(result) == 1 else result
+
     # -- global pose search: every free cell and heading scored by the sensor model, the best kept (mcl_global_search*) ------------
     def _search_params(self, cell_stride, headings, pool, max_results, separation_xy, separation_theta):
         """The facade's metres and radians as cells and heading steps, by round()."""

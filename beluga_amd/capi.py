@@ -38,6 +38,7 @@ c_float_p = C.POINTER(C.c_float)
 c_i8_p = C.POINTER(C.c_int8)
 c_u64_p = C.POINTER(C.c_uint64)
 c_u32_p = C.POINTER(C.c_uint32)
+c_i64_p = C.POINTER(C.c_int64)
 
 
 class AmclParams(C.Structure):
@@ -196,6 +197,8 @@ _SIGNATURES = {
                                            C.POINTER(SearchInfo)]),
     "mcl_global_search_candidates": (C.c_int32, [_ctx, C.POINTER(SearchParams), C.c_uint64, C.c_uint64, c_u64_p, c_double_p, c_u64_p]),
     "mcl_search_suppress": (C.c_int32, [C.POINTER(SearchHit), C.c_uint64, C.c_uint32, C.POINTER(SearchParams), c_u32_p, c_u64_p]),
+    "mcl_cast_rays": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, C.c_uint64, C.c_double, c_double_p, c_i64_p, c_u64_p]),
+    "mcl_cast_rays_device": (C.c_int32, [_ctx, C.c_void_p, C.c_uint64, c_double_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, c_u64_p]),
     "mcl_default_beam_skip_params": (None, [C.POINTER(BeamSkipParams)]),
     "mcl_set_beam_skip": (C.c_int32, [_ctx, C.POINTER(BeamSkipParams)]),
     "mcl_get_beam_skip": (C.c_int32, [_ctx, C.POINTER(BeamSkipParams)]),

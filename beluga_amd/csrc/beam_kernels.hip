@@ -1026,6 +1026,112 @@ __global__ __launch_bounds__(kBlock) void k_block_distances(const uint32_t* __re
                                : static_cast<uint8_t>(kDistCap);
 }
 
+// ---- ray casting as a function (mcl_cast_rays*; DESIGN.md "Ray casting as a function") -------------------------------------------------
+// The bearings (c, s) of the call become the far-end vectors (c * max_range, s * max_range) of raycasting.hpp:78-88, in place, once per
+// call: the products beam_point forms per beam.
+__global__ __launch_bounds__(kBlock) void k_cast_far_ends(double2* __restrict__ table, uint64_t B, double max_range) {
+  const uint64_t b = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (b >= B) return;
+  const double2 v = table[b];
+  table[b] = double2{v.x * max_range, v.y * max_range};
+}
+
+// cast_ray with the hit cell instead of the range (walk_result<true>): the plain walk over the int8 cells, for a map without bit maps.
+__device__ __forceinline__ long long cast_ray_cell(const GridView& g, int sx, int sy, int fx, int fy, double max_range, unsigned long long& steps) {
+  RayWalk r = walk_begin(g, sx, sy, fx, fy);
+  const bool hit = walk_until(r, r.last, [&g](int x, int y) {
+    return g.cells[static_cast<size_t>(y) * g.W + static_cast<size_t>(x)] != g.free_value;
+  });
+  return walk_result<true>(g, r, hit, max_range, steps);
+}
+
+// A lane per ray over the flattened order i * B + b: the lanes of a wave are neighbouring bearings of one pose (or of a few, for a short
+// table), the three outputs are stored coalesced.  The launch covers `count` rays from bearing `first_bearing` of pose poses[0] on;
+// ranges and hit_cells point at the launch's first ray.  A workgroup finds the pose and bearing of its first ray with one division of
+// uniform operands; a lane gets its own from there with a compare (B >= kBlock: the workgroup crosses at most one pose boundary) or a
+// 32-bit division of a number below 2 kBlock.  A table shorter than the workgroup is staged in LDS - every entry is read kBlock / B
+// times -; a longer one is read once per ray, coalesced, from memory.
+// Out of reach, decided on doubles before anything becomes an int: a source cell at or beyond 2^30 in magnitude, or a line that spans 2^27
+// cells or more along an axis (only a bearing or a rotation that is no unit vector gets there: the host refuses max_range / resolution
+// from 2^27 - 2 on) - no hit, no cell visited.  Everything the walks then compute fits an int, and they read cells inside the grid alone.
+constexpr double kCastSourceCells = 1073741824.0;  // 2^30
+constexpr double kCastSpanCells = 134217728.0;     // 2^27: 16 * span stays an int (walk_blocks)
+template <bool kBits>
+__global__ __launch_bounds__(kBlock) void k_cast_rays(const double4* __restrict__ poses, const double2* __restrict__ far_ends, uint64_t B,
+                                                      uint64_t first_bearing, uint64_t count, GridView g, NonFreeBits bits, double max_range,
+                                                      double* __restrict__ ranges, long long* __restrict__ hit_cells,
+                                                      unsigned long long* d_steps) {
+  __shared__ double2 s_far[kBlock];
+  const bool staged = B < static_cast<uint64_t>(kBlock);  // (uniform)
+  if (staged) {
+    if (threadIdx.x < B) s_far[threadIdx.x] = far_ends[threadIdx.x];
+    __syncthreads();
+  }
+  const uint64_t block_ray = static_cast<uint64_t>(blockIdx.x) * kBlock;
+  const uint64_t from = first_bearing + block_ray;  // (uniform: the division below is the workgroup's, not a lane's)
+  const uint64_t block_pose = from / B, block_bearing = from - block_pose * B;
+  const uint64_t ray = block_ray + threadIdx.x;
+  const bool live = ray < count;
+  uint64_t i, b;
+  if (staged) {
+    const uint32_t t = static_cast<uint32_t>(block_bearing) + threadIdx.x, q = t / static_cast<uint32_t>(B);
+    i = block_pose + q;
+    b = t - q * static_cast<uint32_t>(B);
+  } else {
+    const uint64_t t = block_bearing + threadIdx.x;
+    const bool next = t >= B;
+    i = block_pose + (next ? 1u : 0u);
+    b = t - (next ? B : 0u);
+  }
+  unsigned long long steps = 0;
+  if (live) {
+    const double4 v = poses[i];
+    const double2 far = staged ? s_far[b] : far_ends[b];
+    const Pose2 src = pose_mul(g.origin_inverse, Pose2{Rot2{v.x, v.y}, v.z, v.w});
+    const double inv = 1. / g.resolution;  // cell_near's expressions, the conversion to int held back
+    const double sxd = floor(src.x * inv), syd = floor(src.y * inv);
+    double ex, ey;  // trace(): raycasting.hpp:78-88
+    rot_apply(src.r, far.x, far.y, ex, ey);
+    ex += src.x;
+    ey += src.y;
+    const double fxd = floor(ex * inv), fyd = floor(ey * inv);
+    const bool in_reach = fabs(sxd) < kCastSourceCells && fabs(syd) < kCastSourceCells && fabs(fxd - sxd) < kCastSpanCells &&
+                          fabs(fyd - syd) < kCastSpanCells;  // (false for a NaN)
+    long long hit = kNoHitCell;
+    if (in_reach) {
+      const int sx = static_cast<int>(sxd), sy = static_cast<int>(syd), fx = static_cast<int>(fxd), fy = static_cast<int>(fyd);
+      if constexpr (kBits) {
+        const BlockMaps grid_maps{bits.fine, static_cast<int>(bits.words_per_row), static_cast<int>(g.W) - 1, static_cast<int>(g.H) - 1, bits.rows,
+                                  bits.columns, static_cast<int>(bits.row_words), static_cast<int>(bits.column_words), bits.dist,
+                                  static_cast<int>(bits.dist_stride)};
+        hit = cast_ray_grid<true>(g, grid_maps, sx, sy, fx, fy, max_range, steps);
+      } else {
+        hit = cast_ray_cell(g, sx, sy, fx, fy, max_range, steps);
+      }
+    }
+    double range = max_range;
+    long long cell = -1;
+    if (hit != kNoHitCell) {
+      RayWalk at;  // walk_range reads the two cells alone
+      at.sx = static_cast<int>(sxd);
+      at.sy = static_cast<int>(syd);
+      at.x = static_cast<int>(hit >> 32);
+      at.y = static_cast<int>(static_cast<uint32_t>(hit));
+      at.k = 0;
+      at.last = 0;
+      unsigned long long unused = 0;
+      range = walk_range(g, at, true, max_range, unused);
+      cell = static_cast<long long>(at.y) * static_cast<long long>(g.W) + at.x;
+    }
+    ranges[ray] = range;
+    if (hit_cells) hit_cells[ray] = cell;
+  }
+  if (d_steps) {  // the cells looked at, summed over the wave: one vector atomic per wave (beam_wave_total)
+    for (int o = 32; o > 0; o >>= 1) steps += __shfl_down(steps, o);
+    if ((threadIdx.x & 63) == 0 && steps) atomicAdd(d_steps, steps);
+  }
+}
+
 }  // namespace
 
 NonFreeBits nonfree_layout(uint32_t W, uint32_t H, uint32_t* base) {
@@ -1128,6 +1234,28 @@ void launch_likelihoods_beam(hipStream_t st, const double4* poses, uint64_t n, G
     hipLaunchKernelGGL(k_likelihoods_beam, grid, dim3(kBlock), static_cast<size_t>(B) * sizeof(double2), st, poses + at, count, g, m, bits,
                        reinterpret_cast<const double2*>(d_points), B, out + at);
   }
+}
+
+void launch_cast_far_ends(hipStream_t st, double* table, uint64_t B, double max_range) {
+  for (uint64_t at = 0; at < B; at += kCastLaunchRays) {  // (a grid dimension holds 2^31 - 1 blocks)
+    const uint64_t count = std::min<uint64_t>(kCastLaunchRays, B - at);
+    hipLaunchKernelGGL(k_cast_far_ends, dim3(static_cast<unsigned>((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, st,
+                       reinterpret_cast<double2*>(table) + at, count, max_range);
+  }
+}
+static_assert(kCastBlock == kBlock && kCastMaxReachCells == kBeamMaxReachCells, "raycast_host.h restates k_cast_rays' workgroup and the walks' reach");
+void launch_cast_rays(hipStream_t st, const double4* poses, const double* far_ends, uint64_t B, const CastChunk& chunk, GridView g,
+                      const uint32_t* nonfree_bits, double max_range, double* ranges, int64_t* hit_cells, unsigned long long* d_steps) {
+  if (chunk.rays == 0) return;
+  const dim3 grid(static_cast<unsigned>(chunk.blocks));
+  const double2* table = reinterpret_cast<const double2*>(far_ends);
+  long long* hits = reinterpret_cast<long long*>(hit_cells);
+  if (nonfree_bits)
+    hipLaunchKernelGGL(k_cast_rays<true>, grid, dim3(kBlock), 0, st, poses, table, B, chunk.first_bearing, chunk.rays, g,
+                       nonfree_layout(g.W, g.H, const_cast<uint32_t*>(nonfree_bits)), max_range, ranges, hits, d_steps);
+  else
+    hipLaunchKernelGGL(k_cast_rays<false>, grid, dim3(kBlock), 0, st, poses, table, B, chunk.first_bearing, chunk.rays, g, NonFreeBits{}, max_range,
+                       ranges, hits, d_steps);
 }
 
 BatchBeam batch_beam_record(GridView g, BeamModel m, const uint32_t* nonfree_bits, unsigned long long* d_steps) {

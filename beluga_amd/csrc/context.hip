@@ -327,6 +327,14 @@ struct mcl_ctx {
   DeviceBuffer<uint32_t> d_search_u32;
   HostBuffer<unsigned long long> h_search;
 
+  // mcl_cast_rays*: the call's own buffers (RayCastLayout, scratch_layout.h) - the bearing table, the cell count, a chunk's poses and
+  // outputs - and the pinned staging of the bearings.  cast_event, made on the first call, stands behind the copy of the staged
+  // bearings: the next call waits for it before it writes the staging memory again.
+  DeviceBuffer<double> d_cast;
+  HostBuffer<double> h_cast;
+  hipEvent_t cast_event{nullptr};
+  bool cast_in_flight{false};
+
   // Beam skipping (mcl_set_beam_skip; likelihood-field contexts): the parameters, the last decision by the caller's points, and the
   // count's own buffers - the finite points of the scan up, their counts down (BeamSkipLayout, scratch_layout.h; every count ends in a
   // synchronisation, so nothing of it is ever in flight at the next).  Nothing is derived from the field: the count reads it as it is.
@@ -2677,6 +2685,7 @@ void mcl_destroy(mcl_ctx* ctx) {
   }
   if (ctx->points_event) (void)hipEventDestroy(ctx->points_event);
   if (ctx->likelihoods_event) (void)hipEventDestroy(ctx->likelihoods_event);
+  if (ctx->cast_event) (void)hipEventDestroy(ctx->cast_event);
   for (auto& pair : ctx->ev)
     for (auto& e : pair)
       if (e) (void)hipEventDestroy(e);
@@ -5031,6 +5040,109 @@ mcl_status mcl_global_search_candidates(mcl_ctx* ctx, const mcl_search_params* p
                                         double* poses_out, uint64_t* total) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   return search_settled(ctx, search_candidates(ctx, params, first_id_rank, count, ids_out, poses_out, total));
+}
+
+// ---- ray casting as a function: the range the map predicts along caller-given bearings from caller-given poses (Ray2d::cast) ------------
+// The host rule is raycast_host.cpp's.  Everything is checked before the device is used.  The bearings are staged in pinned memory of
+// the call's own and copied on the context's stream, made into the far-end vectors in place, and the rays are cast chunk by chunk of the
+// flattened order.  Nothing the update cycle reads is written and no counter moves.
+static mcl_status cast_check(mcl_ctx* ctx, const char* who, const double* poses, bool host_poses, uint64_t n, const double* bearings_cs,
+                             uint64_t num_bearings, double max_range, const void* ranges_out) {
+  if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": rays are cast over an occupancy grid (likelihood-field and beam contexts)");
+  if (!ctx->have_map) return fail(ctx, MCL_ERR_NOT_READY, std::string(who) + ": no map set");
+  const char* what = nullptr;
+  if (const mcl_status s = cast_check_call(poses, host_poses, poses != nullptr, n, bearings_cs, num_bearings, max_range, ctx->map->resolution,
+                                           ranges_out != nullptr, &what))
+    return fail(ctx, s, std::string(who) + ": " + what);
+  return MCL_OK;
+}
+// The call's buffers; the bearings into the table behind whatever the stream holds, the far ends from them, the cell count zeroed.
+static mcl_status cast_begin(mcl_ctx* ctx, const double* bearings_cs, uint64_t num_bearings, double max_range, const RayCastLayout& lay) {
+  if (ctx->cast_in_flight) {  // the previous call's copy may still be reading the staging memory
+    MCL_HIP(ctx, hipEventSynchronize(ctx->cast_event));
+    ctx->cast_in_flight = false;
+  }
+  if (lay.size > ctx->d_cast.count) MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier call may still be using the block)
+  MCL_HIP(ctx, ctx->d_cast.ensure(lay.size));
+  MCL_HIP(ctx, ctx->h_cast.ensure(lay.h_size, /*mapped=*/false));
+  std::copy(bearings_cs, bearings_cs + 2 * num_bearings, ctx->h_cast.host + lay.h_table);
+  if (!ctx->cast_event) MCL_HIP(ctx, hipEventCreateWithFlags(&ctx->cast_event, hipEventDisableTiming));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->d_cast.ptr + lay.table, ctx->h_cast.host + lay.h_table, 2 * num_bearings * sizeof(double), hipMemcpyHostToDevice,
+                              ctx->stream));
+  MCL_HIP(ctx, hipEventRecord(ctx->cast_event, ctx->stream));
+  ctx->cast_in_flight = true;
+  launch_cast_far_ends(ctx->stream, ctx->d_cast.ptr + lay.table, num_bearings, max_range);
+  MCL_HIP(ctx, hipMemsetAsync(ctx->d_cast.ptr + lay.count, 0, sizeof(unsigned long long), ctx->stream));
+  return MCL_OK;
+}
+// The cell count of the call so far, behind a synchronisation of the stream.
+static mcl_status cast_read_count(mcl_ctx* ctx, const RayCastLayout& lay, uint64_t* cells_visited) {
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_cast.host + lay.h_count, ctx->d_cast.ptr + lay.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  std::memcpy(cells_visited, ctx->h_cast.host + lay.h_count, sizeof(uint64_t));
+  return MCL_OK;
+}
+static mcl_status cast_rays_host(mcl_ctx* ctx, const double* poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
+                                 double* ranges_out, int64_t* hit_cells_out, uint64_t* cells_visited) {
+  const char* who = "mcl_cast_rays";
+  if (const mcl_status s = cast_check(ctx, who, poses, /*host_poses=*/true, n, bearings_cs, num_bearings, max_range, ranges_out)) return s;
+  if (n == 0 || num_bearings == 0) {
+    if (cells_visited) *cells_visited = 0;
+    return MCL_OK;
+  }
+  if (const mcl_status s = bind_device(ctx)) return s;
+  const CastPlan plan = cast_plan(n, num_bearings, static_cast<uint64_t>(ctx->tuning.cast_chunk));
+  const RayCastLayout lay(num_bearings, plan.chunk_poses, std::min(plan.chunk_rays, plan.rays), hit_cells_out != nullptr);
+  if (const mcl_status s = cast_begin(ctx, bearings_cs, num_bearings, max_range, lay)) return s;
+  double* const block = ctx->d_cast.ptr;
+  unsigned long long* const d_steps = cells_visited ? reinterpret_cast<unsigned long long*>(block + lay.count) : nullptr;
+  int64_t* const d_hits = hit_cells_out ? reinterpret_cast<int64_t*>(block + lay.hits) : nullptr;
+  for (uint64_t c = 0; c < plan.chunks; ++c) {  // poses up, rays cast, outputs down: the outputs are written by these last copies alone
+    const CastChunk chunk = cast_chunk_at(plan, num_bearings, c);
+    MCL_HIP(ctx, hipMemcpyAsync(block + lay.poses, poses + 4 * chunk.first_pose, chunk.poses * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    launch_cast_rays(ctx->stream, reinterpret_cast<const double4*>(block + lay.poses), block + lay.table, num_bearings, chunk, ctx->grid_view(),
+                     ctx->map->d_nonfree_bits.ptr, max_range, block + lay.ranges, d_hits, d_steps);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    MCL_HIP(ctx, hipMemcpy(ranges_out + chunk.first_ray, block + lay.ranges, chunk.rays * sizeof(double), hipMemcpyDeviceToHost));
+    if (d_hits) MCL_HIP(ctx, hipMemcpy(hit_cells_out + chunk.first_ray, d_hits, chunk.rays * sizeof(int64_t), hipMemcpyDeviceToHost));
+  }
+  if (cells_visited) return cast_read_count(ctx, lay, cells_visited);
+  return MCL_OK;
+}
+static mcl_status cast_rays_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
+                                   double* d_ranges_out, int64_t* d_hit_cells_out, uint64_t* cells_visited) {
+  const char* who = "mcl_cast_rays_device";
+  if (const mcl_status s = cast_check(ctx, who, d_poses, /*host_poses=*/false, n, bearings_cs, num_bearings, max_range, d_ranges_out)) return s;
+  if (n == 0 || num_bearings == 0) {
+    if (cells_visited) *cells_visited = 0;
+    return MCL_OK;
+  }
+  if (const mcl_status s = bind_device(ctx)) return s;
+  const CastPlan plan = cast_plan(n, num_bearings, kCastLaunchRays);  // (the outputs are the caller's: a chunk is what one launch holds)
+  const RayCastLayout lay(num_bearings, 0, 0, false);
+  if (const mcl_status s = cast_begin(ctx, bearings_cs, num_bearings, max_range, lay)) return s;
+  double* const block = ctx->d_cast.ptr;
+  unsigned long long* const d_steps = cells_visited ? reinterpret_cast<unsigned long long*>(block + lay.count) : nullptr;
+  for (uint64_t c = 0; c < plan.chunks; ++c) {
+    const CastChunk chunk = cast_chunk_at(plan, num_bearings, c);
+    launch_cast_rays(ctx->stream, reinterpret_cast<const double4*>(d_poses) + chunk.first_pose, block + lay.table, num_bearings, chunk, ctx->grid_view(),
+                     ctx->map->d_nonfree_bits.ptr, max_range, d_ranges_out + chunk.first_ray, d_hit_cells_out ? d_hit_cells_out + chunk.first_ray : nullptr,
+                     d_steps);
+  }
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (cells_visited) return cast_read_count(ctx, lay, cells_visited);
+  return MCL_OK;
+}
+mcl_status mcl_cast_rays(mcl_ctx* ctx, const double* poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
+                         double* ranges_out, int64_t* hit_cells_out, uint64_t* cells_visited) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  return search_settled(ctx, cast_rays_host(ctx, poses, n, bearings_cs, num_bearings, max_range, ranges_out, hit_cells_out, cells_visited));
+}
+mcl_status mcl_cast_rays_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
+                                double* d_ranges_out, int64_t* d_hit_cells_out, uint64_t* cells_visited) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  return search_settled(ctx, cast_rays_device(ctx, d_poses, n, bearings_cs, num_bearings, max_range, d_ranges_out, d_hit_cells_out, cells_visited));
 }
 
 // ---- beam skipping: the parameters, the last decision, and the count as a call of its own -------------------------------------------

@@ -137,6 +137,8 @@ struct Tuning {
                                     // the old weight is not loaded (1.0 x = x: bit-identical); 0 = always loaded
   int search_chunk = 1 << 20;       // mcl_global_search*: candidates a chunk holds (64 .. 2^22) - what bounds the call's device memory; the result
                                     // does not depend on it
+  int cast_chunk = 1 << 22;         // mcl_cast_rays: rays a chunk of the host form holds (64 .. 2^28) - what bounds the call's device memory; the
+                                    // result does not depend on it
 };
 
 // Spatial ordering of the particles (kLfSortedLanes, ordered beam kernel): the 64 lanes of a wave should hold neighbouring

@@ -17,6 +17,7 @@
 #include "scratch_layout.h"
 #include "se2.h"
 #include "search_host.h"
+#include "raycast_host.h"
 #include "sensor_records.h"
 
 namespace mcl {
@@ -255,6 +256,15 @@ void launch_likelihoods_ndt_hashed(hipStream_t st, const double4* poses, uint64_
 // k <= kLandmarkMaxDetections; k == 0: 1.0.  bearing: the records sorted by category, as launch_reweight_bearings takes them.
 void launch_likelihoods_landmarks(hipStream_t st, const double4* poses, uint64_t n, const LandmarkMapView& m, const double* detections, uint32_t k,
                                   bool bearing, double* out);
+
+// ---- ray casting as a function (mcl_cast_rays*; DESIGN.md "Ray casting as a function"; the host rule: raycast_host.h) --------------------
+// table: B bearings (c, s) in device memory, made into the far-end vectors (c * max_range, s * max_range) in place.
+void launch_cast_far_ends(hipStream_t st, double* table, uint64_t B, double max_range);
+// One chunk of the flattened order i * B + b (CastChunk): poses points at the chunk's first pose, ranges / hit_cells (may be null) at its
+// first ray; far_ends is the whole table.  nonfree_bits: the packed bit maps of a beam context's map (cast_ray_grid's walk), or null: the
+// plain walk over g.cells (cast_ray's).  *d_steps (may be null) += the cells looked at.
+void launch_cast_rays(hipStream_t st, const double4* poses, const double* far_ends, uint64_t B, const CastChunk& chunk, GridView g,
+                      const uint32_t* nonfree_bits, double max_range, double* ranges, int64_t* hit_cells, unsigned long long* d_steps);
 
 // ---- beam skipping: the cloud's vote on every beam (mcl_beam_agreement, the enabled cycle; DESIGN.md "Beam skipping") ---------------------
 // count[b] = the poses i < n whose end-point of scan point b has a cell inside the grid with f.data[cell] > level - the exact cell of

@@ -75,6 +75,7 @@ constexpr size_t kOptionCount = sizeof(kOptions) / sizeof(kOptions[0]);
 constexpr Option kLaterOptions[] = {
     {"lf_pose_ahead", &Tuning::lf_pose_ahead, Rule::kFlag, 0, 0},
     {"search_chunk", &Tuning::search_chunk, Rule::kClamp, 64, 1ll << 22},
+    {"cast_chunk", &Tuning::cast_chunk, Rule::kClamp, 64, 1ll << 28},
 };
 
 int normalised(const Option& o, int64_t value) {

@@ -299,4 +299,27 @@ struct SearchLayout {
   }
 };
 
+// ---- mcl_cast_rays*: d_cast and the pinned h_cast, the call's own 8-byte words --------------------------------------------------------------
+// d_cast: the bearing table (c, s per bearing, made into the far-end vectors in place; rounded up to whole poses: the poses behind it
+// are read as double4) | the cell count, one word in a granule of four | a chunk's poses | its ranges | its hit cells (int64).  The
+// device form takes the table and the count alone (chunk_poses = chunk_rays = 0); a call that wants no hit cells has no area for them.
+// Sized by the chunk (CastPlan, raycast_host.h) and the table, never by the number of rays.
+// h_cast: the bearings to upload | the cell count read back.
+struct RayCastLayout {
+  size_t table, count, poses, ranges, hits, size;
+  size_t h_table, h_count, h_size;
+  RayCastLayout(uint64_t num_bearings, uint64_t chunk_poses, uint64_t chunk_rays, bool hit_cells) {
+    Cursor c, host;
+    table = c.take((2 * static_cast<size_t>(num_bearings) + 3) / 4 * 4);
+    count = c.take(4);
+    poses = c.take(4 * static_cast<size_t>(chunk_poses));
+    ranges = c.take(static_cast<size_t>(chunk_rays));
+    hits = c.take(hit_cells ? static_cast<size_t>(chunk_rays) : 0);
+    size = c.at;
+    h_table = host.take(2 * static_cast<size_t>(num_bearings));
+    h_count = host.take(1);
+    h_size = host.at;
+  }
+};
+
 }  // namespace mcl

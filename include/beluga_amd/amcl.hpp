@@ -795,6 +795,20 @@ class Amcl {
                                    categories.size(), out.data()));
     return out;
   }
+  /// Extension: Ray2d::cast (algorithm/raycasting.hpp:97-107) on the device for caller-given states and bearings (mcl_cast_rays): the
+  /// range the map predicts from states[i] along bearings[b] = (cos, sin) of the beam's angle in the state's frame - unit vectors, used
+  /// as they are - at [i * bearings.size() + b]; max_range where the ray hits nothing.  hit_cells (optional): y * width + x of each
+  /// hit cell, -1 without one; cells_visited (optional): the cells the walks looked at.  The filter is untouched.  Likelihood-field
+  /// and beam filters (throws on another).
+  [[nodiscard]] std::vector<double> cast_rays(const std::vector<SE2d>& states, const std::vector<std::pair<double, double>>& bearings, double max_range,
+                                              std::vector<std::int64_t>* hit_cells = nullptr, std::uint64_t* cells_visited = nullptr) {
+    static_assert(sizeof(std::pair<double, double>) == 2 * sizeof(double), "bearings are handed over as (cos, sin) doubles");
+    std::vector<double> ranges(states.size() * bearings.size());
+    if (hit_cells) hit_cells->assign(ranges.size(), -1);
+    check(mcl_cast_rays(ctx_, states.empty() ? nullptr : states.data()->data(), states.size(), bearings.empty() ? nullptr : &bearings.data()->first,
+                        bearings.size(), max_range, ranges.data(), hit_cells ? hit_cells->data() : nullptr, cells_visited));
+    return ranges;
+  }
   /// Extension: beam skipping (mcl_set_beam_skip; Nav2 AMCL's do_beamskip, beam_skip_distance, beam_skip_threshold,
   /// beam_skip_error_threshold).  Before every reweight the cloud votes on each beam; beams that too few particles can explain are
   /// left out of that update, unless so much of the scan would go that all of it is used.  Likelihood-field sensor models only.

@@ -162,6 +162,13 @@ class Amcl {
     return filter_.likelihoods(states, measurement);
   }
 
+  /// Extension: the ranges the map predicts from caller-given states along caller-given bearings (beluga_amd::Amcl::cast_rays): an
+  /// expected scan, per-beam residuals; the filter untouched.
+  [[nodiscard]] std::vector<double> cast_rays(const std::vector<SE2d>& states, const std::vector<std::pair<double, double>>& bearings, double max_range,
+                                              std::vector<std::int64_t>* hit_cells = nullptr, std::uint64_t* cells_visited = nullptr) {
+    return filter_.cast_rays(states, bearings, max_range, hit_cells, cells_visited);
+  }
+
   /// Extension: the global pose search (beluga_amd::Amcl::global_search) over the scan types update() takes - a laser scan, a point
   /// cloud, or points already in the base frame - projected exactly as update() projects them: the best poses of the whole map for
   /// this measurement, the filter untouched.

@@ -516,6 +516,56 @@ mcl_status mcl_global_search_candidates(mcl_ctx* ctx, const mcl_search_params* p
 mcl_status mcl_search_suppress(const mcl_search_hit* pool, uint64_t n, uint32_t grid_width, const mcl_search_params* params, uint32_t* kept_index,
                                uint64_t* kept);
 
+/* ---- Ray casting as a function: the range the map predicts along a bearing from a pose (Ray2d::cast, algorithm/raycasting.hpp:97-107) ----
+ * An expected scan to draw over the measured one, per-beam residuals against a stale map or a moving obstacle, a synthetic scan for a
+ * simulated robot, a range table.  The walk is the beam model's own (the kernels mcl_reweight runs on a beam context), opened to
+ * caller-given poses and bearings.  Likelihood-field, likelihood-field-prob and beam contexts with a map.  tests/raycast_reference.py
+ * restates all of this.
+ *
+ * For pose i (cos, sin, x, y: mcl_set_particles' layout), bearing b = (c, s) of bearings_cs[2 b], [2 b + 1] - a unit vector as the caller
+ * gives it, never normalised here - and max_range:
+ *   T = origin^-1 * pose, as the beam model forms it.
+ *   source cell: floor(T.x * (1 / resolution)), floor(T.y * (1 / resolution)).
+ *   far end: T * (c * max_range, s * max_range), every product and sum rounded on its own; its cell likewise.
+ *   trace: the standard Bresenham line from the source cell to the far-end cell (bresenham.hpp:84-160).  It stops at the first cell outside
+ *     the grid (no hit), at the first cell that is not free (hit: an unknown cell is not free), or behind the far-end cell (no hit).
+ *   ranges_out[i * B + b] = fmin(the distance of the two cells' centres (xi + 0.5) * resolution, max_range); max_range without a hit.
+ *   hit_cells_out[i * B + b] = y * width + x of the hit cell, or -1.  May be NULL.
+ *   *cells_visited = the cells looked at, summed over all rays: those of a trace inside the grid, up to and including the hit.  May be NULL.
+ *   Out of reach: a ray whose source cell is at or beyond 2^30 in magnitude along an axis is no hit and visits no cell (no grid that fits
+ *     in memory has such a cell, so this is the rule above); so is a ray whose line spans 2^27 cells or more along an axis, which takes a
+ *     bearing or a pose rotation that is no unit vector.  Both are decided on the doubles, before any conversion to an integer: no input
+ *     forms an address outside a buffer.
+ * With bearings (px / z, py / z), z = sqrt(px^2 + py^2), of scan points and the model's beam_max_range, ranges_out is the expected range
+ * the beam model compares each measured range with, bit for bit.  A beam context walks its packed bit maps, a likelihood-field context
+ * the cells themselves: the three outputs are the same.
+ *
+ * THE FILTER IS UNTOUCHED, by mcl_likelihoods' own contract: the call has buffers of its own, runs on the context's stream behind
+ * whatever is in flight, writes nothing the cycle reads and moves no counter of mcl_get_counter (mcl_beam_cells_visited included: the
+ * count above is the call's own).  It reads the map the context reads NOW - a shared map as well; a map given by mcl_set_map_async counts
+ * from its swap on.  Allowed between the updates of a batch on its members, and on a sharded context on each rank by itself.
+ *
+ * n and num_bearings are limited by memory only (the 4096 points of mcl_likelihoods on a beam context do not apply).  The host form's
+ * device memory is the bearing table (16 bytes per bearing) and one chunk of rays: option cast_chunk, 64 .. 2^28 rays, default 2^22 -
+ * 16 bytes per ray and up to 32 per ray for the poses of a table shorter than a chunk.  The result does not depend on it.  The host form
+ * synchronises once per chunk.
+ *
+ * Checks, all before the device is used; on any error no output is written: MCL_ERR_UNSUPPORTED on NDT, landmark and bearing contexts;
+ * MCL_ERR_NOT_READY without a map; MCL_ERR_INVALID_ARGUMENT for a max_range that is not finite or not positive, max_range / resolution
+ * at or above 2^27 - 2 cells (the bound of mcl_reweight on a beam context), a null poses, bearings_cs or ranges_out, a pose or bearing
+ * value that is not finite; MCL_ERR_OUT_OF_MEMORY for counts no memory holds (n above 2^40, num_bearings above 2^36, n * num_bearings
+ * above 2^62).  n == 0 or num_bearings == 0 is MCL_OK and writes nothing but *cells_visited = 0 (the context and max_range are checked
+ * all the same). */
+mcl_status mcl_cast_rays(mcl_ctx* ctx, const double* poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
+                         double* ranges_out, int64_t* hit_cells_out /* NULL ok */, uint64_t* cells_visited /* NULL ok */);
+/* mcl_cast_rays with d_poses, d_ranges_out and d_hit_cells_out (NULL ok) in device memory of the context's device; bearings_cs and
+ * cells_visited stay host memory.  Enqueued on the context's stream; the call waits for the PREVIOUS call's upload of the bearings before
+ * it stages its own, and synchronises the stream only where cells_visited is given - otherwise synchronise, or order your own work behind
+ * it, before reading the outputs.  The poses are not looked at on the host: one that is not finite is out of reach.  cast_chunk does not
+ * apply (the outputs are the caller's); a launch holds 2^38 rays. */
+mcl_status mcl_cast_rays_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
+                                double* d_ranges_out, int64_t* d_hit_cells_out /* NULL ok */, uint64_t* cells_visited /* NULL ok */);
+
 /* ---- Beam skipping (Nav2 AMCL's do_beamskip) for the likelihood-field models ----------------------------------------------------
  * A beam that hits something the map does not know - a person, a pallet, an open door - pulls the weight of EVERY particle down
  * together and flattens the posterior.  With beam skipping the cloud votes on each beam before the reweight: beams that too few
