@@ -967,6 +967,41 @@ class Amcl:
         result = (ranges,) + ((hits,) if hit_cells else ()) + ((int(visited.value),) if cells_visited else ())
         return result[0] if len(result) == 1 else result
 
+    # -- range table for the beam model: the expected range as one look-up per beam in place of a walk (mcl_build_range_table) -------------
+    def build_range_table(self, num_angles: int = 360):
+        """Build the table of the current map - per cell and heading bin of `num_angles`, the squared cell distance to the cell the exact
+        cast from the cell's centre hits - and switch update(), reweight() and likelihoods() over to it from the next reweight on.  An
+        approximation (the source's position inside its cell and the heading within a bin are discarded), hence opt-in.  Whatever installs
+        a map afterwards rebuilds the table.  width * height * num_angles * 4 bytes; refused above option range_table_max_bytes.  Beam
+        filters only.  cast_rays() and global_search() stay exact."""
+        self._check(self._lib.mcl_build_range_table(self._ctx, int(num_angles)))
+
+    def drop_range_table(self):
+        """Back to the exact walk; the table's memory is freed."""
+        self._check(self._lib.mcl_drop_range_table(self._ctx))
+
+    def range_table_info(self) -> dict:
+        """built, num_angles, width, height, bytes, builds (tables built, rebuilds included), lut_launches (reweights that read a table)."""
+        info = capi.RangeTableInfo()
+        self._check(self._lib.mcl_range_table_get_info(self._ctx, C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in capi.RangeTableInfo._fields_}
+
+    def range_table_bearings(self) -> np.ndarray:
+        """The bins' bearings (cos, sin) the table was built with, float64 (A, 2)."""
+        out = np.empty((self.range_table_info()["num_angles"], 2), dtype=np.float64)
+        self._check(self._lib.mcl_range_table_bearings(self._ctx, _dp(out)))
+        return out
+
+    def range_table(self, first_cell: int = 0, num_cells: Optional[int] = None) -> np.ndarray:
+        """The table as uint32: the whole of it as (H, W, A) - for small maps: it is copied to the host - or, with first_cell / num_cells,
+        the rows of those cells (cell = y * W + x) as (num_cells, A).  0xFFFFFFFF: no hit."""
+        info = self.range_table_info()
+        whole = first_cell == 0 and num_cells is None
+        count = info["width"] * info["height"] - first_cell if num_cells is None else int(num_cells)
+        out = np.empty((max(count, 0), info["num_angles"]), dtype=np.uint32)
+        self._check(self._lib.mcl_range_table_read(self._ctx, int(first_cell), count, out.ctypes.data_as(capi.c_u32_p)))
+        return out.reshape(info["height"], info["width"], info["num_angles"]) if whole else out
+
     # -- global pose search: every free cell and heading scored by the sensor model, the best kept (mcl_global_search*) ------------
     def _search_params(self, cell_stride, headings, pool, max_results, separation_xy, separation_theta):
         """The facade's metres and radians as cells and heading steps, by round()."""

@@ -155,6 +155,11 @@ class SearchInfo(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("candidates", C.c_uint64), ("pool_filled", C.c_uint64), ("chunks", C.c_uint32), ("launches", C.c_uint32)]
 
 
+class RangeTableInfo(C.Structure):
+    _fields_ = [("built", C.c_int32), ("num_angles", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("bytes", C.c_uint64),
+                ("builds", C.c_uint64), ("lut_launches", C.c_uint64)]
+
+
 class SharedMapInfo(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("resolution", C.c_double), ("sensor_kind", C.c_int32),
                 ("device_id", C.c_int32), ("device_bytes", C.c_uint64), ("host_bytes", C.c_uint64), ("users", C.c_uint32)]
@@ -199,6 +204,11 @@ _SIGNATURES = {
     "mcl_search_suppress": (C.c_int32, [C.POINTER(SearchHit), C.c_uint64, C.c_uint32, C.POINTER(SearchParams), c_u32_p, c_u64_p]),
     "mcl_cast_rays": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, C.c_uint64, C.c_double, c_double_p, c_i64_p, c_u64_p]),
     "mcl_cast_rays_device": (C.c_int32, [_ctx, C.c_void_p, C.c_uint64, c_double_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, c_u64_p]),
+    "mcl_build_range_table": (C.c_int32, [_ctx, C.c_uint32]),
+    "mcl_drop_range_table": (C.c_int32, [_ctx]),
+    "mcl_range_table_get_info": (C.c_int32, [_ctx, C.POINTER(RangeTableInfo)]),
+    "mcl_range_table_bearings": (C.c_int32, [_ctx, c_double_p]),
+    "mcl_range_table_read": (C.c_int32, [_ctx, C.c_uint64, C.c_uint64, c_u32_p]),
     "mcl_default_beam_skip_params": (None, [C.POINTER(BeamSkipParams)]),
     "mcl_set_beam_skip": (C.c_int32, [_ctx, C.POINTER(BeamSkipParams)]),
     "mcl_get_beam_skip": (C.c_int32, [_ctx, C.POINTER(BeamSkipParams)]),
@@ -294,7 +304,9 @@ _OPTIONAL = {"mcl_measurement_build", "mcl_set_ndt_small_cycle", "mcl_get_ndt_sm
              "mcl_ndt_batch_counts", "mcl_set_landmark_small_cycle", "mcl_get_landmark_small_cycle", "mcl_landmark_batch_update",
              "mcl_set_ndt_map_layout", "mcl_get_ndt_map_layout",
              # (tools/exp_beam_skip.py measures against a build of the commit before beam skipping)
-             "mcl_default_beam_skip_params", "mcl_set_beam_skip", "mcl_get_beam_skip", "mcl_get_beam_skip_result", "mcl_beam_agreement"}
+             "mcl_default_beam_skip_params", "mcl_set_beam_skip", "mcl_get_beam_skip", "mcl_get_beam_skip_result", "mcl_beam_agreement",
+             # (tools/exp_range_table.py measures against a build of the commit before the range table)
+             "mcl_build_range_table", "mcl_drop_range_table", "mcl_range_table_get_info", "mcl_range_table_bearings", "mcl_range_table_read"}
 _lib = None
 
 

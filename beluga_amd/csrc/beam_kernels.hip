@@ -1132,6 +1132,136 @@ __global__ __launch_bounds__(kBlock) void k_cast_rays(const double4* __restrict_
   }
 }
 
+// ---- the range table of the beam model (mcl_build_range_table; DESIGN.md "Range table for the beam model") ------------------------------
+// table[(y * W + x) * A + k] = the squared cell distance between cell (x, y) and the cell the exact rule's cast from it hits along the
+// bearing of bin k - from the cell's centre, in the grid frame, over beam_max_range - or kRangeTableNoHit.  What it discards of the exact
+// rule: where in its cell the source stands, and the heading within a bin.
+// A lane per entry over the flattened index cell * A + k, as k_cast_rays runs over i * B + b: neighbouring lanes are neighbouring bins of
+// one cell, the stores are coalesced.  The launch covers `count` entries from `first_entry` on.  A workgroup finds the cell and bin of its
+// first entry with one 64-bit division of uniform operands; a lane gets its own with a 32-bit division of a number below A + kBlock, and
+// its cell's column and row with another (a grid has fewer than 2^32 cells).  The walk is cast_ray_grid<true>'s over the packed bit maps
+// (kBits) or cast_ray_cell's over the int8 cells; the cells it visits are not counted anywhere.
+template <bool kBits>
+__global__ __launch_bounds__(kBlock) void k_build_range_table(GridView g, NonFreeBits bits, const double2* __restrict__ bearings, uint32_t A,
+                                                              uint64_t first_entry, uint64_t count, double max_range,
+                                                              uint32_t* __restrict__ table) {
+  const uint64_t block_entry = static_cast<uint64_t>(blockIdx.x) * kBlock;
+  const uint64_t from = first_entry + block_entry;  // (uniform: the division below is the workgroup's, not a lane's)
+  const uint64_t block_cell = from / A;
+  const uint32_t block_bin = static_cast<uint32_t>(from - block_cell * A);
+  const uint64_t entry = block_entry + threadIdx.x;
+  if (entry >= count) return;
+  const uint32_t t = block_bin + threadIdx.x, q = t / A, k = t - q * A;
+  const uint32_t cell = static_cast<uint32_t>(block_cell) + q;
+  const uint32_t y = cell / g.W, x = cell - y * g.W;
+  const double2 cs = bearings[k];
+  // the far end from the cell's centre, every product and sum rounded on its own; its cell by cell_near's expressions
+  const double ex = (static_cast<double>(x) + 0.5) * g.resolution + cs.x * max_range;
+  const double ey = (static_cast<double>(y) + 0.5) * g.resolution + cs.y * max_range;
+  const int sx = static_cast<int>(x), sy = static_cast<int>(y);
+  int fx, fy;
+  cell_near(g, ex, ey, fx, fy);  // (within 2^27 cells of the source: the host has bounded max_range / resolution)
+  unsigned long long steps = 0;
+  long long hit;
+  if constexpr (kBits) {
+    const BlockMaps grid_maps{bits.fine, static_cast<int>(bits.words_per_row), static_cast<int>(g.W) - 1, static_cast<int>(g.H) - 1, bits.rows,
+                              bits.columns, static_cast<int>(bits.row_words), static_cast<int>(bits.column_words), bits.dist,
+                              static_cast<int>(bits.dist_stride)};
+    hit = cast_ray_grid<true>(g, grid_maps, sx, sy, fx, fy, max_range, steps);
+  } else {
+    hit = cast_ray_cell(g, sx, sy, fx, fy, max_range, steps);
+  }
+  uint32_t r2 = kRangeTableNoHit;
+  if (hit != kNoHitCell) {
+    const long long cx = (hit >> 32) - sx, cy = static_cast<long long>(static_cast<int>(static_cast<uint32_t>(hit))) - sy;
+    const unsigned long long d2 = static_cast<unsigned long long>(cx * cx + cy * cy);
+    r2 = d2 < kRangeTableFarthest ? static_cast<uint32_t>(d2) : kRangeTableFarthest;
+  }
+  table[first_entry + entry] = r2;
+}
+
+// What the table reweight reads of a scan point (the same for every particle): BeamPoint's range terms and the point's angle in the
+// sensor frame, beta = atan2(py, px) - one entry per beam, made once per scan.
+__global__ __launch_bounds__(kBlock) void k_beam_lut_points(const double* __restrict__ pts, uint32_t B, BeamModel m, double4* __restrict__ out) {
+  const uint32_t b = blockIdx.x * kBlock + threadIdx.x;
+  if (b >= B) return;
+  const double px = pts[2 * b], py = pts[2 * b + 1];
+  const BeamPoint q = beam_point(m, px, py);
+  out[b] = double4{q.z, q.short_e, q.tail, atan2(py, px)};
+}
+
+// The beam model over the range table: a wave per particle, a lane per beam, the per-beam entries staged in LDS (s_pts).  Per particle:
+// src = origin^-1 * pose and its cell as beam_wave_total forms them, theta = atan2(src.r.s, src.r.c) - once per wave -, and the row of
+// the source cell, (sy * W + sx) * A, formed once in 64 bits.  Per beam: u = (theta + beta) * (A / (2 pi)), k = floor(u + 0.5) brought
+// into [0, A) by integer arithmetic on the 64-bit value (|u| <= A: two additions or subtractions of A at the most), and the entry at the
+// 32-bit offset k of the row - "no hit" for a source cell outside the grid, which is exact: the walk's first cell is outside.  From the
+// entry on the term is beam_term<true>'s table arm without the 1e-9 tie re-derivation (the table knows no hit cell): the expected range
+// is fmin(sqrt(r2) * resolution, max_range).  Without a BeamTable (a reach beyond kBeamTableMaxCells) the lane evaluates
+// beam_table_entry itself: the same function, the same bits.  No cell is walked and none is counted.
+// A k that is not in [0, A) - a pose that is not finite - reads nothing and counts as no hit: no input forms an address outside the table.
+__device__ __forceinline__ double beam_lut_wave_total(uint32_t lane, const Pose2& pose, const GridView& g, const BeamModel& m,
+                                                      const RangeTableView& t, const BeamTable& terms, const double4* s_pts, uint32_t B) {
+  const Pose2 src = pose_mul(g.origin_inverse, pose);
+  int sx, sy;
+  cell_near(g, src.x, src.y, sx, sy);
+  const double theta = atan2(src.r.s, src.r.c);
+  const double norm_hit = 1. / (sqrt(2. * kPi) * m.sigma_hit);
+  const bool inside = sx >= 0 && sy >= 0 && static_cast<uint32_t>(sx) < g.W && static_cast<uint32_t>(sy) < g.H;
+  const uint32_t* row = t.entries + (inside ? (static_cast<uint64_t>(sy) * g.W + static_cast<uint64_t>(sx)) * t.A : 0ull);
+  const double bins_per_radian = static_cast<double>(t.A) / (2. * kPi);
+  const long long A = static_cast<long long>(t.A);
+  double acc = 0.0;
+  for (uint32_t b = lane; b < B; b += kWave) {
+    const double4 q = s_pts[b];  // (z, short_e, tail, beta)
+    const double u = (theta + q.w) * bins_per_radian;
+    long long k = static_cast<long long>(floor(u + 0.5));
+    k += k < 0 ? A : 0;
+    k += k < 0 ? A : 0;
+    k -= k >= A ? A : 0;
+    k -= k >= A ? A : 0;
+    uint32_t r2 = kRangeTableNoHit;
+    if (inside && k >= 0 && k < A) r2 = row[static_cast<uint32_t>(k)];
+    double4 e;
+    if (terms.entries) e = terms.entries[r2 < terms.no_hit ? r2 : terms.no_hit];
+    else e = beam_table_entry(m, g.resolution, norm_hit, r2, r2 == kRangeTableNoHit);
+    const double z_mean = e.x;
+    const double d = (q.x - z_mean) / m.sigma_hit;
+    double pz = e.y * exp(-(d * d) / 2.);
+    if (q.x < z_mean) pz += e.z * q.y;
+    pz += q.z;
+    acc += pz * pz * pz;
+  }
+  return wave_sum_f64(acc);
+}
+constexpr int kLutBlock = 512;  // eight particles share one staging of the scan; 32 B a beam: four workgroups a CU up to 1280 beams
+__global__ __launch_bounds__(kLutBlock) void k_reweight_beam_lut(Particles p, uint64_t n, GridView g, BeamModel m, RangeTableView t, BeamTable terms,
+                                                                 const double4* __restrict__ pts, uint32_t B) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double4* s_pts = reinterpret_cast<double4*>(smem);
+  for (uint32_t i = threadIdx.x; i < B; i += kLutBlock) s_pts[i] = pts[i];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * (kLutBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const double total = beam_lut_wave_total(lane, load_pose(p, i), g, m, t, terms, s_pts, B);
+  if (lane == 0) p.w[i] = p.w[i] * total;
+}
+// (mcl_likelihoods on a beam context with a table: the factor k_reweight_beam_lut multiplies a particle at that pose by)
+__global__ __launch_bounds__(kLutBlock) void k_likelihoods_beam_lut(const double4* __restrict__ poses, uint64_t n, GridView g, BeamModel m,
+                                                                    RangeTableView t, BeamTable terms, const double4* __restrict__ pts, uint32_t B,
+                                                                    double* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double4* s_pts = reinterpret_cast<double4*>(smem);
+  for (uint32_t i = threadIdx.x; i < B; i += kLutBlock) s_pts[i] = pts[i];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * (kLutBlock / kWave) + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const double4 v = poses[i];
+  const double total = beam_lut_wave_total(lane, Pose2{Rot2{v.x, v.y}, v.z, v.w}, g, m, t, terms, s_pts, B);
+  if (lane == 0) out[i] = total;
+}
+
 }  // namespace
 
 NonFreeBits nonfree_layout(uint32_t W, uint32_t H, uint32_t* base) {
@@ -1170,8 +1300,15 @@ hipError_t configure_beam_kernels() {
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_beam_sorted<false>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kBeamLds));
   if (e != hipSuccess) return e;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_beam_sorted<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             static_cast<int>(kBeamLds));
+  const hipError_t s = hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_beam_sorted<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          static_cast<int>(kBeamLds));
+  if (s != hipSuccess) return s;
+  // (the table reweight stages 32 bytes a beam: 128 KB at the 4096 points a beam context takes)
+  const hipError_t l = hipFuncSetAttribute(reinterpret_cast<const void*>(k_reweight_beam_lut), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          static_cast<int>(kBeamLutLds));
+  if (l != hipSuccess) return l;
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(k_likelihoods_beam_lut), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             static_cast<int>(kBeamLutLds));
 }
 
 uint32_t beam_table_entries(double beam_max_range, double resolution) {
@@ -1256,6 +1393,53 @@ void launch_cast_rays(hipStream_t st, const double4* poses, const double* far_en
   else
     hipLaunchKernelGGL(k_cast_rays<false>, grid, dim3(kBlock), 0, st, poses, table, B, chunk.first_bearing, chunk.rays, g, NonFreeBits{}, max_range,
                        ranges, hits, d_steps);
+}
+
+static_assert(kRangeTableBlock == kBlock && kRangeTableMaxReachCells == kBeamMaxReachCells,
+              "range_table_host.h restates k_build_range_table's workgroup and the walks' reach");
+void launch_build_range_table(hipStream_t st, GridView g, const uint32_t* nonfree_bits, const double* bearings_cs, uint32_t A,
+                              const RangeTableLaunch& launch, double max_range, uint32_t* table) {
+  if (launch.entries == 0) return;
+  const dim3 grid(static_cast<unsigned>(launch.blocks));
+  const double2* cs = reinterpret_cast<const double2*>(bearings_cs);
+  if (nonfree_bits)
+    hipLaunchKernelGGL(k_build_range_table<true>, grid, dim3(kBlock), 0, st, g, nonfree_layout(g.W, g.H, const_cast<uint32_t*>(nonfree_bits)), cs, A,
+                       launch.first_entry, launch.entries, max_range, table);
+  else
+    hipLaunchKernelGGL(k_build_range_table<false>, grid, dim3(kBlock), 0, st, g, NonFreeBits{}, cs, A, launch.first_entry, launch.entries, max_range,
+                       table);
+}
+static_assert(kBeamLutPointDoubles * sizeof(double) == sizeof(double4) && kBeamLutMaxPoints * sizeof(double4) == kBeamLutLds,
+              "kernels.h restates the table reweight's per-beam entry and its workgroup memory");
+void launch_beam_lut_points(hipStream_t st, const double* d_points, uint32_t B, BeamModel m, double* d_lut_points) {
+  if (B) hipLaunchKernelGGL(k_beam_lut_points, dim3(blocks_for(B)), dim3(kBlock), 0, st, d_points, B, m, reinterpret_cast<double4*>(d_lut_points));
+}
+void launch_reweight_beam_lut(hipStream_t st, Particles p, uint64_t n, GridView g, BeamModel m, RangeTableView t, const double* d_beam_table,
+                              uint32_t beam_table_count, const double* d_lut_points, uint32_t B) {
+  if (n == 0 || B == 0) return;
+  const BeamTable terms = d_beam_table && beam_table_count ? BeamTable{reinterpret_cast<const double4*>(d_beam_table), beam_table_count - 1u}
+                                                           : BeamTable{nullptr, 0u};
+  constexpr uint64_t per_block = kLutBlock / kWave;
+  const dim3 grid(static_cast<unsigned>((n + per_block - 1) / per_block));
+  hipLaunchKernelGGL(k_reweight_beam_lut, grid, dim3(kLutBlock), static_cast<size_t>(B) * sizeof(double4), st, p, n, g, m, t, terms,
+                     reinterpret_cast<const double4*>(d_lut_points), B);
+}
+void launch_likelihoods_beam_lut(hipStream_t st, const double4* poses, uint64_t n, GridView g, BeamModel m, RangeTableView t,
+                                 const double* d_beam_table, uint32_t beam_table_count, const double* d_lut_points, uint32_t B, double* out) {
+  if (n == 0) return;
+  if (B == 0) {  // (launch_reweight_beam_lut leaves the weights as they are)
+    launch_fill(st, out, n, 1.0);
+    return;
+  }
+  const BeamTable terms = d_beam_table && beam_table_count ? BeamTable{reinterpret_cast<const double4*>(d_beam_table), beam_table_count - 1u}
+                                                           : BeamTable{nullptr, 0u};
+  constexpr uint64_t per_block = kLutBlock / kWave;
+  for (uint64_t at = 0; at < n; at += kLikelihoodsWaveChunk) {  // (a grid dimension holds 2^31 - 1 blocks)
+    const uint64_t count = std::min<uint64_t>(kLikelihoodsWaveChunk, n - at);
+    const dim3 grid(static_cast<unsigned>((count + per_block - 1) / per_block));
+    hipLaunchKernelGGL(k_likelihoods_beam_lut, grid, dim3(kLutBlock), static_cast<size_t>(B) * sizeof(double4), st, poses + at, count, g, m, t, terms,
+                       reinterpret_cast<const double4*>(d_lut_points), B, out + at);
+  }
 }
 
 BatchBeam batch_beam_record(GridView g, BeamModel m, const uint32_t* nonfree_bits, unsigned long long* d_steps) {

@@ -94,6 +94,16 @@ struct mcl_ctx {
   DeviceBuffer<double> d_beam_table;   // beam model: 4 doubles per squared cell distance of a hit (launch_beam_table), built by mcl_set_map
   uint32_t beam_table_count{0};
   bool beam_table_ready{false};        // d_beam_table holds the table of the current map (built lazily: do_reweight)
+  // The range table of the beam model (mcl_build_range_table): range_angles != 0 says one is built, of the map the context reads now
+  // (range_width x range_height cells) and its beam_max_range - the context's own even on a shared map.  From then on the reweight and
+  // mcl_likelihoods* read it (k_reweight_beam_lut); whatever installs a map rebuilds it (range_table_follow_map).
+  DeviceBuffer<uint32_t> d_range_table;   // [(y * W + x) * A + k]
+  DeviceBuffer<double> d_range_bearings;  // the bins' bearings (cos, sin), as range_bearings holds them
+  DeviceBuffer<double> d_lut_points;      // the table reweight's per-beam entries (kBeamLutPointDoubles per beam)
+  std::vector<double> range_bearings;     // range_table_bearings' output: what the device was given and mcl_range_table_bearings returns
+  uint32_t range_angles{0}, range_width{0}, range_height{0};
+  uint64_t range_builds{0};               // tables built on this context, rebuilds included
+  uint64_t range_lut_launches{0};         // reweights of the cycle that read the table (mcl_range_table_info)
   uint64_t beam_wave_launches{0};      // lone launches of k_reweight_beam (a wave per particle) and of k_reweight_beam_sorted (ordered lanes):
   uint64_t beam_ordered_launches{0};   // mcl_get_counter; a fleet's shared k_batch_reweight_beam is the batch's beam_launches, not these
   uint64_t ndt_lane_launches{0};       // lone NDT reweight launches of the lane-per-particle kernels and of the wave-per-particle ones, either
@@ -1074,6 +1084,10 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
       // the beam kernels' walks keep 16 * span in an int (walk_blocks: 8 * dminor, q * dmajor): lines of 2^27 cells and more are refused
       MCL_REQUIRE(ctx, ctx->cfg.beam.beam_max_range / ctx->map->resolution < kBeamMaxReachCells,
                   "beam_max_range / resolution must stay below 2^27 - 2 cells for the beam model");
+      if (ctx->range_angles != 0) {  // the table kernel serves every set size and stages 32 bytes a beam in 128 KB of dynamic LDS
+        MCL_REQUIRE(ctx, B <= kBeamLutMaxPoints, "scan too large for the beam model over a range table (4096 points)");
+        return MCL_OK;
+      }
       if (!(ctx->n < (1ull << 32) && ctx->n >= static_cast<uint64_t>(ctx->tuning.beam_sort_min_particles)))
         // the beam model's small-set kernel (a wave per particle) stages the scan in 64 KB of dynamic LDS
         MCL_REQUIRE(ctx, B * sizeof(double2) <= 64 * 1024, "scan too large for the beam model's small-set kernel (4096 points)");
@@ -1228,7 +1242,8 @@ void decide_hold(mcl_ctx* ctx, const ReweightStep& step) {
   switch (hold->family) {
     case SensorFamily::kLikelihoodField: hold->fused = batch_member_fused(batch_lf_facts(ctx, step.lf)); break;
     // (the wave-per-particle kernel, i.e. no ordering - `ordered` is the same question asked of the planner)
-    case SensorFamily::kBeam: hold->fused = !step.ordered && batch_beam_member_fused(batch_beam_facts(ctx)); break;
+    // (a member with a range table runs its own cycle: the fleet's shared kernel walks)
+    case SensorFamily::kBeam: hold->fused = !step.ordered && ctx->range_angles == 0 && batch_beam_member_fused(batch_beam_facts(ctx)); break;
     case SensorFamily::kNdt: hold->fused = batch_ndt_member_fused(batch_ndt_facts(ctx)); break;
     case SensorFamily::kLandmark: hold->fused = batch_landmark_member_fused(batch_landmark_facts(ctx)); break;
   }
@@ -1265,10 +1280,39 @@ void reweight_lf(mcl_ctx* ctx, const ReweightStep& step) {
   }
   stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
 }
+// What the kernels over the range table need beside it (the reweight and mcl_likelihoods*): the BeamTable of the current map, where the
+// reach allows one and option beam_table is on (*table_count = 0 otherwise: the lanes evaluate the entries themselves, the same bits),
+// and the scan's per-beam entries from the B points at d_points.
+mcl_status range_table_stage(mcl_ctx* ctx, const BeamModel& model, const double* d_points, uint32_t B, uint32_t* table_count) {
+  *table_count = ctx->tuning.beam_table != 0 ? ctx->beam_table_count : 0u;
+  if (*table_count && !ctx->beam_table_ready) {
+    hipError_t e = ctx->d_beam_table.ensure(4 * static_cast<size_t>(ctx->beam_table_count));
+    if (e == hipSuccess) {
+      launch_beam_table(ctx->stream, model, ctx->map->resolution, ctx->beam_table_count, ctx->d_beam_table.ptr);
+      e = hipGetLastError();
+    }
+    if (e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("range table (beam table): ") + hipGetErrorString(e));
+    ctx->beam_table_ready = true;
+  }
+  if (const hipError_t e = ctx->d_lut_points.ensure(static_cast<size_t>(kBeamLutPointDoubles) * std::max<uint32_t>(B, 1u)); e != hipSuccess)
+    return fail(ctx, e == hipErrorOutOfMemory ? MCL_ERR_OUT_OF_MEMORY : MCL_ERR_HIP, std::string("range table (scan entries): ") + hipGetErrorString(e));
+  launch_beam_lut_points(ctx->stream, d_points, B, model, ctx->d_lut_points.ptr);
+  return MCL_OK;
+}
 // Not MCL_OK: the table of the ordered kernel could not be built (nothing was launched; the caller closes its stage).
 mcl_status reweight_beam(mcl_ctx* ctx, const ReweightStep& step) {
   const mcl_beam_params& b = ctx->cfg.beam;
   const BeamModel model{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range};
+  if (ctx->range_angles != 0) {  // the range table serves every set size; never held (decide_hold), nothing walked, no cell counted
+    uint32_t table_count = 0;
+    if (const mcl_status s = range_table_stage(ctx, model, ctx->d_points.ptr, static_cast<uint32_t>(step.B), &table_count)) return s;
+    stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
+    launch_reweight_beam_lut(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model, RangeTableView{ctx->d_range_table.ptr, ctx->range_angles},
+                             table_count ? ctx->d_beam_table.ptr : nullptr, table_count, ctx->d_lut_points.ptr, static_cast<uint32_t>(step.B));
+    if (ctx->n != 0 && step.B != 0) ctx->range_lut_launches += 1;  // (the launcher's own test)
+    stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
+    return MCL_OK;
+  }
   const bool use_table = step.ordered && ctx->tuning.beam_table != 0 && ctx->beam_table_count != 0;  // (only the ordered kernel reads it)
   if (use_table && !ctx->beam_table_ready) {
     hipError_t e = ctx->d_beam_table.ensure(4 * static_cast<size_t>(ctx->beam_table_count));
@@ -2778,6 +2822,71 @@ mcl_status mcl_map_commit(mcl_ctx* ctx, int32_t wait) {
 
 }  // extern "C"
 namespace {
+// ---- the range table of the beam model: build, drop, follow the map (DESIGN.md "Range table for the beam model") ---------------------------
+// The host rule is range_table_host.cpp's.  Everything is checked before anything is allocated; the table is built into buffers of its own,
+// behind whatever the stream holds, and installed once the build has run through: a refusal or a failure leaves the context's table, if
+// it has one, as it was.  The build synchronises the stream (a table is built once per map, and a failed build must be seen here).
+void range_table_drop(mcl_ctx* ctx) {
+  ctx->d_range_table.release();
+  ctx->d_range_bearings.release();
+  ctx->range_bearings.clear();
+  ctx->range_angles = ctx->range_width = ctx->range_height = 0;
+}
+mcl_status range_table_build(mcl_ctx* ctx, uint32_t num_angles, const char* who) {
+  if (!ctx->off_grid() && !ctx->have_map && ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) return fail(ctx, MCL_ERR_NOT_READY, std::string(who) + ": no map set");
+  const char* what = nullptr;
+  uint64_t bytes = 0;
+  const bool have_map = ctx->have_map && !ctx->off_grid();
+  if (const mcl_status s = range_table_check(ctx->cfg.sensor_kind, num_angles, have_map ? ctx->map->W : 1, have_map ? ctx->map->H : 1,
+                                             ctx->cfg.beam.beam_max_range, have_map ? ctx->map->resolution : 1.0, ctx->tuning.range_table_max_bytes,
+                                             &bytes, &what))
+    return fail(ctx, s, std::string(who) + ": " + what);
+  if (const mcl_status s = bind_device(ctx)) return s;
+  std::vector<double> bearings;
+  try {
+    bearings.resize(2 * static_cast<size_t>(num_angles));
+  } catch (const std::bad_alloc&) {
+    return fail(ctx, MCL_ERR_OUT_OF_MEMORY, std::string(who) + ": out of memory");
+  }
+  range_table_bearings(num_angles, bearings.data());
+  const uint64_t cells = static_cast<uint64_t>(ctx->map->W) * ctx->map->H;
+  const RangeTablePlan plan = range_table_plan(cells, num_angles, static_cast<uint64_t>(ctx->tuning.range_table_launch));
+  DeviceBuffer<uint32_t> table;
+  DeviceBuffer<double> cs;
+  MCL_HIP(ctx, table.ensure(static_cast<size_t>(plan.entries)));
+  MCL_HIP(ctx, cs.ensure(bearings.size()));
+  MCL_HIP(ctx, hipMemcpyAsync(cs.ptr, bearings.data(), bearings.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  for (uint64_t c = 0; c < plan.launches; ++c)
+    launch_build_range_table(ctx->stream, ctx->grid_view(), ctx->map->d_nonfree_bits.ptr, cs.ptr, num_angles, range_table_launch_at(plan, c),
+                             ctx->cfg.beam.beam_max_range, table.ptr);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);  // (the buffers above are freed on the way out)
+    return fail(ctx, MCL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  }
+  // (the stream is idle: nothing reads the table this one replaces)
+  ctx->d_range_table.take(table);
+  ctx->d_range_bearings.take(cs);
+  ctx->range_bearings.swap(bearings);
+  ctx->range_angles = num_angles;
+  ctx->range_width = ctx->map->W;
+  ctx->range_height = ctx->map->H;
+  ctx->range_builds += 1;
+  return MCL_OK;
+}
+// Whatever has just installed a map (mcl_set_map, the swap of mcl_set_map_async's, mcl_use_shared_map): a context with a table builds
+// the new map's inside that call, so that it never walks silently; a rebuild that fails drops the table - the filter is on the exact
+// walk again - and its status is the call's.
+mcl_status range_table_follow_map(mcl_ctx* ctx) {
+  if (ctx->range_angles == 0) return MCL_OK;
+  const uint32_t num_angles = ctx->range_angles;
+  ctx->range_angles = 0;  // (the old map's table is not this map's, whatever happens below)
+  const mcl_status s = range_table_build(ctx, num_angles, "range table (rebuilt for the new map)");
+  if (s != MCL_OK) range_table_drop(ctx);
+  return s;
+}
+
 // What a context keeps of its own about the map it has just been given, a private store or a shared one.
 void map_installed(mcl_ctx* ctx) {
   if (ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) {
@@ -2806,7 +2915,7 @@ mcl_status set_map_impl(mcl_ctx* ctx, const int8_t* cells, uint32_t width, uint3
   if (const mcl_status s = build_map_store(*store, in, ctx->stream, &ctx->d_field_scratch, ctx->ev[MCL_STAGE_REWEIGHT], &err)) return fail(ctx, s, err);
   ctx->map.own(std::move(store));
   map_installed(ctx);
-  return MCL_OK;
+  return range_table_follow_map(ctx);
 }
 
 // The host side of installing a set that an entry point has just written into cur(): what each caller sets, and what it leaves as it was.
@@ -2979,7 +3088,7 @@ mcl_status mcl_use_shared_map(mcl_ctx* ctx, mcl_shared_map* map) {
   ctx->map.attach(map->store);
   ctx->map_generation += 1;
   map_installed(ctx);
-  return MCL_OK;
+  return range_table_follow_map(ctx);
 }
 
 mcl_status mcl_initialize_normal(mcl_ctx* ctx, const double mean_xytheta[3], const double cov[9]) {
@@ -4765,8 +4874,9 @@ static mcl_status likelihoods_stage(mcl_ctx* ctx, const LikelihoodsMeasurement& 
 }
 // The family's kernel over n poses in device memory; the measurement lies staged at d_meas.  Reads the map through the views the
 // reweight reads, as they are now (a map that mcl_set_map_async has not swapped in yet is not the context's map).
+// exact_walk (the global search): a beam context with a range table walks all the same.
 static mcl_status likelihoods_launch(mcl_ctx* ctx, const double* d_poses, uint64_t n, const LikelihoodsMeasurement& m, const double* d_meas,
-                                     double* d_out) {
+                                     double* d_out, bool exact_walk = false) {
   const double4* poses = reinterpret_cast<const double4*>(d_poses);
   switch (ctx->family()) {
     case SensorFamily::kLikelihoodField: {
@@ -4777,6 +4887,15 @@ static mcl_status likelihoods_launch(mcl_ctx* ctx, const double* d_poses, uint64
     }
     case SensorFamily::kBeam: {
       const mcl_beam_params& b = ctx->cfg.beam;
+      if (ctx->range_angles != 0 && !exact_walk) {  // the factor a reweight of this context would apply: over the table, as the cycle
+        const BeamModel model{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range};
+        const uint32_t B = static_cast<uint32_t>(m.doubles / 2);
+        uint32_t table_count = 0;
+        if (const mcl_status s = range_table_stage(ctx, model, d_meas, B, &table_count)) return s;
+        launch_likelihoods_beam_lut(ctx->stream, poses, n, ctx->grid_view(), model, RangeTableView{ctx->d_range_table.ptr, ctx->range_angles},
+                                    table_count ? ctx->d_beam_table.ptr : nullptr, table_count, ctx->d_lut_points.ptr, B, d_out);
+        break;
+      }
       launch_likelihoods_beam(ctx->stream, poses, n, ctx->grid_view(), BeamModel{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range},
                               d_meas, static_cast<uint32_t>(m.doubles / 2), ctx->map->d_nonfree_bits.ptr, d_out);
       break;
@@ -4949,7 +5068,8 @@ static mcl_status global_search(mcl_ctx* ctx, const char* who, const double* poi
     if (cells == 0) continue;
     if (const mcl_status s = search_generate_chunk(ctx, &call, cells)) return s;
     const uint64_t n = static_cast<uint64_t>(cells) * p.headings;
-    if (const mcl_status s = likelihoods_launch(ctx, f64 + call.lay.poses, n, m, ctx->d_likelihoods.ptr + meas.measurement, f64 + call.lay.scores)) return s;
+    if (const mcl_status s = likelihoods_launch(ctx, f64 + call.lay.poses, n, m, ctx->d_likelihoods.ptr + meas.measurement, f64 + call.lay.scores,
+                                                /*exact_walk=*/true)) return s;
     call.launches += 1;
     call.launches += launch_search_pool(ctx->stream, f64 + call.lay.scores, u64 + call.lay.ids, n, call.scratch, p.pool, pool_len, &pool_at);
     if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
@@ -5143,6 +5263,49 @@ mcl_status mcl_cast_rays_device(mcl_ctx* ctx, const double* d_poses, uint64_t n,
                                 double* d_ranges_out, int64_t* d_hit_cells_out, uint64_t* cells_visited) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   return search_settled(ctx, cast_rays_device(ctx, d_poses, n, bearings_cs, num_bearings, max_range, d_ranges_out, d_hit_cells_out, cells_visited));
+}
+
+// ---- the range table of the beam model: the C ABI (range_table_build and its kin stand with the map's installation) ----------------------
+mcl_status mcl_build_range_table(mcl_ctx* ctx, uint32_t num_angles) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  return range_table_build(ctx, num_angles, "mcl_build_range_table");
+}
+mcl_status mcl_drop_range_table(mcl_ctx* ctx) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->range_angles == 0) return MCL_OK;
+  if (const mcl_status s = bind_device(ctx)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // nothing in flight reads the table any more
+  range_table_drop(ctx);
+  ctx->d_lut_points.release();
+  return MCL_OK;
+}
+mcl_status mcl_range_table_get_info(mcl_ctx* ctx, mcl_range_table_info* info) {
+  if (!ctx || !info) return MCL_ERR_INVALID_ARGUMENT;
+  const bool built = ctx->range_angles != 0;
+  *info = mcl_range_table_info{built ? 1 : 0, ctx->range_angles, ctx->range_width, ctx->range_height,
+                               built ? static_cast<uint64_t>(ctx->range_width) * ctx->range_height * ctx->range_angles * sizeof(uint32_t) : 0,
+                               ctx->range_builds, ctx->range_lut_launches};
+  return MCL_OK;
+}
+mcl_status mcl_range_table_bearings(mcl_ctx* ctx, double* cs_out) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->range_angles == 0) return fail(ctx, MCL_ERR_NOT_READY, "mcl_range_table_bearings: no range table built");
+  MCL_REQUIRE(ctx, cs_out, "mcl_range_table_bearings: null argument");
+  std::copy(ctx->range_bearings.begin(), ctx->range_bearings.end(), cs_out);
+  return MCL_OK;
+}
+mcl_status mcl_range_table_read(mcl_ctx* ctx, uint64_t first_cell, uint64_t num_cells, uint32_t* out) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  if (ctx->range_angles == 0) return fail(ctx, MCL_ERR_NOT_READY, "mcl_range_table_read: no range table built");
+  const uint64_t cells = static_cast<uint64_t>(ctx->range_width) * ctx->range_height;
+  MCL_REQUIRE(ctx, first_cell <= cells && num_cells <= cells - first_cell, "mcl_range_table_read: cells beyond the grid");
+  if (num_cells == 0) return MCL_OK;
+  MCL_REQUIRE(ctx, out, "mcl_range_table_read: null argument");
+  if (const mcl_status s = bind_device(ctx)) return s;
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  MCL_HIP(ctx, hipMemcpy(out, ctx->d_range_table.ptr + first_cell * ctx->range_angles, num_cells * ctx->range_angles * sizeof(uint32_t),
+                         hipMemcpyDeviceToHost));
+  return MCL_OK;
 }
 
 // ---- beam skipping: the parameters, the last decision, and the count as a call of its own -------------------------------------------

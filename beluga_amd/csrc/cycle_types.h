@@ -139,6 +139,10 @@ struct Tuning {
                                     // does not depend on it
   int cast_chunk = 1 << 22;         // mcl_cast_rays: rays a chunk of the host form holds (64 .. 2^28) - what bounds the call's device memory; the
                                     // result does not depend on it
+  int range_table_launch = 1 << 30; // mcl_build_range_table: entries one launch of the build covers (256 .. 2^30, in whole workgroups of 256); the
+                                    // table does not depend on it
+  int64_t range_table_max_bytes = 4ll << 30;  // mcl_build_range_table: a table larger than this is refused (MCL_ERR_OUT_OF_MEMORY) before
+                                              // anything is allocated; 0 .. 2^62.  The one option that is no int: set_tuning stores it itself
 };
 
 // Spatial ordering of the particles (kLfSortedLanes, ordered beam kernel): the 64 lanes of a wave should hold neighbouring

@@ -18,6 +18,7 @@
 #include "se2.h"
 #include "search_host.h"
 #include "raycast_host.h"
+#include "range_table_host.h"
 #include "sensor_records.h"
 
 namespace mcl {
@@ -486,6 +487,31 @@ void launch_pack_nonfree(hipStream_t st, const int8_t* cells, uint32_t W, uint32
 // mcl_create calls this for every context, after hipSetDevice.
 hipError_t configure_device_kernels();
 hipError_t configure_beam_kernels();
+
+// ---- the range table of the beam model (mcl_build_range_table; DESIGN.md "Range table for the beam model"; the host rule:
+// range_table_host.h) ---------------------------------------------------------------------------------------------------------------------
+// table[(y * W + x) * A + k]: the squared cell distance from cell (x, y) to the cell the exact rule's cast hits along bin k's bearing
+// from the cell's centre, in the grid frame; kRangeTableNoHit without a hit.
+struct RangeTableView {
+  const uint32_t* entries;
+  uint32_t A;
+};
+// One launch of the build (RangeTableLaunch): entries first_entry .. + entries of `table`.  bearings_cs: the A bearings (cos, sin) in
+// device memory.  nonfree_bits: the packed bit maps of a beam context's map, or null: the plain walk over g.cells.
+void launch_build_range_table(hipStream_t st, GridView g, const uint32_t* nonfree_bits, const double* bearings_cs, uint32_t A,
+                              const RangeTableLaunch& launch, double max_range, uint32_t* table);
+// The table reweight's per-beam entries (z, exp(-lambda_short z), the tail, beta = atan2(py, px)): kBeamLutPointDoubles * B doubles.
+constexpr uint32_t kBeamLutPointDoubles = 4;
+constexpr uint32_t kBeamLutMaxPoints = 4096;     // the points a beam context takes (reweight_preconditions, likelihoods_points)
+constexpr size_t kBeamLutLds = 128 * 1024;       // ... staged in workgroup memory
+void launch_beam_lut_points(hipStream_t st, const double* d_points, uint32_t B, BeamModel m, double* d_lut_points);
+// p.w[i] *= the beam model's sum over the scan with the expected ranges read from the table; serves every set size, orders nothing,
+// counts no cells.  d_beam_table / beam_table_count: launch_beam_table's output, or null / 0: a lane evaluates the entry itself.
+void launch_reweight_beam_lut(hipStream_t st, Particles p, uint64_t n, GridView g, BeamModel m, RangeTableView t, const double* d_beam_table,
+                              uint32_t beam_table_count, const double* d_lut_points, uint32_t B);
+// out[i] = that sum for the caller's pose i.  B == 0: 1.0.
+void launch_likelihoods_beam_lut(hipStream_t st, const double4* poses, uint64_t n, GridView g, BeamModel m, RangeTableView t,
+                                 const double* d_beam_table, uint32_t beam_table_count, const double* d_lut_points, uint32_t B, double* out);
 
 // Deterministic chunked reductions / scans: kChunk consecutive elements per workgroup, num_chunks(n) of them (scratch_layout.h).
 

@@ -76,6 +76,7 @@ constexpr Option kLaterOptions[] = {
     {"lf_pose_ahead", &Tuning::lf_pose_ahead, Rule::kFlag, 0, 0},
     {"search_chunk", &Tuning::search_chunk, Rule::kClamp, 64, 1ll << 22},
     {"cast_chunk", &Tuning::cast_chunk, Rule::kClamp, 64, 1ll << 28},
+    {"range_table_launch", &Tuning::range_table_launch, Rule::kClamp, 256, 1ll << 30},
 };
 
 int normalised(const Option& o, int64_t value) {
@@ -113,6 +114,10 @@ bool set_tuning(Tuning& t, const char* name, int64_t value) {
   for (const Option& o : kLaterOptions) {
     if (std::strcmp(o.name, name) != 0) continue;
     t.*o.member = normalised(o, value);
+    return true;
+  }
+  if (std::strcmp(name, "range_table_max_bytes") == 0) {  // (a byte count: the one value an int does not hold)
+    t.range_table_max_bytes = std::clamp<int64_t>(value, 0, 1ll << 62);
     return true;
   }
   return false;

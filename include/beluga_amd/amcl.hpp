@@ -809,6 +809,32 @@ class Amcl {
                         bearings.size(), max_range, ranges.data(), hit_cells ? hit_cells->data() : nullptr, cells_visited));
     return ranges;
   }
+  /// Extension: the range table of the beam model (mcl_build_range_table; what MIT's rangelibc calls a look-up table): per cell and
+  /// heading bin of num_angles, the squared cell distance to the cell the exact cast from the cell's centre hits.  From the next
+  /// reweight on update(), reweight() and likelihoods() read it - one look-up per beam in place of a walk.  An approximation (the
+  /// source's position inside its cell and the heading within a bin are discarded), hence opt-in.  Whatever installs a map afterwards
+  /// rebuilds the table.  Beam filters only (throws on another); cast_rays() and global_search() stay exact.
+  void build_range_table(std::uint32_t num_angles = 360) { check(mcl_build_range_table(ctx_, num_angles)); }
+  /// Back to the exact walk; the table's memory is freed.
+  void drop_range_table() { check(mcl_drop_range_table(ctx_)); }
+  [[nodiscard]] mcl_range_table_info range_table_info() const {
+    mcl_range_table_info info{};
+    check(mcl_range_table_get_info(ctx_, &info));
+    return info;
+  }
+  /// The bins' bearings (cos, sin) the table was built with.
+  [[nodiscard]] std::vector<std::pair<double, double>> range_table_bearings() const {
+    static_assert(sizeof(std::pair<double, double>) == 2 * sizeof(double), "bearings are handed over as (cos, sin) doubles");
+    std::vector<std::pair<double, double>> out(range_table_info().num_angles);
+    check(mcl_range_table_bearings(ctx_, out.empty() ? nullptr : &out.data()->first));
+    return out;
+  }
+  /// The entries of cells first_cell .. first_cell + num_cells - 1 (cell = y * width + x), num_angles each; 0xFFFFFFFF: no hit.
+  [[nodiscard]] std::vector<std::uint32_t> range_table(std::uint64_t first_cell, std::uint64_t num_cells) const {
+    std::vector<std::uint32_t> out(num_cells * range_table_info().num_angles);
+    check(mcl_range_table_read(ctx_, first_cell, num_cells, out.data()));
+    return out;
+  }
   /// Extension: beam skipping (mcl_set_beam_skip; Nav2 AMCL's do_beamskip, beam_skip_distance, beam_skip_threshold,
   /// beam_skip_error_threshold).  Before every reweight the cloud votes on each beam; beams that too few particles can explain are
   /// left out of that update, unless so much of the scan would go that all of it is used.  Likelihood-field sensor models only.

@@ -169,6 +169,16 @@ class Amcl {
     return filter_.cast_rays(states, bearings, max_range, hit_cells, cells_visited);
   }
 
+  /// Extension: the range table of the beam model (beluga_amd::Amcl::build_range_table): the expected range as one look-up per beam in
+  /// place of a walk, from the next update on; opt-in, since it approximates.  A map given later rebuilds it.
+  void build_range_table(std::uint32_t num_angles = 360) { filter_.build_range_table(num_angles); }
+  void drop_range_table() { filter_.drop_range_table(); }
+  [[nodiscard]] mcl_range_table_info range_table_info() const { return filter_.range_table_info(); }
+  [[nodiscard]] std::vector<std::pair<double, double>> range_table_bearings() const { return filter_.range_table_bearings(); }
+  [[nodiscard]] std::vector<std::uint32_t> range_table(std::uint64_t first_cell, std::uint64_t num_cells) const {
+    return filter_.range_table(first_cell, num_cells);
+  }
+
   /// Extension: the global pose search (beluga_amd::Amcl::global_search) over the scan types update() takes - a laser scan, a point
   /// cloud, or points already in the base frame - projected exactly as update() projects them: the best poses of the whole map for
   /// this measurement, the filter untouched.

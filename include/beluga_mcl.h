@@ -566,6 +566,60 @@ mcl_status mcl_cast_rays(mcl_ctx* ctx, const double* poses, uint64_t n, const do
 mcl_status mcl_cast_rays_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
                                 double* d_ranges_out, int64_t* d_hit_cells_out /* NULL ok */, uint64_t* cells_visited /* NULL ok */);
 
+/* ---- Range table for the beam model: the expected range as one look-up per beam in place of a walk ---------------------------------
+ * The exact rule's expected range depends on the source cell and the far-end cell alone.  With the ray's heading in the GRID frame
+ * quantised to A bins it becomes a table over (cell, bin) - what MIT's rangelibc calls a look-up table.  An APPROXIMATION, hence opt-in:
+ * a context without a table is byte for byte what it was.  tests/range_table_reference.py restates all of this.
+ *
+ * The table (the context's own, one per map x beam_max_range x A - even on a shared map): uint32 table[(y * width + x) * A + k] = the
+ * squared cell distance (hx - x)^2 + (hy - y)^2 between cell (x, y) and the cell the exact rule's cast from it hits, 0xFFFFFFFF without a
+ * hit (a distance of 65 536 cells or more is stored as 0xFFFFFFFE).  The cast of entry (x, y, k), all in the grid frame:
+ *   far end ((x + 0.5) * resolution + c_k * max_range, (y + 0.5) * resolution + s_k * max_range), every product and sum rounded on its
+ *     own; its cell floor(v * (1 / resolution)); source cell (x, y); max_range = the context's beam_max_range;
+ *   the walk of mcl_cast_rays (standard Bresenham; stops at the first cell outside the grid, not free, or behind the far end).
+ *   (c_k, s_k) = std::cos, std::sin of double(k) * (2 pi / A), computed on the host, uploaded, kept: mcl_range_table_bearings.
+ * WHAT IT DISCARDS of the exact rule: the source's position inside its cell (the cast starts at the centre), and the heading within a bin.
+ *
+ * The bin of a beam (the reweight's rule).  Per particle: src = origin^-1 * pose and its cell (sx, sy) as the exact path forms them,
+ * theta = atan2(src.r.s, src.r.c).  Per scan point: beta = atan2(py, px).  u = (theta + beta) * (A / (2 pi)); k = floor(u + 0.5) reduced
+ * into [0, A).  The entry is table[(sy * width + sx) * A + k], or "no hit" for a source cell outside the grid (exact: the walk's first
+ * cell is outside).  The expected range is fmin(sqrt(r2) * resolution, max_range), max_range without a hit; the mixture from there on is
+ * the beam model's, with `measured < expected` decided on that value (the exact path's re-derivation of a tie from the two cell centres
+ * has no hit cell to work with here).
+ *
+ * With a table built: mcl_update, mcl_reweight, mcl_likelihoods and mcl_likelihoods_device of the context read it (mcl_likelihoods stays
+ * "the factor a reweight would apply"); one kernel serves every set size, for scans of up to 4096 points (a larger one is
+ * MCL_ERR_INVALID_ARGUMENT while a table is built).  mcl_cast_rays* stays the exact caster and mcl_global_search*
+ * stays on the exact walk.  mcl_beam_cells_visited does not move: nothing is walked.  A member of a batch with a table runs its own
+ * cycle inside mcl_batch_update, whatever batch_beam_fused says.  On a sharded context the build is a LOCAL call that every rank makes
+ * for itself; the library does not compare it across ranks.
+ *
+ * mcl_build_range_table builds the table of the current map on the device (synchronises the stream) and switches the cycle over from
+ * the next reweight on; called again it replaces the table (another A).  Whatever installs a map afterwards - mcl_set_map, the swap of a
+ * map given by mcl_set_map_async (inside mcl_update or mcl_map_commit), mcl_use_shared_map - REBUILDS the table inside that call, so a
+ * context with a table never walks silently; a rebuild that fails drops the table (built == 0, the exact walk again) and its status is
+ * that call's.  Memory: width * height * A * 4 bytes, refused with MCL_ERR_OUT_OF_MEMORY before anything is allocated above option
+ * range_table_max_bytes (default 4 GiB).  Other refusals, MCL_ERR_INVALID_ARGUMENT: a context that is no beam context (a
+ * likelihood-field cycle would never read the table), num_angles outside 1 .. 4096, beam_max_range / resolution at or above 2^27 - 2
+ * cells; MCL_ERR_NOT_READY without a map.  Every refusal leaves the filter and a table it already has as they were. */
+typedef struct mcl_range_table_info {
+  int32_t built;         /* 1: the cycle reads a table */
+  uint32_t num_angles;   /* A */
+  uint32_t width, height;
+  uint64_t bytes;        /* of the table in device memory */
+  uint64_t builds;       /* tables built on this context since mcl_create, rebuilds included */
+  uint64_t lut_launches; /* reweights of the cycle that read a table: one per reweight */
+} mcl_range_table_info;
+mcl_status mcl_build_range_table(mcl_ctx* ctx, uint32_t num_angles);
+/* Back to the exact walk; the memory is freed.  MCL_OK without a table. */
+mcl_status mcl_drop_range_table(mcl_ctx* ctx);
+mcl_status mcl_range_table_get_info(mcl_ctx* ctx, mcl_range_table_info* info);
+/* cs_out[2 k], [2 k + 1] = (c_k, s_k), 2 * A doubles: the bearings the table was built with.  MCL_ERR_NOT_READY without a table. */
+mcl_status mcl_range_table_bearings(mcl_ctx* ctx, double* cs_out);
+/* out[(c - first_cell) * A + k] = the entries of cells first_cell .. first_cell + num_cells - 1 (cell = y * width + x); synchronises the
+ * stream.  MCL_ERR_NOT_READY without a table, MCL_ERR_INVALID_ARGUMENT for cells beyond the grid. */
+mcl_status mcl_range_table_read(mcl_ctx* ctx, uint64_t first_cell, uint64_t num_cells, uint32_t* out);
+
 /* ---- Beam skipping (Nav2 AMCL's do_beamskip) for the likelihood-field models ----------------------------------------------------
  * A beam that hits something the map does not know - a person, a pallet, an open door - pulls the weight of EVERY particle down
  * together and flattens the posterior.  With beam skipping the cloud votes on each beam before the reweight: beams that too few
@@ -944,7 +998,8 @@ mcl_status mcl_profile_enable(mcl_ctx* ctx, int32_t on);
 /* Accumulated milliseconds and launch counts per stage since the last reset. */
 mcl_status mcl_profile_read(mcl_ctx* ctx, double ms[MCL_NUM_STAGES], uint64_t counts[MCL_NUM_STAGES], int32_t reset);
 
-/* Beam model only: grid cells visited by the ray walks since the last reset (cells/s). */
+/* Beam model only: grid cells visited by the ray walks since the last reset (cells/s).  It does not move while the
+ * cycle reads a range table (mcl_build_range_table): nothing is walked there, and the table's build is not counted. */
 mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
 
 /* ---- Switches and hooks for A/B measurements and tests.  No option but field_build changes a result beyond the rounding of a
@@ -1051,6 +1106,8 @@ mcl_status mcl_beam_cells_visited(mcl_ctx* ctx, uint64_t* cells, int32_t reset);
  *   batch_beam_fused (0)  a beam-model member of a batch whose cycle is the small one with the wave-per-particle kernel: 1 = its kernels
  *                   ride on the fleet's shared launches, the reweight on one launch for all such members ("Batches of small filters"),
  *                   0 = it runs its own cycle inside mcl_batch_update.  The same bits either way.  Off until the path has been measured.
+ *   range_table_max_bytes (4 GiB)  mcl_build_range_table refuses a table larger than this (0 .. 2^62) before anything is allocated
+ *   range_table_launch (2^30)  entries one launch of the table's build covers (256 .. 2^30, whole workgroups of 256); the same table
  *   small_fused (1)  sets of up to 4096 particles: everything behind the reweight - normalise, policies, fixed-size or KLD resampling, estimate
  *                   sums - in one launch of one workgroup and one host synchronisation (and two one-workgroup kernels around the host's pass of
  *                   cluster_based_estimate); 0 = the kernels of the large path
