@@ -34,6 +34,7 @@
 #include "map_store.h"
 #include "ndt_host.h"
 #include "options_host.h"
+#include "scan_host.h"
 #include "scratch_layout.h"
 #include "search_host.h"
 #include "set_facts.h"
@@ -55,6 +56,68 @@ struct ParticleSet {
 };
 
 Pose2 pose_from(const double p[4]) { return Pose2{Rot2{p[0], p[1]}, p[2], p[3]}; }
+
+// The calls that are no part of the update cycle keep their state in a struct each, which mcl_ctx holds by value.
+// mcl_likelihoods*: the sensor model evaluated at caller-given poses.  Buffers of the call's own - nothing the cycle reads or writes: the
+// measurement as its kernel reads it, staged and copied on the stream; the host forms' poses and scores (LikelihoodsLayout, scratch_layout.h).
+struct LikelihoodsState {
+  DeviceBuffer<double> block;
+  StagedUpload<double> meas;
+  std::vector<double> records;  // the NDT cells or detection records of the call, before they are staged
+};
+// mcl_global_search*: the call's own buffers (SearchLayout, scratch_layout.h), sized by the chunk; the measurement is staged as
+// mcl_likelihoods_device stages it.  Every call ends in a synchronisation, a device error's return included (settled_after_device_error):
+// nothing of it is in flight at the next.
+struct SearchState {
+  DeviceBuffer<double> f64;
+  DeviceBuffer<unsigned long long> u64;
+  DeviceBuffer<uint32_t> u32;
+  HostBuffer<unsigned long long> pinned;
+};
+// mcl_cast_rays*: the call's own buffers (RayCastLayout, scratch_layout.h) - the bearing table, the cell count, a chunk's poses and
+// outputs - and the pinned staging of the bearings (the next call waits for their copy before it writes the staging memory again).
+struct RayCastState {
+  DeviceBuffer<double> block;
+  StagedUpload<double> staged;
+};
+// Beam skipping (mcl_set_beam_skip; likelihood-field contexts): the parameters, the last decision by the caller's points, and the
+// count's own buffers - the finite points of the scan up, their counts down (BeamSkipLayout, scratch_layout.h; every count ends in a
+// synchronisation, so nothing of it is ever in flight at the next).  Nothing is derived from the field: the count reads it as it is.
+struct BeamSkipState {
+  mcl_beam_skip_params params{0, 0, 0.5, 0.3, 0.9};
+  DeviceBuffer<double> block;
+  HostBuffer<double> pinned;
+  std::vector<uint32_t> slot;    // staged point -> the caller's point
+  std::vector<uint32_t> counts;  // the last decision's counts and mask, by the caller's points
+  std::vector<uint8_t> kept;
+  std::vector<double> points;    // the kept points: the scan the reweight stages
+  mcl_beam_skip_result last{};
+  uint64_t launches{0};          // count launches of enabled cycles and reweights (mcl_get_counter)
+  uint64_t used_all{0};          // decisions that fell back to the whole scan
+  uint64_t agreement_calls{0};   // calls of mcl_beam_agreement that reached the device
+  float level(const mcl_lf_params& lf) const { return beam_skip_level(lf, params.distance); }
+  bool on() const { return params.enabled != 0; }
+};
+// The range table of the beam model (mcl_build_range_table): built() says one is built, of the map the context reads now (width x
+// height cells) and its beam_max_range - the context's own even on a shared map.  From then on the reweight and mcl_likelihoods* read
+// it (k_reweight_beam_lut); whatever installs a map rebuilds it (range_table_follow_map).
+struct RangeTableState {
+  DeviceBuffer<uint32_t> table;        // [(y * W + x) * A + k]
+  DeviceBuffer<double> d_bearings;     // the bins' bearings (cos, sin), as `bearings` holds them
+  DeviceBuffer<double> lut_points;     // the table reweight's per-beam entries (kBeamLutPointDoubles per beam)
+  std::vector<double> bearings;        // range_table_bearings' output: what the device was given and mcl_range_table_bearings returns
+  uint32_t angles{0}, width{0}, height{0};
+  uint64_t builds{0};                  // tables built on this context, rebuilds included
+  uint64_t lut_launches{0};            // reweights of the cycle that read the table (mcl_range_table_info)
+  bool built() const { return angles != 0; }
+  RangeTableView view() const { return RangeTableView{table.ptr, angles}; }
+  void release() {  // the table alone: lut_points may be in flight, the counters are the context's history
+    table.release();
+    d_bearings.release();
+    bearings.clear();
+    angles = width = height = 0;
+  }
+};
 
 }  // namespace
 
@@ -93,26 +156,15 @@ struct mcl_ctx {
   DeviceBuffer<double> d_beam_points;  // beam model: per-beam terms (kBeamPointDoubles per beam)
   DeviceBuffer<double> d_beam_table;   // beam model: 4 doubles per squared cell distance of a hit (launch_beam_table), built by mcl_set_map
   uint32_t beam_table_count{0};
-  bool beam_table_ready{false};        // d_beam_table holds the table of the current map (built lazily: do_reweight)
-  // The range table of the beam model (mcl_build_range_table): range_angles != 0 says one is built, of the map the context reads now
-  // (range_width x range_height cells) and its beam_max_range - the context's own even on a shared map.  From then on the reweight and
-  // mcl_likelihoods* read it (k_reweight_beam_lut); whatever installs a map rebuilds it (range_table_follow_map).
-  DeviceBuffer<uint32_t> d_range_table;   // [(y * W + x) * A + k]
-  DeviceBuffer<double> d_range_bearings;  // the bins' bearings (cos, sin), as range_bearings holds them
-  DeviceBuffer<double> d_lut_points;      // the table reweight's per-beam entries (kBeamLutPointDoubles per beam)
-  std::vector<double> range_bearings;     // range_table_bearings' output: what the device was given and mcl_range_table_bearings returns
-  uint32_t range_angles{0}, range_width{0}, range_height{0};
-  uint64_t range_builds{0};               // tables built on this context, rebuilds included
-  uint64_t range_lut_launches{0};         // reweights of the cycle that read the table (mcl_range_table_info)
-  uint64_t beam_wave_launches{0};      // lone launches of k_reweight_beam (a wave per particle) and of k_reweight_beam_sorted (ordered lanes):
+  bool beam_table_ready{false};        // d_beam_table holds the table of the current map (built lazily: ensure_beam_table)
+  BeamModel beam_model() const { const mcl_beam_params& b = cfg.beam; return BeamModel{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range}; }
+  uint64_t beam_wave_launches{0};     // lone launches of k_reweight_beam (a wave per particle) and of k_reweight_beam_sorted (ordered lanes):
   uint64_t beam_ordered_launches{0};   // mcl_get_counter; a fleet's shared k_batch_reweight_beam is the batch's beam_launches, not these
   uint64_t ndt_lane_launches{0};       // lone NDT reweight launches of the lane-per-particle kernels and of the wave-per-particle ones, either
   uint64_t ndt_wave_launches{0};       // layout (launch_ndt_reweight; mcl_get_counter); a fleet's shared launch is mcl_ndt_batch_counts, not these
-  HostBuffer<double> h_points;  // pinned, mapped
+  StagedUpload<double> h_points;  // pinned, mapped; used behind the kernel that pulls it
   double scan_extent{0.0};     // max |x| + |y| of the staged scan points
   uint64_t scan_no_cell{0};    // points of the scan taken out where it was staged: NaN or infinite, without a cell for any pose (FieldView::acc0)
-  hipEvent_t points_event{nullptr};  // recorded behind the kernel that pulls h_points
-  bool points_in_flight{false}, points_event_valid{false};
 
   // reductions / scans
   DeviceBuffer<double> d_chunk;      // chunk_rows (scratch_layout.h)
@@ -319,48 +371,11 @@ struct mcl_ctx {
   }
   bool is_landmark() const { return family() == SensorFamily::kLandmark; }
 
-  // mcl_likelihoods*: the sensor model evaluated at caller-given poses.  Buffers of the call's own - nothing the cycle reads or writes:
-  // the measurement as its kernel reads it, staged in pinned memory and copied on the stream; the host forms' poses and scores
-  // (LikelihoodsLayout, scratch_layout.h).  likelihoods_event, made on the first call, stands behind the copy of the staged
-  // measurement: the next call waits for it before it writes the staging memory again.
-  DeviceBuffer<double> d_likelihoods;
-  HostBuffer<double> h_likelihoods_meas;
-  std::vector<double> likelihoods_records;  // the NDT cells or detection records of the call, before they are staged
-  hipEvent_t likelihoods_event{nullptr};
-  bool likelihoods_in_flight{false};
-
-  // mcl_global_search*: the call's own buffers (SearchLayout, scratch_layout.h), sized by the chunk; the measurement is staged as
-  // mcl_likelihoods_device stages it.  Every call ends in a synchronisation, a device error's return included (search_settled): nothing
-  // of it is in flight at the next.
-  DeviceBuffer<double> d_search_f64;
-  DeviceBuffer<unsigned long long> d_search_u64;
-  DeviceBuffer<uint32_t> d_search_u32;
-  HostBuffer<unsigned long long> h_search;
-
-  // mcl_cast_rays*: the call's own buffers (RayCastLayout, scratch_layout.h) - the bearing table, the cell count, a chunk's poses and
-  // outputs - and the pinned staging of the bearings.  cast_event, made on the first call, stands behind the copy of the staged
-  // bearings: the next call waits for it before it writes the staging memory again.
-  DeviceBuffer<double> d_cast;
-  HostBuffer<double> h_cast;
-  hipEvent_t cast_event{nullptr};
-  bool cast_in_flight{false};
-
-  // Beam skipping (mcl_set_beam_skip; likelihood-field contexts): the parameters, the last decision by the caller's points, and the
-  // count's own buffers - the finite points of the scan up, their counts down (BeamSkipLayout, scratch_layout.h; every count ends in a
-  // synchronisation, so nothing of it is ever in flight at the next).  Nothing is derived from the field: the count reads it as it is.
-  mcl_beam_skip_params beam_skip{0, 0, 0.5, 0.3, 0.9};
-  DeviceBuffer<double> d_beam_skip;
-  HostBuffer<double> h_beam_skip;
-  std::vector<uint32_t> beam_skip_slot;    // staged point -> the caller's point
-  std::vector<uint32_t> beam_skip_counts;  // the last decision's counts and mask, by the caller's points
-  std::vector<uint8_t> beam_skip_kept;
-  std::vector<double> beam_skip_points;    // the kept points: the scan the reweight stages
-  mcl_beam_skip_result beam_skip_last{};
-  uint64_t beam_skip_launches{0};    // count launches of enabled cycles and reweights (mcl_get_counter)
-  uint64_t beam_skip_used_all{0};    // decisions that fell back to the whole scan
-  uint64_t beam_agreement_calls{0};  // calls of mcl_beam_agreement that reached the device
-  float beam_skip_level() const { return mcl::beam_skip_level(cfg.lf, beam_skip.distance); }
-  bool beam_skip_on() const { return beam_skip.enabled != 0; }
+  LikelihoodsState likelihoods;
+  SearchState search;
+  RayCastState cast;
+  BeamSkipState beam_skip;
+  RangeTableState range;
   // A sensor model with a map of its own: no occupancy grid, none of the likelihood-field machinery, the host-read policy path.
   bool off_grid() const { return is_ndt() || is_landmark(); }
   // What random_intersperse's random states are drawn from (random_free_state).
@@ -425,7 +440,7 @@ void stage_end(mcl_ctx* ctx, int stage) {
 }
 // Call after the stream has been synchronised.
 void stage_collect(mcl_ctx* ctx) {
-  ctx->points_in_flight = false;  // the stream has been synchronised: the kernel that pulled the scan is done
+  ctx->h_points.idle();  // the stream has been synchronised: the kernel that pulled the scan is done
   if (!ctx->profile) return;
   for (int s = 0; s < MCL_NUM_STAGES; ++s) {
     if (!ctx->ev_pending[s]) continue;
@@ -890,7 +905,7 @@ mcl_status ndt_build_from_device_points(mcl_ctx* ctx, const std::string& who, co
 // Stages the measurement in mapped pinned memory; a kernel of the cycle pulls it into d_points (pull_scan_args / launch_pull_scan).
 // The likelihood-field models: a point with a NaN or infinite coordinate has no cell whatever the pose (the reference's
 // static_cast<int>(std::floor(.)) of it is undefined; as compiled it gives INT_MIN, "not in the grid": the unknown-space term).  Such
-// points are taken out here, counted (scan_no_cell -> FieldView::acc0), and *staged is left describing what was staged: the kernels' floor
+// points are taken out here (scan_finite_points), counted (scan_no_cell -> FieldView::acc0), and *staged is left describing what was staged: the kernels' floor
 // by the low mantissa word would read cell (0, 0) for them.
 mcl_status stage_points(mcl_ctx* ctx, Measurement* staged) {
   const Measurement m = *staged;
@@ -898,52 +913,31 @@ mcl_status stage_points(mcl_ctx* ctx, Measurement* staged) {
   if (m.doubles == 0) return MCL_OK;
   MCL_HIP(ctx, ctx->d_points.ensure(m.doubles));
   if (ctx->family() == SensorFamily::kBeam) MCL_HIP(ctx, ctx->d_beam_points.ensure(kBeamPointDoubles * (m.doubles / 2)));
-  if (ctx->points_in_flight) {  // an earlier call may still be reading the staging buffer
-    if (ctx->points_event_valid) MCL_HIP(ctx, hipEventSynchronize(ctx->points_event));
-    else MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->points_in_flight = false;
-  }
-  MCL_HIP(ctx, ctx->h_points.ensure(m.doubles, /*mapped=*/true));
+  MCL_HIP(ctx, ctx->h_points.reserve(ctx->stream, m.doubles, /*mapped=*/true));  // (an earlier call may still be reading the staging buffer)
   if (ctx->off_grid()) {  // records: nothing reads the extent of a scan on these contexts
-    std::copy(m.data, m.data + m.doubles, ctx->h_points.host);
+    std::copy(m.data, m.data + m.doubles, ctx->h_points.buf.host);
     return MCL_OK;
   }
+  double* const h = ctx->h_points.buf.host;
   double extent = 0.0;  // maximum of |x| + |y| over the scan; a NaN point makes it NaN (and every comparison with it false)
   bool poisoned = false, unbounded = false;
   for (uint64_t i = 0; i < m.doubles; i += 2) {  // (one straight pass, as before: the common scan has nothing to take out)
-    const double x = m.data[i], y = m.data[i + 1];
-    ctx->h_points.host[i] = x;
-    ctx->h_points.host[i + 1] = y;
+    const double x = h[i] = m.data[i], y = h[i + 1] = m.data[i + 1];
     const double e = std::abs(x) + std::abs(y);
     if (e != e) poisoned = true;
     if (e == std::numeric_limits<double>::infinity()) unbounded = true;
     extent = e > extent ? e : extent;
   }
   if ((poisoned || unbounded) && ctx->family() == SensorFamily::kLikelihoodField) {  // (the beam model walks rays: its own rules)
-    uint64_t kept = 0;
+    const uint64_t kept = 2 * scan_finite_points(m.data, m.doubles / 2, h);
     extent = 0.0;
-    for (uint64_t i = 0; i < m.doubles; i += 2) {
-      const double x = m.data[i], y = m.data[i + 1];
-      if (!(std::isfinite(x) && std::isfinite(y))) continue;  // a NaN or infinite coordinate (finite ones whose sum overflows stay)
-      const double e = std::abs(x) + std::abs(y);
-      ctx->h_points.host[kept] = x;
-      ctx->h_points.host[kept + 1] = y;
-      kept += 2;
-      extent = e > extent ? e : extent;
-    }
+    for (uint64_t i = 0; i < kept; i += 2) extent = std::max(extent, std::abs(h[i]) + std::abs(h[i + 1]));  // (no NaN among the kept)
     poisoned = false;
     ctx->scan_no_cell = (m.doubles - kept) / 2;
     staged->doubles = kept;
   }
   ctx->scan_extent = poisoned ? std::numeric_limits<double>::quiet_NaN() : extent;
   return MCL_OK;
-}
-// Call right behind the launch that pulls h_points.  with_event: a stage-level call that may return before the stream is
-// synchronised (mcl_update always ends with a synchronisation, which clears the flag: no event record on its stream).
-void points_pulled(mcl_ctx* ctx, bool with_event) {
-  if (with_event) (void)hipEventRecord(ctx->points_event, ctx->stream);
-  ctx->points_event_valid = with_event;
-  ctx->points_in_flight = true;
 }
 
 // ---- steps of beluga::Amcl::update (amcl_core.hpp:165-201) that mcl_update and sharded_update share ------------------------------------
@@ -1042,21 +1036,21 @@ mcl_status do_propagate(mcl_ctx* ctx, const Pose2& pose, const Pose2& prev, uint
     it.seed = ctx->cfg.seed;
     it.step = step;
     it.index_offset = ctx->cfg.shard_offset;
-    it.scan_src = scan_doubles ? ctx->h_points.device : nullptr;
+    it.scan_src = scan_doubles ? ctx->h_points.buf.device : nullptr;
     it.scan_dst = scan_doubles ? ctx->d_points.ptr : nullptr;
     it.scan_doubles = static_cast<uint32_t>(scan_doubles);
     it.field_out = field_out;
     hold->propagate_held = true;
   } else {
     launch_propagate(ctx->stream, ctx->cur(), ctx->n, sampler, ctx->cfg.seed, step, ctx->cfg.shard_offset,
-                     scan_doubles ? ctx->h_points.device : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
+                     scan_doubles ? ctx->h_points.buf.device : nullptr, scan_doubles ? ctx->d_points.ptr : nullptr, static_cast<uint32_t>(scan_doubles),
                      keys ? &sort : nullptr, keys ? &frame : nullptr, ahead ? ctx->d_noise.ptr : nullptr, ctx->facts.noise_ahead_count(),
                      field_out);
   }
   if (field_poses) ctx->facts.field_poses_written(ctx->map_generation);
   else ctx->facts.poses_moved();
   if (ahead) ctx->noise_ahead_used += 1;
-  if (scan_doubles) points_pulled(ctx, false);
+  if (scan_doubles) (void)ctx->h_points.used(ctx->stream, /*with_event=*/false);  // (the cycle ends in a synchronisation: no event on its stream)
   if (keys_emitted) *keys_emitted = keys;
   ctx->facts.order_accepted(use_ahead);
   stage_end(ctx, MCL_STAGE_PROPAGATE);
@@ -1084,7 +1078,7 @@ mcl_status reweight_preconditions(mcl_ctx* ctx, uint64_t B) {
       // the beam kernels' walks keep 16 * span in an int (walk_blocks: 8 * dminor, q * dmajor): lines of 2^27 cells and more are refused
       MCL_REQUIRE(ctx, ctx->cfg.beam.beam_max_range / ctx->map->resolution < kBeamMaxReachCells,
                   "beam_max_range / resolution must stay below 2^27 - 2 cells for the beam model");
-      if (ctx->range_angles != 0) {  // the table kernel serves every set size and stages 32 bytes a beam in 128 KB of dynamic LDS
+      if (ctx->range.built()) {  // the table kernel serves every set size and stages 32 bytes a beam in 128 KB of dynamic LDS
         MCL_REQUIRE(ctx, B <= kBeamLutMaxPoints, "scan too large for the beam model over a range table (4096 points)");
         return MCL_OK;
       }
@@ -1115,8 +1109,8 @@ mcl_status ndt_cell_records(mcl_ctx* ctx, const char* who, const double* means, 
 // The count's buffers for a scan of B points (BeamSkipLayout), made before anything of a cycle moves.
 mcl_status beam_skip_reserve(mcl_ctx* ctx, uint64_t B) {
   const BeamSkipLayout lay(B);
-  MCL_HIP(ctx, ctx->d_beam_skip.ensure(std::max<size_t>(lay.size, 4)));
-  MCL_HIP(ctx, ctx->h_beam_skip.ensure(std::max<size_t>(lay.size, 4), /*mapped=*/false));
+  MCL_HIP(ctx, ctx->beam_skip.block.ensure(std::max<size_t>(lay.size, 4)));
+  MCL_HIP(ctx, ctx->beam_skip.pinned.ensure(std::max<size_t>(lay.size, 4), /*mapped=*/false));
   return MCL_OK;
 }
 // counts[b], b < B: the live particles that point b of the caller's scan agrees with (include/beluga_mcl.h "Beam skipping"), on the
@@ -1129,27 +1123,21 @@ mcl_status beam_skip_count(mcl_ctx* ctx, const double* points_xy, uint64_t B, ui
   std::fill(counts, counts + B, 0u);
   if (const mcl_status s = beam_skip_reserve(ctx, B)) return s;
   const BeamSkipLayout lay(B);
-  std::vector<uint32_t>& slot = ctx->beam_skip_slot;
-  slot.clear();
-  double* const h_points = ctx->h_beam_skip.host + lay.points;
-  for (uint64_t b = 0; b < B; ++b) {
-    const double x = points_xy[2 * b], y = points_xy[2 * b + 1];
-    if (!(std::isfinite(x) && std::isfinite(y))) continue;
-    h_points[2 * slot.size()] = x;
-    h_points[2 * slot.size() + 1] = y;
-    slot.push_back(static_cast<uint32_t>(b));
-  }
+  std::vector<uint32_t>& slot = ctx->beam_skip.slot;
+  slot.resize(B);
+  double* const h_points = ctx->beam_skip.pinned.host + lay.points;
+  slot.resize(scan_finite_points(points_xy, B, h_points, slot.data()));
   const uint32_t staged = static_cast<uint32_t>(slot.size());
   if (staged == 0 || ctx->n == 0) return MCL_OK;
-  double* const block = ctx->d_beam_skip.ptr;
+  double* const block = ctx->beam_skip.block.ptr;
   uint32_t* const d_counts = reinterpret_cast<uint32_t*>(block + lay.counts);
   MCL_HIP(ctx, hipMemcpyAsync(block + lay.points, h_points, 2 * static_cast<size_t>(staged) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   const FieldPosePlan poses = field_pose_plan(ctx->tuning, ctx->d_field_pose.ptr != nullptr, ctx->facts, ctx->map_generation);
   const bool ahead = poses.load && !poses.rebuild_first;
-  *launches = launch_beam_agreement(ctx->stream, ahead ? ctx->d_field_pose.ptr : ctx->cur().pose, ahead, ctx->n, ctx->field_view(), ctx->beam_skip_level(),
+  *launches = launch_beam_agreement(ctx->stream, ahead ? ctx->d_field_pose.ptr : ctx->cur().pose, ahead, ctx->n, ctx->field_view(), ctx->beam_skip.level(ctx->cfg.lf),
                                     block + lay.points, staged, d_counts);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("beam agreement: ") + hipGetErrorString(e));
-  uint32_t* const h_counts = reinterpret_cast<uint32_t*>(ctx->h_beam_skip.host + lay.counts);
+  uint32_t* const h_counts = reinterpret_cast<uint32_t*>(ctx->beam_skip.pinned.host + lay.counts);
   MCL_HIP(ctx, hipMemcpyAsync(h_counts, d_counts, static_cast<size_t>(staged) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (uint32_t k = 0; k < staged; ++k) counts[slot[k]] = h_counts[k];
@@ -1163,24 +1151,24 @@ mcl_status beam_skip_select(mcl_ctx* ctx, Measurement* m) {
   stage_begin(ctx, MCL_STAGE_REWEIGHT);
   if (ctx->n == 0) return MCL_OK;
   const uint64_t B = m->doubles / 2;
-  ctx->beam_skip_counts.resize(B);
-  ctx->beam_skip_kept.resize(B);
+  ctx->beam_skip.counts.resize(B);
+  ctx->beam_skip.kept.resize(B);
   uint32_t launches = 0;
-  if (const mcl_status s = beam_skip_count(ctx, m->data, B, ctx->beam_skip_counts.data(), &launches)) return s;
-  ctx->beam_skip_launches += launches;
-  const BeamSkipDecision d = beam_skip_decide(ctx->beam_skip_counts.data(), B, ctx->n, ctx->beam_skip.threshold, ctx->beam_skip.error_threshold,
-                                              ctx->beam_skip_kept.data());
-  ctx->beam_skip_last = mcl_beam_skip_result{1, d.used_all ? 1 : 0, B, ctx->n, d.skipped, static_cast<double>(ctx->beam_skip_level())};
+  if (const mcl_status s = beam_skip_count(ctx, m->data, B, ctx->beam_skip.counts.data(), &launches)) return s;
+  ctx->beam_skip.launches += launches;
+  const BeamSkipDecision d = beam_skip_decide(ctx->beam_skip.counts.data(), B, ctx->n, ctx->beam_skip.params.threshold, ctx->beam_skip.params.error_threshold,
+                                              ctx->beam_skip.kept.data());
+  ctx->beam_skip.last = mcl_beam_skip_result{1, d.used_all ? 1 : 0, B, ctx->n, d.skipped, static_cast<double>(ctx->beam_skip.level(ctx->cfg.lf))};
   if (d.used_all) {
-    ctx->beam_skip_used_all += 1;
+    ctx->beam_skip.used_all += 1;
     return MCL_OK;
   }
   if (d.skipped == 0) return MCL_OK;
-  std::vector<double>& kept = ctx->beam_skip_points;
+  std::vector<double>& kept = ctx->beam_skip.points;
   kept.clear();
   kept.reserve(2 * (B - d.skipped));
   for (uint64_t b = 0; b < B; ++b) {
-    if (!ctx->beam_skip_kept[b]) continue;
+    if (!ctx->beam_skip.kept[b]) continue;
     kept.push_back(m->data[2 * b]);
     kept.push_back(m->data[2 * b + 1]);
   }
@@ -1219,7 +1207,7 @@ void plan_reweight_lf(mcl_ctx* ctx, ReweightStep* step) {
 // What the predicates of batch_host.h read of a member, family by family.
 BatchMemberFacts batch_lf_facts(const mcl_ctx* ctx, const LfReweightArgs& lf) {
   return BatchMemberFacts{ctx->cfg.sensor_kind, ctx->sharded(), ctx->tuning.small_fused != 0, ctx->n, ctx->max_live(),
-                          lf_takes_beams(lf, ctx->tuning), ctx->profile != 0, ctx->beam_skip_on()};
+                          lf_takes_beams(lf, ctx->tuning), ctx->profile != 0, ctx->beam_skip.on()};
 }
 BatchBeamFacts batch_beam_facts(const mcl_ctx* ctx) {
   return BatchBeamFacts{ctx->cfg.sensor_kind, ctx->sharded(), ctx->tuning.small_fused != 0, ctx->tuning.batch_beam_fused != 0, ctx->n, ctx->max_live(),
@@ -1243,7 +1231,7 @@ void decide_hold(mcl_ctx* ctx, const ReweightStep& step) {
     case SensorFamily::kLikelihoodField: hold->fused = batch_member_fused(batch_lf_facts(ctx, step.lf)); break;
     // (the wave-per-particle kernel, i.e. no ordering - `ordered` is the same question asked of the planner)
     // (a member with a range table runs its own cycle: the fleet's shared kernel walks)
-    case SensorFamily::kBeam: hold->fused = !step.ordered && ctx->range_angles == 0 && batch_beam_member_fused(batch_beam_facts(ctx)); break;
+    case SensorFamily::kBeam: hold->fused = !step.ordered && !ctx->range.built() && batch_beam_member_fused(batch_beam_facts(ctx)); break;
     case SensorFamily::kNdt: hold->fused = batch_ndt_member_fused(batch_ndt_facts(ctx)); break;
     case SensorFamily::kLandmark: hold->fused = batch_landmark_member_fused(batch_landmark_facts(ctx)); break;
   }
@@ -1280,49 +1268,44 @@ void reweight_lf(mcl_ctx* ctx, const ReweightStep& step) {
   }
   stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
 }
+// d_beam_table for the current map, built by the first launch that wants it.  who: the error's prefix.
+mcl_status ensure_beam_table(mcl_ctx* ctx, const BeamModel& model, const char* who) {
+  if (ctx->beam_table_ready) return MCL_OK;
+  hipError_t e = ctx->d_beam_table.ensure(4 * static_cast<size_t>(ctx->beam_table_count));
+  if (e == hipSuccess) {
+    launch_beam_table(ctx->stream, model, ctx->map->resolution, ctx->beam_table_count, ctx->d_beam_table.ptr);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string(who) + " (beam table): " + hipGetErrorString(e));
+  ctx->beam_table_ready = true;
+  return MCL_OK;
+}
 // What the kernels over the range table need beside it (the reweight and mcl_likelihoods*): the BeamTable of the current map, where the
 // reach allows one and option beam_table is on (*table_count = 0 otherwise: the lanes evaluate the entries themselves, the same bits),
 // and the scan's per-beam entries from the B points at d_points.
 mcl_status range_table_stage(mcl_ctx* ctx, const BeamModel& model, const double* d_points, uint32_t B, uint32_t* table_count) {
   *table_count = ctx->tuning.beam_table != 0 ? ctx->beam_table_count : 0u;
-  if (*table_count && !ctx->beam_table_ready) {
-    hipError_t e = ctx->d_beam_table.ensure(4 * static_cast<size_t>(ctx->beam_table_count));
-    if (e == hipSuccess) {
-      launch_beam_table(ctx->stream, model, ctx->map->resolution, ctx->beam_table_count, ctx->d_beam_table.ptr);
-      e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("range table (beam table): ") + hipGetErrorString(e));
-    ctx->beam_table_ready = true;
-  }
-  if (const hipError_t e = ctx->d_lut_points.ensure(static_cast<size_t>(kBeamLutPointDoubles) * std::max<uint32_t>(B, 1u)); e != hipSuccess)
+  if (const mcl_status s = *table_count ? ensure_beam_table(ctx, model, "range table") : MCL_OK) return s;
+  if (const hipError_t e = ctx->range.lut_points.ensure(static_cast<size_t>(kBeamLutPointDoubles) * std::max<uint32_t>(B, 1u)); e != hipSuccess)
     return fail(ctx, e == hipErrorOutOfMemory ? MCL_ERR_OUT_OF_MEMORY : MCL_ERR_HIP, std::string("range table (scan entries): ") + hipGetErrorString(e));
-  launch_beam_lut_points(ctx->stream, d_points, B, model, ctx->d_lut_points.ptr);
+  launch_beam_lut_points(ctx->stream, d_points, B, model, ctx->range.lut_points.ptr);
   return MCL_OK;
 }
 // Not MCL_OK: the table of the ordered kernel could not be built (nothing was launched; the caller closes its stage).
 mcl_status reweight_beam(mcl_ctx* ctx, const ReweightStep& step) {
-  const mcl_beam_params& b = ctx->cfg.beam;
-  const BeamModel model{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range};
-  if (ctx->range_angles != 0) {  // the range table serves every set size; never held (decide_hold), nothing walked, no cell counted
+  const BeamModel model = ctx->beam_model();
+  if (ctx->range.built()) {  // the range table serves every set size; never held (decide_hold), nothing walked, no cell counted
     uint32_t table_count = 0;
     if (const mcl_status s = range_table_stage(ctx, model, ctx->d_points.ptr, static_cast<uint32_t>(step.B), &table_count)) return s;
     stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
-    launch_reweight_beam_lut(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model, RangeTableView{ctx->d_range_table.ptr, ctx->range_angles},
-                             table_count ? ctx->d_beam_table.ptr : nullptr, table_count, ctx->d_lut_points.ptr, static_cast<uint32_t>(step.B));
-    if (ctx->n != 0 && step.B != 0) ctx->range_lut_launches += 1;  // (the launcher's own test)
+    launch_reweight_beam_lut(ctx->stream, ctx->cur(), ctx->n, ctx->grid_view(), model, ctx->range.view(),
+                             table_count ? ctx->d_beam_table.ptr : nullptr, table_count, ctx->range.lut_points.ptr, static_cast<uint32_t>(step.B));
+    if (ctx->n != 0 && step.B != 0) ctx->range.lut_launches += 1;  // (the launcher's own test)
     stage_end(ctx, MCL_STAGE_SENSOR_KERNEL);
     return MCL_OK;
   }
   const bool use_table = step.ordered && ctx->tuning.beam_table != 0 && ctx->beam_table_count != 0;  // (only the ordered kernel reads it)
-  if (use_table && !ctx->beam_table_ready) {
-    hipError_t e = ctx->d_beam_table.ensure(4 * static_cast<size_t>(ctx->beam_table_count));
-    if (e == hipSuccess) {
-      launch_beam_table(ctx->stream, model, ctx->map->resolution, ctx->beam_table_count, ctx->d_beam_table.ptr);
-      e = hipGetLastError();
-    }
-    if (e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("reweight (beam table): ") + hipGetErrorString(e));
-    ctx->beam_table_ready = true;
-  }
+  if (const mcl_status s = use_table ? ensure_beam_table(ctx, model, "reweight") : MCL_OK) return s;
   stage_begin(ctx, MCL_STAGE_SENSOR_KERNEL);
   if (step.held) {  // (never ordered, so no table was built above)
     step.hold->item.B = static_cast<uint32_t>(step.B);
@@ -1382,8 +1365,8 @@ mcl_status do_reweight(mcl_ctx* ctx, Measurement m, bool points_staged = false, 
   if (!points_staged) {
     if (const mcl_status s = stage_points(ctx, &m)) return s;
     if (m.doubles) {
-      launch_pull_scan(ctx->stream, ctx->h_points.device, ctx->d_points.ptr, static_cast<uint32_t>(m.doubles));
-      points_pulled(ctx, true);
+      launch_pull_scan(ctx->stream, ctx->h_points.buf.device, ctx->d_points.ptr, static_cast<uint32_t>(m.doubles));
+      (void)ctx->h_points.used(ctx->stream, /*with_event=*/true);  // (a stage-level call may return before the stream is synchronised)
     }
   }
   if (!stage_open) stage_begin(ctx, MCL_STAGE_REWEIGHT);
@@ -2697,7 +2680,6 @@ mcl_status mcl_create(const mcl_config* cfg, mcl_ctx** out) {
     MCL_HIP(ctx, ctx->h_kld_scalars.ensure(8, /*mapped=*/false));
     for (auto& pair : ctx->ev)
       for (auto& e : pair) MCL_HIP(ctx, hipEventCreate(&e));
-    MCL_HIP(ctx, hipEventCreateWithFlags(&ctx->points_event, hipEventDisableTiming));
     MCL_HIP(ctx, configure_device_kernels());
     {  // the device's compute units: the queue form of the LF patch kernel launches three workgroups per CU
       int count = 0;
@@ -2727,14 +2709,11 @@ void mcl_destroy(mcl_ctx* ctx) {
   if (ctx->rccl_comm) {
     if (RcclApi* api = rccl_api(nullptr)) (void)api->CommDestroy(ctx->rccl_comm);
   }
-  if (ctx->points_event) (void)hipEventDestroy(ctx->points_event);
-  if (ctx->likelihoods_event) (void)hipEventDestroy(ctx->likelihoods_event);
-  if (ctx->cast_event) (void)hipEventDestroy(ctx->cast_event);
   for (auto& pair : ctx->ev)
     for (auto& e : pair)
       if (e) (void)hipEventDestroy(e);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  // Every buffer is a member that frees itself (DeviceBuffer, HostBuffer, the map's hold: a private store frees its buffers, a shared
+  // Every buffer is a member that frees itself (DeviceBuffer, HostBuffer, StagedUpload with its event, the map's hold: a private store frees its buffers, a shared
   // one loses a user).  Relied on: the device is bound, and the stream was idle before it went - freeing memory takes no stream.
   delete ctx;
 }
@@ -2826,12 +2805,6 @@ namespace {
 // The host rule is range_table_host.cpp's.  Everything is checked before anything is allocated; the table is built into buffers of its own,
 // behind whatever the stream holds, and installed once the build has run through: a refusal or a failure leaves the context's table, if
 // it has one, as it was.  The build synchronises the stream (a table is built once per map, and a failed build must be seen here).
-void range_table_drop(mcl_ctx* ctx) {
-  ctx->d_range_table.release();
-  ctx->d_range_bearings.release();
-  ctx->range_bearings.clear();
-  ctx->range_angles = ctx->range_width = ctx->range_height = 0;
-}
 mcl_status range_table_build(mcl_ctx* ctx, uint32_t num_angles, const char* who) {
   if (!ctx->off_grid() && !ctx->have_map && ctx->cfg.sensor_kind == MCL_SENSOR_BEAM) return fail(ctx, MCL_ERR_NOT_READY, std::string(who) + ": no map set");
   const char* what = nullptr;
@@ -2866,24 +2839,24 @@ mcl_status range_table_build(mcl_ctx* ctx, uint32_t num_angles, const char* who)
     return fail(ctx, MCL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
   }
   // (the stream is idle: nothing reads the table this one replaces)
-  ctx->d_range_table.take(table);
-  ctx->d_range_bearings.take(cs);
-  ctx->range_bearings.swap(bearings);
-  ctx->range_angles = num_angles;
-  ctx->range_width = ctx->map->W;
-  ctx->range_height = ctx->map->H;
-  ctx->range_builds += 1;
+  ctx->range.table.take(table);
+  ctx->range.d_bearings.take(cs);
+  ctx->range.bearings.swap(bearings);
+  ctx->range.angles = num_angles;
+  ctx->range.width = ctx->map->W;
+  ctx->range.height = ctx->map->H;
+  ctx->range.builds += 1;
   return MCL_OK;
 }
 // Whatever has just installed a map (mcl_set_map, the swap of mcl_set_map_async's, mcl_use_shared_map): a context with a table builds
 // the new map's inside that call, so that it never walks silently; a rebuild that fails drops the table - the filter is on the exact
 // walk again - and its status is the call's.
 mcl_status range_table_follow_map(mcl_ctx* ctx) {
-  if (ctx->range_angles == 0) return MCL_OK;
-  const uint32_t num_angles = ctx->range_angles;
-  ctx->range_angles = 0;  // (the old map's table is not this map's, whatever happens below)
+  if (!ctx->range.built()) return MCL_OK;
+  const uint32_t num_angles = ctx->range.angles;
+  ctx->range.angles = 0;  // (the old map's table is not this map's, whatever happens below)
   const mcl_status s = range_table_build(ctx, num_angles, "range table (rebuilt for the new map)");
-  if (s != MCL_OK) range_table_drop(ctx);
+  if (s != MCL_OK) ctx->range.release();
   return s;
 }
 
@@ -3172,7 +3145,7 @@ mcl_status mcl_reweight(mcl_ctx* ctx, const double* points_xy, uint64_t num_poin
     if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
     return do_reweight(ctx, ndt_fit_scan(ctx, points_xy, num_points));
   }
-  if (ctx->beam_skip_on()) {  // the vote first, then the reweight with the scan it leaves
+  if (ctx->beam_skip.on()) {  // the vote first, then the reweight with the scan it leaves
     if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
     Measurement m = scan_measurement(points_xy, num_points);
     if (const mcl_status s = beam_skip_select(ctx, &m)) return s;
@@ -3381,7 +3354,7 @@ static mcl_status update_cycle(mcl_ctx* ctx, const double control_pose[4], Measu
   if (ctx->family() == SensorFamily::kNdt) m = ndt_fit_scan(ctx, m.data, m.doubles / 2);  // the scan's measurement cells are what the cycle uploads
   // Beam skipping: the scan the reweight stages is known only behind the propagation - the cycle takes the stage-level form of both,
   // mcl_propagate and mcl_reweight, with the vote between them (beam_skip_select), and runs as its own inside a batch.
-  const bool skipping = ctx->beam_skip_on();
+  const bool skipping = ctx->beam_skip.on();
   if (skipping) {
     hold = nullptr;
     if (const mcl_status s = beam_skip_reserve(ctx, m.doubles / 2)) return s;
@@ -4400,9 +4373,6 @@ constexpr Counter kCounters[] = {
     {"order_ahead_used", &mcl_ctx::order_ahead_used},
     {"order_ahead_missed", &mcl_ctx::order_ahead_missed},
     {"field_pose_rebuilds", &mcl_ctx::field_pose_rebuilds},
-    {"beam_skip_launches", &mcl_ctx::beam_skip_launches},
-    {"beam_skip_used_all", &mcl_ctx::beam_skip_used_all},
-    {"beam_agreement_calls", &mcl_ctx::beam_agreement_calls},
     {"host_cycles", &mcl_ctx::host_cycles},
     {"cluster_cells", &mcl_ctx::cluster_cells},
     {"comm_bytes_out", &mcl_ctx::comm_bytes_out},
@@ -4430,6 +4400,9 @@ mcl_status mcl_get_counter(mcl_ctx* ctx, const char* name, uint64_t* value) {
     patch_totals(ctx, &planned, &through, /*synchronised=*/true);
     *value = key == "lf_patch_groups_planned" ? planned : through;
   }
+  else if (key == "beam_skip_launches") *value = ctx->beam_skip.launches;
+  else if (key == "beam_skip_used_all") *value = ctx->beam_skip.used_all;
+  else if (key == "beam_agreement_calls") *value = ctx->beam_skip.agreement_calls;
   else if (key == "host_ns_to_first_launch") *value = ctx->host_ns[0];
   else if (key == "host_ns_other_launches") *value = ctx->host_ns[1];
   else if (key == "host_ns_wait") *value = ctx->host_ns[2];
@@ -4482,7 +4455,7 @@ mcl_status mcl_debug_last_sampler(mcl_ctx* ctx, double out[9]) {
 mcl_status mcl_comm_attach(mcl_ctx* ctx, uint32_t rank, uint32_t world, const mcl_transport* transport) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach: the NDT, landmark and bearing models run on one device");
-  if (world > 1 && ctx->beam_skip_on())  // (before any collective: the ranks' counts are not exchanged yet)
+  if (world > 1 && ctx->beam_skip.on())  // (before any collective: the ranks' counts are not exchanged yet)
     return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach: beam skipping is enabled, and a sharded filter does not vote yet (mcl_set_beam_skip)");
   MCL_REQUIRE(ctx, world >= 1 && world <= 64 && rank < world, "mcl_comm_attach: world must be 1..64, rank < world");
   MCL_REQUIRE(ctx, world == 1 || (transport && transport->all_gather && transport->all_to_all), "mcl_comm_attach: incomplete transport");
@@ -4518,7 +4491,7 @@ mcl_status mcl_comm_unique_id(uint8_t id[128]) {
 mcl_status mcl_comm_attach_rccl(mcl_ctx* ctx, const uint8_t id[128], uint32_t rank, uint32_t world) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach_rccl: the NDT, landmark and bearing models run on one device");
-  if (world > 1 && ctx->beam_skip_on())  // (before the communicator is made: ncclCommInitRank is a collective)
+  if (world > 1 && ctx->beam_skip.on())  // (before the communicator is made: ncclCommInitRank is a collective)
     return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_comm_attach_rccl: beam skipping is enabled, and a sharded filter does not vote yet (mcl_set_beam_skip)");
   MCL_REQUIRE(ctx, id && world >= 1 && world <= 64 && rank < world, "mcl_comm_attach_rccl: bad argument");
   std::string error;
@@ -4798,27 +4771,21 @@ static mcl_status likelihoods_check_poses(mcl_ctx* ctx, const char* who, const d
     if (!std::isfinite(poses[i])) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, std::string(who) + ": pose " + std::to_string(i / 4) + " has a value that is not finite");
   return MCL_OK;
 }
-// The points form: mcl_reweight's checks, and the scan as stage_points would stage it (into ctx->likelihoods_records).
+// The points form: mcl_reweight's checks, and the scan as stage_points would stage it (into ctx->likelihoods.records).
 static mcl_status likelihoods_points(mcl_ctx* ctx, const char* who, const double* points_xy, uint64_t num_points, LikelihoodsMeasurement* m) {
   if (ctx->is_landmark())
     return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": a landmark or bearing context takes mcl_likelihoods_landmarks / mcl_likelihoods_bearings");
   MCL_REQUIRE(ctx, num_points == 0 || points_xy, "null points");
   if (const mcl_status s = reweight_preconditions(ctx, num_points)) return s;
-  std::vector<double>& recs = ctx->likelihoods_records;
+  std::vector<double>& recs = ctx->likelihoods.records;
   *m = LikelihoodsMeasurement{nullptr, 0, 0};
   switch (ctx->family()) {
     case SensorFamily::kNdt:
       ndt_fit_cells(points_xy, num_points, ctx->ndt_resolution, recs);
       break;
     case SensorFamily::kLikelihoodField:  // a point with a NaN or infinite coordinate has no cell for any pose (stage_points)
-      recs.clear();
-      recs.reserve(2 * num_points);
-      for (uint64_t i = 0; i < num_points; ++i) {
-        const double x = points_xy[2 * i], y = points_xy[2 * i + 1];
-        if (!(std::isfinite(x) && std::isfinite(y))) continue;
-        recs.push_back(x);
-        recs.push_back(y);
-      }
+      recs.resize(2 * num_points);
+      recs.resize(2 * scan_finite_points(points_xy, num_points, recs.data()));
       m->no_cell = num_points - recs.size() / 2;
       break;
     case SensorFamily::kBeam:
@@ -4835,7 +4802,7 @@ static mcl_status likelihoods_points(mcl_ctx* ctx, const char* who, const double
 static mcl_status likelihoods_ndt_cells(mcl_ctx* ctx, const char* who, const double* means, const double* covs, uint64_t num_cells,
                                         LikelihoodsMeasurement* m) {
   if (!ctx->is_ndt()) return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the context's sensor model is not MCL_SENSOR_NDT");
-  std::vector<double>& recs = ctx->likelihoods_records;
+  std::vector<double>& recs = ctx->likelihoods.records;
   if (const mcl_status s = ndt_cell_records(ctx, who, means, covs, num_cells, recs)) return s;
   *m = LikelihoodsMeasurement{recs.data(), recs.size(), 0};
   return MCL_OK;
@@ -4846,30 +4813,24 @@ static mcl_status likelihoods_detections(mcl_ctx* ctx, const char* who, int32_t 
     return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the context's sensor model is not " + (kind == MCL_SENSOR_LANDMARK ? "MCL_SENSOR_LANDMARK" : "MCL_SENSOR_BEARING"));
   std::string error;
   if (const mcl_status s = landmark_records(who, kind, xyz, categories, k, ctx->have_landmark_map ? &ctx->landmark_ranges : nullptr,
-                                            ctx->likelihoods_records, &error))
+                                            ctx->likelihoods.records, &error))
     return fail(ctx, s, error);
   if (const mcl_status s = reweight_preconditions(ctx, 0)) return s;
-  *m = LikelihoodsMeasurement{ctx->likelihoods_records.data(), ctx->likelihoods_records.size(), 0};
+  *m = LikelihoodsMeasurement{ctx->likelihoods.records.data(), ctx->likelihoods.records.size(), 0};
   return MCL_OK;
 }
 // The measurement into the device block's measurement area, behind whatever the stream holds; n_host: the poses the block also takes.
 static mcl_status likelihoods_stage(mcl_ctx* ctx, const LikelihoodsMeasurement& m, uint64_t n_host, LikelihoodsLayout* layout) {
   const LikelihoodsLayout lay(n_host, m.doubles);
-  if (ctx->likelihoods_in_flight) {  // the previous call's copy may still be reading the staging memory
-    MCL_HIP(ctx, hipEventSynchronize(ctx->likelihoods_event));
-    ctx->likelihoods_in_flight = false;
-  }
-  if (lay.size > ctx->d_likelihoods.count) MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier call may still be using the block)
-  MCL_HIP(ctx, ctx->d_likelihoods.ensure(std::max<size_t>(lay.size, 4)));
+  MCL_HIP(ctx, ctx->likelihoods.meas.reserve(ctx->stream, m.doubles, /*mapped=*/false));  // (the previous call's copy may still be reading it)
+  if (lay.size > ctx->likelihoods.block.count) MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier call may still be using the block)
+  MCL_HIP(ctx, ctx->likelihoods.block.ensure(std::max<size_t>(lay.size, 4)));
   *layout = lay;
   if (m.doubles == 0) return MCL_OK;
-  MCL_HIP(ctx, ctx->h_likelihoods_meas.ensure(m.doubles, /*mapped=*/false));
-  std::copy(m.data, m.data + m.doubles, ctx->h_likelihoods_meas.host);
-  if (!ctx->likelihoods_event) MCL_HIP(ctx, hipEventCreateWithFlags(&ctx->likelihoods_event, hipEventDisableTiming));
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->d_likelihoods.ptr + lay.measurement, ctx->h_likelihoods_meas.host, m.doubles * sizeof(double), hipMemcpyHostToDevice,
+  std::copy(m.data, m.data + m.doubles, ctx->likelihoods.meas.buf.host);
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->likelihoods.block.ptr + lay.measurement, ctx->likelihoods.meas.buf.host, m.doubles * sizeof(double), hipMemcpyHostToDevice,
                               ctx->stream));
-  MCL_HIP(ctx, hipEventRecord(ctx->likelihoods_event, ctx->stream));
-  ctx->likelihoods_in_flight = true;
+  MCL_HIP(ctx, ctx->likelihoods.meas.used(ctx->stream, /*with_event=*/true));
   return MCL_OK;
 }
 // The family's kernel over n poses in device memory; the measurement lies staged at d_meas.  Reads the map through the views the
@@ -4886,18 +4847,17 @@ static mcl_status likelihoods_launch(mcl_ctx* ctx, const double* d_poses, uint64
       break;
     }
     case SensorFamily::kBeam: {
-      const mcl_beam_params& b = ctx->cfg.beam;
-      if (ctx->range_angles != 0 && !exact_walk) {  // the factor a reweight of this context would apply: over the table, as the cycle
-        const BeamModel model{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range};
+      const BeamModel model = ctx->beam_model();
+      if (ctx->range.built() && !exact_walk) {  // the factor a reweight of this context would apply: over the table, as the cycle
         const uint32_t B = static_cast<uint32_t>(m.doubles / 2);
         uint32_t table_count = 0;
         if (const mcl_status s = range_table_stage(ctx, model, d_meas, B, &table_count)) return s;
-        launch_likelihoods_beam_lut(ctx->stream, poses, n, ctx->grid_view(), model, RangeTableView{ctx->d_range_table.ptr, ctx->range_angles},
-                                    table_count ? ctx->d_beam_table.ptr : nullptr, table_count, ctx->d_lut_points.ptr, B, d_out);
+        launch_likelihoods_beam_lut(ctx->stream, poses, n, ctx->grid_view(), model, ctx->range.view(),
+                                    table_count ? ctx->d_beam_table.ptr : nullptr, table_count, ctx->range.lut_points.ptr, B, d_out);
         break;
       }
-      launch_likelihoods_beam(ctx->stream, poses, n, ctx->grid_view(), BeamModel{b.z_hit, b.z_short, b.z_max, b.z_rand, b.sigma_hit, b.lambda_short, b.beam_max_range},
-                              d_meas, static_cast<uint32_t>(m.doubles / 2), ctx->map->d_nonfree_bits.ptr, d_out);
+      launch_likelihoods_beam(ctx->stream, poses, n, ctx->grid_view(), model, d_meas, static_cast<uint32_t>(m.doubles / 2),
+                              ctx->map->d_nonfree_bits.ptr, d_out);
       break;
     }
     case SensorFamily::kNdt: {
@@ -4914,13 +4874,16 @@ static mcl_status likelihoods_launch(mcl_ctx* ctx, const double* d_poses, uint64
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("likelihoods: ") + hipGetErrorString(e));
   return MCL_OK;
 }
-// The host forms: poses up, scores down, one synchronisation at the end.  `out` is written by that last copy alone.
-static mcl_status likelihoods_host(mcl_ctx* ctx, const double* poses, uint64_t n, const LikelihoodsMeasurement& m, double* out) {
+// The host forms behind their measurement builder (its status `built`, its output m): the measurement is checked first, then the poses,
+// then the device is used - poses up, scores down, one synchronisation at the end.  `out` is written by that last copy alone.
+static mcl_status likelihoods_host(mcl_ctx* ctx, const char* who, mcl_status built, const LikelihoodsMeasurement& m, const double* poses, uint64_t n, double* out) {
+  if (built != MCL_OK) return built;
+  if (const mcl_status s = likelihoods_check_poses(ctx, who, poses, n, out)) return s;
   if (n == 0) return MCL_OK;
   if (const mcl_status s = bind_device(ctx)) return s;
   LikelihoodsLayout lay(0, 0);
   if (const mcl_status s = likelihoods_stage(ctx, m, n, &lay)) return s;
-  double* const block = ctx->d_likelihoods.ptr;
+  double* const block = ctx->likelihoods.block.ptr;
   MCL_HIP(ctx, hipMemcpyAsync(block + lay.poses, poses, n * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
   if (const mcl_status s = likelihoods_launch(ctx, block + lay.poses, n, m, block + lay.measurement, block + lay.out)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -4931,33 +4894,25 @@ static mcl_status likelihoods_host(mcl_ctx* ctx, const double* poses, uint64_t n
 mcl_status mcl_likelihoods(mcl_ctx* ctx, const double* poses, uint64_t n, const double* points_xy, uint64_t num_points, double* out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   LikelihoodsMeasurement m{};
-  if (const mcl_status s = likelihoods_points(ctx, "mcl_likelihoods", points_xy, num_points, &m)) return s;
-  if (const mcl_status s = likelihoods_check_poses(ctx, "mcl_likelihoods", poses, n, out)) return s;
-  return likelihoods_host(ctx, poses, n, m, out);
+  return likelihoods_host(ctx, "mcl_likelihoods", likelihoods_points(ctx, "mcl_likelihoods", points_xy, num_points, &m), m, poses, n, out);
 }
 mcl_status mcl_likelihoods_ndt_cells(mcl_ctx* ctx, const double* poses, uint64_t n, const double* means, const double* covs, uint64_t num_cells,
                                      double* out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   LikelihoodsMeasurement m{};
-  if (const mcl_status s = likelihoods_ndt_cells(ctx, "mcl_likelihoods_ndt_cells", means, covs, num_cells, &m)) return s;
-  if (const mcl_status s = likelihoods_check_poses(ctx, "mcl_likelihoods_ndt_cells", poses, n, out)) return s;
-  return likelihoods_host(ctx, poses, n, m, out);
+  return likelihoods_host(ctx, "mcl_likelihoods_ndt_cells", likelihoods_ndt_cells(ctx, "mcl_likelihoods_ndt_cells", means, covs, num_cells, &m), m, poses, n, out);
 }
 mcl_status mcl_likelihoods_landmarks(mcl_ctx* ctx, const double* poses, uint64_t n, const double* positions_xyz, const uint32_t* categories,
                                      uint64_t k, double* out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   LikelihoodsMeasurement m{};
-  if (const mcl_status s = likelihoods_detections(ctx, "mcl_likelihoods_landmarks", MCL_SENSOR_LANDMARK, positions_xyz, categories, k, &m)) return s;
-  if (const mcl_status s = likelihoods_check_poses(ctx, "mcl_likelihoods_landmarks", poses, n, out)) return s;
-  return likelihoods_host(ctx, poses, n, m, out);
+  return likelihoods_host(ctx, "mcl_likelihoods_landmarks", likelihoods_detections(ctx, "mcl_likelihoods_landmarks", MCL_SENSOR_LANDMARK, positions_xyz, categories, k, &m), m, poses, n, out);
 }
 mcl_status mcl_likelihoods_bearings(mcl_ctx* ctx, const double* poses, uint64_t n, const double* bearings_xyz, const uint32_t* categories,
                                     uint64_t k, double* out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   LikelihoodsMeasurement m{};
-  if (const mcl_status s = likelihoods_detections(ctx, "mcl_likelihoods_bearings", MCL_SENSOR_BEARING, bearings_xyz, categories, k, &m)) return s;
-  if (const mcl_status s = likelihoods_check_poses(ctx, "mcl_likelihoods_bearings", poses, n, out)) return s;
-  return likelihoods_host(ctx, poses, n, m, out);
+  return likelihoods_host(ctx, "mcl_likelihoods_bearings", likelihoods_detections(ctx, "mcl_likelihoods_bearings", MCL_SENSOR_BEARING, bearings_xyz, categories, k, &m), m, poses, n, out);
 }
 mcl_status mcl_likelihoods_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* points_xy, uint64_t num_points, double* d_out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
@@ -4968,7 +4923,7 @@ mcl_status mcl_likelihoods_device(mcl_ctx* ctx, const double* d_poses, uint64_t 
   if (const mcl_status s = bind_device(ctx)) return s;
   LikelihoodsLayout lay(0, 0);
   if (const mcl_status s = likelihoods_stage(ctx, m, 0, &lay)) return s;
-  return likelihoods_launch(ctx, d_poses, n, m, ctx->d_likelihoods.ptr + lay.measurement, d_out);
+  return likelihoods_launch(ctx, d_poses, n, m, ctx->likelihoods.block.ptr + lay.measurement, d_out);
 }
 
 // ---- global pose search: every free cell and heading scored by likelihoods_launch, the best kept (DESIGN.md "Global pose search") --------
@@ -4981,6 +4936,7 @@ struct SearchCall {
   SearchLayout lay;
   SearchScratch scratch;
   uint32_t launches;
+  std::vector<double> headings;  // search_heading_table: (cos, sin) per heading, as the device was given it
 };
 static mcl_status search_check(mcl_ctx* ctx, const char* who, const mcl_search_params* params, mcl_search_params* p) {
   if (ctx->off_grid()) return fail(ctx, MCL_ERR_UNSUPPORTED, std::string(who) + ": the search goes over the free cells of an occupancy grid (likelihood-field and beam contexts)");
@@ -4992,38 +4948,38 @@ static mcl_status search_check(mcl_ctx* ctx, const char* who, const mcl_search_p
 static mcl_status search_begin(mcl_ctx* ctx, const mcl_search_params& p, SearchCall* call) {
   const SearchPlan plan = search_plan(ctx->map->n_free, p.headings, ctx->tuning.search_chunk);
   const SearchLayout lay(p.headings, plan.cells_per_chunk, plan.chunk_candidates, plan.tiles, kSearchTile, kSearchMaxPool);
-  MCL_HIP(ctx, ctx->d_search_f64.ensure(lay.f64_size));
-  MCL_HIP(ctx, ctx->d_search_u64.ensure(lay.u64_size));
-  MCL_HIP(ctx, ctx->d_search_u32.ensure(lay.u32_size));
-  MCL_HIP(ctx, ctx->h_search.ensure(lay.h_size, /*mapped=*/false));
+  MCL_HIP(ctx, ctx->search.f64.ensure(lay.f64_size));
+  MCL_HIP(ctx, ctx->search.u64.ensure(lay.u64_size));
+  MCL_HIP(ctx, ctx->search.u32.ensure(lay.u32_size));
+  MCL_HIP(ctx, ctx->search.pinned.ensure(lay.h_size, /*mapped=*/false));
   std::vector<double> table;
   search_heading_table(p.headings, table);
-  std::memcpy(ctx->h_search.host + lay.h_table, table.data(), table.size() * sizeof(double));
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->d_search_f64.ptr + lay.table, ctx->h_search.host + lay.h_table, table.size() * sizeof(double), hipMemcpyHostToDevice,
+  std::memcpy(ctx->search.pinned.host + lay.h_table, table.data(), table.size() * sizeof(double));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->search.f64.ptr + lay.table, ctx->search.pinned.host + lay.h_table, table.size() * sizeof(double), hipMemcpyHostToDevice,
                               ctx->stream));
-  unsigned long long* const u64 = ctx->d_search_u64.ptr;
+  unsigned long long* const u64 = ctx->search.u64.ptr;
   *call = SearchCall{p, plan, lay, SearchScratch{{u64 + lay.run_keys[0], u64 + lay.run_keys[1]}, {u64 + lay.run_ids[0], u64 + lay.run_ids[1]},
-                                                   {u64 + lay.pool_keys[0], u64 + lay.pool_keys[1]}, {u64 + lay.pool_ids[0], u64 + lay.pool_ids[1]}}, 0};
+                                                   {u64 + lay.pool_keys[0], u64 + lay.pool_keys[1]}, {u64 + lay.pool_ids[0], u64 + lay.pool_ids[1]}}, 0, std::move(table)};
   return MCL_OK;
 }
 // Chunk c's candidate cells into the `selected` area; *cells = their number, read behind the call's synchronisation of this chunk.
 static mcl_status search_select_chunk(mcl_ctx* ctx, SearchCall* call, uint32_t c, uint32_t* cells) {
   const uint64_t first = static_cast<uint64_t>(c) * call->plan.cells_per_chunk;
   const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(call->plan.cells_per_chunk, ctx->map->n_free - first));
-  uint32_t* const u32 = ctx->d_search_u32.ptr;
+  uint32_t* const u32 = ctx->search.u32.ptr;
   call->launches += launch_search_select(ctx->stream, ctx->map->d_free.ptr + first, count, ctx->map->W, call->p.cell_stride, u32 + call->lay.selected,
                                          u32 + call->lay.count);
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_search.host + call->lay.h_count, u32 + call->lay.count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->search.pinned.host + call->lay.h_count, u32 + call->lay.count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(cells, ctx->h_search.host + call->lay.h_count, sizeof(uint32_t));
+  std::memcpy(cells, ctx->search.pinned.host + call->lay.h_count, sizeof(uint32_t));
   if (*cells > count) return fail(ctx, MCL_ERR_HIP, "global search: the chunk's cell count is beyond its range");
   return MCL_OK;
 }
 static mcl_status search_generate_chunk(mcl_ctx* ctx, SearchCall* call, uint32_t cells) {
   const MapStore& map = *ctx->map;
-  call->launches += launch_search_poses(ctx->stream, ctx->d_search_u32.ptr + call->lay.selected, cells, call->p.headings, ctx->d_search_f64.ptr + call->lay.table,
-                                        SearchGrid{map.W, map.resolution, map.origin}, reinterpret_cast<double4*>(ctx->d_search_f64.ptr + call->lay.poses),
-                                        ctx->d_search_u64.ptr + call->lay.ids);
+  call->launches += launch_search_poses(ctx->stream, ctx->search.u32.ptr + call->lay.selected, cells, call->p.headings, ctx->search.f64.ptr + call->lay.table,
+                                        SearchGrid{map.W, map.resolution, map.origin}, reinterpret_cast<double4*>(ctx->search.f64.ptr + call->lay.poses),
+                                        ctx->search.u64.ptr + call->lay.ids);
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("global search: ") + hipGetErrorString(e));
   return MCL_OK;
 }
@@ -5038,14 +4994,13 @@ static void search_hit_from(const mcl_ctx* ctx, const mcl_search_params& p, cons
   search_cell_position(hit->cell, map.W, map.resolution, map.origin, hit->pose[2], hit->pose[3]);
 }
 // A device error in the middle of a call (MCL_ERR_HIP, MCL_ERR_OUT_OF_MEMORY: the only statuses that arise once the device is in use) may
-// leave the call's work on the stream: wait for it, so that the next call finds h_search and d_search_* idle, as after every other return.
-static mcl_status search_settled(mcl_ctx* ctx, mcl_status s) {
+// leave a query call's work on the stream: wait for it, so that the next call finds the call's own buffers idle, as after every other return.
+static mcl_status settled_after_device_error(mcl_ctx* ctx, mcl_status s) {
   if (s == MCL_ERR_HIP || s == MCL_ERR_OUT_OF_MEMORY) (void)hipStreamSynchronize(ctx->stream);
   return s;
 }
 static mcl_status global_search(mcl_ctx* ctx, const char* who, const double* points_xy, uint64_t num_points, const mcl_search_params* params,
                                 mcl_search_hit* hits, uint64_t capacity, uint64_t* count, mcl_search_info* info, bool suppress) {
-  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   mcl_search_params p{};
   if (const mcl_status s = search_check(ctx, who, params, &p)) return s;
   MCL_REQUIRE(ctx, hits && count, std::string(who) + ": null argument");
@@ -5057,8 +5012,8 @@ static mcl_status global_search(mcl_ctx* ctx, const char* who, const double* poi
   if (const mcl_status s = search_begin(ctx, p, &call)) return s;
   LikelihoodsLayout meas(0, 0);
   if (const mcl_status s = likelihoods_stage(ctx, m, 0, &meas)) return s;
-  double* const f64 = ctx->d_search_f64.ptr;
-  unsigned long long* const u64 = ctx->d_search_u64.ptr;
+  double* const f64 = ctx->search.f64.ptr;
+  unsigned long long* const u64 = ctx->search.u64.ptr;
   uint64_t cells_total = 0;
   uint32_t pool_len = 0;
   int pool_at = 0;
@@ -5068,7 +5023,7 @@ static mcl_status global_search(mcl_ctx* ctx, const char* who, const double* poi
     if (cells == 0) continue;
     if (const mcl_status s = search_generate_chunk(ctx, &call, cells)) return s;
     const uint64_t n = static_cast<uint64_t>(cells) * p.headings;
-    if (const mcl_status s = likelihoods_launch(ctx, f64 + call.lay.poses, n, m, ctx->d_likelihoods.ptr + meas.measurement, f64 + call.lay.scores,
+    if (const mcl_status s = likelihoods_launch(ctx, f64 + call.lay.poses, n, m, ctx->likelihoods.block.ptr + meas.measurement, f64 + call.lay.scores,
                                                 /*exact_walk=*/true)) return s;
     call.launches += 1;
     call.launches += launch_search_pool(ctx->stream, f64 + call.lay.scores, u64 + call.lay.ids, n, call.scratch, p.pool, pool_len, &pool_at);
@@ -5077,17 +5032,15 @@ static mcl_status global_search(mcl_ctx* ctx, const char* who, const double* poi
     cells_total += cells;
   }
   if (pool_len) {
-    MCL_HIP(ctx, hipMemcpyAsync(ctx->h_search.host + call.lay.h_pool_keys, call.scratch.pool_keys[pool_at], pool_len * sizeof(unsigned long long),
+    MCL_HIP(ctx, hipMemcpyAsync(ctx->search.pinned.host + call.lay.h_pool_keys, call.scratch.pool_keys[pool_at], pool_len * sizeof(unsigned long long),
                                 hipMemcpyDeviceToHost, ctx->stream));
-    MCL_HIP(ctx, hipMemcpyAsync(ctx->h_search.host + call.lay.h_pool_ids, call.scratch.pool_ids[pool_at], pool_len * sizeof(unsigned long long),
+    MCL_HIP(ctx, hipMemcpyAsync(ctx->search.pinned.host + call.lay.h_pool_ids, call.scratch.pool_ids[pool_at], pool_len * sizeof(unsigned long long),
                                 hipMemcpyDeviceToHost, ctx->stream));
   }
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<double> table;
-  search_heading_table(p.headings, table);
   std::vector<mcl_search_hit> pool(pool_len);
   for (uint32_t i = 0; i < pool_len; ++i)
-    search_hit_from(ctx, p, table, ctx->h_search.host[call.lay.h_pool_keys + i], ctx->h_search.host[call.lay.h_pool_ids + i], &pool[i]);
+    search_hit_from(ctx, p, call.headings, ctx->search.pinned.host[call.lay.h_pool_keys + i], ctx->search.pinned.host[call.lay.h_pool_ids + i], &pool[i]);
   if (suppress) {
     std::vector<uint32_t> kept(p.max_results);
     const uint64_t k = search_suppress(pool.data(), pool.size(), ctx->map->W, p, kept.data());
@@ -5104,12 +5057,12 @@ static mcl_status global_search(mcl_ctx* ctx, const char* who, const double* poi
 mcl_status mcl_global_search(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, const mcl_search_params* params, mcl_search_hit* hits,
                              uint64_t capacity, uint64_t* count, mcl_search_info* info) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  return search_settled(ctx, global_search(ctx, "mcl_global_search", points_xy, num_points, params, hits, capacity, count, info, /*suppress=*/true));
+  return settled_after_device_error(ctx, global_search(ctx, "mcl_global_search", points_xy, num_points, params, hits, capacity, count, info, /*suppress=*/true));
 }
 mcl_status mcl_global_search_pool(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, const mcl_search_params* params, mcl_search_hit* hits,
                                   uint64_t capacity, uint64_t* count, mcl_search_info* info) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  return search_settled(ctx, global_search(ctx, "mcl_global_search_pool", points_xy, num_points, params, hits, capacity, count, info, /*suppress=*/false));
+  return settled_after_device_error(ctx, global_search(ctx, "mcl_global_search_pool", points_xy, num_points, params, hits, capacity, count, info, /*suppress=*/false));
 }
 static mcl_status search_candidates(mcl_ctx* ctx, const mcl_search_params* params, uint64_t first_id_rank, uint64_t count, uint64_t* ids_out,
                                     double* poses_out, uint64_t* total) {
@@ -5136,8 +5089,8 @@ static mcl_status search_candidates(mcl_ctx* ctx, const mcl_search_params* param
       if (const mcl_status s = search_generate_chunk(ctx, &call, cells)) return s;
       ids.resize(n);
       poses.resize(4 * n);
-      MCL_HIP(ctx, hipMemcpyAsync(ids.data(), ctx->d_search_u64.ptr + call.lay.ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-      MCL_HIP(ctx, hipMemcpyAsync(poses.data(), ctx->d_search_f64.ptr + call.lay.poses, 4 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      MCL_HIP(ctx, hipMemcpyAsync(ids.data(), ctx->search.u64.ptr + call.lay.ids, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+      MCL_HIP(ctx, hipMemcpyAsync(poses.data(), ctx->search.f64.ptr + call.lay.poses, 4 * n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
       MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
       order.resize(n);
       std::iota(order.begin(), order.end(), 0u);
@@ -5159,7 +5112,7 @@ static mcl_status search_candidates(mcl_ctx* ctx, const mcl_search_params* param
 mcl_status mcl_global_search_candidates(mcl_ctx* ctx, const mcl_search_params* params, uint64_t first_id_rank, uint64_t count, uint64_t* ids_out,
                                         double* poses_out, uint64_t* total) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  return search_settled(ctx, search_candidates(ctx, params, first_id_rank, count, ids_out, poses_out, total));
+  return settled_after_device_error(ctx, search_candidates(ctx, params, first_id_rank, count, ids_out, poses_out, total));
 }
 
 // ---- ray casting as a function: the range the map predicts along caller-given bearings from caller-given poses (Ray2d::cast) ------------
@@ -5178,28 +5131,22 @@ static mcl_status cast_check(mcl_ctx* ctx, const char* who, const double* poses,
 }
 // The call's buffers; the bearings into the table behind whatever the stream holds, the far ends from them, the cell count zeroed.
 static mcl_status cast_begin(mcl_ctx* ctx, const double* bearings_cs, uint64_t num_bearings, double max_range, const RayCastLayout& lay) {
-  if (ctx->cast_in_flight) {  // the previous call's copy may still be reading the staging memory
-    MCL_HIP(ctx, hipEventSynchronize(ctx->cast_event));
-    ctx->cast_in_flight = false;
-  }
-  if (lay.size > ctx->d_cast.count) MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier call may still be using the block)
-  MCL_HIP(ctx, ctx->d_cast.ensure(lay.size));
-  MCL_HIP(ctx, ctx->h_cast.ensure(lay.h_size, /*mapped=*/false));
-  std::copy(bearings_cs, bearings_cs + 2 * num_bearings, ctx->h_cast.host + lay.h_table);
-  if (!ctx->cast_event) MCL_HIP(ctx, hipEventCreateWithFlags(&ctx->cast_event, hipEventDisableTiming));
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->d_cast.ptr + lay.table, ctx->h_cast.host + lay.h_table, 2 * num_bearings * sizeof(double), hipMemcpyHostToDevice,
+  MCL_HIP(ctx, ctx->cast.staged.reserve(ctx->stream, lay.h_size, /*mapped=*/false));  // (the previous call's copy may still be reading it)
+  if (lay.size > ctx->cast.block.count) MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier call may still be using the block)
+  MCL_HIP(ctx, ctx->cast.block.ensure(lay.size));
+  std::copy(bearings_cs, bearings_cs + 2 * num_bearings, ctx->cast.staged.buf.host + lay.h_table);
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->cast.block.ptr + lay.table, ctx->cast.staged.buf.host + lay.h_table, 2 * num_bearings * sizeof(double), hipMemcpyHostToDevice,
                               ctx->stream));
-  MCL_HIP(ctx, hipEventRecord(ctx->cast_event, ctx->stream));
-  ctx->cast_in_flight = true;
-  launch_cast_far_ends(ctx->stream, ctx->d_cast.ptr + lay.table, num_bearings, max_range);
-  MCL_HIP(ctx, hipMemsetAsync(ctx->d_cast.ptr + lay.count, 0, sizeof(unsigned long long), ctx->stream));
+  MCL_HIP(ctx, ctx->cast.staged.used(ctx->stream, /*with_event=*/true));
+  launch_cast_far_ends(ctx->stream, ctx->cast.block.ptr + lay.table, num_bearings, max_range);
+  MCL_HIP(ctx, hipMemsetAsync(ctx->cast.block.ptr + lay.count, 0, sizeof(unsigned long long), ctx->stream));
   return MCL_OK;
 }
 // The cell count of the call so far, behind a synchronisation of the stream.
 static mcl_status cast_read_count(mcl_ctx* ctx, const RayCastLayout& lay, uint64_t* cells_visited) {
-  MCL_HIP(ctx, hipMemcpyAsync(ctx->h_cast.host + lay.h_count, ctx->d_cast.ptr + lay.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->cast.staged.buf.host + lay.h_count, ctx->cast.block.ptr + lay.count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(cells_visited, ctx->h_cast.host + lay.h_count, sizeof(uint64_t));
+  std::memcpy(cells_visited, ctx->cast.staged.buf.host + lay.h_count, sizeof(uint64_t));
   return MCL_OK;
 }
 static mcl_status cast_rays_host(mcl_ctx* ctx, const double* poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
@@ -5214,7 +5161,7 @@ static mcl_status cast_rays_host(mcl_ctx* ctx, const double* poses, uint64_t n, 
   const CastPlan plan = cast_plan(n, num_bearings, static_cast<uint64_t>(ctx->tuning.cast_chunk));
   const RayCastLayout lay(num_bearings, plan.chunk_poses, std::min(plan.chunk_rays, plan.rays), hit_cells_out != nullptr);
   if (const mcl_status s = cast_begin(ctx, bearings_cs, num_bearings, max_range, lay)) return s;
-  double* const block = ctx->d_cast.ptr;
+  double* const block = ctx->cast.block.ptr;
   unsigned long long* const d_steps = cells_visited ? reinterpret_cast<unsigned long long*>(block + lay.count) : nullptr;
   int64_t* const d_hits = hit_cells_out ? reinterpret_cast<int64_t*>(block + lay.hits) : nullptr;
   for (uint64_t c = 0; c < plan.chunks; ++c) {  // poses up, rays cast, outputs down: the outputs are written by these last copies alone
@@ -5242,7 +5189,7 @@ static mcl_status cast_rays_device(mcl_ctx* ctx, const double* d_poses, uint64_t
   const CastPlan plan = cast_plan(n, num_bearings, kCastLaunchRays);  // (the outputs are the caller's: a chunk is what one launch holds)
   const RayCastLayout lay(num_bearings, 0, 0, false);
   if (const mcl_status s = cast_begin(ctx, bearings_cs, num_bearings, max_range, lay)) return s;
-  double* const block = ctx->d_cast.ptr;
+  double* const block = ctx->cast.block.ptr;
   unsigned long long* const d_steps = cells_visited ? reinterpret_cast<unsigned long long*>(block + lay.count) : nullptr;
   for (uint64_t c = 0; c < plan.chunks; ++c) {
     const CastChunk chunk = cast_chunk_at(plan, num_bearings, c);
@@ -5257,12 +5204,12 @@ static mcl_status cast_rays_device(mcl_ctx* ctx, const double* d_poses, uint64_t
 mcl_status mcl_cast_rays(mcl_ctx* ctx, const double* poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
                          double* ranges_out, int64_t* hit_cells_out, uint64_t* cells_visited) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  return search_settled(ctx, cast_rays_host(ctx, poses, n, bearings_cs, num_bearings, max_range, ranges_out, hit_cells_out, cells_visited));
+  return settled_after_device_error(ctx, cast_rays_host(ctx, poses, n, bearings_cs, num_bearings, max_range, ranges_out, hit_cells_out, cells_visited));
 }
 mcl_status mcl_cast_rays_device(mcl_ctx* ctx, const double* d_poses, uint64_t n, const double* bearings_cs, uint64_t num_bearings, double max_range,
                                 double* d_ranges_out, int64_t* d_hit_cells_out, uint64_t* cells_visited) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  return search_settled(ctx, cast_rays_device(ctx, d_poses, n, bearings_cs, num_bearings, max_range, d_ranges_out, d_hit_cells_out, cells_visited));
+  return settled_after_device_error(ctx, cast_rays_device(ctx, d_poses, n, bearings_cs, num_bearings, max_range, d_ranges_out, d_hit_cells_out, cells_visited));
 }
 
 // ---- the range table of the beam model: the C ABI (range_table_build and its kin stand with the map's installation) ----------------------
@@ -5272,38 +5219,38 @@ mcl_status mcl_build_range_table(mcl_ctx* ctx, uint32_t num_angles) {
 }
 mcl_status mcl_drop_range_table(mcl_ctx* ctx) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->range_angles == 0) return MCL_OK;
+  if (!ctx->range.built()) return MCL_OK;
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));  // nothing in flight reads the table any more
-  range_table_drop(ctx);
-  ctx->d_lut_points.release();
+  ctx->range.release();
+  ctx->range.lut_points.release();
   return MCL_OK;
 }
 mcl_status mcl_range_table_get_info(mcl_ctx* ctx, mcl_range_table_info* info) {
   if (!ctx || !info) return MCL_ERR_INVALID_ARGUMENT;
-  const bool built = ctx->range_angles != 0;
-  *info = mcl_range_table_info{built ? 1 : 0, ctx->range_angles, ctx->range_width, ctx->range_height,
-                               built ? static_cast<uint64_t>(ctx->range_width) * ctx->range_height * ctx->range_angles * sizeof(uint32_t) : 0,
-                               ctx->range_builds, ctx->range_lut_launches};
+  const bool built = ctx->range.built();
+  *info = mcl_range_table_info{built ? 1 : 0, ctx->range.angles, ctx->range.width, ctx->range.height,
+                               built ? static_cast<uint64_t>(ctx->range.width) * ctx->range.height * ctx->range.angles * sizeof(uint32_t) : 0,
+                               ctx->range.builds, ctx->range.lut_launches};
   return MCL_OK;
 }
 mcl_status mcl_range_table_bearings(mcl_ctx* ctx, double* cs_out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->range_angles == 0) return fail(ctx, MCL_ERR_NOT_READY, "mcl_range_table_bearings: no range table built");
+  if (!ctx->range.built()) return fail(ctx, MCL_ERR_NOT_READY, "mcl_range_table_bearings: no range table built");
   MCL_REQUIRE(ctx, cs_out, "mcl_range_table_bearings: null argument");
-  std::copy(ctx->range_bearings.begin(), ctx->range_bearings.end(), cs_out);
+  std::copy(ctx->range.bearings.begin(), ctx->range.bearings.end(), cs_out);
   return MCL_OK;
 }
 mcl_status mcl_range_table_read(mcl_ctx* ctx, uint64_t first_cell, uint64_t num_cells, uint32_t* out) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
-  if (ctx->range_angles == 0) return fail(ctx, MCL_ERR_NOT_READY, "mcl_range_table_read: no range table built");
-  const uint64_t cells = static_cast<uint64_t>(ctx->range_width) * ctx->range_height;
+  if (!ctx->range.built()) return fail(ctx, MCL_ERR_NOT_READY, "mcl_range_table_read: no range table built");
+  const uint64_t cells = static_cast<uint64_t>(ctx->range.width) * ctx->range.height;
   MCL_REQUIRE(ctx, first_cell <= cells && num_cells <= cells - first_cell, "mcl_range_table_read: cells beyond the grid");
   if (num_cells == 0) return MCL_OK;
   MCL_REQUIRE(ctx, out, "mcl_range_table_read: null argument");
   if (const mcl_status s = bind_device(ctx)) return s;
   MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  MCL_HIP(ctx, hipMemcpy(out, ctx->d_range_table.ptr + first_cell * ctx->range_angles, num_cells * ctx->range_angles * sizeof(uint32_t),
+  MCL_HIP(ctx, hipMemcpy(out, ctx->range.table.ptr + first_cell * ctx->range.angles, num_cells * ctx->range.angles * sizeof(uint32_t),
                          hipMemcpyDeviceToHost));
   return MCL_OK;
 }
@@ -5324,29 +5271,29 @@ mcl_status mcl_set_beam_skip(mcl_ctx* ctx, const mcl_beam_skip_params* params) {
   if (const char* wrong = beam_skip_check_params(*params)) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, std::string("mcl_set_beam_skip: ") + wrong);
   if (params->enabled && ctx->sharded())
     return fail(ctx, MCL_ERR_UNSUPPORTED, "mcl_set_beam_skip: the context is one rank of a sharded filter, whose counts are not exchanged yet");
-  ctx->beam_skip = *params;
-  ctx->beam_skip.reserved0 = 0;
-  ctx->beam_skip_last = mcl_beam_skip_result{};  // (a decision under other parameters is no answer to a question about these)
+  ctx->beam_skip.params = *params;
+  ctx->beam_skip.params.reserved0 = 0;
+  ctx->beam_skip.last = mcl_beam_skip_result{};  // (a decision under other parameters is no answer to a question about these)
   return MCL_OK;
 }
 mcl_status mcl_get_beam_skip(mcl_ctx* ctx, mcl_beam_skip_params* params) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (const mcl_status s = beam_skip_supported(ctx, "mcl_get_beam_skip")) return s;
   MCL_REQUIRE(ctx, params, "mcl_get_beam_skip: null params");
-  *params = ctx->beam_skip;
+  *params = ctx->beam_skip.params;
   return MCL_OK;
 }
 mcl_status mcl_get_beam_skip_result(mcl_ctx* ctx, mcl_beam_skip_result* result, uint32_t* counts, uint8_t* kept, uint64_t capacity) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   if (const mcl_status s = beam_skip_supported(ctx, "mcl_get_beam_skip_result")) return s;
   MCL_REQUIRE(ctx, result, "mcl_get_beam_skip_result: null result");
-  const mcl_beam_skip_result& last = ctx->beam_skip_last;
+  const mcl_beam_skip_result& last = ctx->beam_skip.last;
   MCL_REQUIRE(ctx, !(counts || kept) || capacity >= last.num_beams, "mcl_get_beam_skip_result: capacity is below num_beams");
   *result = last;
-  result->level = static_cast<double>(ctx->beam_skip_level());
+  result->level = static_cast<double>(ctx->beam_skip.level(ctx->cfg.lf));
   if (!last.valid) return MCL_OK;
-  if (counts) std::copy(ctx->beam_skip_counts.begin(), ctx->beam_skip_counts.begin() + last.num_beams, counts);
-  if (kept) std::copy(ctx->beam_skip_kept.begin(), ctx->beam_skip_kept.begin() + last.num_beams, kept);
+  if (counts) std::copy(ctx->beam_skip.counts.begin(), ctx->beam_skip.counts.begin() + last.num_beams, counts);
+  if (kept) std::copy(ctx->beam_skip.kept.begin(), ctx->beam_skip.kept.begin() + last.num_beams, kept);
   return MCL_OK;
 }
 mcl_status mcl_beam_agreement(mcl_ctx* ctx, const double* points_xy, uint64_t num_points, uint32_t* counts) {
@@ -5359,7 +5306,7 @@ mcl_status mcl_beam_agreement(mcl_ctx* ctx, const double* points_xy, uint64_t nu
   if (const mcl_status s = bind_device(ctx)) return s;
   uint32_t launches = 0;
   if (const mcl_status s = beam_skip_count(ctx, points_xy, num_points, counts, &launches)) return s;
-  ctx->beam_agreement_calls += 1;
+  ctx->beam_skip.agreement_calls += 1;
   return MCL_OK;
 }
 

@@ -75,6 +75,35 @@ struct HostBuffer {
   }
 };
 
+// A pinned buffer the host fills and one stream reads behind the call that filled it, and what the next fill has to wait for:
+// reserve() before every fill, used() right behind the copy or the launch that reads the memory, idle() where the stream has been synchronised.
+template <class T>
+struct StagedUpload {
+  HostBuffer<T> buf;
+  hipEvent_t event{nullptr};  // made by the first use that asks for one, destroyed with the owner
+  bool in_flight{false}, event_valid{false};  // a use may still be reading buf; `event` stands behind it (otherwise only the stream's end does)
+  ~StagedUpload() { if (event) (void)hipEventDestroy(event); }
+  // Waits for the previous use - its event, or without one all that `stream` holds - and grows the buffer to n elements.
+  hipError_t reserve(hipStream_t stream, size_t n, bool mapped) {
+    if (in_flight)
+      if (const hipError_t e = event_valid ? hipEventSynchronize(event) : hipStreamSynchronize(stream); e != hipSuccess) return e;
+    in_flight = false;
+    return buf.ensure(n, mapped);
+  }
+  // with_event: the caller may return before the stream is synchronised, so the next reserve() waits for this use alone.  Without
+  // one nothing is recorded on the stream (the update cycle, which always ends in a synchronisation and idle()).
+  hipError_t used(hipStream_t stream, bool with_event) {
+    in_flight = true;
+    event_valid = false;  // (a failure below leaves the next reserve() the stream to wait for)
+    if (!with_event) return hipSuccess;
+    hipError_t e = event ? hipSuccess : hipEventCreateWithFlags(&event, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(event, stream);
+    event_valid = e == hipSuccess;
+    return e;
+  }
+  void idle() { in_flight = false; }
+};
+
 struct MapStore {
   MapStoreKey key{0, MCL_SENSOR_LIKELIHOOD_FIELD, {}};
   struct Rebind {  // (see ~MapStore)

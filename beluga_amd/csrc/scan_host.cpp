@@ -1,5 +1,5 @@
 // scan_host.cpp — the entries of the C ABI (include/beluga_mcl.h) that turn a sensor message into the points of a scan and the estimate's
-// sums into the estimate.  They take no context and use no device.  Host only: se2.h, beluga_mcl.h and the standard library, no HIP and
+// sums into the estimate, and the rule about which points of a scan are staged (scan_host.h).  They take no context and use no device.  Host only: se2.h, beluga_mcl.h and the standard library, no HIP and
 // no mcl_ctx, so that a plain C++ compiler can build and check it (like cluster_host.cpp and map_build.cpp).
 #include <algorithm>
 #include <cmath>
@@ -7,9 +7,23 @@
 #include <limits>
 
 #include "beluga_mcl.h"
+#include "scan_host.h"
 #include "se2.h"
 
 using namespace mcl;
+
+uint64_t mcl::scan_finite_points(const double* points_xy, uint64_t num_points, double* kept_xy, uint32_t* slots) {
+  uint64_t kept = 0;
+  for (uint64_t i = 0; i < num_points; ++i) {
+    const double x = points_xy[2 * i], y = points_xy[2 * i + 1];
+    if (!(std::isfinite(x) && std::isfinite(y))) continue;
+    kept_xy[2 * kept] = x;
+    kept_xy[2 * kept + 1] = y;
+    if (slots) slots[kept] = static_cast<uint32_t>(i);
+    ++kept;
+  }
+  return kept;
+}
 
 extern "C" {
 

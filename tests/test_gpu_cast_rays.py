@@ -168,6 +168,27 @@ def test_device_form_gives_the_host_forms_bits():
             assert np.array_equal(lk.bits(alone.cpu().numpy()), lk.bits(host[0]))
 
 
+@pytest.mark.parametrize("sensor", [lk.LF, lk.BEAM], ids=["lf", "beam"])
+def test_device_form_called_again_while_the_first_call_is_in_flight(sensor):
+    """Two calls in a row with nothing waited for between them: the second, of a longer bearing table, writes the staging memory again
+    and makes it grow.  Each output is what the host form gives for its table on a twin."""
+    import torch
+
+    grid, poses = lk.reuse_grid(), lk.reuse_poses()
+    tables = [np.array([[1.0, 0.0], [0.6, 0.8]]), np.array([[0.0, -1.0], [-0.8, 0.6], [-1.0, 0.0]])]
+    f = Amcl(grid, MOTION, sensor, AmclParams(max_particles=64), seed=1)
+    twin = Amcl(grid, MOTION, sensor, AmclParams(max_particles=64), seed=1)
+    d_poses = torch.from_numpy(poses).to("cuda:0")
+    outs = [f.cast_rays_device(d_poses, bearings=table, max_range=3.0, synchronize=False) for table in tables]
+    f.sync()
+    for got, table in zip(outs, tables):
+        host = twin.cast_rays(poses, bearings=table, max_range=3.0)
+        assert tuple(got.shape) == (64, len(table)) and np.array_equal(lk.bits(got.cpu().numpy()), lk.bits(host))
+        assert np.unique(host).size > 8  # (walls at many distances: no constant answer passes)
+    f.close()
+    twin.close()
+
+
 # ---- 6. the filter is untouched ---------------------------------------------------------------------------------------------------------------
 PROBE_ANGLES = np.linspace(-math.pi, math.pi, 33, endpoint=False)
 

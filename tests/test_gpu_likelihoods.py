@@ -627,6 +627,44 @@ def test_device_form_gives_the_host_forms_bits(world, sensor):
     f.close()
 
 
+def reuse_grid():
+    """16 x 16 cells of 0.25 m: walls around, two obstacles inside."""
+    cells = np.zeros((16, 16), dtype=np.int8)
+    cells[0, :] = cells[-1, :] = cells[:, 0] = cells[:, -1] = 100
+    cells[5, 9] = cells[11, 4] = 100
+    return OccupancyGrid(cells=cells, resolution=0.25, origin=se2_from_xytheta(0.0, 0.0, 0.0))
+
+
+def reuse_poses(n=64, seed=11):
+    rng = np.random.default_rng(seed)
+    theta = rng.uniform(-math.pi, math.pi, n)
+    return np.ascontiguousarray(np.stack([np.cos(theta), np.sin(theta), rng.uniform(0.5, 3.5, n), rng.uniform(0.5, 3.5, n)], axis=1))
+
+
+@pytest.mark.parametrize("sensor", [LF, BEAM], ids=["lf", "beam"])
+def test_device_form_called_again_while_the_first_call_is_in_flight(sensor):
+    """Two calls in a row with nothing waited for between them: the second, of a longer scan, writes the staging memory again and makes
+    it grow.  Each output is what the host form gives for its scan on a twin."""
+    import torch
+
+    grid, poses = reuse_grid(), reuse_poses()
+    first = np.array([[1.0, 0.0], [0.5, 0.5], [-0.75, 0.25]])
+    second = np.array([[0.25, -1.0], [1.5, 0.125], [-0.5, -0.5], [0.0, 2.0], [0.875, 0.875]])
+    f = Amcl(grid, MOTION, sensor, AmclParams(max_particles=64), seed=1)
+    twin = Amcl(grid, MOTION, sensor, AmclParams(max_particles=64), seed=1)
+    d_poses = torch.from_numpy(poses).to("cuda:0")
+    outs = [torch.full((len(poses),), -7.0, dtype=torch.float64, device="cuda:0") for _ in range(2)]
+    f.likelihoods_device(d_poses, first, out=outs[0], synchronize=False)
+    f.likelihoods_device(d_poses, second, out=outs[1], synchronize=False)
+    f.sync()
+    want = [twin.likelihoods(poses, first), twin.likelihoods(poses, second)]
+    assert not np.array_equal(bits(want[0]), bits(want[1]))
+    for got, host in zip(outs, want):
+        assert np.array_equal(bits(got.cpu().numpy()), bits(host))
+    f.close()
+    twin.close()
+
+
 # ---- 6. refusals ----------------------------------------------------------------------------------------------------------------------------
 SENTINEL = -12345.0
 
