@@ -389,6 +389,24 @@ class SearchHit:
     heading: int
 
 
+@dataclass
+class LocalHit:
+    """A seed's result of Amcl.local_search: the best lattice pose (cos, sin, x, y), its score, the seed's own score, the best's integer
+    offsets, the number of candidates that share its score, and the score-weighted mean pose and covariance (x, y, theta) of the lattice
+    with the ten sums they were formed from; moments_valid is False where the scores sum to 0 or to something not finite."""
+    pose: np.ndarray
+    score: float
+    seed_score: float
+    di: int
+    dj: int
+    dk: int
+    plateau: int
+    mean_pose: np.ndarray
+    cov: np.ndarray
+    sums: np.ndarray
+    moments_valid: bool
+
+
 class Amcl:
     def __init__(self, grid: OccupancyGrid, motion, sensor, params: AmclParams = AmclParams(), *,
                  seed: int = 0, device: int = 0, shard_offset: int = 0, shard_capacity: int = 0, hip_stream: int = 0,
@@ -1060,14 +1078,77 @@ class Amcl:
         k = min(int(count), max(total.value - int(first), 0))
         return ids[:k], poses[:k], total.value
 
-    def relocalize(self, measurement, covariance, **search):
+    def relocalize(self, measurement, covariance=None, *, refine=None, **search):
         """global_search(measurement, **search), then initialize(best pose, covariance): host glue.  Returns the hits; with none
-        (a map without a candidate cell) the filter is left as it was."""
+        (a map without a candidate cell) the filter is left as it was.
+        refine: None, or the keywords of local_search as a dict (an empty one: its defaults).  The kept hits are then refined by
+        local_search and ordered by their refined score (stable for ties), the LocalHit list is returned, and the filter is
+        initialised at the best one's mean_pose with its cov + diag(step_xy^2, step_xy^2, step_theta^2) / 12 - the variance of a
+        uniform error inside one lattice step, which keeps the matrix positive definite on a plateau or with no steps at all.  Where
+        the best hit's moments are not valid the caller's covariance is used; `covariance` may be None only with refine."""
+        if refine is None and covariance is None:
+            raise ValueError("relocalize: a covariance is needed unless refine is given")
         hits = self.global_search(measurement, **search)
-        if hits:
-            best = hits[0]
-            self.initialize([best.pose[2], best.pose[3], math.atan2(best.pose[1], best.pose[0])], covariance)
-        return hits
+        if refine is None:
+            if hits:
+                best = hits[0]
+                self.initialize([best.pose[2], best.pose[3], math.atan2(best.pose[1], best.pose[0])], covariance)
+            return hits
+        if not hits:
+            return []
+        refined = self.local_search(np.array([h.pose for h in hits]), measurement, **refine)
+        refined.sort(key=lambda h: -h.score)  # (sort is stable: equal scores keep the search's order)
+        best = refined[0]
+        step_xy, step_theta = self.last_local_search_info["step_xy"], self.last_local_search_info["step_theta"]
+        if best.moments_valid:
+            cov = best.cov + np.diag([step_xy * step_xy / 12.0, step_xy * step_xy / 12.0, step_theta * step_theta / 12.0])
+        elif covariance is None:
+            raise ValueError("relocalize: the best hit's moments are not valid and no covariance was given")
+        else:
+            cov = covariance
+        self.initialize([best.mean_pose[2], best.mean_pose[3], math.atan2(best.mean_pose[1], best.mean_pose[0])], cov)
+        return refined
+
+    # -- local pose search: a lattice of offsets about each seed pose, its best and the response's moments (mcl_local_search*) -------
+    def _local_params(self, half_steps_xy, half_steps_theta, step_xy, step_theta):
+        return capi.LocalSearchParams(int(half_steps_xy), int(half_steps_theta), 0.0 if step_xy is None else float(step_xy), float(step_theta))
+
+    def local_search(self, poses, measurement, half_steps_xy=4, half_steps_theta=5, step_xy=None, step_theta=math.pi / 360):
+        """The correlative scan matcher about each of `poses` (float64 (n, 4) as (cos, sin, x, y)): the lattice of
+        (2 half_steps_xy + 1)^2 (2 half_steps_theta + 1) poses at offsets of step_xy (None: a quarter of the map's cell size) in world x
+        and y and of step_theta in heading is scored on the device as likelihoods() would score it.  Per seed a LocalHit: the best
+        lattice pose (ties go to the one nearest the seed), its score, the seed's own, and the score-weighted mean pose and covariance
+        of the lattice.  The filter is untouched.  Every sensor model; the measurement as likelihoods() takes it.
+        last_local_search_info holds the call's counts and steps."""
+        p = _f64_rows("poses", poses, 4)
+        params = self._local_params(half_steps_xy, half_steps_theta, step_xy, step_theta)
+        hits = (capi.LocalHit * max(len(p), 1))()
+        info = capi.LocalSearchInfo()
+        if self._landmark_kind:
+            landmark = self._landmark_kind == capi.MCL_SENSOR_LANDMARK
+            xyz, cat = _likelihood_detections(measurement, "detection_position_in_robot" if landmark else "detection_bearing_in_sensor")
+            fn = self._lib.mcl_local_search_landmarks if landmark else self._lib.mcl_local_search_bearings
+            self._check(fn(self._ctx, _dp(p), len(p), _dp(xyz), cat.ctypes.data_as(capi.c_u32_p), len(xyz), C.byref(params), hits, C.byref(info)))
+        else:
+            pts = _f64_rows("points", measurement, 2)
+            self._check(self._lib.mcl_local_search(self._ctx, _dp(p), len(p), _dp(pts), len(pts), C.byref(params), hits, C.byref(info)))
+        self.last_local_search_info = {name: getattr(info, name) for name, _ in capi.LocalSearchInfo._fields_}
+        self.last_local_search_info["step_theta"] = params.step_theta
+        return [LocalHit(np.array(h.pose, dtype=np.float64), h.score, h.seed_score, h.di, h.dj, h.dk, h.plateau,
+                         np.array(h.mean_pose, dtype=np.float64), np.array(h.cov, dtype=np.float64).reshape(3, 3),
+                         np.array(h.sums, dtype=np.float64), bool(h.moments_valid)) for h in hits[:len(p)]]
+
+    def local_search_candidates(self, pose, half_steps_xy=4, half_steps_theta=5, step_xy=None, step_theta=math.pi / 360, first=0, count=None):
+        """The lattice of one seed as the device makes it, in id order: (poses float64 (k, 4), total).  count None: all from `first` on."""
+        seed = _f64_rows("pose", np.asarray(pose, dtype=np.float64).reshape(1, -1), 4)
+        params = self._local_params(half_steps_xy, half_steps_theta, step_xy, step_theta)
+        total = C.c_uint64(0)
+        if count is None:
+            self._check(self._lib.mcl_local_search_candidates(self._ctx, _dp(seed), C.byref(params), 0, 0, None, C.byref(total)))
+            count = max(total.value - int(first), 0)
+        poses = np.zeros((int(count), 4), dtype=np.float64)
+        self._check(self._lib.mcl_local_search_candidates(self._ctx, _dp(seed), C.byref(params), int(first), int(count), _dp(poses), C.byref(total)))
+        return poses[:min(int(count), max(total.value - int(first), 0))], total.value
 
     # -- beam skipping (Nav2's do_beamskip; likelihood-field filters) -------------------------------------------------------------
     def set_beam_skip(self, enabled: bool = True, distance: Optional[float] = None, threshold: Optional[float] = None,

@@ -14,8 +14,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libbeluga_mcl.so")
-SOURCES = ["kernels.hip", "beam_kernels.hip", "ndt_kernels.hip", "ndt_build_kernels.hip", "landmark_kernels.hip", "context.hip", "map_build.cpp", "cluster_host.cpp", "cycle_host.cpp", "batch_host.cpp", "map_store_host.cpp", "ndt_host.cpp", "landmark_host.cpp", "scan_host.cpp", "options_host.cpp", "beam_skip_host.cpp", "search_host.cpp", "raycast_host.cpp", "range_table_host.cpp"]
-HEADERS = ["kernels.h", "device_common.hpp", "se2.h", "rng.h", "map_build.h", "cluster_host.h", "cycle_host.h", "batch_host.h", "map_store.h", "map_store_host.h", "cycle_types.h", "sensor_records.h", "ndt_hash.h", "ndt_host.h", "landmark_host.h", "set_facts.h", "options_host.h", "scratch_layout.h", "beam_skip_host.h", "search_host.h", "raycast_host.h", "range_table_host.h", "scan_host.h", os.path.join(ROOT, "include", "beluga_mcl.h")]
+SOURCES = ["kernels.hip", "beam_kernels.hip", "ndt_kernels.hip", "ndt_build_kernels.hip", "landmark_kernels.hip", "context.hip", "map_build.cpp", "cluster_host.cpp", "cycle_host.cpp", "batch_host.cpp", "map_store_host.cpp", "ndt_host.cpp", "landmark_host.cpp", "scan_host.cpp", "options_host.cpp", "beam_skip_host.cpp", "search_host.cpp", "local_search_host.cpp", "raycast_host.cpp", "range_table_host.cpp"]
+HEADERS = ["kernels.h", "device_common.hpp", "se2.h", "rng.h", "map_build.h", "cluster_host.h", "cycle_host.h", "batch_host.h", "map_store.h", "map_store_host.h", "cycle_types.h", "sensor_records.h", "ndt_hash.h", "ndt_host.h", "landmark_host.h", "set_facts.h", "options_host.h", "scratch_layout.h", "beam_skip_host.h", "search_host.h", "local_search_host.h", "raycast_host.h", "range_table_host.h", "scan_host.h", os.path.join(ROOT, "include", "beluga_mcl.h")]
 # -ffp-contract=off: see the header comment of kernels.hip (floor() parity with the reference's arithmetic).
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-result",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC] + os.environ.get("BELUGA_MCL_EXTRA_CXXFLAGS", "").split()

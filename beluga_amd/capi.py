@@ -155,6 +155,21 @@ class SearchInfo(C.Structure):
     _fields_ = [("cells", C.c_uint64), ("candidates", C.c_uint64), ("pool_filled", C.c_uint64), ("chunks", C.c_uint32), ("launches", C.c_uint32)]
 
 
+class LocalSearchParams(C.Structure):
+    _fields_ = [("half_steps_xy", C.c_uint32), ("half_steps_theta", C.c_uint32), ("step_xy", C.c_double), ("step_theta", C.c_double)]
+
+
+class LocalHit(C.Structure):
+    _fields_ = [("pose", C.c_double * 4), ("score", C.c_double), ("seed_score", C.c_double), ("di", C.c_int32), ("dj", C.c_int32),
+                ("dk", C.c_int32), ("moments_valid", C.c_int32), ("plateau", C.c_uint64), ("mean_pose", C.c_double * 4),
+                ("cov", C.c_double * 9), ("sums", C.c_double * 10)]
+
+
+class LocalSearchInfo(C.Structure):
+    _fields_ = [("candidates_per_seed", C.c_uint64), ("seeds_per_pass", C.c_uint64), ("passes", C.c_uint32), ("launches", C.c_uint32),
+                ("step_xy", C.c_double)]
+
+
 class RangeTableInfo(C.Structure):
     _fields_ = [("built", C.c_int32), ("num_angles", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("bytes", C.c_uint64),
                 ("builds", C.c_uint64), ("lut_launches", C.c_uint64)]
@@ -202,6 +217,15 @@ _SIGNATURES = {
                                            C.POINTER(SearchInfo)]),
     "mcl_global_search_candidates": (C.c_int32, [_ctx, C.POINTER(SearchParams), C.c_uint64, C.c_uint64, c_u64_p, c_double_p, c_u64_p]),
     "mcl_search_suppress": (C.c_int32, [C.POINTER(SearchHit), C.c_uint64, C.c_uint32, C.POINTER(SearchParams), c_u32_p, c_u64_p]),
+    "mcl_default_local_search_params": (None, [C.POINTER(LocalSearchParams)]),
+    "mcl_local_search": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, C.c_uint64, C.POINTER(LocalSearchParams), C.POINTER(LocalHit),
+                                     C.POINTER(LocalSearchInfo)]),
+    "mcl_local_search_landmarks": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_u32_p, C.c_uint64, C.POINTER(LocalSearchParams),
+                                               C.POINTER(LocalHit), C.POINTER(LocalSearchInfo)]),
+    "mcl_local_search_bearings": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, c_u32_p, C.c_uint64, C.POINTER(LocalSearchParams),
+                                              C.POINTER(LocalHit), C.POINTER(LocalSearchInfo)]),
+    "mcl_local_search_candidates": (C.c_int32, [_ctx, c_double_p, C.POINTER(LocalSearchParams), C.c_uint64, C.c_uint64, c_double_p, c_u64_p]),
+    "mcl_local_search_finish": (C.c_int32, [c_double_p, C.POINTER(LocalSearchParams), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32)]),
     "mcl_cast_rays": (C.c_int32, [_ctx, c_double_p, C.c_uint64, c_double_p, C.c_uint64, C.c_double, c_double_p, c_i64_p, c_u64_p]),
     "mcl_cast_rays_device": (C.c_int32, [_ctx, C.c_void_p, C.c_uint64, c_double_p, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, c_u64_p]),
     "mcl_build_range_table": (C.c_int32, [_ctx, C.c_uint32]),
@@ -306,7 +330,10 @@ _OPTIONAL = {"mcl_measurement_build", "mcl_set_ndt_small_cycle", "mcl_get_ndt_sm
              # (tools/exp_beam_skip.py measures against a build of the commit before beam skipping)
              "mcl_default_beam_skip_params", "mcl_set_beam_skip", "mcl_get_beam_skip", "mcl_get_beam_skip_result", "mcl_beam_agreement",
              # (tools/exp_range_table.py measures against a build of the commit before the range table)
-             "mcl_build_range_table", "mcl_drop_range_table", "mcl_range_table_get_info", "mcl_range_table_bearings", "mcl_range_table_read"}
+             "mcl_build_range_table", "mcl_drop_range_table", "mcl_range_table_get_info", "mcl_range_table_bearings", "mcl_range_table_read",
+             # (the update cycle of a build of the commit before the local search is measured against this one's)
+             "mcl_default_local_search_params", "mcl_local_search", "mcl_local_search_landmarks", "mcl_local_search_bearings",
+             "mcl_local_search_candidates", "mcl_local_search_finish"}
 _lib = None
 
 

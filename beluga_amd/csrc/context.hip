@@ -37,6 +37,7 @@
 #include "scan_host.h"
 #include "scratch_layout.h"
 #include "search_host.h"
+#include "local_search_host.h"
 #include "set_facts.h"
 
 namespace {
@@ -73,6 +74,13 @@ struct SearchState {
   DeviceBuffer<unsigned long long> u64;
   DeviceBuffer<uint32_t> u32;
   HostBuffer<unsigned long long> pinned;
+};
+// mcl_local_search*: the call's own device block and the pinned block that stages its tables and receives its results (LocalSearchLayout,
+// scratch_layout.h); the measurement is staged as mcl_likelihoods_device stages it.  Every call ends in a synchronisation, as the global
+// search's: nothing of it is in flight at the next.
+struct LocalSearchState {
+  DeviceBuffer<double> block;
+  StagedUpload<double> staged;
 };
 // mcl_cast_rays*: the call's own buffers (RayCastLayout, scratch_layout.h) - the bearing table, the cell count, a chunk's poses and
 // outputs - and the pinned staging of the bearings (the next call waits for their copy before it writes the staging memory again).
@@ -373,6 +381,7 @@ struct mcl_ctx {
 
   LikelihoodsState likelihoods;
   SearchState search;
+  LocalSearchState local;
   RayCastState cast;
   BeamSkipState beam_skip;
   RangeTableState range;
@@ -5113,6 +5122,176 @@ mcl_status mcl_global_search_candidates(mcl_ctx* ctx, const mcl_search_params* p
                                         double* poses_out, uint64_t* total) {
   if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
   return settled_after_device_error(ctx, search_candidates(ctx, params, first_id_rank, count, ids_out, poses_out, total));
+}
+
+// ---- local pose search: a lattice about each seed scored by likelihoods_launch, its best and its moments (DESIGN.md "Local pose search") ----
+// The host rule is local_search_host.cpp's.  The tables (off[], the seeds' positions, the rotations) go up in one copy; a pass is whole
+// seeds: their poses (one launch), their scores by the kernels of mcl_likelihoods_device, their reduction (a workgroup per seed); the
+// results of all seeds come back in one copy behind the last pass, and the call's one synchronisation follows.  Nothing the update
+// cycle reads is written.
+struct LocalCall {
+  mcl_local_search_params p;  // step_xy resolved
+  LocalLattice lat;
+  LocalPlan plan;
+  LocalSearchLayout lay;
+  std::vector<double> off, rot;  // as the device was given them
+  uint32_t launches;
+};
+static bool local_has_map(const mcl_ctx* ctx) {
+  switch (ctx->family()) {
+    case SensorFamily::kNdt: return ctx->have_ndt_map;
+    case SensorFamily::kLandmark: return ctx->have_landmark_map;
+    default: return ctx->have_map;
+  }
+}
+static mcl_status local_check(mcl_ctx* ctx, const char* who, const mcl_local_search_params* params, mcl_local_search_params* p) {
+  if (!local_has_map(ctx)) return fail(ctx, MCL_ERR_NOT_READY, std::string(who) + ": no map set");
+  *p = params ? *params : local_default_params();
+  if (const char* wrong = local_check_params(*p)) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, std::string(who) + ": " + wrong);
+  if (p->step_xy == 0.0) {
+    if (ctx->is_landmark())
+      return fail(ctx, MCL_ERR_INVALID_ARGUMENT, std::string(who) + ": step_xy 0 stands for a quarter of the map's cell size, and a landmark map has no cells");
+    p->step_xy = 0.25 * (ctx->is_ndt() ? ctx->ndt_resolution : ctx->map->resolution);
+  }
+  return MCL_OK;
+}
+static mcl_status local_check_seeds(mcl_ctx* ctx, const char* who, const double* seeds, uint64_t n) {
+  for (uint64_t i = 0; i < 4 * n; ++i)
+    if (!std::isfinite(seeds[i])) return fail(ctx, MCL_ERR_INVALID_ARGUMENT, std::string(who) + ": seed " + std::to_string(i / 4) + " has a value that is not finite");
+  return MCL_OK;
+}
+// The call's buffers, and the tables behind whatever the stream holds.
+static mcl_status local_begin(mcl_ctx* ctx, const mcl_local_search_params& p, const double* seeds, uint64_t n, LocalCall* call) {
+  const uint32_t nx = local_side(p.half_steps_xy), nt = local_side(p.half_steps_theta);
+  const LocalLattice lat{p.half_steps_xy, p.half_steps_theta, nx, nt, static_cast<uint32_t>(local_candidates(p))};
+  const LocalPlan plan = local_plan(n, lat.L, ctx->tuning.search_chunk);
+  const LocalSearchLayout lay(n, nx, nt, plan.pass_candidates, kLocalResultDoubles, kLocalResultWords);
+  MCL_HIP(ctx, ctx->local.staged.reserve(ctx->stream, lay.h_size, /*mapped=*/false));
+  MCL_HIP(ctx, ctx->local.block.ensure(lay.size));  // (every call ends in a synchronisation: nothing reads the old block)
+  *call = LocalCall{p, lat, plan, lay, {}, {}, 0};
+  local_offsets(p.half_steps_xy, p.step_xy, call->off);
+  local_rotations(seeds, n, p.half_steps_theta, p.step_theta, call->rot);
+  double* const h = ctx->local.staged.buf.host + lay.h_tables;
+  std::fill(h, h + lay.tables_size, 0.0);
+  std::copy(call->off.begin(), call->off.end(), h + lay.off);
+  for (uint64_t s = 0; s < n; ++s) {
+    h[lay.seed_xy + 2 * s] = seeds[4 * s + 2];
+    h[lay.seed_xy + 2 * s + 1] = seeds[4 * s + 3];
+  }
+  std::copy(call->rot.begin(), call->rot.end(), h + lay.rot);
+  MCL_HIP(ctx, hipMemcpyAsync(ctx->local.block.ptr, h, lay.tables_size * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  MCL_HIP(ctx, ctx->local.staged.used(ctx->stream, /*with_event=*/false));
+  return MCL_OK;
+}
+// The poses of `count` seeds from seed `first` on into the pass's pose area.
+static mcl_status local_generate_pass(mcl_ctx* ctx, LocalCall* call, uint64_t first, uint32_t count) {
+  double* const block = ctx->local.block.ptr;
+  call->launches += launch_local_generate(ctx->stream, block + call->lay.seed_xy + 2 * first, block + call->lay.rot + 2 * first * call->lat.nt,
+                                          block + call->lay.off, count, call->lat, reinterpret_cast<double4*>(block + call->lay.poses));
+  if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string("local search: ") + hipGetErrorString(e));
+  return MCL_OK;
+}
+// The entries behind their measurement builder (its status `built`, its output m), as likelihoods_host.
+static mcl_status local_search(mcl_ctx* ctx, const char* who, mcl_status built, const LikelihoodsMeasurement& m, const double* seeds, uint64_t n,
+                               const mcl_local_search_params* params, mcl_local_hit* hits, mcl_local_search_info* info) {
+  if (built != MCL_OK) return built;
+  mcl_local_search_params p{};
+  if (const mcl_status s = local_check(ctx, who, params, &p)) return s;
+  MCL_REQUIRE(ctx, n == 0 || (seeds && hits), std::string(who) + ": null argument");
+  if (const mcl_status s = local_check_seeds(ctx, who, seeds, n)) return s;
+  if (n == 0) return MCL_OK;
+  if (const mcl_status s = bind_device(ctx)) return s;
+  LocalCall call{p, {}, {}, LocalSearchLayout(0, 1, 1, 0, 0, 0), {}, {}, 0};
+  if (const mcl_status s = local_begin(ctx, p, seeds, n, &call)) return s;
+  LikelihoodsLayout meas(0, 0);
+  if (const mcl_status s = likelihoods_stage(ctx, m, 0, &meas)) return s;
+  double* const block = ctx->local.block.ptr;
+  const LocalSearchLayout& lay = call.lay;
+  for (uint64_t first = 0; first < n; first += call.plan.seeds_per_pass) {
+    const uint32_t count = static_cast<uint32_t>(std::min<uint64_t>(call.plan.seeds_per_pass, n - first));
+    if (const mcl_status s = local_generate_pass(ctx, &call, first, count)) return s;
+    if (const mcl_status s = likelihoods_launch(ctx, block + lay.poses, static_cast<uint64_t>(count) * call.lat.L, m,
+                                                ctx->likelihoods.block.ptr + meas.measurement, block + lay.scores, /*exact_walk=*/true)) return s;
+    call.launches += 1;
+    call.launches += launch_local_reduce(ctx->stream, block + lay.scores, count, call.lat, block + lay.results_f64 + kLocalResultDoubles * first,
+                                         reinterpret_cast<unsigned long long*>(block + lay.results_u64) + kLocalResultWords * first);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return fail(ctx, MCL_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  }
+  double* const h = ctx->local.staged.buf.host + lay.h_results;
+  MCL_HIP(ctx, hipMemcpyAsync(h, block + lay.results_f64, lay.results_size * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->local.staged.idle();
+  const double* const f64 = h;
+  const double* const words = h + (lay.results_u64 - lay.results_f64);
+  std::vector<mcl_local_hit> found(n);
+  for (uint64_t s = 0; s < n; ++s) {
+    uint64_t word[kLocalResultWords];
+    std::memcpy(word, words + kLocalResultWords * s, sizeof word);
+    const uint32_t id = local_id_of_tie_key(word[0]);
+    if (id >= call.lat.L || word[0] != local_tie_key(p.half_steps_xy, p.half_steps_theta, id) || word[1] == 0 || word[1] > call.lat.L)
+      return fail(ctx, MCL_ERR_HIP, std::string(who) + ": the reduction of seed " + std::to_string(s) + " names no candidate of its lattice");
+    mcl_local_hit& hit = found[s];
+    const double* const r = f64 + kLocalResultDoubles * s;
+    local_pose(seeds + 4 * s, call.off.data(), call.rot.data() + 2 * s * call.lat.nt, p.half_steps_xy, p.half_steps_theta, id, hit.pose);
+    hit.score = r[10];
+    hit.seed_score = r[11];
+    local_offsets_of(p.half_steps_xy, p.half_steps_theta, id, hit.di, hit.dj, hit.dk);
+    hit.plateau = word[1];
+    std::copy(r, r + kLocalSums, hit.sums);
+    hit.moments_valid = local_finish(hit.sums, p.step_xy, p.step_theta, seeds + 4 * s, hit.mean_pose, hit.cov);
+  }
+  std::copy(found.begin(), found.end(), hits);
+  if (info) *info = mcl_local_search_info{call.lat.L, call.plan.seeds_per_pass, call.plan.passes, call.launches, p.step_xy};
+  return MCL_OK;
+}
+static mcl_status local_candidates_of(mcl_ctx* ctx, const double* seed, const mcl_local_search_params* params, uint64_t first, uint64_t count,
+                                      double* poses_out, uint64_t* total) {
+  const char* who = "mcl_local_search_candidates";
+  mcl_local_search_params p{};
+  if (const mcl_status s = local_check(ctx, who, params, &p)) return s;
+  MCL_REQUIRE(ctx, seed && total && (count == 0 || poses_out), std::string(who) + ": null argument");
+  if (const mcl_status s = local_check_seeds(ctx, who, seed, 1)) return s;
+  if (const mcl_status s = bind_device(ctx)) return s;
+  LocalCall call{p, {}, {}, LocalSearchLayout(0, 1, 1, 0, 0, 0), {}, {}, 0};
+  if (const mcl_status s = local_begin(ctx, p, seed, 1, &call)) return s;
+  if (const mcl_status s = local_generate_pass(ctx, &call, 0, 1)) return s;
+  const uint64_t L = call.lat.L, from = std::min(first, L), k = std::min(count, L - from);
+  std::vector<double> poses(4 * k);
+  if (k) MCL_HIP(ctx, hipMemcpyAsync(poses.data(), ctx->local.block.ptr + call.lay.poses + 4 * from, 4 * k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  MCL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->local.staged.idle();
+  if (k) std::copy(poses.begin(), poses.end(), poses_out);
+  *total = L;
+  return MCL_OK;
+}
+
+mcl_status mcl_local_search(mcl_ctx* ctx, const double* seeds, uint64_t n, const double* points_xy, uint64_t num_points,
+                            const mcl_local_search_params* params, mcl_local_hit* hits, mcl_local_search_info* info) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  LikelihoodsMeasurement m{};
+  return settled_after_device_error(ctx, local_search(ctx, "mcl_local_search", likelihoods_points(ctx, "mcl_local_search", points_xy, num_points, &m), m, seeds, n,
+                                                      params, hits, info));
+}
+mcl_status mcl_local_search_landmarks(mcl_ctx* ctx, const double* seeds, uint64_t n, const double* positions_xyz, const uint32_t* categories,
+                                      uint64_t k, const mcl_local_search_params* params, mcl_local_hit* hits, mcl_local_search_info* info) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  LikelihoodsMeasurement m{};
+  return settled_after_device_error(ctx, local_search(ctx, "mcl_local_search_landmarks",
+                                                      likelihoods_detections(ctx, "mcl_local_search_landmarks", MCL_SENSOR_LANDMARK, positions_xyz, categories, k, &m),
+                                                      m, seeds, n, params, hits, info));
+}
+mcl_status mcl_local_search_bearings(mcl_ctx* ctx, const double* seeds, uint64_t n, const double* bearings_xyz, const uint32_t* categories,
+                                     uint64_t k, const mcl_local_search_params* params, mcl_local_hit* hits, mcl_local_search_info* info) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  LikelihoodsMeasurement m{};
+  return settled_after_device_error(ctx, local_search(ctx, "mcl_local_search_bearings",
+                                                      likelihoods_detections(ctx, "mcl_local_search_bearings", MCL_SENSOR_BEARING, bearings_xyz, categories, k, &m),
+                                                      m, seeds, n, params, hits, info));
+}
+mcl_status mcl_local_search_candidates(mcl_ctx* ctx, const double seed[4], const mcl_local_search_params* params, uint64_t first, uint64_t count,
+                                       double* poses_out, uint64_t* total) {
+  if (!ctx) return MCL_ERR_INVALID_ARGUMENT;
+  return settled_after_device_error(ctx, local_candidates_of(ctx, seed, params, first, count, poses_out, total));
 }
 
 // ---- ray casting as a function: the range the map predicts along caller-given bearings from caller-given poses (Ray2d::cast) ------------

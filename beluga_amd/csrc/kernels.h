@@ -301,6 +301,25 @@ uint32_t launch_search_poses(hipStream_t st, const uint32_t* selected, uint32_t 
 uint32_t launch_search_pool(hipStream_t st, const double* scores, const unsigned long long* ids, uint64_t n, const SearchScratch& s, uint32_t pool,
                             uint32_t pool_len, int* pool_at);
 
+// ---- local pose search (mcl_local_search*; DESIGN.md "Local pose search"; the host rule: local_search_host.h) ---------------------------
+struct LocalLattice {
+  uint32_t Kx, Kt;  // half steps
+  uint32_t nx, nt;  // 2 K + 1
+  uint32_t L;       // nx * nx * nt candidates per seed
+};
+constexpr int kLocalReduceBlock = 256;
+constexpr uint32_t kLocalResultDoubles = 12;  // per seed: the ten sums | the best score | the seed's score
+constexpr uint32_t kLocalResultWords = 2;     // per seed: the best candidate's tie key (its id in the low 20 bits) | plateau
+// poses[s * L + id] for the `seeds` seeds of a pass, a lane per candidate: (rot[s * nt + k + Kt], seed_xy[s] + (off[i + Kx], off[j + Kx])).
+// seed_xy and rot start at the pass's first seed.
+uint32_t launch_local_generate(hipStream_t st, const double* seed_xy, const double* rot, const double* off, uint32_t seeds, const LocalLattice& lat,
+                               double4* poses);
+// One workgroup per seed of the pass over its L scores (scores + s * L): the best by (score key descending, tie key ascending), the ten
+// sums by a fixed tree (a lane's candidates in ascending order, the wave's lanes by wave_sum_f64, the waves in order), the plateau
+// count in a second sweep.  out_f64 + s * kLocalResultDoubles, out_u64 + s * kLocalResultWords.
+uint32_t launch_local_reduce(hipStream_t st, const double* scores, uint32_t seeds, const LocalLattice& lat, double* out_f64,
+                             unsigned long long* out_u64);
+
 struct HashParams {
   double res_x, res_y, res_theta;
 };

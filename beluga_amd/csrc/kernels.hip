@@ -4965,6 +4965,110 @@ uint32_t launch_search_pool(hipStream_t st, const double* scores, const unsigned
   return launches + 1;
 }
 
+// ---- local pose search (mcl_local_search*; DESIGN.md "Local pose search") ---------------------------------------------------------------
+// Generation: a lane per candidate of the pass.  Everything a pose is made of was computed on the host (off[], the rotation table): the
+// device adds one offset to each coordinate, so every candidate carries the host's bits.
+__global__ __launch_bounds__(kBlock) void k_local_generate(const double2* __restrict__ seed_xy, const double2* __restrict__ rot,
+                                                           const double* __restrict__ off, uint32_t seeds, LocalLattice lat, double4* __restrict__ poses) {
+  const uint64_t g = static_cast<uint64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (g >= static_cast<uint64_t>(seeds) * lat.L) return;
+  const uint32_t s = static_cast<uint32_t>(g / lat.L), id = static_cast<uint32_t>(g - static_cast<uint64_t>(s) * lat.L);
+  const uint32_t plane = lat.nx * lat.nx;
+  const uint32_t k = id / plane, rest = id - k * plane, j = rest / lat.nx, i = rest - j * lat.nx;
+  const double2 r = rot[static_cast<uint64_t>(s) * lat.nt + k], xy = seed_xy[s];
+  poses[g] = double4{r.x, r.y, xy.x + off[i], xy.y + off[j]};
+}
+
+// Reduction: one workgroup per seed.  Lane t takes the candidates t, t + 256, ... in ascending order, so a wave's loads of the scores
+// coalesce; (i, j, k) of a lane's candidate are kept as the digits of its id and advanced by the digits of 256 with two carries - the
+// divisions are done once, in front of the loop.  A term of a sum is the score times an INTEGER product, one rounding; a lane adds its
+// terms in the order it meets them, wave_sum_f64 adds the lanes and thread k the four waves' k-th sums in order (block_reduce): the tree
+// is fixed by L and the workgroup's size, and no floating-point value goes through an atomic.  The best candidate is the first by
+// (score key descending, tie key ascending) (local_search_host.h): a total order, so its reduction gives one answer in any association.
+// The second sweep counts the scores whose key equals the best's.
+__global__ __launch_bounds__(kLocalReduceBlock) void k_local_reduce(const double* __restrict__ scores, LocalLattice lat, double* __restrict__ out_f64,
+                                                                    unsigned long long* __restrict__ out_u64) {
+  constexpr int kWaves = kLocalReduceBlock / kWave;
+  __shared__ double s_sums[kWaves * 10];
+  __shared__ unsigned long long s_key[kWaves], s_tie[kWaves];
+  __shared__ uint32_t s_count[kWaves];
+  const double* __restrict__ w = scores + static_cast<uint64_t>(blockIdx.x) * lat.L;
+  const uint32_t t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+  const uint32_t nx = lat.nx, plane = nx * nx;
+  uint32_t a = t % nx, b = t / nx % nx, c = t / plane;
+  const uint32_t da = kLocalReduceBlock % nx, db = kLocalReduceBlock / nx % nx, dc = kLocalReduceBlock / plane;
+  const int Kx = static_cast<int>(lat.Kx), Kt = static_cast<int>(lat.Kt);
+  double v[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  unsigned long long best_key = 0ull, best_tie = ~0ull;  // behind every candidate
+  for (uint32_t id = t; id < lat.L; id += kLocalReduceBlock) {
+    const double x = w[id];
+    const int i = static_cast<int>(a) - Kx, j = static_cast<int>(b) - Kx, k = static_cast<int>(c) - Kt;
+    v[0] += x;
+    v[1] += x * static_cast<double>(i);
+    v[2] += x * static_cast<double>(j);
+    v[3] += x * static_cast<double>(k);
+    v[4] += x * static_cast<double>(i * i);
+    v[5] += x * static_cast<double>(i * j);
+    v[6] += x * static_cast<double>(i * k);
+    v[7] += x * static_cast<double>(j * j);
+    v[8] += x * static_cast<double>(j * k);
+    v[9] += x * static_cast<double>(k * k);
+    const unsigned long long key = search_key_of(x);
+    const unsigned long long tie = (static_cast<unsigned long long>(i * i + j * j) << 27) | (static_cast<unsigned long long>(k < 0 ? -k : k) << 20) | id;
+    if (search_before(key, tie, best_key, best_tie)) {
+      best_key = key;
+      best_tie = tie;
+    }
+    a += da, b += db, c += dc;
+    if (a >= nx) a -= nx, ++b;
+    if (b >= nx) b -= nx, ++c;
+  }
+  for (int m = 1; m < kWave; m <<= 1) {
+    const unsigned long long other_key = __shfl_xor(best_key, m), other_tie = __shfl_xor(best_tie, m);
+    if (search_before(other_key, other_tie, best_key, best_tie)) {
+      best_key = other_key;
+      best_tie = other_tie;
+    }
+  }
+  if (lane == 0) {
+    s_key[wave] = best_key;
+    s_tie[wave] = best_tie;
+  }
+  block_reduce<10, kLocalReduceBlock>(v, s_sums);  // (its barriers stand behind the stores above)
+  best_key = s_key[0], best_tie = s_tie[0];
+  for (int k = 1; k < kWaves; ++k)
+    if (search_before(s_key[k], s_tie[k], best_key, best_tie)) best_key = s_key[k], best_tie = s_tie[k];
+  uint32_t count = 0;
+  for (uint32_t id = t; id < lat.L; id += kLocalReduceBlock) count += search_key_of(w[id]) == best_key ? 1u : 0u;
+  for (int m = 1; m < kWave; m <<= 1) count += __shfl_xor(count, m);
+  if (lane == 0) s_count[wave] = count;
+  __syncthreads();
+  if (t == 0) {
+    double* const f = out_f64 + static_cast<uint64_t>(blockIdx.x) * kLocalResultDoubles;
+    for (int k = 0; k < 10; ++k) f[k] = v[k];
+    f[10] = w[best_tie & 0xFFFFFull];
+    f[11] = w[(lat.Kt * nx + lat.Kx) * nx + lat.Kx];
+    uint32_t plateau = 0;
+    for (int k = 0; k < kWaves; ++k) plateau += s_count[k];
+    unsigned long long* const u = out_u64 + static_cast<uint64_t>(blockIdx.x) * kLocalResultWords;
+    u[0] = best_tie;
+    u[1] = plateau;
+  }
+}
+
+uint32_t launch_local_generate(hipStream_t st, const double* seed_xy, const double* rot, const double* off, uint32_t seeds, const LocalLattice& lat,
+                               double4* poses) {
+  if (seeds == 0) return 0;
+  hipLaunchKernelGGL(k_local_generate, dim3(blocks_for(static_cast<uint64_t>(seeds) * lat.L)), dim3(kBlock), 0, st,
+                     reinterpret_cast<const double2*>(seed_xy), reinterpret_cast<const double2*>(rot), off, seeds, lat, poses);
+  return 1;
+}
+uint32_t launch_local_reduce(hipStream_t st, const double* scores, uint32_t seeds, const LocalLattice& lat, double* out_f64, unsigned long long* out_u64) {
+  if (seeds == 0) return 0;
+  hipLaunchKernelGGL(k_local_reduce, dim3(seeds), dim3(kLocalReduceBlock), 0, st, scores, lat, out_f64, out_u64);
+  return 1;
+}
+
 }  // namespace mcl
 // Nonzero for a measurement build of the kernels (tools/build_variant.sh: ablations compute nonsense by design, timing builds
 // distort): beluga_amd/capi.py refuses to load one as the product library unless told so.

@@ -299,6 +299,34 @@ struct SearchLayout {
   }
 };
 
+// ---- mcl_local_search*: the call's own 8-byte words, in device memory and in the pinned block that stages one part and receives another ----
+// device: off[] (2 Kx + 1) | the seeds' (x, y) | the rotation table (cos, sin per seed and step) - these three in the pinned block's
+//   order, so that one copy uploads them - | a pass's poses | its scores | the results per seed: kLocalResultDoubles doubles, then
+//   kLocalResultWords uint64.  Every area is rounded up to whole poses (the poses are read as double4, the tables as double2).
+// pinned: the three tables to upload | the results read back (the device's two result areas, one copy).
+// The tables and the results are sized by the seeds, the poses and scores by the pass (LocalPlan::pass_candidates), never by n * L.
+struct LocalSearchLayout {
+  size_t off, seed_xy, rot, tables_size, poses, scores, results_f64, results_u64, results_size, size;
+  size_t h_tables, h_results, h_size;
+  LocalSearchLayout(uint64_t seeds, uint32_t side_xy, uint32_t side_theta, uint64_t pass_candidates, size_t result_doubles, size_t result_words) {
+    const auto whole = [](size_t doubles) { return (doubles + 3) / 4 * 4; };
+    Cursor c, host;
+    off = c.take(whole(side_xy));
+    seed_xy = c.take(whole(2 * static_cast<size_t>(seeds)));
+    rot = c.take(whole(2 * static_cast<size_t>(seeds) * side_theta));
+    tables_size = c.at;
+    poses = c.take(4 * static_cast<size_t>(pass_candidates));
+    scores = c.take(whole(static_cast<size_t>(pass_candidates)));
+    results_f64 = c.take(whole(result_doubles * static_cast<size_t>(seeds)));
+    results_u64 = c.take(whole(result_words * static_cast<size_t>(seeds)));
+    results_size = c.at - results_f64;
+    size = c.at;
+    h_tables = host.take(tables_size);
+    h_results = host.take(results_size);
+    h_size = host.at;
+  }
+};
+
 // ---- mcl_cast_rays*: d_cast and the pinned h_cast, the call's own 8-byte words --------------------------------------------------------------
 // d_cast: the bearing table (c, s per bearing, made into the far-end vectors in place; rounded up to whole poses: the poses behind it
 // are read as double4) | the cell count, one word in a granule of four | a chunk's poses | its ranges | its hit cells (int64).  The

@@ -763,6 +763,90 @@ class Amcl {
     return hits;
   }
 
+  /// Extension: the local pose search (mcl_local_search): about each of `states` the lattice of (2 half_steps_xy + 1)^2
+  /// (2 half_steps_theta + 1) poses at offsets of step_xy (0: a quarter of the map's cell size) in world x and y and of step_theta in
+  /// heading is scored on the device as likelihoods() would score it.  Per state a LocalHit: the best lattice pose (ties go to the one
+  /// nearest the state), its score, the state's own, and the score-weighted mean pose and covariance of the lattice.  The filter is
+  /// untouched.  Every sensor model; the measurement as likelihoods() takes it.
+  struct LocalSearchParams {
+    std::uint32_t half_steps_xy = 4, half_steps_theta = 5;
+    double step_xy = 0.0, step_theta = 3.14159265358979323846 / 360.0;
+  };
+  struct LocalHit {
+    SE2d pose;
+    double score = 0.0, seed_score = 0.0;
+    std::int32_t di = 0, dj = 0, dk = 0;
+    std::uint64_t plateau = 0;
+    SE2d mean_pose;
+    Matrix3d cov{};
+    std::array<double, 10> sums{};
+    bool moments_valid = false;
+  };
+  [[nodiscard]] std::vector<LocalHit> local_search(const std::vector<SE2d>& states, const std::vector<std::pair<double, double>>& measurement,
+                                                   const LocalSearchParams& search) {
+    static_assert(sizeof(std::pair<double, double>) == 2 * sizeof(double), "points are handed over as (x, y) doubles");
+    const mcl_local_search_params p{search.half_steps_xy, search.half_steps_theta, search.step_xy, search.step_theta};
+    std::vector<mcl_local_hit> raw(std::max<std::size_t>(states.size(), 1));
+    check(mcl_local_search(ctx_, states.empty() ? nullptr : states.data()->data(), states.size(), measurement.empty() ? nullptr : &measurement.data()->first,
+                           measurement.size(), &p, raw.data(), &last_local_search_info_));
+    return local_hits(raw, states.size());
+  }
+  [[nodiscard]] std::vector<LocalHit> local_search(const std::vector<SE2d>& states, const std::vector<LandmarkPositionDetection>& detections,
+                                                   const LocalSearchParams& search) {
+    std::vector<double> xyz;
+    std::vector<std::uint32_t> categories;
+    flatten(detections, [](const LandmarkPositionDetection& d) -> const std::array<double, 3>& { return d.detection_position_in_robot; }, xyz,
+            categories);
+    const mcl_local_search_params p{search.half_steps_xy, search.half_steps_theta, search.step_xy, search.step_theta};
+    std::vector<mcl_local_hit> raw(std::max<std::size_t>(states.size(), 1));
+    check(mcl_local_search_landmarks(ctx_, states.empty() ? nullptr : states.data()->data(), states.size(), xyz.data(), categories.data(), categories.size(),
+                                     &p, raw.data(), &last_local_search_info_));
+    return local_hits(raw, states.size());
+  }
+  [[nodiscard]] std::vector<LocalHit> local_search(const std::vector<SE2d>& states, const std::vector<LandmarkBearingDetection>& detections,
+                                                   const LocalSearchParams& search) {
+    std::vector<double> xyz;
+    std::vector<std::uint32_t> categories;
+    flatten(detections, [](const LandmarkBearingDetection& d) -> const std::array<double, 3>& { return d.detection_bearing_in_sensor; }, xyz,
+            categories);
+    const mcl_local_search_params p{search.half_steps_xy, search.half_steps_theta, search.step_xy, search.step_theta};
+    std::vector<mcl_local_hit> raw(std::max<std::size_t>(states.size(), 1));
+    check(mcl_local_search_bearings(ctx_, states.empty() ? nullptr : states.data()->data(), states.size(), xyz.data(), categories.data(), categories.size(),
+                                    &p, raw.data(), &last_local_search_info_));
+    return local_hits(raw, states.size());
+  }
+  /// local_search with the default parameters, whatever the measurement's type.
+  template <class Measurement>
+  [[nodiscard]] std::vector<LocalHit> local_search(const std::vector<SE2d>& states, const Measurement& measurement) {
+    return local_search(states, measurement, LocalSearchParams{});
+  }
+  /// The counts and the step of the last local_search (mcl_local_search_info).
+  [[nodiscard]] const mcl_local_search_info& last_local_search_info() const { return last_local_search_info_; }
+  /// relocalize with refinement: the kept hits of global_search are refined by local_search and ordered by their refined score (stable
+  /// for ties); the filter is initialised at the best one's mean_pose with its cov + diag(step_xy^2, step_xy^2, step_theta^2) / 12 - the
+  /// variance of a uniform error inside one lattice step, which keeps the matrix positive definite on a plateau or with no steps at all.
+  /// Where the best hit's moments are not valid, `covariance` is used (and must be given).  Returns the refined hits.
+  std::vector<LocalHit> relocalize(const std::vector<std::pair<double, double>>& measurement, const SearchParams& search, const LocalSearchParams& refine,
+                                   const Matrix3d* covariance = nullptr) {
+    const std::vector<SearchHit> hits = global_search(measurement, search);
+    if (hits.empty()) return {};
+    std::vector<SE2d> seeds;
+    for (const SearchHit& h : hits) seeds.push_back(h.pose);
+    std::vector<LocalHit> refined = local_search(seeds, measurement, refine);
+    std::stable_sort(refined.begin(), refined.end(), [](const LocalHit& a, const LocalHit& b) { return a.score > b.score; });
+    const LocalHit& best = refined.front();
+    if (best.moments_valid) {
+      const double sx = last_local_search_info_.step_xy, st = refine.step_theta;
+      Matrix3d cov = best.cov;
+      cov[0] += sx * sx / 12.0, cov[4] += sx * sx / 12.0, cov[8] += st * st / 12.0;
+      initialize(best.mean_pose, cov);
+    } else {
+      if (!covariance) throw std::invalid_argument("relocalize: the best hit's moments are not valid and no covariance was given");
+      initialize(best.mean_pose, *covariance);
+    }
+    return refined;
+  }
+
   /// Extension: states | views::likelihoods(sensor_model(measurement)) (views/likelihoods.hpp:44-59) on the device - for each of
   /// `states`, in their order, the factor by which a reweight with `measurement` would multiply the weight of a particle there
   /// (mcl_likelihoods).  The filter is untouched: particles, weights, random stream, policies and counters stay as they are.
@@ -1203,8 +1287,23 @@ class Amcl {
   void check(mcl_status st) const {
     if (st != MCL_OK) throw std::runtime_error(std::string("beluga_amd::Amcl: ") + mcl_last_error(ctx_));
   }
+  static std::vector<LocalHit> local_hits(const std::vector<mcl_local_hit>& raw, std::size_t n) {
+    std::vector<LocalHit> hits(n);
+    for (std::size_t i = 0; i < n; ++i) {
+      const mcl_local_hit& r = raw[i];
+      LocalHit& h = hits[i];
+      h.pose.c = r.pose[0], h.pose.s = r.pose[1], h.pose.x = r.pose[2], h.pose.y = r.pose[3];
+      h.mean_pose.c = r.mean_pose[0], h.mean_pose.s = r.mean_pose[1], h.mean_pose.x = r.mean_pose[2], h.mean_pose.y = r.mean_pose[3];
+      h.score = r.score, h.seed_score = r.seed_score, h.di = r.di, h.dj = r.dj, h.dk = r.dk, h.plateau = r.plateau;
+      std::copy(r.cov, r.cov + 9, h.cov.begin());
+      std::copy(r.sums, r.sums + 10, h.sums.begin());
+      h.moments_valid = r.moments_valid != 0;
+    }
+    return hits;
+  }
   mcl_ctx* ctx_{nullptr};
   mcl_search_info last_search_info_{};
+  mcl_local_search_info last_local_search_info_{};
   struct PendingShape {
     std::uint32_t width{0}, height{0};
     double resolution{0.0};

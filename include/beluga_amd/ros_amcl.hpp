@@ -197,6 +197,31 @@ class Amcl {
     return filter_.global_search(measurement, search);
   }
 
+  /// Extension: the local pose search (beluga_amd::Amcl::local_search) over the scan types update() takes, projected exactly as
+  /// update() projects them: per state the best pose of a lattice about it and the lattice's score-weighted mean and covariance, the
+  /// filter untouched.
+  using LocalSearchParams = beluga_amd::Amcl::LocalSearchParams;
+  using LocalHit = beluga_amd::Amcl::LocalHit;
+  template <class LaserScan, class = decltype(std::declval<const LaserScan&>().points_in_cartesian_coordinates())>
+  [[nodiscard]] std::vector<LocalHit> local_search(const std::vector<SE2d>& states, const LaserScan& laser_scan,
+                                                   const LocalSearchParams& search = LocalSearchParams()) {
+    return filter_.local_search(states, projected<false>(laser_scan.points_in_cartesian_coordinates(), se3_data(laser_scan.origin())), search);
+  }
+  template <class PointCloud, class = decltype(std::declval<const PointCloud&>().points()), class = void>
+  [[nodiscard]] std::vector<LocalHit> local_search(const std::vector<SE2d>& states, const PointCloud& point_cloud,
+                                                   const LocalSearchParams& search = LocalSearchParams()) {
+    return filter_.local_search(states, projected<true>(point_cloud.points(), se3_data(point_cloud.origin())), search);
+  }
+  [[nodiscard]] std::vector<LocalHit> local_search(const std::vector<SE2d>& states, const std::vector<std::pair<double, double>>& measurement,
+                                                   const LocalSearchParams& search = LocalSearchParams()) {
+    return filter_.local_search(states, measurement, search);
+  }
+  /// relocalize with refinement (beluga_amd::Amcl::relocalize) over a laser scan.
+  template <class LaserScan, class = decltype(std::declval<const LaserScan&>().points_in_cartesian_coordinates())>
+  std::vector<LocalHit> relocalize(const LaserScan& laser_scan, const SearchParams& search, const LocalSearchParams& refine) {
+    return filter_.relocalize(projected<false>(laser_scan.points_in_cartesian_coordinates(), se3_data(laser_scan.origin())), search, refine);
+  }
+
   /// Extension: beam skipping with Nav2's parameters (beluga_amd::Amcl::set_beam_skip; likelihood-field sensor models only).
   void set_beam_skip(const BeamSkipParams& p) {
     filter_.set_beam_skip(p.do_beamskip, p.beam_skip_distance, p.beam_skip_threshold, p.beam_skip_error_threshold);

@@ -516,6 +516,90 @@ mcl_status mcl_global_search_candidates(mcl_ctx* ctx, const mcl_search_params* p
 mcl_status mcl_search_suppress(const mcl_search_hit* pool, uint64_t n, uint32_t grid_width, const mcl_search_params* params, uint32_t* kept_index,
                                uint64_t* kept);
 
+/* ---- Local pose search: a lattice of offsets about each seed pose, the best of it and the response's moments ---------------------------
+ * The correlative scan matcher: refine a hit of mcl_global_search below its quantisation, "look around the current estimate for a
+ * better pose", and learn how well the measurement pins the pose there (tight across a corridor, loose along it).  It needs no map
+ * cells, only seeds: every sensor model has it.  tests/local_search_reference.py restates all of this.
+ *
+ * Parameters: half_steps_xy (Kx) <= 32, half_steps_theta (Kt) <= 64, both steps finite, step_theta > 0, step_xy >= 0, Kt * step_theta
+ *   < pi.  step_xy == 0 stands for a quarter of the map's cell size - the grid's resolution on grid contexts, the NDT map's on NDT
+ *   contexts; a landmark or bearing context has no cell size and refuses it.
+ * Lattice: a seed has L = (2 Kx + 1)^2 (2 Kt + 1) candidates (at most 545 025), the integer triples (i, j, k), |i|, |j| <= Kx, |k| <= Kt;
+ *   the local id of one is ((k + Kt) (2 Kx + 1) + (j + Kx)) (2 Kx + 1) + (i + Kx).
+ * Position: x = seed.x + off[i], y = seed.y + off[j] in world axes; off[i] = double(i) * step_xy is computed once per call on the
+ *   host and uploaded: the device does one addition per coordinate.
+ * Rotation: from a table of n (2 Kt + 1) entries computed on the host and uploaded; the entry for k is the seed's rotation times
+ *   exp(double(k) * step_theta) by SO(2)'s product as the library forms it everywhere (renormalised, then normalised with hypot); the
+ *   entry for k == 0 is the seed's rotation as given.  Every candidate's bits are the host's, and the centre candidate is the seed bit
+ *   for bit.
+ * Score: score(seed, id) is what mcl_likelihoods* returns for that pose and that measurement, bit for bit (the same kernels, as the
+ *   global search's; a beam context with a range table walks all the same).
+ * Best: the candidate that comes first by (score descending, i*i + j*j ascending, |k| ascending, id ascending) - integers only behind
+ *   the score, whose order is that of its bits' order-preserving image (a NaN, which finite poses cannot give, is the lowest).  A
+ *   likelihood field is constant over a cell, so plateaus of equal scores are the normal case: the rule pulls towards the seed, not
+ *   towards a corner.  plateau = the candidates whose score equals the best's bit for bit.
+ * Moments: ten f64 sums per seed with w = score, in integer offset coordinates: S0 = sum w; sum w i, sum w j, sum w k; sum w ii, w ij,
+ *   w ik, w jj, w jk, w kk (sums[0 .. 9] in this order); a term is the score times the integer product, rounded once.  The order of the summation is fixed by L and the launch geometry alone: the
+ *   same call gives the same bits, whatever option search_chunk is.
+ * Finish (on the host; mcl_local_search_finish is this alone): m_a = S_a / S0; mean_dx = step_xy * m_i, mean_dy = step_xy * m_j,
+ *   mean_dtheta = step_theta * m_k; cov[a][b] = ((S_ab / S0 - m_a * m_b) * step_a) * step_b, symmetric, (x, y, theta) order; mean_pose =
+ *   (seed.x + mean_dx, seed.y + mean_dy, seed rotation times exp(mean_dtheta)).  moments_valid = 0 where S0 is 0 or not finite: the
+ *   mean is then the seed as given and the covariance zero.
+ * pose of a hit: formed on the host from the id by the expressions above, as the global search forms its hits.
+ *
+ * The filter is untouched, by mcl_likelihoods' own contract: the call has buffers of its own, runs on the context's stream and reads
+ * the map the context reads now.  Allowed on batch members, on contexts attached to a shared map, and per rank on a sharded context.
+ * Device memory: a pass takes max(1, search_chunk / L) whole seeds, its buffers hold max(search_chunk, L) candidates; a seed is never
+ * split and the result does not depend on search_chunk.  Per seed the call keeps its table entries and 14 words of results.  One host
+ * synchronisation, at the end of the call.
+ *
+ * Checks, all before the device is used; on any error nothing is written: MCL_ERR_NOT_READY without a map; MCL_ERR_INVALID_ARGUMENT
+ * for a null argument, a seed value that is not finite, parameters outside the limits above and whatever mcl_likelihoods* refuses of
+ * the measurement; MCL_ERR_UNSUPPORTED for the entry of another sensor model, as mcl_likelihoods*.  n == 0 is MCL_OK. */
+typedef struct mcl_local_search_params {
+  uint32_t half_steps_xy, half_steps_theta;
+  double step_xy, step_theta;
+} mcl_local_search_params;
+typedef struct mcl_local_hit {
+  double pose[4];      /* the best candidate: cos, sin, x, y */
+  double score;        /* its score */
+  double seed_score;   /* the centre candidate's: mcl_likelihoods at the seed */
+  int32_t di, dj, dk;  /* its integer offsets */
+  int32_t moments_valid;
+  uint64_t plateau;    /* candidates whose score equals `score` bit for bit */
+  double mean_pose[4];
+  double cov[9];       /* row-major, (x, y, theta) */
+  double sums[10];
+} mcl_local_hit;
+typedef struct mcl_local_search_info {
+  uint64_t candidates_per_seed; /* L */
+  uint64_t seeds_per_pass;      /* max(1, search_chunk / L) */
+  uint32_t passes;              /* ceil(n / seeds_per_pass) */
+  uint32_t launches;            /* kernel launches: per pass one generation, one scoring (mcl_likelihoods_device's kernel), one reduction */
+  double step_xy;               /* the step used: the parameter, or a quarter of the map's cell size */
+} mcl_local_search_info;
+/* half_steps_xy 4, half_steps_theta 5, step_xy 0 (a quarter of a cell), step_theta pi / 360: plus or minus one cell and plus or minus
+ * 2.5 degrees, half of the global search's default quantisation in each axis.  Choices of a reasonable start, not measurements. */
+void mcl_default_local_search_params(mcl_local_search_params* params);
+/* seeds: n poses (cos, sin, x, y); hits: room for n; params NULL: the defaults; info may be NULL.  Likelihood-field,
+ * likelihood-field-prob, beam and NDT contexts. */
+mcl_status mcl_local_search(mcl_ctx* ctx, const double* seeds, uint64_t n, const double* points_xy, uint64_t num_points,
+                            const mcl_local_search_params* params, mcl_local_hit* hits, mcl_local_search_info* info);
+/* The same on landmark and bearing contexts, with the measurement of mcl_likelihoods_landmarks / mcl_likelihoods_bearings. */
+mcl_status mcl_local_search_landmarks(mcl_ctx* ctx, const double* seeds, uint64_t n, const double* positions_xyz, const uint32_t* categories,
+                                      uint64_t k, const mcl_local_search_params* params, mcl_local_hit* hits, mcl_local_search_info* info);
+mcl_status mcl_local_search_bearings(mcl_ctx* ctx, const double* seeds, uint64_t n, const double* bearings_xyz, const uint32_t* categories,
+                                     uint64_t k, const mcl_local_search_params* params, mcl_local_hit* hits, mcl_local_search_info* info);
+/* The lattice of one seed as the device makes it, in id order: the candidates first .. first + count - 1 (fewer where the lattice
+ * ends) into poses_out (4 doubles each; host memory; may be NULL with count == 0); *total = L.  Every sensor model. */
+mcl_status mcl_local_search_candidates(mcl_ctx* ctx, const double seed[4], const mcl_local_search_params* params, uint64_t first, uint64_t count,
+                                       double* poses_out, uint64_t* total);
+/* The moments' finish alone, on the host: needs no device and no context.  params NULL: the defaults; its step_xy is used as given (0
+ * is a step of no length, not a quarter of a cell: there is no map here).  MCL_ERR_INVALID_ARGUMENT: a null argument, a seed value that
+ * is not finite, parameters mcl_local_search refuses. */
+mcl_status mcl_local_search_finish(const double sums[10], const mcl_local_search_params* params, const double seed[4], double mean_pose[4],
+                                   double cov[9], int32_t* moments_valid);
+
 /* ---- Ray casting as a function: the range the map predicts along a bearing from a pose (Ray2d::cast, algorithm/raycasting.hpp:97-107) ----
  * An expected scan to draw over the measured one, per-beam residuals against a stale map or a moving obstacle, a synthetic scan for a
  * simulated robot, a range table.  The walk is the beam model's own (the kernels mcl_reweight runs on a beam context), opened to
